@@ -30,6 +30,14 @@ Extra objects: "roofline" (dominant kernel: algorithmic bytes of SURVEY 8d / HIP
 launches, vs the 8 TB/s HBM peak; every kernel in "kernels", the whole frame in "stage_frac") and "cpu_baseline" (the scalar
 C checker, oracle/, running the same sequence over a bounded prefix of the same arrays on the host; a reported baseline,
 not the target).
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the outputs (--dump-outputs) and the result
+line.  Everything else -- the checked frame and bit_match, the CPU baseline, the scheduling / exchange / assignment variants, the
+kernel profile and rooflines, and the nested runs (tris124, configs1, configs4, real_geometry, configs0) -- runs with --full.
+
+  --dump-outputs DIR: after the timed steps, what the last frame computed as DIR/<name>.npy (float64, float32 for the pyramid,
+  under 64 MB in all; rank 0's shard when N > 1).  Lists are sorted, as the checks compare them; a list longer than
+  DUMP_SAMPLE entries is cut to a fixed seeded sample of positions, so two builds with the same arguments compare entry by entry.
 """
 import argparse
 import ctypes as C
@@ -115,6 +123,9 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=6.0)
     ap.add_argument("--cpu-prefix", type=int, default=1000, help="config3 cpu_baseline / bit_match sample: the first this-many mesh instances")
     ap.add_argument("--entities", type=int, default=1000, help="config1: entity count")
+    ap.add_argument("--full", action="store_true", help="config3: also run the checks, CPU baseline, variants, kernel profile, rooflines and nested runs (a plain run "
+                                                        "times the main line only; the --no-* options above trim a --full run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="config3: write the last timed frame's outputs to DIR/<name>.npy (see the module docstring)")
     return ap.parse_args()
 
 
@@ -388,6 +399,42 @@ def hiz_algorithmic_bytes(w: int, h: int, levels: int) -> int:
     return 4 * w * h + written + (4 * max(1, w >> 6) * max(1, h >> 6) if levels > 7 else 0)
 
 
+DUMP_SAMPLE = 1 << 20  # entries kept of a longer list: worst case (pairs, every list sampled) 3 x 8.4 + 16.8 MB + the 4.2 MB pyramid sample
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(out_dir, counters, visible, ne, index_words, pairs, mask, hiz_data):
+    """--dump-outputs: the outputs of the last frame as DIR/<name>.npy.  visible = early list [0, ne) then late list; index_words = the
+    late call's index list (each call's list starts at 0); counters = (total, early, late, late index_count).  Lists are sorted (the
+    unordered forms allocate slots by atomics), then cut to a fixed seeded sample of positions when longer than DUMP_SAMPLE."""
+    import numpy as np
+
+    def sample(t, seed):
+        if t.shape[0] <= DUMP_SAMPLE:
+            return t
+        pos = torch.randint(0, t.shape[0], (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(seed)).sort()[0]
+        return t[pos.to(t.device)]
+
+    keys = index_words.to(torch.int64) & 0xFFFFFFFF
+    if pairs:  # {u32 id, u32 corner}: sorted by (id, corner), written as two columns (a packed key would pass 2^53)
+        keys = (keys.view(-1, 2)[:, 0] << 32) | keys.view(-1, 2)[:, 1]
+    keys = sample(torch.sort(keys)[0], 3)
+    arrays = {
+        "counters": torch.tensor(counters, dtype=torch.float64),
+        "visible_early": sample(torch.sort(visible[:ne])[0], 1).double(),
+        "visible_late": sample(torch.sort(visible[ne:])[0], 2).double(),
+        "indices_late": (torch.stack([keys >> 32, keys & 0xFFFFFFFF], dim=1) if pairs else keys).double(),
+        "visibility_mask": sample(mask, 4).double(),
+        "hiz_sample": sample(hiz_data, 5).float(),
+    }
+    arrays = {k: v.cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs: {total} bytes"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def bench_config3(args, e):
     r, dev, stream, rank, world, dist = e.r, e.dev, e.stream, e.rank, e.world, e.dist
     lib, ctxp, sp = r._lib, r._ctx, C.c_void_p(stream.cuda_stream)
@@ -616,14 +663,15 @@ def bench_config3(args, e):
                 snap[tag]["visible_prefix"] = vis[:nv].cpu()
                 snap[tag]["indices_prefix"] = frame.reordered_indices_buffer[:ni * W].cpu()
 
-    with torch.cuda.stream(stream):
-        run_frame(record)
-    torch.cuda.synchronize()
-    mask_after = mask[: (min(args.cpu_prefix, M) * K + 31) // 32].cpu() if rank == 0 else None
-    counts = {"total": snap["late"]["total"], "early": snap["late"]["early"], "late": snap["late"]["late"],
-              "early_index_count": snap["early"]["index_count"], "late_index_count": snap["late"]["index_count"]}
-    v_early, v_late = counts["early"], counts["late"]
-    t_early, t_late = counts["early_index_count"] // 3, counts["late_index_count"] // 3
+    if args.full:
+        with torch.cuda.stream(stream):
+            run_frame(record)
+        torch.cuda.synchronize()
+        mask_after = mask[: (min(args.cpu_prefix, M) * K + 31) // 32].cpu() if rank == 0 else None
+        counts = {"total": snap["late"]["total"], "early": snap["late"]["early"], "late": snap["late"]["late"],
+                  "early_index_count": snap["early"]["index_count"], "late_index_count": snap["late"]["index_count"]}
+        v_early, v_late = counts["early"], counts["late"]
+        t_early, t_late = counts["early_index_count"] // 3, counts["late_index_count"] // 3
 
     def outputs_checksum():
         """Every output of the last frame folded into a few integers (device-side sums): what a scheduling variant must reproduce.
@@ -659,6 +707,47 @@ def bench_config3(args, e):
     frames = args.steps * inner
     ms_per_frame = elapsed * 1e3 / frames
     value = world_meshlets * frames / elapsed
+    main_async, main_ahead, main_share, main_unord = use_async[0], use_overlap[0], use_share[0], use_unord[0]
+
+    def base_line(counts, exchange_ab=None):
+        """The result line's contract keys and config; a --full run adds its checks and measurements."""
+        n_tri = None if counts["early_index_count"] is None else counts["early_index_count"] // 3 + counts["late_index_count"] // 3
+        return {
+            "metric": "meshlets/s culled", "value": round(value, 1), "unit": "meshlets/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(elapsed * 1e3 / args.steps, 6), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {
+                "workload": ("configs[2]: 10M meshlets + 4096^2 prior-frame HiZ (13 mips, built from an 8192^2 depth): HiZ build + early/late occlusion cull + "
+                             "per-triangle cull + compaction into the indirect-draw buffers (" + ("unordered_output = 1: slots allocated by atomic_add as in the reference, lists "
+                             "compared sorted" if main_unord else "ascending lists") + ")" if world == 1 else
+                             f"configs[3]: {world_meshlets} meshlets sharded {world} ways by " + ("contiguous range" if not (shard_desc and shard_desc["shard_block_instances"] > 0) else shard_desc["assignment"]) + (" of ONE scene" if shard_desc else " (an independent scene per rank)") + " (the configs[2] pipeline per rank): rank 0 builds the "
+                             "4096^2 pyramid and broadcasts it over RCCL/xGMI, per-rank counters all-gathered every frame, shard-local ids and outputs"),
+                "meshlets_per_gpu": n_meshlets, "mesh_instances": M, "meshlets_per_mesh": K, "tris_per_meshlet": args.tris, "verts_per_meshlet": 64,
+                "index_form": ("pairs {u32 id, u32 corner}, 24 B per triangle (wide_triangle_index = 2)" if pairs else "(id << 9) | corner (wide_triangle_index = 1)" if wide else "(id << 8) | corner (visbuffer.slang:9-14)"),
+                "inner_reps": inner, "frames_timed": frames, "ms_per_frame": round(ms_per_frame, 6), "small_triangle_cull": bool(args.small_triangle_cull),
+                "visible_fraction": round((counts["early"] + counts["late"]) / n_meshlets, 4),
+                "triangles_per_visible_meshlet": None if n_tri is None else round(n_tri / max(1, counts["early"] + counts["late"]), 2),
+                "sharding": "single GPU" if world == 1 else {"ranks": world, "rccl_ranks": 0 if e.debug_backend else world, "rccl_ranks_seen": 0 if e.debug_backend else ranks_seen, "debug_backend_not_a_measurement": e.debug_backend or None, "backend": "oxc_comm_* (RCCL via the C ABI)" if use_native[0] else (f"torch.distributed {e.debug_backend} (debug)" if e.debug_backend else "torch.distributed nccl (RCCL)"),
+                                                             "hiz_exchange": (f"levels >= {k_top} broadcast, lower levels built by every rank from its own depth copy" if xmode["top"] else "whole pyramid broadcast from rank 0"),
+                                                             "hiz_broadcast_bytes_per_frame": hiz_wire_bytes, "hiz_one_frame_ahead_on_second_stream": use_overlap[0],
+                                                             "counters_all_gather_bytes_per_rank": 16, "per_rank_ms_per_frame": per_rank_ms_per_frame,
+                                                             "per_rank_visible": per_rank_visible, "scene": shard_desc or {"one_scene": False, "note": "an independent scene per rank (seed + rank): no visibility skew between ranks by construction; --one-scene shards one scene"},
+                                                             "hiz_exchange_ab": exchange_ab},
+                "async_triangles": bool(use_async[0]), "share_pass_tests": bool(use_share[0]), "unordered_output": main_unord,
+            },
+        }
+
+    # ---- the last timed frame's outputs (--dump-outputs), before anything below runs another frame ----
+    torch.cuda.synchronize()
+    last_b = (frame_no[0] - 1) % len(hiz)
+    last = L.Counters()
+    check(lib.oxc_read_counters(ctxp, C.byref(cctx[last_b]), C.byref(last), sp))
+    ne, nl = last.early_visible_meshlet_instances, last.late_visible_meshlet_instances
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, (last.total_visible_meshlet_instances, ne, nl, last.draw_index_count), frame.visible_meshlet_instances_indices_buffer[:ne + nl], ne,
+                     frame.reordered_indices_buffer[:last.draw_index_count * W], pairs, mask, hiz[last_b].data)
+    if not args.full:
+        r_hiz.close()
+        return base_line({"total": last.total_visible_meshlet_instances, "early": ne, "late": nl, "early_index_count": None, "late_index_count": last.draw_index_count})
     sum_main = outputs_checksum()
 
     # ---- the same frames under other schedulings, short runs: (a) async_triangles flipped -- the triangle stage of a call on the context's
@@ -676,7 +765,6 @@ def bench_config3(args, e):
                 "ms_per_frame": round(el * 1e3 / (ab_steps * inner), 6),
                 "value": round(world_meshlets * ab_steps * inner / el, 1), "frames_timed": ab_steps * inner, "outputs_match_main_line": outputs_checksum() == sum_main}
 
-    main_async, main_ahead, main_share, main_unord = use_async[0], use_overlap[0], use_share[0], use_unord[0]
     variants = []
     if not args.no_scheduling_ab:
         for other in (u for u in (0, 1) if u != main_unord):  # the list layouts of include/oxcull.h (compared as sorted sets)
@@ -986,31 +1074,12 @@ def bench_config3(args, e):
                             "matches_single_thread": mt_ok, "single_thread_value": round(single, 1), "single_thread_sequence_s_per_run": round(dt, 3),
                             "hiz_build_s": round(t_hiz_cpu, 3), "sequence_s_per_run": round(dt_mt, 4)}
 
-    line = {
-        "metric": "meshlets/s culled", "value": round(value, 1), "unit": "meshlets/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(elapsed * 1e3 / args.steps, 6), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {
-            "workload": ("configs[2]: 10M meshlets + 4096^2 prior-frame HiZ (13 mips, built from an 8192^2 depth): HiZ build + early/late occlusion cull + "
-                         "per-triangle cull + compaction into the indirect-draw buffers (" + ("unordered_output = 1: slots allocated by atomic_add as in the reference, lists "
-                         "compared sorted" if main_unord else "ascending lists") + ")" if world == 1 else
-                         f"configs[3]: {world_meshlets} meshlets sharded {world} ways by " + ("contiguous range" if not (shard_desc and shard_desc["shard_block_instances"] > 0) else shard_desc["assignment"]) + (" of ONE scene" if shard_desc else " (an independent scene per rank)") + " (the configs[2] pipeline per rank): rank 0 builds the "
-                         "4096^2 pyramid and broadcasts it over RCCL/xGMI, per-rank counters all-gathered every frame, shard-local ids and outputs"),
-            "meshlets_per_gpu": n_meshlets, "mesh_instances": M, "meshlets_per_mesh": K, "tris_per_meshlet": args.tris, "verts_per_meshlet": 64,
-            "index_form": ("pairs {u32 id, u32 corner}, 24 B per triangle (wide_triangle_index = 2)" if pairs else "(id << 9) | corner (wide_triangle_index = 1)" if wide else "(id << 8) | corner (visbuffer.slang:9-14)"),
-            "inner_reps": inner, "frames_timed": frames, "ms_per_frame": round(ms_per_frame, 6), "small_triangle_cull": bool(args.small_triangle_cull),
-            "visible_fraction": round((v_early + v_late) / n_meshlets, 4), "triangles_per_visible_meshlet": round((t_early + t_late) / max(1, v_early + v_late), 2),
-            "sharding": "single GPU" if world == 1 else {"ranks": world, "rccl_ranks": 0 if e.debug_backend else world, "rccl_ranks_seen": 0 if e.debug_backend else ranks_seen, "debug_backend_not_a_measurement": e.debug_backend or None, "backend": "oxc_comm_* (RCCL via the C ABI)" if use_native[0] else (f"torch.distributed {e.debug_backend} (debug)" if e.debug_backend else "torch.distributed nccl (RCCL)"),
-                                                         "hiz_exchange": (f"levels >= {k_top} broadcast, lower levels built by every rank from its own depth copy" if xmode["top"] else "whole pyramid broadcast from rank 0"),
-                                                         "hiz_broadcast_bytes_per_frame": hiz_wire_bytes, "hiz_one_frame_ahead_on_second_stream": use_overlap[0],
-                                                         "counters_all_gather_bytes_per_rank": 16, "per_rank_ms_per_frame": per_rank_ms_per_frame,
-                                                         "per_rank_visible": per_rank_visible, "scene": shard_desc or {"one_scene": False, "note": "an independent scene per rank (seed + rank): no visibility skew between ranks by construction; --one-scene shards one scene"},
-                                                         "hiz_exchange_ab": exchange_ab},
-            "async_triangles": bool(use_async[0]), "share_pass_tests": bool(use_share[0]), "unordered_output": main_unord,
-        },
+    line = base_line(counts, exchange_ab)
+    line.update({
         "bit_match": bit_match, "bit_match_detail": bit_detail if rank == 0 else None, "hiz_bit_match": hiz_match, "bit_match_sample": f"first {min(args.cpu_prefix, M) * K} meshlet instances: visible lists, packed triangle indices, mask words, both passes",
         "unpinned_gap": unpinned, "counts": counts, "kernels": kernels, "stage": stage, "roofline": roofline, "cpu_baseline": cpu_baseline,
         "scheduling_ab": sched_ab,
-    }
+    })
     # ---- N > 1: the same frames with BOTH exchanges through the other RCCL path -- the C ABI's own entry points (oxc_exchange_counts,
     # oxc_broadcast_hiz[_levels]: SURVEY 8b lists them in the boundary) when the main line ran on torch.distributed, and the reverse with
     # --native-comm -- a short run, outputs check-summed against the main line.  These entry points had never run with more than one rank
@@ -1399,6 +1468,8 @@ def line_summary(line: dict) -> dict:
 
 def main():
     args = parse()
+    if args.dump_outputs and args.workload != "config3":
+        raise SystemExit(f"bench.py: --dump-outputs writes the outputs of the default workload (config3), not of --workload {args.workload}")
     if args.workload == "config1":
         return bench_config1(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1432,14 +1503,14 @@ def main():
 
         stage_note("configs[2] main line")
         line = bench_config3(args, e)
-        if e.world > 1 and not args.independent_scenes and not args.no_assignment_ab:
+        if args.full and e.world > 1 and not args.independent_scenes and not args.no_assignment_ab:
             # the OTHER assignment of the same scene, a short run: contiguous instance ranges (the north star's wording; depth slabs of this
             # synthetic scene, i.e. skewed) beside the interleaved blocks of the main line, or the reverse -- per_rank_visible tells them apart
             import copy
 
             a3 = copy.copy(args)
             a3.shard_block = 0 if args.shard_block > 0 else 64
-            a3.steps, a3.warmup = max(2, args.steps // 4), 1
+            a3.steps, a3.warmup, a3.dump_outputs = max(2, args.steps // 4), 1, None
             a3.no_scheduling_ab, a3.no_cpu_baseline, a3.no_exchange_ab, a3.no_native_comm_ab, a3.cpu_prefix = True, True, True, True, min(args.cpu_prefix, 100)
             stage_note("assignment_ab")
             t = bench_config3(a3, e)
@@ -1447,14 +1518,14 @@ def main():
                 sh = t["config"]["sharding"]
                 line["assignment_ab"] = {"assignment": sh["scene"]["assignment"], "value": t["value"], "ms_per_frame": t["config"]["ms_per_frame"], "frames_timed": t["config"]["frames_timed"],
                                          "per_rank_visible": sh["per_rank_visible"], "per_rank_ms_per_frame": sh["per_rank_ms_per_frame"], "bit_match": t["bit_match"]}
-        if e.world == 1 and not args.no_tris124 and args.tris == 64 and not args.meshlets:
+        if args.full and e.world == 1 and not args.no_tris124 and args.tris == 64 and not args.meshlets:
             # BASELINE's stated meshlet shape -- 64 vertices / 124 triangles -- does not fit the reference's 24 + 8 bit packed index: the same
             # frame at the literal 10 M meshlets with the pair form (wide_triangle_index = 2: {u32 id, u32 corner}, 24 B per emitted triangle, two
             # 64-lane triangle passes), a short run.  (`--tris 124 --index-form wide` is round 5's (id << 9) | corner form: at most 2^23 ids, 8 M meshlets.)
             import copy
 
             a2 = copy.copy(args)
-            a2.tris, a2.steps, a2.warmup, a2.index_form = 124, max(4, args.steps // 4), 1, "pairs"
+            a2.tris, a2.steps, a2.warmup, a2.index_form, a2.dump_outputs = 124, max(4, args.steps // 4), 1, "pairs", None
             a2.no_scheduling_ab, a2.no_cpu_baseline, a2.cpu_prefix = True, True, min(args.cpu_prefix, 250)
             stage_note("tris124")
             t = bench_config3(a2, e)
@@ -1465,22 +1536,22 @@ def main():
                                "visible_fraction": t["config"]["visible_fraction"], "triangles_per_visible_meshlet": t["config"]["triangles_per_visible_meshlet"],
                                "bit_match": t["bit_match"], "bit_match_detail": t["bit_match_detail"], "bit_match_sample": t["bit_match_sample"], "counts": t["counts"], "roofline": t["roofline"], "stage": t["stage"],
                                "kernels": {k: v for k, v in t["kernels"].items() if k.startswith("cull_triangles") or k.startswith("_")}}
-        if e.world == 1 and not args.no_configs1:
+        if args.full and e.world == 1 and not args.no_configs1:
             stage_note("configs1")
             line["configs1"] = bench_config2(args, e, steps=8, warmup=1, with_cpu=not args.no_cpu_baseline)
-        if e.world == 1 and not args.no_configs4:
+        if args.full and e.world == 1 and not args.no_configs4:
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import bench_aux
 
             stage_note("configs4")
             line["configs4"] = bench_aux.bench_config5(args, e.r, e.dev, e.stream, e.rank, e.world, e.dist, nested=True)
-        if e.world == 1 and not args.no_real_geometry:
+        if args.full and e.world == 1 and not args.no_real_geometry:
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import bench_aux
 
             stage_note("real_geometry")
             line["real_geometry"] = bench_aux.bench_real_geometry(args, e.r, e.dev, e.stream, e.rank)
-        if e.world == 1 and not args.no_configs0:
+        if args.full and e.world == 1 and not args.no_configs0:
             stage_note("configs0")
             line["configs0"] = measure_config1(args, min(args.cpu_seconds, 2.0))  # BASELINE configs[0]: CPU only by definition, milliseconds per update
         if e.rank == 0:

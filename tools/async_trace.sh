@@ -1,15 +1,16 @@
 #!/bin/bash
 # tools/async_trace.sh <tag> -- on the GPU box: rocprofv3 --kernel-trace of bench.py --async-triangles (triangle stages on the context's own
-# stream), condensed to gpurun_out/profiles_out/<tag>_async_trace.json: per kernel its time, and how much of it another kernel of the
+# stream), condensed to $OUT/profiles_out/<tag>_async_trace.json (OUT: default bench_out): per kernel its time, and how much of it another kernel of the
 # library was running at the same time (the evidence that the two stages do run side by side -- and what that is worth).
 set -u
 TAG=${1:-r03}
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
-mkdir -p "$ROOT/gpurun_out/raw/async" "$ROOT/gpurun_out/profiles_out"
+OUT=${OUT:-bench_out}
+mkdir -p "$ROOT/$OUT/raw/async" "$ROOT/$OUT/profiles_out"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d "$ROOT/gpurun_out/raw/async" -o a -- python $ROOT/bench.py --async-triangles --no-cpu-baseline --no-configs1 --no-configs4 --no-real-geometry --steps 2 --warmup 1 --inner-reps 16 > "$ROOT/gpurun_out/raw/async/bench.json" 2> "$ROOT/gpurun_out/raw/async/err.log"
+rocprofv3 --kernel-trace --output-format csv -d "$ROOT/$OUT/raw/async" -o a -- python $ROOT/bench.py --async-triangles --no-cpu-baseline --no-configs1 --no-configs4 --no-real-geometry --steps 2 --warmup 1 --inner-reps 16 --full > "$ROOT/$OUT/raw/async/bench.json" 2> "$ROOT/$OUT/raw/async/err.log"
 cd "$ROOT"
-python - "$(find gpurun_out/raw/async -name a_kernel_trace.csv | head -1)" gpurun_out/raw/async/bench.json gpurun_out/profiles_out/${TAG}_async_trace.json <<'PY'
+python - "$(find $OUT/raw/async -name a_kernel_trace.csv | head -1)" $OUT/raw/async/bench.json $OUT/profiles_out/${TAG}_async_trace.json <<'PY'
 import csv, json, sys, collections
 rows = []
 for r in csv.DictReader(open(sys.argv[1])):
