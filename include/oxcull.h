@@ -446,6 +446,83 @@ oxc_status oxc_mesh_vertex_fetch_remap(const uint32_t* stream, uint64_t count, u
  * the extent of level i is max(1, width >> i) x max(1, height >> i) (Shadowmaps.cpp:342-346). */
 oxc_status oxc_generate_hpb(oxc_ctx* ctx, oxc_buffer virtual_page_table, const oxc_image_array_u8* hpb_attachment, void* hip_stream);
 
+/* ---- VSM page update: mark, allocate and invalidate shadow pages ------------------------------------
+ * Replaces the page-management part of RendererInstance::draw_virtual_shadowmap (Oxylus/src/Render/Passes/Shadowmaps.cpp:143-421),
+ * the passes the reference runs between the main view's depth buffer and the shadow cull, in its order:
+ *   1. sun_moved: the page table is cleared to 0 (:143-148);
+ *   2. reset page visibility: Visible, Dirty and Invalidated cleared (passes/rmvsm_reset_page_visibility.slang);
+ *   3. invalidate pages, only when !sun_moved && dirty_mesh_instance_count > 0 (:203; rmvsm_invalidate_pages.slang): for each dirty
+ *      mesh instance and each clipmap, project_aabb of the mesh AABB through projection_view_mat * previous_world and through
+ *      projection_view_mat * world (the cull path's project_aabb, `center - extent * 0.5` corner); every page of the clamped page
+ *      rectangle whose entry is Backed becomes exactly Invalidated (8): reset() then set_invalidated, the address bits go too;
+ *   4. mark visible pages (rmvsm_mark_visible_pages.slang), one thread per depth pixel, rules below;
+ *   5. free invisible pages: an entry that is Backed but not Visible loses the Backed bit only (its address bits stay);
+ *   6. build the free page list: physical pages that no Visible && Backed entry names, ascending;
+ *   7. allocate pages: request i (Visible, not Backed) gets free_list[i] -- address, Dirty and Backed set -- when
+ *      i < free_page_count; otherwise the allocation fails and NOTHING is stored (rmvsm_allocate_pages.slang:35-38 returns before
+ *      the Store): the page stays Visible and unbacked, its AllocationFailed bit stays 0, and the failure is counted in
+ *      counters_buffer[4] only;
+ *   8. HPB downsample when hpb_attachment.dptr != NULL: the bytes of oxc_generate_hpb on the final table;
+ *   9. mark dirty pages: every Backed && Dirty entry -- in this sequence, the pages allocated by this call -- appends its physical
+ *      page coords (addr % P, addr / P), P = physical_page_table_size / page_size, to dirty_physical_pages_buffer, counts in
+ *      clear_cmd.z and sets its layer's dirty flag;
+ *  10. clear dirty pages when physical_page_image.dptr != NULL: every texel of every dirty physical page is set to 1.0.
+ * Deterministic orders (the reference orders these lists by atomics; each order below is one its race can produce, and the flags and
+ * the set of backed pages do not depend on it while no allocation fails): requests are taken in ascending (layer, y, x) order of the
+ * wrapped page; the free list is ascending physical index; the dirty list is ascending (layer, y, x).
+ * Mark visible pages (binary32, no contraction, IEEE division and square root, the Slang's evaluation order):
+ *   a pixel with depth == 0.0 marks nothing;  uv = (float2(x, y) + 0.5) / depth_extent;
+ *   unproject(uv, d) = (M (uv * 2 - 1, d, 1)).xyz / w, M = inv_projection_view, each row ((m0 a + m1 b) + m2 c) + m3;
+ *   o = (1.0 / resolution) * 0.5, left = uv + (-o.x, o.y), right = uv + (o.x, o.y);
+ *   dist = sqrt((dx dx + dy dy) + dz dz) of unproject(left, d) - unproject(right, d);
+ *   texel_len = ((first_clipmap_width * (float(n - 1) / float(n))) * 2.0) / virtual_extent, n = page_table_size;  r = dist / texel_len;
+ *   clipmap index (the reference's min(u32(ceil(bias + max(log2(r), 0))), count - 1), stated without log2): the number of k in
+ *     [0, count - 2] for which (double)k - (double)bias < 0 or (double)r > exp2((double)k - (double)bias) -- a negative ceil gives 0, a
+ *     NaN r acts as log2 = 0;
+ *   clip = pv (world, 1) of that clipmap, uv' = (clip.xy / clip.w + 1.0) * 0.5; outside [0, 1] (or NaN) marks nothing;
+ *   virt = int(floor(uv' * float(n))); virt outside [0, n - 1] marks nothing; wrapped = floor_mod(virt + page_offset, n) (integer,
+ *   the result in [0, n)); the entry (clipmap, wrapped.y, wrapped.x) becomes Visible.
+ * Limits (else OXC_INVALID_ARG): 1 <= clipmap_count <= 16, page_table_size a multiple of 8 in [8, 256], page_size a multiple of 16,
+ * physical_page_table_size a multiple of page_size with at most 65536 physical pages (16 address bits), depth_extent equal to the depth
+ * attachment's extent.  The documented configuration is the reference's (RendererInstance.hpp:262-267): page_size 128,
+ * page_table_size 64, physical_page_table_size 8192, 10 clipmaps.
+ * No host synchronisation; the only allocation is the context's own scratch (the per-page mark map, the free page list), which grows
+ * on the first call of a larger shape (not while the stream is captured: OXC_INVALID_ARG then).  Capturable into a HIP graph. */
+typedef struct oxc_vsm_update_context {
+  uint32_t struct_size; /* sizeof(oxc_vsm_update_context) */
+  uint32_t sun_moved;   /* RMVSMContext::sun_moved */
+  /* the GPU::VSMContext fields the passes read (rmvsm.slang:116-127, SceneGPU.hpp:325-337) */
+  int32_t page_size;                /* texels per page side */
+  int32_t page_table_size;          /* n: virtual pages per table side */
+  int32_t physical_page_table_size; /* VSMContext::physcial_page_table_size: physical image side in texels */
+  int32_t clipmap_count;            /* layers of the page table */
+  int32_t depth_extent[2];
+  float first_clipmap_width;
+  float clipmap_selection_bias;
+  float virtual_extent;
+  uint32_t dirty_mesh_instance_count; /* PreparedFrame::dirty_mesh_instance_count */
+  /* the GPU::Camera fields the passes read (scene.slang:162-193) */
+  float inv_projection_view[16]; /* column-major */
+  float resolution[2];
+  oxc_buffer virtual_page_table;  /* in/out, persistent across frames: u32 [clipmap_count][n][n] VSMPageMetadata (rmvsm.slang:16-112) */
+  oxc_buffer vsm_clipmaps_buffer; /* in: oxc_virtual_clipmap[clipmap_count] */
+  oxc_image depth_attachment;     /* in: R32F, levels = 1, the main view's reversed-Z depth (0 = nothing drawn) */
+  oxc_buffer dirty_mesh_instance_indices; /* in (pass 3): u32[dirty_mesh_instance_count] */
+  oxc_buffer mesh_instances_buffer;       /* in (pass 3): GPU::MeshInstance[] */
+  oxc_buffer meshes_buffer;               /* in (pass 3): GPU::Mesh[] */
+  oxc_buffer transforms_world_buffer;     /* in (pass 3): GPU::TransformWorld[] */
+  oxc_buffer transforms_previous_buffer;  /* in (pass 3): GPU::TransformPrevious[] (one mat4, SceneGPU.hpp:24-26) */
+  oxc_buffer vsm_clipmap_dirty_flags_buffer; /* out: u32[clipmap_count], every layer written 0 or 1 (what oxc_cull_geometry(use_hpb) reads) */
+  oxc_buffer dirty_physical_pages_buffer;    /* out: u32x2 dirty_physical_page_coords, one per dirty page (room for min(pages, P * P)) */
+  oxc_buffer clear_cmd_buffer;               /* out: VkDispatchIndirectCommand {page_size / 16, page_size / 16, dirty count}, z counted from 0 */
+  oxc_buffer counters_buffer;                /* out: u32[8] {active_request_count, dirty_physical_page_count, free_page_count, alloc_cursor,
+                                                failed allocations, 0, 0, 0} (VSMPageAllocator's four counts, then the failures) */
+  oxc_image_array_u8 hpb_attachment;         /* optional out (dptr NULL: skipped): width = height = n, layers = clipmap_count */
+  oxc_image physical_page_image;             /* optional out (dptr NULL: skipped): R32F, levels = 1, physical_page_table_size square */
+} oxc_vsm_update_context;
+
+oxc_status oxc_update_virtual_shadowmap(oxc_ctx* ctx, const oxc_vsm_update_context* context, void* hip_stream);
+
 /* ---- terrain patch cull ---------------------------------------------------------
  * Replaces RendererInstance::cull_terrain (Oxylus/src/Render/Passes/Terrain.cpp:159-216) + pipeline
  * terrain_cull (Shaders/passes/terrain_cull.slang:17-83): one thread per patch, world-space AABB from the

@@ -37,6 +37,7 @@ enum {
   OXC_K_DRAW_VISBUFFER = 12, /* every launch of one oxc_draw_visbuffer call (clear, setup, clipped, big, resolve) */
   OXC_K_MESHLET_BOUNDS = 13, /* oxc_build_meshlet_bounds */
   OXC_K_MULTIVIEW_SETUP = 14, /* batched views of one scene: view groups per mesh instance, chunk numbering, step list (three small launches) */
+  OXC_K_VSM_UPDATE = 15, /* every launch of one oxc_update_virtual_shadowmap call (reset + invalidate, mark, resolve, HPB, clear) */
   OXC_K_COUNT = 16
 };
 typedef struct oxc_kernel_times {

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <dlfcn.h>
@@ -74,6 +75,8 @@ struct oxc_ctx {
   uint32_t raster_capacity_request = 0;  // oxc_debug_set_tuning(OXC_TUNE_RASTER_BIG_CAPACITY): used by the first draw instead of the default
   void* raster_rows = nullptr;     // oxc_draw_visbuffer: one DrawRow per mesh instance
   uint32_t raster_rows_cap = 0;
+  void* vsm_scratch = nullptr;     // oxc_update_virtual_shadowmap: free page list (u32 per physical page), then the per-page mark map (a byte per entry)
+  uint64_t vsm_scratch_bytes = 0;
   void* comm = nullptr;            // ncclComm_t (oxc_comm_init)
   uint32_t comm_rank = 0, comm_world = 0;
   // counter slots
@@ -474,6 +477,7 @@ void oxc_destroy(oxc_ctx* ctx) {
   if (ctx->bounds_scratch) (void)hipFree(ctx->bounds_scratch);
   if (ctx->raster_scratch) (void)hipFree(ctx->raster_scratch);
   if (ctx->raster_rows) (void)hipFree(ctx->raster_rows);
+  if (ctx->vsm_scratch) (void)hipFree(ctx->vsm_scratch);
   if (ctx->comm) (void)oxc_comm_destroy(ctx);
   if (ctx->slots) (void)hipFree(ctx->slots);
   if (ctx->order_event) (void)hipEventDestroy(ctx->order_event);
@@ -1455,6 +1459,125 @@ oxc_status oxc_generate_hpb(oxc_ctx* ctx, oxc_buffer page_table, const oxc_image
   OXC_ORDER(ctx, hip_stream);
   launch_generate_hpb(static_cast<const uint32_t*>(page_table.dptr), static_cast<uint8_t*>(h->dptr), h->width, h->height, h->layers, h->levels, h->level_offset,
                       static_cast<hipStream_t>(hip_stream));
+  OXC_HIP(ctx, hipGetLastError());
+  return OXC_OK;
+}
+
+oxc_status oxc_update_virtual_shadowmap(oxc_ctx* ctx, const oxc_vsm_update_context* c, void* hip_stream) {
+  if (!ctx) return OXC_INVALID_ARG;
+  if (!c || c->struct_size != sizeof(oxc_vsm_update_context)) return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: bad context / struct_size");
+  const int32_t n = c->page_table_size, ps = c->page_size, phys = c->physical_page_table_size, layers = c->clipmap_count;
+  if (layers < 1 || layers > 16) return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: clipmap_count must be 1..16");
+  if (n < 8 || n > 256 || n % 8) return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: page_table_size must be a multiple of 8 in [8, 256]");
+  if (ps < 16 || ps % 16 || phys < ps || phys % ps) return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: page_size must be a multiple of 16 and divide physical_page_table_size");
+  const uint32_t P = (uint32_t)(phys / ps);
+  if ((uint64_t)P * P > 65536u) return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: more than 65536 physical pages (16 address bits)");
+  const uint32_t phys_count = P * P;
+  const uint64_t entries = (uint64_t)layers * n * n;
+  const oxc_image& dimg = c->depth_attachment;
+  if (c->depth_extent[0] < 0 || c->depth_extent[1] < 0 || (uint32_t)c->depth_extent[0] != dimg.width || (uint32_t)c->depth_extent[1] != dimg.height)
+    return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: depth_extent must equal the depth attachment's extent");
+  if (dimg.width && dimg.height && (!dimg.dptr || dimg.levels != 1 || dimg.level_offset[0] != 0))
+    return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: depth_attachment must be one R32F level at offset 0");
+  if (!c->virtual_page_table.dptr || c->virtual_page_table.bytes < entries * 4u) return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: virtual_page_table smaller than clipmap_count * n * n u32");
+  if (!c->vsm_clipmaps_buffer.dptr || c->vsm_clipmaps_buffer.bytes < (uint64_t)layers * sizeof(oxc_virtual_clipmap))
+    return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: vsm_clipmaps_buffer smaller than clipmap_count records");
+  if (!c->vsm_clipmap_dirty_flags_buffer.dptr || c->vsm_clipmap_dirty_flags_buffer.bytes < (uint64_t)layers * 4u)
+    return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: vsm_clipmap_dirty_flags_buffer smaller than clipmap_count u32");
+  if (!c->dirty_physical_pages_buffer.dptr || c->dirty_physical_pages_buffer.bytes < std::min<uint64_t>(entries, phys_count) * 8u)
+    return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: dirty_physical_pages_buffer smaller than min(pages, physical pages) u32x2");
+  if (!c->clear_cmd_buffer.dptr || c->clear_cmd_buffer.bytes < 12u) return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: clear_cmd_buffer smaller than a VkDispatchIndirectCommand");
+  if (!c->counters_buffer.dptr || c->counters_buffer.bytes < 32u) return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: counters_buffer smaller than u32[8]");
+  const bool invalidate = !c->sun_moved && c->dirty_mesh_instance_count > 0;
+  if (invalidate) {
+    if (!c->dirty_mesh_instance_indices.dptr || c->dirty_mesh_instance_indices.bytes < (uint64_t)c->dirty_mesh_instance_count * 4u)
+      return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: dirty_mesh_instance_indices smaller than dirty_mesh_instance_count u32");
+    if (!c->mesh_instances_buffer.dptr || !c->meshes_buffer.dptr || !c->transforms_world_buffer.dptr || !c->transforms_previous_buffer.dptr)
+      return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: invalidation needs mesh_instances, meshes, transforms_world and transforms_previous");
+  }
+  const oxc_image_array_u8& h = c->hpb_attachment;
+  if (h.dptr) {
+    if (h.width != (uint32_t)n || h.height != (uint32_t)n || h.layers != (uint32_t)layers || h.levels == 0 || h.levels > 13)
+      return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: hpb_attachment must be n x n x clipmap_count with 1..13 levels");
+    for (uint32_t k = 0; k < h.levels; k++)
+      if (h.level_offset[k] > 0xFFFFFFFFull) return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: hpb level offsets must fit 32 bits");
+  }
+  const oxc_image& pimg = c->physical_page_image;
+  if (pimg.dptr && (pimg.width != (uint32_t)phys || pimg.height != (uint32_t)phys || pimg.levels != 1 || pimg.level_offset[0] != 0 ||
+                    (reinterpret_cast<uintptr_t>(pimg.dptr) & 15u)))
+    return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: physical_page_image must be one 16-byte aligned R32F level of physical_page_table_size^2");
+  OXC_HIP(ctx, hipSetDevice(ctx->device));
+  OXC_ORDER(ctx, hip_stream);
+  const hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  const uint64_t want = align_up((uint64_t)phys_count * 4u, 256) + align_up(entries, 256);
+  if (want > ctx->vsm_scratch_bytes) {
+    if (stream_is_capturing(s))
+      return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: scratch must grow but the stream is being captured; make one un-captured call of this size first");
+    OXC_HIP(ctx, hipDeviceSynchronize());  // in-flight work may still use the old scratch
+    if (ctx->vsm_scratch) OXC_HIP(ctx, hipFree(ctx->vsm_scratch));
+    ctx->vsm_scratch = nullptr;
+    ctx->vsm_scratch_bytes = 0;
+    hipError_t e = hipMalloc(&ctx->vsm_scratch, want);
+    if (e != hipSuccess) return fail(ctx, OXC_OUT_OF_MEMORY, "hipMalloc(vsm scratch)", e);
+    ctx->vsm_scratch_bytes = want;
+  }
+  VsmArgs a = {};
+  a.page_table = static_cast<uint32_t*>(c->virtual_page_table.dptr);
+  a.clipmaps = static_cast<const float*>(c->vsm_clipmaps_buffer.dptr);
+  a.depth = static_cast<const float*>(dimg.dptr);
+  a.depth_w = dimg.width;
+  a.depth_h = dimg.height;
+  a.depth_vec4 = (dimg.width % 4u == 0u && (reinterpret_cast<uintptr_t>(dimg.dptr) & 15u) == 0u) ? 1u : 0u;
+  a.n = (uint32_t)n;
+  a.layers = (uint32_t)layers;
+  a.page_size = (uint32_t)ps;
+  a.phys_side = P;
+  a.phys_count = phys_count;
+  a.sun_moved = c->sun_moved ? 1u : 0u;
+  a.invalidate = invalidate ? 1u : 0u;
+  a.dirty_ids = static_cast<const uint32_t*>(c->dirty_mesh_instance_indices.dptr);
+  a.dirty_count = invalidate ? c->dirty_mesh_instance_count : 0u;
+  a.mesh_instance_count = (uint32_t)std::min<uint64_t>(c->mesh_instances_buffer.bytes / sizeof(GpuMeshInstance), 0xFFFFFFFFu);
+  a.mesh_count = (uint32_t)std::min<uint64_t>(c->meshes_buffer.bytes / sizeof(GpuMesh), 0xFFFFFFFFu);
+  a.transform_count = (uint32_t)std::min<uint64_t>(c->transforms_world_buffer.bytes / 64u, 0xFFFFFFFFu);
+  a.transform_previous_count = (uint32_t)std::min<uint64_t>(c->transforms_previous_buffer.bytes / 64u, 0xFFFFFFFFu);
+  a.mesh_instances = static_cast<const GpuMeshInstance*>(c->mesh_instances_buffer.dptr);
+  a.meshes = static_cast<const GpuMesh*>(c->meshes_buffer.dptr);
+  a.transforms = static_cast<const float*>(c->transforms_world_buffer.dptr);
+  a.transforms_previous = static_cast<const float*>(c->transforms_previous_buffer.dptr);
+  a.dirty_flags = static_cast<uint32_t*>(c->vsm_clipmap_dirty_flags_buffer.dptr);
+  a.dirty_coords = static_cast<uint32_t*>(c->dirty_physical_pages_buffer.dptr);
+  a.clear_cmd = static_cast<uint32_t*>(c->clear_cmd_buffer.dptr);
+  a.counters = static_cast<uint32_t*>(c->counters_buffer.dptr);
+  a.physical = static_cast<float*>(pimg.dptr);
+  a.physical_size = (uint32_t)phys;
+  a.free_list = static_cast<uint32_t*>(ctx->vsm_scratch);
+  a.mark = static_cast<uint8_t*>(ctx->vsm_scratch) + align_up((uint64_t)phys_count * 4u, 256);
+  // per-call constants of the pixel pass, binary32 in the Slang's order (include/oxcull.h)
+  for (int k = 0; k < 16; k++) a.inv_pv[k] = c->inv_projection_view[k];
+  a.off_x = (1.0f / c->resolution[0]) * 0.5f;
+  a.off_y = (1.0f / c->resolution[1]) * 0.5f;
+  const float scale_ratio = (float)(n - 1) / (float)n;  // get_first_clipmap_texel_length, rmvsm.slang:148-155
+  const float effective_width = c->first_clipmap_width * scale_ratio;
+  a.texel_len = (effective_width * 2.0f) / c->virtual_extent;
+  a.lvl_always = 0;
+  for (int k = 0; k + 1 < layers; k++) {
+    const double dk = (double)k - (double)c->clipmap_selection_bias;
+    if (dk < 0.0) {
+      a.lvl_always = (uint32_t)(k + 1);
+      a.lvl_thr[k] = 0.0f;
+      continue;
+    }
+    // (double)r > T  <=>  r > the largest binary32 <= T (r is a binary32)
+    const double T = std::exp2(dk);
+    float f = (float)T;
+    if ((double)f > T) f = std::nextafter(f, -INFINITY);
+    a.lvl_thr[k] = f;
+  }
+  {
+    KernelTimer t(ctx, OXC_K_VSM_UPDATE, s);
+    launch_vsm_update(a, ctx->num_cus, static_cast<uint8_t*>(h.dptr), h.levels, h.level_offset, s);
+  }
   OXC_HIP(ctx, hipGetLastError());
   return OXC_OK;
 }

@@ -461,6 +461,40 @@ void launch_cull_terrain(const TerrainArgs& a, hipStream_t s);
 // oxcull_hpb.hip: hierarchical page buffer producer
 void launch_generate_hpb(const uint32_t* page_table, uint8_t* data, uint32_t w, uint32_t h, uint32_t layers, uint32_t levels, const uint64_t* level_offset,
                          hipStream_t s);
+// oxcull_vsm.hip: VSM page update (oxc_update_virtual_shadowmap)
+struct VsmArgs {
+  uint32_t* page_table;  // [layers][n][n]
+  const float* clipmaps; // GPU::VirtualClipmap[layers], 19 words each
+  const float* depth;
+  uint32_t depth_w, depth_h, depth_vec4;  // depth_vec4: rows may be read with 16-byte loads (width % 4 == 0, 16-byte aligned)
+  uint32_t n, layers, page_size, phys_side, phys_count;  // phys_side = P = physical_page_table_size / page_size
+  uint32_t sun_moved, invalidate;
+  // pass 3 (invalidate); the counts bound every index read on the device
+  const uint32_t* dirty_ids;
+  uint32_t dirty_count, mesh_instance_count, mesh_count, transform_count, transform_previous_count;
+  const GpuMeshInstance* mesh_instances;
+  const GpuMesh* meshes;
+  const float* transforms;
+  const float* transforms_previous;
+  // outputs
+  uint32_t* dirty_flags;
+  uint32_t* dirty_coords;  // u32x2 per dirty page
+  uint32_t* clear_cmd;
+  uint32_t* counters;
+  float* physical;  // optional: physical_size x physical_size R32F
+  uint32_t physical_size;
+  // context scratch
+  uint8_t* mark;  // [layers][n][n]: 1 = marked visible by this call's pixel pass
+  uint32_t* free_list;
+  // pixel pass constants, computed once per call on the host in binary32 / binary64 (include/oxcull.h)
+  float inv_pv[16];
+  float off_x, off_y;  // (1.0 / resolution) * 0.5
+  float texel_len;
+  uint32_t lvl_always;  // k < lvl_always: (double)k - bias < 0, always counted
+  float lvl_thr[16];    // k >= lvl_always: counted when r > lvl_thr[k] (binary32 round-down of exp2(k - bias): the same decision as the binary64 compare)
+};
+// reset + invalidate, mark, resolve (free / allocate / dirty list), then the optional HPB (hpb != nullptr) and clear (a.physical != nullptr)
+void launch_vsm_update(const VsmArgs& a, uint32_t num_cus, uint8_t* hpb, uint32_t hpb_levels, const uint64_t* hpb_level_offset, hipStream_t s);
 // oxcull_bounds.hip: meshlet bounds producer
 void launch_build_meshlet_bounds(const float* pos, uint32_t vertex_count, const void* meshlets, uint32_t meshlet_count, const uint32_t* vidx,
                                  const uint8_t* micro, void* out_bounds, float* out_mesh6, void* out_qpos, float* meshlet_minmax, float* normals,

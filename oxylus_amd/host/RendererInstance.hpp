@@ -213,6 +213,10 @@ public:
   auto generate_hpb(oxc_buffer virtual_page_table, const oxc_image_array_u8& hpb_attachment) -> void {
     check(oxc_generate_hpb(ctx_, virtual_page_table, &hpb_attachment, stream_));
   }
+  // the page-management passes of draw_virtual_shadowmap (Passes/Shadowmaps.cpp:143-421): mark, allocate and invalidate pages
+  auto update_virtual_shadowmap(const oxc_vsm_update_context& context) -> void {
+    check(oxc_update_virtual_shadowmap(ctx_, &context, stream_));
+  }
   auto build_meshlet_bounds(oxc_meshlet_bounds_desc desc) -> void {
     desc.struct_size = sizeof desc;
     check(oxc_build_meshlet_bounds(ctx_, &desc, stream_));

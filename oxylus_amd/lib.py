@@ -235,6 +235,39 @@ class DrawContext(C.Structure):
     ]
 
 
+class VsmUpdateContext(C.Structure):
+    """oxc_vsm_update_context (include/oxcull.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("sun_moved", C.c_uint32),
+        ("page_size", C.c_int32),
+        ("page_table_size", C.c_int32),
+        ("physical_page_table_size", C.c_int32),
+        ("clipmap_count", C.c_int32),
+        ("depth_extent", C.c_int32 * 2),
+        ("first_clipmap_width", C.c_float),
+        ("clipmap_selection_bias", C.c_float),
+        ("virtual_extent", C.c_float),
+        ("dirty_mesh_instance_count", C.c_uint32),
+        ("inv_projection_view", C.c_float * 16),
+        ("resolution", C.c_float * 2),
+        ("virtual_page_table", Buffer),
+        ("vsm_clipmaps_buffer", Buffer),
+        ("depth_attachment", Image),
+        ("dirty_mesh_instance_indices", Buffer),
+        ("mesh_instances_buffer", Buffer),
+        ("meshes_buffer", Buffer),
+        ("transforms_world_buffer", Buffer),
+        ("transforms_previous_buffer", Buffer),
+        ("vsm_clipmap_dirty_flags_buffer", Buffer),
+        ("dirty_physical_pages_buffer", Buffer),
+        ("clear_cmd_buffer", Buffer),
+        ("counters_buffer", Buffer),
+        ("hpb_attachment", ImageArrayU8),
+        ("physical_page_image", Image),
+    ]
+
+
 # every symbol include/oxcull.h declares
 EXPORTS = [
     "oxc_abi_version",
@@ -263,6 +296,7 @@ EXPORTS = [
     "oxc_mesh_build_destroy",
     "oxc_mesh_vertex_fetch_remap",
     "oxc_generate_hpb",
+    "oxc_update_virtual_shadowmap",
     "oxc_cull_terrain",
     "oxc_draw_visbuffer",
     "oxc_comm_unique_id",
@@ -338,6 +372,7 @@ def load(path: str = None) -> C.CDLL:
     lib.oxc_mesh_build_destroy.restype = None
     lib.oxc_mesh_vertex_fetch_remap.argtypes = [vp, C.c_uint64, C.c_uint32, vp, vp]
     lib.oxc_generate_hpb.argtypes = [vp, Buffer, C.POINTER(ImageArrayU8), vp]
+    lib.oxc_update_virtual_shadowmap.argtypes = [vp, C.POINTER(VsmUpdateContext), vp]
     lib.oxc_cull_terrain.argtypes = [vp, C.POINTER(TerrainContext), vp]
     lib.oxc_debug_read_u32.argtypes = [vp, vp, C.c_uint32, vp, vp]
     lib.oxc_debug_shared_tests_mode.argtypes = [vp]
@@ -383,7 +418,7 @@ class KernelTimes(C.Structure):
 KERNEL_NAMES = ["prepare_instances", "cull_meshes_scan", "cull_meshes_expand", "cull_meshlets_test", "cull_meshlets_emit",
                 "cull_triangles_test", "cull_triangles_emit", "hiz", "cull_meshlets_test_late", "cull_meshlets_emit_late",
                 "cull_triangles_test_late", "cull_triangles_emit_late", "draw_visbuffer", "build_meshlet_bounds",
-                "multiview_setup", "_15"]
+                "multiview_setup", "vsm_update"]
 
 
 class OxcError(RuntimeError):

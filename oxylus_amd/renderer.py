@@ -186,6 +186,90 @@ class CullGeometryContext:
 
 
 @dataclass
+class VirtualShadowmapContext:
+    """oxc_vsm_update_context: the page-management part of RendererInstance::draw_virtual_shadowmap (Shadowmaps.cpp:143-421).
+    Sizes default to the reference's configuration (RendererInstance.hpp:262-267); `create` allocates the outputs."""
+    virtual_page_table: torch.Tensor              # int32 [clipmap_count, n, n], persistent across frames
+    vsm_clipmaps_buffer: torch.Tensor             # uint8 [clipmap_count * 76] GPU::VirtualClipmap records
+    depth_attachment: ImageAttachment             # R32F, levels = 1: the main view's reversed-Z depth
+    inv_projection_view: list                     # Camera::inv_projection_view, 16 floats column-major
+    resolution: tuple                             # Camera::resolution
+    vsm_clipmap_dirty_flags_buffer: torch.Tensor  # int32 [clipmap_count] out
+    dirty_physical_pages_buffer: torch.Tensor     # int32 [min(pages, physical pages), 2] out
+    clear_cmd_buffer: torch.Tensor                # int32 [3] out: VkDispatchIndirectCommand
+    counters_buffer: torch.Tensor                 # int32 [8] out
+    page_size: int = 128
+    page_table_size: int = 64
+    physical_page_table_size: int = 8192
+    clipmap_count: int = 10
+    first_clipmap_width: float = 10.0
+    clipmap_selection_bias: float = -1.5
+    virtual_extent: float = 8192.0
+    sun_moved: bool = False
+    dirty_mesh_instance_indices: Optional[torch.Tensor] = None  # int32 [k]; with the four scene buffers below (read when k > 0)
+    mesh_instances_buffer: Optional[torch.Tensor] = None
+    meshes_buffer: Optional[torch.Tensor] = None
+    transforms_world_buffer: Optional[torch.Tensor] = None
+    transforms_previous_buffer: Optional[torch.Tensor] = None   # float32 [M, 16] GPU::TransformPrevious
+    hpb_attachment: Optional[HpbAttachment] = None              # optional out
+    physical_page_image: Optional[ImageAttachment] = None       # optional out
+
+    @staticmethod
+    def create(depth: torch.Tensor, inv_projection_view, resolution, clipmaps: torch.Tensor, page_size: int = 128, page_table_size: int = 64,
+               physical_page_table_size: int = 8192, clipmap_count: int = 10, with_hpb: bool = True, with_physical: bool = False,
+               **kw) -> "VirtualShadowmapContext":
+        dev = depth.device
+        n, layers = page_table_size, clipmap_count
+        phys_pages = (physical_page_table_size // page_size) ** 2
+        hpb = None
+        if with_hpb:
+            hpb = HpbAttachment.create(n, n, layers, min(max(n.bit_length(), 1), 13), dev)
+        phys = None
+        if with_physical:
+            phys = ImageAttachment.depth(torch.zeros((physical_page_table_size, physical_page_table_size), dtype=torch.float32, device=dev))
+        return VirtualShadowmapContext(
+            virtual_page_table=torch.zeros((layers, n, n), dtype=torch.int32, device=dev), vsm_clipmaps_buffer=torch.as_tensor(clipmaps).to(dev),
+            depth_attachment=ImageAttachment.depth(depth), inv_projection_view=[float(x) for x in inv_projection_view],
+            resolution=(float(resolution[0]), float(resolution[1])),
+            vsm_clipmap_dirty_flags_buffer=torch.zeros(layers, dtype=torch.int32, device=dev),
+            dirty_physical_pages_buffer=torch.zeros((max(min(layers * n * n, phys_pages), 1), 2), dtype=torch.int32, device=dev),
+            clear_cmd_buffer=torch.zeros(3, dtype=torch.int32, device=dev), counters_buffer=torch.zeros(8, dtype=torch.int32, device=dev),
+            page_size=page_size, page_table_size=n, physical_page_table_size=physical_page_table_size, clipmap_count=layers,
+            hpb_attachment=hpb, physical_page_image=phys, **kw)
+
+    def c(self) -> L.VsmUpdateContext:
+        c = L.VsmUpdateContext()
+        c.struct_size = C.sizeof(L.VsmUpdateContext)
+        c.sun_moved = int(self.sun_moved)
+        c.page_size, c.page_table_size, c.physical_page_table_size = self.page_size, self.page_table_size, self.physical_page_table_size
+        c.clipmap_count = self.clipmap_count
+        c.depth_extent[0], c.depth_extent[1] = self.depth_attachment.width, self.depth_attachment.height
+        c.first_clipmap_width, c.clipmap_selection_bias, c.virtual_extent = self.first_clipmap_width, self.clipmap_selection_bias, self.virtual_extent
+        ids = self.dirty_mesh_instance_indices
+        c.dirty_mesh_instance_count = 0 if ids is None else ids.numel()
+        for i in range(16):
+            c.inv_projection_view[i] = float(self.inv_projection_view[i])
+        c.resolution[0], c.resolution[1] = float(self.resolution[0]), float(self.resolution[1])
+        c.virtual_page_table = _buf(self.virtual_page_table)
+        c.vsm_clipmaps_buffer = _buf(self.vsm_clipmaps_buffer)
+        c.depth_attachment = self.depth_attachment.c()
+        c.dirty_mesh_instance_indices = _buf(ids)
+        c.mesh_instances_buffer = _buf(self.mesh_instances_buffer)
+        c.meshes_buffer = _buf(self.meshes_buffer)
+        c.transforms_world_buffer = _buf(self.transforms_world_buffer)
+        c.transforms_previous_buffer = _buf(self.transforms_previous_buffer)
+        c.vsm_clipmap_dirty_flags_buffer = _buf(self.vsm_clipmap_dirty_flags_buffer)
+        c.dirty_physical_pages_buffer = _buf(self.dirty_physical_pages_buffer)
+        c.clear_cmd_buffer = _buf(self.clear_cmd_buffer)
+        c.counters_buffer = _buf(self.counters_buffer)
+        if self.hpb_attachment is not None:
+            c.hpb_attachment = self.hpb_attachment.c()
+        if self.physical_page_image is not None:
+            c.physical_page_image = self.physical_page_image.c()
+        return c
+
+
+@dataclass
 class MainGeometryContext:
     """The fields generate_hiz uses (RendererInstance.hpp:199-216)."""
     depth_attachment: ImageAttachment
@@ -324,6 +408,13 @@ class RendererInstance:
         im = hpb.c()
         self._keep = (page_table, hpb)
         self._check(self._lib.oxc_generate_hpb(self._ctx, L.Buffer(C.c_void_p(page_table.data_ptr()), page_table.numel() * 4), C.byref(im), self._stream(stream)))
+
+    def update_virtual_shadowmap(self, context: VirtualShadowmapContext, stream=None):
+        """Shadowmaps.cpp:143-421: sun_moved clear, reset, invalidate, mark, free, free list, allocate, HPB, mark dirty, clear dirty
+        pages (include/oxcull.h, oxc_update_virtual_shadowmap)."""
+        c = context.c()
+        self._keep = context
+        self._check(self._lib.oxc_update_virtual_shadowmap(self._ctx, C.byref(c), self._stream(stream)))
 
     def cull_terrain(self, cull_flags: int, cull_camera, world_min, world_size, patch_count, base_height: float, height_scale: float,
                      patch_minmax: torch.Tensor, mask: torch.Tensor, hiz: "ImageAttachment" = None, stream=None):
