@@ -523,6 +523,61 @@ typedef struct oxc_vsm_update_context {
 
 oxc_status oxc_update_virtual_shadowmap(oxc_ctx* ctx, const oxc_vsm_update_context* context, void* hip_stream);
 
+/* ---- VSM shadow draw: rasterise the shadow cull's triangles into the dirty physical pages ----------------
+ * Replaces the tail of RendererInstance::draw_virtual_shadowmap (Shadowmaps.cpp:466-754): rmvsm_build_draw_commands, then the
+ * indirect multi-draw of rmvsm_draw_physical_pages (vs_main / fs_main), as a compute rasteriser.  The frame is
+ *   oxc_update_virtual_shadowmap -> oxc_cull_geometry(use_hpb, the last clipmap's camera, Shadowmaps.cpp:433-463) -> this call,
+ * with `frame` and draw_geometry_cmd_buffer / wide_triangle_index of that cull.
+ *   active clipmaps  (rmvsm_build_draw_commands) those whose dirty flag is not 0, in DESCENDING clipmap index.  When the three optional
+ *           buffers are given, active clipmap number i gets draw_commands[i] = a copy of the 5 words of the source command,
+ *           draw_clipmaps[i] = its index, and draw_count = the number of active clipmaps (entries past it are not written).  All of it
+ *           is worked out on the device; nothing is read back to the host.
+ *   vertex  each index of the list is drawn once per active clipmap.  Vertex fetch, world, the clipper (w >= 2^-10 and the 64x guard
+ *           band), the screen mapping, the 1/256-pixel snap, the top-left rule and the binary64 z/w interpolation from exact edge values
+ *           are exactly oxc_draw_visbuffer's, with projection_view = that clipmap's projection_view_mat and a V x V viewport,
+ *           V = page_table_size * page_size.  A command with instanceCount == 0 draws nothing (the pair form's overflow rule).
+ *   cull    None (Shadowmaps.cpp: cullMode eNone): a triangle with negative fixed-point area is re-oriented (corners 1 and 2 swapped),
+ *           one with positive area is kept as is, zero area covers nothing; the top-left rule applies after orientation, so a shared
+ *           edge is covered exactly once whatever the windings.
+ *   depth   z = the interpolated value rounded to binary32; a fragment is kept when 0.0 <= z && z <= 1.0 (NaN is dropped).  For the
+ *           clipmaps' orthographic matrices (w = 1) this is the reference's position.z / position.w; there are no z clip planes, the
+ *           test stands in for them.
+ *   page    (fs_main, in integers) for pixel (x, y) of clipmap c: virtual page v = (x / page_size, y / page_size), wrapped =
+ *           floor_mod(v + page_offset, n), e = virtual_page_table[c][wrapped.y][wrapped.x].  The fragment writes only when e is
+ *           Backed && Dirty and its address addr = e >> 16 names a physical page (addr < P * P, P = physical_page_table_size /
+ *           page_size; an out-of-range image store does nothing in Vulkan either); its texel is (addr % P, addr / P) * page_size +
+ *           (x % page_size, y % page_size).  When physical_page_table_size == V and the sizes are powers of two this equals the
+ *           reference's float form (virtual_uv = position.xy / physical extent; the reference's shape is 8192 = 64 x 128).
+ *   write   atomicMin on the texel's u32 bits (the reference's __atomic_min(asuint(z))): a -0.0 fragment never lowers a stored value.
+ *           The result does not depend on the order of the fragments: the image is deterministic byte for byte.
+ *   materials are not read: every material is drawn opaque.  (Stated difference: the reference's alpha-cutoff test samples albedo
+ *           textures, and this library has no textures.)
+ * Limits (else OXC_INVALID_ARG): the shape limits of oxc_update_virtual_shadowmap, V <= 16384 (the guard band's fixed-point range),
+ * physical_page_image one 16-byte aligned R32F level of exactly physical_page_table_size^2, wide_triangle_index 0..2, the optional
+ * outputs all given or all absent.  The context's scratch (drawable-page bitmaps, per-instance rows, the big-triangle / tile / clip
+ * queues, one entry per (triangle, clipmap) pair the index buffer can hold, 4096..2^24) grows on the first call of a larger shape or
+ * frame, with a device synchronisation (not while the stream is captured: a call that would need larger bitmaps or rows returns
+ * OXC_INVALID_ARG then, one that would only want larger queues uses the current ones).  Past a queue, overflow passes find the pairs
+ * again and draw them with whole waves: slower, the same image.  No host synchronisation otherwise; capturable into a HIP graph.
+ * Work: a prologue launch reads the page table once and builds, per active clipmap, a bitmap of drawable virtual pages and their
+ * bounding rectangle; the triangle pass drops every (triangle, clipmap) pair whose page box holds no drawable page, and a large
+ * triangle is rasterised per drawable page of its page box only -- with no active clipmap the call costs its launches only. */
+typedef struct oxc_vsm_draw_context {
+  uint32_t struct_size;         /* sizeof(oxc_vsm_draw_context) */
+  uint32_t wide_triangle_index; /* 0 / 1 / 2, same meaning as in oxc_cull_geometry_context */
+  int32_t page_size, page_table_size, physical_page_table_size, clipmap_count; /* as in oxc_vsm_update_context */
+  oxc_buffer draw_geometry_cmd_buffer;       /* in: the shadow cull's VkDrawIndexedIndirectCommand, read on the device */
+  oxc_buffer virtual_page_table;             /* in: u32 [clipmap_count][n][n] */
+  oxc_buffer vsm_clipmaps_buffer;            /* in: oxc_virtual_clipmap[clipmap_count] (projection_view_mat, page_offset) */
+  oxc_buffer vsm_clipmap_dirty_flags_buffer; /* in: u32[clipmap_count] */
+  oxc_image physical_page_image;             /* in/out: R32F, one level, physical_page_table_size square */
+  oxc_buffer draw_commands_buffer;           /* optional out: VkDrawIndexedIndirectCommand[clipmap_count] */
+  oxc_buffer draw_count_buffer;              /* optional out: u32 */
+  oxc_buffer draw_clipmaps_buffer;           /* optional out: u32[clipmap_count] */
+} oxc_vsm_draw_context;
+
+oxc_status oxc_draw_physical_pages(oxc_ctx* ctx, const oxc_prepared_frame* frame, const oxc_vsm_draw_context* context, void* hip_stream);
+
 /* ---- terrain patch cull ---------------------------------------------------------
  * Replaces RendererInstance::cull_terrain (Oxylus/src/Render/Passes/Terrain.cpp:159-216) + pipeline
  * terrain_cull (Shaders/passes/terrain_cull.slang:17-83): one thread per patch, world-space AABB from the

@@ -78,7 +78,12 @@ uint32_t oxc_debug_tri_loads_mode(const oxc_ctx* ctx);
 enum { OXC_TUNE_ASYNC_MTEST_BLOCKS_PER_CU = 0, OXC_TUNE_ASYNC_TRI_BLOCKS_PER_CU = 1, OXC_TUNE_RASTER_BIG_CAPACITY = 2,
        OXC_TUNE_TRI_BLOCKS_PER_CU = 3 /* grid cap of the triangle kernels in blocks per CU (default 8 = one resident round) */,
        OXC_TUNE_TRI_LOADS = 7 /* triangle kernels' loads of vertex ids / micro indices / positions: 0 (default) = by the scene -- plain loads when the geometry is shared (>= 4 mesh instances per Mesh record), `nt` when it is unique; 1 = always `nt`; 2 = always plain.  Same outputs either way */,
-       OXC_TUNE_MV_EXPAND_ASYNC = 5 /* multi-view batch: blocks per CU of the MeshletInstance expansion on the context's own low-priority stream beside the meshlet stage (default 4); 0: in order on the caller's stream */ };
+       OXC_TUNE_MV_EXPAND_ASYNC = 5 /* multi-view batch: blocks per CU of the MeshletInstance expansion on the context's own low-priority stream beside the meshlet stage (default 4); 0: in order on the caller's stream */,
+       OXC_TUNE_VSM_DRAW_STATS = 8 /* 1: oxc_draw_physical_pages runs counting kernels (oxc_debug_vsm_draw_stats); 0 (default): off */,
+       OXC_TUNE_VSM_DRAW_CAPACITY = 9 /* entries of oxc_draw_physical_pages' big-pair / clip queues (default: every (triangle, clipmap)
+                                         pair of the frame's index buffer, 4096..2^24, growing with the frame; the tile queue holds 2x
+                                         as many); fixed, only before the context's first shadow draw -- the tests shrink it to reach
+                                         the overflow paths */ };
 oxc_status oxc_debug_set_tuning(oxc_ctx* ctx, uint32_t knob, uint32_t value);
 
 /* Measurement aid: counters_dptr != NULL -- the HiZ calls (use_hiz + OXC_CULL_TEST_OCCLUSION) that follow on this context run counting
@@ -91,6 +96,14 @@ oxc_status oxc_debug_count_occlusion_candidates(oxc_ctx* ctx, void* counters_dpt
  * out4 = {triangles queued for the big path (pixel box beyond 8 x 8), triangles that crossed a clip plane, 64 x 64 tiles handed to
  * the tile list, big-list segments that overflowed (their excess triangles were walked by the setup lane: slow, correct)}. */
 oxc_status oxc_debug_raster_stats(oxc_ctx* ctx, uint32_t* host_out4, void* hip_stream);
+
+/* Measurement hook: what the last oxc_draw_physical_pages on this context did; synchronises the stream.
+ * out8 = {(triangle, clipmap) pairs whose page box holds a drawable page, fragments written (page and depth tests passed: atomicMin
+ * issued), big pairs (pixel box beyond the in-wave path), of those the ones the big list could not hold (drawn again by the overflow
+ * pass), (big pair, drawable page) tiles, of those the ones the tile list could not hold (walked by the big pair's wave), pairs that
+ * crossed a clip plane, of those the ones the clip queue could not hold (found again by its overflow pass)}.  The first two are counted
+ * only after oxc_debug_set_tuning(OXC_TUNE_VSM_DRAW_STATS, 1) (a counting instantiation of the kernels, same image, slower); 0 otherwise. */
+oxc_status oxc_debug_vsm_draw_stats(oxc_ctx* ctx, uint32_t* host_out8, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -77,7 +77,12 @@ struct oxc_ctx {
   uint32_t raster_rows_cap = 0;
   void* vsm_scratch = nullptr;     // oxc_update_virtual_shadowmap: free page list (u32 per physical page), then the per-page mark map (a byte per entry)
   uint64_t vsm_scratch_bytes = 0;
-  void* comm = nullptr;            // ncclComm_t (oxc_comm_init)
+  void* vsm_draw_scratch = nullptr;  // oxc_draw_physical_pages: header, drawable-page bitmaps and maps, rows, big-pair / clip / tile queues
+  uint64_t vsm_draw_scratch_bytes = 0;
+  uint32_t vsm_draw_capacity = 0;          // entries of the big-pair and clip queues of that scratch (the tile queue holds 4x as many)
+  uint32_t vsm_draw_capacity_request = 0;  // oxc_debug_set_tuning(OXC_TUNE_VSM_DRAW_CAPACITY): used by the first shadow draw
+  bool vsm_draw_stats = false;             // oxc_debug_set_tuning(OXC_TUNE_VSM_DRAW_STATS): counting kernels
+  void* comm = nullptr;           // ncclComm_t (oxc_comm_init)
   uint32_t comm_rank = 0, comm_world = 0;
   // counter slots
   uint32_t* slots = nullptr;
@@ -478,6 +483,7 @@ void oxc_destroy(oxc_ctx* ctx) {
   if (ctx->raster_scratch) (void)hipFree(ctx->raster_scratch);
   if (ctx->raster_rows) (void)hipFree(ctx->raster_rows);
   if (ctx->vsm_scratch) (void)hipFree(ctx->vsm_scratch);
+  if (ctx->vsm_draw_scratch) (void)hipFree(ctx->vsm_draw_scratch);
   if (ctx->comm) (void)oxc_comm_destroy(ctx);
   if (ctx->slots) (void)hipFree(ctx->slots);
   if (ctx->order_event) (void)hipEventDestroy(ctx->order_event);
@@ -1582,6 +1588,122 @@ oxc_status oxc_update_virtual_shadowmap(oxc_ctx* ctx, const oxc_vsm_update_conte
   return OXC_OK;
 }
 
+// Entries of the shadow draw's big-pair and clip queues (the tile queue holds twice as many): enough for every (triangle, clipmap) pair the
+// frame's index buffer can hold, at most 2^24 (1.07 GB of scratch) and at least 4096.  Beyond them overflow passes find the pairs again
+// and draw each with a whole wave (k_vsm_draw_clipped<RESCAN>, k_vsm_draw_big_rescan), and a big-pair wave walks the tiles that did not
+// fit: slower, same image.  oxc_debug_vsm_draw_stats reports how many went past each queue.
+constexpr uint64_t kVsmDrawCapacityMax = 1u << 24, kVsmDrawCapacityMin = 4096;
+
+oxc_status oxc_draw_physical_pages(oxc_ctx* ctx, const oxc_prepared_frame* f, const oxc_vsm_draw_context* c, void* hip_stream) {
+  if (!ctx) return OXC_INVALID_ARG;
+  if (!f || !c || c->struct_size != sizeof(oxc_vsm_draw_context)) return fail(ctx, OXC_INVALID_ARG, "draw_physical_pages: bad frame / context / struct_size");
+  const int32_t n = c->page_table_size, ps = c->page_size, phys = c->physical_page_table_size, layers = c->clipmap_count;
+  if (layers < 1 || layers > 16) return fail(ctx, OXC_INVALID_ARG, "draw_physical_pages: clipmap_count must be 1..16");
+  if (n < 8 || n > 256 || n % 8) return fail(ctx, OXC_INVALID_ARG, "draw_physical_pages: page_table_size must be a multiple of 8 in [8, 256]");
+  if (ps < 16 || ps % 16 || phys < ps || phys % ps) return fail(ctx, OXC_INVALID_ARG, "draw_physical_pages: page_size must be a multiple of 16 and divide physical_page_table_size");
+  const uint32_t P = (uint32_t)(phys / ps);
+  if ((uint64_t)P * P > 65536u) return fail(ctx, OXC_INVALID_ARG, "draw_physical_pages: more than 65536 physical pages (16 address bits)");
+  if ((int64_t)n * ps > 16384) return fail(ctx, OXC_INVALID_ARG, "draw_physical_pages: V = page_table_size * page_size must be <= 16384 (the guard band's fixed-point range)");
+  if (c->wide_triangle_index > 2u) return fail(ctx, OXC_INVALID_ARG, "draw_physical_pages: wide_triangle_index must be 0, 1 or 2");
+  const uint64_t entries = (uint64_t)layers * n * n;
+  if (!c->virtual_page_table.dptr || c->virtual_page_table.bytes < entries * 4u) return fail(ctx, OXC_INVALID_ARG, "draw_physical_pages: virtual_page_table smaller than clipmap_count * n * n u32");
+  if (!c->vsm_clipmaps_buffer.dptr || c->vsm_clipmaps_buffer.bytes < (uint64_t)layers * sizeof(oxc_virtual_clipmap))
+    return fail(ctx, OXC_INVALID_ARG, "draw_physical_pages: vsm_clipmaps_buffer smaller than clipmap_count records");
+  if (!c->vsm_clipmap_dirty_flags_buffer.dptr || c->vsm_clipmap_dirty_flags_buffer.bytes < (uint64_t)layers * 4u)
+    return fail(ctx, OXC_INVALID_ARG, "draw_physical_pages: vsm_clipmap_dirty_flags_buffer smaller than clipmap_count u32");
+  if (!c->draw_geometry_cmd_buffer.dptr || c->draw_geometry_cmd_buffer.bytes < 20u)
+    return fail(ctx, OXC_INVALID_ARG, "draw_physical_pages: draw_geometry_cmd_buffer must hold a VkDrawIndexedIndirectCommand (run oxc_cull_geometry with the triangle stage first)");
+  const oxc_image& img = c->physical_page_image;
+  if (!img.dptr || img.width != (uint32_t)phys || img.height != (uint32_t)phys || img.levels != 1 || img.level_offset[0] != 0 ||
+      (reinterpret_cast<uintptr_t>(img.dptr) & 15u))
+    return fail(ctx, OXC_INVALID_ARG, "draw_physical_pages: physical_page_image must be one 16-byte aligned R32F level of physical_page_table_size^2");
+  const bool cmds = c->draw_commands_buffer.dptr != nullptr;
+  if (cmds != (c->draw_count_buffer.dptr != nullptr) || cmds != (c->draw_clipmaps_buffer.dptr != nullptr))
+    return fail(ctx, OXC_INVALID_ARG, "draw_physical_pages: draw_commands / draw_count / draw_clipmaps buffers must be given together");
+  if (cmds && (c->draw_commands_buffer.bytes < (uint64_t)layers * 20u || c->draw_count_buffer.bytes < 4u || c->draw_clipmaps_buffer.bytes < (uint64_t)layers * 4u))
+    return fail(ctx, OXC_INVALID_ARG, "draw_physical_pages: draw_commands (clipmap_count x 20 bytes), draw_count (4) or draw_clipmaps (clipmap_count u32) too small");
+  if (!f->meshes_buffer.dptr || !f->transforms_world_buffer.dptr || !f->mesh_instances_buffer.dptr || !f->meshlet_instances_buffer.dptr ||
+      !f->reordered_indices_buffer.dptr)
+    return fail(ctx, OXC_INVALID_ARG, "draw_physical_pages: null PreparedFrame buffer");
+  OXC_HIP(ctx, hipSetDevice(ctx->device));
+  OXC_ORDER(ctx, hip_stream);
+  OXC_JOIN(ctx, hip_stream);  // reads reordered_indices / the draw command
+  const hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  const uint64_t max_tris = f->reordered_indices_buffer.bytes / (c->wide_triangle_index == 2u ? 24u : 12u);
+  // a capacity set with OXC_TUNE_VSM_DRAW_CAPACITY holds; otherwise the queues grow with the frame (not inside a capture: there the
+  // current ones are used, and the overflow passes keep the image right)
+  uint32_t cap = ctx->vsm_draw_capacity_request
+                     ? std::min<uint32_t>(std::max<uint32_t>(ctx->vsm_draw_capacity_request, 64u), 1u << 24)
+                     : (uint32_t)std::min(std::max(max_tris * (uint64_t)layers, kVsmDrawCapacityMin), kVsmDrawCapacityMax);
+  if (ctx->vsm_draw_scratch && (ctx->vsm_draw_capacity_request || stream_is_capturing(s))) cap = ctx->vsm_draw_capacity;
+  cap = std::max(cap, ctx->vsm_draw_capacity);
+  const uint32_t wpl = (uint32_t)((uint64_t)n * n / 32u);
+  uint64_t off = kVsmDrawHeaderBytes;
+  auto carve = [&](uint64_t bytes) {
+    const uint64_t o = off;
+    off = align_up(off + bytes, 256);
+    return o;
+  };
+  const uint64_t o_bitmap = carve((uint64_t)layers * wpl * 4u);
+  const uint64_t o_map = carve(entries * 4u);
+  const uint64_t o_rows = carve((uint64_t)f->mesh_instance_count * sizeof(DrawRow));
+  const uint64_t o_big = carve((uint64_t)cap * sizeof(VsmBig));
+  const uint64_t o_clip = carve((uint64_t)cap * 8u);
+  const uint64_t o_tile = carve((uint64_t)cap * 2u * 8u);
+  if (off > ctx->vsm_draw_scratch_bytes) {
+    if (stream_is_capturing(s))
+      return fail(ctx, OXC_INVALID_ARG, "draw_physical_pages: scratch must grow but the stream is being captured; make one un-captured call of this shape first");
+    OXC_HIP(ctx, hipDeviceSynchronize());  // in-flight work may still use the old scratch
+    if (ctx->vsm_draw_scratch) OXC_HIP(ctx, hipFree(ctx->vsm_draw_scratch));
+    ctx->vsm_draw_scratch = nullptr;
+    ctx->vsm_draw_scratch_bytes = 0;
+    hipError_t e = hipMalloc(&ctx->vsm_draw_scratch, off);
+    if (e != hipSuccess) return fail(ctx, OXC_OUT_OF_MEMORY, "hipMalloc(vsm draw scratch)", e);
+    ctx->vsm_draw_scratch_bytes = off;
+  }
+  ctx->vsm_draw_capacity = cap;  // (never below the previous calls': the scratch holds the largest queues asked for so far)
+  char* const sc = static_cast<char*>(ctx->vsm_draw_scratch);
+  VsmDrawArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.rows = reinterpret_cast<DrawRow*>(sc + o_rows);
+  a.mesh_instance_count = f->mesh_instance_count;
+  a.meshes = static_cast<const GpuMesh*>(f->meshes_buffer.dptr);
+  a.transforms = static_cast<const float*>(f->transforms_world_buffer.dptr);
+  a.mesh_instances = static_cast<const GpuMeshInstance*>(f->mesh_instances_buffer.dptr);
+  a.meshlet_instances = static_cast<const GpuMeshletInstance*>(f->meshlet_instances_buffer.dptr);
+  a.indices = static_cast<const uint32_t*>(f->reordered_indices_buffer.dptr);
+  a.draw_cmd = static_cast<const uint32_t*>(c->draw_geometry_cmd_buffer.dptr);
+  a.wide = c->wide_triangle_index;
+  a.max_triangles = (uint32_t)std::min<uint64_t>(max_tris, 0xFFFFFFFFull);
+  a.page_table = static_cast<const uint32_t*>(c->virtual_page_table.dptr);
+  a.clipmaps = static_cast<const float*>(c->vsm_clipmaps_buffer.dptr);
+  a.dirty_flags = static_cast<const uint32_t*>(c->vsm_clipmap_dirty_flags_buffer.dptr);
+  a.n = (uint32_t)n;
+  a.layers = (uint32_t)layers;
+  a.page_size = (uint32_t)ps;
+  a.phys_side = P;
+  a.V = (uint32_t)(n * ps);
+  a.ps_shift = (ps & (ps - 1)) == 0 ? __builtin_ctz((uint32_t)ps) : -1;
+  a.words_per_layer = wpl;
+  a.physical = static_cast<float*>(img.dptr);
+  a.physical_size = (uint32_t)phys;
+  a.out_cmds = static_cast<uint32_t*>(c->draw_commands_buffer.dptr);
+  a.out_count = static_cast<uint32_t*>(c->draw_count_buffer.dptr);
+  a.out_clipmaps = static_cast<uint32_t*>(c->draw_clipmaps_buffer.dptr);
+  a.header = reinterpret_cast<uint32_t*>(sc);
+  a.bitmap = reinterpret_cast<uint32_t*>(sc + o_bitmap);
+  a.pagemap = reinterpret_cast<uint32_t*>(sc + o_map);
+  a.big_list = reinterpret_cast<VsmBig*>(sc + o_big);
+  a.big_capacity = cap;
+  a.clip_list = reinterpret_cast<uint2*>(sc + o_clip);
+  a.clip_capacity = cap;
+  a.tile_list = reinterpret_cast<uint2*>(sc + o_tile);
+  a.tile_capacity = cap * 2u;
+  launch_vsm_draw(a, ctx->vsm_draw_stats, ctx->num_cus * 8, s);
+  OXC_HIP(ctx, hipGetLastError());
+  return OXC_OK;
+}
+
 oxc_status oxc_cull_terrain(oxc_ctx* ctx, oxc_terrain_context* c, void* hip_stream) {
   if (!ctx) return OXC_INVALID_ARG;
   if (!c || c->struct_size != sizeof(oxc_terrain_context)) return fail(ctx, OXC_INVALID_ARG, "cull_terrain: bad context / struct_size");
@@ -1902,6 +2024,11 @@ oxc_status oxc_debug_set_tuning(oxc_ctx* ctx, uint32_t knob, uint32_t value) {
       if (ctx->raster_scratch) return fail(ctx, OXC_INVALID_ARG, "set_tuning: the raster scratch is allocated by the first oxc_draw_visbuffer; set its capacity before");
       ctx->raster_capacity_request = value;
       return OXC_OK;
+    case OXC_TUNE_VSM_DRAW_STATS: ctx->vsm_draw_stats = value != 0u; return OXC_OK;
+    case OXC_TUNE_VSM_DRAW_CAPACITY:
+      if (ctx->vsm_draw_scratch) return fail(ctx, OXC_INVALID_ARG, "set_tuning: the shadow draw's scratch is allocated by the first oxc_draw_physical_pages; set its capacity before");
+      ctx->vsm_draw_capacity_request = value;
+      return OXC_OK;
     default: return fail(ctx, OXC_INVALID_ARG, "set_tuning: unknown knob");
   }
 }
@@ -1944,6 +2071,29 @@ oxc_status oxc_debug_raster_stats(oxc_ctx* ctx, uint32_t* host_out4, void* hip_s
   host_out4[1] = h[0];
   host_out4[2] = h[32];
   host_out4[3] = overflowed;
+  return OXC_OK;
+}
+
+oxc_status oxc_debug_vsm_draw_stats(oxc_ctx* ctx, uint32_t* host_out8, void* hip_stream) {
+  if (!ctx) return OXC_INVALID_ARG;
+  if (!host_out8) return fail(ctx, OXC_INVALID_ARG, "debug_vsm_draw_stats: null pointer");
+  if (!ctx->vsm_draw_scratch) return fail(ctx, OXC_INVALID_ARG, "debug_vsm_draw_stats: no oxc_draw_physical_pages call on this context yet");
+  OXC_HIP(ctx, hipSetDevice(ctx->device));
+  OXC_ORDER(ctx, hip_stream);
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  std::vector<uint32_t> h(kVsmDrawHeaderBytes / 4);
+  OXC_HIP(ctx, hipMemcpyAsync(h.data(), ctx->vsm_draw_scratch, kVsmDrawHeaderBytes, hipMemcpyDeviceToHost, s));
+  OXC_HIP(ctx, hipStreamSynchronize(s));
+  const uint32_t cap = ctx->vsm_draw_capacity;
+  auto beyond = [](uint32_t count, uint32_t capacity) { return count > capacity ? count - capacity : 0u; };
+  host_out8[0] = h[128];  // pairs kept by the page bitmap (counting kernels only)
+  host_out8[1] = h[160];  // fragments written (counting kernels only)
+  host_out8[2] = h[32];   // big pairs (pixel box beyond the in-wave path)
+  host_out8[3] = beyond(h[32], cap);  // ... of which the big list could not hold
+  host_out8[4] = h[64];   // (big pair, drawable page) tiles
+  host_out8[5] = beyond(h[64], cap * 2u);
+  host_out8[6] = h[96];   // pairs that crossed a clip plane
+  host_out8[7] = beyond(h[96], cap);
   return OXC_OK;
 }
 

@@ -495,6 +495,47 @@ struct VsmArgs {
 };
 // reset + invalidate, mark, resolve (free / allocate / dirty list), then the optional HPB (hpb != nullptr) and clear (a.physical != nullptr)
 void launch_vsm_update(const VsmArgs& a, uint32_t num_cus, uint8_t* hpb, uint32_t hpb_levels, const uint64_t* hpb_level_offset, hipStream_t s);
+// oxcull_vsm_draw.hip: the VSM shadow draw (oxc_draw_physical_pages)
+struct VsmBig {  // a (triangle, clipmap) pair whose pixel box is beyond the in-wave path: snapped corners, oriented with positive area
+  int32_t x[3], y[3];
+  float z[3];
+  uint32_t layer;
+};
+struct VsmDrawArgs {
+  DrawRow* rows;  // [mesh_instance_count], written by the call
+  uint32_t mesh_instance_count;
+  const GpuMesh* meshes;
+  const float* transforms;
+  const GpuMeshInstance* mesh_instances;
+  const GpuMeshletInstance* meshlet_instances;
+  const uint32_t* indices;   // reordered_indices
+  const uint32_t* draw_cmd;  // VkDrawIndexedIndirectCommand
+  uint32_t wide;             // wide_triangle_index
+  uint32_t max_triangles;    // triangles reordered_indices_buffer holds
+  const uint32_t* page_table;  // [layers][n][n]
+  const float* clipmaps;       // GPU::VirtualClipmap[layers], 19 words each
+  const uint32_t* dirty_flags;
+  uint32_t n, layers, page_size, phys_side, V;  // phys_side = P = physical_page_table_size / page_size, V = n * page_size
+  int32_t ps_shift;                             // log2(page_size) when a power of two, else -1
+  uint32_t words_per_layer;                     // n * n / 32
+  float* physical;  // physical_size x physical_size R32F
+  uint32_t physical_size;
+  uint32_t* out_cmds;  // optional (all three or none)
+  uint32_t* out_count;
+  uint32_t* out_clipmaps;
+  // context scratch
+  uint32_t* header;   // active count + list, queue counters, statistics
+  uint32_t* bitmap;   // [layers][words_per_layer]: drawable virtual pages of the active clipmaps
+  uint32_t* pagemap;  // [layers][n][n]: physical page coords (x | y << 16) of a drawable virtual page, else all ones
+  VsmBig* big_list;
+  uint32_t big_capacity;
+  uint2* clip_list;  // {triangle, clipmap}
+  uint32_t clip_capacity;
+  uint2* tile_list;  // {big list index, virtual page vy * n + vx}
+  uint32_t tile_capacity;
+};
+constexpr uint32_t kVsmDrawHeaderBytes = 1024;
+void launch_vsm_draw(const VsmDrawArgs& a, bool stats, uint32_t max_grid, hipStream_t s);
 // oxcull_bounds.hip: meshlet bounds producer
 void launch_build_meshlet_bounds(const float* pos, uint32_t vertex_count, const void* meshlets, uint32_t meshlet_count, const uint32_t* vidx,
                                  const uint8_t* micro, void* out_bounds, float* out_mesh6, void* out_qpos, float* meshlet_minmax, float* normals,

@@ -217,6 +217,24 @@ public:
   auto update_virtual_shadowmap(const oxc_vsm_update_context& context) -> void {
     check(oxc_update_virtual_shadowmap(ctx_, &context, stream_));
   }
+  // the shadow draw of draw_virtual_shadowmap (Passes/Shadowmaps.cpp:466-754: rmvsm_build_draw_commands + rmvsm_draw_physical_pages) for
+  // the compute-only backend: the triangles of the use_hpb cull (context.draw_geometry_cmd_buffer) into the dirty physical pages.
+  // Rules: include/oxcull.h, oxc_draw_physical_pages.
+  auto draw_physical_pages(oxc_vsm_draw_context context) -> void {
+    if (prepared_frame.use_mesh_shaders) throw std::runtime_error("draw_physical_pages: the mesh-shader path is not available on the compute-only backend");
+    oxc_prepared_frame f = {};
+    f.mesh_instance_count = prepared_frame.mesh_instance_count;
+    f.max_meshlet_instance_count = prepared_frame.max_meshlet_instance_count;
+    f.meshes_buffer = prepared_frame.meshes_buffer;
+    f.transforms_world_buffer = prepared_frame.transforms_world_buffer;
+    f.mesh_instances_buffer = prepared_frame.mesh_instances_buffer;
+    f.meshlet_instances_buffer = prepared_frame.meshlet_instances_buffer;
+    f.visible_meshlet_instances_indices_buffer = prepared_frame.visible_meshlet_instances_indices_buffer;
+    f.meshlet_instance_visibility_mask_buffer = prepared_frame.meshlet_instance_visibility_mask_buffer;
+    f.reordered_indices_buffer = prepared_frame.reordered_indices_buffer;
+    context.struct_size = sizeof context;
+    check(oxc_draw_physical_pages(ctx_, &f, &context, stream_));
+  }
   auto build_meshlet_bounds(oxc_meshlet_bounds_desc desc) -> void {
     desc.struct_size = sizeof desc;
     check(oxc_build_meshlet_bounds(ctx_, &desc, stream_));

@@ -28,6 +28,7 @@ STAGE_TRIANGLES = 4
 STAGE_ALL = 7
 
 TUNE_ASYNC_MTEST_BLOCKS_PER_CU, TUNE_ASYNC_TRI_BLOCKS_PER_CU, TUNE_RASTER_BIG_CAPACITY, TUNE_TRI_BLOCKS_PER_CU, TUNE_MV_EXPAND_ASYNC, TUNE_TRI_LOADS = 0, 1, 2, 3, 5, 7  # oxc_debug_set_tuning knobs
+TUNE_VSM_DRAW_STATS, TUNE_VSM_DRAW_CAPACITY = 8, 9
 
 
 class Buffer(C.Structure):
@@ -268,6 +269,26 @@ class VsmUpdateContext(C.Structure):
     ]
 
 
+class VsmDrawContext(C.Structure):
+    """oxc_vsm_draw_context (include/oxcull.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("wide_triangle_index", C.c_uint32),
+        ("page_size", C.c_int32),
+        ("page_table_size", C.c_int32),
+        ("physical_page_table_size", C.c_int32),
+        ("clipmap_count", C.c_int32),
+        ("draw_geometry_cmd_buffer", Buffer),
+        ("virtual_page_table", Buffer),
+        ("vsm_clipmaps_buffer", Buffer),
+        ("vsm_clipmap_dirty_flags_buffer", Buffer),
+        ("physical_page_image", Image),
+        ("draw_commands_buffer", Buffer),
+        ("draw_count_buffer", Buffer),
+        ("draw_clipmaps_buffer", Buffer),
+    ]
+
+
 # every symbol include/oxcull.h declares
 EXPORTS = [
     "oxc_abi_version",
@@ -299,6 +320,8 @@ EXPORTS = [
     "oxc_update_virtual_shadowmap",
     "oxc_cull_terrain",
     "oxc_draw_visbuffer",
+    "oxc_draw_physical_pages",
+    "oxc_debug_vsm_draw_stats",
     "oxc_comm_unique_id",
     "oxc_comm_init",
     "oxc_comm_destroy",
@@ -392,6 +415,8 @@ def load(path: str = None) -> C.CDLL:
     lib.oxc_broadcast_hiz_levels.argtypes = [vp, C.POINTER(Image), C.c_uint32, C.c_uint64, C.c_uint32, vp]
     lib.oxc_debug_project_aabb.argtypes = [vp, C.POINTER(C.c_float), C.c_float, vp, C.c_uint32, vp, vp]
     lib.oxc_draw_visbuffer.argtypes = [vp, C.POINTER(PreparedFrame), C.POINTER(DrawContext), vp]
+    lib.oxc_draw_physical_pages.argtypes = [vp, C.POINTER(PreparedFrame), C.POINTER(VsmDrawContext), vp]
+    lib.oxc_debug_vsm_draw_stats.argtypes = [vp, vp, vp]
     for name in EXPORTS:
         if name not in ("oxc_abi_version", "oxc_destroy", "oxc_last_error", "oxc_mesh_build_lod_count", "oxc_mesh_build_destroy"):
             getattr(lib, name).restype = C.c_int

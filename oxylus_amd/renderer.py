@@ -270,6 +270,58 @@ class VirtualShadowmapContext:
 
 
 @dataclass
+class VsmDrawContext:
+    """oxc_vsm_draw_context: the shadow draw of RendererInstance::draw_virtual_shadowmap (Shadowmaps.cpp:466-754).  `create` takes the shape and
+    the page buffers from a VirtualShadowmapContext and the triangle list from the shadow CullGeometryContext (its draw_geometry_cmd_buffer,
+    read when the draw is enqueued)."""
+    virtual_page_table: torch.Tensor              # int32 [clipmap_count, n, n]
+    vsm_clipmaps_buffer: torch.Tensor             # uint8 [clipmap_count * 76] GPU::VirtualClipmap records
+    vsm_clipmap_dirty_flags_buffer: torch.Tensor  # int32 [clipmap_count]
+    physical_page_image: ImageAttachment          # R32F, physical_page_table_size square (in/out)
+    page_size: int = 128
+    page_table_size: int = 64
+    physical_page_table_size: int = 8192
+    clipmap_count: int = 10
+    wide_triangle_index: int = 0
+    cull: Optional[CullGeometryContext] = None    # the use_hpb cull whose triangles are drawn
+    draw_cmd: Optional[torch.Tensor] = None       # int32 [5] VkDrawIndexedIndirectCommand: replaces the cull's own command
+    draw_commands_buffer: Optional[torch.Tensor] = None  # optional out: int32 [clipmap_count, 5]
+    draw_count_buffer: Optional[torch.Tensor] = None     # optional out: int32 [1]
+    draw_clipmaps_buffer: Optional[torch.Tensor] = None  # optional out: int32 [clipmap_count]
+
+    @staticmethod
+    def create(vsm: VirtualShadowmapContext, cull: Optional[CullGeometryContext] = None, physical_page_image: Optional[ImageAttachment] = None,
+               with_commands: bool = False) -> "VsmDrawContext":
+        img = physical_page_image if physical_page_image is not None else vsm.physical_page_image
+        assert img is not None, "the draw needs a physical_page_image"
+        k, dev = vsm.clipmap_count, vsm.virtual_page_table.device
+        cmds = dict(draw_commands_buffer=torch.zeros((k, 5), dtype=torch.int32, device=dev), draw_count_buffer=torch.zeros(1, dtype=torch.int32, device=dev),
+                    draw_clipmaps_buffer=torch.zeros(k, dtype=torch.int32, device=dev)) if with_commands else {}
+        return VsmDrawContext(vsm.virtual_page_table, vsm.vsm_clipmaps_buffer, vsm.vsm_clipmap_dirty_flags_buffer, img, page_size=vsm.page_size,
+                              page_table_size=vsm.page_table_size, physical_page_table_size=vsm.physical_page_table_size, clipmap_count=k,
+                              wide_triangle_index=int(cull.wide_triangle_index) if cull is not None else 0, cull=cull, **cmds)
+
+    def c(self) -> L.VsmDrawContext:
+        c = L.VsmDrawContext()
+        c.struct_size = C.sizeof(L.VsmDrawContext)
+        c.wide_triangle_index = int(self.wide_triangle_index)
+        c.page_size, c.page_table_size, c.physical_page_table_size = self.page_size, self.page_table_size, self.physical_page_table_size
+        c.clipmap_count = self.clipmap_count
+        if self.draw_cmd is not None:
+            c.draw_geometry_cmd_buffer = _buf(self.draw_cmd)
+        elif self.cull is not None:
+            c.draw_geometry_cmd_buffer = self.cull._c.draw_geometry_cmd_buffer
+        c.virtual_page_table = _buf(self.virtual_page_table)
+        c.vsm_clipmaps_buffer = _buf(self.vsm_clipmaps_buffer)
+        c.vsm_clipmap_dirty_flags_buffer = _buf(self.vsm_clipmap_dirty_flags_buffer)
+        c.physical_page_image = self.physical_page_image.c()
+        c.draw_commands_buffer = _buf(self.draw_commands_buffer)
+        c.draw_count_buffer = _buf(self.draw_count_buffer)
+        c.draw_clipmaps_buffer = _buf(self.draw_clipmaps_buffer)
+        return c
+
+
+@dataclass
 class MainGeometryContext:
     """The fields generate_hiz uses (RendererInstance.hpp:199-216)."""
     depth_attachment: ImageAttachment
@@ -468,6 +520,23 @@ class RendererInstance:
             d.visbuffer_attachment = L.Buffer(C.c_void_p(visbuffer.data_ptr()), visbuffer.numel() * 4)
         self._keep = (visdepth, depth, visbuffer, draw_cmd)
         self._check(self._lib.oxc_draw_visbuffer(self._ctx, C.byref(f), C.byref(d), self._stream(stream)))
+
+    def draw_physical_pages(self, context: VsmDrawContext, stream=None):
+        """Shadowmaps.cpp:466-754 (rmvsm_build_draw_commands + rmvsm_draw_physical_pages): rasterise the shadow cull's triangles once per
+        dirty clipmap into the dirty physical pages of `context.physical_page_image` (include/oxcull.h, oxc_draw_physical_pages)."""
+        assert self.prepared_frame is not None
+        f = self.prepared_frame.c()
+        c = context.c()
+        self._keep = context
+        self._check(self._lib.oxc_draw_physical_pages(self._ctx, C.byref(f), C.byref(c), self._stream(stream)))
+
+    def debug_vsm_draw_stats(self, stream=None) -> dict:
+        """What the last draw_physical_pages did (measurement hook; synchronises).  `pairs` / `fragments` are counted only with
+        debug_set_tuning(L.TUNE_VSM_DRAW_STATS, 1)."""
+        out = (C.c_uint32 * 8)()
+        self._check(self._lib.oxc_debug_vsm_draw_stats(self._ctx, C.cast(out, C.c_void_p), self._stream(stream)))
+        names = ("pairs", "fragments", "big_pairs", "big_pairs_overflowed", "tiles", "tiles_overflowed", "clipped_pairs", "clipped_pairs_overflowed")
+        return {k: int(v) for k, v in zip(names, out)}
 
     def debug_raster_stats(self, stream=None) -> dict:
         """What the last draw_visbuffer did with its triangles (test hook; synchronises)."""
