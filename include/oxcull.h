@@ -578,6 +578,86 @@ typedef struct oxc_vsm_draw_context {
 
 oxc_status oxc_draw_physical_pages(oxc_ctx* ctx, const oxc_prepared_frame* frame, const oxc_vsm_draw_context* context, void* hip_stream);
 
+/* ---- VSM shadow resolve: the PCSS light-visibility term from the physical pages ----------------------------------
+ * Replaces RendererInstance::resolve_shadowmap (Oxylus/src/Render/Passes/Shadowmaps.cpp:756-822, pipeline resolve_shadowmaps,
+ * passes/resolve_shadowmaps.slang), the consumer of oxc_update_virtual_shadowmap -> oxc_cull_geometry(use_hpb) -> oxc_draw_physical_pages:
+ * one thread per pixel of the main view, one R32F value per pixel, every pixel written.  The reference draws a full-screen triangle to get
+ * that thread; nothing else of the graphics pipeline is used.
+ * Arithmetic: binary32, no contraction, IEEE division and square root, the Slang's evaluation order; mul(M, v), dot, length and normalize
+ * as SURVEY.md A.0 / DESIGN.md section 2 define them; cross(a, b).x = a.y * b.z - a.z * b.y and its rotations (y: a.z * b.x - a.x * b.z,
+ * z: a.x * b.y - a.y * b.x), each product rounded before the subtraction; max(a, b) / min(a, b) are fmaxf / fminf (a NaN operand gives the
+ * other one); lerp(a, b, t) = a + (b - a) * t; fract(x) = x - floor(x).  The reference is compiled fast-math and is not bit-defined: this is
+ * the one evaluation the device and the checker (tests/vsm_resolve_model.py) both follow.
+ *   1. sky     depth == 0.0 gives 1.0 (a NaN depth is not sky).
+ *   2. set-up  uv = (float2(x, y) + 0.5) / extent of the depth image;  world = unproject(uv, depth) and base = the clipmap index, both
+ *              exactly as in oxc_update_virtual_shadowmap's mark pass (same footprint o = (1.0 / resolution) * 0.5, texel_len, thresholds);
+ *              e = (.b, .a) of the normal texel, binary16 -> binary32 (exact, denormals kept);  oct_to_vec3(e): v = (e.x, e.y,
+ *              (1.0 - |e.x|) - |e.y|), s = (e.x >= 0 ? 1 : -1, e.y >= 0 ? 1 : -1) (a NaN gives -1), when v.z < 0: v.xy = ((1.0 - |e.y|) * s.x,
+ *              (1.0 - |e.x|) * s.y); normalize(v);  flat_N = normalize(oct_to_vec3(e)) (two normalisations, as the Slang).
+ *   3. pcss    L = directional_light_dir;  NoL = max(dot(N, L), 0.0);  cts = exp2(base + 1) * texel_len (an exact power of two times
+ *              texel_len);  b = (1.41421356f * cts) * 0.5;  base_bias = (2^-22 + b) + (NoL < 0.99f ? (b * length(cross(N, L))) / max(NoL, 0.1f)
+ *              : b);  inv_z = 1.0 / z_length;  P = world + N * (cts * (1.0 + 2.0 * (1.0 - NoL)));  tangent basis of L alone (computed once
+ *              per call): axis = |L.y| < 0.999f ? (0, 1, 0) : (1, 0, 0), T = normalize(cross(axis, L)), B = cross(L, T);
+ *              d_recv = (M_base (P, 1)).z / .w, d_recv_world = d_recv * z_length;  centre = tap(P).
+ *              Blocker search, i = 0..15: xi = fract(hammersley2d(i, 16) + noise);  r = sqrt(xi.x) * 0.1f;  (c, s) = rotation(xi.y);
+ *              offset = r * (T * c + B * s);  bias = inv_z * (base_bias + lerp(2.0 * r, 0.0, NoL));  d = tap(P + offset);  a miss is skipped;
+ *              else valid += 1 and, when d + bias < d_recv, accum += d * z_length and blockers += 1.
+ *              hard = centre missed ? 1.0 : (centre + inv_z * base_bias < d_recv ? 0.0 : 1.0).
+ *              valid == 0 returns hard; blockers == 0 returns 1.0; blockers == valid returns 0.0.
+ *              pcf_radius = min(0.1f, (d_recv_world - accum / f32(blockers)) * 0.002f).
+ *              PCF, i = 0..23: the same with hammersley2d(i, 24) + noise.yx and r = sqrt(xi.x) * pcf_radius;  a hit adds 1 to
+ *              valid_pcf and, when d + bias >= d_recv, 1.0 to light_visibility.
+ *   4. tap     (sample_vsm_shadow_depth_with_fallback) the clipmaps base, base - 1, base + 1 in that order; the first that does not miss
+ *              gives the depth.  For clipmap c: an index outside [0, clipmap_count) is a miss;  h = M_c (p, 1), clip_uv = (h.xy / h.w + 1.0)
+ *              * 0.5 (get_clipmap_info, rmvsm.slang:214-221); a clip_uv outside [0, 1], or NaN, is a miss;  page = int(floor(clip_uv *
+ *              float(n))), a page outside [0, n - 1] is a miss;  wrapped = floor_mod(page + page_offset, n);  an entry that is not Backed is
+ *              a miss (Visible and Dirty are not consulted), so is one whose address addr = e >> 16 is >= P * P (P = physical_page_table_size /
+ *              page_size): it names no physical page and is never loaded;  in-page texel = int(floor(clip_uv * float(V))) % page_size,
+ *              V = page_table_size * page_size;  the value is physical_page_image at (addr % P, addr / P) * page_size + in-page texel;  a
+ *              stored value equal to -1.0 (the Slang's VSM_DEPTH_MISS) is a miss as well.
+ *              Stated difference: the reference multiplies clip_uv by the PHYSICAL extent for the in-page texel; its two extents are both
+ *              8192.  V is the viewport oxc_draw_physical_pages rasterises with, so a tap reads the texel the draw wrote for every shape.
+ *   5. noise   Stated difference: the reference's hash2 is fract(sin(dot(p, k)) * 43758.5453) on arguments near 10^6, which under fast-math
+ *              is not reproducible between two devices.  Here h = pcg2d(x, y) on the u32 pixel coordinate, all operations modulo 2^32:
+ *              v = v * 1664525 + 1013904223 (both components); v.x += v.y * 1664525; v.y += v.x * 1664525; v ^= v >> 16 (both); v.x += v.y *
+ *              1664525; v.y += v.x * 1664525; v ^= v >> 16 (both);  noise = (f32(h.x >> 8), f32(h.y >> 8)) * 2^-24, in [0, 1).
+ *              hammersley2d(i, N) = (f32(i) / f32(N), f32(reversebits(i)) * 2^-32).
+ *   6. rotation  Stated difference: (cos, sin) of xi.y * TAU cannot be matched through a library sin.  For t = xi.y (a binary32 in [0, 1)):
+ *              q = 4 t (exact), k = floor(q), f = q - k (exact);  f > 0.5: g = 1.0 - f (exact) and the pair below is swapped, else g = f;
+ *              in binary64, no contraction: a = (double)g * 0x1.921fb54442d18p+0, z = a * a,
+ *                sin = a + (a * z) * (((0x1.71de3a556c734p-19 * z + -0x1.a01a01a01a01ap-13) * z + 0x1.1111111111111p-7) * z + -0x1.5555555555555p-3),
+ *                cos = 1.0 + z * ((((-0x1.27e4fb7789f5cp-22 * z + 0x1.a01a01a01a01ap-16) * z + -0x1.6c16c16c16c17p-10) * z + 0x1.5555555555555p-5) * z
+ *                      + -0x1.0000000000000p-1),
+ *              each rounded to binary32 once (S, C; swapped when f > 0.5);  (c, s) = (C, S), (-S, C), (-C, -S), (S, -C) for k = 0..3.
+ *              Each component is within 2^-23 of the exact value (tests/test_vsm_resolve_model.py).
+ *   7. result  0.0, 1.0, hard, or light_visibility / f32(valid_pcf) (valid_pcf == 0 returns hard).
+ * Limits (else OXC_INVALID_ARG): the shape limits of oxc_update_virtual_shadowmap; depth_attachment and resolved_shadows_attachment one
+ * R32F level each, of the same extent (at most 65536 a side); normal_attachment 8-byte aligned with one u16x4 per pixel; physical_page_image
+ * one R32F level of exactly physical_page_table_size^2.  One launch, no scratch, no allocation, no host synchronisation; capturable into a
+ * HIP graph. */
+typedef struct oxc_shadow_resolve_context {
+  uint32_t struct_size; /* sizeof(oxc_shadow_resolve_context) */
+  /* the GPU::VSMContext fields the pass reads (rmvsm.slang:116-127) */
+  int32_t page_size, page_table_size, physical_page_table_size, clipmap_count; /* as in oxc_vsm_update_context */
+  float first_clipmap_width;
+  float clipmap_selection_bias;
+  float virtual_extent;
+  float z_length;                 /* the reference sets max_shadow_dist * 2 */
+  float directional_light_dir[3];
+  /* the GPU::Camera fields the pass reads */
+  float inv_projection_view[16];  /* column-major */
+  float resolution[2];
+  oxc_image depth_attachment;     /* in: R32F, levels = 1, reversed Z, 0 = nothing drawn */
+  oxc_buffer normal_attachment;   /* in: the R16G16B16A16Sfloat normal image (RendererInstance.cpp:709-716) as linear u16x4[height][width];
+                                     only .b and .a are read: the octahedral world normal visbuffer_decode writes */
+  oxc_buffer vsm_clipmaps_buffer; /* in: oxc_virtual_clipmap[clipmap_count] */
+  oxc_buffer virtual_page_table;  /* in: u32 [clipmap_count][n][n] */
+  oxc_image physical_page_image;  /* in: R32F, levels = 1, physical_page_table_size square */
+  oxc_image resolved_shadows_attachment; /* out: R32F, levels = 1, the extent of the depth image */
+} oxc_shadow_resolve_context;
+
+oxc_status oxc_resolve_shadowmap(oxc_ctx* ctx, const oxc_shadow_resolve_context* context, void* hip_stream);
+
 /* ---- terrain patch cull ---------------------------------------------------------
  * Replaces RendererInstance::cull_terrain (Oxylus/src/Render/Passes/Terrain.cpp:159-216) + pipeline
  * terrain_cull (Shaders/passes/terrain_cull.slang:17-83): one thread per patch, world-space AABB from the

@@ -83,7 +83,8 @@ enum { OXC_TUNE_ASYNC_MTEST_BLOCKS_PER_CU = 0, OXC_TUNE_ASYNC_TRI_BLOCKS_PER_CU 
        OXC_TUNE_VSM_DRAW_CAPACITY = 9 /* entries of oxc_draw_physical_pages' big-pair / clip queues (default: every (triangle, clipmap)
                                          pair of the frame's index buffer, 4096..2^24, growing with the frame; the tile queue holds 2x
                                          as many); fixed, only before the context's first shadow draw -- the tests shrink it to reach
-                                         the overflow paths */ };
+                                         the overflow paths */,
+       OXC_TUNE_VSM_RESOLVE_STATS = 10 /* 1: oxc_resolve_shadowmap runs its counting instantiation (oxc_debug_vsm_resolve_stats); 0 (default): off */ };
 oxc_status oxc_debug_set_tuning(oxc_ctx* ctx, uint32_t knob, uint32_t value);
 
 /* Measurement aid: counters_dptr != NULL -- the HiZ calls (use_hiz + OXC_CULL_TEST_OCCLUSION) that follow on this context run counting
@@ -104,6 +105,12 @@ oxc_status oxc_debug_raster_stats(oxc_ctx* ctx, uint32_t* host_out4, void* hip_s
  * crossed a clip plane, of those the ones the clip queue could not hold (found again by its overflow pass)}.  The first two are counted
  * only after oxc_debug_set_tuning(OXC_TUNE_VSM_DRAW_STATS, 1) (a counting instantiation of the kernels, same image, slower); 0 otherwise. */
 oxc_status oxc_debug_vsm_draw_stats(oxc_ctx* ctx, uint32_t* host_out8, void* hip_stream);
+
+/* Measurement hook: what the last oxc_resolve_shadowmap on this context did, counted by a counting instantiation of its kernel (same
+ * image, slower) after oxc_debug_set_tuning(OXC_TUNE_VSM_RESOLVE_STATS, 1); synchronises the stream.
+ * out8 = {non-sky pixels, taps taken (one per sample position), taps no clipmap served, taps served by clipmap base - 1, by base + 1,
+ * pixels that returned the hard-shadow value, the "no blocker" 1.0, the "all blockers" 0.0}. */
+oxc_status oxc_debug_vsm_resolve_stats(oxc_ctx* ctx, uint32_t* host_out8, void* hip_stream);
 
 #ifdef __cplusplus
 }

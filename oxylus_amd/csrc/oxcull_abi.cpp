@@ -82,6 +82,8 @@ struct oxc_ctx {
   uint32_t vsm_draw_capacity = 0;          // entries of the big-pair and clip queues of that scratch (the tile queue holds 4x as many)
   uint32_t vsm_draw_capacity_request = 0;  // oxc_debug_set_tuning(OXC_TUNE_VSM_DRAW_CAPACITY): used by the first shadow draw
   bool vsm_draw_stats = false;             // oxc_debug_set_tuning(OXC_TUNE_VSM_DRAW_STATS): counting kernels
+  uint32_t* vsm_resolve_stats = nullptr;   // oxc_resolve_shadowmap with OXC_TUNE_VSM_RESOLVE_STATS: u32[8] the counting kernel adds to
+  bool vsm_resolve_stats_on = false;
   void* comm = nullptr;           // ncclComm_t (oxc_comm_init)
   uint32_t comm_rank = 0, comm_world = 0;
   // counter slots
@@ -484,6 +486,7 @@ void oxc_destroy(oxc_ctx* ctx) {
   if (ctx->raster_rows) (void)hipFree(ctx->raster_rows);
   if (ctx->vsm_scratch) (void)hipFree(ctx->vsm_scratch);
   if (ctx->vsm_draw_scratch) (void)hipFree(ctx->vsm_draw_scratch);
+  if (ctx->vsm_resolve_stats) (void)hipFree(ctx->vsm_resolve_stats);
   if (ctx->comm) (void)oxc_comm_destroy(ctx);
   if (ctx->slots) (void)hipFree(ctx->slots);
   if (ctx->order_event) (void)hipEventDestroy(ctx->order_event);
@@ -1469,6 +1472,26 @@ oxc_status oxc_generate_hpb(oxc_ctx* ctx, oxc_buffer page_table, const oxc_image
   return OXC_OK;
 }
 
+}  // extern "C"
+// The clipmap index without log2 (include/oxcull.h, mark visible pages): k < *always has (double)k - (double)bias < 0 and always counts;
+// k >= *always counts when r > thr[k], the largest binary32 <= exp2(k - bias) -- (double)r > T <=> r > that value, r being a binary32.
+static void vsm_level_thresholds(int layers, float bias, uint32_t* always, float* thr) {
+  *always = 0;
+  for (int k = 0; k + 1 < layers; k++) {
+    const double dk = (double)k - (double)bias;
+    if (dk < 0.0) {
+      *always = (uint32_t)(k + 1);
+      thr[k] = 0.0f;
+      continue;
+    }
+    const double T = std::exp2(dk);
+    float f = (float)T;
+    if ((double)f > T) f = std::nextafter(f, -INFINITY);
+    thr[k] = f;
+  }
+}
+extern "C" {
+
 oxc_status oxc_update_virtual_shadowmap(oxc_ctx* ctx, const oxc_vsm_update_context* c, void* hip_stream) {
   if (!ctx) return OXC_INVALID_ARG;
   if (!c || c->struct_size != sizeof(oxc_vsm_update_context)) return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: bad context / struct_size");
@@ -1566,20 +1589,7 @@ oxc_status oxc_update_virtual_shadowmap(oxc_ctx* ctx, const oxc_vsm_update_conte
   const float scale_ratio = (float)(n - 1) / (float)n;  // get_first_clipmap_texel_length, rmvsm.slang:148-155
   const float effective_width = c->first_clipmap_width * scale_ratio;
   a.texel_len = (effective_width * 2.0f) / c->virtual_extent;
-  a.lvl_always = 0;
-  for (int k = 0; k + 1 < layers; k++) {
-    const double dk = (double)k - (double)c->clipmap_selection_bias;
-    if (dk < 0.0) {
-      a.lvl_always = (uint32_t)(k + 1);
-      a.lvl_thr[k] = 0.0f;
-      continue;
-    }
-    // (double)r > T  <=>  r > the largest binary32 <= T (r is a binary32)
-    const double T = std::exp2(dk);
-    float f = (float)T;
-    if ((double)f > T) f = std::nextafter(f, -INFINITY);
-    a.lvl_thr[k] = f;
-  }
+  vsm_level_thresholds(layers, c->clipmap_selection_bias, &a.lvl_always, a.lvl_thr);
   {
     KernelTimer t(ctx, OXC_K_VSM_UPDATE, s);
     launch_vsm_update(a, ctx->num_cus, static_cast<uint8_t*>(h.dptr), h.levels, h.level_offset, s);
@@ -1700,6 +1710,96 @@ oxc_status oxc_draw_physical_pages(oxc_ctx* ctx, const oxc_prepared_frame* f, co
   a.tile_list = reinterpret_cast<uint2*>(sc + o_tile);
   a.tile_capacity = cap * 2u;
   launch_vsm_draw(a, ctx->vsm_draw_stats, ctx->num_cus * 8, s);
+  OXC_HIP(ctx, hipGetLastError());
+  return OXC_OK;
+}
+
+oxc_status oxc_resolve_shadowmap(oxc_ctx* ctx, const oxc_shadow_resolve_context* c, void* hip_stream) {
+  if (!ctx) return OXC_INVALID_ARG;
+  if (!c || c->struct_size != sizeof(oxc_shadow_resolve_context)) return fail(ctx, OXC_INVALID_ARG, "resolve_shadowmap: bad context / struct_size");
+  const int32_t n = c->page_table_size, ps = c->page_size, phys = c->physical_page_table_size, layers = c->clipmap_count;
+  if (layers < 1 || layers > 16) return fail(ctx, OXC_INVALID_ARG, "resolve_shadowmap: clipmap_count must be 1..16");
+  if (n < 8 || n > 256 || n % 8) return fail(ctx, OXC_INVALID_ARG, "resolve_shadowmap: page_table_size must be a multiple of 8 in [8, 256]");
+  if (ps < 16 || ps % 16 || phys < ps || phys % ps) return fail(ctx, OXC_INVALID_ARG, "resolve_shadowmap: page_size must be a multiple of 16 and divide physical_page_table_size");
+  const uint32_t P = (uint32_t)(phys / ps);
+  if ((uint64_t)P * P > 65536u) return fail(ctx, OXC_INVALID_ARG, "resolve_shadowmap: more than 65536 physical pages (16 address bits)");
+  const oxc_image& dimg = c->depth_attachment;
+  const oxc_image& oimg = c->resolved_shadows_attachment;
+  const uint64_t pixels = (uint64_t)dimg.width * dimg.height;
+  if (dimg.width > 65536u || dimg.height > 65536u) return fail(ctx, OXC_INVALID_ARG, "resolve_shadowmap: depth extent beyond 65536");
+  if (pixels && (!dimg.dptr || dimg.levels != 1 || dimg.level_offset[0] != 0))
+    return fail(ctx, OXC_INVALID_ARG, "resolve_shadowmap: depth_attachment must be one R32F level at offset 0");
+  if (oimg.width != dimg.width || oimg.height != dimg.height || (pixels && (!oimg.dptr || oimg.levels != 1 || oimg.level_offset[0] != 0)))
+    return fail(ctx, OXC_INVALID_ARG, "resolve_shadowmap: resolved_shadows_attachment must be one R32F level of the depth attachment's extent");
+  if (pixels && (!c->normal_attachment.dptr || c->normal_attachment.bytes < pixels * 8u || (reinterpret_cast<uintptr_t>(c->normal_attachment.dptr) & 7u)))
+    return fail(ctx, OXC_INVALID_ARG, "resolve_shadowmap: normal_attachment must be 8-byte aligned u16x4 texels of the depth attachment's extent");
+  const uint64_t entries = (uint64_t)layers * n * n;
+  if (!c->virtual_page_table.dptr || c->virtual_page_table.bytes < entries * 4u) return fail(ctx, OXC_INVALID_ARG, "resolve_shadowmap: virtual_page_table smaller than clipmap_count * n * n u32");
+  if (!c->vsm_clipmaps_buffer.dptr || c->vsm_clipmaps_buffer.bytes < (uint64_t)layers * sizeof(oxc_virtual_clipmap))
+    return fail(ctx, OXC_INVALID_ARG, "resolve_shadowmap: vsm_clipmaps_buffer smaller than clipmap_count records");
+  const oxc_image& pimg = c->physical_page_image;
+  if (!pimg.dptr || pimg.width != (uint32_t)phys || pimg.height != (uint32_t)phys || pimg.levels != 1 || pimg.level_offset[0] != 0)
+    return fail(ctx, OXC_INVALID_ARG, "resolve_shadowmap: physical_page_image must be one R32F level of physical_page_table_size^2");
+  OXC_HIP(ctx, hipSetDevice(ctx->device));
+  OXC_ORDER(ctx, hip_stream);
+  const hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  if (!pixels) return OXC_OK;
+  VsmResolveArgs a;
+  std::memset(&a, 0, sizeof a);
+  if (ctx->vsm_resolve_stats_on) {
+    if (!ctx->vsm_resolve_stats) {
+      if (stream_is_capturing(s)) return fail(ctx, OXC_INVALID_ARG, "resolve_shadowmap: the counters are allocated by the first counting call; make one outside the capture");
+      hipError_t e = hipMalloc(reinterpret_cast<void**>(&ctx->vsm_resolve_stats), 32);
+      if (e != hipSuccess) return fail(ctx, OXC_OUT_OF_MEMORY, "hipMalloc(vsm resolve counters)", e);
+    }
+    OXC_HIP(ctx, hipMemsetAsync(ctx->vsm_resolve_stats, 0, 32, s));
+    a.stats = ctx->vsm_resolve_stats;
+  }
+  a.depth = static_cast<const float*>(dimg.dptr);
+  a.normal = static_cast<const uint32_t*>(c->normal_attachment.dptr);
+  a.out = static_cast<float*>(oimg.dptr);
+  a.w = dimg.width;
+  a.h = dimg.height;
+  a.clipmaps = static_cast<const float*>(c->vsm_clipmaps_buffer.dptr);
+  a.page_table = static_cast<const uint32_t*>(c->virtual_page_table.dptr);
+  a.physical = static_cast<const float*>(pimg.dptr);
+  a.n = (uint32_t)n;
+  a.layers = (uint32_t)layers;
+  a.page_size = (uint32_t)ps;
+  a.phys_side = P;
+  a.phys_count = P * P;
+  a.physical_size = (uint32_t)phys;
+  a.fn = (float)n;
+  a.fV = (float)((int64_t)n * ps);
+  // per-call constants, binary32 in the Slang's order (include/oxcull.h)
+  for (int k = 0; k < 16; k++) a.inv_pv[k] = c->inv_projection_view[k];
+  a.off_x = (1.0f / c->resolution[0]) * 0.5f;
+  a.off_y = (1.0f / c->resolution[1]) * 0.5f;
+  const float scale_ratio = (float)(n - 1) / (float)n;  // get_first_clipmap_texel_length, rmvsm.slang:148-155
+  const float effective_width = c->first_clipmap_width * scale_ratio;
+  a.texel_len = (effective_width * 2.0f) / c->virtual_extent;
+  vsm_level_thresholds(layers, c->clipmap_selection_bias, &a.lvl_always, a.lvl_thr);
+  {  // perpendicular_basis(L): t = normalize(cross(axis, L)), bitangent = cross(L, t)
+    const float* L = c->directional_light_dir;
+    const float ax = std::fabs(L[1]) < 0.999f ? 0.0f : 1.0f, ay = std::fabs(L[1]) < 0.999f ? 1.0f : 0.0f, az = 0.0f;
+    const float cx = ay * L[2] - az * L[1], cy = az * L[0] - ax * L[2], cz = ax * L[1] - ay * L[0];
+    const float len = std::sqrt((cx * cx + cy * cy) + cz * cz);
+    const float t[3] = {cx / len, cy / len, cz / len};
+    for (int k = 0; k < 3; k++) a.light[k] = L[k], a.tangent[k] = t[k];
+    a.bitangent[0] = L[1] * t[2] - L[2] * t[1];
+    a.bitangent[1] = L[2] * t[0] - L[0] * t[2];
+    a.bitangent[2] = L[0] * t[1] - L[1] * t[0];
+  }
+  a.z_length = c->z_length;
+  a.inv_z_length = 1.0f / c->z_length;
+  for (uint32_t i = 0; i < 40; i++) {  // hammersley2d(i, N) = (f32(i) / f32(N), f32(reversebits(i)) * 2^-32)
+    const uint32_t k = i < 16 ? i : i - 16;
+    uint32_t rev = 0;
+    for (int bit = 0; bit < 32; bit++) rev |= ((k >> bit) & 1u) << (31 - bit);
+    a.ham[i][0] = (float)k / (i < 16 ? 16.0f : 24.0f);
+    a.ham[i][1] = (float)rev * 0x1p-32f;
+  }
+  launch_vsm_resolve(a, s);
   OXC_HIP(ctx, hipGetLastError());
   return OXC_OK;
 }
@@ -2025,6 +2125,7 @@ oxc_status oxc_debug_set_tuning(oxc_ctx* ctx, uint32_t knob, uint32_t value) {
       ctx->raster_capacity_request = value;
       return OXC_OK;
     case OXC_TUNE_VSM_DRAW_STATS: ctx->vsm_draw_stats = value != 0u; return OXC_OK;
+    case OXC_TUNE_VSM_RESOLVE_STATS: ctx->vsm_resolve_stats_on = value != 0u; return OXC_OK;
     case OXC_TUNE_VSM_DRAW_CAPACITY:
       if (ctx->vsm_draw_scratch) return fail(ctx, OXC_INVALID_ARG, "set_tuning: the shadow draw's scratch is allocated by the first oxc_draw_physical_pages; set its capacity before");
       ctx->vsm_draw_capacity_request = value;
@@ -2094,6 +2195,18 @@ oxc_status oxc_debug_vsm_draw_stats(oxc_ctx* ctx, uint32_t* host_out8, void* hip
   host_out8[5] = beyond(h[64], cap * 2u);
   host_out8[6] = h[96];   // pairs that crossed a clip plane
   host_out8[7] = beyond(h[96], cap);
+  return OXC_OK;
+}
+
+oxc_status oxc_debug_vsm_resolve_stats(oxc_ctx* ctx, uint32_t* host_out8, void* hip_stream) {
+  if (!ctx) return OXC_INVALID_ARG;
+  if (!host_out8) return fail(ctx, OXC_INVALID_ARG, "debug_vsm_resolve_stats: null pointer");
+  if (!ctx->vsm_resolve_stats) return fail(ctx, OXC_INVALID_ARG, "debug_vsm_resolve_stats: no counting oxc_resolve_shadowmap call on this context yet");
+  OXC_HIP(ctx, hipSetDevice(ctx->device));
+  OXC_ORDER(ctx, hip_stream);
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  OXC_HIP(ctx, hipMemcpyAsync(host_out8, ctx->vsm_resolve_stats, 32, hipMemcpyDeviceToHost, s));
+  OXC_HIP(ctx, hipStreamSynchronize(s));
   return OXC_OK;
 }
 

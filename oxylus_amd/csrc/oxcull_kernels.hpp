@@ -536,6 +536,29 @@ struct VsmDrawArgs {
 };
 constexpr uint32_t kVsmDrawHeaderBytes = 1024;
 void launch_vsm_draw(const VsmDrawArgs& a, bool stats, uint32_t max_grid, hipStream_t s);
+// oxcull_vsm_resolve.hip: the VSM shadow resolve (oxc_resolve_shadowmap)
+struct VsmResolveArgs {
+  const float* depth;        // [h][w]
+  const uint32_t* normal;    // u16x4 [h][w] as two words per pixel: {r | g << 16, b | a << 16}
+  float* out;                // [h][w]
+  uint32_t w, h;
+  const float* clipmaps;       // GPU::VirtualClipmap[layers], 19 words each
+  const uint32_t* page_table;  // [layers][n][n]
+  const float* physical;       // physical_size x physical_size R32F
+  uint32_t n, layers, page_size, phys_side, phys_count, physical_size;  // phys_side = P = physical_page_table_size / page_size
+  float fn, fV;                // float(n), float(n * page_size)
+  uint32_t* stats;             // nullptr, or u32[8] the counting instantiation adds to (oxc_debug_vsm_resolve_stats)
+  // per-call constants, computed once on the host in binary32 / binary64 by the rules of include/oxcull.h
+  float inv_pv[16];
+  float off_x, off_y;  // (1.0 / resolution) * 0.5
+  float texel_len;
+  uint32_t lvl_always;  // as VsmArgs
+  float lvl_thr[16];
+  float light[3], tangent[3], bitangent[3];  // L and perpendicular_basis(L)
+  float z_length, inv_z_length;
+  float ham[40][2];  // hammersley2d(i, 16), i < 16, then hammersley2d(i, 24), i < 24
+};
+void launch_vsm_resolve(const VsmResolveArgs& a, hipStream_t s);
 // oxcull_bounds.hip: meshlet bounds producer
 void launch_build_meshlet_bounds(const float* pos, uint32_t vertex_count, const void* meshlets, uint32_t meshlet_count, const uint32_t* vidx,
                                  const uint8_t* micro, void* out_bounds, float* out_mesh6, void* out_qpos, float* meshlet_minmax, float* normals,

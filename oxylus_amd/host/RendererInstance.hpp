@@ -106,6 +106,10 @@ struct MainGeometryContext {
   uint32_t wide_triangle_index = 0;
 };
 
+// What resolve_shadowmap reads and writes (Passes/Shadowmaps.cpp:756-822): the GPU::VSMContext and GPU::Camera fields, the main view's depth
+// and normal images, the clipmaps, the page table, the physical pages, and the R32F resolved_shadows_attachment.
+using ShadowResolveContext = oxc_shadow_resolve_context;
+
 class RendererInstance {
 public:
   explicit RendererInstance(int device = 0, void* hip_stream = nullptr) : stream_(hip_stream) {
@@ -234,6 +238,13 @@ public:
     f.reordered_indices_buffer = prepared_frame.reordered_indices_buffer;
     context.struct_size = sizeof context;
     check(oxc_draw_physical_pages(ctx_, &f, &context, stream_));
+  }
+  // RendererInstance::resolve_shadowmap (Passes/Shadowmaps.cpp:756-822, pipeline resolve_shadowmaps): the PCSS light-visibility value of
+  // every pixel from the page table and the physical pages, directly after the shadow draw (RendererInstance.cpp:974-985).
+  // Rules: include/oxcull.h, oxc_resolve_shadowmap.
+  auto resolve_shadowmap(ShadowResolveContext context) -> void {
+    context.struct_size = sizeof context;
+    check(oxc_resolve_shadowmap(ctx_, &context, stream_));
   }
   auto build_meshlet_bounds(oxc_meshlet_bounds_desc desc) -> void {
     desc.struct_size = sizeof desc;

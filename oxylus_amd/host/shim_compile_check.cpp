@@ -39,5 +39,10 @@ int main(int argc, char**) {
     std::printf("expected (no attachments bound): %s\n", e.what());
   }
   run_geometry_pass(true);
+  try {  // RendererInstance.cpp:974-985: the shadow term, after draw_virtual_shadowmap
+    self.resolve_shadowmap(ShadowResolveContext{});
+  } catch (const std::exception& e) {
+    std::printf("expected (no attachments bound): %s\n", e.what());
+  }
   return 0;
 }

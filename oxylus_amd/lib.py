@@ -28,7 +28,7 @@ STAGE_TRIANGLES = 4
 STAGE_ALL = 7
 
 TUNE_ASYNC_MTEST_BLOCKS_PER_CU, TUNE_ASYNC_TRI_BLOCKS_PER_CU, TUNE_RASTER_BIG_CAPACITY, TUNE_TRI_BLOCKS_PER_CU, TUNE_MV_EXPAND_ASYNC, TUNE_TRI_LOADS = 0, 1, 2, 3, 5, 7  # oxc_debug_set_tuning knobs
-TUNE_VSM_DRAW_STATS, TUNE_VSM_DRAW_CAPACITY = 8, 9
+TUNE_VSM_DRAW_STATS, TUNE_VSM_DRAW_CAPACITY, TUNE_VSM_RESOLVE_STATS = 8, 9, 10
 
 
 class Buffer(C.Structure):
@@ -289,6 +289,30 @@ class VsmDrawContext(C.Structure):
     ]
 
 
+class ShadowResolveContext(C.Structure):
+    """oxc_shadow_resolve_context (include/oxcull.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("page_size", C.c_int32),
+        ("page_table_size", C.c_int32),
+        ("physical_page_table_size", C.c_int32),
+        ("clipmap_count", C.c_int32),
+        ("first_clipmap_width", C.c_float),
+        ("clipmap_selection_bias", C.c_float),
+        ("virtual_extent", C.c_float),
+        ("z_length", C.c_float),
+        ("directional_light_dir", C.c_float * 3),
+        ("inv_projection_view", C.c_float * 16),
+        ("resolution", C.c_float * 2),
+        ("depth_attachment", Image),
+        ("normal_attachment", Buffer),
+        ("vsm_clipmaps_buffer", Buffer),
+        ("virtual_page_table", Buffer),
+        ("physical_page_image", Image),
+        ("resolved_shadows_attachment", Image),
+    ]
+
+
 # every symbol include/oxcull.h declares
 EXPORTS = [
     "oxc_abi_version",
@@ -322,6 +346,8 @@ EXPORTS = [
     "oxc_draw_visbuffer",
     "oxc_draw_physical_pages",
     "oxc_debug_vsm_draw_stats",
+    "oxc_resolve_shadowmap",
+    "oxc_debug_vsm_resolve_stats",
     "oxc_comm_unique_id",
     "oxc_comm_init",
     "oxc_comm_destroy",
@@ -417,6 +443,8 @@ def load(path: str = None) -> C.CDLL:
     lib.oxc_draw_visbuffer.argtypes = [vp, C.POINTER(PreparedFrame), C.POINTER(DrawContext), vp]
     lib.oxc_draw_physical_pages.argtypes = [vp, C.POINTER(PreparedFrame), C.POINTER(VsmDrawContext), vp]
     lib.oxc_debug_vsm_draw_stats.argtypes = [vp, vp, vp]
+    lib.oxc_resolve_shadowmap.argtypes = [vp, C.POINTER(ShadowResolveContext), vp]
+    lib.oxc_debug_vsm_resolve_stats.argtypes = [vp, vp, vp]
     for name in EXPORTS:
         if name not in ("oxc_abi_version", "oxc_destroy", "oxc_last_error", "oxc_mesh_build_lod_count", "oxc_mesh_build_destroy"):
             getattr(lib, name).restype = C.c_int

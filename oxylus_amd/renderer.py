@@ -322,6 +322,63 @@ class VsmDrawContext:
 
 
 @dataclass
+class ShadowResolveContext:
+    """oxc_shadow_resolve_context: RendererInstance::resolve_shadowmap (Shadowmaps.cpp:756-822).  `create` takes the shape, the camera and the
+    page buffers from a VirtualShadowmapContext and allocates the output."""
+    depth_attachment: ImageAttachment             # R32F, levels = 1: the main view's reversed-Z depth
+    normal_attachment: torch.Tensor               # int16 [H, W, 4]: R16G16B16A16Sfloat bits, .ba = the octahedral world normal
+    vsm_clipmaps_buffer: torch.Tensor             # uint8 [clipmap_count * 76]
+    virtual_page_table: torch.Tensor              # int32 [clipmap_count, n, n]
+    physical_page_image: ImageAttachment          # R32F, physical_page_table_size square
+    resolved_shadows_attachment: ImageAttachment  # R32F out, the extent of the depth image
+    inv_projection_view: list
+    resolution: tuple
+    directional_light_dir: tuple
+    z_length: float                               # max_shadow_dist * 2
+    page_size: int = 128
+    page_table_size: int = 64
+    physical_page_table_size: int = 8192
+    clipmap_count: int = 10
+    first_clipmap_width: float = 10.0
+    clipmap_selection_bias: float = -1.5
+    virtual_extent: float = 8192.0
+
+    @staticmethod
+    def create(vsm: VirtualShadowmapContext, normal: torch.Tensor, light_dir, z_length: float,
+               physical_page_image: Optional[ImageAttachment] = None) -> "ShadowResolveContext":
+        img = physical_page_image if physical_page_image is not None else vsm.physical_page_image
+        assert img is not None, "the resolve needs a physical_page_image"
+        d = vsm.depth_attachment
+        assert normal.dtype == torch.int16 and tuple(normal.shape) == (d.height, d.width, 4) and normal.is_contiguous()
+        out = ImageAttachment.depth(torch.zeros((d.height, d.width), dtype=torch.float32, device=d.data.device))
+        return ShadowResolveContext(d, normal, vsm.vsm_clipmaps_buffer, vsm.virtual_page_table, img, out, list(vsm.inv_projection_view), tuple(vsm.resolution),
+                                    tuple(float(x) for x in light_dir), float(z_length), page_size=vsm.page_size, page_table_size=vsm.page_table_size,
+                                    physical_page_table_size=vsm.physical_page_table_size, clipmap_count=vsm.clipmap_count,
+                                    first_clipmap_width=vsm.first_clipmap_width, clipmap_selection_bias=vsm.clipmap_selection_bias,
+                                    virtual_extent=vsm.virtual_extent)
+
+    def c(self) -> L.ShadowResolveContext:
+        c = L.ShadowResolveContext()
+        c.struct_size = C.sizeof(L.ShadowResolveContext)
+        c.page_size, c.page_table_size, c.physical_page_table_size = self.page_size, self.page_table_size, self.physical_page_table_size
+        c.clipmap_count = self.clipmap_count
+        c.first_clipmap_width, c.clipmap_selection_bias, c.virtual_extent = self.first_clipmap_width, self.clipmap_selection_bias, self.virtual_extent
+        c.z_length = float(self.z_length)
+        for i in range(3):
+            c.directional_light_dir[i] = float(self.directional_light_dir[i])
+        for i in range(16):
+            c.inv_projection_view[i] = float(self.inv_projection_view[i])
+        c.resolution[0], c.resolution[1] = float(self.resolution[0]), float(self.resolution[1])
+        c.depth_attachment = self.depth_attachment.c()
+        c.normal_attachment = _buf(self.normal_attachment)
+        c.vsm_clipmaps_buffer = _buf(self.vsm_clipmaps_buffer)
+        c.virtual_page_table = _buf(self.virtual_page_table)
+        c.physical_page_image = self.physical_page_image.c()
+        c.resolved_shadows_attachment = self.resolved_shadows_attachment.c()
+        return c
+
+
+@dataclass
 class MainGeometryContext:
     """The fields generate_hiz uses (RendererInstance.hpp:199-216)."""
     depth_attachment: ImageAttachment
@@ -529,6 +586,20 @@ class RendererInstance:
         c = context.c()
         self._keep = context
         self._check(self._lib.oxc_draw_physical_pages(self._ctx, C.byref(f), C.byref(c), self._stream(stream)))
+
+    def resolve_shadowmap(self, context: ShadowResolveContext, stream=None):
+        """Shadowmaps.cpp:756-822 (resolve_shadowmaps): the PCSS light-visibility value of every pixel from the page table and the physical
+        pages into `context.resolved_shadows_attachment` (include/oxcull.h, oxc_resolve_shadowmap)."""
+        c = context.c()
+        self._keep = context
+        self._check(self._lib.oxc_resolve_shadowmap(self._ctx, C.byref(c), self._stream(stream)))
+
+    def debug_vsm_resolve_stats(self, stream=None) -> dict:
+        """What the last resolve_shadowmap did, after debug_set_tuning(L.TUNE_VSM_RESOLVE_STATS, 1) (measurement hook; synchronises)."""
+        out = (C.c_uint32 * 8)()
+        self._check(self._lib.oxc_debug_vsm_resolve_stats(self._ctx, C.cast(out, C.c_void_p), self._stream(stream)))
+        names = ("non_sky_pixels", "taps", "misses", "fallback_minus", "fallback_plus", "hard", "no_blocker", "all_blockers")
+        return {k: int(v) for k, v in zip(names, out)}
 
     def debug_vsm_draw_stats(self, stream=None) -> dict:
         """What the last draw_physical_pages did (measurement hook; synchronises).  `pairs` / `fragments` are counted only with

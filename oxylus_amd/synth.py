@@ -680,3 +680,39 @@ def make_scene_from_mesh(n_mesh_instances: int, bounds: torch.Tensor, meshlets: 
                           "tris_per_meshlet": int(meshlets[:, 3].max().item()) if K else 0,
                           "verts_per_meshlet": int(meshlets[:, 2].max().item()) if K else 0})
     return s.bind()
+
+
+# ---------------------------------------------------------------------------------------------
+# Normal image for the shadow resolve.  The reference's producer (visbuffer_decode) needs materials and textures; this stands in for it:
+# geometric normals from the depth image, stored as it stores them.
+# ---------------------------------------------------------------------------------------------
+def normals_from_depth(depth: torch.Tensor, inv_projection_view, camera_position=None) -> torch.Tensor:
+    """float32 [H, W] reversed-Z depth -> int16 [H, W, 4]: the bits of an R16G16B16A16Sfloat image whose .ba (and .rg) hold
+    vec3_to_oct (common/encoding.slang:17-21) of the face normal of each pixel: the cross product of the world-space steps to the right and
+    lower neighbour (the last column / row repeat the step before), turned towards `camera_position` when given.  Pixels without a finite
+    normal (sky, depth edges at infinity) get (0, 1, 0).  Input generation only: any float32 rounding will do."""
+    H, W = depth.shape
+    dev = depth.device
+    m = torch.as_tensor([float(v) for v in inv_projection_view], dtype=torch.float32, device=dev).view(4, 4).T  # column-major -> M
+    xs = (torch.arange(W, dtype=torch.float32, device=dev) + 0.5) / W * 2.0 - 1.0
+    ys = (torch.arange(H, dtype=torch.float32, device=dev) + 0.5) / H * 2.0 - 1.0
+    ndc = torch.stack([xs.view(1, W).expand(H, W), ys.view(H, 1).expand(H, W), depth, torch.ones_like(depth)], dim=-1)
+    h = ndc @ m.T
+    p = h[..., :3] / h[..., 3:4]
+    dx = torch.empty_like(p)
+    dy = torch.empty_like(p)
+    dx[:, :-1], dx[:, -1] = p[:, 1:] - p[:, :-1], p[:, -1] - p[:, -2]
+    dy[:-1], dy[-1] = p[1:] - p[:-1], p[-1] - p[-2]
+    n = torch.linalg.cross(dx, dy, dim=-1)
+    n = n / torch.linalg.norm(n, dim=-1, keepdim=True)
+    if camera_position is not None:
+        cam = torch.as_tensor([float(v) for v in camera_position], dtype=torch.float32, device=dev)
+        n = torch.where(((p - cam) * n).sum(-1, keepdim=True) > 0, -n, n)
+    up = torch.tensor([0.0, 1.0, 0.0], device=dev)
+    n = torch.where(torch.isfinite(n).all(-1, keepdim=True), n, up)
+    s = 1.0 / n.abs().sum(-1, keepdim=True)
+    q = n[..., :2] * s
+    sign = torch.where(q >= 0, 1.0, -1.0)
+    folded = (1.0 - q.flip(-1).abs()) * sign
+    e = torch.where(n[..., 2:3] <= 0, folded, q)
+    return torch.cat([e, e], dim=-1).to(torch.float16).view(torch.int16).contiguous()
