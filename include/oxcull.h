@@ -658,6 +658,84 @@ typedef struct oxc_shadow_resolve_context {
 
 oxc_status oxc_resolve_shadowmap(oxc_ctx* ctx, const oxc_shadow_resolve_context* context, void* hip_stream);
 
+/* ---- Contact shadows: the screen-space ray-marched sun shadow term ------------------------------------------------
+ * Replaces the contact_shadows pass that follows resolve_shadowmap in RendererInstance::render (Oxylus/src/Render/RendererInstance.cpp:
+ * 990-1020, pipeline contact_shadows, passes/contact_shadows.slang + the depth ray marcher raymarch.slang): per pixel of the main view a
+ * short ray towards the sun is marched through the depth image; one R32F value per pixel, every pixel written.  pbr_apply.slang:85-87
+ * multiplies it with oxc_resolve_shadowmap's value (that product is the consumer's).  Engine defaults (RendererCVar.cpp:30-34): steps 8,
+ * thickness 0.1, shadow_length 0.01.
+ * Arithmetic: as oxc_resolve_shadowmap (binary32, round to nearest even, no contraction, IEEE division and square root, the Slang's
+ * evaluation order; mul(M, v) row by row, left to right; max / min are fmaxf / fminf: a NaN operand gives the other one; lerp(a, b, t) =
+ * a + (b - a) * t; 2-component length(v) = sqrt(v.x * v.x + v.y * v.y)).  The reference is compiled fast-math and samples through
+ * hardware filtering, so it is not bit-defined: this is the one evaluation the device and the checker (tests/contact_shadows_model.py)
+ * both follow.  The engine calls the marcher in one configuration (contact_shadows.slang:63-71): jitter = 1, linear_march_exponent = 1,
+ * bisection_steps = 0, use_secant = false, march_behind_surfaces = false, use_sloppy_march = false.  Only that configuration exists here;
+ * the other branches of raymarch.slang are out of scope.  Per pixel (x, y) of the W x H depth image, size = float2(W, H):
+ *   1. sky     depth == 0.0 gives 1.0 (a NaN depth is not sky).  Stated rule: the Slang marches such a pixel through 1 / 0.
+ *   2. set-up  (contact_shadows.slang:45-61)  uv = (float2(x, y) + 0.5) / size;  cs = (uv * 2.0 - 1.0, depth);
+ *              h = mul(inv_projection_view, (cs, 1)): h.r = ((M[r][0] * cs.x + M[r][1] * cs.y) + M[r][2] * cs.z) + M[r][3];  ws = h.xyz / h.w
+ *              (the same operations in the same order as the unprojection of oxc_update_virtual_shadowmap's mark pass);
+ *              ray = normalize(sun_dir) * shadow_length, once per call: l = sqrt((s.x * s.x + s.y * s.y) + s.z * s.z), ray.k = (s.k / l) *
+ *              shadow_length;  end_ws = ws + ray.
+ *   3. ray end (raymarch.slang:559-568, 542-546, 502-537)  v = mul(view, (end_ws, 1)) (four rows, as h above);  p = mul(projection, v):
+ *              p.r = ((P[r][0] * v.x + P[r][1] * v.y) + P[r][2] * v.z) + P[r][3] * v.w;  e = p.xyz / p.w;
+ *              sign(a) = a > 0 ? 1.0 : a < 0 ? -1.0 : 0.0 (a NaN gives 0.0);  end = cs + (e - cs) * sign(e.z), per component.
+ *              to_cs_dir_impl's perspective division has w = 1 + 0 * sign = 1 exactly (or NaN with e.z infinite, where end is NaN already):
+ *              it divides by 1.0 and is omitted.
+ *              Start clip: delta = end - cs;  near_edge.k = delta.k < 0 ? 1.0 : -1.0 for k = x, y (the Slang also computes z and does
+ *              not use it: omitted);  m = max((near_edge.x - cs.x) / delta.x, (near_edge.y - cs.y) / delta.y);  start = cs + delta *
+ *              max(0.0, m), three components.
+ *              End clip: delta = end - start;  far_edge.k = delta.k >= 0 ? 1.0 : (k == z ? 0.0 : -1.0);  q.k = (far_edge.k - start.k) /
+ *              delta.k, three components;  clip = min(1.0, min(min(q.x, q.y), q.z));  ray_end = start + delta * clip.
+ *              A zero delta component divides by a signed zero; the IEEE result is the rule.  A pixel centre lies strictly inside the
+ *              image, so for finite operands m is negative and start == cs.  delta.k == +0.0 gives -Inf in the start clip and +Inf in the
+ *              end clip: that axis constrains neither.  delta.k == -0.0 would give m = +Inf and a NaN start (such a pixel ends as 1.0
+ *              through the NaN rules below); end - cs of equal finite values is +0.0, so only a checker test reaches it.
+ *   4. steps   (raymarch.slang:588-598)  cs_to_uv(c) = c * 0.5 + 0.5;  len_px = (cs_to_uv(ray_end.xy) - cs_to_uv(start.xy)) * size;
+ *              n = max(2, min(steps, u32(floor(length(len_px))))), float -> u32 saturating, NaN -> 0;
+ *              depth_thickness = thickness * (1.0 / near_clip), once per call.
+ *   5. march   (raymarch.slang:123-175)  dir = ray_end - start;  for step = 0 .. n - 1, stopping at the first intersection:
+ *              t = (f32(step) + 1.0) / f32(n)  (pow(v, 1.0) is v and lerp(0, 1, v) is v exactly: neither is evaluated);
+ *              c = start + dir * t;  interp_uv = cs_to_uv(c.xy);  ray_depth = 1.0 / c.z.
+ *   6. taps    (raymarch.slang:254-322)  Stated difference: the Slang's live branch samples with a hardware linear sampler, whose weights
+ *              are fixed-point with an implementation-defined number of bits.  The rule is the Slang's own #else branch, the manual
+ *              bilinear:  g = interp_uv * size - 0.5;  i = floor(g);  f = g - i;  the four texels (i.x + {0, 1}, i.y + {0, 1}), each
+ *              coordinate clamped to [0, size - 1] (clamp to edge);  i is converted float -> i32 saturating, NaN -> 0, and i + 1 does
+ *              not wrap: an i of INT_MAX reads the last column / row twice;
+ *              bil = lerp(lerp(t00, t10, f.x), lerp(t01, t11, f.x), f.y)  (t10 is the texel at (i.x + 1, i.y));
+ *              nearest = the texel at clamp(i32(floor(interp_uv * size)), 0, size - 1), the same conversion.
+ *              linear_depth = 1.0 / bil;  unfiltered_depth = 1.0 / nearest;  max_depth = max(linear_depth, unfiltered_depth), min_depth =
+ *              min(linear_depth, unfiltered_depth);  distance = max_depth * (1.0f + 0.000002f) - ray_depth, the factor rounded to binary32
+ *              once (0x3F800011);  penetration = ray_depth - min_depth;  intersected = distance < 0.0 (a NaN distance is not).
+ *   7. result  (raymarch.slang:617-623, contact_shadows.slang:73-77)  a hit = intersected && penetration < depth_thickness && distance <
+ *              depth_thickness;  then frac = penetration / depth_thickness, smoothstep(1.0, 0.3, frac): s = min(max((frac - 1.0f) /
+ *              (0.3f - 1.0f), 0.0), 1.0) with 0.3f - 1.0f evaluated in binary32 (0xBF333333), shadow = (s * s) * (3.0 - 2.0 * s);  the
+ *              pixel is 1.0 - shadow.  Everything else (no intersection after n steps, or an intersection the thickness test rejects)
+ *              is 1.0.
+ * Rules the reference leaves open, decided here: the sampler's addressing of a coordinate outside the image or NaN is the clamp above;
+ * the ray's sun-side normalisation and the thickness scale are evaluated once on the host, in the order shown; a texel of any bit pattern
+ * (NaN, infinities, negative, denormal) goes through the same arithmetic -- max / min drop a NaN operand, every comparison with NaN is false.
+ * Limits (else OXC_INVALID_ARG): depth_attachment and contact_shadows_attachment one R32F level each, of the same extent (at most 65536 a
+ * side); steps in [1, 64]; thickness, shadow_length and near_clip finite and > 0; sun_dir finite and not the zero vector.  One launch, no
+ * scratch, no allocation, no host synchronisation; capturable into a HIP graph. */
+typedef struct oxc_contact_shadows_context {
+  uint32_t struct_size; /* sizeof(oxc_contact_shadows_context) */
+  /* the GPU::Camera fields the pass reads */
+  float inv_projection_view[16]; /* column-major, as view and projection */
+  float view[16];
+  float projection[16];
+  float near_clip;
+  /* the push constants (contact_shadows.slang:15-20) */
+  float sun_dir[3];     /* towards the sun; normalised by the pass */
+  uint32_t steps;
+  float thickness;
+  float shadow_length;
+  oxc_image depth_attachment;           /* in: R32F, levels = 1, reversed Z, 0 = nothing drawn */
+  oxc_image contact_shadows_attachment; /* out: R32F, levels = 1, the extent of the depth image */
+} oxc_contact_shadows_context;
+
+oxc_status oxc_contact_shadows(oxc_ctx* ctx, const oxc_contact_shadows_context* context, void* hip_stream);
+
 /* ---- terrain patch cull ---------------------------------------------------------
  * Replaces RendererInstance::cull_terrain (Oxylus/src/Render/Passes/Terrain.cpp:159-216) + pipeline
  * terrain_cull (Shaders/passes/terrain_cull.slang:17-83): one thread per patch, world-space AABB from the

@@ -84,7 +84,8 @@ enum { OXC_TUNE_ASYNC_MTEST_BLOCKS_PER_CU = 0, OXC_TUNE_ASYNC_TRI_BLOCKS_PER_CU 
                                          pair of the frame's index buffer, 4096..2^24, growing with the frame; the tile queue holds 2x
                                          as many); fixed, only before the context's first shadow draw -- the tests shrink it to reach
                                          the overflow paths */,
-       OXC_TUNE_VSM_RESOLVE_STATS = 10 /* 1: oxc_resolve_shadowmap runs its counting instantiation (oxc_debug_vsm_resolve_stats); 0 (default): off */ };
+       OXC_TUNE_VSM_RESOLVE_STATS = 10 /* 1: oxc_resolve_shadowmap runs its counting instantiation (oxc_debug_vsm_resolve_stats); 0 (default): off */,
+       OXC_TUNE_CONTACT_SHADOWS_STATS = 11 /* 1: oxc_contact_shadows runs its counting instantiation (oxc_debug_contact_shadows_stats); 0 (default): off */ };
 oxc_status oxc_debug_set_tuning(oxc_ctx* ctx, uint32_t knob, uint32_t value);
 
 /* Measurement aid: counters_dptr != NULL -- the HiZ calls (use_hiz + OXC_CULL_TEST_OCCLUSION) that follow on this context run counting
@@ -111,6 +112,15 @@ oxc_status oxc_debug_vsm_draw_stats(oxc_ctx* ctx, uint32_t* host_out8, void* hip
  * out8 = {non-sky pixels, taps taken (one per sample position), taps no clipmap served, taps served by clipmap base - 1, by base + 1,
  * pixels that returned the hard-shadow value, the "no blocker" 1.0, the "all blockers" 0.0}. */
 oxc_status oxc_debug_vsm_resolve_stats(oxc_ctx* ctx, uint32_t* host_out8, void* hip_stream);
+
+/* Measurement hook: what the last oxc_contact_shadows on this context did, counted by a counting instantiation of its kernel (same
+ * image, slower) after oxc_debug_set_tuning(OXC_TUNE_CONTACT_SHADOWS_STATS, 1); synchronises the stream.
+ * out12 = {non-sky pixels, depth taps (evaluations of rule 6: one per step taken, five texels each), pixels that found no intersection in
+ * their n steps, hits that wrote exactly 0.0, hits that wrote a value strictly inside (0, 1), hits that wrote 1.0, intersections the
+ * thickness test rejected, pixels whose n is 2 by the lower clamp (min(steps, u32(floor(length))) < 2), pixels with 2 <= n < steps taken
+ * from the ray's length, pixels whose n is steps by the upper clamp (steps >= 2), pixels whose end clip is active (clip < 1.0: the ray
+ * is cut at the image border or at z = 0), pixels whose start clip moved the start (max(0.0, m) > 0.0)}. */
+oxc_status oxc_debug_contact_shadows_stats(oxc_ctx* ctx, uint32_t* host_out12, void* hip_stream);
 
 #ifdef __cplusplus
 }

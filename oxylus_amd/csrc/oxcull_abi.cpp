@@ -84,6 +84,8 @@ struct oxc_ctx {
   bool vsm_draw_stats = false;             // oxc_debug_set_tuning(OXC_TUNE_VSM_DRAW_STATS): counting kernels
   uint32_t* vsm_resolve_stats = nullptr;   // oxc_resolve_shadowmap with OXC_TUNE_VSM_RESOLVE_STATS: u32[8] the counting kernel adds to
   bool vsm_resolve_stats_on = false;
+  uint32_t* contact_shadows_stats = nullptr;  // oxc_contact_shadows with OXC_TUNE_CONTACT_SHADOWS_STATS: u32[12] the counting kernel adds to
+  bool contact_shadows_stats_on = false;
   void* comm = nullptr;           // ncclComm_t (oxc_comm_init)
   uint32_t comm_rank = 0, comm_world = 0;
   // counter slots
@@ -487,6 +489,7 @@ void oxc_destroy(oxc_ctx* ctx) {
   if (ctx->vsm_scratch) (void)hipFree(ctx->vsm_scratch);
   if (ctx->vsm_draw_scratch) (void)hipFree(ctx->vsm_draw_scratch);
   if (ctx->vsm_resolve_stats) (void)hipFree(ctx->vsm_resolve_stats);
+  if (ctx->contact_shadows_stats) (void)hipFree(ctx->contact_shadows_stats);
   if (ctx->comm) (void)oxc_comm_destroy(ctx);
   if (ctx->slots) (void)hipFree(ctx->slots);
   if (ctx->order_event) (void)hipEventDestroy(ctx->order_event);
@@ -1804,6 +1807,58 @@ oxc_status oxc_resolve_shadowmap(oxc_ctx* ctx, const oxc_shadow_resolve_context*
   return OXC_OK;
 }
 
+oxc_status oxc_contact_shadows(oxc_ctx* ctx, const oxc_contact_shadows_context* c, void* hip_stream) {
+  if (!ctx) return OXC_INVALID_ARG;
+  if (!c || c->struct_size != sizeof(oxc_contact_shadows_context)) return fail(ctx, OXC_INVALID_ARG, "contact_shadows: bad context / struct_size");
+  const oxc_image& dimg = c->depth_attachment;
+  const oxc_image& oimg = c->contact_shadows_attachment;
+  const uint64_t pixels = (uint64_t)dimg.width * dimg.height;
+  if (dimg.width > 65536u || dimg.height > 65536u) return fail(ctx, OXC_INVALID_ARG, "contact_shadows: depth extent beyond 65536");
+  if (pixels && (!dimg.dptr || dimg.levels != 1 || dimg.level_offset[0] != 0))
+    return fail(ctx, OXC_INVALID_ARG, "contact_shadows: depth_attachment must be one R32F level at offset 0");
+  if (oimg.width != dimg.width || oimg.height != dimg.height || (pixels && (!oimg.dptr || oimg.levels != 1 || oimg.level_offset[0] != 0)))
+    return fail(ctx, OXC_INVALID_ARG, "contact_shadows: contact_shadows_attachment must be one R32F level of the depth attachment's extent");
+  if (c->steps < 1u || c->steps > 64u) return fail(ctx, OXC_INVALID_ARG, "contact_shadows: steps must be 1..64");
+  if (!(std::isfinite(c->thickness) && c->thickness > 0.0f) || !(std::isfinite(c->shadow_length) && c->shadow_length > 0.0f) ||
+      !(std::isfinite(c->near_clip) && c->near_clip > 0.0f))
+    return fail(ctx, OXC_INVALID_ARG, "contact_shadows: thickness, shadow_length and near_clip must be finite and > 0");
+  const float* sd = c->sun_dir;
+  if (!(std::isfinite(sd[0]) && std::isfinite(sd[1]) && std::isfinite(sd[2])) || (sd[0] == 0.0f && sd[1] == 0.0f && sd[2] == 0.0f))
+    return fail(ctx, OXC_INVALID_ARG, "contact_shadows: sun_dir must be finite and not zero");
+  OXC_HIP(ctx, hipSetDevice(ctx->device));
+  OXC_ORDER(ctx, hip_stream);
+  const hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  if (!pixels) return OXC_OK;
+  ContactShadowsArgs a;
+  std::memset(&a, 0, sizeof a);
+  if (ctx->contact_shadows_stats_on) {
+    if (!ctx->contact_shadows_stats) {
+      if (stream_is_capturing(s)) return fail(ctx, OXC_INVALID_ARG, "contact_shadows: the counters are allocated by the first counting call; make one outside the capture");
+      hipError_t e = hipMalloc(reinterpret_cast<void**>(&ctx->contact_shadows_stats), 48);
+      if (e != hipSuccess) return fail(ctx, OXC_OUT_OF_MEMORY, "hipMalloc(contact shadows counters)", e);
+    }
+    OXC_HIP(ctx, hipMemsetAsync(ctx->contact_shadows_stats, 0, 48, s));
+    a.stats = ctx->contact_shadows_stats;
+  }
+  a.depth = static_cast<const float*>(dimg.dptr);
+  a.out = static_cast<float*>(oimg.dptr);
+  a.w = dimg.width;
+  a.h = dimg.height;
+  a.fw = (float)dimg.width;
+  a.fh = (float)dimg.height;
+  a.steps = c->steps;
+  // per-call constants, binary32 in the Slang's order (include/oxcull.h)
+  for (int k = 0; k < 16; k++) a.inv_pv[k] = c->inv_projection_view[k], a.view[k] = c->view[k], a.proj[k] = c->projection[k];
+  const float len = std::sqrt((sd[0] * sd[0] + sd[1] * sd[1]) + sd[2] * sd[2]);  // normalize(sun_dir) * shadow_length
+  for (int k = 0; k < 3; k++) a.ray[k] = (sd[k] / len) * c->shadow_length;
+  a.depth_thickness = c->thickness * (1.0f / c->near_clip);
+  a.one_plus_bias = 1.0f + 0.000002f;
+  a.edge_span = 0.3f - 1.0f;
+  launch_contact_shadows(a, s);
+  OXC_HIP(ctx, hipGetLastError());
+  return OXC_OK;
+}
+
 oxc_status oxc_cull_terrain(oxc_ctx* ctx, oxc_terrain_context* c, void* hip_stream) {
   if (!ctx) return OXC_INVALID_ARG;
   if (!c || c->struct_size != sizeof(oxc_terrain_context)) return fail(ctx, OXC_INVALID_ARG, "cull_terrain: bad context / struct_size");
@@ -2126,6 +2181,7 @@ oxc_status oxc_debug_set_tuning(oxc_ctx* ctx, uint32_t knob, uint32_t value) {
       return OXC_OK;
     case OXC_TUNE_VSM_DRAW_STATS: ctx->vsm_draw_stats = value != 0u; return OXC_OK;
     case OXC_TUNE_VSM_RESOLVE_STATS: ctx->vsm_resolve_stats_on = value != 0u; return OXC_OK;
+    case OXC_TUNE_CONTACT_SHADOWS_STATS: ctx->contact_shadows_stats_on = value != 0u; return OXC_OK;
     case OXC_TUNE_VSM_DRAW_CAPACITY:
       if (ctx->vsm_draw_scratch) return fail(ctx, OXC_INVALID_ARG, "set_tuning: the shadow draw's scratch is allocated by the first oxc_draw_physical_pages; set its capacity before");
       ctx->vsm_draw_capacity_request = value;
@@ -2206,6 +2262,18 @@ oxc_status oxc_debug_vsm_resolve_stats(oxc_ctx* ctx, uint32_t* host_out8, void* 
   OXC_ORDER(ctx, hip_stream);
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   OXC_HIP(ctx, hipMemcpyAsync(host_out8, ctx->vsm_resolve_stats, 32, hipMemcpyDeviceToHost, s));
+  OXC_HIP(ctx, hipStreamSynchronize(s));
+  return OXC_OK;
+}
+
+oxc_status oxc_debug_contact_shadows_stats(oxc_ctx* ctx, uint32_t* host_out12, void* hip_stream) {
+  if (!ctx) return OXC_INVALID_ARG;
+  if (!host_out12) return fail(ctx, OXC_INVALID_ARG, "debug_contact_shadows_stats: null pointer");
+  if (!ctx->contact_shadows_stats) return fail(ctx, OXC_INVALID_ARG, "debug_contact_shadows_stats: no counting oxc_contact_shadows call on this context yet");
+  OXC_HIP(ctx, hipSetDevice(ctx->device));
+  OXC_ORDER(ctx, hip_stream);
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  OXC_HIP(ctx, hipMemcpyAsync(host_out12, ctx->contact_shadows_stats, 48, hipMemcpyDeviceToHost, s));
   OXC_HIP(ctx, hipStreamSynchronize(s));
   return OXC_OK;
 }

@@ -559,6 +559,22 @@ struct VsmResolveArgs {
   float ham[40][2];  // hammersley2d(i, 16), i < 16, then hammersley2d(i, 24), i < 24
 };
 void launch_vsm_resolve(const VsmResolveArgs& a, hipStream_t s);
+// oxcull_contact_shadows.hip: the contact shadow ray march (oxc_contact_shadows)
+struct ContactShadowsArgs {
+  const float* depth;  // [h][w]
+  float* out;          // [h][w]
+  uint32_t w, h;
+  float fw, fh;        // float(w), float(h)
+  uint32_t steps;
+  uint32_t* stats;     // nullptr, or u32[12] the counting instantiation adds to (oxc_debug_contact_shadows_stats)
+  // per-call constants, computed once on the host in binary32 by the rules of include/oxcull.h
+  float inv_pv[16], view[16], proj[16];
+  float ray[3];           // normalize(sun_dir) * shadow_length
+  float depth_thickness;  // thickness * (1.0 / near_clip)
+  float one_plus_bias;    // 1.0f + 0.000002f
+  float edge_span;        // 0.3f - 1.0f, smoothstep's edge1 - edge0
+};
+void launch_contact_shadows(const ContactShadowsArgs& a, hipStream_t s);
 // oxcull_bounds.hip: meshlet bounds producer
 void launch_build_meshlet_bounds(const float* pos, uint32_t vertex_count, const void* meshlets, uint32_t meshlet_count, const uint32_t* vidx,
                                  const uint8_t* micro, void* out_bounds, float* out_mesh6, void* out_qpos, float* meshlet_minmax, float* normals,

@@ -110,6 +110,10 @@ struct MainGeometryContext {
 // and normal images, the clipmaps, the page table, the physical pages, and the R32F resolved_shadows_attachment.
 using ShadowResolveContext = oxc_shadow_resolve_context;
 
+// What the contact_shadows pass reads and writes (RendererInstance.cpp:990-1020, passes/contact_shadows.slang): the GPU::Camera fields, the
+// push constants (sun_dir, steps, thickness, shadow_length), the main view's depth and the R32F contact_shadows_attachment.
+using ContactShadowsContext = oxc_contact_shadows_context;
+
 class RendererInstance {
 public:
   explicit RendererInstance(int device = 0, void* hip_stream = nullptr) : stream_(hip_stream) {
@@ -245,6 +249,12 @@ public:
   auto resolve_shadowmap(ShadowResolveContext context) -> void {
     context.struct_size = sizeof context;
     check(oxc_resolve_shadowmap(ctx_, &context, stream_));
+  }
+  // The contact_shadows pass, inline in RendererInstance::render (RendererInstance.cpp:990-1020, directly after resolve_shadowmap); the
+  // shim gives it a name.  pbr_apply multiplies its output with resolve_shadowmap's.  Rules: include/oxcull.h, oxc_contact_shadows.
+  auto contact_shadows(ContactShadowsContext context) -> void {
+    context.struct_size = sizeof context;
+    check(oxc_contact_shadows(ctx_, &context, stream_));
   }
   auto build_meshlet_bounds(oxc_meshlet_bounds_desc desc) -> void {
     desc.struct_size = sizeof desc;

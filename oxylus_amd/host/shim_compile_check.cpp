@@ -44,5 +44,10 @@ int main(int argc, char**) {
   } catch (const std::exception& e) {
     std::printf("expected (no attachments bound): %s\n", e.what());
   }
+  try {  // RendererInstance.cpp:990-1020: the second shadow term, after resolve_shadowmap
+    self.contact_shadows(ContactShadowsContext{});
+  } catch (const std::exception& e) {
+    std::printf("expected (no attachments bound): %s\n", e.what());
+  }
   return 0;
 }

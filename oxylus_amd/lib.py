@@ -28,7 +28,7 @@ STAGE_TRIANGLES = 4
 STAGE_ALL = 7
 
 TUNE_ASYNC_MTEST_BLOCKS_PER_CU, TUNE_ASYNC_TRI_BLOCKS_PER_CU, TUNE_RASTER_BIG_CAPACITY, TUNE_TRI_BLOCKS_PER_CU, TUNE_MV_EXPAND_ASYNC, TUNE_TRI_LOADS = 0, 1, 2, 3, 5, 7  # oxc_debug_set_tuning knobs
-TUNE_VSM_DRAW_STATS, TUNE_VSM_DRAW_CAPACITY, TUNE_VSM_RESOLVE_STATS = 8, 9, 10
+TUNE_VSM_DRAW_STATS, TUNE_VSM_DRAW_CAPACITY, TUNE_VSM_RESOLVE_STATS, TUNE_CONTACT_SHADOWS_STATS = 8, 9, 10, 11
 
 
 class Buffer(C.Structure):
@@ -313,6 +313,23 @@ class ShadowResolveContext(C.Structure):
     ]
 
 
+class ContactShadowsContext(C.Structure):
+    """oxc_contact_shadows_context (include/oxcull.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("inv_projection_view", C.c_float * 16),
+        ("view", C.c_float * 16),
+        ("projection", C.c_float * 16),
+        ("near_clip", C.c_float),
+        ("sun_dir", C.c_float * 3),
+        ("steps", C.c_uint32),
+        ("thickness", C.c_float),
+        ("shadow_length", C.c_float),
+        ("depth_attachment", Image),
+        ("contact_shadows_attachment", Image),
+    ]
+
+
 # every symbol include/oxcull.h declares
 EXPORTS = [
     "oxc_abi_version",
@@ -348,6 +365,8 @@ EXPORTS = [
     "oxc_debug_vsm_draw_stats",
     "oxc_resolve_shadowmap",
     "oxc_debug_vsm_resolve_stats",
+    "oxc_contact_shadows",
+    "oxc_debug_contact_shadows_stats",
     "oxc_comm_unique_id",
     "oxc_comm_init",
     "oxc_comm_destroy",
@@ -445,6 +464,8 @@ def load(path: str = None) -> C.CDLL:
     lib.oxc_debug_vsm_draw_stats.argtypes = [vp, vp, vp]
     lib.oxc_resolve_shadowmap.argtypes = [vp, C.POINTER(ShadowResolveContext), vp]
     lib.oxc_debug_vsm_resolve_stats.argtypes = [vp, vp, vp]
+    lib.oxc_contact_shadows.argtypes = [vp, C.POINTER(ContactShadowsContext), vp]
+    lib.oxc_debug_contact_shadows_stats.argtypes = [vp, vp, vp]
     for name in EXPORTS:
         if name not in ("oxc_abi_version", "oxc_destroy", "oxc_last_error", "oxc_mesh_build_lod_count", "oxc_mesh_build_destroy"):
             getattr(lib, name).restype = C.c_int

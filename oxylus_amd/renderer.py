@@ -379,6 +379,46 @@ class ShadowResolveContext:
 
 
 @dataclass
+class ContactShadowsContext:
+    """oxc_contact_shadows_context: the contact_shadows pass of RendererInstance::render (RendererInstance.cpp:990-1020).  `create` takes the
+    depth image and the camera and allocates the output; steps / thickness / shadow_length default to the engine's (RendererCVar.cpp:30-34)."""
+    depth_attachment: ImageAttachment            # R32F, levels = 1: the main view's reversed-Z depth
+    contact_shadows_attachment: ImageAttachment  # R32F out, the extent of the depth image
+    inv_projection_view: list                    # column-major float[16], as view and projection
+    view: list
+    projection: list
+    near_clip: float
+    sun_dir: tuple                               # towards the sun; the pass normalises it
+    steps: int = 8
+    thickness: float = 0.1
+    shadow_length: float = 0.01
+
+    @staticmethod
+    def create(depth, inv_projection_view, view, projection, near_clip: float, sun_dir, steps: int = 8, thickness: float = 0.1,
+               shadow_length: float = 0.01) -> "ContactShadowsContext":
+        d = depth if isinstance(depth, ImageAttachment) else ImageAttachment.depth(depth)
+        out = ImageAttachment.depth(torch.zeros((d.height, d.width), dtype=torch.float32, device=d.data.device))
+        return ContactShadowsContext(d, out, [float(x) for x in inv_projection_view], [float(x) for x in view], [float(x) for x in projection],
+                                     float(near_clip), tuple(float(x) for x in sun_dir), int(steps), float(thickness), float(shadow_length))
+
+    def c(self) -> L.ContactShadowsContext:
+        c = L.ContactShadowsContext()
+        c.struct_size = C.sizeof(L.ContactShadowsContext)
+        for i in range(16):
+            c.inv_projection_view[i] = float(self.inv_projection_view[i])
+            c.view[i] = float(self.view[i])
+            c.projection[i] = float(self.projection[i])
+        c.near_clip = float(self.near_clip)
+        for i in range(3):
+            c.sun_dir[i] = float(self.sun_dir[i])
+        c.steps = int(self.steps)
+        c.thickness, c.shadow_length = float(self.thickness), float(self.shadow_length)
+        c.depth_attachment = self.depth_attachment.c()
+        c.contact_shadows_attachment = self.contact_shadows_attachment.c()
+        return c
+
+
+@dataclass
 class MainGeometryContext:
     """The fields generate_hiz uses (RendererInstance.hpp:199-216)."""
     depth_attachment: ImageAttachment
@@ -599,6 +639,21 @@ class RendererInstance:
         out = (C.c_uint32 * 8)()
         self._check(self._lib.oxc_debug_vsm_resolve_stats(self._ctx, C.cast(out, C.c_void_p), self._stream(stream)))
         names = ("non_sky_pixels", "taps", "misses", "fallback_minus", "fallback_plus", "hard", "no_blocker", "all_blockers")
+        return {k: int(v) for k, v in zip(names, out)}
+
+    def contact_shadows(self, context: ContactShadowsContext, stream=None):
+        """RendererInstance.cpp:990-1020 (contact_shadows): per pixel a short ray towards the sun marched through the depth image, the
+        shadow term into `context.contact_shadows_attachment` (include/oxcull.h, oxc_contact_shadows)."""
+        c = context.c()
+        self._keep = context
+        self._check(self._lib.oxc_contact_shadows(self._ctx, C.byref(c), self._stream(stream)))
+
+    def debug_contact_shadows_stats(self, stream=None) -> dict:
+        """What the last contact_shadows did, after debug_set_tuning(L.TUNE_CONTACT_SHADOWS_STATS, 1) (measurement hook; synchronises)."""
+        out = (C.c_uint32 * 12)()
+        self._check(self._lib.oxc_debug_contact_shadows_stats(self._ctx, C.cast(out, C.c_void_p), self._stream(stream)))
+        names = ("non_sky_pixels", "taps", "miss", "hit_zero", "hit_partial", "hit_one", "rejected", "n_lower", "n_between", "n_upper", "end_clip",
+                 "start_moved")
         return {k: int(v) for k, v in zip(names, out)}
 
     def debug_vsm_draw_stats(self, stream=None) -> dict:

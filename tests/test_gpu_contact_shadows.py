@@ -1,0 +1,230 @@
+"""oxc_contact_shadows on the GPU: the image byte-identical to tests/contact_shadows_model.py, every pixel -- a depth drawn by
+oxc_draw_visbuffer with every outcome class populated, the engine's defaults on it, an odd non-square extent under a rotated camera with
+1, 3 and 64 steps, an all-sky image, non-finite / negative / denormal texels, the resolve and the contact shadows captured into one graph,
+and invalid arguments."""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import contact_shadows_model as CM
+from test_contact_shadows_model import MAIN, MAIN_SEED, MAIN_SIZE, SUN, assert_not_degenerate, identity_camera
+
+pytestmark = pytest.mark.gpu
+
+
+def drawn_depth(r, W, H, seed):
+    """The main view's depth of tests/test_gpu_vsm_resolve.py::occluder_scene, drawn by oxc_draw_visbuffer (the first steps of its Frame)."""
+    from oxylus_amd import lib as L
+    from oxylus_amd.renderer import CullGeometryContext, ImageAttachment, PreparedFrame
+    from test_gpu_vsm_resolve import occluder_scene
+
+    cpu = occluder_scene(seed)
+    gpu = cpu.to("cuda")
+    r.reserve(gpu.n_mesh_instances, gpu.n_meshlet_instances)
+    r.prepared_frame = PreparedFrame.create(gpu)
+    main = CullGeometryContext(init_cull_meshes=False, cull_flags=L.CULL_TEST_ALL, cull_camera=gpu.cull_camera())
+    r.seed_meshlet_instances(main, gpu.n_meshlet_instances)
+    r.cull_geometry(main)
+    pv = [float(x) for x in cpu.camera["projection_view"]]
+    visdepth = torch.empty((H, W), dtype=torch.int64, device="cuda")
+    depth = torch.zeros((H, W), dtype=torch.float32, device="cuda")
+    r.draw_visbuffer(main, pv, W, H, visdepth, clear=True, depth=ImageAttachment.depth(depth))
+    torch.cuda.synchronize()
+    return cpu, depth
+
+
+def context(depth, camera, sun=SUN, **kw):
+    from oxylus_amd.renderer import ContactShadowsContext
+
+    inv, view, proj, near = camera
+    return ContactShadowsContext.create(depth, inv, view, proj, near, sun, **kw)
+
+
+def got_of(ctx):
+    torch.cuda.synchronize()
+    a = ctx.contact_shadows_attachment
+    return a.data.view(a.height, a.width).cpu().numpy().copy()
+
+
+def want_of(ctx, stats=None):
+    d = ctx.depth_attachment
+    return CM.contact_shadows(d.data.view(d.height, d.width).cpu().numpy(), ctx.inv_projection_view, ctx.view, ctx.projection, ctx.near_clip, ctx.sun_dir,
+                              ctx.steps, ctx.thickness, ctx.shadow_length, stats=stats)
+
+
+def check(ctx, stats=None):
+    got, want = got_of(ctx), want_of(ctx, stats)
+    bad = int((got.view(np.uint32) != want.view(np.uint32)).sum())
+    assert bad == 0, f"{bad} of {got.size} pixels differ"
+    return got
+
+
+def test_main_frame_every_outcome_class(renderer):
+    """occluder_scene(61) drawn at 768 x 768, steps 12, thickness 0.3, shadow_length 0.15: image == checker, device counters == checker's, and
+    the fixture is not degenerate by the floors of tests/test_contact_shadows_model.py (each outcome class >= 1000 pixels, end clip >= 100),
+    judged by the checker on the drawn depth.  Counts reached by the checker on the oracle-drawn frame: see
+    test_the_main_gpu_frame_is_not_degenerate; on the device-drawn one: the same (sky 267 518, miss 243 076, hit == 0.0 51 106, hit inside
+    (0, 1) 22 239, rejected 5 885, n lower / between / upper 7 522 / 228 162 / 86 622, end clip 5 893, 2 132 799 taps)."""
+    from oxylus_amd import lib as L
+
+    cpu, depth = drawn_depth(renderer, MAIN_SIZE, MAIN_SIZE, MAIN_SEED)
+    ctx = context(depth, identity_camera(cpu), **MAIN)
+    renderer.debug_set_tuning(L.TUNE_CONTACT_SHADOWS_STATS, 1)
+    try:
+        renderer.contact_shadows(ctx)
+        st = {}
+        check(ctx, st)
+        dev = renderer.debug_contact_shadows_stats()
+    finally:
+        renderer.debug_set_tuning(L.TUNE_CONTACT_SHADOWS_STATS, 0)
+    counts = assert_not_degenerate(st)
+    print("checker", counts)
+    print("device", dev)
+    assert dev == CM.counters(st)
+    ctx.contact_shadows_attachment.data.fill_(-5.0)
+    renderer.contact_shadows(ctx)  # the plain instantiation writes the same image
+    check(ctx)
+
+
+def test_engine_defaults_on_the_main_frame(renderer):
+    """steps 8, thickness 0.1, shadow_length 0.01 (RendererCVar.cpp:30-34): rays shorter than two pixels, n == 2 everywhere."""
+    cpu, depth = drawn_depth(renderer, MAIN_SIZE, MAIN_SIZE, MAIN_SEED)
+    ctx = context(depth, identity_camera(cpu))
+    assert (ctx.steps, ctx.thickness, ctx.shadow_length) == (8, 0.1, 0.01)
+    renderer.contact_shadows(ctx)
+    st = {}
+    got = check(ctx, st)
+    assert (st["n"][st["outcome"] != CM.SKY] == 2).all() and ((got > 0) & (got < 1)).sum() > 1000
+
+
+def rotated_camera():
+    """A camera at (3, 1.5, -2) turned 25 degrees about y and 10 degrees down: neither view nor its inverse has an exact entry."""
+    from oxylus_amd.synth import perspective_reversed_z
+
+    proj = perspective_reversed_z(60.0, 1.0, 0.1, 1000.0).numpy().astype(np.float64).reshape(4, 4).T
+    a, b = math.radians(25.0), math.radians(-10.0)
+    ry = np.array([[math.cos(a), 0, math.sin(a), 0], [0, 1, 0, 0], [-math.sin(a), 0, math.cos(a), 0], [0, 0, 0, 1]])
+    rx = np.array([[1, 0, 0, 0], [0, math.cos(b), -math.sin(b), 0], [0, math.sin(b), math.cos(b), 0], [0, 0, 0, 1]])
+    tr = np.eye(4)
+    tr[:3, 3] = (-3.0, -1.5, 2.0)
+    view = rx @ ry @ tr
+    inv = np.linalg.inv(proj @ view)
+    f = lambda m: m.T.reshape(-1).astype(np.float32)  # noqa: E731
+    return f(inv), f(view), f(proj), 0.1
+
+
+@pytest.mark.parametrize("steps", [1, 3, 64])
+def test_second_shape_odd_extent_rotated_camera(renderer, steps):
+    """1277 x 719, a synthetic depth of overlapping quads at 15..150 m seen by a rotated and translated camera, a sun low over the horizon, rays
+    of four units and a thickness of 30 (the quads lie tens of metres apart): steps = 1 (n = 2 by the lower clamp everywhere), 3 and 64
+    (most rays shorter than 64 pixels: n from the length).  The checker alone, on the CPU, reaches at steps = 64: miss 469 208, hit == 0.0
+    13 125, hit inside (0, 1) 5 699, rejected 12 285, n lower / between / upper 981 / 394 037 / 105 299, end clip 29 010."""
+    from oxylus_amd.synth import make_depth
+
+    depth = make_depth(1277, 719, 48, seed=11).cuda()
+    ctx = context(depth, rotated_camera(), sun=(-0.7, 0.25, 0.4), steps=steps, thickness=30.0, shadow_length=4.0)
+    renderer.contact_shadows(ctx)
+    st = {}
+    got = check(ctx, st)
+    assert ((got > 0) & (got < 1)).any() and (got == 1).any() and (st["outcome"] == CM.MISS).sum() > 1000 and st["end_clip"].sum() > 0
+    nonsky = st["outcome"] != CM.SKY
+    if steps == 1:
+        assert (st["n"][nonsky] == 2).all()
+    else:
+        assert (st["n"][nonsky] == steps).any() and (st["n"][nonsky] < steps).any()
+
+
+def test_all_sky_and_non_finite_texels(renderer):
+    cpu, depth = drawn_depth(renderer, 256, 256, 65)
+    ctx = context(depth, identity_camera(cpu), steps=8, thickness=0.3, shadow_length=0.3)
+    renderer.contact_shadows(ctx)
+    check(ctx)
+    # NaN, infinities, negative, denormal and huge texels scattered over covered and sky pixels: every NaN rule agrees
+    ys, xs = np.nonzero(depth.cpu().numpy() != 0)
+    assert len(xs) > 2000
+    values = (float("nan"), float("inf"), -float("inf"), -0.0, 1e-30, 3e38, -0.5, 1e-42, -1e-42)
+    for k in range(180):
+        depth[int(ys[k * 11]), int(xs[k * 11])] = values[k % len(values)]
+    for k in range(40):
+        depth[(k * 37) % 256, (k * 91 + 5) % 256] = values[k % len(values)]
+    renderer.contact_shadows(ctx)
+    got = check(ctx)
+    assert np.isfinite(got).all()
+    depth.zero_()
+    ctx.contact_shadows_attachment.data.fill_(-5.0)
+    renderer.contact_shadows(ctx)
+    assert (got_of(ctx) == 1.0).all()
+
+
+def test_resolve_and_contact_shadows_in_one_graph(renderer):
+    from test_gpu_vsm_resolve import Frame
+
+    f = Frame(renderer, 320, 320, seed=66)
+    f.shadow_path()  # eager; every scratch grows here
+    ctx = context(f.depth, identity_camera(f.gpu), steps=8, thickness=0.3, shadow_length=0.3)
+    renderer.contact_shadows(ctx)
+    resolved = f.check()
+    contact = check(ctx)
+    assert ((contact > 0) & (contact < 1)).any() and ((resolved > 0) & (resolved < 1)).any()
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=s):
+        renderer.resolve_shadowmap(f.rctx, stream=s)
+        renderer.contact_shadows(ctx, stream=s)
+    for _ in range(2):
+        f.rctx.resolved_shadows_attachment.data.fill_(-5.0)
+        ctx.contact_shadows_attachment.data.fill_(-5.0)
+        torch.cuda.synchronize()
+        g.replay()
+        assert np.array_equal(f.got().view(np.uint32), resolved.view(np.uint32))
+        assert np.array_equal(got_of(ctx).view(np.uint32), contact.view(np.uint32))
+
+
+def test_invalid_arguments(renderer):
+    from oxylus_amd import lib as L
+    from oxylus_amd.renderer import ImageAttachment
+
+    cpu, depth = drawn_depth(renderer, 128, 128, 67)
+    ctx = context(depth, identity_camera(cpu), steps=8, thickness=0.3, shadow_length=0.3)
+    ctx.contact_shadows_attachment.data.fill_(-5.0)
+
+    def bad(**kw):
+        saved = {k: getattr(ctx, k) for k in kw}
+        for k, v in kw.items():
+            setattr(ctx, k, v)
+        with pytest.raises(L.OxcError) as e:
+            renderer.contact_shadows(ctx)
+        assert e.value.status == L.OXC_INVALID_ARG
+        for k, v in saved.items():
+            setattr(ctx, k, v)
+
+    inf, nan = float("inf"), float("nan")
+    bad(steps=0)
+    bad(steps=65)
+    for name in ("thickness", "shadow_length", "near_clip"):
+        for v in (0.0, -1.0, inf, nan):
+            bad(**{name: v})
+    bad(sun_dir=(0.0, 0.0, 0.0))
+    bad(sun_dir=(0.0, -0.0, 0.0))
+    bad(sun_dir=(nan, 1.0, 0.0))
+    bad(sun_dir=(0.0, inf, 0.0))
+    bad(contact_shadows_attachment=ImageAttachment.depth(torch.zeros((128, 64), dtype=torch.float32, device="cuda")))
+    bad(contact_shadows_attachment=ImageAttachment.depth(torch.zeros((64, 128), dtype=torch.float32, device="cuda")))
+    c = ctx.c()
+    c.depth_attachment.levels = 2
+    assert renderer._lib.oxc_contact_shadows(renderer._ctx, c, renderer._stream(None)) == L.OXC_INVALID_ARG
+    c = ctx.c()
+    c.contact_shadows_attachment.levels = 2
+    assert renderer._lib.oxc_contact_shadows(renderer._ctx, c, renderer._stream(None)) == L.OXC_INVALID_ARG
+    c = ctx.c()
+    c.depth_attachment.width, c.contact_shadows_attachment.width = 65537, 65537
+    assert renderer._lib.oxc_contact_shadows(renderer._ctx, c, renderer._stream(None)) == L.OXC_INVALID_ARG
+    c = ctx.c()
+    c.struct_size = 4
+    assert renderer._lib.oxc_contact_shadows(renderer._ctx, c, renderer._stream(None)) == L.OXC_INVALID_ARG
+    assert (got_of(ctx) == -5.0).all()  # nothing was written
+    renderer.contact_shadows(ctx)       # and the context still runs
+    check(ctx)
