@@ -736,6 +736,130 @@ typedef struct oxc_contact_shadows_context {
 
 oxc_status oxc_contact_shadows(oxc_ctx* ctx, const oxc_contact_shadows_context* context, void* hip_stream);
 
+/* ---- Ambient occlusion: the VBGTAO term from depth and normals -----------------------------------------------------
+ * Replaces RendererInstance::generate_ambient_occlusion (Oxylus/src/Render/Passes/PBR.cpp:179-311), the call that follows the contact shadows
+ * in RendererInstance::render (RendererInstance.cpp:1040-1055): the pipelines vbgtao_prefilter, vbgtao_main and vbgtao_denoise (passes/gtao/)
+ * as three launches.  It fills the ambient_occlusion_attachment that pbr_apply reads.  Engine defaults: pp.vbgtao = 1, quality 3 ("ultra":
+ * 9 slices x 3 samples per side; the four presets are 1 x 2, 2 x 2, 3 x 3, 9 x 3), GPU::VBGTAOSettings (SceneGPU.hpp:286-293): thickness 0.25,
+ * effect_radius 0.5, noise_index 0, final_power 2.2.
+ * Arithmetic: as oxc_resolve_shadowmap (binary32, round to nearest even, no contraction, IEEE division and square root, the Slang's evaluation
+ * order; dot, length, normalize and cross as defined there; max / min are fmaxf / fminf: a NaN operand gives the other one; lerp(a, b, t) =
+ * a + (b - a) * t; frac(x) = x - floor(x)); saturate(x) = min(max(x, 0), 1), so a NaN gives 0; sign(a) = a > 0 ? 1 : a < 0 ? -1 : 0 (NaN: 0);
+ * float -> integer conversions saturate and NaN converts to 0; u32 -> f32 conversions are of values below 2^24 and exact; countbits is the
+ * population count.  HALF_PI = 1.57079632679f, PI = 3.1415926535897932f, each rounded to binary32 once.  The reference is compiled fast-math
+ * and samples through hardware gather and trilinear filtering, so it is not bit-defined: this is the one evaluation the device and the
+ * checker (tests/ambient_occlusion_model.py) both follow.  No float operation of the per-pixel rules is reordered, contracted or approximated.
+ * W x H is the extent of the depth image; level k of prefiltered_depth is max(1, W >> k) x max(1, H >> k).
+ * Host evaluation, once per call, binary32, in this order:  (mul, add) = (projection[3][2], projection[2][2]) in glm indexing = elements 14
+ *   and 10 of the column-major array (PBR.cpp:183-186);  the prefilter's radius r0 = (0.75f * 0.5f) * 1.457f;  for a radius r the falloff pair
+ *   is falloff_range = 0.615f * r, falloff_from = r * (1.0f - 0.615f), falloff_mul = -1.0f / falloff_range, falloff_add = falloff_from /
+ *   falloff_range + 1.0f (vbgtao_prefilter.slang:24-29 with r0, vbgtao_main.slang:157-161 with r = effect_radius * 1.457f);  far_thr =
+ *   far_clip * 0.999f;  radius = ((0.5f * r) * |projection[0][0]|, (0.5f * r) * |projection[1][1]|);  f32(slice_count),
+ *   f32(samples_per_slice_side);  noise_add = 288 * (noise_index % 64).  The divisions by projection[0][0] / [1][1] and by PI stay divisions,
+ *   per evaluation.
+ * Prefilter (vbgtao_prefilter.slang), one thread per 2 x 2 source texels, threads (bx, by) on a grid padded to multiples of 8:
+ *   1. gather  (:57-58)  Stated rule: Gather at the corner of texel p0 = 2 * (bx, by) with offset (1, 1) names the integer texels .w = p0,
+ *              .z = p0 + (1, 0), .x = p0 + (0, 1), .y = p0 + (1, 1), each coordinate clamped to [0, extent - 1].
+ *   2. mip 0   (:19-21, :60-70)  linear = mul / (device_depth + add) for each of the four; each is stored at its own coordinate when that
+ *              lies inside the image (odd extents: the clamped duplicates are computed and not stored).
+ *   3. mip 1   (:23-39, :73-75)  weighted_average(d0 = .w, d1 = .z, d2 = .x, d3 = .y): m = min(min(d0, d1), min(d2, d3));  w_i =
+ *              saturate((d_i - m) * falloff_mul + falloff_add);  total = ((w0 + w1) + w2) + w3;  result = ((((w0 * d0) + (w1 * d1)) +
+ *              (w2 * d2)) + (w3 * d3)) / total.  Stored at (bx, by) when inside level 1.
+ *   4. mips 2..4  (:79-115)  the thread with bx and by multiples of 2^(k-1) averages the level k - 1 values of the THREADS (bx, by),
+ *              (bx + s, by), (bx, by + s), (bx + s, by + s), s = 2^(k-2), in that order, and stores at (bx, by) >> (k - 1) when inside
+ *              level k.  A thread's value exists whether or not its own destination does: a destination texel outside a level is not
+ *              written, and a 1-wide level's texel still averages the clamped values next to it.
+ * Main (vbgtao_main.slang), one thread per pixel (x, y):
+ *   5. edges   (:69-100)  Stated rule: the two GatherRed name the level-0 texels centre = (x, y), left = (x - 1, y), right = (x + 1, y), top =
+ *              (x, y - 1), bottom = (x, y + 1), clamped.  e = (left, right, top, bottom) - centre;  slr = (e.y - e.x) * 0.5, stb = (e.w - e.z)
+ *              * 0.5;  adj = e + (slr, -slr, stb, -stb);  e = min(|e|, |adj|);  e = saturate((1.0f + 0.25f) - e / (centre * 0.011f));
+ *              depth_differences = packUnorm4x8(e): byte k = u32(floor(saturate(e_k) * 255.0f + 0.5f)) (a half-way value rounds up), component
+ *              x in the low byte.  Written for every pixel.
+ *   6. sky     (:171-174)  centre >= far_thr stores 1.0 (a NaN is not sky).  Otherwise linear_depth = centre * 0.99999f.
+ *   7. set-up  (:59-67, :164, :176-188)  uv = (float2(x, y) + 0.5) / resolution;  view_position(uv, d) = (((uv.x * 2.0 - 1.0) / projection[0][0])
+ *              * d, ((uv.y * 2.0 - 1.0) / projection[1][1]) * d, -d);  origin = view_position(uv, linear_depth);  view_dir = normalize(-origin);
+ *              normal: Stated rule: the point sample is the normal texel at (x, y);  e = (.b, .a), binary16 -> binary32 exact with denormals
+ *              kept;  n_w = oct_to_vec3(e) as in oxc_resolve_shadowmap step 2 (one normalisation);  normal = normalize(n_v), n_v.r = (V[r][0]
+ *              * n_w.x + V[r][1] * n_w.y) + V[r][2] * n_w.z (the w = 0 term is left out);
+ *              noise (:39-45): index = f32(hilbert_noise[y % 64][x % 64] + noise_add);  noise = frac(0.5f + index * (0.75487766624669276005f,
+ *              0.5698402909980532659114f));
+ *              screen_radius_uv = radius / linear_depth (both components);  min_s = 1.3f / max(screen_radius_uv.x * resolution.x, 1.3f).
+ *   8. slice   (:191-208)  for slice_t = 0 .. slice_count - 1:  slice = (f32(slice_t) + noise.x) / f32(slice_count);  Stated difference:
+ *              (c, s) = (cos, sin)(slice * PI) is the rotation rule of oxc_resolve_shadowmap step 6 applied to t = slice * 0.5f.  The zero
+ *              component of direction = (c, s, 0) is left out of its products:  dv = c * view_dir.x + s * view_dir.y;  ortho = normalize((c -
+ *              dv * view_dir.x, s - dv * view_dir.y, 0.0 - dv * view_dir.z));  axis = normalize((s * view_dir.z, -(c * view_dir.z), c *
+ *              view_dir.y - s * view_dir.x));  pn = normal - axis * dot(normal, axis);  pnl = max(length(pn), 1e-6f);  sign_norm =
+ *              sign(dot(ortho, pn));  n = sign_norm * fast_acos(saturate(dot(pn, view_dir) / pnl));  sample_mul = (c * screen_radius_uv.x,
+ *              (-s) * screen_radius_uv.y).
+ *              fast_acos(v) (:32-37): x = |v|;  res = -0.156583f * x + HALF_PI;  res = res * sqrt(saturate(1.0 - x));  v >= 0 ? res : PI - res.
+ *   9. sample  (:212-231)  for sample_t = 0 .. samples_per_slice_side - 1:  sn = frac(noise.y + (f32(slice_t) + f32(sample_t) * f32(samples))
+ *              * 0.6180339887498948482f);  s = (f32(sample_t) + sn) / f32(samples);  s = s * s;  s = s + min_s;  offset = s * sample_mul;
+ *              p1 = uv + offset, p2 = uv - offset;  len = sqrt(q.x * q.x + q.y * q.y), q = offset * resolution;
+ *              l = min(max(log2(len) - 3.30f, 0.0), 4.0), the log2 rule below.
+ *              Stated difference (filtered samples): SampleLevel(linear clamp, p, l) is the manual bilinear of oxc_contact_shadows step 6
+ *              (g = p * level_extent - 0.5, i = floor(g), f = g - i, four clamped texels, lerp(lerp(t00, t10, f.x), lerp(t01, t11, f.x), f.y))
+ *              at level floor(l), giving a, and at level min(floor(l) + 1, 4), giving b;  depth = lerp(a, b, l - floor(l)).  Both levels are
+ *              ALWAYS evaluated, also for a zero fraction: a non-finite texel of the second level then makes the sample NaN.
+ *  10. arcs    (:124-146, :230-246)  delta = view_position(p, depth) - origin;  back = delta - view_dir * thickness;  h_f =
+ *              fast_acos(dot(normalize(delta), view_dir)), h_b the same of back;  for side = +1 (p1) or -1 (p2): h = saturate((((side * -h)
+ *              + n) + HALF_PI) / PI) for both;  (lo, hi) = side >= 0 ? (h_b, h_f) : (h_f, h_b).
+ *              update_sectors (:102-119): angle = u32(ceil(saturate(hi - lo) * 32.0));  angle == 0 gives the empty mask;  start =
+ *              min(u32(saturate(lo) * 32.0), 31);  mask = (0xFFFFFFFF >> (32 - angle)) << start, in 32 bits.
+ *              falloff = saturate(length(delta) * falloff_mul + falloff_add);  occlusion += (falloff * f32(countbits(mask & ~bitmask))) / 32.0;
+ *              bitmask |= mask;  side +1 first, then side -1.
+ *  11. result  (:249-253)  per slice visibility += saturate(1.0 - occlusion);  ao = saturate(visibility / f32(slice_count)), stored in
+ *              noisy_occlusion as binary16, round to nearest even, denormals kept.
+ * Denoise (vbgtao_denoise.slang), one thread per pixel:
+ *  12. taps    (:21-56)  Stated rule: the seven GatherRed name, clamped, the edge words of centre, left, right, top, bottom and the nine
+ *              noisy values of the 3 x 3 neighbourhood (binary16 -> binary32, exact, denormals kept).  unpackUnorm4x8ToFloat: f32(byte k) /
+ *              255.0f, (x, y, z, w) = (left, right, top, bottom) edge.  centre_edges *= (left.y, right.x, top.w, bottom.z);  the diagonal
+ *              weights are 0.425f * (a * b + c * d) as the Slang writes them (:43-46).
+ *  13. filter  (:58-81)  sum = centre * 1.2f, then += left, right, top, bottom, top-left, top-right, bottom-left, bottom-right value * weight
+ *              in that order;  sum_weight likewise from 1.2f;  v = max(sum / sum_weight, 0.0);  out = pow(v, final_power), the pow rule
+ *              below, stored as binary16 like step 11 (the reference's image is R16F).
+ * log2 rule (stated difference: neither a library log2 nor v_log_f32 can be matched from numpy).  For binary32 x >= 2^-126: x = m * 2^e with m
+ *   in [1, 2) from the bits;  m > 1.41421356f: m = m * 0.5 (exact), e = e + 1;  in binary64, no contraction: f = (double)m - 1.0, s = f / (2.0 +
+ *   f), z = s * s, P = 1 + z (1/3 + z (1/5 + z (1/7 + z (1/9 + z (1/11 + z (1/13 + z (1/15 + z / 17))))))) by Horner with the binary64
+ *   quotients 1.0 / k, L = (double)e + ((2.0 * s) * P) * 0x1.71547652b82fep+0;  log2(x) = L rounded to binary32 once.  x < 2^-126 (zero,
+ *   denormal, negative) and NaN give -Inf; +Inf gives +Inf.  Within 2^-23 relative (2^-24 absolute below 1) of the exact value
+ *   (tests/test_ambient_occlusion_model.py).
+ * pow rule, for v >= 0 and final_power p > 0:  y = (double)p * L(v), L the binary64 value above before its rounding;  k = floor(y + 0.5), r =
+ *   y - k (exact), t = r * 0x1.62e42fefa39efp-1, E = sum_{n = 0..13} t^n / n! by Horner with the binary64 quotients 1.0 / n!;  pow = E * 2^k
+ *   rounded to binary32 once.  y <= -160 gives 0.0 and y >= 160 gives +Inf (what the rounding would give).  pow(0, p) = 0.0 (v below 2^-126
+ *   likewise) and pow(1, p) = 1.0 exactly.
+ * Rules the reference leaves open, decided here: a texel of any bit pattern goes through the same arithmetic; the kernels run with the FP16
+ * denormal mode at its default (denormals kept), unlike the cull kernels.
+ * Limits (else OXC_INVALID_ARG, nothing written): depth_attachment one R32F level at offset 0, at most 65536 a side; prefiltered_depth of the
+ * same extent with exactly 5 levels at 4-byte aligned offsets; normal_attachment 8-byte aligned with one u16x4 per pixel; hilbert_noise
+ * u16[64][64], 2-byte aligned; depth_differences 4-byte aligned u32 per pixel; noisy_occlusion and ambient_occlusion_attachment 2-byte
+ * aligned u16 per pixel; slice_count in [1, 16], samples_per_slice_side in [1, 8]; thickness, effect_radius, final_power, far_clip and both
+ * components of resolution finite and > 0; noise_index any value.  The three intermediates are caller-owned; the context's arena is not
+ * touched.  Three launches, no allocation, no host synchronisation; capturable into a HIP graph.  Every pixel of every output is written. */
+typedef struct oxc_ambient_occlusion_context {
+  uint32_t struct_size; /* sizeof(oxc_ambient_occlusion_context) */
+  /* the GPU::Camera fields the pass reads */
+  float view[16];       /* column-major, as projection */
+  float projection[16];
+  float resolution[2];
+  float far_clip;
+  /* GPU::VBGTAOSettings (SceneGPU.hpp:286-293), same order and types */
+  float thickness;
+  uint32_t slice_count;
+  uint32_t samples_per_slice_side;
+  float effect_radius;
+  uint32_t noise_index;
+  float final_power;
+  oxc_image depth_attachment;              /* in: R32F, levels = 1, reversed Z */
+  oxc_buffer normal_attachment;            /* in: u16x4[height][width], only .b and .a are read (as in oxc_shadow_resolve_context) */
+  oxc_buffer hilbert_noise;                /* in: u16[64][64], the engine's Hilbert index table (RendererInstance.cpp:150-177) */
+  oxc_image prefiltered_depth;             /* out, caller-owned: R32F, exactly 5 levels, linear view-space depth */
+  oxc_buffer depth_differences;            /* out, caller-owned: u32[height][width], the packed edges */
+  oxc_buffer noisy_occlusion;              /* out, caller-owned: binary16 as u16[height][width] */
+  oxc_buffer ambient_occlusion_attachment; /* out: binary16 as u16[height][width] */
+} oxc_ambient_occlusion_context;
+
+oxc_status oxc_generate_ambient_occlusion(oxc_ctx* ctx, const oxc_ambient_occlusion_context* context, void* hip_stream);
+
 /* ---- terrain patch cull ---------------------------------------------------------
  * Replaces RendererInstance::cull_terrain (Oxylus/src/Render/Passes/Terrain.cpp:159-216) + pipeline
  * terrain_cull (Shaders/passes/terrain_cull.slang:17-83): one thread per patch, world-space AABB from the

@@ -85,7 +85,8 @@ enum { OXC_TUNE_ASYNC_MTEST_BLOCKS_PER_CU = 0, OXC_TUNE_ASYNC_TRI_BLOCKS_PER_CU 
                                          as many); fixed, only before the context's first shadow draw -- the tests shrink it to reach
                                          the overflow paths */,
        OXC_TUNE_VSM_RESOLVE_STATS = 10 /* 1: oxc_resolve_shadowmap runs its counting instantiation (oxc_debug_vsm_resolve_stats); 0 (default): off */,
-       OXC_TUNE_CONTACT_SHADOWS_STATS = 11 /* 1: oxc_contact_shadows runs its counting instantiation (oxc_debug_contact_shadows_stats); 0 (default): off */ };
+       OXC_TUNE_CONTACT_SHADOWS_STATS = 11 /* 1: oxc_contact_shadows runs its counting instantiation (oxc_debug_contact_shadows_stats); 0 (default): off */,
+       OXC_TUNE_AMBIENT_OCCLUSION_STATS = 12 /* 1: oxc_generate_ambient_occlusion runs the counting instantiation of its main kernel (oxc_debug_ambient_occlusion_stats); 0 (default): off */ };
 oxc_status oxc_debug_set_tuning(oxc_ctx* ctx, uint32_t knob, uint32_t value);
 
 /* Measurement aid: counters_dptr != NULL -- the HiZ calls (use_hiz + OXC_CULL_TEST_OCCLUSION) that follow on this context run counting
@@ -121,6 +122,13 @@ oxc_status oxc_debug_vsm_resolve_stats(oxc_ctx* ctx, uint32_t* host_out8, void* 
  * from the ray's length, pixels whose n is steps by the upper clamp (steps >= 2), pixels whose end clip is active (clip < 1.0: the ray
  * is cut at the image border or at z = 0), pixels whose start clip moved the start (max(0.0, m) > 0.0)}. */
 oxc_status oxc_debug_contact_shadows_stats(oxc_ctx* ctx, uint32_t* host_out12, void* hip_stream);
+
+/* Measurement hook: what the last oxc_generate_ambient_occlusion on this context did, counted by a counting instantiation of its main kernel
+ * (same images, slower) after oxc_debug_set_tuning(OXC_TUNE_AMBIENT_OCCLUSION_STATS, 1); synchronises the stream.
+ * out15 = {non-sky pixels, depth samples taken (filtered samples of step 9: two per sample pair, eight texels each), samples whose integer
+ * level floor(l) is 0, 1, 2, 3, 4, samples with a non-zero level fraction, non-sky pixels whose stored noisy half is exactly 1.0, strictly
+ * inside (0, 1), exactly 0.0, update_sectors calls whose arc has zero width, slices whose sign_norm is -1, 0, +1}. */
+oxc_status oxc_debug_ambient_occlusion_stats(oxc_ctx* ctx, uint32_t* host_out15, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -86,6 +86,8 @@ struct oxc_ctx {
   bool vsm_resolve_stats_on = false;
   uint32_t* contact_shadows_stats = nullptr;  // oxc_contact_shadows with OXC_TUNE_CONTACT_SHADOWS_STATS: u32[12] the counting kernel adds to
   bool contact_shadows_stats_on = false;
+  uint32_t* ambient_occlusion_stats = nullptr;  // oxc_generate_ambient_occlusion with OXC_TUNE_AMBIENT_OCCLUSION_STATS: u32[15] (16 allocated)
+  bool ambient_occlusion_stats_on = false;
   void* comm = nullptr;           // ncclComm_t (oxc_comm_init)
   uint32_t comm_rank = 0, comm_world = 0;
   // counter slots
@@ -490,6 +492,7 @@ void oxc_destroy(oxc_ctx* ctx) {
   if (ctx->vsm_draw_scratch) (void)hipFree(ctx->vsm_draw_scratch);
   if (ctx->vsm_resolve_stats) (void)hipFree(ctx->vsm_resolve_stats);
   if (ctx->contact_shadows_stats) (void)hipFree(ctx->contact_shadows_stats);
+  if (ctx->ambient_occlusion_stats) (void)hipFree(ctx->ambient_occlusion_stats);
   if (ctx->comm) (void)oxc_comm_destroy(ctx);
   if (ctx->slots) (void)hipFree(ctx->slots);
   if (ctx->order_event) (void)hipEventDestroy(ctx->order_event);
@@ -1859,6 +1862,98 @@ oxc_status oxc_contact_shadows(oxc_ctx* ctx, const oxc_contact_shadows_context* 
   return OXC_OK;
 }
 
+oxc_status oxc_generate_ambient_occlusion(oxc_ctx* ctx, const oxc_ambient_occlusion_context* c, void* hip_stream) {
+  if (!ctx) return OXC_INVALID_ARG;
+  if (!c || c->struct_size != sizeof(oxc_ambient_occlusion_context)) return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: bad context / struct_size");
+  const oxc_image& dimg = c->depth_attachment;
+  const oxc_image& pimg = c->prefiltered_depth;
+  const uint64_t pixels = (uint64_t)dimg.width * dimg.height;
+  if (dimg.width > 65536u || dimg.height > 65536u) return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: depth extent beyond 65536");
+  if (pixels && (!dimg.dptr || dimg.levels != 1 || dimg.level_offset[0] != 0))
+    return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: depth_attachment must be one R32F level at offset 0");
+  if (pimg.width != dimg.width || pimg.height != dimg.height || pimg.levels != 5 || (pixels && !pimg.dptr))
+    return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: prefiltered_depth must have the depth attachment's extent and exactly 5 levels");
+  for (int k = 0; k < 5; k++)
+    if (pimg.level_offset[k] & 3u) return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: prefiltered_depth level offsets must be multiples of 4");
+  auto bad_buffer = [&](const oxc_buffer& b, uint64_t texel, uintptr_t align) {
+    return pixels && (!b.dptr || b.bytes < pixels * texel || (reinterpret_cast<uintptr_t>(b.dptr) & (align - 1u)));
+  };
+  if (bad_buffer(c->normal_attachment, 8u, 8u))
+    return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: normal_attachment must be 8-byte aligned u16x4 texels of the depth attachment's extent");
+  if (pixels && (!c->hilbert_noise.dptr || c->hilbert_noise.bytes < 64u * 64u * 2u || (reinterpret_cast<uintptr_t>(c->hilbert_noise.dptr) & 1u)))
+    return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: hilbert_noise must be u16[64][64]");
+  if (bad_buffer(c->depth_differences, 4u, 4u)) return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: depth_differences must be one aligned u32 per pixel");
+  if (bad_buffer(c->noisy_occlusion, 2u, 2u) || bad_buffer(c->ambient_occlusion_attachment, 2u, 2u))
+    return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: noisy_occlusion and ambient_occlusion_attachment must be one aligned u16 per pixel");
+  if (c->slice_count < 1u || c->slice_count > 16u || c->samples_per_slice_side < 1u || c->samples_per_slice_side > 8u)
+    return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: slice_count must be 1..16 and samples_per_slice_side 1..8");
+  auto positive = [](float v) { return std::isfinite(v) && v > 0.0f; };
+  if (!positive(c->thickness) || !positive(c->effect_radius) || !positive(c->final_power) || !positive(c->far_clip))
+    return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: thickness, effect_radius, final_power and far_clip must be finite and > 0");
+  if (!positive(c->resolution[0]) || !positive(c->resolution[1])) return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: resolution must be finite and > 0");
+  OXC_HIP(ctx, hipSetDevice(ctx->device));
+  OXC_ORDER(ctx, hip_stream);
+  const hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  if (!pixels) return OXC_OK;
+  AmbientOcclusionArgs a;
+  std::memset(&a, 0, sizeof a);
+  if (ctx->ambient_occlusion_stats_on) {
+    if (!ctx->ambient_occlusion_stats) {
+      if (stream_is_capturing(s)) return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: the counters are allocated by the first counting call; make one outside the capture");
+      hipError_t e = hipMalloc(reinterpret_cast<void**>(&ctx->ambient_occlusion_stats), 64);
+      if (e != hipSuccess) return fail(ctx, OXC_OUT_OF_MEMORY, "hipMalloc(ambient occlusion counters)", e);
+    }
+    OXC_HIP(ctx, hipMemsetAsync(ctx->ambient_occlusion_stats, 0, 64, s));
+    a.stats = ctx->ambient_occlusion_stats;
+  }
+  a.depth = static_cast<const float*>(dimg.dptr);
+  a.normal = static_cast<const uint32_t*>(c->normal_attachment.dptr);
+  a.hilbert = static_cast<const uint16_t*>(c->hilbert_noise.dptr);
+  a.pre = static_cast<float*>(pimg.dptr);
+  a.edges = static_cast<uint32_t*>(c->depth_differences.dptr);
+  a.noisy = static_cast<uint16_t*>(c->noisy_occlusion.dptr);
+  a.out = static_cast<uint16_t*>(c->ambient_occlusion_attachment.dptr);
+  a.w = dimg.width;
+  a.h = dimg.height;
+  for (uint32_t k = 0; k < 5; k++) {
+    a.lvl_off[k] = pimg.level_offset[k] / 4u;
+    a.lvl_w[k] = std::max(1u, dimg.width >> k);
+    a.lvl_h[k] = std::max(1u, dimg.height >> k);
+  }
+  a.slice_count = c->slice_count;
+  a.samples = c->samples_per_slice_side;
+  a.noise_add = 288u * (c->noise_index % 64u);
+  // per-call constants, binary32 in the order include/oxcull.h states
+  auto falloff = [](float r, float& mul, float& add) {
+    const float falloff_range = 0.615f * r;
+    const float falloff_from = r * (1.0f - 0.615f);
+    mul = -1.0f / falloff_range;
+    add = falloff_from / falloff_range + 1.0f;
+  };
+  a.lin_mul = c->projection[14];  // glm projection[3][2]
+  a.lin_add = c->projection[10];  // glm projection[2][2]
+  falloff((0.75f * 0.5f) * 1.457f, a.pf_mul, a.pf_add);
+  const float r = c->effect_radius * 1.457f;
+  falloff(r, a.falloff_mul, a.falloff_add);
+  for (int row = 0; row < 3; row++)
+    for (int col = 0; col < 3; col++) a.view3[row * 3 + col] = c->view[col * 4 + row];
+  a.p00 = c->projection[0];
+  a.p11 = c->projection[5];
+  a.res_x = c->resolution[0];
+  a.res_y = c->resolution[1];
+  a.far_thr = c->far_clip * 0.999f;
+  a.thickness = c->thickness;
+  a.slice_count_f = (float)c->slice_count;
+  a.samples_f = (float)c->samples_per_slice_side;
+  const float half_r = 0.5f * r;
+  a.radius_x = half_r * std::fabs(a.p00);
+  a.radius_y = half_r * std::fabs(a.p11);
+  a.final_power = c->final_power;
+  launch_ambient_occlusion(a, s);
+  OXC_HIP(ctx, hipGetLastError());
+  return OXC_OK;
+}
+
 oxc_status oxc_cull_terrain(oxc_ctx* ctx, oxc_terrain_context* c, void* hip_stream) {
   if (!ctx) return OXC_INVALID_ARG;
   if (!c || c->struct_size != sizeof(oxc_terrain_context)) return fail(ctx, OXC_INVALID_ARG, "cull_terrain: bad context / struct_size");
@@ -2182,6 +2277,7 @@ oxc_status oxc_debug_set_tuning(oxc_ctx* ctx, uint32_t knob, uint32_t value) {
     case OXC_TUNE_VSM_DRAW_STATS: ctx->vsm_draw_stats = value != 0u; return OXC_OK;
     case OXC_TUNE_VSM_RESOLVE_STATS: ctx->vsm_resolve_stats_on = value != 0u; return OXC_OK;
     case OXC_TUNE_CONTACT_SHADOWS_STATS: ctx->contact_shadows_stats_on = value != 0u; return OXC_OK;
+    case OXC_TUNE_AMBIENT_OCCLUSION_STATS: ctx->ambient_occlusion_stats_on = value != 0u; return OXC_OK;
     case OXC_TUNE_VSM_DRAW_CAPACITY:
       if (ctx->vsm_draw_scratch) return fail(ctx, OXC_INVALID_ARG, "set_tuning: the shadow draw's scratch is allocated by the first oxc_draw_physical_pages; set its capacity before");
       ctx->vsm_draw_capacity_request = value;
@@ -2274,6 +2370,18 @@ oxc_status oxc_debug_contact_shadows_stats(oxc_ctx* ctx, uint32_t* host_out12, v
   OXC_ORDER(ctx, hip_stream);
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   OXC_HIP(ctx, hipMemcpyAsync(host_out12, ctx->contact_shadows_stats, 48, hipMemcpyDeviceToHost, s));
+  OXC_HIP(ctx, hipStreamSynchronize(s));
+  return OXC_OK;
+}
+
+oxc_status oxc_debug_ambient_occlusion_stats(oxc_ctx* ctx, uint32_t* host_out15, void* hip_stream) {
+  if (!ctx) return OXC_INVALID_ARG;
+  if (!host_out15) return fail(ctx, OXC_INVALID_ARG, "debug_ambient_occlusion_stats: null pointer");
+  if (!ctx->ambient_occlusion_stats) return fail(ctx, OXC_INVALID_ARG, "debug_ambient_occlusion_stats: no counting oxc_generate_ambient_occlusion call on this context yet");
+  OXC_HIP(ctx, hipSetDevice(ctx->device));
+  OXC_ORDER(ctx, hip_stream);
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  OXC_HIP(ctx, hipMemcpyAsync(host_out15, ctx->ambient_occlusion_stats, 60, hipMemcpyDeviceToHost, s));
   OXC_HIP(ctx, hipStreamSynchronize(s));
   return OXC_OK;
 }

@@ -575,6 +575,32 @@ struct ContactShadowsArgs {
   float edge_span;        // 0.3f - 1.0f, smoothstep's edge1 - edge0
 };
 void launch_contact_shadows(const ContactShadowsArgs& a, hipStream_t s);
+// oxcull_ambient_occlusion.hip: VBGTAO prefilter, main and denoise (oxc_generate_ambient_occlusion)
+struct AmbientOcclusionArgs {
+  const float* depth;       // [h][w] device depth
+  const uint32_t* normal;   // [h][w] u16x4 as two words
+  const uint16_t* hilbert;  // [64][64]
+  float* pre;               // prefiltered_depth: five levels
+  uint32_t* edges;          // depth_differences [h][w]
+  uint16_t* noisy;          // noisy_occlusion [h][w], binary16
+  uint16_t* out;            // ambient_occlusion_attachment [h][w], binary16
+  uint32_t* stats;          // nullptr, or u32[15] the counting instantiation of the main kernel adds to (oxc_debug_ambient_occlusion_stats)
+  uint64_t lvl_off[5];      // first float of each level
+  uint32_t lvl_w[5], lvl_h[5];
+  uint32_t w, h;
+  uint32_t slice_count, samples, noise_add;  // noise_add = 288 * (noise_index % 64)
+  // per-call constants, computed once on the host in binary32 by the rules of include/oxcull.h
+  float lin_mul, lin_add;  // projection[3][2], projection[2][2] (glm indexing)
+  float pf_mul, pf_add;    // the prefilter's falloff pair
+  float view3[9];          // view's upper 3 x 3, row by row
+  float p00, p11, res_x, res_y;
+  float far_thr;           // far_clip * 0.999f
+  float thickness, slice_count_f, samples_f;
+  float falloff_mul, falloff_add;
+  float radius_x, radius_y;  // (0.5f * effect_radius') * |p00|, * |p11|
+  float final_power;
+};
+void launch_ambient_occlusion(const AmbientOcclusionArgs& a, hipStream_t s);
 // oxcull_bounds.hip: meshlet bounds producer
 void launch_build_meshlet_bounds(const float* pos, uint32_t vertex_count, const void* meshlets, uint32_t meshlet_count, const uint32_t* vidx,
                                  const uint8_t* micro, void* out_bounds, float* out_mesh6, void* out_qpos, float* meshlet_minmax, float* normals,

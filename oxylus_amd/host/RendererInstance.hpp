@@ -114,6 +114,10 @@ using ShadowResolveContext = oxc_shadow_resolve_context;
 // push constants (sun_dir, steps, thickness, shadow_length), the main view's depth and the R32F contact_shadows_attachment.
 using ContactShadowsContext = oxc_contact_shadows_context;
 
+// What generate_ambient_occlusion reads and writes (Passes/PBR.cpp:179-311): the GPU::Camera fields, GPU::VBGTAOSettings, the main view's depth,
+// the normal image, the Hilbert index table, the three caller-owned intermediates and the R16F ambient_occlusion_attachment.
+using AmbientOcclusionContext = oxc_ambient_occlusion_context;
+
 class RendererInstance {
 public:
   explicit RendererInstance(int device = 0, void* hip_stream = nullptr) : stream_(hip_stream) {
@@ -255,6 +259,12 @@ public:
   auto contact_shadows(ContactShadowsContext context) -> void {
     context.struct_size = sizeof context;
     check(oxc_contact_shadows(ctx_, &context, stream_));
+  }
+  // RendererInstance::generate_ambient_occlusion (Passes/PBR.cpp:179-311), the call after the contact shadows (RendererInstance.cpp:1040-1055):
+  // vbgtao_prefilter, vbgtao_main and vbgtao_denoise.  Rules: include/oxcull.h, oxc_generate_ambient_occlusion.
+  auto generate_ambient_occlusion(AmbientOcclusionContext context) -> void {
+    context.struct_size = sizeof context;
+    check(oxc_generate_ambient_occlusion(ctx_, &context, stream_));
   }
   auto build_meshlet_bounds(oxc_meshlet_bounds_desc desc) -> void {
     desc.struct_size = sizeof desc;

@@ -49,5 +49,10 @@ int main(int argc, char**) {
   } catch (const std::exception& e) {
     std::printf("expected (no attachments bound): %s\n", e.what());
   }
+  try {  // RendererInstance.cpp:1040-1055: the ambient occlusion term pbr_apply reads
+    self.generate_ambient_occlusion(AmbientOcclusionContext{});
+  } catch (const std::exception& e) {
+    std::printf("expected (no attachments bound): %s\n", e.what());
+  }
   return 0;
 }

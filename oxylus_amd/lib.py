@@ -28,7 +28,7 @@ STAGE_TRIANGLES = 4
 STAGE_ALL = 7
 
 TUNE_ASYNC_MTEST_BLOCKS_PER_CU, TUNE_ASYNC_TRI_BLOCKS_PER_CU, TUNE_RASTER_BIG_CAPACITY, TUNE_TRI_BLOCKS_PER_CU, TUNE_MV_EXPAND_ASYNC, TUNE_TRI_LOADS = 0, 1, 2, 3, 5, 7  # oxc_debug_set_tuning knobs
-TUNE_VSM_DRAW_STATS, TUNE_VSM_DRAW_CAPACITY, TUNE_VSM_RESOLVE_STATS, TUNE_CONTACT_SHADOWS_STATS = 8, 9, 10, 11
+TUNE_VSM_DRAW_STATS, TUNE_VSM_DRAW_CAPACITY, TUNE_VSM_RESOLVE_STATS, TUNE_CONTACT_SHADOWS_STATS, TUNE_AMBIENT_OCCLUSION_STATS = 8, 9, 10, 11, 12
 
 
 class Buffer(C.Structure):
@@ -330,6 +330,30 @@ class ContactShadowsContext(C.Structure):
     ]
 
 
+class AmbientOcclusionContext(C.Structure):
+    """oxc_ambient_occlusion_context (include/oxcull.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("view", C.c_float * 16),
+        ("projection", C.c_float * 16),
+        ("resolution", C.c_float * 2),
+        ("far_clip", C.c_float),
+        ("thickness", C.c_float),
+        ("slice_count", C.c_uint32),
+        ("samples_per_slice_side", C.c_uint32),
+        ("effect_radius", C.c_float),
+        ("noise_index", C.c_uint32),
+        ("final_power", C.c_float),
+        ("depth_attachment", Image),
+        ("normal_attachment", Buffer),
+        ("hilbert_noise", Buffer),
+        ("prefiltered_depth", Image),
+        ("depth_differences", Buffer),
+        ("noisy_occlusion", Buffer),
+        ("ambient_occlusion_attachment", Buffer),
+    ]
+
+
 # every symbol include/oxcull.h declares
 EXPORTS = [
     "oxc_abi_version",
@@ -367,6 +391,8 @@ EXPORTS = [
     "oxc_debug_vsm_resolve_stats",
     "oxc_contact_shadows",
     "oxc_debug_contact_shadows_stats",
+    "oxc_generate_ambient_occlusion",
+    "oxc_debug_ambient_occlusion_stats",
     "oxc_comm_unique_id",
     "oxc_comm_init",
     "oxc_comm_destroy",
@@ -466,6 +492,8 @@ def load(path: str = None) -> C.CDLL:
     lib.oxc_debug_vsm_resolve_stats.argtypes = [vp, vp, vp]
     lib.oxc_contact_shadows.argtypes = [vp, C.POINTER(ContactShadowsContext), vp]
     lib.oxc_debug_contact_shadows_stats.argtypes = [vp, vp, vp]
+    lib.oxc_generate_ambient_occlusion.argtypes = [vp, C.POINTER(AmbientOcclusionContext), vp]
+    lib.oxc_debug_ambient_occlusion_stats.argtypes = [vp, vp, vp]
     for name in EXPORTS:
         if name not in ("oxc_abi_version", "oxc_destroy", "oxc_last_error", "oxc_mesh_build_lod_count", "oxc_mesh_build_destroy"):
             getattr(lib, name).restype = C.c_int

@@ -419,6 +419,61 @@ class ContactShadowsContext:
 
 
 @dataclass
+class AmbientOcclusionContext:
+    """oxc_ambient_occlusion_context: RendererInstance::generate_ambient_occlusion (Passes/PBR.cpp:179-311).  `create` takes the depth image,
+    the normal image, the Hilbert table and the camera and allocates the three intermediates and the output; the settings default to
+    GPU::VBGTAOSettings' (SceneGPU.hpp:286-293)."""
+    depth_attachment: ImageAttachment         # R32F, levels = 1: the main view's reversed-Z depth
+    normal_attachment: torch.Tensor           # int16 / uint16 [H, W, 4]
+    hilbert_noise: torch.Tensor               # int16 / uint16 [64, 64]
+    prefiltered_depth: ImageAttachment        # R32F out, 5 levels
+    depth_differences: torch.Tensor           # int32 [H, W] out: the packed edges
+    noisy_occlusion: torch.Tensor             # int16 [H, W] out: binary16 bits
+    ambient_occlusion_attachment: torch.Tensor  # int16 [H, W] out: binary16 bits
+    view: list                                # column-major float[16], as projection
+    projection: list
+    resolution: tuple
+    far_clip: float
+    thickness: float = 0.25
+    slice_count: int = 3
+    samples_per_slice_side: int = 3
+    effect_radius: float = 0.5
+    noise_index: int = 0
+    final_power: float = 2.2
+
+    @staticmethod
+    def create(depth, normal, hilbert_noise, view, projection, far_clip: float, resolution=None, thickness: float = 0.25, slice_count: int = 3,
+               samples_per_slice_side: int = 3, effect_radius: float = 0.5, noise_index: int = 0, final_power: float = 2.2) -> "AmbientOcclusionContext":
+        d = depth if isinstance(depth, ImageAttachment) else ImageAttachment.depth(depth)
+        dev = d.data.device
+        pre = ImageAttachment.hiz(d.width, d.height, dev, levels=5)
+        z16 = lambda: torch.zeros((d.height, d.width), dtype=torch.int16, device=dev)  # noqa: E731
+        res = (float(d.width), float(d.height)) if resolution is None else (float(resolution[0]), float(resolution[1]))
+        return AmbientOcclusionContext(d, normal, hilbert_noise, pre, torch.zeros((d.height, d.width), dtype=torch.int32, device=dev), z16(), z16(),
+                                       [float(x) for x in view], [float(x) for x in projection], res, float(far_clip), float(thickness),
+                                       int(slice_count), int(samples_per_slice_side), float(effect_radius), int(noise_index), float(final_power))
+
+    def c(self) -> L.AmbientOcclusionContext:
+        c = L.AmbientOcclusionContext()
+        c.struct_size = C.sizeof(L.AmbientOcclusionContext)
+        for i in range(16):
+            c.view[i] = float(self.view[i])
+            c.projection[i] = float(self.projection[i])
+        c.resolution[0], c.resolution[1] = float(self.resolution[0]), float(self.resolution[1])
+        c.far_clip, c.thickness, c.effect_radius, c.final_power = float(self.far_clip), float(self.thickness), float(self.effect_radius), float(self.final_power)
+        c.slice_count, c.samples_per_slice_side = int(self.slice_count), int(self.samples_per_slice_side)
+        c.noise_index = int(self.noise_index) & 0xFFFFFFFF
+        c.depth_attachment = self.depth_attachment.c()
+        c.normal_attachment = _buf(self.normal_attachment)
+        c.hilbert_noise = _buf(self.hilbert_noise)
+        c.prefiltered_depth = self.prefiltered_depth.c()
+        c.depth_differences = _buf(self.depth_differences)
+        c.noisy_occlusion = _buf(self.noisy_occlusion)
+        c.ambient_occlusion_attachment = _buf(self.ambient_occlusion_attachment)
+        return c
+
+
+@dataclass
 class MainGeometryContext:
     """The fields generate_hiz uses (RendererInstance.hpp:199-216)."""
     depth_attachment: ImageAttachment
@@ -654,6 +709,22 @@ class RendererInstance:
         self._check(self._lib.oxc_debug_contact_shadows_stats(self._ctx, C.cast(out, C.c_void_p), self._stream(stream)))
         names = ("non_sky_pixels", "taps", "miss", "hit_zero", "hit_partial", "hit_one", "rejected", "n_lower", "n_between", "n_upper", "end_clip",
                  "start_moved")
+        return {k: int(v) for k, v in zip(names, out)}
+
+    def generate_ambient_occlusion(self, context: AmbientOcclusionContext, stream=None):
+        """Passes/PBR.cpp:179-311 (vbgtao_prefilter, vbgtao_main, vbgtao_denoise): the ambient occlusion term pbr_apply reads, into
+        `context.ambient_occlusion_attachment` as binary16 (include/oxcull.h, oxc_generate_ambient_occlusion)."""
+        c = context.c()
+        self._keep = context
+        self._check(self._lib.oxc_generate_ambient_occlusion(self._ctx, C.byref(c), self._stream(stream)))
+
+    def debug_ambient_occlusion_stats(self, stream=None) -> dict:
+        """What the last generate_ambient_occlusion did, after debug_set_tuning(L.TUNE_AMBIENT_OCCLUSION_STATS, 1) (measurement hook;
+        synchronises)."""
+        out = (C.c_uint32 * 15)()
+        self._check(self._lib.oxc_debug_ambient_occlusion_stats(self._ctx, C.cast(out, C.c_void_p), self._stream(stream)))
+        names = ("non_sky_pixels", "samples", "mip0", "mip1", "mip2", "mip3", "mip4", "fractional", "result_one", "result_partial", "result_zero",
+                 "zero_width", "sign_minus", "sign_zero", "sign_plus")
         return {k: int(v) for k, v in zip(names, out)}
 
     def debug_vsm_draw_stats(self, stream=None) -> dict:

@@ -716,3 +716,24 @@ def normals_from_depth(depth: torch.Tensor, inv_projection_view, camera_position
     folded = (1.0 - q.flip(-1).abs()) * sign
     e = torch.where(n[..., 2:3] <= 0, folded, q)
     return torch.cat([e, e], dim=-1).to(torch.float16).view(torch.int16).contiguous()
+
+
+def hilbert_noise_lut() -> torch.Tensor:
+    """The 64 x 64 Hilbert index table the engine uploads once for VBGTAO's noise (RendererInstance.cpp:150-177), int16 [64][64] holding the
+    u16 values: entry [y][x] is the position of cell (x, y) on the order-6 Hilbert curve.  Per level, from 32 down to 1: the quadrant (rx, ry)
+    of the cell adds level^2 * ((3 * rx) ^ ry); in the two lower-y quadrants the cell is transposed, after a point reflection when rx is set."""
+    n = 64
+    lut = [[0] * n for _ in range(n)]
+    for y in range(n):
+        for x in range(n):
+            px, py, index, level = x, y, 0, n // 2
+            while level > 0:
+                rx, ry = int((px & level) > 0), int((py & level) > 0)
+                index += level * level * ((3 * rx) ^ ry)
+                if ry == 0:
+                    if rx == 1:
+                        px, py = (n - 1) - px, (n - 1) - py
+                    px, py = py, px
+                level //= 2
+            lut[y][x] = index
+    return torch.tensor(lut, dtype=torch.int32).to(torch.int16)

@@ -1,0 +1,276 @@
+"""oxc_generate_ambient_occlusion on the GPU: every output byte-identical to tests/ambient_occlusion_model.py -- the five prefiltered depth
+levels, depth_differences, noisy_occlusion and the final image -- on a depth drawn by oxc_draw_visbuffer at the four presets with the device's
+counters, an odd extent under a rotated camera, an all-sky image, non-finite / negative / denormal texels and normals, the hand-made pit that
+reaches an exactly-0.0 result, resolve + contact shadows + ambient occlusion captured into one graph, and invalid arguments."""
+import numpy as np
+import pytest
+import torch
+
+import ambient_occlusion_model as AM
+from test_ambient_occlusion_model import MAIN, MAIN_SEED, MAIN_SIZE, PROJ, assert_not_degenerate, camera_of, far_clip_of, flat_normals, pit_image
+from test_contact_shadows_model import I16
+from test_gpu_contact_shadows import drawn_depth, rotated_camera
+
+pytestmark = pytest.mark.gpu
+
+
+def hilbert_gpu():
+    from oxylus_amd.synth import hilbert_noise_lut
+
+    return hilbert_noise_lut().cuda()
+
+
+def context(depth, normal, view, proj, far, **kw):
+    from oxylus_amd.renderer import AmbientOcclusionContext
+
+    return AmbientOcclusionContext.create(depth, normal, hilbert_gpu(), view, proj, far, **kw)
+
+
+def got_of(ctx) -> dict:
+    torch.cuda.synchronize()
+    u16 = lambda t: t.cpu().numpy().view(np.uint16).copy()  # noqa: E731
+    return {"levels": [ctx.prefiltered_depth.level(k).cpu().numpy().copy() for k in range(5)],
+            "depth_differences": ctx.depth_differences.cpu().numpy().view(np.uint32).copy(), "noisy_occlusion": u16(ctx.noisy_occlusion),
+            "ambient_occlusion": u16(ctx.ambient_occlusion_attachment)}
+
+
+def want_of(ctx, stats=None) -> dict:
+    d = ctx.depth_attachment
+    return AM.generate(d.data.view(d.height, d.width).cpu().numpy(), ctx.normal_attachment.cpu().numpy(), ctx.hilbert_noise.cpu().numpy().view(np.uint16),
+                       ctx.view, ctx.projection, ctx.resolution, ctx.far_clip, ctx.thickness, ctx.slice_count, ctx.samples_per_slice_side,
+                       ctx.effect_radius, ctx.noise_index, ctx.final_power, stats=stats)
+
+
+def same(got: dict, want: dict):
+    for k in range(5):
+        bad = int((got["levels"][k].view(np.uint32) != want["levels"][k].view(np.uint32)).sum())
+        assert bad == 0, f"prefiltered level {k}: {bad} of {got['levels'][k].size} texels differ"
+    for name in ("depth_differences", "noisy_occlusion", "ambient_occlusion"):
+        bad = int((got[name] != want[name]).sum())
+        assert bad == 0, f"{name}: {bad} of {got[name].size} pixels differ"
+
+
+def check(ctx, stats=None) -> dict:
+    got = got_of(ctx)
+    same(got, want_of(ctx, stats))
+    return got
+
+
+def main_frame(renderer, size=MAIN_SIZE, seed=MAIN_SEED):
+    from oxylus_amd.synth import normals_from_depth
+
+    cpu, depth = drawn_depth(renderer, size, size, seed)
+    inv, view, proj, far = camera_of(cpu)
+    return depth, normals_from_depth(depth, inv, (0.0, 0.0, 0.0)), view, proj, far
+
+
+@pytest.mark.parametrize("preset", ["low", "medium", "high", "ultra"])
+def test_drawn_frame_at_the_four_presets(renderer, preset):
+    """occluder_scene(61) drawn at 512 x 512 (the checker needs a few seconds per preset at that size, and with effect_radius 3.0 the sample
+    distances still reach mip 4), normals from synth.normals_from_depth: all outputs == checker, device counters == checker's.  At ultra every
+    counter class the scene can produce is non-zero by the floors of tests/test_ambient_occlusion_model.py, judged by the checker on the drawn
+    depth; an exactly-0.0 result and a zero sign_norm cannot come from this scene (no fully enclosed pixel, no NaN): they are reached by
+    test_the_pit_reaches_exactly_zero and test_all_sky_and_non_finite_texels."""
+    from oxylus_amd import lib as L
+
+    depth, normal, view, proj, far = main_frame(renderer)
+    slices, samples = AM.PRESETS[preset]
+    ctx = context(depth, normal, view, proj, far, slice_count=slices, samples_per_slice_side=samples, **MAIN)
+    renderer.debug_set_tuning(L.TUNE_AMBIENT_OCCLUSION_STATS, 1)
+    try:
+        renderer.generate_ambient_occlusion(ctx)
+        st = {}
+        check(ctx, st)
+        dev = renderer.debug_ambient_occlusion_stats()
+    finally:
+        renderer.debug_set_tuning(L.TUNE_AMBIENT_OCCLUSION_STATS, 0)
+    counts = AM.counters(st)
+    print("checker", counts)
+    print("device", dev)
+    assert dev == counts
+    if preset == "ultra":
+        assert_not_degenerate(st)
+    for t in (ctx.depth_differences, ctx.noisy_occlusion, ctx.ambient_occlusion_attachment, ctx.prefiltered_depth.data):
+        t.fill_(-5)
+    renderer.generate_ambient_occlusion(ctx)  # the plain instantiation writes the same images
+    check(ctx)
+
+
+@pytest.mark.parametrize("noise_index,final_power", [(0, 2.2), (37, 1.0), (4294967295, 2.2)])
+def test_second_shape_odd_extent_rotated_camera(renderer, noise_index, final_power):
+    """1001 x 563, a synthetic depth of overlapping quads under a rotated camera (a view matrix without an exact entry), the high preset: the engine's struct default final_power 2.2, final_power 1.0, and
+    noise_index 37 and 2^32 - 1 (used mod 64: 63)."""
+    from oxylus_amd.synth import make_depth, normals_from_depth
+
+    depth = make_depth(1001, 563, 48, seed=11).cuda()
+    inv, view, proj, _ = rotated_camera()
+    normal = normals_from_depth(depth, inv)
+    ctx = context(depth, normal, view, proj, far_clip_of(proj), noise_index=noise_index, final_power=final_power, effect_radius=1.5)
+    assert (ctx.slice_count, ctx.samples_per_slice_side, ctx.thickness) == (3, 3, 0.25)
+    renderer.generate_ambient_occlusion(ctx)
+    st = {}
+    got = check(ctx, st)
+    ao = AM.from_half_bits(got["ambient_occlusion"])
+    c = AM.counters(st)
+    assert ((ao > 0) & (ao < 1)).sum() > 1000 and c["non_sky_pixels"] > 10000 and c["fractional"] > 1000 and c["sign_minus"] > 0 and c["sign_plus"] > 0
+
+
+def test_all_sky_and_non_finite_texels(renderer):
+    depth, normal, view, proj, far = main_frame(renderer, 256, 65)
+    ctx = context(depth, normal, view, proj, far, **MAIN)
+    renderer.generate_ambient_occlusion(ctx)
+    check(ctx)
+    # NaN, infinities, negative, denormal, huge and -0.0 texels over covered and sky pixels; NaN, Inf and denormal halves in the normals
+    ys, xs = np.nonzero(depth.cpu().numpy() != 0)
+    assert len(xs) > 2000
+    values = (float("nan"), float("inf"), -float("inf"), -0.0, 1e-30, 3e38, -0.5, 1e-42, -1e-42)
+    for k in range(180):
+        depth[int(ys[k * 11]), int(xs[k * 11])] = values[k % len(values)]
+    for k in range(40):
+        depth[(k * 37) % 256, (k * 91 + 5) % 256] = values[k % len(values)]
+    halves = (0x7E00, 0x7C00, -0x0400, 0x0001, -0x7FFF, 0x03FF)  # NaN, +Inf, -Inf (0xFC00), +-denormals
+    for k in range(120):
+        normal[int(ys[k * 13 + 3]), int(xs[k * 13 + 3]), 2 + k % 2] = halves[k % len(halves)]
+    renderer.generate_ambient_occlusion(ctx)
+    st = {}
+    got = check(ctx, st)
+    assert np.isfinite(AM.from_half_bits(got["ambient_occlusion"])).all() and AM.counters(st)["sign_zero"] > 0
+    depth.zero_()
+    for t in (ctx.noisy_occlusion, ctx.ambient_occlusion_attachment, ctx.depth_differences):
+        t.fill_(-5)
+    renderer.generate_ambient_occlusion(ctx)
+    got = check(ctx)
+    assert (got["ambient_occlusion"] == 0x3C00).all() and (got["noisy_occlusion"] == 0x3C00).all() and (got["depth_differences"] == 0xFFFFFFFF).all()
+
+
+def test_the_pit_reaches_exactly_zero(renderer):
+    """The hand-made image of tests/test_ambient_occlusion_model.py::test_a_fully_occluded_pixel_is_exactly_zero: the result class the drawn
+    scene cannot produce."""
+    from oxylus_amd import lib as L
+
+    d, kw = pit_image()
+    far = kw.pop("far")
+    ctx = context(torch.from_numpy(d).cuda(), torch.from_numpy(flat_normals(33, 33).view(np.int16)).cuda(), I16, PROJ, far, **kw)
+    renderer.debug_set_tuning(L.TUNE_AMBIENT_OCCLUSION_STATS, 1)
+    try:
+        renderer.generate_ambient_occlusion(ctx)
+        st = {}
+        got = check(ctx, st)
+        dev = renderer.debug_ambient_occlusion_stats()
+    finally:
+        renderer.debug_set_tuning(L.TUNE_AMBIENT_OCCLUSION_STATS, 0)
+    assert got["noisy_occlusion"][16, 16] == 0 and dev == AM.counters(st) and dev["result_zero"] >= 1
+
+
+def test_resolve_contact_shadows_and_ambient_occlusion_in_one_graph(renderer):
+    from oxylus_amd.synth import normals_from_depth
+    from test_gpu_contact_shadows import check as check_contact
+    from test_gpu_contact_shadows import context as contact_context
+    from test_gpu_contact_shadows import got_of as contact_got
+    from test_contact_shadows_model import identity_camera
+    from test_gpu_vsm_resolve import Frame
+
+    f = Frame(renderer, 320, 320, seed=66)
+    f.shadow_path()  # eager; every scratch grows here
+    cctx = contact_context(f.depth, identity_camera(f.gpu), steps=8, thickness=0.3, shadow_length=0.3)
+    inv, view, proj, far = camera_of(f.gpu)
+    actx = context(f.depth, normals_from_depth(f.depth, inv, (0.0, 0.0, 0.0)), view, proj, far, **MAIN)
+    renderer.contact_shadows(cctx)
+    renderer.generate_ambient_occlusion(actx)
+    resolved = f.check()
+    contact = check_contact(cctx)
+    ao = check(actx)
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=s):
+        renderer.resolve_shadowmap(f.rctx, stream=s)
+        renderer.contact_shadows(cctx, stream=s)
+        renderer.generate_ambient_occlusion(actx, stream=s)
+    for _ in range(2):
+        f.rctx.resolved_shadows_attachment.data.fill_(-5.0)
+        cctx.contact_shadows_attachment.data.fill_(-5.0)
+        for t in (actx.depth_differences, actx.noisy_occlusion, actx.ambient_occlusion_attachment, actx.prefiltered_depth.data):
+            t.fill_(-5)
+        torch.cuda.synchronize()
+        g.replay()
+        assert np.array_equal(f.got().view(np.uint32), resolved.view(np.uint32))
+        assert np.array_equal(contact_got(cctx).view(np.uint32), contact.view(np.uint32))
+        same(got_of(actx), ao)
+
+
+def test_invalid_arguments(renderer):
+    from oxylus_amd import lib as L
+    from oxylus_amd.renderer import ImageAttachment
+
+    depth, normal, view, proj, far = main_frame(renderer, 128, 67)
+    ctx = context(depth, normal, view, proj, far, **MAIN)
+    outputs = (ctx.depth_differences, ctx.noisy_occlusion, ctx.ambient_occlusion_attachment, ctx.prefiltered_depth.data)
+    for t in outputs:
+        t.fill_(-5)
+
+    def bad(**kw):
+        saved = {k: getattr(ctx, k) for k in kw}
+        for k, v in kw.items():
+            setattr(ctx, k, v)
+        with pytest.raises(L.OxcError) as e:
+            renderer.generate_ambient_occlusion(ctx)
+        assert e.value.status == L.OXC_INVALID_ARG
+        for k, v in saved.items():
+            setattr(ctx, k, v)
+
+    def bad_c(edit):
+        c = ctx.c()
+        edit(c)
+        assert renderer._lib.oxc_generate_ambient_occlusion(renderer._ctx, c, renderer._stream(None)) == L.OXC_INVALID_ARG
+
+    inf, nan = float("inf"), float("nan")
+    for v in (0, 17):
+        bad(slice_count=v)
+    for v in (0, 9):
+        bad(samples_per_slice_side=v)
+    for name in ("thickness", "effect_radius", "final_power", "far_clip"):
+        for v in (0.0, -1.0, inf, nan):
+            bad(**{name: v})
+    for v in (0.0, -1.0, inf, nan):
+        bad(resolution=(v, 128.0))
+        bad(resolution=(128.0, v))
+    dev = depth.device
+    bad(prefiltered_depth=ImageAttachment.hiz(128, 128, dev, levels=4))
+    bad(prefiltered_depth=ImageAttachment.hiz(128, 128, dev, levels=6))
+    bad(prefiltered_depth=ImageAttachment.hiz(64, 128, dev, levels=5))
+    bad(prefiltered_depth=ImageAttachment.hiz(128, 64, dev, levels=5))
+    small16 = torch.zeros((128, 64), dtype=torch.int16, device=dev)
+    bad(noisy_occlusion=small16)
+    bad(ambient_occlusion_attachment=small16)
+    bad(depth_differences=torch.zeros((128, 64), dtype=torch.int32, device=dev))
+    bad(normal_attachment=normal[:64].contiguous())
+    bad(hilbert_noise=torch.zeros((64, 32), dtype=torch.int16, device=dev))
+    bad(normal_attachment=normal.view(-1)[2:])  # 4-byte aligned only
+    odd = torch.zeros(128 * 128 * 2 + 2, dtype=torch.int16, device=dev)
+    bad(depth_differences=odd[1:])  # 2-byte aligned only
+
+    def levels2(c):
+        c.depth_attachment.levels = 2
+    bad_c(levels2)
+
+    def wide(c):
+        c.depth_attachment.width = c.prefiltered_depth.width = 65537
+    bad_c(wide)
+
+    def misaligned_level(c):
+        c.prefiltered_depth.level_offset[2] += 2
+    bad_c(misaligned_level)
+
+    def size4(c):
+        c.struct_size = 4
+    bad_c(size4)
+
+    def null_out(c):
+        c.ambient_occlusion_attachment.dptr = None
+    bad_c(null_out)
+    torch.cuda.synchronize()
+    for t in outputs:
+        assert (t == -5).all()  # nothing was written
+    renderer.generate_ambient_occlusion(ctx)  # and the context still runs
+    check(ctx)
