@@ -121,7 +121,8 @@ def shadow_of(frac):
 
 def contact_shadows(depth, inv_projection_view, view, projection, near_clip, sun_dir, steps=8, thickness=0.1, shadow_length=0.01, stats=None):
     """float32 [H, W] depth -> float32 [H, W] contact shadow term.  `stats` (a dict) receives per-pixel arrays: outcome, n (0 for sky),
-    n_class (-1 for sky), taps, end_clip, start_moved."""
+    n_class (-1 for sky), taps, end_clip, start_moved; and clamped_taps, the number of taps whose four-texel footprint reached past the
+    left / right / top / bottom border and was clamped."""
     depth = np.ascontiguousarray(depth, dtype=np.float32)
     H, W = depth.shape
     out = np.ones((H, W), dtype=np.float32)
@@ -153,6 +154,7 @@ def contact_shadows(depth, inv_projection_view, view, projection, near_clip, sun
         distance = np.zeros(count, dtype=np.float32)
         penetration = np.zeros(count, dtype=np.float32)
         taps = np.zeros(count, dtype=np.int64)
+        clamped = {"left": 0, "right": 0, "top": 0, "bottom": 0}  # taps whose 2 x 2 footprint was pulled back inside at that side
         for step in range(int(n.max()) if count else 0):
             k = np.nonzero(alive & (step < n))[0]
             if not len(k):
@@ -162,7 +164,10 @@ def contact_shadows(depth, inv_projection_view, view, projection, near_clip, sun
             ux, uy = (c[0] * F(0.5) + F(0.5)) * F(W), (c[1] * F(0.5) + F(0.5)) * F(H)
             ray_depth = F(1.0) / c[2]
             linear, unfiltered, _ = tap(depth, ux, uy)
-            dist = np.fmax(linear, unfiltered) * BIAS_SCALE - ray_depth
+            jx, jy = cvt_i32_sat(np.floor(ux - F(0.5))), cvt_i32_sat(np.floor(uy - F(0.5)))
+            for side, over in (("left", jx < 0), ("right", jx + 1 > W - 1), ("top", jy < 0), ("bottom", jy + 1 > H - 1)):
+                clamped[side] += int(over.sum())
+            dist =np.fmax(linear, unfiltered) * BIAS_SCALE - ray_depth
             pen = ray_depth - np.fmin(linear, unfiltered)
             distance[k], penetration[k] = dist, pen
             taps[k] += 1
@@ -178,6 +183,7 @@ def contact_shadows(depth, inv_projection_view, view, projection, near_clip, sun
         oc[ys, xs] = np.where(~intersected, MISS, np.where(~hit, REJECTED, np.where(res == 0, HIT_ZERO, np.where(res == 1, HIT_ONE, HIT_PARTIAL))))
         full = {"n": (n, 0), "n_class": (ncls, -1), "taps": (taps, 0), "end_clip": (clip < 1, False), "start_moved": (moved > 0, False)}
         stats["outcome"] = oc
+        stats["clamped_taps"] = clamped
         for name, (vals, fill) in full.items():
             a = np.full((H, W), fill, dtype=np.asarray(vals).dtype if name in ("end_clip", "start_moved") else np.int64)
             a[ys, xs] = vals
