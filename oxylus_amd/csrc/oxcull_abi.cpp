@@ -82,12 +82,15 @@ struct oxc_ctx {
   uint32_t vsm_draw_capacity = 0;          // entries of the big-pair and clip queues of that scratch (the tile queue holds 4x as many)
   uint32_t vsm_draw_capacity_request = 0;  // oxc_debug_set_tuning(OXC_TUNE_VSM_DRAW_CAPACITY): used by the first shadow draw
   bool vsm_draw_stats = false;             // oxc_debug_set_tuning(OXC_TUNE_VSM_DRAW_STATS): counting kernels
-  uint32_t* vsm_resolve_stats = nullptr;   // oxc_resolve_shadowmap with OXC_TUNE_VSM_RESOLVE_STATS: u32[8] the counting kernel adds to
-  bool vsm_resolve_stats_on = false;
-  uint32_t* contact_shadows_stats = nullptr;  // oxc_contact_shadows with OXC_TUNE_CONTACT_SHADOWS_STATS: u32[12] the counting kernel adds to
-  bool contact_shadows_stats_on = false;
-  uint32_t* ambient_occlusion_stats = nullptr;  // oxc_generate_ambient_occlusion with OXC_TUNE_AMBIENT_OCCLUSION_STATS: u32[15] (16 allocated)
-  bool ambient_occlusion_stats_on = false;
+  // The counters a pass's counting instantiation adds to: switched by oxc_debug_set_tuning, allocated by the first counting call
+  // (arm_counters), read by the pass's oxc_debug_*_stats (read_counters).
+  struct PassCounters {
+    uint32_t* dev = nullptr;
+    bool on = false;
+  };
+  PassCounters vsm_resolve_stats;        // OXC_TUNE_VSM_RESOLVE_STATS: u32[8]
+  PassCounters contact_shadows_stats;    // OXC_TUNE_CONTACT_SHADOWS_STATS: u32[12]
+  PassCounters ambient_occlusion_stats;  // OXC_TUNE_AMBIENT_OCCLUSION_STATS: u32[15] (16 allocated)
   void* comm = nullptr;           // ncclComm_t (oxc_comm_init)
   uint32_t comm_rank = 0, comm_world = 0;
   // counter slots
@@ -367,6 +370,144 @@ struct KernelTimer {
 
 bool image_ok(const oxc_image& im) { return im.dptr && im.width && im.height && im.levels >= 1 && im.levels <= 13; }
 
+// ---- the rules the VSM entry points (page update, shadow draw, shadow resolve) and the per-pixel passes (shadow resolve, contact
+// shadows, ambient occlusion) share.  `entry` is the entry point's name as oxc_last_error prefixes it.
+#define OXC_TRY(expr)                 \
+  do {                                \
+    oxc_status _t = (expr);           \
+    if (_t != OXC_OK) return _t;      \
+  } while (0)
+
+// OXC_INVALID_ARG with the message "<entry>: <what><more><rest>"
+oxc_status bad_arg(oxc_ctx* ctx, const char* entry, const char* what, const char* more = "", const char* rest = "") {
+  std::string m;
+  for (const char* part : {entry, ": ", what, more, rest}) m += part;
+  return fail(ctx, OXC_INVALID_ARG, m.c_str());
+}
+
+struct VsmShape {
+  int32_t n, ps, phys, layers;  // page_table_size, page_size, physical_page_table_size, clipmap_count
+  uint32_t P, phys_count;       // physical pages per side, in all
+  uint64_t entries;             // page-table entries of all clipmaps
+};
+
+// The shape rule, from the four fields every VSM context carries under the same names.
+template <class Context>
+oxc_status vsm_shape(oxc_ctx* ctx, const char* entry, const Context& c, VsmShape& sh) {
+  const int32_t n = c.page_table_size, ps = c.page_size, phys = c.physical_page_table_size, layers = c.clipmap_count;
+  if (layers < 1 || layers > 16) return bad_arg(ctx, entry, "clipmap_count must be 1..16");
+  if (n < 8 || n > 256 || n % 8) return bad_arg(ctx, entry, "page_table_size must be a multiple of 8 in [8, 256]");
+  if (ps < 16 || ps % 16 || phys < ps || phys % ps) return bad_arg(ctx, entry, "page_size must be a multiple of 16 and divide physical_page_table_size");
+  const uint32_t P = (uint32_t)(phys / ps);
+  if ((uint64_t)P * P > 65536u) return bad_arg(ctx, entry, "more than 65536 physical pages (16 address bits)");
+  sh = {n, ps, phys, layers, P, P * P, (uint64_t)layers * n * n};
+  return OXC_OK;
+}
+
+// virtual_page_table and vsm_clipmaps_buffer hold the shape's entries and records
+template <class Context>
+oxc_status vsm_tables(oxc_ctx* ctx, const char* entry, const Context& c, const VsmShape& sh) {
+  if (!c.virtual_page_table.dptr || c.virtual_page_table.bytes < sh.entries * 4u) return bad_arg(ctx, entry, "virtual_page_table smaller than clipmap_count * n * n u32");
+  if (!c.vsm_clipmaps_buffer.dptr || c.vsm_clipmaps_buffer.bytes < (uint64_t)sh.layers * sizeof(oxc_virtual_clipmap))
+    return bad_arg(ctx, entry, "vsm_clipmaps_buffer smaller than clipmap_count records");
+  return OXC_OK;
+}
+
+oxc_status vsm_dirty_flags(oxc_ctx* ctx, const char* entry, const oxc_buffer& flags, const VsmShape& sh) {
+  if (!flags.dptr || flags.bytes < (uint64_t)sh.layers * 4u) return bad_arg(ctx, entry, "vsm_clipmap_dirty_flags_buffer smaller than clipmap_count u32");
+  return OXC_OK;
+}
+
+// The clipmap index without log2 (include/oxcull.h, mark visible pages): k < *always has (double)k - (double)bias < 0 and always counts;
+// k >= *always counts when r > thr[k], the largest binary32 <= exp2(k - bias) -- (double)r > T <=> r > that value, r being a binary32.
+void vsm_level_thresholds(int layers, float bias, uint32_t* always, float* thr) {
+  *always = 0;
+  for (int k = 0; k + 1 < layers; k++) {
+    const double dk = (double)k - (double)bias;
+    if (dk < 0.0) {
+      *always = (uint32_t)(k + 1);
+      thr[k] = 0.0f;
+      continue;
+    }
+    const double T = std::exp2(dk);
+    float f = (float)T;
+    if ((double)f > T) f = std::nextafter(f, -INFINITY);
+    thr[k] = f;
+  }
+}
+
+// The per-call constants by which a pixel selects its clipmap, binary32 in the Slang's order (include/oxcull.h).  One function for the
+// page update's VsmArgs and the resolve's VsmResolveArgs: the two kernels must select the same clipmap for the same pixel.
+template <class Args, class Context>
+void clipmap_selection_constants(Args& a, const Context& c, const VsmShape& sh) {
+  a.off_x = (1.0f / c.resolution[0]) * 0.5f;
+  a.off_y = (1.0f / c.resolution[1]) * 0.5f;
+  const float scale_ratio = (float)(sh.n - 1) / (float)sh.n;  // get_first_clipmap_texel_length, rmvsm.slang:148-155
+  const float effective_width = c.first_clipmap_width * scale_ratio;
+  a.texel_len = (effective_width * 2.0f) / c.virtual_extent;
+  vsm_level_thresholds(sh.layers, c.clipmap_selection_bias, &a.lvl_always, a.lvl_thr);
+}
+
+// The image contract of a per-pixel pass: an extent of at most 65536, the depth one R32F level at offset 0 and, where the pass writes an
+// R32F image (`out`, the field `out_name`), that image of the depth's extent.  An empty image is valid: the pass is a no-op then.
+oxc_status pixel_images(oxc_ctx* ctx, const char* entry, const oxc_image& depth, const oxc_image* out, const char* out_name, uint64_t& pixels) {
+  pixels = (uint64_t)depth.width * depth.height;
+  if (depth.width > 65536u || depth.height > 65536u) return bad_arg(ctx, entry, "depth extent beyond 65536");
+  if (pixels && (!depth.dptr || depth.levels != 1 || depth.level_offset[0] != 0)) return bad_arg(ctx, entry, "depth_attachment must be one R32F level at offset 0");
+  if (out && (out->width != depth.width || out->height != depth.height || (pixels && (!out->dptr || out->levels != 1 || out->level_offset[0] != 0))))
+    return bad_arg(ctx, entry, out_name, " must be one R32F level of the depth attachment's extent");
+  return OXC_OK;
+}
+
+// not a buffer of one `texel`-byte texel per pixel, aligned to its texel
+bool bad_pixel_buffer(const oxc_buffer& b, uint64_t pixels, uint64_t texel) {
+  return pixels && (!b.dptr || b.bytes < pixels * texel || (reinterpret_cast<uintptr_t>(b.dptr) & (texel - 1u)));
+}
+
+// The counting instantiation's counters for this call, zeroed on `s`: `bytes` of them, allocated by the first counting call (never inside
+// a capture).  nullptr while the pass is not counting.
+oxc_status arm_counters(oxc_ctx* ctx, const char* entry, const char* malloc_label, oxc_ctx::PassCounters& pc, size_t bytes, hipStream_t s, uint32_t** out) {
+  if (!pc.on) return OXC_OK;
+  if (!pc.dev) {
+    if (stream_is_capturing(s)) return bad_arg(ctx, entry, "the counters are allocated by the first counting call; make one outside the capture");
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&pc.dev), bytes);
+    if (e != hipSuccess) return fail(ctx, OXC_OUT_OF_MEMORY, malloc_label, e);
+  }
+  OXC_HIP(ctx, hipMemsetAsync(pc.dev, 0, bytes, s));
+  *out = pc.dev;
+  return OXC_OK;
+}
+
+// oxc_debug_<pass>_stats: `bytes` of the counters of the last counting call of `pass` to the host; synchronises
+oxc_status read_counters(oxc_ctx* ctx, const char* entry, const char* pass, oxc_ctx::PassCounters oxc_ctx::*which, uint32_t* host_out, size_t bytes, void* hip_stream) {
+  if (!ctx) return OXC_INVALID_ARG;
+  if (!host_out) return bad_arg(ctx, entry, "null pointer");
+  const uint32_t* dev = (ctx->*which).dev;
+  if (!dev) return bad_arg(ctx, entry, "no counting ", pass, " call on this context yet");
+  OXC_HIP(ctx, hipSetDevice(ctx->device));
+  OXC_ORDER(ctx, hip_stream);
+  hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  OXC_HIP(ctx, hipMemcpyAsync(host_out, dev, bytes, hipMemcpyDeviceToHost, s));
+  OXC_HIP(ctx, hipStreamSynchronize(s));
+  return OXC_OK;
+}
+
+// Grows one scratch buffer of the context to `bytes` when the call wants more (`want`, in the unit `have` is kept in) than it holds:
+// device sync + free + malloc, never during stream capture (`capture_msg`).  On failure the buffer is gone and `have` is 0.
+template <class T, class N>
+oxc_status grow_scratch(oxc_ctx* ctx, hipStream_t s, T*& ptr, N& have, N want, size_t bytes, const char* capture_msg, const char* malloc_label) {
+  if (want <= have) return OXC_OK;
+  if (stream_is_capturing(s)) return fail(ctx, OXC_INVALID_ARG, capture_msg);
+  OXC_HIP(ctx, hipDeviceSynchronize());  // in-flight work may still use the old scratch
+  if (ptr) OXC_HIP(ctx, hipFree(ptr));
+  ptr = nullptr;
+  have = 0;
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&ptr), bytes);
+  if (e != hipSuccess) return fail(ctx, OXC_OUT_OF_MEMORY, malloc_label, e);
+  have = want;
+  return OXC_OK;
+}
+
 }  // namespace
 
 // Everything oxc_cull_geometry derives from (frame, context) before it touches the device.
@@ -490,9 +631,8 @@ void oxc_destroy(oxc_ctx* ctx) {
   if (ctx->raster_rows) (void)hipFree(ctx->raster_rows);
   if (ctx->vsm_scratch) (void)hipFree(ctx->vsm_scratch);
   if (ctx->vsm_draw_scratch) (void)hipFree(ctx->vsm_draw_scratch);
-  if (ctx->vsm_resolve_stats) (void)hipFree(ctx->vsm_resolve_stats);
-  if (ctx->contact_shadows_stats) (void)hipFree(ctx->contact_shadows_stats);
-  if (ctx->ambient_occlusion_stats) (void)hipFree(ctx->ambient_occlusion_stats);
+  for (const auto& pc : {ctx->vsm_resolve_stats, ctx->contact_shadows_stats, ctx->ambient_occlusion_stats})
+    if (pc.dev) (void)hipFree(pc.dev);
   if (ctx->comm) (void)oxc_comm_destroy(ctx);
   if (ctx->slots) (void)hipFree(ctx->slots);
   if (ctx->order_event) (void)hipEventDestroy(ctx->order_event);
@@ -1349,18 +1489,10 @@ oxc_status oxc_build_meshlet_bounds(oxc_ctx* ctx, const oxc_meshlet_bounds_desc*
   OXC_ORDER(ctx, hip_stream);
   // scratch: [boxes: 24 B per meshlet][fold partials: 256 x 12 words][normals: 768 B per meshlet of one chunk][counts]
   const uint32_t want = std::max(d->meshlet_count, 1u);
-  if (want > ctx->bounds_scratch_cap) {
-    if (stream_is_capturing(static_cast<hipStream_t>(hip_stream)))
-      return fail(ctx, OXC_INVALID_ARG, "build_meshlet_bounds: scratch must grow but the stream is being captured; make one un-captured call of this size first");
-    OXC_HIP(ctx, hipDeviceSynchronize());  // in-flight work may still use the old scratch
-    if (ctx->bounds_scratch) OXC_HIP(ctx, hipFree(ctx->bounds_scratch));
-    ctx->bounds_scratch = nullptr;
-    ctx->bounds_scratch_cap = 0;
-    const size_t bytes = align_up((size_t)want * 24u, 256) + 256u * 48u + (size_t)std::min(kBoundsChunk, want) * (768u + 4u);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&ctx->bounds_scratch), bytes);
-    if (e != hipSuccess) return fail(ctx, OXC_OUT_OF_MEMORY, "hipMalloc(bounds scratch)", e);
-    ctx->bounds_scratch_cap = want;
-  }
+  OXC_TRY(grow_scratch(ctx, static_cast<hipStream_t>(hip_stream), ctx->bounds_scratch, ctx->bounds_scratch_cap, want,
+                       align_up((size_t)want * 24u, 256) + 256u * 48u + (size_t)std::min(kBoundsChunk, want) * (768u + 4u),
+                       "build_meshlet_bounds: scratch must grow but the stream is being captured; make one un-captured call of this size first",
+                       "hipMalloc(bounds scratch)"));
   const uint32_t chunk = std::min(kBoundsChunk, ctx->bounds_scratch_cap);
   float* fold = ctx->bounds_scratch + align_up((size_t)ctx->bounds_scratch_cap * 24u, 256) / 4;
   float* normals = fold + 256 * 12;
@@ -1478,47 +1610,22 @@ oxc_status oxc_generate_hpb(oxc_ctx* ctx, oxc_buffer page_table, const oxc_image
   return OXC_OK;
 }
 
-}  // extern "C"
-// The clipmap index without log2 (include/oxcull.h, mark visible pages): k < *always has (double)k - (double)bias < 0 and always counts;
-// k >= *always counts when r > thr[k], the largest binary32 <= exp2(k - bias) -- (double)r > T <=> r > that value, r being a binary32.
-static void vsm_level_thresholds(int layers, float bias, uint32_t* always, float* thr) {
-  *always = 0;
-  for (int k = 0; k + 1 < layers; k++) {
-    const double dk = (double)k - (double)bias;
-    if (dk < 0.0) {
-      *always = (uint32_t)(k + 1);
-      thr[k] = 0.0f;
-      continue;
-    }
-    const double T = std::exp2(dk);
-    float f = (float)T;
-    if ((double)f > T) f = std::nextafter(f, -INFINITY);
-    thr[k] = f;
-  }
-}
-extern "C" {
-
 oxc_status oxc_update_virtual_shadowmap(oxc_ctx* ctx, const oxc_vsm_update_context* c, void* hip_stream) {
   if (!ctx) return OXC_INVALID_ARG;
   if (!c || c->struct_size != sizeof(oxc_vsm_update_context)) return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: bad context / struct_size");
-  const int32_t n = c->page_table_size, ps = c->page_size, phys = c->physical_page_table_size, layers = c->clipmap_count;
-  if (layers < 1 || layers > 16) return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: clipmap_count must be 1..16");
-  if (n < 8 || n > 256 || n % 8) return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: page_table_size must be a multiple of 8 in [8, 256]");
-  if (ps < 16 || ps % 16 || phys < ps || phys % ps) return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: page_size must be a multiple of 16 and divide physical_page_table_size");
-  const uint32_t P = (uint32_t)(phys / ps);
-  if ((uint64_t)P * P > 65536u) return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: more than 65536 physical pages (16 address bits)");
-  const uint32_t phys_count = P * P;
-  const uint64_t entries = (uint64_t)layers * n * n;
+  const char* const entry = "update_virtual_shadowmap";
+  VsmShape sh;
+  OXC_TRY(vsm_shape(ctx, entry, *c, sh));
+  const int32_t n = sh.n, ps = sh.ps, phys = sh.phys, layers = sh.layers;
+  const uint32_t P = sh.P, phys_count = sh.phys_count;
+  const uint64_t entries = sh.entries;
   const oxc_image& dimg = c->depth_attachment;
   if (c->depth_extent[0] < 0 || c->depth_extent[1] < 0 || (uint32_t)c->depth_extent[0] != dimg.width || (uint32_t)c->depth_extent[1] != dimg.height)
     return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: depth_extent must equal the depth attachment's extent");
   if (dimg.width && dimg.height && (!dimg.dptr || dimg.levels != 1 || dimg.level_offset[0] != 0))
     return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: depth_attachment must be one R32F level at offset 0");
-  if (!c->virtual_page_table.dptr || c->virtual_page_table.bytes < entries * 4u) return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: virtual_page_table smaller than clipmap_count * n * n u32");
-  if (!c->vsm_clipmaps_buffer.dptr || c->vsm_clipmaps_buffer.bytes < (uint64_t)layers * sizeof(oxc_virtual_clipmap))
-    return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: vsm_clipmaps_buffer smaller than clipmap_count records");
-  if (!c->vsm_clipmap_dirty_flags_buffer.dptr || c->vsm_clipmap_dirty_flags_buffer.bytes < (uint64_t)layers * 4u)
-    return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: vsm_clipmap_dirty_flags_buffer smaller than clipmap_count u32");
+  OXC_TRY(vsm_tables(ctx, entry, *c, sh));
+  OXC_TRY(vsm_dirty_flags(ctx, entry, c->vsm_clipmap_dirty_flags_buffer, sh));
   if (!c->dirty_physical_pages_buffer.dptr || c->dirty_physical_pages_buffer.bytes < std::min<uint64_t>(entries, phys_count) * 8u)
     return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: dirty_physical_pages_buffer smaller than min(pages, physical pages) u32x2");
   if (!c->clear_cmd_buffer.dptr || c->clear_cmd_buffer.bytes < 12u) return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: clear_cmd_buffer smaller than a VkDispatchIndirectCommand");
@@ -1545,17 +1652,9 @@ oxc_status oxc_update_virtual_shadowmap(oxc_ctx* ctx, const oxc_vsm_update_conte
   OXC_ORDER(ctx, hip_stream);
   const hipStream_t s = static_cast<hipStream_t>(hip_stream);
   const uint64_t want = align_up((uint64_t)phys_count * 4u, 256) + align_up(entries, 256);
-  if (want > ctx->vsm_scratch_bytes) {
-    if (stream_is_capturing(s))
-      return fail(ctx, OXC_INVALID_ARG, "update_virtual_shadowmap: scratch must grow but the stream is being captured; make one un-captured call of this size first");
-    OXC_HIP(ctx, hipDeviceSynchronize());  // in-flight work may still use the old scratch
-    if (ctx->vsm_scratch) OXC_HIP(ctx, hipFree(ctx->vsm_scratch));
-    ctx->vsm_scratch = nullptr;
-    ctx->vsm_scratch_bytes = 0;
-    hipError_t e = hipMalloc(&ctx->vsm_scratch, want);
-    if (e != hipSuccess) return fail(ctx, OXC_OUT_OF_MEMORY, "hipMalloc(vsm scratch)", e);
-    ctx->vsm_scratch_bytes = want;
-  }
+  OXC_TRY(grow_scratch(ctx, s, ctx->vsm_scratch, ctx->vsm_scratch_bytes, want, want,
+                       "update_virtual_shadowmap: scratch must grow but the stream is being captured; make one un-captured call of this size first",
+                       "hipMalloc(vsm scratch)"));
   VsmArgs a = {};
   a.page_table = static_cast<uint32_t*>(c->virtual_page_table.dptr);
   a.clipmaps = static_cast<const float*>(c->vsm_clipmaps_buffer.dptr);
@@ -1588,14 +1687,8 @@ oxc_status oxc_update_virtual_shadowmap(oxc_ctx* ctx, const oxc_vsm_update_conte
   a.physical_size = (uint32_t)phys;
   a.free_list = static_cast<uint32_t*>(ctx->vsm_scratch);
   a.mark = static_cast<uint8_t*>(ctx->vsm_scratch) + align_up((uint64_t)phys_count * 4u, 256);
-  // per-call constants of the pixel pass, binary32 in the Slang's order (include/oxcull.h)
   for (int k = 0; k < 16; k++) a.inv_pv[k] = c->inv_projection_view[k];
-  a.off_x = (1.0f / c->resolution[0]) * 0.5f;
-  a.off_y = (1.0f / c->resolution[1]) * 0.5f;
-  const float scale_ratio = (float)(n - 1) / (float)n;  // get_first_clipmap_texel_length, rmvsm.slang:148-155
-  const float effective_width = c->first_clipmap_width * scale_ratio;
-  a.texel_len = (effective_width * 2.0f) / c->virtual_extent;
-  vsm_level_thresholds(layers, c->clipmap_selection_bias, &a.lvl_always, a.lvl_thr);
+  clipmap_selection_constants(a, *c, sh);
   {
     KernelTimer t(ctx, OXC_K_VSM_UPDATE, s);
     launch_vsm_update(a, ctx->num_cus, static_cast<uint8_t*>(h.dptr), h.levels, h.level_offset, s);
@@ -1613,20 +1706,16 @@ constexpr uint64_t kVsmDrawCapacityMax = 1u << 24, kVsmDrawCapacityMin = 4096;
 oxc_status oxc_draw_physical_pages(oxc_ctx* ctx, const oxc_prepared_frame* f, const oxc_vsm_draw_context* c, void* hip_stream) {
   if (!ctx) return OXC_INVALID_ARG;
   if (!f || !c || c->struct_size != sizeof(oxc_vsm_draw_context)) return fail(ctx, OXC_INVALID_ARG, "draw_physical_pages: bad frame / context / struct_size");
-  const int32_t n = c->page_table_size, ps = c->page_size, phys = c->physical_page_table_size, layers = c->clipmap_count;
-  if (layers < 1 || layers > 16) return fail(ctx, OXC_INVALID_ARG, "draw_physical_pages: clipmap_count must be 1..16");
-  if (n < 8 || n > 256 || n % 8) return fail(ctx, OXC_INVALID_ARG, "draw_physical_pages: page_table_size must be a multiple of 8 in [8, 256]");
-  if (ps < 16 || ps % 16 || phys < ps || phys % ps) return fail(ctx, OXC_INVALID_ARG, "draw_physical_pages: page_size must be a multiple of 16 and divide physical_page_table_size");
-  const uint32_t P = (uint32_t)(phys / ps);
-  if ((uint64_t)P * P > 65536u) return fail(ctx, OXC_INVALID_ARG, "draw_physical_pages: more than 65536 physical pages (16 address bits)");
+  const char* const entry = "draw_physical_pages";
+  VsmShape sh;
+  OXC_TRY(vsm_shape(ctx, entry, *c, sh));
+  const int32_t n = sh.n, ps = sh.ps, phys = sh.phys, layers = sh.layers;
+  const uint32_t P = sh.P;
+  const uint64_t entries = sh.entries;
   if ((int64_t)n * ps > 16384) return fail(ctx, OXC_INVALID_ARG, "draw_physical_pages: V = page_table_size * page_size must be <= 16384 (the guard band's fixed-point range)");
   if (c->wide_triangle_index > 2u) return fail(ctx, OXC_INVALID_ARG, "draw_physical_pages: wide_triangle_index must be 0, 1 or 2");
-  const uint64_t entries = (uint64_t)layers * n * n;
-  if (!c->virtual_page_table.dptr || c->virtual_page_table.bytes < entries * 4u) return fail(ctx, OXC_INVALID_ARG, "draw_physical_pages: virtual_page_table smaller than clipmap_count * n * n u32");
-  if (!c->vsm_clipmaps_buffer.dptr || c->vsm_clipmaps_buffer.bytes < (uint64_t)layers * sizeof(oxc_virtual_clipmap))
-    return fail(ctx, OXC_INVALID_ARG, "draw_physical_pages: vsm_clipmaps_buffer smaller than clipmap_count records");
-  if (!c->vsm_clipmap_dirty_flags_buffer.dptr || c->vsm_clipmap_dirty_flags_buffer.bytes < (uint64_t)layers * 4u)
-    return fail(ctx, OXC_INVALID_ARG, "draw_physical_pages: vsm_clipmap_dirty_flags_buffer smaller than clipmap_count u32");
+  OXC_TRY(vsm_tables(ctx, entry, *c, sh));
+  OXC_TRY(vsm_dirty_flags(ctx, entry, c->vsm_clipmap_dirty_flags_buffer, sh));
   if (!c->draw_geometry_cmd_buffer.dptr || c->draw_geometry_cmd_buffer.bytes < 20u)
     return fail(ctx, OXC_INVALID_ARG, "draw_physical_pages: draw_geometry_cmd_buffer must hold a VkDrawIndexedIndirectCommand (run oxc_cull_geometry with the triangle stage first)");
   const oxc_image& img = c->physical_page_image;
@@ -1666,17 +1755,9 @@ oxc_status oxc_draw_physical_pages(oxc_ctx* ctx, const oxc_prepared_frame* f, co
   const uint64_t o_big = carve((uint64_t)cap * sizeof(VsmBig));
   const uint64_t o_clip = carve((uint64_t)cap * 8u);
   const uint64_t o_tile = carve((uint64_t)cap * 2u * 8u);
-  if (off > ctx->vsm_draw_scratch_bytes) {
-    if (stream_is_capturing(s))
-      return fail(ctx, OXC_INVALID_ARG, "draw_physical_pages: scratch must grow but the stream is being captured; make one un-captured call of this shape first");
-    OXC_HIP(ctx, hipDeviceSynchronize());  // in-flight work may still use the old scratch
-    if (ctx->vsm_draw_scratch) OXC_HIP(ctx, hipFree(ctx->vsm_draw_scratch));
-    ctx->vsm_draw_scratch = nullptr;
-    ctx->vsm_draw_scratch_bytes = 0;
-    hipError_t e = hipMalloc(&ctx->vsm_draw_scratch, off);
-    if (e != hipSuccess) return fail(ctx, OXC_OUT_OF_MEMORY, "hipMalloc(vsm draw scratch)", e);
-    ctx->vsm_draw_scratch_bytes = off;
-  }
+  OXC_TRY(grow_scratch(ctx, s, ctx->vsm_draw_scratch, ctx->vsm_draw_scratch_bytes, off, off,
+                       "draw_physical_pages: scratch must grow but the stream is being captured; make one un-captured call of this shape first",
+                       "hipMalloc(vsm draw scratch)"));
   ctx->vsm_draw_capacity = cap;  // (never below the previous calls': the scratch holds the largest queues asked for so far)
   char* const sc = static_cast<char*>(ctx->vsm_draw_scratch);
   VsmDrawArgs a;
@@ -1723,26 +1804,17 @@ oxc_status oxc_draw_physical_pages(oxc_ctx* ctx, const oxc_prepared_frame* f, co
 oxc_status oxc_resolve_shadowmap(oxc_ctx* ctx, const oxc_shadow_resolve_context* c, void* hip_stream) {
   if (!ctx) return OXC_INVALID_ARG;
   if (!c || c->struct_size != sizeof(oxc_shadow_resolve_context)) return fail(ctx, OXC_INVALID_ARG, "resolve_shadowmap: bad context / struct_size");
-  const int32_t n = c->page_table_size, ps = c->page_size, phys = c->physical_page_table_size, layers = c->clipmap_count;
-  if (layers < 1 || layers > 16) return fail(ctx, OXC_INVALID_ARG, "resolve_shadowmap: clipmap_count must be 1..16");
-  if (n < 8 || n > 256 || n % 8) return fail(ctx, OXC_INVALID_ARG, "resolve_shadowmap: page_table_size must be a multiple of 8 in [8, 256]");
-  if (ps < 16 || ps % 16 || phys < ps || phys % ps) return fail(ctx, OXC_INVALID_ARG, "resolve_shadowmap: page_size must be a multiple of 16 and divide physical_page_table_size");
-  const uint32_t P = (uint32_t)(phys / ps);
-  if ((uint64_t)P * P > 65536u) return fail(ctx, OXC_INVALID_ARG, "resolve_shadowmap: more than 65536 physical pages (16 address bits)");
+  const char* const entry = "resolve_shadowmap";
+  VsmShape sh;
+  OXC_TRY(vsm_shape(ctx, entry, *c, sh));
+  const int32_t n = sh.n, ps = sh.ps, phys = sh.phys;
   const oxc_image& dimg = c->depth_attachment;
   const oxc_image& oimg = c->resolved_shadows_attachment;
-  const uint64_t pixels = (uint64_t)dimg.width * dimg.height;
-  if (dimg.width > 65536u || dimg.height > 65536u) return fail(ctx, OXC_INVALID_ARG, "resolve_shadowmap: depth extent beyond 65536");
-  if (pixels && (!dimg.dptr || dimg.levels != 1 || dimg.level_offset[0] != 0))
-    return fail(ctx, OXC_INVALID_ARG, "resolve_shadowmap: depth_attachment must be one R32F level at offset 0");
-  if (oimg.width != dimg.width || oimg.height != dimg.height || (pixels && (!oimg.dptr || oimg.levels != 1 || oimg.level_offset[0] != 0)))
-    return fail(ctx, OXC_INVALID_ARG, "resolve_shadowmap: resolved_shadows_attachment must be one R32F level of the depth attachment's extent");
-  if (pixels && (!c->normal_attachment.dptr || c->normal_attachment.bytes < pixels * 8u || (reinterpret_cast<uintptr_t>(c->normal_attachment.dptr) & 7u)))
-    return fail(ctx, OXC_INVALID_ARG, "resolve_shadowmap: normal_attachment must be 8-byte aligned u16x4 texels of the depth attachment's extent");
-  const uint64_t entries = (uint64_t)layers * n * n;
-  if (!c->virtual_page_table.dptr || c->virtual_page_table.bytes < entries * 4u) return fail(ctx, OXC_INVALID_ARG, "resolve_shadowmap: virtual_page_table smaller than clipmap_count * n * n u32");
-  if (!c->vsm_clipmaps_buffer.dptr || c->vsm_clipmaps_buffer.bytes < (uint64_t)layers * sizeof(oxc_virtual_clipmap))
-    return fail(ctx, OXC_INVALID_ARG, "resolve_shadowmap: vsm_clipmaps_buffer smaller than clipmap_count records");
+  uint64_t pixels;
+  OXC_TRY(pixel_images(ctx, entry, dimg, &oimg, "resolved_shadows_attachment", pixels));
+  if (bad_pixel_buffer(c->normal_attachment, pixels, 8u))
+    return bad_arg(ctx, entry, "normal_attachment must be 8-byte aligned u16x4 texels of the depth attachment's extent");
+  OXC_TRY(vsm_tables(ctx, entry, *c, sh));
   const oxc_image& pimg = c->physical_page_image;
   if (!pimg.dptr || pimg.width != (uint32_t)phys || pimg.height != (uint32_t)phys || pimg.levels != 1 || pimg.level_offset[0] != 0)
     return fail(ctx, OXC_INVALID_ARG, "resolve_shadowmap: physical_page_image must be one R32F level of physical_page_table_size^2");
@@ -1752,15 +1824,7 @@ oxc_status oxc_resolve_shadowmap(oxc_ctx* ctx, const oxc_shadow_resolve_context*
   if (!pixels) return OXC_OK;
   VsmResolveArgs a;
   std::memset(&a, 0, sizeof a);
-  if (ctx->vsm_resolve_stats_on) {
-    if (!ctx->vsm_resolve_stats) {
-      if (stream_is_capturing(s)) return fail(ctx, OXC_INVALID_ARG, "resolve_shadowmap: the counters are allocated by the first counting call; make one outside the capture");
-      hipError_t e = hipMalloc(reinterpret_cast<void**>(&ctx->vsm_resolve_stats), 32);
-      if (e != hipSuccess) return fail(ctx, OXC_OUT_OF_MEMORY, "hipMalloc(vsm resolve counters)", e);
-    }
-    OXC_HIP(ctx, hipMemsetAsync(ctx->vsm_resolve_stats, 0, 32, s));
-    a.stats = ctx->vsm_resolve_stats;
-  }
+  OXC_TRY(arm_counters(ctx, entry, "hipMalloc(vsm resolve counters)", ctx->vsm_resolve_stats, 32, s, &a.stats));
   a.depth = static_cast<const float*>(dimg.dptr);
   a.normal = static_cast<const uint32_t*>(c->normal_attachment.dptr);
   a.out = static_cast<float*>(oimg.dptr);
@@ -1770,21 +1834,16 @@ oxc_status oxc_resolve_shadowmap(oxc_ctx* ctx, const oxc_shadow_resolve_context*
   a.page_table = static_cast<const uint32_t*>(c->virtual_page_table.dptr);
   a.physical = static_cast<const float*>(pimg.dptr);
   a.n = (uint32_t)n;
-  a.layers = (uint32_t)layers;
+  a.layers = (uint32_t)sh.layers;
   a.page_size = (uint32_t)ps;
-  a.phys_side = P;
-  a.phys_count = P * P;
+  a.phys_side = sh.P;
+  a.phys_count = sh.phys_count;
   a.physical_size = (uint32_t)phys;
   a.fn = (float)n;
   a.fV = (float)((int64_t)n * ps);
   // per-call constants, binary32 in the Slang's order (include/oxcull.h)
   for (int k = 0; k < 16; k++) a.inv_pv[k] = c->inv_projection_view[k];
-  a.off_x = (1.0f / c->resolution[0]) * 0.5f;
-  a.off_y = (1.0f / c->resolution[1]) * 0.5f;
-  const float scale_ratio = (float)(n - 1) / (float)n;  // get_first_clipmap_texel_length, rmvsm.slang:148-155
-  const float effective_width = c->first_clipmap_width * scale_ratio;
-  a.texel_len = (effective_width * 2.0f) / c->virtual_extent;
-  vsm_level_thresholds(layers, c->clipmap_selection_bias, &a.lvl_always, a.lvl_thr);
+  clipmap_selection_constants(a, *c, sh);
   {  // perpendicular_basis(L): t = normalize(cross(axis, L)), bitangent = cross(L, t)
     const float* L = c->directional_light_dir;
     const float ax = std::fabs(L[1]) < 0.999f ? 0.0f : 1.0f, ay = std::fabs(L[1]) < 0.999f ? 1.0f : 0.0f, az = 0.0f;
@@ -1815,12 +1874,8 @@ oxc_status oxc_contact_shadows(oxc_ctx* ctx, const oxc_contact_shadows_context* 
   if (!c || c->struct_size != sizeof(oxc_contact_shadows_context)) return fail(ctx, OXC_INVALID_ARG, "contact_shadows: bad context / struct_size");
   const oxc_image& dimg = c->depth_attachment;
   const oxc_image& oimg = c->contact_shadows_attachment;
-  const uint64_t pixels = (uint64_t)dimg.width * dimg.height;
-  if (dimg.width > 65536u || dimg.height > 65536u) return fail(ctx, OXC_INVALID_ARG, "contact_shadows: depth extent beyond 65536");
-  if (pixels && (!dimg.dptr || dimg.levels != 1 || dimg.level_offset[0] != 0))
-    return fail(ctx, OXC_INVALID_ARG, "contact_shadows: depth_attachment must be one R32F level at offset 0");
-  if (oimg.width != dimg.width || oimg.height != dimg.height || (pixels && (!oimg.dptr || oimg.levels != 1 || oimg.level_offset[0] != 0)))
-    return fail(ctx, OXC_INVALID_ARG, "contact_shadows: contact_shadows_attachment must be one R32F level of the depth attachment's extent");
+  uint64_t pixels;
+  OXC_TRY(pixel_images(ctx, "contact_shadows", dimg, &oimg, "contact_shadows_attachment", pixels));
   if (c->steps < 1u || c->steps > 64u) return fail(ctx, OXC_INVALID_ARG, "contact_shadows: steps must be 1..64");
   if (!(std::isfinite(c->thickness) && c->thickness > 0.0f) || !(std::isfinite(c->shadow_length) && c->shadow_length > 0.0f) ||
       !(std::isfinite(c->near_clip) && c->near_clip > 0.0f))
@@ -1834,15 +1889,7 @@ oxc_status oxc_contact_shadows(oxc_ctx* ctx, const oxc_contact_shadows_context* 
   if (!pixels) return OXC_OK;
   ContactShadowsArgs a;
   std::memset(&a, 0, sizeof a);
-  if (ctx->contact_shadows_stats_on) {
-    if (!ctx->contact_shadows_stats) {
-      if (stream_is_capturing(s)) return fail(ctx, OXC_INVALID_ARG, "contact_shadows: the counters are allocated by the first counting call; make one outside the capture");
-      hipError_t e = hipMalloc(reinterpret_cast<void**>(&ctx->contact_shadows_stats), 48);
-      if (e != hipSuccess) return fail(ctx, OXC_OUT_OF_MEMORY, "hipMalloc(contact shadows counters)", e);
-    }
-    OXC_HIP(ctx, hipMemsetAsync(ctx->contact_shadows_stats, 0, 48, s));
-    a.stats = ctx->contact_shadows_stats;
-  }
+  OXC_TRY(arm_counters(ctx, "contact_shadows", "hipMalloc(contact shadows counters)", ctx->contact_shadows_stats, 48, s, &a.stats));
   a.depth = static_cast<const float*>(dimg.dptr);
   a.out = static_cast<float*>(oimg.dptr);
   a.w = dimg.width;
@@ -1867,23 +1914,18 @@ oxc_status oxc_generate_ambient_occlusion(oxc_ctx* ctx, const oxc_ambient_occlus
   if (!c || c->struct_size != sizeof(oxc_ambient_occlusion_context)) return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: bad context / struct_size");
   const oxc_image& dimg = c->depth_attachment;
   const oxc_image& pimg = c->prefiltered_depth;
-  const uint64_t pixels = (uint64_t)dimg.width * dimg.height;
-  if (dimg.width > 65536u || dimg.height > 65536u) return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: depth extent beyond 65536");
-  if (pixels && (!dimg.dptr || dimg.levels != 1 || dimg.level_offset[0] != 0))
-    return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: depth_attachment must be one R32F level at offset 0");
+  uint64_t pixels;
+  OXC_TRY(pixel_images(ctx, "generate_ambient_occlusion", dimg, nullptr, nullptr, pixels));
   if (pimg.width != dimg.width || pimg.height != dimg.height || pimg.levels != 5 || (pixels && !pimg.dptr))
     return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: prefiltered_depth must have the depth attachment's extent and exactly 5 levels");
   for (int k = 0; k < 5; k++)
     if (pimg.level_offset[k] & 3u) return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: prefiltered_depth level offsets must be multiples of 4");
-  auto bad_buffer = [&](const oxc_buffer& b, uint64_t texel, uintptr_t align) {
-    return pixels && (!b.dptr || b.bytes < pixels * texel || (reinterpret_cast<uintptr_t>(b.dptr) & (align - 1u)));
-  };
-  if (bad_buffer(c->normal_attachment, 8u, 8u))
+  if (bad_pixel_buffer(c->normal_attachment, pixels, 8u))
     return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: normal_attachment must be 8-byte aligned u16x4 texels of the depth attachment's extent");
   if (pixels && (!c->hilbert_noise.dptr || c->hilbert_noise.bytes < 64u * 64u * 2u || (reinterpret_cast<uintptr_t>(c->hilbert_noise.dptr) & 1u)))
     return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: hilbert_noise must be u16[64][64]");
-  if (bad_buffer(c->depth_differences, 4u, 4u)) return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: depth_differences must be one aligned u32 per pixel");
-  if (bad_buffer(c->noisy_occlusion, 2u, 2u) || bad_buffer(c->ambient_occlusion_attachment, 2u, 2u))
+  if (bad_pixel_buffer(c->depth_differences, pixels, 4u)) return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: depth_differences must be one aligned u32 per pixel");
+  if (bad_pixel_buffer(c->noisy_occlusion, pixels, 2u) || bad_pixel_buffer(c->ambient_occlusion_attachment, pixels, 2u))
     return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: noisy_occlusion and ambient_occlusion_attachment must be one aligned u16 per pixel");
   if (c->slice_count < 1u || c->slice_count > 16u || c->samples_per_slice_side < 1u || c->samples_per_slice_side > 8u)
     return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: slice_count must be 1..16 and samples_per_slice_side 1..8");
@@ -1897,15 +1939,7 @@ oxc_status oxc_generate_ambient_occlusion(oxc_ctx* ctx, const oxc_ambient_occlus
   if (!pixels) return OXC_OK;
   AmbientOcclusionArgs a;
   std::memset(&a, 0, sizeof a);
-  if (ctx->ambient_occlusion_stats_on) {
-    if (!ctx->ambient_occlusion_stats) {
-      if (stream_is_capturing(s)) return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: the counters are allocated by the first counting call; make one outside the capture");
-      hipError_t e = hipMalloc(reinterpret_cast<void**>(&ctx->ambient_occlusion_stats), 64);
-      if (e != hipSuccess) return fail(ctx, OXC_OUT_OF_MEMORY, "hipMalloc(ambient occlusion counters)", e);
-    }
-    OXC_HIP(ctx, hipMemsetAsync(ctx->ambient_occlusion_stats, 0, 64, s));
-    a.stats = ctx->ambient_occlusion_stats;
-  }
+  OXC_TRY(arm_counters(ctx, "generate_ambient_occlusion", "hipMalloc(ambient occlusion counters)", ctx->ambient_occlusion_stats, 64, s, &a.stats));
   a.depth = static_cast<const float*>(dimg.dptr);
   a.normal = static_cast<const uint32_t*>(c->normal_attachment.dptr);
   a.hilbert = static_cast<const uint16_t*>(c->hilbert_noise.dptr);
@@ -2041,17 +2075,9 @@ oxc_status oxc_draw_visbuffer(oxc_ctx* ctx, const oxc_prepared_frame* f, const o
     if (e != hipSuccess) return fail(ctx, OXC_OUT_OF_MEMORY, "hipMalloc(raster scratch)", e);
     ctx->raster_capacity = cap;
   }
-  if (f->mesh_instance_count > ctx->raster_rows_cap) {
-    if (stream_is_capturing(static_cast<hipStream_t>(hip_stream)))
-      return fail(ctx, OXC_INVALID_ARG, "draw_visbuffer: more mesh instances than any earlier call (scratch would grow); make one un-captured call first");
-    OXC_HIP(ctx, hipDeviceSynchronize());  // in-flight draws may still read the old rows
-    if (ctx->raster_rows) OXC_HIP(ctx, hipFree(ctx->raster_rows));
-    ctx->raster_rows = nullptr;
-    ctx->raster_rows_cap = 0;
-    hipError_t e = hipMalloc(&ctx->raster_rows, (size_t)f->mesh_instance_count * sizeof(DrawRow));
-    if (e != hipSuccess) return fail(ctx, OXC_OUT_OF_MEMORY, "hipMalloc(raster rows)", e);
-    ctx->raster_rows_cap = f->mesh_instance_count;
-  }
+  OXC_TRY(grow_scratch(ctx, static_cast<hipStream_t>(hip_stream), ctx->raster_rows, ctx->raster_rows_cap, f->mesh_instance_count,
+                       (size_t)f->mesh_instance_count * sizeof(DrawRow),
+                       "draw_visbuffer: more mesh instances than any earlier call (scratch would grow); make one un-captured call first", "hipMalloc(raster rows)"));
   DrawArgs a;
   std::memset(&a, 0, sizeof a);
   std::memcpy(a.pv, d->projection_view, 64);
@@ -2275,9 +2301,9 @@ oxc_status oxc_debug_set_tuning(oxc_ctx* ctx, uint32_t knob, uint32_t value) {
       ctx->raster_capacity_request = value;
       return OXC_OK;
     case OXC_TUNE_VSM_DRAW_STATS: ctx->vsm_draw_stats = value != 0u; return OXC_OK;
-    case OXC_TUNE_VSM_RESOLVE_STATS: ctx->vsm_resolve_stats_on = value != 0u; return OXC_OK;
-    case OXC_TUNE_CONTACT_SHADOWS_STATS: ctx->contact_shadows_stats_on = value != 0u; return OXC_OK;
-    case OXC_TUNE_AMBIENT_OCCLUSION_STATS: ctx->ambient_occlusion_stats_on = value != 0u; return OXC_OK;
+    case OXC_TUNE_VSM_RESOLVE_STATS: ctx->vsm_resolve_stats.on = value != 0u; return OXC_OK;
+    case OXC_TUNE_CONTACT_SHADOWS_STATS: ctx->contact_shadows_stats.on = value != 0u; return OXC_OK;
+    case OXC_TUNE_AMBIENT_OCCLUSION_STATS: ctx->ambient_occlusion_stats.on = value != 0u; return OXC_OK;
     case OXC_TUNE_VSM_DRAW_CAPACITY:
       if (ctx->vsm_draw_scratch) return fail(ctx, OXC_INVALID_ARG, "set_tuning: the shadow draw's scratch is allocated by the first oxc_draw_physical_pages; set its capacity before");
       ctx->vsm_draw_capacity_request = value;
@@ -2351,39 +2377,15 @@ oxc_status oxc_debug_vsm_draw_stats(oxc_ctx* ctx, uint32_t* host_out8, void* hip
 }
 
 oxc_status oxc_debug_vsm_resolve_stats(oxc_ctx* ctx, uint32_t* host_out8, void* hip_stream) {
-  if (!ctx) return OXC_INVALID_ARG;
-  if (!host_out8) return fail(ctx, OXC_INVALID_ARG, "debug_vsm_resolve_stats: null pointer");
-  if (!ctx->vsm_resolve_stats) return fail(ctx, OXC_INVALID_ARG, "debug_vsm_resolve_stats: no counting oxc_resolve_shadowmap call on this context yet");
-  OXC_HIP(ctx, hipSetDevice(ctx->device));
-  OXC_ORDER(ctx, hip_stream);
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  OXC_HIP(ctx, hipMemcpyAsync(host_out8, ctx->vsm_resolve_stats, 32, hipMemcpyDeviceToHost, s));
-  OXC_HIP(ctx, hipStreamSynchronize(s));
-  return OXC_OK;
+  return read_counters(ctx, "debug_vsm_resolve_stats", "oxc_resolve_shadowmap", &oxc_ctx::vsm_resolve_stats, host_out8, 32, hip_stream);
 }
 
 oxc_status oxc_debug_contact_shadows_stats(oxc_ctx* ctx, uint32_t* host_out12, void* hip_stream) {
-  if (!ctx) return OXC_INVALID_ARG;
-  if (!host_out12) return fail(ctx, OXC_INVALID_ARG, "debug_contact_shadows_stats: null pointer");
-  if (!ctx->contact_shadows_stats) return fail(ctx, OXC_INVALID_ARG, "debug_contact_shadows_stats: no counting oxc_contact_shadows call on this context yet");
-  OXC_HIP(ctx, hipSetDevice(ctx->device));
-  OXC_ORDER(ctx, hip_stream);
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  OXC_HIP(ctx, hipMemcpyAsync(host_out12, ctx->contact_shadows_stats, 48, hipMemcpyDeviceToHost, s));
-  OXC_HIP(ctx, hipStreamSynchronize(s));
-  return OXC_OK;
+  return read_counters(ctx, "debug_contact_shadows_stats", "oxc_contact_shadows", &oxc_ctx::contact_shadows_stats, host_out12, 48, hip_stream);
 }
 
 oxc_status oxc_debug_ambient_occlusion_stats(oxc_ctx* ctx, uint32_t* host_out15, void* hip_stream) {
-  if (!ctx) return OXC_INVALID_ARG;
-  if (!host_out15) return fail(ctx, OXC_INVALID_ARG, "debug_ambient_occlusion_stats: null pointer");
-  if (!ctx->ambient_occlusion_stats) return fail(ctx, OXC_INVALID_ARG, "debug_ambient_occlusion_stats: no counting oxc_generate_ambient_occlusion call on this context yet");
-  OXC_HIP(ctx, hipSetDevice(ctx->device));
-  OXC_ORDER(ctx, hip_stream);
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
-  OXC_HIP(ctx, hipMemcpyAsync(host_out15, ctx->ambient_occlusion_stats, 60, hipMemcpyDeviceToHost, s));
-  OXC_HIP(ctx, hipStreamSynchronize(s));
-  return OXC_OK;
+  return read_counters(ctx, "debug_ambient_occlusion_stats", "oxc_generate_ambient_occlusion", &oxc_ctx::ambient_occlusion_stats, host_out15, 60, hip_stream);
 }
 
 }  // extern "C"

@@ -16,39 +16,15 @@
 // (denormals kept): no kernel here may call set_half_denorm_flush().
 #include <hip/hip_runtime.h>
 
-#include "oxcull_device.hpp"
 #include "oxcull_kernels.hpp"
+#include "oxcull_pixel_device.hpp"
 
 namespace oxc {
 
 namespace {
 constexpr float kHalfPi = 1.57079632679f, kPi = 3.1415926535897932384626433832795f;
 
-OXC_DEV float saturate_f(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }  // NaN gives 0
-OXC_DEV float sign_f(float a) { return a > 0.0f ? 1.0f : a < 0.0f ? -1.0f : 0.0f; }
-OXC_DEV int clamp_i(int v, int lo, int hi) { return min(max(v, lo), hi); }
-OXC_DEV float half_to_f(uint32_t h) { return (float)__builtin_bit_cast(_Float16, (unsigned short)h); }
 OXC_DEV unsigned short f_to_half(float x) { return __builtin_bit_cast(unsigned short, (_Float16)x); }
-
-// (cos, sin) of 2 pi t: the rotation rule of oxc_resolve_shadowmap (step 6 of its header block), the same function as in oxcull_vsm_resolve.hip
-OXC_DEV void cos_sin_turn(float t, float& cs, float& sn) {
-  const float q4 = t * 4.0f;  // exact
-  const float kf = floorf(q4);
-  const float f = q4 - kf;  // exact, in [0, 1)
-  const bool swap = f > 0.5f;
-  const float g = swap ? 1.0f - f : f;  // exact, in [0, 0.5]
-  const double a = (double)g * 0x1.921fb54442d18p+0;
-  const double z = a * a;
-  const double ps = ((0x1.71de3a556c734p-19 * z + -0x1.a01a01a01a01ap-13) * z + 0x1.1111111111111p-7) * z + -0x1.5555555555555p-3;
-  const double s = a + (a * z) * ps;
-  const double pc = (((-0x1.27e4fb7789f5cp-22 * z + 0x1.a01a01a01a01ap-16) * z + -0x1.6c16c16c16c17p-10) * z + 0x1.5555555555555p-5) * z + -0x1.0000000000000p-1;
-  const double c = 1.0 + z * pc;
-  const float sf = (float)s, cf = (float)c;
-  const float sq = swap ? cf : sf, cq = swap ? sf : cf;
-  const int k = (int)kf;
-  cs = k == 0 ? cq : k == 1 ? -sq : k == 2 ? -cq : sq;
-  sn = k == 0 ? sq : k == 1 ? cq : k == 2 ? -sq : -cq;
-}
 
 // the log2 rule before its rounding: binary64, no contraction
 OXC_DEV double log2_f64(float x) {
@@ -149,13 +125,6 @@ OXC_DEV float bil(const Tap& t, float t00, float t10, float t01, float t11) {
   return top + (bot - top) * t.fy;
 }
 
-struct V3 {
-  float x, y, z;
-};
-OXC_DEV V3 normalize3(const V3& v) {
-  const float l = len3(v.x, v.y, v.z);
-  return {v.x / l, v.y / l, v.z / l};
-}
 OXC_DEV float dotv(const V3& a, const V3& b) { return dot3(a.x, a.y, a.z, b.x, b.y, b.z); }
 
 // update_sectors into an empty bitmask; zero: the arc has no width
@@ -214,9 +183,8 @@ __global__ __launch_bounds__(256) void k_ao_prefilter(AmbientOcclusionArgs a) {
 
 template <bool STATS>
 __global__ __launch_bounds__(256) void k_ao_main(AmbientOcclusionArgs a) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t px = blockIdx.x * 16u + (wave & 1u) * 8u + (lane & 7u);
-  const uint32_t py = blockIdx.y * 16u + (wave >> 1) * 8u + (lane >> 3);
+  const uint2 tp = tile_pixel();
+  const uint32_t px = tp.x, py = tp.y;
   if (px >= a.w || py >= a.h) return;
   const size_t pix = (size_t)py * a.w + px;
   const float* pre = a.pre;
@@ -253,15 +221,7 @@ __global__ __launch_bounds__(256) void k_ao_main(AmbientOcclusionArgs a) {
   // load_normal_view_space: the texel at the pixel
   V3 nrm;
   {
-    const uint32_t nba = a.normal[pix * 2u + 1u];  // .b in the low half, .a in the high half
-    const float ex = half_to_f(nba & 0xFFFFu), ey = half_to_f(nba >> 16);
-    V3 o;
-    o.z = (1.0f - __builtin_fabsf(ex)) - __builtin_fabsf(ey);
-    const float sx = ex >= 0.0f ? 1.0f : -1.0f, sy = ey >= 0.0f ? 1.0f : -1.0f;
-    const bool fold = o.z < 0.0f;
-    o.x = fold ? (1.0f - __builtin_fabsf(ey)) * sx : ex;
-    o.y = fold ? (1.0f - __builtin_fabsf(ex)) * sy : ey;
-    const V3 wn = normalize3(o);
+    const V3 wn = normalize3(oct_normal_ba(a.normal[pix * 2u + 1u]));
     nrm = normalize3({(a.view3[0] * wn.x + a.view3[1] * wn.y) + a.view3[2] * wn.z, (a.view3[3] * wn.x + a.view3[4] * wn.y) + a.view3[5] * wn.z,
                       (a.view3[6] * wn.x + a.view3[7] * wn.y) + a.view3[8] * wn.z});
   }
@@ -352,17 +312,16 @@ __global__ __launch_bounds__(256) void k_ao_main(AmbientOcclusionArgs a) {
 }
 
 __global__ __launch_bounds__(256) void k_ao_denoise(AmbientOcclusionArgs a) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t px = blockIdx.x * 16u + (wave & 1u) * 8u + (lane & 7u);
-  const uint32_t py = blockIdx.y * 16u + (wave >> 1) * 8u + (lane >> 3);
+  const uint2 tp = tile_pixel();
+  const uint32_t px = tp.x, py = tp.y;
   if (px >= a.w || py >= a.h) return;
   const uint32_t xl = max(px, 1u) - 1u, xr = min(px + 1u, a.w - 1u), yt = max(py, 1u) - 1u, yb = min(py + 1u, a.h - 1u);
   const size_t rt = (size_t)yt * a.w, rc = (size_t)py * a.w, rb = (size_t)yb * a.w;
   // fourteen loads, one batch
   const uint32_t ec = a.edges[rc + px], el = a.edges[rc + xl], er = a.edges[rc + xr], et = a.edges[rt + px], eb = a.edges[rb + px];
-  const float v_tl = half_to_f(a.noisy[rt + xl]), v_t = half_to_f(a.noisy[rt + px]), v_tr = half_to_f(a.noisy[rt + xr]);
-  const float v_l = half_to_f(a.noisy[rc + xl]), v_c = half_to_f(a.noisy[rc + px]), v_r = half_to_f(a.noisy[rc + xr]);
-  const float v_bl = half_to_f(a.noisy[rb + xl]), v_b = half_to_f(a.noisy[rb + px]), v_br = half_to_f(a.noisy[rb + xr]);
+  const float v_tl = dequantize_half(a.noisy[rt + xl]), v_t = dequantize_half(a.noisy[rt + px]), v_tr = dequantize_half(a.noisy[rt + xr]);
+  const float v_l = dequantize_half(a.noisy[rc + xl]), v_c = dequantize_half(a.noisy[rc + px]), v_r = dequantize_half(a.noisy[rc + xr]);
+  const float v_bl = dequantize_half(a.noisy[rb + xl]), v_b = dequantize_half(a.noisy[rb + px]), v_br = dequantize_half(a.noisy[rb + xr]);
 
   const float lw = unorm(ec, 0) * unorm(el, 1), rw = unorm(ec, 1) * unorm(er, 0), tw = unorm(ec, 2) * unorm(et, 3), bw = unorm(ec, 3) * unorm(eb, 2);
   const float tlw = 0.425f * (tw * unorm(et, 0) + lw * unorm(el, 2));

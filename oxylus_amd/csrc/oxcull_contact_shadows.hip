@@ -13,8 +13,8 @@
 // root are the IEEE ones.
 #include <hip/hip_runtime.h>
 
-#include "oxcull_device.hpp"
 #include "oxcull_kernels.hpp"
+#include "oxcull_pixel_device.hpp"
 
 namespace oxc {
 
@@ -25,15 +25,12 @@ OXC_DEV float row1(const float* m, int r, float x, float y, float z) { return ((
 OXC_DEV float row4(const float* m, int r, float x, float y, float z, float w) {
   return ((OXC_M(m, r, 0) * x + OXC_M(m, r, 1) * y) + OXC_M(m, r, 2) * z) + OXC_M(m, r, 3) * w;
 }
-OXC_DEV float sign_f(float a) { return a > 0.0f ? 1.0f : a < 0.0f ? -1.0f : 0.0f; }
-OXC_DEV int clamp_i(int v, int lo, int hi) { return min(max(v, lo), hi); }
 }  // namespace
 
 template <bool STATS>
 __global__ __launch_bounds__(256) void k_contact_shadows(ContactShadowsArgs a) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t px = blockIdx.x * 16u + (wave & 1u) * 8u + (lane & 7u);
-  const uint32_t py = blockIdx.y * 16u + (wave >> 1) * 8u + (lane >> 3);
+  const uint2 tp = tile_pixel();
+  const uint32_t px = tp.x, py = tp.y;
   if (px >= a.w || py >= a.h) return;
   const size_t pix = (size_t)py * a.w + px;
   const float d = a.depth[pix];

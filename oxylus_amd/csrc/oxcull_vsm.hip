@@ -18,8 +18,8 @@
 
 #include <algorithm>
 
-#include "oxcull_device.hpp"
 #include "oxcull_kernels.hpp"
+#include "oxcull_pixel_device.hpp"
 
 namespace oxc {
 
@@ -29,12 +29,6 @@ constexpr uint32_t kVsmResolveThreads = 1024;
 constexpr uint32_t kVsmMarkRows = 4;         // pixel pass: one row segment of 256 pixels per wave, 4 rows per block
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint32_t kVisible = 1u, kDirty = 2u, kBacked = 4u, kInvalidated = 8u;
-
-OXC_DEV int floor_mod_i(int x, int n) {
-  const int r = x % n;
-  return r < 0 ? r + n : r;
-}
-OXC_DEV float clamp01(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }  // a NaN becomes 0 (max(NaN, 0) = 0)
 }  // namespace
 
 // ---- pass 1-3: sun_moved clear, reset page visibility, invalidate pages ----------------------------------------------
@@ -84,7 +78,7 @@ __global__ __launch_bounds__(256) void k_vsm_reset_invalidate(VsmArgs a) {
             float sa[6];
             if (project_aabb(mvp, z_near, m.aabb_center[0], m.aabb_center[1], m.aabb_center[2], m.aabb_extent[0], m.aabb_extent[1],
                              m.aabb_extent[2], sa)) {
-              const float u0 = clamp01(sa[0]), v0 = clamp01(sa[1]), u1 = clamp01(sa[3]), v1 = clamp01(sa[4]);
+              const float u0 = saturate_f(sa[0]), v0 = saturate_f(sa[1]), u1 = saturate_f(sa[3]), v1 = saturate_f(sa[4]);
               if (!(u0 >= u1) && !(v0 >= v1)) {
                 const float fn = (float)a.n;
                 r.x = min(max((int)floorf(u0 * fn), 0), n - 1);
@@ -114,17 +108,6 @@ __global__ __launch_bounds__(256) void k_vsm_reset_invalidate(VsmArgs a) {
 }
 
 // ---- pass 4: mark visible pages ---------------------------------------------------------------------------------------
-OXC_DEV void unproject(const float* m, float u, float v, float d, float& x, float& y, float& z) {
-  const float nx = u * 2.0f - 1.0f, ny = v * 2.0f - 1.0f;
-  const float hx = ((OXC_M(m, 0, 0) * nx + OXC_M(m, 0, 1) * ny) + OXC_M(m, 0, 2) * d) + OXC_M(m, 0, 3);
-  const float hy = ((OXC_M(m, 1, 0) * nx + OXC_M(m, 1, 1) * ny) + OXC_M(m, 1, 2) * d) + OXC_M(m, 1, 3);
-  const float hz = ((OXC_M(m, 2, 0) * nx + OXC_M(m, 2, 1) * ny) + OXC_M(m, 2, 2) * d) + OXC_M(m, 2, 3);
-  const float hw = ((OXC_M(m, 3, 0) * nx + OXC_M(m, 3, 1) * ny) + OXC_M(m, 3, 2) * d) + OXC_M(m, 3, 3);
-  x = hx / hw;
-  y = hy / hw;
-  z = hz / hw;
-}
-
 // The page (linear entry index) pixel (px, py) with depth d marks, or kNone.
 OXC_DEV uint32_t pixel_page(const VsmArgs& a, const float* cms, uint32_t px, uint32_t py, float d) {
   if (d == 0.0f) return kNone;  // mark_visible_pages.slang:39
@@ -136,7 +119,7 @@ OXC_DEV uint32_t pixel_page(const VsmArgs& a, const float* cms, uint32_t px, uin
   const float dx = lx - rx, dy = ly - ry, dz = lz - rz;
   const float dist = __builtin_sqrtf((dx * dx + dy * dy) + dz * dz);
   const float r = dist / a.texel_len;
-  uint32_t idx = a.lvl_always;
+  uint32_t idx = a.lvl_always;  // (the loop of oxcull_vsm_resolve.hip's kernel: the two must select the same clipmap)
   for (uint32_t k = a.lvl_always; k + 1 < a.layers; k++) idx += (r > a.lvl_thr[k]) ? 1u : 0u;  // NaN: never
   const float* c = cms + idx * 19;
   const float hx = ((OXC_M(c, 0, 0) * cx + OXC_M(c, 0, 1) * cy) + OXC_M(c, 0, 2) * cz) + OXC_M(c, 0, 3);
@@ -144,12 +127,8 @@ OXC_DEV uint32_t pixel_page(const VsmArgs& a, const float* cms, uint32_t px, uin
   const float hw = ((OXC_M(c, 3, 0) * cx + OXC_M(c, 3, 1) * cy) + OXC_M(c, 3, 2) * cz) + OXC_M(c, 3, 3);
   const float su = (hx / hw + 1.0f) * 0.5f, sv = (hy / hw + 1.0f) * 0.5f;
   if (!(su >= 0.0f && su <= 1.0f && sv >= 0.0f && sv <= 1.0f)) return kNone;  // outside, or NaN
-  const float fn = (float)a.n;
-  const int vx = (int)floorf(su * fn), vy = (int)floorf(sv * fn);
-  const int n = (int)a.n;
-  if (vx > n - 1 || vy > n - 1) return kNone;  // uv == 1.0 lands on virt == n
-  const int ox = __builtin_bit_cast(int, c[16]), oy = __builtin_bit_cast(int, c[17]);
-  const uint32_t wx = (uint32_t)floor_mod_i(vx + floor_mod_i(ox, n), n), wy = (uint32_t)floor_mod_i(vy + floor_mod_i(oy, n), n);
+  uint32_t wx, wy;
+  if (!wrapped_page(c, su, sv, (float)a.n, (int)a.n, wx, wy)) return kNone;
   return (idx * a.n + wy) * a.n + wx;
 }
 

@@ -13,8 +13,8 @@
 // root are the IEEE ones, the rotation pair is evaluated in binary64.
 #include <hip/hip_runtime.h>
 
-#include "oxcull_device.hpp"
 #include "oxcull_kernels.hpp"
+#include "oxcull_pixel_device.hpp"
 
 namespace oxc {
 
@@ -22,32 +22,7 @@ namespace {
 constexpr uint32_t kBacked = 4u;
 constexpr float kMiss = -1.0f;  // VSM_DEPTH_MISS
 
-struct V3 {
-  float x, y, z;
-};
-
-OXC_DEV int floor_mod_i(int x, int n) {
-  const int r = x % n;
-  return r < 0 ? r + n : r;
-}
-
-OXC_DEV void unproject(const float* m, float u, float v, float d, float& x, float& y, float& z) {
-  const float nx = u * 2.0f - 1.0f, ny = v * 2.0f - 1.0f;
-  const float hx = ((OXC_M(m, 0, 0) * nx + OXC_M(m, 0, 1) * ny) + OXC_M(m, 0, 2) * d) + OXC_M(m, 0, 3);
-  const float hy = ((OXC_M(m, 1, 0) * nx + OXC_M(m, 1, 1) * ny) + OXC_M(m, 1, 2) * d) + OXC_M(m, 1, 3);
-  const float hz = ((OXC_M(m, 2, 0) * nx + OXC_M(m, 2, 1) * ny) + OXC_M(m, 2, 2) * d) + OXC_M(m, 2, 3);
-  const float hw = ((OXC_M(m, 3, 0) * nx + OXC_M(m, 3, 1) * ny) + OXC_M(m, 3, 2) * d) + OXC_M(m, 3, 3);
-  x = hx / hw;
-  y = hy / hw;
-  z = hz / hw;
-}
-
 OXC_DEV float row(const float* c, int r, const V3& p) { return ((OXC_M(c, r, 0) * p.x + OXC_M(c, r, 1) * p.y) + OXC_M(c, r, 2) * p.z) + OXC_M(c, r, 3); }
-
-OXC_DEV V3 normalize3(const V3& v) {
-  const float l = len3(v.x, v.y, v.z);
-  return {v.x / l, v.y / l, v.z / l};
-}
 
 // pcg2d on (x, y), u32 wrap-around
 OXC_DEV void pcg2d(uint32_t& x, uint32_t& y) {
@@ -63,26 +38,6 @@ OXC_DEV void pcg2d(uint32_t& x, uint32_t& y) {
   y ^= y >> 16;
 }
 
-// (cos, sin) of 2 pi t, t a binary32 in [0, 1): exact reduction to an octant, two binary64 polynomials by Horner, one rounding each.
-OXC_DEV void cos_sin_turn(float t, float& cs, float& sn) {
-  const float q4 = t * 4.0f;  // exact
-  const float kf = floorf(q4);
-  const float f = q4 - kf;  // exact, in [0, 1)
-  const bool swap = f > 0.5f;
-  const float g = swap ? 1.0f - f : f;  // exact, in [0, 0.5]
-  const double a = (double)g * 0x1.921fb54442d18p+0;
-  const double z = a * a;
-  const double ps = ((0x1.71de3a556c734p-19 * z + -0x1.a01a01a01a01ap-13) * z + 0x1.1111111111111p-7) * z + -0x1.5555555555555p-3;
-  const double s = a + (a * z) * ps;
-  const double pc = (((-0x1.27e4fb7789f5cp-22 * z + 0x1.a01a01a01a01ap-16) * z + -0x1.6c16c16c16c17p-10) * z + 0x1.5555555555555p-5) * z + -0x1.0000000000000p-1;
-  const double c = 1.0 + z * pc;
-  const float sf = (float)s, cf = (float)c;
-  const float sq = swap ? cf : sf, cq = swap ? sf : cf;
-  const int k = (int)kf;
-  cs = k == 0 ? cq : k == 1 ? -sq : k == 2 ? -cq : sq;
-  sn = k == 0 ? sq : k == 1 ? cq : k == 2 ? -sq : -cq;
-}
-
 // sample_vsm_shadow_depth: the depth clipmap `ci` holds for world position p, or kMiss
 OXC_DEV float tap(const VsmResolveArgs& a, const float* cms, int ci, const V3& p) {
   if (ci < 0 || ci >= (int)a.layers) return kMiss;
@@ -90,11 +45,8 @@ OXC_DEV float tap(const VsmResolveArgs& a, const float* cms, int ci, const V3& p
   const float hx = row(c, 0, p), hy = row(c, 1, p), hw = row(c, 3, p);
   const float su = (hx / hw + 1.0f) * 0.5f, sv = (hy / hw + 1.0f) * 0.5f;
   if (!(su >= 0.0f && su <= 1.0f && sv >= 0.0f && sv <= 1.0f)) return kMiss;  // outside, or NaN
-  const int n = (int)a.n;
-  const int vx = (int)floorf(su * a.fn), vy = (int)floorf(sv * a.fn);
-  if (vx > n - 1 || vy > n - 1) return kMiss;  // uv == 1.0 lands on virt == n
-  const int ox = __builtin_bit_cast(int, c[16]), oy = __builtin_bit_cast(int, c[17]);
-  const uint32_t wx = (uint32_t)floor_mod_i(vx + floor_mod_i(ox, n), n), wy = (uint32_t)floor_mod_i(vy + floor_mod_i(oy, n), n);
+  uint32_t wx, wy;
+  if (!wrapped_page(c, su, sv, a.fn, (int)a.n, wx, wy)) return kMiss;
   const uint32_t e = a.page_table[((uint32_t)ci * a.n + wy) * a.n + wx];
   if (!(e & kBacked)) return kMiss;
   const uint32_t addr = e >> 16;
@@ -125,9 +77,8 @@ __global__ __launch_bounds__(256) void k_vsm_resolve_shadow(VsmResolveArgs a) {
   __shared__ float cms[16 * 19];
   for (uint32_t i = threadIdx.x; i < a.layers * 19; i += blockDim.x) cms[i] = a.clipmaps[i];
   __syncthreads();
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t px = blockIdx.x * 16u + (wave & 1u) * 8u + (lane & 7u);
-  const uint32_t py = blockIdx.y * 16u + (wave >> 1) * 8u + (lane >> 3);
+  const uint2 tp = tile_pixel();
+  const uint32_t px = tp.x, py = tp.y;
   if (px >= a.w || py >= a.h) return;
   const size_t pix = (size_t)py * a.w + px;
   const float d = a.depth[pix];
@@ -144,21 +95,12 @@ __global__ __launch_bounds__(256) void k_vsm_resolve_shadow(VsmResolveArgs a) {
   unproject(a.inv_pv, u + -a.off_x, v + a.off_y, d, lf.x, lf.y, lf.z);
   unproject(a.inv_pv, u + a.off_x, v + a.off_y, d, rt.x, rt.y, rt.z);
   const float r = len3(lf.x - rt.x, lf.y - rt.y, lf.z - rt.z) / a.texel_len;
-  uint32_t idx = a.lvl_always;
+  uint32_t idx = a.lvl_always;  // (the loop of oxcull_vsm.hip's pixel_page: the two must select the same clipmap)
   for (uint32_t k = a.lvl_always; k + 1 < a.layers; k++) idx += (r > a.lvl_thr[k]) ? 1u : 0u;  // NaN: never
   const int base = (int)idx;
 
   // flat_N = normalize(oct_to_vec3(normal.ba))
-  const uint32_t nba = a.normal[pix * 2u + 1u];  // .b in the low half, .a in the high half
-  const float ex = (float)__builtin_bit_cast(_Float16, (unsigned short)(nba & 0xFFFFu));
-  const float ey = (float)__builtin_bit_cast(_Float16, (unsigned short)(nba >> 16));
-  V3 o;
-  o.z = (1.0f - __builtin_fabsf(ex)) - __builtin_fabsf(ey);
-  const float sx = ex >= 0.0f ? 1.0f : -1.0f, sy = ey >= 0.0f ? 1.0f : -1.0f;
-  const bool fold = o.z < 0.0f;
-  o.x = fold ? (1.0f - __builtin_fabsf(ey)) * sx : ex;
-  o.y = fold ? (1.0f - __builtin_fabsf(ex)) * sy : ey;
-  const V3 N = normalize3(normalize3(o));
+  const V3 N = normalize3(normalize3(oct_normal_ba(a.normal[pix * 2u + 1u])));
 
   uint32_t hx = px, hy = py;
   pcg2d(hx, hy);

@@ -689,12 +689,16 @@ class RendererInstance:
         self._keep = context
         self._check(self._lib.oxc_resolve_shadowmap(self._ctx, C.byref(c), self._stream(stream)))
 
+    def _read_stats(self, fn, stream, names) -> dict:
+        """One of the oxc_debug_*_stats read-backs: len(names) u32 counters under their names."""
+        out = (C.c_uint32 * len(names))()
+        self._check(fn(self._ctx, C.cast(out, C.c_void_p), self._stream(stream)))
+        return {k: int(v) for k, v in zip(names, out)}
+
     def debug_vsm_resolve_stats(self, stream=None) -> dict:
         """What the last resolve_shadowmap did, after debug_set_tuning(L.TUNE_VSM_RESOLVE_STATS, 1) (measurement hook; synchronises)."""
-        out = (C.c_uint32 * 8)()
-        self._check(self._lib.oxc_debug_vsm_resolve_stats(self._ctx, C.cast(out, C.c_void_p), self._stream(stream)))
-        names = ("non_sky_pixels", "taps", "misses", "fallback_minus", "fallback_plus", "hard", "no_blocker", "all_blockers")
-        return {k: int(v) for k, v in zip(names, out)}
+        return self._read_stats(self._lib.oxc_debug_vsm_resolve_stats, stream,
+                                ("non_sky_pixels", "taps", "misses", "fallback_minus", "fallback_plus", "hard", "no_blocker", "all_blockers"))
 
     def contact_shadows(self, context: ContactShadowsContext, stream=None):
         """RendererInstance.cpp:990-1020 (contact_shadows): per pixel a short ray towards the sun marched through the depth image, the
@@ -705,11 +709,9 @@ class RendererInstance:
 
     def debug_contact_shadows_stats(self, stream=None) -> dict:
         """What the last contact_shadows did, after debug_set_tuning(L.TUNE_CONTACT_SHADOWS_STATS, 1) (measurement hook; synchronises)."""
-        out = (C.c_uint32 * 12)()
-        self._check(self._lib.oxc_debug_contact_shadows_stats(self._ctx, C.cast(out, C.c_void_p), self._stream(stream)))
-        names = ("non_sky_pixels", "taps", "miss", "hit_zero", "hit_partial", "hit_one", "rejected", "n_lower", "n_between", "n_upper", "end_clip",
-                 "start_moved")
-        return {k: int(v) for k, v in zip(names, out)}
+        return self._read_stats(self._lib.oxc_debug_contact_shadows_stats, stream,
+                                ("non_sky_pixels", "taps", "miss", "hit_zero", "hit_partial", "hit_one", "rejected", "n_lower", "n_between", "n_upper",
+                                 "end_clip", "start_moved"))
 
     def generate_ambient_occlusion(self, context: AmbientOcclusionContext, stream=None):
         """Passes/PBR.cpp:179-311 (vbgtao_prefilter, vbgtao_main, vbgtao_denoise): the ambient occlusion term pbr_apply reads, into
@@ -721,25 +723,20 @@ class RendererInstance:
     def debug_ambient_occlusion_stats(self, stream=None) -> dict:
         """What the last generate_ambient_occlusion did, after debug_set_tuning(L.TUNE_AMBIENT_OCCLUSION_STATS, 1) (measurement hook;
         synchronises)."""
-        out = (C.c_uint32 * 15)()
-        self._check(self._lib.oxc_debug_ambient_occlusion_stats(self._ctx, C.cast(out, C.c_void_p), self._stream(stream)))
-        names = ("non_sky_pixels", "samples", "mip0", "mip1", "mip2", "mip3", "mip4", "fractional", "result_one", "result_partial", "result_zero",
-                 "zero_width", "sign_minus", "sign_zero", "sign_plus")
-        return {k: int(v) for k, v in zip(names, out)}
+        return self._read_stats(self._lib.oxc_debug_ambient_occlusion_stats, stream,
+                                ("non_sky_pixels", "samples", "mip0", "mip1", "mip2", "mip3", "mip4", "fractional", "result_one", "result_partial",
+                                 "result_zero", "zero_width", "sign_minus", "sign_zero", "sign_plus"))
 
     def debug_vsm_draw_stats(self, stream=None) -> dict:
         """What the last draw_physical_pages did (measurement hook; synchronises).  `pairs` / `fragments` are counted only with
         debug_set_tuning(L.TUNE_VSM_DRAW_STATS, 1)."""
-        out = (C.c_uint32 * 8)()
-        self._check(self._lib.oxc_debug_vsm_draw_stats(self._ctx, C.cast(out, C.c_void_p), self._stream(stream)))
-        names = ("pairs", "fragments", "big_pairs", "big_pairs_overflowed", "tiles", "tiles_overflowed", "clipped_pairs", "clipped_pairs_overflowed")
-        return {k: int(v) for k, v in zip(names, out)}
+        return self._read_stats(self._lib.oxc_debug_vsm_draw_stats, stream,
+                                ("pairs", "fragments", "big_pairs", "big_pairs_overflowed", "tiles", "tiles_overflowed", "clipped_pairs",
+                                 "clipped_pairs_overflowed"))
 
     def debug_raster_stats(self, stream=None) -> dict:
         """What the last draw_visbuffer did with its triangles (test hook; synchronises)."""
-        out = (C.c_uint32 * 4)()
-        self._check(self._lib.oxc_debug_raster_stats(self._ctx, C.cast(out, C.c_void_p), self._stream(stream)))
-        return {"big": int(out[0]), "clipped": int(out[1]), "tiles": int(out[2]), "overflowed_segments": int(out[3])}
+        return self._read_stats(self._lib.oxc_debug_raster_stats, stream, ("big", "clipped", "tiles", "overflowed_segments"))
 
     def debug_set_tuning(self, knob: int, value: int):
         """Harness knobs (L.TUNE_*): async stage grid caps, the raster queues' capacity (before the first draw)."""
