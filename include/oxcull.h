@@ -927,6 +927,93 @@ typedef struct oxc_draw_context {
 
 oxc_status oxc_draw_visbuffer(oxc_ctx* ctx, const oxc_prepared_frame* frame, const oxc_draw_context* context, void* hip_stream);
 
+/* ---- Visbuffer decode: the G-buffer images from the visibility buffer --------------------------------------------------
+ * Replaces RendererInstance::decode_visbuffer (Oxylus/src/Render/Passes/DrawGeometry.cpp:192-274, pipeline visbuffer_decode, passes/
+ * visbuffer_decode.slang), the full-screen pass directly after the draw (RendererInstance.cpp:924): per pixel the visbuffer texel is turned
+ * back into a triangle, the perspective-correct barycentrics are found, the vertex normals are interpolated, and the four G-buffer images
+ * every later pass reads are written (formats: RendererInstance.cpp:700-737).  Its normal_attachment is what oxc_resolve_shadowmap and
+ * oxc_generate_ambient_occlusion read.
+ * Scope: the geometry and material-factor half of the shader.  Texture sampling is NOT done -- bindless images, SampleGrad and anisotropy
+ * are hardware rules this library has no image table for: the Has*Image bits of Material::flags are ignored, every sample_* returns its
+ * factor alone (scene.slang:110-159 without the image branches), sample_occlusion_color is 1.0, normal.xy equals normal.zw, and what feeds
+ * only the sampling -- uv_size, uv_offset, the texcoord stream, the tangent frame, the rescaled ddx / ddy of compute_partial_derivatives
+ * (visbuffer_decode.slang:74-83) -- is not computed.  Camera::position is read by the Slang for the tangent frame only; the context has no
+ * such field.  Terrain pixels and the mesh-shader path are out of scope.
+ * Arithmetic: canonical binary32 -- round to nearest even, one fixed evaluation order, no contraction, IEEE division and square root; 1.0 / x
+ * is a division; sums run left to right as written in the Slang; mul(M, (p, 1)).r = ((M[r][0] * p.x + M[r][1] * p.y) + M[r][2] * p.z) +
+ * M[r][3]; mul(vec, mat) is the dot product in component order; saturate(x) = min(max(x, 0), 1) with fmaxf / fminf, so a NaN gives 0.  The
+ * reference is compiled fast-math: this is the one evaluation the device and the checker (tests/visbuffer_decode_model.py) both follow.
+ * Per pixel (x, y) of the W x H images:
+ *   1. empty   (visbuffer_decode.slang:90-93)  The pixel is empty when texel == ~0u, or is_terrain(texel) ((texel >> 8) == 0xFFFFFE,
+ *              visbuffer.slang:16-20), or the bits of the depth texel are 0 (the library's own cleared state: oxc_draw_visbuffer resolves an
+ *              uncovered pixel to vis 0 and depth 0), or meshlet_instance_index = texel >> 8 is >= meshlet_instance_count (the reference
+ *              would read past the buffer).  With clear != 0 the four outputs of an empty pixel are written as zero (the engine's
+ *              clear_image to black, folded in); with clear == 0 they are not touched.
+ *   2. fetch   (visbuffer_decode.slang:95-110)  VisBufferData(texel): triangle_index = texel & 0xFF.  meshlet_instance -> mesh_instance ->
+ *              mesh, material_index, transform, mesh.lods[lod_index] -> meshlet; Meshlet::indices (scene.slang:365-376): the three micro
+ *              indices at bytes local_triangle_index_offset + 3 * triangle_index + {0, 1, 2} of local_triangle_indices (get_micro_index reads
+ *              the u32 word that holds the byte), then indirect_vertex_indices[indirect_vertex_index_offset + micro].  If any of the three
+ *              vertex indices exceeds vertex_count - 1 (unsigned: vertex_count == 0 wraps and nothing exceeds it, as in the Slang), all four
+ *              outputs are written as zero -- written, not discarded, also with clear == 0.  material_index >= material_count uses a default
+ *              Material, all fields zero.  Only meshlet_instance_index and material_index are bounded by the call; every other index of the
+ *              chain is the scene's own, as everywhere in this library.
+ *   3. vertex  positions through com::dequantize_half (Mesh::decode_position, scene.slang:478-484): a half with exponent field 0 gives the
+ *              sign alone (+-0), every other half its IEEE value; the material's halves likewise.  Normals through Mesh::decode_normal
+ *              (scene.slang:486-489): (f32((packed >> {20, 10, 0}) & 1023) / 511.0) - 1.0.  A null Mesh::vertex_normals decodes every normal
+ *              as (0, 0, 0) and the arithmetic runs on (stated rule: the Slang would read through the null pointer).
+ *   4. bary    (visbuffer_decode.slang:45-73)  world_i = mul(world, (p_i, 1)).xyz (TransformWorld::to_world_positions); clip_i =
+ *              mul(projection_view, (world_i, 1)) (x, y and w are used);  inv_w_i = 1.0 / clip_i.w;  ndc_i = clip_i.xy * inv_w_i;
+ *              inv_det = 1.0 / ((ndc_2.x - ndc_1.x) * (ndc_0.y - ndc_1.y) - (ndc_2.y - ndc_1.y) * (ndc_0.x - ndc_1.x));
+ *              ddx = ((ndc_1.y - ndc_2.y, ndc_2.y - ndc_0.y, ndc_0.y - ndc_1.y) * inv_det) * inv_w, ddy = ((ndc_2.x - ndc_1.x, ndc_0.x -
+ *              ndc_2.x, ndc_1.x - ndc_0.x) * inv_det) * inv_w, per component;  ddx_sum = (ddx.x + ddx.y) + ddx.z, ddy_sum likewise;
+ *              uv = ((f32(x) + 0.5) / f32(W), (f32(y) + 0.5) / f32(H)) * 2.0 - 1.0 (the fullscreen triangle's tex_coord: the pixel-centre rule
+ *              of the other per-pixel passes);  d = uv - ndc_0;  interp_inv_w = (inv_w_0 + d.x * ddx_sum) + d.y * ddy_sum;  interp_w = 1.0 /
+ *              interp_inv_w;  lambda = (interp_w * ((inv_w_0 + d.x * ddx.x) + d.y * ddy.x), interp_w * (d.x * ddx.y + d.y * ddy.y),
+ *              interp_w * (d.x * ddx.z + d.y * ddy.z)).  A zero-area triangle divides by zero; the IEEE results are the rule.
+ *   5. normal  (visbuffer_decode.slang:136-137, 169-170)  N = TransformWorld::normal_matrix() (scene.slang:292-299: the cofactor matrix of
+ *              world's upper 3 x 3, each entry a * b - c * d with both products rounded);  n_i = mul(N, normal_i) row by row;  v.c =
+ *              (lambda.x * n_0.c + lambda.y * n_1.c) + lambda.z * n_2.c;  world_normal = v / sqrt((v.x * v.x + v.y * v.y) + v.z * v.z), three
+ *              divisions;  vec3_to_oct (common/encoding.slang:17-21): s = 1.0 / ((|x| + |y|) + |z|), p = (x * s, y * s), and for z <= 0
+ *              ((1.0 - |p.y|) * (p.x >= 0 ? 1 : -1), (1.0 - |p.x|) * (p.y >= 0 ? 1 : -1)), else p.  Both .rg and .ba of normal_attachment
+ *              get it, converted to binary16 with round to nearest even, denormals kept.  Stated rule: a NaN component is stored as 0x7E00
+ *              whatever its sign and payload (IEEE leaves both open, and processors differ).
+ *   6. albedo  (scene.slang:67-74, 110-119)  the four dequantized halves of albedo_color;  each of r, g, b through the sRGB encoding x <=
+ *              0.0031308f ? 12.92f * x : 1.055f * pow(x, 1.0f / 2.4f) - 0.055f, the exponent rounded to binary32 once (0x3ED55555) and pow
+ *              the closed form of oxc_generate_ambient_occlusion (above; a NaN or negative x ends as 0 through saturate, +Inf as 255);
+ *              alpha stays linear;  every channel is u32(floor(saturate(c) * 255.0f + 0.5f)), R in the low byte.
+ *   7. m/r/o   metallic_roughness_occlusion = (metallic_factor, roughness_factor, 1.0, 0.0) by the same unorm8 rule, metallic in the low byte.
+ *   8. emissive  the three dequantized halves of emissive_color packed as UF11 (bits 0-10), UF11 (11-21), UF10 (22-31): 5 exponent bits
+ *              (bias 15) and 6 / 5 mantissa bits.  The Vulkan specification leaves the rounding open; the rule, for the binary32 value:
+ *              NaN gives exponent 31 with an all-ones mantissa; negative values, -0 and -Inf give 0; +Inf gives exponent 31, mantissa 0; a
+ *              value at or above 2^16 gives the largest finite pattern (exponent 30, all-ones mantissa); otherwise the exponent is re-biased
+ *              and the mantissa truncated toward zero, and below 2^-14 the small format's denormals are kept (truncated likewise).
+ * Limits (else OXC_INVALID_ARG, nothing launched): width and height not zero and equal to the depth attachment's (at most 65536 a side);
+ * depth_attachment one R32F level at offset 0; visbuffer_attachment, albedo_attachment, emissive_attachment and
+ * metallic_roughness_occlusion_attachment 4-byte aligned with one u32 per pixel; normal_attachment 8-byte aligned with one u16x4 per pixel;
+ * materials_buffer 4-byte aligned with material_count records of 56 bytes (may be null when material_count is 0); the frame's meshes,
+ * transforms (16-byte aligned), mesh_instances and meshlet_instances buffers not null, the last holding meshlet_instance_count records.  A
+ * MeshLOD's local_triangle_indices must be allocated in whole u32 words (its byte count rounded up to a multiple of 4): get_micro_index loads
+ * the word that holds a byte, as the Slang and oxc_draw_visbuffer do, so the last word is read even when the stream ends inside it.  One
+ * launch, no scratch, no allocation, no host synchronisation; capturable into a HIP graph. */
+typedef struct oxc_decode_context {
+  uint32_t struct_size; /* sizeof(oxc_decode_context) */
+  uint32_t width, height;
+  uint32_t clear;                  /* != 0: empty pixels are written as zero */
+  uint32_t meshlet_instance_count; /* records of frame->meshlet_instances_buffer a texel may name */
+  uint32_t material_count;
+  float projection_view[16];       /* Camera::projection_view, column-major: the matrix the visbuffer was drawn with */
+  oxc_buffer visbuffer_attachment; /* in: u32[height][width], as oxc_draw_visbuffer resolves it */
+  oxc_image depth_attachment;      /* in: R32F, levels = 1, as oxc_draw_visbuffer resolves it */
+  oxc_buffer materials_buffer;     /* in: GPU::Material[material_count], 56 bytes each (SceneGPU.hpp:67-82) */
+  oxc_buffer albedo_attachment;    /* out: R8G8B8A8 sRGB, u32[height][width], R in the low byte */
+  oxc_buffer normal_attachment;    /* out: R16G16B16A16 Sfloat, u16x4[height][width], the layout oxc_resolve_shadowmap reads */
+  oxc_buffer emissive_attachment;  /* out: B10G11R11 UfloatPack32, u32[height][width] */
+  oxc_buffer metallic_roughness_occlusion_attachment; /* out: R8G8B8A8 Unorm, u32[height][width] */
+} oxc_decode_context;
+
+/* meshlet_instances, mesh_instances, meshes and transforms come from `frame`, as in oxc_draw_visbuffer. */
+oxc_status oxc_decode_visbuffer(oxc_ctx* ctx, const oxc_prepared_frame* frame, const oxc_decode_context* context, void* hip_stream);
+
 /* ---- multi-GPU exchange: one process per GPU, RCCL over xGMI ---------------------------
  * The meshlet-instance array shards by contiguous range and every rank culls its shard on its own; the only
  * exchanges of the path are (1) the per-rank counters {emitted meshlets, early, late, index count} to every rank

@@ -86,7 +86,8 @@ enum { OXC_TUNE_ASYNC_MTEST_BLOCKS_PER_CU = 0, OXC_TUNE_ASYNC_TRI_BLOCKS_PER_CU 
                                          the overflow paths */,
        OXC_TUNE_VSM_RESOLVE_STATS = 10 /* 1: oxc_resolve_shadowmap runs its counting instantiation (oxc_debug_vsm_resolve_stats); 0 (default): off */,
        OXC_TUNE_CONTACT_SHADOWS_STATS = 11 /* 1: oxc_contact_shadows runs its counting instantiation (oxc_debug_contact_shadows_stats); 0 (default): off */,
-       OXC_TUNE_AMBIENT_OCCLUSION_STATS = 12 /* 1: oxc_generate_ambient_occlusion runs the counting instantiation of its main kernel (oxc_debug_ambient_occlusion_stats); 0 (default): off */ };
+       OXC_TUNE_AMBIENT_OCCLUSION_STATS = 12 /* 1: oxc_generate_ambient_occlusion runs the counting instantiation of its main kernel (oxc_debug_ambient_occlusion_stats); 0 (default): off */,
+       OXC_TUNE_VISBUFFER_DECODE_STATS = 13 /* 1: oxc_decode_visbuffer runs its counting instantiation (oxc_debug_visbuffer_decode_stats); 0 (default): off */ };
 oxc_status oxc_debug_set_tuning(oxc_ctx* ctx, uint32_t knob, uint32_t value);
 
 /* Measurement aid: counters_dptr != NULL -- the HiZ calls (use_hiz + OXC_CULL_TEST_OCCLUSION) that follow on this context run counting
@@ -129,6 +130,12 @@ oxc_status oxc_debug_contact_shadows_stats(oxc_ctx* ctx, uint32_t* host_out12, v
  * level floor(l) is 0, 1, 2, 3, 4, samples with a non-zero level fraction, non-sky pixels whose stored noisy half is exactly 1.0, strictly
  * inside (0, 1), exactly 0.0, update_sectors calls whose arc has zero width, slices whose sign_norm is -1, 0, +1}. */
 oxc_status oxc_debug_ambient_occlusion_stats(oxc_ctx* ctx, uint32_t* host_out15, void* hip_stream);
+
+/* Measurement hook: what the last oxc_decode_visbuffer on this context did, counted by a counting instantiation of its kernel (same
+ * images, slower) after oxc_debug_set_tuning(OXC_TUNE_VISBUFFER_DECODE_STATS, 1); synchronises the stream.
+ * out4 = {decoded pixels (all four images written from a triangle), empty pixels (rule 1), pixels written as zeros because a vertex index
+ * exceeds vertex_count - 1 (rule 2), decoded pixels whose material_index is beyond material_count (the all-zero Material)}. */
+oxc_status oxc_debug_visbuffer_decode_stats(oxc_ctx* ctx, uint32_t* host_out4, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -91,6 +91,7 @@ struct oxc_ctx {
   PassCounters vsm_resolve_stats;        // OXC_TUNE_VSM_RESOLVE_STATS: u32[8]
   PassCounters contact_shadows_stats;    // OXC_TUNE_CONTACT_SHADOWS_STATS: u32[12]
   PassCounters ambient_occlusion_stats;  // OXC_TUNE_AMBIENT_OCCLUSION_STATS: u32[15] (16 allocated)
+  PassCounters visbuffer_decode_stats;   // OXC_TUNE_VISBUFFER_DECODE_STATS: u32[4]
   void* comm = nullptr;           // ncclComm_t (oxc_comm_init)
   uint32_t comm_rank = 0, comm_world = 0;
   // counter slots
@@ -631,7 +632,7 @@ void oxc_destroy(oxc_ctx* ctx) {
   if (ctx->raster_rows) (void)hipFree(ctx->raster_rows);
   if (ctx->vsm_scratch) (void)hipFree(ctx->vsm_scratch);
   if (ctx->vsm_draw_scratch) (void)hipFree(ctx->vsm_draw_scratch);
-  for (const auto& pc : {ctx->vsm_resolve_stats, ctx->contact_shadows_stats, ctx->ambient_occlusion_stats})
+  for (const auto& pc : {ctx->vsm_resolve_stats, ctx->contact_shadows_stats, ctx->ambient_occlusion_stats, ctx->visbuffer_decode_stats})
     if (pc.dev) (void)hipFree(pc.dev);
   if (ctx->comm) (void)oxc_comm_destroy(ctx);
   if (ctx->slots) (void)hipFree(ctx->slots);
@@ -1909,6 +1910,58 @@ oxc_status oxc_contact_shadows(oxc_ctx* ctx, const oxc_contact_shadows_context* 
   return OXC_OK;
 }
 
+oxc_status oxc_decode_visbuffer(oxc_ctx* ctx, const oxc_prepared_frame* f, const oxc_decode_context* c, void* hip_stream) {
+  if (!ctx) return OXC_INVALID_ARG;
+  if (!f || !c || c->struct_size != sizeof(oxc_decode_context)) return fail(ctx, OXC_INVALID_ARG, "decode_visbuffer: bad frame / context / struct_size");
+  const char* const entry = "decode_visbuffer";
+  const oxc_image& dimg = c->depth_attachment;
+  if (c->width == 0u || c->height == 0u) return bad_arg(ctx, entry, "the extent must not be zero");
+  if (dimg.width != c->width || dimg.height != c->height) return bad_arg(ctx, entry, "depth_attachment extent differs from the visbuffer's (width, height)");
+  uint64_t pixels;
+  OXC_TRY(pixel_images(ctx, entry, dimg, nullptr, nullptr, pixels));
+  if (bad_pixel_buffer(c->visbuffer_attachment, pixels, 4u)) return bad_arg(ctx, entry, "visbuffer_attachment must be one aligned u32 per pixel");
+  if (bad_pixel_buffer(c->albedo_attachment, pixels, 4u) || bad_pixel_buffer(c->emissive_attachment, pixels, 4u) ||
+      bad_pixel_buffer(c->metallic_roughness_occlusion_attachment, pixels, 4u))
+    return bad_arg(ctx, entry, "albedo_attachment, emissive_attachment and metallic_roughness_occlusion_attachment must be one aligned u32 per pixel");
+  if (bad_pixel_buffer(c->normal_attachment, pixels, 8u)) return bad_arg(ctx, entry, "normal_attachment must be 8-byte aligned u16x4 texels of the depth attachment's extent");
+  const oxc_buffer& mat = c->materials_buffer;
+  if (c->material_count && (!mat.dptr || mat.bytes < (uint64_t)c->material_count * 56u || (reinterpret_cast<uintptr_t>(mat.dptr) & 3u)))
+    return bad_arg(ctx, entry, "materials_buffer must hold material_count 4-byte aligned GPU::Material records of 56 bytes");
+  if (!f->meshes_buffer.dptr || !f->transforms_world_buffer.dptr || !f->mesh_instances_buffer.dptr || !f->meshlet_instances_buffer.dptr)
+    return bad_arg(ctx, entry, "null PreparedFrame buffer");
+  if (f->meshlet_instances_buffer.bytes < (uint64_t)c->meshlet_instance_count * sizeof(GpuMeshletInstance))
+    return bad_arg(ctx, entry, "meshlet_instances_buffer smaller than meshlet_instance_count records");
+  if (reinterpret_cast<uintptr_t>(f->transforms_world_buffer.dptr) & 15u) return bad_arg(ctx, entry, "transforms_world_buffer must be 16-byte aligned");
+  OXC_HIP(ctx, hipSetDevice(ctx->device));
+  OXC_ORDER(ctx, hip_stream);
+  const hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  VisbufferDecodeArgs a;
+  std::memset(&a, 0, sizeof a);
+  OXC_TRY(arm_counters(ctx, entry, "hipMalloc(visbuffer decode counters)", ctx->visbuffer_decode_stats, 16, s, &a.stats));
+  a.vis = static_cast<const uint32_t*>(c->visbuffer_attachment.dptr);
+  a.depth_bits = static_cast<const uint32_t*>(dimg.dptr);
+  a.albedo = static_cast<uint32_t*>(c->albedo_attachment.dptr);
+  a.normal = static_cast<uint2*>(c->normal_attachment.dptr);
+  a.emissive = static_cast<uint32_t*>(c->emissive_attachment.dptr);
+  a.mro = static_cast<uint32_t*>(c->metallic_roughness_occlusion_attachment.dptr);
+  a.w = c->width;
+  a.h = c->height;
+  a.fw = (float)c->width;
+  a.fh = (float)c->height;
+  a.clear = c->clear ? 1u : 0u;
+  a.meshlet_instance_count = c->meshlet_instance_count;
+  a.material_count = c->material_count;
+  a.meshlet_instances = static_cast<const GpuMeshletInstance*>(f->meshlet_instances_buffer.dptr);
+  a.mesh_instances = static_cast<const GpuMeshInstance*>(f->mesh_instances_buffer.dptr);
+  a.meshes = static_cast<const GpuMesh*>(f->meshes_buffer.dptr);
+  a.transforms = static_cast<const float*>(f->transforms_world_buffer.dptr);
+  a.materials = static_cast<const uint32_t*>(mat.dptr);
+  for (int k = 0; k < 16; k++) a.pv[k] = c->projection_view[k];
+  launch_visbuffer_decode(a, s);
+  OXC_HIP(ctx, hipGetLastError());
+  return OXC_OK;
+}
+
 oxc_status oxc_generate_ambient_occlusion(oxc_ctx* ctx, const oxc_ambient_occlusion_context* c, void* hip_stream) {
   if (!ctx) return OXC_INVALID_ARG;
   if (!c || c->struct_size != sizeof(oxc_ambient_occlusion_context)) return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: bad context / struct_size");
@@ -2303,6 +2356,7 @@ oxc_status oxc_debug_set_tuning(oxc_ctx* ctx, uint32_t knob, uint32_t value) {
     case OXC_TUNE_VSM_DRAW_STATS: ctx->vsm_draw_stats = value != 0u; return OXC_OK;
     case OXC_TUNE_VSM_RESOLVE_STATS: ctx->vsm_resolve_stats.on = value != 0u; return OXC_OK;
     case OXC_TUNE_CONTACT_SHADOWS_STATS: ctx->contact_shadows_stats.on = value != 0u; return OXC_OK;
+    case OXC_TUNE_VISBUFFER_DECODE_STATS: ctx->visbuffer_decode_stats.on = value != 0u; return OXC_OK;
     case OXC_TUNE_AMBIENT_OCCLUSION_STATS: ctx->ambient_occlusion_stats.on = value != 0u; return OXC_OK;
     case OXC_TUNE_VSM_DRAW_CAPACITY:
       if (ctx->vsm_draw_scratch) return fail(ctx, OXC_INVALID_ARG, "set_tuning: the shadow draw's scratch is allocated by the first oxc_draw_physical_pages; set its capacity before");
@@ -2378,6 +2432,10 @@ oxc_status oxc_debug_vsm_draw_stats(oxc_ctx* ctx, uint32_t* host_out8, void* hip
 
 oxc_status oxc_debug_vsm_resolve_stats(oxc_ctx* ctx, uint32_t* host_out8, void* hip_stream) {
   return read_counters(ctx, "debug_vsm_resolve_stats", "oxc_resolve_shadowmap", &oxc_ctx::vsm_resolve_stats, host_out8, 32, hip_stream);
+}
+
+oxc_status oxc_debug_visbuffer_decode_stats(oxc_ctx* ctx, uint32_t* host_out4, void* hip_stream) {
+  return read_counters(ctx, "debug_visbuffer_decode_stats", "oxc_decode_visbuffer", &oxc_ctx::visbuffer_decode_stats, host_out4, 16, hip_stream);
 }
 
 oxc_status oxc_debug_contact_shadows_stats(oxc_ctx* ctx, uint32_t* host_out12, void* hip_stream) {

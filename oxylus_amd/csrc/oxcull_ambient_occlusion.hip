@@ -24,61 +24,6 @@ namespace oxc {
 namespace {
 constexpr float kHalfPi = 1.57079632679f, kPi = 3.1415926535897932384626433832795f;
 
-OXC_DEV unsigned short f_to_half(float x) { return __builtin_bit_cast(unsigned short, (_Float16)x); }
-
-// the log2 rule before its rounding: binary64, no contraction
-OXC_DEV double log2_f64(float x) {
-  const uint32_t bits = asu(x);
-  int e = (int)((bits >> 23) & 0xFFu) - 127;
-  float m = asf((bits & 0x7FFFFFu) | 0x3F800000u);  // in [1, 2)
-  const bool big = m > 1.41421356f;
-  m = big ? m * 0.5f : m;  // exact
-  e += big ? 1 : 0;
-  const double f = (double)m - 1.0;
-  const double s = f / (2.0 + f);
-  const double z = s * s;
-  double p = 1.0 / 17.0;
-  p = p * z + 1.0 / 15.0;
-  p = p * z + 1.0 / 13.0;
-  p = p * z + 1.0 / 11.0;
-  p = p * z + 1.0 / 9.0;
-  p = p * z + 1.0 / 7.0;
-  p = p * z + 1.0 / 5.0;
-  p = p * z + 1.0 / 3.0;
-  p = p * z + 1.0;
-  double r = (double)e + ((2.0 * s) * p) * 0x1.71547652b82fep+0;
-  r = x >= 0x1p-126f ? r : -__builtin_inf();  // zero, denormal, negative, NaN
-  return x == __builtin_inff() ? __builtin_inf() : r;
-}
-
-// pow(v, p), v >= 0 (or NaN-free by the caller's max), p > 0: exp2(p * log2(v)) in binary64, rounded to binary32 once
-OXC_DEV float pow_rule(float v, float p) {
-  const double y = (double)p * log2_f64(v);
-  const double k = __builtin_floor(y + 0.5);
-  const double r = y - k;  // exact, in [-0.5, 0.5]
-  const double t = r * 0x1.62e42fefa39efp-1;
-  double q = 1.0 / 6227020800.0;
-  q = q * t + 1.0 / 479001600.0;
-  q = q * t + 1.0 / 39916800.0;
-  q = q * t + 1.0 / 3628800.0;
-  q = q * t + 1.0 / 362880.0;
-  q = q * t + 1.0 / 40320.0;
-  q = q * t + 1.0 / 5040.0;
-  q = q * t + 1.0 / 720.0;
-  q = q * t + 1.0 / 120.0;
-  q = q * t + 1.0 / 24.0;
-  q = q * t + 1.0 / 6.0;
-  q = q * t + 1.0 / 2.0;
-  q = q * t + 1.0;
-  q = q * t + 1.0;
-  if (y <= -160.0) return 0.0f;
-  if (y >= 160.0) return __builtin_inff();
-  if (!(y == y)) return __builtin_nanf("");
-  const long long ki = (long long)k;  // in (-161, 161)
-  const double scale = __builtin_bit_cast(double, (unsigned long long)(ki + 1023) << 52);
-  return (float)(q * scale);
-}
-
 OXC_DEV float fast_acos(float in) {
   const float x = __builtin_fabsf(in);
   float res = -0.156583f * x + kHalfPi;
@@ -86,7 +31,6 @@ OXC_DEV float fast_acos(float in) {
   return in >= 0.0f ? res : kPi - res;
 }
 
-OXC_DEV uint32_t pack_unorm(float e) { return cvt_u32_sat(floorf(saturate_f(e) * 255.0f + 0.5f)); }
 OXC_DEV float unorm(uint32_t w, int k) { return (float)((w >> (8 * k)) & 0xFFu) / 255.0f; }
 
 OXC_DEV float weighted_average(float d0, float d1, float d2, float d3, float mul, float add) {

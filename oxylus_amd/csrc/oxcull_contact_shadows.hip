@@ -19,8 +19,6 @@
 namespace oxc {
 
 namespace {
-// mul(M, (x, y, z, 1)).r
-OXC_DEV float row1(const float* m, int r, float x, float y, float z) { return ((OXC_M(m, r, 0) * x + OXC_M(m, r, 1) * y) + OXC_M(m, r, 2) * z) + OXC_M(m, r, 3); }
 // mul(M, (x, y, z, w)).r
 OXC_DEV float row4(const float* m, int r, float x, float y, float z, float w) {
   return ((OXC_M(m, r, 0) * x + OXC_M(m, r, 1) * y) + OXC_M(m, r, 2) * z) + OXC_M(m, r, 3) * w;

@@ -601,6 +601,27 @@ struct AmbientOcclusionArgs {
   float final_power;
 };
 void launch_ambient_occlusion(const AmbientOcclusionArgs& a, hipStream_t s);
+// oxcull_visbuffer_decode.hip: the G-buffer images from the visibility buffer (oxc_decode_visbuffer)
+struct VisbufferDecodeArgs {
+  const uint32_t* vis;         // [h][w]
+  const uint32_t* depth_bits;  // [h][w]: the R32F depth's bit patterns (only "is it 0" is read)
+  uint32_t* albedo;            // [h][w] R8G8B8A8 sRGB
+  uint2* normal;               // [h][w] R16G16B16A16 Sfloat as two words: {r | g << 16, b | a << 16}
+  uint32_t* emissive;          // [h][w] B10G11R11 UfloatPack32
+  uint32_t* mro;               // [h][w] R8G8B8A8 Unorm
+  uint32_t w, h;
+  float fw, fh;                // float(w), float(h)
+  uint32_t clear;
+  uint32_t meshlet_instance_count, material_count;
+  const GpuMeshletInstance* meshlet_instances;
+  const GpuMeshInstance* mesh_instances;
+  const GpuMesh* meshes;
+  const float* transforms;     // 16-byte aligned
+  const uint32_t* materials;   // GPU::Material[material_count], 14 words each
+  uint32_t* stats;             // nullptr, or u32[4] the counting instantiation adds to (oxc_debug_visbuffer_decode_stats)
+  float pv[16];
+};
+void launch_visbuffer_decode(const VisbufferDecodeArgs& a, hipStream_t s);
 // oxcull_bounds.hip: meshlet bounds producer
 void launch_build_meshlet_bounds(const float* pos, uint32_t vertex_count, const void* meshlets, uint32_t meshlet_count, const uint32_t* vidx,
                                  const uint8_t* micro, void* out_bounds, float* out_mesh6, void* out_qpos, float* meshlet_minmax, float* normals,

@@ -1,5 +1,5 @@
-// oxcull_pixel_device.hpp -- the device rules the VSM page update and the per-pixel passes (shadow resolve, contact shadows, ambient
-// occlusion) share: one copy each, so that two kernels which must agree on a pixel's clipmap, page or normal cannot drift apart.
+// oxcull_pixel_device.hpp -- the device rules the VSM page update and the per-pixel passes (visbuffer decode, shadow resolve, contact
+// shadows, ambient occlusion) share: one copy each, so that two kernels which must agree on a pixel's clipmap, page or normal cannot drift apart.
 // Every float operation keeps the order and rounding include/oxcull.h states; the including files are compiled without contraction.
 #pragma once
 
@@ -23,6 +23,68 @@ OXC_DEV int floor_mod_i(int x, int n) {
 OXC_DEV float saturate_f(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }  // a NaN becomes 0 (max(NaN, 0) = 0)
 OXC_DEV float sign_f(float a) { return a > 0.0f ? 1.0f : a < 0.0f ? -1.0f : 0.0f; }
 OXC_DEV int clamp_i(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+// mul(M, (x, y, z, 1)).r
+OXC_DEV float row1(const float* m, int r, float x, float y, float z) { return ((OXC_M(m, r, 0) * x + OXC_M(m, r, 1) * y) + OXC_M(m, r, 2) * z) + OXC_M(m, r, 3); }
+
+// binary32 -> binary16 bits, round to nearest even; the wave's FP16 denormal mode is at its default, so denormal halves are kept
+OXC_DEV unsigned short f_to_half(float x) { return __builtin_bit_cast(unsigned short, (_Float16)x); }
+
+// the log2 rule before its rounding: binary64, no contraction
+OXC_DEV double log2_f64(float x) {
+  const uint32_t bits = asu(x);
+  int e = (int)((bits >> 23) & 0xFFu) - 127;
+  float m = asf((bits & 0x7FFFFFu) | 0x3F800000u);  // in [1, 2)
+  const bool big = m > 1.41421356f;
+  m = big ? m * 0.5f : m;  // exact
+  e += big ? 1 : 0;
+  const double f = (double)m - 1.0;
+  const double s = f / (2.0 + f);
+  const double z = s * s;
+  double p = 1.0 / 17.0;
+  p = p * z + 1.0 / 15.0;
+  p = p * z + 1.0 / 13.0;
+  p = p * z + 1.0 / 11.0;
+  p = p * z + 1.0 / 9.0;
+  p = p * z + 1.0 / 7.0;
+  p = p * z + 1.0 / 5.0;
+  p = p * z + 1.0 / 3.0;
+  p = p * z + 1.0;
+  double r = (double)e + ((2.0 * s) * p) * 0x1.71547652b82fep+0;
+  r = x >= 0x1p-126f ? r : -__builtin_inf();  // zero, denormal, negative, NaN
+  return x == __builtin_inff() ? __builtin_inf() : r;
+}
+
+// pow(v, p), v >= 0 (or NaN-free by the caller's max), p > 0: exp2(p * log2(v)) in binary64, rounded to binary32 once
+OXC_DEV float pow_rule(float v, float p) {
+  const double y = (double)p * log2_f64(v);
+  const double k = __builtin_floor(y + 0.5);
+  const double r = y - k;  // exact, in [-0.5, 0.5]
+  const double t = r * 0x1.62e42fefa39efp-1;
+  double q = 1.0 / 6227020800.0;
+  q = q * t + 1.0 / 479001600.0;
+  q = q * t + 1.0 / 39916800.0;
+  q = q * t + 1.0 / 3628800.0;
+  q = q * t + 1.0 / 362880.0;
+  q = q * t + 1.0 / 40320.0;
+  q = q * t + 1.0 / 5040.0;
+  q = q * t + 1.0 / 720.0;
+  q = q * t + 1.0 / 120.0;
+  q = q * t + 1.0 / 24.0;
+  q = q * t + 1.0 / 6.0;
+  q = q * t + 1.0 / 2.0;
+  q = q * t + 1.0;
+  q = q * t + 1.0;
+  if (y <= -160.0) return 0.0f;
+  if (y >= 160.0) return __builtin_inff();
+  if (!(y == y)) return __builtin_nanf("");
+  const long long ki = (long long)k;  // in (-161, 161)
+  const double scale = __builtin_bit_cast(double, (unsigned long long)(ki + 1023) << 52);
+  return (float)(q * scale);
+}
+
+// one component of packUnorm4x8: u32(floor(saturate(e) * 255.0 + 0.5)); a NaN gives 0
+OXC_DEV uint32_t pack_unorm(float e) { return cvt_u32_sat(floorf(saturate_f(e) * 255.0f + 0.5f)); }
 
 // The pixel of this thread: an 8 x 8 pixel tile per wave, a 16 x 16 tile per block of 256 threads.
 OXC_DEV uint2 tile_pixel() {

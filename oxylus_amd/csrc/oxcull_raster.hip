@@ -625,6 +625,15 @@ __global__ __launch_bounds__(256) void k_draw_big_tiles(DrawArgs a) {
   }
 }
 
+// The draw's clears as one kernel: `n` texels of the packed image and `words` u32 of the scratch header.  Not hipMemsetAsync: captured into
+// a HIP graph, the memset node of the image zero-filled it on the first replay only and wrote other bytes from the second replay on
+// (DESIGN.md section 15); a kernel node replays as it was captured.
+__global__ __launch_bounds__(256) void k_draw_clear(unsigned long long* __restrict__ visdepth, uint64_t n, uint32_t* __restrict__ header, uint32_t words) {
+  const uint64_t first = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = first; i < n; i += stride) visdepth[i] = 0ull;
+  for (uint64_t i = first; i < words; i += stride) header[i] = 0u;
+}
+
 __global__ __launch_bounds__(256) void k_resolve_visbuffer(const unsigned long long* __restrict__ visdepth, uint64_t n, float* __restrict__ depth,
                                                            uint32_t* __restrict__ vis) {
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
@@ -636,8 +645,9 @@ __global__ __launch_bounds__(256) void k_resolve_visbuffer(const unsigned long l
 
 void launch_draw_visbuffer(const DrawArgs& a, bool clear, float* depth_out, uint32_t* vis_out, uint32_t max_grid, hipStream_t s) {
   const uint64_t n = (uint64_t)a.width * a.height;
-  if (clear) (void)hipMemsetAsync(a.visdepth, 0, n * 8u, s);
-  (void)hipMemsetAsync(a.clip_count, 0, kRasterHeaderBytes, s);  // clip / tile counters and the big list's segment counters
+  // the image (with `clear`) and the clip / tile counters and the big list's segment counters
+  hipLaunchKernelGGL(k_draw_clear, dim3((uint32_t)std::min<uint64_t>(((clear ? n : 0) + kRasterHeaderBytes / 4u + 255) / 256, max_grid)), dim3(256), 0, s,
+                     a.visdepth, clear ? n : 0, a.clip_count, kRasterHeaderBytes / 4u);
   hipLaunchKernelGGL(k_draw_rows, dim3(std::max(1u, std::min((a.mesh_instance_count + 255u) / 256u, max_grid))), dim3(256), 0, s, a);
   if (a.wide == 2u) {  // {id, corner} pairs
     hipLaunchKernelGGL(k_draw_setup<true>, dim3(max_grid), dim3(256), 0, s, a);

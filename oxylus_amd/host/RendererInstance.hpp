@@ -53,6 +53,7 @@ struct PreparedFrame {
   Buffer visible_meshlet_instances_indices_buffer = {};
   Buffer meshlet_instance_visibility_mask_buffer = {};
   Buffer reordered_indices_buffer = {};
+  Buffer materials_buffer = {};  // GPU::Material[], read by decode_visbuffer
 };
 
 struct CullGeometryContext {
@@ -104,6 +105,12 @@ struct MainGeometryContext {
   Buffer visdepth_buffer = {};
   bool clear = true;
   uint32_t wide_triangle_index = 0;
+  // decode_visbuffer's outputs, linear buffers of width * height texels in the reference's formats (RendererInstance.cpp:700-737):
+  // R8G8B8A8 sRGB, R16G16B16A16 Sfloat, B10G11R11 UfloatPack32, R8G8B8A8 Unorm
+  Buffer albedo_attachment = {};
+  Buffer normal_attachment = {};
+  Buffer emissive_attachment = {};
+  Buffer metallic_roughness_occlusion_attachment = {};
 };
 
 // What resolve_shadowmap reads and writes (Passes/Shadowmaps.cpp:756-822): the GPU::VSMContext and GPU::Camera fields, the main view's depth
@@ -211,6 +218,35 @@ public:
     d.depth_attachment = context.depth_attachment;
     d.visbuffer_attachment = context.visbuffer_attachment;
     check(oxc_draw_visbuffer(ctx_, &f, &d, stream_));
+  }
+
+  // Oxylus/src/Render/Passes/DrawGeometry.cpp:192-274, the full-screen pass after the draw (RendererInstance.cpp:924): the four G-buffer
+  // images from visbuffer_attachment / depth_attachment, with context.cull_camera.projection_view as Camera::projection_view and
+  // prepared_frame.materials_buffer.  Material factors only, no texture sampling.  Rules: include/oxcull.h, oxc_decode_visbuffer.
+  auto decode_visbuffer(MainGeometryContext& context) -> void {
+    oxc_prepared_frame f = {};
+    f.mesh_instance_count = prepared_frame.mesh_instance_count;
+    f.max_meshlet_instance_count = prepared_frame.max_meshlet_instance_count;
+    f.meshes_buffer = prepared_frame.meshes_buffer;
+    f.transforms_world_buffer = prepared_frame.transforms_world_buffer;
+    f.mesh_instances_buffer = prepared_frame.mesh_instances_buffer;
+    f.meshlet_instances_buffer = prepared_frame.meshlet_instances_buffer;
+    oxc_decode_context d = {};
+    d.struct_size = sizeof d;
+    d.width = context.depth_attachment.width;
+    d.height = context.depth_attachment.height;
+    d.clear = 1;  // the engine clears the four images to black before the pass
+    d.meshlet_instance_count = static_cast<uint32_t>(prepared_frame.meshlet_instances_buffer.bytes / 8u);
+    d.material_count = static_cast<uint32_t>(prepared_frame.materials_buffer.bytes / 56u);
+    for (int i = 0; i < 16; i++) d.projection_view[i] = context.cull_camera.projection_view[i];
+    d.visbuffer_attachment = context.visbuffer_attachment;
+    d.depth_attachment = context.depth_attachment;
+    d.materials_buffer = prepared_frame.materials_buffer;
+    d.albedo_attachment = context.albedo_attachment;
+    d.normal_attachment = context.normal_attachment;
+    d.emissive_attachment = context.emissive_attachment;
+    d.metallic_roughness_occlusion_attachment = context.metallic_roughness_occlusion_attachment;
+    check(oxc_decode_visbuffer(ctx_, &f, &d, stream_));
   }
 
   // Oxylus/src/Render/Passes/Terrain.cpp:159-216 (the reference's TerrainContext carries the Terrain object; here its GPU-side fields)

@@ -39,6 +39,7 @@ int main(int argc, char**) {
     std::printf("expected (no attachments bound): %s\n", e.what());
   }
   run_geometry_pass(true);
+  try { self.decode_visbuffer(main_geometry_context); } catch (const std::exception& e) { std::printf("expected (no attachments bound): %s\n", e.what()); }  // RendererInstance.cpp:924
   try {  // RendererInstance.cpp:974-985: the shadow term, after draw_virtual_shadowmap
     self.resolve_shadowmap(ShadowResolveContext{});
   } catch (const std::exception& e) {

@@ -29,6 +29,7 @@ STAGE_ALL = 7
 
 TUNE_ASYNC_MTEST_BLOCKS_PER_CU, TUNE_ASYNC_TRI_BLOCKS_PER_CU, TUNE_RASTER_BIG_CAPACITY, TUNE_TRI_BLOCKS_PER_CU, TUNE_MV_EXPAND_ASYNC, TUNE_TRI_LOADS = 0, 1, 2, 3, 5, 7  # oxc_debug_set_tuning knobs
 TUNE_VSM_DRAW_STATS, TUNE_VSM_DRAW_CAPACITY, TUNE_VSM_RESOLVE_STATS, TUNE_CONTACT_SHADOWS_STATS, TUNE_AMBIENT_OCCLUSION_STATS = 8, 9, 10, 11, 12
+TUNE_VISBUFFER_DECODE_STATS = 13
 
 
 class Buffer(C.Structure):
@@ -354,6 +355,26 @@ class AmbientOcclusionContext(C.Structure):
     ]
 
 
+class DecodeContext(C.Structure):
+    """oxc_decode_context (include/oxcull.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("clear", C.c_uint32),
+        ("meshlet_instance_count", C.c_uint32),
+        ("material_count", C.c_uint32),
+        ("projection_view", C.c_float * 16),
+        ("visbuffer_attachment", Buffer),
+        ("depth_attachment", Image),
+        ("materials_buffer", Buffer),
+        ("albedo_attachment", Buffer),
+        ("normal_attachment", Buffer),
+        ("emissive_attachment", Buffer),
+        ("metallic_roughness_occlusion_attachment", Buffer),
+    ]
+
+
 # every symbol include/oxcull.h declares
 EXPORTS = [
     "oxc_abi_version",
@@ -385,6 +406,8 @@ EXPORTS = [
     "oxc_update_virtual_shadowmap",
     "oxc_cull_terrain",
     "oxc_draw_visbuffer",
+    "oxc_decode_visbuffer",
+    "oxc_debug_visbuffer_decode_stats",
     "oxc_draw_physical_pages",
     "oxc_debug_vsm_draw_stats",
     "oxc_resolve_shadowmap",
@@ -486,6 +509,8 @@ def load(path: str = None) -> C.CDLL:
     lib.oxc_broadcast_hiz_levels.argtypes = [vp, C.POINTER(Image), C.c_uint32, C.c_uint64, C.c_uint32, vp]
     lib.oxc_debug_project_aabb.argtypes = [vp, C.POINTER(C.c_float), C.c_float, vp, C.c_uint32, vp, vp]
     lib.oxc_draw_visbuffer.argtypes = [vp, C.POINTER(PreparedFrame), C.POINTER(DrawContext), vp]
+    lib.oxc_decode_visbuffer.argtypes = [vp, C.POINTER(PreparedFrame), C.POINTER(DecodeContext), vp]
+    lib.oxc_debug_visbuffer_decode_stats.argtypes = [vp, vp, vp]
     lib.oxc_draw_physical_pages.argtypes = [vp, C.POINTER(PreparedFrame), C.POINTER(VsmDrawContext), vp]
     lib.oxc_debug_vsm_draw_stats.argtypes = [vp, vp, vp]
     lib.oxc_resolve_shadowmap.argtypes = [vp, C.POINTER(ShadowResolveContext), vp]

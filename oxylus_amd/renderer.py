@@ -474,6 +474,52 @@ class AmbientOcclusionContext:
 
 
 @dataclass
+class VisbufferDecodeContext:
+    """oxc_decode_context: RendererInstance::decode_visbuffer (Passes/DrawGeometry.cpp:192-274), the geometry and material-factor half of
+    visbuffer_decode.slang.  `create` takes the visbuffer and the depth as oxc_draw_visbuffer resolved them, the matrix they were drawn with and
+    the materials, and allocates the four G-buffer images; the scene buffers come from the renderer's prepared_frame."""
+    visbuffer_attachment: torch.Tensor            # int32 [H, W]
+    depth_attachment: ImageAttachment             # R32F, levels = 1
+    projection_view: list                         # column-major float[16]
+    meshlet_instance_count: int
+    materials_buffer: Optional[torch.Tensor]      # uint8 [material_count * 56] GPU::Material records (synth.pack_materials)
+    material_count: int
+    albedo_attachment: torch.Tensor               # int32 [H, W] out: R8G8B8A8 sRGB
+    normal_attachment: torch.Tensor               # int16 [H, W, 4] out: R16G16B16A16 Sfloat bits, what the resolve and the ambient occlusion read
+    emissive_attachment: torch.Tensor             # int32 [H, W] out: B10G11R11 UfloatPack32
+    metallic_roughness_occlusion_attachment: torch.Tensor  # int32 [H, W] out: R8G8B8A8 Unorm
+    clear: bool = True
+
+    @staticmethod
+    def create(visbuffer: torch.Tensor, depth, projection_view, meshlet_instance_count: int, materials: Optional[torch.Tensor] = None,
+               clear: bool = True) -> "VisbufferDecodeContext":
+        d = depth if isinstance(depth, ImageAttachment) else ImageAttachment.depth(depth)
+        dev = d.data.device
+        assert visbuffer.dtype == torch.int32 and tuple(visbuffer.shape) == (d.height, d.width) and visbuffer.is_contiguous()
+        z32 = lambda: torch.zeros((d.height, d.width), dtype=torch.int32, device=dev)  # noqa: E731
+        count = 0 if materials is None else materials.numel() * materials.element_size() // 56
+        return VisbufferDecodeContext(visbuffer, d, [float(x) for x in projection_view], int(meshlet_instance_count), materials, count, z32(),
+                                      torch.zeros((d.height, d.width, 4), dtype=torch.int16, device=dev), z32(), z32(), bool(clear))
+
+    def c(self) -> L.DecodeContext:
+        c = L.DecodeContext()
+        c.struct_size = C.sizeof(L.DecodeContext)
+        c.width, c.height = self.depth_attachment.width, self.depth_attachment.height
+        c.clear = int(bool(self.clear))
+        c.meshlet_instance_count, c.material_count = int(self.meshlet_instance_count), int(self.material_count)
+        for i in range(16):
+            c.projection_view[i] = float(self.projection_view[i])
+        c.visbuffer_attachment = _buf(self.visbuffer_attachment)
+        c.depth_attachment = self.depth_attachment.c()
+        c.materials_buffer = _buf(self.materials_buffer)
+        c.albedo_attachment = _buf(self.albedo_attachment)
+        c.normal_attachment = _buf(self.normal_attachment)
+        c.emissive_attachment = _buf(self.emissive_attachment)
+        c.metallic_roughness_occlusion_attachment = _buf(self.metallic_roughness_occlusion_attachment)
+        return c
+
+
+@dataclass
 class MainGeometryContext:
     """The fields generate_hiz uses (RendererInstance.hpp:199-216)."""
     depth_attachment: ImageAttachment
@@ -672,6 +718,20 @@ class RendererInstance:
             d.visbuffer_attachment = L.Buffer(C.c_void_p(visbuffer.data_ptr()), visbuffer.numel() * 4)
         self._keep = (visdepth, depth, visbuffer, draw_cmd)
         self._check(self._lib.oxc_draw_visbuffer(self._ctx, C.byref(f), C.byref(d), self._stream(stream)))
+
+    def decode_visbuffer(self, context: VisbufferDecodeContext, stream=None):
+        """Passes/DrawGeometry.cpp:192-274 (visbuffer_decode): per pixel the triangle behind the visbuffer texel, its perspective-correct
+        barycentrics, the interpolated vertex normal and the material factors, into the four G-buffer images of `context`
+        (include/oxcull.h, oxc_decode_visbuffer)."""
+        assert self.prepared_frame is not None
+        f = self.prepared_frame.c()
+        c = context.c()
+        self._keep = context
+        self._check(self._lib.oxc_decode_visbuffer(self._ctx, C.byref(f), C.byref(c), self._stream(stream)))
+
+    def debug_visbuffer_decode_stats(self, stream=None) -> dict:
+        """What the last decode_visbuffer did, after debug_set_tuning(L.TUNE_VISBUFFER_DECODE_STATS, 1) (measurement hook; synchronises)."""
+        return self._read_stats(self._lib.oxc_debug_visbuffer_decode_stats, stream, ("decoded", "empty", "zero_vertex_index", "default_material"))
 
     def draw_physical_pages(self, context: VsmDrawContext, stream=None):
         """Shadowmaps.cpp:466-754 (rmvsm_build_draw_commands + rmvsm_draw_physical_pages): rasterise the shadow cull's triangles once per

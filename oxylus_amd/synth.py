@@ -77,6 +77,9 @@ class Scene:
     n_meshes: int = 0
     lod_meshlet_counts: Optional[list] = None
     _lod_tables: Optional[dict] = None
+    # what visbuffer_decode reads beyond the cull path (both optional; sub-scenes made by prefix / slice / take do not carry them)
+    normals: Optional[torch.Tensor] = None    # int32 [.., ]  10:10:10 vertex normals, one per entry of `positions`
+    materials: Optional[torch.Tensor] = None  # uint8 [n * 56]  GPU::Material records (pack_materials)
 
     @property
     def n_mesh_instances(self) -> int:
@@ -114,7 +117,7 @@ class Scene:
         lods[:, 4] = base_vidx + t["vidx_start"].to(dev) * 4
         meshes = self.meshes
         meshes[:, 0] = base_pos + t["mesh_vertex_start"].to(dev) * 8
-        meshes[:, 1] = 0
+        meshes[:, 1] = 0 if self.normals is None else self.normals.data_ptr() + t["mesh_vertex_start"].to(dev) * 4
         meshes[:, 2] = 0
         L = self.spec.lod_count
         meshes[:, 4] = lods.data_ptr() + torch.arange(self.n_meshes, dtype=torch.int64, device=dev) * (64 * L)
@@ -126,6 +129,9 @@ class Scene:
         for name in ("bounds", "meshlets", "micro", "vidx", "positions", "lods", "meshes", "transforms",
                      "mesh_instances", "meshlet_instances"):
             kw[name] = getattr(self, name).to(device).contiguous().clone()
+        for name in ("normals", "materials"):
+            if getattr(self, name) is not None:
+                kw[name] = getattr(self, name).to(device).contiguous().clone()
         s = Scene(spec=self.spec, device=device, camera=self.camera, n_meshes=self.n_meshes,
                   lod_meshlet_counts=self.lod_meshlet_counts, _lod_tables=self._lod_tables, **kw)
         return s.bind()
@@ -659,9 +665,11 @@ def build_meshlets_simple(triangles: torch.Tensor, max_vertices: int = 64, max_t
 
 
 def make_scene_from_mesh(n_mesh_instances: int, bounds: torch.Tensor, meshlets: torch.Tensor, micro: torch.Tensor, vidx: torch.Tensor,
-                         positions_u16x4: torch.Tensor, mesh_bounds6: torch.Tensor, seed: int = 0x0A1DE5, device="cpu", **spec_kw) -> Scene:
+                         positions_u16x4: torch.Tensor, mesh_bounds6: torch.Tensor, seed: int = 0x0A1DE5, device="cpu", normals: torch.Tensor = None,
+                         **spec_kw) -> Scene:
     """A scene of `n_mesh_instances` randomly placed instances of ONE real mesh whose GPU arrays come from the
-    asset path (clusteriser output + oxc_build_meshlet_bounds / its checker): the producer -> cull hand-over."""
+    asset path (clusteriser output + oxc_build_meshlet_bounds / its checker): the producer -> cull hand-over.
+    `normals`: the mesh's 10:10:10 vertex normals (int32 [V], oxc_quantize_vertex_streams), for visbuffer_decode."""
     K = int(meshlets.shape[0])
     spec = SceneSpec(n_mesh_instances=n_mesh_instances, meshlets_per_mesh=K, share_meshes=1, with_geometry=False, seed=seed, **spec_kw)
     s = make_scene(spec, device)
@@ -671,6 +679,9 @@ def make_scene_from_mesh(n_mesh_instances: int, bounds: torch.Tensor, meshlets: 
     s.micro = micro.to(dev).contiguous().clone()
     s.vidx = vidx.to(dev).contiguous().clone()
     s.positions = positions_u16x4.to(dev).contiguous().clone()
+    if normals is not None:
+        assert normals.dtype == torch.int32 and normals.shape[0] == positions_u16x4.shape[0]
+        s.normals = normals.to(dev).contiguous().clone()
     m32 = s.meshes.view(torch.int32)
     m32[0, 6] = int(positions_u16x4.shape[0])
     m32[0, 10:16] = mesh_bounds6.to(dev).to(torch.float32).view(torch.int32)
@@ -680,6 +691,33 @@ def make_scene_from_mesh(n_mesh_instances: int, bounds: torch.Tensor, meshlets: 
                           "tris_per_meshlet": int(meshlets[:, 3].max().item()) if K else 0,
                           "verts_per_meshlet": int(meshlets[:, 2].max().item()) if K else 0})
     return s.bind()
+
+
+def pack_materials(albedo, emissive=None, roughness=None, metallic=None, alpha_cutoff=None, flags=None) -> torch.Tensor:
+    """-> uint8 [n * 56]: GPU::Material records (SceneGPU.hpp:67-82).  albedo [n, 4], emissive [n, 3], roughness / metallic / alpha_cutoff [n]
+    are rounded to binary16; an integer array (any of them) is taken as the half bit patterns themselves.  The image indices, the sampler
+    index, uv_size and uv_offset stay zero: oxc_decode_visbuffer reads none of them."""
+    import numpy as np
+
+    def halves(v, shape):
+        if v is None:
+            return np.zeros(shape, dtype=np.uint16)
+        v = np.asarray(v)
+        if np.issubdtype(v.dtype, np.integer):
+            return (v.astype(np.int64) & 0xFFFF).astype(np.uint16).reshape(shape)
+        with np.errstate(all="ignore"):
+            return v.astype(np.float32).astype(np.float16).view(np.uint16).reshape(shape)
+
+    n = int(np.asarray(albedo).shape[0])
+    rec = np.zeros((n, 28), dtype=np.uint16)
+    rec[:, 0:4] = halves(albedo, (n, 4))
+    rec[:, 4:7] = halves(emissive, (n, 3))
+    rec[:, 7] = halves(roughness, (n,))
+    rec[:, 8] = halves(metallic, (n,))
+    rec[:, 9] = halves(alpha_cutoff, (n,))
+    if flags is not None:
+        rec.view(np.uint32)[:, 5] = np.asarray(flags, dtype=np.uint32)
+    return torch.from_numpy(rec.view(np.uint8).reshape(-1).copy())
 
 
 # ---------------------------------------------------------------------------------------------
