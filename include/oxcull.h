@@ -1014,6 +1014,127 @@ typedef struct oxc_decode_context {
 /* meshlet_instances, mesh_instances, meshes and transforms come from `frame`, as in oxc_draw_visbuffer. */
 oxc_status oxc_decode_visbuffer(oxc_ctx* ctx, const oxc_prepared_frame* frame, const oxc_decode_context* context, void* hip_stream);
 
+/* ---- PBR apply: the lit HDR image from the G-buffer and the shadow terms --------------------------------------------------
+ * Replaces the no-atmosphere branch of RendererInstance::apply_pbr (Oxylus/src/Render/Passes/PBR.cpp:313-534, the else branch from :435,
+ * pipeline pbr_apply_no_atmos, passes/pbr_apply_no_atmos.slang with pbr.slang), the full-screen pass that reads what oxc_decode_visbuffer,
+ * oxc_resolve_shadowmap, oxc_contact_shadows and oxc_generate_ambient_occlusion wrote and the first one whose output is a picture.
+ * Out of scope: the atmosphere branch (passes/pbr_apply.slang: the sky LUTs, the cubemap, aerial perspective) -- scene_flags with
+ * OXC_SCENE_HAS_ATMOSPHERE is OXC_INVALID_ARG; tone mapping and the other post passes; tiled or clustered light culling (the reference
+ * has none); any change to what the five producer passes write.
+ * Arithmetic: the canonical binary32 arithmetic of the other passes -- round to nearest even, one fixed order, no contraction, IEEE division
+ * and square root; 1.0 / x is a division; min, max, clamp and saturate go through fmaxf / fminf, so a NaN operand loses (saturate(NaN) = 0,
+ * clamp(x, lo, hi) = min(max(x, lo), hi)); sums and dot products run left to right as written in the Slang (dot(a, b) = (a.x * b.x + a.y *
+ * b.y) + a.z * b.z); a product of three factors a * b * c is (a * b) * c; lerp(a, b, t) = a + (b - a) * t; reflect(i, n) = i - (2.0 * dot(n,
+ * i)) * n; length(v) = sqrt(dot(v, v)), normalize(v) = v / length(v) (three divisions), smoothstep(e0, e1, x): s = saturate((x - e0) / (e1 -
+ * e0)), (s * s) * (3.0 - 2.0 * s), as oxc_contact_shadows states them.  PI = 3.1415926535897932f rounded to binary32 once; Fd_Lambert() =
+ * 1.0f / PI, one binary32 division.  A comparison with a NaN operand is false.  The reference is compiled fast-math and reads its images
+ * through samplers: this is the one evaluation the device and the checker (tests/pbr_apply_model.py) both follow.
+ * Per pixel (x, y) of the W x H images:
+ *   1. transparent  (:34-38)  depth = the depth texel.  With OXC_SCENE_TRANSPARENT_BACKGROUND and depth == 0.0 all four channels are 0 and the
+ *              pixel is done (class "transparent empty").
+ *   2. decode  (:40-54)  albedo: Stated rule: the linear sampler at the pixel centre is, in exact arithmetic, the texel itself: a load of
+ *              texel (x, y).  Bytes R, G, B (R in the low byte; alpha is not read) through the sRGB decode c = f32(byte) / 255.0f;  c <=
+ *              0.04045f ? c / 12.92f : pow((c + 0.055f) / 1.055f, 2.4f), pow the pow rule of oxc_generate_ambient_occlusion with the exponent
+ *              rounded to binary32 once (256 possible results).  normal: the four halves through binary16 -> binary32, exact, denormals kept;
+ *              mapped = oct_to_vec3(.rg), smooth = oct_to_vec3(.ba), oct_to_vec3 as in oxc_resolve_shadowmap step 2 (one normalisation
+ *              inside).  emission: UF11 (bits 0-10), UF11 (11-21), UF10 (22-31) decoded exactly -- exponent field 0: mantissa * 2^-(14 + M),
+ *              1..30: (1 + mantissa / 2^M) * 2^(e - 15), 31: +Inf for a zero mantissa, NaN otherwise (M = 6 or 5 mantissa bits); every
+ *              pattern is a binary32 value.  metallic_roughness_occlusion: bytes 0, 1, 2 as f32(byte) / 255.0f;  metallic = clamp(.r, 0.0,
+ *              1.0);  roughness = clamp(.g, 0.045f, 1.0);  occlusion = .b * ao, ao the ambient-occlusion half (binary16 -> binary32, exact,
+ *              denormals kept).
+ *   3. position  (:56-58)  uv = ((f32(x) + 0.5) / f32(W), (f32(y) + 0.5) / f32(H));  NDC = (uv * 2.0 - 1.0, depth);  h = mul(inv_projection_view,
+ *              (NDC, 1)) row by row as in oxc_decode_visbuffer;  world = h.xyz / h.w, three divisions.
+ *   4. frame   (:63-67)  V = normalize(camera_position - world);  N = normalize(mapped) (a second normalisation, as the Slang);  R =
+ *              reflect(-V, N);  NoV = |dot(N, V)| + 1e-5f;  NoL = max(dot(N, L), 0.0), L = sun_dir as given (not normalised).
+ *   5. sky     (:69-71)  With OXC_SCENE_HAS_SKY and depth == 0.0 the colour is sky_has_texture != 0 ? (1, 1, 1) : sky_solid_color.rgb and the
+ *              pixel is done (class "sky"; it cannot be reached with a transparent background, so its alpha is never stored).  Without
+ *              either flag a pixel with depth == 0.0 runs on as the Slang does (class "fall-through empty"): the IEEE results are the rule,
+ *              a division by a zero h.w included.
+ *   6. terms   (:73-84)  directional_shadow = HasDirectionalLight ? resolved_shadows texel : 1.0;  contact_shadow = HasContactShadows ?
+ *              contact_shadows texel : 1.0;  visibility = directional_shadow * contact_shadow;  direct = HasDirectionalLight ? sun_intensity
+ *              : 0.0;  env = HasSky ? sky_ambient_color : base_ambient_color.  An image whose flag is clear is not read.
+ *   7. surface (pbr.slang:6-9, 35-50, 69-73; hoisted: BRDF recomputes them with the same operands for every light)  F0 = lerp(0.04f, albedo,
+ *              metallic) per channel;  alpha = max(roughness * roughness, 0.0025f);  alpha2 = alpha * alpha;
+ *              GGX_directional_albedo(NoV, alpha): x = NoV, y = alpha, x2 = x * x, y2 = y * y;  per component k of the nine float4 constants
+ *              c0..c8 as the Slang lists them:  r_k = (((((((c0 + c1 * x) + c2 * y) + (c3 * x) * y) + c4 * x2) + c5 * y2) + (c6 * x2) * y) +
+ *              (c7 * x) * y2) + (c8 * x2) * y2;  AB = (clamp(r_0 / r_2, 0.0, 1.0), clamp(r_1 / r_3, 0.0, 1.0));  Ess = saturate(AB.x + AB.y);
+ *              energy_compensation = 1.0 + (F0 * (1.0 - Ess)) / max(Ess, 1e-4f) per channel.
+ *   8. ambient (:86-100)  kS = F0 * AB.x + AB.y;  kD = (1.0 - metallic) * (1.0 - kS);  spec_occlusion = saturate((pow(NoV + occlusion,
+ *              exp2(-16.0 * roughness - 1.0)) - 1.0) + occlusion), pow the pow rule (a base below 2^-126, negative or NaN gives 0), exp2 the
+ *              exp2 rule below;  ibl_diffuse = ((kD * env) * albedo) * Fd_Lambert();  ibl_specular = (kS * env) * spec_occlusion;  indirect =
+ *              ibl_diffuse * occlusion + ibl_specular.
+ *   9. lights  (:102-113, pbr.slang:89-172)  total = 0;  for i = 0 .. light_count - 1 in order, light = lights[i] (64 bytes: position f32x3,
+ *              intensity, color f32x3, range, direction f32x3, inner_cone_angle, outer_cone_angle, kind u32, two pad words).  kind == 1
+ *              (Point) and kind == 2 (Spot) are shaded; every other value (0 = Directional included) is skipped, as the Slang's if / else if.
+ *              lv = light.position - world;  dist = length(lv);  Ll = lv / dist;  attenuation = lights_attenuate_point(dist, range): range <=
+ *              0.0 gives 1.0 / (dist * dist + 0.1f);  otherwise (a NaN range too) win = dist / range, win = ((win * win) * win) * win, win =
+ *              max(0.0, 1.0 - win), win = win * win, win / (dist * dist + 0.1f).  Spot: attenuation = attenuation * smoothstep(cos(outer),
+ *              cos(inner), dot(-Ll, normalize(direction))), cos the cos rule below.  attenuation <= 0.0 || intensity <= 0.0 ends the light
+ *              (outcome "attenuation or intensity out"; a NaN passes both tests);  NdotL = saturate(dot(N, Ll));  NdotL <= 0.0 ends it
+ *              (outcome "NdotL out").  Otherwise (outcome "shaded") b = BRDF(V, N, Ll) of step 10;  radiance = (color * attenuation) *
+ *              intensity;  total += ((b.diffuse + b.specular) * radiance) * NdotL per channel.  A light that ends early adds nothing.
+ *  10. BRDF(V, N, l)  (pbr.slang:11-24, 61-87)  VL = V + l;  H = dot(VL, VL) > 1e-8f ? normalize(VL) : N;  NoLb = saturate(dot(N, l));  NoH =
+ *              saturate(dot(N, H));  LoH = saturate(dot(l, H));  f = (NoH * alpha2 - NoH) * NoH + 1.0;  D = alpha2 / ((PI * f) * f + 1e-7f);
+ *              GGXV = NoLb * sqrt((NoV * NoV) * (1.0 - alpha2) + alpha2);  GGXL = NoV * sqrt((NoLb * NoLb) * (1.0 - alpha2) + alpha2);  Vis =
+ *              saturate(0.5 / ((GGXV + GGXL) + 1e-7f));  F = F0 + (1.0 - F0) * pow(saturate(1.0 - LoH), 5.0) per channel, the pow rule;
+ *              specular = ((D * Vis) * F) * energy_compensation;  diffuse = (((1.0 - metallic) * (1.0 - F)) * albedo) * Fd_Lambert().
+ *  11. sun     (:115-123)  horizon = saturate(1.0 + 1.3f * dot(R, smooth));  horizon = horizon * horizon;  surface = 0;  if NoL > 0.0 (class
+ *              "lit, NoL > 0"; otherwise "lit, NoL == 0"):  b = BRDF(V, N, L);  surface = (((b.diffuse + b.specular * horizon) * direct) *
+ *              NoL) * visibility per channel.
+ *  12. store   (:125-126)  colour = ((surface + total) + indirect) + emission per channel, alpha = 1.0.  Without
+ *              OXC_SCENE_TRANSPARENT_BACKGROUND final_attachment is B10G11R11 UfloatPack32: R, G, B packed as UF11, UF11, UF10 by the rule of
+ *              oxc_decode_visbuffer step 8.  With it, R16G16B16A16 Sfloat: each channel converted to binary16 with round to nearest even,
+ *              denormals kept, a NaN stored as 0x7E00 (oxc_decode_visbuffer step 5), R in the lowest half.  So no NaN bit pattern of the
+ *              arithmetic reaches the image.
+ * exp2 rule, for a binary32 t:  y = (double)t, then the second half of the pow rule: k = floor(y + 0.5), r = y - k, E(r * ln 2) * 2^k rounded
+ *   to binary32 once; y <= -160 gives 0.0, y >= 160 gives +Inf, NaN gives NaN.
+ * cos rule, for a binary32 x:  a non-finite x or |x| > 2^24 gives NaN (so a spot light with such an angle ends at its attenuation test).
+ *   Otherwise in binary64, no contraction:  a = |x|;  q = floor(a * 0x1.45f306dc9c883p-1 + 0.5) (an integer below 2^24);  r = (a - q *
+ *   0x1.921fb54p+0) - q * 0x1.10b4611a62633p-30 (pi / 2 in two constants: the first has 29 significant bits, so its product with q is
+ *   exact);  z = r * r;  S = r + (r * z) * ps(z), Cc = 1.0 + z * pc(z) with the two polynomials of the rotation rule of oxc_resolve_shadowmap
+ *   step 6;  cos = Cc, -S, -Cc, S for q mod 4 = 0, 1, 2, 3, rounded to binary32 once.  Within one binary32 ulp of the correctly rounded
+ *   cosine on [0, pi] (tests/test_pbr_apply_model.py).
+ * Limits (else OXC_INVALID_ARG, nothing launched, the output untouched): width and height not zero, at most 65536 a side and equal to the
+ * depth attachment's; depth_attachment one R32F level at offset 0; albedo, emissive and metallic_roughness_occlusion 4-byte aligned with one
+ * u32 per pixel; normal_attachment 8-byte aligned with one u16x4 per pixel; ambient_occlusion_attachment 2-byte aligned with one u16 per
+ * pixel; resolved_shadows_attachment (read with HasDirectionalLight) and contact_shadows_attachment (read with HasContactShadows) one R32F
+ * level of the depth's extent at offset 0 -- an image whose flag is clear is not read, not checked and may be null; lights_buffer 4-byte
+ * aligned with light_count records of 64 bytes (may be null when light_count is 0); final_attachment 4-byte aligned with one u32 per pixel,
+ * or 8-byte aligned with one u16x4 per pixel with a transparent background; every host scalar (the matrix, camera_position, sun_dir,
+ * sun_intensity, the three colours) finite.  Light records live on the device and are not validated: the rule gives a defined result for
+ * any bit pattern in them.  One launch, no scratch, no allocation, no host synchronisation; capturable into a HIP graph. */
+#define OXC_SCENE_HAS_DIRECTIONAL_LIGHT (1u << 0)  /* GPU::SceneFlags (scene.slang:242-256); the other bits are not read */
+#define OXC_SCENE_HAS_ATMOSPHERE (1u << 1)         /* not built: OXC_INVALID_ARG */
+#define OXC_SCENE_HAS_CONTACT_SHADOWS (1u << 9)
+#define OXC_SCENE_HAS_SKY (1u << 10)
+#define OXC_SCENE_TRANSPARENT_BACKGROUND (1u << 11)
+typedef struct oxc_pbr_context {
+  uint32_t struct_size; /* sizeof(oxc_pbr_context) */
+  uint32_t width, height;
+  uint32_t scene_flags;           /* GPU::SceneFlags */
+  uint32_t light_count;
+  uint32_t sky_has_texture;       /* GPU::Sky::has_texture */
+  float inv_projection_view[16];  /* Camera::inv_projection_view, column-major */
+  float camera_position[3];
+  float sun_dir[3];               /* L: towards the sun, used as given */
+  float sun_intensity;            /* Li */
+  float base_ambient_color[3];    /* the engine passes 0.03 */
+  float sky_solid_color[4];       /* GPU::Sky::solid_color */
+  float sky_ambient_color[3];     /* GPU::Sky::ambient_color */
+  oxc_image depth_attachment;     /* in: R32F, levels = 1, reversed Z */
+  oxc_buffer albedo_attachment;   /* in: R8G8B8A8 sRGB, u32[height][width], R in the low byte */
+  oxc_buffer normal_attachment;   /* in: u16x4[height][width], .rg mapped, .ba smooth */
+  oxc_buffer emissive_attachment; /* in: B10G11R11 UfloatPack32, u32[height][width] */
+  oxc_buffer metallic_roughness_occlusion_attachment; /* in: R8G8B8A8 Unorm, u32[height][width] */
+  oxc_buffer ambient_occlusion_attachment;            /* in: binary16 as u16[height][width] */
+  oxc_image resolved_shadows_attachment;              /* in: R32F, read with HasDirectionalLight */
+  oxc_image contact_shadows_attachment;               /* in: R32F, read with HasContactShadows */
+  oxc_buffer lights_buffer;       /* in: GPU::Light[light_count], 64 bytes each (scene.slang:272-283) */
+  oxc_buffer final_attachment;    /* out: u32[height][width] B10G11R11, or u16x4[height][width] with a transparent background */
+} oxc_pbr_context;
+
+oxc_status oxc_apply_pbr(oxc_ctx* ctx, const oxc_pbr_context* context, void* hip_stream);
+
 /* ---- multi-GPU exchange: one process per GPU, RCCL over xGMI ---------------------------
  * The meshlet-instance array shards by contiguous range and every rank culls its shard on its own; the only
  * exchanges of the path are (1) the per-rank counters {emitted meshlets, early, late, index count} to every rank

@@ -87,7 +87,8 @@ enum { OXC_TUNE_ASYNC_MTEST_BLOCKS_PER_CU = 0, OXC_TUNE_ASYNC_TRI_BLOCKS_PER_CU 
        OXC_TUNE_VSM_RESOLVE_STATS = 10 /* 1: oxc_resolve_shadowmap runs its counting instantiation (oxc_debug_vsm_resolve_stats); 0 (default): off */,
        OXC_TUNE_CONTACT_SHADOWS_STATS = 11 /* 1: oxc_contact_shadows runs its counting instantiation (oxc_debug_contact_shadows_stats); 0 (default): off */,
        OXC_TUNE_AMBIENT_OCCLUSION_STATS = 12 /* 1: oxc_generate_ambient_occlusion runs the counting instantiation of its main kernel (oxc_debug_ambient_occlusion_stats); 0 (default): off */,
-       OXC_TUNE_VISBUFFER_DECODE_STATS = 13 /* 1: oxc_decode_visbuffer runs its counting instantiation (oxc_debug_visbuffer_decode_stats); 0 (default): off */ };
+       OXC_TUNE_VISBUFFER_DECODE_STATS = 13 /* 1: oxc_decode_visbuffer runs its counting instantiation (oxc_debug_visbuffer_decode_stats); 0 (default): off */,
+       OXC_TUNE_PBR_APPLY_STATS = 14 /* 1: oxc_apply_pbr runs its counting instantiation (oxc_debug_pbr_apply_stats); 0 (default): off */ };
 oxc_status oxc_debug_set_tuning(oxc_ctx* ctx, uint32_t knob, uint32_t value);
 
 /* Measurement aid: counters_dptr != NULL -- the HiZ calls (use_hiz + OXC_CULL_TEST_OCCLUSION) that follow on this context run counting
@@ -136,6 +137,13 @@ oxc_status oxc_debug_ambient_occlusion_stats(oxc_ctx* ctx, uint32_t* host_out15,
  * out4 = {decoded pixels (all four images written from a triangle), empty pixels (rule 1), pixels written as zeros because a vertex index
  * exceeds vertex_count - 1 (rule 2), decoded pixels whose material_index is beyond material_count (the all-zero Material)}. */
 oxc_status oxc_debug_visbuffer_decode_stats(oxc_ctx* ctx, uint32_t* host_out4, void* hip_stream);
+
+/* Measurement hook: what the last oxc_apply_pbr on this context did, counted by a counting instantiation of its kernel (same image,
+ * slower) after oxc_debug_set_tuning(OXC_TUNE_PBR_APPLY_STATS, 1); synchronises the stream.
+ * out9 = {pixels per outcome class: transparent empty (rule 1), sky (rule 5), fall-through empty (depth == 0.0 with neither flag), lit with
+ * NoL > 0, lit with NoL == 0 (rule 11);  light evaluations (one per light per pixel that reaches rule 9) per outcome: skipped by kind,
+ * attenuation or intensity out, NdotL out, shaded}. */
+oxc_status oxc_debug_pbr_apply_stats(oxc_ctx* ctx, uint32_t* host_out9, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -92,6 +92,7 @@ struct oxc_ctx {
   PassCounters contact_shadows_stats;    // OXC_TUNE_CONTACT_SHADOWS_STATS: u32[12]
   PassCounters ambient_occlusion_stats;  // OXC_TUNE_AMBIENT_OCCLUSION_STATS: u32[15] (16 allocated)
   PassCounters visbuffer_decode_stats;   // OXC_TUNE_VISBUFFER_DECODE_STATS: u32[4]
+  PassCounters pbr_apply_stats;          // OXC_TUNE_PBR_APPLY_STATS: u32[9]
   void* comm = nullptr;           // ncclComm_t (oxc_comm_init)
   uint32_t comm_rank = 0, comm_world = 0;
   // counter slots
@@ -632,7 +633,7 @@ void oxc_destroy(oxc_ctx* ctx) {
   if (ctx->raster_rows) (void)hipFree(ctx->raster_rows);
   if (ctx->vsm_scratch) (void)hipFree(ctx->vsm_scratch);
   if (ctx->vsm_draw_scratch) (void)hipFree(ctx->vsm_draw_scratch);
-  for (const auto& pc : {ctx->vsm_resolve_stats, ctx->contact_shadows_stats, ctx->ambient_occlusion_stats, ctx->visbuffer_decode_stats})
+  for (const auto& pc : {ctx->vsm_resolve_stats, ctx->contact_shadows_stats, ctx->ambient_occlusion_stats, ctx->visbuffer_decode_stats, ctx->pbr_apply_stats})
     if (pc.dev) (void)hipFree(pc.dev);
   if (ctx->comm) (void)oxc_comm_destroy(ctx);
   if (ctx->slots) (void)hipFree(ctx->slots);
@@ -1962,6 +1963,69 @@ oxc_status oxc_decode_visbuffer(oxc_ctx* ctx, const oxc_prepared_frame* f, const
   return OXC_OK;
 }
 
+oxc_status oxc_apply_pbr(oxc_ctx* ctx, const oxc_pbr_context* c, void* hip_stream) {
+  if (!ctx) return OXC_INVALID_ARG;
+  if (!c || c->struct_size != sizeof(oxc_pbr_context)) return fail(ctx, OXC_INVALID_ARG, "apply_pbr: bad context / struct_size");
+  const char* const entry = "apply_pbr";
+  const oxc_image& dimg = c->depth_attachment;
+  const uint32_t flags = c->scene_flags;
+  if (flags & OXC_SCENE_HAS_ATMOSPHERE) return bad_arg(ctx, entry, "HasAtmosphere: the atmosphere branch (pbr_apply.slang) is not built");
+  if (c->width == 0u || c->height == 0u) return bad_arg(ctx, entry, "the extent must not be zero");
+  if (dimg.width != c->width || dimg.height != c->height) return bad_arg(ctx, entry, "depth_attachment extent differs from (width, height)");
+  uint64_t pixels;
+  OXC_TRY(pixel_images(ctx, entry, dimg, (flags & OXC_SCENE_HAS_DIRECTIONAL_LIGHT) ? &c->resolved_shadows_attachment : nullptr, "resolved_shadows_attachment", pixels));
+  OXC_TRY(pixel_images(ctx, entry, dimg, (flags & OXC_SCENE_HAS_CONTACT_SHADOWS) ? &c->contact_shadows_attachment : nullptr, "contact_shadows_attachment", pixels));
+  if (bad_pixel_buffer(c->albedo_attachment, pixels, 4u) || bad_pixel_buffer(c->emissive_attachment, pixels, 4u) ||
+      bad_pixel_buffer(c->metallic_roughness_occlusion_attachment, pixels, 4u))
+    return bad_arg(ctx, entry, "albedo_attachment, emissive_attachment and metallic_roughness_occlusion_attachment must be one aligned u32 per pixel");
+  if (bad_pixel_buffer(c->normal_attachment, pixels, 8u)) return bad_arg(ctx, entry, "normal_attachment must be 8-byte aligned u16x4 texels of the depth attachment's extent");
+  if (bad_pixel_buffer(c->ambient_occlusion_attachment, pixels, 2u)) return bad_arg(ctx, entry, "ambient_occlusion_attachment must be one aligned u16 per pixel");
+  const bool transparent = (flags & OXC_SCENE_TRANSPARENT_BACKGROUND) != 0u;
+  if (bad_pixel_buffer(c->final_attachment, pixels, transparent ? 8u : 4u))
+    return bad_arg(ctx, entry, "final_attachment must be one aligned u32 per pixel, or one 8-byte aligned u16x4 per pixel with TransparentBackground");
+  const oxc_buffer& lb = c->lights_buffer;
+  if (c->light_count && (!lb.dptr || lb.bytes < (uint64_t)c->light_count * 64u || (reinterpret_cast<uintptr_t>(lb.dptr) & 3u)))
+    return bad_arg(ctx, entry, "lights_buffer must hold light_count 4-byte aligned GPU::Light records of 64 bytes");
+  bool finite = std::isfinite(c->sun_intensity);
+  for (int k = 0; k < 16; k++) finite = finite && std::isfinite(c->inv_projection_view[k]);
+  for (int k = 0; k < 3; k++)
+    finite = finite && std::isfinite(c->camera_position[k]) && std::isfinite(c->sun_dir[k]) && std::isfinite(c->base_ambient_color[k]) && std::isfinite(c->sky_ambient_color[k]);
+  for (int k = 0; k < 4; k++) finite = finite && std::isfinite(c->sky_solid_color[k]);
+  if (!finite) return bad_arg(ctx, entry, "inv_projection_view, camera_position, sun_dir, sun_intensity and the three colours must be finite");
+  OXC_HIP(ctx, hipSetDevice(ctx->device));
+  OXC_ORDER(ctx, hip_stream);
+  const hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  PbrApplyArgs a;
+  std::memset(&a, 0, sizeof a);
+  OXC_TRY(arm_counters(ctx, entry, "hipMalloc(pbr apply counters)", ctx->pbr_apply_stats, 36, s, &a.stats));
+  a.depth = static_cast<const float*>(dimg.dptr);
+  a.albedo = static_cast<const uint32_t*>(c->albedo_attachment.dptr);
+  a.normal = static_cast<const uint2*>(c->normal_attachment.dptr);
+  a.emissive = static_cast<const uint32_t*>(c->emissive_attachment.dptr);
+  a.mro = static_cast<const uint32_t*>(c->metallic_roughness_occlusion_attachment.dptr);
+  a.ao = static_cast<const uint16_t*>(c->ambient_occlusion_attachment.dptr);
+  a.resolved = (flags & OXC_SCENE_HAS_DIRECTIONAL_LIGHT) ? static_cast<const float*>(c->resolved_shadows_attachment.dptr) : nullptr;
+  a.contact = (flags & OXC_SCENE_HAS_CONTACT_SHADOWS) ? static_cast<const float*>(c->contact_shadows_attachment.dptr) : nullptr;
+  a.lights = lb.dptr;
+  a.out = c->final_attachment.dptr;
+  a.w = c->width;
+  a.h = c->height;
+  a.fw = (float)c->width;
+  a.fh = (float)c->height;
+  a.flags = flags;
+  a.light_count = c->light_count;
+  for (int k = 0; k < 16; k++) a.inv_pv[k] = c->inv_projection_view[k];
+  for (int k = 0; k < 3; k++) {
+    a.camera[k] = c->camera_position[k], a.sun[k] = c->sun_dir[k];
+    a.env[k] = (flags & OXC_SCENE_HAS_SKY) ? c->sky_ambient_color[k] : c->base_ambient_color[k];
+    a.sky_color[k] = c->sky_has_texture ? 1.0f : c->sky_solid_color[k];
+  }
+  a.sun_intensity = c->sun_intensity;
+  launch_pbr_apply(a, s);
+  OXC_HIP(ctx, hipGetLastError());
+  return OXC_OK;
+}
+
 oxc_status oxc_generate_ambient_occlusion(oxc_ctx* ctx, const oxc_ambient_occlusion_context* c, void* hip_stream) {
   if (!ctx) return OXC_INVALID_ARG;
   if (!c || c->struct_size != sizeof(oxc_ambient_occlusion_context)) return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: bad context / struct_size");
@@ -2357,6 +2421,7 @@ oxc_status oxc_debug_set_tuning(oxc_ctx* ctx, uint32_t knob, uint32_t value) {
     case OXC_TUNE_VSM_RESOLVE_STATS: ctx->vsm_resolve_stats.on = value != 0u; return OXC_OK;
     case OXC_TUNE_CONTACT_SHADOWS_STATS: ctx->contact_shadows_stats.on = value != 0u; return OXC_OK;
     case OXC_TUNE_VISBUFFER_DECODE_STATS: ctx->visbuffer_decode_stats.on = value != 0u; return OXC_OK;
+    case OXC_TUNE_PBR_APPLY_STATS: ctx->pbr_apply_stats.on = value != 0u; return OXC_OK;
     case OXC_TUNE_AMBIENT_OCCLUSION_STATS: ctx->ambient_occlusion_stats.on = value != 0u; return OXC_OK;
     case OXC_TUNE_VSM_DRAW_CAPACITY:
       if (ctx->vsm_draw_scratch) return fail(ctx, OXC_INVALID_ARG, "set_tuning: the shadow draw's scratch is allocated by the first oxc_draw_physical_pages; set its capacity before");
@@ -2436,6 +2501,10 @@ oxc_status oxc_debug_vsm_resolve_stats(oxc_ctx* ctx, uint32_t* host_out8, void* 
 
 oxc_status oxc_debug_visbuffer_decode_stats(oxc_ctx* ctx, uint32_t* host_out4, void* hip_stream) {
   return read_counters(ctx, "debug_visbuffer_decode_stats", "oxc_decode_visbuffer", &oxc_ctx::visbuffer_decode_stats, host_out4, 16, hip_stream);
+}
+
+oxc_status oxc_debug_pbr_apply_stats(oxc_ctx* ctx, uint32_t* host_out9, void* hip_stream) {
+  return read_counters(ctx, "debug_pbr_apply_stats", "oxc_apply_pbr", &oxc_ctx::pbr_apply_stats, host_out9, 36, hip_stream);
 }
 
 oxc_status oxc_debug_contact_shadows_stats(oxc_ctx* ctx, uint32_t* host_out12, void* hip_stream) {

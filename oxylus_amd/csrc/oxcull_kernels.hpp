@@ -622,6 +622,29 @@ struct VisbufferDecodeArgs {
   float pv[16];
 };
 void launch_visbuffer_decode(const VisbufferDecodeArgs& a, hipStream_t s);
+// oxcull_pbr_apply.hip: the lit HDR image from the G-buffer and the shadow terms (oxc_apply_pbr)
+struct PbrApplyArgs {
+  const float* depth;       // [h][w]
+  const uint32_t* albedo;   // [h][w] R8G8B8A8 sRGB
+  const uint2* normal;      // [h][w] u16x4 as two words: {r | g << 16, b | a << 16}
+  const uint32_t* emissive; // [h][w] B10G11R11 UfloatPack32
+  const uint32_t* mro;      // [h][w] R8G8B8A8 Unorm
+  const uint16_t* ao;       // [h][w] binary16
+  const float* resolved;    // [h][w], read with HasDirectionalLight
+  const float* contact;     // [h][w], read with HasContactShadows
+  const void* lights;       // GPU::Light[light_count], 64 bytes each
+  void* out;                // [h][w] u32 (B10G11R11), or uint2 (R16G16B16A16 Sfloat) with TransparentBackground
+  uint32_t* stats;          // nullptr, or u32[9] the counting instantiation adds to (oxc_debug_pbr_apply_stats)
+  uint32_t w, h;
+  float fw, fh;             // float(w), float(h)
+  uint32_t flags;           // GPU::SceneFlags
+  uint32_t light_count;
+  float inv_pv[16];
+  float camera[3], sun[3], sun_intensity;
+  // selected once on the host (no arithmetic): HasSky ? sky_ambient_color : base_ambient_color;  sky_has_texture ? (1, 1, 1) : sky_solid_color.rgb
+  float env[3], sky_color[3];
+};
+void launch_pbr_apply(const PbrApplyArgs& a, hipStream_t s);
 // oxcull_bounds.hip: meshlet bounds producer
 void launch_build_meshlet_bounds(const float* pos, uint32_t vertex_count, const void* meshlets, uint32_t meshlet_count, const uint32_t* vidx,
                                  const uint8_t* micro, void* out_bounds, float* out_mesh6, void* out_qpos, float* meshlet_minmax, float* normals,

@@ -55,9 +55,8 @@ OXC_DEV double log2_f64(float x) {
   return x == __builtin_inff() ? __builtin_inf() : r;
 }
 
-// pow(v, p), v >= 0 (or NaN-free by the caller's max), p > 0: exp2(p * log2(v)) in binary64, rounded to binary32 once
-OXC_DEV float pow_rule(float v, float p) {
-  const double y = (double)p * log2_f64(v);
+// exp2(y) of a binary64 y, rounded to binary32 once: the second half of the pow rule
+OXC_DEV float exp2_f64_round(double y) {
   const double k = __builtin_floor(y + 0.5);
   const double r = y - k;  // exact, in [-0.5, 0.5]
   const double t = r * 0x1.62e42fefa39efp-1;
@@ -83,8 +82,31 @@ OXC_DEV float pow_rule(float v, float p) {
   return (float)(q * scale);
 }
 
+// pow(v, p), v >= 0 (or NaN-free by the caller's max), p > 0: exp2(p * log2(v)) in binary64, rounded to binary32 once
+OXC_DEV float pow_rule(float v, float p) { return exp2_f64_round((double)p * log2_f64(v)); }
+
+// exp2(t) of a binary32 t (the exp2 rule of oxc_apply_pbr)
+OXC_DEV float exp2_rule(float t) { return exp2_f64_round((double)t); }
+
 // one component of packUnorm4x8: u32(floor(saturate(e) * 255.0 + 0.5)); a NaN gives 0
 OXC_DEV uint32_t pack_unorm(float e) { return cvt_u32_sat(floorf(saturate_f(e) * 255.0f + 0.5f)); }
+
+// binary32 -> unsigned small float with a 5-bit exponent and MBITS of mantissa (UF11: 6, UF10: 5), truncating (oxc_decode_visbuffer
+// step 8; oxc_apply_pbr packs its B10G11R11 output by it)
+template <int MBITS>
+OXC_DEV uint32_t pack_ufloat(float v) {
+  constexpr uint32_t kMantissa = (1u << MBITS) - 1u;
+  const uint32_t bits = asu(v);
+  if (!(v == v)) return (31u << MBITS) | kMantissa;
+  if (bits >> 31) return 0u;  // negative values, -0, -Inf
+  if (bits == 0x7F800000u) return 31u << MBITS;
+  const int e = (int)(bits >> 23) - 127 + 15;
+  const uint32_t m = bits & 0x7FFFFFu;
+  if (e >= 31) return (30u << MBITS) | kMantissa;
+  if (e >= 1) return ((uint32_t)e << MBITS) | (m >> (23 - MBITS));
+  const int sh = (23 - MBITS) + (1 - e);  // a denormal of the small format
+  return sh > 24 ? 0u : (0x800000u | m) >> sh;
+}
 
 // The pixel of this thread: an 8 x 8 pixel tile per wave, a 16 x 16 tile per block of 256 threads.
 OXC_DEV uint2 tile_pixel() {

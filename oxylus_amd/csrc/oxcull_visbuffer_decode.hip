@@ -40,22 +40,6 @@ OXC_DEV uint32_t srgb_unorm(float x) {
   return pack_unorm(e);
 }
 
-// binary32 -> unsigned small float with a 5-bit exponent and MBITS of mantissa (UF11: 6, UF10: 5), truncating
-template <int MBITS>
-OXC_DEV uint32_t pack_ufloat(float v) {
-  constexpr uint32_t kMantissa = (1u << MBITS) - 1u;
-  const uint32_t bits = asu(v);
-  if (!(v == v)) return (31u << MBITS) | kMantissa;
-  if (bits >> 31) return 0u;  // negative values, -0, -Inf
-  if (bits == 0x7F800000u) return 31u << MBITS;
-  const int e = (int)(bits >> 23) - 127 + 15;
-  const uint32_t m = bits & 0x7FFFFFu;
-  if (e >= 31) return (30u << MBITS) | kMantissa;
-  if (e >= 1) return ((uint32_t)e << MBITS) | (m >> (23 - MBITS));
-  const int sh = (23 - MBITS) + (1 - e);  // a denormal of the small format
-  return sh > 24 ? 0u : (0x800000u | m) >> sh;
-}
-
 template <bool STATS>
 OXC_DEV void count(const VisbufferDecodeArgs& a, int k) {
   if (STATS) atomicAdd(&a.stats[k], 1u);

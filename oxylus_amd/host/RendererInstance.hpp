@@ -54,6 +54,7 @@ struct PreparedFrame {
   Buffer meshlet_instance_visibility_mask_buffer = {};
   Buffer reordered_indices_buffer = {};
   Buffer materials_buffer = {};  // GPU::Material[], read by decode_visbuffer
+  Buffer lights_buffer = {};     // GPU::Light[], 64 bytes each, read by apply_pbr
 };
 
 struct CullGeometryContext {
@@ -125,6 +126,39 @@ using ContactShadowsContext = oxc_contact_shadows_context;
 // the normal image, the Hilbert index table, the three caller-owned intermediates and the R16F ambient_occlusion_attachment.
 using AmbientOcclusionContext = oxc_ambient_occlusion_context;
 
+// What apply_pbr reads (RendererInstance.hpp:310-325 of the reference, without bindless_set and the four sky LUTs of the atmosphere branch):
+// the depth, the four G-buffer images of decode_visbuffer as linear buffers, the ambient occlusion and the two R32F shadow terms.
+struct PBRContext {
+  ImageAttachment depth_attachment = {};
+  Buffer albedo_attachment = {};
+  Buffer normal_attachment = {};
+  Buffer emissive_attachment = {};
+  Buffer metallic_roughness_occlusion_attachment = {};
+  Buffer ambient_occlusion_attachment = {};
+  ImageAttachment contact_shadows_attachment = {};
+  ImageAttachment resolved_shadows_attachment = {};
+};
+
+namespace GPU {
+// scene.slang:236-240
+struct Sky {
+  float solid_color[4] = {0.0f, 0.0f, 0.0f, 1.0f};
+  float ambient_color[3] = {0.0f, 0.0f, 0.0f};
+  uint32_t has_texture = 0;
+};
+// scene.slang:264-268
+struct DirectionalLight {
+  float color[3] = {1.0f, 1.0f, 1.0f};
+  float intensity = 0.0f;
+  float direction[3] = {0.0f, 1.0f, 0.0f};
+};
+// the GPU::Camera fields apply_pbr reads
+struct Camera {
+  float inv_projection_view[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  float position[3] = {0.0f, 0.0f, 0.0f};
+};
+}  // namespace GPU
+
 class RendererInstance {
 public:
   explicit RendererInstance(int device = 0, void* hip_stream = nullptr) : stream_(hip_stream) {
@@ -135,6 +169,12 @@ public:
   RendererInstance& operator=(const RendererInstance&) = delete;
 
   PreparedFrame prepared_frame = {};
+  // what apply_pbr takes from the instance in the reference: gpu_scene_flags (the specialisation constant), directional_light (sun_dir,
+  // sun_intensity), sky_data (the Sky record) and the camera buffer's contents
+  uint32_t gpu_scene_flags = 0;  // GPU::SceneFlags, OXC_SCENE_*
+  GPU::DirectionalLight directional_light = {};
+  GPU::Sky sky_data = {};
+  GPU::Camera camera = {};
 
   void set_stream(void* hip_stream) { stream_ = hip_stream; }
 
@@ -301,6 +341,39 @@ public:
   auto generate_ambient_occlusion(AmbientOcclusionContext context) -> void {
     context.struct_size = sizeof context;
     check(oxc_generate_ambient_occlusion(ctx_, &context, stream_));
+  }
+  // RendererInstance::apply_pbr (Passes/PBR.cpp:313-534), the no-atmosphere branch (pipeline pbr_apply_no_atmos): the lit HDR colour of every
+  // pixel into dst_attachment -- B10G11R11 UfloatPack32 (u32 per pixel), or R16G16B16A16 Sfloat (u16x4 per pixel) with TransparentBackground in
+  // gpu_scene_flags (RendererInstance.cpp:545-546).  HasAtmosphere in gpu_scene_flags is refused.  Rules: include/oxcull.h, oxc_apply_pbr.
+  auto apply_pbr(PBRContext& context, Buffer dst_attachment) -> Buffer {
+    oxc_pbr_context c = {};
+    c.struct_size = sizeof c;
+    c.width = context.depth_attachment.width;
+    c.height = context.depth_attachment.height;
+    c.scene_flags = gpu_scene_flags;
+    c.light_count = static_cast<uint32_t>(prepared_frame.lights_buffer.bytes / 64u);
+    c.sky_has_texture = sky_data.has_texture;
+    for (int i = 0; i < 16; i++) c.inv_projection_view[i] = camera.inv_projection_view[i];
+    for (int i = 0; i < 3; i++) {
+      c.camera_position[i] = camera.position[i];
+      c.sun_dir[i] = directional_light.direction[i];
+      c.base_ambient_color[i] = 0.03f;  // glm::vec3(0.03f), PBR.cpp:480
+      c.sky_ambient_color[i] = sky_data.ambient_color[i];
+    }
+    for (int i = 0; i < 4; i++) c.sky_solid_color[i] = sky_data.solid_color[i];
+    c.sun_intensity = directional_light.intensity;
+    c.depth_attachment = context.depth_attachment;
+    c.albedo_attachment = context.albedo_attachment;
+    c.normal_attachment = context.normal_attachment;
+    c.emissive_attachment = context.emissive_attachment;
+    c.metallic_roughness_occlusion_attachment = context.metallic_roughness_occlusion_attachment;
+    c.ambient_occlusion_attachment = context.ambient_occlusion_attachment;
+    c.resolved_shadows_attachment = context.resolved_shadows_attachment;
+    c.contact_shadows_attachment = context.contact_shadows_attachment;
+    c.lights_buffer = prepared_frame.lights_buffer;
+    c.final_attachment = dst_attachment;
+    check(oxc_apply_pbr(ctx_, &c, stream_));
+    return dst_attachment;
   }
   auto build_meshlet_bounds(oxc_meshlet_bounds_desc desc) -> void {
     desc.struct_size = sizeof desc;

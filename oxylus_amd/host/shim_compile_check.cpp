@@ -55,5 +55,17 @@ int main(int argc, char**) {
   } catch (const std::exception& e) {
     std::printf("expected (no attachments bound): %s\n", e.what());
   }
+  try {  // RendererInstance.cpp: apply_pbr, the consumer of every image above
+    auto pbr_context = PBRContext{.depth_attachment = main_geometry_context.depth_attachment,
+                                  .albedo_attachment = main_geometry_context.albedo_attachment,
+                                  .normal_attachment = main_geometry_context.normal_attachment,
+                                  .emissive_attachment = main_geometry_context.emissive_attachment,
+                                  .metallic_roughness_occlusion_attachment = main_geometry_context.metallic_roughness_occlusion_attachment};
+    self.gpu_scene_flags = OXC_SCENE_HAS_DIRECTIONAL_LIGHT | OXC_SCENE_HAS_SKY;
+    auto final_attachment = self.apply_pbr(pbr_context, Buffer{});
+    (void)final_attachment;
+  } catch (const std::exception& e) {
+    std::printf("expected (no attachments bound): %s\n", e.what());
+  }
   return 0;
 }

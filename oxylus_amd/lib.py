@@ -30,6 +30,11 @@ STAGE_ALL = 7
 TUNE_ASYNC_MTEST_BLOCKS_PER_CU, TUNE_ASYNC_TRI_BLOCKS_PER_CU, TUNE_RASTER_BIG_CAPACITY, TUNE_TRI_BLOCKS_PER_CU, TUNE_MV_EXPAND_ASYNC, TUNE_TRI_LOADS = 0, 1, 2, 3, 5, 7  # oxc_debug_set_tuning knobs
 TUNE_VSM_DRAW_STATS, TUNE_VSM_DRAW_CAPACITY, TUNE_VSM_RESOLVE_STATS, TUNE_CONTACT_SHADOWS_STATS, TUNE_AMBIENT_OCCLUSION_STATS = 8, 9, 10, 11, 12
 TUNE_VISBUFFER_DECODE_STATS = 13
+TUNE_PBR_APPLY_STATS = 14
+
+# GPU::SceneFlags bits oxc_apply_pbr reads (scene.slang:242-256)
+SCENE_HAS_DIRECTIONAL_LIGHT, SCENE_HAS_ATMOSPHERE, SCENE_HAS_CONTACT_SHADOWS, SCENE_HAS_SKY, SCENE_TRANSPARENT_BACKGROUND = 1 << 0, 1 << 1, 1 << 9, 1 << 10, 1 << 11
+LIGHT_KIND_DIRECTIONAL, LIGHT_KIND_POINT, LIGHT_KIND_SPOT = 0, 1, 2  # GPU::LightKind
 
 
 class Buffer(C.Structure):
@@ -375,6 +380,35 @@ class DecodeContext(C.Structure):
     ]
 
 
+class PbrContext(C.Structure):
+    """oxc_pbr_context (include/oxcull.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("scene_flags", C.c_uint32),
+        ("light_count", C.c_uint32),
+        ("sky_has_texture", C.c_uint32),
+        ("inv_projection_view", C.c_float * 16),
+        ("camera_position", C.c_float * 3),
+        ("sun_dir", C.c_float * 3),
+        ("sun_intensity", C.c_float),
+        ("base_ambient_color", C.c_float * 3),
+        ("sky_solid_color", C.c_float * 4),
+        ("sky_ambient_color", C.c_float * 3),
+        ("depth_attachment", Image),
+        ("albedo_attachment", Buffer),
+        ("normal_attachment", Buffer),
+        ("emissive_attachment", Buffer),
+        ("metallic_roughness_occlusion_attachment", Buffer),
+        ("ambient_occlusion_attachment", Buffer),
+        ("resolved_shadows_attachment", Image),
+        ("contact_shadows_attachment", Image),
+        ("lights_buffer", Buffer),
+        ("final_attachment", Buffer),
+    ]
+
+
 # every symbol include/oxcull.h declares
 EXPORTS = [
     "oxc_abi_version",
@@ -408,6 +442,8 @@ EXPORTS = [
     "oxc_draw_visbuffer",
     "oxc_decode_visbuffer",
     "oxc_debug_visbuffer_decode_stats",
+    "oxc_apply_pbr",
+    "oxc_debug_pbr_apply_stats",
     "oxc_draw_physical_pages",
     "oxc_debug_vsm_draw_stats",
     "oxc_resolve_shadowmap",
@@ -511,6 +547,8 @@ def load(path: str = None) -> C.CDLL:
     lib.oxc_draw_visbuffer.argtypes = [vp, C.POINTER(PreparedFrame), C.POINTER(DrawContext), vp]
     lib.oxc_decode_visbuffer.argtypes = [vp, C.POINTER(PreparedFrame), C.POINTER(DecodeContext), vp]
     lib.oxc_debug_visbuffer_decode_stats.argtypes = [vp, vp, vp]
+    lib.oxc_apply_pbr.argtypes = [vp, C.POINTER(PbrContext), vp]
+    lib.oxc_debug_pbr_apply_stats.argtypes = [vp, vp, vp]
     lib.oxc_draw_physical_pages.argtypes = [vp, C.POINTER(PreparedFrame), C.POINTER(VsmDrawContext), vp]
     lib.oxc_debug_vsm_draw_stats.argtypes = [vp, vp, vp]
     lib.oxc_resolve_shadowmap.argtypes = [vp, C.POINTER(ShadowResolveContext), vp]

@@ -474,6 +474,79 @@ class AmbientOcclusionContext:
 
 
 @dataclass
+class PBRContext:
+    """oxc_pbr_context: the no-atmosphere branch of RendererInstance::apply_pbr (Passes/PBR.cpp:313-534, pbr_apply_no_atmos).  `create` takes
+    the depth image, the four G-buffer images of decode_visbuffer, the ambient occlusion and the two shadow terms as their producers wrote
+    them, the camera, the sun, the lights (synth.pack_lights) and the Sky record, and allocates the output: int32 [H, W] (B10G11R11), or
+    int16 [H, W, 4] (R16G16B16A16 Sfloat) with L.SCENE_TRANSPARENT_BACKGROUND.  An image whose flag is clear may be None."""
+    depth_attachment: ImageAttachment             # R32F, levels = 1
+    albedo_attachment: torch.Tensor               # int32 [H, W]: R8G8B8A8 sRGB
+    normal_attachment: torch.Tensor               # int16 [H, W, 4]: .rg mapped, .ba smooth
+    emissive_attachment: torch.Tensor             # int32 [H, W]: B10G11R11 UfloatPack32
+    metallic_roughness_occlusion_attachment: torch.Tensor  # int32 [H, W]: R8G8B8A8 Unorm
+    ambient_occlusion_attachment: torch.Tensor    # int16 [H, W]: binary16 bits
+    resolved_shadows_attachment: Optional[ImageAttachment]  # R32F, read with HasDirectionalLight
+    contact_shadows_attachment: Optional[ImageAttachment]   # R32F, read with HasContactShadows
+    final_attachment: torch.Tensor                # out
+    scene_flags: int
+    inv_projection_view: list                     # column-major float[16]
+    camera_position: tuple
+    sun_dir: tuple                                # L, used as given
+    sun_intensity: float
+    lights_buffer: Optional[torch.Tensor] = None  # uint8 [light_count * 64] GPU::Light records
+    light_count: int = 0
+    base_ambient_color: tuple = (0.03, 0.03, 0.03)
+    sky_solid_color: tuple = (0.0, 0.0, 0.0, 1.0)
+    sky_ambient_color: tuple = (0.0, 0.0, 0.0)
+    sky_has_texture: bool = False
+
+    @staticmethod
+    def create(depth, albedo, normal, emissive, metallic_roughness_occlusion, ambient_occlusion, resolved_shadows, contact_shadows, scene_flags: int,
+               inv_projection_view, camera_position, sun_dir, sun_intensity: float, lights: Optional[torch.Tensor] = None,
+               base_ambient_color=(0.03, 0.03, 0.03), sky_solid_color=(0.0, 0.0, 0.0, 1.0), sky_ambient_color=(0.0, 0.0, 0.0),
+               sky_has_texture: bool = False) -> "PBRContext":
+        d = depth if isinstance(depth, ImageAttachment) else ImageAttachment.depth(depth)
+        img = lambda t: t if t is None or isinstance(t, ImageAttachment) else ImageAttachment.depth(t)  # noqa: E731
+        dev = d.data.device
+        if int(scene_flags) & L.SCENE_TRANSPARENT_BACKGROUND:
+            out = torch.zeros((d.height, d.width, 4), dtype=torch.int16, device=dev)
+        else:
+            out = torch.zeros((d.height, d.width), dtype=torch.int32, device=dev)
+        count = 0 if lights is None else lights.numel() * lights.element_size() // 64
+        return PBRContext(d, albedo, normal, emissive, metallic_roughness_occlusion, ambient_occlusion, img(resolved_shadows), img(contact_shadows), out,
+                          int(scene_flags), [float(x) for x in inv_projection_view], tuple(float(x) for x in camera_position),
+                          tuple(float(x) for x in sun_dir), float(sun_intensity), lights, count, tuple(float(x) for x in base_ambient_color),
+                          tuple(float(x) for x in sky_solid_color), tuple(float(x) for x in sky_ambient_color), bool(sky_has_texture))
+
+    def c(self) -> L.PbrContext:
+        c = L.PbrContext()
+        c.struct_size = C.sizeof(L.PbrContext)
+        c.width, c.height = self.depth_attachment.width, self.depth_attachment.height
+        c.scene_flags, c.light_count, c.sky_has_texture = int(self.scene_flags), int(self.light_count), int(bool(self.sky_has_texture))
+        for i in range(16):
+            c.inv_projection_view[i] = float(self.inv_projection_view[i])
+        for i in range(3):
+            c.camera_position[i], c.sun_dir[i] = float(self.camera_position[i]), float(self.sun_dir[i])
+            c.base_ambient_color[i], c.sky_ambient_color[i] = float(self.base_ambient_color[i]), float(self.sky_ambient_color[i])
+        for i in range(4):
+            c.sky_solid_color[i] = float(self.sky_solid_color[i])
+        c.sun_intensity = float(self.sun_intensity)
+        c.depth_attachment = self.depth_attachment.c()
+        c.albedo_attachment = _buf(self.albedo_attachment)
+        c.normal_attachment = _buf(self.normal_attachment)
+        c.emissive_attachment = _buf(self.emissive_attachment)
+        c.metallic_roughness_occlusion_attachment = _buf(self.metallic_roughness_occlusion_attachment)
+        c.ambient_occlusion_attachment = _buf(self.ambient_occlusion_attachment)
+        if self.resolved_shadows_attachment is not None:
+            c.resolved_shadows_attachment = self.resolved_shadows_attachment.c()
+        if self.contact_shadows_attachment is not None:
+            c.contact_shadows_attachment = self.contact_shadows_attachment.c()
+        c.lights_buffer = _buf(self.lights_buffer)
+        c.final_attachment = _buf(self.final_attachment)
+        return c
+
+
+@dataclass
 class VisbufferDecodeContext:
     """oxc_decode_context: RendererInstance::decode_visbuffer (Passes/DrawGeometry.cpp:192-274), the geometry and material-factor half of
     visbuffer_decode.slang.  `create` takes the visbuffer and the depth as oxc_draw_visbuffer resolved them, the matrix they were drawn with and
@@ -748,6 +821,19 @@ class RendererInstance:
         c = context.c()
         self._keep = context
         self._check(self._lib.oxc_resolve_shadowmap(self._ctx, C.byref(c), self._stream(stream)))
+
+    def apply_pbr(self, context: PBRContext, stream=None):
+        """Passes/PBR.cpp:313-534, the no-atmosphere branch (pbr_apply_no_atmos): per pixel the G-buffer, the ambient occlusion, the two shadow
+        terms, the sun and the point / spot lights become the lit HDR colour in `context.final_attachment` (include/oxcull.h, oxc_apply_pbr)."""
+        c = context.c()
+        self._keep = context
+        self._check(self._lib.oxc_apply_pbr(self._ctx, C.byref(c), self._stream(stream)))
+
+    def debug_pbr_apply_stats(self, stream=None) -> dict:
+        """What the last apply_pbr did, after debug_set_tuning(L.TUNE_PBR_APPLY_STATS, 1) (measurement hook; synchronises)."""
+        return self._read_stats(self._lib.oxc_debug_pbr_apply_stats, stream,
+                                ("transparent_empty", "sky", "fallthrough_empty", "lit_nol_positive", "lit_nol_zero", "light_kind_skipped",
+                                 "light_attenuation_out", "light_ndotl_out", "light_shaded"))
 
     def _read_stats(self, fn, stream, names) -> dict:
         """One of the oxc_debug_*_stats read-backs: len(names) u32 counters under their names."""

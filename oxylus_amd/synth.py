@@ -721,6 +721,26 @@ def pack_materials(albedo, emissive=None, roughness=None, metallic=None, alpha_c
 
 
 # ---------------------------------------------------------------------------------------------
+def pack_lights(lights) -> torch.Tensor:
+    """-> uint8 [n * 64]: GPU::Light records (scene.slang:272-283) for oxc_apply_pbr.  `lights`: dicts with the struct's field names -- position
+    (3), intensity, color (3), range, direction (3), inner_cone_angle, outer_cone_angle, kind (0 Directional, 1 Point, 2 Spot) -- missing
+    fields take the struct's defaults.  A float field given as a numpy.uint32 is taken as the binary32 bit pattern itself (NaN payloads, -0)."""
+    import numpy as np
+
+    defaults = dict(position=(0.0, 0.0, 0.0), intensity=1.0, color=(1.0, 1.0, 1.0), range=0.0, direction=(0.0, 0.0, 0.0), inner_cone_angle=0.0,
+                    outer_cone_angle=0.0, kind=1)
+    words = dict(position=0, intensity=3, color=4, range=7, direction=8, inner_cone_angle=11, outer_cone_angle=12)
+    rec = np.zeros((len(lights), 16), dtype=np.uint32)
+    for i, light in enumerate(lights):
+        assert set(light) <= set(defaults), sorted(set(light) - set(defaults))
+        f = {**defaults, **light}
+        for name, w in words.items():
+            for k, v in enumerate(f[name] if isinstance(f[name], (tuple, list)) else (f[name],)):
+                rec[i, w + k] = v if isinstance(v, np.uint32) else np.array(v, dtype=np.float32).view(np.uint32)
+        rec[i, 13] = np.uint32(int(f["kind"]) & 0xFFFFFFFF)
+    return torch.from_numpy(rec.view(np.uint8).reshape(-1).copy())
+
+
 # Normal image for the shadow resolve.  The reference's producer (visbuffer_decode) needs materials and textures; this stands in for it:
 # geometric normals from the depth image, stored as it stores them.
 # ---------------------------------------------------------------------------------------------

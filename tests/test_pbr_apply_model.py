@@ -1,0 +1,295 @@
+"""The checker of oxc_apply_pbr (tests/pbr_apply_model.py) against answers worked out on paper and against the properties its closed forms
+must have: the sRGB decode inverts the decode pass's encoder on all 256 bytes, the packed floats round-trip, exp2 and cos stay within one
+binary32 ulp of the correctly rounded value, and pow_rule did not move when exp2 was factored out of it.
+
+The paper cases use a 1 x 1 image under the identity matrix, so the pixel is at NDC (0, 0) and world = (0, 0, depth), a roughness byte of 255
+(alpha = alpha2 = 1: D_GGX's f is exactly 1 and both square roots of V_SmithGGXCorrelated are sqrt(1) = 1) and an albedo byte of 255 (1.0)."""
+import numpy as np
+import pytest
+
+import ambient_occlusion_model as AM
+import pbr_apply_model as PM
+import visbuffer_decode_model as VD
+from pbr_apply_model import HAS_CONTACT_SHADOWS, HAS_DIRECTIONAL_LIGHT, HAS_SKY, TRANSPARENT_BACKGROUND
+from vsm_resolve_model import vec3_to_oct
+
+F = np.float32
+I16 = np.eye(4, dtype=np.float32).reshape(-1)
+
+# ---- what the GPU tests share: a camera whose w is depth + 0.5, a sun, a Sky record, and random G-buffer images ---------------------------------
+INV_PV = [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 1.0, 0.0, 0.0, 0.0, 0.5]  # column-major: h = (x, y, d, d + 0.5)
+CAMERA = (0.1, -0.2, 3.0)
+SUN = (0.3, 0.5, 0.8)  # not unit length: the rule does not normalise it
+SUN_INTENSITY = 2.5
+SKY = dict(base_ambient_color=(0.03, 0.03, 0.03), sky_solid_color=(0.25, 0.5, 1.0, 1.0), sky_ambient_color=(0.2, 0.3, 0.4), sky_has_texture=False)
+
+
+def synthetic_inputs(W, H, seed, empty=0.15) -> dict:
+    """Random images in the producers' formats: depth in (0.05, 0.95) with a share of empty (0.0) pixels, any albedo and m/r/o bytes, mapped and
+    smooth normals of random directions (every octant, the fold included), mostly-zero emissive words of finite patterns, ambient occlusion and
+    the two shadow terms in [0, 1] with exact 0 and 1 among them."""
+    rng = np.random.default_rng(seed)
+    depth = rng.uniform(0.05, 0.95, (H, W)).astype(np.float32)
+    depth[rng.random((H, W)) < empty] = 0.0
+
+    def octs():
+        v = rng.normal(size=(H, W, 3)).astype(np.float32)
+        e = vec3_to_oct(tuple(v[..., c] / np.linalg.norm(v, axis=-1).astype(np.float32) for c in range(3)))
+        return AM.to_half_bits(e[0]), AM.to_half_bits(e[1])
+
+    (r, g), (b, a) = octs(), octs()
+    normal = np.stack([r, g, b, a], axis=-1).astype(np.uint16)
+    finite = lambda bits, m: np.where((rng.integers(0, 1 << bits, (H, W)) >> m) == 31, 0, rng.integers(0, 1 << bits, (H, W)))  # noqa: E731
+    emissive = (finite(11, 6) | (finite(11, 6) << 11) | (finite(10, 5) << 22)).astype(np.uint32)
+    emissive[rng.random((H, W)) < 0.6] = 0
+    unit = lambda: np.clip(rng.uniform(-0.2, 1.2, (H, W)), 0.0, 1.0).astype(np.float32)  # noqa: E731
+    return dict(depth=depth, albedo=rng.integers(0, 1 << 32, (H, W), dtype=np.uint64).astype(np.uint32), normal=normal, emissive=emissive,
+                mro=rng.integers(0, 1 << 32, (H, W), dtype=np.uint64).astype(np.uint32), ao=AM.to_half_bits(unit()), resolved=unit(), contact=unit())
+
+
+# ---- the rules ------------------------------------------------------------------------------------------------------------------------------------
+def ulps(a, b):
+    """Distance in binary32 steps between two positive-or-zero finite arrays of one sign pattern."""
+    key = lambda x: np.where(x.view(np.int32) < 0, np.int64(-0x80000000) - x.view(np.int32), x.view(np.int32)).astype(np.int64)  # noqa: E731
+    return np.abs(key(np.asarray(a, np.float32)) - key(np.asarray(b, np.float32)))
+
+
+def test_srgb_decode_inverts_the_decode_pass_encoder():
+    byte = np.arange(256)
+    assert np.array_equal(VD.unorm8(VD.srgb_encode(PM.srgb_decode(byte))), byte)
+    lin = PM.srgb_decode(byte)
+    assert lin[0] == 0 and lin[255] == 1 and (np.diff(lin) > 0).all()
+
+
+def test_packed_floats_round_trip():
+    """Decode then pack is the identity on every finite pattern: 2048 - 64 UF11 and 1024 - 32 UF10 words (exponent 31 is Inf / NaN)."""
+    for mbits, n in ((6, 2048), (5, 1024)):
+        w = np.arange(n, dtype=np.uint32)
+        v = PM.unpack_ufloat(w, mbits)
+        fin = (w >> mbits) != 31
+        assert np.isfinite(v[fin]).all() and (np.diff(v[fin]) > 0).all()
+        assert np.array_equal(VD.pack_ufloat(v[fin], mbits), w[fin])
+        assert np.isposinf(v[31 << mbits]) and np.isnan(v[(31 << mbits) + 1:]).all()
+        assert VD.pack_ufloat(v[31 << mbits], mbits)[0] == 31 << mbits                   # +Inf keeps its pattern
+        assert (VD.pack_ufloat(v[(31 << mbits) + 1:], mbits) == n - 1).all()             # every NaN becomes the all-ones one
+    assert PM.unpack_ufloat(15 << 6, 6)[0] == 1.0 and PM.unpack_ufloat(1, 6)[0] == F(2.0 ** -20) and PM.unpack_ufloat(1, 5)[0] == F(2.0 ** -19)
+
+
+def test_exp2_rule_is_within_one_ulp():
+    """Both rules carry a binary64 error far below a binary32 half-ulp and round once, so they differ from the correctly rounded value only
+    at a rounding boundary: one ulp, derived and not measured."""
+    t = np.concatenate([np.linspace(-17.0, 0.0, 200001), -16.0 * (np.arange(256) / 255.0) - 1.0]).astype(np.float32)
+    assert ulps(PM.exp2_rule(t), np.exp2(t.astype(np.float64)).astype(np.float32)).max() <= 1
+    assert PM.exp2_rule(F(0.0))[0] == 1.0 and PM.exp2_rule(F(-17.0))[0] == F(2.0 ** -17) and PM.exp2_rule(F(-1.0))[0] == 0.5
+    assert PM.exp2_rule(F(-200.0))[0] == 0.0 and np.isposinf(PM.exp2_rule(F(200.0))[0]) and np.isnan(PM.exp2_rule(F(np.nan))[0])
+
+
+def test_cos_rule_is_within_one_ulp():
+    x = np.linspace(0.0, np.pi, 200001).astype(np.float32)
+    got, want = PM.cos_rule(x), np.cos(x.astype(np.float64)).astype(np.float32)
+    assert ulps(got, want).max() <= 1  # also next to pi / 2: the reduction keeps the small cosines of the binary32 neighbours of pi / 2 to full precision
+    assert PM.cos_rule(F(0.0))[0] == 1.0 and np.array_equal(PM.cos_rule(-x[:1000]), got[:1000])
+    wide = np.array([10.0, 1000.0, 1.0e6, 16777216.0], dtype=np.float32)
+    assert np.abs(PM.cos_rule(wide).astype(np.float64) - np.cos(wide.astype(np.float64))).max() < 1e-7
+    for bad in (np.nan, np.inf, -np.inf, 16777218.0, -3.0e7):
+        assert np.isnan(PM.cos_rule(F(bad))[0])
+
+
+def test_pow_rule_is_unchanged():
+    """exp2 factored out: the same bits as the ambient occlusion's pow_rule on the inputs its own model test uses, and on a grid."""
+    v = np.concatenate([np.linspace(0.0, 1.0, 4097), [0.0, 1.0, 0.5, 2.0 ** -126, 2.0 ** -127, 3.0, 1e30, np.inf]]).astype(np.float32)
+    for p in (2.2, 1.0, 0.5, 1.0 / 2.4, 2.4, 5.0, 3.7):
+        assert np.array_equal(PM.pow_rule(v, F(p)).view(np.uint32), AM.pow_rule(v, p).view(np.uint32)), p
+    assert np.isnan(PM.pow_rule(F(np.nan), F(2.0))[0]) == np.isnan(AM.pow_rule(F(np.nan), 2.0)[0])
+    assert PM.pow_rule(F(-1.0), F(0.3))[0] == 0.0 and PM.pow_rule(F(0.0), F(5.0))[0] == 0.0 and PM.pow_rule(F(1.0), F(5.0))[0] == 1.0
+
+
+# ---- answers worked out on paper ---------------------------------------------------------------------------------------------------------------
+def one_pixel(flags, depth=0.5, normal_rg=(0.0, 0.0), normal_ba=None, albedo=0xFFFFFF, mro=0x00FFFF00, emissive=0, ao=1.0, resolved=1.0, contact=1.0,
+              camera=(0.0, 0.0, 2.5), sun=(0.0, 0.0, 1.0), li=2.0, lights=None, ambient=(0.0, 0.0, 0.0), **sky):
+    """The 1 x 1 image: mro's default is metallic 0, roughness 255, occlusion 255."""
+    ba = normal_rg if normal_ba is None else normal_ba
+    n = np.array([[list(normal_rg) + list(ba)]], dtype=np.float16).view(np.uint16)
+    a = lambda v, t: np.array([[v]], dtype=t)  # noqa: E731
+    st = {}
+    out = PM.apply_pbr(a(depth, np.float32), a(albedo, np.uint32), n, a(emissive, np.uint32), a(mro, np.uint32), AM.to_half_bits(a(ao, np.float32)),
+                       a(resolved, np.float32), a(contact, np.float32), flags, I16, camera, sun, li, lights, base_ambient_color=ambient, stats=st, **sky)
+    return out, st
+
+
+def rgb_of(out):
+    return [float(c[0]) for c in PM.unpack_b10g11r11(out.reshape(-1))]
+
+
+def trunc_uf(v, mbits):
+    """What the B10G11R11 image keeps of a binary32 value in the small format's normal range: the mantissa cut to mbits."""
+    return float(PM.unpack_ufloat(VD.pack_ufloat(F(v), mbits), mbits)[0])
+
+
+def fit(x, y):
+    """GGX_directional_albedo in scalar binary32, term by term."""
+    c = PM.ALBEDO_FIT
+    x, y = F(x), F(y)
+    x2, y2 = F(x * x), F(y * y)
+    r = []
+    for k in range(4):
+        s = F(c[0, k] + F(c[1, k] * x))
+        for term in (F(c[2, k] * y), F(F(c[3, k] * x) * y), F(c[4, k] * x2), F(c[5, k] * y2), F(F(c[6, k] * x2) * y), F(F(c[7, k] * x) * y2), F(F(c[8, k] * x2) * y2)):
+            s = F(s + term)
+        r.append(s)
+    sat = lambda v: F(min(max(v, F(0.0)), F(1.0)))  # noqa: E731
+    return sat(F(r[0] / r[2])), sat(F(r[1] / r[3]))
+
+
+def rough_brdf(NoV, NoL, LoH, F0, metallic=0.0, albedo=1.0):
+    """BRDF at alpha2 == 1 on paper: f = (NoH * 1 - NoH) * NoH + 1 = 1, so D = 1 / (PI + 1e-7f) = 1 / PI (1e-7 is below half an ulp of PI);
+    GGXV = NoL * sqrt(NoV^2 * 0 + 1) = NoL, GGXL = NoV;  Vis = saturate(0.5 / ((NoL + NoV) + 1e-7)).  -> (diffuse, specular) of one channel."""
+    NoV, NoL, F0, metallic = F(NoV), F(NoL), F(F0), F(metallic)
+    D = F(F(1.0) / F(F(PM.PI * F(1.0)) * F(1.0) + F(1e-7)))
+    Vis = F(min(max(F(F(0.5) / F(F(NoL + NoV) + F(1e-7))), F(0.0)), F(1.0)))
+    p5 = PM.pow_rule(F(min(max(F(F(1.0) - F(LoH)), F(0.0)), F(1.0))), F(5.0))[0]
+    Fr = F(F0 + F(F(F(1.0) - F0) * p5))
+    ABx, ABy = fit(NoV, 1.0)
+    Ess = F(min(max(F(ABx + ABy), F(0.0)), F(1.0)))
+    ec = F(F(1.0) + F(F(F0 * F(F(1.0) - Ess)) / max(Ess, F(1e-4))))
+    specular = F(F(F(D * Vis) * Fr) * ec)
+    diffuse = F(F(F(F(F(1.0) - metallic) * F(F(1.0) - Fr)) * F(albedo)) * PM.FD_LAMBERT)
+    return diffuse, specular
+
+
+def test_empty_pixel_outcomes():
+    """depth == 0: zeros with a transparent background (all four halves, alpha included); (1, 1, 1) under a textured sky = exponent 15,
+    mantissa 0 in all three fields; the solid colour (0.25, 0.5, 1.0) = exponents 13, 14, 15; with neither flag the arithmetic runs on."""
+    out, st = one_pixel(TRANSPARENT_BACKGROUND | HAS_SKY, depth=0.0)
+    assert out.tolist() == [[[0, 0, 0, 0]]] and st["transparent_empty"] == 1
+    out, st = one_pixel(HAS_SKY, depth=0.0, sky_has_texture=True)
+    assert int(out[0, 0]) == (15 << 6) | (15 << 17) | (15 << 27) and st["sky"] == 1
+    out, st = one_pixel(HAS_SKY, depth=0.0, sky_solid_color=(0.25, 0.5, 1.0, 0.0))
+    assert int(out[0, 0]) == (13 << 6) | (14 << 17) | (15 << 27)
+    out, st = one_pixel(0, depth=0.0, emissive=15 << 6)  # world = (0, 0, 0), nothing lights it (no sun flag, no ambient): the emission alone
+    assert st["fallthrough_empty"] == 1 and rgb_of(out) == [1.0, 0.0, 0.0]
+    out, st = one_pixel(TRANSPARENT_BACKGROUND, depth=0.5, emissive=15 << 6)
+    assert out.tolist() == [[[0x3C00, 0, 0, 0x3C00]]] and st["lit_nol_positive"] == 1  # alpha 1.0
+
+
+def test_n_equals_v_equals_l():
+    """N = V = L = +z: H = normalize((0, 0, 2)) = N, NoH = LoH = 1, pow(0, 5) = 0 so F = F0 = 0.04 (albedo 1, metallic 0: lerp gives 0.04 + 0.96
+    * 0);  NoV = 1 + 1e-5, NoL = 1;  R = +z, horizon = saturate(1 + 1.3)^2 = 1;  colour = ((diffuse + specular) * Li) * NoL * visibility."""
+    out, st = one_pixel(HAS_DIRECTIONAL_LIGHT | HAS_CONTACT_SHADOWS, resolved=0.5, contact=0.5)
+    NoV = F(F(1.0) + F(1e-5))
+    d, s = rough_brdf(NoV, 1.0, 1.0, 0.04)
+    want = F(F(F(F(d + F(s * F(1.0))) * F(2.0)) * F(1.0)) * F(0.25))
+    assert st["lit_nol_positive"] == 1
+    assert rgb_of(out) == [trunc_uf(want, 6), trunc_uf(want, 6), trunc_uf(want, 5)]
+    # The same pixel by hand in decimal, with nothing taken from the checker: the fit at (x, y) = (1.00001, 1) gives AB = (0.305533, 0.001214),
+    # Ess = 0.306747, energy compensation 1 + 0.04 * 0.693253 / 0.306747 = 1.090401;  specular = (1 / pi) * (0.5 / 2.00001) * 0.04 * 1.090401 =
+    # 0.003471, diffuse = 0.96 / pi = 0.305577;  (0.305577 + 0.003471) * 2 * 0.25 = 0.154524 = 1.236193 * 2^-3: exponent field 12, mantissa
+    # floor(0.236193 * 64) = 15 (15.12: a seventh of a step from the nearest boundary, against a binary32 error of a thousandth of one), so
+    # the UF11 fields are 12 * 64 + 15 = 783 and the UF10 field is 12 * 32 + floor(7.56) = 391.
+    assert int(out[0, 0]) == 783 | (783 << 11) | (391 << 22)
+    dark, _ = one_pixel(HAS_CONTACT_SHADOWS)  # without HasDirectionalLight the sun's illuminance is 0
+    assert int(dark[0, 0]) == 0
+
+
+def test_fully_metallic_pixel():
+    """metallic 255: F0 = 0.04 + (albedo - 0.04) * 1 per channel, kd = (1 - 1) * .. = 0: no diffuse; albedo bytes (255, 0, 128)."""
+    out, _ = one_pixel(HAS_DIRECTIONAL_LIGHT, albedo=(128 << 16) | 255, mro=0x00FFFFFF)
+    NoV = F(F(1.0) + F(1e-5))
+    want = []
+    for byte, mbits in ((255, 6), (0, 6), (128, 5)):
+        alb = PM.srgb_decode(byte)[0]
+        F0 = F(F(0.04) + F(F(alb - F(0.04)) * F(1.0)))
+        d, s = rough_brdf(NoV, 1.0, 1.0, F0, metallic=1.0, albedo=alb)
+        assert d == 0.0
+        want.append(trunc_uf(F(F(F(d + s) * F(2.0)) * F(1.0)), mbits))
+    assert rgb_of(out) == want
+
+
+def test_h_equals_n_when_v_plus_l_cancels():
+    """V = +z, L = -z: VL = 0, dot(VL, VL) <= 1e-8, H = N.  N = +z: NoL = max(-1, 0) = 0, so the sun adds nothing; a point light straight
+    behind the surface cancels V the same way but ends at NdotL <= 0.  With N = (1, 0, 0)-ish both dots vanish too.  What is left is checked
+    through brdf() itself: H = N gives NoH = 1 and LoH = saturate(dot(L, N))."""
+    S = dict(N=(F(0.6), F(0.0), F(0.8)), V=(F(0.0), F(0.0), F(1.0)), albedo=[F(1.0)] * 3, F0=[F(0.04)] * 3, ec=[F(1.0)] * 3, metallic=F(0.0), NoV=F(0.8), alpha2=F(1.0))
+    d, s = PM.brdf(S, (F(0.0), F(0.0), F(-1.0)))
+    # NoL = saturate(-0.8) = 0, LoH = saturate(dot(L, N)) = 0: F = 0.04 + 0.96 * pow(1, 5) = 1;  Vis = saturate(0.5 / ((0 + 0.8 * 1) + 1e-7))
+    Vis = F(F(0.5) / F(F(F(0.0) + F(0.8)) + F(1e-7)))
+    D = F(F(1.0) / F(PM.PI + F(1e-7)))
+    assert F(s[0]) == F(F(F(D * Vis) * F(1.0)) * F(1.0)) and F(d[0]) == 0.0
+    out, st = one_pixel(HAS_DIRECTIONAL_LIGHT, sun=(0.0, 0.0, -1.0), lights=light_bytes(dict(kind=1, position=(0.0, 0.0, -1.5))))
+    assert st["lit_nol_zero"] == 1 and st["light_ndotl_out"] == 1 and int(out[0, 0]) == 0
+
+
+def light_bytes(*lights):
+    from oxylus_amd.synth import pack_lights
+
+    return pack_lights(list(lights)).numpy()
+
+
+def test_point_light_with_and_without_a_cutoff():
+    """A light at (0, 0, 2.5) above the pixel at (0, 0, 0.5): dist = 2, Ll = +z = N = V.  range 0: attenuation = 1 / (4 + 0.1).  range 4: win =
+    (2 / 4)^4 = 0.0625, (1 - 0.0625)^2 = 0.87890625 exactly, / 4.1.  range 2: win = 1, 1 - 1 = 0: out.  range 1: 1 - 16 < 0, max gives 0: out."""
+    NoV = F(F(1.0) + F(1e-5))
+    d, s = rough_brdf(NoV, 1.0, 1.0, 0.04)
+    for rng, att in ((0.0, F(F(1.0) / F(F(4.0) + F(0.1)))), (4.0, F(F(0.87890625) / F(F(4.0) + F(0.1))))):
+        out, st = one_pixel(0, lights=light_bytes(dict(kind=1, position=(0.0, 0.0, 2.5), range=rng, color=(1.0, 0.5, 0.25), intensity=3.0)))
+        want = [F(F(F(d + s) * F(F(F(c) * att) * F(3.0))) * F(1.0)) for c in (1.0, 0.5, 0.25)]
+        assert st["light_shaded"] == 1 and rgb_of(out) == [trunc_uf(want[0], 6), trunc_uf(want[1], 6), trunc_uf(want[2], 5)], rng
+        if rng == 0.0:
+            # by hand in decimal, as in test_n_equals_v_equals_l: (0.305577 + 0.003471) * (c / 4.1) * 3 = 0.226133 c = 1.809063 * 2^-3 (c = 1),
+            # 2^-4 (c = 0.5), 2^-5 (c = 0.25): UF11 12 * 64 + floor(51.78) = 819 and 11 * 64 + 51 = 755, UF10 10 * 32 + floor(25.89) = 345
+            assert int(out[0, 0]) == 819 | (755 << 11) | (345 << 22)
+    for rng in (2.0, 1.0):
+        out, st = one_pixel(0, lights=light_bytes(dict(kind=1, position=(0.0, 0.0, 2.5), range=rng, intensity=3.0)))
+        assert st["light_attenuation_out"] == 1 and int(out[0, 0]) == 0
+    out, st = one_pixel(0, lights=light_bytes(dict(kind=0, position=(0.0, 0.0, 2.5)), dict(kind=7, position=(0.0, 0.0, 2.5))))
+    assert st["light_kind_skipped"] == 2 and int(out[0, 0]) == 0
+
+
+def test_spot_light_inside_the_band_and_outside():
+    """The same light as a spot that points down -z: cos_angle = dot(-Ll, (0, 0, -1)) = 1.  inner 0.2 / outer 0.4: 1 >= cos(0.2), smoothstep's s
+    saturates to 1: the point light's value.  Tilted so that cos_angle = cos(0.3) exactly half-way in angle: s = (c - cos(0.4)) / (cos(0.2) -
+    cos(0.4)), the band.  Pointing away (+z): cos_angle = -1, s = 0: out."""
+    NoV = F(F(1.0) + F(1e-5))
+    d, s = rough_brdf(NoV, 1.0, 1.0, 0.04)
+    base = dict(kind=2, position=(0.0, 0.0, 2.5), inner_cone_angle=0.2, outer_cone_angle=0.4, intensity=3.0)
+    att = F(F(1.0) / F(F(4.0) + F(0.1)))
+    out, st = one_pixel(0, lights=light_bytes(dict(base, direction=(0.0, 0.0, -2.0))))
+    want = F(F(F(d + s) * F(F(F(1.0) * F(att * F(1.0))) * F(3.0))) * F(1.0))
+    assert st["light_shaded"] == 1 and rgb_of(out)[0] == trunc_uf(want, 6)
+    tilt = (F(np.sin(0.3)), F(0.0), F(-np.cos(0.3)))
+    ln = F(np.sqrt(F(F(F(tilt[0] * tilt[0]) + F(0.0)) + F(tilt[2] * tilt[2]))))
+    cos_angle = F(F(F(F(-0.0) * F(tilt[0] / ln)) + F(F(-0.0) * F(tilt[1] / ln))) + F(F(-1.0) * F(tilt[2] / ln)))
+    c_in, c_out = PM.cos_rule(F(0.2))[0], PM.cos_rule(F(0.4))[0]
+    t = F(F(cos_angle - c_out) / F(c_in - c_out))
+    assert 0.3 < t < 0.7
+    band = F(F(t * t) * F(F(3.0) - F(F(2.0) * t)))
+    out, st = one_pixel(0, lights=light_bytes(dict(base, direction=tuple(float(v) for v in tilt))))
+    want = F(F(F(d + s) * F(F(F(1.0) * F(att * band)) * F(3.0))) * F(1.0))
+    assert st["light_shaded"] == 1 and rgb_of(out)[0] == trunc_uf(want, 6)
+    out, st = one_pixel(0, lights=light_bytes(dict(base, direction=(0.0, 0.0, 1.0))))
+    assert st["light_attenuation_out"] == 1 and int(out[0, 0]) == 0
+
+
+def test_ambient_and_emission_alone():
+    """No sun, no lights, ambient 0.5: kS = F0 * AB.x + AB.y, kD = 1 - kS, spec_occlusion = saturate(pow(NoV + 1, 2^-17) - 1 + 1) = 1 (the power
+    of a value above 1 is above 1), indirect = kD * 0.5 * (1 / PI) + kS * 0.5;  plus the emission (1.0, 0.5, 2.0)."""
+    NoV = F(F(1.0) + F(1e-5))
+    ABx, ABy = fit(NoV, 1.0)
+    kS = F(F(F(0.04) * ABx) + ABy)
+    kD = F(F(1.0) * F(F(1.0) - kS))
+    indirect = F(F(F(F(F(kD * F(0.5)) * F(1.0)) * PM.FD_LAMBERT) * F(1.0)) + F(F(kS * F(0.5)) * F(1.0)))
+    out, _ = one_pixel(0, ambient=(0.5, 0.5, 0.5), emissive=(15 << 6) | (14 << 17) | (16 << 27))
+    assert rgb_of(out) == [trunc_uf(F(indirect + F(1.0)), 6), trunc_uf(F(indirect + F(0.5)), 6), trunc_uf(F(indirect + F(2.0)), 5)]
+
+
+def test_synthetic_inputs_reach_every_class():
+    """The images the GPU tests use: every pixel class and light outcome they are meant to reach occurs, by the checker's counts."""
+    inp = synthetic_inputs(33, 17, seed=7)
+    lights = light_bytes(dict(kind=1, position=(0.2, 0.1, 1.5), range=3.0), dict(kind=2, position=(-0.5, 0.4, 2.0), direction=(0.3, -0.2, -1.0),
+                                                                                inner_cone_angle=0.2, outer_cone_angle=0.5), dict(kind=0))
+    st = {}
+    out = PM.apply_pbr(inp["depth"], inp["albedo"], inp["normal"], inp["emissive"], inp["mro"], inp["ao"], inp["resolved"], inp["contact"],
+                       HAS_DIRECTIONAL_LIGHT | HAS_CONTACT_SHADOWS | HAS_SKY, INV_PV, CAMERA, SUN, SUN_INTENSITY, lights, stats=st, **SKY)
+    c = PM.counters(st)
+    assert c["sky"] > 20 and c["lit_nol_positive"] > 50 and c["lit_nol_zero"] > 50 and min(c[k] for k in PM.COUNTER_NAMES[5:]) > 0, c
+    assert len(np.unique(out)) > 300
