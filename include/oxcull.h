@@ -1135,6 +1135,61 @@ typedef struct oxc_pbr_context {
 
 oxc_status oxc_apply_pbr(oxc_ctx* ctx, const oxc_pbr_context* context, void* hip_stream);
 
+/* ---- eye adaptation: the luminance histogram of the lit HDR image and the exposure it gives ---------------------------------
+ * Replaces RendererInstance::apply_eye_adaptation (Oxylus/src/Render/Passes/PostProcess.cpp:7-77, pipelines histogram_generate and
+ * histogram_average, passes/histogram_generate.slang, passes/histogram_average.slang, passes/histogram.slang, com::remap at
+ * common/math.slang:203), the pass directly behind apply_pbr and the first reader of its image: a 256-bin log-luminance histogram of
+ * final_attachment, reduced to GPU::HistogramLuminance {adapted_luminance, exposure}, the record bloom_prefilter and tonemap multiply by.
+ * Out of scope: bloom, tone mapping and the lens effects, FXAA, the atmosphere branch, any change to what oxc_apply_pbr writes.
+ * time_coeff is taken as given: the reference computes 1 - glm::exp(-adaptation_speed * delta_time) on the host with the platform's exp,
+ * which no checker can pin, so it stays outside the parity claim; the C++ shim and the Python twin compute it from adaptation_speed and
+ * delta_time with their own expf and pass the result on.
+ * Arithmetic: the canonical binary32 arithmetic of oxc_apply_pbr -- round to nearest even, left to right, no contraction, IEEE division
+ * (1.0 / x is a division), max through fmaxf, a comparison with a NaN operand is false; a float to int conversion truncates and saturates
+ * and gives 0 for a NaN.  log2 is the log2 rule of oxc_generate_ambient_occlusion (rounded to binary32 once; NaN and everything below
+ * 2^-126 give -Inf, +Inf gives +Inf), exp2 the exp2 rule of oxc_apply_pbr.  The checker is tests/eye_adaptation_model.py.
+ * Per pixel (x, y) of the W x H image (histogram_generate.slang:19-43):
+ *   1. decode    (:35)  Stated rule, as for the albedo tap of oxc_apply_pbr: the Slang's Load is a load of texel (x, y).  source_format 0:
+ *              R = UF11 of bits 0-10, G = UF11 of bits 11-21, B = UF10 of bits 22-31 by the exact decode of oxc_apply_pbr step 2 (exponent
+ *              field 31 is +Inf for a zero mantissa, NaN otherwise).  source_format 1: halves 0, 1, 2 through binary16 -> binary32, exact,
+ *              denormals kept; alpha is not read.
+ *   2. luminance (:36)  luminance = (r * 0.2127f + g * 0.7152f) + b * 0.0722f, the constants as the Slang writes them.
+ *   3. dark      (:20-22)  luminance < 0.001f gives bin 0 (a negative or -0 luminance from RGBA16F too); a NaN fails the test and goes on.
+ *   4. bin       (:24-25)  l = log2(luminance);  mapped = ((l - min_exposure) / (max_exposure - min_exposure)) * 254.0f + 1.0f (com::remap
+ *              with the output range 1 .. 255; the difference of the two exposures is one binary32 subtraction);  bin = clamp(i32(mapped),
+ *              0, 255).  So a NaN luminance gives bin 0 and +Inf gives bin 255.
+ *   5. count     (:38-42)  histogram[bin] += 1.  The counts are integers: the result does not depend on the order.
+ * Once per call (histogram_average.slang:22-50):
+ *   6. weighted sum (:36-43)  weighted_sum = sum over k of histogram[k] * k in u32, modulo 2^32 as the Slang's InterlockedAdd gives it;
+ *              dark = f32(histogram[0]);  pixel_count = f32(width * height);  avg = f32(weighted_sum) / max(pixel_count - dark, 1.0f) - 1.0f.
+ *   7. desired   (:44)  desired = exp2(((avg / 254.0f) * (max_exposure - min_exposure)) + min_exposure).
+ *   8. adaptation (:45-46)  last = exposure_buffer.adapted_luminance;  adapted = last + (desired - last) * time_coeff.
+ *   9. exposure  (:22-26, :47-49)  ev100 = log2(adapted * ((100.0f * ev100_bias) / 12.5f));  exposure = 1.0f / (exp2(ev100) * 1.2f);  store
+ *              {adapted, exposure}.  A NaN in either word is stored as 0x7FC00000: no NaN bit pattern of the arithmetic reaches memory.
+ * Limits (else OXC_INVALID_ARG, nothing launched, nothing written): width and height not zero and at most 65536 a side, width * height at
+ * most 2^32 - 1; source_format 0 or 1; final_attachment 4-byte aligned with one u32 per pixel (format 0) or 8-byte aligned with one u16x4
+ * per pixel (format 1); histogram_buffer 4-byte aligned, 1024 bytes; exposure_buffer 4-byte aligned, 8 bytes; min_exposure, max_exposure,
+ * ev100_bias, time_coeff and max_exposure - min_exposure finite; max_exposure > min_exposure.  The exposure buffer's content is device
+ * data and is not validated: the rule is defined for any bit pattern in it.  histogram_buffer stands for the reference's transient
+ * histogram_bin_indices_buffer; after the call it holds this frame's counts.  exposure_buffer is caller-owned and persists between frames;
+ * the caller initialises it to {1.0f, 1.0f}, as RendererInstance.cpp:1778-1784 fills it.  The histogram is zeroed in-stream by a kernel;
+ * three launches, no scratch, no allocation, no host synchronisation; capturable into a HIP graph. */
+#define OXC_SCENE_HAS_EYE_ADAPTATION (1u << 2) /* GPU::SceneFlags, for callers that mirror RendererInstance.cpp:1278; the library does not read it */
+typedef struct oxc_eye_adaptation_context {
+  uint32_t struct_size; /* sizeof(oxc_eye_adaptation_context) */
+  uint32_t width, height;
+  uint32_t source_format;       /* 0: B10G11R11 UfloatPack32, u32[height][width];  1: R16G16B16A16 Sfloat, u16x4[height][width] */
+  float min_exposure;           /* GPU::HistogramLuminanceInfo: -6 (the component: -11.5) */
+  float max_exposure;           /* 18 */
+  float ev100_bias;             /* 1 */
+  float time_coeff;             /* 1 - exp(-adaptation_speed * delta_time), computed by the caller */
+  oxc_buffer final_attachment;  /* in: what oxc_apply_pbr wrote */
+  oxc_buffer histogram_buffer;  /* out: u32[256] */
+  oxc_buffer exposure_buffer;   /* in/out: {f32 adapted_luminance, f32 exposure} */
+} oxc_eye_adaptation_context;
+
+oxc_status oxc_apply_eye_adaptation(oxc_ctx* ctx, const oxc_eye_adaptation_context* context, void* hip_stream);
+
 /* ---- multi-GPU exchange: one process per GPU, RCCL over xGMI ---------------------------
  * The meshlet-instance array shards by contiguous range and every rank culls its shard on its own; the only
  * exchanges of the path are (1) the per-rank counters {emitted meshlets, early, late, index count} to every rank

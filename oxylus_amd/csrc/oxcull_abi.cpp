@@ -93,6 +93,7 @@ struct oxc_ctx {
   PassCounters ambient_occlusion_stats;  // OXC_TUNE_AMBIENT_OCCLUSION_STATS: u32[15] (16 allocated)
   PassCounters visbuffer_decode_stats;   // OXC_TUNE_VISBUFFER_DECODE_STATS: u32[4]
   PassCounters pbr_apply_stats;          // OXC_TUNE_PBR_APPLY_STATS: u32[9]
+  uint32_t eye_adaptation_grid = 0;      // OXC_TUNE_EYE_ADAPTATION_GRID: cap of the histogram kernel's grid in blocks, 0 = uncapped
   void* comm = nullptr;           // ncclComm_t (oxc_comm_init)
   uint32_t comm_rank = 0, comm_world = 0;
   // counter slots
@@ -2026,6 +2027,52 @@ oxc_status oxc_apply_pbr(oxc_ctx* ctx, const oxc_pbr_context* c, void* hip_strea
   return OXC_OK;
 }
 
+oxc_status oxc_apply_eye_adaptation(oxc_ctx* ctx, const oxc_eye_adaptation_context* c, void* hip_stream) {
+  if (!ctx) return OXC_INVALID_ARG;
+  if (!c || c->struct_size != sizeof(oxc_eye_adaptation_context)) return fail(ctx, OXC_INVALID_ARG, "apply_eye_adaptation: bad context / struct_size");
+  const char* const entry = "apply_eye_adaptation";
+  if (c->width == 0u || c->height == 0u) return bad_arg(ctx, entry, "the extent must not be zero");
+  if (c->width > 65536u || c->height > 65536u) return bad_arg(ctx, entry, "extent beyond 65536");
+  const uint64_t pixels = (uint64_t)c->width * c->height;
+  if (pixels > 0xFFFFFFFFull) return bad_arg(ctx, entry, "width * height beyond 2^32 - 1");
+  if (c->source_format > 1u) return bad_arg(ctx, entry, "source_format must be 0 (B10G11R11) or 1 (R16G16B16A16 Sfloat)");
+  const uint32_t texel = c->source_format ? 8u : 4u;
+  if (bad_pixel_buffer(c->final_attachment, pixels, texel))
+    return bad_arg(ctx, entry, "final_attachment must be one aligned u32 per pixel (format 0) or one 8-byte aligned u16x4 per pixel (format 1)");
+  if (bad_pixel_buffer(c->histogram_buffer, 256u, 4u)) return bad_arg(ctx, entry, "histogram_buffer must be 256 aligned u32");
+  if (bad_pixel_buffer(c->exposure_buffer, 2u, 4u)) return bad_arg(ctx, entry, "exposure_buffer must be two aligned f32");
+  const float exposure_range = c->max_exposure - c->min_exposure;
+  if (!std::isfinite(c->min_exposure) || !std::isfinite(c->max_exposure) || !std::isfinite(c->ev100_bias) || !std::isfinite(c->time_coeff) || !std::isfinite(exposure_range))
+    return bad_arg(ctx, entry, "min_exposure, max_exposure, ev100_bias, time_coeff and max_exposure - min_exposure must be finite");
+  if (!(c->max_exposure > c->min_exposure)) return bad_arg(ctx, entry, "max_exposure must be above min_exposure");
+  OXC_HIP(ctx, hipSetDevice(ctx->device));
+  OXC_ORDER(ctx, hip_stream);
+  const hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  EyeAdaptationArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.src = c->final_attachment.dptr;
+  a.histogram = static_cast<uint32_t*>(c->histogram_buffer.dptr);
+  a.exposure = static_cast<float*>(c->exposure_buffer.dptr);
+  a.pixels = pixels;
+  // the texels before the first 16-byte boundary (the buffer is aligned to its texel), then whole vectors
+  const uint32_t per_vector = 16u / texel;
+  const uint64_t misaligned = ((16u - (reinterpret_cast<uintptr_t>(a.src) & 15u)) & 15u) / texel;
+  a.head = (uint32_t)std::min<uint64_t>(misaligned, pixels);
+  a.vectors = (pixels - a.head) / per_vector;
+  a.format = c->source_format;
+  a.min_exposure = c->min_exposure;
+  a.exposure_range = exposure_range;
+  a.pixel_count = (float)(uint32_t)pixels;
+  a.time_coeff = c->time_coeff;
+  a.ev100_bias = c->ev100_bias;
+  // about one resident round: four blocks of four waves per CU, every thread with at least one vector
+  uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((a.vectors + 255u) / 256u, 1u), (uint64_t)ctx->num_cus * 4u);
+  if (ctx->eye_adaptation_grid) grid = std::min(grid, ctx->eye_adaptation_grid);
+  launch_eye_adaptation(a, grid, s);
+  OXC_HIP(ctx, hipGetLastError());
+  return OXC_OK;
+}
+
 oxc_status oxc_generate_ambient_occlusion(oxc_ctx* ctx, const oxc_ambient_occlusion_context* c, void* hip_stream) {
   if (!ctx) return OXC_INVALID_ARG;
   if (!c || c->struct_size != sizeof(oxc_ambient_occlusion_context)) return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: bad context / struct_size");
@@ -2422,6 +2469,7 @@ oxc_status oxc_debug_set_tuning(oxc_ctx* ctx, uint32_t knob, uint32_t value) {
     case OXC_TUNE_CONTACT_SHADOWS_STATS: ctx->contact_shadows_stats.on = value != 0u; return OXC_OK;
     case OXC_TUNE_VISBUFFER_DECODE_STATS: ctx->visbuffer_decode_stats.on = value != 0u; return OXC_OK;
     case OXC_TUNE_PBR_APPLY_STATS: ctx->pbr_apply_stats.on = value != 0u; return OXC_OK;
+    case OXC_TUNE_EYE_ADAPTATION_GRID: ctx->eye_adaptation_grid = value; return OXC_OK;
     case OXC_TUNE_AMBIENT_OCCLUSION_STATS: ctx->ambient_occlusion_stats.on = value != 0u; return OXC_OK;
     case OXC_TUNE_VSM_DRAW_CAPACITY:
       if (ctx->vsm_draw_scratch) return fail(ctx, OXC_INVALID_ARG, "set_tuning: the shadow draw's scratch is allocated by the first oxc_draw_physical_pages; set its capacity before");

@@ -645,6 +645,20 @@ struct PbrApplyArgs {
   float env[3], sky_color[3];
 };
 void launch_pbr_apply(const PbrApplyArgs& a, hipStream_t s);
+// oxcull_eye_adaptation.hip: the luminance histogram of the lit HDR image and the exposure it gives (oxc_apply_eye_adaptation)
+struct EyeAdaptationArgs {
+  const void* src;       // `pixels` texels in one run: u32 (B10G11R11, format 0) or u16x4 (R16G16B16A16 Sfloat, format 1)
+  uint32_t* histogram;   // u32[256], zeroed by the first launch
+  float* exposure;       // {adapted_luminance, exposure}, read and written by the averaging kernel
+  uint64_t pixels;       // width * height
+  uint64_t vectors;      // whole 16-byte vectors behind the head
+  uint32_t head;         // texels before the first 16-byte boundary
+  uint32_t format;
+  float min_exposure, exposure_range;  // max_exposure - min_exposure, one binary32 subtraction on the host
+  float pixel_count;     // f32(width * height)
+  float time_coeff, ev100_bias;
+};
+void launch_eye_adaptation(const EyeAdaptationArgs& a, uint32_t grid, hipStream_t s);
 // oxcull_bounds.hip: meshlet bounds producer
 void launch_build_meshlet_bounds(const float* pos, uint32_t vertex_count, const void* meshlets, uint32_t meshlet_count, const uint32_t* vidx,
                                  const uint8_t* micro, void* out_bounds, float* out_mesh6, void* out_qpos, float* meshlet_minmax, float* normals,

@@ -73,15 +73,6 @@ OXC_DEV float srgb_decode(uint32_t byte) {
   return c <= 0.04045f ? c / 12.92f : pow_rule((c + 0.055f) / 1.055f, 2.4f);
 }
 
-// unsigned small float with a 5-bit exponent and MBITS of mantissa -> binary32, exact
-template <int MBITS>
-OXC_DEV float unpack_ufloat(uint32_t v) {
-  const uint32_t e = v >> MBITS, m = v & ((1u << MBITS) - 1u);
-  if (e == 0u) return (float)m * (MBITS == 6 ? 0x1p-20f : 0x1p-19f);
-  if (e == 31u) return m ? __builtin_nanf("") : __builtin_inff();
-  return asf(((e + 112u) << 23) | (m << (23 - MBITS)));
-}
-
 // com::oct_to_vec3 of the two halves of `word` (the first in the low half): one normalisation
 OXC_DEV V3 oct_to_vec3(uint32_t word) { return normalize3(oct_normal_ba(word)); }
 

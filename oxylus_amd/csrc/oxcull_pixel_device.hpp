@@ -108,6 +108,16 @@ OXC_DEV uint32_t pack_ufloat(float v) {
   return sh > 24 ? 0u : (0x800000u | m) >> sh;
 }
 
+// unsigned small float with a 5-bit exponent and MBITS of mantissa -> binary32, exact (oxc_apply_pbr step 2; oxc_apply_eye_adaptation
+// reads its B10G11R11 source by it)
+template <int MBITS>
+OXC_DEV float unpack_ufloat(uint32_t v) {
+  const uint32_t e = v >> MBITS, m = v & ((1u << MBITS) - 1u);
+  if (e == 0u) return (float)m * (MBITS == 6 ? 0x1p-20f : 0x1p-19f);
+  if (e == 31u) return m ? __builtin_nanf("") : __builtin_inff();
+  return asf(((e + 112u) << 23) | (m << (23 - MBITS)));
+}
+
 // The pixel of this thread: an 8 x 8 pixel tile per wave, a 16 x 16 tile per block of 256 threads.
 OXC_DEV uint2 tile_pixel() {
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;

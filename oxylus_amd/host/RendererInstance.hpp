@@ -13,6 +13,7 @@
 // programmer errors (Oxylus/include/Utils/Log.hpp:38-47); the shim throws std::runtime_error
 // carrying oxc_last_error() instead of aborting.
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -55,6 +56,7 @@ struct PreparedFrame {
   Buffer reordered_indices_buffer = {};
   Buffer materials_buffer = {};  // GPU::Material[], read by decode_visbuffer
   Buffer lights_buffer = {};     // GPU::Light[], 64 bytes each, read by apply_pbr
+  Buffer exposure_buffer = {};   // GPU::HistogramLuminance {adapted_luminance, exposure}, 8 bytes, kept between frames; the caller fills it with 1.0f once (RendererInstance.cpp:1778-1784)
 };
 
 struct CullGeometryContext {
@@ -139,7 +141,25 @@ struct PBRContext {
   ImageAttachment resolved_shadows_attachment = {};
 };
 
+// What the post passes share (RendererInstance.hpp:344-351 of the reference, the members apply_eye_adaptation reads): final_attachment is the
+// linear buffer apply_pbr wrote, in the format gpu_scene_flags' TransparentBackground picks.
+struct Extent3D {
+  uint32_t width = 0, height = 0, depth = 1;
+};
+struct PostProcessContext {
+  float delta_time = 0.0f;
+  Extent3D extent = {};
+  Buffer final_attachment = {};
+};
+
 namespace GPU {
+// SceneGPU.hpp:278-284
+struct HistogramLuminanceInfo {
+  float min_exposure = -6.0f;
+  float max_exposure = 18.0f;
+  float adaptation_speed = 1.1f;
+  float ev100_bias = 1.0f;
+};
 // scene.slang:236-240
 struct Sky {
   float solid_color[4] = {0.0f, 0.0f, 0.0f, 1.0f};
@@ -175,6 +195,8 @@ public:
   GPU::DirectionalLight directional_light = {};
   GPU::Sky sky_data = {};
   GPU::Camera camera = {};
+  GPU::HistogramLuminanceInfo eye_adaptation = {};  // read by apply_eye_adaptation
+  Buffer histogram_bin_indices_buffer = {};         // u32[256]: the reference's transient buffer, here caller-owned; this frame's counts after the call
 
   void set_stream(void* hip_stream) { stream_ = hip_stream; }
 
@@ -374,6 +396,24 @@ public:
     c.final_attachment = dst_attachment;
     check(oxc_apply_pbr(ctx_, &c, stream_));
     return dst_attachment;
+  }
+  // RendererInstance::apply_eye_adaptation (Passes/PostProcess.cpp:7-77): the luminance histogram of context.final_attachment into
+  // histogram_bin_indices_buffer and the adapted luminance and exposure into prepared_frame.exposure_buffer.  time_coeff is computed here
+  // with this platform's expf (PostProcess.cpp:63).  Rules: include/oxcull.h, oxc_apply_eye_adaptation.
+  auto apply_eye_adaptation(PostProcessContext& context) -> void {
+    oxc_eye_adaptation_context c = {};
+    c.struct_size = sizeof c;
+    c.width = context.extent.width;
+    c.height = context.extent.height;
+    c.source_format = (gpu_scene_flags & OXC_SCENE_TRANSPARENT_BACKGROUND) ? 1u : 0u;
+    c.min_exposure = eye_adaptation.min_exposure;
+    c.max_exposure = eye_adaptation.max_exposure;
+    c.ev100_bias = eye_adaptation.ev100_bias;
+    c.time_coeff = 1.0f - std::exp(-eye_adaptation.adaptation_speed * context.delta_time);
+    c.final_attachment = context.final_attachment;
+    c.histogram_buffer = histogram_bin_indices_buffer;
+    c.exposure_buffer = prepared_frame.exposure_buffer;
+    check(oxc_apply_eye_adaptation(ctx_, &c, stream_));
   }
   auto build_meshlet_bounds(oxc_meshlet_bounds_desc desc) -> void {
     desc.struct_size = sizeof desc;

@@ -67,5 +67,13 @@ int main(int argc, char**) {
   } catch (const std::exception& e) {
     std::printf("expected (no attachments bound): %s\n", e.what());
   }
+  try {  // RendererInstance.cpp:1278: the post passes start with the eye adaptation
+    auto post_process_context = PostProcessContext{.delta_time = 1.0f / 60.0f, .extent = {.width = 1920, .height = 1080}, .final_attachment = Buffer{}};
+    self.gpu_scene_flags |= OXC_SCENE_HAS_EYE_ADAPTATION;
+    self.eye_adaptation = {.min_exposure = -11.5f, .max_exposure = 18.0f};
+    self.apply_eye_adaptation(post_process_context);
+  } catch (const std::exception& e) {
+    std::printf("expected (no attachments bound): %s\n", e.what());
+  }
   return 0;
 }

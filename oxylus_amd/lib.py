@@ -31,9 +31,12 @@ TUNE_ASYNC_MTEST_BLOCKS_PER_CU, TUNE_ASYNC_TRI_BLOCKS_PER_CU, TUNE_RASTER_BIG_CA
 TUNE_VSM_DRAW_STATS, TUNE_VSM_DRAW_CAPACITY, TUNE_VSM_RESOLVE_STATS, TUNE_CONTACT_SHADOWS_STATS, TUNE_AMBIENT_OCCLUSION_STATS = 8, 9, 10, 11, 12
 TUNE_VISBUFFER_DECODE_STATS = 13
 TUNE_PBR_APPLY_STATS = 14
+TUNE_EYE_ADAPTATION_GRID = 15
 
 # GPU::SceneFlags bits oxc_apply_pbr reads (scene.slang:242-256)
 SCENE_HAS_DIRECTIONAL_LIGHT, SCENE_HAS_ATMOSPHERE, SCENE_HAS_CONTACT_SHADOWS, SCENE_HAS_SKY, SCENE_TRANSPARENT_BACKGROUND = 1 << 0, 1 << 1, 1 << 9, 1 << 10, 1 << 11
+SCENE_HAS_EYE_ADAPTATION = 1 << 2  # for callers that mirror RendererInstance.cpp:1278; the library does not read it
+EYE_SOURCE_B10G11R11, EYE_SOURCE_R16G16B16A16 = 0, 1  # oxc_eye_adaptation_context.source_format
 LIGHT_KIND_DIRECTIONAL, LIGHT_KIND_POINT, LIGHT_KIND_SPOT = 0, 1, 2  # GPU::LightKind
 
 
@@ -409,6 +412,23 @@ class PbrContext(C.Structure):
     ]
 
 
+class EyeAdaptationContext(C.Structure):
+    """oxc_eye_adaptation_context (include/oxcull.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("source_format", C.c_uint32),
+        ("min_exposure", C.c_float),
+        ("max_exposure", C.c_float),
+        ("ev100_bias", C.c_float),
+        ("time_coeff", C.c_float),
+        ("final_attachment", Buffer),
+        ("histogram_buffer", Buffer),
+        ("exposure_buffer", Buffer),
+    ]
+
+
 # every symbol include/oxcull.h declares
 EXPORTS = [
     "oxc_abi_version",
@@ -444,6 +464,7 @@ EXPORTS = [
     "oxc_debug_visbuffer_decode_stats",
     "oxc_apply_pbr",
     "oxc_debug_pbr_apply_stats",
+    "oxc_apply_eye_adaptation",
     "oxc_draw_physical_pages",
     "oxc_debug_vsm_draw_stats",
     "oxc_resolve_shadowmap",
@@ -549,6 +570,7 @@ def load(path: str = None) -> C.CDLL:
     lib.oxc_debug_visbuffer_decode_stats.argtypes = [vp, vp, vp]
     lib.oxc_apply_pbr.argtypes = [vp, C.POINTER(PbrContext), vp]
     lib.oxc_debug_pbr_apply_stats.argtypes = [vp, vp, vp]
+    lib.oxc_apply_eye_adaptation.argtypes = [vp, C.POINTER(EyeAdaptationContext), vp]
     lib.oxc_draw_physical_pages.argtypes = [vp, C.POINTER(PreparedFrame), C.POINTER(VsmDrawContext), vp]
     lib.oxc_debug_vsm_draw_stats.argtypes = [vp, vp, vp]
     lib.oxc_resolve_shadowmap.argtypes = [vp, C.POINTER(ShadowResolveContext), vp]

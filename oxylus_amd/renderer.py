@@ -10,6 +10,8 @@ runner and bench driver are Python.
 from __future__ import annotations
 
 import ctypes as C
+import math
+import struct
 from dataclasses import dataclass, field
 from typing import Optional
 
@@ -546,6 +548,57 @@ class PBRContext:
         return c
 
 
+def exposure_buffer(device="cuda") -> torch.Tensor:
+    """A fresh GPU::HistogramLuminance {adapted_luminance, exposure} = {1.0, 1.0}, as RendererInstance.cpp:1778-1784 fills it: float32 [2].
+    The caller keeps it between frames; apply_eye_adaptation reads and rewrites it."""
+    return torch.ones(2, dtype=torch.float32, device=device)
+
+
+def eye_adaptation_time_coeff(adaptation_speed: float, delta_time: float) -> float:
+    """1 - exp(-adaptation_speed * delta_time) in binary32 (PostProcess.cpp:63) with this host's exp: outside the parity claim.  The exponential is
+    Python's binary64 `exp` rounded to binary32 once, the C++ shim's is the platform's `expf`: for the same inputs the two may differ in the last
+    bit.  Both pass their result on as `time_coeff`, and the rule starts behind it."""
+    f32 = lambda x: struct.unpack("<f", struct.pack("<f", x))[0]  # noqa: E731
+    return f32(1.0 - f32(math.exp(f32(-f32(adaptation_speed) * f32(delta_time)))))
+
+
+@dataclass
+class EyeAdaptationContext:
+    """oxc_eye_adaptation_context: RendererInstance::apply_eye_adaptation (Passes/PostProcess.cpp:7-77).  `create` takes the image apply_pbr
+    wrote -- int32 [H, W] (B10G11R11) or int16 [H, W, 4] (R16G16B16A16 Sfloat); the format follows from the shape --, the persistent
+    exposure buffer (exposure_buffer()) and the GPU::HistogramLuminanceInfo settings, and allocates the histogram: int32 [256]."""
+    final_attachment: torch.Tensor   # in
+    histogram_buffer: torch.Tensor   # out: int32 [256], this frame's counts
+    exposure_buffer: torch.Tensor    # in/out: float32 [2]
+    width: int
+    height: int
+    source_format: int
+    min_exposure: float = -6.0
+    max_exposure: float = 18.0
+    adaptation_speed: float = 1.1
+    ev100_bias: float = 1.0
+    time_coeff: Optional[float] = None  # set: passed on as given; None: from adaptation_speed and the call's delta_time
+
+    @staticmethod
+    def create(final_attachment: torch.Tensor, exposure: torch.Tensor, min_exposure: float = -6.0, max_exposure: float = 18.0,
+               adaptation_speed: float = 1.1, ev100_bias: float = 1.0, time_coeff: Optional[float] = None) -> "EyeAdaptationContext":
+        fmt = L.EYE_SOURCE_R16G16B16A16 if final_attachment.dim() == 3 else L.EYE_SOURCE_B10G11R11
+        hist = torch.zeros(256, dtype=torch.int32, device=final_attachment.device)
+        return EyeAdaptationContext(final_attachment, hist, exposure, int(final_attachment.shape[1]), int(final_attachment.shape[0]), fmt,
+                                    float(min_exposure), float(max_exposure), float(adaptation_speed), float(ev100_bias), time_coeff)
+
+    def c(self, delta_time: float = 0.0) -> L.EyeAdaptationContext:
+        c = L.EyeAdaptationContext()
+        c.struct_size = C.sizeof(L.EyeAdaptationContext)
+        c.width, c.height, c.source_format = int(self.width), int(self.height), int(self.source_format)
+        c.min_exposure, c.max_exposure, c.ev100_bias = float(self.min_exposure), float(self.max_exposure), float(self.ev100_bias)
+        c.time_coeff = float(self.time_coeff) if self.time_coeff is not None else eye_adaptation_time_coeff(self.adaptation_speed, delta_time)
+        c.final_attachment = _buf(self.final_attachment)
+        c.histogram_buffer = _buf(self.histogram_buffer)
+        c.exposure_buffer = _buf(self.exposure_buffer)
+        return c
+
+
 @dataclass
 class VisbufferDecodeContext:
     """oxc_decode_context: RendererInstance::decode_visbuffer (Passes/DrawGeometry.cpp:192-274), the geometry and material-factor half of
@@ -828,6 +881,14 @@ class RendererInstance:
         c = context.c()
         self._keep = context
         self._check(self._lib.oxc_apply_pbr(self._ctx, C.byref(c), self._stream(stream)))
+
+    def apply_eye_adaptation(self, context: EyeAdaptationContext, delta_time: float = 0.0, stream=None):
+        """Passes/PostProcess.cpp:7-77: the 256-bin log-luminance histogram of `context.final_attachment` into `context.histogram_buffer` and
+        the adapted luminance and exposure it gives into `context.exposure_buffer` (include/oxcull.h, oxc_apply_eye_adaptation).  time_coeff
+        is `context.time_coeff` where set, else 1 - exp(-adaptation_speed * delta_time)."""
+        c = context.c(delta_time)
+        self._keep = context
+        self._check(self._lib.oxc_apply_eye_adaptation(self._ctx, C.byref(c), self._stream(stream)))
 
     def debug_pbr_apply_stats(self, stream=None) -> dict:
         """What the last apply_pbr did, after debug_set_tuning(L.TUNE_PBR_APPLY_STATS, 1) (measurement hook; synchronises)."""
