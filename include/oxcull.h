@@ -1174,7 +1174,7 @@ oxc_status oxc_apply_pbr(oxc_ctx* ctx, const oxc_pbr_context* context, void* hip
  * histogram_bin_indices_buffer; after the call it holds this frame's counts.  exposure_buffer is caller-owned and persists between frames;
  * the caller initialises it to {1.0f, 1.0f}, as RendererInstance.cpp:1778-1784 fills it.  The histogram is zeroed in-stream by a kernel;
  * three launches, no scratch, no allocation, no host synchronisation; capturable into a HIP graph. */
-#define OXC_SCENE_HAS_EYE_ADAPTATION (1u << 2) /* GPU::SceneFlags, for callers that mirror RendererInstance.cpp:1278; the library does not read it */
+#define OXC_SCENE_HAS_EYE_ADAPTATION (1u << 2) /* GPU::SceneFlags (RendererInstance.cpp:1278); oxc_apply_eye_adaptation does not read it, oxc_apply_bloom's scene_flags does */
 typedef struct oxc_eye_adaptation_context {
   uint32_t struct_size; /* sizeof(oxc_eye_adaptation_context) */
   uint32_t width, height;
@@ -1189,6 +1189,96 @@ typedef struct oxc_eye_adaptation_context {
 } oxc_eye_adaptation_context;
 
 oxc_status oxc_apply_eye_adaptation(oxc_ctx* ctx, const oxc_eye_adaptation_context* context, void* hip_stream);
+
+/* ---- bloom: the prefiltered half-resolution image, its downsample pyramid and the upsample pyramid the tonemap reads -------------
+ * Replaces RendererInstance::apply_bloom (Oxylus/src/Render/Passes/PostProcess.cpp:79-203, pipelines bloom_prefilter, bloom_downsample
+ * and bloom_upsample: passes/bloom_prefilter.slang, passes/bloom_downsample.slang, passes/bloom_upsample.slang, com::luminance at
+ * common/color.slang:79-81, the extents at RendererInstance.cpp:509-510 and 1257-1267, Texture::calculate_mip_count at
+ * include/Asset/Texture.hpp:144-146, the samplers LinearSamplerBorder and LinearSamplerClamped at include/Render/Utils/VukCommon.hpp:
+ * 103-120), the pass directly behind apply_eye_adaptation and the first reader of its exposure.
+ * Out of scope: tone mapping, the lens effects, FXAA, the atmosphere branch.  bloom_intensity is set by apply_bloom for the tonemap; the
+ * C++ shim and the Python twin carry it, the library does not read it.
+ * Arithmetic: the canonical binary32 arithmetic of oxc_apply_pbr -- round to nearest even, left to right, no contraction, IEEE division
+ * (1.0 / x is a division), min / max through fminf / fmaxf (a NaN operand gives the other one), clamp(x, a, b) = min(max(x, a), b),
+ * lerp(a, b, t) = a + (b - a) * t.  UF11 / UF10 decode is the exact decode of oxc_apply_pbr step 2, the pack the truncating one of
+ * oxc_decode_visbuffer step 8 (a NaN becomes the one fixed pattern, negatives become 0); binary16 conversion as in oxc_apply_pbr step 12
+ * (round to nearest even, denormals kept, a NaN stored as 0x7E00; binary16 -> binary32 exact).  The checker is tests/bloom_model.py.
+ * Geometry: the source is W x H; the bloom extent is (w2, h2) = (W / 2, H / 2), integer divisions; L = floor(log2(max(w2, h2))) + 1
+ * levels, computed in integers -- equal to the reference's u32(log2f(f32(m))) + 1 for every side the limits allow (m < 8192 is exact in
+ * binary32, and a correctly rounded log2f of such an m is below the next integer unless m is that power of two); level k is
+ * max(1, w2 >> k) x max(1, h2 >> k); two pyramids of that shape, bloom_downsampled (D) and bloom_upsampled (U).  Level L - 1 is 1 x 1.
+ * Sampling (stated difference, as in oxc_contact_shadows step 6 and oxc_generate_ambient_occlusion step 9): a hardware linear sampler
+ * has fixed-point weights of an implementation-defined width, so the rule is the manual bilinear.  For the output pixel (x, y) of an
+ * ow x oh output reading an sw x sh source level with the tap offset (kx, ky):  uv = ((f32(x) + 0.5) / f32(ow), (f32(y) + 0.5) / f32(oh));
+ * ts = (1.0 / f32(ow), 1.0 / f32(oh)) -- from the OUTPUT extent, as the shaders write it;  p = uv + ts * (kx, ky);
+ * g = p * (f32(sw), f32(sh)) - 0.5;  i = floor(g) converted to i32 saturating;  f = g - floor(g);  the four texels are
+ * (i.x + {0, 1}, i.y + {0, 1});  the result is lerp(lerp(t00, t10, f.x), lerp(t01, t11, f.x), f.y) per channel.  Address modes:
+ * border (LinearSamplerBorder, transparent black): a texel whose x or y lies outside [0, size - 1] is (0, 0, 0) -- not clamped;
+ * clamp (LinearSamplerClamped): each coordinate is clamped to [0, size - 1], exactly as oxc_contact_shadows does.
+ * The tap offsets (bloom_prefilter.slang:51-63, bloom_downsample.slang:21-33): a (-2, 2), b (0, 2), c (2, 2), d (-2, 0), e (0, 0),
+ * f (2, 0), g (-2, -2), h (0, -2), i (2, -2), j (-1, 1), k (1, 1), l (-1, -1), m (1, -1);  of the upsample (bloom_upsample.slang:31-39):
+ * a (-1, 1), b (0, 1), c (1, 1), d (-1, 0), e (0, 0), f (1, 0), g (-1, -1), h (0, -1), i (1, -1).
+ *   1. clear     (RendererInstance.cpp:1267, PostProcess.cpp:98)  The texel of level L - 1 of U is stored as zero (alpha 1.0 with RGBA16F,
+ *              step 5).  The reference clears both pyramids to black; every other level of both is fully overwritten below, so after the
+ *              call every byte of both pyramids is defined.  With L = 1 that level is U's level 0: the bloom the tonemap reads is black.
+ *              The clear is done by a kernel in-stream.
+ *   2. prefilter (bloom_prefilter.slang:41-87)  Output D level 0, source the W x H final image, border.  The 13 taps a..m.
+ *              exposure = OXC_SCENE_HAS_EYE_ADAPTATION ? the second word of exposure_buffer : 1.0 -- device data, any bit pattern.
+ *              Five groups per channel: (((a + b) + d) + e) * 0.25 * exposure, (((b + c) + e) + f) ..., (((d + e) + g) + h) ...,
+ *              (((e + f) + h) + i) ..., (((j + k) + l) + m) ... .  Then in that order over the groups: group = min(group, clamp_value)
+ *              per channel;  weight = 1.0 / (1.0 + ((r * 0.299f + g * 0.587f) + b * 0.114f));  prefilter(group): brightness = max(r,
+ *              max(g, b)), knee = threshold * soft_threshold, soft = clamp((brightness - threshold) + knee, 0.0, 2.0 * knee),
+ *              soft = ((soft * soft) * 0.25) / (knee + 1.0e-5f), contribution = max(soft, brightness - threshold) / max(brightness,
+ *              1.0e-5f), group * contribution per channel;  color_sum += prefilter(group) * weight (from 0.0);  weight_sum += weight
+ *              (from 0.0).  Store color_sum / (weight_sum + 1.0e-5f) per channel.
+ *   3. downsample (bloom_downsample.slang:12-40, PostProcess.cpp:136-163)  For k = 1 .. L - 1 in order: output D level k, source D level
+ *              k - 1, border, the 13 taps:  result = ((((a + c) + g) + i) * 0.03125 + (((b + d) + f) + h) * 0.0625) + ((((e + j) + k) + l)
+ *              + m) * 0.125.
+ *   4. upsample  (bloom_upsample.slang:18-47, PostProcess.cpp:169-202)  For k = L - 1 down to 1 in order: output U level k - 1; the 9-tap
+ *              source is D level L - 1 when k = L - 1, else U level k; clamp.  color_sum = (e * 0.25 + (((b + d) + f) + h) * 0.125) +
+ *              (((a + c) + g) + i) * 0.0625.  source_color: the Slang's un-offset SampleLevel of D level k - 1 samples a level of the
+ *              output's own extent at the pixel centre; the stated rule, as for the albedo tap of oxc_apply_pbr, is a load of texel (x, y).
+ *              Store lerp(source_color, color_sum, radius).
+ *   5. formats   source_format 0: the source and both pyramids are B10G11R11 UfloatPack32, one u32 per texel.  source_format 1
+ *              (transparent background): R16G16B16A16 Sfloat, one u16x4 per texel; alpha is never read and is stored as 1.0 (0x3C00).
+ *              A decision the reference leaves open: its shaders declare the storage images R11F_G11F_B10F while same_format_as(
+ *              final_attachment) makes them RGBA16F in that mode, and no Vulkan rule defines what such a store does; the rule here is
+ *              the attachment's format.  Every level is packed when stored and decoded when the next step reads it: the truncation of
+ *              the pack is part of the result.
+ * Limits (else OXC_INVALID_ARG, nothing launched, nothing written; the first broken rule in this order gives the message): width and
+ * height at least 2 and max(width, height) / 2 < 8192 (so L <= 13); source_format 0 or 1; final_attachment aligned to its texel (4 or 8
+ * bytes) with one texel per pixel; both pyramids with width == W / 2, height == H / 2, levels == L; every level aligned to its texel and
+ * inside the pyramid's `bytes`; the levels of a pyramid do not overlap each other; no level of one pyramid shares a byte with a level of the other or
+ * with the source; exposure_buffer, when read, 4-byte aligned and 8 bytes (without the flag it is not looked at and may be null);
+ * threshold, soft_threshold, clamp_value and radius finite.  No scratch, no allocation, no host synchronisation; capturable into a HIP
+ * graph on one stream as a linear chain of kernels. */
+#define OXC_SCENE_HAS_BLOOM (1u << 3) /* GPU::SceneFlags, for callers that mirror RendererInstance.cpp:1282; the library does not read it */
+/* A mip pyramid of 4-byte (B10G11R11) or 8-byte (R16G16B16A16 Sfloat) texels in one device allocation: oxc_image's fields under the
+ * same names, then the allocation's size.  Level k is max(1, width >> k) x max(1, height >> k) texels, row-major, at byte offset
+ * level_offset[k]; the levels may lie in any order and with gaps. */
+typedef struct oxc_image_pyramid {
+  void* dptr;
+  uint32_t width, height, levels, _pad;
+  uint64_t level_offset[13];
+  uint64_t bytes;
+} oxc_image_pyramid;
+typedef struct oxc_bloom_context {
+  uint32_t struct_size; /* sizeof(oxc_bloom_context) */
+  uint32_t width, height;
+  uint32_t source_format;       /* 0: B10G11R11 UfloatPack32;  1: R16G16B16A16 Sfloat -- the source and both pyramids */
+  uint32_t scene_flags;         /* only OXC_SCENE_HAS_EYE_ADAPTATION is read */
+  float threshold;              /* pp.bloom_threshold: 1.0 (RendererCVar.cpp:44-48) */
+  float soft_threshold;         /* 0.125 */
+  float clamp_value;            /* 4.0 */
+  float radius;                 /* 0.75 */
+  uint32_t _pad;
+  oxc_buffer final_attachment;  /* in: what oxc_apply_pbr wrote */
+  oxc_buffer exposure_buffer;   /* in, read only with OXC_SCENE_HAS_EYE_ADAPTATION: {f32 adapted_luminance, f32 exposure} */
+  oxc_image_pyramid bloom_downsampled_attachment; /* out: D */
+  oxc_image_pyramid bloom_upsampled_attachment;   /* out: U; level 0 is what the tonemap reads */
+} oxc_bloom_context;
+
+oxc_status oxc_apply_bloom(oxc_ctx* ctx, const oxc_bloom_context* context, void* hip_stream);
 
 /* ---- multi-GPU exchange: one process per GPU, RCCL over xGMI ---------------------------
  * The meshlet-instance array shards by contiguous range and every rank culls its shard on its own; the only

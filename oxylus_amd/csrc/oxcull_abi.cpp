@@ -94,6 +94,7 @@ struct oxc_ctx {
   PassCounters visbuffer_decode_stats;   // OXC_TUNE_VISBUFFER_DECODE_STATS: u32[4]
   PassCounters pbr_apply_stats;          // OXC_TUNE_PBR_APPLY_STATS: u32[9]
   uint32_t eye_adaptation_grid = 0;      // OXC_TUNE_EYE_ADAPTATION_GRID: cap of the histogram kernel's grid in blocks, 0 = uncapped
+  uint32_t bloom_tail_level = 0;         // OXC_TUNE_BLOOM_TAIL_LEVEL: the first level of oxc_apply_bloom's tail kernel, 0 = the library's choice
   void* comm = nullptr;           // ncclComm_t (oxc_comm_init)
   uint32_t comm_rank = 0, comm_world = 0;
   // counter slots
@@ -2073,6 +2074,79 @@ oxc_status oxc_apply_eye_adaptation(oxc_ctx* ctx, const oxc_eye_adaptation_conte
   return OXC_OK;
 }
 
+namespace {
+struct ByteSpan {
+  uintptr_t lo, hi;  // [lo, hi)
+  bool overlaps(const ByteSpan& o) const { return lo < o.hi && o.lo < hi; }
+};
+
+// The pyramid contract of oxc_apply_bloom: the extent and level count, every level aligned to its texel and inside the allocation, no
+// two levels sharing a byte.  `level` receives the byte span of every level.
+oxc_status bloom_pyramid(oxc_ctx* ctx, const char* entry, const oxc_image_pyramid& p, const char* name, uint32_t w2, uint32_t h2, uint32_t levels, uint32_t texel,
+                         ByteSpan* level) {
+  if (p.width != w2 || p.height != h2 || p.levels != levels) return bad_arg(ctx, entry, name, " must have width / 2, height / 2 and floor(log2(max of them)) + 1 levels");
+  const uintptr_t base = reinterpret_cast<uintptr_t>(p.dptr);
+  for (uint32_t k = 0; k < levels; k++) {
+    const uint64_t size = (uint64_t)std::max(1u, w2 >> k) * std::max(1u, h2 >> k) * texel, off = p.level_offset[k];
+    if (!p.dptr || ((base + off) & (texel - 1u)) || off > p.bytes || size > p.bytes - off) return bad_arg(ctx, entry, name, ": every level must be aligned to its texel and lie inside the allocation");
+    level[k] = {base + (uintptr_t)off, base + (uintptr_t)(off + size)};
+  }
+  for (uint32_t k = 1; k < levels; k++)
+    for (uint32_t j = 0; j < k; j++)
+      if (level[k].overlaps(level[j])) return bad_arg(ctx, entry, name, ": two levels overlap");
+  return OXC_OK;
+}
+}  // namespace
+
+oxc_status oxc_apply_bloom(oxc_ctx* ctx, const oxc_bloom_context* c, void* hip_stream) {
+  if (!ctx) return OXC_INVALID_ARG;
+  if (!c || c->struct_size != sizeof(oxc_bloom_context)) return fail(ctx, OXC_INVALID_ARG, "apply_bloom: bad context / struct_size");
+  const char* const entry = "apply_bloom";
+  if (c->width < 2u || c->height < 2u) return bad_arg(ctx, entry, "width and height must be at least 2");
+  const uint32_t w2 = c->width / 2u, h2 = c->height / 2u;
+  if (std::max(w2, h2) >= 8192u) return bad_arg(ctx, entry, "extent too large: max(width, height) / 2 must be below 8192 (13 levels)");
+  uint32_t levels = 0;  // floor(log2(max(w2, h2))) + 1
+  for (uint32_t m = std::max(w2, h2); m; m >>= 1) levels++;
+  if (c->source_format > 1u) return bad_arg(ctx, entry, "source_format must be 0 (B10G11R11) or 1 (R16G16B16A16 Sfloat)");
+  const uint32_t texel = c->source_format ? 8u : 4u;
+  const uint64_t pixels = (uint64_t)c->width * c->height;
+  if (bad_pixel_buffer(c->final_attachment, pixels, texel))
+    return bad_arg(ctx, entry, "final_attachment must be one aligned u32 per pixel (format 0) or one 8-byte aligned u16x4 per pixel (format 1)");
+  ByteSpan down[13], up[13];
+  OXC_TRY(bloom_pyramid(ctx, entry, c->bloom_downsampled_attachment, "bloom_downsampled_attachment", w2, h2, levels, texel, down));
+  OXC_TRY(bloom_pyramid(ctx, entry, c->bloom_upsampled_attachment, "bloom_upsampled_attachment", w2, h2, levels, texel, up));
+  const uintptr_t src_lo = reinterpret_cast<uintptr_t>(c->final_attachment.dptr);
+  const ByteSpan src = {src_lo, src_lo + (uintptr_t)(pixels * texel)};
+  for (uint32_t k = 0; k < levels; k++) {
+    if (down[k].overlaps(src) || up[k].overlaps(src)) return bad_arg(ctx, entry, "the two pyramids and final_attachment must not overlap");
+    for (uint32_t j = 0; j < levels; j++)
+      if (down[k].overlaps(up[j])) return bad_arg(ctx, entry, "the two pyramids and final_attachment must not overlap");
+  }
+  const bool has_exposure = (c->scene_flags & OXC_SCENE_HAS_EYE_ADAPTATION) != 0u;
+  if (has_exposure && bad_pixel_buffer(c->exposure_buffer, 2u, 4u)) return bad_arg(ctx, entry, "exposure_buffer must be two aligned f32");
+  if (!std::isfinite(c->threshold) || !std::isfinite(c->soft_threshold) || !std::isfinite(c->clamp_value) || !std::isfinite(c->radius))
+    return bad_arg(ctx, entry, "threshold, soft_threshold, clamp_value and radius must be finite");
+  OXC_HIP(ctx, hipSetDevice(ctx->device));
+  OXC_ORDER(ctx, hip_stream);
+  const hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  BloomArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.src = c->final_attachment.dptr;
+  a.exposure = has_exposure ? static_cast<const float*>(c->exposure_buffer.dptr) : nullptr;
+  for (uint32_t k = 0; k < levels; k++) {
+    a.down[k] = static_cast<char*>(c->bloom_downsampled_attachment.dptr) + c->bloom_downsampled_attachment.level_offset[k];
+    a.up[k] = static_cast<char*>(c->bloom_upsampled_attachment.dptr) + c->bloom_upsampled_attachment.level_offset[k];
+  }
+  a.w = c->width, a.h = c->height, a.w2 = w2, a.h2 = h2;
+  a.levels = levels;
+  a.tail = ctx->bloom_tail_level ? std::min(std::max(ctx->bloom_tail_level, bloom_lowest_tail(w2, h2, levels)), levels) : bloom_default_tail(w2, h2, levels);
+  a.format = c->source_format;
+  a.threshold = c->threshold, a.soft_threshold = c->soft_threshold, a.clamp_value = c->clamp_value, a.radius = c->radius;
+  launch_bloom(a, s);
+  OXC_HIP(ctx, hipGetLastError());
+  return OXC_OK;
+}
+
 oxc_status oxc_generate_ambient_occlusion(oxc_ctx* ctx, const oxc_ambient_occlusion_context* c, void* hip_stream) {
   if (!ctx) return OXC_INVALID_ARG;
   if (!c || c->struct_size != sizeof(oxc_ambient_occlusion_context)) return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: bad context / struct_size");
@@ -2470,6 +2544,7 @@ oxc_status oxc_debug_set_tuning(oxc_ctx* ctx, uint32_t knob, uint32_t value) {
     case OXC_TUNE_VISBUFFER_DECODE_STATS: ctx->visbuffer_decode_stats.on = value != 0u; return OXC_OK;
     case OXC_TUNE_PBR_APPLY_STATS: ctx->pbr_apply_stats.on = value != 0u; return OXC_OK;
     case OXC_TUNE_EYE_ADAPTATION_GRID: ctx->eye_adaptation_grid = value; return OXC_OK;
+    case OXC_TUNE_BLOOM_TAIL_LEVEL: ctx->bloom_tail_level = value; return OXC_OK;
     case OXC_TUNE_AMBIENT_OCCLUSION_STATS: ctx->ambient_occlusion_stats.on = value != 0u; return OXC_OK;
     case OXC_TUNE_VSM_DRAW_CAPACITY:
       if (ctx->vsm_draw_scratch) return fail(ctx, OXC_INVALID_ARG, "set_tuning: the shadow draw's scratch is allocated by the first oxc_draw_physical_pages; set its capacity before");

@@ -659,6 +659,22 @@ struct EyeAdaptationArgs {
   float time_coeff, ev100_bias;
 };
 void launch_eye_adaptation(const EyeAdaptationArgs& a, uint32_t grid, hipStream_t s);
+// oxcull_bloom.hip: the bloom prefilter and the two mip pyramids (oxc_apply_bloom)
+struct BloomArgs {
+  const void* src;        // W x H texels: u32 (B10G11R11, format 0) or u16x4 (R16G16B16A16 Sfloat, format 1)
+  const float* exposure;  // the exposure buffer's {adapted_luminance, exposure}; nullptr: the exposure is 1.0
+  void* down[13];         // D: level k is max(1, w2 >> k) x max(1, h2 >> k) texels of the source's format
+  void* up[13];           // U
+  uint32_t w, h;          // the source's extent
+  uint32_t w2, h2;        // w / 2, h / 2: the extent of level 0
+  uint32_t levels;        // L
+  uint32_t tail;          // T in 1 .. L: the tail kernel runs downsample levels T .. L - 1 and upsample levels L - 1 .. T; L: no tail kernel
+  uint32_t format;
+  float threshold, soft_threshold, clamp_value, radius;
+};
+uint32_t bloom_default_tail(uint32_t w2, uint32_t h2, uint32_t levels);
+uint32_t bloom_lowest_tail(uint32_t w2, uint32_t h2, uint32_t levels);  // the lowest T OXC_TUNE_BLOOM_TAIL_LEVEL can force
+void launch_bloom(const BloomArgs& a, hipStream_t s);
 // oxcull_bounds.hip: meshlet bounds producer
 void launch_build_meshlet_bounds(const float* pos, uint32_t vertex_count, const void* meshlets, uint32_t meshlet_count, const uint32_t* vidx,
                                  const uint8_t* micro, void* out_bounds, float* out_mesh6, void* out_qpos, float* meshlet_minmax, float* normals,

@@ -27,7 +27,6 @@ namespace oxc {
 namespace {
 constexpr uint32_t kLightChunk = 256;  // lights staged per round: one per thread of the block
 constexpr float kPi = 3.1415926535897932f;
-constexpr uint32_t kHalfNaN = 0x7E00u;
 
 // GPU::Light, scene.slang:272-283
 struct GpuLight {
@@ -75,9 +74,6 @@ OXC_DEV float srgb_decode(uint32_t byte) {
 
 // com::oct_to_vec3 of the two halves of `word` (the first in the low half): one normalisation
 OXC_DEV V3 oct_to_vec3(uint32_t word) { return normalize3(oct_normal_ba(word)); }
-
-// binary16 bits of a channel: round to nearest even, denormals kept, every NaN the one pattern 0x7E00
-OXC_DEV uint32_t channel_half(float x) { return x == x ? (uint32_t)f_to_half(x) : kHalfNaN; }
 
 // what BRDF (pbr.slang:61-87) takes from the pixel alone
 struct Surface {

@@ -29,6 +29,9 @@ OXC_DEV float row1(const float* m, int r, float x, float y, float z) { return ((
 
 // binary32 -> binary16 bits, round to nearest even; the wave's FP16 denormal mode is at its default, so denormal halves are kept
 OXC_DEV unsigned short f_to_half(float x) { return __builtin_bit_cast(unsigned short, (_Float16)x); }
+// binary16 bits of a colour channel: the same, every NaN the one pattern 0x7E00 (oxc_apply_pbr step 12; oxc_apply_bloom stores its RGBA16F
+// levels by it)
+OXC_DEV uint32_t channel_half(float x) { return x == x ? (uint32_t)f_to_half(x) : 0x7E00u; }
 
 // the log2 rule before its rounding: binary64, no contraction
 OXC_DEV double log2_f64(float x) {

@@ -146,10 +146,23 @@ struct PBRContext {
 struct Extent3D {
   uint32_t width = 0, height = 0, depth = 1;
 };
+// A mip pyramid of the final attachment's format in one allocation (oxc_image_pyramid): the stand-in for the two bloom images.
+using ImagePyramid = oxc_image_pyramid;
 struct PostProcessContext {
   float delta_time = 0.0f;
   Extent3D extent = {};
   Buffer final_attachment = {};
+  ImagePyramid bloom_upsampled_attachment = {};  // extent / 2, Texture::calculate_mip_count levels (RendererInstance.cpp:1257-1267); written by apply_bloom
+  float bloom_intensity = 0.0f;                  // set by apply_bloom for the tonemap
+};
+
+// The five pp.bloom_* cvars apply_bloom reads, with the engine's defaults (RendererCVar.cpp:44-48)
+struct BloomCVars {
+  float threshold = 1.0f;
+  float soft_threshold = 0.125f;
+  float radius = 0.75f;
+  float intensity = 0.1f;
+  float clamp = 4.0f;
 };
 
 namespace GPU {
@@ -414,6 +427,28 @@ public:
     c.histogram_buffer = histogram_bin_indices_buffer;
     c.exposure_buffer = prepared_frame.exposure_buffer;
     check(oxc_apply_eye_adaptation(ctx_, &c, stream_));
+  }
+  // RendererInstance::apply_bloom (Passes/PostProcess.cpp:79-203): the prefiltered half-resolution image and its downsample pyramid into
+  // bloom_downsampled_attachment (the reference declares it inside the pass; here caller-owned, of bloom_upsampled_attachment's shape), the
+  // upsample pyramid into context.bloom_upsampled_attachment.  The exposure is read from prepared_frame.exposure_buffer when gpu_scene_flags
+  // has HasEyeAdaptation.  Rules: include/oxcull.h, oxc_apply_bloom.
+  auto apply_bloom(PostProcessContext& context, const BloomCVars& cvar, const ImagePyramid& bloom_downsampled_attachment) -> void {
+    context.bloom_intensity = cvar.intensity;
+    oxc_bloom_context c = {};
+    c.struct_size = sizeof c;
+    c.width = context.extent.width;
+    c.height = context.extent.height;
+    c.source_format = (gpu_scene_flags & OXC_SCENE_TRANSPARENT_BACKGROUND) ? 1u : 0u;
+    c.scene_flags = gpu_scene_flags;
+    c.threshold = cvar.threshold;
+    c.soft_threshold = cvar.soft_threshold;
+    c.clamp_value = cvar.clamp;
+    c.radius = cvar.radius;
+    c.final_attachment = context.final_attachment;
+    c.exposure_buffer = prepared_frame.exposure_buffer;
+    c.bloom_downsampled_attachment = bloom_downsampled_attachment;
+    c.bloom_upsampled_attachment = context.bloom_upsampled_attachment;
+    check(oxc_apply_bloom(ctx_, &c, stream_));
   }
   auto build_meshlet_bounds(oxc_meshlet_bounds_desc desc) -> void {
     desc.struct_size = sizeof desc;

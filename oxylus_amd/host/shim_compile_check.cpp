@@ -75,5 +75,12 @@ int main(int argc, char**) {
   } catch (const std::exception& e) {
     std::printf("expected (no attachments bound): %s\n", e.what());
   }
+  try {  // RendererInstance.cpp:1282: bloom behind the eye adaptation, with the engine's cvar defaults
+    auto post_process_context = PostProcessContext{.extent = {.width = 1920, .height = 1080}, .final_attachment = Buffer{}, .bloom_upsampled_attachment = ImagePyramid{}};
+    self.gpu_scene_flags |= OXC_SCENE_HAS_BLOOM;
+    self.apply_bloom(post_process_context, BloomCVars{}, ImagePyramid{});
+  } catch (const std::exception& e) {
+    std::printf("expected (no attachments bound): %s\n", e.what());
+  }
   return 0;
 }

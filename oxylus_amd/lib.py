@@ -32,11 +32,13 @@ TUNE_VSM_DRAW_STATS, TUNE_VSM_DRAW_CAPACITY, TUNE_VSM_RESOLVE_STATS, TUNE_CONTAC
 TUNE_VISBUFFER_DECODE_STATS = 13
 TUNE_PBR_APPLY_STATS = 14
 TUNE_EYE_ADAPTATION_GRID = 15
+TUNE_BLOOM_TAIL_LEVEL = 16
 
 # GPU::SceneFlags bits oxc_apply_pbr reads (scene.slang:242-256)
 SCENE_HAS_DIRECTIONAL_LIGHT, SCENE_HAS_ATMOSPHERE, SCENE_HAS_CONTACT_SHADOWS, SCENE_HAS_SKY, SCENE_TRANSPARENT_BACKGROUND = 1 << 0, 1 << 1, 1 << 9, 1 << 10, 1 << 11
-SCENE_HAS_EYE_ADAPTATION = 1 << 2  # for callers that mirror RendererInstance.cpp:1278; the library does not read it
-EYE_SOURCE_B10G11R11, EYE_SOURCE_R16G16B16A16 = 0, 1  # oxc_eye_adaptation_context.source_format
+SCENE_HAS_EYE_ADAPTATION = 1 << 2  # RendererInstance.cpp:1278; oxc_apply_eye_adaptation does not read it, oxc_bloom_context.scene_flags does
+EYE_SOURCE_B10G11R11, EYE_SOURCE_R16G16B16A16 = 0, 1  # oxc_eye_adaptation_context.source_format, oxc_bloom_context.source_format
+SCENE_HAS_BLOOM = 1 << 3  # for callers that mirror RendererInstance.cpp:1282; the library does not read it
 LIGHT_KIND_DIRECTIONAL, LIGHT_KIND_POINT, LIGHT_KIND_SPOT = 0, 1, 2  # GPU::LightKind
 
 
@@ -429,6 +431,39 @@ class EyeAdaptationContext(C.Structure):
     ]
 
 
+class ImagePyramid(C.Structure):
+    """oxc_image_pyramid (include/oxcull.h): oxc_image's fields, then the allocation's size."""
+    _fields_ = [
+        ("dptr", C.c_void_p),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("levels", C.c_uint32),
+        ("_pad", C.c_uint32),
+        ("level_offset", C.c_uint64 * 13),
+        ("bytes", C.c_uint64),
+    ]
+
+
+class BloomContext(C.Structure):
+    """oxc_bloom_context (include/oxcull.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("source_format", C.c_uint32),
+        ("scene_flags", C.c_uint32),
+        ("threshold", C.c_float),
+        ("soft_threshold", C.c_float),
+        ("clamp_value", C.c_float),
+        ("radius", C.c_float),
+        ("_pad", C.c_uint32),
+        ("final_attachment", Buffer),
+        ("exposure_buffer", Buffer),
+        ("bloom_downsampled_attachment", ImagePyramid),
+        ("bloom_upsampled_attachment", ImagePyramid),
+    ]
+
+
 # every symbol include/oxcull.h declares
 EXPORTS = [
     "oxc_abi_version",
@@ -465,6 +500,7 @@ EXPORTS = [
     "oxc_apply_pbr",
     "oxc_debug_pbr_apply_stats",
     "oxc_apply_eye_adaptation",
+    "oxc_apply_bloom",
     "oxc_draw_physical_pages",
     "oxc_debug_vsm_draw_stats",
     "oxc_resolve_shadowmap",
@@ -571,6 +607,7 @@ def load(path: str = None) -> C.CDLL:
     lib.oxc_apply_pbr.argtypes = [vp, C.POINTER(PbrContext), vp]
     lib.oxc_debug_pbr_apply_stats.argtypes = [vp, vp, vp]
     lib.oxc_apply_eye_adaptation.argtypes = [vp, C.POINTER(EyeAdaptationContext), vp]
+    lib.oxc_apply_bloom.argtypes = [vp, C.POINTER(BloomContext), vp]
     lib.oxc_draw_physical_pages.argtypes = [vp, C.POINTER(PreparedFrame), C.POINTER(VsmDrawContext), vp]
     lib.oxc_debug_vsm_draw_stats.argtypes = [vp, vp, vp]
     lib.oxc_resolve_shadowmap.argtypes = [vp, C.POINTER(ShadowResolveContext), vp]

@@ -599,6 +599,98 @@ class EyeAdaptationContext:
         return c
 
 
+def bloom_layout(width: int, height: int, source_format: int = L.EYE_SOURCE_B10G11R11, gap_texels: int = 0):
+    """The shape of oxc_apply_bloom's two pyramids for a width x height source: (w2, h2, L, level_offset, total_bytes) with
+    (w2, h2) = (width // 2, height // 2), L = floor(log2(max(w2, h2))) + 1 and level k, max(1, w2 >> k) x max(1, h2 >> k) texels of 4
+    (B10G11R11) or 8 (R16G16B16A16 Sfloat) bytes, at level_offset[k] in one buffer, the levels one behind the other with `gap_texels`
+    unused texels before each.  (Texture::calculate_mip_count and RendererInstance.cpp:509-510.)"""
+    w2, h2 = width // 2, height // 2
+    levels = max(w2, h2, 1).bit_length()
+    texel = 8 if source_format == L.EYE_SOURCE_R16G16B16A16 else 4
+    offsets, at = [], 0
+    for k in range(levels):
+        at += gap_texels * texel
+        offsets.append(at)
+        at += max(1, w2 >> k) * max(1, h2 >> k) * texel
+    return w2, h2, levels, offsets, at + gap_texels * texel
+
+
+@dataclass
+class BloomPyramid:
+    """oxc_image_pyramid: a mip pyramid of B10G11R11 (int32 buffer) or R16G16B16A16 Sfloat (int16 buffer) texels in one 1-D tensor."""
+    data: torch.Tensor
+    width: int
+    height: int
+    levels: int
+    level_offset: list  # bytes
+    source_format: int
+
+    @staticmethod
+    def create(width: int, height: int, source_format: int, device="cuda") -> "BloomPyramid":
+        """The pyramid of a width x height SOURCE image: level 0 is width // 2 x height // 2."""
+        w2, h2, levels, offsets, total = bloom_layout(width, height, source_format)
+        dtype, size = (torch.int16, 2) if source_format == L.EYE_SOURCE_R16G16B16A16 else (torch.int32, 4)
+        return BloomPyramid(torch.zeros(total // size, dtype=dtype, device=device), w2, h2, levels, offsets, source_format)
+
+    def level(self, k: int) -> torch.Tensor:
+        """Level k as a view: int32 [h, w] or int16 [h, w, 4]."""
+        w, h = max(1, self.width >> k), max(1, self.height >> k)
+        per = 4 if self.source_format == L.EYE_SOURCE_R16G16B16A16 else 1
+        first = self.level_offset[k] // self.data.element_size()
+        flat = self.data[first:first + w * h * per]
+        return flat.view(h, w, 4) if per == 4 else flat.view(h, w)
+
+    def c(self) -> L.ImagePyramid:
+        im = L.ImagePyramid()
+        im.dptr = self.data.data_ptr() if self.data is not None else None
+        im.width, im.height, im.levels = int(self.width), int(self.height), int(self.levels)
+        for k, o in enumerate(self.level_offset[:13]):
+            im.level_offset[k] = int(o)
+        im.bytes = self.data.numel() * self.data.element_size() if self.data is not None else 0
+        return im
+
+
+@dataclass
+class BloomContext:
+    """oxc_bloom_context: RendererInstance::apply_bloom (Passes/PostProcess.cpp:79-203).  `create` takes the image apply_pbr wrote -- int32
+    [H, W] (B10G11R11) or int16 [H, W, 4] (R16G16B16A16 Sfloat); the format follows from the shape --, the scene flags (only
+    L.SCENE_HAS_EYE_ADAPTATION is read) and the exposure buffer apply_eye_adaptation left behind, and allocates the two pyramids.
+    bloom_intensity is what apply_bloom hands to the tonemap; the library does not read it."""
+    final_attachment: torch.Tensor                # in
+    exposure_buffer: Optional[torch.Tensor]       # in with SCENE_HAS_EYE_ADAPTATION: float32 [2]
+    bloom_downsampled_attachment: BloomPyramid    # out
+    bloom_upsampled_attachment: BloomPyramid      # out: level 0 is the bloom the tonemap reads
+    width: int
+    height: int
+    source_format: int
+    scene_flags: int = 0
+    threshold: float = 1.0        # the pp.bloom_* defaults, RendererCVar.cpp:44-48
+    soft_threshold: float = 0.125
+    clamp_value: float = 4.0
+    radius: float = 0.75
+    bloom_intensity: float = 0.1
+
+    @staticmethod
+    def create(final_attachment: torch.Tensor, scene_flags: int = 0, exposure: Optional[torch.Tensor] = None, threshold: float = 1.0,
+               soft_threshold: float = 0.125, clamp_value: float = 4.0, radius: float = 0.75, bloom_intensity: float = 0.1) -> "BloomContext":
+        fmt = L.EYE_SOURCE_R16G16B16A16 if final_attachment.dim() == 3 else L.EYE_SOURCE_B10G11R11
+        H, W = int(final_attachment.shape[0]), int(final_attachment.shape[1])
+        dev = final_attachment.device
+        return BloomContext(final_attachment, exposure, BloomPyramid.create(W, H, fmt, dev), BloomPyramid.create(W, H, fmt, dev), W, H, fmt, int(scene_flags),
+                            float(threshold), float(soft_threshold), float(clamp_value), float(radius), float(bloom_intensity))
+
+    def c(self) -> L.BloomContext:
+        c = L.BloomContext()
+        c.struct_size = C.sizeof(L.BloomContext)
+        c.width, c.height, c.source_format, c.scene_flags = int(self.width), int(self.height), int(self.source_format), int(self.scene_flags)
+        c.threshold, c.soft_threshold, c.clamp_value, c.radius = float(self.threshold), float(self.soft_threshold), float(self.clamp_value), float(self.radius)
+        c.final_attachment = _buf(self.final_attachment)
+        c.exposure_buffer = _buf(self.exposure_buffer)
+        c.bloom_downsampled_attachment = self.bloom_downsampled_attachment.c()
+        c.bloom_upsampled_attachment = self.bloom_upsampled_attachment.c()
+        return c
+
+
 @dataclass
 class VisbufferDecodeContext:
     """oxc_decode_context: RendererInstance::decode_visbuffer (Passes/DrawGeometry.cpp:192-274), the geometry and material-factor half of
@@ -889,6 +981,14 @@ class RendererInstance:
         c = context.c(delta_time)
         self._keep = context
         self._check(self._lib.oxc_apply_eye_adaptation(self._ctx, C.byref(c), self._stream(stream)))
+
+    def apply_bloom(self, context: BloomContext, stream=None):
+        """Passes/PostProcess.cpp:79-203: the thresholded half-resolution image and its downsample pyramid into
+        `context.bloom_downsampled_attachment`, the upsample pyramid into `context.bloom_upsampled_attachment` (include/oxcull.h,
+        oxc_apply_bloom).  The exposure is the second word of `context.exposure_buffer` with L.SCENE_HAS_EYE_ADAPTATION, else 1."""
+        c = context.c()
+        self._keep = context
+        self._check(self._lib.oxc_apply_bloom(self._ctx, C.byref(c), self._stream(stream)))
 
     def debug_pbr_apply_stats(self, stream=None) -> dict:
         """What the last apply_pbr did, after debug_set_tuning(L.TUNE_PBR_APPLY_STATS, 1) (measurement hook; synchronises)."""
