@@ -7,8 +7,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from contact_shadows_model import cvt_i32_sat, cvt_u32_sat, sign
-from vsm_resolve_model import cos_sin_turn, cross, dot, length, normalize, oct_to_vec3
+from pixel_rules import (cos_sin_turn, cvt_i32_sat, cvt_u32_sat, dot, f32a, from_half_bits, length, log2_rule, normalize, oct_to_vec3, pack_unorm4x8, pow_rule,
+                         saturate, sign, to_half_bits)
 
 F = np.float32
 HALF_PI, PI = F(1.57079632679), F(3.1415926535897932384626433832795)
@@ -18,74 +18,13 @@ PIXEL_TOO_CLOSE = F(1.3)
 MIP_OFFSET = F(3.30)
 R2 = (F(0.75487766624669276005), F(0.5698402909980532659114))
 GOLDEN = F(0.6180339887498948482)
-SQRT2_F = F(1.41421356)
-INV_LN2 = float.fromhex("0x1.71547652b82fep+0")
-LN2 = float.fromhex("0x1.62e42fefa39efp-1")
-LOG_C = [1.0 / k for k in (3.0, 5.0, 7.0, 9.0, 11.0, 13.0, 15.0, 17.0)]  # the binary64 quotients
-EXP_C = [1.0, 1.0, 1.0 / 2.0, 1.0 / 6.0, 1.0 / 24.0, 1.0 / 120.0, 1.0 / 720.0, 1.0 / 5040.0, 1.0 / 40320.0, 1.0 / 362880.0, 1.0 / 3628800.0,
-         1.0 / 39916800.0, 1.0 / 479001600.0, 1.0 / 6227020800.0]
 COUNTER_NAMES = ("non_sky_pixels", "samples", "mip0", "mip1", "mip2", "mip3", "mip4", "fractional", "result_one", "result_partial", "result_zero",
                  "zero_width", "sign_minus", "sign_zero", "sign_plus")
 PRESETS = {"low": (1, 2), "medium": (2, 2), "high": (3, 3), "ultra": (9, 3)}  # slice_count, samples_per_slice_side
 
 
-def f32a(v) -> np.ndarray:
-    return np.asarray(v, dtype=np.float32)
-
-
-def saturate(x):
-    """min(max(x, 0), 1): a NaN gives 0."""
-    return np.fmin(np.fmax(f32a(x), F(0.0)), F(1.0))
-
-
 def frac(x):
     return x - np.floor(x)
-
-
-# ---- log2 and pow ---------------------------------------------------------------------------------------------------------------------------
-@np.errstate(all="ignore")
-def log2_f64(x) -> np.ndarray:
-    """The binary64 value of the log2 rule before its rounding, for binary32 x.  x < 2^-126 (zero, denormal, negative) or NaN: -Inf;
-    +Inf: +Inf."""
-    x = np.atleast_1d(f32a(x))
-    bits = x.view(np.uint32)
-    e = ((bits >> np.uint32(23)) & np.uint32(0xFF)).astype(np.int64) - 127
-    m = ((bits & np.uint32(0x7FFFFF)) | np.uint32(0x3F800000)).view(np.float32)  # in [1, 2)
-    big = m > SQRT2_F
-    m = np.where(big, m * F(0.5), m)  # exact
-    e = e + big
-    f = m.astype(np.float64) - 1.0
-    s = f / (2.0 + f)
-    z = s * s
-    p = LOG_C[7]
-    for c in LOG_C[6::-1]:
-        p = p * z + c
-    p = p * z + 1.0
-    r = e.astype(np.float64) + ((2.0 * s) * p) * INV_LN2
-    r = np.where(x >= F(2.0 ** -126), r, -np.inf)
-    return np.where(x == F(np.inf), np.inf, r)
-
-
-def log2_rule(x) -> np.ndarray:
-    return log2_f64(x).astype(np.float32)
-
-
-@np.errstate(all="ignore")
-def pow_rule(v, p) -> np.ndarray:
-    """pow(v, p) for binary32 v >= 0 (the caller's max(.., 0) has run) and p > 0: exp2(p * log2(v)) in binary64, rounded once."""
-    v = np.atleast_1d(f32a(v))
-    y = np.float64(F(p)) * log2_f64(v)
-    k = np.floor(y + 0.5)
-    r = y - k
-    t = r * LN2
-    q = EXP_C[13]
-    for c in EXP_C[12::-1]:
-        q = q * t + c
-    ki = np.where(np.isfinite(k), np.clip(k, -160, 160), 0).astype(np.int64)
-    scale = ((ki + 1023).astype(np.uint64) << np.uint64(52)).view(np.float64)
-    res = (q * scale).astype(np.float32)
-    res = np.where(y <= -160.0, F(0.0), np.where(y >= 160.0, F(np.inf), res))
-    return np.where(np.isnan(y), F(np.nan), res).astype(np.float32)
 
 
 # ---- small rules ----------------------------------------------------------------------------------------------------------------------------
@@ -98,28 +37,9 @@ def fast_acos(x):
     return np.where(x >= 0, res, PI - res).astype(np.float32)
 
 
-@np.errstate(all="ignore")
-def pack_unorm4x8(e0, e1, e2, e3) -> np.ndarray:
-    """byte k = u32(floor(saturate(e_k) * 255.0 + 0.5)), component 0 in the low byte."""
-    out = np.zeros(np.shape(e0), dtype=np.uint32)
-    for k, e in enumerate((e0, e1, e2, e3)):
-        out |= cvt_u32_sat(np.floor(saturate(e) * F(255.0) + F(0.5))).astype(np.uint32) << np.uint32(8 * k)
-    return out
-
-
 def unpack_unorm4x8(w):
     w = np.asarray(w, dtype=np.uint32)
     return tuple(((w >> np.uint32(8 * k)) & np.uint32(0xFF)).astype(np.float32) / F(255.0) for k in range(4))
-
-
-def to_half_bits(x) -> np.ndarray:
-    """binary32 -> binary16, round to nearest even, denormals kept."""
-    with np.errstate(all="ignore"):
-        return f32a(x).astype(np.float16).view(np.uint16)
-
-
-def from_half_bits(h) -> np.ndarray:
-    return np.asarray(h, dtype=np.uint16).view(np.float16).astype(np.float32)
 
 
 def noise_pair(entry, noise_index):

@@ -5,10 +5,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from ambient_occlusion_model import from_half_bits
-from contact_shadows_model import cvt_i32_sat
-from pbr_apply_model import channel_half, pack_b10g11r11, unpack_b10g11r11
-from visbuffer_decode_model import pack_ufloat  # noqa: F401  (the pack the B10G11R11 store goes through; the tests name it)
+from pixel_rules import channel_half, cvt_i32_sat, f32a, from_half_bits, pack_b10g11r11, unpack_b10g11r11
+from pixel_rules import pack_ufloat  # noqa: F401  (the pack the B10G11R11 store goes through; the tests name it)
 
 F = np.float32
 FORMAT_B10G11R11, FORMAT_R16G16B16A16 = 0, 1
@@ -18,10 +16,6 @@ HALF_ONE = 0x3C00
 TAPS13 = dict(a=(-2, 2), b=(0, 2), c=(2, 2), d=(-2, 0), e=(0, 0), f=(2, 0), g=(-2, -2), h=(0, -2), i=(2, -2), j=(-1, 1), k=(1, 1), l=(-1, -1), m=(1, -1))
 # bloom_upsample.slang:31-39
 TAPS9 = dict(a=(-1, 1), b=(0, 1), c=(1, 1), d=(-1, 0), e=(0, 0), f=(1, 0), g=(-1, -1), h=(0, -1), i=(1, -1))
-
-
-def f32a(v) -> np.ndarray:
-    return np.asarray(v, dtype=np.float32)
 
 
 # ---- geometry ------------------------------------------------------------------------------------------------------------------------------------

@@ -6,6 +6,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from pixel_rules import cvt_i32_sat, cvt_u32_sat, f32a, sign
+
 F = np.float32
 BIAS_SCALE = F(1.0) + F(0.000002)  # rule 6: rounded to binary32 once
 EDGE_SPAN = F(0.3) - F(1.0)        # rule 7: smoothstep's edge1 - edge0
@@ -15,21 +17,6 @@ SKY, MISS, HIT_ZERO, HIT_PARTIAL, HIT_ONE, REJECTED = 0, 1, 2, 3, 4, 5
 N_LOWER, N_BETWEEN, N_UPPER = 0, 1, 2
 COUNTER_NAMES = ("non_sky_pixels", "taps", "miss", "hit_zero", "hit_partial", "hit_one", "rejected", "n_lower", "n_between", "n_upper", "end_clip",
                  "start_moved")
-
-
-def f32a(v) -> np.ndarray:
-    return np.asarray(v, dtype=np.float32)
-
-
-def cvt_i32_sat(v) -> np.ndarray:
-    """float -> i32, saturating, NaN -> 0 (truncation inside the range; every caller passes a floor)."""
-    v = np.asarray(v, dtype=np.float64)
-    return np.where(np.isnan(v), 0.0, np.clip(v, -2147483648.0, 2147483647.0)).astype(np.int64)
-
-
-def cvt_u32_sat(v) -> np.ndarray:
-    v = np.asarray(v, dtype=np.float64)
-    return np.where(np.isnan(v), 0.0, np.clip(v, 0.0, 4294967295.0)).astype(np.int64)
 
 
 def mul_point(m, x, y, z):
@@ -42,11 +29,6 @@ def mul_vec4(m, x, y, z, w):
     """mul(M, (x, y, z, w)): ((M[r][0] x + M[r][1] y) + M[r][2] z) + M[r][3] w."""
     m = f32a(m)
     return tuple(((m[0 + r] * x + m[4 + r] * y) + m[8 + r] * z) + m[12 + r] * w for r in range(4))
-
-
-def sign(a):
-    a = f32a(a)
-    return np.where(a > 0, F(1.0), np.where(a < 0, F(-1.0), F(0.0))).astype(np.float32)
 
 
 def ray_vector(sun_dir, shadow_length):

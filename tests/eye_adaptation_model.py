@@ -5,19 +5,13 @@ from __future__ import annotations
 
 import numpy as np
 
-from ambient_occlusion_model import from_half_bits, log2_rule
-from contact_shadows_model import cvt_i32_sat
-from pbr_apply_model import exp2_rule, unpack_b10g11r11
+from pixel_rules import cvt_i32_sat, exp2_rule, f32a, from_half_bits, log2_rule, unpack_b10g11r11
 
 F = np.float32
 BINS = 256
 LUMINANCE_EPSILON = F(0.001)
 QUIET_NAN = np.uint32(0x7FC00000)
 FORMAT_B10G11R11, FORMAT_R16G16B16A16 = 0, 1
-
-
-def f32a(v) -> np.ndarray:
-    return np.asarray(v, dtype=np.float32)
 
 
 def decode(image, source_format: int):

@@ -6,9 +6,9 @@ from __future__ import annotations
 
 import numpy as np
 
-from ambient_occlusion_model import EXP_C, LN2, from_half_bits, log2_f64, saturate, to_half_bits
-from visbuffer_decode_model import pack_ufloat
-from vsm_resolve_model import COS_C, SIN_C, dot, normalize, oct_to_vec3
+from pixel_rules import (COS_C, SIN_C, channel_half, dot, exp2_rule, f32a, from_half_bits, normalize, oct_to_vec3, pack_b10g11r11, pow_rule, saturate,
+                         unpack_b10g11r11)
+from pixel_rules import unpack_ufloat  # noqa: F401  (the decode behind unpack_b10g11r11; the tests name it)
 
 F = np.float32
 HAS_DIRECTIONAL_LIGHT, HAS_ATMOSPHERE, HAS_CONTACT_SHADOWS, HAS_SKY, TRANSPARENT_BACKGROUND = 1 << 0, 1 << 1, 1 << 9, 1 << 10, 1 << 11
@@ -16,7 +16,6 @@ KIND_DIRECTIONAL, KIND_POINT, KIND_SPOT = 0, 1, 2
 PI = F(3.1415926535897932)
 FD_LAMBERT = F(1.0) / PI
 MIN_ALPHA = F(0.0025)
-HALF_NAN = 0x7E00
 TWO_OVER_PI = float.fromhex("0x1.45f306dc9c883p-1")
 PIO2_HI = float.fromhex("0x1.921fb54p+0")          # pi / 2 to 29 significant bits
 PIO2_LO = float.fromhex("0x1.10b4611a62633p-30")   # the rest
@@ -29,38 +28,7 @@ COUNTER_NAMES = ("transparent_empty", "sky", "fallthrough_empty", "lit_nol_posit
 LIGHT_FIELDS = dict(position=slice(0, 3), intensity=3, color=slice(4, 7), range=7, direction=slice(8, 11), inner_cone_angle=11, outer_cone_angle=12)
 
 
-def f32a(v) -> np.ndarray:
-    return np.asarray(v, dtype=np.float32)
-
-
 # ---- the closed forms ------------------------------------------------------------------------------------------------------------------------
-@np.errstate(all="ignore")
-def exp2_f64_round(y) -> np.ndarray:
-    """exp2 of a binary64 y rounded to binary32 once: the second half of the pow rule."""
-    y = np.atleast_1d(np.asarray(y, dtype=np.float64))
-    k = np.floor(y + 0.5)
-    r = y - k
-    t = r * LN2
-    q = EXP_C[13]
-    for c in EXP_C[12::-1]:
-        q = q * t + c
-    ki = np.where(np.isfinite(k), np.clip(k, -160, 160), 0).astype(np.int64)
-    scale = ((ki + 1023).astype(np.uint64) << np.uint64(52)).view(np.float64)
-    res = (q * scale).astype(np.float32)
-    res = np.where(y <= -160.0, F(0.0), np.where(y >= 160.0, F(np.inf), res))
-    return np.where(np.isnan(y), F(np.nan), res).astype(np.float32)
-
-
-def exp2_rule(t) -> np.ndarray:
-    return exp2_f64_round(np.atleast_1d(f32a(t)).astype(np.float64))
-
-
-@np.errstate(all="ignore")
-def pow_rule(v, p) -> np.ndarray:
-    """The pow rule with the exponent a binary32 array or scalar: exp2((double)p * L(v))."""
-    return exp2_f64_round(np.atleast_1d(f32a(p)).astype(np.float64) * log2_f64(v))
-
-
 @np.errstate(all="ignore")
 def cos_rule(x) -> np.ndarray:
     """The cos rule: two-constant reduction, the polynomials of the rotation rule, one rounding; NaN beyond 2^24 and for non-finite x."""
@@ -85,29 +53,6 @@ def cos_rule(x) -> np.ndarray:
 def srgb_decode(byte) -> np.ndarray:
     c = np.atleast_1d(np.asarray(byte)).astype(np.float32) / F(255.0)
     return np.where(c <= F(0.04045), c / F(12.92), pow_rule((c + F(0.055)) / F(1.055), F(2.4))).astype(np.float32)
-
-
-def unpack_ufloat(v, mbits: int) -> np.ndarray:
-    """The unsigned small float with 5 exponent bits and `mbits` mantissa bits -> binary32, exact."""
-    v = np.atleast_1d(np.asarray(v)).astype(np.uint32)
-    e, m = v >> np.uint32(mbits), v & np.uint32((1 << mbits) - 1)
-    normal = (((e + np.uint32(112)) << np.uint32(23)) | (m << np.uint32(23 - mbits))).astype(np.uint32).view(np.float32)
-    out = np.where(e == 0, m.astype(np.float32) * F(2.0 ** -(14 + mbits)), normal)
-    return np.where(e == 31, np.where(m != 0, F(np.nan), F(np.inf)), out).astype(np.float32)
-
-
-def unpack_b10g11r11(w):
-    w = np.asarray(w).astype(np.uint32)
-    return unpack_ufloat(w & np.uint32(0x7FF), 6), unpack_ufloat((w >> np.uint32(11)) & np.uint32(0x7FF), 6), unpack_ufloat(w >> np.uint32(22), 5)
-
-
-def pack_b10g11r11(r, g, b) -> np.ndarray:
-    return pack_ufloat(r, 6) | (pack_ufloat(g, 6) << np.uint32(11)) | (pack_ufloat(b, 5) << np.uint32(22))
-
-
-def channel_half(x) -> np.ndarray:
-    x = f32a(x)
-    return np.where(np.isnan(x), np.uint16(HALF_NAN), to_half_bits(x)).astype(np.uint16)
 
 
 def clamp(x, lo, hi):

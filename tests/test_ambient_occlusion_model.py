@@ -8,52 +8,14 @@ import pytest
 
 import ambient_occlusion_model as AM
 import vsm_resolve_model as RM
-from test_contact_shadows_model import I16, identity_camera, main_frame_depth_from_the_oracle
+from scenes import AO_MAIN as MAIN
+from scenes import AO_MAIN_SIZE as MAIN_SIZE
+from scenes import I16, PROJ
+from scenes import ao_assert_not_degenerate as assert_not_degenerate
+from scenes import ao_main_frame_inputs as main_frame_inputs
+from scenes import flat_normals, hilbert, pit_image
 
 F = np.float32
-
-# ---- the main GPU frame (tests/test_gpu_ambient_occlusion.py draws the same scene with oxc_draw_visbuffer) ---------------------------------
-MAIN_SIZE, MAIN_SEED = 512, 61  # 512 x 512: the checker takes a few seconds per preset there, and the radius below still reaches mip 4
-MAIN = dict(thickness=0.25, effect_radius=3.0, noise_index=0, final_power=2.2)
-# every class the scene can produce; an exactly-0.0 pixel and a zero sign_norm cannot come from it (see test_a_fully_occluded_pixel_is_exactly_zero
-# and the non-finite GPU test)
-FLOORS = dict(non_sky_pixels=10000, mip0=1000, mip1=1000, mip2=1000, mip3=1000, mip4=100, fractional=1000, result_one=100, result_partial=1000,
-              zero_width=1000, sign_minus=1000, sign_plus=1000)
-
-
-def assert_not_degenerate(st) -> dict:
-    c = AM.counters(st)
-    for name, floor in FLOORS.items():
-        assert c[name] >= floor, (name, c)
-    return c
-
-
-def far_clip_of(proj) -> float:
-    """far of perspective_reversed_z from its two z entries: m32 / m22 = (far * near / (far - near)) / (near / (far - near))."""
-    return float(np.float64(proj[14]) / np.float64(proj[10]))
-
-
-def camera_of(scene):
-    inv, view, proj, _ = identity_camera(scene)
-    return inv, view, proj, far_clip_of(proj)
-
-
-def flat_normals(H, W, n=(0.0, 0.0, 1.0)):
-    """A u16x4 image whose .ba hold vec3_to_oct(n)."""
-    e = RM.vec3_to_oct(tuple(F(v) for v in n))
-    img = np.zeros((H, W, 4), dtype=np.float16)
-    img[..., 2], img[..., 3] = e[0], e[1]
-    return img.view(np.uint16)
-
-
-def hilbert():
-    from oxylus_amd.synth import hilbert_noise_lut
-
-    return hilbert_noise_lut().numpy().view(np.uint16)
-
-
-PROJ = np.zeros(16, dtype=np.float32)
-PROJ[0], PROJ[5], PROJ[10], PROJ[11], PROJ[14] = 1.0, -1.0, 0.0, -1.0, 1.0  # linear = 1 / device depth
 
 
 # ---- prefilter -----------------------------------------------------------------------------------------------------------------------------
@@ -241,13 +203,6 @@ def test_denoise_of_a_constant_image_with_all_edges_open():
     assert (AM.denoise(np.full((5, 7), 0x3800, dtype=np.uint16), edges, 2.0) == 0x3400).all()  # 0.25
 
 
-def pit_image():
-    """33 x 33 at linear depth 1 with a one-pixel pit of linear depth 1000 in the exact middle (uv = 0.5: view_dir = (0, 0, 1) = the normal)."""
-    d = np.full((33, 33), 1.0, dtype=np.float32)
-    d[16, 16] = 0.001
-    return d, dict(far=1e6, thickness=1e6, effect_radius=2000.0, slice_count=9, samples_per_slice_side=3)
-
-
 def test_a_fully_occluded_pixel_is_exactly_zero():
     """The class the drawn scene cannot produce.  From the bottom of the pit every sample (at least 1.3 pixels away, and the pit's weight in
     the upper mips is 0) lands hundreds of units nearer to the camera and at most a few units to the side: the front horizon is within 0.01 of
@@ -273,22 +228,6 @@ def test_non_finite_texels_and_normals_stay_finite_in_the_output():
 
 
 # ---- the GPU fixture is not degenerate -----------------------------------------------------------------------------------------------------
-def main_frame_inputs():
-    import torch
-
-    from oxylus_amd.synth import normals_from_depth
-
-    import test_contact_shadows_model as TC
-
-    saved = TC.MAIN_SIZE
-    TC.MAIN_SIZE = MAIN_SIZE
-    try:
-        s, depth = main_frame_depth_from_the_oracle()
-    finally:
-        TC.MAIN_SIZE = saved
-    inv, view, proj, far = camera_of(s)
-    normal = normals_from_depth(torch.from_numpy(depth), inv, (0.0, 0.0, 0.0)).numpy()
-    return depth, normal, view, proj, far
 
 
 def test_the_main_gpu_frame_is_not_degenerate():

@@ -8,35 +8,14 @@ import numpy as np
 import pytest
 
 import contact_shadows_model as CM
+from scenes import CS_MAIN as MAIN
+from scenes import CS_MAIN_SIZE as MAIN_SIZE
+from scenes import CS_SUN as SUN
+from scenes import I16
+from scenes import cs_assert_not_degenerate as assert_not_degenerate
+from scenes import identity_camera, main_frame_depth_from_the_oracle
 
 F = np.float32
-I16 = np.eye(4, dtype=np.float32).reshape(-1)
-
-# ---- the main GPU frame (tests/test_gpu_contact_shadows.py draws the same scene with oxc_draw_visbuffer) -----------------------------------
-MAIN_SIZE, MAIN_SEED = 768, 61
-MAIN = dict(steps=12, thickness=0.3, shadow_length=0.15)
-SUN = np.array([0.35, 0.8, 0.5]) / np.linalg.norm([0.35, 0.8, 0.5])
-FLOORS = dict(sky=1000, miss=1000, hit_zero=1000, hit_partial=1000, rejected=1000, n_lower=1000, n_between=1000, n_upper=1000, end_clip=100)
-
-
-def class_counts(st) -> dict:
-    c = CM.counters(st)
-    c["sky"] = int((st["outcome"] == CM.SKY).sum())
-    return c
-
-
-def assert_not_degenerate(st) -> dict:
-    c = class_counts(st)
-    for name, floor in FLOORS.items():
-        assert c[name] >= floor, (name, c)
-    return c
-
-
-def identity_camera(scene):
-    """(inv_projection_view, view, projection, near_clip) of a synth scene: its camera sits at the origin and looks down -z."""
-    proj = np.asarray([float(v) for v in scene.camera["projection_view"]], dtype=np.float32)
-    inv = np.linalg.inv(proj.astype(np.float64).reshape(4, 4).T).T.reshape(-1).astype(np.float32)
-    return inv, I16.copy(), proj, float(scene.camera["near_clip"])
 
 
 def plane(W, H, d):
@@ -257,19 +236,6 @@ def test_a_rotated_view_is_the_same_frame_with_the_sun_rotated():
 
 
 # ---- the GPU fixture is not degenerate -------------------------------------------------------------------------------------------------------
-def main_frame_depth_from_the_oracle():
-    """The main GPU frame's scene (tests/test_gpu_vsm_resolve.py::occluder_scene) drawn by the CPU oracle's visbuffer draw, every triangle."""
-    import torch
-
-    import oracle
-    from test_gpu_vsm_resolve import occluder_scene
-
-    s = occluder_scene(MAIN_SEED)
-    ml = s.meshlet_instances[:, 1].long()
-    idx = torch.tensor([(i << 8) | c for i, m in enumerate(ml.tolist()) for c in range(3 * int(s.meshlets[m, 3]))], dtype=torch.int64).to(torch.int32)
-    vd = torch.zeros((MAIN_SIZE, MAIN_SIZE), dtype=torch.int64)
-    oracle.draw_visbuffer(s, s.meshlet_instances, idx, [float(x) for x in s.camera["projection_view"]], MAIN_SIZE, MAIN_SIZE, vd)
-    return s, oracle.resolve_visbuffer(vd)[0].numpy()
 
 
 def test_the_main_gpu_frame_is_not_degenerate():

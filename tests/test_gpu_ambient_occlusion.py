@@ -7,53 +7,19 @@ import pytest
 import torch
 
 import ambient_occlusion_model as AM
-from test_ambient_occlusion_model import MAIN, MAIN_SEED, MAIN_SIZE, PROJ, assert_not_degenerate, camera_of, far_clip_of, flat_normals, pit_image
-from test_contact_shadows_model import I16
-from test_gpu_contact_shadows import drawn_depth, rotated_camera
+from gpu_passes import Frame
+from gpu_passes import ao_check as check
+from gpu_passes import ao_context as context
+from gpu_passes import ao_got_of as got_of
+from gpu_passes import contact_check, contact_context, contact_got_of, drawn_depth, same
+from scenes import AO_MAIN as MAIN
+from scenes import AO_MAIN_SEED as MAIN_SEED
+from scenes import AO_MAIN_SIZE as MAIN_SIZE
+from scenes import I16, PROJ
+from scenes import ao_assert_not_degenerate as assert_not_degenerate
+from scenes import camera_of, far_clip_of, flat_normals, identity_camera, pit_image, rotated_camera
 
 pytestmark = pytest.mark.gpu
-
-
-def hilbert_gpu():
-    from oxylus_amd.synth import hilbert_noise_lut
-
-    return hilbert_noise_lut().cuda()
-
-
-def context(depth, normal, view, proj, far, **kw):
-    from oxylus_amd.renderer import AmbientOcclusionContext
-
-    return AmbientOcclusionContext.create(depth, normal, hilbert_gpu(), view, proj, far, **kw)
-
-
-def got_of(ctx) -> dict:
-    torch.cuda.synchronize()
-    u16 = lambda t: t.cpu().numpy().view(np.uint16).copy()  # noqa: E731
-    return {"levels": [ctx.prefiltered_depth.level(k).cpu().numpy().copy() for k in range(5)],
-            "depth_differences": ctx.depth_differences.cpu().numpy().view(np.uint32).copy(), "noisy_occlusion": u16(ctx.noisy_occlusion),
-            "ambient_occlusion": u16(ctx.ambient_occlusion_attachment)}
-
-
-def want_of(ctx, stats=None) -> dict:
-    d = ctx.depth_attachment
-    return AM.generate(d.data.view(d.height, d.width).cpu().numpy(), ctx.normal_attachment.cpu().numpy(), ctx.hilbert_noise.cpu().numpy().view(np.uint16),
-                       ctx.view, ctx.projection, ctx.resolution, ctx.far_clip, ctx.thickness, ctx.slice_count, ctx.samples_per_slice_side,
-                       ctx.effect_radius, ctx.noise_index, ctx.final_power, stats=stats)
-
-
-def same(got: dict, want: dict):
-    for k in range(5):
-        bad = int((got["levels"][k].view(np.uint32) != want["levels"][k].view(np.uint32)).sum())
-        assert bad == 0, f"prefiltered level {k}: {bad} of {got['levels'][k].size} texels differ"
-    for name in ("depth_differences", "noisy_occlusion", "ambient_occlusion"):
-        bad = int((got[name] != want[name]).sum())
-        assert bad == 0, f"{name}: {bad} of {got[name].size} pixels differ"
-
-
-def check(ctx, stats=None) -> dict:
-    got = got_of(ctx)
-    same(got, want_of(ctx, stats))
-    return got
 
 
 def main_frame(renderer, size=MAIN_SIZE, seed=MAIN_SEED):
@@ -164,11 +130,6 @@ def test_the_pit_reaches_exactly_zero(renderer):
 
 def test_resolve_contact_shadows_and_ambient_occlusion_in_one_graph(renderer):
     from oxylus_amd.synth import normals_from_depth
-    from test_gpu_contact_shadows import check as check_contact
-    from test_gpu_contact_shadows import context as contact_context
-    from test_gpu_contact_shadows import got_of as contact_got
-    from test_contact_shadows_model import identity_camera
-    from test_gpu_vsm_resolve import Frame
 
     f = Frame(renderer, 320, 320, seed=66)
     f.shadow_path()  # eager; every scratch grows here
@@ -178,7 +139,7 @@ def test_resolve_contact_shadows_and_ambient_occlusion_in_one_graph(renderer):
     renderer.contact_shadows(cctx)
     renderer.generate_ambient_occlusion(actx)
     resolved = f.check()
-    contact = check_contact(cctx)
+    contact = contact_check(cctx)
     ao = check(actx)
     torch.cuda.synchronize()
     s = torch.cuda.Stream()
@@ -195,7 +156,7 @@ def test_resolve_contact_shadows_and_ambient_occlusion_in_one_graph(renderer):
         torch.cuda.synchronize()
         g.replay()
         assert np.array_equal(f.got().view(np.uint32), resolved.view(np.uint32))
-        assert np.array_equal(contact_got(cctx).view(np.uint32), contact.view(np.uint32))
+        assert np.array_equal(contact_got_of(cctx).view(np.uint32), contact.view(np.uint32))
         same(got_of(actx), ao)
 
 

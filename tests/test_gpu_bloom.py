@@ -9,6 +9,9 @@ import pytest
 import torch
 
 import bloom_model as BM
+from gpu_passes import ALL_FLAGS, EYE_COMPONENT, ONE_ONE, DrawnFrame, eye_context, eye_want_of, lights_tensor, words_tensor
+from pbr_apply_model import TRANSPARENT_BACKGROUND
+from pixel_rules import pack_b10g11r11
 
 pytestmark = pytest.mark.gpu
 
@@ -76,10 +79,6 @@ class Pyramid:
         assert bad.size == 0, f"{label}: {bad.size} words differ, the first at byte {4 * int(bad[0])} (levels at {self.offsets}): 0x{int(got[bad[0]]):08X} != 0x{int(want[bad[0]]):08X}"
 
 
-def words_tensor(words) -> torch.Tensor:
-    return torch.from_numpy(np.asarray(words, dtype=np.uint32).view(np.float32).copy()).cuda()
-
-
 def run_and_check(r, image: np.ndarray, fmt: int, label, exposure_words=None, tails=(TAIL_DEFAULT,), shift=1, gap=3, **params):
     """The call on `image` for every tail setting, both pyramids and the source between guard bands; `exposure_words` switches HasEyeAdaptation
     on.  Returns the checker's (D, U)."""
@@ -110,8 +109,6 @@ def run_and_check(r, image: np.ndarray, fmt: int, label, exposure_words=None, ta
 
 
 def pack_image(r, g, b, fmt) -> np.ndarray:
-    from pbr_apply_model import pack_b10g11r11
-
     if fmt == 0:
         return pack_b10g11r11(r.reshape(-1), g.reshape(-1), b.reshape(-1)).astype(np.uint32).reshape(r.shape)
     with np.errstate(over="ignore"):
@@ -128,23 +125,20 @@ def random_image(W, H, fmt, seed, lo=-6.0, hi=4.0) -> np.ndarray:
 # ---- 1. the drawn frame ---------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("eye", [False, True], ids=["unit-exposure", "eye-adaptation"])
 @FORMATS
-def test_drawn_frame(renderer, monkeypatch, fmt, eye):
+def test_drawn_frame(renderer, fmt, eye):
     """The 192 x 192 frame drawn, decoded, resolved, occluded and lit by the library's own passes under four lights; with HasEyeAdaptation the
     exposure is what oxc_apply_eye_adaptation left in its buffer."""
-    import test_gpu_eye_adaptation as GE
-    import test_gpu_pbr_apply as GP
-
-    frame = GP.DrawnFrame(renderer, monkeypatch)
+    frame = DrawnFrame(renderer)
     frame.passes()
-    pbr = frame.pbr(GP.ALL_FLAGS | (GP.TRANSPARENT_BACKGROUND if fmt else 0), GP.lights_tensor(frame.four_lights()))
+    pbr = frame.pbr(ALL_FLAGS | (TRANSPARENT_BACKGROUND if fmt else 0), lights_tensor(frame.four_lights()))
     renderer.apply_pbr(pbr)
     words = None
     if eye:
-        ectx = GE.make_context(pbr.final_attachment, GE.words_tensor(GE.ONE_ONE), time_coeff=0.25, settings=GE.COMPONENT)
+        ectx = eye_context(pbr.final_attachment, words_tensor(ONE_ONE), time_coeff=0.25, settings=EYE_COMPONENT)
         renderer.apply_eye_adaptation(ectx)
         torch.cuda.synchronize()
         words = ectx.exposure_buffer.cpu().numpy().view(np.uint32).copy()
-        assert words.tolist() == GE.want_of(ectx, GE.ONE_ONE)[1].tolist() and words[1] != 0x3F800000
+        assert words.tolist() == eye_want_of(ectx, ONE_ONE)[1].tolist() and words[1] != 0x3F800000
     torch.cuda.synchronize()
     image = pbr.final_attachment.cpu().numpy()
     image = image.view(np.uint16) if fmt else image.view(np.uint32)
@@ -319,27 +313,25 @@ def test_interleaved_pyramids_in_one_allocation(renderer, fmt):
 
 
 # ---- 4. all eight passes in one captured graph ------------------------------------------------------------------------------------------------------
-def test_eight_passes_in_one_graph(renderer, monkeypatch):
+def test_eight_passes_in_one_graph(renderer):
     """Draw -> decode -> resolve -> contact shadows -> ambient occlusion -> apply -> eye adaptation -> bloom captured into one graph on one
     stream and replayed three times with the lights changed between the replays: each replay's pyramids equal the checker's on the image that
     replay lit and on the exposure that replay's eye adaptation stored.  Captured with the default queue settings."""
-    import test_gpu_eye_adaptation as GE
-    import test_gpu_pbr_apply as GP
     from oxylus_amd.renderer import BloomContext
 
-    frame = GP.DrawnFrame(renderer, monkeypatch)
+    frame = DrawnFrame(renderer)
     frame.passes()
-    sets = [GP.lights_tensor(frame.four_lights(shift)) for shift in (0.0, 0.3, -0.2)]
+    sets = [lights_tensor(frame.four_lights(shift)) for shift in (0.0, 0.3, -0.2)]
     lights = sets[0].clone()
-    pbr = frame.pbr(GP.ALL_FLAGS, lights)
+    pbr = frame.pbr(ALL_FLAGS, lights)
     renderer.apply_pbr(pbr)
-    exposure = GE.words_tensor(GE.ONE_ONE)
-    ectx = GE.make_context(pbr.final_attachment, exposure, time_coeff=0.4, settings=GE.COMPONENT)
+    exposure = words_tensor(ONE_ONE)
+    ectx = eye_context(pbr.final_attachment, exposure, time_coeff=0.4, settings=EYE_COMPONENT)
     D, U = Pyramid(192, 192, 0), Pyramid(192, 192, 0)
     bctx = BloomContext(pbr.final_attachment, exposure, D.attachment, U.attachment, 192, 192, 0, HAS_EYE_ADAPTATION, **DEFAULTS)
     renderer.apply_eye_adaptation(ectx)  # eager once
     renderer.apply_bloom(bctx)
-    exposure.copy_(GE.words_tensor(GE.ONE_ONE))
+    exposure.copy_(words_tensor(ONE_ONE))
     torch.cuda.synchronize()
     stream = torch.cuda.Stream()
     g = torch.cuda.CUDAGraph()
@@ -348,7 +340,7 @@ def test_eight_passes_in_one_graph(renderer, monkeypatch):
         renderer.apply_pbr(pbr, stream=stream)
         renderer.apply_eye_adaptation(ectx, stream=stream)
         renderer.apply_bloom(bctx, stream=stream)
-    words, blooms = GE.ONE_ONE, []
+    words, blooms = ONE_ONE, []
     for replay, s in enumerate(sets):
         pbr.final_attachment.fill_(-5)
         D.refill()
@@ -357,7 +349,7 @@ def test_eight_passes_in_one_graph(renderer, monkeypatch):
         torch.cuda.synchronize()
         g.replay()
         torch.cuda.synchronize()
-        words = GE.want_of(ectx, words)[1]  # the chain of exposures, from the image this replay wrote
+        words = eye_want_of(ectx, words)[1]  # the chain of exposures, from the image this replay wrote
         assert exposure.cpu().numpy().view(np.uint32).tolist() == words.tolist(), f"replay {replay}: exposure"
         want = BM.apply_bloom(pbr.final_attachment.cpu().numpy().view(np.uint32), 0, words, **DEFAULTS)
         D.check(f"replay {replay}: bloom_downsampled", want[0])

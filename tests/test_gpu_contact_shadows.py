@@ -2,63 +2,22 @@
 oxc_draw_visbuffer with every outcome class populated, the engine's defaults on it, an odd non-square extent under a rotated camera with
 1, 3 and 64 steps, an all-sky image, non-finite / negative / denormal texels, the resolve and the contact shadows captured into one graph,
 and invalid arguments."""
-import math
-
 import numpy as np
 import pytest
 import torch
 
 import contact_shadows_model as CM
-from test_contact_shadows_model import MAIN, MAIN_SEED, MAIN_SIZE, SUN, assert_not_degenerate, identity_camera
+from gpu_passes import Frame, drawn_depth
+from gpu_passes import contact_check as check
+from gpu_passes import contact_context as context
+from gpu_passes import contact_got_of as got_of
+from scenes import CS_MAIN as MAIN
+from scenes import CS_MAIN_SEED as MAIN_SEED
+from scenes import CS_MAIN_SIZE as MAIN_SIZE
+from scenes import cs_assert_not_degenerate as assert_not_degenerate
+from scenes import identity_camera, rotated_camera
 
 pytestmark = pytest.mark.gpu
-
-
-def drawn_depth(r, W, H, seed):
-    """The main view's depth of tests/test_gpu_vsm_resolve.py::occluder_scene, drawn by oxc_draw_visbuffer (the first steps of its Frame)."""
-    from oxylus_amd import lib as L
-    from oxylus_amd.renderer import CullGeometryContext, ImageAttachment, PreparedFrame
-    from test_gpu_vsm_resolve import occluder_scene
-
-    cpu = occluder_scene(seed)
-    gpu = cpu.to("cuda")
-    r.reserve(gpu.n_mesh_instances, gpu.n_meshlet_instances)
-    r.prepared_frame = PreparedFrame.create(gpu)
-    main = CullGeometryContext(init_cull_meshes=False, cull_flags=L.CULL_TEST_ALL, cull_camera=gpu.cull_camera())
-    r.seed_meshlet_instances(main, gpu.n_meshlet_instances)
-    r.cull_geometry(main)
-    pv = [float(x) for x in cpu.camera["projection_view"]]
-    visdepth = torch.empty((H, W), dtype=torch.int64, device="cuda")
-    depth = torch.zeros((H, W), dtype=torch.float32, device="cuda")
-    r.draw_visbuffer(main, pv, W, H, visdepth, clear=True, depth=ImageAttachment.depth(depth))
-    torch.cuda.synchronize()
-    return cpu, depth
-
-
-def context(depth, camera, sun=SUN, **kw):
-    from oxylus_amd.renderer import ContactShadowsContext
-
-    inv, view, proj, near = camera
-    return ContactShadowsContext.create(depth, inv, view, proj, near, sun, **kw)
-
-
-def got_of(ctx):
-    torch.cuda.synchronize()
-    a = ctx.contact_shadows_attachment
-    return a.data.view(a.height, a.width).cpu().numpy().copy()
-
-
-def want_of(ctx, stats=None):
-    d = ctx.depth_attachment
-    return CM.contact_shadows(d.data.view(d.height, d.width).cpu().numpy(), ctx.inv_projection_view, ctx.view, ctx.projection, ctx.near_clip, ctx.sun_dir,
-                              ctx.steps, ctx.thickness, ctx.shadow_length, stats=stats)
-
-
-def check(ctx, stats=None):
-    got, want = got_of(ctx), want_of(ctx, stats)
-    bad = int((got.view(np.uint32) != want.view(np.uint32)).sum())
-    assert bad == 0, f"{bad} of {got.size} pixels differ"
-    return got
 
 
 def test_main_frame_every_outcome_class(renderer):
@@ -97,22 +56,6 @@ def test_engine_defaults_on_the_main_frame(renderer):
     st = {}
     got = check(ctx, st)
     assert (st["n"][st["outcome"] != CM.SKY] == 2).all() and ((got > 0) & (got < 1)).sum() > 1000
-
-
-def rotated_camera():
-    """A camera at (3, 1.5, -2) turned 25 degrees about y and 10 degrees down: neither view nor its inverse has an exact entry."""
-    from oxylus_amd.synth import perspective_reversed_z
-
-    proj = perspective_reversed_z(60.0, 1.0, 0.1, 1000.0).numpy().astype(np.float64).reshape(4, 4).T
-    a, b = math.radians(25.0), math.radians(-10.0)
-    ry = np.array([[math.cos(a), 0, math.sin(a), 0], [0, 1, 0, 0], [-math.sin(a), 0, math.cos(a), 0], [0, 0, 0, 1]])
-    rx = np.array([[1, 0, 0, 0], [0, math.cos(b), -math.sin(b), 0], [0, math.sin(b), math.cos(b), 0], [0, 0, 0, 1]])
-    tr = np.eye(4)
-    tr[:3, 3] = (-3.0, -1.5, 2.0)
-    view = rx @ ry @ tr
-    inv = np.linalg.inv(proj @ view)
-    f = lambda m: m.T.reshape(-1).astype(np.float32)  # noqa: E731
-    return f(inv), f(view), f(proj), 0.1
 
 
 @pytest.mark.parametrize("steps", [1, 3, 64])
@@ -159,8 +102,6 @@ def test_all_sky_and_non_finite_texels(renderer):
 
 
 def test_resolve_and_contact_shadows_in_one_graph(renderer):
-    from test_gpu_vsm_resolve import Frame
-
     f = Frame(renderer, 320, 320, seed=66)
     f.shadow_path()  # eager; every scratch grows here
     ctx = context(f.depth, identity_camera(f.gpu), steps=8, thickness=0.3, shadow_length=0.3)

@@ -8,16 +8,19 @@ import numpy as np
 import pytest
 import torch
 
-import eye_adaptation_model as EM
-from pbr_apply_model import pack_b10g11r11
+from gpu_passes import ALL_FLAGS, DrawnFrame, Guard, ONE_ONE, lights_tensor, same, words_tensor
+from gpu_passes import EYE_COMPONENT as COMPONENT
+from gpu_passes import EYE_DEFAULTS as DEFAULTS
+from gpu_passes import eye_context as make_context
+from gpu_passes import eye_want_of as want_of
+from pbr_apply_model import TRANSPARENT_BACKGROUND
+from pixel_rules import pack_b10g11r11
+from scenes import NAN16, NAN32
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 FORMATS = pytest.mark.parametrize("fmt", [0, 1], ids=["b10g11r11", "rgba16f"])
-ONE_ONE = np.array([0x3F800000, 0x3F800000], dtype=np.uint32)
-DEFAULTS = dict(min_exposure=-6.0, max_exposure=18.0, ev100_bias=1.0)
-COMPONENT = dict(min_exposure=-11.5, max_exposure=18.0, ev100_bias=1.0)
 POISON = 0xFFFFFFFB  # what the histogram and the exposure buffer hold before a call: no count of these images and no stored float
 
 
@@ -46,32 +49,9 @@ def upload(image: np.ndarray) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(image).view(view).copy()).cuda()
 
 
-def words_tensor(words) -> torch.Tensor:
-    return torch.from_numpy(np.asarray(words, dtype=np.uint32).view(np.float32).copy()).cuda()
-
-
-def make_context(image_t, exposure_t, time_coeff=1.0, settings=DEFAULTS):
-    from oxylus_amd.renderer import EyeAdaptationContext
-
-    ctx = EyeAdaptationContext.create(image_t, exposure_t, time_coeff=time_coeff, **settings)
-    ctx.histogram_buffer.fill_(-5)
-    return ctx
-
-
 def got_of(ctx):
     torch.cuda.synchronize()
     return ctx.histogram_buffer.cpu().numpy().view(np.uint32).copy(), ctx.exposure_buffer.cpu().numpy().view(np.uint32).copy()
-
-
-def want_of(ctx, exposure_words):
-    image = ctx.final_attachment.cpu().numpy()
-    return EM.apply_eye_adaptation(image, ctx.source_format, exposure_words, ctx.min_exposure, ctx.max_exposure, ctx.ev100_bias, ctx.time_coeff)
-
-
-def same(got, want, label):
-    for name, g, w in (("histogram", got[0], want[0]), ("exposure", got[1], want[1])):
-        bad = np.flatnonzero(g != w)
-        assert bad.size == 0, f"{label}: {name}: {bad.size} words differ, the first at {int(bad[0])}: 0x{int(g[bad[0]]):X} != 0x{int(w[bad[0]]):X}"
 
 
 def run_and_check(r, image: np.ndarray, label, exposure_words=ONE_ONE, time_coeff=1.0, settings=DEFAULTS):
@@ -85,14 +65,12 @@ def run_and_check(r, image: np.ndarray, label, exposure_words=ONE_ONE, time_coef
 
 # ---- 1. the drawn frame ---------------------------------------------------------------------------------------------------------------------------
 @FORMATS
-def test_drawn_frame(renderer, monkeypatch, fmt):
+def test_drawn_frame(renderer, fmt):
     """The 192 x 192 frame drawn, decoded, resolved, occluded and lit by the library's own passes: the histogram and the exposure equal the
     checker's, the frame spreads over several bins, and the source image is unchanged."""
-    import test_gpu_pbr_apply as GP
-
-    frame = GP.DrawnFrame(renderer, monkeypatch)
+    frame = DrawnFrame(renderer)
     frame.passes()
-    pbr = frame.pbr(GP.ALL_FLAGS | (GP.TRANSPARENT_BACKGROUND if fmt else 0), GP.lights_tensor(frame.four_lights()))
+    pbr = frame.pbr(ALL_FLAGS | (TRANSPARENT_BACKGROUND if fmt else 0), lights_tensor(frame.four_lights()))
     renderer.apply_pbr(pbr)
     torch.cuda.synchronize()
     before = pbr.final_attachment.clone()
@@ -116,8 +94,6 @@ def test_extent_between_guard_bands(renderer, extent, fmt):
     demands (so the texels before the first 16-byte boundary are there): a load outside the image is one count too many, a store outside an
     output changes a band.  Again with the grid capped to 1 and to 3 blocks: every block walks its stride loop several times."""
     from oxylus_amd import lib as L
-    from test_gpu_pixel_pass_edges import Guard
-    from test_pixel_pass_edge_cases import NAN16, NAN32
 
     W, H = extent
     image = random_image(W, H, fmt, seed=23 + W)
@@ -150,8 +126,6 @@ def test_every_alignment_of_the_image(renderer, fmt):
     """The image at every texel offset from a 16-byte boundary -- addresses 0, 4, 8 and 12 mod 16 (B10G11R11), 0 and 8 mod 16 (RGBA16F) --
     and with 1 to 11 and 35 texels: every count of texels before the first vector (0 to 3, 0 to 1) meets every count behind the last one,
     with and without whole vectors in between.  The buffer around the image holds poison texels; one read outside is one count too many."""
-    from test_pixel_pass_edge_cases import NAN16, NAN32
-
     per_texel, dtype, poison = ((1, torch.int32, NAN32), (4, torch.int16, NAN16))[fmt]
     for offset in range(16 // (8 if fmt else 4)):
         for shape in [(1, n) for n in range(1, 12)] + [(7, 5)]:
@@ -294,17 +268,15 @@ def test_five_frames_on_one_exposure_buffer(renderer, fmt):
 
 
 # ---- 7. all seven passes in one captured graph ------------------------------------------------------------------------------------------------------
-def test_seven_passes_in_one_graph(renderer, monkeypatch):
+def test_seven_passes_in_one_graph(renderer):
     """Draw -> decode -> resolve -> contact shadows -> ambient occlusion -> apply -> eye adaptation captured into one graph and replayed three
     times with the lights changed between the replays: after each replay the histogram and the exposure equal the checker's chain from the
     image that replay wrote.  Captured with the default queue settings."""
-    import test_gpu_pbr_apply as GP
-
-    frame = GP.DrawnFrame(renderer, monkeypatch)
+    frame = DrawnFrame(renderer)
     frame.passes()
-    sets = [GP.lights_tensor(frame.four_lights(shift)) for shift in (0.0, 0.3, -0.2)]
+    sets = [lights_tensor(frame.four_lights(shift)) for shift in (0.0, 0.3, -0.2)]
     lights = sets[0].clone()
-    pbr = frame.pbr(GP.ALL_FLAGS, lights)
+    pbr = frame.pbr(ALL_FLAGS, lights)
     renderer.apply_pbr(pbr)
     exposure = words_tensor(ONE_ONE)
     ctx = make_context(pbr.final_attachment, exposure, time_coeff=0.4, settings=COMPONENT)

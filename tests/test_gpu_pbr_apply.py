@@ -12,59 +12,20 @@ import torch
 
 import pbr_apply_model as PM
 from pbr_apply_model import HAS_ATMOSPHERE, HAS_CONTACT_SHADOWS, HAS_DIRECTIONAL_LIGHT, HAS_SKY, TRANSPARENT_BACKGROUND
-from test_pbr_apply_model import CAMERA, INV_PV, SKY, SUN, SUN_INTENSITY, synthetic_inputs
+from gpu_passes import ALL_FLAGS, FILL_U16, FILL_U32, DrawnFrame, Guard, lights_tensor
+from gpu_passes import pbr_context as make_context
+from gpu_passes import pbr_got_of as got_of
+from gpu_passes import pbr_want_of as want_of
+from gpu_passes import same, upload
+from scenes import CAMERA, EXTENT_IDS, EXTENTS, INV_PV, NAN16, NAN32, SKY, SUN_INTENSITY
+from scenes import PBR_SUN as SUN
+from scenes import synthetic_inputs
 
 pytestmark = pytest.mark.gpu
 
-ALL_FLAGS = HAS_DIRECTIONAL_LIGHT | HAS_CONTACT_SHADOWS | HAS_SKY
 LIGHT_CHUNK = 256  # kLightChunk of oxcull_pbr_apply.hip: lights staged per round
 FILL = -5          # 0xFFFFFFFB / 0xFFFB: a pattern the pass never writes (a NaN channel is stored with an all-ones mantissa / as 0x7E00)
 U32 = lambda bits: np.uint32(bits)  # noqa: E731
-
-
-def lights_tensor(lights):
-    from oxylus_amd.synth import pack_lights
-
-    return pack_lights(lights).cuda() if lights else None
-
-
-def upload(inp: dict) -> dict:
-    """The numpy images of synthetic_inputs() as CUDA tensors in the dtypes the renderer takes."""
-    t = lambda a, view: torch.from_numpy(np.ascontiguousarray(a).view(view).copy()).cuda()  # noqa: E731
-    return dict(depth=t(inp["depth"], np.float32), albedo=t(inp["albedo"], np.int32), normal=t(inp["normal"], np.int16), emissive=t(inp["emissive"], np.int32),
-                mro=t(inp["mro"], np.int32), ao=t(inp["ao"], np.int16), resolved=t(inp["resolved"], np.float32), contact=t(inp["contact"], np.float32))
-
-
-def make_context(dev: dict, flags: int, lights=None, **kw):
-    from oxylus_amd.renderer import PBRContext
-
-    kw = {**dict(inv_projection_view=INV_PV, camera_position=CAMERA, sun_dir=SUN, sun_intensity=SUN_INTENSITY, **SKY), **kw}
-    return PBRContext.create(dev["depth"], dev["albedo"], dev["normal"], dev["emissive"], dev["mro"], dev["ao"], dev["resolved"], dev["contact"], flags,
-                             lights=lights, **kw)
-
-
-def got_of(ctx) -> np.ndarray:
-    torch.cuda.synchronize()
-    a = ctx.final_attachment.cpu().numpy()
-    return a.view(np.uint16 if a.dtype == np.int16 else np.uint32).copy()
-
-
-def want_of(ctx, stats=None) -> np.ndarray:
-    d = ctx.depth_attachment
-    img = lambda a: None if a is None else a.data.view(d.height, d.width).cpu().numpy()  # noqa: E731
-    lights = None if ctx.lights_buffer is None else ctx.lights_buffer.cpu().numpy()
-    return PM.apply_pbr(img(d), ctx.albedo_attachment.cpu().numpy(), ctx.normal_attachment.cpu().numpy(), ctx.emissive_attachment.cpu().numpy(),
-                        ctx.metallic_roughness_occlusion_attachment.cpu().numpy(), ctx.ambient_occlusion_attachment.cpu().numpy(),
-                        img(ctx.resolved_shadows_attachment) if ctx.scene_flags & HAS_DIRECTIONAL_LIGHT else None,
-                        img(ctx.contact_shadows_attachment) if ctx.scene_flags & HAS_CONTACT_SHADOWS else None, ctx.scene_flags, ctx.inv_projection_view,
-                        ctx.camera_position, ctx.sun_dir, ctx.sun_intensity, lights, ctx.light_count, ctx.base_ambient_color, ctx.sky_solid_color,
-                        ctx.sky_ambient_color, ctx.sky_has_texture, stats=stats)
-
-
-def same(got, want, label=""):
-    bad = np.argwhere(got != want)
-    assert len(bad) == 0, (f"{label}: {len(bad)} of {got.size} elements differ, the first at {bad[0].tolist()}: 0x{int(got[tuple(bad[0])]):X} != "
-                           f"0x{int(want[tuple(bad[0])]):X}")
 
 
 def run_and_check(r, ctx, label="", want=None, st=None):
@@ -91,86 +52,13 @@ def run_and_check(r, ctx, label="", want=None, st=None):
 
 
 # ---- 1. the drawn frame, 6. one captured graph ------------------------------------------------------------------------------------------------
-class DrawnFrame:
-    """The 192 x 192 frame of tests/test_gpu_visbuffer_decode.py's graph test: draw -> decode -> resolve -> contact shadows -> ambient occlusion,
-    every context kept, `passes(stream)` runs the five producers."""
-
-    def __init__(self, renderer, monkeypatch):
-        import test_gpu_ambient_occlusion as GA
-        import test_gpu_contact_shadows as GC
-        import test_gpu_visbuffer_decode as GD
-        import test_gpu_vsm_resolve as GR
-        from oxylus_amd import lib as L
-        from oxylus_amd.renderer import CullGeometryContext, ImageAttachment, PreparedFrame
-        from test_ambient_occlusion_model import MAIN, camera_of
-        from test_contact_shadows_model import identity_camera
-        from test_visbuffer_decode_model import main_scene
-
-        self.r, self.W, self.H = renderer, 192, 192
-        W, H = self.W, self.H
-        self.cpu = cpu = main_scene(66)[0]
-        monkeypatch.setattr(GR, "occluder_scene", lambda seed: cpu)
-        self.f = f = GR.Frame(renderer, W, H, seed=66)
-        f.shadow_path()  # eager; every scratch grows here
-        gpu = f.gpu
-        self.frame = PreparedFrame.create(gpu)
-        renderer.prepared_frame = self.frame
-        self.main = CullGeometryContext(init_cull_meshes=False, cull_flags=L.CULL_TEST_ALL, cull_camera=gpu.cull_camera())
-        renderer.seed_meshlet_instances(self.main, gpu.n_meshlet_instances)
-        renderer.cull_geometry(self.main)
-        self.pv = cpu.camera["projection_view"]
-        self.visdepth = torch.empty((H, W), dtype=torch.int64, device="cuda")
-        self.vis = torch.zeros((H, W), dtype=torch.int32, device="cuda")
-        self.dctx = GD.context(gpu, self.vis, f.depth, self.pv)
-        f.rctx.normal_attachment = self.dctx.normal_attachment
-        self.cctx = GC.context(f.depth, identity_camera(gpu), steps=8, thickness=0.3, shadow_length=0.3)
-        _, view, proj, far = camera_of(gpu)
-        self.actx = GA.context(f.depth, self.dctx.normal_attachment, view, proj, far, **MAIN)
-        self.sun = tuple(float(v) for v in GR.LIGHT)
-        self.depth_image = ImageAttachment.depth(f.depth)
-
-    def passes(self, stream=None):
-        r, f = self.r, self.f
-        r.prepared_frame = self.frame
-        r.draw_visbuffer(self.main, self.pv, self.W, self.H, self.visdepth, clear=True, depth=self.depth_image, visbuffer=self.vis, stream=stream)
-        r.decode_visbuffer(self.dctx, stream=stream)
-        r.resolve_shadowmap(f.rctx, stream=stream)
-        r.contact_shadows(self.cctx, stream=stream)
-        r.generate_ambient_occlusion(self.actx, stream=stream)
-
-    def pbr(self, flags, lights):
-        from oxylus_amd.renderer import PBRContext
-
-        d, f = self.dctx, self.f
-        return PBRContext.create(f.depth, d.albedo_attachment, d.normal_attachment, d.emissive_attachment, d.metallic_roughness_occlusion_attachment,
-                                 self.actx.ambient_occlusion_attachment, f.rctx.resolved_shadows_attachment, self.cctx.contact_shadows_attachment, flags,
-                                 f.inv, self.cpu.camera["position"], self.sun, 3.0, lights=lights, sky_solid_color=(0.25, 0.5, 1.0, 1.0),
-                                 sky_ambient_color=(0.1, 0.15, 0.2))
-
-    def four_lights(self, shift=0.0):
-        """A point light with a cutoff that leaves part of the frame at win == 0, a point light with range == 0, a spot light whose cone edge
-        crosses the frame, and a record of kind Directional -- placed from the world positions the checker finds behind the lit pixels."""
-        st = {}
-        want_of(self.pbr(ALL_FLAGS, None), st)
-        lit = st["lit"] & (self.f.depth.cpu().numpy()[st["ys"], st["xs"]] != 0)
-        world = np.stack([w[lit] for w in st["world"]], axis=-1).astype(np.float64)
-        cam = np.asarray(self.cpu.camera["position"], dtype=np.float64)
-        centre = np.median(world, axis=0)
-        near = centre + 0.25 * (cam - centre) + shift
-        reach = float(np.median(np.linalg.norm(world - near, axis=-1)))
-        to_centre = centre - cam
-        return [dict(kind=1, position=tuple(near), range=reach, color=(1.0, 0.8, 0.6), intensity=40.0),
-                dict(kind=1, position=tuple(cam + 0.1 + shift), range=0.0, color=(0.2, 0.4, 1.0), intensity=15.0),
-                dict(kind=2, position=tuple(cam + shift), direction=tuple(to_centre), inner_cone_angle=0.06, outer_cone_angle=0.14, range=0.0, color=(1.0, 1.0, 1.0),
-                     intensity=60.0),
-                dict(kind=0, position=tuple(centre), range=0.0, color=(9.0, 9.0, 9.0), intensity=1000.0)]
 
 
 @pytest.mark.parametrize("transparent", [0, TRANSPARENT_BACKGROUND], ids=["b10g11r11", "rgba16f"])
-def test_drawn_frame(renderer, monkeypatch, transparent):
+def test_drawn_frame(renderer, transparent):
     """The library's own frame under four lights: the image and the counters equal the checker's, at least three of the five pixel classes
     and all four light outcomes occur (asserted from the checker's counts), and the Directional record changes nothing."""
-    frame = DrawnFrame(renderer, monkeypatch)
+    frame = DrawnFrame(renderer)
     frame.passes()
     lights = frame.four_lights()
     ctx = frame.pbr(ALL_FLAGS | transparent, lights_tensor(lights))
@@ -188,10 +76,10 @@ def test_drawn_frame(renderer, monkeypatch, transparent):
     assert (got_of(none) != got_of(ctx)).any()  # the lights show
 
 
-def test_six_passes_in_one_graph(renderer, monkeypatch):
+def test_six_passes_in_one_graph(renderer):
     """Draw -> decode -> resolve -> contact shadows -> ambient occlusion -> apply captured into one graph and replayed three times with the
     lights changed between the replays: every replay equals the eager frame under the same lights.  Captured with the default queue settings."""
-    frame = DrawnFrame(renderer, monkeypatch)
+    frame = DrawnFrame(renderer)
     frame.passes()
     sets = [lights_tensor(frame.four_lights(shift)) for shift in (0.0, 0.3, -0.2)]
     lights = sets[0].clone()
@@ -258,20 +146,14 @@ def test_flags(renderer, flags):
 
 
 # ---- 3. extents between guard bands -----------------------------------------------------------------------------------------------------------
-def _extents():
-    from test_pixel_pass_edge_cases import EXTENT_IDS, EXTENTS
-
-    return EXTENTS, EXTENT_IDS
 
 
-@pytest.mark.parametrize("extent", _extents()[0], ids=_extents()[1])
+@pytest.mark.parametrize("extent", EXTENTS, ids=EXTENT_IDS)
 @pytest.mark.parametrize("transparent", [0, TRANSPARENT_BACKGROUND], ids=["b10g11r11", "rgba16f"])
 def test_extent_between_guard_bands(renderer, extent, transparent):
     """Every image a window in the middle of a larger poisoned buffer: a load outside an input reads NaN and shows as a parity failure, a
     store outside the output changes a band."""
     from oxylus_amd.renderer import ImageAttachment, PBRContext
-    from test_gpu_pixel_pass_edges import FILL_U16, FILL_U32, Guard
-    from test_pixel_pass_edge_cases import NAN16, NAN32
 
     W, H = extent
     inp = synthetic_inputs(W, H, seed=11 + W)

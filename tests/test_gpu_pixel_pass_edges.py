@@ -13,67 +13,13 @@ import torch
 
 import ambient_occlusion_model as AM
 import contact_shadows_model as CM
-import test_gpu_ambient_occlusion as GA
-import test_gpu_contact_shadows as GC
 import vsm_resolve_model as RM
-from test_ambient_occlusion_model import PROJ, hilbert
-from test_contact_shadows_model import I16
-from test_pixel_pass_edge_cases import (AO_FAR, AO_RESOLUTIONS, AO_WIDE, CS_SETTINGS, EXTENT_IDS, EXTENTS, HILBERT_POISON, NAN16, NAN32, OUT16, OUT32,
-                                        ao_inputs, assert_resolve_sweep_is_not_degenerate, cs_depth, cs_runs, resample, resolve_counts)
+from gpu_passes import (DEVICE, FILL_F32, FILL_U16, FILL_U32, Frame, Guard, _signed, ao_context, ao_got_of, ao_want_of, contact_context, contact_got_of,
+                        contact_want_of, same)
+from scenes import (AO_FAR, AO_RESOLUTIONS, AO_WIDE, CS_SETTINGS, EXTENT_IDS, EXTENTS, HILBERT_POISON, I16, LIGHT, NAN16, NAN32, OUT16, OUT32, PROJ, Z_LENGTH, ao_inputs,
+                    assert_resolve_sweep_is_not_degenerate, cs_depth, cs_runs, hilbert, resample, resolve_counts)
 
 pytestmark = pytest.mark.gpu
-
-FILL_F32 = 0xC0A00000  # -5.0f: no pass writes a negative value
-FILL_U32 = 0xFFFFFFFB  # -5, as the existing tests pre-fill; compared against the checker's image before it is trusted
-FILL_U16 = 0xFFFB      # -5: a NaN half
-DEVICE = "cuda"
-
-
-def _signed(bits: int, size: int) -> int:
-    return bits - (1 << (8 * size)) if bits >> (8 * size - 1) else bits
-
-
-class Guard:
-    """A tensor as a contiguous window in the middle of a larger 1-D buffer.  The band before it and the band after it hold `poison` and
-    are each at least `row` + 64 elements long; the window starts at a multiple of `align` bytes that is not a multiple of 2 * `align`
-    (the least the ABI demands).  `data` (numpy, same element size) fills an input window, `fill` pre-fills an output window with a pattern
-    the pass does not write there."""
-
-    def __init__(self, name, shape, dtype, row, poison, align, data=None, fill=None):
-        size = torch.empty((), dtype=dtype).element_size()
-        store, view = (torch.int16, np.int16) if size == 2 else (torch.int32, np.int32)
-        per = align // size
-        band = -(-(row + 64) // per) * per
-        band += per if (band // per) % 2 == 0 else 0
-        n = int(np.prod(shape))
-        self.name, self.poison, self.fill, self.size, self.lo, self.hi = name, poison, fill, size, band, band + n
-        self.buf = torch.full((band + n + band,), _signed(poison, size), dtype=store, device=DEVICE)
-        window = self.buf[band:band + n]
-        if data is not None:
-            window.copy_(torch.from_numpy(np.ascontiguousarray(data).view(view).reshape(-1).copy()))
-        else:
-            window.fill_(_signed(fill, size))
-        self.tensor = window.view(dtype).view(shape)
-        assert self.tensor.data_ptr() % align == 0 and self.tensor.is_contiguous()
-
-    def refill(self):
-        self.buf[self.lo:self.hi].fill_(_signed(self.fill, self.size))
-
-    def bits(self):
-        """(band before, window, band after) as unsigned bit patterns."""
-        a = self.buf.cpu().numpy().view(np.uint16 if self.size == 2 else np.uint32)
-        return a[:self.lo], a[self.lo:self.hi], a[self.hi:]
-
-    def check(self, label, want=None):
-        """Both bands bit-identical to the poison (a NaN poison equals itself: patterns are compared, not values).  With `want`, the
-        checker's image: no element of it equals the pre-fill pattern, so a window equal to `want` was overwritten everywhere."""
-        before, _, after = self.bits()
-        for side, band, base in (("before", before, -len(before)), ("after", after, self.hi - self.lo)):
-            bad = np.flatnonzero(band != self.poison)
-            assert bad.size == 0, (f"{label}: {self.name}: {bad.size} elements of the band {side} the image changed, the first at element "
-                                   f"{int(bad[0]) + base} relative to the window's start (value 0x{int(band[bad[0]]):X})")
-        if want is not None:
-            assert not (np.ascontiguousarray(want).view(before.dtype) == self.fill).any(), f"{label}: {self.name}: the checker's image holds the pre-fill pattern"
 
 
 class Pyramid:
@@ -133,7 +79,7 @@ class AoCase:
                         "noisy_occlusion": Guard("noisy_occlusion", (H, W), torch.int16, W, OUT16, 2, fill=FILL_U16),
                         "ambient_occlusion": Guard("ambient_occlusion_attachment", (H, W), torch.int16, W, OUT16, 2, fill=FILL_U16)}
         self.pyramid = Pyramid(W, H)
-        ctx = GA.context(self.inputs[0].tensor, self.inputs[1].tensor, I16, PROJ, AO_FAR, resolution=resolution)
+        ctx = ao_context(self.inputs[0].tensor, self.inputs[1].tensor, I16, PROJ, AO_FAR, resolution=resolution)
         ctx.hilbert_noise = self.inputs[2].tensor
         ctx.prefiltered_depth = self.pyramid.attachment
         ctx.depth_differences, ctx.noisy_occlusion = self.outputs["depth_differences"].tensor, self.outputs["noisy_occlusion"].tensor
@@ -148,9 +94,9 @@ class AoCase:
     def compare(self, what, want):
         """All five levels, depth_differences, noisy_occlusion and the final image == `want`; every band and gap untouched."""
         label = f"{self.label}, {what}"
-        got = GA.got_of(self.ctx)
+        got = ao_got_of(self.ctx)
         try:
-            GA.same(got, want)
+            same(got, want)
         except AssertionError as e:
             first = {f"level {k}": _where(got["levels"][k].view(np.uint32), want["levels"][k].view(np.uint32)) for k in range(5)}
             first.update({name: _where(got[name], want[name]) for name in self.outputs})
@@ -169,7 +115,7 @@ class AoCase:
         for k, v in settings.items():
             setattr(self.ctx, k, v)
         st = {}
-        want = GA.want_of(self.ctx, st)
+        want = ao_want_of(self.ctx, st)
         self.refill()
         renderer.debug_set_tuning(L.TUNE_AMBIENT_OCCLUSION_STATS, 1)
         try:
@@ -220,13 +166,13 @@ def test_contact_shadows_extent(renderer, extent):
     out = Guard("contact_shadows_attachment", (H, W), torch.float32, W, OUT32, 4, fill=FILL_F32)
     for name, camera, steps, sun in cs_runs():
         label = f"{W} x {H}, {name} camera, steps {steps}, sun {sun}"
-        ctx = GC.context(depth.tensor, camera, sun=sun, steps=steps, **CS_SETTINGS)
+        ctx = contact_context(depth.tensor, camera, sun=sun, steps=steps, **CS_SETTINGS)
         ctx.contact_shadows_attachment = ImageAttachment.depth(out.tensor)
         st = {}
-        want = GC.want_of(ctx, st)
+        want = contact_want_of(ctx, st)
 
         def compare(what):
-            got = GC.got_of(ctx)
+            got = contact_got_of(ctx)
             bad = _where(got.view(np.uint32), want.view(np.uint32))
             assert not bad, f"{label}, {what}: contact_shadows_attachment differs from the checker, first at (y, x) {bad}"
             out.check(f"{label}, {what}", want)
@@ -251,8 +197,6 @@ def test_contact_shadows_extent(renderer, extent):
 def resolve_frame(renderer):
     """Frame(renderer, 128, 128, seed=67) with a third of its pages evicted before the resolve (the taps near a clipmap boundary are then
     served by the neighbouring clipmaps), its shadow path run once, and the CPU copies the checker needs."""
-    from test_gpu_vsm_resolve import Frame
-
     f = Frame(renderer, 128, 128, seed=67, evict=True)
     f.shadow_path()
     f.check()
@@ -263,8 +207,6 @@ def resolve_frame(renderer):
 
 
 def _resolve_want(f, cpu, depth, normal, W, H, stats):
-    from test_gpu_vsm_resolve import LIGHT, Z_LENGTH
-
     return RM.resolve(depth, normal, cpu["table"], cpu["clipmaps"], cpu["physical"], f.inv, (W, H), LIGHT, Z_LENGTH, first_clipmap_width=f.fcw,
                       bias=f.vctx.clipmap_selection_bias, virtual_extent=f.vctx.virtual_extent, stats=stats, **f.shape)
 

@@ -6,109 +6,10 @@ import numpy as np
 import pytest
 import torch
 
-import vsm_draw_model as DM
 import vsm_resolve_model as RM
+from gpu_passes import Frame
 
 pytestmark = pytest.mark.gpu
-
-LIGHT = np.array([0.35, 0.8, 0.5]) / np.linalg.norm([0.35, 0.8, 0.5])  # towards the light: above and behind the camera's right shoulder
-MAX_SHADOW_DIST = 500.0
-Z_LENGTH = 4000.0  # four times the clipmaps' depth range (the reference: max_shadow_dist * 2): a four times wider light, penumbrae of several texels
-REFERENCE = dict(page_size=128, page_table_size=64, physical_page_table_size=8192, clipmap_count=10)
-
-
-def occluder_scene(seed):
-    """A floor at y = -2 below a camera at the origin that looks down -z, and 40 horizontal quads of 2..6 units floating 2..12 units above
-    it: lit floor, umbra, penumbra bands and sky in one view.  Every surface is drawn with both windings (the main view culls back
-    faces).  Integer coordinates: exact in the mesh's binary16 positions."""
-    rng = np.random.default_rng(seed)
-    tris = []
-
-    def quad(x0, x1, z0, z1, y):
-        a, b, c, d = (x0, y, z0), (x1, y, z0), (x1, y, z1), (x0, y, z1)
-        tris.extend([[a, b, c], [a, c, d], [a, c, b], [a, d, c]])
-
-    quad(-24, 24, -4, -64, -2)
-    for _ in range(40):
-        cx, cz, y = int(rng.integers(-14, 15)), int(rng.integers(-40, -7)), int(rng.integers(0, 11))
-        w, d = int(rng.integers(1, 4)), int(rng.integers(1, 4))
-        quad(cx - w, cx + w, cz - d, cz + d, y)
-    return DM.flat_scene([[tuple(float(v) for v in p) for p in t] for t in tris])[0]
-
-
-class Frame:
-    """The compute-only shadow frame of tests/test_gpu_vsm_draw.py with the resolve at its end.  `evict`: before the resolve a third of
-    the page-table entries, chosen by (7 x + 13 y + layer) % 3 == 0, lose their Backed bit, as pages evicted since the draw.  In a frame
-    straight from the update every pixel's own page is backed and the fallback clipmaps are hardly ever asked; with evicted pages the
-    taps near a clipmap boundary are served by the neighbouring clipmaps and the others miss."""
-
-    def __init__(self, r, W, H, shape=REFERENCE, seed=61, evict=False, first_clipmap_width=10.0):
-        from oxylus_amd import lib as L
-        from oxylus_amd.renderer import CullGeometryContext, ImageAttachment, PreparedFrame, ShadowResolveContext, VirtualShadowmapContext, VsmDrawContext
-        from oxylus_amd.synth import normals_from_depth, pack_clipmaps, virtual_shadow_matrices
-
-        self.r, self.W, self.H, self.shape, self.L, self.evict = r, W, H, shape, L, evict
-        self.fcw = first_clipmap_width
-        count, n = shape["clipmap_count"], shape["page_table_size"]
-        cpu = occluder_scene(seed)
-        self.gpu = gpu = cpu.to("cuda")
-        r.reserve(gpu.n_mesh_instances, gpu.n_meshlet_instances)
-        r.prepared_frame = PreparedFrame.create(gpu)
-        main = CullGeometryContext(init_cull_meshes=False, cull_flags=L.CULL_TEST_ALL, cull_camera=gpu.cull_camera())
-        r.seed_meshlet_instances(main, gpu.n_meshlet_instances)
-        r.cull_geometry(main)
-        pv = [float(x) for x in cpu.camera["projection_view"]]
-        visdepth = torch.empty((H, W), dtype=torch.int64, device="cuda")
-        self.depth = torch.zeros((H, W), dtype=torch.float32, device="cuda")
-        r.draw_visbuffer(main, pv, W, H, visdepth, clear=True, depth=ImageAttachment.depth(self.depth))
-        torch.cuda.synchronize()
-        self.inv = np.linalg.inv(np.asarray(pv, np.float64).reshape(4, 4).T).T.reshape(-1).astype(np.float32)
-        mats, offs, zn = virtual_shadow_matrices(list(cpu.camera["position"]), LIGHT, MAX_SHADOW_DIST, first_clipmap_width, count, page_table_size=n)
-        self.clip = pack_clipmaps(mats, offs, zn)
-        self.vctx = VirtualShadowmapContext.create(self.depth, self.inv, (W, H), self.clip, with_physical=True, first_clipmap_width=first_clipmap_width,
-                                                   virtual_extent=float(n * shape["page_size"]), **shape)
-        cam = gpu.cull_camera()
-        for i in range(16):
-            cam.projection_view[i] = float(mats[count - 1][i])
-        for i in range(3):
-            cam.position[i] = float(-LIGHT[i])
-        cam.near_clip = zn
-        self.sframe = PreparedFrame.create(gpu, expand=False)
-        self.sctx = CullGeometryContext(use_hpb=True, init_cull_meshes=True, cull_flags=L.CULL_TEST_FRUSTUM, cull_camera=cam, hpb_attachment=self.vctx.hpb_attachment,
-                                        vsm_clipmaps_buffer=self.vctx.vsm_clipmaps_buffer, vsm_clipmap_dirty_flags_buffer=self.vctx.vsm_clipmap_dirty_flags_buffer,
-                                        vsm_clipmap_count=count)
-        self.dctx = VsmDrawContext.create(self.vctx, self.sctx)
-        self.normal = normals_from_depth(self.depth, self.inv, cpu.camera["position"])
-        self.rctx = ShadowResolveContext.create(self.vctx, self.normal, LIGHT, Z_LENGTH)
-        c, y, x = np.mgrid[0:count, 0:n, 0:n]
-        self.keep = torch.from_numpy(np.where((7 * x + 13 * y + c) % 3 == 0, ~np.int32(4), np.int32(-1)).astype(np.int32)).cuda()
-
-    def shadow_path(self, stream=None):
-        r = self.r
-        r.update_virtual_shadowmap(self.vctx, stream=stream)
-        r.prepared_frame = self.sframe
-        r.cull_geometry(self.sctx, stream=stream)
-        r.draw_physical_pages(self.dctx, stream=stream)
-        if self.evict:
-            self.vctx.virtual_page_table &= self.keep
-        r.resolve_shadowmap(self.rctx, stream=stream)
-
-    def got(self):
-        torch.cuda.synchronize()
-        return self.rctx.resolved_shadows_attachment.data.view(self.H, self.W).cpu().numpy().copy()
-
-    def want(self, stats=None):
-        phys = self.shape["physical_page_table_size"]
-        return RM.resolve(self.rctx.depth_attachment.data.view(self.H, self.W).cpu().numpy(), self.rctx.normal_attachment.cpu().numpy(),
-                          self.vctx.virtual_page_table.cpu().numpy(), self.clip.numpy(), self.vctx.physical_page_image.data.view(phys, phys).cpu().numpy(),
-                          self.inv, (self.W, self.H), LIGHT, Z_LENGTH, first_clipmap_width=self.fcw, bias=self.vctx.clipmap_selection_bias,
-                          virtual_extent=self.vctx.virtual_extent, stats=stats, **self.shape)
-
-    def check(self, stats=None):
-        got, want = self.got(), self.want(stats)
-        bad = int((got.view(np.uint32) != want.view(np.uint32)).sum())
-        assert bad == 0, f"{bad} of {got.size} pixels differ"
-        return got
 
 
 def _outcomes(st):

@@ -7,6 +7,8 @@ import torch
 from hypothesis import assume, given, settings, strategies as st
 
 import oracle
+from scenes import _coverage
+
 
 def f32(x):
     return float(np.float32(x))
@@ -86,8 +88,6 @@ def test_project_aabb_contains_the_projected_centre(x, y, z, e):
 def test_raster_fan_is_watertight(tri, seed):
     """A point inside a front-facing triangle splits it into three: together they cover exactly what the whole covers,
     no pixel twice (top-left rule on the shared edges)."""
-    from test_raster import _coverage
-
     (ax, ay), (bx, by), (cx, cy) = tri
     area2 = (bx - ax) * (cy - ay) - (cx - ax) * (by - ay)
     if area2 == 0:

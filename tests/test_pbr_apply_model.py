@@ -11,40 +11,11 @@ import ambient_occlusion_model as AM
 import pbr_apply_model as PM
 import visbuffer_decode_model as VD
 from pbr_apply_model import HAS_CONTACT_SHADOWS, HAS_DIRECTIONAL_LIGHT, HAS_SKY, TRANSPARENT_BACKGROUND
-from vsm_resolve_model import vec3_to_oct
+from scenes import CAMERA, I16, INV_PV, SKY, SUN_INTENSITY
+from scenes import PBR_SUN as SUN
+from scenes import synthetic_inputs
 
 F = np.float32
-I16 = np.eye(4, dtype=np.float32).reshape(-1)
-
-# ---- what the GPU tests share: a camera whose w is depth + 0.5, a sun, a Sky record, and random G-buffer images ---------------------------------
-INV_PV = [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 1.0, 0.0, 0.0, 0.0, 0.5]  # column-major: h = (x, y, d, d + 0.5)
-CAMERA = (0.1, -0.2, 3.0)
-SUN = (0.3, 0.5, 0.8)  # not unit length: the rule does not normalise it
-SUN_INTENSITY = 2.5
-SKY = dict(base_ambient_color=(0.03, 0.03, 0.03), sky_solid_color=(0.25, 0.5, 1.0, 1.0), sky_ambient_color=(0.2, 0.3, 0.4), sky_has_texture=False)
-
-
-def synthetic_inputs(W, H, seed, empty=0.15) -> dict:
-    """Random images in the producers' formats: depth in (0.05, 0.95) with a share of empty (0.0) pixels, any albedo and m/r/o bytes, mapped and
-    smooth normals of random directions (every octant, the fold included), mostly-zero emissive words of finite patterns, ambient occlusion and
-    the two shadow terms in [0, 1] with exact 0 and 1 among them."""
-    rng = np.random.default_rng(seed)
-    depth = rng.uniform(0.05, 0.95, (H, W)).astype(np.float32)
-    depth[rng.random((H, W)) < empty] = 0.0
-
-    def octs():
-        v = rng.normal(size=(H, W, 3)).astype(np.float32)
-        e = vec3_to_oct(tuple(v[..., c] / np.linalg.norm(v, axis=-1).astype(np.float32) for c in range(3)))
-        return AM.to_half_bits(e[0]), AM.to_half_bits(e[1])
-
-    (r, g), (b, a) = octs(), octs()
-    normal = np.stack([r, g, b, a], axis=-1).astype(np.uint16)
-    finite = lambda bits, m: np.where((rng.integers(0, 1 << bits, (H, W)) >> m) == 31, 0, rng.integers(0, 1 << bits, (H, W)))  # noqa: E731
-    emissive = (finite(11, 6) | (finite(11, 6) << 11) | (finite(10, 5) << 22)).astype(np.uint32)
-    emissive[rng.random((H, W)) < 0.6] = 0
-    unit = lambda: np.clip(rng.uniform(-0.2, 1.2, (H, W)), 0.0, 1.0).astype(np.float32)  # noqa: E731
-    return dict(depth=depth, albedo=rng.integers(0, 1 << 32, (H, W), dtype=np.uint64).astype(np.uint32), normal=normal, emissive=emissive,
-                mro=rng.integers(0, 1 << 32, (H, W), dtype=np.uint64).astype(np.uint32), ao=AM.to_half_bits(unit()), resolved=unit(), contact=unit())
 
 
 # ---- the rules ------------------------------------------------------------------------------------------------------------------------------------

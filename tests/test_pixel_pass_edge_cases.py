@@ -10,23 +10,14 @@ import pytest
 import ambient_occlusion_model as AM
 import contact_shadows_model as CM
 import vsm_resolve_model as RM
-from test_ambient_occlusion_model import PROJ, hilbert
-from test_contact_shadows_model import I16, class_counts
+from scenes import (AO_FAR, AO_WIDE, AO_RESOLUTIONS, CS_CLASSES, CS_SETTINGS, EXTENT_IDS, EXTENTS, HILBERT_POISON, I16, LIGHT, MAX_SHADOW_DIST, NAN16, NAN32, PROJ, REFERENCE,
+                    RESOLVE_SOURCE, Z_LENGTH, ao_inputs, assert_resolve_sweep_is_not_degenerate, class_counts, cs_depth, cs_runs, hilbert, occluder_scene, resample,
+                    resolve_counts)
 
 F = np.float32
 
-# below one 8 x 8 wave tile; exactly one and one-plus-one wave tile, 16 x 16 block and 32 x 32 prefilter block in each axis separately; strips
-# one texel wide or high that span several tiles; every combination of upper prefilter levels collapsed to max(1, dim >> k)
-EXTENTS = [(1, 1), (1, 7), (7, 1), (2, 2), (5, 3), (8, 8), (9, 7), (15, 17), (16, 16), (17, 9), (31, 33), (32, 32), (33, 31), (47, 1), (1, 47),
-           (64, 3), (129, 65)]
-EXTENT_IDS = [f"{w}x{h}" for w, h in EXTENTS]
 
 # ---- the poison of the guard bands ----------------------------------------------------------------------------------------------------------
-NAN32 = 0x7FC00000   # around float inputs: a read changes the result
-NAN16 = 0x7E00       # around the normals
-HILBERT_POISON = 0xFFFF  # around the Hilbert table (its entries are 0..4095)
-OUT32 = 0x7FC00BAD   # around 32-bit outputs and between the prefiltered levels: a NaN as a float, no edge word the checker produces nearby
-OUT16 = 0x7EAD       # around the half outputs: a NaN half
 
 
 def holds(a, bits, dtype) -> bool:
@@ -34,31 +25,6 @@ def holds(a, bits, dtype) -> bool:
 
 
 # ---- ambient occlusion ----------------------------------------------------------------------------------------------------------------------
-AO_FAR = 100.0
-AO_SKY_DEPTH = F(0.005)  # linear 200 under PROJ (linear = 1 / depth): beyond far * 0.999
-AO_WIDE = dict(slice_count=3, samples_per_slice_side=8, effect_radius=400.0)  # the sample distances reach all five levels at every extent
-AO_RESOLUTIONS = [((33, 31), (40.0, 25.0)), ((33, 31), (33.5, 30.25))]  # resolution is a float argument of its own
-
-
-def ao_seed(W, H):
-    return 1000 * W + H
-
-
-@functools.lru_cache(maxsize=None)
-def ao_inputs(W, H):
-    """(depth float32 [H, W], normal uint16 [H, W, 4]): a seeded device depth in (0.05, 0.95) with about one texel in twelve sky (none in an
-    image of fewer than four texels; one non-sky texel always stays), and view-space normals of mixed directions that face the camera."""
-    rng = np.random.default_rng(ao_seed(W, H))
-    depth = rng.uniform(0.05, 0.95, (H, W)).astype(np.float32)
-    if W * H >= 4:
-        sky = rng.permutation(W * H)[:max(1, W * H // 12)]
-        depth.reshape(-1)[sky] = AO_SKY_DEPTH
-    n = np.stack([rng.uniform(-1, 1, (H, W)), rng.uniform(-1, 1, (H, W)), rng.uniform(0.15, 1, (H, W))], axis=-1)
-    n = (n / np.linalg.norm(n, axis=-1, keepdims=True)).astype(np.float32)
-    depth.setflags(write=False)
-    normal = RM.encode_normal(n)
-    normal.setflags(write=False)
-    return depth, normal
 
 
 def ao_want(W, H, resolution=None, stats=None, **kw):
@@ -113,38 +79,6 @@ def test_ambient_occlusion_inputs_hold_no_poison():
 
 
 # ---- contact shadows ------------------------------------------------------------------------------------------------------------------------
-CS_STEPS = (1, 2, 64)
-CS_SUNS = ((0.7, 0.6, 0.3), (-0.7, 0.6, 0.3), (0.7, -0.6, 0.3), (-0.7, -0.6, 0.3))  # one per quadrant of screen space
-CS_SETTINGS = dict(thickness=8.0, shadow_length=4.0)  # rays of four units through surfaces 5 .. 30 units away: a quarter of the image wide
-CS_NEAR = 0.1
-# the classes test_contact_shadows_model.FLOORS names, and a hit that writes exactly 1.0
-CS_CLASSES = ("sky", "miss", "hit_zero", "hit_partial", "hit_one", "rejected", "n_lower", "n_between", "n_upper", "end_clip")
-
-
-def cs_cameras():
-    """{name: (inv_projection_view, view, projection, near_clip)}: the 60 degree reversed-Z camera at the origin, and the rotated one."""
-    from oxylus_amd.synth import perspective_reversed_z
-    from test_gpu_contact_shadows import rotated_camera
-
-    proj = perspective_reversed_z(60.0, 1.0, CS_NEAR, 1000.0).numpy()
-    inv = np.linalg.inv(proj.astype(np.float64).reshape(4, 4).T).T.reshape(-1).astype(np.float32)
-    return {"identity": (inv, I16.copy(), proj, CS_NEAR), "rotated": rotated_camera()}
-
-
-@functools.lru_cache(maxsize=None)
-def cs_depth(W, H):
-    """A seeded reversed-Z depth of surfaces 5 .. 30 units away (depth = near / distance), about one texel in twelve sky (0.0)."""
-    rng = np.random.default_rng(7000 + 1000 * W + H)
-    depth = (F(CS_NEAR) / rng.uniform(5.0, 30.0, (H, W)).astype(np.float32)).astype(np.float32)
-    if W * H >= 4:
-        depth.reshape(-1)[rng.permutation(W * H)[:max(1, W * H // 12)]] = 0.0
-    depth.setflags(write=False)
-    return depth
-
-
-def cs_runs():
-    """(camera name, camera, steps, sun) of every run of one extent."""
-    return [(name, cam, steps, sun) for name, cam in cs_cameras().items() for steps in CS_STEPS for sun in CS_SUNS]
 
 
 @functools.lru_cache(maxsize=None)
@@ -189,44 +123,6 @@ def test_contact_shadows_inputs_hold_no_poison():
 
 
 # ---- shadow resolve -------------------------------------------------------------------------------------------------------------------------
-RESOLVE_SOURCE = 128  # Frame(renderer, 128, 128, seed=67) of tests/test_gpu_vsm_resolve.py
-
-
-RESOLVE_FIRST_ROW = 32  # the rows above hold mostly sky: the horizon crosses the middle row, which a 1-high strip would otherwise land on
-
-
-def resample_index(dim, first=0, source=RESOLVE_SOURCE):
-    """Nearest neighbour: the source row / column in [first, source) under the centre of each of `dim` texels."""
-    span = source - first
-    return first + np.minimum(((np.arange(dim) * 2 + 1) * span) // (2 * dim), span - 1)
-
-
-def resample(image, W, H):
-    """[source, source, ...] -> [H, W, ...] by nearest neighbour, from the rows RESOLVE_FIRST_ROW .. source - 1 and every column."""
-    return np.ascontiguousarray(np.asarray(image)[resample_index(H, RESOLVE_FIRST_ROW)][:, resample_index(W)])
-
-
-def resolve_counts(st, got):
-    oc = st["outcome"]
-    c = {name: int((oc == k).sum()) for name, k in (("sky", RM.SKY), ("hard", RM.HARD), ("no_blocker", RM.NO_BLOCKER), ("all_blockers", RM.ALL_BLOCKERS),
-                                                    ("pcf", RM.PCF))}
-    c.update(non_sky=int((oc != RM.SKY).sum()), lit=int(((oc != RM.SKY) & (got == 1.0)).sum()), shadowed=int((got == 0.0).sum()),
-             partial=int(((got > 0.0) & (got < 1.0)).sum()), taps=st["taps"], misses=st["misses"], fallback_minus=st["fallback_minus"],
-             fallback_plus=st["fallback_plus"])
-    return c
-
-
-def assert_resolve_sweep_is_not_degenerate(per_extent: dict):
-    """per_extent: {(W, H): resolve_counts}.  A non-sky pixel at every extent; over the sweep fully lit, fully shadowed and partial pixels
-    and a tap served by a neighbouring clipmap."""
-    total = {}
-    for extent, c in per_extent.items():
-        assert c["non_sky"] >= 1, (extent, c)
-        for k, v in c.items():
-            total[k] = total.get(k, 0) + v
-    print(total)
-    assert total["lit"] > 0 and total["shadowed"] > 0 and total["partial"] > 0 and total["fallback_minus"] + total["fallback_plus"] > 0, total
-    return total
 
 
 def resolve_frame_from_the_models():
@@ -239,7 +135,6 @@ def resolve_frame_from_the_models():
     import vsm_draw_model as DM
     import vsm_pages_model as VP
     from oxylus_amd.synth import normals_from_depth, pack_clipmaps, virtual_shadow_matrices
-    from test_gpu_vsm_resolve import LIGHT, MAX_SHADOW_DIST, REFERENCE, Z_LENGTH, occluder_scene
 
     S, count, n, ps, phys = RESOLVE_SOURCE, REFERENCE["clipmap_count"], REFERENCE["page_table_size"], REFERENCE["page_size"], REFERENCE["physical_page_table_size"]
     s = occluder_scene(67)

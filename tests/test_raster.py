@@ -6,39 +6,7 @@ import torch
 
 from oxylus_amd import lib as L
 from oxylus_amd.synth import SceneSpec, build_meshlets_simple, make_scene, make_scene_from_mesh
-
-
-def _flat_scene(tris_xy, W, H, z=0.5):
-    """One mesh instance, identity world matrix, vertices at the given PIXEL coordinates (half-exact values) and a
-    projection_view that maps pixels to NDC with w = 1: screen = (ndc * 0.5 + 0.5) * extent = the pixel coordinate."""
-    import oracle
-
-    verts = sorted({tuple(v) for t in tris_xy for v in t})
-    index = {v: i for i, v in enumerate(verts)}
-    pos = torch.tensor([[x, y, z] for x, y in verts], dtype=torch.float32)
-    tris = torch.tensor([[index[tuple(v)] for v in t] for t in tris_xy], dtype=torch.int64)
-    meshlets, vidx, micro = build_meshlets_simple(tris)
-    b, m6, q = oracle.build_meshlet_bounds(pos, meshlets, vidx, micro)
-    s = make_scene_from_mesh(1, b, meshlets, micro, vidx, q, m6, device="cpu")
-    s.transforms[0] = torch.eye(4).flatten()
-    pv = torch.zeros(4, 4)  # [col][row]
-    pv[0, 0], pv[3, 0] = 2.0 / W, -1.0
-    pv[1, 1], pv[3, 1] = 2.0 / H, -1.0
-    pv[2, 2], pv[3, 3] = 1.0, 1.0
-    n_tris = tris.shape[0]
-    # index list as cull_triangles writes it: (meshlet instance << 8) | corner, all triangles of meshlet 0
-    idx = torch.tensor([(0 << 8) | c for c in range(3 * n_tris)], dtype=torch.int32)
-    return s, pv.flatten().tolist(), idx
-
-
-def _coverage(tris_xy, W=16, H=16):
-    import oracle
-
-    s, pv, idx = _flat_scene(tris_xy, W, H)
-    vd = torch.zeros((H, W), dtype=torch.int64)
-    oracle.draw_visbuffer(s, s.meshlet_instances, idx, pv, W, H, vd)
-    depth, vis = oracle.resolve_visbuffer(vd)
-    return depth.numpy(), vis.numpy()
+from scenes import _coverage, _flat_scene
 
 
 def test_front_face_right_triangle_coverage_and_top_left_rule(oracle_lib):

@@ -2,143 +2,22 @@
 lambda at a vertex, the sRGB / unorm8 / UF11 / UF10 encoders, the explicit half flush -- and, on a frame drawn by the CPU oracle's rasteriser,
 that the barycentrics interpolate the depth the rasteriser stored.  Also the scene builders and the main frame tests/test_gpu_visbuffer_decode.py
 uses, with the proof that the frame is not degenerate."""
-import math
-
 import numpy as np
 import pytest
 import torch
 
 import visbuffer_decode_model as VD
 import vsm_draw_model as DM
-from ambient_occlusion_model import to_half_bits
+from pixel_rules import to_half_bits
+from scenes import DECODE_MAIN_SIZE as MAIN_SIZE
+from scenes import build_scene
+from scenes import decode_assert_not_degenerate as assert_not_degenerate
+from scenes import main_scene
 
 F = np.float32
-MAIN_SIZE, MAIN_SEED = 256, 61
 
 
 # ---- scenes ----------------------------------------------------------------------------------------------------------------------------------
-def build_scene(meshes, instances, materials=None):
-    """A CPU Scene of several meshes: `meshes` = [(positions f32 [V, 3] with half-exact values or not, triangles i64 [T, 3], normals f32 [V, 3] or
-    None)], `instances` = [(mesh index, world 4 x 4 row-major, material index)].  One LOD per mesh; meshlets by the greedy clusteriser, bounds and
-    the quantised streams by the CPU oracle; the camera of synth.make_scene (identity view, reversed-Z perspective).  Returns (scene, indices):
-    the index list of every triangle as cull_triangles writes it."""
-    import oracle
-    from oxylus_amd.synth import Scene, SceneSpec, build_meshlets_simple, perspective_reversed_z
-
-    parts = {k: [] for k in ("bounds", "meshlets", "micro", "vidx", "positions", "normals")}
-    starts = {k: [] for k in ("meshlet_start", "micro_start", "vidx_start", "mesh_vertex_start")}
-    run = dict(meshlet=0, micro=0, vidx=0, vertex=0)
-    counts, mesh6, with_normals = [], [], all(m[2] is not None for m in meshes)
-    for pos, tris, nrm in meshes:
-        pos = torch.as_tensor(np.asarray(pos, dtype=np.float32))
-        meshlets, vidx, micro = build_meshlets_simple(torch.as_tensor(np.asarray(tris, dtype=np.int64)))
-        b, m6, q = oracle.build_meshlet_bounds(pos, meshlets, vidx, micro)
-        for k, v in (("bounds", b), ("meshlets", meshlets), ("micro", micro), ("vidx", vidx), ("positions", q)):
-            parts[k].append(v)
-        if with_normals:
-            parts["normals"].append(oracle.quantize_vertex_streams(normals=torch.as_tensor(np.asarray(nrm, dtype=np.float32)))[1])
-        for k, r in (("meshlet_start", "meshlet"), ("micro_start", "micro"), ("vidx_start", "vidx"), ("mesh_vertex_start", "vertex")):
-            starts[k].append(run[r])
-        run["meshlet"] += meshlets.shape[0]
-        run["micro"] += micro.shape[0]
-        run["vidx"] += vidx.shape[0]
-        run["vertex"] += pos.shape[0]
-        counts.append((int(meshlets.shape[0]), int(pos.shape[0])))
-        mesh6.append(m6)
-    n_meshes, M = len(meshes), len(instances)
-    lods = torch.zeros((n_meshes, 8), dtype=torch.int64)
-    meshes_t = torch.zeros((n_meshes, 8), dtype=torch.int64)
-    for i, (k, v) in enumerate(counts):
-        lods.view(torch.int32)[i, 11] = lods.view(torch.int32)[i, 12] = k
-        meshes_t.view(torch.int32)[i, 6], meshes_t.view(torch.int32)[i, 7] = v, 1
-        meshes_t.view(torch.int32)[i, 10:16] = mesh6[i].to(torch.float32).view(torch.int32)
-    mesh_instances = torch.zeros((M, 5), dtype=torch.int32)
-    transforms = torch.zeros((M, 16), dtype=torch.float32)
-    mli, offset = [], 0
-    for i, (mesh, world, material) in enumerate(instances):
-        mesh_instances[i] = torch.tensor([mesh, 0, material, i, offset], dtype=torch.int32)
-        transforms[i] = torch.as_tensor(np.asarray(world, dtype=np.float32).T.reshape(-1).copy())  # column-major
-        mli += [(i, k) for k in range(counts[mesh][0])]
-        offset += counts[mesh][0]
-    proj = perspective_reversed_z(60.0, 1.0, 0.1, 1000.0)
-    camera = {"projection_view": proj.tolist(), "position": [0.0, 0.0, 0.0], "acceptable_lod_error": 2.0, "resolution": [4096.0, 4096.0], "near_clip": 0.1}
-    spec = SceneSpec(n_mesh_instances=M, meshlets_per_mesh=max(c[0] for c in counts), share_meshes=n_meshes)
-    s = Scene(spec=spec, device=torch.device("cpu"), lods=lods, meshes=meshes_t, transforms=transforms, mesh_instances=mesh_instances,
-              meshlet_instances=torch.tensor(mli, dtype=torch.int32).reshape(-1, 2), camera=camera, n_meshes=n_meshes, lod_meshlet_counts=[spec.meshlets_per_mesh],
-              _lod_tables={k: torch.tensor(v, dtype=torch.int64) for k, v in starts.items()},
-              normals=torch.cat(parts["normals"]).contiguous() if with_normals else None, materials=materials,
-              **{k: torch.cat(parts[k]).contiguous() for k in ("bounds", "meshlets", "micro", "vidx", "positions")})
-    s.bind()
-    meshlets_all = s.meshlets
-    first = {i: starts["meshlet_start"][i] for i in range(n_meshes)}
-    idx = [(i << 8) | c for i, (inst, k) in enumerate(mli) for c in range(3 * int(meshlets_all[first[instances[inst][0]] + k, 3]))]
-    return s, torch.tensor(idx, dtype=torch.int64).to(torch.int32)
-
-
-def world_matrix(scale=(1.0, 1.0, 1.0), axis=(0.0, 1.0, 0.0), degrees=0.0, translate=(0.0, 0.0, 0.0)):
-    """translate * rotate(axis, degrees) * scale, 4 x 4 row-major float64."""
-    a = np.asarray(axis, dtype=np.float64)
-    a = a / np.linalg.norm(a)
-    c, s = math.cos(math.radians(degrees)), math.sin(math.radians(degrees))
-    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
-    m = np.eye(4)
-    m[:3, :3] = (np.eye(3) + s * K + (1 - c) * (K @ K)) @ np.diag(scale)
-    m[:3, 3] = translate
-    return m
-
-
-def occluder_mesh(seed):
-    """The floor and the 40 floating quads of tests/test_gpu_vsm_resolve.py::occluder_scene, both windings, with the flat normal (0, 1, 0)."""
-    rng = np.random.default_rng(seed)
-    verts, tris = {}, []
-
-    def vid(p):
-        return verts.setdefault(tuple(float(v) for v in p), len(verts))
-
-    def quad(x0, x1, z0, z1, y):
-        a, b, c, d = (vid(p) for p in ((x0, y, z0), (x1, y, z0), (x1, y, z1), (x0, y, z1)))
-        tris.extend([[a, b, c], [a, c, d], [a, c, b], [a, d, c]])
-
-    quad(-24, 24, -4, -64, -2)
-    for _ in range(40):
-        cx, cz, y = int(rng.integers(-14, 15)), int(rng.integers(-40, -7)), int(rng.integers(0, 11))
-        w, d = int(rng.integers(1, 4)), int(rng.integers(1, 4))
-        quad(cx - w, cx + w, cz - d, cz + d, y)
-    pos = np.array(list(verts), dtype=np.float32)
-    return pos, np.array(tris, dtype=np.int64), np.tile(np.array([0.0, 1.0, 0.0], dtype=np.float32), (len(pos), 1))
-
-
-def sphere_mesh(n=20):
-    """synth.make_mesh("sphere"): smooth normals = position minus centre, normalised; both windings."""
-    from oxylus_amd.synth import make_mesh
-
-    pos, tris = make_mesh("sphere", n=n)
-    pos, tris = pos.numpy(), tris.numpy()
-    nrm = pos - np.array([1.0, -2.0, 0.5], dtype=np.float32)
-    nrm = nrm / np.linalg.norm(nrm, axis=1, keepdims=True)
-    return pos, np.concatenate([tris, tris[:, [0, 2, 1]]]), nrm.astype(np.float32)
-
-
-def main_materials():
-    """Five materials: plain, metallic, rough with an alpha, emissive, and one with values outside [0, 1]."""
-    from oxylus_amd.synth import pack_materials
-
-    albedo = [[0.8, 0.7, 0.6, 1.0], [0.95, 0.64, 0.54, 1.0], [0.02, 0.3, 0.002, 0.5], [0.0, 0.0, 0.0, 1.0], [1.5, -0.25, 0.5, 2.0]]
-    emissive = [[0, 0, 0], [0, 0, 0], [0, 0, 0], [4.0, 1.25, 0.03], [70000.0, 1e-5, 0.5]]
-    return pack_materials(albedo, emissive, roughness=[0.9, 0.25, 0.5, 1.0, 0.1], metallic=[0.0, 1.0, 0.5, 0.0, 0.75])
-
-
-def main_scene(seed=MAIN_SEED):
-    """The occluder floor and quads (flat normals, material 0) and four smooth-normal spheres under non-uniform scales and rotations
-    (materials 1..4; the last sphere names material 5 = material_count: the default Material)."""
-    sph = sphere_mesh()
-    instances = [(0, np.eye(4), 0),
-                 (1, world_matrix((1.0, 0.55, 1.5), (1, 2, 0.5), 35.0, (-7.0, 3.0, -18.0)), 1),
-                 (1, world_matrix((0.6, 1.3, 0.8), (0.3, 1, -1), -50.0, (6.0, 2.0, -12.0)), 2),
-                 (1, world_matrix((1.2, 1.2, 0.4), (1, 0, 1), 70.0, (1.0, 6.0, -25.0)), 3),
-                 (1, world_matrix((0.35, 0.5, 0.3), (0, 0, 1), 20.0, (-1.5, 0.5, -6.0)), 4),
-                 (1, world_matrix((0.5, 0.25, 0.5), (1, 1, 1), 10.0, (2.5, -0.5, -7.0)), 5)]
-    return build_scene([occluder_mesh(seed), sph], instances, main_materials())
 
 
 def oracle_frame(scene, indices, W, H):
@@ -155,15 +34,6 @@ def decode_scene(scene, vis, depth, stats=None, **kw):
     m = scene.materials
     return VD.decode(scene, scene.meshlet_instances, vis, depth, scene.camera["projection_view"], None if m is None else m.numpy(),
                      0 if m is None else m.numel() // 56, stats=stats, **kw)
-
-
-def assert_not_degenerate(st, img, pixels):
-    """The floors of the GPU test's main frame."""
-    rg = img["normal"][st["ys"], st["xs"], :2]
-    distinct = len(np.unique(rg.astype(np.uint32)[:, 0] | (rg.astype(np.uint32)[:, 1] << 16)))
-    figures = dict(decoded=st["decoded"], empty=st["empty"], triangles=st["distinct_triangles"], materials=st["distinct_materials"], rg_values=distinct)
-    assert st["decoded"] >= 0.30 * pixels and st["empty"] >= 0.05 * pixels and st["distinct_triangles"] >= 200 and st["distinct_materials"] >= 4 and distinct >= 1000, figures
-    return figures
 
 
 # ---- answers worked out on paper ---------------------------------------------------------------------------------------------------------------

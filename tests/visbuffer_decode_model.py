@@ -7,8 +7,7 @@ from __future__ import annotations
 import numpy as np
 
 import vsm_draw_model as DM
-from ambient_occlusion_model import pack_unorm4x8, pow_rule, to_half_bits
-from vsm_resolve_model import cross, vec3_to_oct
+from pixel_rules import _u32, cross, mul_mp, pack_ufloat, pack_unorm4x8, pow_rule, to_half_bits, vec3_to_oct
 
 F = np.float32
 TERRAIN_INSTANCE_ID = 0xFFFFFE
@@ -17,10 +16,6 @@ MATERIAL_BYTES = 56
 SRGB_EXPONENT = F(1.0) / F(2.4)
 IMAGES = ("albedo", "normal", "emissive", "mro")
 COUNTER_NAMES = ("decoded", "empty", "zero_vertex_index", "default_material")
-
-
-def _u32(a) -> np.ndarray:
-    return np.ascontiguousarray(np.asarray(a)).view(np.uint32)
 
 
 def dequantize_half_flush(h) -> np.ndarray:
@@ -49,22 +44,6 @@ def unorm8(v) -> np.ndarray:
     return pack_unorm4x8(v, np.zeros_like(v), np.zeros_like(v), np.zeros_like(v))
 
 
-def pack_ufloat(v, mbits: int) -> np.ndarray:
-    """binary32 -> the unsigned small float with 5 exponent bits and `mbits` mantissa bits (UF11: 6, UF10: 5), rule 8 of the header."""
-    v = np.atleast_1d(np.asarray(v, dtype=np.float32))
-    bits = v.view(np.uint32).astype(np.int64)
-    top = (1 << mbits) - 1
-    e = (bits >> 23) - 127 + 15
-    m = bits & 0x7FFFFF
-    normal = (e << mbits) | (m >> (23 - mbits))
-    sh = np.clip((23 - mbits) + (1 - e), 0, 63)
-    denormal = np.where(sh > 24, 0, (0x800000 | m) >> sh)
-    out = np.where(e >= 31, (30 << mbits) | top, np.where(e >= 1, normal, denormal))
-    out = np.where(bits == 0x7F800000, 31 << mbits, out)
-    out = np.where((bits >> 31) != 0, 0, out)
-    return np.where(np.isnan(v), (31 << mbits) | top, out).astype(np.uint32)
-
-
 def normal_half(x) -> np.ndarray:
     """binary16 bits, round to nearest even, denormals kept, every NaN 0x7E00."""
     x = np.asarray(x, dtype=np.float32)
@@ -77,11 +56,6 @@ def normal_matrix(world) -> np.ndarray:
     b = [(world[..., 4 * j + 0], world[..., 4 * j + 1], world[..., 4 * j + 2]) for j in range(3)]
     cols = [cross(b[1], b[2]), cross(b[2], b[0]), cross(b[0], b[1])]
     return np.stack([np.stack([cols[c][r] for c in range(3)], axis=-1) for r in range(3)], axis=-2)
-
-
-def mul_mp(m, p):
-    """DM.mul_mp in the dtype of its operands (the checker runs it in binary32, the tolerance measurement in binary64)."""
-    return np.stack([((m[..., r] * p[..., 0] + m[..., 4 + r] * p[..., 1]) + m[..., 8 + r] * p[..., 2]) + m[..., 12 + r] for r in range(4)], axis=-1)
 
 
 @np.errstate(all="ignore")

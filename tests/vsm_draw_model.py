@@ -9,6 +9,7 @@ from __future__ import annotations
 import numpy as np
 
 import vsm_pages_model as VM
+from pixel_rules import _u32, mul_mp
 
 F = np.float32
 VISIBLE, DIRTY, BACKED = VM.VISIBLE, VM.DIRTY, VM.BACKED
@@ -16,21 +17,11 @@ WMIN, GUARD = F(0.0009765625), F(64.0)
 SMALL = 8
 
 
-def _u32(a) -> np.ndarray:
-    return np.ascontiguousarray(np.asarray(a)).view(np.uint32)
-
-
 def dequantize_half(h) -> np.ndarray:
     """com::dequantize_half: denormals flush to signed zero, everything else is the IEEE value."""
     h = np.asarray(h).astype(np.uint16)
     f = h.view(np.float16).astype(np.float32)
     return np.where((h & 0x7FFF) < 0x400, np.where((h & 0x8000) != 0, F(-0.0), F(0.0)), f).astype(np.float32)
-
-
-def mul_mp(m, p) -> np.ndarray:
-    """mul(M, float4(p, 1)), every row ((m0 p0 + m1 p1) + m2 p2) + m3 in binary32; m column-major [..., 16], p [..., 3] -> [..., 4]."""
-    m, p = np.asarray(m, dtype=np.float32), np.asarray(p, dtype=np.float32)
-    return np.stack([((m[..., r] * p[..., 0] + m[..., 4 + r] * p[..., 1]) + m[..., 8 + r] * p[..., 2]) + m[..., 12 + r] for r in range(4)], axis=-1)
 
 
 def decode_indices(indices, wide=0):

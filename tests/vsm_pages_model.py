@@ -6,6 +6,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from pixel_rules import _m, unproject
+
 VISIBLE, DIRTY, BACKED, INVALIDATED, ALLOC_FAILED = 1, 2, 4, 8, 16
 F = np.float32
 
@@ -33,17 +35,6 @@ def clipmap_index(r, bias: float, count: int) -> np.ndarray:
 def wrap(virt, offset, n: int):
     """page_coords_virtual_to_wrapped: floor_mod(virt + offset, n), the result in [0, n)."""
     return np.mod(np.asarray(virt, dtype=np.int64) + np.asarray(offset, dtype=np.int64), n)
-
-
-def _m(m, r, c):
-    return m[..., c * 4 + r]
-
-
-def unproject(m, u, v, d):
-    """Camera::unproject_uv (scene.slang:189-193): (M (uv * 2 - 1, d, 1)).xyz / w, rows ((m0 a + m1 b) + m2 c) + m3."""
-    nx, ny = u * F(2.0) - F(1.0), v * F(2.0) - F(1.0)
-    h = [((_m(m, i, 0) * nx + _m(m, i, 1) * ny) + _m(m, i, 2) * d) + _m(m, i, 3) for i in range(4)]
-    return h[0] / h[3], h[1] / h[3], h[2] / h[3]
 
 
 def unpack_clipmaps(clipmaps):

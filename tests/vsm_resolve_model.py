@@ -6,7 +6,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from vsm_pages_model import BACKED, clipmap_index, texel_length, unpack_clipmaps, unproject, wrap
+from pixel_rules import COS_C, PIO2, SIN_C, _m, cos_sin_turn, cross, decode_normal, dot, length, normalize, unproject, vec3_to_oct
+from vsm_pages_model import BACKED, clipmap_index, texel_length, unpack_clipmaps, wrap
 
 F = np.float32
 BLOCKER_SAMPLES, PCF_SAMPLES = 16, 24
@@ -15,12 +16,6 @@ SQRT2, QUANTIZE = F(1.41421356), F(2.0 ** -22)
 MISS = F(-1.0)
 # outcome of a pixel
 SKY, HARD, NO_BLOCKER, ALL_BLOCKERS, PCF = 0, 1, 2, 3, 4
-
-PIO2 = float.fromhex("0x1.921fb54442d18p+0")
-SIN_C = [float.fromhex(h) for h in ("-0x1.5555555555555p-3", "0x1.1111111111111p-7", "-0x1.a01a01a01a01ap-13", "0x1.71de3a556c734p-19")]
-COS_C = [float.fromhex(h) for h in ("-0x1.0000000000000p-1", "0x1.5555555555555p-5", "-0x1.6c16c16c16c17p-10", "0x1.a01a01a01a01ap-16",
-                                    "-0x1.27e4fb7789f5cp-22")]
-
 
 # ---- rule 5: noise ------------------------------------------------------------------------------------------------------------------------
 def pcg2d(x, y):
@@ -65,28 +60,6 @@ def fract(x):
 
 
 # ---- rule 6: rotation ---------------------------------------------------------------------------------------------------------------------
-def cos_sin_turn(t):
-    """(cos, sin) of 2 pi t for binary32 t in [0, 1): exact reduction to an octant, binary64 Horner, one rounding to binary32."""
-    t = np.asarray(t, dtype=np.float32)
-    q4 = t * F(4.0)        # exact
-    k = np.floor(q4)
-    f = q4 - k             # exact, in [0, 1)
-    swap = f > F(0.5)
-    g = np.where(swap, F(1.0) - f, f)  # exact, in [0, 0.5]
-    a = g.astype(np.float64) * PIO2
-    z = a * a
-    ps = ((SIN_C[3] * z + SIN_C[2]) * z + SIN_C[1]) * z + SIN_C[0]
-    s = a + (a * z) * ps
-    pc = (((COS_C[4] * z + COS_C[3]) * z + COS_C[2]) * z + COS_C[1]) * z + COS_C[0]
-    c = 1.0 + z * pc
-    sf, cf = s.astype(np.float32), c.astype(np.float32)
-    sq, cq = np.where(swap, cf, sf), np.where(swap, sf, cf)
-    ki = k.astype(np.int64)
-    cos = np.where(ki == 0, cq, np.where(ki == 1, -sq, np.where(ki == 2, -cq, sq)))
-    sin = np.where(ki == 0, sq, np.where(ki == 1, cq, np.where(ki == 2, -sq, -cq)))
-    return cos.astype(np.float32), sin.astype(np.float32)
-
-
 def cos_sin_turn_scalar(t):
     """The same, one value, in Python floats (binary64) with explicit binary32 roundings."""
     q4 = float(F(t)) * 4.0
@@ -104,55 +77,12 @@ def cos_sin_turn_scalar(t):
     return [(cq, sq), (-sq, cq), (-cq, -sq), (sq, -cq)][k]
 
 
-# ---- vectors ------------------------------------------------------------------------------------------------------------------------------
-def cross(a, b):
-    """cross(a, b).x = a.y * b.z - a.z * b.y and its rotations, each product rounded before the subtraction."""
-    return (a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0])
-
-
-def dot(a, b):
-    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
-
-
-def length(a):
-    return np.sqrt(dot(a, a))
-
-
-def normalize(a):
-    ln = length(a)
-    return (a[0] / ln, a[1] / ln, a[2] / ln)
-
-
-def oct_to_vec3(ex, ey):
-    """com::oct_to_vec3 (common/encoding.slang:7-15)."""
-    vz = (F(1.0) - np.abs(ex)) - np.abs(ey)
-    sx = np.where(ex >= 0, F(1.0), F(-1.0))
-    sy = np.where(ey >= 0, F(1.0), F(-1.0))
-    neg = vz < 0
-    vx = np.where(neg, (F(1.0) - np.abs(ey)) * sx, ex)
-    vy = np.where(neg, (F(1.0) - np.abs(ex)) * sy, ey)
-    return normalize((vx, vy, vz))
-
-
-def vec3_to_oct(v):
-    """com::vec3_to_oct (common/encoding.slang:17-21): what visbuffer_decode stores."""
-    s = F(1.0) / ((np.abs(v[0]) + np.abs(v[1])) + np.abs(v[2]))
-    px, py = v[0] * s, v[1] * s
-    sx = np.where(px >= 0, F(1.0), F(-1.0))
-    sy = np.where(py >= 0, F(1.0), F(-1.0))
-    return np.where(v[2] <= 0, (F(1.0) - np.abs(py)) * sx, px), np.where(v[2] <= 0, (F(1.0) - np.abs(px)) * sy, py)
-
-
 def perpendicular_basis(L):
     L = tuple(F(v) for v in L)
     axis = (F(0), F(1), F(0)) if abs(L[1]) < F(0.999) else (F(1), F(0), F(0))
     with np.errstate(all="ignore"):
         t = normalize(cross(axis, L))
         return t, cross(L, t)
-
-
-def _m(m, r, c):
-    return m[..., c * 4 + r]
 
 
 def _row(c, r, p):
@@ -224,13 +154,6 @@ def tap_with_fallback(S: Shape, base, p, stats=None):
 
 
 # ---- rules 1-3 and 7 ------------------------------------------------------------------------------------------------------------------------
-def decode_normal(normal_u16x4):
-    """.b and .a of the R16G16B16A16Sfloat image as binary32 (exact), then flat_N = normalize(oct_to_vec3(.ba))."""
-    h = np.ascontiguousarray(np.asarray(normal_u16x4)).view(np.uint16)
-    ex, ey = h[..., 2].view(np.float16).astype(np.float32), h[..., 3].view(np.float16).astype(np.float32)
-    return normalize(oct_to_vec3(ex, ey))
-
-
 def resolve(depth, normal, table, clipmaps, physical, inv_pv, resolution, light_dir, z_length, *, page_size=128, page_table_size=64,
             physical_page_table_size=8192, clipmap_count=10, first_clipmap_width=10.0, bias=-1.5, virtual_extent=8192.0, stats: dict = None):
     """One oxc_resolve_shadowmap call: float32 [H, W].  `normal` is the uint16 / int16 [H, W, 4] image.  `stats` receives the tap counts
