@@ -1196,8 +1196,8 @@ oxc_status oxc_apply_eye_adaptation(oxc_ctx* ctx, const oxc_eye_adaptation_conte
  * common/color.slang:79-81, the extents at RendererInstance.cpp:509-510 and 1257-1267, Texture::calculate_mip_count at
  * include/Asset/Texture.hpp:144-146, the samplers LinearSamplerBorder and LinearSamplerClamped at include/Render/Utils/VukCommon.hpp:
  * 103-120), the pass directly behind apply_eye_adaptation and the first reader of its exposure.
- * Out of scope: tone mapping, the lens effects, FXAA, the atmosphere branch.  bloom_intensity is set by apply_bloom for the tonemap; the
- * C++ shim and the Python twin carry it, the library does not read it.
+ * Out of scope: FXAA, the atmosphere branch.  bloom_intensity is set by apply_bloom for the tonemap: the C++ shim and the Python twin
+ * carry it to oxc_apply_tonemap, this call does not read it.
  * Arithmetic: the canonical binary32 arithmetic of oxc_apply_pbr -- round to nearest even, left to right, no contraction, IEEE division
  * (1.0 / x is a division), min / max through fminf / fmaxf (a NaN operand gives the other one), clamp(x, a, b) = min(max(x, a), b),
  * lerp(a, b, t) = a + (b - a) * t.  UF11 / UF10 decode is the exact decode of oxc_apply_pbr step 2, the pack the truncating one of
@@ -1252,7 +1252,7 @@ oxc_status oxc_apply_eye_adaptation(oxc_ctx* ctx, const oxc_eye_adaptation_conte
  * with the source; exposure_buffer, when read, 4-byte aligned and 8 bytes (without the flag it is not looked at and may be null);
  * threshold, soft_threshold, clamp_value and radius finite.  No scratch, no allocation, no host synchronisation; capturable into a HIP
  * graph on one stream as a linear chain of kernels. */
-#define OXC_SCENE_HAS_BLOOM (1u << 3) /* GPU::SceneFlags, for callers that mirror RendererInstance.cpp:1282; the library does not read it */
+#define OXC_SCENE_HAS_BLOOM (1u << 3) /* GPU::SceneFlags (RendererInstance.cpp:1282); oxc_apply_bloom does not read it, oxc_apply_tonemap's scene_flags does */
 /* A mip pyramid of 4-byte (B10G11R11) or 8-byte (R16G16B16A16 Sfloat) texels in one device allocation: oxc_image's fields under the
  * same names, then the allocation's size.  Level k is max(1, width >> k) x max(1, height >> k) texels, row-major, at byte offset
  * level_offset[k]; the levels may lie in any order and with gaps. */
@@ -1279,6 +1279,132 @@ typedef struct oxc_bloom_context {
 } oxc_bloom_context;
 
 oxc_status oxc_apply_bloom(oxc_ctx* ctx, const oxc_bloom_context* context, void* hip_stream);
+
+/* ---- tonemap: exposure, bloom composite, tone curve, lens effects and the 8-bit image ------------------------------------------
+ * Replaces RendererInstance::apply_tonemap (Oxylus/src/Render/Passes/PostProcess.cpp:205-247, pipeline tonemap: passes/tonemap.slang,
+ * passes/lens.slang, common/color.slang:4-55, GPU::PostProcessSettings and GPU::TonemapType at include/Scene/SceneGPU.hpp:295-309, the
+ * scene flags at SceneGPU.hpp:258-266, the swapchain formats at RenderContext.cpp:102-105), the last pass of the frame: the HDR image
+ * oxc_apply_pbr wrote, times the exposure oxc_apply_eye_adaptation left behind, plus level 0 of the upsample pyramid oxc_apply_bloom wrote,
+ * through one of four tone curves and three lens effects into one 8-bit word per pixel.
+ * Out of scope: FXAA (in the reference it runs on the HDR image before the eye adaptation), the atmosphere branch, the unused
+ * agx_tonemapping (tonemap.slang:90-129) and the Jzazbz UCS (TONE_MAPPING_UCS is ICtCp).
+ * Arithmetic: the canonical binary32 arithmetic as the oxc_apply_bloom block states it (round to nearest even, left to right, no
+ * contraction, IEEE division and square root, min / max through fminf / fmaxf, clamp, lerp, the UF11 / UF10 / binary16 decodes), a
+ * comparison with a NaN operand is false, a float to int conversion truncates, saturates and gives 0 for a NaN; mul(M, v) row r is
+ * (M[r][0] * v.x + M[r][1] * v.y) + M[r][2] * v.z and mul(A, B) element (r, c) is (A[r][0] * B[0][c] + A[r][1] * B[1][c]) + A[r][2] * B[2][c];
+ * dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z; a decimal literal is the binary32 nearest to it.  The checker is tests/tonemap_model.py.
+ * Per pixel (x, y) of the W x H image (tonemap.slang:668-723), in this order:
+ *   1. source    (:670-671)  Stated rule, as in oxc_apply_bloom step 4: SampleLevel(input_image, tex_coord) of an image of the output's own
+ *              extent at the pixel centre is a load of texel (x, y).  source_format 0: the exact UF11 / UF11 / UF10 decode, alpha 1.0;
+ *              source_format 1: four halves through binary16 -> binary32, exact, denormals kept; alpha is the fourth.
+ *   2. exposure  (:673-678)  OXC_SCENE_HAS_EYE_ADAPTATION: color *= the second word of exposure_buffer (device data, any bit pattern);
+ *              else color *= exposure (post_process_settings.exposure).
+ *   3. bloom     (:680-683)  OXC_SCENE_HAS_BLOOM: color += bloom * bloom_intensity per channel (the product rounded, then the sum), bloom the
+ *              manual bilinear of the oxc_apply_bloom block on level 0 of bloom_upsampled_attachment, (W / 2) x (H / 2), at uv = ((f32(x) +
+ *              0.5) / f32(W), (f32(y) + 0.5) / f32(H)): g = uv * (f32(sw), f32(sh)) - 0.5, i = floor(g) converted to i32 saturating,
+ *              f = g - floor(g), lerp(lerp(t00, t10, f.x), lerp(t01, t11, f.x), f.y).  The stated difference about hardware samplers is the
+ *              same.  Address mode: repeat -- the texel coordinates are i0 = floor_mod_i(i, size) and i1 = (i0 + 1 == size ? 0 : i0 + 1)
+ *              per axis, both in [0, size - 1] for every bit pattern of uv.  STATED ASSUMPTION: the pass binds a sampler created with
+ *              only its filters set (PostProcess.cpp:228), and a zero-initialised VkSamplerCreateInfo has address mode repeat; vuk's
+ *              SamplerCreateInfo defaults could not be read where this was written.  tools/reference_capture/ is where a capture of the
+ *              reference would pin it.
+ *   4. tone curve by tonemap_type (:685-702):
+ *              0 None   nothing is applied (no clamp either: the store saturates).
+ *              1 ACES   ACES_Fitted (:37-69): v = mul(ACESInputMat, color); per channel a = v * (v + 0.0245786f) - 0.000090537f,
+ *                       b = v * (0.983729f * v + 0.4329510f) + 0.238081f, a / b; mul(ACESOutputMat, .); saturate.
+ *              2 AgX    AgX_DS (:131-262): w = max(color, 0.0); w = mul(sRGB_to_adjusted, w); per channel color_DualSection(x, 0.10, 1.0):
+ *                       x < S ? x : peak - (peak - S) * exp((-C * (x - S)) / peak) with S = peak * linear, C = peak / (peak - S); clamp 0..1;
+ *                       d = dot(w, (0.2126729, 0.7151522, 0.0721750)); w = clamp(d + (w - d) * 1.3, 0, 1); mul(inverse(sRGB_to_adjusted), w).
+ *              3 GT7    (:267-666) rec2020 = mul(XYZ_TO_REC2020_MAT, mul(REC709_TO_XYZ_MAT, color)) (two products, as written); GT7ToneMapping
+ *                       initializeAsSDR + applyToneMapping with the ICtCp UCS: rgbToICtCp and iCtCpToRgb with every sum left to right as
+ *                       written ((r * 1688.0f + g * 2146.0f) + b * 262.0f) / 4096.0f ...), inverseEotfSt2084 = exp2(m2 * (log2(c1 + c2 * ym) -
+ *                       log2(1.0f + c3 * ym))) with ym = pow(v * 100.0f / 10000.0f, m1), eotfSt2084 with its three clamps as ifs (a NaN
+ *                       passes them), evaluateCurve: x < 0 gives 0; x < linearSection_ * peakIntensity_ gives weightToe * (midPoint_ *
+ *                       pow(x / midPoint_, toeStrength_)) + weightLinear * x; else kA_ + kB_ * exp(x * kC_); smoothStep(x, e0, e1): t =
+ *                       (x - e0) / (e1 - e0), x < e0 gives 0, x > e1 gives 1, else (t * t) * (3.0f - 2.0f * t); out = sdrCorrectionFactor_ *
+ *                       min((1.0f - blendRatio_) * skewed + blendRatio_ * scaled, framebufferLuminanceTarget_); then
+ *                       mul(XYZ_TO_REC709_MAT, mul(REC2020_TO_XYZ_MAT, out)).  pow(y, m1) of a negative Rec.2020 channel (a saturated
+ *                       Rec.709 colour has one) is 0 by rule 6, where the reference's pow is undefined.
+ *   5. constants  Everything of 4 and 7 that does not depend on the pixel is evaluated ONCE per call, in the canonical binary32, in the order
+ *              the Slang writes it, ON THE HOST (the library's host code is compiled without contraction and uses the rule functions of 6,
+ *              not the platform's libm) and reaches the kernel as arguments: color_PrimariesToMatrix / color_ComputeCompressionMatrix /
+ *              inverse (:131-202) for sRGB_to_XYZ, adjusted_to_XYZ, XYZ_to_adjusted, sRGB_to_adjusted = mul(sRGB_to_XYZ, XYZ_to_adjusted)
+ *              and inverse(sRGB_to_adjusted); S, peak - S and -C of color_DualSection; kA_, kB_, kC_ (kB_ = ((-peak) * k) * exp(
+ *              linearSection_ / k)), linearSection_ * peakIntensity_, framebufferLuminanceTarget_ = 250.0f / 100.0f,
+ *              framebufferLuminanceTargetUcs_ = rgbToICtCp((target, target, target))[0], sdrCorrectionFactor_ = 1.0f / (250.0f / 100.0f),
+ *              1.0f - blendRatio_, the two e1 - e0, m2 = 78.84375f * 1.0f, 1.0f / m2, 1.0f / m1; FfxLensGetRGMag.  The checker evaluates
+ *              them the same way.
+ *   6. transcendentals  (stated difference: the reference's are implementation-defined)  pow(v, p) is the pow rule of oxc_apply_pbr,
+ *              exp2((double)p * L(v)) rounded once, and L of a negative, zero, denormal or NaN v is -Inf: such a base gives 0 for p > 0.
+ *              log2 is the log2 rule rounded to binary32 once; exp2 the exp2 rule; exp(x) = the exp2 rule's binary64 half of
+ *              (double)x * 0x1.71547652b82fep+0, rounded once; sqrt is IEEE.  cos(a): a non-finite a gives NaN; otherwise
+ *              u = (double)|a| * 0x1.45f306dc9c883p-3, t = (float)(u - floor(u)), t == 1.0f becomes 0, and the result is the cosine of the
+ *              rotation rule of oxc_resolve_shadowmap step 6 at the turn t.
+ *   7. chromatic aberration (:704-707, lens.slang:51-88)  OXC_SCENE_HAS_CHROMATIC_ABERRATION.  AS THE REFERENCE WRITES IT, the three channels
+ *              are re-sampled from the UN-EXPOSED, UN-TONEMAPPED input_image and REPLACE color: steps 2-4 have no effect on the pixel then.
+ *              That is kept.  center = (W / 2, H / 2), integer divisions; rcp = 1.0f / f32(2 * center) per axis; (redMag, greenMag) =
+ *              FfxLensGetRGMag(chromatic_aberration_amount): B = 0.00459f * amount, n(w) = 1.5220f + B / (w * w) for w = 0.612f, 0.549f,
+ *              0.464f, redMag = (n_r - 1.0f) / (n_b - 1.0f), greenMag likewise.  redShift = ((f32(coord - center) * redMag + f32(center)) +
+ *              0.5f) * rcp, greenShift with greenMag, blue at f32(coord) * rcp (no half, as written).  red = .r of the manual bilinear of
+ *              the W x H source at redShift with the repeat rule of 3, green = .g at greenShift, blue = .b.  W or H of 1 makes rcp(0)
+ *              infinite: the canonical arithmetic defines the result (Inf and NaN coordinates convert saturating, the weights are NaN,
+ *              the channel is NaN and stores as 0).  No special case.
+ *   8. vignette  (:709-711, lens.slang:115-125)  OXC_SCENE_HAS_VIGNETTE.  per axis m = cos(((f32(|coord - center|) / f32(center)) *
+ *              vignette_amount) * piOver4), piOver4 = 3.1415926535897932384626433832795f * 0.25f; m = m * m; m = m * m; color *=
+ *              clamp(m.x * m.y, 0, 1), and clamp of a NaN is 0.  A centre of 0 gives 0 / 0 = NaN: the pixel becomes 0.
+ *   9. film grain (:713-719, lens.slang:9-44, 98-106)  OXC_SCENE_HAS_FILM_GRAIN.  v = pcg3d16(u32x3(coord / divisor, film_grain_seed)) in
+ *              wrapping u32; fine = f32(v.xy) * (1.0 / 65536.0) - 0.5, exact; P = f32(coord) / film_grain_scale + fine; simplex(P): u =
+ *              (P.x + P.y) * F2, Pi = round(P + u) with halves to even (SPIR-V leaves halves open; stated), v = (Pi.x + Pi.y) * G2,
+ *              Pf0 = P - (Pi - v), F2 and G2 the binary32 nearest (sqrt(3) - 1) / 2 and (3 - sqrt(3)) / 6; grain = 1.0f - 2.0f *
+ *              exp2((-sqrt(Pf0.x * Pf0.x + Pf0.y * Pf0.y)) * 3.0f); color = color + (grain * min(color, 1.0f - color)) * film_grain_amount.
+ *              A decision the reference leaves open: coord / (i32)(grainScaleVal / 8) divides by zero for every scale below 8, the
+ *              engine's default 1.0 included (the FidelityFX original divides in floating point).  The rule here: divisor = the saturating
+ *              truncation of film_grain_scale / 8.0f, and a divisor of 0 is taken as 1; a negative one is refused by the limits.
+ *  10. alpha     (:721)  OXC_SCENE_TRANSPARENT_BACKGROUND ? the source's alpha : 1.0.
+ *  11. store     output_format 0: R8G8B8A8 Srgb, 1: B8G8R8A8 Srgb (the swapchain formats), 2: R8G8B8A8 Unorm; byte 0 is the first-named
+ *              channel.  Srgb formats, per colour channel: c = saturate(color); c <= 0.0031308f ? c * 12.92f : 1.055f * pow(c, p) - 0.055f
+ *              with p the binary32 nearest 1 / 2.4; then u32(floor(saturate(e) * 255.0f + 0.5f)) as in oxc_decode_visbuffer.  Alpha and
+ *              format 2 go through that last expression directly.  A NaN stores 0.  Stated difference: the hardware's own sRGB
+ *              conversion of a colour attachment has a tolerance; this is the rule.
+ * Limits (else OXC_INVALID_ARG, nothing launched, nothing written; the first broken rule in this order gives the message): width and
+ * height not zero; at most 65536 a side; width * height at most 2^32 - 1; source_format 0 or 1; output_format 0, 1 or 2; tonemap_type
+ * 0 .. 3; final_attachment aligned to its texel (4 or 8 bytes) with one texel per pixel; dst_attachment 4-byte aligned with one u32 per
+ * pixel; with OXC_SCENE_HAS_BLOOM: width and height at least 2, the pyramid's width == W / 2, height == H / 2 and 1 <= levels <= 13,
+ * level 0 aligned to its texel and inside the pyramid's `bytes` (the other levels are not looked at); dst_attachment shares no byte with
+ * final_attachment, with level 0 of the pyramid or with exposure_buffer (each only when read); with OXC_SCENE_HAS_EYE_ADAPTATION
+ * exposure_buffer 4-byte aligned and 8 bytes; every float setting the flags read finite -- exposure without HasEyeAdaptation,
+ * bloom_intensity with HasBloom, chromatic_aberration_amount, vignette_amount, film_grain_scale and film_grain_amount with their flags;
+ * film_grain_scale > 0 with HasFilmGrain.  Without its flag the pyramid and the exposure buffer are not looked at and may be null.
+ * Every other bit of scene_flags is ignored.  One launch, no scratch, no allocation, no host synchronisation; capturable into a HIP
+ * graph as one more link of the linear chain. */
+#define OXC_SCENE_HAS_FILM_GRAIN (1u << 6) /* GPU::SceneFlags (SceneGPU.hpp:258-266) */
+#define OXC_SCENE_HAS_CHROMATIC_ABERRATION (1u << 7)
+#define OXC_SCENE_HAS_VIGNETTE (1u << 8)
+#define OXC_TONEMAP_NONE 0u /* GPU::TonemapType (SceneGPU.hpp:304-309) */
+#define OXC_TONEMAP_ACES 1u
+#define OXC_TONEMAP_AGX 2u
+#define OXC_TONEMAP_GT7 3u
+typedef struct oxc_tonemap_context {
+  uint32_t struct_size; /* sizeof(oxc_tonemap_context) */
+  uint32_t width, height;
+  uint32_t source_format;             /* 0: B10G11R11 UfloatPack32;  1: R16G16B16A16 Sfloat -- the source and the bloom pyramid */
+  uint32_t output_format;             /* 0: R8G8B8A8 Srgb;  1: B8G8R8A8 Srgb;  2: R8G8B8A8 Unorm */
+  uint32_t scene_flags;               /* HasEyeAdaptation, HasBloom, HasFilmGrain, HasChromaticAberration, HasVignette, TransparentBackground */
+  uint32_t tonemap_type;              /* OXC_TONEMAP_* */
+  float exposure;                     /* GPU::PostProcessSettings (SceneGPU.hpp:295-302): 1.0; read without HasEyeAdaptation */
+  float chromatic_aberration_amount;  /* 0.5 */
+  float vignette_amount;              /* 0.5 */
+  float film_grain_scale;             /* 1.0 */
+  float film_grain_amount;            /* 0.5 */
+  uint32_t film_grain_seed;           /* 0 */
+  float bloom_intensity;              /* pp.bloom_intensity, what apply_bloom left in PostProcessContext: 0.1 */
+  oxc_buffer final_attachment;        /* in: what oxc_apply_pbr wrote */
+  oxc_image_pyramid bloom_upsampled_attachment; /* in, read only with OXC_SCENE_HAS_BLOOM: what oxc_apply_bloom wrote; only level 0 is read */
+  oxc_buffer exposure_buffer;         /* in, read only with OXC_SCENE_HAS_EYE_ADAPTATION: {f32 adapted_luminance, f32 exposure} */
+  oxc_buffer dst_attachment;          /* out: u32[height][width] */
+} oxc_tonemap_context;
+
+oxc_status oxc_apply_tonemap(oxc_ctx* ctx, const oxc_tonemap_context* context, void* hip_stream);
 
 /* ---- multi-GPU exchange: one process per GPU, RCCL over xGMI ---------------------------
  * The meshlet-instance array shards by contiguous range and every rank culls its shard on its own; the only

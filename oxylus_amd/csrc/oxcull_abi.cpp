@@ -2147,6 +2147,79 @@ oxc_status oxc_apply_bloom(oxc_ctx* ctx, const oxc_bloom_context* c, void* hip_s
   return OXC_OK;
 }
 
+oxc_status oxc_apply_tonemap(oxc_ctx* ctx, const oxc_tonemap_context* c, void* hip_stream) {
+  if (!ctx) return OXC_INVALID_ARG;
+  if (!c || c->struct_size != sizeof(oxc_tonemap_context)) return fail(ctx, OXC_INVALID_ARG, "apply_tonemap: bad context / struct_size");
+  const char* const entry = "apply_tonemap";
+  const uint32_t flags = c->scene_flags;
+  const bool has_exposure = (flags & OXC_SCENE_HAS_EYE_ADAPTATION) != 0u, has_bloom = (flags & OXC_SCENE_HAS_BLOOM) != 0u;
+  const bool has_ca = (flags & OXC_SCENE_HAS_CHROMATIC_ABERRATION) != 0u, has_vignette = (flags & OXC_SCENE_HAS_VIGNETTE) != 0u;
+  const bool has_grain = (flags & OXC_SCENE_HAS_FILM_GRAIN) != 0u;
+  if (c->width == 0u || c->height == 0u) return bad_arg(ctx, entry, "the extent must not be zero");
+  if (c->width > 65536u || c->height > 65536u) return bad_arg(ctx, entry, "extent beyond 65536");
+  const uint64_t pixels = (uint64_t)c->width * c->height;
+  if (pixels > 0xFFFFFFFFull) return bad_arg(ctx, entry, "width * height beyond 2^32 - 1");
+  if (c->source_format > 1u) return bad_arg(ctx, entry, "source_format must be 0 (B10G11R11) or 1 (R16G16B16A16 Sfloat)");
+  if (c->output_format > 2u) return bad_arg(ctx, entry, "output_format must be 0 (R8G8B8A8 Srgb), 1 (B8G8R8A8 Srgb) or 2 (R8G8B8A8 Unorm)");
+  if (c->tonemap_type > 3u) return bad_arg(ctx, entry, "tonemap_type must be 0 (None), 1 (ACES), 2 (AgX) or 3 (GT7)");
+  const uint32_t texel = c->source_format ? 8u : 4u;
+  if (bad_pixel_buffer(c->final_attachment, pixels, texel))
+    return bad_arg(ctx, entry, "final_attachment must be one aligned u32 per pixel (format 0) or one 8-byte aligned u16x4 per pixel (format 1)");
+  if (bad_pixel_buffer(c->dst_attachment, pixels, 4u)) return bad_arg(ctx, entry, "dst_attachment must be one aligned u32 per pixel");
+  const oxc_image_pyramid& p = c->bloom_upsampled_attachment;
+  const uint32_t bw = c->width / 2u, bh = c->height / 2u;
+  if (has_bloom) {
+    if (c->width < 2u || c->height < 2u) return bad_arg(ctx, entry, "HasBloom: width and height must be at least 2");
+    if (p.width != bw || p.height != bh || p.levels < 1u || p.levels > 13u)
+      return bad_arg(ctx, entry, "bloom_upsampled_attachment must have width / 2, height / 2 and at least one level");
+    const uint64_t size = (uint64_t)bw * bh * texel, off = p.level_offset[0];
+    if (!p.dptr || ((reinterpret_cast<uintptr_t>(p.dptr) + off) & (texel - 1u)) || off > p.bytes || size > p.bytes - off)
+      return bad_arg(ctx, entry, "bloom_upsampled_attachment: level 0 must be aligned to its texel and lie inside the allocation");
+  }
+  const uintptr_t dst_lo = reinterpret_cast<uintptr_t>(c->dst_attachment.dptr);
+  const ByteSpan dst = {dst_lo, dst_lo + (uintptr_t)(pixels * 4u)};
+  const uintptr_t src_lo = reinterpret_cast<uintptr_t>(c->final_attachment.dptr);
+  bool shared = dst.overlaps({src_lo, src_lo + (uintptr_t)(pixels * texel)});
+  if (has_bloom) {
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(p.dptr) + (uintptr_t)p.level_offset[0];
+    shared = shared || dst.overlaps({lo, lo + (uintptr_t)((uint64_t)bw * bh * texel)});
+  }
+  if (has_exposure && c->exposure_buffer.dptr) {
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(c->exposure_buffer.dptr);
+    shared = shared || dst.overlaps({lo, lo + 8u});
+  }
+  if (shared) return bad_arg(ctx, entry, "dst_attachment must not overlap final_attachment, level 0 of bloom_upsampled_attachment or exposure_buffer");
+  if (has_exposure && bad_pixel_buffer(c->exposure_buffer, 2u, 4u)) return bad_arg(ctx, entry, "exposure_buffer must be two aligned f32");
+  if ((!has_exposure && !std::isfinite(c->exposure)) || (has_bloom && !std::isfinite(c->bloom_intensity)) || (has_ca && !std::isfinite(c->chromatic_aberration_amount)) ||
+      (has_vignette && !std::isfinite(c->vignette_amount)) || (has_grain && (!std::isfinite(c->film_grain_scale) || !std::isfinite(c->film_grain_amount))))
+    return bad_arg(ctx, entry, "every setting the scene flags read must be finite");
+  if (has_grain && !(c->film_grain_scale > 0.0f)) return bad_arg(ctx, entry, "film_grain_scale must be above 0");
+  OXC_HIP(ctx, hipSetDevice(ctx->device));
+  OXC_ORDER(ctx, hip_stream);
+  const hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  TonemapArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.src = c->final_attachment.dptr;
+  a.bloom = has_bloom ? static_cast<const char*>(p.dptr) + p.level_offset[0] : nullptr;
+  a.exposure = has_exposure ? static_cast<const float*>(c->exposure_buffer.dptr) : nullptr;
+  a.dst = static_cast<uint32_t*>(c->dst_attachment.dptr);
+  a.w = c->width, a.h = c->height, a.bw = bw, a.bh = bh;
+  a.flags = flags, a.format = c->source_format, a.output_format = c->output_format, a.tonemap_type = c->tonemap_type;
+  a.exposure_setting = c->exposure;
+  a.vignette_amount = c->vignette_amount;
+  a.grain_scale = c->film_grain_scale, a.grain_amount = c->film_grain_amount, a.grain_seed = c->film_grain_seed;
+  a.bloom_intensity = c->bloom_intensity;
+  if (has_grain) {  // step 9: the saturating truncation of film_grain_scale / 8.0f, 0 taken as 1
+    const float q = c->film_grain_scale / 8.0f;
+    a.grain_divisor = q >= 2147483648.0f ? 0x7FFFFFFFu : (uint32_t)(int32_t)q;
+  }
+  if (a.grain_divisor == 0u) a.grain_divisor = 1u;
+  tonemap_constants(has_ca ? c->chromatic_aberration_amount : 0.0f, a.k);  // step 5
+  launch_tonemap(a, s);
+  OXC_HIP(ctx, hipGetLastError());
+  return OXC_OK;
+}
+
 oxc_status oxc_generate_ambient_occlusion(oxc_ctx* ctx, const oxc_ambient_occlusion_context* c, void* hip_stream) {
   if (!ctx) return OXC_INVALID_ARG;
   if (!c || c->struct_size != sizeof(oxc_ambient_occlusion_context)) return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: bad context / struct_size");

@@ -675,6 +675,33 @@ struct BloomArgs {
 uint32_t bloom_default_tail(uint32_t w2, uint32_t h2, uint32_t levels);
 uint32_t bloom_lowest_tail(uint32_t w2, uint32_t h2, uint32_t levels);  // the lowest T OXC_TUNE_BLOOM_TAIL_LEVEL can force
 void launch_bloom(const BloomArgs& a, hipStream_t s);
+// oxcull_tonemap.hip: exposure, bloom composite, tone curve, lens effects and the 8-bit store (oxc_apply_tonemap)
+// What of the tone curves and of FfxLensGetRGMag does not depend on the pixel (step 5 of the header block): evaluated once per call on the
+// host by tonemap_constants(), binary32 in the Slang's order.
+struct TonemapConstants {
+  float agx_in[9], agx_out[9];  // sRGB_to_adjusted and its inverse, row-major
+  float agx_s, agx_span, agx_neg_c, agx_peak;  // color_DualSection: S = peak * linear, peak - S, -(peak / (peak - S)), peak
+  float gt_sdr, gt_target, gt_target_ucs;      // sdrCorrectionFactor_, framebufferLuminanceTarget_, framebufferLuminanceTargetUcs_
+  float gt_mid, gt_toe, gt_ka, gt_kb, gt_kc;   // midPoint_, toeStrength_, kA_, kB_, kC_
+  float gt_lin_peak, gt_mid_span;              // linearSection_ * peakIntensity_, midPoint_ - 0.0
+  float gt_blend, gt_one_minus_blend, gt_fade_start, gt_fade_end, gt_fade_span;
+  float pq_m2, pq_inv_m2, pq_inv_m1;           // 78.84375 * exponentScaleFactor, 1.0 / m2, 1.0 / m1
+  float red_mag, green_mag;                    // FfxLensGetRGMag(chromatic_aberration_amount)
+};
+struct TonemapArgs {
+  const void* src;        // w x h texels: u32 (B10G11R11, format 0) or u16x4 (R16G16B16A16 Sfloat, format 1)
+  const void* bloom;      // U level 0, bw x bh texels of the source's format; read with HasBloom
+  const float* exposure;  // {adapted_luminance, exposure}; read with HasEyeAdaptation
+  uint32_t* dst;          // [h][w]
+  uint32_t w, h, bw, bh;
+  uint32_t flags, format, output_format, tonemap_type;
+  float exposure_setting, vignette_amount, grain_scale, grain_amount, bloom_intensity;
+  uint32_t grain_seed;
+  uint32_t grain_divisor;  // the saturating truncation of grain_scale / 8.0f, 0 taken as 1
+  TonemapConstants k;
+};
+void tonemap_constants(float chromatic_aberration_amount, TonemapConstants& k);
+void launch_tonemap(const TonemapArgs& a, hipStream_t s);
 // oxcull_bounds.hip: meshlet bounds producer
 void launch_build_meshlet_bounds(const float* pos, uint32_t vertex_count, const void* meshlets, uint32_t meshlet_count, const uint32_t* vidx,
                                  const uint8_t* micro, void* out_bounds, float* out_mesh6, void* out_qpos, float* meshlet_minmax, float* normals,

@@ -153,7 +153,8 @@ struct PostProcessContext {
   Extent3D extent = {};
   Buffer final_attachment = {};
   ImagePyramid bloom_upsampled_attachment = {};  // extent / 2, Texture::calculate_mip_count levels (RendererInstance.cpp:1257-1267); written by apply_bloom
-  float bloom_intensity = 0.0f;                  // set by apply_bloom for the tonemap
+  float bloom_intensity = 0.0f;                  // set by apply_bloom, read by apply_tonemap
+  Buffer dst_attachment = {};                    // the 8-bit image apply_tonemap writes, one u32 per pixel
 };
 
 // The five pp.bloom_* cvars apply_bloom reads, with the engine's defaults (RendererCVar.cpp:44-48)
@@ -166,6 +167,22 @@ struct BloomCVars {
 };
 
 namespace GPU {
+// SceneGPU.hpp:295-302
+struct PostProcessSettings {
+  float exposure = 1.0f;
+  float chromatic_aberration_amount = 0.5f;
+  float vignette_amount = 0.5f;
+  float film_grain_scale = 1.0f;
+  float film_grain_amount = 0.5f;
+  uint32_t film_grain_seed = 0;
+};
+// SceneGPU.hpp:304-309
+enum struct TonemapType : uint32_t {
+  None = 0,
+  ACES,
+  AgX,
+  GT7,
+};
 // SceneGPU.hpp:278-284
 struct HistogramLuminanceInfo {
   float min_exposure = -6.0f;
@@ -209,6 +226,8 @@ public:
   GPU::Sky sky_data = {};
   GPU::Camera camera = {};
   GPU::HistogramLuminanceInfo eye_adaptation = {};  // read by apply_eye_adaptation
+  GPU::PostProcessSettings post_proces_settings = {};  // read by apply_tonemap (the reference spells it so: RendererInstance.hpp)
+  GPU::TonemapType tonemap_type = GPU::TonemapType::AgX;
   Buffer histogram_bin_indices_buffer = {};         // u32[256]: the reference's transient buffer, here caller-owned; this frame's counts after the call
 
   void set_stream(void* hip_stream) { stream_ = hip_stream; }
@@ -449,6 +468,33 @@ public:
     c.bloom_downsampled_attachment = bloom_downsampled_attachment;
     c.bloom_upsampled_attachment = context.bloom_upsampled_attachment;
     check(oxc_apply_bloom(ctx_, &c, stream_));
+  }
+  // RendererInstance::apply_tonemap (Passes/PostProcess.cpp:205-247): exposure, bloom composite, tone curve, lens effects and the 8-bit store
+  // of context.final_attachment into context.dst_attachment, whose format (the swapchain's: 0 R8G8B8A8 Srgb, 1 B8G8R8A8 Srgb; 2 R8G8B8A8 Unorm)
+  // the caller names.  Reads post_proces_settings and tonemap_type (the reference's spelling), gpu_scene_flags, context.bloom_intensity as
+  // apply_bloom left it, and prepared_frame.exposure_buffer.  Rules: include/oxcull.h, oxc_apply_tonemap.
+  auto apply_tonemap(PostProcessContext& context, uint32_t dst_format = 0) -> Buffer {
+    oxc_tonemap_context c = {};
+    c.struct_size = sizeof c;
+    c.width = context.extent.width;
+    c.height = context.extent.height;
+    c.source_format = (gpu_scene_flags & OXC_SCENE_TRANSPARENT_BACKGROUND) ? 1u : 0u;
+    c.output_format = dst_format;
+    c.scene_flags = gpu_scene_flags;
+    c.tonemap_type = static_cast<uint32_t>(tonemap_type);
+    c.exposure = post_proces_settings.exposure;
+    c.chromatic_aberration_amount = post_proces_settings.chromatic_aberration_amount;
+    c.vignette_amount = post_proces_settings.vignette_amount;
+    c.film_grain_scale = post_proces_settings.film_grain_scale;
+    c.film_grain_amount = post_proces_settings.film_grain_amount;
+    c.film_grain_seed = post_proces_settings.film_grain_seed;
+    c.bloom_intensity = context.bloom_intensity;
+    c.final_attachment = context.final_attachment;
+    c.bloom_upsampled_attachment = context.bloom_upsampled_attachment;
+    c.exposure_buffer = prepared_frame.exposure_buffer;
+    c.dst_attachment = context.dst_attachment;
+    check(oxc_apply_tonemap(ctx_, &c, stream_));
+    return context.dst_attachment;
   }
   auto build_meshlet_bounds(oxc_meshlet_bounds_desc desc) -> void {
     desc.struct_size = sizeof desc;

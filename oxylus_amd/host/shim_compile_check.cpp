@@ -82,5 +82,16 @@ int main(int argc, char**) {
   } catch (const std::exception& e) {
     std::printf("expected (no attachments bound): %s\n", e.what());
   }
+  try {  // the last pass of the frame: the tonemap, with the lens effects on
+    auto post_process_context = PostProcessContext{.extent = {.width = 1920, .height = 1080}, .final_attachment = Buffer{}, .bloom_upsampled_attachment = ImagePyramid{},
+                                                   .bloom_intensity = BloomCVars{}.intensity, .dst_attachment = Buffer{}};
+    self.gpu_scene_flags |= OXC_SCENE_HAS_FILM_GRAIN | OXC_SCENE_HAS_CHROMATIC_ABERRATION | OXC_SCENE_HAS_VIGNETTE;
+    self.post_proces_settings = GPU::PostProcessSettings{.exposure = 1.0f, .film_grain_seed = 7};
+    self.tonemap_type = GPU::TonemapType::GT7;
+    auto dst_attachment = self.apply_tonemap(post_process_context, /*dst_format: B8G8R8A8 Srgb*/ 1);
+    (void)dst_attachment;
+  } catch (const std::exception& e) {
+    std::printf("expected (no attachments bound): %s\n", e.what());
+  }
   return 0;
 }

@@ -655,7 +655,7 @@ class BloomContext:
     """oxc_bloom_context: RendererInstance::apply_bloom (Passes/PostProcess.cpp:79-203).  `create` takes the image apply_pbr wrote -- int32
     [H, W] (B10G11R11) or int16 [H, W, 4] (R16G16B16A16 Sfloat); the format follows from the shape --, the scene flags (only
     L.SCENE_HAS_EYE_ADAPTATION is read) and the exposure buffer apply_eye_adaptation left behind, and allocates the two pyramids.
-    bloom_intensity is what apply_bloom hands to the tonemap; the library does not read it."""
+    bloom_intensity is what apply_bloom hands to the tonemap: TonemapContext.create reads it from here; oxc_apply_bloom does not."""
     final_attachment: torch.Tensor                # in
     exposure_buffer: Optional[torch.Tensor]       # in with SCENE_HAS_EYE_ADAPTATION: float32 [2]
     bloom_downsampled_attachment: BloomPyramid    # out
@@ -688,6 +688,57 @@ class BloomContext:
         c.exposure_buffer = _buf(self.exposure_buffer)
         c.bloom_downsampled_attachment = self.bloom_downsampled_attachment.c()
         c.bloom_upsampled_attachment = self.bloom_upsampled_attachment.c()
+        return c
+
+
+@dataclass
+class TonemapContext:
+    """oxc_tonemap_context: RendererInstance::apply_tonemap (Passes/PostProcess.cpp:205-247).  `create` takes the image apply_pbr wrote -- int32
+    [H, W] (B10G11R11) or int16 [H, W, 4] (R16G16B16A16 Sfloat); the format follows from the shape --, the scene flags, the tone curve, the
+    exposure buffer apply_eye_adaptation left behind and the BloomContext apply_bloom ran on (its upsample pyramid and its bloom_intensity),
+    and allocates the 8-bit destination, int32 [H, W].  The six GPU::PostProcessSettings fields carry the engine's defaults."""
+    final_attachment: torch.Tensor                            # in
+    exposure_buffer: Optional[torch.Tensor]                   # in with SCENE_HAS_EYE_ADAPTATION: float32 [2]
+    bloom_upsampled_attachment: Optional[BloomPyramid]        # in with SCENE_HAS_BLOOM: only level 0 is read
+    dst_attachment: torch.Tensor                              # out: int32 [H, W]
+    width: int
+    height: int
+    source_format: int
+    output_format: int = L.TONEMAP_OUT_R8G8B8A8_SRGB
+    scene_flags: int = 0
+    tonemap_type: int = L.TONEMAP_ACES
+    exposure: float = 1.0                                     # SceneGPU.hpp:295-302
+    chromatic_aberration_amount: float = 0.5
+    vignette_amount: float = 0.5
+    film_grain_scale: float = 1.0
+    film_grain_amount: float = 0.5
+    film_grain_seed: int = 0
+    bloom_intensity: float = 0.1
+
+    @staticmethod
+    def create(final_attachment: torch.Tensor, scene_flags: int = 0, tonemap_type: int = L.TONEMAP_ACES, exposure_buffer: Optional[torch.Tensor] = None,
+               bloom: Optional[BloomContext] = None, output_format: int = L.TONEMAP_OUT_R8G8B8A8_SRGB, **settings) -> "TonemapContext":
+        fmt = L.EYE_SOURCE_R16G16B16A16 if final_attachment.dim() == 3 else L.EYE_SOURCE_B10G11R11
+        H, W = int(final_attachment.shape[0]), int(final_attachment.shape[1])
+        dst = torch.zeros((H, W), dtype=torch.int32, device=final_attachment.device)
+        if bloom is not None:
+            settings.setdefault("bloom_intensity", bloom.bloom_intensity)
+        return TonemapContext(final_attachment, exposure_buffer, bloom.bloom_upsampled_attachment if bloom is not None else None, dst, W, H, fmt,
+                              int(output_format), int(scene_flags), int(tonemap_type), **settings)
+
+    def c(self) -> L.TonemapContext:
+        c = L.TonemapContext()
+        c.struct_size = C.sizeof(L.TonemapContext)
+        c.width, c.height, c.source_format, c.output_format = int(self.width), int(self.height), int(self.source_format), int(self.output_format)
+        c.scene_flags, c.tonemap_type = int(self.scene_flags) & 0xFFFFFFFF, int(self.tonemap_type)
+        c.exposure, c.chromatic_aberration_amount, c.vignette_amount = float(self.exposure), float(self.chromatic_aberration_amount), float(self.vignette_amount)
+        c.film_grain_scale, c.film_grain_amount, c.film_grain_seed = float(self.film_grain_scale), float(self.film_grain_amount), int(self.film_grain_seed) & 0xFFFFFFFF
+        c.bloom_intensity = float(self.bloom_intensity)
+        c.final_attachment = _buf(self.final_attachment)
+        if self.bloom_upsampled_attachment is not None:
+            c.bloom_upsampled_attachment = self.bloom_upsampled_attachment.c()
+        c.exposure_buffer = _buf(self.exposure_buffer)
+        c.dst_attachment = _buf(self.dst_attachment)
         return c
 
 
@@ -989,6 +1040,13 @@ class RendererInstance:
         c = context.c()
         self._keep = context
         self._check(self._lib.oxc_apply_bloom(self._ctx, C.byref(c), self._stream(stream)))
+
+    def apply_tonemap(self, context: TonemapContext, stream=None):
+        """Passes/PostProcess.cpp:205-247: exposure, bloom composite, tone curve, lens effects and the 8-bit store of `context.final_attachment`
+        into `context.dst_attachment`, one launch (include/oxcull.h, oxc_apply_tonemap)."""
+        c = context.c()
+        self._keep = context
+        self._check(self._lib.oxc_apply_tonemap(self._ctx, C.byref(c), self._stream(stream)))
 
     def debug_pbr_apply_stats(self, stream=None) -> dict:
         """What the last apply_pbr did, after debug_set_tuning(L.TUNE_PBR_APPLY_STATS, 1) (measurement hook; synchronises)."""
