@@ -1,53 +1,23 @@
-"""Time oxc_apply_tonemap (tools/, not bench.py) on the lit frame of tools/eye_adaptation_bench.py: the configs[2] scene drawn, decoded and lit
+"""Time oxc_apply_tonemap (tools/, not bench.py) on pass_frames.lit_frame: the configs[2] scene drawn, decoded and lit
 under 8 lights at 3840 x 2160 (random ambient occlusion and shadow terms), with the exposure oxc_apply_eye_adaptation leaves behind and the
 pyramid oxc_apply_bloom writes, per tone curve, with the lens flags off and all on.  One more row per curve is the same call on a 2 x 2
 image: the launch floor.  Prints one JSON line per row: ms per call (HIP events around the call, median and minimum of --steps after
 --warmup), the bytes the rule reads and writes at least once and, with --hbm-tbs, the streaming floor of those bytes."""
-import argparse
-import json
-import os
-import sys
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import pass_frames as pf  # first: it puts the repository root on sys.path
+from oxylus_amd import lib as L
+from oxylus_amd.renderer import BloomContext, EyeAdaptationContext, TonemapContext, exposure_buffer
 
 
-def time_call(r, c, steps, warmup):
-    times = []
-    for i in range(warmup + steps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        r.apply_tonemap(c)
-        b.record()
-        b.synchronize()
-        if i >= warmup:
-            times.append(a.elapsed_time(b))
-    return float(np.median(times)), float(np.min(times))
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--size", default="3840x2160")
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--meshlets", type=int, default=10_000_000)
+def main(argv=None):
+    ap = pf.common_arguments()
     ap.add_argument("--transparent", action="store_true", help="the RGBA16F source of a transparent background instead of B10G11R11")
-    ap.add_argument("--hbm-tbs", type=float, default=0.0, help="measured streaming rate in TB/s for the floor (0: not reported)")
-    ap.add_argument("--out", default="")
-    args = ap.parse_args()
+    args = pf.parse(ap, argv, hbm_help="measured streaming rate in TB/s for the floor (0: not reported)")
 
-    from eye_adaptation_bench import lit_frame
-    from oxylus_amd import lib as L
-    from oxylus_amd.renderer import BloomContext, EyeAdaptationContext, RendererInstance, TonemapContext, exposure_buffer
-
-    dev = torch.device("cuda:0")
-    r = RendererInstance(0)
-    W, H = (int(v) for v in args.size.split("x"))
-    lit = lit_frame(r, W, H, args.meshlets, (args.transparent,), dev)[0]
+    r, dev = pf.renderer()
+    W, H = pf.extent(args.size)
+    lit = pf.lit_frame(r, W, H, args.meshlets, (args.transparent,), dev)[0]
     small = torch.zeros((2, 2, 4), dtype=torch.int16, device=dev) if args.transparent else torch.zeros((2, 2), dtype=torch.int32, device=dev)
     base = L.SCENE_HAS_EYE_ADAPTATION | L.SCENE_HAS_BLOOM | (L.SCENE_TRANSPARENT_BACKGROUND if args.transparent else 0)
     lens = L.SCENE_HAS_FILM_GRAIN | L.SCENE_HAS_CHROMATIC_ABERRATION | L.SCENE_HAS_VIGNETTE
@@ -62,7 +32,7 @@ def main():
             for lens_name, flags in (("off", base), ("on", base | lens)):
                 c = TonemapContext.create(image, flags, curve, exposure, bloom)
                 c.dst_attachment.fill_(-9)
-                med, mn = time_call(r, c, args.steps, args.warmup)
+                med, mn = pf.time_call(lambda: r.apply_tonemap(c), args.steps, args.warmup)
                 torch.cuda.synchronize()
                 texel = 8 if c.source_format else 4
                 # the source once, level 0 of the bloom once, the destination once (the aberration's taps land on texels the pass reads anyway)
@@ -70,14 +40,10 @@ def main():
                 out = {"workload": "tonemap", "image": image_name, "size": f"{c.width}x{c.height}", "format": "rgba16f" if c.source_format else "b10g11r11",
                        "tonemap_type": curve_name, "lens": lens_name, "ms_median": med, "ms_min": mn, "exposure": float(exposure[1]), "rule_bytes": rule_bytes,
                        "distinct_colours": int(torch.unique(c.dst_attachment & 0xFFFFFF).numel())}
-                if args.hbm_tbs > 0:
-                    out["streaming_floor_ms"] = rule_bytes / (args.hbm_tbs * 1e12) * 1e3
-                lines.append(json.dumps(out))
-                print(lines[-1])
+                pf.streaming_floor(out, rule_bytes, args.hbm_tbs)
+                pf.report(lines, out)
     r.close()
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    return pf.write_out(args.out, lines)
 
 
 if __name__ == "__main__":
