@@ -1140,7 +1140,7 @@ oxc_status oxc_apply_pbr(oxc_ctx* ctx, const oxc_pbr_context* context, void* hip
  * histogram_average, passes/histogram_generate.slang, passes/histogram_average.slang, passes/histogram.slang, com::remap at
  * common/math.slang:203), the pass directly behind apply_pbr and the first reader of its image: a 256-bin log-luminance histogram of
  * final_attachment, reduced to GPU::HistogramLuminance {adapted_luminance, exposure}, the record bloom_prefilter and tonemap multiply by.
- * Out of scope: bloom, tone mapping and the lens effects, FXAA, the atmosphere branch, any change to what oxc_apply_pbr writes.
+ * Out of scope: bloom, tone mapping and the lens effects, the atmosphere branch, any change to what oxc_apply_pbr writes.
  * time_coeff is taken as given: the reference computes 1 - glm::exp(-adaptation_speed * delta_time) on the host with the platform's exp,
  * which no checker can pin, so it stays outside the parity claim; the C++ shim and the Python twin compute it from adaptation_speed and
  * delta_time with their own expf and pass the result on.
@@ -1196,7 +1196,7 @@ oxc_status oxc_apply_eye_adaptation(oxc_ctx* ctx, const oxc_eye_adaptation_conte
  * common/color.slang:79-81, the extents at RendererInstance.cpp:509-510 and 1257-1267, Texture::calculate_mip_count at
  * include/Asset/Texture.hpp:144-146, the samplers LinearSamplerBorder and LinearSamplerClamped at include/Render/Utils/VukCommon.hpp:
  * 103-120), the pass directly behind apply_eye_adaptation and the first reader of its exposure.
- * Out of scope: FXAA, the atmosphere branch.  bloom_intensity is set by apply_bloom for the tonemap: the C++ shim and the Python twin
+ * Out of scope: the atmosphere branch.  bloom_intensity is set by apply_bloom for the tonemap: the C++ shim and the Python twin
  * carry it to oxc_apply_tonemap, this call does not read it.
  * Arithmetic: the canonical binary32 arithmetic of oxc_apply_pbr -- round to nearest even, left to right, no contraction, IEEE division
  * (1.0 / x is a division), min / max through fminf / fmaxf (a NaN operand gives the other one), clamp(x, a, b) = min(max(x, a), b),
@@ -1286,7 +1286,7 @@ oxc_status oxc_apply_bloom(oxc_ctx* ctx, const oxc_bloom_context* context, void*
  * scene flags at SceneGPU.hpp:258-266, the swapchain formats at RenderContext.cpp:102-105), the last pass of the frame: the HDR image
  * oxc_apply_pbr wrote, times the exposure oxc_apply_eye_adaptation left behind, plus level 0 of the upsample pyramid oxc_apply_bloom wrote,
  * through one of four tone curves and three lens effects into one 8-bit word per pixel.
- * Out of scope: FXAA (in the reference it runs on the HDR image before the eye adaptation), the atmosphere branch, the unused
+ * Out of scope: the atmosphere branch (FXAA, which the reference runs on the HDR image before the eye adaptation, is oxc_apply_fxaa), the unused
  * agx_tonemapping (tonemap.slang:90-129) and the Jzazbz UCS (TONE_MAPPING_UCS is ICtCp).
  * Arithmetic: the canonical binary32 arithmetic as the oxc_apply_bloom block states it (round to nearest even, left to right, no
  * contraction, IEEE division and square root, min / max through fminf / fmaxf, clamp, lerp, the UF11 / UF10 / binary16 decodes), a
@@ -1405,6 +1405,78 @@ typedef struct oxc_tonemap_context {
 } oxc_tonemap_context;
 
 oxc_status oxc_apply_tonemap(oxc_ctx* ctx, const oxc_tonemap_context* context, void* hip_stream);
+
+/* ---- FXAA: edge anti-aliasing of the lit HDR image ---------------------------------------------------------------------------------
+ * Replaces the `fxaa` pass of the reference's post-process chain (Oxylus/src/Render/Shaders/passes/fxaa/fxaa.slang, bound at
+ * RendererInstance.cpp:1225-1255 with LinearSamplerClamped of include/Render/Utils/VukCommon.hpp), which runs between apply_pbr and
+ * apply_eye_adaptation whenever SceneFlags::HasFXAA is set (RendererInstance.cpp:531-532): the image oxc_apply_pbr wrote goes in, a second
+ * image of the same extent and format comes out, and the eye adaptation, the bloom and the tonemap read that one.
+ * Out of scope: the atmosphere branch.  The call does not read OXC_SCENE_HAS_FXAA: the C++ shim and the Python twin use it to decide
+ * whether the pass runs and which image the later passes read.
+ * Arithmetic: the canonical binary32 arithmetic of oxc_apply_pbr -- round to nearest even, left to right, no contraction, IEEE division
+ * (1.0 / x is a division) and sqrt, min / max through fminf / fmaxf (a NaN operand gives the other one), clamp(x, a, b) = min(max(x, a), b),
+ * lerp(a, b, t) = a + (b - a) * t, abs clears the sign bit; a comparison with a NaN operand is false; a decimal literal is the binary32
+ * nearest to it.  The decodes are those of oxc_apply_tonemap step 1: source_format 0 the exact UF11 / UF11 / UF10 decode with alpha 1.0,
+ * source_format 1 four halves through binary16 -> binary32, exact, denormals kept.  The checker is tests/fxaa_model.py.
+ * Per pixel (x, y) of the W x H image, every statement in the order the Slang writes it:
+ *   1. coordinates  tex_coord = ((f32(x) + 0.5) / f32(W), (f32(y) + 0.5) / f32(H));  inverse_screen_size = (1.0f / f32(W), 1.0f / f32(H)).
+ *   2. neighbour taps (:24-33, 48-51)  The centre tap and the eight Sample(..., offset) taps sample an image of the output's own extent at a
+ *              pixel centre plus an integer offset.  Stated rule, as in oxc_apply_bloom step 4 and oxc_apply_tonemap step 1: a load of
+ *              texel (clamp(x + dx, 0, W - 1), clamp(y + dy, 0, H - 1)).  "down" is dy = -1 and "up" dy = +1, "left" dx = -1, as the Slang
+ *              writes them.
+ *   3. luma      (:19)  luma = sqrt((r * 0.299f + g * 0.587f) + b * 0.114f), of the decoded texel for the nine taps of 2 and of the
+ *              bilinear-filtered colour for the samples of 6, as written.  A negative sum (RGBA16F only) gives NaN; every comparison with
+ *              a NaN is false, so such a pixel follows the path the Slang's comparisons give it.  No special cases.
+ *   4. early out (:36-45)  luma_min = min(center, min(min(down, up), min(left, right))), luma_max likewise with max, luma_range =
+ *              luma_max - luma_min; if luma_range < max(0.0312f, luma_max * 0.125f) the pixel's colour is the centre texel's (store, 8).
+ *   5. edge      (:53-103)  luma_down_up = down + up, luma_left_right = left + right, left_corners = down_left + up_left, down_corners =
+ *              down_left + down_right, right_corners = down_right + up_right, up_corners = up_right + up_left;  edge_horizontal =
+ *              (abs(-2.0f * left + left_corners) + abs(-2.0f * center + luma_down_up) * 2.0f) + abs(-2.0f * right + right_corners);
+ *              edge_vertical = (abs(-2.0f * up + up_corners) + abs(-2.0f * center + luma_left_right) * 2.0f) + abs(-2.0f * down +
+ *              down_corners);  is_horizontal = edge_horizontal >= edge_vertical;  step_length = is_horizontal ? inverse.y : inverse.x;
+ *              (luma1, luma2) = is_horizontal ? (down, up) : (left, right);  gradient = luma - center for both;  is1_steepest =
+ *              abs(gradient1) >= abs(gradient2);  gradient_scaled = 0.25f * max(abs(gradient1), abs(gradient2));  is1_steepest:
+ *              step_length = -step_length and luma_local_average = 0.5f * (luma1 + center), else 0.5f * (luma2 + center);  current_uv =
+ *              tex_coord with step_length * 0.5f added to .y (is_horizontal) or .x.
+ *   6. search    (:105-161)  offset = is_horizontal ? (inverse.x, 0.0f) : (0.0f, inverse.y);  QUALITY(0 .. 11) = 1, 1, 1, 1, 1, 1.5, 2, 2,
+ *              2, 2, 4, 8;  uv1 = current_uv - offset * QUALITY(0), uv2 = current_uv + offset * QUALITY(0);  luma_end1 = luma(Sample(uv1))
+ *              - luma_local_average, luma_end2 likewise;  reached1 = abs(luma_end1) >= gradient_scaled, reached2 likewise, reached_both
+ *              their conjunction -- computed after the first pair of taps;  then the conditional advance uv1 -= offset * QUALITY(1)
+ *              without reached1 and uv2 += offset * QUALITY(1) without reached2;  then, without reached_both, for i = 2 .. 11: a side
+ *              not reached samples again (a side that has been reached keeps its last luma_end), both flags are computed anew, a side
+ *              not reached advances by offset * QUALITY(i), and reached_both ends the loop.  ITERATIONS is 12.
+ *              Every Sample here and in 7 is the manual bilinear of the oxc_apply_bloom block in clamp mode on the W x H source:
+ *              g = uv * (f32(W), f32(H)) - 0.5, i = floor(g) converted to i32 saturating (a NaN gives 0), f = g - floor(g), the four
+ *              texels (clamp(i.x + {0, 1}, 0, W - 1), clamp(i.y + {0, 1}, 0, H - 1)), lerp(lerp(t00, t10, f.x), lerp(t01, t11, f.x), f.y)
+ *              per channel.  The stated difference about hardware samplers is the same.
+ *   7. result    (:163-211)  distance1 = is_horizontal ? tex_coord.x - uv1.x : tex_coord.y - uv1.y, distance2 = is_horizontal ? uv2.x -
+ *              tex_coord.x : uv2.y - tex_coord.y;  is_direction1 = distance1 < distance2;  distance_final = min(distance1, distance2);
+ *              edge_thickness = distance1 + distance2;  is_luma_center_smaller = center < luma_local_average;  correct_variation =
+ *              ((is_direction1 ? luma_end1 : luma_end2) < 0.0f) != is_luma_center_smaller;  pixel_offset = (-distance_final) /
+ *              edge_thickness + 0.5f;  final_offset = correct_variation ? pixel_offset : 0.0f;  luma_average = k * ((2.0f * (luma_down_up
+ *              + luma_left_right) + left_corners) + right_corners) with k = 1.0f / 12.0f as one binary32 constant;  s1 = clamp(abs(
+ *              luma_average - center) / luma_range, 0.0f, 1.0f);  s2 = ((-2.0f * s1 + 3.0f) * s1) * s1;  sub_pixel_offset_final = (s2 *
+ *              s2) * 0.75f (SUBPIXEL_QUALITY);  final_offset = max(final_offset, sub_pixel_offset_final);  final_uv = tex_coord with
+ *              final_offset * step_length added to .y (is_horizontal) or .x;  the pixel's colour is Sample(final_uv), all four channels.
+ *   8. store     source_format 0: the truncating UF11 / UF11 / UF10 pack of oxc_decode_visbuffer step 8.  source_format 1: the binary16
+ *              conversion of oxc_apply_pbr step 12 for all four channels (a NaN stored as 0x7E00); alpha is the centre texel's alpha on the
+ *              early-out path and the bilinear alpha at final_uv otherwise.  The early-out path stores the DECODED centre colour through
+ *              the same packers, not a raw copy: a NaN half becomes 0x7E00 there too.  The reference clears the destination first;
+ *              every texel is overwritten, so no clear is launched.
+ * Limits (else OXC_INVALID_ARG, nothing launched, nothing written; the first broken rule in this order gives the message): width and
+ * height not zero; at most 65536 a side; width * height at most 2^32 - 1; source_format 0 or 1; final_attachment, then fxaa_attachment,
+ * aligned to its texel (4 or 8 bytes) with one texel per pixel; the two images share no byte.  One launch, no scratch, no allocation, no
+ * host synchronisation; capturable into a HIP graph as one more link of the linear chain. */
+#define OXC_SCENE_HAS_FXAA (1u << 4) /* GPU::SceneFlags (SceneGPU.hpp:259); oxc_apply_fxaa does not read it: the shim and the Python twin do */
+typedef struct oxc_fxaa_context {
+  uint32_t struct_size; /* sizeof(oxc_fxaa_context) */
+  uint32_t width, height;
+  uint32_t source_format;       /* 0: B10G11R11 UfloatPack32;  1: R16G16B16A16 Sfloat -- both images */
+  oxc_buffer final_attachment;  /* in: what oxc_apply_pbr wrote */
+  oxc_buffer fxaa_attachment;   /* out: the same extent and format */
+} oxc_fxaa_context;
+
+oxc_status oxc_apply_fxaa(oxc_ctx* ctx, const oxc_fxaa_context* context, void* hip_stream);
 
 /* ---- multi-GPU exchange: one process per GPU, RCCL over xGMI ---------------------------
  * The meshlet-instance array shards by contiguous range and every rank culls its shard on its own; the only

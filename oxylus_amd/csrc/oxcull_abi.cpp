@@ -93,6 +93,7 @@ struct oxc_ctx {
   PassCounters ambient_occlusion_stats;  // OXC_TUNE_AMBIENT_OCCLUSION_STATS: u32[15] (16 allocated)
   PassCounters visbuffer_decode_stats;   // OXC_TUNE_VISBUFFER_DECODE_STATS: u32[4]
   PassCounters pbr_apply_stats;          // OXC_TUNE_PBR_APPLY_STATS: u32[9]
+  PassCounters fxaa_stats;               // OXC_TUNE_FXAA_STATS: u32[4]
   uint32_t eye_adaptation_grid = 0;      // OXC_TUNE_EYE_ADAPTATION_GRID: cap of the histogram kernel's grid in blocks, 0 = uncapped
   uint32_t bloom_tail_level = 0;         // OXC_TUNE_BLOOM_TAIL_LEVEL: the first level of oxc_apply_bloom's tail kernel, 0 = the library's choice
   void* comm = nullptr;           // ncclComm_t (oxc_comm_init)
@@ -635,7 +636,7 @@ void oxc_destroy(oxc_ctx* ctx) {
   if (ctx->raster_rows) (void)hipFree(ctx->raster_rows);
   if (ctx->vsm_scratch) (void)hipFree(ctx->vsm_scratch);
   if (ctx->vsm_draw_scratch) (void)hipFree(ctx->vsm_draw_scratch);
-  for (const auto& pc : {ctx->vsm_resolve_stats, ctx->contact_shadows_stats, ctx->ambient_occlusion_stats, ctx->visbuffer_decode_stats, ctx->pbr_apply_stats})
+  for (const auto& pc : {ctx->vsm_resolve_stats, ctx->contact_shadows_stats, ctx->ambient_occlusion_stats, ctx->visbuffer_decode_stats, ctx->pbr_apply_stats, ctx->fxaa_stats})
     if (pc.dev) (void)hipFree(pc.dev);
   if (ctx->comm) (void)oxc_comm_destroy(ctx);
   if (ctx->slots) (void)hipFree(ctx->slots);
@@ -2220,6 +2221,37 @@ oxc_status oxc_apply_tonemap(oxc_ctx* ctx, const oxc_tonemap_context* c, void* h
   return OXC_OK;
 }
 
+oxc_status oxc_apply_fxaa(oxc_ctx* ctx, const oxc_fxaa_context* c, void* hip_stream) {
+  if (!ctx) return OXC_INVALID_ARG;
+  if (!c || c->struct_size != sizeof(oxc_fxaa_context)) return fail(ctx, OXC_INVALID_ARG, "apply_fxaa: bad context / struct_size");
+  const char* const entry = "apply_fxaa";
+  if (c->width == 0u || c->height == 0u) return bad_arg(ctx, entry, "the extent must not be zero");
+  if (c->width > 65536u || c->height > 65536u) return bad_arg(ctx, entry, "extent beyond 65536");
+  const uint64_t pixels = (uint64_t)c->width * c->height;
+  if (pixels > 0xFFFFFFFFull) return bad_arg(ctx, entry, "width * height beyond 2^32 - 1");
+  if (c->source_format > 1u) return bad_arg(ctx, entry, "source_format must be 0 (B10G11R11) or 1 (R16G16B16A16 Sfloat)");
+  const uint32_t texel = c->source_format ? 8u : 4u;
+  if (bad_pixel_buffer(c->final_attachment, pixels, texel))
+    return bad_arg(ctx, entry, "final_attachment must be one aligned u32 per pixel (format 0) or one 8-byte aligned u16x4 per pixel (format 1)");
+  if (bad_pixel_buffer(c->fxaa_attachment, pixels, texel))
+    return bad_arg(ctx, entry, "fxaa_attachment must be one aligned u32 per pixel (format 0) or one 8-byte aligned u16x4 per pixel (format 1)");
+  const uintptr_t src_lo = reinterpret_cast<uintptr_t>(c->final_attachment.dptr), dst_lo = reinterpret_cast<uintptr_t>(c->fxaa_attachment.dptr);
+  if (ByteSpan{dst_lo, dst_lo + (uintptr_t)(pixels * texel)}.overlaps({src_lo, src_lo + (uintptr_t)(pixels * texel)}))
+    return bad_arg(ctx, entry, "fxaa_attachment must not overlap final_attachment");
+  OXC_HIP(ctx, hipSetDevice(ctx->device));
+  OXC_ORDER(ctx, hip_stream);
+  const hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  FxaaArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.src = c->final_attachment.dptr;
+  a.dst = c->fxaa_attachment.dptr;
+  a.w = c->width, a.h = c->height, a.format = c->source_format;
+  OXC_TRY(arm_counters(ctx, entry, "hipMalloc(fxaa counters)", ctx->fxaa_stats, 16, s, &a.stats));
+  launch_fxaa(a, s);
+  OXC_HIP(ctx, hipGetLastError());
+  return OXC_OK;
+}
+
 oxc_status oxc_generate_ambient_occlusion(oxc_ctx* ctx, const oxc_ambient_occlusion_context* c, void* hip_stream) {
   if (!ctx) return OXC_INVALID_ARG;
   if (!c || c->struct_size != sizeof(oxc_ambient_occlusion_context)) return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: bad context / struct_size");
@@ -2616,6 +2648,7 @@ oxc_status oxc_debug_set_tuning(oxc_ctx* ctx, uint32_t knob, uint32_t value) {
     case OXC_TUNE_CONTACT_SHADOWS_STATS: ctx->contact_shadows_stats.on = value != 0u; return OXC_OK;
     case OXC_TUNE_VISBUFFER_DECODE_STATS: ctx->visbuffer_decode_stats.on = value != 0u; return OXC_OK;
     case OXC_TUNE_PBR_APPLY_STATS: ctx->pbr_apply_stats.on = value != 0u; return OXC_OK;
+    case OXC_TUNE_FXAA_STATS: ctx->fxaa_stats.on = value != 0u; return OXC_OK;
     case OXC_TUNE_EYE_ADAPTATION_GRID: ctx->eye_adaptation_grid = value; return OXC_OK;
     case OXC_TUNE_BLOOM_TAIL_LEVEL: ctx->bloom_tail_level = value; return OXC_OK;
     case OXC_TUNE_AMBIENT_OCCLUSION_STATS: ctx->ambient_occlusion_stats.on = value != 0u; return OXC_OK;
@@ -2701,6 +2734,10 @@ oxc_status oxc_debug_visbuffer_decode_stats(oxc_ctx* ctx, uint32_t* host_out4, v
 
 oxc_status oxc_debug_pbr_apply_stats(oxc_ctx* ctx, uint32_t* host_out9, void* hip_stream) {
   return read_counters(ctx, "debug_pbr_apply_stats", "oxc_apply_pbr", &oxc_ctx::pbr_apply_stats, host_out9, 36, hip_stream);
+}
+
+oxc_status oxc_debug_fxaa_stats(oxc_ctx* ctx, uint32_t* host_out4, void* hip_stream) {
+  return read_counters(ctx, "debug_fxaa_stats", "oxc_apply_fxaa", &oxc_ctx::fxaa_stats, host_out4, 16, hip_stream);
 }
 
 oxc_status oxc_debug_contact_shadows_stats(oxc_ctx* ctx, uint32_t* host_out12, void* hip_stream) {

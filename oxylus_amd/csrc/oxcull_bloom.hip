@@ -32,8 +32,6 @@ constexpr uint32_t kTailTexelsForced = 16384;  // and a forced start is raised t
 OXC_DEV V3 add3(const V3& a, const V3& b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
 OXC_DEV V3 mul3(const V3& a, float s) { return {a.x * s, a.y * s, a.z * s}; }
 OXC_DEV V3 sum4(const V3& a, const V3& b, const V3& c, const V3& d) { return add3(add3(add3(a, b), c), d); }
-OXC_DEV float lerp_f(float a, float b, float t) { return a + (b - a) * t; }
-OXC_DEV V3 lerp3(const V3& a, const V3& b, float t) { return {lerp_f(a.x, b.x, t), lerp_f(a.y, b.y, t), lerp_f(a.z, b.z, t)}; }
 
 OXC_DEV uint32_t level_side(uint32_t side, uint32_t k) { return max(1u, side >> k); }
 
@@ -55,33 +53,10 @@ OXC_DEV void store_texel(void* base, size_t i, const V3& c) {
     static_cast<uint2*>(base)[i] = make_uint2(channel_half(c.x) | (channel_half(c.y) << 16), channel_half(c.z) | (0x3C00u << 16));
 }
 
-// One axis of a bilinear tap: the two texel coordinates, whether each lies inside the level (border mode; a coordinate outside is
-// stored as 0 and not loaded) and the weight of the second.
-struct Axis {
-  int i0, i1;
-  bool in0, in1;
-  float f;
-};
-
 // uv = (f32(x) + 0.5) / f32(extent of the output), ts = 1.0 / that extent, k the tap offset, fsize / last the source level's side
 template <bool BORDER>
 OXC_DEV Axis axis_tap(float uv, float ts, float k, float fsize, int last) {
-  const float g = (uv + ts * k) * fsize - 0.5f;
-  const float fl = floorf(g);
-  const int i = clamp_i(cvt_i32_sat(fl), -2, last + 1);  // i + 1 cannot wrap after this, and what lay outside [-1, last] still does
-  Axis a;
-  a.f = g - fl;
-  if (BORDER) {
-    a.in0 = i >= 0 && i <= last;
-    a.in1 = i + 1 >= 0 && i + 1 <= last;
-    a.i0 = a.in0 ? i : 0;
-    a.i1 = a.in1 ? i + 1 : 0;
-  } else {
-    a.in0 = a.in1 = true;
-    a.i0 = clamp_i(i, 0, last);
-    a.i1 = clamp_i(i + 1, 0, last);
-  }
-  return a;
+  return axis_at<BORDER>(uv + ts * k, fsize, last);
 }
 
 template <int FORMAT, bool BORDER>

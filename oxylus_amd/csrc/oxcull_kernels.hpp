@@ -702,6 +702,14 @@ struct TonemapArgs {
 };
 void tonemap_constants(float chromatic_aberration_amount, TonemapConstants& k);
 void launch_tonemap(const TonemapArgs& a, hipStream_t s);
+// oxcull_fxaa.hip: edge anti-aliasing of the lit HDR image (oxc_apply_fxaa)
+struct FxaaArgs {
+  const void* src;  // w x h texels: u32 (B10G11R11, format 0) or u16x4 (R16G16B16A16 Sfloat, format 1)
+  void* dst;        // the same extent and format
+  uint32_t w, h, format;
+  uint32_t* stats;  // nullptr, or u32[4] the counting instantiation adds to (oxc_debug_fxaa_stats)
+};
+void launch_fxaa(const FxaaArgs& a, hipStream_t s);
 // oxcull_bounds.hip: meshlet bounds producer
 void launch_build_meshlet_bounds(const float* pos, uint32_t vertex_count, const void* meshlets, uint32_t meshlet_count, const uint32_t* vidx,
                                  const uint8_t* micro, void* out_bounds, float* out_mesh6, void* out_qpos, float* meshlet_minmax, float* normals,

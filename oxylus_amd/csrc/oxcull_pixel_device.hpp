@@ -1,5 +1,5 @@
 // oxcull_pixel_device.hpp -- the device rules the VSM page update and the per-pixel passes (visbuffer decode, shadow resolve, contact
-// shadows, ambient occlusion) share: one copy each, so that two kernels which must agree on a pixel's clipmap, page or normal cannot drift apart.
+// shadows, ambient occlusion, bloom, tonemap, FXAA) share: one copy each, so that two kernels which must agree on a pixel's clipmap, page or normal cannot drift apart.
 // Every float operation keeps the order and rounding include/oxcull.h states; the including files are compiled without contraction.
 #pragma once
 
@@ -119,6 +119,54 @@ OXC_DEV float unpack_ufloat(uint32_t v) {
   if (e == 0u) return (float)m * (MBITS == 6 ? 0x1p-20f : 0x1p-19f);
   if (e == 31u) return m ? __builtin_nanf("") : __builtin_inff();
   return asf(((e + 112u) << 23) | (m << (23 - MBITS)));
+}
+
+OXC_DEV float lerp_f(float a, float b, float t) { return a + (b - a) * t; }
+OXC_DEV V3 lerp3(const V3& a, const V3& b, float t) { return {lerp_f(a.x, b.x, t), lerp_f(a.y, b.y, t), lerp_f(a.z, b.z, t)}; }
+
+// A texel of the lit HDR image: B10G11R11 UfloatPack32 (FORMAT 0: the exact UF11 / UF11 / UF10 decode, alpha 1.0) or R16G16B16A16 Sfloat
+// (FORMAT 1: four halves, exact, denormals kept)
+struct Texel {
+  V3 c;
+  float a;
+};
+template <int FORMAT>
+OXC_DEV Texel load_rgba(const void* base, size_t i) {
+  if (FORMAT == 0) {
+    const uint32_t w = static_cast<const uint32_t*>(base)[i];
+    return {{unpack_ufloat<6>(w & 0x7FFu), unpack_ufloat<6>((w >> 11) & 0x7FFu), unpack_ufloat<5>(w >> 22)}, 1.0f};
+  }
+  const uint2 v = static_cast<const uint2*>(base)[i];
+  return {{dequantize_half(v.x & 0xFFFFu), dequantize_half(v.x >> 16), dequantize_half(v.y & 0xFFFFu)}, dequantize_half(v.y >> 16)};
+}
+
+// One axis of a manual bilinear tap (the oxc_apply_bloom block): the two texel coordinates, whether each lies inside the level (border
+// mode; a coordinate outside is stored as 0 and not loaded) and the weight of the second.
+struct Axis {
+  int i0, i1;
+  bool in0, in1;
+  float f;
+};
+// p the normalised coordinate of the tap, fsize / last the source level's side.  Clamp mode (BORDER false): both coordinates lie in
+// [0, last] for every bit pattern of p (a NaN converts to 0, +-Inf saturates).
+template <bool BORDER>
+OXC_DEV Axis axis_at(float p, float fsize, int last) {
+  const float g = p * fsize - 0.5f;
+  const float fl = floorf(g);
+  const int i = clamp_i(cvt_i32_sat(fl), -2, last + 1);  // i + 1 cannot wrap after this, and what lay outside [-1, last] still does
+  Axis a;
+  a.f = g - fl;
+  if (BORDER) {
+    a.in0 = i >= 0 && i <= last;
+    a.in1 = i + 1 >= 0 && i + 1 <= last;
+    a.i0 = a.in0 ? i : 0;
+    a.i1 = a.in1 ? i + 1 : 0;
+  } else {
+    a.in0 = a.in1 = true;
+    a.i0 = clamp_i(i, 0, last);
+    a.i1 = clamp_i(i + 1, 0, last);
+  }
+  return a;
 }
 
 // The pixel of this thread: an 8 x 8 pixel tile per wave, a 16 x 16 tile per block of 256 threads.

@@ -286,19 +286,6 @@ OXC_DEV V3 gt7(const V3& c, const TonemapConstants& k) {
 }
 
 // ---- sampling --------------------------------------------------------------------------------------------------------------------------------
-struct Texel {
-  V3 c;
-  float a;
-};
-template <int FORMAT>
-OXC_DEV Texel load_texel(const void* base, size_t i) {
-  if (FORMAT == 0) {
-    const uint32_t w = static_cast<const uint32_t*>(base)[i];
-    return {{unpack_ufloat<6>(w & 0x7FFu), unpack_ufloat<6>((w >> 11) & 0x7FFu), unpack_ufloat<5>(w >> 22)}, 1.0f};
-  }
-  const uint2 v = static_cast<const uint2*>(base)[i];
-  return {{dequantize_half(v.x & 0xFFFFu), dequantize_half(v.x >> 16), dequantize_half(v.y & 0xFFFFu)}, dequantize_half(v.y >> 16)};
-}
 // channel CH of texel i
 template <int FORMAT, int CH>
 OXC_DEV float load_channel(const void* base, size_t i) {
@@ -324,7 +311,6 @@ OXC_DEV WrapAxis wrap_axis(float coord, int size) {
   a.f = g - fl;
   return a;
 }
-OXC_DEV float lerp_f(float a, float b, float t) { return a + (b - a) * t; }
 
 template <int FORMAT, int CH>
 OXC_DEV float tap_channel(const void* src, int sw, int sh, float u, float v) {
@@ -367,7 +353,7 @@ __global__ __launch_bounds__(256) void k_tonemap(TonemapArgs a) {
   const uint2 tp = tile_pixel();
   if (tp.x >= a.w || tp.y >= a.h) return;
   const size_t pix = (size_t)tp.y * a.w + tp.x;
-  const Texel source = load_texel<FORMAT>(a.src, pix);  // step 1
+  const Texel source = load_rgba<FORMAT>(a.src, pix);  // step 1
   V3 color = source.c;
   const float exposure = (a.flags & OXC_SCENE_HAS_EYE_ADAPTATION) ? a.exposure[1] : a.exposure_setting;  // step 2
   color = {color.x * exposure, color.y * exposure, color.z * exposure};
@@ -375,8 +361,8 @@ __global__ __launch_bounds__(256) void k_tonemap(TonemapArgs a) {
     const float u = ((float)tp.x + 0.5f) / (float)a.w, v = ((float)tp.y + 0.5f) / (float)a.h;
     const WrapAxis ax = wrap_axis(u, (int)a.bw), ay = wrap_axis(v, (int)a.bh);
     const size_t r0 = (size_t)ay.i0 * a.bw, r1 = (size_t)ay.i1 * a.bw;
-    const V3 t00 = load_texel<FORMAT>(a.bloom, r0 + ax.i0).c, t10 = load_texel<FORMAT>(a.bloom, r0 + ax.i1).c;
-    const V3 t01 = load_texel<FORMAT>(a.bloom, r1 + ax.i0).c, t11 = load_texel<FORMAT>(a.bloom, r1 + ax.i1).c;
+    const V3 t00 = load_rgba<FORMAT>(a.bloom, r0 + ax.i0).c, t10 = load_rgba<FORMAT>(a.bloom, r0 + ax.i1).c;
+    const V3 t01 = load_rgba<FORMAT>(a.bloom, r1 + ax.i0).c, t11 = load_rgba<FORMAT>(a.bloom, r1 + ax.i1).c;
     color.x = color.x + lerp_f(lerp_f(t00.x, t10.x, ax.f), lerp_f(t01.x, t11.x, ax.f), ay.f) * a.bloom_intensity;
     color.y = color.y + lerp_f(lerp_f(t00.y, t10.y, ax.f), lerp_f(t01.y, t11.y, ax.f), ay.f) * a.bloom_intensity;
     color.z = color.z + lerp_f(lerp_f(t00.z, t10.z, ax.f), lerp_f(t01.z, t11.z, ax.f), ay.f) * a.bloom_intensity;

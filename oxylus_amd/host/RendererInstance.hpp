@@ -17,6 +17,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <utility>
 
 #include "oxcull.h"
 
@@ -155,6 +156,7 @@ struct PostProcessContext {
   ImagePyramid bloom_upsampled_attachment = {};  // extent / 2, Texture::calculate_mip_count levels (RendererInstance.cpp:1257-1267); written by apply_bloom
   float bloom_intensity = 0.0f;                  // set by apply_bloom, read by apply_tonemap
   Buffer dst_attachment = {};                    // the 8-bit image apply_tonemap writes, one u32 per pixel
+  Buffer fxaa_attachment = {};                   // the image apply_fxaa writes with HasFXAA: final_attachment's extent and format
 };
 
 // The five pp.bloom_* cvars apply_bloom reads, with the engine's defaults (RendererCVar.cpp:44-48)
@@ -428,6 +430,21 @@ public:
     c.final_attachment = dst_attachment;
     check(oxc_apply_pbr(ctx_, &c, stream_));
     return dst_attachment;
+  }
+  // The `fxaa` pass (RendererInstance.cpp:1225-1255), between apply_pbr and apply_eye_adaptation: with HasFXAA in gpu_scene_flags, edge
+  // anti-aliasing of context.final_attachment into context.fxaa_attachment, which is then handed on as context.final_attachment (the
+  // reference's std::tie swaps the two names); without the flag nothing runs.  Rules: include/oxcull.h, oxc_apply_fxaa.
+  auto apply_fxaa(PostProcessContext& context) -> void {
+    if (!(gpu_scene_flags & OXC_SCENE_HAS_FXAA)) return;
+    oxc_fxaa_context c = {};
+    c.struct_size = sizeof c;
+    c.width = context.extent.width;
+    c.height = context.extent.height;
+    c.source_format = (gpu_scene_flags & OXC_SCENE_TRANSPARENT_BACKGROUND) ? 1u : 0u;
+    c.final_attachment = context.final_attachment;
+    c.fxaa_attachment = context.fxaa_attachment;
+    check(oxc_apply_fxaa(ctx_, &c, stream_));
+    std::swap(context.final_attachment, context.fxaa_attachment);
   }
   // RendererInstance::apply_eye_adaptation (Passes/PostProcess.cpp:7-77): the luminance histogram of context.final_attachment into
   // histogram_bin_indices_buffer and the adapted luminance and exposure into prepared_frame.exposure_buffer.  time_coeff is computed here

@@ -67,6 +67,14 @@ int main(int argc, char**) {
   } catch (const std::exception& e) {
     std::printf("expected (no attachments bound): %s\n", e.what());
   }
+  try {  // RendererInstance.cpp:1225-1255: FXAA between apply_pbr and the eye adaptation; its output becomes final_attachment
+    auto post_process_context = PostProcessContext{.extent = {.width = 1920, .height = 1080}, .final_attachment = Buffer{}, .fxaa_attachment = Buffer{}};
+    self.apply_fxaa(post_process_context);  // HasFXAA clear: nothing runs
+    self.gpu_scene_flags |= OXC_SCENE_HAS_FXAA;
+    self.apply_fxaa(post_process_context);
+  } catch (const std::exception& e) {
+    std::printf("expected (no attachments bound): %s\n", e.what());
+  }
   try {  // RendererInstance.cpp:1278: the post passes start with the eye adaptation
     auto post_process_context = PostProcessContext{.delta_time = 1.0f / 60.0f, .extent = {.width = 1920, .height = 1080}, .final_attachment = Buffer{}};
     self.gpu_scene_flags |= OXC_SCENE_HAS_EYE_ADAPTATION;

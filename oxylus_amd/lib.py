@@ -33,6 +33,7 @@ TUNE_VISBUFFER_DECODE_STATS = 13
 TUNE_PBR_APPLY_STATS = 14
 TUNE_EYE_ADAPTATION_GRID = 15
 TUNE_BLOOM_TAIL_LEVEL = 16
+TUNE_FXAA_STATS = 17
 
 # GPU::SceneFlags bits oxc_apply_pbr reads (scene.slang:242-256)
 SCENE_HAS_DIRECTIONAL_LIGHT, SCENE_HAS_ATMOSPHERE, SCENE_HAS_CONTACT_SHADOWS, SCENE_HAS_SKY, SCENE_TRANSPARENT_BACKGROUND = 1 << 0, 1 << 1, 1 << 9, 1 << 10, 1 << 11
@@ -40,6 +41,7 @@ SCENE_HAS_EYE_ADAPTATION = 1 << 2  # RendererInstance.cpp:1278; oxc_apply_eye_ad
 EYE_SOURCE_B10G11R11, EYE_SOURCE_R16G16B16A16 = 0, 1  # oxc_eye_adaptation_context.source_format, oxc_bloom_context.source_format
 SCENE_HAS_BLOOM = 1 << 3  # RendererInstance.cpp:1282; oxc_apply_bloom does not read it, oxc_tonemap_context.scene_flags does
 SCENE_HAS_FILM_GRAIN, SCENE_HAS_CHROMATIC_ABERRATION, SCENE_HAS_VIGNETTE = 1 << 6, 1 << 7, 1 << 8  # SceneGPU.hpp:258-266; oxc_tonemap_context.scene_flags
+SCENE_HAS_FXAA = 1 << 4  # SceneGPU.hpp:259; oxc_apply_fxaa does not read it: RendererInstance.apply_fxaa decides by it which image the later passes read
 TONEMAP_NONE, TONEMAP_ACES, TONEMAP_AGX, TONEMAP_GT7 = 0, 1, 2, 3  # GPU::TonemapType, oxc_tonemap_context.tonemap_type
 TONEMAP_OUT_R8G8B8A8_SRGB, TONEMAP_OUT_B8G8R8A8_SRGB, TONEMAP_OUT_R8G8B8A8_UNORM = 0, 1, 2  # oxc_tonemap_context.output_format
 LIGHT_KIND_DIRECTIONAL, LIGHT_KIND_POINT, LIGHT_KIND_SPOT = 0, 1, 2  # GPU::LightKind
@@ -491,6 +493,18 @@ class TonemapContext(C.Structure):
     ]
 
 
+class FxaaContext(C.Structure):
+    """oxc_fxaa_context (include/oxcull.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("source_format", C.c_uint32),
+        ("final_attachment", Buffer),
+        ("fxaa_attachment", Buffer),
+    ]
+
+
 # every symbol include/oxcull.h declares
 EXPORTS = [
     "oxc_abi_version",
@@ -529,6 +543,8 @@ EXPORTS = [
     "oxc_apply_eye_adaptation",
     "oxc_apply_bloom",
     "oxc_apply_tonemap",
+    "oxc_apply_fxaa",
+    "oxc_debug_fxaa_stats",
     "oxc_draw_physical_pages",
     "oxc_debug_vsm_draw_stats",
     "oxc_resolve_shadowmap",
@@ -637,6 +653,8 @@ def load(path: str = None) -> C.CDLL:
     lib.oxc_apply_eye_adaptation.argtypes = [vp, C.POINTER(EyeAdaptationContext), vp]
     lib.oxc_apply_bloom.argtypes = [vp, C.POINTER(BloomContext), vp]
     lib.oxc_apply_tonemap.argtypes = [vp, C.POINTER(TonemapContext), vp]
+    lib.oxc_apply_fxaa.argtypes = [vp, C.POINTER(FxaaContext), vp]
+    lib.oxc_debug_fxaa_stats.argtypes = [vp, vp, vp]
     lib.oxc_draw_physical_pages.argtypes = [vp, C.POINTER(PreparedFrame), C.POINTER(VsmDrawContext), vp]
     lib.oxc_debug_vsm_draw_stats.argtypes = [vp, vp, vp]
     lib.oxc_resolve_shadowmap.argtypes = [vp, C.POINTER(ShadowResolveContext), vp]

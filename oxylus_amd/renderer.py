@@ -743,6 +743,32 @@ class TonemapContext:
 
 
 @dataclass
+class FxaaContext:
+    """oxc_fxaa_context: the `fxaa` pass (RendererInstance.cpp:1225-1255, passes/fxaa/fxaa.slang).  `create` takes the image apply_pbr wrote --
+    int32 [H, W] (B10G11R11) or int16 [H, W, 4] (R16G16B16A16 Sfloat); the format follows from the shape -- and allocates fxaa_attachment,
+    a second image of the same shape."""
+    final_attachment: torch.Tensor  # in
+    fxaa_attachment: torch.Tensor   # out
+    width: int
+    height: int
+    source_format: int
+
+    @staticmethod
+    def create(final_attachment: torch.Tensor) -> "FxaaContext":
+        fmt = L.EYE_SOURCE_R16G16B16A16 if final_attachment.dim() == 3 else L.EYE_SOURCE_B10G11R11
+        H, W = int(final_attachment.shape[0]), int(final_attachment.shape[1])
+        return FxaaContext(final_attachment, torch.zeros_like(final_attachment), W, H, fmt)
+
+    def c(self) -> L.FxaaContext:
+        c = L.FxaaContext()
+        c.struct_size = C.sizeof(L.FxaaContext)
+        c.width, c.height, c.source_format = int(self.width), int(self.height), int(self.source_format)
+        c.final_attachment = _buf(self.final_attachment)
+        c.fxaa_attachment = _buf(self.fxaa_attachment)
+        return c
+
+
+@dataclass
 class VisbufferDecodeContext:
     """oxc_decode_context: RendererInstance::decode_visbuffer (Passes/DrawGeometry.cpp:192-274), the geometry and material-factor half of
     visbuffer_decode.slang.  `create` takes the visbuffer and the depth as oxc_draw_visbuffer resolved them, the matrix they were drawn with and
@@ -1047,6 +1073,21 @@ class RendererInstance:
         c = context.c()
         self._keep = context
         self._check(self._lib.oxc_apply_tonemap(self._ctx, C.byref(c), self._stream(stream)))
+
+    def apply_fxaa(self, context: FxaaContext, scene_flags: int = L.SCENE_HAS_FXAA, stream=None) -> torch.Tensor:
+        """RendererInstance.cpp:1225-1255: with L.SCENE_HAS_FXAA in `scene_flags`, edge anti-aliasing of `context.final_attachment` into
+        `context.fxaa_attachment`, one launch (include/oxcull.h, oxc_apply_fxaa); without it nothing runs.  Returns the image the eye
+        adaptation, the bloom and the tonemap read: fxaa_attachment when the pass ran, final_attachment otherwise, as the reference hands it on."""
+        if not int(scene_flags) & L.SCENE_HAS_FXAA:
+            return context.final_attachment
+        c = context.c()
+        self._keep = context
+        self._check(self._lib.oxc_apply_fxaa(self._ctx, C.byref(c), self._stream(stream)))
+        return context.fxaa_attachment
+
+    def debug_fxaa_stats(self, stream=None) -> dict:
+        """What the last apply_fxaa did, after debug_set_tuning(L.TUNE_FXAA_STATS, 1) (measurement hook; synchronises)."""
+        return self._read_stats(self._lib.oxc_debug_fxaa_stats, stream, ("early_out", "searched", "search_taps", "ran_all_steps"))
 
     def debug_pbr_apply_stats(self, stream=None) -> dict:
         """What the last apply_pbr did, after debug_set_tuning(L.TUNE_PBR_APPLY_STATS, 1) (measurement hook; synchronises)."""
