@@ -1478,6 +1478,141 @@ typedef struct oxc_fxaa_context {
 
 oxc_status oxc_apply_fxaa(oxc_ctx* ctx, const oxc_fxaa_context* context, void* hip_stream);
 
+/* ---- the sky LUTs of the atmosphere path ------------------------------------------------------------------------------------------------
+ * oxc_generate_sky_luts replaces the pair the reference builds once in the RendererInstance constructor (RendererInstance.cpp:136-251:
+ * pipelines sky_transmittance and sky_multiscatter; passes/sky_transmittance.slang, passes/sky_multiscattering.slang); an engine calls it
+ * again whenever the Atmosphere record changes.  oxc_draw_atmosphere replaces RendererInstance::draw_atmosphere (Passes/PBR.cpp:9-141)
+ * without its middle sky_ibl pass: pipelines sky_view and sky_aerial_perspective.  All four passes go through sky.slang, bound with
+ * LinearSamplerClamped.
+ * Out of scope, the two follow-ups: the sky_ibl cubemap (passes/sky_ibl.slang) and the atmosphere branch of pbr_apply.slang, the consumer
+ * of these LUTs -- oxc_apply_pbr still refuses OXC_SCENE_HAS_ATMOSPHERE.
+ * Images: all four are R16G16B16A16 Sfloat, here linear u16x4 buffers of binary16 bits like the normal image, row-major; the 3-D LUT is
+ * [depth][height][width].  A store is the binary16 conversion of oxc_apply_pbr step 12 per channel (a NaN stored as 0x7E00).  A
+ * SampleLevel(LinearSamplerClamped, uv, 0).rgb is the manual bilinear of the oxc_apply_bloom block in clamp mode on the decoded halves
+ * (exact, denormals kept), as oxc_apply_fxaa step 6 states it.  The reference clears the two images of draw_atmosphere first; every texel
+ * is written, so no clear is launched.
+ * oxc_atmosphere is the byte layout of GPU::Atmosphere (SceneGPU.hpp:158-181: 4-byte alignment, vuk::Extent3D as three u32), 136 bytes.
+ * The LUT extents come from the record, as in the Slang; the .z of the three 2-D sizes is not read.
+ * Arithmetic: the canonical binary32 arithmetic of oxc_apply_pbr, as oxc_apply_fxaa restates it.  exp(x) is the exp rule of
+ * oxc_apply_tonemap step 6, pow(v, p) its pow rule (a base under 2^-126, zero or negative, has log2 -Inf), cos(a) its cos rule.
+ * dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z; length = sqrt(dot(a, a)); normalize(a) = a / length(a) per component; o + t * d per component
+ * with the product first; safe_sqrt(x) = sqrt(max(0, x)); PI and TAU are the binary32 nearest to the Slang's literals.
+ * Host constants: what depends on the call's arguments alone is evaluated once per call on the host in binary64 from the binary32
+ * arguments (a decimal literal is the binary32 nearest to it, widened; max is fmax), each value rounded to binary32 once:
+ *     H = sqrt(max(0, atmos_radius^2 - planet_radius^2))  -- the `h` of sky_transmittance.slang and of transmittance_params_to_lut_uv;
+ *     the four constants of henyey_greenstein_draine_phase (common/math.slang:64-68) with g = mie_asymmetry: the argument of each exp
+ *     (-(0.0990567 / (g - 1.67154)); -(2.20679 / (g + 3.91029)) - 0.428934; 3.62489 - (8.29288 / (g + 5.52825)); -(0.599085 / (g - 0.641583))
+ *     - 0.665888) in binary64, rounded to binary32, then the exp rule: g_hg, g_d, alpha, w_d;
+ *     oxc_draw_atmosphere only: eye_altitude = max(camera_position.y * 0.01 + min_altitude, min_altitude), min_altitude = planet_radius +
+ *     0.001 (Atmosphere::get_eye_pos; eye_pos = (0, eye_altitude, 0) and h = length(eye_pos) = eye_altitude);  horizon = sqrt(max(0,
+ *     h^2 - planet_radius^2)) of the rounded h;  beta = acos(horizon / h), libm's acos of the binary64 quotient;  zenith_horizon_angle = pi -
+ *     beta with the binary64 pi.
+ * Shared rules, every statement in the Slang's order:
+ *   1. intersect  ray_sphere_intersect_nearest(o, d, R): a = dot(d, d), b = 2.0f * dot(d, o), c = dot(o, o) - R * R, delta = b * b - (4.0f
+ *              * a) * c;  delta < 0: none.  s0 = (-b + -1.0f * sqrt(delta)) / (2.0f * a), s1 = (-b + sqrt(delta)) / (2.0f * a);  both
+ *              negative: none;  s0 < 0: max(0, s1);  s1 < 0: max(0, s0);  else max(0, min(s0, s1)).  Where the Slang reads .value of a
+ *              none (the transmittance pass does), the value is 0.0.
+ *   2. medium    MediumScattering(altitude): rd = exp(-altitude / rayleigh_density), md = exp(-altitude / mie_density), od = max(0, 1.0f -
+ *              abs(altitude - ozone_height) / ozone_thickness);  rayleigh = rayleigh_scatter * rd, mie = mie_scatter * md, me =
+ *              mie_extinction * md, ozone = ozone_absorption * od;  scattering_sum = rayleigh + mie;  extinction_sum = (rayleigh + me) +
+ *              ozone.  A zero density divides by zero; the exp rule takes what comes (exp(-Inf) = 0, exp(NaN) = NaN).
+ *   3. transmittance sample  at (h, mu): rho = safe_sqrt(h * h - planet_radius^2), discriminant = (h * h) * (mu * mu - 1.0f) +
+ *              atmos_radius^2, d = max(0, -h * mu + safe_sqrt(discriminant)), d_min = atmos_radius - h, d_max = rho + H, uv = ((d - d_min) /
+ *              (d_max - d_min), rho / H), the sample of sky_transmittance_lut there.
+ *   4. phases    rayleigh_phase = k * (1.0f + c * c), k = 3.0f / (16.0f * PI) in binary32;  draine_phase(alpha, g, c) = ((1.0f / (4.0f *
+ *              PI)) * ((1.0f - g * g) / pow((1.0f + g * g) - (2.0f * g) * c, 1.5f))) * ((1.0f + (alpha * c) * c) / (1.0f + (alpha * (1.0f /
+ *              3.0f)) * (1.0f + (2.0f * g) * g)));  mie_phase = lerp(draine_phase(0, g_hg, c), draine_phase(alpha, g_d, c), w_d);  c =
+ *              dot(sun_dir, eye_dir).
+ *   5. integrate  integrate_single_scattered_luminance (sky.slang:169-256) with luminance = multiscattering_as_1 = 0, transmittance = 1:
+ *              dot(eye, eye) <= planet_radius^2 returns that.  planet = intersect(eye, dir, planet_radius).  t_max == -1.0 (the default,
+ *              which the multiscattering and the sky-view pass leave) selects the intersection path: atmos = intersect(eye, dir,
+ *              atmos_radius); none returns the initial result; length = planet is none ? atmos.value : max(0, planet.value).  The aerial
+ *              pass sets t_max, a max(0, ..) or a NaN and so never -1.0: length = t_max.  Then for (step = 0.0f; step < step_count; step
+ *              += 1.0f): shift = (length * (step + 0.3f)) / step_count, step_length = shift - the previous shift (0 at first);  pos = eye +
+ *              shift * dir, h = length(pos), altitude = h - planet_radius, the medium of 2, up = pos / h, sun_theta = dot(sun_dir, up), T_sun
+ *              = the sample of 3 at (h, sun_theta);  MS = 0 -- eval_multiscattering is false in all three callers as the Slang stands
+ *              (only the multiscattering pass assigns it, to false), so sky_multiscatter_lut is bound and checked but not read; the kernel
+ *              keeps the switch as a template parameter (uv = from_unit_to_sub_uvs(clamp((sun_theta * 0.5f + 0.5f, altitude / (atmos_radius
+ *              - planet_radius)), 0, 1)));  phase = mie * mie_phase + rayleigh * rayleigh_phase;  earth_shadow = intersect(pos - 0.001f *
+ *              up, sun_dir, planet_radius) is none ? 1 : 0;  sun_luminance = (earth_shadow * T_sun) * phase + MS * scattering_sum;  t =
+ *              exp(-step_length * extinction_sum);  integral = (sun_luminance - sun_luminance * t) / extinction_sum, ms_integral =
+ *              (scattering_sum - scattering_sum * t) / extinction_sum;  luminance += sun_intensity * (integral * transmittance),
+ *              multiscattering_as_1 += ms_integral * transmittance, transmittance *= t.  With eval_planet_luminance, a planet hit and
+ *              length == planet.value: pos = eye + length * dir, h, up = pos / h, sun_theta, NoL = saturate(dot(normalize(sun_dir),
+ *              normalize(up))), luminance += sun_intensity * ((((T_sun * transmittance) * NoL) * terrain_albedo) / PI).
+ *   6. move_to_top_atmosphere(pos, dir): h = length(pos); h > atmos_radius: top = intersect(pos, dir, atmos_radius), none returns
+ *              false, else pos = (pos + dir * top.value) + (pos / h) * -0.001f.
+ * oxc_generate_sky_luts, texel (x, y) with uv = ((f32(x) + 0.5f) / f32(width), (f32(y) + 0.5f) / f32(height)):
+ *   7. transmittance  rho = H * uv.y, lut_x = sqrt(rho * rho + planet_radius^2), d_min = atmos_radius - lut_x, d_max = rho + H, d = d_min +
+ *              uv.x * (d_max - d_min), lut_y = d == 0 ? 1.0f : ((H * H - rho * rho) - d * d) / ((2.0f * lut_x) * d) clamped to [-1, 1];
+ *              sun_dir = (0, sqrt(1.0f - lut_y * lut_y), lut_y), ray_pos = (0, 0, lut_x), distance_per_step = intersect(ray_pos, sun_dir,
+ *              atmos_radius).value / 1000.0f;  1000 times, in this order: ray_pos += sun_dir * distance_per_step, optical_depth +=
+ *              extinction_sum(length(ray_pos) - planet_radius) * distance_per_step.  Stored: (exp(-optical_depth), 1.0).
+ *   8. multiscatter  altitude = (planet_radius + uv.y * (atmos_radius - planet_radius)) + 0.001f, c = uv.x * 2.0f - 1.0f, sun_dir = (0, c,
+ *              safe_sqrt(1.0f - c * c)), eye = (0, altitude, 0);  for each of the 64 caller-supplied directions in ascending order, the
+ *              integral of 5 with eval_planet_luminance, step_count 32 and AtmosphereIntegrateInfo's default sun_intensity 10.0; luminance and
+ *              multiscattering_as_1 are summed from 0 in that order.  luminance *= (4.0f * PI) * (1.0f / 64.0f), multiscattering_as_1 *=
+ *              1.0f / 64.0f, stored: ((luminance * (1.0f / (4.0f * PI))) * (1.0f / (1.0f - multiscattering_as_1)), 1.0).  The table
+ *              (HEMISPHERE_64 of the reference's embedded.hemisphere) is the caller's, like the Hilbert table of
+ *              oxc_generate_ambient_occlusion: 64 x float3, read as given -- not normalised, not checked.
+ * oxc_draw_atmosphere:
+ *   9. sky view  uv of the texel as above, then uv_to_sky_view_lut_params: uv = (uv - 0.5f / res) * (res / (res - 1.0f));  uv.y < 0.5f: coord
+ *              = uv.y * 2.0f, 1.0f - coord, squared, 1.0f - coord, view_zenith_angle = zenith_horizon_angle * coord;  else coord = uv.y * 2.0f
+ *              - 1.0f, squared, view_zenith_angle = zenith_horizon_angle + beta * coord.  longitude = uv.x * TAU;  cz = cos(view_zenith_angle),
+ *              sz = safe_sqrt(1.0f - cz * cz) * (view_zenith_angle > 0 ? 1 : -1);  cl = cos(longitude), sl = safe_sqrt(1.0f - cl * cl) *
+ *              (longitude <= PI ? 1 : -1);  eye_dir = (sz * cl, cz, sz * sl).  move_to_top_atmosphere(eye_pos, eye_dir) false: the texel is
+ *              four zeros.  up = eye_pos / h with the h from before the move, c = dot(sun_dir, up), sun = normalize((safe_sqrt(1.0f - c *
+ *              c), c, 0)) -- a non-normalised sun_dir is used as given.  The integral of 5 with step_count 48, without the planet term.
+ *              luminance = max(luminance, 0) (a NaN gives 0), an Inf replaced by 0 (com::sanitize);  mult = clamp(max(l.x, max(l.y, l.z)),
+ *              HALF_MIN_NORMAL = 6.103515625e-5, HALF_MAX = 65504);  stored: (luminance / mult, mult).
+ *  10. aerial    texel (x, y, z): world = mul(inv_projection_view, (2.0f * uv - 1.0f, 1.0f, 1.0f)), rows ((m0 a + m1 b) + m2 c) + m3,
+ *              world.xyz / world.w;  world_dir = normalize(world - camera_position);  slice = (f32(z) + 0.5f) * (1.0f / f32(depth)),
+ *              squared, times f32(depth);  per_slice_depth = f32(width / depth), the INTEGER division of the two i32 the Slang writes (the
+ *              consumer in sky.slang divides floats);  t_max = slice * per_slice_depth.  eye_altitude >= atmos_radius: prev = eye_pos;
+ *              move_to_top_atmosphere false: four zeros;  length_to_atmosphere = length(prev - eye_pos);  t_max < length_to_atmosphere: four
+ *              zeros;  t_max = max(0, t_max - length_to_atmosphere).  The integral of 5 with sun_dir as given, step_count the FLOAT
+ *              max(1.0f, (f32(z) + 1.0f) * 2.0f), that t_max, without the planet term.  Stored: (luminance, (t.x * k + t.y * k) + t.z * k)
+ *              with k = 1.0f / 3.0f.  The Slang's start_depth, start_pos and ray_pos feed nothing and are not evaluated.
+ * Limits (else OXC_INVALID_ARG, nothing launched, nothing written; the first broken rule in this order gives the message): every side of
+ * a 2-D LUT the call reads or writes in 2 .. 4096 (from_sub_uvs_to_unit divides by res - 1); oxc_draw_atmosphere: every side of the
+ * aerial LUT in 1 .. 4096 and at most 2^26 texels; planet_radius and atmos_radius finite, planet_radius > 0, atmos_radius >
+ * planet_radius; every buffer, in the order of the context's fields, non-null, then aligned to 8 bytes, then at least as large as its
+ * extent says (hemisphere_directions: 768 bytes), each with a message of its own; no output shares a byte with another output or with an
+ * input.  oxc_generate_sky_luts is two
+ * launches, oxc_draw_atmosphere two; no scratch, no allocation, no host synchronisation; both are capturable into a HIP graph. */
+typedef struct oxc_atmosphere {
+  float rayleigh_scatter[3], rayleigh_density;
+  float mie_scatter[3], mie_density, mie_extinction, mie_asymmetry;
+  float ozone_absorption[3], ozone_height, ozone_thickness;
+  float terrain_albedo[3], planet_radius, atmos_radius, aerial_perspective_start_km, aerial_perspective_exposure;
+  uint32_t transmittance_lut_size[3], sky_view_lut_size[3], multiscattering_lut_size[3], aerial_perspective_lut_size[3];
+} oxc_atmosphere;
+
+typedef struct oxc_sky_lut_context {
+  uint32_t struct_size; /* sizeof(oxc_sky_lut_context) */
+  uint32_t _pad;
+  oxc_atmosphere atmosphere;
+  oxc_buffer hemisphere_directions; /* in: 64 x float3, required */
+  oxc_buffer sky_transmittance_lut; /* out: u16x4 [transmittance_lut_size.y][.x] */
+  oxc_buffer sky_multiscatter_lut;  /* out: u16x4 [multiscattering_lut_size.y][.x] */
+} oxc_sky_lut_context;
+
+typedef struct oxc_atmosphere_context {
+  uint32_t struct_size; /* sizeof(oxc_atmosphere_context) */
+  uint32_t _pad;
+  oxc_atmosphere atmosphere;
+  float sun_dir[3], sun_intensity;       /* directional_light.direction, .intensity */
+  float camera_position[3], _pad1;       /* GPU::Camera::position.xyz */
+  float camera_inv_projection_view[16];  /* GPU::Camera::inv_projection_view, column-major */
+  oxc_buffer sky_transmittance_lut;      /* in: what oxc_generate_sky_luts wrote */
+  oxc_buffer sky_multiscatter_lut;       /* in (bound, not read: step 5) */
+  oxc_buffer sky_view_lut;               /* out: u16x4 [sky_view_lut_size.y][.x], the engine's 312 x 192 */
+  oxc_buffer sky_aerial_perspective_lut; /* out: u16x4 [aerial_perspective_lut_size.z][.y][.x], the engine's 32 x 32 x 32 */
+} oxc_atmosphere_context;
+
+oxc_status oxc_generate_sky_luts(oxc_ctx* ctx, const oxc_sky_lut_context* context, void* hip_stream);
+oxc_status oxc_draw_atmosphere(oxc_ctx* ctx, const oxc_atmosphere_context* context, void* hip_stream);
+
 /* ---- multi-GPU exchange: one process per GPU, RCCL over xGMI ---------------------------
  * The meshlet-instance array shards by contiguous range and every rank culls its shard on its own; the only
  * exchanges of the path are (1) the per-rank counters {emitted meshlets, early, late, index count} to every rank

@@ -2252,6 +2252,106 @@ oxc_status oxc_apply_fxaa(oxc_ctx* ctx, const oxc_fxaa_context* c, void* hip_str
   return OXC_OK;
 }
 
+namespace {
+// The checks oxc_generate_sky_luts and oxc_draw_atmosphere share, in the order of the header's limits
+struct SkyBuffer {
+  const oxc_buffer& b;
+  uint64_t bytes;
+  const char* name;
+  bool output;
+};
+bool bad_lut_side(const uint32_t* size) { return size[0] < 2u || size[0] > 4096u || size[1] < 2u || size[1] > 4096u; }
+uint64_t lut_bytes(const uint32_t* size) { return (uint64_t)size[0] * size[1] * 8u; }
+oxc_status check_radii(oxc_ctx* ctx, const char* entry, const oxc_atmosphere& A) {
+  if (!std::isfinite(A.planet_radius) || !std::isfinite(A.atmos_radius)) return bad_arg(ctx, entry, "planet_radius and atmos_radius must be finite");
+  if (!(A.planet_radius > 0.0f)) return bad_arg(ctx, entry, "planet_radius must be above 0");
+  if (!(A.atmos_radius > A.planet_radius)) return bad_arg(ctx, entry, "atmos_radius must be above planet_radius");
+  return OXC_OK;
+}
+oxc_status check_sky_buffers(oxc_ctx* ctx, const char* entry, std::initializer_list<SkyBuffer> buffers) {
+  for (const SkyBuffer& s : buffers) {
+    if (!s.b.dptr) return bad_arg(ctx, entry, s.name, " must not be null");
+    if (reinterpret_cast<uintptr_t>(s.b.dptr) & 7u) return bad_arg(ctx, entry, s.name, " must be aligned to 8 bytes");
+    if (s.b.bytes < s.bytes) return bad_arg(ctx, entry, s.name, " is smaller than its extent");
+  }
+  for (const SkyBuffer& s : buffers) {
+    if (!s.output) continue;
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(s.b.dptr);
+    for (const SkyBuffer& o : buffers) {
+      const uintptr_t olo = reinterpret_cast<uintptr_t>(o.b.dptr);
+      if (&o != &s && ByteSpan{lo, lo + (uintptr_t)s.bytes}.overlaps({olo, olo + (uintptr_t)o.bytes})) return bad_arg(ctx, entry, s.name, " must not overlap ", o.name);
+    }
+  }
+  return OXC_OK;
+}
+}  // namespace
+
+oxc_status oxc_generate_sky_luts(oxc_ctx* ctx, const oxc_sky_lut_context* c, void* hip_stream) {
+  if (!ctx) return OXC_INVALID_ARG;
+  if (!c || c->struct_size != sizeof(oxc_sky_lut_context)) return fail(ctx, OXC_INVALID_ARG, "generate_sky_luts: bad context / struct_size");
+  const char* const entry = "generate_sky_luts";
+  const oxc_atmosphere& A = c->atmosphere;
+  if (bad_lut_side(A.transmittance_lut_size)) return bad_arg(ctx, entry, "transmittance_lut_size: every side must be in 2 .. 4096");
+  if (bad_lut_side(A.multiscattering_lut_size)) return bad_arg(ctx, entry, "multiscattering_lut_size: every side must be in 2 .. 4096");
+  OXC_TRY(check_radii(ctx, entry, A));
+  OXC_TRY(check_sky_buffers(ctx, entry, {{c->hemisphere_directions, 768u, "hemisphere_directions", false},
+                                         {c->sky_transmittance_lut, lut_bytes(A.transmittance_lut_size), "sky_transmittance_lut", true},
+                                         {c->sky_multiscatter_lut, lut_bytes(A.multiscattering_lut_size), "sky_multiscatter_lut", true}}));
+  OXC_HIP(ctx, hipSetDevice(ctx->device));
+  OXC_ORDER(ctx, hip_stream);
+  const hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  SkyLutArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.in.atm = A;
+  atmosphere_constants(A, nullptr, a.in.k);
+  a.hemisphere = static_cast<const float*>(c->hemisphere_directions.dptr);
+  a.transmittance = static_cast<uint2*>(c->sky_transmittance_lut.dptr);
+  a.multiscatter = static_cast<uint2*>(c->sky_multiscatter_lut.dptr);
+  a.in.transmittance = a.transmittance;
+  a.in.multiscatter = a.transmittance;  // the Slang binds the transmittance LUT in the multiscattering image's place
+  launch_sky_luts(a, s);
+  OXC_HIP(ctx, hipGetLastError());
+  return OXC_OK;
+}
+
+oxc_status oxc_draw_atmosphere(oxc_ctx* ctx, const oxc_atmosphere_context* c, void* hip_stream) {
+  if (!ctx) return OXC_INVALID_ARG;
+  if (!c || c->struct_size != sizeof(oxc_atmosphere_context)) return fail(ctx, OXC_INVALID_ARG, "draw_atmosphere: bad context / struct_size");
+  const char* const entry = "draw_atmosphere";
+  const oxc_atmosphere& A = c->atmosphere;
+  if (bad_lut_side(A.transmittance_lut_size)) return bad_arg(ctx, entry, "transmittance_lut_size: every side must be in 2 .. 4096");
+  if (bad_lut_side(A.multiscattering_lut_size)) return bad_arg(ctx, entry, "multiscattering_lut_size: every side must be in 2 .. 4096");
+  if (bad_lut_side(A.sky_view_lut_size)) return bad_arg(ctx, entry, "sky_view_lut_size: every side must be in 2 .. 4096");
+  const uint32_t* ap = A.aerial_perspective_lut_size;
+  if (ap[0] < 1u || ap[0] > 4096u || ap[1] < 1u || ap[1] > 4096u || ap[2] < 1u || ap[2] > 4096u)
+    return bad_arg(ctx, entry, "aerial_perspective_lut_size: every side must be in 1 .. 4096");
+  const uint64_t aerial_texels = (uint64_t)ap[0] * ap[1] * ap[2];
+  if (aerial_texels > (1ull << 26)) return bad_arg(ctx, entry, "aerial_perspective_lut_size: more than 2^26 texels");
+  OXC_TRY(check_radii(ctx, entry, A));
+  OXC_TRY(check_sky_buffers(ctx, entry, {{c->sky_transmittance_lut, lut_bytes(A.transmittance_lut_size), "sky_transmittance_lut", false},
+                                         {c->sky_multiscatter_lut, lut_bytes(A.multiscattering_lut_size), "sky_multiscatter_lut", false},
+                                         {c->sky_view_lut, lut_bytes(A.sky_view_lut_size), "sky_view_lut", true},
+                                         {c->sky_aerial_perspective_lut, aerial_texels * 8u, "sky_aerial_perspective_lut", true}}));
+  OXC_HIP(ctx, hipSetDevice(ctx->device));
+  OXC_ORDER(ctx, hip_stream);
+  const hipStream_t s = static_cast<hipStream_t>(hip_stream);
+  AtmosphereArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.in.atm = A;
+  atmosphere_constants(A, &c->camera_position[1], a.in.k);
+  a.in.transmittance = static_cast<const uint2*>(c->sky_transmittance_lut.dptr);
+  a.in.multiscatter = static_cast<const uint2*>(c->sky_multiscatter_lut.dptr);
+  std::memcpy(a.sun_dir, c->sun_dir, sizeof a.sun_dir);
+  a.sun_intensity = c->sun_intensity;
+  std::memcpy(a.camera_position, c->camera_position, sizeof a.camera_position);
+  std::memcpy(a.inv_projection_view, c->camera_inv_projection_view, sizeof a.inv_projection_view);
+  a.sky_view = static_cast<uint2*>(c->sky_view_lut.dptr);
+  a.aerial = static_cast<uint2*>(c->sky_aerial_perspective_lut.dptr);
+  launch_atmosphere(a, s);
+  OXC_HIP(ctx, hipGetLastError());
+  return OXC_OK;
+}
+
 oxc_status oxc_generate_ambient_occlusion(oxc_ctx* ctx, const oxc_ambient_occlusion_context* c, void* hip_stream) {
   if (!ctx) return OXC_INVALID_ARG;
   if (!c || c->struct_size != sizeof(oxc_ambient_occlusion_context)) return fail(ctx, OXC_INVALID_ARG, "generate_ambient_occlusion: bad context / struct_size");

@@ -710,6 +710,39 @@ struct FxaaArgs {
   uint32_t* stats;  // nullptr, or u32[4] the counting instantiation adds to (oxc_debug_fxaa_stats)
 };
 void launch_fxaa(const FxaaArgs& a, hipStream_t s);
+// oxcull_atmosphere.hip: the four sky LUTs (oxc_generate_sky_luts, oxc_draw_atmosphere)
+// What does not depend on the texel (the header block's "host constants"): evaluated once per call by atmosphere_constants() in binary64 from
+// the binary32 arguments, each rounded to binary32 once.
+struct AtmosphereConstants {
+  float h_atmos;                       // sqrt(max(0, atmos_radius^2 - planet_radius^2))
+  float g_hg, g_d, alpha, w_d;         // the four exp constants of henyey_greenstein_draine_phase
+  float eye_altitude;                  // Atmosphere::get_eye_pos(camera.position).y, also length(eye_pos)
+  float beta, zenith_horizon_angle;    // acos(horizon / eye_altitude), pi - beta
+};
+struct SkyLutInputs {
+  oxc_atmosphere atm;
+  AtmosphereConstants k;
+  const uint2* transmittance;  // read by the multiscattering, sky-view and aerial passes
+  const uint2* multiscatter;   // bound as the reference binds it; read only by an instantiation with eval_multiscattering
+};
+struct SkyLutArgs {
+  SkyLutInputs in;
+  const float* hemisphere;  // 64 x float3
+  uint2* transmittance;     // out, == in.transmittance
+  uint2* multiscatter;      // out
+};
+struct AtmosphereArgs {
+  SkyLutInputs in;
+  float sun_dir[3], sun_intensity;
+  float camera_position[3];
+  float inv_projection_view[16];
+  uint2* sky_view;  // out
+  uint2* aerial;    // out, [depth][height][width]
+  uint32_t slice_blocks;  // blocks per aerial slice, filled by launch_atmosphere
+};
+void atmosphere_constants(const oxc_atmosphere& atm, const float* camera_y, AtmosphereConstants& k);  // camera_y nullptr: the camera terms stay 0
+void launch_sky_luts(const SkyLutArgs& a, hipStream_t s);
+void launch_atmosphere(AtmosphereArgs a, hipStream_t s);
 // oxcull_bounds.hip: meshlet bounds producer
 void launch_build_meshlet_bounds(const float* pos, uint32_t vertex_count, const void* meshlets, uint32_t meshlet_count, const uint32_t* vidx,
                                  const uint8_t* micro, void* out_bounds, float* out_mesh6, void* out_qpos, float* meshlet_minmax, float* normals,

@@ -1,5 +1,5 @@
 // oxcull_pixel_device.hpp -- the device rules the VSM page update and the per-pixel passes (visbuffer decode, shadow resolve, contact
-// shadows, ambient occlusion, bloom, tonemap, FXAA) share: one copy each, so that two kernels which must agree on a pixel's clipmap, page or normal cannot drift apart.
+// shadows, ambient occlusion, bloom, tonemap, FXAA, the sky LUTs) share: one copy each, so that two kernels which must agree on a pixel's clipmap, page or normal cannot drift apart.
 // Every float operation keeps the order and rounding include/oxcull.h states; the including files are compiled without contraction.
 #pragma once
 
@@ -58,8 +58,9 @@ OXC_DEV double log2_f64(float x) {
   return x == __builtin_inff() ? __builtin_inf() : r;
 }
 
-// exp2(y) of a binary64 y, rounded to binary32 once: the second half of the pow rule
-OXC_DEV float exp2_f64_round(double y) {
+// exp2(y) of a binary64 y, rounded to binary32 once: the second half of the pow rule.  Host code runs the same expressions where a pass
+// evaluates its pixel-independent constants (oxc_generate_sky_luts).
+__host__ OXC_DEV float exp2_f64_round(double y) {
   const double k = __builtin_floor(y + 0.5);
   const double r = y - k;  // exact, in [-0.5, 0.5]
   const double t = r * 0x1.62e42fefa39efp-1;
@@ -90,6 +91,9 @@ OXC_DEV float pow_rule(float v, float p) { return exp2_f64_round((double)p * log
 
 // exp2(t) of a binary32 t (the exp2 rule of oxc_apply_pbr)
 OXC_DEV float exp2_rule(float t) { return exp2_f64_round((double)t); }
+
+// exp(x) = exp2((double)x * log2(e)) (oxc_apply_tonemap step 6; the sky LUTs take every exp by it)
+__host__ OXC_DEV float exp_rule(float x) { return exp2_f64_round((double)x * 0x1.71547652b82fep+0); }
 
 // one component of packUnorm4x8: u32(floor(saturate(e) * 255.0 + 0.5)); a NaN gives 0
 OXC_DEV uint32_t pack_unorm(float e) { return cvt_u32_sat(floorf(saturate_f(e) * 255.0f + 0.5f)); }
@@ -229,6 +233,19 @@ OXC_DEV void cos_sin_turn(float t, float& cs, float& sn) {
   const int k = (int)kf;
   cs = k == 0 ? cq : k == 1 ? -sq : k == 2 ? -cq : sq;
   sn = k == 0 ? sq : k == 1 ? cq : k == 2 ? -sq : -cq;
+}
+
+// cos(a) of a binary32 angle in radians (oxc_apply_tonemap step 6; oxc_draw_atmosphere turns its view directions by it): NaN for a
+// non-finite a; else u = (double)|a| / (2 pi), t = (float)(u - floor(u)), t == 1 becomes 0, the cosine of the turn t
+OXC_DEV float cos_turn_rule(float a) {
+  const float aa = __builtin_fabsf(a);
+  const double u = (double)aa * 0x1.45f306dc9c883p-3;
+  float t = (float)(u - __builtin_floor(u));
+  t = t == 1.0f ? 0.0f : t;
+  t = aa < __builtin_inff() ? t : 0.0f;  // a non-finite argument: any turn, the result is replaced below
+  float cs, sn;
+  cos_sin_turn(t, cs, sn);
+  return aa < __builtin_inff() ? cs : __builtin_nanf("");
 }
 
 }  // namespace oxc

@@ -9,8 +9,8 @@
 // Step 5 of the header: whatever of the curves and of FfxLensGetRGMag does not depend on the pixel is evaluated once per call on the
 // host by tonemap_constants() below -- binary32 in the Slang's order, this file being compiled without contraction for the host as for the
 // device -- and reaches the kernel in TonemapArgs::k.  The host needs log2 / exp2 / pow of oxcull_pixel_device.hpp for three of them (kB_,
-// framebufferLuminanceTargetUcs_): host_rules holds the same expressions as plain C++, and tests/test_gpu_tonemap.py pins the two against
-// the checker's constants through every GT7 pixel.  The exp and cos rules live here: only this pass needs them.
+// framebufferLuminanceTargetUcs_): exp2 and exp are the header's own functions, compiled for the host too; host_rules holds log2 as plain
+// C++, and tests/test_gpu_tonemap.py pins the two against the checker's constants through every GT7 pixel.  The exp and cos rules are those of oxcull_pixel_device.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -23,12 +23,12 @@ namespace oxc {
 
 namespace {
 constexpr double kLog2E = 0x1.71547652b82fep+0;
-constexpr double kInvTwoPi = 0x1.45f306dc9c883p-3;
 // eotfSt2084 / inverseEotfSt2084 (tonemap.slang:403-408): every one exact in binary32 but m1 and its kin, which are literals
 constexpr float kPqM1 = 0.1593017578125f, kPqC1 = 0.8359375f, kPqC2 = 18.8515625f, kPqC3 = 18.6875f, kPqC = 10000.0f;
 constexpr float kReferenceLuminance = 100.0f, kSdrPaperWhite = 250.0f;
 
-// ---- the host's copy of the log2 / exp2 rules (oxcull_pixel_device.hpp), for tonemap_constants ------------------------------------------------
+// ---- the host's side of the log2 / exp2 rules, for tonemap_constants: exp2_f64_round and exp_rule are the shared host-and-device functions of
+// oxcull_pixel_device.hpp; log2_f64 there takes its bits through device-only casts, so the host keeps this one copy of it ---------------------------
 namespace host_rules {
 double log2_f64(float x) {
   uint32_t bits;
@@ -49,27 +49,9 @@ double log2_f64(float x) {
   r = x >= 0x1p-126f ? r : -HUGE_VAL;
   return x == HUGE_VALF ? HUGE_VAL : r;
 }
-float exp2_f64_round(double y) {
-  const double k = std::floor(y + 0.5);
-  const double r = y - k;
-  const double t = r * 0x1.62e42fefa39efp-1;
-  double q = 1.0 / 6227020800.0;
-  for (double c : {1.0 / 479001600.0, 1.0 / 39916800.0, 1.0 / 3628800.0, 1.0 / 362880.0, 1.0 / 40320.0, 1.0 / 5040.0, 1.0 / 720.0, 1.0 / 120.0, 1.0 / 24.0,
-                   1.0 / 6.0, 1.0 / 2.0, 1.0, 1.0})
-    q = q * t + c;
-  if (y <= -160.0) return 0.0f;
-  if (y >= 160.0) return HUGE_VALF;
-  if (!(y == y)) return NAN;
-  const long long ki = (long long)k;
-  const unsigned long long sb = (unsigned long long)(ki + 1023) << 52;
-  double scale;
-  std::memcpy(&scale, &sb, 8);
-  return (float)(q * scale);
-}
 float pow_rule(float v, float p) { return exp2_f64_round((double)p * log2_f64(v)); }
 float log2_rule(float x) { return (float)log2_f64(x); }
 float exp2_rule(float t) { return exp2_f64_round((double)t); }
-float exp_rule(float x) { return exp2_f64_round((double)x * kLog2E); }
 float inverse_eotf(float v, float m2) {
   const float y = (v * kReferenceLuminance) / kPqC;
   const float ym = pow_rule(y, kPqM1);
@@ -143,7 +125,7 @@ void tonemap_constants(float chromatic_aberration_amount, TonemapConstants& k) {
   k.gt_mid = mid;
   k.gt_toe = toe;
   k.gt_ka = k.gt_target * lin + k.gt_target * kk;
-  k.gt_kb = (-k.gt_target * kk) * host_rules::exp_rule(lin / kk);
+  k.gt_kb = (-k.gt_target * kk) * exp_rule(lin / kk);
   k.gt_kc = -1.0f / (kk * k.gt_target);
   k.gt_lin_peak = lin * k.gt_target;
   k.gt_mid_span = mid - 0.0f;
@@ -168,19 +150,8 @@ void tonemap_constants(float chromatic_aberration_amount, TonemapConstants& k) {
 }
 
 namespace {
-// ---- step 6: the transcendentals only this pass needs ----------------------------------------------------------------------------------------
+// ---- step 6: the log2 rule rounded to binary32 (exp and cos: oxcull_pixel_device.hpp) ---------------------------------------------------------
 OXC_DEV float log2_rule(float x) { return (float)log2_f64(x); }
-OXC_DEV float exp_rule(float x) { return exp2_f64_round((double)x * kLog2E); }
-OXC_DEV float cos_rule(float a) {
-  const float aa = __builtin_fabsf(a);
-  const double u = (double)aa * kInvTwoPi;
-  float t = (float)(u - __builtin_floor(u));
-  t = t == 1.0f ? 0.0f : t;
-  t = aa < __builtin_inff() ? t : 0.0f;  // a non-finite argument: any turn, the result is replaced below
-  float cs, sn;
-  cos_sin_turn(t, cs, sn);
-  return aa < __builtin_inff() ? cs : __builtin_nanf("");
-}
 
 OXC_DEV V3 mul_mv(const float* m, const V3& v) {
   return {(m[0] * v.x + m[1] * v.y) + m[2] * v.z, (m[3] * v.x + m[4] * v.y) + m[5] * v.z, (m[6] * v.x + m[7] * v.y) + m[8] * v.z};
@@ -381,8 +352,8 @@ __global__ __launch_bounds__(256) void k_tonemap(TonemapArgs a) {
   }
   if (a.flags & OXC_SCENE_HAS_VIGNETTE) {  // step 8
     const float pi_over_4 = 3.1415926535897932384626433832795f * 0.25f;
-    float mx = cos_rule((((float)abs(dx) / (float)cx) * a.vignette_amount) * pi_over_4);
-    float my = cos_rule((((float)abs(dy) / (float)cy) * a.vignette_amount) * pi_over_4);
+    float mx = cos_turn_rule((((float)abs(dx) / (float)cx) * a.vignette_amount) * pi_over_4);
+    float my = cos_turn_rule((((float)abs(dy) / (float)cy) * a.vignette_amount) * pi_over_4);
     mx = mx * mx, my = my * my;
     mx = mx * mx, my = my * my;
     const float factor = clamp01(mx * my);

@@ -159,6 +159,15 @@ struct PostProcessContext {
   Buffer fxaa_attachment = {};                   // the image apply_fxaa writes with HasFXAA: final_attachment's extent and format
 };
 
+// RendererInstance.hpp:294-300 of the reference without sky_cubemap_attachment (the sky_ibl pass is not in the library): the four sky LUTs,
+// linear u16x4 buffers of the extents the Atmosphere record names.
+struct AtmosphereContext {
+  Buffer sky_transmittance_lut_attachment = {};
+  Buffer sky_multiscatter_lut_attachment = {};
+  Buffer sky_view_lut_attachment = {};
+  Buffer sky_aerial_perspective_lut_attachment = {};
+};
+
 // The five pp.bloom_* cvars apply_bloom reads, with the engine's defaults (RendererCVar.cpp:44-48)
 struct BloomCVars {
   float threshold = 1.0f;
@@ -227,6 +236,8 @@ public:
   GPU::DirectionalLight directional_light = {};
   GPU::Sky sky_data = {};
   GPU::Camera camera = {};
+  oxc_atmosphere atmosphere = {};                   // prepared_frame.atmosphere_buffer's contents: read by generate_sky_luts and draw_atmosphere
+  Buffer hemisphere_directions = {};                // 64 x float3, the caller's table (the reference embeds its own in the shader)
   GPU::HistogramLuminanceInfo eye_adaptation = {};  // read by apply_eye_adaptation
   GPU::PostProcessSettings post_proces_settings = {};  // read by apply_tonemap (the reference spells it so: RendererInstance.hpp)
   GPU::TonemapType tonemap_type = GPU::TonemapType::AgX;
@@ -430,6 +441,33 @@ public:
     c.final_attachment = dst_attachment;
     check(oxc_apply_pbr(ctx_, &c, stream_));
     return dst_attachment;
+  }
+  // The pair the reference builds in its constructor (RendererInstance.cpp:136-251): sky_transmittance_lut, then sky_multiscatter_lut from it.
+  // Called once the `atmosphere` record and `hemisphere_directions` are set, and again whenever the record changes.  Rules: include/oxcull.h,
+  // oxc_generate_sky_luts.
+  auto generate_sky_luts(AtmosphereContext& context) -> void {
+    oxc_sky_lut_context c = {};
+    c.struct_size = sizeof c;
+    c.atmosphere = atmosphere;
+    c.hemisphere_directions = hemisphere_directions;
+    c.sky_transmittance_lut = context.sky_transmittance_lut_attachment;
+    c.sky_multiscatter_lut = context.sky_multiscatter_lut_attachment;
+    check(oxc_generate_sky_luts(ctx_, &c, stream_));
+  }
+  // RendererInstance::draw_atmosphere (Passes/PBR.cpp:9-141) without its sky_ibl pass: sky_view_lut and sky_aerial_perspective_lut from the
+  // two LUTs above, directional_light and camera.  Rules: include/oxcull.h, oxc_draw_atmosphere.
+  auto draw_atmosphere(AtmosphereContext& context) -> void {
+    oxc_atmosphere_context c = {};
+    c.struct_size = sizeof c;
+    c.atmosphere = atmosphere;
+    for (int i = 0; i < 3; i++) c.sun_dir[i] = directional_light.direction[i], c.camera_position[i] = camera.position[i];
+    c.sun_intensity = directional_light.intensity;
+    for (int i = 0; i < 16; i++) c.camera_inv_projection_view[i] = camera.inv_projection_view[i];
+    c.sky_transmittance_lut = context.sky_transmittance_lut_attachment;
+    c.sky_multiscatter_lut = context.sky_multiscatter_lut_attachment;
+    c.sky_view_lut = context.sky_view_lut_attachment;
+    c.sky_aerial_perspective_lut = context.sky_aerial_perspective_lut_attachment;
+    check(oxc_draw_atmosphere(ctx_, &c, stream_));
   }
   // The `fxaa` pass (RendererInstance.cpp:1225-1255), between apply_pbr and apply_eye_adaptation: with HasFXAA in gpu_scene_flags, edge
   // anti-aliasing of context.final_attachment into context.fxaa_attachment, which is then handed on as context.final_attachment (the

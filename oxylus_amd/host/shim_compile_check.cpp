@@ -55,6 +55,13 @@ int main(int argc, char**) {
   } catch (const std::exception& e) {
     std::printf("expected (no attachments bound): %s\n", e.what());
   }
+  try {  // RendererInstance.cpp:136-251 and :1023-1038: the constructor-time LUT pair, then draw_atmosphere between contact shadows and ambient occlusion
+    auto atmosphere_context = AtmosphereContext{};
+    self.generate_sky_luts(atmosphere_context);
+    self.draw_atmosphere(atmosphere_context);
+  } catch (const std::exception& e) {
+    std::printf("expected (no attachments bound): %s\n", e.what());
+  }
   try {  // RendererInstance.cpp: apply_pbr, the consumer of every image above
     auto pbr_context = PBRContext{.depth_attachment = main_geometry_context.depth_attachment,
                                   .albedo_attachment = main_geometry_context.albedo_attachment,

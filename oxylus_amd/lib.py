@@ -505,6 +505,60 @@ class FxaaContext(C.Structure):
     ]
 
 
+class Atmosphere(C.Structure):
+    """oxc_atmosphere: the byte layout of GPU::Atmosphere (SceneGPU.hpp:158-181), 136 bytes; the defaults are the record's own."""
+    _fields_ = [
+        ("rayleigh_scatter", C.c_float * 3),
+        ("rayleigh_density", C.c_float),
+        ("mie_scatter", C.c_float * 3),
+        ("mie_density", C.c_float),
+        ("mie_extinction", C.c_float),
+        ("mie_asymmetry", C.c_float),
+        ("ozone_absorption", C.c_float * 3),
+        ("ozone_height", C.c_float),
+        ("ozone_thickness", C.c_float),
+        ("terrain_albedo", C.c_float * 3),
+        ("planet_radius", C.c_float),
+        ("atmos_radius", C.c_float),
+        ("aerial_perspective_start_km", C.c_float),
+        ("aerial_perspective_exposure", C.c_float),
+        ("transmittance_lut_size", C.c_uint32 * 3),
+        ("sky_view_lut_size", C.c_uint32 * 3),
+        ("multiscattering_lut_size", C.c_uint32 * 3),
+        ("aerial_perspective_lut_size", C.c_uint32 * 3),
+    ]
+
+
+class SkyLutContext(C.Structure):
+    """oxc_sky_lut_context (include/oxcull.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("_pad", C.c_uint32),
+        ("atmosphere", Atmosphere),
+        ("hemisphere_directions", Buffer),
+        ("sky_transmittance_lut", Buffer),
+        ("sky_multiscatter_lut", Buffer),
+    ]
+
+
+class AtmosphereContext(C.Structure):
+    """oxc_atmosphere_context (include/oxcull.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("_pad", C.c_uint32),
+        ("atmosphere", Atmosphere),
+        ("sun_dir", C.c_float * 3),
+        ("sun_intensity", C.c_float),
+        ("camera_position", C.c_float * 3),
+        ("_pad1", C.c_float),
+        ("camera_inv_projection_view", C.c_float * 16),
+        ("sky_transmittance_lut", Buffer),
+        ("sky_multiscatter_lut", Buffer),
+        ("sky_view_lut", Buffer),
+        ("sky_aerial_perspective_lut", Buffer),
+    ]
+
+
 # every symbol include/oxcull.h declares
 EXPORTS = [
     "oxc_abi_version",
@@ -545,6 +599,8 @@ EXPORTS = [
     "oxc_apply_tonemap",
     "oxc_apply_fxaa",
     "oxc_debug_fxaa_stats",
+    "oxc_generate_sky_luts",
+    "oxc_draw_atmosphere",
     "oxc_draw_physical_pages",
     "oxc_debug_vsm_draw_stats",
     "oxc_resolve_shadowmap",
@@ -655,6 +711,8 @@ def load(path: str = None) -> C.CDLL:
     lib.oxc_apply_tonemap.argtypes = [vp, C.POINTER(TonemapContext), vp]
     lib.oxc_apply_fxaa.argtypes = [vp, C.POINTER(FxaaContext), vp]
     lib.oxc_debug_fxaa_stats.argtypes = [vp, vp, vp]
+    lib.oxc_generate_sky_luts.argtypes = [vp, C.POINTER(SkyLutContext), vp]
+    lib.oxc_draw_atmosphere.argtypes = [vp, C.POINTER(AtmosphereContext), vp]
     lib.oxc_draw_physical_pages.argtypes = [vp, C.POINTER(PreparedFrame), C.POINTER(VsmDrawContext), vp]
     lib.oxc_debug_vsm_draw_stats.argtypes = [vp, vp, vp]
     lib.oxc_resolve_shadowmap.argtypes = [vp, C.POINTER(ShadowResolveContext), vp]

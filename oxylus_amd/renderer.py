@@ -769,6 +769,121 @@ class FxaaContext:
 
 
 @dataclass
+class Atmosphere:
+    """GPU::Atmosphere (SceneGPU.hpp:158-181).  The defaults are the record's own; `engine()` is what RendererInstance.cpp:1445-1455 makes of the
+    AtmosphereComponent's defaults (the scattering and absorption coefficients times 1e-3f in binary32) with the engine's four LUT extents."""
+    rayleigh_scatter: tuple = (0.005802, 0.013558, 0.033100)
+    rayleigh_density: float = 8.0
+    mie_scatter: tuple = (0.003996, 0.003996, 0.003996)
+    mie_density: float = 1.2
+    mie_extinction: float = 0.004440
+    mie_asymmetry: float = 3.6
+    ozone_absorption: tuple = (0.000650, 0.001881, 0.000085)
+    ozone_height: float = 25.0
+    ozone_thickness: float = 15.0
+    terrain_albedo: tuple = (0.3, 0.3, 0.3)
+    planet_radius: float = 6360.0
+    atmos_radius: float = 6460.0
+    aerial_perspective_start_km: float = 8.0
+    aerial_perspective_exposure: float = 1.0
+    transmittance_lut_size: tuple = (256, 64, 1)
+    sky_view_lut_size: tuple = (312, 192, 1)
+    multiscattering_lut_size: tuple = (32, 32, 1)
+    aerial_perspective_lut_size: tuple = (32, 32, 32)
+
+    @staticmethod
+    def engine(**overrides) -> "Atmosphere":
+        f32 = lambda x: struct.unpack("f", struct.pack("f", x))[0]  # noqa: E731
+        s = lambda v: tuple(f32(f32(x) * f32(1e-3)) for x in v)  # noqa: E731  (the binary32 product the engine forms: exact in binary64, rounded once)
+        a = Atmosphere(rayleigh_scatter=s((5.802, 13.558, 33.100)), mie_scatter=s((3.996, 3.996, 3.996)), mie_extinction=s((4.44,))[0],
+                       ozone_absorption=s((0.650, 1.881, 0.085)))
+        for k, v in overrides.items():
+            setattr(a, k, v)
+        return a
+
+    def c(self) -> L.Atmosphere:
+        c = L.Atmosphere()
+        for name, _ in L.Atmosphere._fields_:
+            v = getattr(self, name)
+            if isinstance(v, (tuple, list)):
+                for i in range(3):
+                    getattr(c, name)[i] = v[i]
+            else:
+                setattr(c, name, float(v))
+        return c
+
+
+def _lut(size, device) -> torch.Tensor:
+    return torch.zeros(tuple(int(n) for n in size) + (4,), dtype=torch.int16, device=device)
+
+
+@dataclass
+class SkyLutContext:
+    """oxc_sky_lut_context: the constructor-time pair of the reference (RendererInstance.cpp:136-251).  `create` takes the Atmosphere record and
+    the caller's 64 hemisphere directions (float32 [64, 3]) and allocates the two LUTs, int16 [H, W, 4] of binary16 bits."""
+    atmosphere: Atmosphere
+    hemisphere_directions: torch.Tensor  # in: float32 [64, 3]
+    sky_transmittance_lut: torch.Tensor  # out
+    sky_multiscatter_lut: torch.Tensor   # out
+
+    @staticmethod
+    def create(atmosphere: Atmosphere, hemisphere_directions: torch.Tensor) -> "SkyLutContext":
+        dev = hemisphere_directions.device
+        t, m = atmosphere.transmittance_lut_size, atmosphere.multiscattering_lut_size
+        return SkyLutContext(atmosphere, hemisphere_directions, _lut((t[1], t[0]), dev), _lut((m[1], m[0]), dev))
+
+    def c(self) -> L.SkyLutContext:
+        c = L.SkyLutContext()
+        c.struct_size = C.sizeof(L.SkyLutContext)
+        c.atmosphere = self.atmosphere.c()
+        c.hemisphere_directions = _buf(self.hemisphere_directions)
+        c.sky_transmittance_lut = _buf(self.sky_transmittance_lut)
+        c.sky_multiscatter_lut = _buf(self.sky_multiscatter_lut)
+        return c
+
+
+@dataclass
+class AtmosphereContext:
+    """oxc_atmosphere_context: RendererInstance::draw_atmosphere (Passes/PBR.cpp:9-141) without its sky_ibl pass, so without the reference's
+    sky_cubemap_attachment.  `create` lays out the four buffers from an Atmosphere; generate_sky_luts fills the first two through
+    `sky_luts(hemisphere_directions)`."""
+    atmosphere: Atmosphere
+    sky_transmittance_lut_attachment: torch.Tensor       # in
+    sky_multiscatter_lut_attachment: torch.Tensor        # in
+    sky_view_lut_attachment: torch.Tensor                # out: int16 [H, W, 4]
+    sky_aerial_perspective_lut_attachment: torch.Tensor  # out: int16 [D, H, W, 4]
+    sun_dir: tuple = (0.0, 1.0, 0.0)
+    sun_intensity: float = 10.0
+    camera_position: tuple = (0.0, 0.0, 0.0)
+    camera_inv_projection_view: tuple = (1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0)
+
+    @staticmethod
+    def create(atmosphere: Atmosphere, device="cuda", **settings) -> "AtmosphereContext":
+        t, m, v, a = (atmosphere.transmittance_lut_size, atmosphere.multiscattering_lut_size, atmosphere.sky_view_lut_size,
+                      atmosphere.aerial_perspective_lut_size)
+        return AtmosphereContext(atmosphere, _lut((t[1], t[0]), device), _lut((m[1], m[0]), device), _lut((v[1], v[0]), device),
+                                 _lut((a[2], a[1], a[0]), device), **settings)
+
+    def sky_luts(self, hemisphere_directions: torch.Tensor) -> SkyLutContext:
+        return SkyLutContext(self.atmosphere, hemisphere_directions, self.sky_transmittance_lut_attachment, self.sky_multiscatter_lut_attachment)
+
+    def c(self) -> L.AtmosphereContext:
+        c = L.AtmosphereContext()
+        c.struct_size = C.sizeof(L.AtmosphereContext)
+        c.atmosphere = self.atmosphere.c()
+        for i in range(3):
+            c.sun_dir[i], c.camera_position[i] = float(self.sun_dir[i]), float(self.camera_position[i])
+        c.sun_intensity = float(self.sun_intensity)
+        for i in range(16):
+            c.camera_inv_projection_view[i] = float(self.camera_inv_projection_view[i])
+        c.sky_transmittance_lut = _buf(self.sky_transmittance_lut_attachment)
+        c.sky_multiscatter_lut = _buf(self.sky_multiscatter_lut_attachment)
+        c.sky_view_lut = _buf(self.sky_view_lut_attachment)
+        c.sky_aerial_perspective_lut = _buf(self.sky_aerial_perspective_lut_attachment)
+        return c
+
+
+@dataclass
 class VisbufferDecodeContext:
     """oxc_decode_context: RendererInstance::decode_visbuffer (Passes/DrawGeometry.cpp:192-274), the geometry and material-factor half of
     visbuffer_decode.slang.  `create` takes the visbuffer and the depth as oxc_draw_visbuffer resolved them, the matrix they were drawn with and
@@ -1084,6 +1199,18 @@ class RendererInstance:
         self._keep = context
         self._check(self._lib.oxc_apply_fxaa(self._ctx, C.byref(c), self._stream(stream)))
         return context.fxaa_attachment
+
+    def generate_sky_luts(self, context: SkyLutContext, stream=None) -> None:
+        """RendererInstance.cpp:136-251, the pair the reference builds in its constructor: sky_transmittance_lut, then sky_multiscatter_lut from
+        it, two launches (include/oxcull.h, oxc_generate_sky_luts).  Called again whenever the Atmosphere record changes."""
+        c = context.c()
+        self._check(self._lib.oxc_generate_sky_luts(self._ctx, C.byref(c), self._stream(stream)))
+
+    def draw_atmosphere(self, context: AtmosphereContext, stream=None) -> None:
+        """Passes/PBR.cpp:9-141 without the sky_ibl pass: sky_view_lut and sky_aerial_perspective_lut from the two LUTs of generate_sky_luts, the
+        sun and the camera, two launches (include/oxcull.h, oxc_draw_atmosphere)."""
+        c = context.c()
+        self._check(self._lib.oxc_draw_atmosphere(self._ctx, C.byref(c), self._stream(stream)))
 
     def debug_fxaa_stats(self, stream=None) -> dict:
         """What the last apply_fxaa did, after debug_set_tuning(L.TUNE_FXAA_STATS, 1) (measurement hook; synchronises)."""
