@@ -48,10 +48,12 @@ LIGHT_KIND_DIRECTIONAL, LIGHT_KIND_POINT, LIGHT_KIND_SPOT = 0, 1, 2  # GPU::Ligh
 
 
 class Buffer(C.Structure):
+    _c_name_ = "oxc_buffer"
     _fields_ = [("dptr", C.c_void_p), ("bytes", C.c_uint64)]
 
 
 class Image(C.Structure):
+    _c_name_ = "oxc_image"
     _fields_ = [
         ("dptr", C.c_void_p),
         ("width", C.c_uint32),
@@ -63,6 +65,7 @@ class Image(C.Structure):
 
 
 class ImageArrayU8(C.Structure):
+    _c_name_ = "oxc_image_array_u8"
     _fields_ = [
         ("dptr", C.c_void_p),
         ("width", C.c_uint32),
@@ -74,10 +77,12 @@ class ImageArrayU8(C.Structure):
 
 
 class VirtualClipmap(C.Structure):
+    _c_name_ = "oxc_virtual_clipmap"
     _fields_ = [("projection_view_mat", C.c_float * 16), ("page_offset", C.c_int32 * 2), ("z_near", C.c_float)]
 
 
 class CullCamera(C.Structure):
+    _c_name_ = "oxc_cull_camera"
     _fields_ = [
         ("projection_view", C.c_float * 16),
         ("position", C.c_float * 3),
@@ -89,6 +94,7 @@ class CullCamera(C.Structure):
 
 
 class PreparedFrame(C.Structure):
+    _c_name_ = "oxc_prepared_frame"
     _fields_ = [
         ("mesh_instance_count", C.c_uint32),
         ("max_meshlet_instance_count", C.c_uint32),
@@ -103,6 +109,7 @@ class PreparedFrame(C.Structure):
 
 
 class CullGeometryContext(C.Structure):
+    _c_name_ = "oxc_cull_geometry_context"
     _fields_ = [
         ("struct_size", C.c_uint32),
         ("use_hiz", C.c_uint32),
@@ -132,6 +139,7 @@ class CullGeometryContext(C.Structure):
 
 
 class MainGeometryContext(C.Structure):
+    _c_name_ = "oxc_main_geometry_context"
     _fields_ = [
         ("struct_size", C.c_uint32),
         ("_pad", C.c_uint32),
@@ -141,6 +149,7 @@ class MainGeometryContext(C.Structure):
 
 
 class Counters(C.Structure):
+    _c_name_ = "oxc_counters"
     _fields_ = [
         ("total_visible_meshlet_instances", C.c_uint32),
         ("early_visible_meshlet_instances", C.c_uint32),
@@ -152,6 +161,7 @@ class Counters(C.Structure):
 
 
 class MeshletBoundsDesc(C.Structure):
+    _c_name_ = "oxc_meshlet_bounds_desc"
     _fields_ = [
         ("struct_size", C.c_uint32),
         ("vertex_count", C.c_uint32),
@@ -168,6 +178,7 @@ class MeshletBoundsDesc(C.Structure):
 
 
 class VertexStreamsDesc(C.Structure):
+    _c_name_ = "oxc_vertex_streams_desc"
     _fields_ = [
         ("struct_size", C.c_uint32),
         ("vertex_count", C.c_uint32),
@@ -184,6 +195,7 @@ MESH_MAX_LODS = 8
 
 
 class MeshLodCounts(C.Structure):
+    _c_name_ = "oxc_mesh_lod_counts"
     _fields_ = [
         ("indices_count", C.c_uint32),
         ("meshlet_count", C.c_uint32),
@@ -194,6 +206,7 @@ class MeshLodCounts(C.Structure):
 
 
 class MeshBlobDesc(C.Structure):
+    _c_name_ = "oxc_mesh_blob_desc"
     _fields_ = [
         ("struct_size", C.c_uint32),
         ("vertex_count", C.c_uint32),
@@ -204,10 +217,12 @@ class MeshBlobDesc(C.Structure):
 
 
 class MeshLodOffsets(C.Structure):
+    _c_name_ = "oxc_mesh_lod_offsets"
     _fields_ = [(n, C.c_uint64) for n in ("indices", "meshlets", "meshlet_bounds", "local_triangle_indices", "indirect_vertex_indices")]
 
 
 class MeshBlobLayout(C.Structure):
+    _c_name_ = "oxc_mesh_blob_layout"
     _fields_ = [
         ("size", C.c_uint64),
         ("lod_metadata_offset", C.c_uint64),
@@ -219,6 +234,7 @@ class MeshBlobLayout(C.Structure):
 
 
 class TerrainContext(C.Structure):
+    _c_name_ = "oxc_terrain_context"
     _fields_ = [
         ("struct_size", C.c_uint32),
         ("cull_flags", C.c_uint32),
@@ -237,6 +253,7 @@ class TerrainContext(C.Structure):
 
 
 class DrawContext(C.Structure):
+    _c_name_ = "oxc_draw_context"
     _fields_ = [
         ("struct_size", C.c_uint32),
         ("wide_triangle_index", C.c_uint32),
@@ -253,7 +270,7 @@ class DrawContext(C.Structure):
 
 
 class VsmUpdateContext(C.Structure):
-    """oxc_vsm_update_context (include/oxcull.h)."""
+    _c_name_ = "oxc_vsm_update_context"
     _fields_ = [
         ("struct_size", C.c_uint32),
         ("sun_moved", C.c_uint32),
@@ -286,7 +303,7 @@ class VsmUpdateContext(C.Structure):
 
 
 class VsmDrawContext(C.Structure):
-    """oxc_vsm_draw_context (include/oxcull.h)."""
+    _c_name_ = "oxc_vsm_draw_context"
     _fields_ = [
         ("struct_size", C.c_uint32),
         ("wide_triangle_index", C.c_uint32),
@@ -306,7 +323,7 @@ class VsmDrawContext(C.Structure):
 
 
 class ShadowResolveContext(C.Structure):
-    """oxc_shadow_resolve_context (include/oxcull.h)."""
+    _c_name_ = "oxc_shadow_resolve_context"
     _fields_ = [
         ("struct_size", C.c_uint32),
         ("page_size", C.c_int32),
@@ -330,7 +347,7 @@ class ShadowResolveContext(C.Structure):
 
 
 class ContactShadowsContext(C.Structure):
-    """oxc_contact_shadows_context (include/oxcull.h)."""
+    _c_name_ = "oxc_contact_shadows_context"
     _fields_ = [
         ("struct_size", C.c_uint32),
         ("inv_projection_view", C.c_float * 16),
@@ -347,7 +364,7 @@ class ContactShadowsContext(C.Structure):
 
 
 class AmbientOcclusionContext(C.Structure):
-    """oxc_ambient_occlusion_context (include/oxcull.h)."""
+    _c_name_ = "oxc_ambient_occlusion_context"
     _fields_ = [
         ("struct_size", C.c_uint32),
         ("view", C.c_float * 16),
@@ -371,7 +388,7 @@ class AmbientOcclusionContext(C.Structure):
 
 
 class DecodeContext(C.Structure):
-    """oxc_decode_context (include/oxcull.h)."""
+    _c_name_ = "oxc_decode_context"
     _fields_ = [
         ("struct_size", C.c_uint32),
         ("width", C.c_uint32),
@@ -391,7 +408,7 @@ class DecodeContext(C.Structure):
 
 
 class PbrContext(C.Structure):
-    """oxc_pbr_context (include/oxcull.h)."""
+    _c_name_ = "oxc_pbr_context"
     _fields_ = [
         ("struct_size", C.c_uint32),
         ("width", C.c_uint32),
@@ -420,7 +437,7 @@ class PbrContext(C.Structure):
 
 
 class EyeAdaptationContext(C.Structure):
-    """oxc_eye_adaptation_context (include/oxcull.h)."""
+    _c_name_ = "oxc_eye_adaptation_context"
     _fields_ = [
         ("struct_size", C.c_uint32),
         ("width", C.c_uint32),
@@ -437,6 +454,7 @@ class EyeAdaptationContext(C.Structure):
 
 
 class ImagePyramid(C.Structure):
+    _c_name_ = "oxc_image_pyramid"
     """oxc_image_pyramid (include/oxcull.h): oxc_image's fields, then the allocation's size."""
     _fields_ = [
         ("dptr", C.c_void_p),
@@ -450,7 +468,7 @@ class ImagePyramid(C.Structure):
 
 
 class BloomContext(C.Structure):
-    """oxc_bloom_context (include/oxcull.h)."""
+    _c_name_ = "oxc_bloom_context"
     _fields_ = [
         ("struct_size", C.c_uint32),
         ("width", C.c_uint32),
@@ -470,7 +488,7 @@ class BloomContext(C.Structure):
 
 
 class TonemapContext(C.Structure):
-    """oxc_tonemap_context (include/oxcull.h)."""
+    _c_name_ = "oxc_tonemap_context"
     _fields_ = [
         ("struct_size", C.c_uint32),
         ("width", C.c_uint32),
@@ -494,7 +512,7 @@ class TonemapContext(C.Structure):
 
 
 class FxaaContext(C.Structure):
-    """oxc_fxaa_context (include/oxcull.h)."""
+    _c_name_ = "oxc_fxaa_context"
     _fields_ = [
         ("struct_size", C.c_uint32),
         ("width", C.c_uint32),
@@ -506,6 +524,7 @@ class FxaaContext(C.Structure):
 
 
 class Atmosphere(C.Structure):
+    _c_name_ = "oxc_atmosphere"
     """oxc_atmosphere: the byte layout of GPU::Atmosphere (SceneGPU.hpp:158-181), 136 bytes; the defaults are the record's own."""
     _fields_ = [
         ("rayleigh_scatter", C.c_float * 3),
@@ -530,7 +549,7 @@ class Atmosphere(C.Structure):
 
 
 class SkyLutContext(C.Structure):
-    """oxc_sky_lut_context (include/oxcull.h)."""
+    _c_name_ = "oxc_sky_lut_context"
     _fields_ = [
         ("struct_size", C.c_uint32),
         ("_pad", C.c_uint32),
@@ -542,7 +561,7 @@ class SkyLutContext(C.Structure):
 
 
 class AtmosphereContext(C.Structure):
-    """oxc_atmosphere_context (include/oxcull.h)."""
+    _c_name_ = "oxc_atmosphere_context"
     _fields_ = [
         ("struct_size", C.c_uint32),
         ("_pad", C.c_uint32),
@@ -559,71 +578,93 @@ class AtmosphereContext(C.Structure):
     ]
 
 
-# every symbol include/oxcull.h declares
-EXPORTS = [
-    "oxc_abi_version",
-    "oxc_create",
-    "oxc_destroy",
-    "oxc_last_error",
-    "oxc_reserve",
-    "oxc_generate_hiz",
-    "oxc_cull_geometry",
-    "oxc_cull_geometry_batch",
-    "oxc_join_triangles",
-    "oxc_seed_meshlet_instances",
-    "oxc_read_counters",
-    "oxc_stream_read_probe",
-    "oxc_debug_decode_bounds",
-    "oxc_debug_raster_stats",
-    "oxc_profile_begin",
-    "oxc_profile_end",
-    "oxc_build_meshlet_bounds",
-    "oxc_quantize_vertex_streams",
-    "oxc_mesh_blob_layout_of",
-    "oxc_mesh_blob_finalize",
-    "oxc_mesh_build_create",
-    "oxc_mesh_build_lod_count",
-    "oxc_mesh_build_lod",
-    "oxc_mesh_build_destroy",
-    "oxc_mesh_vertex_fetch_remap",
-    "oxc_generate_hpb",
-    "oxc_update_virtual_shadowmap",
-    "oxc_cull_terrain",
-    "oxc_draw_visbuffer",
-    "oxc_decode_visbuffer",
-    "oxc_debug_visbuffer_decode_stats",
-    "oxc_apply_pbr",
-    "oxc_debug_pbr_apply_stats",
-    "oxc_apply_eye_adaptation",
-    "oxc_apply_bloom",
-    "oxc_apply_tonemap",
-    "oxc_apply_fxaa",
-    "oxc_debug_fxaa_stats",
-    "oxc_generate_sky_luts",
-    "oxc_draw_atmosphere",
-    "oxc_draw_physical_pages",
-    "oxc_debug_vsm_draw_stats",
-    "oxc_resolve_shadowmap",
-    "oxc_debug_vsm_resolve_stats",
-    "oxc_contact_shadows",
-    "oxc_debug_contact_shadows_stats",
-    "oxc_generate_ambient_occlusion",
-    "oxc_debug_ambient_occlusion_stats",
-    "oxc_comm_unique_id",
-    "oxc_comm_init",
-    "oxc_comm_destroy",
-    "oxc_pack_counters",
-    "oxc_pack_counters_batch",
-    "oxc_exchange_counts",
-    "oxc_broadcast_hiz",
-    "oxc_broadcast_hiz_levels",
-    "oxc_debug_read_u32",
-    "oxc_debug_shared_tests_mode",
-    "oxc_debug_tri_loads_mode",
-    "oxc_debug_set_tuning",
-    "oxc_debug_count_occlusion_candidates",
-    "oxc_debug_project_aabb",
-]
+class MeshBuildDesc(C.Structure):
+    _c_name_ = "oxc_mesh_build_desc"
+    _fields_ = [("struct_size", C.c_uint32), ("vertex_count", C.c_uint32), ("index_count", C.c_uint32), ("max_lods", C.c_uint32), ("max_vertices", C.c_uint32),
+                ("max_triangles", C.c_uint32), ("positions", C.c_void_p), ("normals", C.c_void_p), ("indices", C.c_void_p)]
+
+
+class MeshLodView(C.Structure):
+    _c_name_ = "oxc_mesh_lod_view"
+    _fields_ = [("indices", C.c_void_p), ("meshlets", C.c_void_p), ("indirect_vertex_indices", C.c_void_p), ("local_triangle_indices", C.c_void_p),
+                ("indices_count", C.c_uint32), ("meshlet_count", C.c_uint32), ("indirect_vertex_indices_count", C.c_uint32),
+                ("local_triangle_indices_count", C.c_uint32), ("error", C.c_float), ("_pad", C.c_uint32)]
+
+
+class KernelTimes(C.Structure):
+    _c_name_ = "oxc_kernel_times"
+    _fields_ = [("total_ms", C.c_double * 16), ("launches", C.c_uint32 * 16), ("empty_pair_ms", C.c_double)]
+
+
+_vp, _u32, _u64, _P, _status = C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER, C.c_int  # every entry point but five returns an oxc_status
+_stats = (_status, [_vp, _vp, _vp])  # the oxc_debug_*_stats read-backs: (ctx, u32 counters out, stream)
+
+# every symbol include/oxcull.h and include/oxcull_debug.h declare: symbol -> (restype, argtypes); load() applies it
+PROTOTYPES = {
+    "oxc_abi_version": (_u32, []),
+    "oxc_create": (_status, [C.c_int, _P(_vp)]),
+    "oxc_destroy": (None, [_vp]),
+    "oxc_last_error": (C.c_char_p, [_vp]),
+    "oxc_reserve": (_status, [_vp, _u32, _u32]),
+    "oxc_generate_hiz": (_status, [_vp, _P(MainGeometryContext), _vp]),
+    "oxc_cull_geometry": (_status, [_vp, _P(PreparedFrame), _P(CullGeometryContext), _vp]),
+    "oxc_cull_geometry_batch": (_status, [_vp, _u32, _P(PreparedFrame), _P(CullGeometryContext), _vp]),
+    "oxc_join_triangles": (_status, [_vp, _vp]),
+    "oxc_seed_meshlet_instances": (_status, [_vp, _P(CullGeometryContext), _u32, _vp]),
+    "oxc_read_counters": (_status, [_vp, _P(CullGeometryContext), _P(Counters), _vp]),
+    "oxc_stream_read_probe": (_status, [_vp, _vp, _u64, _vp]),
+    "oxc_debug_decode_bounds": (_status, [_vp, _vp, _u32, _vp, _vp]),
+    "oxc_debug_raster_stats": _stats,
+    "oxc_profile_begin": (_status, [_vp]),
+    "oxc_profile_end": (_status, [_vp, _P(KernelTimes)]),
+    "oxc_build_meshlet_bounds": (_status, [_vp, _P(MeshletBoundsDesc), _vp]),
+    "oxc_quantize_vertex_streams": (_status, [_vp, _P(VertexStreamsDesc), _vp]),
+    "oxc_mesh_blob_layout_of": (_status, [_P(MeshBlobDesc), _P(MeshBlobLayout)]),
+    "oxc_mesh_blob_finalize": (_status, [_P(MeshBlobDesc), _P(MeshBlobLayout), _u64, _vp, _u64, _P(C.c_float * 6), _vp]),
+    "oxc_mesh_build_create": (_status, [_P(MeshBuildDesc), _P(_vp)]),
+    "oxc_mesh_build_lod_count": (_u32, [_vp]),
+    "oxc_mesh_build_lod": (_status, [_vp, _u32, _P(MeshLodView)]),
+    "oxc_mesh_build_destroy": (None, [_vp]),
+    "oxc_mesh_vertex_fetch_remap": (_status, [_vp, _u64, _u32, _vp, _vp]),
+    "oxc_generate_hpb": (_status, [_vp, Buffer, _P(ImageArrayU8), _vp]),
+    "oxc_update_virtual_shadowmap": (_status, [_vp, _P(VsmUpdateContext), _vp]),
+    "oxc_cull_terrain": (_status, [_vp, _P(TerrainContext), _vp]),
+    "oxc_draw_visbuffer": (_status, [_vp, _P(PreparedFrame), _P(DrawContext), _vp]),
+    "oxc_decode_visbuffer": (_status, [_vp, _P(PreparedFrame), _P(DecodeContext), _vp]),
+    "oxc_debug_visbuffer_decode_stats": _stats,
+    "oxc_apply_pbr": (_status, [_vp, _P(PbrContext), _vp]),
+    "oxc_debug_pbr_apply_stats": _stats,
+    "oxc_apply_eye_adaptation": (_status, [_vp, _P(EyeAdaptationContext), _vp]),
+    "oxc_apply_bloom": (_status, [_vp, _P(BloomContext), _vp]),
+    "oxc_apply_tonemap": (_status, [_vp, _P(TonemapContext), _vp]),
+    "oxc_apply_fxaa": (_status, [_vp, _P(FxaaContext), _vp]),
+    "oxc_debug_fxaa_stats": _stats,
+    "oxc_generate_sky_luts": (_status, [_vp, _P(SkyLutContext), _vp]),
+    "oxc_draw_atmosphere": (_status, [_vp, _P(AtmosphereContext), _vp]),
+    "oxc_draw_physical_pages": (_status, [_vp, _P(PreparedFrame), _P(VsmDrawContext), _vp]),
+    "oxc_debug_vsm_draw_stats": _stats,
+    "oxc_resolve_shadowmap": (_status, [_vp, _P(ShadowResolveContext), _vp]),
+    "oxc_debug_vsm_resolve_stats": _stats,
+    "oxc_contact_shadows": (_status, [_vp, _P(ContactShadowsContext), _vp]),
+    "oxc_debug_contact_shadows_stats": _stats,
+    "oxc_generate_ambient_occlusion": (_status, [_vp, _P(AmbientOcclusionContext), _vp]),
+    "oxc_debug_ambient_occlusion_stats": _stats,
+    "oxc_comm_unique_id": (_status, [_vp, _vp]),
+    "oxc_comm_init": (_status, [_vp, _vp, _u32, _u32]),
+    "oxc_comm_destroy": (_status, [_vp]),
+    "oxc_pack_counters": (_status, [_vp, _P(CullGeometryContext), _vp, _vp]),
+    "oxc_pack_counters_batch": (_status, [_vp, _u32, _P(CullGeometryContext), _vp, _vp]),
+    "oxc_exchange_counts": (_status, [_vp, _vp, _vp, _vp]),
+    "oxc_broadcast_hiz": (_status, [_vp, _P(Image), _u64, _u32, _vp]),
+    "oxc_broadcast_hiz_levels": (_status, [_vp, _P(Image), _u32, _u64, _u32, _vp]),
+    "oxc_debug_read_u32": (_status, [_vp, _vp, _u32, _vp, _vp]),
+    "oxc_debug_shared_tests_mode": (_u32, [_vp]),
+    "oxc_debug_tri_loads_mode": (_u32, [_vp]),
+    "oxc_debug_set_tuning": (_status, [_vp, _u32, _u32]),
+    "oxc_debug_count_occlusion_candidates": (_status, [_vp, _vp]),
+    "oxc_debug_project_aabb": (_status, [_vp, _P(C.c_float), C.c_float, _vp, _u32, _vp, _vp]),
+}
+EXPORTS = list(PROTOTYPES)
 
 
 def build(force: bool = False) -> str:
@@ -652,95 +693,11 @@ def load(path: str = None) -> C.CDLL:
     lib.oxc_abi_version.restype = C.c_uint32
     if lib.oxc_abi_version() != ABI_VERSION:
         raise RuntimeError(f"{path}: ABI version {lib.oxc_abi_version()} != {ABI_VERSION} (stale build: run __graft_entry__.build())")
-    vp = C.c_void_p
-    lib.oxc_abi_version.restype = C.c_uint32
-    lib.oxc_create.argtypes = [C.c_int, C.POINTER(vp)]
-    lib.oxc_destroy.argtypes = [vp]
-    lib.oxc_destroy.restype = None
-    lib.oxc_last_error.argtypes = [vp]
-    lib.oxc_last_error.restype = C.c_char_p
-    lib.oxc_reserve.argtypes = [vp, C.c_uint32, C.c_uint32]
-    lib.oxc_generate_hiz.argtypes = [vp, C.POINTER(MainGeometryContext), vp]
-    lib.oxc_cull_geometry.argtypes = [vp, C.POINTER(PreparedFrame), C.POINTER(CullGeometryContext), vp]
-    lib.oxc_cull_geometry_batch.argtypes = [vp, C.c_uint32, C.POINTER(PreparedFrame), C.POINTER(CullGeometryContext), vp]
-    lib.oxc_join_triangles.argtypes = [vp, vp]
-    lib.oxc_seed_meshlet_instances.argtypes = [vp, C.POINTER(CullGeometryContext), C.c_uint32, vp]
-    lib.oxc_read_counters.argtypes = [vp, C.POINTER(CullGeometryContext), C.POINTER(Counters), vp]
-    lib.oxc_stream_read_probe.argtypes = [vp, vp, C.c_uint64, vp]
-    lib.oxc_debug_decode_bounds.argtypes = [vp, vp, C.c_uint32, vp, vp]
-    lib.oxc_profile_begin.argtypes = [vp]
-    lib.oxc_profile_end.argtypes = [vp, C.POINTER(KernelTimes)]
-    lib.oxc_build_meshlet_bounds.argtypes = [vp, C.POINTER(MeshletBoundsDesc), vp]
-    lib.oxc_quantize_vertex_streams.argtypes = [vp, C.POINTER(VertexStreamsDesc), vp]
-    lib.oxc_mesh_blob_layout_of.argtypes = [C.POINTER(MeshBlobDesc), C.POINTER(MeshBlobLayout)]
-    lib.oxc_mesh_blob_finalize.argtypes = [C.POINTER(MeshBlobDesc), C.POINTER(MeshBlobLayout), C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_float * 6), vp]
-    lib.oxc_mesh_build_create.argtypes = [C.POINTER(MeshBuildDesc), C.POINTER(vp)]
-    lib.oxc_mesh_build_lod_count.argtypes = [vp]
-    lib.oxc_mesh_build_lod_count.restype = C.c_uint32
-    lib.oxc_mesh_build_lod.argtypes = [vp, C.c_uint32, C.POINTER(MeshLodView)]
-    lib.oxc_mesh_build_destroy.argtypes = [vp]
-    lib.oxc_mesh_build_destroy.restype = None
-    lib.oxc_mesh_vertex_fetch_remap.argtypes = [vp, C.c_uint64, C.c_uint32, vp, vp]
-    lib.oxc_generate_hpb.argtypes = [vp, Buffer, C.POINTER(ImageArrayU8), vp]
-    lib.oxc_update_virtual_shadowmap.argtypes = [vp, C.POINTER(VsmUpdateContext), vp]
-    lib.oxc_cull_terrain.argtypes = [vp, C.POINTER(TerrainContext), vp]
-    lib.oxc_debug_read_u32.argtypes = [vp, vp, C.c_uint32, vp, vp]
-    lib.oxc_debug_shared_tests_mode.argtypes = [vp]
-    lib.oxc_debug_shared_tests_mode.restype = C.c_uint32
-    lib.oxc_debug_tri_loads_mode.argtypes = [vp]
-    lib.oxc_debug_tri_loads_mode.restype = C.c_uint32
-    lib.oxc_debug_raster_stats.argtypes = [vp, vp, vp]
-    lib.oxc_debug_set_tuning.argtypes = [vp, C.c_uint32, C.c_uint32]
-    lib.oxc_debug_count_occlusion_candidates.argtypes = [vp, vp]
-    lib.oxc_comm_unique_id.argtypes = [vp, vp]
-    lib.oxc_comm_init.argtypes = [vp, vp, C.c_uint32, C.c_uint32]
-    lib.oxc_comm_destroy.argtypes = [vp]
-    lib.oxc_pack_counters.argtypes = [vp, C.POINTER(CullGeometryContext), vp, vp]
-    lib.oxc_pack_counters_batch.argtypes = [vp, C.c_uint32, C.POINTER(CullGeometryContext), vp, vp]
-    lib.oxc_exchange_counts.argtypes = [vp, vp, vp, vp]
-    lib.oxc_broadcast_hiz.argtypes = [vp, C.POINTER(Image), C.c_uint64, C.c_uint32, vp]
-    lib.oxc_broadcast_hiz_levels.argtypes = [vp, C.POINTER(Image), C.c_uint32, C.c_uint64, C.c_uint32, vp]
-    lib.oxc_debug_project_aabb.argtypes = [vp, C.POINTER(C.c_float), C.c_float, vp, C.c_uint32, vp, vp]
-    lib.oxc_draw_visbuffer.argtypes = [vp, C.POINTER(PreparedFrame), C.POINTER(DrawContext), vp]
-    lib.oxc_decode_visbuffer.argtypes = [vp, C.POINTER(PreparedFrame), C.POINTER(DecodeContext), vp]
-    lib.oxc_debug_visbuffer_decode_stats.argtypes = [vp, vp, vp]
-    lib.oxc_apply_pbr.argtypes = [vp, C.POINTER(PbrContext), vp]
-    lib.oxc_debug_pbr_apply_stats.argtypes = [vp, vp, vp]
-    lib.oxc_apply_eye_adaptation.argtypes = [vp, C.POINTER(EyeAdaptationContext), vp]
-    lib.oxc_apply_bloom.argtypes = [vp, C.POINTER(BloomContext), vp]
-    lib.oxc_apply_tonemap.argtypes = [vp, C.POINTER(TonemapContext), vp]
-    lib.oxc_apply_fxaa.argtypes = [vp, C.POINTER(FxaaContext), vp]
-    lib.oxc_debug_fxaa_stats.argtypes = [vp, vp, vp]
-    lib.oxc_generate_sky_luts.argtypes = [vp, C.POINTER(SkyLutContext), vp]
-    lib.oxc_draw_atmosphere.argtypes = [vp, C.POINTER(AtmosphereContext), vp]
-    lib.oxc_draw_physical_pages.argtypes = [vp, C.POINTER(PreparedFrame), C.POINTER(VsmDrawContext), vp]
-    lib.oxc_debug_vsm_draw_stats.argtypes = [vp, vp, vp]
-    lib.oxc_resolve_shadowmap.argtypes = [vp, C.POINTER(ShadowResolveContext), vp]
-    lib.oxc_debug_vsm_resolve_stats.argtypes = [vp, vp, vp]
-    lib.oxc_contact_shadows.argtypes = [vp, C.POINTER(ContactShadowsContext), vp]
-    lib.oxc_debug_contact_shadows_stats.argtypes = [vp, vp, vp]
-    lib.oxc_generate_ambient_occlusion.argtypes = [vp, C.POINTER(AmbientOcclusionContext), vp]
-    lib.oxc_debug_ambient_occlusion_stats.argtypes = [vp, vp, vp]
-    for name in EXPORTS:
-        if name not in ("oxc_abi_version", "oxc_destroy", "oxc_last_error", "oxc_mesh_build_lod_count", "oxc_mesh_build_destroy"):
-            getattr(lib, name).restype = C.c_int
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _libs[path] = lib
     return lib
-
-
-class MeshBuildDesc(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("vertex_count", C.c_uint32), ("index_count", C.c_uint32), ("max_lods", C.c_uint32), ("max_vertices", C.c_uint32),
-                ("max_triangles", C.c_uint32), ("positions", C.c_void_p), ("normals", C.c_void_p), ("indices", C.c_void_p)]
-
-
-class MeshLodView(C.Structure):
-    _fields_ = [("indices", C.c_void_p), ("meshlets", C.c_void_p), ("indirect_vertex_indices", C.c_void_p), ("local_triangle_indices", C.c_void_p),
-                ("indices_count", C.c_uint32), ("meshlet_count", C.c_uint32), ("indirect_vertex_indices_count", C.c_uint32),
-                ("local_triangle_indices_count", C.c_uint32), ("error", C.c_float), ("_pad", C.c_uint32)]
-
-
-class KernelTimes(C.Structure):
-    _fields_ = [("total_ms", C.c_double * 16), ("launches", C.c_uint32 * 16), ("empty_pair_ms", C.c_double)]
 
 
 # OXC_K_* (include/oxcull.h); the *_late entries are the LatePass instantiations, timed apart

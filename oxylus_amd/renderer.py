@@ -1,11 +1,17 @@
-"""Host-side mirror of the reference's RendererInstance cull entry points over the C ABI.
+"""Host-side mirror of the reference's RendererInstance over the C ABI: the passes of a frame from the cull to the anti-aliased,
+tonemapped image, and the producers around them.
 
-Same names and field meaning as Oxylus/include/Render/RendererInstance.hpp:143-216,397-398:
-`RendererInstance.generate_hiz(MainGeometryContext)` and
-`RendererInstance.cull_geometry(CullGeometryContext)`.  Buffers are torch CUDA tensors (device
-memory + streams only; all compute is in liboxcull.so).  The compiled C++ shim with the same
-surface is oxylus_amd/host/RendererInstance.hpp; this Python twin exists because the test
-runner and bench driver are Python.
+Same names and field meaning as Oxylus/include/Render/RendererInstance.hpp.  The module holds the image types (ImageAttachment,
+HpbAttachment, BloomPyramid), PreparedFrame, one dataclass per oxc_*_context of include/oxcull.h (CullGeometryContext, the virtual
+shadowmap's three, the per-pixel passes', the post-process passes', the two sky contexts) and `RendererInstance`, whose methods are the
+entry points.  Buffers are torch CUDA tensors (device memory + streams only; all compute is in liboxcull.so).  The compiled C++ shim with
+the same surface is oxylus_amd/host/RendererInstance.hpp; this Python twin exists because the test runner and bench driver are Python.
+
+Marshalling (_marshal.py): a context's `.c()` fills its L.<Structure> by walking the structure's `_fields_`.  A C field takes the
+dataclass field of the same name, converted by the C type (tensor -> oxc_buffer, image -> its own .c(), sequence -> array, bool / int ->
+u32, number -> float); the class states only the exceptions, `_derived` (C field -> another attribute's path, or a function of the context)
+and `_leave` (padding and what the library writes back).  A C field that none of the three accounts for is a TypeError when the class is
+created.
 """
 from __future__ import annotations
 
@@ -18,13 +24,8 @@ from typing import Optional
 import torch
 
 from . import lib as L
+from ._marshal import Marshalled, _buf
 from .synth import Scene, hiz_layout
-
-
-def _buf(t: Optional[torch.Tensor]) -> L.Buffer:
-    if t is None:
-        return L.Buffer(None, 0)
-    return L.Buffer(t.data_ptr(), t.numel() * t.element_size())
 
 
 @dataclass
@@ -103,9 +104,12 @@ class HpbAttachment:
 
 
 @dataclass
-class PreparedFrame:
+class PreparedFrame(Marshalled):
     """The PreparedFrame buffers of the cull path (RendererInstance.hpp:143-169), sized as in
     RendererInstance::update (RendererInstance.cpp:1640-1732)."""
+    _ctype = L.PreparedFrame
+    _derived = {"mesh_instance_count": "scene.n_mesh_instances", "meshes_buffer": "scene.meshes", "transforms_world_buffer": "scene.transforms",
+                "mesh_instances_buffer": "scene.mesh_instances"}
     scene: Scene
     max_meshlet_instance_count: int
     meshlet_instances_buffer: torch.Tensor
@@ -125,24 +129,13 @@ class PreparedFrame:
         reordered = torch.zeros(max(n, 1) * max_tris * 3 * index_words, dtype=torch.int32, device=dev) if with_triangles else None
         return PreparedFrame(scene, n, mli, vis_idx, mask, reordered)
 
-    def c(self) -> L.PreparedFrame:
-        f = L.PreparedFrame()
-        s = self.scene
-        f.mesh_instance_count = s.n_mesh_instances
-        f.max_meshlet_instance_count = self.max_meshlet_instance_count
-        f.meshes_buffer = _buf(s.meshes)
-        f.transforms_world_buffer = _buf(s.transforms)
-        f.mesh_instances_buffer = _buf(s.mesh_instances)
-        f.meshlet_instances_buffer = _buf(self.meshlet_instances_buffer)
-        f.visible_meshlet_instances_indices_buffer = _buf(self.visible_meshlet_instances_indices_buffer)
-        f.meshlet_instance_visibility_mask_buffer = _buf(self.meshlet_instance_visibility_mask_buffer)
-        f.reordered_indices_buffer = _buf(self.reordered_indices_buffer)
-        return f
-
 
 @dataclass
-class CullGeometryContext:
-    """RendererInstance.hpp:171-197."""
+class CullGeometryContext(Marshalled):
+    """RendererInstance.hpp:171-197.  `.c()` fills and returns the persistent `_c`: the library writes the call's output buffers into it, and
+    read_counters, draw_visbuffer and VsmDrawContext read them there."""
+    _ctype = L.CullGeometryContext
+    _leave = ("_reserved1", "visibility_buffer", "cull_meshlets_cmd_buffer", "cull_triangles_cmd_buffer", "draw_geometry_cmd_buffer")
     use_hiz: bool = False
     use_hpb: bool = False
     init_cull_meshes: bool = False
@@ -164,33 +157,16 @@ class CullGeometryContext:
     _c: L.CullGeometryContext = field(default_factory=L.CullGeometryContext)
 
     def c(self) -> L.CullGeometryContext:
-        c = self._c
-        c.struct_size = C.sizeof(L.CullGeometryContext)
-        c.use_hiz, c.use_hpb, c.init_cull_meshes = int(self.use_hiz), int(self.use_hpb), int(self.init_cull_meshes)
-        c.cull_flags, c.stages = self.cull_flags, self.stages
-        if self.cull_camera is not None:
-            c.cull_camera = self.cull_camera
-        if self.hiz_attachment is not None:
-            c.hiz_attachment = self.hiz_attachment.c()
-        if self.hpb_attachment is not None:
-            c.hpb_attachment = self.hpb_attachment.c()
-        c.vsm_clipmaps_buffer = _buf(self.vsm_clipmaps_buffer)
-        c.vsm_clipmap_dirty_flags_buffer = _buf(self.vsm_clipmap_dirty_flags_buffer)
-        c.vsm_clipmap_count = self.vsm_clipmap_count
-        c.wide_triangle_index = int(self.wide_triangle_index)
-        c.small_triangle_cull = int(self.small_triangle_cull)
-        c.async_triangles = int(self.async_triangles)
-        c.share_pass_tests = int(self.share_pass_tests)
-        c.unordered_output = int(self.unordered_output)
-        c.implicit_meshlet_instances = int(self.implicit_meshlet_instances)
-        c.meshlet_instance_runs_buffer = _buf(self.meshlet_instance_runs_buffer)
-        return c
+        return self._fill(self._c)
 
 
 @dataclass
-class VirtualShadowmapContext:
+class VirtualShadowmapContext(Marshalled):
     """oxc_vsm_update_context: the page-management part of RendererInstance::draw_virtual_shadowmap (Shadowmaps.cpp:143-421).
     Sizes default to the reference's configuration (RendererInstance.hpp:262-267); `create` allocates the outputs."""
+    _ctype = L.VsmUpdateContext
+    _derived = {"depth_extent": lambda s: (s.depth_attachment.width, s.depth_attachment.height),
+                "dirty_mesh_instance_count": lambda s: 0 if s.dirty_mesh_instance_indices is None else s.dirty_mesh_instance_indices.numel()}
     virtual_page_table: torch.Tensor              # int32 [clipmap_count, n, n], persistent across frames
     vsm_clipmaps_buffer: torch.Tensor             # uint8 [clipmap_count * 76] GPU::VirtualClipmap records
     depth_attachment: ImageAttachment             # R32F, levels = 1: the main view's reversed-Z depth
@@ -239,43 +215,20 @@ class VirtualShadowmapContext:
             page_size=page_size, page_table_size=n, physical_page_table_size=physical_page_table_size, clipmap_count=layers,
             hpb_attachment=hpb, physical_page_image=phys, **kw)
 
-    def c(self) -> L.VsmUpdateContext:
-        c = L.VsmUpdateContext()
-        c.struct_size = C.sizeof(L.VsmUpdateContext)
-        c.sun_moved = int(self.sun_moved)
-        c.page_size, c.page_table_size, c.physical_page_table_size = self.page_size, self.page_table_size, self.physical_page_table_size
-        c.clipmap_count = self.clipmap_count
-        c.depth_extent[0], c.depth_extent[1] = self.depth_attachment.width, self.depth_attachment.height
-        c.first_clipmap_width, c.clipmap_selection_bias, c.virtual_extent = self.first_clipmap_width, self.clipmap_selection_bias, self.virtual_extent
-        ids = self.dirty_mesh_instance_indices
-        c.dirty_mesh_instance_count = 0 if ids is None else ids.numel()
-        for i in range(16):
-            c.inv_projection_view[i] = float(self.inv_projection_view[i])
-        c.resolution[0], c.resolution[1] = float(self.resolution[0]), float(self.resolution[1])
-        c.virtual_page_table = _buf(self.virtual_page_table)
-        c.vsm_clipmaps_buffer = _buf(self.vsm_clipmaps_buffer)
-        c.depth_attachment = self.depth_attachment.c()
-        c.dirty_mesh_instance_indices = _buf(ids)
-        c.mesh_instances_buffer = _buf(self.mesh_instances_buffer)
-        c.meshes_buffer = _buf(self.meshes_buffer)
-        c.transforms_world_buffer = _buf(self.transforms_world_buffer)
-        c.transforms_previous_buffer = _buf(self.transforms_previous_buffer)
-        c.vsm_clipmap_dirty_flags_buffer = _buf(self.vsm_clipmap_dirty_flags_buffer)
-        c.dirty_physical_pages_buffer = _buf(self.dirty_physical_pages_buffer)
-        c.clear_cmd_buffer = _buf(self.clear_cmd_buffer)
-        c.counters_buffer = _buf(self.counters_buffer)
-        if self.hpb_attachment is not None:
-            c.hpb_attachment = self.hpb_attachment.c()
-        if self.physical_page_image is not None:
-            c.physical_page_image = self.physical_page_image.c()
-        return c
+
+def _vsm_draw_cmd(s: "VsmDrawContext") -> L.Buffer:
+    if s.draw_cmd is not None:
+        return _buf(s.draw_cmd)
+    return s.cull._c.draw_geometry_cmd_buffer if s.cull is not None else _buf(None)
 
 
 @dataclass
-class VsmDrawContext:
+class VsmDrawContext(Marshalled):
     """oxc_vsm_draw_context: the shadow draw of RendererInstance::draw_virtual_shadowmap (Shadowmaps.cpp:466-754).  `create` takes the shape and
     the page buffers from a VirtualShadowmapContext and the triangle list from the shadow CullGeometryContext (its draw_geometry_cmd_buffer,
     read when the draw is enqueued)."""
+    _ctype = L.VsmDrawContext
+    _derived = {"draw_geometry_cmd_buffer": _vsm_draw_cmd}
     virtual_page_table: torch.Tensor              # int32 [clipmap_count, n, n]
     vsm_clipmaps_buffer: torch.Tensor             # uint8 [clipmap_count * 76] GPU::VirtualClipmap records
     vsm_clipmap_dirty_flags_buffer: torch.Tensor  # int32 [clipmap_count]
@@ -303,30 +256,12 @@ class VsmDrawContext:
                               page_table_size=vsm.page_table_size, physical_page_table_size=vsm.physical_page_table_size, clipmap_count=k,
                               wide_triangle_index=int(cull.wide_triangle_index) if cull is not None else 0, cull=cull, **cmds)
 
-    def c(self) -> L.VsmDrawContext:
-        c = L.VsmDrawContext()
-        c.struct_size = C.sizeof(L.VsmDrawContext)
-        c.wide_triangle_index = int(self.wide_triangle_index)
-        c.page_size, c.page_table_size, c.physical_page_table_size = self.page_size, self.page_table_size, self.physical_page_table_size
-        c.clipmap_count = self.clipmap_count
-        if self.draw_cmd is not None:
-            c.draw_geometry_cmd_buffer = _buf(self.draw_cmd)
-        elif self.cull is not None:
-            c.draw_geometry_cmd_buffer = self.cull._c.draw_geometry_cmd_buffer
-        c.virtual_page_table = _buf(self.virtual_page_table)
-        c.vsm_clipmaps_buffer = _buf(self.vsm_clipmaps_buffer)
-        c.vsm_clipmap_dirty_flags_buffer = _buf(self.vsm_clipmap_dirty_flags_buffer)
-        c.physical_page_image = self.physical_page_image.c()
-        c.draw_commands_buffer = _buf(self.draw_commands_buffer)
-        c.draw_count_buffer = _buf(self.draw_count_buffer)
-        c.draw_clipmaps_buffer = _buf(self.draw_clipmaps_buffer)
-        return c
-
 
 @dataclass
-class ShadowResolveContext:
+class ShadowResolveContext(Marshalled):
     """oxc_shadow_resolve_context: RendererInstance::resolve_shadowmap (Shadowmaps.cpp:756-822).  `create` takes the shape, the camera and the
     page buffers from a VirtualShadowmapContext and allocates the output."""
+    _ctype = L.ShadowResolveContext
     depth_attachment: ImageAttachment             # R32F, levels = 1: the main view's reversed-Z depth
     normal_attachment: torch.Tensor               # int16 [H, W, 4]: R16G16B16A16Sfloat bits, .ba = the octahedral world normal
     vsm_clipmaps_buffer: torch.Tensor             # uint8 [clipmap_count * 76]
@@ -359,31 +294,12 @@ class ShadowResolveContext:
                                     first_clipmap_width=vsm.first_clipmap_width, clipmap_selection_bias=vsm.clipmap_selection_bias,
                                     virtual_extent=vsm.virtual_extent)
 
-    def c(self) -> L.ShadowResolveContext:
-        c = L.ShadowResolveContext()
-        c.struct_size = C.sizeof(L.ShadowResolveContext)
-        c.page_size, c.page_table_size, c.physical_page_table_size = self.page_size, self.page_table_size, self.physical_page_table_size
-        c.clipmap_count = self.clipmap_count
-        c.first_clipmap_width, c.clipmap_selection_bias, c.virtual_extent = self.first_clipmap_width, self.clipmap_selection_bias, self.virtual_extent
-        c.z_length = float(self.z_length)
-        for i in range(3):
-            c.directional_light_dir[i] = float(self.directional_light_dir[i])
-        for i in range(16):
-            c.inv_projection_view[i] = float(self.inv_projection_view[i])
-        c.resolution[0], c.resolution[1] = float(self.resolution[0]), float(self.resolution[1])
-        c.depth_attachment = self.depth_attachment.c()
-        c.normal_attachment = _buf(self.normal_attachment)
-        c.vsm_clipmaps_buffer = _buf(self.vsm_clipmaps_buffer)
-        c.virtual_page_table = _buf(self.virtual_page_table)
-        c.physical_page_image = self.physical_page_image.c()
-        c.resolved_shadows_attachment = self.resolved_shadows_attachment.c()
-        return c
-
 
 @dataclass
-class ContactShadowsContext:
+class ContactShadowsContext(Marshalled):
     """oxc_contact_shadows_context: the contact_shadows pass of RendererInstance::render (RendererInstance.cpp:990-1020).  `create` takes the
     depth image and the camera and allocates the output; steps / thickness / shadow_length default to the engine's (RendererCVar.cpp:30-34)."""
+    _ctype = L.ContactShadowsContext
     depth_attachment: ImageAttachment            # R32F, levels = 1: the main view's reversed-Z depth
     contact_shadows_attachment: ImageAttachment  # R32F out, the extent of the depth image
     inv_projection_view: list                    # column-major float[16], as view and projection
@@ -403,28 +319,13 @@ class ContactShadowsContext:
         return ContactShadowsContext(d, out, [float(x) for x in inv_projection_view], [float(x) for x in view], [float(x) for x in projection],
                                      float(near_clip), tuple(float(x) for x in sun_dir), int(steps), float(thickness), float(shadow_length))
 
-    def c(self) -> L.ContactShadowsContext:
-        c = L.ContactShadowsContext()
-        c.struct_size = C.sizeof(L.ContactShadowsContext)
-        for i in range(16):
-            c.inv_projection_view[i] = float(self.inv_projection_view[i])
-            c.view[i] = float(self.view[i])
-            c.projection[i] = float(self.projection[i])
-        c.near_clip = float(self.near_clip)
-        for i in range(3):
-            c.sun_dir[i] = float(self.sun_dir[i])
-        c.steps = int(self.steps)
-        c.thickness, c.shadow_length = float(self.thickness), float(self.shadow_length)
-        c.depth_attachment = self.depth_attachment.c()
-        c.contact_shadows_attachment = self.contact_shadows_attachment.c()
-        return c
-
 
 @dataclass
-class AmbientOcclusionContext:
+class AmbientOcclusionContext(Marshalled):
     """oxc_ambient_occlusion_context: RendererInstance::generate_ambient_occlusion (Passes/PBR.cpp:179-311).  `create` takes the depth image,
     the normal image, the Hilbert table and the camera and allocates the three intermediates and the output; the settings default to
     GPU::VBGTAOSettings' (SceneGPU.hpp:286-293)."""
+    _ctype = L.AmbientOcclusionContext
     depth_attachment: ImageAttachment         # R32F, levels = 1: the main view's reversed-Z depth
     normal_attachment: torch.Tensor           # int16 / uint16 [H, W, 4]
     hilbert_noise: torch.Tensor               # int16 / uint16 [64, 64]
@@ -455,32 +356,15 @@ class AmbientOcclusionContext:
                                        [float(x) for x in view], [float(x) for x in projection], res, float(far_clip), float(thickness),
                                        int(slice_count), int(samples_per_slice_side), float(effect_radius), int(noise_index), float(final_power))
 
-    def c(self) -> L.AmbientOcclusionContext:
-        c = L.AmbientOcclusionContext()
-        c.struct_size = C.sizeof(L.AmbientOcclusionContext)
-        for i in range(16):
-            c.view[i] = float(self.view[i])
-            c.projection[i] = float(self.projection[i])
-        c.resolution[0], c.resolution[1] = float(self.resolution[0]), float(self.resolution[1])
-        c.far_clip, c.thickness, c.effect_radius, c.final_power = float(self.far_clip), float(self.thickness), float(self.effect_radius), float(self.final_power)
-        c.slice_count, c.samples_per_slice_side = int(self.slice_count), int(self.samples_per_slice_side)
-        c.noise_index = int(self.noise_index) & 0xFFFFFFFF
-        c.depth_attachment = self.depth_attachment.c()
-        c.normal_attachment = _buf(self.normal_attachment)
-        c.hilbert_noise = _buf(self.hilbert_noise)
-        c.prefiltered_depth = self.prefiltered_depth.c()
-        c.depth_differences = _buf(self.depth_differences)
-        c.noisy_occlusion = _buf(self.noisy_occlusion)
-        c.ambient_occlusion_attachment = _buf(self.ambient_occlusion_attachment)
-        return c
-
 
 @dataclass
-class PBRContext:
+class PBRContext(Marshalled):
     """oxc_pbr_context: the no-atmosphere branch of RendererInstance::apply_pbr (Passes/PBR.cpp:313-534, pbr_apply_no_atmos).  `create` takes
     the depth image, the four G-buffer images of decode_visbuffer, the ambient occlusion and the two shadow terms as their producers wrote
     them, the camera, the sun, the lights (synth.pack_lights) and the Sky record, and allocates the output: int32 [H, W] (B10G11R11), or
     int16 [H, W, 4] (R16G16B16A16 Sfloat) with L.SCENE_TRANSPARENT_BACKGROUND.  An image whose flag is clear may be None."""
+    _ctype = L.PbrContext
+    _derived = {"width": "depth_attachment.width", "height": "depth_attachment.height"}
     depth_attachment: ImageAttachment             # R32F, levels = 1
     albedo_attachment: torch.Tensor               # int32 [H, W]: R8G8B8A8 sRGB
     normal_attachment: torch.Tensor               # int16 [H, W, 4]: .rg mapped, .ba smooth
@@ -520,33 +404,6 @@ class PBRContext:
                           tuple(float(x) for x in sun_dir), float(sun_intensity), lights, count, tuple(float(x) for x in base_ambient_color),
                           tuple(float(x) for x in sky_solid_color), tuple(float(x) for x in sky_ambient_color), bool(sky_has_texture))
 
-    def c(self) -> L.PbrContext:
-        c = L.PbrContext()
-        c.struct_size = C.sizeof(L.PbrContext)
-        c.width, c.height = self.depth_attachment.width, self.depth_attachment.height
-        c.scene_flags, c.light_count, c.sky_has_texture = int(self.scene_flags), int(self.light_count), int(bool(self.sky_has_texture))
-        for i in range(16):
-            c.inv_projection_view[i] = float(self.inv_projection_view[i])
-        for i in range(3):
-            c.camera_position[i], c.sun_dir[i] = float(self.camera_position[i]), float(self.sun_dir[i])
-            c.base_ambient_color[i], c.sky_ambient_color[i] = float(self.base_ambient_color[i]), float(self.sky_ambient_color[i])
-        for i in range(4):
-            c.sky_solid_color[i] = float(self.sky_solid_color[i])
-        c.sun_intensity = float(self.sun_intensity)
-        c.depth_attachment = self.depth_attachment.c()
-        c.albedo_attachment = _buf(self.albedo_attachment)
-        c.normal_attachment = _buf(self.normal_attachment)
-        c.emissive_attachment = _buf(self.emissive_attachment)
-        c.metallic_roughness_occlusion_attachment = _buf(self.metallic_roughness_occlusion_attachment)
-        c.ambient_occlusion_attachment = _buf(self.ambient_occlusion_attachment)
-        if self.resolved_shadows_attachment is not None:
-            c.resolved_shadows_attachment = self.resolved_shadows_attachment.c()
-        if self.contact_shadows_attachment is not None:
-            c.contact_shadows_attachment = self.contact_shadows_attachment.c()
-        c.lights_buffer = _buf(self.lights_buffer)
-        c.final_attachment = _buf(self.final_attachment)
-        return c
-
 
 def exposure_buffer(device="cuda") -> torch.Tensor:
     """A fresh GPU::HistogramLuminance {adapted_luminance, exposure} = {1.0, 1.0}, as RendererInstance.cpp:1778-1784 fills it: float32 [2].
@@ -563,10 +420,13 @@ def eye_adaptation_time_coeff(adaptation_speed: float, delta_time: float) -> flo
 
 
 @dataclass
-class EyeAdaptationContext:
+class EyeAdaptationContext(Marshalled):
     """oxc_eye_adaptation_context: RendererInstance::apply_eye_adaptation (Passes/PostProcess.cpp:7-77).  `create` takes the image apply_pbr
     wrote -- int32 [H, W] (B10G11R11) or int16 [H, W, 4] (R16G16B16A16 Sfloat); the format follows from the shape --, the persistent
     exposure buffer (exposure_buffer()) and the GPU::HistogramLuminanceInfo settings, and allocates the histogram: int32 [256]."""
+    _ctype = L.EyeAdaptationContext
+    _derived = {"time_coeff": lambda s, delta_time: float(s.time_coeff) if s.time_coeff is not None
+                else eye_adaptation_time_coeff(s.adaptation_speed, delta_time)}
     final_attachment: torch.Tensor   # in
     histogram_buffer: torch.Tensor   # out: int32 [256], this frame's counts
     exposure_buffer: torch.Tensor    # in/out: float32 [2]
@@ -588,15 +448,7 @@ class EyeAdaptationContext:
                                     float(min_exposure), float(max_exposure), float(adaptation_speed), float(ev100_bias), time_coeff)
 
     def c(self, delta_time: float = 0.0) -> L.EyeAdaptationContext:
-        c = L.EyeAdaptationContext()
-        c.struct_size = C.sizeof(L.EyeAdaptationContext)
-        c.width, c.height, c.source_format = int(self.width), int(self.height), int(self.source_format)
-        c.min_exposure, c.max_exposure, c.ev100_bias = float(self.min_exposure), float(self.max_exposure), float(self.ev100_bias)
-        c.time_coeff = float(self.time_coeff) if self.time_coeff is not None else eye_adaptation_time_coeff(self.adaptation_speed, delta_time)
-        c.final_attachment = _buf(self.final_attachment)
-        c.histogram_buffer = _buf(self.histogram_buffer)
-        c.exposure_buffer = _buf(self.exposure_buffer)
-        return c
+        return self._fill(L.EyeAdaptationContext(), delta_time)
 
 
 def bloom_layout(width: int, height: int, source_format: int = L.EYE_SOURCE_B10G11R11, gap_texels: int = 0):
@@ -651,11 +503,13 @@ class BloomPyramid:
 
 
 @dataclass
-class BloomContext:
+class BloomContext(Marshalled):
     """oxc_bloom_context: RendererInstance::apply_bloom (Passes/PostProcess.cpp:79-203).  `create` takes the image apply_pbr wrote -- int32
     [H, W] (B10G11R11) or int16 [H, W, 4] (R16G16B16A16 Sfloat); the format follows from the shape --, the scene flags (only
     L.SCENE_HAS_EYE_ADAPTATION is read) and the exposure buffer apply_eye_adaptation left behind, and allocates the two pyramids.
     bloom_intensity is what apply_bloom hands to the tonemap: TonemapContext.create reads it from here; oxc_apply_bloom does not."""
+    _ctype = L.BloomContext
+    _leave = ("_pad",)
     final_attachment: torch.Tensor                # in
     exposure_buffer: Optional[torch.Tensor]       # in with SCENE_HAS_EYE_ADAPTATION: float32 [2]
     bloom_downsampled_attachment: BloomPyramid    # out
@@ -679,24 +533,14 @@ class BloomContext:
         return BloomContext(final_attachment, exposure, BloomPyramid.create(W, H, fmt, dev), BloomPyramid.create(W, H, fmt, dev), W, H, fmt, int(scene_flags),
                             float(threshold), float(soft_threshold), float(clamp_value), float(radius), float(bloom_intensity))
 
-    def c(self) -> L.BloomContext:
-        c = L.BloomContext()
-        c.struct_size = C.sizeof(L.BloomContext)
-        c.width, c.height, c.source_format, c.scene_flags = int(self.width), int(self.height), int(self.source_format), int(self.scene_flags)
-        c.threshold, c.soft_threshold, c.clamp_value, c.radius = float(self.threshold), float(self.soft_threshold), float(self.clamp_value), float(self.radius)
-        c.final_attachment = _buf(self.final_attachment)
-        c.exposure_buffer = _buf(self.exposure_buffer)
-        c.bloom_downsampled_attachment = self.bloom_downsampled_attachment.c()
-        c.bloom_upsampled_attachment = self.bloom_upsampled_attachment.c()
-        return c
-
 
 @dataclass
-class TonemapContext:
+class TonemapContext(Marshalled):
     """oxc_tonemap_context: RendererInstance::apply_tonemap (Passes/PostProcess.cpp:205-247).  `create` takes the image apply_pbr wrote -- int32
     [H, W] (B10G11R11) or int16 [H, W, 4] (R16G16B16A16 Sfloat); the format follows from the shape --, the scene flags, the tone curve, the
     exposure buffer apply_eye_adaptation left behind and the BloomContext apply_bloom ran on (its upsample pyramid and its bloom_intensity),
     and allocates the 8-bit destination, int32 [H, W].  The six GPU::PostProcessSettings fields carry the engine's defaults."""
+    _ctype = L.TonemapContext
     final_attachment: torch.Tensor                            # in
     exposure_buffer: Optional[torch.Tensor]                   # in with SCENE_HAS_EYE_ADAPTATION: float32 [2]
     bloom_upsampled_attachment: Optional[BloomPyramid]        # in with SCENE_HAS_BLOOM: only level 0 is read
@@ -726,27 +570,13 @@ class TonemapContext:
         return TonemapContext(final_attachment, exposure_buffer, bloom.bloom_upsampled_attachment if bloom is not None else None, dst, W, H, fmt,
                               int(output_format), int(scene_flags), int(tonemap_type), **settings)
 
-    def c(self) -> L.TonemapContext:
-        c = L.TonemapContext()
-        c.struct_size = C.sizeof(L.TonemapContext)
-        c.width, c.height, c.source_format, c.output_format = int(self.width), int(self.height), int(self.source_format), int(self.output_format)
-        c.scene_flags, c.tonemap_type = int(self.scene_flags) & 0xFFFFFFFF, int(self.tonemap_type)
-        c.exposure, c.chromatic_aberration_amount, c.vignette_amount = float(self.exposure), float(self.chromatic_aberration_amount), float(self.vignette_amount)
-        c.film_grain_scale, c.film_grain_amount, c.film_grain_seed = float(self.film_grain_scale), float(self.film_grain_amount), int(self.film_grain_seed) & 0xFFFFFFFF
-        c.bloom_intensity = float(self.bloom_intensity)
-        c.final_attachment = _buf(self.final_attachment)
-        if self.bloom_upsampled_attachment is not None:
-            c.bloom_upsampled_attachment = self.bloom_upsampled_attachment.c()
-        c.exposure_buffer = _buf(self.exposure_buffer)
-        c.dst_attachment = _buf(self.dst_attachment)
-        return c
-
 
 @dataclass
-class FxaaContext:
+class FxaaContext(Marshalled):
     """oxc_fxaa_context: the `fxaa` pass (RendererInstance.cpp:1225-1255, passes/fxaa/fxaa.slang).  `create` takes the image apply_pbr wrote --
     int32 [H, W] (B10G11R11) or int16 [H, W, 4] (R16G16B16A16 Sfloat); the format follows from the shape -- and allocates fxaa_attachment,
     a second image of the same shape."""
+    _ctype = L.FxaaContext
     final_attachment: torch.Tensor  # in
     fxaa_attachment: torch.Tensor   # out
     width: int
@@ -759,19 +589,12 @@ class FxaaContext:
         H, W = int(final_attachment.shape[0]), int(final_attachment.shape[1])
         return FxaaContext(final_attachment, torch.zeros_like(final_attachment), W, H, fmt)
 
-    def c(self) -> L.FxaaContext:
-        c = L.FxaaContext()
-        c.struct_size = C.sizeof(L.FxaaContext)
-        c.width, c.height, c.source_format = int(self.width), int(self.height), int(self.source_format)
-        c.final_attachment = _buf(self.final_attachment)
-        c.fxaa_attachment = _buf(self.fxaa_attachment)
-        return c
-
 
 @dataclass
-class Atmosphere:
+class Atmosphere(Marshalled):
     """GPU::Atmosphere (SceneGPU.hpp:158-181).  The defaults are the record's own; `engine()` is what RendererInstance.cpp:1445-1455 makes of the
     AtmosphereComponent's defaults (the scattering and absorption coefficients times 1e-3f in binary32) with the engine's four LUT extents."""
+    _ctype = L.Atmosphere
     rayleigh_scatter: tuple = (0.005802, 0.013558, 0.033100)
     rayleigh_density: float = 8.0
     mie_scatter: tuple = (0.003996, 0.003996, 0.003996)
@@ -801,26 +624,17 @@ class Atmosphere:
             setattr(a, k, v)
         return a
 
-    def c(self) -> L.Atmosphere:
-        c = L.Atmosphere()
-        for name, _ in L.Atmosphere._fields_:
-            v = getattr(self, name)
-            if isinstance(v, (tuple, list)):
-                for i in range(3):
-                    getattr(c, name)[i] = v[i]
-            else:
-                setattr(c, name, float(v))
-        return c
-
 
 def _lut(size, device) -> torch.Tensor:
     return torch.zeros(tuple(int(n) for n in size) + (4,), dtype=torch.int16, device=device)
 
 
 @dataclass
-class SkyLutContext:
+class SkyLutContext(Marshalled):
     """oxc_sky_lut_context: the constructor-time pair of the reference (RendererInstance.cpp:136-251).  `create` takes the Atmosphere record and
     the caller's 64 hemisphere directions (float32 [64, 3]) and allocates the two LUTs, int16 [H, W, 4] of binary16 bits."""
+    _ctype = L.SkyLutContext
+    _leave = ("_pad",)
     atmosphere: Atmosphere
     hemisphere_directions: torch.Tensor  # in: float32 [64, 3]
     sky_transmittance_lut: torch.Tensor  # out
@@ -832,21 +646,16 @@ class SkyLutContext:
         t, m = atmosphere.transmittance_lut_size, atmosphere.multiscattering_lut_size
         return SkyLutContext(atmosphere, hemisphere_directions, _lut((t[1], t[0]), dev), _lut((m[1], m[0]), dev))
 
-    def c(self) -> L.SkyLutContext:
-        c = L.SkyLutContext()
-        c.struct_size = C.sizeof(L.SkyLutContext)
-        c.atmosphere = self.atmosphere.c()
-        c.hemisphere_directions = _buf(self.hemisphere_directions)
-        c.sky_transmittance_lut = _buf(self.sky_transmittance_lut)
-        c.sky_multiscatter_lut = _buf(self.sky_multiscatter_lut)
-        return c
-
 
 @dataclass
-class AtmosphereContext:
+class AtmosphereContext(Marshalled):
     """oxc_atmosphere_context: RendererInstance::draw_atmosphere (Passes/PBR.cpp:9-141) without its sky_ibl pass, so without the reference's
     sky_cubemap_attachment.  `create` lays out the four buffers from an Atmosphere; generate_sky_luts fills the first two through
     `sky_luts(hemisphere_directions)`."""
+    _ctype = L.AtmosphereContext
+    _derived = {"sky_transmittance_lut": "sky_transmittance_lut_attachment", "sky_multiscatter_lut": "sky_multiscatter_lut_attachment",
+                "sky_view_lut": "sky_view_lut_attachment", "sky_aerial_perspective_lut": "sky_aerial_perspective_lut_attachment"}
+    _leave = ("_pad", "_pad1")
     atmosphere: Atmosphere
     sky_transmittance_lut_attachment: torch.Tensor       # in
     sky_multiscatter_lut_attachment: torch.Tensor        # in
@@ -867,27 +676,14 @@ class AtmosphereContext:
     def sky_luts(self, hemisphere_directions: torch.Tensor) -> SkyLutContext:
         return SkyLutContext(self.atmosphere, hemisphere_directions, self.sky_transmittance_lut_attachment, self.sky_multiscatter_lut_attachment)
 
-    def c(self) -> L.AtmosphereContext:
-        c = L.AtmosphereContext()
-        c.struct_size = C.sizeof(L.AtmosphereContext)
-        c.atmosphere = self.atmosphere.c()
-        for i in range(3):
-            c.sun_dir[i], c.camera_position[i] = float(self.sun_dir[i]), float(self.camera_position[i])
-        c.sun_intensity = float(self.sun_intensity)
-        for i in range(16):
-            c.camera_inv_projection_view[i] = float(self.camera_inv_projection_view[i])
-        c.sky_transmittance_lut = _buf(self.sky_transmittance_lut_attachment)
-        c.sky_multiscatter_lut = _buf(self.sky_multiscatter_lut_attachment)
-        c.sky_view_lut = _buf(self.sky_view_lut_attachment)
-        c.sky_aerial_perspective_lut = _buf(self.sky_aerial_perspective_lut_attachment)
-        return c
-
 
 @dataclass
-class VisbufferDecodeContext:
+class VisbufferDecodeContext(Marshalled):
     """oxc_decode_context: RendererInstance::decode_visbuffer (Passes/DrawGeometry.cpp:192-274), the geometry and material-factor half of
     visbuffer_decode.slang.  `create` takes the visbuffer and the depth as oxc_draw_visbuffer resolved them, the matrix they were drawn with and
     the materials, and allocates the four G-buffer images; the scene buffers come from the renderer's prepared_frame."""
+    _ctype = L.DecodeContext
+    _derived = {"width": "depth_attachment.width", "height": "depth_attachment.height"}
     visbuffer_attachment: torch.Tensor            # int32 [H, W]
     depth_attachment: ImageAttachment             # R32F, levels = 1
     projection_view: list                         # column-major float[16]
@@ -911,29 +707,33 @@ class VisbufferDecodeContext:
         return VisbufferDecodeContext(visbuffer, d, [float(x) for x in projection_view], int(meshlet_instance_count), materials, count, z32(),
                                       torch.zeros((d.height, d.width, 4), dtype=torch.int16, device=dev), z32(), z32(), bool(clear))
 
-    def c(self) -> L.DecodeContext:
-        c = L.DecodeContext()
-        c.struct_size = C.sizeof(L.DecodeContext)
-        c.width, c.height = self.depth_attachment.width, self.depth_attachment.height
-        c.clear = int(bool(self.clear))
-        c.meshlet_instance_count, c.material_count = int(self.meshlet_instance_count), int(self.material_count)
-        for i in range(16):
-            c.projection_view[i] = float(self.projection_view[i])
-        c.visbuffer_attachment = _buf(self.visbuffer_attachment)
-        c.depth_attachment = self.depth_attachment.c()
-        c.materials_buffer = _buf(self.materials_buffer)
-        c.albedo_attachment = _buf(self.albedo_attachment)
-        c.normal_attachment = _buf(self.normal_attachment)
-        c.emissive_attachment = _buf(self.emissive_attachment)
-        c.metallic_roughness_occlusion_attachment = _buf(self.metallic_roughness_occlusion_attachment)
-        return c
-
 
 @dataclass
-class MainGeometryContext:
+class MainGeometryContext(Marshalled):
     """The fields generate_hiz uses (RendererInstance.hpp:199-216)."""
+    _ctype = L.MainGeometryContext
+    _leave = ("_pad",)
     depth_attachment: ImageAttachment
     hiz_attachment: ImageAttachment
+
+
+# the oxc_debug_*_stats read-backs: RendererInstance.debug_<key>_stats -> (symbol, the u32 counters in the library's order)
+_STATS = {
+    "raster": ("oxc_debug_raster_stats", ("big", "clipped", "tiles", "overflowed_segments")),
+    "visbuffer_decode": ("oxc_debug_visbuffer_decode_stats", ("decoded", "empty", "zero_vertex_index", "default_material")),
+    "vsm_draw": ("oxc_debug_vsm_draw_stats", ("pairs", "fragments", "big_pairs", "big_pairs_overflowed", "tiles", "tiles_overflowed", "clipped_pairs",
+                                              "clipped_pairs_overflowed")),
+    "vsm_resolve": ("oxc_debug_vsm_resolve_stats", ("non_sky_pixels", "taps", "misses", "fallback_minus", "fallback_plus", "hard", "no_blocker",
+                                                    "all_blockers")),
+    "contact_shadows": ("oxc_debug_contact_shadows_stats", ("non_sky_pixels", "taps", "miss", "hit_zero", "hit_partial", "hit_one", "rejected", "n_lower",
+                                                            "n_between", "n_upper", "end_clip", "start_moved")),
+    "ambient_occlusion": ("oxc_debug_ambient_occlusion_stats", ("non_sky_pixels", "samples", "mip0", "mip1", "mip2", "mip3", "mip4", "fractional",
+                                                                "result_one", "result_partial", "result_zero", "zero_width", "sign_minus", "sign_zero",
+                                                                "sign_plus")),
+    "pbr_apply": ("oxc_debug_pbr_apply_stats", ("transparent_empty", "sky", "fallthrough_empty", "lit_nol_positive", "lit_nol_zero", "light_kind_skipped",
+                                                "light_attenuation_out", "light_ndotl_out", "light_shaded")),
+    "fxaa": ("oxc_debug_fxaa_stats", ("early_out", "searched", "search_taps", "ran_all_steps")),
+}
 
 
 class RendererInstance:
@@ -973,12 +773,19 @@ class RendererInstance:
     def reserve(self, max_mesh_instances: int, max_meshlet_instances: int):
         self._check(self._lib.oxc_reserve(self._ctx, max_mesh_instances, max_meshlet_instances))
 
+    def _call(self, symbol: str, context, stream, *, frame: bool = False, c=None):
+        """One pass over its context: oxc_<pass>(ctx, [prepared frame,] context, stream).  The context stays referenced in `_keep`, so its
+        tensors outlive the launches the call enqueued."""
+        args = [self._ctx]
+        if frame:
+            assert self.prepared_frame is not None
+            args.append(C.byref(self.prepared_frame.c()))
+        args.append(C.byref(context.c() if c is None else c))
+        self._keep = context
+        self._check(getattr(self._lib, symbol)(*args, self._stream(stream)))
+
     def generate_hiz(self, context: MainGeometryContext, stream=None):
-        c = L.MainGeometryContext()
-        c.struct_size = C.sizeof(L.MainGeometryContext)
-        c.depth_attachment = context.depth_attachment.c()
-        c.hiz_attachment = context.hiz_attachment.c()
-        self._check(self._lib.oxc_generate_hiz(self._ctx, C.byref(c), self._stream(stream)))
+        self._check(self._lib.oxc_generate_hiz(self._ctx, C.byref(context.c()), self._stream(stream)))
 
     def cull_geometry(self, context: CullGeometryContext, stream=None):
         assert self.prepared_frame is not None
@@ -1072,9 +879,7 @@ class RendererInstance:
     def update_virtual_shadowmap(self, context: VirtualShadowmapContext, stream=None):
         """Shadowmaps.cpp:143-421: sun_moved clear, reset, invalidate, mark, free, free list, allocate, HPB, mark dirty, clear dirty
         pages (include/oxcull.h, oxc_update_virtual_shadowmap)."""
-        c = context.c()
-        self._keep = context
-        self._check(self._lib.oxc_update_virtual_shadowmap(self._ctx, C.byref(c), self._stream(stream)))
+        self._call("oxc_update_virtual_shadowmap", context, stream)
 
     def cull_terrain(self, cull_flags: int, cull_camera, world_min, world_size, patch_count, base_height: float, height_scale: float,
                      patch_minmax: torch.Tensor, mask: torch.Tensor, hiz: "ImageAttachment" = None, stream=None):
@@ -1133,61 +938,43 @@ class RendererInstance:
         """Passes/DrawGeometry.cpp:192-274 (visbuffer_decode): per pixel the triangle behind the visbuffer texel, its perspective-correct
         barycentrics, the interpolated vertex normal and the material factors, into the four G-buffer images of `context`
         (include/oxcull.h, oxc_decode_visbuffer)."""
-        assert self.prepared_frame is not None
-        f = self.prepared_frame.c()
-        c = context.c()
-        self._keep = context
-        self._check(self._lib.oxc_decode_visbuffer(self._ctx, C.byref(f), C.byref(c), self._stream(stream)))
+        self._call("oxc_decode_visbuffer", context, stream, frame=True)
 
     def debug_visbuffer_decode_stats(self, stream=None) -> dict:
         """What the last decode_visbuffer did, after debug_set_tuning(L.TUNE_VISBUFFER_DECODE_STATS, 1) (measurement hook; synchronises)."""
-        return self._read_stats(self._lib.oxc_debug_visbuffer_decode_stats, stream, ("decoded", "empty", "zero_vertex_index", "default_material"))
+        return self._read_stats("visbuffer_decode", stream)
 
     def draw_physical_pages(self, context: VsmDrawContext, stream=None):
         """Shadowmaps.cpp:466-754 (rmvsm_build_draw_commands + rmvsm_draw_physical_pages): rasterise the shadow cull's triangles once per
         dirty clipmap into the dirty physical pages of `context.physical_page_image` (include/oxcull.h, oxc_draw_physical_pages)."""
-        assert self.prepared_frame is not None
-        f = self.prepared_frame.c()
-        c = context.c()
-        self._keep = context
-        self._check(self._lib.oxc_draw_physical_pages(self._ctx, C.byref(f), C.byref(c), self._stream(stream)))
+        self._call("oxc_draw_physical_pages", context, stream, frame=True)
 
     def resolve_shadowmap(self, context: ShadowResolveContext, stream=None):
         """Shadowmaps.cpp:756-822 (resolve_shadowmaps): the PCSS light-visibility value of every pixel from the page table and the physical
         pages into `context.resolved_shadows_attachment` (include/oxcull.h, oxc_resolve_shadowmap)."""
-        c = context.c()
-        self._keep = context
-        self._check(self._lib.oxc_resolve_shadowmap(self._ctx, C.byref(c), self._stream(stream)))
+        self._call("oxc_resolve_shadowmap", context, stream)
 
     def apply_pbr(self, context: PBRContext, stream=None):
         """Passes/PBR.cpp:313-534, the no-atmosphere branch (pbr_apply_no_atmos): per pixel the G-buffer, the ambient occlusion, the two shadow
         terms, the sun and the point / spot lights become the lit HDR colour in `context.final_attachment` (include/oxcull.h, oxc_apply_pbr)."""
-        c = context.c()
-        self._keep = context
-        self._check(self._lib.oxc_apply_pbr(self._ctx, C.byref(c), self._stream(stream)))
+        self._call("oxc_apply_pbr", context, stream)
 
     def apply_eye_adaptation(self, context: EyeAdaptationContext, delta_time: float = 0.0, stream=None):
         """Passes/PostProcess.cpp:7-77: the 256-bin log-luminance histogram of `context.final_attachment` into `context.histogram_buffer` and
         the adapted luminance and exposure it gives into `context.exposure_buffer` (include/oxcull.h, oxc_apply_eye_adaptation).  time_coeff
         is `context.time_coeff` where set, else 1 - exp(-adaptation_speed * delta_time)."""
-        c = context.c(delta_time)
-        self._keep = context
-        self._check(self._lib.oxc_apply_eye_adaptation(self._ctx, C.byref(c), self._stream(stream)))
+        self._call("oxc_apply_eye_adaptation", context, stream, c=context.c(delta_time))
 
     def apply_bloom(self, context: BloomContext, stream=None):
         """Passes/PostProcess.cpp:79-203: the thresholded half-resolution image and its downsample pyramid into
         `context.bloom_downsampled_attachment`, the upsample pyramid into `context.bloom_upsampled_attachment` (include/oxcull.h,
         oxc_apply_bloom).  The exposure is the second word of `context.exposure_buffer` with L.SCENE_HAS_EYE_ADAPTATION, else 1."""
-        c = context.c()
-        self._keep = context
-        self._check(self._lib.oxc_apply_bloom(self._ctx, C.byref(c), self._stream(stream)))
+        self._call("oxc_apply_bloom", context, stream)
 
     def apply_tonemap(self, context: TonemapContext, stream=None):
         """Passes/PostProcess.cpp:205-247: exposure, bloom composite, tone curve, lens effects and the 8-bit store of `context.final_attachment`
         into `context.dst_attachment`, one launch (include/oxcull.h, oxc_apply_tonemap)."""
-        c = context.c()
-        self._keep = context
-        self._check(self._lib.oxc_apply_tonemap(self._ctx, C.byref(c), self._stream(stream)))
+        self._call("oxc_apply_tonemap", context, stream)
 
     def apply_fxaa(self, context: FxaaContext, scene_flags: int = L.SCENE_HAS_FXAA, stream=None) -> torch.Tensor:
         """RendererInstance.cpp:1225-1255: with L.SCENE_HAS_FXAA in `scene_flags`, edge anti-aliasing of `context.final_attachment` into
@@ -1195,81 +982,65 @@ class RendererInstance:
         adaptation, the bloom and the tonemap read: fxaa_attachment when the pass ran, final_attachment otherwise, as the reference hands it on."""
         if not int(scene_flags) & L.SCENE_HAS_FXAA:
             return context.final_attachment
-        c = context.c()
-        self._keep = context
-        self._check(self._lib.oxc_apply_fxaa(self._ctx, C.byref(c), self._stream(stream)))
+        self._call("oxc_apply_fxaa", context, stream)
         return context.fxaa_attachment
 
     def generate_sky_luts(self, context: SkyLutContext, stream=None) -> None:
         """RendererInstance.cpp:136-251, the pair the reference builds in its constructor: sky_transmittance_lut, then sky_multiscatter_lut from
         it, two launches (include/oxcull.h, oxc_generate_sky_luts).  Called again whenever the Atmosphere record changes."""
-        c = context.c()
-        self._check(self._lib.oxc_generate_sky_luts(self._ctx, C.byref(c), self._stream(stream)))
+        self._call("oxc_generate_sky_luts", context, stream)
 
     def draw_atmosphere(self, context: AtmosphereContext, stream=None) -> None:
         """Passes/PBR.cpp:9-141 without the sky_ibl pass: sky_view_lut and sky_aerial_perspective_lut from the two LUTs of generate_sky_luts, the
         sun and the camera, two launches (include/oxcull.h, oxc_draw_atmosphere)."""
-        c = context.c()
-        self._check(self._lib.oxc_draw_atmosphere(self._ctx, C.byref(c), self._stream(stream)))
+        self._call("oxc_draw_atmosphere", context, stream)
 
     def debug_fxaa_stats(self, stream=None) -> dict:
         """What the last apply_fxaa did, after debug_set_tuning(L.TUNE_FXAA_STATS, 1) (measurement hook; synchronises)."""
-        return self._read_stats(self._lib.oxc_debug_fxaa_stats, stream, ("early_out", "searched", "search_taps", "ran_all_steps"))
+        return self._read_stats("fxaa", stream)
 
     def debug_pbr_apply_stats(self, stream=None) -> dict:
         """What the last apply_pbr did, after debug_set_tuning(L.TUNE_PBR_APPLY_STATS, 1) (measurement hook; synchronises)."""
-        return self._read_stats(self._lib.oxc_debug_pbr_apply_stats, stream,
-                                ("transparent_empty", "sky", "fallthrough_empty", "lit_nol_positive", "lit_nol_zero", "light_kind_skipped",
-                                 "light_attenuation_out", "light_ndotl_out", "light_shaded"))
+        return self._read_stats("pbr_apply", stream)
 
-    def _read_stats(self, fn, stream, names) -> dict:
-        """One of the oxc_debug_*_stats read-backs: len(names) u32 counters under their names."""
+    def _read_stats(self, key: str, stream) -> dict:
+        """One of the oxc_debug_*_stats read-backs (_STATS): its u32 counters under their names."""
+        symbol, names = _STATS[key]
         out = (C.c_uint32 * len(names))()
-        self._check(fn(self._ctx, C.cast(out, C.c_void_p), self._stream(stream)))
+        self._check(getattr(self._lib, symbol)(self._ctx, C.cast(out, C.c_void_p), self._stream(stream)))
         return {k: int(v) for k, v in zip(names, out)}
 
     def debug_vsm_resolve_stats(self, stream=None) -> dict:
         """What the last resolve_shadowmap did, after debug_set_tuning(L.TUNE_VSM_RESOLVE_STATS, 1) (measurement hook; synchronises)."""
-        return self._read_stats(self._lib.oxc_debug_vsm_resolve_stats, stream,
-                                ("non_sky_pixels", "taps", "misses", "fallback_minus", "fallback_plus", "hard", "no_blocker", "all_blockers"))
+        return self._read_stats("vsm_resolve", stream)
 
     def contact_shadows(self, context: ContactShadowsContext, stream=None):
         """RendererInstance.cpp:990-1020 (contact_shadows): per pixel a short ray towards the sun marched through the depth image, the
         shadow term into `context.contact_shadows_attachment` (include/oxcull.h, oxc_contact_shadows)."""
-        c = context.c()
-        self._keep = context
-        self._check(self._lib.oxc_contact_shadows(self._ctx, C.byref(c), self._stream(stream)))
+        self._call("oxc_contact_shadows", context, stream)
 
     def debug_contact_shadows_stats(self, stream=None) -> dict:
         """What the last contact_shadows did, after debug_set_tuning(L.TUNE_CONTACT_SHADOWS_STATS, 1) (measurement hook; synchronises)."""
-        return self._read_stats(self._lib.oxc_debug_contact_shadows_stats, stream,
-                                ("non_sky_pixels", "taps", "miss", "hit_zero", "hit_partial", "hit_one", "rejected", "n_lower", "n_between", "n_upper",
-                                 "end_clip", "start_moved"))
+        return self._read_stats("contact_shadows", stream)
 
     def generate_ambient_occlusion(self, context: AmbientOcclusionContext, stream=None):
         """Passes/PBR.cpp:179-311 (vbgtao_prefilter, vbgtao_main, vbgtao_denoise): the ambient occlusion term pbr_apply reads, into
         `context.ambient_occlusion_attachment` as binary16 (include/oxcull.h, oxc_generate_ambient_occlusion)."""
-        c = context.c()
-        self._keep = context
-        self._check(self._lib.oxc_generate_ambient_occlusion(self._ctx, C.byref(c), self._stream(stream)))
+        self._call("oxc_generate_ambient_occlusion", context, stream)
 
     def debug_ambient_occlusion_stats(self, stream=None) -> dict:
         """What the last generate_ambient_occlusion did, after debug_set_tuning(L.TUNE_AMBIENT_OCCLUSION_STATS, 1) (measurement hook;
         synchronises)."""
-        return self._read_stats(self._lib.oxc_debug_ambient_occlusion_stats, stream,
-                                ("non_sky_pixels", "samples", "mip0", "mip1", "mip2", "mip3", "mip4", "fractional", "result_one", "result_partial",
-                                 "result_zero", "zero_width", "sign_minus", "sign_zero", "sign_plus"))
+        return self._read_stats("ambient_occlusion", stream)
 
     def debug_vsm_draw_stats(self, stream=None) -> dict:
         """What the last draw_physical_pages did (measurement hook; synchronises).  `pairs` / `fragments` are counted only with
         debug_set_tuning(L.TUNE_VSM_DRAW_STATS, 1)."""
-        return self._read_stats(self._lib.oxc_debug_vsm_draw_stats, stream,
-                                ("pairs", "fragments", "big_pairs", "big_pairs_overflowed", "tiles", "tiles_overflowed", "clipped_pairs",
-                                 "clipped_pairs_overflowed"))
+        return self._read_stats("vsm_draw", stream)
 
     def debug_raster_stats(self, stream=None) -> dict:
         """What the last draw_visbuffer did with its triangles (test hook; synchronises)."""
-        return self._read_stats(self._lib.oxc_debug_raster_stats, stream, ("big", "clipped", "tiles", "overflowed_segments"))
+        return self._read_stats("raster", stream)
 
     def debug_set_tuning(self, knob: int, value: int):
         """Harness knobs (L.TUNE_*): async stage grid caps, the raster queues' capacity (before the first draw)."""

@@ -51,19 +51,40 @@ def test_struct_sizes_match_reference_layouts():
 
 
 def test_context_struct_matches_the_header(tmp_path):
-    """sizeof / offsetof of the ctypes mirror == what a C compiler makes of include/oxcull.h."""
+    """sizeof and every offsetof of every ctypes mirror in lib.py == what a C compiler makes of the headers.  A mirror names its C type in
+    `_c_name_`; the headers' structures and the mirrors are the same set."""
     import subprocess
 
+    mirrors = [c for c in vars(L).values() if isinstance(c, type) and issubclass(c, ctypes.Structure) and c is not ctypes.Structure]
+    untagged = [c.__name__ for c in mirrors if "_c_name_" not in vars(c)]
+    assert not untagged, f"ctypes mirrors without a _c_name_: {untagged}"
+    text = "".join(open(os.path.join(ROOT, "include", h)).read() for h in ("oxcull.h", "oxcull_debug.h"))
+    assert sorted(c._c_name_ for c in mirrors) == sorted(re.findall(r"typedef struct (oxc_\w+)\s*\{", text))
+
+    # one line per value, keyed S <type> / O <type> <field>: oxc_mesh_blob_layout has a field called `size`
+    lines = []
+    for c in mirrors:
+        lines.append(f'printf("S {c._c_name_} %zu\\n", sizeof({c._c_name_}));')
+        lines += [f'printf("O {c._c_name_} {f[0]} %zu\\n", offsetof({c._c_name_}, {f[0]}));' for f in c._fields_]
     src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "oxcull_debug.h"\nint main(void) { printf("%zu %zu %zu %zu\\n", sizeof(oxc_cull_geometry_context), '
-                   'offsetof(oxc_cull_geometry_context, small_triangle_cull), offsetof(oxc_cull_geometry_context, visibility_buffer), sizeof(oxc_kernel_times)); return 0; }\n')
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "oxcull_debug.h"\nint main(void) {\n' + "\n".join(lines) + "\nreturn 0; }\n")
     exe = str(tmp_path / "sz")
     subprocess.check_call(["gcc", "-std=c99", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe])
-    size, off_small, off_vis, kt = [int(x) for x in subprocess.check_output([exe]).split()]
-    assert size == ctypes.sizeof(L.CullGeometryContext)
-    assert off_small == L.CullGeometryContext.small_triangle_cull.offset
-    assert off_vis == L.CullGeometryContext.visibility_buffer.offset
-    assert kt == ctypes.sizeof(L.KernelTimes)
+    want = {}
+    for line in subprocess.check_output([exe]).decode().splitlines():
+        *key, value = line.split()
+        want[tuple(key)] = int(value)
+    got = {}
+    for c in mirrors:
+        got[("S", c._c_name_)] = ctypes.sizeof(c)
+        got.update({("O", c._c_name_, f[0]): getattr(c, f[0]).offset for f in c._fields_})
+    assert len(got) == len(lines) == len(want)
+    wrong = {k: (got[k], want[k]) for k in got if got[k] != want[k]}
+    assert not wrong, f"(ctypes, C) differ: {wrong}"
+    assert want[("S", "oxc_cull_geometry_context")] == ctypes.sizeof(L.CullGeometryContext)
+    assert want[("O", "oxc_cull_geometry_context", "small_triangle_cull")] == L.CullGeometryContext.small_triangle_cull.offset
+    assert want[("O", "oxc_cull_geometry_context", "visibility_buffer")] == L.CullGeometryContext.visibility_buffer.offset
+    assert want[("S", "oxc_kernel_times")] == ctypes.sizeof(L.KernelTimes)
 
 
 def test_product_path_never_imports_the_oracle():
