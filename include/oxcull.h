@@ -1482,10 +1482,10 @@ oxc_status oxc_apply_fxaa(oxc_ctx* ctx, const oxc_fxaa_context* context, void* h
  * oxc_generate_sky_luts replaces the pair the reference builds once in the RendererInstance constructor (RendererInstance.cpp:136-251:
  * pipelines sky_transmittance and sky_multiscatter; passes/sky_transmittance.slang, passes/sky_multiscattering.slang); an engine calls it
  * again whenever the Atmosphere record changes.  oxc_draw_atmosphere replaces RendererInstance::draw_atmosphere (Passes/PBR.cpp:9-141)
- * without its middle sky_ibl pass: pipelines sky_view and sky_aerial_perspective.  All four passes go through sky.slang, bound with
- * LinearSamplerClamped.
- * Out of scope, the two follow-ups: the sky_ibl cubemap (passes/sky_ibl.slang) and the atmosphere branch of pbr_apply.slang, the consumer
- * of these LUTs -- oxc_apply_pbr still refuses OXC_SCENE_HAS_ATMOSPHERE.
+ * without its middle sky_ibl pass, which is oxc_generate_sky_ibl below: pipelines sky_view and sky_aerial_perspective.  All four passes go
+ * through sky.slang, bound with LinearSamplerClamped.
+ * Out of scope, the follow-up: the atmosphere branch of pbr_apply.slang, the consumer of these LUTs and of the sky cubemap --
+ * oxc_apply_pbr still refuses OXC_SCENE_HAS_ATMOSPHERE.
  * Images: all four are R16G16B16A16 Sfloat, here linear u16x4 buffers of binary16 bits like the normal image, row-major; the 3-D LUT is
  * [depth][height][width].  A store is the binary16 conversion of oxc_apply_pbr step 12 per channel (a NaN stored as 0x7E00).  A
  * SampleLevel(LinearSamplerClamped, uv, 0).rgb is the manual bilinear of the oxc_apply_bloom block in clamp mode on the decoded halves
@@ -1612,6 +1612,87 @@ typedef struct oxc_atmosphere_context {
 
 oxc_status oxc_generate_sky_luts(oxc_ctx* ctx, const oxc_sky_lut_context* context, void* hip_stream);
 oxc_status oxc_draw_atmosphere(oxc_ctx* ctx, const oxc_atmosphere_context* context, void* hip_stream);
+
+/* ---- the sky cubemap of the atmosphere path ---------------------------------------------------------------------------------------------
+ * oxc_generate_sky_ibl is the middle pass of RendererInstance::draw_atmosphere (Passes/PBR.cpp:52-94, passes/sky_ibl.slang): from the
+ * sky-view LUT oxc_draw_atmosphere wrote and the transmittance LUT it writes sky_cubemap, the image pbr_apply.slang samples for the ambient
+ * term.  With it the reference's draw_atmosphere is oxc_draw_atmosphere, then this call (three with oxc_generate_sky_luts, which the
+ * reference runs at construction); the aerial LUT and the cube do not read each other.  Out of scope, the follow-up: the atmosphere branch of pbr_apply.slang -- oxc_apply_pbr still refuses
+ * OXC_SCENE_HAS_ATMOSPHERE.
+ * Images: the cube is R16G16B16A16 Sfloat, here a linear u16x4 buffer [6][cube_size][cube_size] like the LUTs; face f is the Slang's
+ * thread_id.z, texel (x, y) of it thread_id.xy.  The cube is read and written: a texel is its own history.  The reference clears it to
+ * black once, in the constructor (RendererInstance.cpp:187-201); here the caller zeroes the buffer once and the call never clears it.
+ * frame_index (render_context->num_frames) travels by value, like the sun of oxc_draw_atmosphere: a captured graph replays the index it
+ * was captured with -- every replay still accumulates into the cube, which is memory, but with the sample rotation of that one index; an
+ * engine that wants the rotation to advance captures again or updates the node's arguments.
+ * Arithmetic and shared rules: those of the block above (steps 1 - 10): intersect (1), the clamp bilinear SampleLevel (here .rgba: the
+ * alpha is interpolated like a colour channel), the transmittance sample of 3, the binary16 store, the exact half decode, dot, length,
+ * normalize, the cos rule.  cross(a, b) = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x), each product rounded before the
+ * subtraction; a 2-D dot is a.x b.x + a.y b.y; frac(x) = x - floor(x); lerp(a, b, t) = a + (b - a) * t; f32(u32) rounds to nearest even;
+ * every decimal literal (0.61803398875, 2.3283064365386963e-10, 0.06711056, 0.00583715, 52.9829189, 0.999, 1e-5, 1e-20, 0.02, 37.0, 17.0)
+ * is the binary32 nearest to it.  sanitize(v) is 0 for each non-finite component.
+ * Host constants: eye_altitude, horizon, beta and zenith_horizon_angle, the ones of oxc_draw_atmosphere, from camera_position.y; H.
+ *  11. closed forms  A(y, x), the atan2 of two binary64: ax = |x|, ay = |y|, a = min(ax, ay) / max(ax, ay);  a > 0x1.a827999fcef32p-2
+ *              (sqrt(2) - 1): t = (a - 1) / (a + 1), else t = a;  z = t * t;  p = 1/39, then p = c - p * z for c = 1/37, 1/35, .. 1/3, 1 (the
+ *              binary64 quotients; 20 terms);  r = t * p;  reduced: r = pi/4 + r;  ay > ax: r = pi/2 - r;  x < 0: r = pi - r;  y < 0: r = -r
+ *              (a negative zero counts as positive in both tests);  max(ax, ay) == 0: r = 0;  a NaN argument gives NaN, as do two infinite
+ *              ones (Inf / Inf).  pi = 0x1.921fb54442d18p+1 and its exact half and quarter.  All of it in binary64 without contraction.
+ *              atan2(y, x) = (float)A((double)y, (double)x).  acos(x) = (float)A(sqrt(1 - xd * xd), xd) with xd = (double)x -- xd * xd is
+ *              exact -- and NaN for a NaN and for |x| > 1;  acos(1) = 0, acos(-1) = (float)pi, acos(0) = (float)(pi/2).  The binary64 value
+ *              is within 10 roundings of 2^-53 each (1.2e-15 relative) of the true one, so the result is the correctly rounded binary32 or, where the true value lies that
+ *              close to a rounding boundary, its neighbour: at most 1 ulp from the correctly rounded value.
+ *              sin(a): the turn t of the cos rule (u = (double)|a| / (2 pi), t = (float)(u - floor(u)), t == 1 becomes 0), the sine of that
+ *              turn by the rotation rule of oxc_resolve_shadowmap, negated for a < 0;  NaN for a non-finite a.
+ *              rsqrt(x) = 1.0f / sqrt(x) in binary32.
+ *  12. texel frame  uv = (f32(pixel) + 0.5f) / f32(cube_size);  v = (uv.x * 2.0f - 1.0f, uv.y * 2.0f - 1.0f, -1.0f);  M =
+ *              CUBE_MAP_FACE_ROTATION(face), whose nine scalars fill M ROW by row in the constructor's order (row r = scalars 3 r .. 3 r + 2)
+ *              and mul(M, v).r = (M[r][0] v.x + M[r][1] v.y) + M[r][2] v.z, every product formed even where the scalar is 0 or 1: at
+ *              cube_size 1 faces 0 .. 5 look along +X, -X, +Y, -Y, +Z, -Z (the transposed convention would swap faces 2 and 3).
+ *              output_dir = normalize(mul(M, v));  eye_pos = (0, eye_altitude, 0);  up = |output_dir.y| < 0.999f ? (0, 1, 0) : (1, 0, 0);
+ *              tangent = normalize(cross(up, output_dir)), bitangent = cross(output_dir, tangent).  history = the decoded texel;
+ *              has_history = history.a > 0 and the three colours finite: a positive denormal alpha is history, -0, a NaN and negatives
+ *              are not.  p = (f32(x) + f32(face) * 37.0f, f32(y) + f32(face) * 17.0f), base_rotation = frac(52.9829189f * frac(p.x *
+ *              0.06711056f + p.y * 0.00583715f));  rotation = has_history ? frac(base_rotation + f32(frame_index) * 0.61803398875f) :
+ *              base_rotation.
+ *  13. sample i of 0 .. 63:  u1 = (f32(i) + 0.5f) / 64.0f;  radical_inverse_vdc(i) = f32(the 32-bit reversal of i) *
+ *              2.3283064365386963e-10f;  u2 = frac(that + rotation);  r = sqrt(u1), phi = TAU * u2;  local = (r * cos(phi), r * sin(phi),
+ *              sqrt(max(0, 1.0f - u1)));  input_dir = normalize((local.x * tangent + local.y * bitangent) + local.z * output_dir).
+ *  14. illuminance along input_dir (get_atmosphere_illuminance_along_ray, sky.slang:296-322, as written, whatever it simplifies to):
+ *              height = length(eye_pos), up_vec = eye_pos / height, c = dot(input_dir, up_vec);  side_raw = cross(up_vec, input_dir), side
+ *              = length(side_raw) > 1e-5f ? normalize(side_raw) : (1, 0, 0);  forward = normalize(cross(side, up_vec));  sun =
+ *              normalize(sun_dir);  l = (dot(sun, forward), dot(sun, side)), len_sq = dot(l, l), light_on_plane = len_sq > 1e-20f ? l *
+ *              rsqrt(len_sq) : (1, 0) -- the comparison is false for a NaN;  hit = intersect(eye_pos, input_dir, planet_radius) has a value.
+ *              sky_view_params_to_lut_uv (sky.slang:39-67) with the host constants: angle = acos(c);  no hit: coord = angle /
+ *              zenith_horizon_angle, 1.0f - coord, safe_sqrt, 1.0f - coord, uv.y = coord * 0.5f;  hit: coord = (angle -
+ *              zenith_horizon_angle) / beta, safe_sqrt, uv.y = coord * 0.5f + 0.5f.  theta = atan2(-light_on_plane.y, -light_on_plane.x),
+ *              uv.x = (theta + PI) / (2.0f * PI);  uv = (uv + 0.5f / res) * (res / (res + 1.0f)), res = f32(sky_view_lut_size.xy).  s =
+ *              SampleLevel(sky_view_lut, uv);  the sample is sanitize(s.rgb * s.a) (the Slang sanitizes it a second time in its loop: the
+ *              identity).
+ *  15. the texel   frame_sum adds the 64 samples from 0 in ascending i;  frame_estimate = frame_sum / 64.0f.  sun_cos_zenith = (sun_dir.x
+ *              * 0.0f + sun_dir.y * 1.0f) + sun_dir.z * 0.0f -- sun_dir as given, not normalised;  sun_color = the sample of 3 at
+ *              (eye_pos.y, sun_cos_zenith);  sun_facing = saturate(dot(output_dir, sun_dir));  sun_term = (((sun_ambient_strength *
+ *              sun_color) * sun_intensity) * sun_facing) / PI.  frame_result = clamp(sanitize(frame_estimate + sun_term), 0, HALF_MAX), the
+ *              clamp as two selects after the sanitize: v > 0 ? v : +0, then v < 65504 ? v : 65504.  Stored: (has_history ?
+ *              lerp(history.rgb, frame_result, 0.02f) : frame_result, 1.0).  No stored half is a NaN or an Inf, whatever the arguments.
+ * Limits (else OXC_INVALID_ARG, nothing launched, nothing written; the first broken rule in this order gives the message, each has its
+ * own): struct_size; every side of sky_view_lut_size, then of transmittance_lut_size, in 2 .. 4096; cube_size in 1 .. 1024;
+ * planet_radius and atmos_radius finite, planet_radius > 0, atmos_radius > planet_radius; every buffer, in the order of the context's
+ * fields, non-null, then aligned to 8 bytes, then at least as large as its extent says; the cube shares no byte with either LUT.
+ * One launch; no scratch, no allocation, no host synchronisation; capturable into a HIP graph. */
+typedef struct oxc_sky_ibl_context {
+  uint32_t struct_size; /* sizeof(oxc_sky_ibl_context) */
+  uint32_t _pad;
+  oxc_atmosphere atmosphere;
+  float sun_dir[3], sun_intensity;                /* directional_light.direction, .intensity */
+  float camera_position[3], sun_ambient_strength; /* GPU::Camera::position.xyz; the engine passes 0.15f */
+  uint32_t frame_index;                           /* render_context->num_frames */
+  uint32_t cube_size;                             /* the engine's 32 (IBL_CUBE_RES); 64 samples per texel and call */
+  oxc_buffer sky_view_lut;                        /* in: what oxc_draw_atmosphere wrote */
+  oxc_buffer sky_transmittance_lut;               /* in: what oxc_generate_sky_luts wrote */
+  oxc_buffer sky_cubemap;                         /* in and out: u16x4 [6][cube_size][cube_size]; zeroed once by the caller */
+} oxc_sky_ibl_context;
+
+oxc_status oxc_generate_sky_ibl(oxc_ctx* ctx, const oxc_sky_ibl_context* context, void* hip_stream);
 
 /* ---- multi-GPU exchange: one process per GPU, RCCL over xGMI ---------------------------
  * The meshlet-instance array shards by contiguous range and every rank culls its shard on its own; the only

@@ -46,7 +46,7 @@ oxc_status bloom_pyramid(oxc_ctx* ctx, const char* entry, const oxc_image_pyrami
   return OXC_OK;
 }
 
-// The checks oxc_generate_sky_luts and oxc_draw_atmosphere share, in the order of the header's limits
+// The checks oxc_generate_sky_luts, oxc_draw_atmosphere and oxc_generate_sky_ibl share, in the order of the header's limits
 struct SkyBuffer {
   const oxc_buffer& b;
   uint64_t bytes;
@@ -314,6 +314,38 @@ oxc_status oxc_draw_atmosphere(oxc_ctx* ctx, const oxc_atmosphere_context* c, vo
   a.sky_view = static_cast<uint2*>(c->sky_view_lut.dptr);
   a.aerial = static_cast<uint2*>(c->sky_aerial_perspective_lut.dptr);
   launch_atmosphere(a, s);
+  OXC_HIP(ctx, hipGetLastError());
+  return OXC_OK;
+}
+
+oxc_status oxc_generate_sky_ibl(oxc_ctx* ctx, const oxc_sky_ibl_context* c, void* hip_stream) {
+  if (!ctx) return OXC_INVALID_ARG;
+  if (!c || c->struct_size != sizeof(oxc_sky_ibl_context)) return fail(ctx, OXC_INVALID_ARG, "generate_sky_ibl: bad context / struct_size");
+  const char* const entry = "generate_sky_ibl";
+  const oxc_atmosphere& A = c->atmosphere;
+  if (bad_lut_side(A.sky_view_lut_size)) return bad_arg(ctx, entry, "sky_view_lut_size: every side must be in 2 .. 4096");
+  if (bad_lut_side(A.transmittance_lut_size)) return bad_arg(ctx, entry, "transmittance_lut_size: every side must be in 2 .. 4096");
+  if (c->cube_size < 1u || c->cube_size > 1024u) return bad_arg(ctx, entry, "cube_size must be in 1 .. 1024");
+  OXC_TRY(check_radii(ctx, entry, A));
+  const uint32_t texels = 6u * c->cube_size * c->cube_size;
+  OXC_TRY(check_sky_buffers(ctx, entry, {{c->sky_view_lut, lut_bytes(A.sky_view_lut_size), "sky_view_lut", false},
+                                         {c->sky_transmittance_lut, lut_bytes(A.transmittance_lut_size), "sky_transmittance_lut", false},
+                                         {c->sky_cubemap, (uint64_t)texels * 8u, "sky_cubemap", true}}));
+  OXC_ENTER(ctx, hip_stream, s);
+  SkyIblArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.in.atm = A;
+  atmosphere_constants(A, &c->camera_position[1], a.in.k);
+  a.in.transmittance = static_cast<const uint2*>(c->sky_transmittance_lut.dptr);
+  std::memcpy(a.sun_dir, c->sun_dir, sizeof a.sun_dir);
+  a.sun_intensity = c->sun_intensity;
+  a.sun_ambient_strength = c->sun_ambient_strength;
+  a.frame_index = c->frame_index;
+  a.cube_size = c->cube_size;
+  a.texels = texels;
+  a.sky_view = static_cast<const uint2*>(c->sky_view_lut.dptr);
+  a.cube = static_cast<uint2*>(c->sky_cubemap.dptr);
+  launch_sky_ibl(a, s);
   OXC_HIP(ctx, hipGetLastError());
   return OXC_OK;
 }

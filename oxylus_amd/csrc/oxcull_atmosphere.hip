@@ -12,6 +12,8 @@
 //   k_sky_aerial          a one-wave block holds 64 texels of ONE slice z (2 (z + 1) steps each), so the step count never diverges inside
 //                         a wave; the blocks run from the highest z, the longest, down.  Two launches and not one grid with the sky view:
 //                         the fused kernel spilled four SGPRs.
+//   k_sky_ibl             the sky cubemap of oxc_generate_sky_ibl (passes/sky_ibl.slang): one wave per cube texel, one
+//                         lane per sample, four texels per block; lane 0 adds the 64 samples in ascending order and stores the texel.
 //
 // integrate<> is sky.slang's integrate_single_scattered_luminance, its three constexpr switches template parameters; step<> is the body of
 // its loop.  Every float operation keeps the order and rounding the header states: the file is compiled without contraction, division and
@@ -294,6 +296,61 @@ OXC_DEV void aerial_texel(const AtmosphereArgs& a, uint32_t x, uint32_t y, uint3
   const float third = 1.0f / 3.0f;
   store_half4(a.aerial, at, r.luminance.x, r.luminance.y, r.luminance.z, (r.transmittance.x * third + r.transmittance.y * third) + r.transmittance.z * third);
 }
+// ---- the sky cubemap (passes/sky_ibl.slang; the header's steps 11 - 15) -----------------------------------------------------------------------
+OXC_DEV V3 crossv(const V3& a, const V3& b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+OXC_DEV float frac_f(float x) { return x - floorf(x); }
+OXC_DEV float finite_or_zero(float x) { return __builtin_fabsf(x) < __builtin_inff() ? x : 0.0f; }  // com::sanitize, one component
+
+// SampleLevel(LinearSamplerClamped, uv, 0) with its alpha: sample_rgb's bilinear on all four channels
+OXC_DEV Texel sample_rgba(const uint2* lut, uint32_t w, uint32_t h, float u, float v) {
+  const Axis ax = axis_at<false>(u, (float)w, (int)w - 1), ay = axis_at<false>(v, (float)h, (int)h - 1);
+  const size_t r0 = (size_t)ay.i0 * w, r1 = (size_t)ay.i1 * w;
+  const Texel t00 = load_rgba<1>(lut, r0 + ax.i0), t10 = load_rgba<1>(lut, r0 + ax.i1);
+  const Texel t01 = load_rgba<1>(lut, r1 + ax.i0), t11 = load_rgba<1>(lut, r1 + ax.i1);
+  return {lerp3(lerp3(t00.c, t10.c, ax.f), lerp3(t01.c, t11.c, ax.f), ay.f), lerp_f(lerp_f(t00.a, t10.a, ax.f), lerp_f(t01.a, t11.a, ax.f), ay.f)};
+}
+
+// CUBE_MAP_FACE_ROTATION (sky_ibl.slang:21-30), the nine scalars in the constructor's order: row r is elements 3 r .. 3 r + 2
+__constant__ const float kCubeFace[6][9] = {{+0, +0, -1, +0, -1, +0, -1, +0, +0}, {+0, +0, +1, +0, -1, +0, +1, +0, +0}, {+1, +0, +0, +0, +0, -1, +0, +1, +0},
+                                            {+1, +0, +0, +0, +0, +1, +0, -1, +0}, {+1, +0, +0, +0, -1, +0, +0, +0, -1}, {-1, +0, +0, +0, -1, +0, +0, +0, +1}};
+
+// get_atmosphere_illuminance_along_ray (sky.slang:296-322) with sky_view_params_to_lut_uv (sky.slang:39-67) inside, sanitized
+OXC_DEV V3 sky_illuminance(const SkyIblArgs& a, const V3& eye, const V3& dir) {
+  const oxc_atmosphere& A = a.in.atm;
+  const float height = lengthv(eye);
+  const V3 up = {eye.x / height, eye.y / height, eye.z / height};
+  const float view_zenith_cos_angle = dotv(dir, up);
+  const V3 side_raw = crossv(up, dir);
+  const V3 side = lengthv(side_raw) > 1e-5f ? normalize3(side_raw) : V3{1.0f, 0.0f, 0.0f};
+  const V3 forward = normalize3(crossv(side, up));
+  const V3 sun = normalize3({a.sun_dir[0], a.sun_dir[1], a.sun_dir[2]});
+  float lx = dotv(sun, forward), ly = dotv(sun, side);
+  const float len_sq = lx * lx + ly * ly;
+  const float inv_len = 1.0f / __builtin_sqrtf(len_sq);
+  const bool keep = len_sq > 1e-20f;  // false for a NaN
+  lx = keep ? lx * inv_len : 1.0f;
+  ly = keep ? ly * inv_len : 0.0f;
+  const bool intersect_planet = intersect_nearest(eye, dir, A.planet_radius).has;
+  const float zha = a.in.k.zenith_horizon_angle, beta = a.in.k.beta;
+  const float view_zenith_angle = acos_rule(view_zenith_cos_angle);
+  float uy;
+  if (!intersect_planet) {
+    float coord = view_zenith_angle / zha;
+    coord = 1.0f - coord;
+    coord = safe_sqrt(coord);
+    coord = 1.0f - coord;
+    uy = coord * 0.5f;
+  } else {
+    float coord = (view_zenith_angle - zha) / beta;
+    coord = safe_sqrt(coord);
+    uy = coord * 0.5f + 0.5f;
+  }
+  const float theta = atan2_rule(-ly, -lx);
+  const float ux = (theta + kPi) / (2.0f * kPi);
+  const float fw = (float)A.sky_view_lut_size[0], fh = (float)A.sky_view_lut_size[1];
+  const Texel t = sample_rgba(a.sky_view, A.sky_view_lut_size[0], A.sky_view_lut_size[1], (ux + 0.5f / fw) * (fw / (fw + 1.0f)), (uy + 0.5f / fh) * (fh / (fh + 1.0f)));
+  return {finite_or_zero(t.c.x * t.a), finite_or_zero(t.c.y * t.a), finite_or_zero(t.c.z * t.a)};
+}
 }  // namespace
 
 // sky_transmittance.slang
@@ -379,6 +436,73 @@ __global__ __launch_bounds__(64) void k_sky_aerial(AtmosphereArgs a) {
   if (p < size[0] * size[1]) aerial_texel(a, p % size[0], p / size[0], z);
 }
 
+// sky_ibl.slang: one wave per cube texel, one lane per sample of its 64, four texels per block.  Every lane evaluates the texel's frame
+// (a few dozen operations, the same in all 64 lanes) and its own sample; the three sums go through LDS and lane 0 adds them in ascending
+// sample order, then handles the sun term, the history and the store.
+__global__ __launch_bounds__(256) void k_sky_ibl(SkyIblArgs a) {
+  __shared__ float part[4][3][64];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t p = blockIdx.x * 4u + wave;
+  const bool live = p < a.texels;  // wave-uniform
+  const V3 eye = {0.0f, a.in.k.eye_altitude, 0.0f};
+  V3 output_dir = {0.0f, 0.0f, 0.0f};
+  Texel history = {{0.0f, 0.0f, 0.0f}, 0.0f};
+  bool has_history = false;
+  if (live) {
+    const uint32_t cs = a.cube_size, face = p / (cs * cs), rem = p - face * (cs * cs), x = rem % cs, y = rem / cs;
+    const float fcs = (float)cs;
+    const float u = ((float)x + 0.5f) / fcs, v = ((float)y + 0.5f) / fcs;
+    const V3 in = {u * 2.0f - 1.0f, v * 2.0f - 1.0f, -1.0f};
+    const float* m = kCubeFace[face];
+    output_dir = normalize3({(m[0] * in.x + m[1] * in.y) + m[2] * in.z, (m[3] * in.x + m[4] * in.y) + m[5] * in.z, (m[6] * in.x + m[7] * in.y) + m[8] * in.z});
+    const V3 up = __builtin_fabsf(output_dir.y) < 0.999f ? V3{0.0f, 1.0f, 0.0f} : V3{1.0f, 0.0f, 0.0f};
+    const V3 tangent = normalize3(crossv(up, output_dir));
+    const V3 bitangent = crossv(output_dir, tangent);
+    history = load_rgba<1>(a.cube, p);
+    has_history = history.a > 0.0f && __builtin_fabsf(history.c.x) < __builtin_inff() && __builtin_fabsf(history.c.y) < __builtin_inff() &&
+                  __builtin_fabsf(history.c.z) < __builtin_inff();
+    // interleaved_gradient_noise(f32x2(pixel) + f32(face) * (37, 17))
+    const float px = (float)x + (float)face * 37.0f, py = (float)y + (float)face * 17.0f;
+    const float base_rotation = frac_f(52.9829189f * frac_f(px * 0.06711056f + py * 0.00583715f));
+    const float rotation = has_history ? frac_f(base_rotation + (float)a.frame_index * 0.61803398875f) : base_rotation;
+    // cosine_hemisphere_sample(lane, 64, rotation)
+    const float u1 = ((float)lane + 0.5f) / 64.0f;
+    const float u2 = frac_f((float)__builtin_bitreverse32(lane) * 2.3283064365386963e-10f + rotation);
+    const float r = __builtin_sqrtf(u1), phi = kTau * u2;
+    float cs_phi, sn_phi;
+    cos_sin_angle_rule(phi, cs_phi, sn_phi);
+    const float lx = r * cs_phi, ly = r * sn_phi, lz = __builtin_sqrtf(fmaxf(0.0f, 1.0f - u1));
+    const V3 input_dir = normalize3({(lx * tangent.x + ly * bitangent.x) + lz * output_dir.x, (lx * tangent.y + ly * bitangent.y) + lz * output_dir.y,
+                                     (lx * tangent.z + ly * bitangent.z) + lz * output_dir.z});
+    const V3 sample = sky_illuminance(a, eye, input_dir);
+    part[wave][0][lane] = sample.x, part[wave][1][lane] = sample.y, part[wave][2][lane] = sample.z;
+  }
+  __syncthreads();
+  if (!live || lane != 0u) return;
+  float sum[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll 1
+  for (int i = 0; i < 64; i++) {
+    sum[0] += part[wave][0][i];
+    sum[1] += part[wave][1][i];
+    sum[2] += part[wave][2][i];
+  }
+  const float sun_cos_zenith = (a.sun_dir[0] * 0.0f + a.sun_dir[1] * 1.0f) + a.sun_dir[2] * 0.0f;
+  const V3 sun_color = sun_transmittance_at(a.in, eye.y, sun_cos_zenith);
+  const float sun_facing = saturate_f(dotv(output_dir, {a.sun_dir[0], a.sun_dir[1], a.sun_dir[2]}));
+  const float sc[3] = {sun_color.x, sun_color.y, sun_color.z}, hist[3] = {history.c.x, history.c.y, history.c.z};
+  float out[3];
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    const float frame_estimate = sum[c] / 64.0f;
+    const float sun_term = (((a.sun_ambient_strength * sc[c]) * a.sun_intensity) * sun_facing) / kPi;
+    const float clean = finite_or_zero(frame_estimate + sun_term);
+    const float positive = clean > 0.0f ? clean : 0.0f;  // the clamp as two selects: a negative zero becomes +0
+    const float frame_result = positive < kHalfMax ? positive : kHalfMax;
+    out[c] = has_history ? lerp_f(hist[c], frame_result, 0.02f) : frame_result;
+  }
+  store_half4(a.cube, p, out[0], out[1], out[2], 1.0f);
+}
+
 void launch_sky_luts(const SkyLutArgs& a, hipStream_t s) {
   const oxc_atmosphere& A = a.in.atm;
   hipLaunchKernelGGL(k_sky_transmittance, dim3((A.transmittance_lut_size[0] * A.transmittance_lut_size[1] + 63u) / 64u), dim3(64), 0, s, a);
@@ -391,5 +515,7 @@ void launch_atmosphere(AtmosphereArgs a, hipStream_t s) {
   hipLaunchKernelGGL(k_sky_view, dim3((A.sky_view_lut_size[0] * A.sky_view_lut_size[1] + 63u) / 64u), dim3(64), 0, s, a);
   hipLaunchKernelGGL(k_sky_aerial, dim3(A.aerial_perspective_lut_size[2] * a.slice_blocks), dim3(64), 0, s, a);
 }
+
+void launch_sky_ibl(const SkyIblArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_sky_ibl, dim3((a.texels + 3u) / 4u), dim3(256), 0, s, a); }
 
 }  // namespace oxc

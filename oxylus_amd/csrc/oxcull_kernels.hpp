@@ -743,6 +743,15 @@ struct AtmosphereArgs {
 void atmosphere_constants(const oxc_atmosphere& atm, const float* camera_y, AtmosphereConstants& k);  // camera_y nullptr: the camera terms stay 0
 void launch_sky_luts(const SkyLutArgs& a, hipStream_t s);
 void launch_atmosphere(AtmosphereArgs a, hipStream_t s);
+// the sky cubemap (oxc_generate_sky_ibl); in.multiscatter is not bound
+struct SkyIblArgs {
+  SkyLutInputs in;
+  float sun_dir[3], sun_intensity, sun_ambient_strength;
+  uint32_t frame_index, cube_size, texels;  // texels = 6 * cube_size^2
+  const uint2* sky_view;
+  uint2* cube;  // in and out, [6][cube_size][cube_size]
+};
+void launch_sky_ibl(const SkyIblArgs& a, hipStream_t s);
 // oxcull_bounds.hip: meshlet bounds producer
 void launch_build_meshlet_bounds(const float* pos, uint32_t vertex_count, const void* meshlets, uint32_t meshlet_count, const uint32_t* vidx,
                                  const uint8_t* micro, void* out_bounds, float* out_mesh6, void* out_qpos, float* meshlet_minmax, float* normals,

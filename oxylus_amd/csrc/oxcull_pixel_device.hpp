@@ -248,4 +248,68 @@ OXC_DEV float cos_turn_rule(float a) {
   return aa < __builtin_inff() ? cs : __builtin_nanf("");
 }
 
+// (cos(a), sin(a)) of a binary32 angle in radians (oxc_generate_sky_ibl step 11): the turn of the cos rule above, so cs is cos_turn_rule(a)
+// bit for bit; the sine of that turn, negated for a < 0.  Both NaN for a non-finite a.
+OXC_DEV void cos_sin_angle_rule(float a, float& cs, float& sn) {
+  const float aa = __builtin_fabsf(a);
+  const double u = (double)aa * 0x1.45f306dc9c883p-3;
+  float t = (float)(u - __builtin_floor(u));
+  t = t == 1.0f ? 0.0f : t;
+  t = aa < __builtin_inff() ? t : 0.0f;
+  cos_sin_turn(t, cs, sn);
+  sn = a < 0.0f ? -sn : sn;
+  cs = aa < __builtin_inff() ? cs : __builtin_nanf("");
+  sn = aa < __builtin_inff() ? sn : __builtin_nanf("");
+}
+
+// atan2(y, x) before its rounding (oxc_generate_sky_ibl step 11), binary64 throughout, no contraction: a = min(|x|, |y|) / max(|x|, |y|);
+// a > sqrt(2) - 1 is reduced by atan(a) = pi / 4 + atan((a - 1) / (a + 1)); 20 terms of the odd series by Horner; the octant, then the
+// quadrant by `x < 0` and `y < 0` (a negative zero counts as positive).  (0, 0) gives 0; a NaN argument, or two infinite ones, NaN.
+OXC_DEV double atan2_f64(double y, double x) {
+  const double ax = __builtin_fabs(x), ay = __builtin_fabs(y);
+  const double mx = ax > ay ? ax : ay, mn = ax > ay ? ay : ax;
+  const double a = mn / mx;
+  const bool fold = a > 0x1.a827999fcef32p-2;
+  const double t = fold ? (a - 1.0) / (a + 1.0) : a;
+  const double z = t * t;
+  double p = 1.0 / 39.0;
+  p = 1.0 / 37.0 - p * z;
+  p = 1.0 / 35.0 - p * z;
+  p = 1.0 / 33.0 - p * z;
+  p = 1.0 / 31.0 - p * z;
+  p = 1.0 / 29.0 - p * z;
+  p = 1.0 / 27.0 - p * z;
+  p = 1.0 / 25.0 - p * z;
+  p = 1.0 / 23.0 - p * z;
+  p = 1.0 / 21.0 - p * z;
+  p = 1.0 / 19.0 - p * z;
+  p = 1.0 / 17.0 - p * z;
+  p = 1.0 / 15.0 - p * z;
+  p = 1.0 / 13.0 - p * z;
+  p = 1.0 / 11.0 - p * z;
+  p = 1.0 / 9.0 - p * z;
+  p = 1.0 / 7.0 - p * z;
+  p = 1.0 / 5.0 - p * z;
+  p = 1.0 / 3.0 - p * z;
+  p = 1.0 - p * z;
+  double r = t * p;
+  r = fold ? 0x1.921fb54442d18p-1 + r : r;
+  r = ay > ax ? 0x1.921fb54442d18p+0 - r : r;
+  r = x < 0.0 ? 0x1.921fb54442d18p+1 - r : r;
+  r = y < 0.0 ? -r : r;
+  r = mx == 0.0 ? 0.0 : r;
+  return (x == x && y == y) ? r : __builtin_nan("");
+}
+
+// atan2(y, x) of two binary32, rounded to binary32 once
+OXC_DEV float atan2_rule(float y, float x) { return (float)atan2_f64((double)y, (double)x); }
+
+// acos(x) of a binary32 x: atan2(sqrt(1 - x * x), x) in binary64 (x * x is exact there), rounded to binary32 once; NaN for a NaN and for
+// |x| > 1.  acos(1) = 0, acos(-1) = (float)pi, acos(0) = (float)(pi / 2).
+OXC_DEV float acos_rule(float x) {
+  const double xd = (double)x;
+  const float r = (float)atan2_f64(__builtin_sqrt(1.0 - xd * xd), xd);
+  return __builtin_fabsf(x) <= 1.0f ? r : __builtin_nanf("");
+}
+
 }  // namespace oxc

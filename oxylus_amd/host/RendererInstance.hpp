@@ -159,13 +159,14 @@ struct PostProcessContext {
   Buffer fxaa_attachment = {};                   // the image apply_fxaa writes with HasFXAA: final_attachment's extent and format
 };
 
-// RendererInstance.hpp:294-300 of the reference without sky_cubemap_attachment (the sky_ibl pass is not in the library): the four sky LUTs,
-// linear u16x4 buffers of the extents the Atmosphere record names.
+// RendererInstance.hpp:294-300 of the reference: the four sky LUTs, linear u16x4 buffers of the extents the Atmosphere record names, and the
+// sky cubemap, u16x4 [6][32][32], which the owner zeroes once (the reference clears it in its constructor).
 struct AtmosphereContext {
   Buffer sky_transmittance_lut_attachment = {};
   Buffer sky_multiscatter_lut_attachment = {};
   Buffer sky_view_lut_attachment = {};
   Buffer sky_aerial_perspective_lut_attachment = {};
+  Buffer sky_cubemap_attachment = {};
 };
 
 // The five pp.bloom_* cvars apply_bloom reads, with the engine's defaults (RendererCVar.cpp:44-48)
@@ -468,6 +469,23 @@ public:
     c.sky_view_lut = context.sky_view_lut_attachment;
     c.sky_aerial_perspective_lut = context.sky_aerial_perspective_lut_attachment;
     check(oxc_draw_atmosphere(ctx_, &c, stream_));
+  }
+  // The sky_ibl pass of RendererInstance::draw_atmosphere (Passes/PBR.cpp:52-94), after draw_atmosphere: 64 samples of sky_view_lut per texel of
+  // the 32 x 32 x 6 cube, blended into the cube's own history.  frame_index is render_context->num_frames; 0.15f is the sun_ambient_strength the
+  // engine pushes.  Rules: include/oxcull.h, oxc_generate_sky_ibl.
+  auto generate_sky_ibl(AtmosphereContext& context, uint32_t frame_index) -> void {
+    oxc_sky_ibl_context c = {};
+    c.struct_size = sizeof c;
+    c.atmosphere = atmosphere;
+    for (int i = 0; i < 3; i++) c.sun_dir[i] = directional_light.direction[i], c.camera_position[i] = camera.position[i];
+    c.sun_intensity = directional_light.intensity;
+    c.sun_ambient_strength = 0.15f;
+    c.frame_index = frame_index;
+    c.cube_size = 32;
+    c.sky_view_lut = context.sky_view_lut_attachment;
+    c.sky_transmittance_lut = context.sky_transmittance_lut_attachment;
+    c.sky_cubemap = context.sky_cubemap_attachment;
+    check(oxc_generate_sky_ibl(ctx_, &c, stream_));
   }
   // The `fxaa` pass (RendererInstance.cpp:1225-1255), between apply_pbr and apply_eye_adaptation: with HasFXAA in gpu_scene_flags, edge
   // anti-aliasing of context.final_attachment into context.fxaa_attachment, which is then handed on as context.final_attachment (the

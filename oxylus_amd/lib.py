@@ -578,6 +578,24 @@ class AtmosphereContext(C.Structure):
     ]
 
 
+class SkyIblContext(C.Structure):
+    _c_name_ = "oxc_sky_ibl_context"
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("_pad", C.c_uint32),
+        ("atmosphere", Atmosphere),
+        ("sun_dir", C.c_float * 3),
+        ("sun_intensity", C.c_float),
+        ("camera_position", C.c_float * 3),
+        ("sun_ambient_strength", C.c_float),
+        ("frame_index", C.c_uint32),
+        ("cube_size", C.c_uint32),
+        ("sky_view_lut", Buffer),
+        ("sky_transmittance_lut", Buffer),
+        ("sky_cubemap", Buffer),
+    ]
+
+
 class MeshBuildDesc(C.Structure):
     _c_name_ = "oxc_mesh_build_desc"
     _fields_ = [("struct_size", C.c_uint32), ("vertex_count", C.c_uint32), ("index_count", C.c_uint32), ("max_lods", C.c_uint32), ("max_vertices", C.c_uint32),
@@ -641,6 +659,7 @@ PROTOTYPES = {
     "oxc_debug_fxaa_stats": _stats,
     "oxc_generate_sky_luts": (_status, [_vp, _P(SkyLutContext), _vp]),
     "oxc_draw_atmosphere": (_status, [_vp, _P(AtmosphereContext), _vp]),
+    "oxc_generate_sky_ibl": (_status, [_vp, _P(SkyIblContext), _vp]),
     "oxc_draw_physical_pages": (_status, [_vp, _P(PreparedFrame), _P(VsmDrawContext), _vp]),
     "oxc_debug_vsm_draw_stats": _stats,
     "oxc_resolve_shadowmap": (_status, [_vp, _P(ShadowResolveContext), _vp]),

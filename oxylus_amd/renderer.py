@@ -649,8 +649,8 @@ class SkyLutContext(Marshalled):
 
 @dataclass
 class AtmosphereContext(Marshalled):
-    """oxc_atmosphere_context: RendererInstance::draw_atmosphere (Passes/PBR.cpp:9-141) without its sky_ibl pass, so without the reference's
-    sky_cubemap_attachment.  `create` lays out the four buffers from an Atmosphere; generate_sky_luts fills the first two through
+    """oxc_atmosphere_context: RendererInstance::draw_atmosphere (Passes/PBR.cpp:9-141) without its sky_ibl pass; the reference's
+    sky_cubemap_attachment belongs to SkyIblContext, which is made from this one.  `create` lays out the four buffers from an Atmosphere; generate_sky_luts fills the first two through
     `sky_luts(hemisphere_directions)`."""
     _ctype = L.AtmosphereContext
     _derived = {"sky_transmittance_lut": "sky_transmittance_lut_attachment", "sky_multiscatter_lut": "sky_multiscatter_lut_attachment",
@@ -675,6 +675,34 @@ class AtmosphereContext(Marshalled):
 
     def sky_luts(self, hemisphere_directions: torch.Tensor) -> SkyLutContext:
         return SkyLutContext(self.atmosphere, hemisphere_directions, self.sky_transmittance_lut_attachment, self.sky_multiscatter_lut_attachment)
+
+
+@dataclass
+class SkyIblContext(Marshalled):
+    """oxc_sky_ibl_context: the sky_ibl pass of RendererInstance::draw_atmosphere (Passes/PBR.cpp:52-94).  `create` takes the AtmosphereContext
+    whose sky-view and transmittance LUTs it reads -- the tensors are shared, with its record, sun and camera -- and allocates the zeroed cube,
+    int16 [6, cube_size, cube_size, 4]; the cube is its own history, so one context is kept across frames and only `frame_index` moves."""
+    _ctype = L.SkyIblContext
+    _derived = {"sky_view_lut": "sky_view_lut_attachment", "sky_transmittance_lut": "sky_transmittance_lut_attachment", "sky_cubemap": "sky_cubemap_attachment"}
+    _leave = ("_pad",)
+    atmosphere: Atmosphere
+    sky_view_lut_attachment: torch.Tensor           # in
+    sky_transmittance_lut_attachment: torch.Tensor  # in
+    sky_cubemap_attachment: torch.Tensor            # in and out
+    cube_size: int = 32
+    sun_dir: tuple = (0.0, 1.0, 0.0)
+    sun_intensity: float = 10.0
+    camera_position: tuple = (0.0, 0.0, 0.0)
+    sun_ambient_strength: float = 0.15
+    frame_index: int = 0
+
+    @staticmethod
+    def create(context: AtmosphereContext, cube_size: int = 32, **settings) -> "SkyIblContext":
+        view = context.sky_view_lut_attachment
+        for name in ("sun_dir", "sun_intensity", "camera_position"):
+            settings.setdefault(name, getattr(context, name))
+        return SkyIblContext(context.atmosphere, view, context.sky_transmittance_lut_attachment, _lut((6, cube_size, cube_size), view.device),
+                             int(cube_size), **settings)
 
 
 @dataclass
@@ -994,6 +1022,11 @@ class RendererInstance:
         """Passes/PBR.cpp:9-141 without the sky_ibl pass: sky_view_lut and sky_aerial_perspective_lut from the two LUTs of generate_sky_luts, the
         sun and the camera, two launches (include/oxcull.h, oxc_draw_atmosphere)."""
         self._call("oxc_draw_atmosphere", context, stream)
+
+    def generate_sky_ibl(self, context: SkyIblContext, stream=None) -> None:
+        """Passes/PBR.cpp:52-94, the sky_ibl pass of draw_atmosphere: 64 samples of sky_view_lut per cube texel, blended into the texel's own
+        history, one launch (include/oxcull.h, oxc_generate_sky_ibl).  After draw_atmosphere; `context.frame_index` is the caller's to advance."""
+        self._call("oxc_generate_sky_ibl", context, stream)
 
     def debug_fxaa_stats(self, stream=None) -> dict:
         """What the last apply_fxaa did, after debug_set_tuning(L.TUNE_FXAA_STATS, 1) (measurement hook; synchronises)."""
