@@ -1018,8 +1018,8 @@ oxc_status oxc_decode_visbuffer(oxc_ctx* ctx, const oxc_prepared_frame* frame, c
  * Replaces the no-atmosphere branch of RendererInstance::apply_pbr (Oxylus/src/Render/Passes/PBR.cpp:313-534, the else branch from :435,
  * pipeline pbr_apply_no_atmos, passes/pbr_apply_no_atmos.slang with pbr.slang), the full-screen pass that reads what oxc_decode_visbuffer,
  * oxc_resolve_shadowmap, oxc_contact_shadows and oxc_generate_ambient_occlusion wrote and the first one whose output is a picture.
- * Out of scope: the atmosphere branch (passes/pbr_apply.slang: the sky LUTs, the cubemap, aerial perspective) -- scene_flags with
- * OXC_SCENE_HAS_ATMOSPHERE is OXC_INVALID_ARG; tone mapping and the other post passes; tiled or clustered light culling (the reference
+ * Out of scope: the atmosphere branch (passes/pbr_apply.slang: the sky LUTs, the cubemap, aerial perspective), which is
+ * oxc_apply_pbr_atmosphere below -- here scene_flags with OXC_SCENE_HAS_ATMOSPHERE is OXC_INVALID_ARG; tone mapping and the other post passes; tiled or clustered light culling (the reference
  * has none); any change to what the five producer passes write.
  * Arithmetic: the canonical binary32 arithmetic of the other passes -- round to nearest even, one fixed order, no contraction, IEEE division
  * and square root; 1.0 / x is a division; min, max, clamp and saturate go through fmaxf / fminf, so a NaN operand loses (saturate(NaN) = 0,
@@ -1104,7 +1104,7 @@ oxc_status oxc_decode_visbuffer(oxc_ctx* ctx, const oxc_prepared_frame* frame, c
  * sun_intensity, the three colours) finite.  Light records live on the device and are not validated: the rule gives a defined result for
  * any bit pattern in them.  One launch, no scratch, no allocation, no host synchronisation; capturable into a HIP graph. */
 #define OXC_SCENE_HAS_DIRECTIONAL_LIGHT (1u << 0)  /* GPU::SceneFlags (scene.slang:242-256); the other bits are not read */
-#define OXC_SCENE_HAS_ATMOSPHERE (1u << 1)         /* not built: OXC_INVALID_ARG */
+#define OXC_SCENE_HAS_ATMOSPHERE (1u << 1)         /* oxc_apply_pbr: OXC_INVALID_ARG; the branch is oxc_apply_pbr_atmosphere */
 #define OXC_SCENE_HAS_CONTACT_SHADOWS (1u << 9)
 #define OXC_SCENE_HAS_SKY (1u << 10)
 #define OXC_SCENE_TRANSPARENT_BACKGROUND (1u << 11)
@@ -1484,8 +1484,8 @@ oxc_status oxc_apply_fxaa(oxc_ctx* ctx, const oxc_fxaa_context* context, void* h
  * again whenever the Atmosphere record changes.  oxc_draw_atmosphere replaces RendererInstance::draw_atmosphere (Passes/PBR.cpp:9-141)
  * without its middle sky_ibl pass, which is oxc_generate_sky_ibl below: pipelines sky_view and sky_aerial_perspective.  All four passes go
  * through sky.slang, bound with LinearSamplerClamped.
- * Out of scope, the follow-up: the atmosphere branch of pbr_apply.slang, the consumer of these LUTs and of the sky cubemap --
- * oxc_apply_pbr still refuses OXC_SCENE_HAS_ATMOSPHERE.
+ * The consumer of these LUTs and of the sky cubemap is the atmosphere branch of pbr_apply.slang: oxc_apply_pbr_atmosphere (oxc_apply_pbr
+ * refuses OXC_SCENE_HAS_ATMOSPHERE).
  * Images: all four are R16G16B16A16 Sfloat, here linear u16x4 buffers of binary16 bits like the normal image, row-major; the 3-D LUT is
  * [depth][height][width].  A store is the binary16 conversion of oxc_apply_pbr step 12 per channel (a NaN stored as 0x7E00).  A
  * SampleLevel(LinearSamplerClamped, uv, 0).rgb is the manual bilinear of the oxc_apply_bloom block in clamp mode on the decoded halves
@@ -1617,8 +1617,8 @@ oxc_status oxc_draw_atmosphere(oxc_ctx* ctx, const oxc_atmosphere_context* conte
  * oxc_generate_sky_ibl is the middle pass of RendererInstance::draw_atmosphere (Passes/PBR.cpp:52-94, passes/sky_ibl.slang): from the
  * sky-view LUT oxc_draw_atmosphere wrote and the transmittance LUT it writes sky_cubemap, the image pbr_apply.slang samples for the ambient
  * term.  With it the reference's draw_atmosphere is oxc_draw_atmosphere, then this call (three with oxc_generate_sky_luts, which the
- * reference runs at construction); the aerial LUT and the cube do not read each other.  Out of scope, the follow-up: the atmosphere branch of pbr_apply.slang -- oxc_apply_pbr still refuses
- * OXC_SCENE_HAS_ATMOSPHERE.
+ * reference runs at construction); the aerial LUT and the cube do not read each other.  The consumer is the atmosphere branch of pbr_apply.slang:
+ * oxc_apply_pbr_atmosphere.
  * Images: the cube is R16G16B16A16 Sfloat, here a linear u16x4 buffer [6][cube_size][cube_size] like the LUTs; face f is the Slang's
  * thread_id.z, texel (x, y) of it thread_id.xy.  The cube is read and written: a texel is its own history.  The reference clears it to
  * black once, in the constructor (RendererInstance.cpp:187-201); here the caller zeroes the buffer once and the call never clears it.
@@ -1693,6 +1693,100 @@ typedef struct oxc_sky_ibl_context {
 } oxc_sky_ibl_context;
 
 oxc_status oxc_generate_sky_ibl(oxc_ctx* ctx, const oxc_sky_ibl_context* context, void* hip_stream);
+
+/* ---- PBR apply, the atmosphere branch: the lit HDR image with the sky, the sun disc, aerial perspective and the sky-lit ambient ----------------
+ * Replaces the atmosphere branch of RendererInstance::apply_pbr (Oxylus/src/Render/Passes/PBR.cpp:318-434, pipeline pbr_apply,
+ * passes/pbr_apply.slang with pbr.slang, sky.slang and scene.slang): the consumer of what oxc_generate_sky_luts, oxc_draw_atmosphere and
+ * oxc_generate_sky_ibl wrote.  A call of its own with a context of its own: oxc_apply_pbr keeps its layout and keeps refusing
+ * OXC_SCENE_HAS_ATMOSPHERE; here that bit may be set or clear (it is the caller's dispatch bit and is not read).  The call reads
+ * OXC_SCENE_HAS_DIRECTIONAL_LIGHT, OXC_SCENE_HAS_CONTACT_SHADOWS and OXC_SCENE_TRANSPARENT_BACKGROUND.
+ * Not in the context: base_ambient_color and the GPU::Sky record.  In pbr_apply.slang diffuse_sky and specular_sky start as
+ * base_ambient_color and are overwritten on every lit pixel (:139-140), and has_sky (:93) feeds nothing.
+ * Arithmetic: every device operation in the canonical binary32 arithmetic oxc_apply_pbr states; the four sky images are u16x4 buffers in
+ * the layouts their producers write, a SampleLevel(LinearSamplerClamped) of one is the clamp bilinear of the sky LUT block; "atmosphere
+ * step n" is step n of that block, "step n" alone step n of oxc_apply_pbr.
+ * Host constants, once per call: eye_altitude, beta and zenith_horizon_angle as oxc_draw_atmosphere forms them from camera_position.y, and H;
+ * in binary32 operations: min_altitude = planet_radius + 0.001f;  sun_cos_theta = (L.x * 0.0f + L.y * 1.0f) + L.z * 0.0f, L = sun_dir as
+ * given;  horizon_darkening = smoothstep(-0.1f, 0.3f, sun_cos_theta) by the stated smoothstep;  min_cos = the cos rule of oxc_apply_pbr at
+ * (1.0f * PI) / 180.0f;  lut = f32(aerial_perspective_lut_size);  per_slice_depth = lut.x / lut.z, the FLOAT quotient (sky.slang:266; the
+ * producer's integer quotient differs where x is no multiple of z: both are as written);  1.0f / per_slice_depth, 1.0f / lut.z, 1.0f / 0.001f.
+ * Per pixel (x, y):
+ *   A. transparent, decode, position, frame  (pbr_apply.slang:50-83)  steps 1 - 4, unchanged.
+ *   B. visibility  (:85-87)  directional_shadow and contact_shadow as in step 6; an image whose flag is clear is not read, not checked and may
+ *              be null.
+ *   C. sun  (:97-106)  for every pixel that passed A, the empty ones included:  world_eye_y = max(world.y * 0.01f + min_altitude,
+ *              min_altitude), a per-pixel binary32 value (max is fmaxf: a NaN world.y gives min_altitude);  sun_transmittance = the
+ *              transmittance sample of atmosphere step 3 at (world_eye_y, sun_cos_theta);  direct = (sun_transmittance * Li) *
+ *              horizon_darkening per channel.  direct does not depend on HasDirectionalLight, only directional_shadow does: that is what
+ *              the Slang says.  A non-finite world (h.w == 0) runs on: the IEEE results and the clamp bilinear's defined behaviour for a
+ *              NaN coordinate are the rule.
+ *   D. sky pixel  (depth == 0.0, :108-124)  h = eye_altitude, eye_pos = (0, h, 0);  up = (0, 1, 0);  right = normalize(cross(up, -V));
+ *              forward = normalize(cross(right, up));  l = (dot(L, forward), dot(L, right));  light_on_plane = l / sqrt(l.x * l.x + l.y *
+ *              l.y), the plain 2-D normalize and not atmosphere step 14's safe_normalize: a zero l gives NaN, and the NaN goes through
+ *              atan2;  c = dot(-V, up), every product formed;  hit = intersect(eye_pos, -V, planet_radius) has a value;  uv =
+ *              sky_view_params_to_lut_uv exactly as atmosphere step 14 states it (acos and atan2 by step 11);  s = the .rgba sample of
+ *              sky_view_lut at uv.  No hit:  s.rgb += (draw_sun(-V, L) * Li) * sun_transmittance, where draw_sun (:26-38) is: ct = dot(-V, L);
+ *              ct >= min_cos gives 1.0 (a NaN takes the other arm);  otherwise offset = min_cos - ct, g = exp(-offset * 50000.0f) * 0.5f by
+ *              the exp rule, inv = (1.0f / (0.02f + offset * 300.0f)) * 0.01f, g + inv.  The colour is s.rgb * s.a, alpha 1, and the pixel
+ *              is done.  The sun_transmittance is C's, from this pixel's world, as written.
+ *   E. aerial perspective  (:127-133, sky.slang:258-293)  rel = (world - camera_position) * 0.01f per component;  relative_depth = max(0,
+ *              length(rel) - aerial_perspective_start_km);  linear_slice = relative_depth * (1.0f / per_slice_depth);  linear_w =
+ *              linear_slice * (1.0f / lut.z);  non_linear_w = sqrt(linear_w);  non_linear_slice = non_linear_w * lut.z;  weight = 1, and
+ *              with non_linear_slice < 0.70710678118654752f weight = saturate((non_linear_slice * non_linear_slice) * 2.0f);  weight =
+ *              weight * saturate(relative_depth * (1.0f / 0.001f)).  a = the clamp trilinear sample at (uv of step 3, non_linear_w): the third
+ *              axis by the same axis rule on non_linear_w with the LUT's depth, the bilinear .rgba of slice i0 and of slice i1, then lerp
+ *              by the z weight.  a.rgb *= weight;  a.w = 1.0f - (weight * (1.0f - a.w));  a.rgb *= aerial_perspective_exposure;  aerial =
+ *              a.rgb * a.w.
+ *   F. cube sample of a direction r (a stated rule, like the albedo sampler's)  ax = |r.x|, ay = |r.y|, az = |r.z|;  az >= ax && az >= ay
+ *              selects Z, else ay >= ax selects Y, else X (a NaN makes a comparison false);  the sign of the major component picks the
+ *              face of the pair, a negative zero or a NaN counting as positive;  (face, sc, tc, ma) by the Vulkan table: +X (0, -r.z, -r.y,
+ *              r.x), -X (1, +r.z, -r.y, r.x), +Y (2, r.x, +r.z, r.y), -Y (3, r.x, -r.z, r.y), +Z (4, r.x, -r.y, r.z), -Z (5, -r.x, -r.y,
+ *              r.z) -- the inverse of step 12's row-major CUBE_MAP_FACE_ROTATION of oxc_generate_sky_ibl;  s = (sc / |ma|) * 0.5f + 0.5f, t
+ *              likewise;  the sample is the clamp bilinear .rgba of that face alone at (s, t).  Stated deviation: the hardware filters
+ *              seamlessly across face edges, this rule clamps inside the face; the two differ only within half a texel of an edge.
+ *   G. sky ambient  (:135-140)  reflection_dir = normalize(lerp(N, R, 1.0f - roughness));  spec = cube(reflection_dir), diff = cube(N);
+ *              specular_sky = (spec.rgb * spec.a) * horizon_darkening, diffuse_sky likewise.
+ *   H. surface, ambient  (:143-157)  steps 7 and 8 with env replaced per channel: ibl_diffuse = ((kD * diffuse_sky) * albedo) *
+ *              Fd_Lambert(), ibl_specular = (kS * specular_sky) * spec_occlusion.
+ *   I. lights, BRDF  steps 9 and 10, unchanged.
+ *   J. sun term  step 11 with direct per channel: surface = (((b.diffuse + b.specular * horizon) * direct_c) * NoL) * visibility.
+ *   K. store  colour = (((surface + total) + indirect) + emission) + aerial;  formats and NaN handling as step 12.
+ * Limits (else OXC_INVALID_ARG, nothing launched, the output untouched; the first broken rule in this order gives the message, each has its
+ * own): struct_size; the extent rules of oxc_apply_pbr; every side of transmittance_lut_size, then of sky_view_lut_size, in 2 .. 4096; every
+ * side of the aerial LUT in 1 .. 4096 and at most 2^26 texels; cube_size in 1 .. 1024; planet_radius and atmos_radius finite, planet_radius
+ * > 0, atmos_radius > planet_radius; aerial_perspective_start_km and aerial_perspective_exposure finite; every host scalar (the matrix,
+ * camera_position, sun_dir, sun_intensity) finite; the G-buffer, shadow and light rules of oxc_apply_pbr; the four sky buffers in field
+ * order, each non-null, then aligned to 8 bytes, then at least as large as its extent says; final_attachment as in oxc_apply_pbr, sharing
+ * no byte with any input.  One launch, no scratch, no allocation, no host synchronisation; capturable into a HIP graph. */
+typedef struct oxc_pbr_atmosphere_context {
+  uint32_t struct_size; /* sizeof(oxc_pbr_atmosphere_context) */
+  uint32_t width, height;
+  uint32_t scene_flags;           /* GPU::SceneFlags */
+  uint32_t light_count;
+  float inv_projection_view[16];  /* Camera::inv_projection_view, column-major */
+  float camera_position[3];
+  float sun_dir[3];               /* L: towards the sun, used as given */
+  float sun_intensity;            /* Li */
+  oxc_atmosphere atmosphere;      /* the record the three producers were called with */
+  uint32_t cube_size;             /* the engine's 32 */
+  uint32_t _pad;
+  oxc_image depth_attachment;     /* the next nine: as in oxc_pbr_context */
+  oxc_buffer albedo_attachment;
+  oxc_buffer normal_attachment;
+  oxc_buffer emissive_attachment;
+  oxc_buffer metallic_roughness_occlusion_attachment;
+  oxc_buffer ambient_occlusion_attachment;
+  oxc_image resolved_shadows_attachment;
+  oxc_image contact_shadows_attachment;
+  oxc_buffer lights_buffer;
+  oxc_buffer sky_transmittance_lut;      /* in: u16x4 [transmittance_lut_size.y][.x], what oxc_generate_sky_luts wrote */
+  oxc_buffer sky_view_lut;               /* in: u16x4 [sky_view_lut_size.y][.x], what oxc_draw_atmosphere wrote */
+  oxc_buffer sky_aerial_perspective_lut; /* in: u16x4 [aerial_perspective_lut_size.z][.y][.x], what oxc_draw_atmosphere wrote */
+  oxc_buffer sky_cubemap;                /* in: u16x4 [6][cube_size][cube_size], what oxc_generate_sky_ibl wrote */
+  oxc_buffer final_attachment;    /* out: u32[height][width] B10G11R11, or u16x4[height][width] with a transparent background */
+} oxc_pbr_atmosphere_context;
+
+oxc_status oxc_apply_pbr_atmosphere(oxc_ctx* ctx, const oxc_pbr_atmosphere_context* context, void* hip_stream);
 
 /* ---- multi-GPU exchange: one process per GPU, RCCL over xGMI ---------------------------
  * The meshlet-instance array shards by contiguous range and every rank culls its shard on its own; the only

@@ -175,7 +175,7 @@ oxc_status oxc_apply_pbr(oxc_ctx* ctx, const oxc_pbr_context* c, void* hip_strea
   const char* const entry = "apply_pbr";
   const oxc_image& dimg = c->depth_attachment;
   const uint32_t flags = c->scene_flags;
-  if (flags & OXC_SCENE_HAS_ATMOSPHERE) return bad_arg(ctx, entry, "HasAtmosphere: the atmosphere branch (pbr_apply.slang) is not built");
+  if (flags & OXC_SCENE_HAS_ATMOSPHERE) return bad_arg(ctx, entry, "HasAtmosphere: the atmosphere branch (pbr_apply.slang) is oxc_apply_pbr_atmosphere, not this call");
   if (c->width == 0u || c->height == 0u) return bad_arg(ctx, entry, "the extent must not be zero");
   if (dimg.width != c->width || dimg.height != c->height) return bad_arg(ctx, entry, "depth_attachment extent differs from (width, height)");
   uint64_t pixels;
@@ -226,6 +226,116 @@ oxc_status oxc_apply_pbr(oxc_ctx* ctx, const oxc_pbr_context* c, void* hip_strea
   }
   a.sun_intensity = c->sun_intensity;
   launch_pbr_apply(a, s);
+  OXC_HIP(ctx, hipGetLastError());
+  return OXC_OK;
+}
+
+oxc_status oxc_apply_pbr_atmosphere(oxc_ctx* ctx, const oxc_pbr_atmosphere_context* c, void* hip_stream) {
+  if (!ctx) return OXC_INVALID_ARG;
+  if (!c || c->struct_size != sizeof(oxc_pbr_atmosphere_context)) return fail(ctx, OXC_INVALID_ARG, "apply_pbr_atmosphere: bad context / struct_size");
+  const char* const entry = "apply_pbr_atmosphere";
+  const oxc_image& dimg = c->depth_attachment;
+  const oxc_atmosphere& A = c->atmosphere;
+  const uint32_t flags = c->scene_flags;
+  const bool has_sun = (flags & OXC_SCENE_HAS_DIRECTIONAL_LIGHT) != 0u, has_contact = (flags & OXC_SCENE_HAS_CONTACT_SHADOWS) != 0u;
+  // 2. the extent
+  if (c->width == 0u || c->height == 0u) return bad_arg(ctx, entry, "the extent must not be zero");
+  if (dimg.width != c->width || dimg.height != c->height) return bad_arg(ctx, entry, "depth_attachment extent differs from (width, height)");
+  uint64_t pixels;
+  OXC_TRY(pixel_images(ctx, entry, dimg, nullptr, nullptr, pixels));
+  // 3 - 8. the record
+  if (bad_lut_side(A.transmittance_lut_size)) return bad_arg(ctx, entry, "transmittance_lut_size: every side must be in 2 .. 4096");
+  if (bad_lut_side(A.sky_view_lut_size)) return bad_arg(ctx, entry, "sky_view_lut_size: every side must be in 2 .. 4096");
+  uint64_t aerial_texels;
+  OXC_TRY(check_aerial_size(ctx, entry, A.aerial_perspective_lut_size, aerial_texels));
+  if (c->cube_size < 1u || c->cube_size > 1024u) return bad_arg(ctx, entry, "cube_size must be in 1 .. 1024");
+  OXC_TRY(check_radii(ctx, entry, A));
+  if (!std::isfinite(A.aerial_perspective_start_km) || !std::isfinite(A.aerial_perspective_exposure))
+    return bad_arg(ctx, entry, "aerial_perspective_start_km and aerial_perspective_exposure must be finite");
+  // 9. the host scalars
+  bool finite = std::isfinite(c->sun_intensity);
+  for (int k = 0; k < 16; k++) finite = finite && std::isfinite(c->inv_projection_view[k]);
+  for (int k = 0; k < 3; k++) finite = finite && std::isfinite(c->camera_position[k]) && std::isfinite(c->sun_dir[k]);
+  if (!finite) return bad_arg(ctx, entry, "inv_projection_view, camera_position, sun_dir and sun_intensity must be finite");
+  // 10. the G-buffer, the shadow terms, the lights: oxc_apply_pbr's rules
+  OXC_TRY(pixel_images(ctx, entry, dimg, has_sun ? &c->resolved_shadows_attachment : nullptr, "resolved_shadows_attachment", pixels));
+  OXC_TRY(pixel_images(ctx, entry, dimg, has_contact ? &c->contact_shadows_attachment : nullptr, "contact_shadows_attachment", pixels));
+  if (bad_pixel_buffer(c->albedo_attachment, pixels, 4u) || bad_pixel_buffer(c->emissive_attachment, pixels, 4u) ||
+      bad_pixel_buffer(c->metallic_roughness_occlusion_attachment, pixels, 4u))
+    return bad_arg(ctx, entry, "albedo_attachment, emissive_attachment and metallic_roughness_occlusion_attachment must be one aligned u32 per pixel");
+  if (bad_pixel_buffer(c->normal_attachment, pixels, 8u)) return bad_arg(ctx, entry, "normal_attachment must be 8-byte aligned u16x4 texels of the depth attachment's extent");
+  if (bad_pixel_buffer(c->ambient_occlusion_attachment, pixels, 2u)) return bad_arg(ctx, entry, "ambient_occlusion_attachment must be one aligned u16 per pixel");
+  const oxc_buffer& lb = c->lights_buffer;
+  if (c->light_count && (!lb.dptr || lb.bytes < (uint64_t)c->light_count * 64u || (reinterpret_cast<uintptr_t>(lb.dptr) & 3u)))
+    return bad_arg(ctx, entry, "lights_buffer must hold light_count 4-byte aligned GPU::Light records of 64 bytes");
+  // 11. the four sky images
+  const uint64_t t_bytes = lut_bytes(A.transmittance_lut_size), v_bytes = lut_bytes(A.sky_view_lut_size), a_bytes = aerial_texels * 8u,
+                 c_bytes = 6ull * c->cube_size * c->cube_size * 8u;
+  OXC_TRY(check_sky_buffers(ctx, entry, {{c->sky_transmittance_lut, t_bytes, "sky_transmittance_lut", false},
+                                         {c->sky_view_lut, v_bytes, "sky_view_lut", false},
+                                         {c->sky_aerial_perspective_lut, a_bytes, "sky_aerial_perspective_lut", false},
+                                         {c->sky_cubemap, c_bytes, "sky_cubemap", false}}));
+  // 12. the output
+  const bool transparent = (flags & OXC_SCENE_TRANSPARENT_BACKGROUND) != 0u;
+  const uint64_t texel = transparent ? 8u : 4u;
+  if (bad_pixel_buffer(c->final_attachment, pixels, texel))
+    return bad_arg(ctx, entry, "final_attachment must be one aligned u32 per pixel, or one 8-byte aligned u16x4 per pixel with TransparentBackground");
+  const uintptr_t out_lo = reinterpret_cast<uintptr_t>(c->final_attachment.dptr);
+  const ByteSpan out = {out_lo, out_lo + (uintptr_t)(pixels * texel)};
+  const struct {
+    const void* dptr;
+    uint64_t bytes;
+    const char* name;
+  } inputs[] = {{dimg.dptr, pixels * 4u, "depth_attachment"},
+                {c->albedo_attachment.dptr, pixels * 4u, "albedo_attachment"},
+                {c->normal_attachment.dptr, pixels * 8u, "normal_attachment"},
+                {c->emissive_attachment.dptr, pixels * 4u, "emissive_attachment"},
+                {c->metallic_roughness_occlusion_attachment.dptr, pixels * 4u, "metallic_roughness_occlusion_attachment"},
+                {c->ambient_occlusion_attachment.dptr, pixels * 2u, "ambient_occlusion_attachment"},
+                {has_sun ? c->resolved_shadows_attachment.dptr : nullptr, pixels * 4u, "resolved_shadows_attachment"},
+                {has_contact ? c->contact_shadows_attachment.dptr : nullptr, pixels * 4u, "contact_shadows_attachment"},
+                {c->light_count ? lb.dptr : nullptr, (uint64_t)c->light_count * 64u, "lights_buffer"},
+                {c->sky_transmittance_lut.dptr, t_bytes, "sky_transmittance_lut"},
+                {c->sky_view_lut.dptr, v_bytes, "sky_view_lut"},
+                {c->sky_aerial_perspective_lut.dptr, a_bytes, "sky_aerial_perspective_lut"},
+                {c->sky_cubemap.dptr, c_bytes, "sky_cubemap"}};
+  for (const auto& in : inputs) {
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(in.dptr);
+    if (in.dptr && out.overlaps({lo, lo + (uintptr_t)in.bytes})) return bad_arg(ctx, entry, "final_attachment must not overlap ", in.name);
+  }
+  OXC_ENTER(ctx, hip_stream, s);
+  PbrAtmosphereArgs a;
+  std::memset(&a, 0, sizeof a);
+  PbrApplyArgs& g = a.g;
+  g.depth = static_cast<const float*>(dimg.dptr);
+  g.albedo = static_cast<const uint32_t*>(c->albedo_attachment.dptr);
+  g.normal = static_cast<const uint2*>(c->normal_attachment.dptr);
+  g.emissive = static_cast<const uint32_t*>(c->emissive_attachment.dptr);
+  g.mro = static_cast<const uint32_t*>(c->metallic_roughness_occlusion_attachment.dptr);
+  g.ao = static_cast<const uint16_t*>(c->ambient_occlusion_attachment.dptr);
+  g.resolved = has_sun ? static_cast<const float*>(c->resolved_shadows_attachment.dptr) : nullptr;
+  g.contact = has_contact ? static_cast<const float*>(c->contact_shadows_attachment.dptr) : nullptr;
+  g.lights = lb.dptr;
+  g.out = c->final_attachment.dptr;
+  g.w = c->width;
+  g.h = c->height;
+  g.fw = (float)c->width;
+  g.fh = (float)c->height;
+  g.flags = flags;
+  g.light_count = c->light_count;
+  for (int k = 0; k < 16; k++) g.inv_pv[k] = c->inv_projection_view[k];
+  for (int k = 0; k < 3; k++) g.camera[k] = c->camera_position[k], g.sun[k] = c->sun_dir[k];
+  g.sun_intensity = c->sun_intensity;
+  a.transmittance = static_cast<const uint2*>(c->sky_transmittance_lut.dptr);
+  a.sky_view = static_cast<const uint2*>(c->sky_view_lut.dptr);
+  a.aerial = static_cast<const uint2*>(c->sky_aerial_perspective_lut.dptr);
+  a.cube = static_cast<const uint2*>(c->sky_cubemap.dptr);
+  a.cube_size = c->cube_size;
+  AtmosphereConstants k;
+  atmosphere_constants(A, &c->camera_position[1], k);
+  a.h_atmos = k.h_atmos, a.eye_altitude = k.eye_altitude, a.beta = k.beta, a.zenith_horizon_angle = k.zenith_horizon_angle;
+  pbr_atmosphere_constants(A, a);
+  launch_pbr_apply_atmosphere(a, s);
   OXC_HIP(ctx, hipGetLastError());
   return OXC_OK;
 }

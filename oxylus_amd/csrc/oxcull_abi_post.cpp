@@ -46,37 +46,6 @@ oxc_status bloom_pyramid(oxc_ctx* ctx, const char* entry, const oxc_image_pyrami
   return OXC_OK;
 }
 
-// The checks oxc_generate_sky_luts, oxc_draw_atmosphere and oxc_generate_sky_ibl share, in the order of the header's limits
-struct SkyBuffer {
-  const oxc_buffer& b;
-  uint64_t bytes;
-  const char* name;
-  bool output;
-};
-bool bad_lut_side(const uint32_t* size) { return size[0] < 2u || size[0] > 4096u || size[1] < 2u || size[1] > 4096u; }
-uint64_t lut_bytes(const uint32_t* size) { return (uint64_t)size[0] * size[1] * 8u; }
-oxc_status check_radii(oxc_ctx* ctx, const char* entry, const oxc_atmosphere& A) {
-  if (!std::isfinite(A.planet_radius) || !std::isfinite(A.atmos_radius)) return bad_arg(ctx, entry, "planet_radius and atmos_radius must be finite");
-  if (!(A.planet_radius > 0.0f)) return bad_arg(ctx, entry, "planet_radius must be above 0");
-  if (!(A.atmos_radius > A.planet_radius)) return bad_arg(ctx, entry, "atmos_radius must be above planet_radius");
-  return OXC_OK;
-}
-oxc_status check_sky_buffers(oxc_ctx* ctx, const char* entry, std::initializer_list<SkyBuffer> buffers) {
-  for (const SkyBuffer& s : buffers) {
-    if (!s.b.dptr) return bad_arg(ctx, entry, s.name, " must not be null");
-    if (reinterpret_cast<uintptr_t>(s.b.dptr) & 7u) return bad_arg(ctx, entry, s.name, " must be aligned to 8 bytes");
-    if (s.b.bytes < s.bytes) return bad_arg(ctx, entry, s.name, " is smaller than its extent");
-  }
-  for (const SkyBuffer& s : buffers) {
-    if (!s.output) continue;
-    const uintptr_t lo = reinterpret_cast<uintptr_t>(s.b.dptr);
-    for (const SkyBuffer& o : buffers) {
-      const uintptr_t olo = reinterpret_cast<uintptr_t>(o.b.dptr);
-      if (&o != &s && ByteSpan{lo, lo + (uintptr_t)s.bytes}.overlaps({olo, olo + (uintptr_t)o.bytes})) return bad_arg(ctx, entry, s.name, " must not overlap ", o.name);
-    }
-  }
-  return OXC_OK;
-}
 }  // namespace
 
 oxc_status oxc_apply_eye_adaptation(oxc_ctx* ctx, const oxc_eye_adaptation_context* c, void* hip_stream) {
@@ -290,11 +259,8 @@ oxc_status oxc_draw_atmosphere(oxc_ctx* ctx, const oxc_atmosphere_context* c, vo
   if (bad_lut_side(A.transmittance_lut_size)) return bad_arg(ctx, entry, "transmittance_lut_size: every side must be in 2 .. 4096");
   if (bad_lut_side(A.multiscattering_lut_size)) return bad_arg(ctx, entry, "multiscattering_lut_size: every side must be in 2 .. 4096");
   if (bad_lut_side(A.sky_view_lut_size)) return bad_arg(ctx, entry, "sky_view_lut_size: every side must be in 2 .. 4096");
-  const uint32_t* ap = A.aerial_perspective_lut_size;
-  if (ap[0] < 1u || ap[0] > 4096u || ap[1] < 1u || ap[1] > 4096u || ap[2] < 1u || ap[2] > 4096u)
-    return bad_arg(ctx, entry, "aerial_perspective_lut_size: every side must be in 1 .. 4096");
-  const uint64_t aerial_texels = (uint64_t)ap[0] * ap[1] * ap[2];
-  if (aerial_texels > (1ull << 26)) return bad_arg(ctx, entry, "aerial_perspective_lut_size: more than 2^26 texels");
+  uint64_t aerial_texels;
+  OXC_TRY(check_aerial_size(ctx, entry, A.aerial_perspective_lut_size, aerial_texels));
   OXC_TRY(check_radii(ctx, entry, A));
   OXC_TRY(check_sky_buffers(ctx, entry, {{c->sky_transmittance_lut, lut_bytes(A.transmittance_lut_size), "sky_transmittance_lut", false},
                                          {c->sky_multiscatter_lut, lut_bytes(A.multiscattering_lut_size), "sky_multiscatter_lut", false},

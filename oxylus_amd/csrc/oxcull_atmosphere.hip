@@ -17,7 +17,8 @@
 //
 // integrate<> is sky.slang's integrate_single_scattered_luminance, its three constexpr switches template parameters; step<> is the body of
 // its loop.  Every float operation keeps the order and rounding the header states: the file is compiled without contraction, division and
-// sqrt are the IEEE ones, exp / pow / cos are the closed binary64 rules of oxcull_pixel_device.hpp.
+// sqrt are the IEEE ones, exp / pow / cos are the closed binary64 rules of oxcull_pixel_device.hpp, which also holds what the atmosphere branch
+// of apply_pbr (oxcull_pbr_apply.hip) shares with this file: intersect, the clamp bilinear, the transmittance and the sky-view uv mappings.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -57,24 +58,6 @@ constexpr float kInv4Pi = 1.0f / (4.0f * kPi), kRayleighK = 3.0f / (16.0f * kPi)
 OXC_DEV float dotv(const V3& a, const V3& b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 OXC_DEV float lengthv(const V3& a) { return __builtin_sqrtf(dotv(a, a)); }
 OXC_DEV V3 along(const V3& o, float t, const V3& d) { return {o.x + t * d.x, o.y + t * d.y, o.z + t * d.z}; }  // o + t * d
-OXC_DEV float safe_sqrt(float x) { return __builtin_sqrtf(fmaxf(0.0f, x)); }
-
-// com::ray_sphere_intersect_nearest (common/math.slang:104-138); `value` is 0.0 where the Slang's Optional is none
-struct Hit {
-  bool has;
-  float value;
-};
-OXC_DEV Hit intersect_nearest(const V3& o, const V3& d, float radius) {
-  const float a = dotv(d, d), b = 2.0f * dotv(d, o), c = dotv(o, o) - radius * radius;
-  const float delta = b * b - (4.0f * a) * c;
-  if (delta < 0.0f) return {false, 0.0f};
-  const float sq = __builtin_sqrtf(delta), den = 2.0f * a;
-  const float s0 = (-b + -1.0f * sq) / den, s1 = (-b + sq) / den;
-  if (s0 < 0.0f && s1 < 0.0f) return {false, 0.0f};
-  if (s0 < 0.0f) return {true, fmaxf(0.0f, s1)};
-  if (s1 < 0.0f) return {true, fmaxf(0.0f, s0)};
-  return {true, fmaxf(0.0f, fminf(s0, s1))};
-}
 
 // MediumScattering (sky.slang:119-150); mie_extinction is one float for the three channels
 struct Medium {
@@ -93,23 +76,10 @@ OXC_DEV Medium medium_at(const oxc_atmosphere& A, float altitude) {
   return m;
 }
 
-// SampleLevel(LinearSamplerClamped, uv, 0).rgb of a w x h RGBA16F LUT: the manual bilinear of the oxc_apply_bloom block, clamp mode
-OXC_DEV V3 sample_rgb(const uint2* lut, uint32_t w, uint32_t h, float u, float v) {
-  const Axis ax = axis_at<false>(u, (float)w, (int)w - 1), ay = axis_at<false>(v, (float)h, (int)h - 1);
-  const size_t r0 = (size_t)ay.i0 * w, r1 = (size_t)ay.i1 * w;
-  const V3 t00 = load_rgba<1>(lut, r0 + ax.i0).c, t10 = load_rgba<1>(lut, r0 + ax.i1).c;
-  const V3 t01 = load_rgba<1>(lut, r1 + ax.i0).c, t11 = load_rgba<1>(lut, r1 + ax.i1).c;
-  return lerp3(lerp3(t00, t10, ax.f), lerp3(t01, t11, ax.f), ay.f);
-}
-
-// transmittance_params_to_lut_uv (sky.slang:15-29) and the sample at it
+// the transmittance sample of step 3 at (h, mu)
 OXC_DEV V3 sun_transmittance_at(const SkyLutInputs& in, float h, float mu) {
   const oxc_atmosphere& A = in.atm;
-  const float rho = safe_sqrt(h * h - A.planet_radius * A.planet_radius);
-  const float discriminant = (h * h) * (mu * mu - 1.0f) + A.atmos_radius * A.atmos_radius;
-  const float d = fmaxf(0.0f, -h * mu + safe_sqrt(discriminant));
-  const float d_min = A.atmos_radius - h, d_max = rho + in.k.h_atmos;
-  return sample_rgb(in.transmittance, A.transmittance_lut_size[0], A.transmittance_lut_size[1], (d - d_min) / (d_max - d_min), rho / in.k.h_atmos);
+  return transmittance_sample(in.transmittance, A.transmittance_lut_size[0], A.transmittance_lut_size[1], A.planet_radius, A.atmos_radius, in.k.h_atmos, h, mu);
 }
 
 // com::draine_phase (common/math.slang:58-62)
@@ -297,24 +267,14 @@ OXC_DEV void aerial_texel(const AtmosphereArgs& a, uint32_t x, uint32_t y, uint3
   store_half4(a.aerial, at, r.luminance.x, r.luminance.y, r.luminance.z, (r.transmittance.x * third + r.transmittance.y * third) + r.transmittance.z * third);
 }
 // ---- the sky cubemap (passes/sky_ibl.slang; the header's steps 11 - 15) -----------------------------------------------------------------------
-OXC_DEV V3 crossv(const V3& a, const V3& b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 OXC_DEV float frac_f(float x) { return x - floorf(x); }
 OXC_DEV float finite_or_zero(float x) { return __builtin_fabsf(x) < __builtin_inff() ? x : 0.0f; }  // com::sanitize, one component
-
-// SampleLevel(LinearSamplerClamped, uv, 0) with its alpha: sample_rgb's bilinear on all four channels
-OXC_DEV Texel sample_rgba(const uint2* lut, uint32_t w, uint32_t h, float u, float v) {
-  const Axis ax = axis_at<false>(u, (float)w, (int)w - 1), ay = axis_at<false>(v, (float)h, (int)h - 1);
-  const size_t r0 = (size_t)ay.i0 * w, r1 = (size_t)ay.i1 * w;
-  const Texel t00 = load_rgba<1>(lut, r0 + ax.i0), t10 = load_rgba<1>(lut, r0 + ax.i1);
-  const Texel t01 = load_rgba<1>(lut, r1 + ax.i0), t11 = load_rgba<1>(lut, r1 + ax.i1);
-  return {lerp3(lerp3(t00.c, t10.c, ax.f), lerp3(t01.c, t11.c, ax.f), ay.f), lerp_f(lerp_f(t00.a, t10.a, ax.f), lerp_f(t01.a, t11.a, ax.f), ay.f)};
-}
 
 // CUBE_MAP_FACE_ROTATION (sky_ibl.slang:21-30), the nine scalars in the constructor's order: row r is elements 3 r .. 3 r + 2
 __constant__ const float kCubeFace[6][9] = {{+0, +0, -1, +0, -1, +0, -1, +0, +0}, {+0, +0, +1, +0, -1, +0, +1, +0, +0}, {+1, +0, +0, +0, +0, -1, +0, +1, +0},
                                             {+1, +0, +0, +0, +0, +1, +0, -1, +0}, {+1, +0, +0, +0, -1, +0, +0, +0, -1}, {-1, +0, +0, +0, -1, +0, +0, +0, +1}};
 
-// get_atmosphere_illuminance_along_ray (sky.slang:296-322) with sky_view_params_to_lut_uv (sky.slang:39-67) inside, sanitized
+// get_atmosphere_illuminance_along_ray (sky.slang:296-322), sanitized
 OXC_DEV V3 sky_illuminance(const SkyIblArgs& a, const V3& eye, const V3& dir) {
   const oxc_atmosphere& A = a.in.atm;
   const float height = lengthv(eye);
@@ -331,24 +291,9 @@ OXC_DEV V3 sky_illuminance(const SkyIblArgs& a, const V3& eye, const V3& dir) {
   lx = keep ? lx * inv_len : 1.0f;
   ly = keep ? ly * inv_len : 0.0f;
   const bool intersect_planet = intersect_nearest(eye, dir, A.planet_radius).has;
-  const float zha = a.in.k.zenith_horizon_angle, beta = a.in.k.beta;
-  const float view_zenith_angle = acos_rule(view_zenith_cos_angle);
-  float uy;
-  if (!intersect_planet) {
-    float coord = view_zenith_angle / zha;
-    coord = 1.0f - coord;
-    coord = safe_sqrt(coord);
-    coord = 1.0f - coord;
-    uy = coord * 0.5f;
-  } else {
-    float coord = (view_zenith_angle - zha) / beta;
-    coord = safe_sqrt(coord);
-    uy = coord * 0.5f + 0.5f;
-  }
-  const float theta = atan2_rule(-ly, -lx);
-  const float ux = (theta + kPi) / (2.0f * kPi);
-  const float fw = (float)A.sky_view_lut_size[0], fh = (float)A.sky_view_lut_size[1];
-  const Texel t = sample_rgba(a.sky_view, A.sky_view_lut_size[0], A.sky_view_lut_size[1], (ux + 0.5f / fw) * (fw / (fw + 1.0f)), (uy + 0.5f / fh) * (fh / (fh + 1.0f)));
+  float u, v;
+  sky_view_lut_uv(a.in.k.zenith_horizon_angle, a.in.k.beta, A.sky_view_lut_size[0], A.sky_view_lut_size[1], intersect_planet, view_zenith_cos_angle, lx, ly, u, v);
+  const Texel t = sample_rgba(a.sky_view, A.sky_view_lut_size[0], A.sky_view_lut_size[1], u, v);
   return {finite_or_zero(t.c.x * t.a), finite_or_zero(t.c.y * t.a), finite_or_zero(t.c.z * t.a)};
 }
 }  // namespace

@@ -397,6 +397,48 @@ struct ByteSpan {
   bool overlaps(const ByteSpan& o) const { return lo < o.hi && o.lo < hi; }
 };
 
+// ---- the checks the sky passes (oxc_generate_sky_luts, oxc_draw_atmosphere, oxc_generate_sky_ibl) and oxc_apply_pbr_atmosphere share, each
+// applied in the order of its header block's limits
+struct SkyBuffer {
+  const oxc_buffer& b;
+  uint64_t bytes;
+  const char* name;
+  bool output;
+};
+inline bool bad_lut_side(const uint32_t* size) { return size[0] < 2u || size[0] > 4096u || size[1] < 2u || size[1] > 4096u; }
+inline uint64_t lut_bytes(const uint32_t* size) { return (uint64_t)size[0] * size[1] * 8u; }
+// every side of the aerial LUT in 1 .. 4096 and at most 2^26 texels
+inline oxc_status check_aerial_size(oxc_ctx* ctx, const char* entry, const uint32_t* ap, uint64_t& texels) {
+  if (ap[0] < 1u || ap[0] > 4096u || ap[1] < 1u || ap[1] > 4096u || ap[2] < 1u || ap[2] > 4096u)
+    return bad_arg(ctx, entry, "aerial_perspective_lut_size: every side must be in 1 .. 4096");
+  texels = (uint64_t)ap[0] * ap[1] * ap[2];
+  if (texels > (1ull << 26)) return bad_arg(ctx, entry, "aerial_perspective_lut_size: more than 2^26 texels");
+  return OXC_OK;
+}
+inline oxc_status check_radii(oxc_ctx* ctx, const char* entry, const oxc_atmosphere& A) {
+  if (!std::isfinite(A.planet_radius) || !std::isfinite(A.atmos_radius)) return bad_arg(ctx, entry, "planet_radius and atmos_radius must be finite");
+  if (!(A.planet_radius > 0.0f)) return bad_arg(ctx, entry, "planet_radius must be above 0");
+  if (!(A.atmos_radius > A.planet_radius)) return bad_arg(ctx, entry, "atmos_radius must be above planet_radius");
+  return OXC_OK;
+}
+// every buffer, in the order given: non-null, then aligned to 8 bytes, then large enough; then no output shares a byte with another buffer
+inline oxc_status check_sky_buffers(oxc_ctx* ctx, const char* entry, std::initializer_list<SkyBuffer> buffers) {
+  for (const SkyBuffer& s : buffers) {
+    if (!s.b.dptr) return bad_arg(ctx, entry, s.name, " must not be null");
+    if (reinterpret_cast<uintptr_t>(s.b.dptr) & 7u) return bad_arg(ctx, entry, s.name, " must be aligned to 8 bytes");
+    if (s.b.bytes < s.bytes) return bad_arg(ctx, entry, s.name, " is smaller than its extent");
+  }
+  for (const SkyBuffer& s : buffers) {
+    if (!s.output) continue;
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(s.b.dptr);
+    for (const SkyBuffer& o : buffers) {
+      const uintptr_t olo = reinterpret_cast<uintptr_t>(o.b.dptr);
+      if (&o != &s && ByteSpan{lo, lo + (uintptr_t)s.bytes}.overlaps({olo, olo + (uintptr_t)o.bytes})) return bad_arg(ctx, entry, s.name, " must not overlap ", o.name);
+    }
+  }
+  return OXC_OK;
+}
+
 // The counting instantiation's counters for this call, zeroed on `s`: `bytes` of them, allocated by the first counting call (never inside
 // a capture).  nullptr while the pass is not counting.
 inline oxc_status arm_counters(oxc_ctx* ctx, const char* entry, const char* malloc_label, oxc_ctx::PassCounters& pc, size_t bytes, hipStream_t s, uint32_t** out) {

@@ -645,6 +645,27 @@ struct PbrApplyArgs {
   float env[3], sky_color[3];
 };
 void launch_pbr_apply(const PbrApplyArgs& a, hipStream_t s);
+// the atmosphere branch (oxc_apply_pbr_atmosphere): `g` as above without stats, env and sky_color; the four sky images and what of the rule
+// depends on the call alone, evaluated once on the host by pbr_atmosphere_constants() in the binary32 operations the header states
+struct PbrAtmosphereArgs {
+  PbrApplyArgs g;
+  const uint2* transmittance;  // [th][tw] u16x4
+  const uint2* sky_view;       // [vh][vw]
+  const uint2* aerial;         // [ad][ah][aw]
+  const uint2* cube;           // [6][cube_size][cube_size]
+  uint32_t tw, th, vw, vh, aw, ah, ad, cube_size;
+  float planet_radius, atmos_radius;
+  float h_atmos, eye_altitude, beta, zenith_horizon_angle;  // AtmosphereConstants, from camera_position.y
+  float min_altitude;                                       // planet_radius + 0.001f
+  float sun_cos_theta, horizon_darkening;                   // dot(L, up); smoothstep(-0.1f, 0.3f, sun_cos_theta)
+  float min_cos;                                            // draw_sun: the cos rule at (1.0f * PI) / 180.0f
+  float aerial_depth;                                       // f32(aerial_perspective_lut_size.z)
+  float inv_per_slice_depth, inv_aerial_depth;              // 1.0f / (lut.x / lut.z), 1.0f / lut.z
+  float near_depth_fade_out;                                // 1.0f / 0.001f
+  float aerial_start_km, aerial_exposure;
+};
+void pbr_atmosphere_constants(const oxc_atmosphere& atm, PbrAtmosphereArgs& a);  // fills everything below `cube` but the AtmosphereConstants; reads a.g.sun
+void launch_pbr_apply_atmosphere(const PbrAtmosphereArgs& a, hipStream_t s);
 // oxcull_eye_adaptation.hip: the luminance histogram of the lit HDR image and the exposure it gives (oxc_apply_eye_adaptation)
 struct EyeAdaptationArgs {
   const void* src;       // `pixels` texels in one run: u32 (B10G11R11, format 0) or u16x4 (R16G16B16A16 Sfloat, format 1)

@@ -312,4 +312,76 @@ OXC_DEV float acos_rule(float x) {
   return __builtin_fabsf(x) <= 1.0f ? r : __builtin_nanf("");
 }
 
+// ---- what the sky passes (oxcull_atmosphere.hip) and the atmosphere branch of apply_pbr (oxcull_pbr_apply.hip) share ------------------------------
+OXC_DEV float dot3v(const V3& a, const V3& b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+OXC_DEV V3 crossv(const V3& a, const V3& b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+OXC_DEV float safe_sqrt(float x) { return __builtin_sqrtf(fmaxf(0.0f, x)); }
+
+// com::ray_sphere_intersect_nearest (common/math.slang:104-138); `value` is 0.0 where the Slang's Optional is none
+struct Hit {
+  bool has;
+  float value;
+};
+OXC_DEV Hit intersect_nearest(const V3& o, const V3& d, float radius) {
+  const float a = dot3v(d, d), b = 2.0f * dot3v(d, o), c = dot3v(o, o) - radius * radius;
+  const float delta = b * b - (4.0f * a) * c;
+  if (delta < 0.0f) return {false, 0.0f};
+  const float sq = __builtin_sqrtf(delta), den = 2.0f * a;
+  const float s0 = (-b + -1.0f * sq) / den, s1 = (-b + sq) / den;
+  if (s0 < 0.0f && s1 < 0.0f) return {false, 0.0f};
+  if (s0 < 0.0f) return {true, fmaxf(0.0f, s1)};
+  if (s1 < 0.0f) return {true, fmaxf(0.0f, s0)};
+  return {true, fmaxf(0.0f, fminf(s0, s1))};
+}
+
+// SampleLevel(LinearSamplerClamped, uv, 0).rgb of a w x h RGBA16F LUT: the manual bilinear of the oxc_apply_bloom block, clamp mode
+OXC_DEV V3 sample_rgb(const uint2* lut, uint32_t w, uint32_t h, float u, float v) {
+  const Axis ax = axis_at<false>(u, (float)w, (int)w - 1), ay = axis_at<false>(v, (float)h, (int)h - 1);
+  const size_t r0 = (size_t)ay.i0 * w, r1 = (size_t)ay.i1 * w;
+  const V3 t00 = load_rgba<1>(lut, r0 + ax.i0).c, t10 = load_rgba<1>(lut, r0 + ax.i1).c;
+  const V3 t01 = load_rgba<1>(lut, r1 + ax.i0).c, t11 = load_rgba<1>(lut, r1 + ax.i1).c;
+  return lerp3(lerp3(t00, t10, ax.f), lerp3(t01, t11, ax.f), ay.f);
+}
+
+// ... with its alpha: the same bilinear on all four channels
+OXC_DEV Texel sample_rgba(const uint2* lut, uint32_t w, uint32_t h, float u, float v) {
+  const Axis ax = axis_at<false>(u, (float)w, (int)w - 1), ay = axis_at<false>(v, (float)h, (int)h - 1);
+  const size_t r0 = (size_t)ay.i0 * w, r1 = (size_t)ay.i1 * w;
+  const Texel t00 = load_rgba<1>(lut, r0 + ax.i0), t10 = load_rgba<1>(lut, r0 + ax.i1);
+  const Texel t01 = load_rgba<1>(lut, r1 + ax.i0), t11 = load_rgba<1>(lut, r1 + ax.i1);
+  return {lerp3(lerp3(t00.c, t10.c, ax.f), lerp3(t01.c, t11.c, ax.f), ay.f), lerp_f(lerp_f(t00.a, t10.a, ax.f), lerp_f(t01.a, t11.a, ax.f), ay.f)};
+}
+
+// transmittance_params_to_lut_uv (sky.slang:15-29) at (h, mu) and the sample there: step 3 of the sky LUT block; h_atmos the host constant H
+OXC_DEV V3 transmittance_sample(const uint2* lut, uint32_t w, uint32_t hgt, float planet_radius, float atmos_radius, float h_atmos, float h, float mu) {
+  const float rho = safe_sqrt(h * h - planet_radius * planet_radius);
+  const float discriminant = (h * h) * (mu * mu - 1.0f) + atmos_radius * atmos_radius;
+  const float d = fmaxf(0.0f, -h * mu + safe_sqrt(discriminant));
+  const float d_min = atmos_radius - h, d_max = rho + h_atmos;
+  return sample_rgb(lut, w, hgt, (d - d_min) / (d_max - d_min), rho / h_atmos);
+}
+
+// sky_view_params_to_lut_uv (sky.slang:39-67) with the host constants zenith_horizon_angle and beta: step 14 of oxc_generate_sky_ibl
+OXC_DEV void sky_view_lut_uv(float zha, float beta, uint32_t w, uint32_t hgt, bool intersect_planet, float view_zenith_cos_angle, float lx, float ly, float& u, float& v) {
+  const float view_zenith_angle = acos_rule(view_zenith_cos_angle);
+  float uy;
+  if (!intersect_planet) {
+    float coord = view_zenith_angle / zha;
+    coord = 1.0f - coord;
+    coord = safe_sqrt(coord);
+    coord = 1.0f - coord;
+    uy = coord * 0.5f;
+  } else {
+    float coord = (view_zenith_angle - zha) / beta;
+    coord = safe_sqrt(coord);
+    uy = coord * 0.5f + 0.5f;
+  }
+  const float pi = 3.1415926535897932384626433832795f;
+  const float theta = atan2_rule(-ly, -lx);
+  const float ux = (theta + pi) / (2.0f * pi);
+  const float fw = (float)w, fh = (float)hgt;
+  u = (ux + 0.5f / fw) * (fw / (fw + 1.0f));
+  v = (uy + 0.5f / fh) * (fh / (fh + 1.0f));
+}
+
 }  // namespace oxc

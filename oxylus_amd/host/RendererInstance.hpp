@@ -129,9 +129,14 @@ using ContactShadowsContext = oxc_contact_shadows_context;
 // the normal image, the Hilbert index table, the three caller-owned intermediates and the R16F ambient_occlusion_attachment.
 using AmbientOcclusionContext = oxc_ambient_occlusion_context;
 
-// What apply_pbr reads (RendererInstance.hpp:310-325 of the reference, without bindless_set and the four sky LUTs of the atmosphere branch):
-// the depth, the four G-buffer images of decode_visbuffer as linear buffers, the ambient occlusion and the two R32F shadow terms.
+// What apply_pbr reads (RendererInstance.hpp:310-325 of the reference, without bindless_set): the depth, the four G-buffer images of
+// decode_visbuffer as linear buffers, the ambient occlusion, the two R32F shadow terms and, for the atmosphere branch, the four sky images
+// generate_sky_luts, draw_atmosphere and generate_sky_ibl wrote (the AtmosphereContext's buffers; unread without HasAtmosphere).
 struct PBRContext {
+  Buffer sky_transmittance_lut_attachment = {};
+  Buffer sky_aerial_perspective_lut_attachment = {};
+  Buffer sky_view_lut_attachment = {};
+  Buffer sky_cubemap_attachment = {};
   ImageAttachment depth_attachment = {};
   Buffer albedo_attachment = {};
   Buffer normal_attachment = {};
@@ -410,10 +415,41 @@ public:
     context.struct_size = sizeof context;
     check(oxc_generate_ambient_occlusion(ctx_, &context, stream_));
   }
-  // RendererInstance::apply_pbr (Passes/PBR.cpp:313-534), the no-atmosphere branch (pipeline pbr_apply_no_atmos): the lit HDR colour of every
-  // pixel into dst_attachment -- B10G11R11 UfloatPack32 (u32 per pixel), or R16G16B16A16 Sfloat (u16x4 per pixel) with TransparentBackground in
-  // gpu_scene_flags (RendererInstance.cpp:545-546).  HasAtmosphere in gpu_scene_flags is refused.  Rules: include/oxcull.h, oxc_apply_pbr.
+  // RendererInstance::apply_pbr (Passes/PBR.cpp:313-534): the lit HDR colour of every pixel into dst_attachment -- B10G11R11 UfloatPack32 (u32
+  // per pixel), or R16G16B16A16 Sfloat (u16x4 per pixel) with TransparentBackground in gpu_scene_flags (RendererInstance.cpp:545-546).  It
+  // dispatches on HasAtmosphere as PBR.cpp:318 does: with the flag the atmosphere branch (pipeline pbr_apply) from `atmosphere`,
+  // directional_light, camera, the context's four sky images and the 32-texel cube; without it the no-atmosphere branch (pbr_apply_no_atmos)
+  // with sky_data.  Rules: include/oxcull.h, oxc_apply_pbr_atmosphere and oxc_apply_pbr.
   auto apply_pbr(PBRContext& context, Buffer dst_attachment) -> Buffer {
+    if (gpu_scene_flags & OXC_SCENE_HAS_ATMOSPHERE) {
+      oxc_pbr_atmosphere_context c = {};
+      c.struct_size = sizeof c;
+      c.width = context.depth_attachment.width;
+      c.height = context.depth_attachment.height;
+      c.scene_flags = gpu_scene_flags;
+      c.light_count = static_cast<uint32_t>(prepared_frame.lights_buffer.bytes / 64u);
+      for (int i = 0; i < 16; i++) c.inv_projection_view[i] = camera.inv_projection_view[i];
+      for (int i = 0; i < 3; i++) c.camera_position[i] = camera.position[i], c.sun_dir[i] = directional_light.direction[i];
+      c.sun_intensity = directional_light.intensity;
+      c.atmosphere = atmosphere;
+      c.cube_size = 32;
+      c.depth_attachment = context.depth_attachment;
+      c.albedo_attachment = context.albedo_attachment;
+      c.normal_attachment = context.normal_attachment;
+      c.emissive_attachment = context.emissive_attachment;
+      c.metallic_roughness_occlusion_attachment = context.metallic_roughness_occlusion_attachment;
+      c.ambient_occlusion_attachment = context.ambient_occlusion_attachment;
+      c.resolved_shadows_attachment = context.resolved_shadows_attachment;
+      c.contact_shadows_attachment = context.contact_shadows_attachment;
+      c.lights_buffer = prepared_frame.lights_buffer;
+      c.sky_transmittance_lut = context.sky_transmittance_lut_attachment;
+      c.sky_view_lut = context.sky_view_lut_attachment;
+      c.sky_aerial_perspective_lut = context.sky_aerial_perspective_lut_attachment;
+      c.sky_cubemap = context.sky_cubemap_attachment;
+      c.final_attachment = dst_attachment;
+      check(oxc_apply_pbr_atmosphere(ctx_, &c, stream_));
+      return dst_attachment;
+    }
     oxc_pbr_context c = {};
     c.struct_size = sizeof c;
     c.width = context.depth_attachment.width;

@@ -596,6 +596,38 @@ class SkyIblContext(C.Structure):
     ]
 
 
+class PbrAtmosphereContext(C.Structure):
+    _c_name_ = "oxc_pbr_atmosphere_context"
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("scene_flags", C.c_uint32),
+        ("light_count", C.c_uint32),
+        ("inv_projection_view", C.c_float * 16),
+        ("camera_position", C.c_float * 3),
+        ("sun_dir", C.c_float * 3),
+        ("sun_intensity", C.c_float),
+        ("atmosphere", Atmosphere),
+        ("cube_size", C.c_uint32),
+        ("_pad", C.c_uint32),
+        ("depth_attachment", Image),
+        ("albedo_attachment", Buffer),
+        ("normal_attachment", Buffer),
+        ("emissive_attachment", Buffer),
+        ("metallic_roughness_occlusion_attachment", Buffer),
+        ("ambient_occlusion_attachment", Buffer),
+        ("resolved_shadows_attachment", Image),
+        ("contact_shadows_attachment", Image),
+        ("lights_buffer", Buffer),
+        ("sky_transmittance_lut", Buffer),
+        ("sky_view_lut", Buffer),
+        ("sky_aerial_perspective_lut", Buffer),
+        ("sky_cubemap", Buffer),
+        ("final_attachment", Buffer),
+    ]
+
+
 class MeshBuildDesc(C.Structure):
     _c_name_ = "oxc_mesh_build_desc"
     _fields_ = [("struct_size", C.c_uint32), ("vertex_count", C.c_uint32), ("index_count", C.c_uint32), ("max_lods", C.c_uint32), ("max_vertices", C.c_uint32),
@@ -660,6 +692,7 @@ PROTOTYPES = {
     "oxc_generate_sky_luts": (_status, [_vp, _P(SkyLutContext), _vp]),
     "oxc_draw_atmosphere": (_status, [_vp, _P(AtmosphereContext), _vp]),
     "oxc_generate_sky_ibl": (_status, [_vp, _P(SkyIblContext), _vp]),
+    "oxc_apply_pbr_atmosphere": (_status, [_vp, _P(PbrAtmosphereContext), _vp]),
     "oxc_draw_physical_pages": (_status, [_vp, _P(PreparedFrame), _P(VsmDrawContext), _vp]),
     "oxc_debug_vsm_draw_stats": _stats,
     "oxc_resolve_shadowmap": (_status, [_vp, _P(ShadowResolveContext), _vp]),

@@ -706,6 +706,59 @@ class SkyIblContext(Marshalled):
 
 
 @dataclass
+class PBRAtmosphereContext(Marshalled):
+    """oxc_pbr_atmosphere_context: the atmosphere branch of RendererInstance::apply_pbr (Passes/PBR.cpp:318-434, pbr_apply).  `create` takes the
+    G-buffer, the shadow terms, the lights and the flags from a PBRContext, the record, the transmittance, sky-view and aerial LUTs, the sun and
+    the camera from the AtmosphereContext they were drawn with, and the cube and its size from the SkyIblContext -- every tensor is shared --
+    and allocates the output in the format the flags pick.  The Sky record and base_ambient_color of the PBRContext are not read."""
+    _ctype = L.PbrAtmosphereContext
+    _derived = {"width": "depth_attachment.width", "height": "depth_attachment.height", "sky_transmittance_lut": "sky_transmittance_lut_attachment",
+                "sky_view_lut": "sky_view_lut_attachment", "sky_aerial_perspective_lut": "sky_aerial_perspective_lut_attachment",
+                "sky_cubemap": "sky_cubemap_attachment"}
+    _leave = ("_pad",)
+    depth_attachment: ImageAttachment
+    albedo_attachment: torch.Tensor
+    normal_attachment: torch.Tensor
+    emissive_attachment: torch.Tensor
+    metallic_roughness_occlusion_attachment: torch.Tensor
+    ambient_occlusion_attachment: torch.Tensor
+    resolved_shadows_attachment: Optional[ImageAttachment]  # R32F, read with HasDirectionalLight
+    contact_shadows_attachment: Optional[ImageAttachment]   # R32F, read with HasContactShadows
+    final_attachment: torch.Tensor                          # out
+    scene_flags: int
+    inv_projection_view: list
+    camera_position: tuple
+    sun_dir: tuple
+    sun_intensity: float
+    atmosphere: Atmosphere
+    sky_transmittance_lut_attachment: torch.Tensor          # in: int16 [H, W, 4]
+    sky_view_lut_attachment: torch.Tensor                   # in: int16 [H, W, 4]
+    sky_aerial_perspective_lut_attachment: torch.Tensor     # in: int16 [D, H, W, 4]
+    sky_cubemap_attachment: torch.Tensor                    # in: int16 [6, cube_size, cube_size, 4]
+    cube_size: int = 32
+    lights_buffer: Optional[torch.Tensor] = None
+    light_count: int = 0
+
+    @staticmethod
+    def create(pbr_context: PBRContext, atmosphere_context: AtmosphereContext, sky_ibl_context: SkyIblContext, **settings) -> "PBRAtmosphereContext":
+        p, a, i = pbr_context, atmosphere_context, sky_ibl_context
+        values = dict(scene_flags=p.scene_flags, inv_projection_view=list(a.camera_inv_projection_view), camera_position=tuple(a.camera_position),
+                      sun_dir=tuple(a.sun_dir), sun_intensity=float(a.sun_intensity), atmosphere=a.atmosphere, cube_size=int(i.cube_size),
+                      lights_buffer=p.lights_buffer, light_count=p.light_count)
+        values.update(settings)
+        d = p.depth_attachment
+        if int(values["scene_flags"]) & L.SCENE_TRANSPARENT_BACKGROUND:
+            out = torch.zeros((d.height, d.width, 4), dtype=torch.int16, device=d.data.device)
+        else:
+            out = torch.zeros((d.height, d.width), dtype=torch.int32, device=d.data.device)
+        return PBRAtmosphereContext(d, p.albedo_attachment, p.normal_attachment, p.emissive_attachment, p.metallic_roughness_occlusion_attachment,
+                                    p.ambient_occlusion_attachment, p.resolved_shadows_attachment, p.contact_shadows_attachment, out,
+                                    sky_transmittance_lut_attachment=a.sky_transmittance_lut_attachment, sky_view_lut_attachment=a.sky_view_lut_attachment,
+                                    sky_aerial_perspective_lut_attachment=a.sky_aerial_perspective_lut_attachment,
+                                    sky_cubemap_attachment=i.sky_cubemap_attachment, **values)
+
+
+@dataclass
 class VisbufferDecodeContext(Marshalled):
     """oxc_decode_context: RendererInstance::decode_visbuffer (Passes/DrawGeometry.cpp:192-274), the geometry and material-factor half of
     visbuffer_decode.slang.  `create` takes the visbuffer and the depth as oxc_draw_visbuffer resolved them, the matrix they were drawn with and
@@ -984,8 +1037,15 @@ class RendererInstance:
 
     def apply_pbr(self, context: PBRContext, stream=None):
         """Passes/PBR.cpp:313-534, the no-atmosphere branch (pbr_apply_no_atmos): per pixel the G-buffer, the ambient occlusion, the two shadow
-        terms, the sun and the point / spot lights become the lit HDR colour in `context.final_attachment` (include/oxcull.h, oxc_apply_pbr)."""
+        terms, the sun and the point / spot lights become the lit HDR colour in `context.final_attachment` (include/oxcull.h, oxc_apply_pbr).
+        L.SCENE_HAS_ATMOSPHERE in the flags is refused: that branch is apply_pbr_atmosphere."""
         self._call("oxc_apply_pbr", context, stream)
+
+    def apply_pbr_atmosphere(self, context: PBRAtmosphereContext, stream=None):
+        """Passes/PBR.cpp:318-434, the atmosphere branch (pbr_apply): apply_pbr's G-buffer, shadow terms and lights under the sun's colour from
+        the transmittance LUT, the sky cube as the ambient term, aerial perspective on lit pixels, and the sky-view LUT with the sun disc on
+        empty ones, one launch (include/oxcull.h, oxc_apply_pbr_atmosphere).  After generate_sky_luts, draw_atmosphere and generate_sky_ibl."""
+        self._call("oxc_apply_pbr_atmosphere", context, stream)
 
     def apply_eye_adaptation(self, context: EyeAdaptationContext, delta_time: float = 0.0, stream=None):
         """Passes/PostProcess.cpp:7-77: the 256-bin log-luminance histogram of `context.final_attachment` into `context.histogram_buffer` and
