@@ -1,70 +1,62 @@
-// oxcull_abi_cull.cpp -- the cull path of liboxcull.so's C ABI: the scratch arena and the counter-slot ring, the HiZ build, the cull
-// calls (oxc_cull_geometry, its batched form) with their async-triangle and share_pass_tests bookkeeping, terrain.
+// oxcull_abi_cull.cpp -- the cull path of liboxcull.so's C ABI: the two scratch arenas (each laid out by one function, walked once for
+// its size and once to bind its pointers) and the counter-slot ring, the HiZ build, the cull calls -- oxc_cull_geometry and its batched
+// form, each a sequence of named steps -- with their async-triangle and share_pass_tests bookkeeping, terrain.
 #include "oxcull_host.hpp"
 
 namespace {
 constexpr uint32_t kMaxPackedInstances = 1u << 24;  // MESHLET_INSTANCE_ID_BITS, visbuffer.slang:9-10
+
+// The lane arena for M mesh instances, N meshlets and Vw views (use_hpb): every part once, in arena order.  Returns the arena's size; with
+// `base` (the allocation) it also binds the lane's pointers (Carve::take).
+uint64_t lay_out_lane(oxc_ctx::Lane& L, uint32_t M, uint32_t N, uint32_t Vw, void* base) {
+  const uint32_t m_chunks = cdiv(N, 64u), t_chunks = cdiv(N, kTriChunk);  // meshlet counts: per wave step, >= 64 meshlets
+  Carve carve{0, static_cast<char*>(base)};
+  carve.take(L.cache, (uint64_t)M * sizeof(InstCache));
+  carve.take(L.cache_alt, (uint64_t)M * sizeof(InstCache));
+  carve.take(L.view_cache, (uint64_t)M * Vw * sizeof(InstCache) + 64);
+  carve.take(L.mesh_counts, (uint64_t)M * 4);
+  carve.take(L.mesh_offsets, (uint64_t)M * 4);
+  carve.take(L.bits, (uint64_t)cdiv(N, 64) * 8);
+  carve.take(L.m_chunk_counts, (uint64_t)m_chunks * 4);
+  carve.take(L.m_supers, (uint64_t)cdiv(m_chunks, kChunksPerSuper) * 4 * kSuperStride);
+  carve.take(L.m_tickets, (uint64_t)kTicketCounters * 4 * kSuperStride);
+  carve.take(L.m_supers_late, (uint64_t)cdiv(m_chunks, kChunksPerSuper) * 4 * kSuperStride);
+  carve.take(L.m_tickets_late, (uint64_t)kTicketCounters * 4 * kSuperStride);
+  carve.take(L.camera_test_bits, (uint64_t)cdiv(N, 64) * 8);
+  carve.take(L.step_info, (uint64_t)m_chunks * 8);
+  carve.take(L.tri_masks, (uint64_t)N * 16);  // one 64-bit pass mask per visible meshlet (two in wide mode)
+  carve.take(L.t_chunk_counts, (uint64_t)t_chunks * 4);
+  carve.take(L.t_supers, (uint64_t)cdiv(t_chunks, kChunksPerSuper) * 4 * kSuperStride);
+  carve.take(L.t_supers_alt, (uint64_t)cdiv(t_chunks, kChunksPerSuper) * 4 * kSuperStride);
+  return carve.off;
+}
+
 }  // namespace
 
 // Grows the lane's scratch arena when the call needs more than it holds: device sync + free + malloc (documented in
 // include/oxcull.h; oxc_reserve up front avoids it).  Never during stream capture: `s` = the calling stream.
+// (Not grow_scratch: what goes with the old arena is forgotten between the sync and the free, and a failed malloc zeroes the capacities.)
 oxc_status ensure_capacity(oxc_ctx* ctx, uint32_t mesh_instances, uint32_t meshlets, uint32_t views, uint32_t lane_index, hipStream_t s) {
   oxc_ctx::Lane* L = &ctx->lane[lane_index];
   if (mesh_instances <= L->cap_mesh_instances && meshlets <= L->cap_meshlets && views <= L->cap_views && L->arena) return OXC_OK;
   if (stream_is_capturing(s))
     return fail(ctx, OXC_INVALID_ARG, "scratch memory must grow but the stream is being captured: call oxc_reserve (or one un-captured call of this size) first");
   const uint32_t Vw = std::max(views, L->cap_views);
-  uint32_t M = std::max(std::max(mesh_instances, L->cap_mesh_instances), 1u);
-  uint32_t N = std::max(std::max(meshlets, L->cap_meshlets), 1u);
-  const uint32_t m_chunks = cdiv(N, 64u), t_chunks = cdiv(N, kTriChunk);  // meshlet counts: per wave step, >= 64 meshlets
-  Carve carve;
-  const uint64_t o_cache = carve((uint64_t)M * sizeof(InstCache));
-  const uint64_t o_cache_alt = carve((uint64_t)M * sizeof(InstCache));
-  const uint64_t o_vcache = carve((uint64_t)M * Vw * sizeof(InstCache) + 64);
-  const uint64_t o_counts = carve((uint64_t)M * 4);
-  const uint64_t o_offsets = carve((uint64_t)M * 4);
-  const uint64_t o_bits = carve((uint64_t)cdiv(N, 64) * 8);
-  const uint64_t o_mcc = carve((uint64_t)m_chunks * 4);
-  const uint64_t o_msup = carve((uint64_t)cdiv(m_chunks, kChunksPerSuper) * 4 * kSuperStride);
-  const uint64_t o_mtick = carve((uint64_t)kTicketCounters * 4 * kSuperStride);
-  const uint64_t o_msup_late = carve((uint64_t)cdiv(m_chunks, kChunksPerSuper) * 4 * kSuperStride);
-  const uint64_t o_mtick_late = carve((uint64_t)kTicketCounters * 4 * kSuperStride);
-  const uint64_t o_fb = carve((uint64_t)cdiv(N, 64) * 8);
-  const uint64_t o_si = carve((uint64_t)m_chunks * 8);
-  const uint64_t o_tm = carve((uint64_t)N * 16);  // one 64-bit pass mask per visible meshlet (two in wide mode)
-  const uint64_t o_tcc = carve((uint64_t)t_chunks * 4);
-  const uint64_t o_tsup = carve((uint64_t)cdiv(t_chunks, kChunksPerSuper) * 4 * kSuperStride);
-  const uint64_t o_tsup_alt = carve((uint64_t)cdiv(t_chunks, kChunksPerSuper) * 4 * kSuperStride);
+  const uint32_t M = std::max(std::max(mesh_instances, L->cap_mesh_instances), 1u);
+  const uint32_t N = std::max(std::max(meshlets, L->cap_meshlets), 1u);
+  const uint64_t bytes = lay_out_lane(*L, M, N, Vw, nullptr);
   OXC_HIP(ctx, hipDeviceSynchronize());  // in-flight work (the side stream's included) may still use the old arena
   for (auto& tp : ctx->tri) tp.valid = false;
   if (lane_index == 0) ctx->shared.valid = false;  // the early call's bits go with the arena
   if (L->arena) OXC_HIP(ctx, hipFree(L->arena));
   L->arena = nullptr;
-  hipError_t e = hipMalloc(&L->arena, carve.off);
+  hipError_t e = hipMalloc(&L->arena, bytes);
   if (e != hipSuccess) {
     L->cap_mesh_instances = L->cap_meshlets = 0;
     return fail(ctx, OXC_OUT_OF_MEMORY, "hipMalloc(scratch arena)", e);
   }
-  L->arena_bytes = carve.off;
-  char* b = static_cast<char*>(L->arena);
-  L->cache = reinterpret_cast<InstCache*>(b + o_cache);
-  L->cache_alt = reinterpret_cast<InstCache*>(b + o_cache_alt);
-  L->view_cache = reinterpret_cast<InstCache*>(b + o_vcache);
+  L->arena_bytes = lay_out_lane(*L, M, N, Vw, L->arena);
   L->cap_views = Vw;
-  L->mesh_counts = reinterpret_cast<uint32_t*>(b + o_counts);
-  L->mesh_offsets = reinterpret_cast<uint32_t*>(b + o_offsets);
-  L->bits = reinterpret_cast<uint64_t*>(b + o_bits);
-  L->m_chunk_counts = reinterpret_cast<uint32_t*>(b + o_mcc);
-  L->m_supers = reinterpret_cast<uint32_t*>(b + o_msup);
-  L->m_tickets = reinterpret_cast<uint32_t*>(b + o_mtick);
-  L->m_supers_late = reinterpret_cast<uint32_t*>(b + o_msup_late);
-  L->m_tickets_late = reinterpret_cast<uint32_t*>(b + o_mtick_late);
-  L->camera_test_bits = reinterpret_cast<uint64_t*>(b + o_fb);
-  L->step_info = reinterpret_cast<uint2*>(b + o_si);
-  L->tri_masks = reinterpret_cast<uint64_t*>(b + o_tm);
-  L->t_chunk_counts = reinterpret_cast<uint32_t*>(b + o_tcc);
-  L->t_supers = reinterpret_cast<uint32_t*>(b + o_tsup);
-  L->t_supers_alt = reinterpret_cast<uint32_t*>(b + o_tsup_alt);
   L->cap_mesh_instances = M;
   L->cap_meshlets = N;
   return OXC_OK;
@@ -156,6 +148,12 @@ struct CullLists {
   uint32_t *vis, *meshlets_cmd;
   uint32_t n_host;
 };
+
+// The caller's context is told where a call leaves its triangle-stage and draw commands: in the call's slot
+void name_cmd_buffers(oxc_cull_geometry_context* c, uint32_t* slot) {
+  c->cull_triangles_cmd_buffer = {slot + SLOT_TRI_CMD, 12};
+  c->draw_geometry_cmd_buffer = {slot + SLOT_DRAW_CMD, 20};
+}
 
 // With init_cull_meshes the counters are those of `slot`, and the caller's context is told; otherwise that context names them.
 CullLists resolve_lists(oxc_ctx* ctx, oxc_cull_geometry_context* c, uint32_t* slot, uint32_t N) {
@@ -565,6 +563,281 @@ oxc_status triangle_stage(const CullCall& k) {
   return OXC_OK;
 }
 
+// ---- oxc_cull_geometry_batch in steps ----
+// What the steps of one batched call hand to each other
+struct BatchCall {
+  oxc_ctx* ctx;
+  const oxc_prepared_frame* frames;
+  oxc_cull_geometry_context* contexts;
+  hipStream_t s;
+  uint32_t count;
+  CallInfo ci[kMaxBatch] = {};
+  BatchCore cores[kMaxBatch] = {};  // every field once; k_prepare_batch rebuilds the seven stage blocks from it on the device (expand_batch_core)
+  // plan_batch: one launch per stage serves all elements / they are views of one scene / from one camera position / with implicit_meshlet_instances;
+  // batch_meshes_stage: the MeshletInstance expansion runs on the side stream
+  bool fusable = false, multiview = false, same_pos = false, implicit_lists = false, mv_expand_async = false;
+  uint32_t g_prep = 1, g_expand = 1, g_test = 1, g_emit = 1, g_ttest = 1, g_temit = 1;  // grid.x of each stage: the largest any element asks for
+  uint32_t cap = 0, max_grid = 0;
+};
+
+// Can the elements share their launches, and in which form?  Enqueues nothing.
+oxc_status plan_batch(BatchCall& b) {
+  const oxc_prepared_frame* frames = b.frames;
+  const oxc_cull_geometry_context* contexts = b.contexts;
+  const CallInfo* ci = b.ci;
+  const uint32_t count = b.count;
+  b.fusable = count > 1 && count <= kMaxBatch;
+  for (uint32_t e = 0; b.fusable && e < count; e++) {
+    OXC_TRY(check_call(b.ctx, &frames[e], &contexts[e], b.ci[e]));
+    const oxc_cull_geometry_context& c = contexts[e];
+    b.fusable = !c.use_hiz && !c.use_hpb && !c.wide_triangle_index && !c.small_triangle_cull && !ci[e].late && ci[e].stages == ci[0].stages && ci[e].do_meshes == ci[0].do_meshes &&
+                (c.init_cull_meshes != 0) == (contexts[0].init_cull_meshes != 0);
+  }
+  if (!b.fusable) return OXC_OK;
+  // Several VIEWS of one scene (every element runs cull_meshes + cull_meshlets over the same meshes / transforms with its own camera --
+  // shadow cascades, BASELINE configs[4]): the meshlet stage then runs once over the scene for all views (k_mv_test) instead of
+  // once per view over that view's list.  Same outputs, element by element.
+  b.multiview = ci[0].do_meshes && ci[0].do_meshlets && ci[0].M > 0;
+  b.same_pos = true;
+  for (uint32_t e = 1; b.multiview && e < count; e++) {
+    b.multiview = ci[e].M == ci[0].M && frames[e].meshes_buffer.dptr == frames[0].meshes_buffer.dptr &&
+                  frames[e].transforms_world_buffer.dptr == frames[0].transforms_world_buffer.dptr && contexts[e].cull_flags == contexts[0].cull_flags;
+    b.same_pos = b.same_pos && std::memcmp(contexts[e].cull_camera.position, contexts[0].cull_camera.position, 12) == 0;
+  }
+  // implicit_meshlet_instances: all elements or none, and only where nothing reads the records -- the multi-view meshlet stage
+  uint32_t n_implicit = 0;
+  for (uint32_t e = 0; e < count; e++) n_implicit += contexts[e].implicit_meshlet_instances ? 1u : 0u;
+  if (n_implicit && (n_implicit != count || !b.multiview || ci[0].do_tris))
+    return fail(b.ctx, OXC_INVALID_ARG, "cull_geometry_batch: implicit_meshlet_instances must be set on every element of a multi-view batch (same scene, cull_meshes in every element, no triangle stage)");
+  b.implicit_lists = n_implicit != 0;
+  return OXC_OK;
+}
+
+// The elements one call at a time: a batch that cannot be fused, or whose prepare launch was refused
+oxc_status cull_one_by_one(const BatchCall& b) {
+  for (uint32_t e = 0; e < b.count; e++) OXC_TRY(oxc_cull_geometry(b.ctx, &b.frames[e], &b.contexts[e], b.s));
+  return OXC_OK;
+}
+
+// The device copy of the argument blocks, allocated by the context's first batched call
+oxc_status ensure_batch_block(oxc_ctx* ctx, hipStream_t s) {
+  if (ctx->batch_dev) return OXC_OK;
+  if (stream_is_capturing(s))
+    return fail(ctx, OXC_INVALID_ARG, "cull_geometry_batch: the first batched call allocates its argument block; make one un-captured call first");
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&ctx->batch_dev), sizeof(BatchElem) * kMaxBatch);
+  if (e != hipSuccess) return fail(ctx, OXC_OUT_OF_MEMORY, "hipMalloc(batch argument block)", e);
+  OXC_HIP(ctx, hipMemset(ctx->batch_dev, 0, sizeof(BatchElem) * kMaxBatch));  // fields no plain-pipeline block uses stay 0
+  // The fill runs on the NULL stream; `s` is usually a non-blocking stream, i.e. NOT ordered behind it.  Round 4 found the race the hard way:
+  // in a fresh process the first hipMemset loads its kernel lazily, k_prepare_batch (on `s`) wrote the argument blocks first, the late fill
+  // zeroed them and the next kernel dereferenced null -- "memory access fault on address (nil)" in 2 of ~25 bench runs, only on slow boxes.
+  OXC_HIP(ctx, hipDeviceSynchronize());
+  return OXC_OK;
+}
+
+// Element e: its counter slot and lists, its core, and what it asks of the stages' grids
+void fill_batch_core(BatchCall& b, uint32_t e) {
+  const oxc_prepared_frame* f = &b.frames[e];
+  oxc_cull_geometry_context* c = &b.contexts[e];
+  oxc_ctx::Lane& L = b.ctx->lane[e];
+  const uint32_t M = b.ci[e].M, N = b.ci[e].N, max_grid = b.max_grid;
+  uint32_t* slot = next_slot(b.ctx);
+  const CullLists lists = resolve_lists(b.ctx, c, slot, N);
+  name_cmd_buffers(c, slot);
+  const uint32_t m_chunks = cdiv(std::max(N, 1u), kMeshletChunk), t_chunks = cdiv(std::max(N, 1u), kTriChunk);
+
+  BatchCore& k = b.cores[e];
+  k.meshes = static_cast<const GpuMesh*>(f->meshes_buffer.dptr);
+  k.transforms = static_cast<const float*>(f->transforms_world_buffer.dptr);
+  k.mesh_instances = static_cast<GpuMeshInstance*>(f->mesh_instances_buffer.dptr);
+  k.meshlet_instances = static_cast<GpuMeshletInstance*>(f->meshlet_instances_buffer.dptr);
+  k.visible_out = static_cast<uint32_t*>(f->visible_meshlet_instances_indices_buffer.dptr);
+  k.reordered_out = static_cast<uint32_t*>(f->reordered_indices_buffer.dptr);
+  k.cache = L.cache;
+  k.view_cache = L.view_cache;
+  k.mesh_counts = L.mesh_counts;
+  k.mesh_offsets = L.mesh_offsets;
+  k.bits = L.bits;
+  k.m_chunk_counts = L.m_chunk_counts;
+  k.m_supers = L.m_supers;
+  k.tri_masks = L.tri_masks;
+  k.t_chunk_counts = L.t_chunk_counts;
+  k.t_supers = L.t_supers;
+  k.slot = slot;
+  k.vis = lists.vis;
+  k.meshlets_cmd = lists.meshlets_cmd;
+  k.n_supers_meshlets = cdiv(cdiv(std::max(N, 1u), 64u), kChunksPerSuper);
+  k.n_supers_tris = cdiv(t_chunks, kChunksPerSuper);
+  k.mesh_instance_count = M;
+  k.cull_flags = c->cull_flags;
+  k.do_cull_meshes = b.ci[0].do_meshes ? 1u : 0u;
+  k.init_vis = c->init_cull_meshes ? 1u : 0u;
+  k.n_host = lists.n_host;
+  k.n_cap = N;
+  k.count_meshlets = 64u * kPlainGroups;
+  k.cam = c->cull_camera;
+  b.g_prep = std::max(b.g_prep, std::min(cdiv(std::max(std::max(M * 8u, k.n_supers_tris), 1u), 256), max_grid));
+  b.g_expand = std::max(b.g_expand, std::max(std::min(cdiv(M, 4), max_grid), 1u));
+  b.g_test = std::max(b.g_test, std::min(m_chunks, max_grid));
+  b.g_emit = std::max(b.g_emit, std::min(cdiv(std::max(N, 1u), kMeshletSpan), max_grid));
+  b.g_ttest = std::max(b.g_ttest, std::min(t_chunks, max_grid));
+  b.g_temit = std::max(b.g_temit, std::min(cdiv(std::max(N, 1u), kTriSpan), max_grid));
+}
+
+// One launch hands over all element cores: a 4.5 KB kernarg segment.  A runtime that refuses a segment of that
+// size fails the launch synchronously (false); nothing has been enqueued then and the elements are culled one by one.
+bool launch_batch_prepare(const BatchCall& b) {
+  static_assert(kBatchPerPrepare == kMaxBatch, "one prepare launch per batched call");
+  BatchBlob blob;
+  std::memset(&blob, 0, sizeof blob);
+  blob.count = b.count;
+  blob.first = 0;
+  std::memcpy(blob.core, b.cores, sizeof(BatchCore) * b.count);
+  KernelTimer t(b.ctx, OXC_K_PREPARE, b.s);
+  launch_prepare_batch(blob, b.ctx->batch_dev, b.g_prep, b.s);
+  return hipGetLastError() == hipSuccess;
+}
+
+// --- cull_meshes of every element: the scan, then the MeshletInstance expansion -- in order on `s`, or (multi-view, nothing of the call reads the
+// records) on the context's lowest-priority side stream, forked from `s` here and joined at the end of the call (multiview_meshlet_stage)
+oxc_status batch_meshes_stage(BatchCall& b) {
+  oxc_ctx* ctx = b.ctx;
+  {
+    KernelTimer t(ctx, OXC_K_MESHES_SCAN, b.s);
+    launch_scan_batch(ctx->batch_dev, b.count, b.s);
+  }
+  if (b.implicit_lists) return OXC_OK;  // (implicit: the records have no reader in this call; the runs are written by k_mv_group)
+  // Round 5: in the multi-view form nothing of this call reads the MeshletInstance records (k_mv_test walks the instances' bounds), so their
+  // expansion -- a pure store stream, 466 MB per 16 views of a 10 M-meshlet scene -- runs on the context's side stream beside the
+  // latency-bound set-up launches and the VALU-bound test of the meshlet stage, and is joined at the end of the call (fork / join by
+  // events, capturable like async_triangles).  A triangle stage in the call reads the records: in order then.
+  const bool on_side = b.mv_expand_async = b.multiview && b.ci[0].do_meshlets && !b.ci[0].do_tris && ctx->mv_expand_async != 0;
+  // (Round 6 measured the fork behind the meshlet stage's three set-up launches instead -- they are chains of dependent loads and take 78 us next to
+  //  the store stream against 33 us alone -- : 0.2600 against 0.2615 ms per 16 views on one box, 0.2616 against 0.2568 on another; the test and the
+  //  emit then share the machine with the whole store stream.  The fork stays here.)
+  hipStream_t es = b.s;
+  if (on_side) {
+    if (!ctx->mv_side) {  // its own stream, at the lowest priority: the store stream yields wave slots to the meshlet stage's launches
+      int lo = 0, hi = 0;
+      OXC_HIP(ctx, hipDeviceGetStreamPriorityRange(&lo, &hi));
+      OXC_HIP(ctx, hipStreamCreateWithPriority(&ctx->mv_side, hipStreamNonBlocking, lo));
+    }
+    if (!ctx->mv_fork) OXC_HIP(ctx, hipEventCreateWithFlags(&ctx->mv_fork, hipEventDisableTiming));
+    if (!ctx->mv_join) OXC_HIP(ctx, hipEventCreateWithFlags(&ctx->mv_join, hipEventDisableTiming));
+    OXC_HIP(ctx, hipEventRecord(ctx->mv_fork, b.s));
+    OXC_HIP(ctx, hipStreamWaitEvent(ctx->mv_side, ctx->mv_fork, 0));
+    es = ctx->mv_side;
+  }
+  {
+    KernelTimer t(ctx, OXC_K_MESHES_EXPAND, es);
+    // (beside the meshlet stage the expansion takes mv_expand_async blocks per CU, not every wave slot: the small set-up launches queue behind it otherwise)
+    const uint32_t ecap = on_side ? std::max(1u, ctx->num_cus * ctx->mv_expand_async / b.count) : b.cap;
+    launch_expand_batch(ctx->batch_dev, b.count, std::min(b.g_expand, ecap), es);
+  }
+  if (on_side) OXC_HIP(ctx, hipEventRecord(ctx->mv_join, es));
+  return OXC_OK;
+}
+
+// The multi-view arena for `count` views of Mv mesh instances, view e with at most vchunks_max[e] chunks: view table | groups [M][views] |
+// chunks per instance, their prefix [M] | totals | step list | per view: vchunks, vchunk0 [M], ballots [chunks][4], counts, idbase [chunks],
+// supers, totals.  Every part once, in arena order; returns the arena's size and, with `base` (the allocation), binds `ma` and the views.
+uint64_t lay_out_multiview(MvArgs& ma, MvView* views, uint32_t Mv, uint32_t count, const uint32_t* vchunks_max, void* base) {
+  uint64_t steps_max = 0;
+  for (uint32_t e = 0; e < count; e++) steps_max += vchunks_max[e];
+  Carve carve{0, static_cast<char*>(base)};
+  carve.take(ma.dev, sizeof(MvView) * kMaxBatch);
+  carve.take(ma.groups, (uint64_t)Mv * count * sizeof(MvGroup));
+  carve.take(ma.grp_chunks, (uint64_t)Mv * 4);
+  carve.take(ma.inst_step0, (uint64_t)Mv * 4);
+  carve.take(ma.step_total, 64);
+  carve.take(ma.steps, steps_max * 8);
+  for (uint32_t e = 0; e < count; e++) {
+    MvView& w = views[e];
+    carve.take(w.vchunks, (uint64_t)Mv * 4);
+    carve.take(w.vchunk0, (uint64_t)Mv * 4);
+    carve.take(w.bits, (uint64_t)vchunks_max[e] * 32);
+    carve.take(w.counts, (uint64_t)vchunks_max[e] * 4);
+    carve.take(w.idbase, (uint64_t)vchunks_max[e] * 4);
+    carve.take(w.supers, (uint64_t)cdiv(vchunks_max[e], kChunksPerSuper) * 4 * kSuperStride);
+    carve.take(w.scan_total, 64);
+  }
+  return carve.off;
+}
+
+// --- meshlet stage of the views of one scene: one pass over the scene for all views (plan_batch)
+oxc_status multiview_meshlet_stage(const BatchCall& b) {
+  oxc_ctx* ctx = b.ctx;
+  const uint32_t count = b.count, Mv = b.ci[0].M;
+  uint32_t vchunks_max[kMaxBatch];
+  uint32_t max_vchunks = 0;
+  for (uint32_t e = 0; e < count; e++) {
+    vchunks_max[e] = cdiv(std::max(b.ci[e].N, 1u), 256u) + Mv;  // sum over instances of ceil(count / 256) <= N / 256 + M
+    max_vchunks = std::max(max_vchunks, vchunks_max[e]);
+  }
+  MvArgs ma;
+  std::memset(&ma, 0, sizeof ma);
+  MvBlob blob;
+  std::memset(&blob, 0, sizeof blob);
+  const uint64_t bytes = lay_out_multiview(ma, blob.v, Mv, count, vchunks_max, nullptr);
+  OXC_TRY(grow_scratch(ctx, b.s, ctx->mv_arena, ctx->mv_arena_bytes, bytes, bytes,
+                       "cull_geometry_batch: the multi-view scratch must grow but the stream is being captured; make one un-captured call of this size first",
+                       "hipMalloc(multi-view scratch)"));
+  lay_out_multiview(ma, blob.v, Mv, count, vchunks_max, ctx->mv_arena);
+  ma.views = count;
+  ma.M = Mv;
+  ma.same_pos = b.same_pos ? 1u : 0u;
+  ma.tickets = ctx->lane[0].m_tickets;
+  for (uint32_t e = 0; e < count; e++) {
+    MvView& w = blob.v[e];
+    oxc_ctx::Lane& L = ctx->lane[e];
+    w.rows = L.cache;
+    w.mesh_counts = L.mesh_counts;
+    w.mesh_offsets = L.mesh_offsets;
+    w.out = static_cast<uint32_t*>(b.frames[e].visible_meshlet_instances_indices_buffer.dptr);
+    w.runs = static_cast<uint32_t*>(b.contexts[e].meshlet_instance_runs_buffer.dptr);
+    w.tri_cmd = b.cores[e].slot + SLOT_TRI_CMD;
+    w.n_cap = b.ci[e].N;
+    w.n_supers = cdiv(vchunks_max[e], kChunksPerSuper);
+    std::memcpy(w.cam_pos, b.contexts[e].cull_camera.position, 12);
+  }
+  {
+    KernelTimer t(ctx, OXC_K_MULTIVIEW_SETUP, b.s);
+    launch_mv_setup(ma, blob, std::max(1u, std::min(cdiv(Mv, 16u), b.max_grid)), b.s);  // 16 lanes per mesh instance
+  }
+  {
+    KernelTimer t(ctx, OXC_K_MESHLETS_TEST, b.s);
+    launch_mv_test(ma, ctx->num_cus, b.s);
+  }
+  {
+    KernelTimer t(ctx, OXC_K_MESHLETS_EMIT, b.s);
+    launch_mv_emit(ma, max_vchunks, b.max_grid, b.s);
+  }
+  if (b.mv_expand_async) OXC_HIP(ctx, hipStreamWaitEvent(b.s, ctx->mv_join, 0));  // join: the records are part of what the call leaves behind on `s`
+  return OXC_OK;
+}
+
+// --- the stages that run per element over its own list, grid.y = element: the meshlet stage (unless the multi-view one ran) and the triangle stage
+void plain_batch_stages(const BatchCall& b) {
+  oxc_ctx* ctx = b.ctx;
+  if (b.ci[0].do_meshlets && !b.multiview) {
+    {
+      KernelTimer t(ctx, OXC_K_MESHLETS_TEST, b.s);
+      // At 64 VGPRs (8 waves/SIMD) the test kernel wants every block it can get: with 16 x 1M meshlets, blocks per element
+      // 384 -> 74.6 us, 512 -> 73.7, 768 -> 73.2, 1024 -> 70.7, 2048 -> 70.0 (>= 977 blocks: one 1024-meshlet step per block)
+      launch_meshlets_test_batch(ctx->batch_dev, b.count, b.g_test, b.s);
+    }
+    KernelTimer t(ctx, OXC_K_MESHLETS_EMIT, b.s);
+    launch_meshlets_emit_batch(ctx->batch_dev, b.count, std::min(b.g_emit, b.cap), b.s);
+  }
+  if (b.ci[0].do_tris) {
+    {
+      KernelTimer t(ctx, OXC_K_TRIANGLES_TEST, b.s);
+      launch_tris_test_batch(ctx->batch_dev, b.count, std::min(b.g_ttest, b.cap), b.s);
+    }
+    KernelTimer t(ctx, OXC_K_TRIANGLES_EMIT, b.s);
+    launch_tris_emit_batch(ctx->batch_dev, b.count, std::min(b.g_temit, b.cap), b.s);
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -643,8 +916,7 @@ oxc_status oxc_cull_geometry(oxc_ctx* ctx, const oxc_prepared_frame* f, oxc_cull
   k.share = plan_shared_tests(k, slot);
   k.tri_cmd = k.share.slot + SLOT_TRI_CMD;
   k.draw_cmd = k.share.slot + SLOT_DRAW_CMD;
-  c->cull_triangles_cmd_buffer = {k.tri_cmd, 12};
-  c->draw_geometry_cmd_buffer = {k.draw_cmd, 20};
+  name_cmd_buffers(c, k.share.slot);
 
   k.max_grid = ctx->num_cus * 8;
   k.m_chunks = cdiv(std::max(N, 1u), kMeshletChunk);
@@ -669,273 +941,23 @@ oxc_status oxc_cull_geometry_batch(oxc_ctx* ctx, uint32_t count, const oxc_prepa
   if (!ctx) return OXC_INVALID_ARG;
   if (count == 0) return OXC_OK;
   if (!frames || !contexts) return fail(ctx, OXC_INVALID_ARG, "cull_geometry_batch: null frames/contexts");
-  CallInfo ci[kMaxBatch];
-  bool fusable = count > 1 && count <= kMaxBatch;
-  for (uint32_t e = 0; fusable && e < count; e++) {
-    OXC_TRY(check_call(ctx, &frames[e], &contexts[e], ci[e]));
-    const oxc_cull_geometry_context& c = contexts[e];
-    fusable = !c.use_hiz && !c.use_hpb && !c.wide_triangle_index && !c.small_triangle_cull && !ci[e].late && ci[e].stages == ci[0].stages && ci[e].do_meshes == ci[0].do_meshes &&
-              (c.init_cull_meshes != 0) == (contexts[0].init_cull_meshes != 0);
-  }
-  if (!fusable) {
-    for (uint32_t e = 0; e < count; e++) OXC_TRY(oxc_cull_geometry(ctx, &frames[e], &contexts[e], hip_stream));
-    return OXC_OK;
-  }
-  // Several VIEWS of one scene (every element runs cull_meshes + cull_meshlets over the same meshes / transforms with its own camera --
-  // shadow cascades, BASELINE configs[4]): the meshlet stage then runs once over the scene for all views (k_mv_test) instead of
-  // once per view over that view's list.  Same outputs, element by element.
-  bool multiview = ci[0].do_meshes && ci[0].do_meshlets && ci[0].M > 0;
-  bool same_pos = true;
-  for (uint32_t e = 1; multiview && e < count; e++) {
-    multiview = ci[e].M == ci[0].M && frames[e].meshes_buffer.dptr == frames[0].meshes_buffer.dptr &&
-                frames[e].transforms_world_buffer.dptr == frames[0].transforms_world_buffer.dptr && contexts[e].cull_flags == contexts[0].cull_flags;
-    same_pos = same_pos && std::memcmp(contexts[e].cull_camera.position, contexts[0].cull_camera.position, 12) == 0;
-  }
-  // implicit_meshlet_instances: all elements or none, and only where nothing reads the records -- the multi-view meshlet stage
-  uint32_t n_implicit = 0;
-  for (uint32_t e = 0; e < count; e++) n_implicit += contexts[e].implicit_meshlet_instances ? 1u : 0u;
-  if (n_implicit && (n_implicit != count || !multiview || ci[0].do_tris))
-    return fail(ctx, OXC_INVALID_ARG, "cull_geometry_batch: implicit_meshlet_instances must be set on every element of a multi-view batch (same scene, cull_meshes in every element, no triangle stage)");
-  const bool implicit_lists = n_implicit != 0;
+  BatchCall b = {ctx, frames, contexts, static_cast<hipStream_t>(hip_stream), count};
+  OXC_TRY(plan_batch(b));
+  if (!b.fusable) return cull_one_by_one(b);
   OXC_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t s = static_cast<hipStream_t>(hip_stream);
   ctx->shared.valid = false;  // (share_pass_tests: a batch may rebuild any list)
-  for (uint32_t e = 0; e < count; e++) OXC_TRY(ensure_capacity(ctx, ci[e].M, ci[e].N, 0, e, s));
+  for (uint32_t e = 0; e < count; e++) OXC_TRY(ensure_capacity(ctx, b.ci[e].M, b.ci[e].N, 0, e, b.s));
   OXC_ORDER(ctx, hip_stream);
-  OXC_JOIN(ctx, s);  // the batched call uses lane 0's scratch in order on hip_stream
-  if (!ctx->batch_dev) {
-    if (stream_is_capturing(s))
-      return fail(ctx, OXC_INVALID_ARG, "cull_geometry_batch: the first batched call allocates its argument block; make one un-captured call first");
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&ctx->batch_dev), sizeof(BatchElem) * kMaxBatch);
-    if (e != hipSuccess) return fail(ctx, OXC_OUT_OF_MEMORY, "hipMalloc(batch argument block)", e);
-    OXC_HIP(ctx, hipMemset(ctx->batch_dev, 0, sizeof(BatchElem) * kMaxBatch));  // fields no plain-pipeline block uses stay 0
-    // The fill runs on the NULL stream; `s` is usually a non-blocking stream, i.e. NOT ordered behind it.  Round 4 found the race the hard way:
-    // in a fresh process the first hipMemset loads its kernel lazily, k_prepare_batch (on `s`) wrote the argument blocks first, the late fill
-    // zeroed them and the next kernel dereferenced null -- "memory access fault on address (nil)" in 2 of ~25 bench runs, only on slow boxes.
-    OXC_HIP(ctx, hipDeviceSynchronize());
-  }
-  const uint32_t max_grid = ctx->num_cus * 8;
-  const bool do_meshes = ci[0].do_meshes, do_meshlets = ci[0].do_meshlets, do_tris = ci[0].do_tris;
-  bool mv_expand_async = false;
-  // The MeshletInstance expansion of a batched call: in order on `s`, or (multi-view, nothing of the call reads the records) on the context's
-  // lowest-priority side stream, forked from `s` where this is called and joined at the end of the call.
-  auto launch_mv_expand = [&](uint32_t count_, uint32_t g_expand_, uint32_t cap_, bool on_side) -> oxc_status {
-    hipStream_t es = s;
-    if (on_side) {
-      if (!ctx->mv_side) {  // its own stream, at the lowest priority: the store stream yields wave slots to the meshlet stage's launches
-        int lo = 0, hi = 0;
-        OXC_HIP(ctx, hipDeviceGetStreamPriorityRange(&lo, &hi));
-        OXC_HIP(ctx, hipStreamCreateWithPriority(&ctx->mv_side, hipStreamNonBlocking, lo));
-      }
-      if (!ctx->mv_fork) OXC_HIP(ctx, hipEventCreateWithFlags(&ctx->mv_fork, hipEventDisableTiming));
-      if (!ctx->mv_join) OXC_HIP(ctx, hipEventCreateWithFlags(&ctx->mv_join, hipEventDisableTiming));
-      OXC_HIP(ctx, hipEventRecord(ctx->mv_fork, s));
-      OXC_HIP(ctx, hipStreamWaitEvent(ctx->mv_side, ctx->mv_fork, 0));
-      es = ctx->mv_side;
-    }
-    {
-      KernelTimer t(ctx, OXC_K_MESHES_EXPAND, es);
-      // (beside the meshlet stage the expansion takes mv_expand_async blocks per CU, not every wave slot: the small set-up launches queue behind it otherwise)
-      const uint32_t ecap = on_side ? std::max(1u, ctx->num_cus * ctx->mv_expand_async / count_) : cap_;
-      launch_expand_batch(ctx->batch_dev, count_, std::min(g_expand_, ecap), es);
-    }
-    if (on_side) OXC_HIP(ctx, hipEventRecord(ctx->mv_join, es));
-    return OXC_OK;
-  };
-  BatchCore cores[kMaxBatch];
-  std::memset(cores, 0, sizeof cores);
-  uint32_t g_prep = 1, g_expand = 1, g_test = 1, g_emit = 1, g_ttest = 1, g_temit = 1;
-  for (uint32_t e = 0; e < count; e++) {
-    const oxc_prepared_frame* f = &frames[e];
-    oxc_cull_geometry_context* c = &contexts[e];
-    oxc_ctx::Lane& L = ctx->lane[e];
-    const uint32_t M = ci[e].M, N = ci[e].N;
-    uint32_t* slot = next_slot(ctx);
-    const CullLists lists = resolve_lists(ctx, c, slot, N);
-    c->cull_triangles_cmd_buffer = {slot + SLOT_TRI_CMD, 12};
-    c->draw_geometry_cmd_buffer = {slot + SLOT_DRAW_CMD, 20};
-    const uint32_t m_chunks = cdiv(std::max(N, 1u), kMeshletChunk), t_chunks = cdiv(std::max(N, 1u), kTriChunk);
-
-    // every field once; k_prepare_batch rebuilds the seven stage blocks from it on the device (expand_batch_core)
-    BatchCore& k = cores[e];
-    k.meshes = static_cast<const GpuMesh*>(f->meshes_buffer.dptr);
-    k.transforms = static_cast<const float*>(f->transforms_world_buffer.dptr);
-    k.mesh_instances = static_cast<GpuMeshInstance*>(f->mesh_instances_buffer.dptr);
-    k.meshlet_instances = static_cast<GpuMeshletInstance*>(f->meshlet_instances_buffer.dptr);
-    k.visible_out = static_cast<uint32_t*>(f->visible_meshlet_instances_indices_buffer.dptr);
-    k.reordered_out = static_cast<uint32_t*>(f->reordered_indices_buffer.dptr);
-    k.cache = L.cache;
-    k.view_cache = L.view_cache;
-    k.mesh_counts = L.mesh_counts;
-    k.mesh_offsets = L.mesh_offsets;
-    k.bits = L.bits;
-    k.m_chunk_counts = L.m_chunk_counts;
-    k.m_supers = L.m_supers;
-    k.tri_masks = L.tri_masks;
-    k.t_chunk_counts = L.t_chunk_counts;
-    k.t_supers = L.t_supers;
-    k.slot = slot;
-    k.vis = lists.vis;
-    k.meshlets_cmd = lists.meshlets_cmd;
-    k.n_supers_meshlets = cdiv(cdiv(std::max(N, 1u), 64u), kChunksPerSuper);
-    k.n_supers_tris = cdiv(t_chunks, kChunksPerSuper);
-    k.mesh_instance_count = M;
-    k.cull_flags = c->cull_flags;
-    k.do_cull_meshes = do_meshes ? 1u : 0u;
-    k.init_vis = c->init_cull_meshes ? 1u : 0u;
-    k.n_host = lists.n_host;
-    k.n_cap = N;
-    k.count_meshlets = 64u * kPlainGroups;
-    k.cam = c->cull_camera;
-    g_prep = std::max(g_prep, std::min(cdiv(std::max(std::max(M * 8u, k.n_supers_tris), 1u), 256), max_grid));
-    g_expand = std::max(g_expand, std::max(std::min(cdiv(M, 4), max_grid), 1u));
-    g_test = std::max(g_test, std::min(m_chunks, max_grid));
-    g_emit = std::max(g_emit, std::min(cdiv(std::max(N, 1u), kMeshletSpan), max_grid));
-    g_ttest = std::max(g_ttest, std::min(t_chunks, max_grid));
-    g_temit = std::max(g_temit, std::min(cdiv(std::max(N, 1u), kTriSpan), max_grid));
-  }
-  // grid.y = count; grid.x cap per element for the small stages (the meshlet test kernel takes its full grid, below)
-  const uint32_t cap = std::max(max_grid / count, ctx->num_cus * 2);
-  {
-    // One launch hands over all element cores: a 4.5 KB kernarg segment.  A runtime that refuses a segment of that
-    // size fails the launch synchronously; nothing has been enqueued then and the elements are culled one by one.
-    static_assert(kBatchPerPrepare == kMaxBatch, "one prepare launch per batched call");
-    BatchBlob blob;
-    std::memset(&blob, 0, sizeof blob);
-    blob.count = count;
-    blob.first = 0;
-    std::memcpy(blob.core, cores, sizeof(BatchCore) * count);
-    hipError_t launch_err;
-    {
-      KernelTimer t(ctx, OXC_K_PREPARE, s);
-      launch_prepare_batch(blob, ctx->batch_dev, g_prep, s);
-      launch_err = hipGetLastError();
-    }
-    if (launch_err != hipSuccess) {
-      for (uint32_t e = 0; e < count; e++) OXC_TRY(oxc_cull_geometry(ctx, &frames[e], &contexts[e], hip_stream));
-      return OXC_OK;
-    }
-  }
-  if (do_meshes) {
-    {
-      KernelTimer t(ctx, OXC_K_MESHES_SCAN, s);
-      launch_scan_batch(ctx->batch_dev, count, s);
-    }
-    if (!implicit_lists) {  // (implicit: the records have no reader in this call; the runs are written by k_mv_group)
-      // Round 5: in the multi-view form nothing of this call reads the MeshletInstance records (k_mv_test walks the instances' bounds), so their
-      // expansion -- a pure store stream, 466 MB per 16 views of a 10 M-meshlet scene -- runs on the context's side stream beside the
-      // latency-bound set-up launches and the VALU-bound test of the meshlet stage, and is joined at the end of the call (fork / join by
-      // events, capturable like async_triangles).  A triangle stage in the call reads the records: in order then.
-      mv_expand_async = multiview && do_meshlets && !do_tris && ctx->mv_expand_async != 0;
-      // (Round 6 measured the fork behind the meshlet stage's three set-up launches instead -- they are chains of dependent loads and take 78 us next to
-      //  the store stream against 33 us alone -- : 0.2600 against 0.2615 ms per 16 views on one box, 0.2616 against 0.2568 on another; the test and the
-      //  emit then share the machine with the whole store stream.  The fork stays here.)
-      OXC_TRY(launch_mv_expand(count, g_expand, cap, mv_expand_async));
-    }
-  }
-  if (do_meshlets && multiview) {
-    const uint32_t Mv = ci[0].M;
-    // scratch: view table | groups [M][views] | chunks per instance, their prefix [M] | totals | step list | per view: vchunks, vchunk0 [M],
-    // ballots [chunks][4], counts, idbase [chunks], supers, totals
-    Carve carve;
-    uint32_t vchunks_max[kMaxBatch];
-    uint64_t steps_max = 0;
-    uint32_t max_vchunks = 0;
-    for (uint32_t e = 0; e < count; e++) {
-      vchunks_max[e] = cdiv(std::max(ci[e].N, 1u), 256u) + Mv;  // sum over instances of ceil(count / 256) <= N / 256 + M
-      steps_max += vchunks_max[e];
-      max_vchunks = std::max(max_vchunks, vchunks_max[e]);
-    }
-    const uint64_t o_table = carve(sizeof(MvView) * kMaxBatch);
-    const uint64_t o_groups = carve((uint64_t)Mv * count * sizeof(MvGroup));
-    const uint64_t o_gch = carve((uint64_t)Mv * 4), o_st0 = carve((uint64_t)Mv * 4), o_tot = carve(64);
-    const uint64_t o_steps = carve(steps_max * 8);
-    uint64_t o_vch[kMaxBatch], o_vc0[kMaxBatch], o_bits[kMaxBatch], o_cnt[kMaxBatch], o_idb[kMaxBatch], o_sup[kMaxBatch], o_vtot[kMaxBatch];
-    for (uint32_t e = 0; e < count; e++) {
-      o_vch[e] = carve((uint64_t)Mv * 4);
-      o_vc0[e] = carve((uint64_t)Mv * 4);
-      o_bits[e] = carve((uint64_t)vchunks_max[e] * 32);
-      o_cnt[e] = carve((uint64_t)vchunks_max[e] * 4);
-      o_idb[e] = carve((uint64_t)vchunks_max[e] * 4);
-      o_sup[e] = carve((uint64_t)cdiv(vchunks_max[e], kChunksPerSuper) * 4 * kSuperStride);
-      o_vtot[e] = carve(64);
-    }
-    if (carve.off > ctx->mv_arena_bytes) {
-      if (stream_is_capturing(s)) return fail(ctx, OXC_INVALID_ARG, "cull_geometry_batch: the multi-view scratch must grow but the stream is being captured; make one un-captured call of this size first");
-      OXC_HIP(ctx, hipDeviceSynchronize());
-      if (ctx->mv_arena) OXC_HIP(ctx, hipFree(ctx->mv_arena));
-      ctx->mv_arena = nullptr;
-      ctx->mv_arena_bytes = 0;
-      hipError_t me = hipMalloc(&ctx->mv_arena, carve.off);
-      if (me != hipSuccess) return fail(ctx, OXC_OUT_OF_MEMORY, "hipMalloc(multi-view scratch)", me);
-      ctx->mv_arena_bytes = carve.off;
-    }
-    char* const mb = static_cast<char*>(ctx->mv_arena);
-    MvArgs ma;
-    std::memset(&ma, 0, sizeof ma);
-    ma.views = count;
-    ma.M = Mv;
-    ma.same_pos = same_pos ? 1u : 0u;
-    ma.dev = reinterpret_cast<MvView*>(mb + o_table);
-    ma.groups = reinterpret_cast<MvGroup*>(mb + o_groups);
-    ma.grp_chunks = reinterpret_cast<uint32_t*>(mb + o_gch);
-    ma.inst_step0 = reinterpret_cast<uint32_t*>(mb + o_st0);
-    ma.step_total = reinterpret_cast<uint32_t*>(mb + o_tot);
-    ma.steps = reinterpret_cast<uint2*>(mb + o_steps);
-    ma.tickets = ctx->lane[0].m_tickets;
-    MvBlob blob;
-    std::memset(&blob, 0, sizeof blob);
-    for (uint32_t e = 0; e < count; e++) {
-      MvView& w = blob.v[e];
-      oxc_ctx::Lane& L = ctx->lane[e];
-      w.rows = L.cache;
-      w.mesh_counts = L.mesh_counts;
-      w.mesh_offsets = L.mesh_offsets;
-      w.vchunks = reinterpret_cast<uint32_t*>(mb + o_vch[e]);
-      w.vchunk0 = reinterpret_cast<uint32_t*>(mb + o_vc0[e]);
-      w.bits = reinterpret_cast<uint64_t*>(mb + o_bits[e]);
-      w.counts = reinterpret_cast<uint32_t*>(mb + o_cnt[e]);
-      w.idbase = reinterpret_cast<uint32_t*>(mb + o_idb[e]);
-      w.supers = reinterpret_cast<uint32_t*>(mb + o_sup[e]);
-      w.scan_total = reinterpret_cast<uint32_t*>(mb + o_vtot[e]);
-      w.out = static_cast<uint32_t*>(frames[e].visible_meshlet_instances_indices_buffer.dptr);
-      w.runs = static_cast<uint32_t*>(contexts[e].meshlet_instance_runs_buffer.dptr);
-      w.tri_cmd = cores[e].slot + SLOT_TRI_CMD;
-      w.n_cap = ci[e].N;
-      w.n_supers = cdiv(vchunks_max[e], kChunksPerSuper);
-      std::memcpy(w.cam_pos, contexts[e].cull_camera.position, 12);
-    }
-    {
-      KernelTimer t(ctx, OXC_K_MULTIVIEW_SETUP, s);
-      launch_mv_setup(ma, blob, std::max(1u, std::min(cdiv(Mv, 16u), max_grid)), s);  // 16 lanes per mesh instance
-    }
-    {
-      KernelTimer t(ctx, OXC_K_MESHLETS_TEST, s);
-      launch_mv_test(ma, ctx->num_cus, s);
-    }
-    {
-      KernelTimer t(ctx, OXC_K_MESHLETS_EMIT, s);
-      launch_mv_emit(ma, max_vchunks, max_grid, s);
-    }
-    if (mv_expand_async) OXC_HIP(ctx, hipStreamWaitEvent(s, ctx->mv_join, 0));  // join: the records are part of what the call leaves behind on `s`
-  } else if (do_meshlets) {
-    {
-      KernelTimer t(ctx, OXC_K_MESHLETS_TEST, s);
-      // At 64 VGPRs (8 waves/SIMD) the test kernel wants every block it can get: with 16 x 1M meshlets, blocks per element
-      // 384 -> 74.6 us, 512 -> 73.7, 768 -> 73.2, 1024 -> 70.7, 2048 -> 70.0 (>= 977 blocks: one 1024-meshlet step per block)
-      launch_meshlets_test_batch(ctx->batch_dev, count, g_test, s);
-    }
-    KernelTimer t(ctx, OXC_K_MESHLETS_EMIT, s);
-    launch_meshlets_emit_batch(ctx->batch_dev, count, std::min(g_emit, cap), s);
-  }
-  if (do_tris) {
-    {
-      KernelTimer t(ctx, OXC_K_TRIANGLES_TEST, s);
-      launch_tris_test_batch(ctx->batch_dev, count, std::min(g_ttest, cap), s);
-    }
-    KernelTimer t(ctx, OXC_K_TRIANGLES_EMIT, s);
-    launch_tris_emit_batch(ctx->batch_dev, count, std::min(g_temit, cap), s);
-  }
+  OXC_JOIN(ctx, b.s);  // the batched call uses lane 0's scratch in order on hip_stream
+  OXC_TRY(ensure_batch_block(ctx, b.s));
+  b.max_grid = ctx->num_cus * 8;
+  for (uint32_t e = 0; e < count; e++) fill_batch_core(b, e);
+  // grid.y = count; grid.x cap per element for the small stages (the meshlet test kernel takes its full grid: plain_batch_stages)
+  b.cap = std::max(b.max_grid / count, ctx->num_cus * 2);
+  if (!launch_batch_prepare(b)) return cull_one_by_one(b);
+  if (b.ci[0].do_meshes) OXC_TRY(batch_meshes_stage(b));
+  if (b.ci[0].do_meshlets && b.multiview) OXC_TRY(multiview_meshlet_stage(b));
+  plain_batch_stages(b);
   OXC_HIP(ctx, hipGetLastError());
   return OXC_OK;
 }

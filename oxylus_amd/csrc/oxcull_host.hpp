@@ -26,12 +26,20 @@ inline uint32_t cdiv(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 inline uint64_t align_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
 
 // Lays out one scratch allocation: each call returns the offset of the next part, 256-byte aligned; `off` ends as the size of the whole.
+// take() states a part once for both uses of a layout: a layout function walked without `base` gives the size, and walked again with the
+// allocation as `base` it binds every field to its part.
 struct Carve {
   uint64_t off = 0;
+  char* base = nullptr;
   uint64_t operator()(uint64_t bytes) {
     const uint64_t o = off;
     off = align_up(off + bytes, 256);
     return o;
+  }
+  template <class T>
+  void take(T*& field, uint64_t bytes) {
+    const uint64_t o = (*this)(bytes);
+    if (base) field = reinterpret_cast<T*>(base + o);
   }
 };
 

@@ -377,6 +377,148 @@ def test_multiview_batch_with_the_triangle_stage(renderer, oracle_lib):
     assert emitted > 10_000
 
 
+# The branches of oxc_cull_geometry_batch the tests above do not take.  Everything a call leaves behind for one frame, cut to its counters:
+def _frame_outputs(renderer, frame, ctx):
+    c = renderer.read_counters(ctx)
+    out = {"counters": (c.total_visible_meshlet_instances, c.early_visible_meshlet_instances, c.late_visible_meshlet_instances, c.cull_meshlets_cmd_x,
+                        c.cull_triangles_cmd_x, c.draw_index_count),
+           "records": frame.meshlet_instances_buffer[:c.total_visible_meshlet_instances].cpu(),
+           "visible": frame.visible_meshlet_instances_indices_buffer[:c.cull_triangles_cmd_x].cpu(),
+           "lod": frame.scene.mesh_instances[:, 1].cpu(), "mask": frame.meshlet_instance_visibility_mask_buffer.cpu()}
+    if frame.reordered_indices_buffer is not None:
+        out["indices"] = frame.reordered_indices_buffer[:c.draw_index_count].cpu()
+    return out
+
+
+def _assert_outputs_equal(got, want, tag, keys=None):
+    for k in keys or want:
+        assert (got[k] == want[k]) if k == "counters" else torch.equal(got[k], want[k]), f"{tag}: {k} differs"
+
+
+def _view_frames(gpu, n, with_triangles):
+    import dataclasses
+
+    return [PreparedFrame.create(gpu if e == 0 else dataclasses.replace(gpu, mesh_instances=gpu.mesh_instances.clone()), with_triangles=with_triangles, expand=False)
+            for e in range(n)]
+
+
+def _views_batched_and_single(renderer, gpu, cams, stages):
+    """The views `cams` of one scene through one batched call, and through one single call each: two lists of _frame_outputs."""
+    flags, tri = L.CULL_TEST_FRUSTUM | L.CULL_SELECT_LOD, bool(stages & L.STAGE_TRIANGLES)
+    frames = _view_frames(gpu, len(cams), tri)
+    ctxs = [CullGeometryContext(init_cull_meshes=True, cull_flags=flags, cull_camera=cam, stages=stages) for cam in cams]
+    renderer.cull_geometry_batch(frames, ctxs)
+    batched = [_frame_outputs(renderer, f, c) for f, c in zip(frames, ctxs)]
+    single = []
+    for cam in cams:
+        renderer.prepared_frame = _view_frames(gpu, 2, tri)[1]
+        c1 = CullGeometryContext(init_cull_meshes=True, cull_flags=flags, cull_camera=cam, stages=stages)
+        renderer.cull_geometry(c1)
+        single.append(_frame_outputs(renderer, renderer.prepared_frame, c1))
+    return batched, single
+
+
+def test_batch_that_cannot_be_fused_equals_single_calls(renderer, oracle_lib):
+    """Three elements, the middle one an early HiZ call: the batch is not fusable and its elements are culled one by one -- every output and
+    counter is what three single calls leave."""
+    scenes = [make_scene(SceneSpec(n_mesh_instances=m, meshlets_per_mesh=k, lod_count=2, seed=0x0A1DE5 + 20 + i), "cuda") for i, (m, k) in enumerate([(40, 90), (24, 130), (7, 500)])]
+    hiz = ImageAttachment.hiz(128, 128, "cuda")
+    renderer.generate_hiz(MainGeometryContext(ImageAttachment.depth(make_depth(256, 256, 24, seed=7).cuda()), hiz))
+    g = torch.Generator().manual_seed(3)
+    masks = [torch.randint(-2**31, 2**31 - 1, ((s.n_meshlet_instances + 31) // 32,), generator=g, dtype=torch.int64).to(torch.int32).cuda() for s in scenes]
+
+    def frames_and_contexts():
+        frames = [PreparedFrame.create(s, expand=False) for s in scenes]
+        for f, m in zip(frames, masks):
+            f.meshlet_instance_visibility_mask_buffer.copy_(m)
+        return frames, [CullGeometryContext(init_cull_meshes=True, cull_flags=L.CULL_TEST_ALL, cull_camera=s.cull_camera(), use_hiz=(i == 1),
+                                            hiz_attachment=hiz if i == 1 else None) for i, s in enumerate(scenes)]
+
+    lods = [s.mesh_instances[:, 1].clone() for s in scenes]  # (cull_meshes writes lod_index into the scene the frames share)
+    frames, ctxs = frames_and_contexts()
+    renderer.cull_geometry_batch(frames, ctxs)
+    got = [_frame_outputs(renderer, f, c) for f, c in zip(frames, ctxs)]
+    for s, lod in zip(scenes, lods):
+        s.mesh_instances[:, 1] = lod
+    frames, ctxs = frames_and_contexts()
+    emitted = 0
+    for i, (f, c) in enumerate(zip(frames, ctxs)):
+        renderer.prepared_frame = f
+        renderer.cull_geometry(c)
+        want = _frame_outputs(renderer, f, c)
+        _assert_outputs_equal(got[i], want, f"element {i}")
+        emitted += want["counters"][5]
+        assert want["counters"][4] > 0, f"element {i} sees nothing"
+    assert emitted > 10_000
+
+
+def test_batch_implicit_list_rule_refuses_and_enqueues_nothing(renderer, oracle_lib):
+    """implicit_meshlet_instances on 2 of 3 views, and on all 3 of a batch with the triangle stage: OXC_INVALID_ARG with the rule's message.  The
+    valid implicit batch that follows on the same context equals single calls."""
+    gpu = make_scene(SceneSpec(n_mesh_instances=40, meshlets_per_mesh=120, lod_count=2, seed=0x0A1DE5 + 13, with_geometry=True), "cuda")
+    M, flags, cams = gpu.n_mesh_instances, L.CULL_TEST_FRUSTUM | L.CULL_SELECT_LOD, _cascade_cameras(gpu, 6)[3:]
+
+    def contexts(stages, implicit):
+        return [CullGeometryContext(init_cull_meshes=True, cull_flags=flags, cull_camera=cam, stages=stages, implicit_meshlet_instances=implicit(v),
+                                    meshlet_instance_runs_buffer=torch.full((M, 2), -1, dtype=torch.int32, device="cuda")) for v, cam in enumerate(cams)]
+
+    for stages, implicit, message in [
+            (L.STAGE_MESHES | L.STAGE_MESHLETS, lambda v: v != 1,
+             "cull_geometry_batch: implicit_meshlet_instances must be set on every element of a multi-view batch (same scene, cull_meshes in every element, no triangle stage)"),
+            (L.STAGE_ALL, lambda v: True, "cull_geometry: implicit_meshlet_instances needs meshlet_instance_runs_buffer, cull_meshes in the call and no triangle stage")]:
+        frames, ctxs = _view_frames(gpu, 3, True), contexts(stages, implicit)
+        with pytest.raises(L.OxcError) as ei:
+            renderer.cull_geometry_batch(frames, ctxs)
+        assert ei.value.status == L.OXC_INVALID_ARG and message in str(ei.value)
+        torch.cuda.synchronize()
+        for f, c in zip(frames, ctxs):  # nothing was written
+            assert int(f.visible_meshlet_instances_indices_buffer.abs().sum()) == 0 and int((c.meshlet_instance_runs_buffer != -1).sum()) == 0
+    frames, ctxs = _view_frames(gpu, 3, False), contexts(L.STAGE_MESHES | L.STAGE_MESHLETS, lambda v: True)
+    renderer.cull_geometry_batch(frames, ctxs)
+    got = [_frame_outputs(renderer, f, c) for f, c in zip(frames, ctxs)]
+    _, single = _views_batched_and_single(renderer, gpu, cams, L.STAGE_MESHES | L.STAGE_MESHLETS)
+    seen = 0
+    for v in range(3):
+        _assert_outputs_equal(got[v], single[v], f"view {v}", ["counters", "visible", "lod"])
+        count = ctxs[v].meshlet_instance_runs_buffer[:, 1].long()
+        want = single[v]["records"]  # the runs, expanded, are the records of the single call
+        assert torch.equal(torch.repeat_interleave(torch.arange(M, device="cuda"), count).cpu().to(torch.int32), want[:, 0]), f"view {v}: runs"
+        seen += want.shape[0]
+    assert seen > 3 * 256  # (the lists are not empty: more than a 256-meshlet chunk per view)
+
+
+def test_multiview_batches_that_grow_the_scratch_between_calls():
+    """One context: 2 views of a small scene, then 3 views of a larger one -- the lane arenas and the multi-view arena are re-allocated and
+    re-bound (the views' chunk arrays cross their 256-byte parts, the chunk count kChunksPerSuper = 64: 4 + 24 chunks per view, then 75 + 48) --,
+    then the small batch again inside the larger arena.  Every batch equals its single calls."""
+    r = RendererInstance(0)  # a fresh context: nothing allocated
+    try:
+        small = make_scene(SceneSpec(n_mesh_instances=24, meshlets_per_mesh=40, lod_count=1, seed=0x0A1DE5 + 14, with_geometry=False), "cuda")
+        large = make_scene(SceneSpec(n_mesh_instances=48, meshlets_per_mesh=400, lod_count=1, seed=0x0A1DE5 + 15, with_geometry=False), "cuda")
+        assert small.n_meshlet_instances == 960 and large.n_meshlet_instances == 19200
+        for tag, gpu, views in (("small", small, 2), ("large", large, 3), ("small again", small, 2)):
+            batched, single = _views_batched_and_single(r, gpu, _cascade_cameras(gpu, 6)[6 - views:], L.STAGE_MESHES | L.STAGE_MESHLETS)
+            for v in range(views):
+                _assert_outputs_equal(batched[v], single[v], f"{tag}, view {v}")
+            assert sum(s["counters"][4] for s in single) > 100, tag
+    finally:
+        r.close()
+
+
+def test_multiview_batch_expansion_on_the_side_stream_and_in_order(renderer, oracle_lib):
+    """Without a triangle stage the MeshletInstance expansion of a multi-view batch runs on the context's side stream, with one in order on the
+    caller's: both leave the same records (and visible lists), those of single calls."""
+    gpu = make_scene(SceneSpec(n_mesh_instances=60, meshlets_per_mesh=120, lod_count=2, seed=0x0A1DE5 + 16, with_geometry=True), "cuda")
+    cams = _cascade_cameras(gpu, 6)[3:]
+    side, single = _views_batched_and_single(renderer, gpu, cams, L.STAGE_MESHES | L.STAGE_MESHLETS)
+    in_order, single_tris = _views_batched_and_single(renderer, gpu, cams, L.STAGE_ALL)
+    for v in range(3):
+        _assert_outputs_equal(side[v], single[v], f"side stream, view {v}")
+        _assert_outputs_equal(in_order[v], single_tris[v], f"in order, view {v}")
+        _assert_outputs_equal(side[v], in_order[v], f"view {v}", ["records", "visible", "lod"])
+    assert sum(s["records"].shape[0] for s in single) > 3 * 256  # (the lists are not empty: more than a 256-meshlet chunk per view)
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # opt-in small-triangle cull (include/oxcull.h: oxc_cull_geometry_context::small_triangle_cull)
 # ------------------------------------------------------------------------------------------------------------------
