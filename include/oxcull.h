@@ -1788,6 +1788,148 @@ typedef struct oxc_pbr_atmosphere_context {
 
 oxc_status oxc_apply_pbr_atmosphere(oxc_ctx* ctx, const oxc_pbr_atmosphere_context* context, void* hip_stream);
 
+/* ---- the terrain maps: height, ridge, normal, splat and the per-patch min/max ---------------------------------------------------------------
+ * oxc_generate_terrain_maps is the three compute passes Terrain::bake (Scene/Terrain.cpp:406-461) runs over the whole map and
+ * RendererInstance::apply_terrain_brush (Passes/Terrain.cpp:134-156) runs again over a region: passes/terrain_generate.slang with terrain.slang,
+ * passes/terrain_derive.slang and passes/terrain_minmax.slang.  They produce what the terrain consumers read: the heightmap
+ * (terrain_visbuffer.slang), the normal and splat maps (terrain_decode.slang) and patch_minmax, the image oxc_cull_terrain takes.  `stages`
+ * selects them; the selected ones run in the order generate, derive, minmax on the stream, each seeing what the one before wrote.
+ * Images: linear row-major buffers, texel (x, y) at element y * resolution.x + x.  heightmap R16 Unorm (u16), ridgemap R16 Sfloat (u16 of
+ * binary16 bits), normalmap R16G16 Sfloat (u16 x 2, .x first), splatmap R8G8B8A8 Unorm (u32, .x in the low byte), height_edit R32 Sfloat,
+ * splat_edit R8G8B8A8 Unorm.  Stated deviation: patch_minmax, R16G16 Unorm in the reference, is here the RG32F oxc_image that
+ * oxc_terrain_context.patch_minmax_attachment takes (one level, patch (x, y) at float pair y * patch_count.x + x); each float is exactly
+ * what a load of the Unorm texel returns, f32(q) / 65535.0f, so the image goes to oxc_cull_terrain as it is.
+ * region: 16 bytes of GPU::TerrainRegion {texel_origin.xy, patch_origin.xy} in DEVICE memory, read by the kernels (the brush trace writes it
+ * on the GPU); a null buffer means both origins are zero, which is what bake passes.
+ * What a call writes: generate and derive the texels texel_origin + [0, roundup(dispatch_texels, 16)) clipped to resolution, minmax the patches
+ * patch_origin + [0, roundup(dispatch_patches, 8)) clipped to patch_count: the reference's whole work groups.  Every other byte of every
+ * image is left as it was.  origin + index is a u32 sum.  Stated deviation: an index beyond roundup(resolution, 16) (roundup(patch_count, 8))
+ * can land inside the map only by that sum wrapping past 2^32; such indices are not launched.
+ * Arithmetic: binary32, the expressions of the Slang left to right, one rounding per operation, no contraction, IEEE division and square
+ * root; every decimal literal is the binary32 nearest to it (0.3183099, 0.3678794, 0.06711056, 0.00583715, 0.01111, 1e-10, 0.6, TAU =
+ * 6.283185307179586476925286766559, ..).  Shared rules, the ones of the blocks above: saturate(x) = min(max(x, 0), 1) and clamp(x, lo, hi) =
+ * min(max(x, lo), hi) with fmin / fmax (a NaN gives the lower bound), max(a, b) = fmax, lerp(a, b, t) = a + (b - a) * t, frac(x) = x -
+ * floor(x), sign(x) = x > 0 ? 1 : x < 0 ? -1 : 0, smoothstep(e0, e1, x): s = saturate((x - e0) / (e1 - e0)), (s * s) * (3.0f - 2.0f * s);  a
+ * 2-D dot is a.x b.x + a.y b.y, a 3-D one (a.x b.x + a.y b.y) + a.z b.z, length = sqrt(dot(v, v)), normalize = v / length;  exp by the exp
+ * rule of oxc_apply_tonemap, pow by the pow rule of oxc_apply_pbr, (cos, sin) of a binary32 angle by the rule of oxc_generate_sky_ibl step 11
+ * (its binary64 turn reduction holds for every finite angle; a non-finite one gives NaN);  a binary16 store rounds to nearest even, keeps
+ * denormals and writes every NaN as 0x7E00; a binary16 load is exact;  unorm8(e) = u32(floor(saturate(e) * 255.0f + 0.5f)), unorm16(e) the
+ * same with 65535.0f, their loads f32(q) / 255.0f and f32(q) / 65535.0f;  f32(u32) rounds to nearest even;  seed + i wraps in u32.
+ * The host may evaluate what depends on the call alone, once, by the same binary32 operations (strength * scale, 1.0f / (scale *
+ * cell_scale), f32(resolution), 1.0f - normalization, height_amplitude * 0.6f, 8.0f * texel_world_size, the minmax scale).
+ * E = settings.erosion, G = settings (oxc_terrain_generate), D = oxc_terrain_derive.
+ *   T1. texel   texel = texel_origin + thread;  any(texel >= resolution) writes nothing.  uv = (f32(texel) + 0.5f) / f32(resolution);  p = uv *
+ *              G.domain_size.
+ *   T2. hash2(x, seed)   k = (0.3183099f, 0.3678794f);  so = (f32(seed) * 0.06711056f, f32(seed) * 0.00583715f);  q = ((x.x + so.x) * k.x +
+ *              k.y, (x.y + so.y) * k.y + k.x);  t = frac((q.x * q.y) * (q.x + q.y));  hash2 = (-1.0f + 2.0f * frac((16.0f * k.x) * t), -1.0f +
+ *              2.0f * frac((16.0f * k.y) * t)).
+ *   T3. noised(p, seed)   i = floor(p), f = p - i;  per component u = ((f * f) * f) * (f * (f * 6.0f - 15.0f) + 10.0f), du = ((30.0f * f) * f) *
+ *              (f * (f - 2.0f) + 1.0f);  ga, gb, gc, gd = hash2 at i + (0, 0), (1, 0), (0, 1), (1, 1);  va = dot(ga, f), vb = dot(gb, f - (1,
+ *              0)), vc = dot(gc, f - (0, 1)), vd = dot(gd, f - (1, 1));  k = ((va - vb) - vc) + vd;  value = ((va + u.x * (vb - va)) + u.y *
+ *              (vc - va)) + (u.x * u.y) * k;  derivative.c = (((ga.c + u.x * (gb.c - ga.c)) + u.y * (gc.c - ga.c)) + (u.x * u.y) * (((ga.c -
+ *              gb.c) - gc.c) + gd.c)) + du.c * ((w.c * k + v.c) - va) with (w, v).x = (u.y, vb), (w, v).y = (u.x, vc).
+ *   T4. fractal_noise   r = (0, 0, 0), amplitude = 1, freq = G.height_frequency;  for i in 0 .. G.height_octaves - 1: o = noised(p * freq,
+ *              E.seed + i);  r.x = r.x + o.x * amplitude;  r.yz = r.yz + o.yz * (amplitude * freq);  amplitude = amplitude * G.height_gain;
+ *              freq = freq * G.height_lacunarity.
+ *   T5. base   base = r * G.height_amplitude;  fade_target = clamp(base.x / (G.height_amplitude * 0.6f), -1, 1);  base.x = base.x * 0.5f +
+ *              0.5f.
+ *   T6. erosion, before the octaves   clamp01 = saturate;  ease_out(t): v = 1.0f - clamp01(t), 1.0f - v * v;  smooth_start(t, s) = t >= s ? t -
+ *              0.5f * s : ((0.5f * t) * t) / s (a NaN takes the second arm);  pow_inv(t, w) = 1.0f - pow(1.0f - clamp01(t), w).
+ *              strength = E.strength * E.scale;  target = clamp(fade_target, -1, 1);  height = base.x;  freq = 1.0f / (E.scale *
+ *              E.cell_scale);  slope_length = max(length(base.yz), 1e-10f);  magnitude = 0;  rounding_mult = 1;  rounding_for_input =
+ *              lerp(E.rounding.y, E.rounding.x, clamp01(target + 0.5f)) * E.rounding.z;  combi_mask = ease_out(smooth_start(slope_length *
+ *              E.onset.x, rounding_for_input * E.onset.x));  ridge_mask = ease_out(slope_length * E.onset.z);  ridge_target = target;
+ *              gully_slope = lerp(base.yz, (base.yz / slope_length) * E.assumed_slope.x, E.assumed_slope.y) per component.
+ *   T7. phacelle(pp, seed), for octave i of 0 .. E.octaves - 1 with pp = p * freq and seed = E.seed + i:   len = length(gully_slope), n = len
+ *              > 1e-10f ? gully_slope / len : (0, 0);  side = (((n.y * -1.0f) * E.cell_scale) * TAU, ((n.x * 1.0f) * E.cell_scale) * TAU);
+ *              phase_offset = 0.25f * TAU;  c = floor(pp), f = pp - c;  phase_dir = (0, 0), weight_sum = 0;  for a in -1 .. 2, inside it
+ *              for b in -1 .. 2 (16 cells, b fastest): g = (f32(a), f32(b));  d = (f - g) - hash2(c + g, seed) * 0.5f;  sq = dot(d, d);
+ *              weight = max(0, exp((-sq) * 2.0f) - 0.01111f);  weight_sum = weight_sum + weight;  w = dot(d, side) + phase_offset;
+ *              phase_dir = phase_dir + (cos(w) * weight, sin(w) * weight).  interpolated = phase_dir / max(weight_sum, 1e-10f);
+ *              magnitude_p = max(1.0f - E.normalization, length(interpolated));  ph.xy = interpolated / magnitude_p, ph.zw = side.
+ *   T8. the octave   ph.zw = ph.zw * (-freq);  sloping = |ph.y|;  gully_slope = gully_slope + ((sign(ph.y) * ph.zw) * strength) *
+ *              E.gully_weight;  gx = ph.x;  faded = lerp(target, gx * E.gully_weight, combi_mask);  height = height + faded * strength;
+ *              magnitude = magnitude + strength;  target = faded;  rounding_for_octave = lerp(E.rounding.y, E.rounding.x, clamp01(ph.x +
+ *              0.5f)) * rounding_mult;  new_mask = ease_out(smooth_start(sloping * E.onset.y, rounding_for_octave * E.onset.y));
+ *              combi_mask = pow_inv(combi_mask, E.detail) * new_mask;  ridge_target = lerp(ridge_target, gx, ridge_mask);  ridge_mask =
+ *              ridge_mask * ease_out(sloping * E.onset.w);  strength = strength * E.gain;  freq = freq * E.lacunarity;  rounding_mult =
+ *              rounding_mult * E.rounding.w.  (The Slang also accumulates the slope delta, which nothing reads.)
+ *   T9. store   delta = height - base.x;  ridge = ridge_target * (1.0f - ridge_mask);  offset = lerp(G.height_offset.x, -fade_target,
+ *              G.height_offset.y) * magnitude;  h = (base.x + delta) + offset;  heightmap = unorm16(h + height_edit[texel]);  ridgemap = the
+ *              binary16 store of ridge.
+ *   T10. derive   load_height(c) = the unorm16 load at c clamped to [0, resolution - 1] per axis: the heightmap as it is AFTER the generate
+ *              stage of the same call, and for a neighbour outside the written region whatever the buffer held.  h00 .. h22 the eight
+ *              neighbours, first index x, 0 = -1.  dhdx = ((((h20 + 2.0f * h21) + h22) - ((h00 + 2.0f * h01) + h02)) * D.height_range) / (8.0f *
+ *              D.texel_world_size.x);  dhdz = ((((h02 + 2.0f * h12) + h22) - ((h00 + 2.0f * h10) + h20)) * D.height_range) / (8.0f *
+ *              D.texel_world_size.y);  normal = normalize((-dhdx, 1.0f, -dhdz));  normalmap = the binary16 stores of (normal.x, normal.z).
+ *   T11. splat   height = load_height(texel), ridge = the binary16 load;  slope = saturate(1.0f - normal.y);  rock =
+ *              smoothstep(D.slope_rock_begin, D.slope_rock_end, slope);  snow = smoothstep(D.altitude_snow_begin, D.altitude_snow_end,
+ *              height) * (1.0f - rock);  drainage = (saturate((-ridge) * D.ridge_drainage_scale) * (1.0f - rock)) * (1.0f - snow);  grass =
+ *              saturate(((1.0f - rock) - snow) - drainage);  procedural = (grass, rock, drainage, snow);  painted = the four unorm8 loads of
+ *              splat_edit;  painted_weights = (saturate(((1.0f - painted.x) - painted.y) - painted.z), painted.x, painted.y, painted.z);
+ *              splatmap = unorm8 of lerp(procedural, painted_weights, painted.w) per component.
+ *   T12. minmax   patch = patch_origin + thread;  any(patch >= patch_count) writes nothing.  scale = f32(resolution) / f32(patch_count);
+ *              begin = u32(floor(f32(patch) * scale));  end = min(u32(ceil(f32(patch + 1) * scale)) + 1, resolution);  bounds = (1.0, 0.0),
+ *              then min / max with the unorm16 load of every texel of [begin, end) on both axes (the seed takes part; min and max of such
+ *              values do not depend on the order).  patch_minmax = bounds.
+ * Limits (else OXC_INVALID_ARG, nothing launched, nothing written; the first broken rule in this order gives the message, each has its own):
+ * struct_size; stages non-zero with no unknown bit; every side of resolution in 1 .. 16384, then of patch_count in 1 .. 4096;
+ * generate.resolution and derive.resolution equal to resolution; generate.height_octaves and generate.erosion.octaves at most 16 (this limit
+ * is the library's: the Slang has none, and an unbounded loop count would be a hang); erosion.detail finite and above 0, the pow rule's
+ * domain; every buffer a requested stage touches, in the order of the context's fields, non-null (region may be null), then aligned to its
+ * texel (region and patch_minmax to 8 bytes), then at least as large as its extent says (patch_minmax: one level at offset 0 of
+ * patch_count's extent); no written image shares a byte with another buffer the requested stages touch.  Every other float is taken as
+ * given: NaN, Inf and denormals go through the rules.  Generate touches region, heightmap, ridgemap, height_edit; derive region, heightmap,
+ * ridgemap, normalmap, splatmap, splat_edit; minmax region, heightmap, patch_minmax.
+ * One launch per stage; no scratch, no allocation, no host synchronisation; capturable into a HIP graph. */
+#define OXC_TERRAIN_GENERATE 1u
+#define OXC_TERRAIN_DERIVE 2u
+#define OXC_TERRAIN_MINMAX 4u
+typedef struct oxc_terrain_erosion { /* GPU::TerrainErosion (SceneGPU.hpp:358-372, scene.slang:541-558) */
+  float scale, strength, gully_weight, detail;
+  float rounding[4];
+  float onset[4];
+  float assumed_slope[2];
+  float cell_scale, gain, lacunarity, normalization;
+  uint32_t octaves, seed;
+} oxc_terrain_erosion;
+typedef struct oxc_terrain_generate { /* GPU::TerrainGenerate (SceneGPU.hpp:374-384) */
+  oxc_terrain_erosion erosion;
+  uint32_t resolution[2];
+  float height_offset[2];
+  float domain_size, height_frequency, height_amplitude, height_lacunarity, height_gain;
+  uint32_t height_octaves;
+} oxc_terrain_generate;
+typedef struct oxc_terrain_derive { /* GPU::TerrainDerive (SceneGPU.hpp:386-395); the caller fills the first three as Terrain::bake does */
+  uint32_t resolution[2];
+  float texel_world_size[2]; /* world_size / resolution */
+  float height_range;        /* height_range.y - height_range.x */
+  float slope_rock_begin, slope_rock_end, altitude_snow_begin, altitude_snow_end, ridge_drainage_scale;
+} oxc_terrain_derive;
+#ifdef __cplusplus
+static_assert(sizeof(oxc_terrain_erosion) == 80 && sizeof(oxc_terrain_generate) == 120 && sizeof(oxc_terrain_derive) == 40, "the GPU:: records");
+#else
+_Static_assert(sizeof(oxc_terrain_erosion) == 80 && sizeof(oxc_terrain_generate) == 120 && sizeof(oxc_terrain_derive) == 40, "the GPU:: records");
+#endif
+typedef struct oxc_terrain_maps_context {
+  uint32_t struct_size; /* sizeof(oxc_terrain_maps_context) */
+  uint32_t stages;      /* OXC_TERRAIN_GENERATE | OXC_TERRAIN_DERIVE | OXC_TERRAIN_MINMAX */
+  oxc_terrain_generate generate;
+  oxc_terrain_derive derive;
+  uint32_t resolution[2], patch_count[2];              /* GPU::TerrainMinMax */
+  uint32_t dispatch_texels[2], dispatch_patches[2];    /* the reference's dispatch arguments: bake passes resolution and patch_count */
+  oxc_buffer region;       /* in, device memory, may be null: u32[4] {texel_origin.xy, patch_origin.xy} */
+  oxc_buffer heightmap;    /* u16 [resolution.y][.x]: written by generate, read by derive and minmax */
+  oxc_buffer ridgemap;     /* u16 [resolution.y][.x] of binary16 bits: written by generate, read by derive */
+  oxc_buffer normalmap;    /* out (derive): u16x2 [resolution.y][.x] */
+  oxc_buffer splatmap;     /* out (derive): u32 [resolution.y][.x] */
+  oxc_buffer height_edit;  /* in (generate): f32 [resolution.y][.x] */
+  oxc_buffer splat_edit;   /* in (derive): u32 [resolution.y][.x] */
+  oxc_image patch_minmax;  /* out (minmax): RG32F, one level, patch_count.x x patch_count.y */
+} oxc_terrain_maps_context;
+
+oxc_status oxc_generate_terrain_maps(oxc_ctx* ctx, const oxc_terrain_maps_context* context, void* hip_stream);
+
 /* ---- multi-GPU exchange: one process per GPU, RCCL over xGMI ---------------------------
  * The meshlet-instance array shards by contiguous range and every rank culls its shard on its own; the only
  * exchanges of the path are (1) the per-rank counters {emitted meshlets, early, late, index count} to every rank

@@ -1,0 +1,101 @@
+// oxcull_abi_terrain.cpp -- the terrain map producers of liboxcull.so's C ABI: oxc_generate_terrain_maps (height, ridge, normal, splat and the
+// per-patch min / max).  The terrain cull, their consumer, is in oxcull_abi_cull.cpp.
+#include "oxcull_host.hpp"
+
+namespace {
+constexpr uint32_t kStageAll = OXC_TERRAIN_GENERATE | OXC_TERRAIN_DERIVE | OXC_TERRAIN_MINMAX;
+
+// One buffer of the call, as the limits see it: which stages touch it, which write it, its texel (= alignment) and the bytes its extent asks
+struct MapBuffer {
+  const char* name;
+  const void* dptr;
+  uint64_t have, need;
+  uint32_t align, touched_by, written_by;
+  bool may_be_null;
+};
+
+// roundup(dispatch, group) as a thread count, capped at roundup(extent, group): what lies beyond cannot land inside the map without wrapping
+uint32_t threads_of(uint32_t dispatch, uint32_t extent, uint32_t group) {
+  const uint64_t want = ((uint64_t)dispatch + group - 1u) / group * group;
+  return (uint32_t)std::min<uint64_t>(want, (extent + group - 1u) / group * group);
+}
+}  // namespace
+
+extern "C" {
+
+oxc_status oxc_generate_terrain_maps(oxc_ctx* ctx, const oxc_terrain_maps_context* c, void* hip_stream) {
+  if (!ctx) return OXC_INVALID_ARG;
+  if (!c || c->struct_size != sizeof(oxc_terrain_maps_context)) return fail(ctx, OXC_INVALID_ARG, "generate_terrain_maps: bad context / struct_size");
+  const char* const entry = "generate_terrain_maps";
+  const uint32_t stages = c->stages;
+  if (stages == 0u || (stages & ~kStageAll)) return bad_arg(ctx, entry, "stages must be a non-empty mask of OXC_TERRAIN_GENERATE | OXC_TERRAIN_DERIVE | OXC_TERRAIN_MINMAX");
+  const uint32_t *res = c->resolution, *pc = c->patch_count;
+  if (res[0] < 1u || res[0] > 16384u || res[1] < 1u || res[1] > 16384u) return bad_arg(ctx, entry, "resolution: every side must be in 1 .. 16384");
+  if (pc[0] < 1u || pc[0] > 4096u || pc[1] < 1u || pc[1] > 4096u) return bad_arg(ctx, entry, "patch_count: every side must be in 1 .. 4096");
+  if (c->generate.resolution[0] != res[0] || c->generate.resolution[1] != res[1]) return bad_arg(ctx, entry, "generate.resolution must equal resolution");
+  if (c->derive.resolution[0] != res[0] || c->derive.resolution[1] != res[1]) return bad_arg(ctx, entry, "derive.resolution must equal resolution");
+  if (c->generate.height_octaves > 16u) return bad_arg(ctx, entry, "generate.height_octaves must be at most 16");
+  if (c->generate.erosion.octaves > 16u) return bad_arg(ctx, entry, "generate.erosion.octaves must be at most 16");
+  if (!std::isfinite(c->generate.erosion.detail) || !(c->generate.erosion.detail > 0.0f)) return bad_arg(ctx, entry, "generate.erosion.detail must be finite and above 0");
+
+  const uint64_t texels = (uint64_t)res[0] * res[1], patches = (uint64_t)pc[0] * pc[1];
+  const oxc_image& mm = c->patch_minmax;
+  const bool mm_extent = mm.width == pc[0] && mm.height == pc[1] && mm.levels == 1u && mm.level_offset[0] == 0u;
+  const uint32_t G = OXC_TERRAIN_GENERATE, D = OXC_TERRAIN_DERIVE, M = OXC_TERRAIN_MINMAX;
+  const MapBuffer buffers[] = {
+      {"region", c->region.dptr, c->region.bytes, 16u, 8u, kStageAll, 0u, true},
+      {"heightmap", c->heightmap.dptr, c->heightmap.bytes, texels * 2u, 2u, kStageAll, G, false},
+      {"ridgemap", c->ridgemap.dptr, c->ridgemap.bytes, texels * 2u, 2u, G | D, G, false},
+      {"normalmap", c->normalmap.dptr, c->normalmap.bytes, texels * 4u, 4u, D, D, false},
+      {"splatmap", c->splatmap.dptr, c->splatmap.bytes, texels * 4u, 4u, D, D, false},
+      {"height_edit", c->height_edit.dptr, c->height_edit.bytes, texels * 4u, 4u, G, 0u, false},
+      {"splat_edit", c->splat_edit.dptr, c->splat_edit.bytes, texels * 4u, 4u, D, 0u, false},
+      {"patch_minmax", mm.dptr, mm_extent ? patches * 8u : 0u, patches * 8u, 8u, M, M, false},
+  };
+  for (const MapBuffer& b : buffers) {
+    if (!(b.touched_by & stages)) continue;
+    if (!b.dptr) {
+      if (b.may_be_null) continue;
+      return bad_arg(ctx, entry, b.name, " must not be null");
+    }
+    if (reinterpret_cast<uintptr_t>(b.dptr) & (b.align - 1u)) return bad_arg(ctx, entry, b.name, " must be aligned to its texel");
+    if (b.have < b.need) return bad_arg(ctx, entry, b.name, &b == &buffers[7] ? " must be one RG32F level at offset 0 of patch_count's extent" : " is smaller than its extent");
+  }
+  for (const MapBuffer& w : buffers) {
+    if (!(w.written_by & stages)) continue;
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(w.dptr);
+    for (const MapBuffer& o : buffers) {
+      if (&o == &w || !(o.touched_by & stages) || !o.dptr) continue;
+      const uintptr_t olo = reinterpret_cast<uintptr_t>(o.dptr);
+      if (ByteSpan{lo, lo + (uintptr_t)w.need}.overlaps({olo, olo + (uintptr_t)o.need})) return bad_arg(ctx, entry, w.name, " must not overlap ", o.name);
+    }
+  }
+
+  OXC_ENTER(ctx, hip_stream, s);
+  TerrainMapsArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.g = c->generate;
+  a.d = c->derive;
+  for (int k = 0; k < 2; k++) {
+    a.res[k] = res[k];
+    a.patches[k] = pc[k];
+    a.threads_texels[k] = threads_of(c->dispatch_texels[k], res[k], 16u);
+    a.threads_patches[k] = threads_of(c->dispatch_patches[k], pc[k], 8u);
+  }
+  terrain_maps_constants(a);
+  a.region = static_cast<const uint32_t*>(c->region.dptr);
+  a.heightmap = static_cast<uint16_t*>(c->heightmap.dptr);
+  a.ridgemap = static_cast<uint16_t*>(c->ridgemap.dptr);
+  a.normalmap = static_cast<uint32_t*>(c->normalmap.dptr);
+  a.splatmap = static_cast<uint32_t*>(c->splatmap.dptr);
+  a.height_edit = static_cast<const float*>(c->height_edit.dptr);
+  a.splat_edit = static_cast<const uint32_t*>(c->splat_edit.dptr);
+  a.patch_minmax = static_cast<float2*>(mm.dptr);
+  if (stages & G) launch_terrain_generate(a, s);
+  if (stages & D) launch_terrain_derive(a, s);
+  if (stages & M) launch_terrain_minmax(a, s);
+  OXC_HIP(ctx, hipGetLastError());
+  return OXC_OK;
+}
+
+}  // extern "C"

@@ -773,6 +773,31 @@ struct SkyIblArgs {
   uint2* cube;  // in and out, [6][cube_size][cube_size]
 };
 void launch_sky_ibl(const SkyIblArgs& a, hipStream_t s);
+// oxcull_terrain_maps.hip: the terrain maps (oxc_generate_terrain_maps); the folded values are the header block's "the host may evaluate"
+struct TerrainMapsArgs {
+  oxc_terrain_generate g;
+  oxc_terrain_derive d;
+  uint32_t res[2], patches[2];
+  uint32_t threads_texels[2], threads_patches[2];  // roundup(dispatch, 16 / 8), capped at roundup(resolution / patch_count): multiples of 16 / 8
+  float fres[2];                // f32(resolution)
+  float strength0, freq0;       // E.strength * E.scale; 1.0f / (E.scale * E.cell_scale)
+  float one_minus_norm;         // 1.0f - E.normalization
+  float amp06;                  // G.height_amplitude * 0.6f
+  float den[2];                 // 8.0f * D.texel_world_size
+  float mm_scale[2];            // f32(resolution) / f32(patch_count)
+  const uint32_t* region;       // nullptr: both origins zero
+  uint16_t* heightmap;
+  uint16_t* ridgemap;
+  uint32_t* normalmap;
+  uint32_t* splatmap;
+  const float* height_edit;
+  const uint32_t* splat_edit;
+  float2* patch_minmax;
+};
+void terrain_maps_constants(TerrainMapsArgs& a);  // fills the folded values from g, d, res and patches
+void launch_terrain_generate(const TerrainMapsArgs& a, hipStream_t s);
+void launch_terrain_derive(const TerrainMapsArgs& a, hipStream_t s);
+void launch_terrain_minmax(const TerrainMapsArgs& a, hipStream_t s);
 // oxcull_bounds.hip: meshlet bounds producer
 void launch_build_meshlet_bounds(const float* pos, uint32_t vertex_count, const void* meshlets, uint32_t meshlet_count, const uint32_t* vidx,
                                  const uint8_t* micro, void* out_bounds, float* out_mesh6, void* out_qpos, float* meshlet_minmax, float* normals,

@@ -605,6 +605,13 @@ public:
     check(oxc_apply_tonemap(ctx_, &c, stream_));
     return context.dst_attachment;
   }
+  // The terrain map producers (Scene/Terrain.cpp:406-461, Passes/Terrain.cpp:134-156): the stages of context.stages in the order generate,
+  // derive, minmax.  The three free functions below, with the reference's names, each run one.  Rules: include/oxcull.h,
+  // oxc_generate_terrain_maps.
+  auto generate_terrain_maps(oxc_terrain_maps_context context) -> void {
+    context.struct_size = sizeof context;
+    check(oxc_generate_terrain_maps(ctx_, &context, stream_));
+  }
   auto build_meshlet_bounds(oxc_meshlet_bounds_desc desc) -> void {
     desc.struct_size = sizeof desc;
     check(oxc_build_meshlet_bounds(ctx_, &desc, stream_));
@@ -624,5 +631,68 @@ private:
   oxc_ctx* ctx_ = nullptr;
   void* stream_ = nullptr;
 };
+
+namespace GPU {
+using TerrainErosion = oxc_terrain_erosion;    // SceneGPU.hpp:358-372, 80 bytes
+using TerrainGenerate = oxc_terrain_generate;  // SceneGPU.hpp:374-384, 120 bytes
+using TerrainDerive = oxc_terrain_derive;      // SceneGPU.hpp:386-395, 40 bytes
+struct TerrainMinMax {                         // SceneGPU.hpp:397-400
+  uint32_t resolution[2] = {};
+  uint32_t patch_count[2] = {};
+};
+}  // namespace GPU
+
+struct uvec2 {  // stands in for glm::uvec2
+  uint32_t x = 0, y = 0;
+};
+
+// Scene/Terrain.hpp:22-31 of the reference: the seven images and the region record, here linear buffers in the layouts include/oxcull.h
+// states (patch_minmax the RG32F image oxc_cull_terrain takes).  `renderer` is what the reference's passes take from the render graph: the
+// instance whose context and stream the three passes below run on.
+struct TerrainMaps {
+  RendererInstance* renderer = nullptr;
+  Buffer heightmap = {};
+  Buffer ridgemap = {};
+  Buffer normalmap = {};
+  Buffer splatmap = {};
+  ImageAttachment patch_minmax = {};
+  Buffer height_edit = {};
+  Buffer splat_edit = {};
+  Buffer region = {};  // device memory, 16 bytes of GPU::TerrainRegion; {} for zero origins
+};
+
+namespace detail {
+inline oxc_terrain_maps_context terrain_context(const TerrainMaps& maps, uint32_t stages, const uint32_t* resolution) {
+  if (!maps.renderer) throw std::runtime_error("TerrainMaps::renderer is not set");
+  oxc_terrain_maps_context c = {};
+  c.stages = stages;
+  for (int k = 0; k < 2; k++) c.resolution[k] = c.generate.resolution[k] = c.derive.resolution[k] = resolution[k], c.patch_count[k] = 1;
+  c.generate.erosion.detail = 1.0f;  // a stage that does not read the record still passes its limit
+  c.region = maps.region;
+  c.heightmap = maps.heightmap, c.ridgemap = maps.ridgemap, c.normalmap = maps.normalmap, c.splatmap = maps.splatmap;
+  c.height_edit = maps.height_edit, c.splat_edit = maps.splat_edit, c.patch_minmax = maps.patch_minmax;
+  return c;
+}
+}  // namespace detail
+
+// Scene/Terrain.hpp:33-35 of the reference, the same names and argument lists
+inline auto terrain_generate_pass(TerrainMaps& maps, const GPU::TerrainGenerate& settings, uvec2 dispatch_texels) -> void {
+  oxc_terrain_maps_context c = detail::terrain_context(maps, OXC_TERRAIN_GENERATE, settings.resolution);
+  c.generate = settings;
+  c.dispatch_texels[0] = dispatch_texels.x, c.dispatch_texels[1] = dispatch_texels.y;
+  maps.renderer->generate_terrain_maps(c);
+}
+inline auto terrain_derive_pass(TerrainMaps& maps, const GPU::TerrainDerive& settings, uvec2 dispatch_texels) -> void {
+  oxc_terrain_maps_context c = detail::terrain_context(maps, OXC_TERRAIN_DERIVE, settings.resolution);
+  c.derive = settings;
+  c.dispatch_texels[0] = dispatch_texels.x, c.dispatch_texels[1] = dispatch_texels.y;
+  maps.renderer->generate_terrain_maps(c);
+}
+inline auto terrain_minmax_pass(TerrainMaps& maps, const GPU::TerrainMinMax& settings, uvec2 dispatch_patches) -> void {
+  oxc_terrain_maps_context c = detail::terrain_context(maps, OXC_TERRAIN_MINMAX, settings.resolution);
+  c.patch_count[0] = settings.patch_count[0], c.patch_count[1] = settings.patch_count[1];
+  c.dispatch_patches[0] = dispatch_patches.x, c.dispatch_patches[1] = dispatch_patches.y;
+  maps.renderer->generate_terrain_maps(c);
+}
 
 }  // namespace ox::amd

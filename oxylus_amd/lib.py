@@ -45,6 +45,7 @@ SCENE_HAS_FXAA = 1 << 4  # SceneGPU.hpp:259; oxc_apply_fxaa does not read it: Re
 TONEMAP_NONE, TONEMAP_ACES, TONEMAP_AGX, TONEMAP_GT7 = 0, 1, 2, 3  # GPU::TonemapType, oxc_tonemap_context.tonemap_type
 TONEMAP_OUT_R8G8B8A8_SRGB, TONEMAP_OUT_B8G8R8A8_SRGB, TONEMAP_OUT_R8G8B8A8_UNORM = 0, 1, 2  # oxc_tonemap_context.output_format
 LIGHT_KIND_DIRECTIONAL, LIGHT_KIND_POINT, LIGHT_KIND_SPOT = 0, 1, 2  # GPU::LightKind
+TERRAIN_GENERATE, TERRAIN_DERIVE, TERRAIN_MINMAX, TERRAIN_ALL = 1, 2, 4, 7  # oxc_terrain_maps_context.stages
 
 
 class Buffer(C.Structure):
@@ -628,6 +629,76 @@ class PbrAtmosphereContext(C.Structure):
     ]
 
 
+class TerrainErosion(C.Structure):
+    _c_name_ = "oxc_terrain_erosion"
+    _fields_ = [
+        ("scale", C.c_float),
+        ("strength", C.c_float),
+        ("gully_weight", C.c_float),
+        ("detail", C.c_float),
+        ("rounding", C.c_float * 4),
+        ("onset", C.c_float * 4),
+        ("assumed_slope", C.c_float * 2),
+        ("cell_scale", C.c_float),
+        ("gain", C.c_float),
+        ("lacunarity", C.c_float),
+        ("normalization", C.c_float),
+        ("octaves", C.c_uint32),
+        ("seed", C.c_uint32),
+    ]
+
+
+class TerrainGenerate(C.Structure):
+    _c_name_ = "oxc_terrain_generate"
+    _fields_ = [
+        ("erosion", TerrainErosion),
+        ("resolution", C.c_uint32 * 2),
+        ("height_offset", C.c_float * 2),
+        ("domain_size", C.c_float),
+        ("height_frequency", C.c_float),
+        ("height_amplitude", C.c_float),
+        ("height_lacunarity", C.c_float),
+        ("height_gain", C.c_float),
+        ("height_octaves", C.c_uint32),
+    ]
+
+
+class TerrainDerive(C.Structure):
+    _c_name_ = "oxc_terrain_derive"
+    _fields_ = [
+        ("resolution", C.c_uint32 * 2),
+        ("texel_world_size", C.c_float * 2),
+        ("height_range", C.c_float),
+        ("slope_rock_begin", C.c_float),
+        ("slope_rock_end", C.c_float),
+        ("altitude_snow_begin", C.c_float),
+        ("altitude_snow_end", C.c_float),
+        ("ridge_drainage_scale", C.c_float),
+    ]
+
+
+class TerrainMapsContext(C.Structure):
+    _c_name_ = "oxc_terrain_maps_context"
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("stages", C.c_uint32),
+        ("generate", TerrainGenerate),
+        ("derive", TerrainDerive),
+        ("resolution", C.c_uint32 * 2),
+        ("patch_count", C.c_uint32 * 2),
+        ("dispatch_texels", C.c_uint32 * 2),
+        ("dispatch_patches", C.c_uint32 * 2),
+        ("region", Buffer),
+        ("heightmap", Buffer),
+        ("ridgemap", Buffer),
+        ("normalmap", Buffer),
+        ("splatmap", Buffer),
+        ("height_edit", Buffer),
+        ("splat_edit", Buffer),
+        ("patch_minmax", Image),
+    ]
+
+
 class MeshBuildDesc(C.Structure):
     _c_name_ = "oxc_mesh_build_desc"
     _fields_ = [("struct_size", C.c_uint32), ("vertex_count", C.c_uint32), ("index_count", C.c_uint32), ("max_lods", C.c_uint32), ("max_vertices", C.c_uint32),
@@ -693,6 +764,7 @@ PROTOTYPES = {
     "oxc_draw_atmosphere": (_status, [_vp, _P(AtmosphereContext), _vp]),
     "oxc_generate_sky_ibl": (_status, [_vp, _P(SkyIblContext), _vp]),
     "oxc_apply_pbr_atmosphere": (_status, [_vp, _P(PbrAtmosphereContext), _vp]),
+    "oxc_generate_terrain_maps": (_status, [_vp, _P(TerrainMapsContext), _vp]),
     "oxc_draw_physical_pages": (_status, [_vp, _P(PreparedFrame), _P(VsmDrawContext), _vp]),
     "oxc_debug_vsm_draw_stats": _stats,
     "oxc_resolve_shadowmap": (_status, [_vp, _P(ShadowResolveContext), _vp]),

@@ -759,6 +759,103 @@ class PBRAtmosphereContext(Marshalled):
 
 
 @dataclass
+class TerrainErosion(Marshalled):
+    """GPU::TerrainErosion (SceneGPU.hpp:358-372) with the record's own defaults."""
+    _ctype = L.TerrainErosion
+    scale: float = 0.15
+    strength: float = 0.22
+    gully_weight: float = 0.5
+    detail: float = 1.5
+    rounding: tuple = (0.1, 0.0, 0.1, 2.0)
+    onset: tuple = (1.25, 1.25, 2.8, 1.5)
+    assumed_slope: tuple = (0.7, 1.0)
+    cell_scale: float = 0.7
+    gain: float = 0.5
+    lacunarity: float = 2.0
+    normalization: float = 0.5
+    octaves: int = 5
+    seed: int = 0
+
+
+@dataclass
+class TerrainGenerate(Marshalled):
+    """GPU::TerrainGenerate (SceneGPU.hpp:374-384) with the record's own defaults; `resolution` is filled by the context."""
+    _ctype = L.TerrainGenerate
+    erosion: TerrainErosion = field(default_factory=TerrainErosion)
+    resolution: tuple = (0, 0)
+    height_offset: tuple = (-0.65, 0.0)
+    domain_size: float = 2.0
+    height_frequency: float = 3.0
+    height_amplitude: float = 0.125
+    height_lacunarity: float = 2.0
+    height_gain: float = 0.1
+    height_octaves: int = 3
+
+
+@dataclass
+class TerrainDerive(Marshalled):
+    """GPU::TerrainDerive (SceneGPU.hpp:386-395) with the record's own defaults; the first three are what Terrain::bake fills."""
+    _ctype = L.TerrainDerive
+    resolution: tuple = (0, 0)
+    texel_world_size: tuple = (0.0, 0.0)
+    height_range: float = 0.0
+    slope_rock_begin: float = 0.55
+    slope_rock_end: float = 0.8
+    altitude_snow_begin: float = 0.7
+    altitude_snow_end: float = 0.85
+    ridge_drainage_scale: float = 1.0
+
+
+def _patch_minmax_image(self) -> L.Image:
+    im = L.Image()
+    t = self.patch_minmax
+    if t is not None:
+        im.dptr, im.width, im.height, im.levels = t.data_ptr(), int(t.shape[1]), int(t.shape[0]), 1
+    return im
+
+
+@dataclass
+class TerrainMapsContext(Marshalled):
+    """oxc_terrain_maps_context: the three passes of Terrain::bake (Scene/Terrain.cpp:406-461) and of the brush's regional re-bake
+    (Passes/Terrain.cpp:134-156).  `create` allocates the five outputs and zeroed edit images for a Terrain of `resolution`, `patch_count`,
+    `world_size` and `height_range`, and fills the settings' resolution, texel_world_size and height_range as bake does; the dispatch is the
+    whole map.  `patch_minmax` is float32 [patch_count.y, patch_count.x, 2], what RendererInstance.cull_terrain takes.  `region`: int32 [4]
+    on the device {texel_origin.xy, patch_origin.xy}, or None for zero origins."""
+    _ctype = L.TerrainMapsContext
+    _derived = {"patch_minmax": _patch_minmax_image}
+    generate: TerrainGenerate
+    derive: TerrainDerive
+    resolution: tuple
+    patch_count: tuple
+    dispatch_texels: tuple
+    dispatch_patches: tuple
+    heightmap: Optional[torch.Tensor]     # int16 [H, W]: R16 Unorm
+    ridgemap: Optional[torch.Tensor]      # int16 [H, W]: binary16 bits
+    normalmap: Optional[torch.Tensor]     # int16 [H, W, 2]: binary16 bits
+    splatmap: Optional[torch.Tensor]      # int32 [H, W]: R8G8B8A8 Unorm
+    height_edit: Optional[torch.Tensor]   # float32 [H, W]
+    splat_edit: Optional[torch.Tensor]    # int32 [H, W]
+    patch_minmax: Optional[torch.Tensor]  # float32 [py, px, 2]
+    region: Optional[torch.Tensor] = None
+    stages: int = L.TERRAIN_ALL
+
+    @staticmethod
+    def create(resolution=(2048, 2048), patch_count=(64, 64), world_size=(1024.0, 1024.0), height_range=(0.0, 400.0),
+               generate: Optional[TerrainGenerate] = None, derive: Optional[TerrainDerive] = None, device="cuda", **settings) -> "TerrainMapsContext":
+        import dataclasses
+
+        f32 = lambda x: struct.unpack("f", struct.pack("f", x))[0]  # noqa: E731
+        W, H = int(resolution[0]), int(resolution[1])
+        g = dataclasses.replace(generate or TerrainGenerate(), resolution=(W, H))
+        tws = tuple(f32(f32(world_size[k]) / f32(float(resolution[k]))) for k in range(2))  # Terrain::texel_world_size, binary32
+        d = dataclasses.replace(derive or TerrainDerive(), resolution=(W, H), texel_world_size=tws, height_range=f32(f32(height_range[1]) - f32(height_range[0])))
+        z = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=device)  # noqa: E731
+        return TerrainMapsContext(g, d, (W, H), tuple(int(v) for v in patch_count), (W, H), tuple(int(v) for v in patch_count), z((H, W), torch.int16),
+                                  z((H, W), torch.int16), z((H, W, 2), torch.int16), z((H, W), torch.int32), z((H, W), torch.float32), z((H, W), torch.int32),
+                                  z((int(patch_count[1]), int(patch_count[0]), 2), torch.float32), **settings)
+
+
+@dataclass
 class VisbufferDecodeContext(Marshalled):
     """oxc_decode_context: RendererInstance::decode_visbuffer (Passes/DrawGeometry.cpp:192-274), the geometry and material-factor half of
     visbuffer_decode.slang.  `create` takes the visbuffer and the depth as oxc_draw_visbuffer resolved them, the matrix they were drawn with and
@@ -1087,6 +1184,12 @@ class RendererInstance:
         """Passes/PBR.cpp:52-94, the sky_ibl pass of draw_atmosphere: 64 samples of sky_view_lut per cube texel, blended into the texel's own
         history, one launch (include/oxcull.h, oxc_generate_sky_ibl).  After draw_atmosphere; `context.frame_index` is the caller's to advance."""
         self._call("oxc_generate_sky_ibl", context, stream)
+
+    def generate_terrain_maps(self, context: TerrainMapsContext, stream=None) -> None:
+        """Scene/Terrain.cpp:406-461 and Passes/Terrain.cpp:134-156 (terrain_generate, terrain_derive, terrain_minmax): the stages of
+        `context.stages` in that order, one launch each: heightmap and ridgemap, normalmap and splatmap, patch_minmax (include/oxcull.h,
+        oxc_generate_terrain_maps).  `context.patch_minmax` is what cull_terrain reads."""
+        self._call("oxc_generate_terrain_maps", context, stream)
 
     def debug_fxaa_stats(self, stream=None) -> dict:
         """What the last apply_fxaa did, after debug_set_tuning(L.TUNE_FXAA_STATS, 1) (measurement hook; synchronises)."""
