@@ -1930,6 +1930,106 @@ typedef struct oxc_terrain_maps_context {
 
 oxc_status oxc_generate_terrain_maps(oxc_ctx* ctx, const oxc_terrain_maps_context* context, void* hip_stream);
 
+/* ---- the terrain brush: the mouse ray against the heightmap, and the strokes into the edit images -------------------------------------------
+ * oxc_apply_terrain_brush is the two compute passes of RendererInstance::apply_terrain_brush (Passes/Terrain.cpp:35-132):
+ * passes/terrain_brush_trace.slang and passes/terrain_brush_apply.slang with GPU::TerrainBrushParams (scene.slang:606-630).  Trace marches
+ * the ray through the heightmap and writes `hit` and `region`, the record oxc_generate_terrain_maps reads on the device; apply reads `hit`
+ * from the device and writes the brush footprint into height_edit (modes Raise, Smooth, Flatten, Noise) or splat_edit (PaintLayer).  `stages`
+ * selects them; the selected ones run in the order trace, apply on the stream.  Apply alone works on a hit written earlier: the reference's
+ * `painting == false` split seen from the other side.  Images, formats and the arithmetic conventions are those of the terrain maps block:
+ * binary32, the Slang's expressions left to right, one rounding per operation, no contraction; min / max / clamp / saturate through fmin /
+ * fmax; the dots, length and normalize as defined there; the unorm8 and unorm16 load and store rules; decimal literals the nearest binary32
+ * (1e-6f, 1e9f, 1e-3f, 0.05f).  Stated deviation: every float-to-integer conversion is cvt_u32_sat / cvt_i32_sat (saturating, a NaN gives 0)
+ * where the Slang's conversion of a NaN or an out-of-range value is undefined.  B = params (oxc_terrain_brush_params).
+ *   B1. the ray   direction = normalize(B.ray_direction) (a zero direction gives NaN in every component).  world_to_uv(w) = (w - B.world_min)
+ *              * B.inv_world_size;  decode_height(n) = B.base_height + n * B.height_scale.
+ *   B2. clip_to_footprint   world_max = B.world_min + B.world_size;  near = 0, far = 1e9f;  for the axes (origin.x, direction.x, world_min.x,
+ *              world_max.x) and then (origin.z, direction.z, world_min.y, world_max.y) as (o, d, lo, hi):  if |d| < 1e-6f: if o < lo || o >
+ *              hi the span is (1, 0) at once, else the axis is skipped;  otherwise t0 = (lo - o) / d, t1 = (hi - o) / d, near = max(near,
+ *              min(t0, t1)), far = min(far, max(t0, t1)).  span = (near, far).  span.x <= span.y false (a NaN included) is a miss.
+ *   B3. sample_height(w)   uv = world_to_uv(w).  Stated rule: SampleLevel(LinearSamplerClamped, uv, 0) is the manual bilinear of the
+ *              oxc_apply_bloom block in clamp mode on the resolution.x x resolution.y heightmap, applied to the unorm16 loads: per axis g = uv
+ *              * f32(resolution) - 0.5f, i = cvt_i32_sat(floor(g)), f = g - floor(g), the texels i and i + 1 each clamped to [0, resolution -
+ *              1];  n = lerp(lerp(t00, t10, f.x), lerp(t01, t11, f.x), f.y);  sample_height = decode_height(n).
+ *   B4. march   step = (span.y - span.x) / 512.0f;  t_0 = span.x exactly, t_i = span.x + step * f32(i) for i = 1 .. 512;  position_i =
+ *              B.ray_origin + direction * t_i per component;  gap_i = position_i.y - sample_height(position_i.xz) (the Slang's i = 0 gap,
+ *              ray_origin.y + direction.y * t, is the same expression).  The crossing is the smallest i in 1 .. 512 with gap_i <= 0 &&
+ *              gap_(i-1) > 0; a NaN makes both comparisons false.  No gap depends on an earlier one.  Without a crossing: a miss.
+ *   B5. bisect   lo = t_(i-1), hi = t_i;  24 times: mid = (lo + hi) * 0.5f, gap at mid as in B4;  gap > 0 ? lo = mid : hi = mid (a NaN takes
+ *              hi).  world_position = B.ray_origin + direction * hi;  hit = {world_position, 1}.
+ *   B6. region   center_texel = world_to_uv(world_position.xz) * f32(B.resolution);  radius = B.radius_texels + 1.0f;  texel_origin =
+ *              cvt_u32_sat(max(floor(center_texel - radius), 0)) per component (max through fmax: a NaN gives 0);  patch_scale =
+ *              f32(B.patch_count) / f32(B.resolution);  patch_origin = cvt_u32_sat(max(floor((center_texel - radius) * patch_scale), 0)).
+ *              Trace always writes all 32 bytes of hit and region; on a miss it writes zeros.
+ *   B7. apply, the texel   hit.valid == 0 writes nothing.  center = world_to_uv(hit.world_position.xz) * f32(B.resolution);  radius =
+ *              cvt_i32_sat(ceil(B.radius_texels));  signed_texel = cvt_i32_sat(floor(center)) - radius + thread per component, evaluated
+ *              without wrapping (a 64-bit sum; stated deviation: the Slang's i32 sum wraps);  a component below 0 or at least
+ *              B.resolution writes nothing, so a centre far outside the map writes nothing.  The grid is sized on the host from
+ *              radius_texels alone: footprint = 2 * u32(ceil(radius_texels)) + 1 threads a side in whole 16 x 16 groups, the reference's
+ *              dispatch.
+ *   B8. falloff   radius_texels <= 0 gives 0.  distance = length((f32(texel) + 0.5f) - center);  t = saturate(1.0f - distance /
+ *              B.radius_texels);  smoothed = ((t * t) * t) * (t * (t * 6.0f - 15.0f) + 10.0f);  falloff = pow(smoothed, max(B.falloff,
+ *              1e-3f)), pow the pow rule of oxc_apply_pbr: a base that is zero, below 2^-126, negative or NaN gives 0.  falloff <= 0 writes
+ *              nothing.  amount = falloff * B.strength.
+ *   B9. PaintLayer (mode 4)   target = (layer == 1 ? 1 : 0, layer == 2 ? 1 : 0, layer == 3 ? 1 : 0, 1): a layer outside 1 .. 3 paints (0, 0,
+ *              0, 1).  splat_edit[texel] = the unorm8 stores of lerp(p, target, saturate(amount)) per component, p the four unorm8 loads of
+ *              splat_edit[texel], lerp(a, b, t) = a + (b - a) * t.
+ *   B10. the height modes   load_height(c) = the unorm16 load of the heightmap at c clamped to [0, resolution - 1] per axis;  height =
+ *              load_height(texel).  Raise (0): delta = amount.  Smooth (1): sum = 0 and then sum = sum + load_height(texel + (x, y)) for y
+ *              in -2 .. 2 and inside it x in -2 .. 2; delta = (sum / 25.0f - height) * amount.  Flatten (2): delta = (B.flatten_height -
+ *              height) * amount.  Noise (3): delta = noised(f32(texel) * 0.05f, 0).x * amount, noised step T3 with seed 0.
+ *              height_edit[texel] = clamp(height_edit[texel] + delta, -1, 1) (a NaN gives -1).
+ * A texel is written by at most one thread; Smooth reads the heightmap, never height_edit, so there is no ordering between threads to
+ * define.  Every byte the rule does not write stays as it was.
+ * Limits (else OXC_INVALID_ARG, nothing launched, nothing written; the first broken rule in this order gives the message, each has its own):
+ * struct_size; stages non-zero with no unknown bit; every side of resolution in 1 .. 16384; every side of patch_count in 1 .. 4096; mode in
+ * 0 .. 4; radius_texels finite and in 0 .. 4096 (this limit is the library's: it bounds the apply grid at 513 x 513 groups); falloff finite,
+ * the pow rule's domain; every buffer a requested stage touches, in the order of the context's fields, non-null, then aligned to its texel
+ * (hit and region to 8 bytes), then at least as large as its extent; no written buffer shares a byte with another buffer the requested
+ * stages touch.  Trace touches heightmap, hit, region; apply in modes 0 - 3 heightmap, height_edit, hit; apply in PaintLayer splat_edit,
+ * hit.  Every other float goes through the rules as given: NaN / Inf rays, a zero direction, a zero world_size, a NaN strength.
+ * One launch per stage; no scratch, no allocation, no host synchronisation; capturable into a HIP graph. */
+#define OXC_TERRAIN_BRUSH_TRACE 1u
+#define OXC_TERRAIN_BRUSH_APPLY 2u
+#define OXC_TERRAIN_BRUSH_RAISE 0u /* GPU::TerrainBrushMode (scene.slang:593-599) */
+#define OXC_TERRAIN_BRUSH_SMOOTH 1u
+#define OXC_TERRAIN_BRUSH_FLATTEN 2u
+#define OXC_TERRAIN_BRUSH_NOISE 3u
+#define OXC_TERRAIN_BRUSH_PAINT_LAYER 4u
+typedef struct oxc_terrain_brush_params { /* GPU::TerrainBrushParams (scene.slang:606-621), field for field */
+  float ray_origin[3], radius_texels;
+  float ray_direction[3], strength;
+  uint32_t resolution[2];
+  float world_min[2], world_size[2], inv_world_size[2];
+  uint32_t patch_count[2];
+  float base_height, height_scale, falloff, flatten_height;
+  uint32_t mode, layer;
+} oxc_terrain_brush_params;
+typedef struct oxc_terrain_brush_hit { /* GPU::TerrainBrushHit (scene.slang:601-604) */
+  float world_position[3];
+  uint32_t valid;
+} oxc_terrain_brush_hit;
+typedef struct oxc_terrain_region { /* GPU::TerrainRegion (scene.slang:588-591): what oxc_terrain_maps_context.region points at */
+  uint32_t texel_origin[2], patch_origin[2];
+} oxc_terrain_region;
+#ifdef __cplusplus
+static_assert(sizeof(oxc_terrain_brush_params) == 96 && sizeof(oxc_terrain_brush_hit) == 16 && sizeof(oxc_terrain_region) == 16, "the GPU:: records");
+#else
+_Static_assert(sizeof(oxc_terrain_brush_params) == 96 && sizeof(oxc_terrain_brush_hit) == 16 && sizeof(oxc_terrain_region) == 16, "the GPU:: records");
+#endif
+typedef struct oxc_terrain_brush_context {
+  uint32_t struct_size; /* sizeof(oxc_terrain_brush_context) */
+  uint32_t stages;      /* OXC_TERRAIN_BRUSH_TRACE | OXC_TERRAIN_BRUSH_APPLY */
+  oxc_terrain_brush_params params;
+  oxc_buffer heightmap;   /* in: u16 [resolution.y][.x], R16 Unorm */
+  oxc_buffer height_edit; /* in/out (apply, modes 0 - 3): f32 [resolution.y][.x] */
+  oxc_buffer splat_edit;  /* in/out (apply, PaintLayer): u32 [resolution.y][.x], R8G8B8A8 Unorm */
+  oxc_buffer hit;         /* device memory, 16 bytes of oxc_terrain_brush_hit: written by trace, read by apply */
+  oxc_buffer region;      /* device memory, 16 bytes of oxc_terrain_region: written by trace */
+} oxc_terrain_brush_context;
+
+oxc_status oxc_apply_terrain_brush(oxc_ctx* ctx, const oxc_terrain_brush_context* context, void* hip_stream);
+
 /* ---- multi-GPU exchange: one process per GPU, RCCL over xGMI ---------------------------
  * The meshlet-instance array shards by contiguous range and every rank culls its shard on its own; the only
  * exchanges of the path are (1) the per-rank counters {emitted meshlets, early, late, index count} to every rank

@@ -1,5 +1,6 @@
 // oxcull_abi_terrain.cpp -- the terrain map producers of liboxcull.so's C ABI: oxc_generate_terrain_maps (height, ridge, normal, splat and the
-// per-patch min / max).  The terrain cull, their consumer, is in oxcull_abi_cull.cpp.
+// per-patch min / max) and oxc_apply_terrain_brush (the brush ray trace and the strokes into the edit images).  The terrain cull, their
+// consumer, is in oxcull_abi_cull.cpp.
 #include "oxcull_host.hpp"
 
 namespace {
@@ -12,7 +13,33 @@ struct MapBuffer {
   uint64_t have, need;
   uint32_t align, touched_by, written_by;
   bool may_be_null;
+  const char* too_small = " is smaller than its extent";
 };
+
+// The buffer limits both calls share, over the buffers `stages` touches: in the table's order non-null, aligned, large enough; then no
+// written buffer sharing a byte with another touched one.  The message of the first broken rule, or OXC_OK.
+template <size_t N>
+oxc_status check_buffers(oxc_ctx* ctx, const char* entry, const MapBuffer (&buffers)[N], uint32_t stages) {
+  for (const MapBuffer& b : buffers) {
+    if (!(b.touched_by & stages)) continue;
+    if (!b.dptr) {
+      if (b.may_be_null) continue;
+      return bad_arg(ctx, entry, b.name, " must not be null");
+    }
+    if (reinterpret_cast<uintptr_t>(b.dptr) & (b.align - 1u)) return bad_arg(ctx, entry, b.name, " must be aligned to its texel");
+    if (b.have < b.need) return bad_arg(ctx, entry, b.name, b.too_small);
+  }
+  for (const MapBuffer& w : buffers) {
+    if (!(w.written_by & stages)) continue;
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(w.dptr);
+    for (const MapBuffer& o : buffers) {
+      if (&o == &w || !(o.touched_by & stages) || !o.dptr) continue;
+      const uintptr_t olo = reinterpret_cast<uintptr_t>(o.dptr);
+      if (ByteSpan{lo, lo + (uintptr_t)w.need}.overlaps({olo, olo + (uintptr_t)o.need})) return bad_arg(ctx, entry, w.name, " must not overlap ", o.name);
+    }
+  }
+  return OXC_OK;
+}
 
 // roundup(dispatch, group) as a thread count, capped at roundup(extent, group): what lies beyond cannot land inside the map without wrapping
 uint32_t threads_of(uint32_t dispatch, uint32_t extent, uint32_t group) {
@@ -50,26 +77,9 @@ oxc_status oxc_generate_terrain_maps(oxc_ctx* ctx, const oxc_terrain_maps_contex
       {"splatmap", c->splatmap.dptr, c->splatmap.bytes, texels * 4u, 4u, D, D, false},
       {"height_edit", c->height_edit.dptr, c->height_edit.bytes, texels * 4u, 4u, G, 0u, false},
       {"splat_edit", c->splat_edit.dptr, c->splat_edit.bytes, texels * 4u, 4u, D, 0u, false},
-      {"patch_minmax", mm.dptr, mm_extent ? patches * 8u : 0u, patches * 8u, 8u, M, M, false},
+      {"patch_minmax", mm.dptr, mm_extent ? patches * 8u : 0u, patches * 8u, 8u, M, M, false, " must be one RG32F level at offset 0 of patch_count's extent"},
   };
-  for (const MapBuffer& b : buffers) {
-    if (!(b.touched_by & stages)) continue;
-    if (!b.dptr) {
-      if (b.may_be_null) continue;
-      return bad_arg(ctx, entry, b.name, " must not be null");
-    }
-    if (reinterpret_cast<uintptr_t>(b.dptr) & (b.align - 1u)) return bad_arg(ctx, entry, b.name, " must be aligned to its texel");
-    if (b.have < b.need) return bad_arg(ctx, entry, b.name, &b == &buffers[7] ? " must be one RG32F level at offset 0 of patch_count's extent" : " is smaller than its extent");
-  }
-  for (const MapBuffer& w : buffers) {
-    if (!(w.written_by & stages)) continue;
-    const uintptr_t lo = reinterpret_cast<uintptr_t>(w.dptr);
-    for (const MapBuffer& o : buffers) {
-      if (&o == &w || !(o.touched_by & stages) || !o.dptr) continue;
-      const uintptr_t olo = reinterpret_cast<uintptr_t>(o.dptr);
-      if (ByteSpan{lo, lo + (uintptr_t)w.need}.overlaps({olo, olo + (uintptr_t)o.need})) return bad_arg(ctx, entry, w.name, " must not overlap ", o.name);
-    }
-  }
+  if (const oxc_status st = check_buffers(ctx, entry, buffers, stages)) return st;
 
   OXC_ENTER(ctx, hip_stream, s);
   TerrainMapsArgs a;
@@ -94,6 +104,49 @@ oxc_status oxc_generate_terrain_maps(oxc_ctx* ctx, const oxc_terrain_maps_contex
   if (stages & G) launch_terrain_generate(a, s);
   if (stages & D) launch_terrain_derive(a, s);
   if (stages & M) launch_terrain_minmax(a, s);
+  OXC_HIP(ctx, hipGetLastError());
+  return OXC_OK;
+}
+
+oxc_status oxc_apply_terrain_brush(oxc_ctx* ctx, const oxc_terrain_brush_context* c, void* hip_stream) {
+  if (!ctx) return OXC_INVALID_ARG;
+  if (!c || c->struct_size != sizeof(oxc_terrain_brush_context)) return fail(ctx, OXC_INVALID_ARG, "apply_terrain_brush: bad context / struct_size");
+  const char* const entry = "apply_terrain_brush";
+  const oxc_terrain_brush_params& p = c->params;
+  const uint32_t stages = c->stages;
+  if (stages == 0u || (stages & ~(OXC_TERRAIN_BRUSH_TRACE | OXC_TERRAIN_BRUSH_APPLY))) return bad_arg(ctx, entry, "stages must be a non-empty mask of OXC_TERRAIN_BRUSH_TRACE | OXC_TERRAIN_BRUSH_APPLY");
+  const uint32_t *res = p.resolution, *pc = p.patch_count;
+  if (res[0] < 1u || res[0] > 16384u || res[1] < 1u || res[1] > 16384u) return bad_arg(ctx, entry, "params.resolution: every side must be in 1 .. 16384");
+  if (pc[0] < 1u || pc[0] > 4096u || pc[1] < 1u || pc[1] > 4096u) return bad_arg(ctx, entry, "params.patch_count: every side must be in 1 .. 4096");
+  if (p.mode > OXC_TERRAIN_BRUSH_PAINT_LAYER) return bad_arg(ctx, entry, "params.mode must be in 0 .. 4");
+  if (!std::isfinite(p.radius_texels) || !(p.radius_texels >= 0.0f && p.radius_texels <= 4096.0f)) return bad_arg(ctx, entry, "params.radius_texels must be finite and in 0 .. 4096");
+  if (!std::isfinite(p.falloff)) return bad_arg(ctx, entry, "params.falloff must be finite");
+
+  // what the requested stages do, as the buffer table sees it: the trace, the apply of a height mode, the apply of PaintLayer
+  const uint32_t T = 1u, H = 2u, P = 4u;
+  const uint32_t uses = (stages & OXC_TERRAIN_BRUSH_TRACE ? T : 0u) | (stages & OXC_TERRAIN_BRUSH_APPLY ? (p.mode == OXC_TERRAIN_BRUSH_PAINT_LAYER ? P : H) : 0u);
+  const uint64_t texels = (uint64_t)res[0] * res[1];
+  const MapBuffer buffers[] = {
+      {"heightmap", c->heightmap.dptr, c->heightmap.bytes, texels * 2u, 2u, T | H, 0u, false},
+      {"height_edit", c->height_edit.dptr, c->height_edit.bytes, texels * 4u, 4u, H, H, false},
+      {"splat_edit", c->splat_edit.dptr, c->splat_edit.bytes, texels * 4u, 4u, P, P, false},
+      {"hit", c->hit.dptr, c->hit.bytes, 16u, 8u, T | H | P, T, false},
+      {"region", c->region.dptr, c->region.bytes, 16u, 8u, T, T, false},
+  };
+  if (const oxc_status st = check_buffers(ctx, entry, buffers, uses)) return st;
+
+  OXC_ENTER(ctx, hip_stream, s);
+  TerrainBrushArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.p = p;
+  a.groups = (2u * (uint32_t)std::ceil(p.radius_texels) + 1u + 15u) / 16u;  // the reference's dispatch: at most 513
+  a.heightmap = static_cast<const uint16_t*>(c->heightmap.dptr);
+  a.height_edit = static_cast<float*>(c->height_edit.dptr);
+  a.splat_edit = static_cast<uint32_t*>(c->splat_edit.dptr);
+  a.hit = static_cast<uint32_t*>(c->hit.dptr);
+  a.region = static_cast<uint32_t*>(c->region.dptr);
+  if (stages & OXC_TERRAIN_BRUSH_TRACE) launch_terrain_brush_trace(a, s);
+  if (stages & OXC_TERRAIN_BRUSH_APPLY) launch_terrain_brush_apply(a, s);
   OXC_HIP(ctx, hipGetLastError());
   return OXC_OK;
 }

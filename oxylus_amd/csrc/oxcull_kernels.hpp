@@ -798,6 +798,18 @@ void terrain_maps_constants(TerrainMapsArgs& a);  // fills the folded values fro
 void launch_terrain_generate(const TerrainMapsArgs& a, hipStream_t s);
 void launch_terrain_derive(const TerrainMapsArgs& a, hipStream_t s);
 void launch_terrain_minmax(const TerrainMapsArgs& a, hipStream_t s);
+// oxcull_terrain_brush.hip: the terrain brush (oxc_apply_terrain_brush); the kernels evaluate the direction and the span themselves
+struct TerrainBrushArgs {
+  oxc_terrain_brush_params p;
+  uint32_t groups;  // of 16 x 16 threads a side: (2 * u32(ceil(radius_texels)) + 1 + 15) / 16, at most 513
+  const uint16_t* heightmap;
+  float* height_edit;
+  uint32_t* splat_edit;
+  uint32_t* hit;     // {f32 world_position[3], u32 valid}: written by trace, read by apply
+  uint32_t* region;  // {texel_origin.xy, patch_origin.xy}
+};
+void launch_terrain_brush_trace(const TerrainBrushArgs& a, hipStream_t s);
+void launch_terrain_brush_apply(const TerrainBrushArgs& a, hipStream_t s);
 // oxcull_bounds.hip: meshlet bounds producer
 void launch_build_meshlet_bounds(const float* pos, uint32_t vertex_count, const void* meshlets, uint32_t meshlet_count, const uint32_t* vidx,
                                  const uint8_t* micro, void* out_bounds, float* out_mesh6, void* out_qpos, float* meshlet_minmax, float* normals,

@@ -14,7 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include "oxcull_kernels.hpp"
-#include "oxcull_pixel_device.hpp"
+#include "oxcull_terrain_device.hpp"  // hash2 (T2), noised (T3), clamp_lo_hi: shared with the terrain brush
 
 namespace oxc {
 
@@ -35,13 +35,7 @@ void terrain_maps_constants(TerrainMapsArgs& a) {
 namespace {
 constexpr float kTau = 6.283185307179586476925286766559f;
 constexpr float kEpsilon = 1e-10f;  // TERRAIN_EPSILON
-constexpr float kK0 = 0.3183099f, kK1 = 0.3678794f;
 
-struct V2 {
-  float x, y;
-};
-
-OXC_DEV float clamp_lo_hi(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
 OXC_DEV float ease_out(float t) {
   const float v = 1.0f - saturate_f(t);
   return 1.0f - v * v;
@@ -57,33 +51,6 @@ OXC_DEV float smoothstep_f(float e0, float e1, float x) {
 OXC_DEV float opaque(float x) {
   asm("" : "+v"(x));
   return x;
-}
-
-// T2; (sx, sy) = f32(seed) * (0.06711056f, 0.00583715f)
-OXC_DEV V2 hash2(float x, float y, float sx, float sy) {
-  const float qx = (x + sx) * kK0 + kK1, qy = (y + sy) * kK1 + kK0;
-  const float t = fract_f((qx * qy) * (qx + qy));
-  return {-1.0f + 2.0f * fract_f((16.0f * kK0) * t), -1.0f + 2.0f * fract_f((16.0f * kK1) * t)};
-}
-
-// T3: (value, derivative.x, derivative.y)
-OXC_DEV V3 noised(float px, float py, float sx, float sy) {
-  const float ix = floorf(px), iy = floorf(py);
-  const float fx = px - ix, fy = py - iy;
-  const float ux = ((fx * fx) * fx) * (fx * (fx * 6.0f - 15.0f) + 10.0f), uy = ((fy * fy) * fy) * (fy * (fy * 6.0f - 15.0f) + 10.0f);
-  const float dux = ((30.0f * fx) * fx) * (fx * (fx - 2.0f) + 1.0f), duy = ((30.0f * fy) * fy) * (fy * (fy - 2.0f) + 1.0f);
-  const V2 ga = hash2(ix, iy, sx, sy), gb = hash2(ix + 1.0f, iy, sx, sy), gc = hash2(ix, iy + 1.0f, sx, sy), gd = hash2(ix + 1.0f, iy + 1.0f, sx, sy);
-  const float va = ga.x * fx + ga.y * fy;
-  const float vb = gb.x * (fx - 1.0f) + gb.y * fy;
-  const float vc = gc.x * fx + gc.y * (fy - 1.0f);
-  const float vd = gd.x * (fx - 1.0f) + gd.y * (fy - 1.0f);
-  const float k = ((va - vb) - vc) + vd;
-  const float uxy = ux * uy;
-  V3 r;
-  r.x = ((va + ux * (vb - va)) + uy * (vc - va)) + uxy * k;
-  r.y = (((ga.x + ux * (gb.x - ga.x)) + uy * (gc.x - ga.x)) + uxy * (((ga.x - gb.x) - gc.x) + gd.x)) + dux * ((uy * k + vb) - va);
-  r.z = (((ga.y + ux * (gb.y - ga.y)) + uy * (gc.y - ga.y)) + uxy * (((ga.y - gb.y) - gc.y) + gd.y)) + duy * ((ux * k + vc) - va);
-  return r;
 }
 
 // the origin pair of a kernel: words `first`, `first + 1` of the region record, or zero without one

@@ -13,6 +13,7 @@
 // programmer errors (Oxylus/include/Utils/Log.hpp:38-47); the shim throws std::runtime_error
 // carrying oxc_last_error() instead of aborting.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <stdexcept>
@@ -612,6 +613,13 @@ public:
     context.struct_size = sizeof context;
     check(oxc_generate_terrain_maps(ctx_, &context, stream_));
   }
+  // The terrain brush (Passes/Terrain.cpp:35-132): the stages of context.stages in the order trace, apply.  The free function
+  // apply_terrain_brush below does what the reference's method does after its params are built.  Rules: include/oxcull.h,
+  // oxc_apply_terrain_brush.
+  auto apply_terrain_brush(oxc_terrain_brush_context context) -> void {
+    context.struct_size = sizeof context;
+    check(oxc_apply_terrain_brush(ctx_, &context, stream_));
+  }
   auto build_meshlet_bounds(oxc_meshlet_bounds_desc desc) -> void {
     desc.struct_size = sizeof desc;
     check(oxc_build_meshlet_bounds(ctx_, &desc, stream_));
@@ -636,6 +644,9 @@ namespace GPU {
 using TerrainErosion = oxc_terrain_erosion;    // SceneGPU.hpp:358-372, 80 bytes
 using TerrainGenerate = oxc_terrain_generate;  // SceneGPU.hpp:374-384, 120 bytes
 using TerrainDerive = oxc_terrain_derive;      // SceneGPU.hpp:386-395, 40 bytes
+using TerrainBrushParams = oxc_terrain_brush_params;  // scene.slang:606-621, 96 bytes
+using TerrainBrushHit = oxc_terrain_brush_hit;        // scene.slang:601-604
+using TerrainRegion = oxc_terrain_region;             // scene.slang:588-591
 struct TerrainMinMax {                         // SceneGPU.hpp:397-400
   uint32_t resolution[2] = {};
   uint32_t patch_count[2] = {};
@@ -693,6 +704,46 @@ inline auto terrain_minmax_pass(TerrainMaps& maps, const GPU::TerrainMinMax& set
   c.patch_count[0] = settings.patch_count[0], c.patch_count[1] = settings.patch_count[1];
   c.dispatch_patches[0] = dispatch_patches.x, c.dispatch_patches[1] = dispatch_patches.y;
   maps.renderer->generate_terrain_maps(c);
+}
+
+// RendererInstance.hpp's TerrainBrushContext of the reference, with the params the method builds from the Terrain (Passes/Terrain.cpp:42-67)
+// and the two settings records it copies from it carried beside the maps.  hit_buffer and maps.region are device memory, 16 bytes each.
+struct TerrainBrushContext {
+  TerrainMaps maps = {};
+  Buffer hit_buffer = {};
+  GPU::TerrainBrushParams params = {};
+  bool painting = false;
+  GPU::TerrainGenerate generate_settings = {};  // terrain.generate_settings, terrain.derive_settings with the fields bake fills
+  GPU::TerrainDerive derive_settings = {};
+};
+
+// RendererInstance::apply_terrain_brush (Passes/Terrain.cpp:69-156) after the params are built: trace; if painting, apply, then the three
+// regional passes with the reference's dispatch sizes.
+inline auto apply_terrain_brush(TerrainBrushContext& context) -> void {
+  if (!context.maps.renderer) throw std::runtime_error("TerrainMaps::renderer is not set");
+  const GPU::TerrainBrushParams& params = context.params;
+  oxc_terrain_brush_context c = {};
+  c.stages = OXC_TERRAIN_BRUSH_TRACE | (context.painting ? OXC_TERRAIN_BRUSH_APPLY : 0u);
+  c.params = params;
+  c.heightmap = context.maps.heightmap, c.height_edit = context.maps.height_edit, c.splat_edit = context.maps.splat_edit;
+  c.hit = context.hit_buffer, c.region = context.maps.region;
+  context.maps.renderer->apply_terrain_brush(c);
+  if (!context.painting) return;
+
+  GPU::TerrainGenerate generate_settings = context.generate_settings;
+  GPU::TerrainDerive derive_settings = context.derive_settings;
+  GPU::TerrainMinMax minmax_settings = {};
+  for (int k = 0; k < 2; k++) {
+    generate_settings.resolution[k] = derive_settings.resolution[k] = minmax_settings.resolution[k] = params.resolution[k];
+    minmax_settings.patch_count[k] = params.patch_count[k];
+  }
+  const uint32_t derive_texels = 2u * static_cast<uint32_t>(std::ceil(params.radius_texels + 1.0f)) + 1u;
+  terrain_generate_pass(context.maps, generate_settings, uvec2{derive_texels, derive_texels});
+  terrain_derive_pass(context.maps, derive_settings, uvec2{derive_texels, derive_texels});
+  const float patch_texels_x = static_cast<float>(params.resolution[0]) / static_cast<float>(params.patch_count[0]);
+  const float patch_texels_y = static_cast<float>(params.resolution[1]) / static_cast<float>(params.patch_count[1]);
+  const uint32_t derive_patches = static_cast<uint32_t>(std::ceil(static_cast<float>(derive_texels) / std::min(patch_texels_x, patch_texels_y))) + 1u;
+  terrain_minmax_pass(context.maps, minmax_settings, uvec2{derive_patches, derive_patches});
 }
 
 }  // namespace ox::amd

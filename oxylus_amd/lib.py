@@ -46,6 +46,8 @@ TONEMAP_NONE, TONEMAP_ACES, TONEMAP_AGX, TONEMAP_GT7 = 0, 1, 2, 3  # GPU::Tonema
 TONEMAP_OUT_R8G8B8A8_SRGB, TONEMAP_OUT_B8G8R8A8_SRGB, TONEMAP_OUT_R8G8B8A8_UNORM = 0, 1, 2  # oxc_tonemap_context.output_format
 LIGHT_KIND_DIRECTIONAL, LIGHT_KIND_POINT, LIGHT_KIND_SPOT = 0, 1, 2  # GPU::LightKind
 TERRAIN_GENERATE, TERRAIN_DERIVE, TERRAIN_MINMAX, TERRAIN_ALL = 1, 2, 4, 7  # oxc_terrain_maps_context.stages
+TERRAIN_BRUSH_TRACE, TERRAIN_BRUSH_APPLY, TERRAIN_BRUSH_ALL = 1, 2, 3  # oxc_terrain_brush_context.stages
+TERRAIN_BRUSH_RAISE, TERRAIN_BRUSH_SMOOTH, TERRAIN_BRUSH_FLATTEN, TERRAIN_BRUSH_NOISE, TERRAIN_BRUSH_PAINT_LAYER = 0, 1, 2, 3, 4  # GPU::TerrainBrushMode
 
 
 class Buffer(C.Structure):
@@ -699,6 +701,51 @@ class TerrainMapsContext(C.Structure):
     ]
 
 
+class TerrainBrushParams(C.Structure):
+    _c_name_ = "oxc_terrain_brush_params"
+    _fields_ = [
+        ("ray_origin", C.c_float * 3),
+        ("radius_texels", C.c_float),
+        ("ray_direction", C.c_float * 3),
+        ("strength", C.c_float),
+        ("resolution", C.c_uint32 * 2),
+        ("world_min", C.c_float * 2),
+        ("world_size", C.c_float * 2),
+        ("inv_world_size", C.c_float * 2),
+        ("patch_count", C.c_uint32 * 2),
+        ("base_height", C.c_float),
+        ("height_scale", C.c_float),
+        ("falloff", C.c_float),
+        ("flatten_height", C.c_float),
+        ("mode", C.c_uint32),
+        ("layer", C.c_uint32),
+    ]
+
+
+class TerrainBrushHit(C.Structure):
+    _c_name_ = "oxc_terrain_brush_hit"
+    _fields_ = [("world_position", C.c_float * 3), ("valid", C.c_uint32)]
+
+
+class TerrainRegion(C.Structure):
+    _c_name_ = "oxc_terrain_region"
+    _fields_ = [("texel_origin", C.c_uint32 * 2), ("patch_origin", C.c_uint32 * 2)]
+
+
+class TerrainBrushContext(C.Structure):
+    _c_name_ = "oxc_terrain_brush_context"
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("stages", C.c_uint32),
+        ("params", TerrainBrushParams),
+        ("heightmap", Buffer),
+        ("height_edit", Buffer),
+        ("splat_edit", Buffer),
+        ("hit", Buffer),
+        ("region", Buffer),
+    ]
+
+
 class MeshBuildDesc(C.Structure):
     _c_name_ = "oxc_mesh_build_desc"
     _fields_ = [("struct_size", C.c_uint32), ("vertex_count", C.c_uint32), ("index_count", C.c_uint32), ("max_lods", C.c_uint32), ("max_vertices", C.c_uint32),
@@ -765,6 +812,7 @@ PROTOTYPES = {
     "oxc_generate_sky_ibl": (_status, [_vp, _P(SkyIblContext), _vp]),
     "oxc_apply_pbr_atmosphere": (_status, [_vp, _P(PbrAtmosphereContext), _vp]),
     "oxc_generate_terrain_maps": (_status, [_vp, _P(TerrainMapsContext), _vp]),
+    "oxc_apply_terrain_brush": (_status, [_vp, _P(TerrainBrushContext), _vp]),
     "oxc_draw_physical_pages": (_status, [_vp, _P(PreparedFrame), _P(VsmDrawContext), _vp]),
     "oxc_debug_vsm_draw_stats": _stats,
     "oxc_resolve_shadowmap": (_status, [_vp, _P(ShadowResolveContext), _vp]),

@@ -856,6 +856,68 @@ class TerrainMapsContext(Marshalled):
 
 
 @dataclass
+class TerrainBrushParams(Marshalled):
+    """GPU::TerrainBrushParams (scene.slang:606-621), field for field.  `engine` forms them from a Terrain's and its brush's values the way
+    RendererInstance::apply_terrain_brush does (Passes/Terrain.cpp:42-67), in binary32."""
+    _ctype = L.TerrainBrushParams
+    ray_origin: tuple = (0.0, 0.0, 0.0)
+    radius_texels: float = 0.0
+    ray_direction: tuple = (0.0, -1.0, 0.0)
+    strength: float = 0.0
+    resolution: tuple = (0, 0)
+    world_min: tuple = (0.0, 0.0)
+    world_size: tuple = (0.0, 0.0)
+    inv_world_size: tuple = (0.0, 0.0)
+    patch_count: tuple = (0, 0)
+    base_height: float = 0.0
+    height_scale: float = 0.0
+    falloff: float = 1.0
+    flatten_height: float = 0.0
+    mode: int = L.TERRAIN_BRUSH_RAISE
+    layer: int = 0
+
+    @staticmethod
+    def engine(resolution, patch_count, ray_origin, ray_direction, world_size=(1024.0, 1024.0), height_range=(0.0, 400.0), radius_world: float = 32.0,
+               mode: int = L.TERRAIN_BRUSH_RAISE, layer: int = 0, falloff: float = 1.0, height_rate: float = 4.0, blend_rate: float = 3.0,
+               flatten_height_world: float = 0.0, invert: bool = False, delta_time: float = 1.0 / 60.0, world_origin=(0.0, 0.0, 0.0)) -> "TerrainBrushParams":
+        import numpy as np
+
+        F = np.float32
+        ws, res = [F(v) for v in world_size], [F(float(v)) for v in resolution]
+        texel = [ws[k] / res[k] for k in range(2)]  # Terrain::texel_world_size
+        base, scale = F(world_origin[1]) + F(height_range[0]), F(height_range[1]) - F(height_range[0])
+        height_scale = max(scale, F(1e-3))
+        dt = min(max(F(delta_time), F(0.0)), F(1.0) / F(30.0))
+        displaces = mode in (L.TERRAIN_BRUSH_RAISE, L.TERRAIN_BRUSH_NOISE)
+        strength = F(height_rate) * dt / height_scale if displaces else min(max(F(blend_rate) * dt, F(0.0)), F(1.0))
+        flatten = min(max((F(flatten_height_world) - base) / height_scale, F(0.0)), F(1.0))
+        return TerrainBrushParams(tuple(ray_origin), float(F(radius_world) / max(texel[0], texel[1])), tuple(ray_direction), float(-strength if invert else strength),
+                                  tuple(int(v) for v in resolution), tuple(float(F(world_origin[2 * k]) - ws[k] * F(0.5)) for k in range(2)), tuple(float(w) for w in ws),
+                                  tuple(float(F(1.0) / w) for w in ws), tuple(int(v) for v in patch_count), float(base), float(scale), float(falloff),
+                                  float(flatten), int(mode), int(layer))
+
+
+@dataclass
+class TerrainBrushContext(Marshalled):
+    """oxc_terrain_brush_context: the brush's ray trace and its stroke into the edit images (Passes/Terrain.cpp:35-132).  `hit` int32 [4]
+    ({f32 world_position[3], u32 valid}) and `region` int32 [4] on the device; `region` is what TerrainMapsContext.region takes.  `over` binds a
+    TerrainMapsContext's heightmap and edit images and allocates the two records."""
+    _ctype = L.TerrainBrushContext
+    params: TerrainBrushParams
+    heightmap: Optional[torch.Tensor]    # int16 [H, W]: R16 Unorm
+    height_edit: Optional[torch.Tensor]  # float32 [H, W]
+    splat_edit: Optional[torch.Tensor]   # int32 [H, W]
+    hit: Optional[torch.Tensor]          # int32 [4]
+    region: Optional[torch.Tensor]       # int32 [4]
+    stages: int = L.TERRAIN_BRUSH_ALL
+
+    @staticmethod
+    def over(maps: TerrainMapsContext, params: TerrainBrushParams, **settings) -> "TerrainBrushContext":
+        z = lambda: torch.zeros((4,), dtype=torch.int32, device=maps.heightmap.device)  # noqa: E731
+        return TerrainBrushContext(params, maps.heightmap, maps.height_edit, maps.splat_edit, z(), z() if maps.region is None else maps.region, **settings)
+
+
+@dataclass
 class VisbufferDecodeContext(Marshalled):
     """oxc_decode_context: RendererInstance::decode_visbuffer (Passes/DrawGeometry.cpp:192-274), the geometry and material-factor half of
     visbuffer_decode.slang.  `create` takes the visbuffer and the depth as oxc_draw_visbuffer resolved them, the matrix they were drawn with and
@@ -1184,6 +1246,11 @@ class RendererInstance:
         """Passes/PBR.cpp:52-94, the sky_ibl pass of draw_atmosphere: 64 samples of sky_view_lut per cube texel, blended into the texel's own
         history, one launch (include/oxcull.h, oxc_generate_sky_ibl).  After draw_atmosphere; `context.frame_index` is the caller's to advance."""
         self._call("oxc_generate_sky_ibl", context, stream)
+
+    def apply_terrain_brush(self, context: TerrainBrushContext, stream=None) -> None:
+        """Passes/Terrain.cpp:35-132 (terrain_brush_trace, terrain_brush_apply): the stages of context.stages in the order trace, apply
+        (include/oxcull.h, oxc_apply_terrain_brush).  `context.region` is the record generate_terrain_maps reads for the regional re-bake."""
+        self._call("oxc_apply_terrain_brush", context, stream)
 
     def generate_terrain_maps(self, context: TerrainMapsContext, stream=None) -> None:
         """Scene/Terrain.cpp:406-461 and Passes/Terrain.cpp:134-156 (terrain_generate, terrain_derive, terrain_minmax): the stages of
