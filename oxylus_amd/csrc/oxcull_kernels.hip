@@ -38,6 +38,11 @@ OXC_DEV uint32_t wave_incl_scan(uint32_t v, int lane) {
   }
   return v;
 }
+// A lane's rank among the set bits of a ballot (v_mbcnt with the ballot as its mask operand).
+OXC_DEV uint32_t ballot_rank(uint64_t ballot) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u)); }
+// Hand-off through LDS between lanes of ONE wave: a wave's LDS traffic is in order, so waiting for its own operations is enough and
+// no barrier is needed.
+OXC_DEV void lds_handoff() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 // sum over a 256-thread block; result valid in every thread.  s_red: 4 words of LDS.
 OXC_DEV uint32_t block_sum_256(uint32_t v, uint32_t* s_red) {
   v = wave_sum(v);
@@ -283,7 +288,7 @@ OXC_DEV void prepare_body(const PrepareArgs& a, const uint32_t view) {
       out->vidx = lod.indirect_vertex_indices;
       out->positions = mesh.vertex_positions;
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // same-wave LDS hand-off (the eight lanes of an instance sit in one wave)
+    lds_handoff();  // (the eight lanes of an instance sit in one wave)
     if (valid) {
       const uint4* src = reinterpret_cast<const uint4*>(out);
       uint4* dst = reinterpret_cast<uint4*>(rows + mi);
@@ -291,7 +296,7 @@ OXC_DEV void prepare_body(const PrepareArgs& a, const uint32_t view) {
 #pragma unroll
       for (uint32_t k = 0; k < 3u; k++) dst[sub + 8u * k] = src[sub + 8u * k];
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the LDS rows are rewritten by the next round
+    lds_handoff();  // the LDS rows are rewritten by the next round
   }
 }
 
@@ -463,6 +468,66 @@ OXC_DEV void update_visibility_mask(uint32_t* __restrict__ mask, uint32_t idx, b
 typedef const uint32_t __attribute__((address_space(4))) * kconst32p;
 OXC_DEV kconst32p const_row(const InstCache* cache, uint32_t mi) { return (kconst32p)(reinterpret_cast<uint64_t>(cache + mi)); }
 
+// ---- pieces the meshlet test kernels share ----
+// Centre / extent of a 16-byte MeshletBounds record: six halfs in b.x, b.y (low), b.z, b.w (low).
+struct BoundsBox {
+  float cx, cy, cz, ex, ey, ez;
+};
+OXC_DEV BoundsBox decode_box(const uint4& b) {
+  BoundsBox q;
+  q.cx = dequantize_half(b.x & 0xFFFFu), q.cy = dequantize_half(b.x >> 16), q.cz = dequantize_half(b.y & 0xFFFFu);
+  q.ex = dequantize_half(b.z & 0xFFFFu), q.ey = dequantize_half(b.z >> 16), q.ez = dequantize_half(b.w & 0xFFFFu);
+  return q;
+}
+// The cone operands of the row's mesh instance, by scalar loads from the InstCache row.
+OXC_DEV ConeU load_cone_operands(const kconst32p row) {
+  ConeU cu;
+#pragma unroll
+  for (int k = 0; k < 9; k++) cu.nm[k] = asf(row[kRowNm + k]);
+#pragma unroll
+  for (int k = 0; k < 6; k++) cu.w2[k >> 1][k & 1] = asf(row[kRowWorld2 + k]);
+#pragma unroll
+  for (int k = 0; k < 2; k++) cu.wt2[k] = asf(row[kRowWorldT2 + k]);
+#pragma unroll
+  for (int k = 0; k < 4; k++) cu.wr2[k] = asf(row[kRowWorldR2 + k]);
+  cu.scale_max = asf(row[kRowScale]);
+  return cu;
+}
+// The two-tier cone test of record `b` (centre q*, extent r* decoded from it): tier 1 for every lane, and when some lane the caller still
+// `consider`s sits within the margin (wave-uniform ballot) the canonical IEEE path decides for the undecided lanes.
+OXC_DEV bool cone_two_tier(const ConeU& cu, float camx, float camy, float camz, float qx, float qy, float qz, float rx, float ry, float rz, const uint4& b, bool consider) {
+  const f2 axy = s8_over_127_x2((int32_t)(b.y << 8) >> 24, (int32_t)b.y >> 24);
+  const f2 azc = s8_over_127_x2((int32_t)(b.w << 8) >> 24, (int32_t)b.w >> 24);
+  const int tier1 = cone_visible_fast(cu, camx, camy, camz, qx, qy, qz, rx, ry, rz, axy.x, axy.y, azc.x, azc.y);
+  bool cone_ok = tier1 == 1;
+  if (__builtin_amdgcn_ballot_w64(consider && tier1 == 2)) {
+    const bool exact = cone_visible(cu, camx, camy, camz, qx, qy, qz, rx, ry, rz, axy.x, axy.y, azc.x, azc.y);
+    cone_ok = tier1 == 2 ? exact : cone_ok;
+  }
+  return cone_ok;
+}
+// The instance of the first lane that is still to be decided (bit 0 of st), in the first group that has one (wave-uniform).
+template <int G>
+OXC_DEV bool first_undecided_instance(const uint32_t (&st)[G], const uint2 (&rec)[G], uint32_t& mi_u) {
+  mi_u = 0;
+  bool found = false;
+#pragma unroll
+  for (int j = 0; j < G; j++) {
+    const uint64_t p = __builtin_amdgcn_ballot_w64((st[j] & 1u) != 0u);
+    if (!found && p) {
+      mi_u = readlane_u(rec[j].x, __ffsll((unsigned long long)p) - 1);
+      found = true;
+    }
+  }
+  return found;
+}
+// One ticket of a counter (lane 0; the value is read from there once the round trip is over)
+OXC_DEV uint32_t draw_ticket(uint32_t* ticket, int lane) {
+  uint32_t t = 0;
+  if (lane == 0) t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return t;
+}
+
 // MeshletInstance records and MeshletBounds are read exactly once per call: `nt` loads (measured on configs[1]:
 // test kernel 28.0 -> 27.4 us per 4M meshlets, whole job +2.5 %).
 #define OXC_LOAD_MLI load_stream_u2
@@ -492,18 +557,8 @@ OXC_DEV void meshlets_plain_body(const MeshletTestArgs& a) {
     for (int j = 0; j < G; j++) st[j] = ((group0 + j) * 64 + lane < N) ? 1u : 0u;
 
     for (;;) {
-      // leader = first undecided lane of the first group that has one (wave-uniform)
-      uint32_t mi_u = 0;
-      bool found = false;
-#pragma unroll
-      for (int j = 0; j < G; j++) {
-        const uint64_t p = __builtin_amdgcn_ballot_w64((st[j] & 1u) != 0u);
-        if (!found && p) {
-          mi_u = readlane_u(rec[j].x, __ffsll((unsigned long long)p) - 1);
-          found = true;
-        }
-      }
-      if (!found) break;
+      uint32_t mi_u;
+      if (!first_undecided_instance<G>(st, rec, mi_u)) break;
       const kconst32p row = const_row(a.cache, mi_u);
       const uint64_t bounds = (uint64_t)row[kRowBounds] | ((uint64_t)row[kRowBounds + 1] << 32);
       uint4 bnd[G];
@@ -526,8 +581,8 @@ OXC_DEV void meshlets_plain_body(const MeshletTestArgs& a) {
 #pragma unroll
         for (int j = 0; j < G; j++) {
           const uint4 b = bnd[j];
-          cx[j] = dequantize_half(b.x & 0xFFFFu), cy[j] = dequantize_half(b.x >> 16), cz[j] = dequantize_half(b.y & 0xFFFFu);
-          ex[j] = dequantize_half(b.z & 0xFFFFu), ey[j] = dequantize_half(b.z >> 16), ez[j] = dequantize_half(b.w & 0xFFFFu);
+          const BoundsBox q = decode_box(b);
+          cx[j] = q.cx, cy[j] = q.cy, cz[j] = q.cz, ex[j] = q.ex, ey[j] = q.ey, ez[j] = q.ez;
           const bool vis = mine[j] & test_frustum_planes(pl, sg, cx[j], cy[j], cz[j], ex[j], ey[j], ez[j]);
           // cutoff >= 1.0 <=> s8 == 127: cone test skipped (cull_meshlets.slang:52)
           const bool nc = vis & (((int32_t)b.w >> 24) != 127);
@@ -540,16 +595,7 @@ OXC_DEV void meshlets_plain_body(const MeshletTestArgs& a) {
       }
       // ---- phase 2: normal cone, only when some frustum survivor of this instance needs it
       if (any_need) {
-        ConeU cu;
-#pragma unroll
-        for (int k = 0; k < 9; k++) cu.nm[k] = asf(row[kRowNm + k]);
-#pragma unroll
-        for (int k = 0; k < 6; k++) cu.w2[k >> 1][k & 1] = asf(row[kRowWorld2 + k]);
-#pragma unroll
-        for (int k = 0; k < 2; k++) cu.wt2[k] = asf(row[kRowWorldT2 + k]);
-#pragma unroll
-        for (int k = 0; k < 4; k++) cu.wr2[k] = asf(row[kRowWorldR2 + k]);
-        cu.scale_max = asf(row[kRowScale]);
+        const ConeU cu = load_cone_operands(row);
 #pragma unroll
         for (int j = 0; j < G; j++) {
           if (__builtin_amdgcn_ballot_w64(need[j] != 0u) == 0) continue;  // wave-uniform
@@ -558,16 +604,8 @@ OXC_DEV void meshlets_plain_body(const MeshletTestArgs& a) {
           // opaque asm stops the optimiser from recognising the repeat and keeping them anyway): ~9 more VALU per group for
           // ~24 fewer VGPRs at the pressure peak.
           asm volatile("" : "+v"(b.x), "+v"(b.y), "+v"(b.z), "+v"(b.w));
-          const float qx = dequantize_half(b.x & 0xFFFFu), qy = dequantize_half(b.x >> 16), qz = dequantize_half(b.y & 0xFFFFu);
-          const float rx = dequantize_half(b.z & 0xFFFFu), ry = dequantize_half(b.z >> 16), rz = dequantize_half(b.w & 0xFFFFu);
-          const f2 axy = s8_over_127_x2((int32_t)(b.y << 8) >> 24, (int32_t)b.y >> 24);
-          const f2 azc = s8_over_127_x2((int32_t)(b.w << 8) >> 24, (int32_t)b.w >> 24);
-          const int tier1 = cone_visible_fast(cu, camx, camy, camz, qx, qy, qz, rx, ry, rz, axy.x, axy.y, azc.x, azc.y);
-          bool cone_ok = tier1 == 1;
-          if (__builtin_amdgcn_ballot_w64(need[j] != 0u && tier1 == 2)) {  // some lane sits within the margin: the canonical IEEE path decides
-            const bool exact = cone_visible(cu, camx, camy, camz, qx, qy, qz, rx, ry, rz, axy.x, axy.y, azc.x, azc.y);
-            cone_ok = tier1 == 2 ? exact : cone_ok;
-          }
+          const BoundsBox q = decode_box(b);
+          const bool cone_ok = cone_two_tier(cu, camx, camy, camz, q.cx, q.cy, q.cz, q.ex, q.ey, q.ez, b, need[j] != 0u);
           st[j] = (need[j] != 0u && !cone_ok) ? 0u : st[j];
         }
       }
@@ -598,7 +636,7 @@ OXC_DEV void meshlets_plain_body(const MeshletTestArgs& a) {
 #pragma unroll
       for (int j = 0; j < G; j++) {
         if ((bits[j] >> lane) & 1ull)
-          gptr(a.out)[at + __builtin_amdgcn_mbcnt_hi((uint32_t)(bits[j] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bits[j], 0u))] = (group0 + j) * 64 + (uint32_t)lane;
+          gptr(a.out)[at + ballot_rank(bits[j])] = (group0 + j) * 64 + (uint32_t)lane;
         at += (uint32_t)__popcll((unsigned long long)bits[j]);
       }
     } else {
@@ -630,6 +668,69 @@ OXC_DEV void meshlets_plain_body(const MeshletTestArgs& a) {
 // instance: its InstCache row, mask words and pyramid texels stay in the L2 of the XCD the counter's blocks run on; measured ~1 %).
 constexpr uint32_t kTicketRun = 4;
 OXC_DEV uint32_t OXC_TICKET_STEP(uint32_t t, uint32_t K, uint32_t x) { return ((t / kTicketRun) * K + x) * kTicketRun + t % kTicketRun; }
+// The instantiations without an occlusion phase: the cone test where it stands, one pass per group that needs it.
+template <int G>
+OXC_DEV void hiz_cone_in_place(float camx, float camy, float camz, const kconst32p row, const uint4 (&bnd)[G], const uint32_t (&need)[G], uint32_t (&st)[G]) {
+  const ConeU cu = load_cone_operands(row);
+#pragma unroll
+  for (int j = 0; j < G; j++) {
+    if (__builtin_amdgcn_ballot_w64(need[j] != 0u) == 0) continue;  // wave-uniform
+    uint4 b = bnd[j];
+    asm volatile("" : "+v"(b.x), "+v"(b.y), "+v"(b.z), "+v"(b.w));  // decode again instead of keeping phase 1's floats alive (see meshlets_plain_body)
+    const BoundsBox q = decode_box(b);
+    const bool cone_ok = cone_two_tier(cu, camx, camy, camz, q.cx, q.cy, q.cz, q.ex, q.ey, q.ez, b, need[j] != 0u);
+    st[j] = (need[j] != 0u && !cone_ok) ? (st[j] & ~2u) : st[j];
+  }
+}
+
+// The one-run mask write.  The usual step is 64 * G consecutive meshlets of one instance: its mask bits are ONE run of 64 * G bits at bit
+// offset d0 -- 2 G whole words (+ one partial word at either end when d0 is not a multiple of 32).  Lane k builds word k from the G
+// visibility ballots and the run is written in one go, instead of once per 64-meshlet group through update_visibility_mask (~40 VALU
+// instructions each, 13 % of a late step's instructions).  Same stores / atomics as the per-group path would issue, merged.
+// Returns whether the step was such a run (run_first: its first bit); row8 is the wave's LDS flag row, free between rounds.
+template <int G>
+OXC_DEV bool hiz_write_mask_run(const MeshletTestArgs& a, int lane, uint32_t N, uint32_t group0, const uint32_t (&st)[G], const uint32_t (&mask_idx)[G], uint32_t* row8, uint32_t& run_first) {
+  bool step_run = false;
+  if ((group0 + G) * 64u <= N) {  // (wave-uniform)
+    const uint32_t d0 = readfirst_u(mask_idx[0]);
+    run_first = d0;
+    uint64_t bad = 0;
+#pragma unroll
+    for (int j = 0; j < G; j++) bad |= __builtin_amdgcn_ballot_w64(mask_idx[j] != d0 + 64u * (uint32_t)j + (uint32_t)lane);  // (kMaskNone lanes differ)
+    if (bad == 0ull && d0 <= 0xFFFFFFFFu - 64u * G) {
+      step_run = true;
+      // the G ballots go through the LDS row: lane k then picks dword k and dword k - 1 of the run
+#pragma unroll
+      for (int j = 0; j < G; j++) {
+        const uint64_t vb = __builtin_amdgcn_ballot_w64((st[j] & 2u) != 0u);
+        if (lane == 0) {
+          row8[2 * j] = (uint32_t)vb;
+          row8[2 * j + 1] = (uint32_t)(vb >> 32);
+        }
+      }
+      lds_handoff();
+      const uint32_t cur = lane < 2 * G ? row8[lane] : 0u;
+      const uint32_t prev = (lane >= 1 && lane <= 2 * G) ? row8[lane - 1] : 0u;
+      const uint32_t sh = d0 & 31u, w0 = d0 >> 5;
+      if (sh == 0u) {
+        if (lane < 2 * G) a.mask[w0 + (uint32_t)lane] = cur;
+      } else {
+        const uint32_t word = __builtin_amdgcn_alignbit(cur, prev, 32u - sh);  // (cur << sh) | (prev >> (32 - sh))
+        if (lane >= 1 && lane < 2 * G) {
+          a.mask[w0 + (uint32_t)lane] = word;
+        } else if (lane == 0 || lane == 2 * G) {  // the run's first / last word: only its own bits
+          const uint32_t own = lane == 0 ? (0xFFFFFFFFu << sh) : (0xFFFFFFFFu >> (32u - sh));
+          const uint32_t zero = own & ~word;
+          if (zero) atomicAnd(&a.mask[w0 + (uint32_t)lane], ~zero);
+          if (word) atomicOr(&a.mask[w0 + (uint32_t)lane], word);
+        }
+      }
+      lds_handoff();  // the flag row is rewritten by the next step
+    }
+  }
+  return step_run;
+}
+
 // COUNT (measurement aid, oxc_debug_count_occlusion_candidates): the same kernel also adds the number of candidates that reach
 // test_occlusion -- SURVEY 8d's f, each costs four pyramid taps = 16 B -- to MeshletTestArgs::dbg_occlusion; a separate instantiation,
 // so that the kernels that are timed do not carry the pointer.
@@ -688,13 +789,8 @@ OXC_DEV void meshlets_hiz_body(const MeshletTestArgs& a) {
   const uint32_t nsteps = nchunks * kWaves;
   const uint32_t K = min(kTicketCounters, gridDim.x), kx = blockIdx.x % K;  // every counter in use has at least one block drawing from it
   uint32_t* const ticket = a.tickets ? a.tickets + kx * kSuperStride : nullptr;
-  auto draw_ticket = [&]() -> uint32_t {
-    uint32_t t = 0;
-    if (lane == 0) t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return t;
-  };
   uint32_t step = blockIdx.x * kWaves + wave;
-  if (ticket) step = OXC_TICKET_STEP(readlane_u(draw_ticket(), 0), K, kx);
+  if (ticket) step = OXC_TICKET_STEP(readlane_u(draw_ticket(ticket, lane), 0), K, kx);
   while (step < nsteps) {
     const uint32_t group0 = step * G;
     uint2 rec[G];
@@ -729,7 +825,7 @@ OXC_DEV void meshlets_hiz_body(const MeshletTestArgs& a) {
 #pragma unroll
       for (int j = 0; j < G; j++) rec[j] = OXC_LOAD_MLI(mlis, min((group0 + j) * 64 + lane, last_index));
     }
-    const uint32_t next_ticket = ticket ? draw_ticket() : 0u;  // in flight behind the record loads; read at the end of the step
+    const uint32_t next_ticket = ticket ? draw_ticket(ticket, lane) : 0u;  // in flight behind the record loads; read at the end of the step
     if (!quick) {
 #pragma unroll
       for (int j = 0; j < G; j++) {
@@ -738,17 +834,8 @@ OXC_DEV void meshlets_hiz_body(const MeshletTestArgs& a) {
       }
     }
     for (;;) {
-      uint32_t mi_u = 0;
-      bool found = false;
-#pragma unroll
-      for (int j = 0; j < G; j++) {
-        const uint64_t p = __builtin_amdgcn_ballot_w64((st[j] & 1u) != 0u);
-        if (!found && p) {
-          mi_u = readlane_u(rec[j].x, __ffsll((unsigned long long)p) - 1);
-          found = true;
-        }
-      }
-      if (!found) break;
+      uint32_t mi_u;
+      if (!first_undecided_instance<G>(st, rec, mi_u)) break;
       const kconst32p row = const_row(a.cache, mi_u);
       const uint64_t bounds = (uint64_t)row[kRowBounds] | ((uint64_t)row[kRowBounds + 1] << 32);
       const uint32_t vis_offset = row[kRowVisOffset];
@@ -803,8 +890,8 @@ OXC_DEV void meshlets_hiz_body(const MeshletTestArgs& a) {
             st[j] = mine[j] ? 0u : st[j];
             continue;
           }
-          cx[j] = dequantize_half(b.x & 0xFFFFu), cy[j] = dequantize_half(b.x >> 16), cz[j] = dequantize_half(b.y & 0xFFFFu);
-          ex[j] = dequantize_half(b.z & 0xFFFFu), ey[j] = dequantize_half(b.z >> 16), ez[j] = dequantize_half(b.w & 0xFFFFu);
+          const BoundsBox q = decode_box(b);
+          cx[j] = q.cx, cy[j] = q.cy, cz[j] = q.cz, ex[j] = q.ex, ey[j] = q.ey, ez[j] = q.ez;
           const bool inside = mine[j] & test_frustum_planes(pl, sg, cx[j], cy[j], cz[j], ex[j], ey[j], ez[j]);
           // (SHARE == 1: every meshlet inside the frustum goes on to the cone test, whose result the late call reuses; bit 1 means
           //  "visible" only after the scatter below)
@@ -839,7 +926,7 @@ OXC_DEV void meshlets_hiz_body(const MeshletTestArgs& a) {
           uint32_t slot[G];
 #pragma unroll
           for (int j = 0; j < G; j++) {
-            slot[j] = base[j] + __builtin_amdgcn_mbcnt_hi((uint32_t)(vb[j] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)vb[j], 0u));
+            slot[j] = base[j] + ballot_rank(vb[j]);
             if ((vb[j] >> lane) & 1ull) {
               if constexpr (SHARE == 2) {  // these passed frustum and cone in the early call: straight to the occlusion batches
                 strip[slot[j]] = make_uint4(bnd[j].x, bnd[j].y, bnd[j].z, (bnd[j].w & 0x00FFFFFFu) | (slot[j] << 24));
@@ -850,19 +937,10 @@ OXC_DEV void meshlets_hiz_body(const MeshletTestArgs& a) {
               }
             }
           }
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // same-wave LDS hand-off: in order, no barrier needed
+          lds_handoff();
           uint32_t nb = SHARE == 2 ? total : 0u;  // occlusion candidates: they occupy strip[0 .. nb)
           if constexpr (SHARE != 2) {
-          ConeU cu;
-#pragma unroll
-          for (int k = 0; k < 9; k++) cu.nm[k] = asf(row[kRowNm + k]);
-#pragma unroll
-          for (int k = 0; k < 6; k++) cu.w2[k >> 1][k & 1] = asf(row[kRowWorld2 + k]);
-#pragma unroll
-          for (int k = 0; k < 2; k++) cu.wt2[k] = asf(row[kRowWorldT2 + k]);
-#pragma unroll
-          for (int k = 0; k < 4; k++) cu.wr2[k] = asf(row[kRowWorldR2 + k]);
-          cu.scale_max = asf(row[kRowScale]);
+          const ConeU cu = load_cone_operands(row);
           for (uint32_t t0 = 0; t0 < total; t0 += 64) {
             const uint32_t t = t0 + (uint32_t)lane;
             const bool act = t < total;
@@ -886,14 +964,14 @@ OXC_DEV void meshlets_hiz_body(const MeshletTestArgs& a) {
             // cone (published for the late call), bit 1 = visible so far
             const bool okv = SHARE == 1 ? (ok && (flg[act ? t : 0u] & 4u) != 0u) : ok;
             const uint64_t okb = __builtin_amdgcn_ballot_w64(okv);
-            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(okb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)okb, 0u));
+            const uint32_t rank = ballot_rank(okb);
             if (act) flg[t] = SHARE == 1 ? ((ok ? 1u : 0u) | (okv ? 2u : 0u)) : (ok ? 1u : 0u);
             // (nb + rank <= t, and every lane of this batch has read its record: the LDS queue of a wave is in order)
             if (okv) strip[nb + rank] = make_uint4(b.x, b.y, b.z, (b.w & 0x00FFFFFFu) | (t << 24));  // the cutoff byte now carries the survivor's strip position
             nb += (uint32_t)__popcll((unsigned long long)okb);
           }
           }
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          lds_handoff();
           if constexpr (COUNT) {
             if (nb && lane == 0) __hip_atomic_fetch_add(gptr(a.dbg_occlusion) + (step & 255u) * kSuperStride, nb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           }
@@ -905,12 +983,11 @@ OXC_DEV void meshlets_hiz_body(const MeshletTestArgs& a) {
               const uint32_t u = u0 + (uint32_t)lane;
               const bool act = u < nb;
               const uint4 b = strip[act ? u : nb - 1u];
-              const float qx = dequantize_half(b.x & 0xFFFFu), qy = dequantize_half(b.x >> 16), qz = dequantize_half(b.y & 0xFFFFu);
-              const float rx = dequantize_half(b.z & 0xFFFFu), ry = dequantize_half(b.z >> 16), rz = dequantize_half(b.w & 0xFFFFu);
-              const bool occluded = aabb_occluded(mvp, a.near_clip, qx, qy, qz, rx, ry, rz, hiz, s_level_off, act);
+              const BoundsBox q = decode_box(b);
+              const bool occluded = aabb_occluded(mvp, a.near_clip, q.cx, q.cy, q.cz, q.ex, q.ey, q.ez, hiz, s_level_off, act);
               if (act && occluded) flg[b.w >> 24] = SHARE == 1 ? 1u : 0u;
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            lds_handoff();
           }
 #pragma unroll
           for (int j = 0; j < G; j++) {
@@ -922,85 +999,16 @@ OXC_DEV void meshlets_hiz_body(const MeshletTestArgs& a) {
                 st[j] = f ? st[j] : (st[j] & ~2u);
             }
           }
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // strip and flags are rewritten by the next round
+          lds_handoff();  // strip and flags are rewritten by the next round
         }
       } else if (any_need) {  // no occlusion phase: the cone test where it stands, one pass per group that needs it
-        ConeU cu;
-#pragma unroll
-        for (int k = 0; k < 9; k++) cu.nm[k] = asf(row[kRowNm + k]);
-#pragma unroll
-        for (int k = 0; k < 6; k++) cu.w2[k >> 1][k & 1] = asf(row[kRowWorld2 + k]);
-#pragma unroll
-        for (int k = 0; k < 2; k++) cu.wt2[k] = asf(row[kRowWorldT2 + k]);
-#pragma unroll
-        for (int k = 0; k < 4; k++) cu.wr2[k] = asf(row[kRowWorldR2 + k]);
-        cu.scale_max = asf(row[kRowScale]);
-#pragma unroll
-        for (int j = 0; j < G; j++) {
-          if (__builtin_amdgcn_ballot_w64(need[j] != 0u) == 0) continue;  // wave-uniform
-          uint4 b = bnd[j];
-          asm volatile("" : "+v"(b.x), "+v"(b.y), "+v"(b.z), "+v"(b.w));  // decode again instead of keeping phase 1's floats alive (see meshlets_plain_body)
-          const float qx = dequantize_half(b.x & 0xFFFFu), qy = dequantize_half(b.x >> 16), qz = dequantize_half(b.y & 0xFFFFu);
-          const float rx = dequantize_half(b.z & 0xFFFFu), ry = dequantize_half(b.z >> 16), rz = dequantize_half(b.w & 0xFFFFu);
-          const f2 axy = s8_over_127_x2((int32_t)(b.y << 8) >> 24, (int32_t)b.y >> 24);
-          const f2 azc = s8_over_127_x2((int32_t)(b.w << 8) >> 24, (int32_t)b.w >> 24);
-          const int tier1 = cone_visible_fast(cu, camx, camy, camz, qx, qy, qz, rx, ry, rz, axy.x, axy.y, azc.x, azc.y);
-          bool cone_ok = tier1 == 1;
-          if (__builtin_amdgcn_ballot_w64(need[j] != 0u && tier1 == 2)) {
-            const bool exact = cone_visible(cu, camx, camy, camz, qx, qy, qz, rx, ry, rz, axy.x, axy.y, azc.x, azc.y);
-            cone_ok = tier1 == 2 ? exact : cone_ok;
-          }
-          st[j] = (need[j] != 0u && !cone_ok) ? (st[j] & ~2u) : st[j];
-        }
+        hiz_cone_in_place<G>(camx, camy, camz, row, bnd, need, st);
       }
     }
     // ---- mask update, ballots, per-wave survivor count
-    // The usual step is 64 * G consecutive meshlets of one instance: its mask bits are ONE run of 64 * G bits at bit offset d0 -- 2 G
-    // whole words (+ one partial word at either end when d0 is not a multiple of 32).  Lane k builds word k from the G visibility
-    // ballots and the run is written in one go, instead of once per 64-meshlet group through update_visibility_mask (~40 VALU
-    // instructions each, 13 % of a late step's instructions).  Same stores / atomics as the per-group path would issue, merged.
     bool step_run = false;
     uint32_t run_first = 0;
-    if constexpr (OCCL && G == 4) {
-      if ((group0 + G) * 64u <= N) {  // (wave-uniform)
-        const uint32_t d0 = readfirst_u(mask_idx[0]);
-        run_first = d0;
-        uint64_t bad = 0;
-#pragma unroll
-        for (int j = 0; j < G; j++) bad |= __builtin_amdgcn_ballot_w64(mask_idx[j] != d0 + 64u * (uint32_t)j + (uint32_t)lane);  // (kMaskNone lanes differ)
-        if (bad == 0ull && d0 <= 0xFFFFFFFFu - 64u * G) {
-          step_run = true;
-          // the G ballots go through the wave's LDS flag row (free between rounds): lane k then picks dword k and dword k - 1 of the run
-          uint32_t* row8 = s_flags[wave];
-#pragma unroll
-          for (int j = 0; j < G; j++) {
-            const uint64_t vb = __builtin_amdgcn_ballot_w64((st[j] & 2u) != 0u);
-            if (lane == 0) {
-              row8[2 * j] = (uint32_t)vb;
-              row8[2 * j + 1] = (uint32_t)(vb >> 32);
-            }
-          }
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // same-wave LDS hand-off
-          const uint32_t cur = lane < 2 * G ? row8[lane] : 0u;
-          const uint32_t prev = (lane >= 1 && lane <= 2 * G) ? row8[lane - 1] : 0u;
-          const uint32_t sh = d0 & 31u, w0 = d0 >> 5;
-          if (sh == 0u) {
-            if (lane < 2 * G) a.mask[w0 + (uint32_t)lane] = cur;
-          } else {
-            const uint32_t word = __builtin_amdgcn_alignbit(cur, prev, 32u - sh);  // (cur << sh) | (prev >> (32 - sh))
-            if (lane >= 1 && lane < 2 * G) {
-              a.mask[w0 + (uint32_t)lane] = word;
-            } else if (lane == 0 || lane == 2 * G) {  // the run's first / last word: only its own bits
-              const uint32_t own = lane == 0 ? (0xFFFFFFFFu << sh) : (0xFFFFFFFFu >> (32u - sh));
-              const uint32_t zero = own & ~word;
-              if (zero) atomicAnd(&a.mask[w0 + (uint32_t)lane], ~zero);
-              if (word) atomicOr(&a.mask[w0 + (uint32_t)lane], word);
-            }
-          }
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the flag row is rewritten by the next step
-        }
-      }
-    }
+    if constexpr (OCCL && G == 4) step_run = hiz_write_mask_run<G>(a, lane, N, group0, st, mask_idx, s_flags[wave], run_first);
     if constexpr (SHARE == 1) {
 #pragma unroll
       for (int j = 0; j < G; j++) {
@@ -1082,36 +1090,22 @@ __global__ __launch_bounds__(256, kHpbWaves) void k_cull_meshlets_hpb_test(HpbTe
   const uint32_t nsteps = nchunks * kWaves;
   const uint32_t K = min(kTicketCounters, gridDim.x), kx = blockIdx.x % K;
   uint32_t* const ticket = a.tickets + kx * kSuperStride;
-  auto draw_ticket = [&]() -> uint32_t {
-    uint32_t t = 0;
-    if (lane == 0) t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return t;
-  };
   uint4* const strip = s_strip[wave];
   uint32_t* const strip2 = s_strip2[wave];
   uint32_t* const seen = s_seen[wave];
-  uint32_t step = OXC_TICKET_STEP(readlane_u(draw_ticket(), 0), K, kx);
+  uint32_t step = OXC_TICKET_STEP(readlane_u(draw_ticket(ticket, lane), 0), K, kx);
   while (step < nsteps) {
     const uint32_t group0 = step * G;
     uint2 rec[G];
     uint32_t st[G];  // bit 0: still to be decided, bit 1: visible
 #pragma unroll
     for (int j = 0; j < G; j++) rec[j] = load_stream_u2(mlis, min((group0 + j) * 64 + lane, last_index));
-    const uint32_t next_ticket = draw_ticket();
+    const uint32_t next_ticket = draw_ticket(ticket, lane);
 #pragma unroll
     for (int j = 0; j < G; j++) st[j] = ((group0 + j) * 64 + lane < N) ? 1u : 0u;
     for (;;) {
-      uint32_t mi_u = 0;
-      bool found = false;
-#pragma unroll
-      for (int j = 0; j < G; j++) {
-        const uint64_t p = __builtin_amdgcn_ballot_w64((st[j] & 1u) != 0u);
-        if (!found && p) {
-          mi_u = readlane_u(rec[j].x, __ffsll((unsigned long long)p) - 1);
-          found = true;
-        }
-      }
-      if (!found) break;
+      uint32_t mi_u;
+      if (!first_undecided_instance<G>(st, rec, mi_u)) break;
       const kconst32p row = const_row(a.cache, mi_u);
       const uint64_t bounds = (uint64_t)row[kRowBounds] | ((uint64_t)row[kRowBounds + 1] << 32);
       uint4 bnd[G];
@@ -1122,9 +1116,6 @@ __global__ __launch_bounds__(256, kHpbWaves) void k_cull_meshlets_hpb_test(HpbTe
         bnd[j] = load_stream_u4(bounds, mine[j] ? rec[j].y : 0u);  // other lanes read element 0 (always valid)
       }
       // (centre / extent are decoded from the 16-byte record at every use: 6 conversions against 24 VGPRs held across the view loop)
-#define OXC_HPB_DECODE(b)                                                                                                             \
-  const float cxj = dequantize_half((b).x & 0xFFFFu), cyj = dequantize_half((b).x >> 16), czj = dequantize_half((b).y & 0xFFFFu); \
-  const float exj = dequantize_half((b).z & 0xFFFFu), eyj = dequantize_half((b).z >> 16), ezj = dequantize_half((b).w & 0xFFFFu)
       uint64_t any_cand = 0;
       {  // camera frustum (cull_meshlets_hpb.slang:49-52)
         float pl[24], sg[18];
@@ -1134,8 +1125,8 @@ __global__ __launch_bounds__(256, kHpbWaves) void k_cull_meshlets_hpb_test(HpbTe
         for (int k = 0; k < 18; k++) sg[k] = asf(row[kRowSigns + k]);
 #pragma unroll
         for (int j = 0; j < G; j++) {
-          OXC_HPB_DECODE(bnd[j]);
-          cand[j] = mine[j] & test_frustum_planes(pl, sg, cxj, cyj, czj, exj, eyj, ezj);
+          const BoundsBox q = decode_box(bnd[j]);
+          cand[j] = mine[j] & test_frustum_planes(pl, sg, q.cx, q.cy, q.cz, q.ex, q.ey, q.ez);
           vis[j] = false;
           any_cand |= __builtin_amdgcn_ballot_w64(cand[j]);
         }
@@ -1172,13 +1163,13 @@ __global__ __launch_bounds__(256, kHpbWaves) void k_cull_meshlets_hpb_test(HpbTe
         const uint32_t total = base[G];
 #pragma unroll
         for (int j = 0; j < G; j++) {
-          slot[j] = base[j] + __builtin_amdgcn_mbcnt_hi((uint32_t)(cb[j] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cb[j], 0u));
+          slot[j] = base[j] + ballot_rank(cb[j]);
           if (cand[j]) {
             strip[slot[j]] = bnd[j];
             seen[slot[j]] = 0u;
           }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // same-wave LDS hand-off: in order, no barrier needed
+        lds_handoff();
         uint32_t open_count = total;  // candidates no view has accepted yet (wave-uniform)
         // ---- phase A (round 4): the frustum of EVERY dirty view over the candidates, two batches at a time.  A box's six plane distances
         // are computed once, against clipmap 0's normals; a view whose row says "same normals" (prepare_body) only compares them with its
@@ -1214,8 +1205,8 @@ __global__ __launch_bounds__(256, kHpbWaves) void k_cull_meshlets_hpb_test(HpbTe
               const uint32_t t = c0 + 64u * (uint32_t)h + (uint32_t)lane;
               actb[h] = t < total;
               bb[h] = strip[actb[h] ? t : total - 1u];
-              OXC_HPB_DECODE(bb[h]);
-              frustum_plane_dots(rpl, rsg, cxj, cyj, czj, exj, eyj, ezj, dd[h]);
+              const BoundsBox q = decode_box(bb[h]);
+              frustum_plane_dots(rpl, rsg, q.cx, q.cy, q.cz, q.ex, q.ey, q.ez, dd[h]);
             }
             for (uint32_t v = 0; v < a.clipmap_count; v++) {
               if (((dirty_mask >> v) & 1ull) == 0ull) continue;  // uniform
@@ -1245,8 +1236,8 @@ __global__ __launch_bounds__(256, kHpbWaves) void k_cull_meshlets_hpb_test(HpbTe
                   for (int k = 0; k < 6; k++) sg6[k] = asf(vrow[kRowSigns + p * 6 + k]);
 #pragma unroll
                   for (int h = 0; h < 2; h++) {
-                    OXC_HPB_DECODE(bb[h]);
-                    inh[h] = inh[h] & frustum_pair_inside(n8, sg6, cxj, cyj, czj, exj, eyj, ezj);
+                    const BoundsBox q = decode_box(bb[h]);
+                    inh[h] = inh[h] & frustum_pair_inside(n8, sg6, q.cx, q.cy, q.cz, q.ex, q.ey, q.ez);
                   }
                 }
                 ib[0] = __builtin_amdgcn_ballot_w64(inh[0]);
@@ -1255,7 +1246,7 @@ __global__ __launch_bounds__(256, kHpbWaves) void k_cull_meshlets_hpb_test(HpbTe
               if (lane < 2) s_in[wave][v][(c0 >> 6) + (uint32_t)lane] = lane == 0 ? ib[0] : ib[1];
             }
           }
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // same-wave LDS hand-off
+          lds_handoff();
         }
         for (uint32_t v = 0; v < a.clipmap_count && open_count; v++) {
           if (((dirty_mask >> v) & 1ull) == 0ull) continue;  // uniform
@@ -1266,11 +1257,11 @@ __global__ __launch_bounds__(256, kHpbWaves) void k_cull_meshlets_hpb_test(HpbTe
             const uint64_t inb = s_in[wave][v][t0 >> 6];
             const bool in = ((inb >> lane) & 1ull) != 0ull && seen[t < total ? t : 0u] == 0u;  // (a set bit implies t < total)
             const uint64_t ib = __builtin_amdgcn_ballot_w64(in);
-            if (in) strip2[n_in + __builtin_amdgcn_mbcnt_hi((uint32_t)(ib >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ib, 0u))] = t;
+            if (in) strip2[n_in + ballot_rank(ib)] = t;
             n_in += (uint32_t)__popcll((unsigned long long)ib);
           }
           if (n_in == 0) continue;
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          lds_handoff();
           float vmvp[16];
 #pragma unroll
           for (int k = 0; k < 16; k++) vmvp[k] = asf(vrow[kRowMvp + k]);
@@ -1282,25 +1273,24 @@ __global__ __launch_bounds__(256, kHpbWaves) void k_cull_meshlets_hpb_test(HpbTe
             const bool act = t < n_in;
             const uint32_t at = strip2[act ? t : n_in - 1u];
             const uint4 b = strip[at];
-            OXC_HPB_DECODE(b);
+            const BoundsBox q = decode_box(b);
             float sa[6];
             bool pass = true;  // projection crosses the near plane: visible (cull_meshlets_hpb.slang:70-76)
-            if (project_aabb<true, false>(vmvp, z_near, cxj, cyj, czj, exj, eyj, ezj, sa)) pass = test_vsm_page(sa, hpb, s_level_off, v, pox, poy);
+            if (project_aabb<true, false>(vmvp, z_near, q.cx, q.cy, q.cz, q.ex, q.ey, q.ez, sa)) pass = test_vsm_page(sa, hpb, s_level_off, v, pox, poy);
             const bool hit = act && pass;
             if (hit) seen[at] = 1u;
             open_count -= (uint32_t)__popcll((unsigned long long)__builtin_amdgcn_ballot_w64(hit));
           }
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the next view reads the flags and rewrites strip2
+          lds_handoff();  // the next view reads the flags and rewrites strip2
         }
 #pragma unroll
         for (int j = 0; j < G; j++) {
           if (cand[j]) vis[j] = seen[slot[j]] != 0u;
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // strip and flags are rewritten by the next round
+        lds_handoff();  // strip and flags are rewritten by the next round
       }
 #pragma unroll
       for (int j = 0; j < G; j++) st[j] = mine[j] ? ((cand[j] && vis[j]) ? 2u : 0u) : st[j];
-#undef OXC_HPB_DECODE
     }
     uint32_t cnt = 0;
 #pragma unroll
@@ -1935,12 +1925,9 @@ __global__ __launch_bounds__(256) void k_debug_decode_bounds(const uint4* __rest
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     const uint4 b = bounds[i];
     float* o = out10 + (size_t)i * 10;
-    o[0] = dequantize_half(b.x & 0xFFFFu);
-    o[1] = dequantize_half(b.x >> 16);
-    o[2] = dequantize_half(b.y & 0xFFFFu);
-    o[3] = dequantize_half(b.z & 0xFFFFu);
-    o[4] = dequantize_half(b.z >> 16);
-    o[5] = dequantize_half(b.w & 0xFFFFu);
+    const BoundsBox q = decode_box(b);
+    o[0] = q.cx, o[1] = q.cy, o[2] = q.cz;
+    o[3] = q.ex, o[4] = q.ey, o[5] = q.ez;
     o[6] = s8_over_127((int32_t)(b.y << 8) >> 24);
     o[7] = s8_over_127((int32_t)b.y >> 24);
     o[8] = s8_over_127((int32_t)(b.w << 8) >> 24);
@@ -2187,14 +2174,9 @@ __global__ __launch_bounds__(256, SAME_POS ? 6 : 4) void k_mv_test(MvArgs a) {
   const uint32_t nsteps = gptr(a.step_total)[0];
   const uint32_t K = min(kTicketCounters, gridDim.x), kx = blockIdx.x % K;
   uint32_t* const ticket = a.tickets + kx * kSuperStride;
-  auto draw_ticket = [&]() -> uint32_t {
-    uint32_t t = 0;
-    if (lane == 0) t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return t;
-  };
-  uint32_t step = OXC_TICKET_STEP(readlane_u(draw_ticket(), 0), K, kx);
+  uint32_t step = OXC_TICKET_STEP(readlane_u(draw_ticket(ticket, lane), 0), K, kx);
   while (step < nsteps) {
-    const uint32_t next_ticket = draw_ticket();
+    const uint32_t next_ticket = draw_ticket(ticket, lane);
     const uint2 sd = load_global_u2(reinterpret_cast<uint64_t>(a.steps), step);
     const uint32_t mi = readfirst_u(sd.x), gi = readfirst_u(sd.y) & 0xFFu, c = readfirst_u(sd.y) >> 8;
     const kconst32p grp = (kconst32p)(reinterpret_cast<uint64_t>(a.groups + (size_t)mi * a.views + gi));
@@ -2225,16 +2207,7 @@ __global__ __launch_bounds__(256, SAME_POS ? 6 : 4) void k_mv_test(MvArgs a) {
   const float exj = dequantize_half((b).z & 0xFFFFu), eyj = dequantize_half((b).z >> 16), ezj = dequantize_half((b).w & 0xFFFFu)
     uint64_t okb[G];  // lanes that exist and pass the cone test (per view when the views have different camera positions)
     auto cone_pass = [&](const kconst32p row, float camx, float camy, float camz) {
-      ConeU cu;
-#pragma unroll
-      for (int k = 0; k < 9; k++) cu.nm[k] = asf(row[kRowNm + k]);
-#pragma unroll
-      for (int k = 0; k < 6; k++) cu.w2[k >> 1][k & 1] = asf(row[kRowWorld2 + k]);
-#pragma unroll
-      for (int k = 0; k < 2; k++) cu.wt2[k] = asf(row[kRowWorldT2 + k]);
-#pragma unroll
-      for (int k = 0; k < 4; k++) cu.wr2[k] = asf(row[kRowWorldR2 + k]);
-      cu.scale_max = asf(row[kRowScale]);
+      const ConeU cu = load_cone_operands(row);
 #pragma unroll
       for (int j = 0; j < G; j++) {
         const uint4 b = bnd[j];
@@ -2385,8 +2358,7 @@ __global__ __launch_bounds__(256) void k_mv_emit(MvArgs a) {
       const uint64_t bk = (uint64_t)readlane_u(blo, k) | ((uint64_t)readlane_u(bhi, k) << 32);
       if (bk == 0ull) continue;  // wave-uniform
       const uint32_t ok = readlane_u(off, k), ik = readlane_u(idb, k);
-      // (a lane's rank among the word's set bits: v_mbcnt with the word as its scalar mask operand)
-      if ((bk >> lane) & 1ull) gptr(out)[ok + __builtin_amdgcn_mbcnt_hi((uint32_t)(bk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bk, 0u))] = ik + (uint32_t)lane;
+      if ((bk >> lane) & 1ull) gptr(out)[ok + ballot_rank(bk)] = ik + (uint32_t)lane;
     }
   }
 }
@@ -2453,6 +2425,14 @@ static uint32_t resident_grid(K kernel, uint32_t block, uint32_t num_cus) {
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, (int)block, 0) != hipSuccess || per_cu <= 0) return num_cus * 8u;
   return (uint32_t)per_cu * num_cus;
 }
+// One launch of instantiation K, its grid capped at the blocks of K that are resident at once on `cus` CUs (0: no cap).  The occupancy query runs
+// once per instantiation and process: the static below is this instantiation's own.
+template <auto K, class Args>
+static void launch_resident(uint32_t grid, uint32_t block, uint32_t cus, hipStream_t s, const Args& a) {
+  static const uint32_t per_cu = resident_grid(K, block, 1);
+  if (cus) grid = std::min(grid, per_cu * cus);
+  hipLaunchKernelGGL(K, dim3(grid), dim3(block), 0, s, a);
+}
 void launch_meshlets_test(const MeshletTestArgs& a, bool hiz, bool occl, bool late, uint32_t grid, uint32_t num_cus, uint32_t grid_limit, hipStream_t s) {
   constexpr uint32_t hb = 1024 / kHizGroups;
   if (hiz && grid_limit) grid = std::min(grid, grid_limit);
@@ -2472,29 +2452,20 @@ void launch_meshlets_test(const MeshletTestArgs& a, bool hiz, bool occl, bool la
       hipLaunchKernelGGL((k_cull_meshlets_test_counting<false, 0>), g, b, 0, s, a);
     return;
   }
-  if (!hiz) {
+  if (!hiz)
     hipLaunchKernelGGL((k_cull_meshlets_test<false, false, false>), dim3(grid * (4 / kPlainBlockWaves)), dim3(64 * kPlainBlockWaves), 0, s, a);
-  } else if (occl && a.share) {
-    if (a.share == 2) {
-      static const uint32_t cap = resident_grid(k_cull_meshlets_test_shared<true>, hb, num_cus);
-      hipLaunchKernelGGL((k_cull_meshlets_test_shared<true>), dim3(std::min(grid, cap)), dim3(hb), 0, s, a);
-    } else {
-      static const uint32_t cap = resident_grid(k_cull_meshlets_test_shared<false>, hb, num_cus);
-      hipLaunchKernelGGL((k_cull_meshlets_test_shared<false>), dim3(std::min(grid, cap)), dim3(hb), 0, s, a);
-    }
-  } else if (occl && late) {
-    static const uint32_t cap = resident_grid(k_cull_meshlets_test<true, true, true, kHizGroups>, hb, num_cus);
-    hipLaunchKernelGGL((k_cull_meshlets_test<true, true, true, kHizGroups>), dim3(std::min(grid, cap)), dim3(hb), 0, s, a);
-  } else if (occl) {
-    static const uint32_t cap = resident_grid(k_cull_meshlets_test<true, true, false, kHizGroups>, hb, num_cus);
-    hipLaunchKernelGGL((k_cull_meshlets_test<true, true, false, kHizGroups>), dim3(std::min(grid, cap)), dim3(hb), 0, s, a);
-  } else if (late) {
-    static const uint32_t cap = resident_grid(k_cull_meshlets_test<true, false, true, kHizGroups>, hb, num_cus);
-    hipLaunchKernelGGL((k_cull_meshlets_test<true, false, true, kHizGroups>), dim3(std::min(grid, cap)), dim3(hb), 0, s, a);
-  } else {
-    static const uint32_t cap = resident_grid(k_cull_meshlets_test<true, false, false, kHizGroups>, hb, num_cus);
-    hipLaunchKernelGGL((k_cull_meshlets_test<true, false, false, kHizGroups>), dim3(std::min(grid, cap)), dim3(hb), 0, s, a);
-  }
+  else if (occl && a.share == 2)
+    launch_resident<k_cull_meshlets_test_shared<true>>(grid, hb, num_cus, s, a);
+  else if (occl && a.share)
+    launch_resident<k_cull_meshlets_test_shared<false>>(grid, hb, num_cus, s, a);
+  else if (occl && late)
+    launch_resident<k_cull_meshlets_test<true, true, true, kHizGroups>>(grid, hb, num_cus, s, a);
+  else if (occl)
+    launch_resident<k_cull_meshlets_test<true, true, false, kHizGroups>>(grid, hb, num_cus, s, a);
+  else if (late)
+    launch_resident<k_cull_meshlets_test<true, false, true, kHizGroups>>(grid, hb, num_cus, s, a);
+  else
+    launch_resident<k_cull_meshlets_test<true, false, false, kHizGroups>>(grid, hb, num_cus, s, a);
 }
 void launch_hpb_test(const HpbTestArgs& a, uint32_t grid, hipStream_t s) { hipLaunchKernelGGL(k_cull_meshlets_hpb_test, dim3(grid), dim3(256), 0, s, a); }
 void launch_meshlets_emit(const MeshletEmitArgs& a, bool hiz, bool late, uint32_t grid, hipStream_t s) {
@@ -2535,51 +2506,38 @@ void launch_tris_test(const TriTestArgs& a, bool late, bool wide, bool small_tri
 // query).  The fused kernel hands out its work by rounds of the grid (tris_fused_body): a grid of two resident rounds -- the WIDE
 // instantiations run 4 waves per SIMD, the generic cap was 8 blocks per CU -- cost the 8 M x 124-triangle frame 33 us (0.562 -> 0.529 ms).
 void launch_tris_fused(const TriTestArgs& a, bool late, uint32_t wide, bool small_triangle_cull, bool cached, uint32_t grid, uint32_t resident_cus, hipStream_t s) {
-  dim3 b(256);
+  const uint32_t g = std::max(grid, 1u), cus = resident_cus;
   const int v = (late ? 4 : 0) | (wide ? 2 : 0) | (small_triangle_cull ? 1 : 0);
-#define OXC_FUSED_LAUNCH(K_)                                                                                       \
-  {                                                                                                                \
-    static const uint32_t per_cu = resident_grid(K_, 256, 1);                                                      \
-    const uint32_t g = resident_cus ? std::min(grid, per_cu * resident_cus) : grid;                                \
-    hipLaunchKernelGGL(K_, dim3(std::max(g, 1u)), b, 0, s, a);                                                     \
-  }
-#define OXC_FUSED_CASE(i, L_, W_, S_)                                                                              \
-  case i:                                                                                                          \
-    OXC_FUSED_LAUNCH((k_cull_triangles_fused<L_, W_, S_>))                                                         \
-    break;
   if (cached && !small_triangle_cull) {  // shared geometry: plain loads
     switch ((late ? 4 : 0) | (int)std::min(wide, 2u)) {
-      case 0: OXC_FUSED_LAUNCH((k_cull_triangles_fused_cached<false, 0>)) break;
-      case 1: OXC_FUSED_LAUNCH((k_cull_triangles_fused_cached<false, 1>)) break;
-      case 2: OXC_FUSED_LAUNCH((k_cull_triangles_fused_cached<false, 2>)) break;
-      case 4: OXC_FUSED_LAUNCH((k_cull_triangles_fused_cached<true, 0>)) break;
-      case 5: OXC_FUSED_LAUNCH((k_cull_triangles_fused_cached<true, 1>)) break;
-      default: OXC_FUSED_LAUNCH((k_cull_triangles_fused_cached<true, 2>)) break;
+      case 0: launch_resident<k_cull_triangles_fused_cached<false, 0>>(g, 256, cus, s, a); break;
+      case 1: launch_resident<k_cull_triangles_fused_cached<false, 1>>(g, 256, cus, s, a); break;
+      case 2: launch_resident<k_cull_triangles_fused_cached<false, 2>>(g, 256, cus, s, a); break;
+      case 4: launch_resident<k_cull_triangles_fused_cached<true, 0>>(g, 256, cus, s, a); break;
+      case 5: launch_resident<k_cull_triangles_fused_cached<true, 1>>(g, 256, cus, s, a); break;
+      default: launch_resident<k_cull_triangles_fused_cached<true, 2>>(g, 256, cus, s, a); break;
     }
     return;
   }
   if (wide == 2u) {  // {id, corner} pairs
     switch (v & 5) {
-      case 0: OXC_FUSED_LAUNCH((k_cull_triangles_fused_pairs<false, false>)) break;
-      case 1: OXC_FUSED_LAUNCH((k_cull_triangles_fused_pairs<false, true>)) break;
-      case 4: OXC_FUSED_LAUNCH((k_cull_triangles_fused_pairs<true, false>)) break;
-      default: OXC_FUSED_LAUNCH((k_cull_triangles_fused_pairs<true, true>)) break;
+      case 0: launch_resident<k_cull_triangles_fused_pairs<false, false>>(g, 256, cus, s, a); break;
+      case 1: launch_resident<k_cull_triangles_fused_pairs<false, true>>(g, 256, cus, s, a); break;
+      case 4: launch_resident<k_cull_triangles_fused_pairs<true, false>>(g, 256, cus, s, a); break;
+      default: launch_resident<k_cull_triangles_fused_pairs<true, true>>(g, 256, cus, s, a); break;
     }
     return;
   }
   switch (v) {
-    OXC_FUSED_CASE(0, false, false, false)
-    OXC_FUSED_CASE(1, false, false, true)
-    OXC_FUSED_CASE(2, false, true, false)
-    OXC_FUSED_CASE(3, false, true, true)
-    OXC_FUSED_CASE(4, true, false, false)
-    OXC_FUSED_CASE(5, true, false, true)
-    OXC_FUSED_CASE(6, true, true, false)
-    default:
-      OXC_FUSED_CASE(7, true, true, true)
+    case 0: launch_resident<k_cull_triangles_fused<false, false, false>>(g, 256, cus, s, a); break;
+    case 1: launch_resident<k_cull_triangles_fused<false, false, true>>(g, 256, cus, s, a); break;
+    case 2: launch_resident<k_cull_triangles_fused<false, true, false>>(g, 256, cus, s, a); break;
+    case 3: launch_resident<k_cull_triangles_fused<false, true, true>>(g, 256, cus, s, a); break;
+    case 4: launch_resident<k_cull_triangles_fused<true, false, false>>(g, 256, cus, s, a); break;
+    case 5: launch_resident<k_cull_triangles_fused<true, false, true>>(g, 256, cus, s, a); break;
+    case 6: launch_resident<k_cull_triangles_fused<true, true, false>>(g, 256, cus, s, a); break;
+    default: launch_resident<k_cull_triangles_fused<true, true, true>>(g, 256, cus, s, a); break;
   }
-#undef OXC_FUSED_CASE
-#undef OXC_FUSED_LAUNCH
 }
 void launch_tris_emit(const TriEmitArgs& a, bool late, uint32_t wide, uint32_t grid, hipStream_t s) {
   dim3 g(grid), b(256);

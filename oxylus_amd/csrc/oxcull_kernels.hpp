@@ -1,5 +1,5 @@
 // oxcull_kernels.hpp -- kernel argument blocks and launcher prototypes shared by the kernel TU
-// (oxcull_kernels.hip) and the C-ABI host TU (oxcull_abi.cpp).
+// (oxcull_kernels.hip) and the C-ABI host TUs (oxcull_abi_*.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
