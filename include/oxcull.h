@@ -2030,6 +2030,107 @@ typedef struct oxc_terrain_brush_context {
 
 oxc_status oxc_apply_terrain_brush(oxc_ctx* ctx, const oxc_terrain_brush_context* context, void* hip_stream);
 
+/* ---- the terrain decode: the G-buffer images of the terrain pixels --------------------------------------------------------------------------
+ * oxc_decode_terrain is RendererInstance::decode_terrain (Passes/Terrain.cpp:279-360, pipeline terrain_decode, passes/terrain_decode.slang),
+ * the full-screen pass directly after decode_visbuffer (RendererInstance.cpp:929-952): per terrain pixel the world position is unprojected
+ * from the depth, the normal map and the splat map are sampled there, the four splat layers are blended by weight, the brush ring is drawn,
+ * and the four G-buffer images oxc_decode_visbuffer writes for the mesh pixels are written for the ground.  It runs after
+ * oxc_decode_visbuffer on the same attachments.  The first consumer of the normal map and the splat map of oxc_generate_terrain_maps and of
+ * the `hit` record of oxc_apply_terrain_brush.
+ * Scope: the cut of oxc_decode_visbuffer -- the geometry and material-factor half of the shader; texture sampling is NOT done (D6).  The
+ * tessellated terrain draw (terrain_visbuffer.slang) that produces the terrain texels and their depth stays out of scope.
+ * Arithmetic: the conventions of the terrain maps block (binary32, the Slang's expressions left to right, one rounding per operation, no
+ * contraction; min / max / saturate through fmin / fmax, so saturate(NaN) = 0; length, normalize, lerp(a, b, t) = a + (b - a) * t and
+ * smoothstep as oxc_apply_pbr states them; the unorm8 load f32(byte) / 255.0f; a binary16 load is exact, denormals kept); decimal literals
+ * the nearest binary32 (1e-4f, 0.02f, 0.05f, 0.55f, 0.1f); a comparison with a NaN operand is false.  T = terrain (oxc_terrain_data).
+ * Per pixel (x, y) of the W x H images:
+ *   D1. selection  (terrain_decode.slang:179-182)  A pixel whose visbuffer texel is not is_terrain ((texel >> 8) == 0xFFFFFE,
+ *              visbuffer.slang:16-20) is not touched: the Slang's discard.  There is no clear flag; mesh texels, ~0u and every other texel
+ *              keep the bytes the earlier passes left in all four images.  The depth texel's bits play no part in the selection: a terrain
+ *              texel over depth 0 is decoded by the rule.
+ *   D2. position   (:80-81)  uv = ((f32(x) + 0.5) / f32(W), (f32(y) + 0.5) / f32(H)).  Stated rule: the Slang's u32x2(uv * camera.resolution)
+ *              with resolution == (W, H) is (x, y): the depth is the load of texel (x, y).  world = Camera::unproject_uv(uv, depth)
+ *              (scene.slang:189-193): h = mul(inv_projection_view, (uv * 2.0 - 1.0, depth, 1)) row by row, ((m0 a + m1 b) + m2 c) + m3 as in
+ *              oxc_apply_pbr step 3;  world = h.xyz / h.w, three divisions.  A depth of 0 or a zero h.w runs on with the IEEE results.
+ *   D3. geometric normal  (:84-86)  terrain_uv = (world.xz - T.world_min) * T.inv_world_size.  SampleLevel(LinearSamplerClamped, terrain_uv, 0)
+ *              on the normal map and on the splat map is the manual clamp bilinear of oxc_apply_terrain_brush step B3 on the
+ *              map_resolution.x x map_resolution.y maps, applied per channel to the two binary16 loads of a normal-map texel and to the
+ *              four unorm8 loads of a splat-map texel: n = (normal map .x, .y), w = the four splat channels.  geometric_normal =
+ *              normalize((n.x, sqrt(saturate(1.0 - (n.x * n.x + n.y * n.y))), n.y)): dot(n, n) > 1 gives a zero y, a NaN in n a NaN normal.
+ *   D4. weights    (:105-107)  weight_sum = ((w.x + w.y) + w.z) + w.w;  weights = weight_sum > 1e-4f ? w / weight_sum (four divisions) :
+ *              (1, 0, 0, 0).  A NaN weight_sum takes the second arm.
+ *   D5. layers     (:38-77)  albedo (four channels), emissive, metallic, roughness and occlusion start at 0.  For i = 0 .. 3 in order, weight =
+ *              weights[i]:  weight <= 0 skips the layer (a NaN weight does not).  index = T.layer_material_indices[i].  index ==
+ *              TERRAIN_INVALID_LAYER_MATERIAL (~0u, scene.slang:632): albedo += (1, 1, 1, 1) * weight, (metallic, roughness) += (0.0, 1.0) *
+ *              weight (the product 0.0 * weight is formed), occlusion += weight, nothing is added to emissive.  Any other index >=
+ *              material_count uses the all-zero Material of oxc_decode_visbuffer; otherwise the record materials_buffer[index].  Its
+ *              factors -- the four halves of albedo_color, the three of emissive_color, metallic_factor, roughness_factor -- go through the
+ *              flushing com::dequantize_half (oxc_decode_visbuffer step 3) and each sum is sum = sum + factor * weight; occlusion += 1.0 *
+ *              weight.  Sums accumulate in layer order.
+ *   D6. out of scope, stated  Texture sampling is not done: the Has*Image and NormalFlipY bits are ignored and every sample_* returns its
+ *              factor alone, as in oxc_decode_visbuffer.  Nothing that only feeds a SampleGrad is computed: the two neighbour rays with
+ *              plane_offset, ddx_world and ddy_world (:88-103), inv_tiling (:109), the side projection's uv and gradients (:120-123);
+ *              T.layer_tiling and Camera::position are not read.  Consequences: (a) the side sample (:125-127) reads the same factors with
+ *              the same weights as the top sample, so the triplanar blend (:110-111, 119-139) is dropped and with it slope and
+ *              triplanar_amount; T.triplanar_begin is not read.  lerp(a, a, t) is a for every finite a and t; stated deviation: a
+ *              non-finite sum (an Inf or NaN factor, a NaN weight) is stored as D5 left it, where the Slang's a + (a - a) * t would turn
+ *              an Inf into a NaN on slopes with triplanar_amount > 0, and a NaN triplanar_amount is not spread into finite sums.  (b)
+ *              every layer's tangent normal is (0, 0, 1), the blended one normalises to (0, 0, 1) or takes the (0, 0, 1) fallback, and the
+ *              tangent frame (:116-149) multiplies zeros: shading_normal = normalize(geometric_normal), the second normalisation kept
+ *              because the Slang performs it (:154-156).  A zero weight total, which leaves the blended tangent normal at its fallback, gives
+ *              the same.
+ *   D7. brush ring (:158-164)  Only when T.brush_radius > 0 (false for a NaN) and hit.valid != 0; hit is read from device memory, and not
+ *              read at all unless T.brush_radius > 0.  d = world.xz - hit.world_position.xz;  ring_distance = sqrt(d.x * d.x + d.y * d.y);
+ *              ring_width = max(T.brush_radius * 0.02f, 0.05f);  ring = 1.0 - smoothstep(0.0, ring_width, |ring_distance -
+ *              T.brush_radius|);  albedo.rgb = lerp(albedo.rgb, (1.0, 0.55f, 0.1f), ring) per channel; alpha is left.
+ *   D8. stores     albedo_attachment: r, g, b through the sRGB encoding and every channel through the unorm8 rule, alpha linear
+ *              (oxc_decode_visbuffer step 6).  normal_attachment: .rg = vec3_to_oct(shading_normal), .ba = vec3_to_oct(geometric_normal),
+ *              four binary16 by step 5 there (a NaN stored as 0x7E00).  emissive_attachment: B10G11R11 by the UF11 / UF11 / UF10 rule of
+ *              step 8.  metallic_roughness_occlusion_attachment: (metallic, roughness, occlusion, 0.0) by the unorm8 rule, metallic in the
+ *              low byte (step 7).
+ * Limits (else OXC_INVALID_ARG, nothing launched, nothing written; the first broken rule in this order gives the message, each has its own):
+ * struct_size; width and height non-zero; both equal to the depth attachment's, which is one R32F level at offset 0 of at most 65536 a
+ * side; every side of map_resolution in 1 .. 16384; then every buffer in the order of the context's fields -- visbuffer_attachment,
+ * depth_attachment, normalmap, splatmap, materials_buffer, brush_hit and the four outputs -- non-null, then aligned to its texel (4 bytes; the
+ * normal attachment and brush_hit 8), then at least as large as its extent (one texel per pixel or per map texel; material_count records
+ * of 56 bytes; 16 bytes of brush_hit); materials_buffer may be null when material_count is 0 and brush_hit when T.brush_radius > 0 is false
+ * (a buffer that may be null and is null is not checked further and not read); then no output shares a byte with any other buffer of the
+ * call.  Every float is taken as given: NaN / Inf in the matrix, in world_min, inv_world_size and brush_radius run through the rules.  The
+ * layer indices need no limit (D5).  One launch, no scratch, no allocation, no host synchronisation; capturable into a HIP graph. */
+#define OXC_TERRAIN_INVALID_LAYER_MATERIAL 0xFFFFFFFFu /* scene.slang:632 */
+typedef struct oxc_terrain_data { /* GPU::TerrainData (scene.slang:634-661 with its world_to_uv, SceneGPU.hpp:440-453), field for field, 76 bytes */
+  float world_min[2], world_size[2], inv_world_size[2];
+  uint32_t patch_count[2];
+  float base_height, height_scale, target_edge_pixels, max_tessellation, layer_tiling, triplanar_begin;
+  uint32_t layer_material_indices[4];
+  float brush_radius;
+} oxc_terrain_data;
+#ifdef __cplusplus
+static_assert(sizeof(oxc_terrain_data) == 76, "GPU::TerrainData");
+#else
+_Static_assert(sizeof(oxc_terrain_data) == 76, "GPU::TerrainData");
+#endif
+typedef struct oxc_terrain_decode_context {
+  uint32_t struct_size; /* sizeof(oxc_terrain_decode_context) */
+  uint32_t width, height;
+  float inv_projection_view[16]; /* Camera::inv_projection_view, column-major */
+  oxc_terrain_data terrain;      /* read: world_min, inv_world_size, layer_material_indices, brush_radius */
+  uint32_t map_resolution[2];    /* the extent of normalmap and splatmap */
+  uint32_t material_count;
+  oxc_buffer visbuffer_attachment; /* in: u32[height][width] */
+  oxc_image depth_attachment;      /* in: R32F, levels = 1 */
+  oxc_buffer normalmap;            /* in: u16x2 [map_resolution.y][.x], R16G16 Sfloat, as oxc_generate_terrain_maps writes it */
+  oxc_buffer splatmap;             /* in: u32 [map_resolution.y][.x], R8G8B8A8 Unorm */
+  oxc_buffer materials_buffer;     /* in: GPU::Material[material_count], 56 bytes each */
+  oxc_buffer brush_hit;            /* in: device memory, 16 bytes of oxc_terrain_brush_hit, as oxc_apply_terrain_brush writes it */
+  oxc_buffer albedo_attachment;    /* out, terrain pixels only: the four attachments of oxc_decode_context, same formats and layouts */
+  oxc_buffer normal_attachment;
+  oxc_buffer emissive_attachment;
+  oxc_buffer metallic_roughness_occlusion_attachment;
+} oxc_terrain_decode_context;
+
+oxc_status oxc_decode_terrain(oxc_ctx* ctx, const oxc_terrain_decode_context* context, void* hip_stream);
+
 /* ---- multi-GPU exchange: one process per GPU, RCCL over xGMI ---------------------------
  * The meshlet-instance array shards by contiguous range and every rank culls its shard on its own; the only
  * exchanges of the path are (1) the per-rank counters {emitted meshlets, early, late, index count} to every rank

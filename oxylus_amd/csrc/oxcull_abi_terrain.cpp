@@ -1,6 +1,7 @@
 // oxcull_abi_terrain.cpp -- the terrain map producers of liboxcull.so's C ABI: oxc_generate_terrain_maps (height, ridge, normal, splat and the
-// per-patch min / max) and oxc_apply_terrain_brush (the brush ray trace and the strokes into the edit images).  The terrain cull, their
-// consumer, is in oxcull_abi_cull.cpp.
+// per-patch min / max), oxc_apply_terrain_brush (the brush ray trace and the strokes into the edit images) and oxc_decode_terrain (the
+// G-buffer of the terrain pixels, the consumer of the normal map, the splat map and the hit record).  The terrain cull, the consumer of
+// the min / max, is in oxcull_abi_cull.cpp.
 #include "oxcull_host.hpp"
 
 namespace {
@@ -147,6 +148,60 @@ oxc_status oxc_apply_terrain_brush(oxc_ctx* ctx, const oxc_terrain_brush_context
   a.region = static_cast<uint32_t*>(c->region.dptr);
   if (stages & OXC_TERRAIN_BRUSH_TRACE) launch_terrain_brush_trace(a, s);
   if (stages & OXC_TERRAIN_BRUSH_APPLY) launch_terrain_brush_apply(a, s);
+  OXC_HIP(ctx, hipGetLastError());
+  return OXC_OK;
+}
+
+oxc_status oxc_decode_terrain(oxc_ctx* ctx, const oxc_terrain_decode_context* c, void* hip_stream) {
+  if (!ctx) return OXC_INVALID_ARG;
+  if (!c || c->struct_size != sizeof(oxc_terrain_decode_context)) return fail(ctx, OXC_INVALID_ARG, "decode_terrain: bad context / struct_size");
+  const char* const entry = "decode_terrain";
+  const oxc_image& dimg = c->depth_attachment;
+  const oxc_terrain_data& T = c->terrain;
+  if (c->width == 0u || c->height == 0u) return bad_arg(ctx, entry, "the extent must not be zero");
+  if (dimg.width != c->width || dimg.height != c->height) return bad_arg(ctx, entry, "depth_attachment extent differs from (width, height)");
+  uint64_t pixels;
+  OXC_TRY(pixel_images(ctx, entry, dimg, nullptr, nullptr, pixels));
+  const uint32_t* res = c->map_resolution;
+  if (res[0] < 1u || res[0] > 16384u || res[1] < 1u || res[1] > 16384u) return bad_arg(ctx, entry, "map_resolution: every side must be in 1 .. 16384");
+
+  const bool ring = T.brush_radius > 0.0f;  // false for a NaN: the record is not read then
+  const uint64_t texels = (uint64_t)res[0] * res[1];
+  const oxc_buffer &mat = c->materials_buffer, &mro = c->metallic_roughness_occlusion_attachment;
+  const MapBuffer buffers[] = {
+      {"visbuffer_attachment", c->visbuffer_attachment.dptr, c->visbuffer_attachment.bytes, pixels * 4u, 4u, 1u, 0u, false},
+      {"depth_attachment", dimg.dptr, pixels * 4u, pixels * 4u, 4u, 1u, 0u, false},
+      {"normalmap", c->normalmap.dptr, c->normalmap.bytes, texels * 4u, 4u, 1u, 0u, false},
+      {"splatmap", c->splatmap.dptr, c->splatmap.bytes, texels * 4u, 4u, 1u, 0u, false},
+      {"materials_buffer", mat.dptr, mat.bytes, (uint64_t)c->material_count * 56u, 4u, 1u, 0u, c->material_count == 0u, " is smaller than material_count records of 56 bytes"},
+      {"brush_hit", c->brush_hit.dptr, c->brush_hit.bytes, 16u, 8u, 1u, 0u, !ring},
+      {"albedo_attachment", c->albedo_attachment.dptr, c->albedo_attachment.bytes, pixels * 4u, 4u, 1u, 1u, false},
+      {"normal_attachment", c->normal_attachment.dptr, c->normal_attachment.bytes, pixels * 8u, 8u, 1u, 1u, false},
+      {"emissive_attachment", c->emissive_attachment.dptr, c->emissive_attachment.bytes, pixels * 4u, 4u, 1u, 1u, false},
+      {"metallic_roughness_occlusion_attachment", mro.dptr, mro.bytes, pixels * 4u, 4u, 1u, 1u, false},
+  };
+  if (const oxc_status st = check_buffers(ctx, entry, buffers, 1u)) return st;
+
+  OXC_ENTER(ctx, hip_stream, s);
+  TerrainDecodeArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.w = c->width, a.h = c->height;
+  a.fw = (float)c->width, a.fh = (float)c->height;
+  for (int k = 0; k < 16; k++) a.ipv[k] = c->inv_projection_view[k];
+  a.t = T;
+  a.map_w = res[0], a.map_h = res[1];
+  a.material_count = mat.dptr ? c->material_count : 0u;
+  a.vis = static_cast<const uint32_t*>(c->visbuffer_attachment.dptr);
+  a.depth = static_cast<const float*>(dimg.dptr);
+  a.normalmap = static_cast<const uint32_t*>(c->normalmap.dptr);
+  a.splatmap = static_cast<const uint32_t*>(c->splatmap.dptr);
+  a.materials = static_cast<const uint32_t*>(mat.dptr);
+  a.hit = ring ? static_cast<const uint32_t*>(c->brush_hit.dptr) : nullptr;
+  a.albedo = static_cast<uint32_t*>(c->albedo_attachment.dptr);
+  a.normal = static_cast<uint2*>(c->normal_attachment.dptr);
+  a.emissive = static_cast<uint32_t*>(c->emissive_attachment.dptr);
+  a.mro = static_cast<uint32_t*>(mro.dptr);
+  launch_terrain_decode(a, s);
   OXC_HIP(ctx, hipGetLastError());
   return OXC_OK;
 }

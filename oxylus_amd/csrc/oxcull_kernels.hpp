@@ -810,6 +810,25 @@ struct TerrainBrushArgs {
 };
 void launch_terrain_brush_trace(const TerrainBrushArgs& a, hipStream_t s);
 void launch_terrain_brush_apply(const TerrainBrushArgs& a, hipStream_t s);
+// oxcull_terrain_decode.hip: the G-buffer of the terrain pixels (oxc_decode_terrain)
+struct TerrainDecodeArgs {
+  uint32_t w, h;
+  float fw, fh;
+  float ipv[16];         // Camera::inv_projection_view, column-major
+  oxc_terrain_data t;    // GPU::TerrainData; the decode reads world_min, inv_world_size, layer_material_indices, brush_radius
+  uint32_t map_w, map_h, material_count;
+  const uint32_t* vis;
+  const float* depth;
+  const uint32_t* normalmap;  // one word per texel: two binary16, x in the low half
+  const uint32_t* splatmap;   // R8G8B8A8 Unorm, R in the low byte
+  const uint32_t* materials;  // 14 words a record
+  const uint32_t* hit;        // {f32 world_position[3], u32 valid}; not read unless brush_radius > 0
+  uint32_t* albedo;
+  uint2* normal;
+  uint32_t* emissive;
+  uint32_t* mro;
+};
+void launch_terrain_decode(const TerrainDecodeArgs& a, hipStream_t s);
 // oxcull_bounds.hip: meshlet bounds producer
 void launch_build_meshlet_bounds(const float* pos, uint32_t vertex_count, const void* meshlets, uint32_t meshlet_count, const uint32_t* vidx,
                                  const uint8_t* micro, void* out_bounds, float* out_mesh6, void* out_qpos, float* meshlet_minmax, float* normals,

@@ -33,6 +33,26 @@ OXC_DEV unsigned short f_to_half(float x) { return __builtin_bit_cast(unsigned s
 // levels by it)
 OXC_DEV uint32_t channel_half(float x) { return x == x ? (uint32_t)f_to_half(x) : 0x7E00u; }
 
+// ---- what the two G-buffer producers (oxcull_visbuffer_decode.hip, oxcull_terrain_decode.hip) share ----------------------------------------
+constexpr uint32_t kTerrainInstanceId = 0xFFFFFEu;  // visbuffer.slang:16
+constexpr uint32_t kHalfNaN = 0x7E00u;
+
+// com::dequantize_half with the flush spelled out: an exponent field of 0 gives the sign alone (h in the low 16 bits)
+OXC_DEV float dequantize_half_flush(uint32_t h) { return (h & 0x7C00u) ? dequantize_half(h) : asf((h & 0x8000u) << 16); }
+
+// binary16 bits of a normal component: round to nearest even, denormals kept, every NaN the one pattern 0x7E00
+OXC_DEV uint32_t normal_half(float x) { return x == x ? (uint32_t)f_to_half(x) : kHalfNaN; }
+
+// com::vec3_to_oct (common/encoding.slang:17-21) as two normal halves, x in the low half (oxc_decode_visbuffer step 5)
+OXC_DEV uint32_t oct_halves(const V3& n) {
+  const float s = 1.0f / ((__builtin_fabsf(n.x) + __builtin_fabsf(n.y)) + __builtin_fabsf(n.z));
+  const float ox = n.x * s, oy = n.y * s;
+  const float sx = ox >= 0.0f ? 1.0f : -1.0f, sy = oy >= 0.0f ? 1.0f : -1.0f;
+  const bool fold = n.z <= 0.0f;
+  const float ex = fold ? (1.0f - __builtin_fabsf(oy)) * sx : ox, ey = fold ? (1.0f - __builtin_fabsf(ox)) * sy : oy;
+  return normal_half(ex) | (normal_half(ey) << 16);
+}
+
 // the log2 rule before its rounding: binary64, no contraction
 OXC_DEV double log2_f64(float x) {
   const uint32_t bits = asu(x);
@@ -97,6 +117,12 @@ __host__ OXC_DEV float exp_rule(float x) { return exp2_f64_round((double)x * 0x1
 
 // one component of packUnorm4x8: u32(floor(saturate(e) * 255.0 + 0.5)); a NaN gives 0
 OXC_DEV uint32_t pack_unorm(float e) { return cvt_u32_sat(floorf(saturate_f(e) * 255.0f + 0.5f)); }
+
+// the sRGB encoding of one linear channel, then unorm8 (oxc_decode_visbuffer step 6)
+OXC_DEV uint32_t srgb_unorm(float x) {
+  const float e = x <= 0.0031308f ? 12.92f * x : 1.055f * pow_rule(x, 1.0f / 2.4f) - 0.055f;
+  return pack_unorm(e);
+}
 
 // binary32 -> unsigned small float with a 5-bit exponent and MBITS of mantissa (UF11: 6, UF10: 5), truncating (oxc_decode_visbuffer
 // step 8; oxc_apply_pbr packs its B10G11R11 output by it)

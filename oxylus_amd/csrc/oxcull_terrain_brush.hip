@@ -33,11 +33,10 @@ OXC_DEV float sample_height(const TerrainBrushArgs& a, float wx, float wz) {
   const oxc_terrain_brush_params& B = a.p;
   const uint32_t w = B.resolution[0], h = B.resolution[1];
   const float u = (wx - B.world_min[0]) * B.inv_world_size[0], v = (wz - B.world_min[1]) * B.inv_world_size[1];
-  const Axis ax = axis_at<false>(u, (float)w, (int)w - 1), ay = axis_at<false>(v, (float)h, (int)h - 1);
-  const size_t r0 = (size_t)ay.i0 * w, r1 = (size_t)ay.i1 * w;
-  const float t00 = (float)a.heightmap[r0 + ax.i0] / 65535.0f, t10 = (float)a.heightmap[r0 + ax.i1] / 65535.0f;
-  const float t01 = (float)a.heightmap[r1 + ax.i0] / 65535.0f, t11 = (float)a.heightmap[r1 + ax.i1] / 65535.0f;
-  const float n = lerp_f(lerp_f(t00, t10, ax.f), lerp_f(t01, t11, ax.f), ay.f);
+  const MapTaps t = map_taps(u, v, w, h);
+  const float t00 = (float)a.heightmap[t.r0 + t.ax.i0] / 65535.0f, t10 = (float)a.heightmap[t.r0 + t.ax.i1] / 65535.0f;
+  const float t01 = (float)a.heightmap[t.r1 + t.ax.i0] / 65535.0f, t11 = (float)a.heightmap[t.r1 + t.ax.i1] / 65535.0f;
+  const float n = lerp_f(lerp_f(t00, t10, t.ax.f), lerp_f(t01, t11, t.ax.f), t.ay.f);
   return B.base_height + n * B.height_scale;
 }
 

@@ -15,6 +15,18 @@ struct V2 {
 
 OXC_DEV float clamp_lo_hi(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
 
+// Step B3's SampleLevel(LinearSamplerClamped, (u, v), 0) on a w x h terrain map before its loads: the clamped texel coordinates and
+// weights per axis and the two row offsets.  The caller loads texel (x, y) at r{y} + ax.i{x} in its map's format and blends
+// lerp(lerp(t00, t10, ax.f), lerp(t01, t11, ax.f), ay.f).
+struct MapTaps {
+  Axis ax, ay;
+  size_t r0, r1;
+};
+OXC_DEV MapTaps map_taps(float u, float v, uint32_t w, uint32_t h) {
+  const Axis ax = axis_at<false>(u, (float)w, (int)w - 1), ay = axis_at<false>(v, (float)h, (int)h - 1);
+  return {ax, ay, (size_t)ay.i0 * w, (size_t)ay.i1 * w};
+}
+
 // T2; (sx, sy) = f32(seed) * (0.06711056f, 0.00583715f)
 OXC_DEV V2 hash2(float x, float y, float sx, float sy) {
   const float qx = (x + sx) * kK0 + kK1, qy = (y + sy) * kK1 + kK0;

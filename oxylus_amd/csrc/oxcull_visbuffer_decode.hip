@@ -20,24 +20,9 @@
 namespace oxc {
 
 namespace {
-constexpr uint32_t kTerrainInstanceId = 0xFFFFFEu;  // visbuffer.slang:16
-constexpr uint32_t kHalfNaN = 0x7E00u;
-
-// com::dequantize_half with the flush spelled out: an exponent field of 0 gives the sign alone (h in the low 16 bits)
-OXC_DEV float dequantize_half_flush(uint32_t h) { return (h & 0x7C00u) ? dequantize_half(h) : asf((h & 0x8000u) << 16); }
-
 // Mesh::decode_normal, scene.slang:486-489
 OXC_DEV V3 decode_normal(uint32_t packed) {
   return {(float)((packed >> 20) & 1023u) / 511.0f - 1.0f, (float)((packed >> 10) & 1023u) / 511.0f - 1.0f, (float)(packed & 1023u) / 511.0f - 1.0f};
-}
-
-// binary16 bits of a normal component: round to nearest even, denormals kept, every NaN the one pattern 0x7E00
-OXC_DEV uint32_t normal_half(float x) { return x == x ? (uint32_t)f_to_half(x) : kHalfNaN; }
-
-// the sRGB encoding of one linear channel, then unorm8
-OXC_DEV uint32_t srgb_unorm(float x) {
-  const float e = x <= 0.0031308f ? 12.92f * x : 1.055f * pow_rule(x, 1.0f / 2.4f) - 0.055f;
-  return pack_unorm(e);
 }
 
 template <bool STATS>
@@ -153,12 +138,7 @@ __global__ __launch_bounds__(256) void k_visbuffer_decode(VisbufferDecodeArgs a)
   // 5. normal
   const V3 wnrm = normalize3({(l0 * wn[0].x + l1 * wn[1].x) + l2 * wn[2].x, (l0 * wn[0].y + l1 * wn[1].y) + l2 * wn[2].y,
                               (l0 * wn[0].z + l1 * wn[1].z) + l2 * wn[2].z});
-  const float s = 1.0f / ((__builtin_fabsf(wnrm.x) + __builtin_fabsf(wnrm.y)) + __builtin_fabsf(wnrm.z));
-  const float ox = wnrm.x * s, oy = wnrm.y * s;
-  const float sx = ox >= 0.0f ? 1.0f : -1.0f, sy = oy >= 0.0f ? 1.0f : -1.0f;
-  const bool fold = wnrm.z <= 0.0f;
-  const float ex = fold ? (1.0f - __builtin_fabsf(oy)) * sx : ox, ey = fold ? (1.0f - __builtin_fabsf(ox)) * sy : oy;
-  const uint32_t oct = normal_half(ex) | (normal_half(ey) << 16);
+  const uint32_t oct = oct_halves(wnrm);
   a.normal[pix] = make_uint2(oct, oct);
 
   // 6. albedo, 7. metallic / roughness / occlusion, 8. emissive

@@ -620,6 +620,13 @@ public:
     context.struct_size = sizeof context;
     check(oxc_apply_terrain_brush(ctx_, &context, stream_));
   }
+  // The terrain decode (Passes/Terrain.cpp:279-360): the four G-buffer images at the terrain pixels, after decode_visbuffer on the same
+  // attachments.  The free function decode_terrain below has the reference's name and argument shape.  Rules: include/oxcull.h,
+  // oxc_decode_terrain.
+  auto decode_terrain(oxc_terrain_decode_context context) -> void {
+    context.struct_size = sizeof context;
+    check(oxc_decode_terrain(ctx_, &context, stream_));
+  }
   auto build_meshlet_bounds(oxc_meshlet_bounds_desc desc) -> void {
     desc.struct_size = sizeof desc;
     check(oxc_build_meshlet_bounds(ctx_, &desc, stream_));
@@ -647,6 +654,7 @@ using TerrainDerive = oxc_terrain_derive;      // SceneGPU.hpp:386-395, 40 bytes
 using TerrainBrushParams = oxc_terrain_brush_params;  // scene.slang:606-621, 96 bytes
 using TerrainBrushHit = oxc_terrain_brush_hit;        // scene.slang:601-604
 using TerrainRegion = oxc_terrain_region;             // scene.slang:588-591
+using TerrainData = oxc_terrain_data;                 // scene.slang:634-647, SceneGPU.hpp:440-453, 76 bytes
 struct TerrainMinMax {                         // SceneGPU.hpp:397-400
   uint32_t resolution[2] = {};
   uint32_t patch_count[2] = {};
@@ -744,6 +752,43 @@ inline auto apply_terrain_brush(TerrainBrushContext& context) -> void {
   const float patch_texels_y = static_cast<float>(params.resolution[1]) / static_cast<float>(params.patch_count[1]);
   const uint32_t derive_patches = static_cast<uint32_t>(std::ceil(static_cast<float>(derive_texels) / std::min(patch_texels_x, patch_texels_y))) + 1u;
   terrain_minmax_pass(context.maps, minmax_settings, uvec2{derive_patches, derive_patches});
+}
+
+// RendererInstance.hpp's TerrainDecodeContext of the reference: its buffers and attachments under the reference's names, with what the
+// reference takes from the prepared frame (the camera's inv_projection_view, the materials) and from the terrain buffer carried beside them.
+struct TerrainDecodeContext {
+  RendererInstance* renderer = nullptr;
+  GPU::TerrainData terrain = {};  // terrain_buffer
+  float inv_projection_view[16] = {};
+  uvec2 map_resolution = {};
+  Buffer materials_buffer = {};
+  uint32_t material_count = 0;
+  Buffer brush_hit_buffer = {};
+  Buffer visbuffer_attachment = {};
+  oxc_image depth_attachment = {};
+  Buffer normalmap_attachment = {};
+  Buffer splatmap_attachment = {};
+  Buffer albedo_attachment = {};
+  Buffer normal_attachment = {};
+  Buffer emissive_attachment = {};
+  Buffer metallic_roughness_occlusion_attachment = {};
+};
+
+// RendererInstance::decode_terrain (Passes/Terrain.cpp:279-360)
+inline auto decode_terrain(TerrainDecodeContext& context) -> void {
+  if (!context.renderer) throw std::runtime_error("TerrainDecodeContext::renderer is not set");
+  oxc_terrain_decode_context c = {};
+  c.width = context.depth_attachment.width, c.height = context.depth_attachment.height;
+  for (int k = 0; k < 16; k++) c.inv_projection_view[k] = context.inv_projection_view[k];
+  c.terrain = context.terrain;
+  c.map_resolution[0] = context.map_resolution.x, c.map_resolution[1] = context.map_resolution.y;
+  c.material_count = context.material_count;
+  c.visbuffer_attachment = context.visbuffer_attachment, c.depth_attachment = context.depth_attachment;
+  c.normalmap = context.normalmap_attachment, c.splatmap = context.splatmap_attachment;
+  c.materials_buffer = context.materials_buffer, c.brush_hit = context.brush_hit_buffer;
+  c.albedo_attachment = context.albedo_attachment, c.normal_attachment = context.normal_attachment;
+  c.emissive_attachment = context.emissive_attachment, c.metallic_roughness_occlusion_attachment = context.metallic_roughness_occlusion_attachment;
+  context.renderer->decode_terrain(c);
 }
 
 }  // namespace ox::amd

@@ -108,5 +108,11 @@ int main(int argc, char**) {
   } catch (const std::exception& e) {
     std::printf("expected (no attachments bound): %s\n", e.what());
   }
+  try {  // RendererInstance.cpp:929-952: the terrain decode directly behind the visbuffer decode
+    auto terrain_decode_context = TerrainDecodeContext{.renderer = &self, .terrain = GPU::TerrainData{.layer_material_indices = {0, 1, 2, 3}}, .map_resolution = {2048, 2048}};
+    decode_terrain(terrain_decode_context);
+  } catch (const std::exception& e) {
+    std::printf("expected (no attachments bound): %s\n", e.what());
+  }
   return 0;
 }

@@ -47,6 +47,7 @@ TONEMAP_OUT_R8G8B8A8_SRGB, TONEMAP_OUT_B8G8R8A8_SRGB, TONEMAP_OUT_R8G8B8A8_UNORM
 LIGHT_KIND_DIRECTIONAL, LIGHT_KIND_POINT, LIGHT_KIND_SPOT = 0, 1, 2  # GPU::LightKind
 TERRAIN_GENERATE, TERRAIN_DERIVE, TERRAIN_MINMAX, TERRAIN_ALL = 1, 2, 4, 7  # oxc_terrain_maps_context.stages
 TERRAIN_BRUSH_TRACE, TERRAIN_BRUSH_APPLY, TERRAIN_BRUSH_ALL = 1, 2, 3  # oxc_terrain_brush_context.stages
+TERRAIN_INVALID_LAYER_MATERIAL = 0xFFFFFFFF  # scene.slang:632
 TERRAIN_BRUSH_RAISE, TERRAIN_BRUSH_SMOOTH, TERRAIN_BRUSH_FLATTEN, TERRAIN_BRUSH_NOISE, TERRAIN_BRUSH_PAINT_LAYER = 0, 1, 2, 3, 4  # GPU::TerrainBrushMode
 
 
@@ -746,6 +747,47 @@ class TerrainBrushContext(C.Structure):
     ]
 
 
+class TerrainData(C.Structure):
+    _c_name_ = "oxc_terrain_data"
+    _fields_ = [
+        ("world_min", C.c_float * 2),
+        ("world_size", C.c_float * 2),
+        ("inv_world_size", C.c_float * 2),
+        ("patch_count", C.c_uint32 * 2),
+        ("base_height", C.c_float),
+        ("height_scale", C.c_float),
+        ("target_edge_pixels", C.c_float),
+        ("max_tessellation", C.c_float),
+        ("layer_tiling", C.c_float),
+        ("triplanar_begin", C.c_float),
+        ("layer_material_indices", C.c_uint32 * 4),
+        ("brush_radius", C.c_float),
+    ]
+
+
+class TerrainDecodeContext(C.Structure):
+    _c_name_ = "oxc_terrain_decode_context"
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("inv_projection_view", C.c_float * 16),
+        ("terrain", TerrainData),
+        ("map_resolution", C.c_uint32 * 2),
+        ("material_count", C.c_uint32),
+        ("visbuffer_attachment", Buffer),
+        ("depth_attachment", Image),
+        ("normalmap", Buffer),
+        ("splatmap", Buffer),
+        ("materials_buffer", Buffer),
+        ("brush_hit", Buffer),
+        ("albedo_attachment", Buffer),
+        ("normal_attachment", Buffer),
+        ("emissive_attachment", Buffer),
+        ("metallic_roughness_occlusion_attachment", Buffer),
+    ]
+
+
 class MeshBuildDesc(C.Structure):
     _c_name_ = "oxc_mesh_build_desc"
     _fields_ = [("struct_size", C.c_uint32), ("vertex_count", C.c_uint32), ("index_count", C.c_uint32), ("max_lods", C.c_uint32), ("max_vertices", C.c_uint32),
@@ -813,6 +855,7 @@ PROTOTYPES = {
     "oxc_apply_pbr_atmosphere": (_status, [_vp, _P(PbrAtmosphereContext), _vp]),
     "oxc_generate_terrain_maps": (_status, [_vp, _P(TerrainMapsContext), _vp]),
     "oxc_apply_terrain_brush": (_status, [_vp, _P(TerrainBrushContext), _vp]),
+    "oxc_decode_terrain": (_status, [_vp, _P(TerrainDecodeContext), _vp]),
     "oxc_draw_physical_pages": (_status, [_vp, _P(PreparedFrame), _P(VsmDrawContext), _vp]),
     "oxc_debug_vsm_draw_stats": _stats,
     "oxc_resolve_shadowmap": (_status, [_vp, _P(ShadowResolveContext), _vp]),

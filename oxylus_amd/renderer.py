@@ -918,6 +918,64 @@ class TerrainBrushContext(Marshalled):
 
 
 @dataclass
+class TerrainData(Marshalled):
+    """GPU::TerrainData (scene.slang:634-647), field for field, with the record's own defaults (SceneGPU.hpp:440-453).  `of` forms it for a
+    Terrain centred on the origin, in binary32."""
+    _ctype = L.TerrainData
+    world_min: tuple = (0.0, 0.0)
+    world_size: tuple = (0.0, 0.0)
+    inv_world_size: tuple = (0.0, 0.0)
+    patch_count: tuple = (0, 0)
+    base_height: float = 0.0
+    height_scale: float = 0.0
+    target_edge_pixels: float = 16.0
+    max_tessellation: float = 64.0
+    layer_tiling: float = 8.0
+    triplanar_begin: float = 0.5
+    layer_material_indices: tuple = (L.TERRAIN_INVALID_LAYER_MATERIAL,) * 4
+    brush_radius: float = 0.0
+
+    @staticmethod
+    def of(world_size=(1024.0, 1024.0), patch_count=(64, 64), height_range=(0.0, 400.0), **settings) -> "TerrainData":
+        import numpy as np
+
+        F = np.float32
+        ws = [F(v) for v in world_size]
+        return TerrainData(tuple(float(-w * F(0.5)) for w in ws), tuple(float(w) for w in ws), tuple(float(F(1.0) / w) for w in ws),
+                           tuple(int(v) for v in patch_count), float(F(height_range[0])), float(F(height_range[1]) - F(height_range[0])), **settings)
+
+
+@dataclass
+class TerrainDecodeContext(Marshalled):
+    """oxc_terrain_decode_context: RendererInstance::decode_terrain (Passes/Terrain.cpp:279-360), the geometry and material-factor half of
+    terrain_decode.slang.  The four attachments are the ones a VisbufferDecodeContext wrote; only their terrain pixels are written.  `over`
+    binds a VisbufferDecodeContext's images, a TerrainMapsContext's normal and splat maps and a TerrainBrushContext's hit record."""
+    _ctype = L.TerrainDecodeContext
+    _derived = {"width": "depth_attachment.width", "height": "depth_attachment.height"}
+    visbuffer_attachment: Optional[torch.Tensor]  # int32 [H, W]
+    depth_attachment: ImageAttachment             # R32F, levels = 1
+    inv_projection_view: list                     # column-major float[16]
+    terrain: TerrainData
+    map_resolution: tuple
+    normalmap: Optional[torch.Tensor]             # int16 [h, w, 2]: R16G16 Sfloat bits
+    splatmap: Optional[torch.Tensor]              # int32 [h, w]: R8G8B8A8 Unorm
+    materials_buffer: Optional[torch.Tensor]      # uint8 [material_count * 56]
+    material_count: int
+    brush_hit: Optional[torch.Tensor]             # int32 [4]: oxc_terrain_brush_hit; may be None unless terrain.brush_radius > 0
+    albedo_attachment: Optional[torch.Tensor]
+    normal_attachment: Optional[torch.Tensor]
+    emissive_attachment: Optional[torch.Tensor]
+    metallic_roughness_occlusion_attachment: Optional[torch.Tensor]
+
+    @staticmethod
+    def over(decode: "VisbufferDecodeContext", maps: TerrainMapsContext, inv_projection_view, terrain: TerrainData, brush_hit: Optional[torch.Tensor] = None) -> "TerrainDecodeContext":
+        h, w = maps.splatmap.shape[:2]
+        return TerrainDecodeContext(decode.visbuffer_attachment, decode.depth_attachment, [float(x) for x in inv_projection_view], terrain, (int(w), int(h)),
+                                    maps.normalmap, maps.splatmap, decode.materials_buffer, decode.material_count, brush_hit, decode.albedo_attachment,
+                                    decode.normal_attachment, decode.emissive_attachment, decode.metallic_roughness_occlusion_attachment)
+
+
+@dataclass
 class VisbufferDecodeContext(Marshalled):
     """oxc_decode_context: RendererInstance::decode_visbuffer (Passes/DrawGeometry.cpp:192-274), the geometry and material-factor half of
     visbuffer_decode.slang.  `create` takes the visbuffer and the depth as oxc_draw_visbuffer resolved them, the matrix they were drawn with and
@@ -1251,6 +1309,11 @@ class RendererInstance:
         """Passes/Terrain.cpp:35-132 (terrain_brush_trace, terrain_brush_apply): the stages of context.stages in the order trace, apply
         (include/oxcull.h, oxc_apply_terrain_brush).  `context.region` is the record generate_terrain_maps reads for the regional re-bake."""
         self._call("oxc_apply_terrain_brush", context, stream)
+
+    def decode_terrain(self, context: TerrainDecodeContext, stream=None) -> None:
+        """Passes/Terrain.cpp:279-360 (terrain_decode): the four G-buffer images at the terrain pixels, one launch (include/oxcull.h,
+        oxc_decode_terrain).  After decode_visbuffer on the same attachments; every other pixel keeps its bytes."""
+        self._call("oxc_decode_terrain", context, stream)
 
     def generate_terrain_maps(self, context: TerrainMapsContext, stream=None) -> None:
         """Scene/Terrain.cpp:406-461 and Passes/Terrain.cpp:134-156 (terrain_generate, terrain_derive, terrain_minmax): the stages of
