@@ -60,10 +60,12 @@ oxc_status oxc_draw_visbuffer(oxc_ctx* ctx, const oxc_prepared_frame* f, const o
   a.clip_list = reinterpret_cast<uint32_t*>(rs + kRasterHeaderBytes + (size_t)cap * kTriSetupBytes);
   a.tile_capacity = cap * 2;
   a.tile_list = reinterpret_cast<uint2*>(rs + kRasterHeaderBytes + (size_t)cap * (kTriSetupBytes + 4));
+  const uint32_t full_grid = ctx->num_cus * 8;
+  const uint32_t max_grid = ctx->raster_grid ? std::min(ctx->raster_grid, full_grid) : full_grid;  // OXC_TUNE_RASTER_GRID
   {
     KernelTimer t(ctx, OXC_K_DRAW_VISBUFFER, s);
     launch_draw_visbuffer(a, d->clear != 0, dep.dptr ? reinterpret_cast<float*>(static_cast<char*>(dep.dptr) + dep.level_offset[0]) : nullptr,
-                          static_cast<uint32_t*>(d->visbuffer_attachment.dptr), ctx->num_cus * 8, s);
+                          static_cast<uint32_t*>(d->visbuffer_attachment.dptr), max_grid, s);
   }
   OXC_HIP(ctx, hipGetLastError());
   return OXC_OK;

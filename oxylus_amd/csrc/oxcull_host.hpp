@@ -83,6 +83,7 @@ struct oxc_ctx {
   void* raster_scratch = nullptr;  // oxc_draw_visbuffer: list of large triangles + its counter
   uint32_t raster_capacity = 0;    // entries of the big / clip lists (the tile list has twice as many)
   uint32_t raster_capacity_request = 0;  // oxc_debug_set_tuning(OXC_TUNE_RASTER_BIG_CAPACITY): used by the first draw instead of the default
+  uint32_t raster_grid = 0;              // OXC_TUNE_RASTER_GRID: cap of every launch of the draw in blocks, 0 = uncapped
   void* raster_rows = nullptr;     // oxc_draw_visbuffer: one DrawRow per mesh instance
   uint32_t raster_rows_cap = 0;
   void* vsm_scratch = nullptr;     // oxc_update_virtual_shadowmap: free page list (u32 per physical page), then the per-page mark map (a byte per entry)

@@ -651,11 +651,11 @@ void launch_draw_visbuffer(const DrawArgs& a, bool clear, float* depth_out, uint
   hipLaunchKernelGGL(k_draw_rows, dim3(std::max(1u, std::min((a.mesh_instance_count + 255u) / 256u, max_grid))), dim3(256), 0, s, a);
   if (a.wide == 2u) {  // {id, corner} pairs
     hipLaunchKernelGGL(k_draw_setup<true>, dim3(max_grid), dim3(256), 0, s, a);
-    hipLaunchKernelGGL((k_draw_clipped<false, true>), dim3(256), dim3(64), 0, s, a);
+    hipLaunchKernelGGL((k_draw_clipped<false, true>), dim3(std::min(256u, max_grid)), dim3(64), 0, s, a);
     hipLaunchKernelGGL((k_draw_clipped<true, true>), dim3(max_grid), dim3(64), 0, s, a);
   } else {
     hipLaunchKernelGGL(k_draw_setup<false>, dim3(max_grid), dim3(256), 0, s, a);
-    hipLaunchKernelGGL((k_draw_clipped<false, false>), dim3(256), dim3(64), 0, s, a);
+    hipLaunchKernelGGL((k_draw_clipped<false, false>), dim3(std::min(256u, max_grid)), dim3(64), 0, s, a);
     hipLaunchKernelGGL((k_draw_clipped<true, false>), dim3(max_grid), dim3(64), 0, s, a);  // (returns at once unless the id queue overflowed)
   }
   hipLaunchKernelGGL(k_draw_big, dim3(max_grid), dim3(256), 0, s, a);
