@@ -2131,6 +2131,137 @@ typedef struct oxc_terrain_decode_context {
 
 oxc_status oxc_decode_terrain(oxc_ctx* ctx, const oxc_terrain_decode_context* context, void* hip_stream);
 
+/* ---- the debug views: what the cull, the LOD select, the rasteriser, the decodes and the page update decided, as a picture ----------------
+ * oxc_apply_debug_view is RendererInstance::apply_debug_view (Passes/Debug.cpp:9-153, pipelines debug_view and rmvsm_debug, shaders
+ * passes/debug_view.slang and passes/rmvsm_debug.slang), the pass that replaces the final image when a debug view is selected
+ * (RendererInstance.cpp:1300-1323): per pixel a colour for the triangle, meshlet, material, mesh or LOD behind the visbuffer texel, the
+ * overdraw heat, one G-buffer channel or the ambient occlusion, with a depth outline; or, for OXC_DEBUG_VIEW_RMVSM, the state of the VSM
+ * page the pixel falls in.  One launch, one R16G16B16A16 Sfloat image out.
+ * Not built: a producer for the overdraw image (oxc_draw_visbuffer has no counting mode, visbuffer_encode.slang:69-71; the caller fills
+ * the u32 image); draw_bounding_boxes (Debug.cpp:155-211, line rasterisation); the editor's picking and highlight passes.
+ * Arithmetic: the conventions of oxc_apply_pbr's block -- binary32, round to nearest even, the Slang's order left to right, no
+ * contraction, IEEE division; min, max and saturate through fminf / fmaxf (a NaN operand loses, saturate(NaN) = 0); a comparison with a
+ * NaN operand is false; f32(u32) rounds to nearest even; a half store is round to nearest even with denormals kept and a NaN stored as
+ * 0x7E00 (oxc_apply_pbr step 12); log2 is the log2 rule of oxc_generate_ambient_occlusion rounded to binary32 once (an argument below
+ * 2^-126, negative or NaN gives -Inf), exp2 the exp2 rule of oxc_apply_pbr.  TAU = 6.283185307179586f, the nearest binary32.  The float
+ * `%` is fmodf, which is exact; a non-finite operand gives NaN.
+ *   hash(a)  (debug_view.slang:31-39), modulo 2^32:  a = (a + 0x7ed55d16) + (a << 12);  a = (a ^ 0xc761c23c) ^ (a >> 19);  a = (a +
+ *              0x165667b1) + (a << 5);  a = (a + 0xd3a2646c) ^ (a << 9);  a = (a + 0xfd7046c5) + (a << 3);  a = (a ^ 0xb55a4f09) ^ (a >> 16).
+ *              hash colour of h = hash(a): (f32(h & 255), f32((h >> 8) & 255), f32((h >> 16) & 255)) / 255.0f, three divisions.
+ *   hsv_to_rgb((hue, 1.0, 0.5))  (:25-29, rmvsm_debug.slang:14-18)  q = hue / 1.0471975512f;  per component of n = (5.0, 3.0, 1.0):  k =
+ *              fmodf(n + q, 6.0f);  0.5 - (0.5 * 1.0) * max(0.0, min(k, min(4.0 - k, 1.0))).  A NaN k gives 0.5 - 0.5 * 1.0 = 0.0.
+ * The main views (debug_view.slang), per pixel (x, y) of the W x H images, texel = the visbuffer texel:
+ *   V1. discard  (:97-101)  texel == ~0u: with `clear` the pixel is written as the four halves 0, 0, 0, 0x3C00, otherwise it is not
+ *              touched.  Stated rule: that value stands for the engine's clear_image(.., vuk::Black) in front of the pass (Debug.cpp:34);
+ *              the vuk header that defines Black is not part of the reference tree.
+ *   V2. colour   (:109-164)
+ *              Triangles: the hash colour of texel & 0xFF.  Meshlets: of texel >> 8.  Neither reads a record.
+ *              Materials: of mesh_instance.material_index.  MeshInstances: of mesh_instance.mesh_index, as the Slang does despite the
+ *              name.  mesh_instance = mesh_instances[meshlet_instances[texel >> 8].mesh_instance_index], by V3.
+ *              MeshLods: hue = (f32(mesh_instance.lod_index) / f32(mesh.lod_count + 1)) * TAU, the u32 sum wrapping (lod_count ==
+ *              0xFFFFFFFF divides by 0.0), mesh = meshes[mesh_instance.mesh_index];  hsv_to_rgb((hue, 1.0, 0.5)).
+ *              Overdraw: draw_scale = min(max(heatmap_scale, 0.0), 100.0) / 100.0f (a NaN scale gives 0);  heat = 1.0 - exp2((-f32(count))
+ *              * draw_scale), count the overdraw texel;  t = saturate(heat);  inferno(t) per channel = c0 + t * (c1 + t * (c2 + t * (c3 + t
+ *              * (c4 + t * (c5 + t * c6))))) as nested at :51, the seven constants of :42-48 the nearest binary32.
+ *              Albedo: stated rule, as oxc_apply_pbr step 2 for the clamped sampler: the linear repeat sampler at the pixel centre is the
+ *              load of texel (x, y); bytes R, G, B through the sRGB decode of that step.
+ *              Normal: oct_to_vec3(.rg of the normal texel) * 0.5 + 0.5 per channel, oct_to_vec3 as in oxc_resolve_shadowmap step 2 (one
+ *              normalisation).  GeometricNormal: the same on .ba.
+ *              Emissive: the exact UF11 / UF11 / UF10 decode of oxc_apply_pbr step 2 (it can give Inf and NaN; V4 saturates them).
+ *              Metallic, Roughness, BakedOcclusion: byte 0, 1 or 2 of the texel as f32(byte) / 255.0f, in all three channels.
+ *              GTAO: the ambient-occlusion half, binary16 -> binary32 exact with denormals kept, in all three channels.
+ *   V3. bounds   Stated rule for Materials, MeshInstances and MeshLods: a texel with (texel >> 8) >= meshlet_instance_count uses an
+ *              all-zero MeshInstance and an all-zero Mesh -- hash(0), or hue (0.0 / 1.0) * TAU -- and loads nothing; terrain texels
+ *              (0xFFFFFE) are the common case.  The Slang reads past the buffer there.  Every other index of the chain
+ *              (mesh_instance_index, mesh_index) is the scene's own and is not checked, as in oxc_decode_visbuffer.  Triangles, Meshlets,
+ *              Overdraw and the G-buffer views perform no record load at all: the Slang's three loads (:105-107) are dead code for them.
+ *   V4. outline  (:54-89)  gx = gy = 0.0.  For tap = 0 .. 8 in the order of sample_offset, (-1, 1) (0, 1) (1, 1) (-1, 0) (0, 0) (1, 0) (-1, -1)
+ *              (0, -1) (1, -1):  p = (x, y) + offset.  A tap outside the image adds nothing (the robust loads give texel 0 and depth 0, and
+ *              log2(1.0) * 10.0 = 0.0 changes no sum); a tap whose visbuffer texel is ~0u is skipped.  Otherwise s = log2(depth(p) + 1.0f) *
+ *              10.0f;  gx = gx + f32(sobel_x[tap]) * s;  gy = gy + f32(sobel_y[tap]) * s, sobel_x = 1 0 -1 2 0 -2 1 0 -1, sobel_y = 1 2 1 0
+ *              0 0 -1 -2 -1.  The product with a zero weight is formed: 0.0 * Inf is NaN.  (The Slang's three channels of x and of y are
+ *              equal; one is kept.)  outline = fmaxf(|gx|, |gy|);  colour = saturate(colour * (1.0 - outline)) per channel;  the store is
+ *              the four halves of (colour, 1.0), R lowest.  s is -Inf for depth <= -1 and for a NaN depth, +Inf for +Inf, never NaN.
+ * The RMVSM view (rmvsm_debug.slang), per pixel; no outline, no discard, `clear` is ignored, every pixel is written:
+ *   R1. sky      (:25-28)  depth == 0.0 stores (1, 1, 1, 1) (a NaN depth is not sky).
+ *   R2. set-up   (:33-39)  uv, world and the clipmap index c exactly as oxc_resolve_shadowmap step 2.  flat_N (:30-31) is unused and not
+ *              computed; the normal image is not read.  h = M_c (world, 1);  clip_uv = (h.xy / h.w + 1.0) * 0.5, as in that block's tap.
+ *   R3. texel    (:45-48)  A component of clip_uv outside [0, 1], or NaN (stated: a NaN counts as outside, as the resolve does): the in-page
+ *              texel is page_size - 1 on both axes, the Slang's com::mod(-1, page_size).  Otherwise in_page = int(floor(clip_uv *
+ *              f32(physical_page_table_size))) % page_size per axis, in integers -- the Slang's physical extent, NOT the resolve's V =
+ *              page_table_size * page_size: this pass draws the grid the reference draws.  near_border = any(in_page < 2) || any(in_page >
+ *              page_size - 2).
+ *   R4. border   (:51-55)  near_border stores hsv_to_rgb(((f32(c) / f32(clipmap_count + 1)) * TAU, 1.0, 0.5)) with alpha 1.0 and reads no
+ *              page-table entry.
+ *   R5. page     (:41-43, 57-62)  virt = int(floor(clip_uv * f32(page_table_size))) per axis;  entry = virtual_page_table[c][wrapped.y]
+ *              [wrapped.x], wrapped = floor_mod(virt + page_offset, page_table_size) as in oxc_update_virtual_shadowmap.  virt is inside
+ *              the table: clip_uv lies in [0, 1], so virt >= 0; and n * u rounds to n only for u == 1.0 (for u <= 1 - 2^-24 the product is
+ *              at least half an ulp of n below n), where in_page is physical_page_table_size % page_size = 0 and R4 has taken the pixel
+ *              (f32(physical_page_table_size) is exact up to 2^24; beyond it the kernel still loads nothing outside the table: a virt
+ *              outside [0, n - 1] reads entry 0, the Slang's robust load at INVALID_COORDS).  With the flag bits of
+ *              oxc_update_virtual_shadowmap (Visible 1, Dirty 2, Backed 4):  not Backed and Visible stores (1, 0, 0, 1);  otherwise
+ *              (Backed, Dirty, Visible, 1) as 0.0 or 1.0.
+ * Inputs: an input the selected view does not read is not read, not checked and may be null (as the images of oxc_apply_pbr whose flag
+ * is clear).  Every view except RMVSM reads visbuffer_attachment and depth_attachment (V1, V4); Overdraw also overdraw_attachment;
+ * Albedo albedo_attachment; Normal and GeometricNormal normal_attachment; Emissive emissive_attachment; Metallic, Roughness and
+ * BakedOcclusion metallic_roughness_occlusion_attachment; GTAO ambient_occlusion_attachment; Materials, MeshInstances and MeshLods the
+ * frame's meshlet_instances_buffer, mesh_instances_buffer and meshes_buffer (`frame` may be NULL for every other view).  RMVSM reads
+ * depth_attachment, vsm_clipmaps_buffer and virtual_page_table only, with the eleven VSM and camera fields.
+ * Limits (else OXC_INVALID_ARG, nothing launched, nothing written; the first broken rule in this order gives the message, each has its
+ * own): struct_size; debug_view in OXC_DEBUG_VIEW_TRIANGLES .. OXC_DEBUG_VIEW_RMVSM (0, the reference's None, is refused: the engine does
+ * not run the pass then); width and height non-zero; both equal to the depth attachment's, which is one R32F level at offset 0 of at most
+ * 65536 a side; for RMVSM the shape limits of oxc_resolve_shadowmap; for Materials, MeshInstances and MeshLods `frame` non-null; then
+ * every buffer the view reads in the order of the context's fields, then the frame's three, then debug_attachment -- non-null, then
+ * aligned to its texel or record (4 bytes; ambient_occlusion_attachment 2; normal_attachment, debug_attachment and meshes_buffer, whose
+ * GPU::Mesh records hold 64-bit addresses, 8), then at least as large as its
+ * extent (one texel per pixel; clipmap_count records of 76 bytes; clipmap_count * n * n entries; meshlet_instance_count records of 8
+ * bytes; the other two frame buffers as given); then debug_attachment shares no byte with any buffer the view reads.  heatmap_scale and
+ * every other float are taken as given, NaN included.  One launch, no scratch, no allocation, no host synchronisation; capturable into a
+ * HIP graph. */
+#define OXC_DEBUG_VIEW_TRIANGLES 1u /* GPU::DebugView, scene.slang:10-26 and SceneGPU.hpp:28-47; 0 is None */
+#define OXC_DEBUG_VIEW_MESHLETS 2u
+#define OXC_DEBUG_VIEW_OVERDRAW 3u
+#define OXC_DEBUG_VIEW_MATERIALS 4u
+#define OXC_DEBUG_VIEW_MESH_INSTANCES 5u
+#define OXC_DEBUG_VIEW_MESH_LODS 6u
+#define OXC_DEBUG_VIEW_ALBEDO 7u
+#define OXC_DEBUG_VIEW_NORMAL 8u
+#define OXC_DEBUG_VIEW_EMISSIVE 9u
+#define OXC_DEBUG_VIEW_METALLIC 10u
+#define OXC_DEBUG_VIEW_ROUGHNESS 11u
+#define OXC_DEBUG_VIEW_BAKED_OCCLUSION 12u
+#define OXC_DEBUG_VIEW_GTAO 13u
+#define OXC_DEBUG_VIEW_GEOMETRIC_NORMAL 14u
+#define OXC_DEBUG_VIEW_RMVSM 15u /* the C++ enum's member after GeometricNormal (SceneGPU.hpp:44); the Slang enum stops at 14 */
+typedef struct oxc_debug_view_context {
+  uint32_t struct_size; /* sizeof(oxc_debug_view_context) */
+  uint32_t width, height;
+  uint32_t debug_view;             /* OXC_DEBUG_VIEW_* */
+  uint32_t clear;                  /* V1: discarded pixels are written as 0, 0, 0, 0x3C00 */
+  float heatmap_scale;             /* Overdraw: DebugContext::overdraw_heatmap_scale */
+  uint32_t meshlet_instance_count; /* V3 */
+  /* RMVSM: the GPU::VSMContext and GPU::Camera fields the pass reads, as in oxc_shadow_resolve_context */
+  int32_t page_size, page_table_size, physical_page_table_size, clipmap_count;
+  float first_clipmap_width;
+  float clipmap_selection_bias;
+  float virtual_extent;
+  float inv_projection_view[16];   /* column-major */
+  float resolution[2];
+  oxc_buffer visbuffer_attachment; /* in: u32[height][width] */
+  oxc_image depth_attachment;      /* in: R32F, levels = 1 */
+  oxc_buffer overdraw_attachment;  /* in: R32 Uint, u32[height][width] */
+  oxc_buffer albedo_attachment;    /* in: the four attachments of oxc_decode_context, same formats and layouts */
+  oxc_buffer normal_attachment;
+  oxc_buffer emissive_attachment;
+  oxc_buffer metallic_roughness_occlusion_attachment;
+  oxc_buffer ambient_occlusion_attachment; /* in: binary16 as u16[height][width], as oxc_apply_pbr reads it */
+  oxc_buffer vsm_clipmaps_buffer;  /* in: oxc_virtual_clipmap[clipmap_count] */
+  oxc_buffer virtual_page_table;   /* in: u32 [clipmap_count][n][n] */
+  oxc_buffer debug_attachment;     /* out: R16G16B16A16 Sfloat, u16x4[height][width], R in the lowest half */
+} oxc_debug_view_context;
+
+oxc_status oxc_apply_debug_view(oxc_ctx* ctx, const oxc_prepared_frame* frame, const oxc_debug_view_context* context, void* hip_stream);
+
 /* ---- multi-GPU exchange: one process per GPU, RCCL over xGMI ---------------------------
  * The meshlet-instance array shards by contiguous range and every rank culls its shard on its own; the only
  * exchanges of the path are (1) the per-rank counters {emitted meshlets, early, late, index count} to every rank

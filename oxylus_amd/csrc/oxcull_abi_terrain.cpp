@@ -7,41 +7,6 @@
 namespace {
 constexpr uint32_t kStageAll = OXC_TERRAIN_GENERATE | OXC_TERRAIN_DERIVE | OXC_TERRAIN_MINMAX;
 
-// One buffer of the call, as the limits see it: which stages touch it, which write it, its texel (= alignment) and the bytes its extent asks
-struct MapBuffer {
-  const char* name;
-  const void* dptr;
-  uint64_t have, need;
-  uint32_t align, touched_by, written_by;
-  bool may_be_null;
-  const char* too_small = " is smaller than its extent";
-};
-
-// The buffer limits both calls share, over the buffers `stages` touches: in the table's order non-null, aligned, large enough; then no
-// written buffer sharing a byte with another touched one.  The message of the first broken rule, or OXC_OK.
-template <size_t N>
-oxc_status check_buffers(oxc_ctx* ctx, const char* entry, const MapBuffer (&buffers)[N], uint32_t stages) {
-  for (const MapBuffer& b : buffers) {
-    if (!(b.touched_by & stages)) continue;
-    if (!b.dptr) {
-      if (b.may_be_null) continue;
-      return bad_arg(ctx, entry, b.name, " must not be null");
-    }
-    if (reinterpret_cast<uintptr_t>(b.dptr) & (b.align - 1u)) return bad_arg(ctx, entry, b.name, " must be aligned to its texel");
-    if (b.have < b.need) return bad_arg(ctx, entry, b.name, b.too_small);
-  }
-  for (const MapBuffer& w : buffers) {
-    if (!(w.written_by & stages)) continue;
-    const uintptr_t lo = reinterpret_cast<uintptr_t>(w.dptr);
-    for (const MapBuffer& o : buffers) {
-      if (&o == &w || !(o.touched_by & stages) || !o.dptr) continue;
-      const uintptr_t olo = reinterpret_cast<uintptr_t>(o.dptr);
-      if (ByteSpan{lo, lo + (uintptr_t)w.need}.overlaps({olo, olo + (uintptr_t)o.need})) return bad_arg(ctx, entry, w.name, " must not overlap ", o.name);
-    }
-  }
-  return OXC_OK;
-}
-
 // roundup(dispatch, group) as a thread count, capped at roundup(extent, group): what lies beyond cannot land inside the map without wrapping
 uint32_t threads_of(uint32_t dispatch, uint32_t extent, uint32_t group) {
   const uint64_t want = ((uint64_t)dispatch + group - 1u) / group * group;

@@ -829,6 +829,42 @@ struct TerrainDecodeArgs {
   uint32_t* mro;
 };
 void launch_terrain_decode(const TerrainDecodeArgs& a, hipStream_t s);
+// oxcull_debug_view.hip: the debug views (oxc_apply_debug_view)
+struct DebugViewArgs {  // the main views, OXC_DEBUG_VIEW_TRIANGLES .. OXC_DEBUG_VIEW_GEOMETRIC_NORMAL
+  uint32_t w, h, clear, meshlet_instance_count;
+  float heatmap_scale;
+  const uint32_t* vis;
+  const float* depth;
+  // what the selected view reads; the others are null
+  const uint32_t* overdraw;
+  const uint32_t* albedo;
+  const uint2* normal;  // {r | g << 16, b | a << 16}
+  const uint32_t* emissive;
+  const uint32_t* mro;
+  const uint16_t* ao;
+  const GpuMeshletInstance* meshlet_instances;
+  const GpuMeshInstance* mesh_instances;
+  const GpuMesh* meshes;
+  uint2* out;  // u16x4 [h][w]
+};
+void launch_debug_view(uint32_t view, const DebugViewArgs& a, hipStream_t s);
+struct DebugViewVsmArgs {  // OXC_DEBUG_VIEW_RMVSM
+  const float* depth;
+  uint2* out;
+  uint32_t w, h;
+  const float* clipmaps;       // GPU::VirtualClipmap[layers], 19 words each
+  const uint32_t* page_table;  // [layers][n][n]
+  uint32_t n, layers, page_size;
+  float fn, fphys;             // float(n), float(physical_page_table_size)
+  float hue_divisor;           // f32(clipmap_count + 1)
+  // as VsmResolveArgs: clipmap_selection_constants fills them
+  float inv_pv[16];
+  float off_x, off_y;
+  float texel_len;
+  uint32_t lvl_always;
+  float lvl_thr[16];
+};
+void launch_debug_view_vsm(const DebugViewVsmArgs& a, hipStream_t s);
 // oxcull_bounds.hip: meshlet bounds producer
 void launch_build_meshlet_bounds(const float* pos, uint32_t vertex_count, const void* meshlets, uint32_t meshlet_count, const uint32_t* vidx,
                                  const uint8_t* micro, void* out_bounds, float* out_mesh6, void* out_qpos, float* meshlet_minmax, float* normals,

@@ -70,15 +70,6 @@ __host__ OXC_DEV float cos_rule(float x) {
   return (float)v;
 }
 
-// one channel of the sRGB decode
-OXC_DEV float srgb_decode(uint32_t byte) {
-  const float c = (float)byte / 255.0f;
-  return c <= 0.04045f ? c / 12.92f : pow_rule((c + 0.055f) / 1.055f, 2.4f);
-}
-
-// com::oct_to_vec3 of the two halves of `word` (the first in the low half): one normalisation
-OXC_DEV V3 oct_to_vec3(uint32_t word) { return normalize3(oct_normal_ba(word)); }
-
 // what BRDF (pbr.slang:61-87) takes from the pixel alone
 struct Surface {
   V3 N, V;

@@ -124,6 +124,12 @@ OXC_DEV uint32_t srgb_unorm(float x) {
   return pack_unorm(e);
 }
 
+// one channel of the sRGB decode (oxc_apply_pbr step 2; the Albedo debug view reads by it too)
+OXC_DEV float srgb_decode(uint32_t byte) {
+  const float c = (float)byte / 255.0f;
+  return c <= 0.04045f ? c / 12.92f : pow_rule((c + 0.055f) / 1.055f, 2.4f);
+}
+
 // binary32 -> unsigned small float with a 5-bit exponent and MBITS of mantissa (UF11: 6, UF10: 5), truncating (oxc_decode_visbuffer
 // step 8; oxc_apply_pbr packs its B10G11R11 output by it)
 template <int MBITS>
@@ -238,6 +244,24 @@ OXC_DEV V3 oct_normal_ba(uint32_t nba) {
   o.x = fold ? (1.0f - __builtin_fabsf(ey)) * sx : ex;
   o.y = fold ? (1.0f - __builtin_fabsf(ex)) * sy : ey;
   return o;
+}
+
+// com::oct_to_vec3 of the two halves of `word` (the first in the low half): one normalisation
+OXC_DEV V3 oct_to_vec3(uint32_t word) { return normalize3(oct_normal_ba(word)); }
+
+// The world position and the clipmap index of pixel (u, v) at depth d (oxc_resolve_shadowmap step 2): `a` carries inv_pv, the footprint
+// offsets, texel_len and the level thresholds of clipmap_selection_constants.  One copy for the resolve and the RMVSM debug view, which
+// must agree with the page update's pixel_page (oxcull_vsm.hip) on every pixel's clipmap.
+template <class Args>
+OXC_DEV int pixel_world_and_clipmap(const Args& a, float u, float v, float d, V3& world) {
+  V3 lf, rt;
+  unproject(a.inv_pv, u, v, d, world.x, world.y, world.z);
+  unproject(a.inv_pv, u + -a.off_x, v + a.off_y, d, lf.x, lf.y, lf.z);
+  unproject(a.inv_pv, u + a.off_x, v + a.off_y, d, rt.x, rt.y, rt.z);
+  const float r = len3(lf.x - rt.x, lf.y - rt.y, lf.z - rt.z) / a.texel_len;
+  uint32_t idx = a.lvl_always;
+  for (uint32_t k = a.lvl_always; k + 1 < a.layers; k++) idx += (r > a.lvl_thr[k]) ? 1u : 0u;  // NaN: never
+  return (int)idx;
 }
 
 // (cos, sin) of 2 pi t, t a binary32 in [0, 1): exact reduction to an octant, two binary64 polynomials by Horner, one rounding each

@@ -90,14 +90,8 @@ __global__ __launch_bounds__(256) void k_vsm_resolve_shadow(VsmResolveArgs a) {
 
   // pixel set-up
   const float u = ((float)px + 0.5f) / (float)a.w, v = ((float)py + 0.5f) / (float)a.h;
-  V3 world, lf, rt;
-  unproject(a.inv_pv, u, v, d, world.x, world.y, world.z);
-  unproject(a.inv_pv, u + -a.off_x, v + a.off_y, d, lf.x, lf.y, lf.z);
-  unproject(a.inv_pv, u + a.off_x, v + a.off_y, d, rt.x, rt.y, rt.z);
-  const float r = len3(lf.x - rt.x, lf.y - rt.y, lf.z - rt.z) / a.texel_len;
-  uint32_t idx = a.lvl_always;  // (the loop of oxcull_vsm.hip's pixel_page: the two must select the same clipmap)
-  for (uint32_t k = a.lvl_always; k + 1 < a.layers; k++) idx += (r > a.lvl_thr[k]) ? 1u : 0u;  // NaN: never
-  const int base = (int)idx;
+  V3 world;
+  const int base = pixel_world_and_clipmap(a, u, v, d, world);
 
   // flat_N = normalize(oct_to_vec3(normal.ba))
   const V3 N = normalize3(normalize3(oct_normal_ba(a.normal[pix * 2u + 1u])));

@@ -155,6 +155,27 @@ struct Extent3D {
 };
 // A mip pyramid of the final attachment's format in one allocation (oxc_image_pyramid): the stand-in for the two bloom images.
 using ImagePyramid = oxc_image_pyramid;
+// RendererInstance.hpp:327-342 of the reference: the debug view's settings and attachments under the reference's names.  debug_view is
+// GPU::DebugView as OXC_DEBUG_VIEW_* (0 = None).  What the reference takes from the instance for the RMVSM view -- the VSM shape constants,
+// first_clipmap_width, clipmap_selection_bias and the camera -- is carried in `vsm` (its depth, normal, physical-page and output fields are
+// not read), and `debug_attachment`, which the reference declares inside the pass, is caller-owned.
+struct DebugContext {
+  float overdraw_heatmap_scale = 0.0f;
+  uint32_t debug_view = 0;
+  Buffer vsm_clipmaps_buffer = {};
+  Buffer visbuffer_attachment = {};
+  ImageAttachment depth_attachment = {};
+  Buffer overdraw_attachment = {};
+  Buffer albedo_attachment = {};
+  Buffer normal_attachment = {};
+  Buffer emissive_attachment = {};
+  Buffer metallic_roughness_occlusion_attachment = {};
+  Buffer ambient_occlusion_attachment = {};
+  Buffer vsm_page_table_attachment = {};
+  ShadowResolveContext vsm = {};
+  Buffer debug_attachment = {};
+};
+
 struct PostProcessContext {
   float delta_time = 0.0f;
   Extent3D extent = {};
@@ -626,6 +647,46 @@ public:
   auto decode_terrain(oxc_terrain_decode_context context) -> void {
     context.struct_size = sizeof context;
     check(oxc_decode_terrain(ctx_, &context, stream_));
+  }
+  // RendererInstance::apply_debug_view (Passes/Debug.cpp:9-153, pipelines debug_view and rmvsm_debug): the picture of context.debug_view
+  // into context.debug_attachment, cleared to black first as the reference's clear_image does; with no mesh instance in the frame the six
+  // geometry views return the cleared image (Debug.cpp:36-49), here without a launch on an image the caller cleared.  Rules:
+  // include/oxcull.h, oxc_apply_debug_view.
+  auto apply_debug_view(DebugContext& context, Extent3D extent) -> Buffer {
+    if (prepared_frame.mesh_instance_count == 0 && context.debug_view >= OXC_DEBUG_VIEW_TRIANGLES && context.debug_view <= OXC_DEBUG_VIEW_MESH_LODS)
+      return context.debug_attachment;
+    oxc_prepared_frame f = {};
+    f.mesh_instance_count = prepared_frame.mesh_instance_count;
+    f.max_meshlet_instance_count = prepared_frame.max_meshlet_instance_count;
+    f.meshes_buffer = prepared_frame.meshes_buffer;
+    f.mesh_instances_buffer = prepared_frame.mesh_instances_buffer;
+    f.meshlet_instances_buffer = prepared_frame.meshlet_instances_buffer;
+    oxc_debug_view_context c = {};
+    c.struct_size = sizeof c;
+    c.width = extent.width;
+    c.height = extent.height;
+    c.debug_view = context.debug_view;
+    c.clear = 1;
+    c.heatmap_scale = context.overdraw_heatmap_scale;
+    c.meshlet_instance_count = static_cast<uint32_t>(prepared_frame.meshlet_instances_buffer.bytes / 8u);
+    const ShadowResolveContext& v = context.vsm;
+    c.page_size = v.page_size, c.page_table_size = v.page_table_size, c.physical_page_table_size = v.physical_page_table_size, c.clipmap_count = v.clipmap_count;
+    c.first_clipmap_width = v.first_clipmap_width, c.clipmap_selection_bias = v.clipmap_selection_bias, c.virtual_extent = v.virtual_extent;
+    for (int i = 0; i < 16; i++) c.inv_projection_view[i] = v.inv_projection_view[i];
+    c.resolution[0] = v.resolution[0], c.resolution[1] = v.resolution[1];
+    c.visbuffer_attachment = context.visbuffer_attachment;
+    c.depth_attachment = context.depth_attachment;
+    c.overdraw_attachment = context.overdraw_attachment;
+    c.albedo_attachment = context.albedo_attachment;
+    c.normal_attachment = context.normal_attachment;
+    c.emissive_attachment = context.emissive_attachment;
+    c.metallic_roughness_occlusion_attachment = context.metallic_roughness_occlusion_attachment;
+    c.ambient_occlusion_attachment = context.ambient_occlusion_attachment;
+    c.vsm_clipmaps_buffer = context.vsm_clipmaps_buffer;
+    c.virtual_page_table = context.vsm_page_table_attachment;
+    c.debug_attachment = context.debug_attachment;
+    check(oxc_apply_debug_view(ctx_, &f, &c, stream_));
+    return context.debug_attachment;
   }
   auto build_meshlet_bounds(oxc_meshlet_bounds_desc desc) -> void {
     desc.struct_size = sizeof desc;

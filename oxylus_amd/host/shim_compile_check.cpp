@@ -114,5 +114,12 @@ int main(int argc, char**) {
   } catch (const std::exception& e) {
     std::printf("expected (no attachments bound): %s\n", e.what());
   }
+  try {  // RendererInstance.cpp:1300-1323: the debug view in place of the final image
+    auto debug_context = DebugContext{.overdraw_heatmap_scale = 10.0f, .debug_view = OXC_DEBUG_VIEW_ALBEDO};
+    self.prepared_frame.mesh_instance_count = 1;
+    self.apply_debug_view(debug_context, Extent3D{.width = 16, .height = 16});
+  } catch (const std::exception& e) {
+    std::printf("expected (no attachments bound): %s\n", e.what());
+  }
   return 0;
 }

@@ -49,6 +49,10 @@ LIGHT_KIND_DIRECTIONAL, LIGHT_KIND_POINT, LIGHT_KIND_SPOT = 0, 1, 2  # GPU::Ligh
 TERRAIN_GENERATE, TERRAIN_DERIVE, TERRAIN_MINMAX, TERRAIN_ALL = 1, 2, 4, 7  # oxc_terrain_maps_context.stages
 TERRAIN_BRUSH_TRACE, TERRAIN_BRUSH_APPLY, TERRAIN_BRUSH_ALL = 1, 2, 3  # oxc_terrain_brush_context.stages
 TERRAIN_INVALID_LAYER_MATERIAL = 0xFFFFFFFF  # scene.slang:632
+# GPU::DebugView (scene.slang:10-26; RMVSM from SceneGPU.hpp:44), oxc_debug_view_context.debug_view
+(DEBUG_VIEW_TRIANGLES, DEBUG_VIEW_MESHLETS, DEBUG_VIEW_OVERDRAW, DEBUG_VIEW_MATERIALS, DEBUG_VIEW_MESH_INSTANCES, DEBUG_VIEW_MESH_LODS, DEBUG_VIEW_ALBEDO,
+ DEBUG_VIEW_NORMAL, DEBUG_VIEW_EMISSIVE, DEBUG_VIEW_METALLIC, DEBUG_VIEW_ROUGHNESS, DEBUG_VIEW_BAKED_OCCLUSION, DEBUG_VIEW_GTAO, DEBUG_VIEW_GEOMETRIC_NORMAL,
+ DEBUG_VIEW_RMVSM) = range(1, 16)
 TERRAIN_BRUSH_RAISE, TERRAIN_BRUSH_SMOOTH, TERRAIN_BRUSH_FLATTEN, TERRAIN_BRUSH_NOISE, TERRAIN_BRUSH_PAINT_LAYER = 0, 1, 2, 3, 4  # GPU::TerrainBrushMode
 
 
@@ -789,6 +793,39 @@ class TerrainDecodeContext(C.Structure):
     ]
 
 
+class DebugViewContext(C.Structure):
+    _c_name_ = "oxc_debug_view_context"
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("debug_view", C.c_uint32),
+        ("clear", C.c_uint32),
+        ("heatmap_scale", C.c_float),
+        ("meshlet_instance_count", C.c_uint32),
+        ("page_size", C.c_int32),
+        ("page_table_size", C.c_int32),
+        ("physical_page_table_size", C.c_int32),
+        ("clipmap_count", C.c_int32),
+        ("first_clipmap_width", C.c_float),
+        ("clipmap_selection_bias", C.c_float),
+        ("virtual_extent", C.c_float),
+        ("inv_projection_view", C.c_float * 16),
+        ("resolution", C.c_float * 2),
+        ("visbuffer_attachment", Buffer),
+        ("depth_attachment", Image),
+        ("overdraw_attachment", Buffer),
+        ("albedo_attachment", Buffer),
+        ("normal_attachment", Buffer),
+        ("emissive_attachment", Buffer),
+        ("metallic_roughness_occlusion_attachment", Buffer),
+        ("ambient_occlusion_attachment", Buffer),
+        ("vsm_clipmaps_buffer", Buffer),
+        ("virtual_page_table", Buffer),
+        ("debug_attachment", Buffer),
+    ]
+
+
 class MeshBuildDesc(C.Structure):
     _c_name_ = "oxc_mesh_build_desc"
     _fields_ = [("struct_size", C.c_uint32), ("vertex_count", C.c_uint32), ("index_count", C.c_uint32), ("max_lods", C.c_uint32), ("max_vertices", C.c_uint32),
@@ -857,6 +894,7 @@ PROTOTYPES = {
     "oxc_generate_terrain_maps": (_status, [_vp, _P(TerrainMapsContext), _vp]),
     "oxc_apply_terrain_brush": (_status, [_vp, _P(TerrainBrushContext), _vp]),
     "oxc_decode_terrain": (_status, [_vp, _P(TerrainDecodeContext), _vp]),
+    "oxc_apply_debug_view": (_status, [_vp, _P(PreparedFrame), _P(DebugViewContext), _vp]),
     "oxc_draw_physical_pages": (_status, [_vp, _P(PreparedFrame), _P(VsmDrawContext), _vp]),
     "oxc_debug_vsm_draw_stats": _stats,
     "oxc_resolve_shadowmap": (_status, [_vp, _P(ShadowResolveContext), _vp]),

@@ -976,6 +976,65 @@ class TerrainDecodeContext(Marshalled):
 
 
 @dataclass
+class DebugViewContext(Marshalled):
+    """oxc_debug_view_context: RendererInstance::apply_debug_view (Passes/Debug.cpp:9-153), the views of debug_view.slang and rmvsm_debug.slang.
+    Only what `debug_view` reads has to be given (include/oxcull.h, oxc_apply_debug_view); the rest may stay None.  `over` binds the images of
+    a VisbufferDecodeContext, `vsm` the shape, camera and page buffers of a ShadowResolveContext; both allocate the output when none is
+    given.  The frame's record buffers (Materials, MeshInstances, MeshLods) come from the renderer's prepared_frame."""
+    _ctype = L.DebugViewContext
+    _derived = {"width": "depth_attachment.width", "height": "depth_attachment.height"}
+    debug_view: int
+    depth_attachment: ImageAttachment                       # R32F, levels = 1
+    debug_attachment: Optional[torch.Tensor]                # int16 [H, W, 4] out: R16G16B16A16 Sfloat bits
+    visbuffer_attachment: Optional[torch.Tensor] = None     # int32 [H, W]
+    clear: bool = True
+    heatmap_scale: float = 10.0
+    meshlet_instance_count: int = 0
+    overdraw_attachment: Optional[torch.Tensor] = None      # int32 [H, W]: R32 Uint
+    albedo_attachment: Optional[torch.Tensor] = None
+    normal_attachment: Optional[torch.Tensor] = None
+    emissive_attachment: Optional[torch.Tensor] = None
+    metallic_roughness_occlusion_attachment: Optional[torch.Tensor] = None
+    ambient_occlusion_attachment: Optional[torch.Tensor] = None  # int16 [H, W]: binary16 bits
+    vsm_clipmaps_buffer: Optional[torch.Tensor] = None
+    virtual_page_table: Optional[torch.Tensor] = None
+    inv_projection_view: tuple = (0.0,) * 16
+    resolution: tuple = (0.0, 0.0)
+    page_size: int = 0
+    page_table_size: int = 0
+    physical_page_table_size: int = 0
+    clipmap_count: int = 0
+    first_clipmap_width: float = 0.0
+    clipmap_selection_bias: float = 0.0
+    virtual_extent: float = 0.0
+
+    @staticmethod
+    def _output(d: ImageAttachment) -> torch.Tensor:
+        return torch.zeros((d.height, d.width, 4), dtype=torch.int16, device=d.data.device)
+
+    @staticmethod
+    def over(debug_view: int, decode: "VisbufferDecodeContext", ambient_occlusion: Optional[torch.Tensor] = None, overdraw: Optional[torch.Tensor] = None,
+             debug_attachment: Optional[torch.Tensor] = None, **settings) -> "DebugViewContext":
+        d = decode.depth_attachment
+        return DebugViewContext(int(debug_view), d, DebugViewContext._output(d) if debug_attachment is None else debug_attachment,
+                                visbuffer_attachment=decode.visbuffer_attachment, meshlet_instance_count=decode.meshlet_instance_count,
+                                overdraw_attachment=overdraw, albedo_attachment=decode.albedo_attachment, normal_attachment=decode.normal_attachment,
+                                emissive_attachment=decode.emissive_attachment,
+                                metallic_roughness_occlusion_attachment=decode.metallic_roughness_occlusion_attachment,
+                                ambient_occlusion_attachment=ambient_occlusion, **settings)
+
+    @staticmethod
+    def vsm(resolve: "ShadowResolveContext", debug_attachment: Optional[torch.Tensor] = None) -> "DebugViewContext":
+        d = resolve.depth_attachment
+        return DebugViewContext(L.DEBUG_VIEW_RMVSM, d, DebugViewContext._output(d) if debug_attachment is None else debug_attachment,
+                                vsm_clipmaps_buffer=resolve.vsm_clipmaps_buffer, virtual_page_table=resolve.virtual_page_table,
+                                inv_projection_view=tuple(resolve.inv_projection_view), resolution=tuple(resolve.resolution), page_size=resolve.page_size,
+                                page_table_size=resolve.page_table_size, physical_page_table_size=resolve.physical_page_table_size,
+                                clipmap_count=resolve.clipmap_count, first_clipmap_width=resolve.first_clipmap_width,
+                                clipmap_selection_bias=resolve.clipmap_selection_bias, virtual_extent=resolve.virtual_extent)
+
+
+@dataclass
 class VisbufferDecodeContext(Marshalled):
     """oxc_decode_context: RendererInstance::decode_visbuffer (Passes/DrawGeometry.cpp:192-274), the geometry and material-factor half of
     visbuffer_decode.slang.  `create` takes the visbuffer and the depth as oxc_draw_visbuffer resolved them, the matrix they were drawn with and
@@ -1071,13 +1130,14 @@ class RendererInstance:
     def reserve(self, max_mesh_instances: int, max_meshlet_instances: int):
         self._check(self._lib.oxc_reserve(self._ctx, max_mesh_instances, max_meshlet_instances))
 
-    def _call(self, symbol: str, context, stream, *, frame: bool = False, c=None):
-        """One pass over its context: oxc_<pass>(ctx, [prepared frame,] context, stream).  The context stays referenced in `_keep`, so its
-        tensors outlive the launches the call enqueued."""
+    def _call(self, symbol: str, context, stream, *, frame=False, c=None):
+        """One pass over its context: oxc_<pass>(ctx, [prepared frame,] context, stream).  `frame`: True passes the prepared frame, which
+        must exist; "optional" passes it when there is one and NULL otherwise.  The context stays referenced in `_keep`, so its tensors
+        outlive the launches the call enqueued."""
         args = [self._ctx]
         if frame:
-            assert self.prepared_frame is not None
-            args.append(C.byref(self.prepared_frame.c()))
+            assert frame == "optional" or self.prepared_frame is not None
+            args.append(C.byref(self.prepared_frame.c()) if self.prepared_frame is not None else None)
         args.append(C.byref(context.c() if c is None else c))
         self._keep = context
         self._check(getattr(self._lib, symbol)(*args, self._stream(stream)))
@@ -1314,6 +1374,12 @@ class RendererInstance:
         """Passes/Terrain.cpp:279-360 (terrain_decode): the four G-buffer images at the terrain pixels, one launch (include/oxcull.h,
         oxc_decode_terrain).  After decode_visbuffer on the same attachments; every other pixel keeps its bytes."""
         self._call("oxc_decode_terrain", context, stream)
+
+    def apply_debug_view(self, context: DebugViewContext, stream=None) -> None:
+        """Passes/Debug.cpp:9-153 (debug_view, rmvsm_debug): the picture of `context.debug_view` into `context.debug_attachment`, one launch
+        (include/oxcull.h, oxc_apply_debug_view).  The prepared frame is passed when there is one; only the Materials, MeshInstances and
+        MeshLods views read it."""
+        self._call("oxc_apply_debug_view", context, stream, frame="optional")
 
     def generate_terrain_maps(self, context: TerrainMapsContext, stream=None) -> None:
         """Scene/Terrain.cpp:406-461 and Passes/Terrain.cpp:134-156 (terrain_generate, terrain_derive, terrain_minmax): the stages of

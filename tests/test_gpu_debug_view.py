@@ -1,0 +1,513 @@
+"""oxc_apply_debug_view on the GPU against tests/debug_view_model.py: every word of the debug attachment equal to the checker's between
+poisoned guard bands (debug_view_frames.run / run_vsm), on the drawn 192 x 192 frame, at the tile-apron extents, on hand-made frames, in a
+captured graph, and at every limit."""
+import ctypes as C
+import dataclasses
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import debug_view_frames as DF
+import debug_view_model as DV
+from gpu_passes import DrawnFrame, Guard, same
+
+pytestmark = pytest.mark.gpu
+rep = dataclasses.replace
+NAN, INF = float("nan"), float("inf")
+ids = lambda v: DV.NAMES[v]  # noqa: E731
+
+
+@pytest.fixture(scope="module")
+def r(renderer):
+    return renderer
+
+
+@pytest.fixture(scope="module")
+def drawn(r):
+    d = DrawnFrame(r)
+    d.passes()
+    torch.cuda.synchronize()
+    return d
+
+
+def drawn_inputs(d, overdraw) -> dict:
+    u = lambda t, view: np.ascontiguousarray(t.cpu().numpy()).view(view)  # noqa: E731
+    c, cpu = d.dctx, d.cpu
+    return dict(heatmap_scale=10.0, meshlet_instance_count=c.meshlet_instance_count, overdraw=u(overdraw, np.uint32), albedo=u(c.albedo_attachment, np.uint32),
+                normal=u(c.normal_attachment, np.uint16), emissive=u(c.emissive_attachment, np.uint32), mr_occlusion=u(c.metallic_roughness_occlusion_attachment, np.uint32),
+                ao=u(d.actx.ambient_occlusion_attachment, np.uint16), meshlet_instances=cpu.meshlet_instances.numpy(), mesh_instances=cpu.mesh_instances.numpy(),
+                meshes=cpu.meshes.numpy())
+
+
+def checker_arguments(view, inputs) -> dict:
+    names = {DV.OVERDRAW: ("heatmap_scale", "overdraw"), **{v: ("meshlet_instance_count", "meshlet_instances", "mesh_instances", "meshes") for v in DV.RECORD_VIEWS}}
+    names = names.get(view, (DF.READS[view],) if view in DF.READS else ())
+    return {k: inputs[k] for k in names}
+
+
+# ---- the drawn frame ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("view", DV.MAIN_VIEWS, ids=ids)
+def test_drawn_frame(r, drawn, view):
+    """The drawn, decoded and occluded 192 x 192 frame of gpu_passes under every main view."""
+    from oxylus_amd.renderer import DebugViewContext
+
+    d = drawn
+    W, H = d.W, d.H
+    overdraw = torch.from_numpy(np.random.default_rng(7).integers(0, 24, (H, W)).astype(np.int32)).cuda()
+    out = Guard("debug", (H, W, 4), torch.int16, W * 4, DF.POISON16, 8, fill=DF.FILL16)
+    r.prepared_frame = d.frame
+    c = DebugViewContext.over(view, d.dctx, ambient_occlusion=d.actx.ambient_occlusion_attachment, overdraw=overdraw, debug_attachment=out.tensor, heatmap_scale=10.0)
+    r.apply_debug_view(c)
+    torch.cuda.synchronize()
+    st = {}
+    want = DV.debug_view(view, d.vis.cpu().numpy(), d.f.depth.cpu().numpy(), clear=True, stats=st, **checker_arguments(view, drawn_inputs(d, overdraw)))
+    out.check(DV.NAMES[view], want)
+    got = out.bits()[1].reshape(H, W, 4)
+    same(got, want, DV.NAMES[view])
+    assert st["covered"].sum() > 1000
+    if view in DV.ID_VIEWS:
+        colours = np.unique(got[st["covered"]][:, :3], axis=0)
+        assert len(colours) >= 3, f"{len(colours)} distinct colours"
+        assert (st["outline"][st["covered"]] > 0).any()
+
+
+# ---- the tile-apron extents -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("extent", DF.EXTENTS, ids=lambda e: f"{e[0]}x{e[1]}")
+def test_extents(r, extent):
+    """One pixel, below one tile, exactly one tile, one past a tile on each axis, several tiles; with `clear` on and off."""
+    f = DF.frame(extent)
+    for view in DV.MAIN_VIEWS:
+        for clear in (True, False):
+            DF.run(r, f, view, f"{extent} {DV.NAMES[view]} clear={clear}", clear=clear)
+
+
+# ---- hand-made 17 x 9 frames ----------------------------------------------------------------------------------------------------------------
+def covered_frame(extent=(17, 9)) -> DF.Frame:
+    f = DF.frame(extent)
+    vis = np.where(f.vis == DV.EMPTY, np.uint32(0x00000305), f.vis).astype(np.uint32)
+    return rep(f, vis=vis)
+
+
+def run_views(r, f, label, views=(DV.TRIANGLES, DV.MESH_LODS, DV.OVERDRAW, DV.NORMAL), **kw):
+    out = {}
+    for view in views:
+        st = {}
+        out[view] = (DF.run(r, f, view, f"{label}: {DV.NAMES[view]}", stats=st, **kw), st)
+    return out
+
+
+def test_outline_taps_outside_the_image(r):
+    """Every pixel covered: at the four corners five taps lie outside, along the four edges three."""
+    f = covered_frame()
+    _, st = run_views(r, f, "all covered")[DV.TRIANGLES]
+    ol = st["outline"]
+    assert st["covered"].all() and all(ol[y, x] > 1 for y in (0, -1) for x in (0, -1)) and (ol[0, 1:-1] > 1).all() and (ol[1:-1, 0] > 1).all()
+
+
+def test_empty_neighbours_and_empty_centres(r):
+    f = covered_frame()
+    ring = f.vis.copy()
+    ring[3:6, 4:7] = DV.EMPTY
+    ring[4, 5] = 0x00000711            # a covered pixel whose eight neighbours are ~0u: no tap but its own, weight 0
+    ring[1, 11] = DV.EMPTY             # a ~0u pixel inside covered ones: its neighbours lose one tap each
+    res = run_views(r, rep(f, vis=ring), "holes")
+    assert res[DV.TRIANGLES][1]["outline"][4, 5] == 0 and res[DV.TRIANGLES][1]["outline"][1, 10] > 1
+
+
+def test_depth_number_classes(r):
+    """0, -1, -2, NaN, +-Inf and a denormal: s is 0, -Inf, -Inf, -Inf, +Inf / -Inf and 0; 0 * Inf in a neighbour's sum is a NaN."""
+    f = covered_frame()
+    depth = f.depth.copy()
+    specials = np.array([0.0, -1.0, -2.0, NAN, INF, -INF, 1e-40, -0.0], np.float32)
+    for k, v in enumerate(specials):
+        depth[1 + 3 * (k // 4), 2 + 4 * (k % 4)] = v
+    res = run_views(r, rep(f, depth=depth), "special depths")
+    assert np.isnan(res[DV.TRIANGLES][1]["outline"]).any()
+    run_views(r, rep(f, depth=np.full_like(depth, NAN)), "all NaN")
+    run_views(r, rep(f, depth=np.full_like(depth, INF)), "all Inf")
+
+
+def unit_step_depths():
+    """Two depths whose densities differ by exactly 0.5: with the weight 2 of the middle row the outline beside a single such texel is
+    exactly 1.0.  Found among the binary32 values above 0.25 and above 0.29."""
+    def walk(first, count):
+        d = (np.arange(0, 4 * count, 4, dtype=np.int64) + int(np.float32(first).view(np.uint32))).astype(np.uint32).view(np.float32)
+        return d, DV.density(np.zeros(d.shape, np.uint32), d)
+
+    (low, s_low), (high, s_high) = walk(0.25, 100000), walk(0.29, 1000000)
+    common, i, j = np.intersect1d((s_low + np.float32(0.5)).astype(np.float32), s_high, return_indices=True)
+    assert common.size, "no pair of binary32 depths with densities exactly 0.5 apart"
+    return low[i[0]], high[j[0]]
+
+
+def test_outline_exactly_one_and_beyond(r):
+    base, other = unit_step_depths()
+    f = covered_frame()
+    depth = np.full_like(f.depth, base)
+    depth[4, 8] = other                      # its left and right neighbours: outline exactly 1.0
+    depth[6, 3] = np.float32(0.9)            # far beyond 1.0
+    res = run_views(r, rep(f, depth=depth), "unit step")
+    ol = res[DV.TRIANGLES][1]["outline"]
+    assert ol[4, 7] == 1.0 and ol[4, 9] == 1.0 and ol[6, 2] > 1.0 and ol[2, 2] == 0.0
+    got = res[DV.TRIANGLES][0]
+    assert (got[4, 7, :3] == 0).all() and (got[2, 2, :3] != 0).any()
+
+
+def test_texels_beyond_the_meshlet_instance_count(r):
+    """Terrain texels, an index equal to the count and one far beyond it under views 1 - 6; the guard bands poison what lies beyond the
+    frame's records, and the record views colour such a texel as hash(0) / hue 0."""
+    f = covered_frame()
+    vis = f.vis.copy()
+    vis[2, 3:9] = DF.TERRAIN_TEXEL | 0x11
+    vis[5, 2:6] = (f.meshlet_instance_count << 8) | 0x07
+    vis[7, 10:15] = 0x7FFFFF00
+    f = rep(f, vis=vis)
+    res = run_views(r, f, "beyond the count", views=tuple(range(DV.TRIANGLES, DV.MESH_LODS + 1)))
+    zero = DF.want(rep(f, depth=np.full_like(f.depth, 0.5)), DV.MATERIALS)[2, 5]
+    assert (zero[:3] == DV.channel_half(np.stack(DV.hash_colour([0]), axis=-1))[0]).all()
+    run_views(r, f, "beyond the count, the rest poisoned", views=tuple(range(DV.TRIANGLES, DV.MESH_LODS + 1)), poisoned_rest=True)
+    run_views(r, rep(f, meshlet_instance_count=0), "count 0", views=DV.RECORD_VIEWS)
+    assert res
+
+
+def test_lod_count_wraps(r):
+    f = covered_frame()
+    meshes = f.meshes.copy()
+    meshes[0, 7] = 0xFFFFFFFF   # lod_count + 1 == 0: 0 / 0 for lod_index 0, x / 0 beyond
+    mi = f.mesh_instances.copy()
+    mi[0, 1], mi[3, 1] = 0, 5
+    assert mi[0, 0] == 0 and mi[3, 0] == 0
+    run_views(r, rep(f, meshes=meshes, mesh_instances=mi), "lod_count 0xFFFFFFFF", views=(DV.MESH_LODS,))
+    huge = f.mesh_instances.copy()
+    huge[:, 1] = (0xFFFFFFFF, 0x80000000, 1 << 24, (1 << 24) + 1, 7)
+    run_views(r, rep(f, mesh_instances=huge), "huge lod_index", views=(DV.MESH_LODS,))
+
+
+@pytest.mark.parametrize("scale", [-1.0, 0.0, 50.0, 100.0, 1e9, NAN, INF])
+def test_overdraw_counts_and_scales(r, scale):
+    f = covered_frame()
+    counts = np.array([0, 1, 100, (1 << 24) + 1, 0xFFFFFFFF, 7, 31, 1000], np.uint32)
+    overdraw = counts[(np.arange(f.overdraw.size) % counts.size)].reshape(f.overdraw.shape)
+    DF.run(r, rep(f, overdraw=overdraw, depth=np.full_like(f.depth, 0.5), heatmap_scale=scale), DV.OVERDRAW, f"scale {scale}")
+
+
+def test_gbuffer_number_classes(r):
+    """Every UF11 / UF10 class (zero, denormal, normal, the largest, Inf, NaN) and every binary16 class in the views that decode them."""
+    f = covered_frame()
+    n = f.emissive.size
+    uf = np.array([0x000, 0x001, 0x03F, 0x040, 0x3C0, 0x7BF, 0x7C0, 0x7C1, 0x7FF], np.uint32)
+    uf10 = np.array([0x000, 0x001, 0x01F, 0x020, 0x1E0, 0x3DF, 0x3E0, 0x3E1, 0x3FF], np.uint32)
+    k = np.arange(n)
+    emissive = (uf[k % 9] | (uf[(k // 9) % 9] << np.uint32(11)) | (uf10[(k // 3) % 9] << np.uint32(22))).astype(np.uint32).reshape(f.emissive.shape)
+    halves = np.array([0x0000, 0x8000, 0x0001, 0x83FF, 0x0400, 0x3800, 0x3C00, 0xBC00, 0x7BFF, 0x7C00, 0xFC00, 0x7E00, 0x7C01, 0xFFFF, 0x3555, 0xB555], np.uint16)
+    normal = halves[(np.arange(n * 4) * 5 + np.arange(n * 4) // 16) % 16].reshape(f.normal.shape)
+    ao = halves[k % 16].reshape(f.ao.shape)
+    bytes_ = np.array([0x00, 0x01, 0x0A, 0x0B, 0x7F, 0x80, 0xFE, 0xFF], np.uint32)
+    words = (bytes_[k % 8] | (bytes_[(k // 8) % 8] << np.uint32(8)) | (bytes_[(k // 2) % 8] << np.uint32(16)) | np.uint32(0xAB000000)).astype(np.uint32).reshape(f.albedo.shape)
+    g = rep(f, emissive=emissive, normal=normal, ao=ao, albedo=words, mr_occlusion=words, depth=np.full_like(f.depth, 0.5))
+    run_views(r, g, "number classes", views=tuple(range(DV.ALBEDO, DV.GEOMETRIC_NORMAL + 1)))
+
+
+@pytest.mark.parametrize("view", DV.MAIN_VIEWS, ids=ids)
+def test_unread_inputs_null_and_poisoned(r, view):
+    """Null (run's default: only what the view reads is bound, the frame is NULL unless the view reads records) and bound but poisoned."""
+    f = DF.golden_frame()
+    got = DF.run(r, f, view, "null")
+    same(DF.run(r, f, view, "poisoned", poisoned_rest=True), got, "poisoned == null")
+    same(got, np.load(DF.GOLDEN)["out_" + DV.NAMES[view]], "the golden fixture")
+
+
+# ---- RMVSM ----------------------------------------------------------------------------------------------------------------------------------
+def test_rmvsm_on_the_shadow_frame(r, drawn):
+    """The end-to-end shadow frame the resolve test uses (update -> shadow cull -> shadow draw), as the drawn frame built it."""
+    from oxylus_amd.renderer import DebugViewContext
+
+    f = drawn.f
+    out = Guard("debug", (f.H, f.W, 4), torch.int16, f.W * 4, DF.POISON16, 8, fill=DF.FILL16)
+    r.prepared_frame = None
+    table = f.vctx.virtual_page_table & f.keep  # a third of the entries lose their Backed bit, as pages evicted since the draw
+    r.apply_debug_view(rep(DebugViewContext.vsm(f.rctx, debug_attachment=out.tensor), virtual_page_table=table))
+    torch.cuda.synchronize()
+    st = {}
+    want = DV.rmvsm(f.rctx.depth_attachment.data.view(f.H, f.W).cpu().numpy(), table.cpu().numpy(), f.clip.numpy(), f.inv, (f.W, f.H),
+                    first_clipmap_width=f.fcw, bias=f.vctx.clipmap_selection_bias, virtual_extent=f.vctx.virtual_extent, stats=st, **f.shape)
+    out.check("shadow frame", want)
+    same(out.bits()[1].reshape(f.H, f.W, 4), want, "shadow frame")
+    classes = set(int(c) for c in np.unique(st["classes"]))
+    print("classes on the shadow frame:", sorted(classes))
+    pages = classes - {DV.SKY, DV.BORDER}
+    assert DV.BORDER in classes and all(any(c & bit for c in pages) for bit in (DV.PAGE_BACKED, DV.PAGE_DIRTY, DV.PAGE_VISIBLE, DV.NOT_BACKED_VISIBLE)), classes
+
+
+@pytest.mark.parametrize("name,kw", [("small shape", {}), ("33x19", dict(extent=(33, 19))), ("a NaN clipmap", dict(nan_clipmap=1)),
+                                     ("page 64, table 16", dict(extent=(33, 19), shape=DF.SECOND)), ("1x1", dict(extent=(1, 1))),
+                                     ("129x65", dict(extent=(129, 65), shape=DF.SECOND))])
+def test_rmvsm_hand_made(r, name, kw):
+    f = DF.vsm_frame(**kw)
+    st = {}
+    DF.run_vsm(r, f, name, st)
+    if "nan_clipmap" in kw:
+        assert ((st["clipmap"] == kw["nan_clipmap"]) & st["nan_uv"]).sum() >= 8, "no pixel selects the zeroed clipmap"
+    if name in ("small shape", "page 64, table 16"):
+        classes, ps = set(int(c) for c in np.unique(st["classes"])), f.shape["page_size"]
+        assert {DV.SKY, DV.BORDER, DV.PAGE_VISIBLE | DV.NOT_BACKED_VISIBLE} <= classes and any(c & DV.PAGE_DIRTY for c in classes - {DV.BORDER}), classes
+        assert any(c & DV.PAGE_BACKED for c in classes - {DV.SKY, DV.BORDER})
+        if name == "small shape":
+            assert {0, 1, 2, ps - 2, ps - 1} <= set(int(v) for v in np.unique(st["in_page"]))
+
+
+def test_rmvsm_clip_uv_at_zero_at_one_and_outside(r):
+    """Two pixels a row, ndc.x = -0.5 and 0.5; four rows, ndc.y = -0.75 .. 0.75.  Depth 0.5 in the two middle rows puts them at world x = -1
+    and 1, clip_uv.x exactly 0 and 1 under clipmaps 2 wide; depth 0.25 in the first row puts it at x = -2 and 2, outside; the last is sky."""
+    depth = np.array([[0.25, 0.25], [0.5, 0.5], [0.5, 0.5], [0.0, 0.0]], np.float32)
+    f = DF.vsm_frame((2, 4), widths=(2.0, 2.0, 2.0, 2.0), depth=depth)
+    st = {}
+    DF.run_vsm(r, f, "uv 0, 1, outside", st)
+    ps = f.shape["page_size"]
+    assert (st["in_page"][1:3, :, 0] == 0).all() and (st["in_page"][0] == ps - 1).all() and (st["classes"][3] == DV.SKY).all()
+    assert (st["classes"][:3] == DV.BORDER).all()
+
+
+# ---- captured graph -------------------------------------------------------------------------------------------------------------------------
+def test_draw_decode_ao_debug_view_in_one_graph(r, drawn):
+    """Draw -> decode -> ambient occlusion -> the GTAO, Overdraw and MeshLods views in one captured graph, replayed three times; between
+    the replays the overdraw image is rewritten and the outputs are poisoned."""
+    from oxylus_amd.renderer import DebugViewContext
+
+    d = drawn
+    W, H = d.W, d.H
+    rng = np.random.default_rng(11)
+    overdraw = torch.zeros((H, W), dtype=torch.int32, device="cuda")
+    views = (DV.GTAO, DV.OVERDRAW, DV.MESH_LODS)
+    outs = {v: Guard("debug", (H, W, 4), torch.int16, W * 4, DF.POISON16, 8, fill=DF.FILL16) for v in views}
+    ctxs = {v: DebugViewContext.over(v, d.dctx, ambient_occlusion=d.actx.ambient_occlusion_attachment, overdraw=overdraw, debug_attachment=outs[v].tensor,
+                                     heatmap_scale=25.0) for v in views}
+
+    def chain(stream=None):
+        r.prepared_frame = d.frame
+        r.draw_visbuffer(d.main, d.pv, W, H, d.visdepth, clear=True, depth=d.depth_image, visbuffer=d.vis, stream=stream)
+        r.decode_visbuffer(d.dctx, stream=stream)
+        r.generate_ambient_occlusion(d.actx, stream=stream)
+        for v in views:
+            r.apply_debug_view(ctxs[v], stream=stream)
+
+    chain()
+    torch.cuda.synchronize()
+    stream = torch.cuda.Stream()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=stream):
+        chain(stream)
+    vis, depth = d.vis.cpu().numpy(), d.f.depth.cpu().numpy()
+    for replay in range(3):
+        overdraw.copy_(torch.from_numpy(rng.integers(0, 8 << replay, (H, W)).astype(np.int32)))
+        for g in outs.values():
+            g.refill()
+        graph.replay()
+        torch.cuda.synchronize()
+        inputs = {**drawn_inputs(d, overdraw), "heatmap_scale": 25.0}
+        for v in views:
+            want = DV.debug_view(v, vis, depth, clear=True, **checker_arguments(v, inputs))
+            outs[v].check(f"replay {replay}", want)
+            same(outs[v].bits()[1].reshape(H, W, 4), want, f"replay {replay}: {DV.NAMES[v]}")
+
+
+# ---- limits ---------------------------------------------------------------------------------------------------------------------------------
+def _frame_with(frame, **fields):
+    """`frame` with some of the three record buffers replaced: meshlet_instances_buffer is its own, the other two are the scene's."""
+    scene = types.SimpleNamespace(**vars(frame.scene))
+    own = {k: fields.pop(k) for k in list(fields) if k == "meshlet_instances_buffer"}
+    for k, v in fields.items():
+        setattr(scene, k, v)
+    return rep(frame, scene=scene, **own)
+
+
+def _attempt(r, base, frame, changes):
+    """One call of the C entry point with `changes` applied to the context `base` and the prepared frame `frame`: a plain key replaces a
+    field of the context, "frame" the whole prepared frame, "frame:<name>" one of its record buffers, "raw:<name>" a field of the filled C
+    structure (what the dataclass derives and cannot be told: struct_size, width, height).  Returns (status, oxc_last_error)."""
+    c = rep(base, **{k: v for k, v in changes.items() if ":" not in k and k != "frame"}).c()
+    for k, v in changes.items():
+        if k.startswith("raw:"):
+            setattr(c, k[4:], v)
+    frame = changes.get("frame", frame)
+    records = {k[6:]: v for k, v in changes.items() if k.startswith("frame:")}
+    if frame is not None and records:
+        frame = _frame_with(frame, **records)
+    fc = frame.c() if frame is not None else None
+    status = r._lib.oxc_apply_debug_view(r._ctx, C.byref(fc) if fc is not None else None, C.byref(c), r._stream(None))
+    return status, r._lib.oxc_last_error(r._ctx).decode()
+
+
+def _refused(r, base, changes, message, label, frame=None):
+    """OXC_INVALID_ARG with `message` right behind the entry point's name: the message of that rule and of no other."""
+    from oxylus_amd import lib as L
+
+    status, error = _attempt(r, base, frame, changes)
+    assert status == L.OXC_INVALID_ARG and f"apply_debug_view: {message}" in error, f"{label}: status {status}, {error!r}, expected {message!r}"
+
+
+def _alone_and_in_pairs(r, cases, base, frame, unwritten):
+    """Every case alone, then every two cases that change different things: the message is that of the case earlier in the documented
+    order.  `unwritten(label)` asserts that the output holds its pre-fill and every band its poison; what a call wrote would stay, so it
+    is asked after every single case and after each case's pairs."""
+    for name, change, message in cases:
+        _refused(r, base, change, message, name, frame)
+        torch.cuda.synchronize()
+        unwritten(name)
+    for i, (name, first, message) in enumerate(cases):
+        for other, second, _ in cases[i + 1:]:
+            if not set(first) & set(second):
+                _refused(r, base, {**first, **second}, message, f"{name} + {other}", frame)
+        torch.cuda.synchronize()
+        unwritten(f"{name} and a later one")
+
+
+def _null_image(W, H):
+    """A one-level image descriptor of W x H with no memory behind it."""
+    from oxylus_amd import lib as L
+
+    im = L.Image()
+    im.width, im.height, im.levels = W, H, 1
+    return types.SimpleNamespace(width=W, height=H, c=lambda: im)
+
+
+def _later(x, unit):
+    """The tensor's bytes from `unit`'s size onwards: a start that is aligned to `unit` and to nothing larger."""
+    return x.view(-1).view(unit)[1:]
+
+
+def _buffer_cases(field, tensor, texel, smaller=None, name=None):
+    """Null, then unaligned (half a texel later), then one element short: the three rules of one buffer, in the header's order.  `name` is
+    what the messages call the buffer where that is not the key."""
+    name = name or field
+    unit = {2: torch.int8, 4: torch.int16, 8: torch.int32}[texel]
+    cases = [(f"{name} null", {field: None}, f"{name} must not be null"),
+             (f"{name} unaligned", {field: _later(tensor, unit)}, f"{name} must be aligned to its texel")]
+    if smaller:
+        cases.append((f"{name} small", {field: tensor.view(-1)[:-1]}, name + smaller))
+    return cases
+
+
+def _shared_first_cases(W, H, depth):
+    """The rules in front of the buffers, as every view has them: struct_size, debug_view, the extent, the depth image."""
+    from oxylus_amd import lib as L
+    from oxylus_amd.renderer import ImageAttachment
+
+    one_level = "depth_attachment must be one R32F level at offset 0"
+    return [("struct_size", {"raw:struct_size": C.sizeof(L.DebugViewContext) - 8}, "bad context / struct_size"),
+            ("view 0", dict(debug_view=0), "debug_view must be"), ("view 16", dict(debug_view=16), "debug_view must be"),
+            ("height 0", {"raw:height": 0}, "the extent must not be zero"), ("width 0", {"raw:width": 0}, "the extent must not be zero"),
+            ("width differs", {"raw:width": W + 1}, "depth_attachment extent differs"), ("height differs", {"raw:height": H - 1 or 2}, "depth_attachment extent differs"),
+            ("65537 wide", dict(depth_attachment=ImageAttachment(depth.view(-1), 65537, H, 1, [0])), "depth extent beyond 65536"),
+            ("65537 tall", dict(depth_attachment=ImageAttachment(depth.view(-1), W, 65537, 1, [0])), "depth extent beyond 65536"),
+            ("depth null", dict(depth_attachment=_null_image(W, H)), one_level),
+            ("two levels", dict(depth_attachment=ImageAttachment(depth.view(-1), W, H, 2, [0, 0])), one_level),
+            ("level offset", dict(depth_attachment=ImageAttachment(depth.view(-1), W, H, 1, [4])), one_level)]
+
+
+def _limit_cases(f, gs, view):
+    """(name, changes, the message of the rule) in the header's order, for what `view` reads.  The overlap cases leave the guarded output
+    where it is and put an input's descriptor over its bytes, so that `nothing written` is asserted for them as for the rest."""
+    from oxylus_amd.renderer import ImageAttachment
+
+    W, H = f.extent
+    t = lambda name: gs[name].tensor  # noqa: E731
+    small = " is smaller than its extent"
+    debug = t("debug")
+    words = debug.view(-1).view(torch.int32)   # the output's bytes as 2 * W * H words
+    over = lambda what: f"debug_attachment must not overlap {what}"  # noqa: E731
+    cases = _shared_first_cases(W, H, t("depth"))
+    if view in DV.RECORD_VIEWS:
+        cases.append(("frame null", {"frame": None}, "the frame must not be null"))
+    cases += _buffer_cases("visbuffer_attachment", t("vis"), 4, small)
+    cases.append(("depth unaligned", dict(depth_attachment=ImageAttachment(_later(t("depth"), torch.int16), W, H, 1, [0])), "depth_attachment must be aligned to its texel"))
+    overlaps = [("over the visbuffer", dict(visbuffer_attachment=words[:W * H]), over("visbuffer_attachment")),
+                ("over the depth", dict(depth_attachment=ImageAttachment(words[-W * H:].view(torch.float32), W, H, 1, [0])), over("depth_attachment"))]
+    if view in DF.READS:
+        name = DF.READS[view]
+        field = {"mr_occlusion": "metallic_roughness_occlusion_attachment", "ao": "ambient_occlusion_attachment"}.get(name, name + "_attachment")
+        texel = {"ao": 2, "normal": 8}.get(name, 4)
+        cases += _buffer_cases(field, t(name), texel, small)
+        overlaps.append((f"over {field}", {field: debug.view(-1).view(t(name).dtype)[-t(name).numel():]}, over(field)))
+    if view in DV.RECORD_VIEWS:
+        cases += _buffer_cases("frame:meshlet_instances_buffer", t("meshlet_instances"), 4, " is smaller than meshlet_instance_count records", "meshlet_instances_buffer")
+        cases += _buffer_cases("frame:mesh_instances", t("mesh_instances"), 4, name="mesh_instances_buffer")
+        cases += _buffer_cases("frame:meshes", t("meshes"), 8, name="meshes_buffer")
+        overlaps += [("over the meshlet instances", {"frame:meshlet_instances_buffer": words[:2 * f.meshlet_instance_count].view(-1, 2)}, over("meshlet_instances_buffer")),
+                     ("over the mesh instances", {"frame:mesh_instances": words[-f.mesh_instances.size:]}, over("mesh_instances_buffer")),
+                     ("over the meshes", {"frame:meshes": words[:f.meshes.size]}, over("meshes_buffer"))]
+    cases += _buffer_cases("debug_attachment", debug, 8, small)
+    return cases + overlaps
+
+
+@pytest.mark.parametrize("view", [DV.TRIANGLES, DV.OVERDRAW, DV.MESH_LODS, DV.ALBEDO, DV.NORMAL, DV.EMISSIVE, DV.METALLIC, DV.GTAO], ids=ids)
+def test_limits_alone_and_in_pairs(r, view):
+    f = DF.golden_frame()
+    gs = DF.guards(f, view)
+    frame = DF.prepared_frame(gs, f) if view in DV.RECORD_VIEWS else None
+    base = DF.context(f, gs, view)
+    _alone_and_in_pairs(r, _limit_cases(f, gs, view), base, frame, lambda label: DF.check_unwritten(gs, f, label))
+    r.prepared_frame = frame
+    # and the frame accepted after all: the same context runs
+    r.apply_debug_view(base)
+    torch.cuda.synchronize()
+    same(DF.got_of(gs, f), DF.want(f, view), "accepted after the refusals")
+
+
+def test_rmvsm_limits(r):
+    from oxylus_amd.renderer import ImageAttachment
+
+    f = DF.vsm_frame()
+    gs = DF.vsm_guards(f)
+    base = DF.vsm_context(f, gs)
+    W, H = f.extent
+    t = lambda name: gs[name].tensor  # noqa: E731
+    words = t("debug").view(-1).view(torch.int32)   # the output's bytes as 2 * W * H words
+    pages = "page_size must be a multiple of 16 and divide physical_page_table_size"
+    cases = _shared_first_cases(W, H, t("depth"))
+    cases += [("no clipmap", dict(clipmap_count=0), "clipmap_count must be 1..16"), ("17 clipmaps", dict(clipmap_count=17), "clipmap_count must be 1..16"),
+              ("table of 12", dict(page_table_size=12), "page_table_size must be a multiple of 8 in [8, 256]"), ("page of 24", dict(page_size=24), pages),
+              ("physical 72", dict(physical_page_table_size=72), pages),
+              ("257 x 257 pages", dict(physical_page_table_size=257 * f.shape["page_size"]), "more than 65536 physical pages"),
+              ("depth unaligned", dict(depth_attachment=ImageAttachment(_later(t("depth"), torch.int16), W, H, 1, [0])), "depth_attachment must be aligned to its texel")]
+    cases += _buffer_cases("vsm_clipmaps_buffer", t("clipmaps"), 4, " is smaller than clipmap_count records")
+    cases += _buffer_cases("virtual_page_table", t("table"), 4, " is smaller than clipmap_count * n * n u32")
+    cases += _buffer_cases("debug_attachment", t("debug"), 8, " is smaller than its extent")
+    over = lambda what: f"debug_attachment must not overlap {what}"  # noqa: E731
+    cases += [("over the depth", dict(depth_attachment=ImageAttachment(words[-W * H:].view(torch.float32), W, H, 1, [0])), over("depth_attachment")),
+              ("over the clipmaps", dict(vsm_clipmaps_buffer=words[:t("clipmaps").numel()]), over("vsm_clipmaps_buffer")),
+              ("over the table", dict(virtual_page_table=words[-t("table").numel():]), over("virtual_page_table"))]
+
+    def unwritten(label):
+        for g in gs.values():
+            g.check(label)
+        assert (gs["debug"].bits()[1] == DF.FILL16).all(), f"{label}: written after a refusal"
+
+    _alone_and_in_pairs(r, cases, base, None, unwritten)
+    r.prepared_frame = None
+    # the inputs of the main views are not looked at: null and fine
+    r.apply_debug_view(base)
+    torch.cuda.synchronize()
+    same(gs["debug"].bits()[1].reshape(f.depth.shape + (4,)), DF.vsm_want(f), "accepted after the refusals")
+
+
+def test_struct_size_and_null_context(r):
+    from oxylus_amd import lib as L
+
+    f = DF.golden_frame()
+    gs = DF.guards(f, DV.TRIANGLES)
+    lib = r._lib
+    c = DF.context(f, gs, DV.TRIANGLES).c()
+    c.struct_size = C.sizeof(L.DebugViewContext) - 8
+    assert lib.oxc_apply_debug_view(r._ctx, None, C.byref(c), None) == L.OXC_INVALID_ARG
+    assert b"struct_size" in lib.oxc_last_error(r._ctx)
+    assert lib.oxc_apply_debug_view(r._ctx, None, None, None) == L.OXC_INVALID_ARG
+    c = DF.context(f, gs, DV.TRIANGLES).c()
+    c.width += 1
+    assert lib.oxc_apply_debug_view(r._ctx, None, C.byref(c), None) == L.OXC_INVALID_ARG and b"extent differs" in lib.oxc_last_error(r._ctx)
+    c.width = c.height = 0
+    assert lib.oxc_apply_debug_view(r._ctx, None, C.byref(c), None) == L.OXC_INVALID_ARG and b"must not be zero" in lib.oxc_last_error(r._ctx)
+    torch.cuda.synchronize()
+    DF.check_unwritten(gs, f, "short struct_size")
