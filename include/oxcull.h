@@ -535,7 +535,10 @@ oxc_status oxc_update_virtual_shadowmap(oxc_ctx* ctx, const oxc_vsm_update_conte
  *   vertex  each index of the list is drawn once per active clipmap.  Vertex fetch, world, the clipper (w >= 2^-10 and the 64x guard
  *           band), the screen mapping, the 1/256-pixel snap, the top-left rule and the binary64 z/w interpolation from exact edge values
  *           are exactly oxc_draw_visbuffer's, with projection_view = that clipmap's projection_view_mat and a V x V viewport,
- *           V = page_table_size * page_size.  A command with instanceCount == 0 draws nothing (the pair form's overflow rule).
+ *           V = page_table_size * page_size.  A command with instanceCount == 0 draws nothing (the pair form's overflow rule); any other
+ *           instanceCount draws the list once.  indexCount / 3 triangles are drawn (a remainder of 1 or 2 indices is ignored), at most
+ *           those the index buffer holds.  firstIndex, vertexOffset and firstInstance (words 2..4) are copied to draw_commands verbatim
+ *           and have no other effect: the list is read from its start.
  *   cull    None (Shadowmaps.cpp: cullMode eNone): a triangle with negative fixed-point area is re-oriented (corners 1 and 2 swapped),
  *           one with positive area is kept as is, zero area covers nothing; the top-left rule applies after orientation, so a shared
  *           edge is covered exactly once whatever the windings.

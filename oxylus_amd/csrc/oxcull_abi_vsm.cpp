@@ -195,7 +195,8 @@ oxc_status oxc_draw_physical_pages(oxc_ctx* ctx, const oxc_prepared_frame* f, co
   a.clip_capacity = cap;
   a.tile_list = reinterpret_cast<uint2*>(sc + o_tile);
   a.tile_capacity = cap * 2u;
-  launch_vsm_draw(a, ctx->vsm_draw_stats, ctx->num_cus * 8, s);
+  const uint32_t full_grid = ctx->num_cus * 8;
+  launch_vsm_draw(a, ctx->vsm_draw_stats, ctx->vsm_draw_grid ? std::min(ctx->vsm_draw_grid, full_grid) : full_grid, s);  // OXC_TUNE_VSM_DRAW_GRID
   OXC_HIP(ctx, hipGetLastError());
   return OXC_OK;
 }

@@ -92,6 +92,7 @@ struct oxc_ctx {
   uint64_t vsm_draw_scratch_bytes = 0;
   uint32_t vsm_draw_capacity = 0;          // entries of the big-pair and clip queues of that scratch (the tile queue holds 4x as many)
   uint32_t vsm_draw_capacity_request = 0;  // oxc_debug_set_tuning(OXC_TUNE_VSM_DRAW_CAPACITY): used by the first shadow draw
+  uint32_t vsm_draw_grid = 0;              // OXC_TUNE_VSM_DRAW_GRID: cap of every launch of the shadow draw in blocks, 0 = uncapped
   bool vsm_draw_stats = false;             // oxc_debug_set_tuning(OXC_TUNE_VSM_DRAW_STATS): counting kernels
   // The counters a pass's counting instantiation adds to: switched by oxc_debug_set_tuning, allocated by the first counting call
   // (arm_counters), read by the pass's oxc_debug_*_stats (read_counters).

@@ -736,7 +736,7 @@ __global__ __launch_bounds__(256) void k_vsm_draw_big_rescan(VsmDrawArgs a) {
 template <bool PAIR, bool STATS>
 static void launch_draw(const VsmDrawArgs& a, uint32_t max_grid, hipStream_t s) {
   hipLaunchKernelGGL((k_vsm_draw_tris<PAIR, STATS>), dim3(max_grid), dim3(256), 0, s, a);
-  hipLaunchKernelGGL((k_vsm_draw_clipped<false, PAIR, STATS>), dim3(256), dim3(64), 0, s, a);
+  hipLaunchKernelGGL((k_vsm_draw_clipped<false, PAIR, STATS>), dim3(std::min(256u, max_grid)), dim3(64), 0, s, a);
   hipLaunchKernelGGL((k_vsm_draw_clipped<true, PAIR, STATS>), dim3(max_grid), dim3(64), 0, s, a);  // (returns at once unless the queue overflowed)
   hipLaunchKernelGGL((k_vsm_draw_big<STATS>), dim3(max_grid), dim3(256), 0, s, a);
   hipLaunchKernelGGL((k_vsm_draw_tiles<STATS>), dim3(max_grid), dim3(256), 0, s, a);

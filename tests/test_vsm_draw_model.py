@@ -156,3 +156,190 @@ def test_pinned_to_the_oracle_visbuffer_draw_on_the_shared_rules():
     assert covered.sum() > 5000
     assert np.array_equal(img < 1.0, covered)
     assert np.array_equal(img[covered].view(np.uint32), depth[covered].view(np.uint32))
+
+
+# ---- the path predictor and the hand-written frames of tests/vsm_draw_frames.py ----------------------------------------------------------------------
+import pytest  # noqa: E402
+
+import vsm_draw_frames as VF  # noqa: E402
+import vsm_pages_model as VM  # noqa: E402
+
+
+@pytest.mark.parametrize("name", sorted(VF.all_frames()))
+def test_every_frame_sits_on_its_intended_path(name):
+    """`intent`: the setup snaps the frame's corners to exactly the 1/256-px integers it was written for; `expect`: predict gives every
+    triangle the path (and drawable-page and tile counts) the frame claims, in its first active clipmap."""
+    vf = VF.all_frames()[name]
+    rows = vf.first_clipmap()
+    for t, want in enumerate(vf.intent or []):
+        assert sorted(zip(rows[t]["X"], rows[t]["Y"])) == sorted(zip(*want)), (name, t, rows[t], want)
+    for t, want in enumerate(vf.expect or []):
+        if want is None:
+            continue
+        path, pages, tiles = want if isinstance(want, tuple) else (want, None, None)
+        assert rows[t]["path"] == path, (name, t, rows[t])
+        assert pages is None or (rows[t]["pages"], rows[t]["tiles"]) == (pages, tiles), (name, t, rows[t])
+    st = vf.model()[1]
+    kept = [r for r in vf.predict() if r["path"] != DM.DROPPED]
+    assert st["pairs"] == len(kept) and st["big_pairs"] == sum(r["path"] in (DM.DIRECT, DM.TILED) for r in kept) and st["tiles"] == sum(r["tiles"] for r in kept)
+
+
+def test_predict_splits_on_the_box_and_the_spread_but_on_the_box_alone_behind_the_clipper():
+    pm = np.zeros((8, 8, 2), np.int64)
+    X, Y = np.array([[0, 2048, 0], [-2048, 2048, 2048], [-2047, 2048, 2048]]), np.array([[0, 0, 2048], [256, 256, 2304], [256, 256, 2304]])
+    k = DM.classify(X, Y, 128, pm, 16)
+    assert k["spread"].tolist() == [2048, 4096, 4095] and k["small"].tolist() == [True, False, True] and k["big"].tolist() == [False, True, False]
+    assert DM.classify(X, Y, 128, pm, 16, from_clipper=[True] * 3)["small"].tolist() == [True] * 3
+    pm[...] = -1
+    assert not DM.classify(X, Y, 128, pm, 16)["kept"].any()
+
+
+def test_direct_or_tiled_follows_the_cut_page_box():
+    """The box is cut to the rectangle of the clipmap's drawable pages before its pages are counted: one drawable page under a triangle over
+    the whole 16 x 16-page viewport is a 1-page box (direct); two in opposite corners make a 256-page box (tiled, 2 tiles)."""
+    X, Y = np.array([[0, 0, 2 * 65536]]), np.array([[0, 2 * 65536, 0]])
+    pm = np.full((16, 16, 2), -1, np.int64)
+    pm[5, 9] = 0
+    k = DM.classify(X, Y, 256, pm, 16)
+    assert (k["pages"][0], k["box_pages"][0], bool(k["tiled"][0]), k["tiles"][0]) == (1, 1, False, 0)
+    pm[15, 15] = pm[0, 0] = 0
+    k = DM.classify(X, Y, 256, pm, 16)
+    assert (k["pages"][0], k["box_pages"][0], bool(k["tiled"][0]), k["tiles"][0]) == (3, 256, True, 3)
+
+
+def test_the_stride_frames_make_every_loop_step_with_one_block():
+    assert VF.RF.STRIDE_INSTANCES > 256 and set(VF.RF.STRIDE_COUNTS) == {255, 256, 257, 512, 513, 769, 1025}
+    for n in VF.RF.STRIDE_COUNTS:
+        st = VF.stride_frame(n).model()[1]
+        assert st["pairs"] == n and st["big_pairs"] == st["clipped_pairs"] == 0  # every triangle on the in-wave path
+    assert VF.clip_stride_frame().model()[1]["clipped_pairs"] == 136 >= 130  # three steps of one 64-thread block
+    st = VF.big_stride_frame().model()[1]
+    assert st["big_pairs"] >= 9 and st["tiles"] >= 9 and any(r["path"] == DM.DIRECT for r in VF.big_stride_frame().predict())
+    n = VF.wide_table_frame().shape[0]
+    assert n * n // 32 == 288 > 256
+    assert any((y * n + x) // 32 >= 256 for c in range(2) for y, x in zip(*np.nonzero(VF.wide_table_frame().table[c] & 6 == 6)))
+
+
+@pytest.mark.parametrize("n", VF.BITMAP_NS)
+def test_the_bitmap_frames_put_their_page_where_they_say(n):
+    for which, want in zip(VF.BITMAP_BITS, (lambda b: b == 0, lambda b: b == 31, lambda b: 0 < b < 31)):
+        vx, vy = VF.bitmap_page(n, which)
+        assert want((vy * n + vx) & 31) and (vy * n) >> 5 != (vy * n + n - 1) >> 5
+        assert VF.bitmap_frame(n, which, 0).model()[1]["pairs"] == 1
+    assert VF.bitmap_frame(n, "mid", 16).model()[1]["pairs"] == 0  # address P * P: no page
+    assert VF.corners_frame(n).model()[1]["pairs"] == 3
+
+
+def test_the_box_shape_frame_covers_every_shape_and_fills_its_waves_as_claimed():
+    vf = VF.box_shapes_frame()
+    rows = vf.first_clipmap()
+    assert {(r["bw"], r["bh"]) for r in rows.values() if r["path"] == DM.SMALL_PATH} == {(w, h) for w in range(1, 9) for h in range(1, 9)}
+    cnt = [rows[t]["bw"] * rows[t]["bh"] if rows[t]["path"] == DM.SMALL_PATH else 0 for t in range(len(rows))]
+    waves = [cnt[i:i + 64] for i in range(0, len(cnt), 64)]
+    assert len(waves) == 2 and sum(waves[0]) > 64
+    assert waves[0][0] == 0 and waves[1][-1] == 0 and any(a and not b and c for w in waves for a, b, c in zip(w, w[1:], w[2:]))
+
+
+def test_the_threshold_frames_sit_on_both_sides_of_each_switch():
+    c = VF.threshold_frames()
+    rows = c["spread-4095-4096"].first_clipmap()
+    assert [rows[t]["spread"] for t in range(8)] == [4095] * 4 + [4096] * 4 and all(rows[t]["bw"] <= 8 and rows[t]["bh"] <= 8 for t in range(8))
+    assert c["spread-4095-4096"].model()[1]["big_pairs"] == 4
+    for s in (32767, 32768):
+        rows = c[f"spread-{s}"].first_clipmap()
+        assert [rows[t]["spread"] for t in range(4)] == [s] * 4
+    rows = c["box-8x8-9x8-8x9"].first_clipmap()
+    assert [(rows[t]["bw"], rows[t]["bh"]) for t in range(3)] == [(8, 8), (9, 8), (8, 9)]
+
+
+def test_the_page_count_frames_sit_on_both_sides_of_each_switch():
+    c = VF.direct_tiled_frames()
+    box = {k: v.first_clipmap()[0]["box_pages"] for k, v in c.items()}
+    assert box == {"4-pages": 16, "5-pages": 16, "64-page-box": 64, "72-page-box": 72, "65-page-box": 65, "second-batch": 81}
+    t = c["second-batch"].table[0]
+    inside = [(x, y) for y, x in zip(*np.nonzero(t & 6 == 6)) if 1 <= x <= 9 and 1 <= y <= 9]
+    assert len(inside) == 3 and all((y - 1) * 9 + (x - 1) >= 64 for x, y in inside)  # the first batch of 64 pages holds none
+
+
+def test_the_overflow_frames_overflow_what_they_claim():
+    c = {k: v.model()[1] for k, v in VF.overflow_frames().items()}
+    cap = VF.CAPACITY
+    assert c["tiles"]["tiles"] == 150 > 2 * cap > 100 and c["tiles"]["big_pairs"] == 3
+    assert c["big"]["big_pairs"] > cap >= c["big"]["clipped_pairs"] > 0 and c["big"]["tiles"] == 0
+    assert any(r["fan"] >= 0 and r["path"] == DM.DIRECT for r in VF.overflow_frames()["big"].predict())  # some big pairs come from the clipper
+    assert c["clip"]["clipped_pairs"] > cap and c["clip"]["big_pairs"] == 0
+    assert c["big-and-clip"]["clipped_pairs"] > cap and c["big-and-clip"]["big_pairs"] > cap and c["big-and-clip"]["tiles"] == 0
+    assert not any(r["fan"] >= 0 and r["path"] in (DM.DIRECT, DM.TILED) for r in VF.overflow_frames()["big-and-clip"].predict())
+
+
+@pytest.mark.parametrize("n", VF.OFFSET_NS)
+def test_the_wrap_of_extreme_page_offsets(n):
+    """floor_mod(v + page_offset, n) in unbounded integers: vsm_pages_model.wrap works in int64 whatever its inputs' types, so int32 offsets
+    at either end of their range do not overflow; page_map reads the entries that puts under each virtual page."""
+    v = np.arange(n)
+    for off in VF.offset_values(n):
+        want = [(int(x) + off) % n for x in v]
+        assert VM.wrap(v, off, n).tolist() == want
+        assert VM.wrap(v.astype(np.int32), np.int32(off), n).tolist() == want
+        assert VM.wrap(np.int32(n - 1), np.array([off], np.int32), n).tolist() == [(n - 1 + off) % n]
+    for i in range(8):
+        vf = VF.offset_frame(n, i)
+        ox, oy = VF.offset_values(n)[i], VF.offset_values(n)[(i + 3) % 8]
+        assert VM.unpack_clipmaps(vf.clipmaps)[1][0].tolist() == [ox, oy]
+        pm = DM.page_map(vf.table, vf.clipmaps, 1, n, 16, vf.shape[2])[0]
+        addr = pm[..., 1] * (vf.shape[2] // 16) + pm[..., 0]
+        assert len(set(addr.reshape(-1).tolist())) == n * n
+        for vy, vx in ((0, 0), (n - 1, 0), (3, n - 2)):
+            assert addr[vy, vx] == vf.table[0, (vy + oy) % n, (vx + ox) % n] >> 16
+
+
+def test_negative_zero_fragments_are_kept_and_lower_no_positive_value():
+    vf = VF.neg_zero_frame()
+    img, st = vf.model()
+    before, after = vf.image.view(np.uint32), img.view(np.uint32)
+    changed = before != after
+    assert st["fragments"] > 100 and st["big_pairs"] == 1 and changed.sum() > 20
+    assert (before[changed] == np.float32(-1.0).view(np.uint32)).all() and (after[changed] == VF.NEG_ZERO_BITS).all()
+
+
+def test_depth_from_binary16_around_one():
+    vf = VF.half_depth_frame()
+    img = vf.model()[0]
+    assert set(np.unique(img).tolist()) >= {1.0, 2.0} and img.max() == 2.0
+    assert not any(r["path"] == DM.DROPPED for r in vf.predict())  # the page test keeps all eight; the depth test decides
+    per = []
+    for k in range(4):  # each meshlet alone
+        one = VF.VFrame(vf.frame, vf.shape, vf.table, image=vf.image, draw=[(k, k, 0), (k, k, 1)])
+        per.append(one.model()[1]["fragments"])
+    assert per[0] > 200 and per[1] == 0 and 0 < per[2] < per[0] and per[2] < per[3] < per[0], per
+
+
+@pytest.mark.parametrize("name", ["nan", "inf"])
+def test_a_triangle_with_a_non_finite_vertex_is_dropped_whole(name):
+    vf = VF.all_frames()[name]
+    img, st = vf.model()
+    assert st["pairs"] == 2 and st["clipped_pairs"] == 1  # it crosses every plane's test, and nothing comes out of the clipper
+    alone = VF.VFrame(vf.frame, vf.shape, vf.table, draw=[vf.frame.draw[0], vf.frame.draw[2]])
+    assert np.array_equal(alone.model()[0], img) and alone.model()[1]["fragments"] == st["fragments"] > 40
+
+
+@pytest.mark.parametrize("s", [8, 40])
+def test_a_shared_edge_with_opposite_windings_is_covered_once(s):
+    vf = VF.shared_edge_frame(s)
+    rows = vf.first_clipmap()
+    area = lambda r: (r["X"][1] - r["X"][0]) * (r["Y"][2] - r["Y"][0]) - (r["Y"][1] - r["Y"][0]) * (r["X"][2] - r["X"][0])  # noqa: E731
+    assert area(rows[0]) > 0 and area(rows[1]) > 0  # oriented; the list winds them oppositely:
+    w = DM.fetch_world(vf.frame.scene, vf.frame.scene.meshlet_instances, vf.indices())
+    sign = [np.sign((t[1, 0] - t[0, 0]) * (t[2, 1] - t[0, 1]) - (t[1, 1] - t[0, 1]) * (t[2, 0] - t[0, 0])) for t in w]
+    assert sign[0] == -sign[1] != 0
+    assert vf.model()[1]["fragments"] == s * s
+
+
+def test_the_limit_frame_reaches_the_largest_viewport():
+    vf = VF.limit_frame()
+    assert vf.V == 16384 and int(((vf.table & 6) == 6).sum()) == 16
+    img, st = vf.model()
+    assert st["clipped_pairs"] == 2 and st["big_pairs"] >= 3 and st["fragments"] > 10000
+    rows = vf.predict()
+    assert max(max(abs(v) for v in r["X"] + r["Y"]) for r in rows) > 32 * 16384 * 256  # the guard band's fixed-point range is reached
+    assert {r["clipmap"] for r in rows if r["path"] != DM.DROPPED} == {0, 1}

@@ -51,7 +51,8 @@ def fetch_world(scene, meshlet_instances, indices, wide=0, triangles=None) -> np
     q = _u32(scene.positions).view(np.uint16).reshape(-1, 4)[(mesh[:, 0] - scene.positions.data_ptr()) // 8 + vi]
     p = dequantize_half(q[:, :3])
     xf = np.asarray(scene.transforms, dtype=np.float32).reshape(-1, 16)[mi[:, 3]]
-    return mul_mp(xf, p)[:, :3].reshape(T, 3, 3)
+    with np.errstate(invalid="ignore", over="ignore"):  # (a non-finite position is the caller's to drop)
+        return mul_mp(xf, p)[:, :3].reshape(T, 3, 3)
 
 
 def build_draw_commands(dirty_flags, count: int, source_command, commands=None, clipmaps=None):
@@ -179,73 +180,144 @@ def _write(u, pm, ps: int, phys: int, px, py, keep, zf):
     return int(keep.sum())
 
 
-def raster(u, X, Y, z, V: int, pm, ps: int, phys: int, chunk: int = 8192):
-    """Draw oriented triangles [K] into the u32 view `u` of the physical image through page map `pm` [n, n, 2] of one clipmap.
-    Returns (pairs whose page box holds a drawable page, fragments written)."""
-    if len(X) == 0:
-        return 0, 0
+DROPPED, SMALL_PATH, DIRECT, TILED = "dropped", "small", "direct", "tiled"
+SMALL_SPREAD, DIRECT_PAGES, BATCH = 4096, 4, 64
+
+
+def classify(X, Y, V: int, pm, ps: int, from_clipper=None) -> dict:
+    """What the kernels have to do with oriented set-up triangles [K] of one clipmap (page map `pm` [n, n, 2]), as arrays [K]:
+    px0, py0, px1, py1  the pixel box clamped to the viewport;  spread  the larger of the corners' x and y extents (1/256 px);
+    pages    drawable pages in the page box cut to the clipmap's rectangle of drawable pages (0: the pair is dropped);
+    box_pages  pages of that cut box;
+    small    pixel box at most 8 x 8 and -- unless the triangle comes out of the clipper (`from_clipper` bool [K]) -- spread < 4096: drawn
+             where it was set up; every other kept pair goes to the big list;
+    tiled    a big pair that hands out tiles: its cut box has more than 64 pages (every batch of 64 with a drawable page queues them) or more
+             than 4 of its pages are drawable; `tiles` is then `pages`.  Other big pairs are drawn by their own wave (direct).
+    All in int64: |X|, |Y| <= 2^28 (the 2^20-pixel guard of the setup), so extents stay below 2^29 and page counts below 2^16."""
+    K = len(X)
+    fc = np.zeros(K, bool) if from_clipper is None else np.asarray(from_clipper, bool)
     minx, maxx, miny, maxy = X.min(1), X.max(1), Y.min(1), Y.max(1)
     px0, py0 = np.maximum((minx - 128 + 255) >> 8, 0), np.maximum((miny - 128 + 255) >> 8, 0)
     px1, py1 = np.minimum((maxx - 128) >> 8, V - 1), np.minimum((maxy - 128) >> 8, V - 1)
-    draw = np.flatnonzero((px1 >= px0) & (py1 >= py0))
-    ok_page = (pm[..., 0] >= 0).astype(np.int64)
-    sat = np.zeros((ok_page.shape[0] + 1, ok_page.shape[1] + 1), np.int64)
-    sat[1:, 1:] = ok_page.cumsum(0).cumsum(1)
-    qx0, qx1, qy0, qy1 = px0[draw] // ps, px1[draw] // ps, py0[draw] // ps, py1[draw] // ps
-    drawable = (sat[qy1 + 1, qx1 + 1] - sat[qy0, qx1 + 1] - sat[qy1 + 1, qx0] + sat[qy0, qx0]) > 0
-    draw = draw[drawable]
+    spread = np.maximum(maxx - minx, maxy - miny)
+    boxed = (px1 >= px0) & (py1 >= py0)
+    ok_page = pm[..., 0] >= 0
+    n = ok_page.shape[0]
+    sat = np.zeros((n + 1, n + 1), np.int64)
+    sat[1:, 1:] = ok_page.astype(np.int64).cumsum(0).cumsum(1)
+    pages, box_pages = np.zeros(K, np.int64), np.zeros(K, np.int64)
+    if ok_page.any():
+        ys, xs = np.nonzero(ok_page)
+        rx0, rx1, ry0, ry1 = xs.min(), xs.max(), ys.min(), ys.max()
+        sx0, sy0, sx1, sy1 = (np.where(boxed, v, 0) for v in (px0, py0, px1, py1))
+        qx0, qx1 = np.maximum(sx0 // ps, rx0), np.minimum(sx1 // ps, rx1)
+        qy0, qy1 = np.maximum(sy0 // ps, ry0), np.minimum(sy1 // ps, ry1)
+        cut = boxed & (qx1 >= qx0) & (qy1 >= qy0)
+        qx0, qx1, qy0, qy1 = (np.where(cut, v, 0) for v in (qx0, qx1, qy0, qy1))
+        pages = np.where(cut, sat[qy1 + 1, qx1 + 1] - sat[qy0, qx1 + 1] - sat[qy1 + 1, qx0] + sat[qy0, qx0], 0)
+        box_pages = np.where(cut, (qx1 - qx0 + 1) * (qy1 - qy0 + 1), 0)
+    kept = pages > 0
+    bw, bh = px1 - px0 + 1, py1 - py0 + 1
+    small = kept & (bw <= SMALL) & (bh <= SMALL) & (fc | (spread < SMALL_SPREAD))
+    big = kept & ~small
+    tiled = big & ((box_pages > BATCH) | (pages > DIRECT_PAGES))
+    return dict(px0=px0, py0=py0, px1=px1, py1=py1, spread=spread, pages=pages, box_pages=box_pages, kept=kept, small=small, big=big, tiled=tiled,
+                tiles=np.where(tiled, pages, 0))
+
+
+def raster(u, X, Y, z, V: int, pm, ps: int, phys: int, chunk: int = 8192, from_clipper=None):
+    """Draw oriented triangles [K] into the u32 view `u` of the physical image through page map `pm` [n, n, 2] of one clipmap.
+    Returns (pairs whose page box holds a drawable page, fragments written, big pairs, tiles) -- the last two as `classify` counts them.
+    (Which pixel walk a pair gets here follows its box alone: every walk writes the same texels.)"""
+    if len(X) == 0:
+        return 0, 0, 0, 0
+    k = classify(X, Y, V, pm, ps, from_clipper)
+    px0, py0, px1, py1 = k["px0"], k["py0"], k["px1"], k["py1"]
+    draw = np.flatnonzero(k["kept"])
     pairs, frags = len(draw), 0
     bw, bh = px1[draw] - px0[draw] + 1, py1[draw] - py0[draw] + 1
     small = draw[(bw <= SMALL) & (bh <= SMALL)]
-    k = np.arange(SMALL * SMALL)
+    kk = np.arange(SMALL * SMALL)
     for s in range(0, len(small), chunk):
         ids = small[s:s + chunk]
-        px = px0[ids, None] + k % SMALL
-        py = py0[ids, None] + k // SMALL
+        px = px0[ids, None] + kk % SMALL
+        py = py0[ids, None] + kk // SMALL
         inbox = (px <= px1[ids, None]) & (py <= py1[ids, None])
         px, py = np.minimum(px, V - 1), np.minimum(py, V - 1)
         keep, zf = _fragments(X[ids], Y[ids], z[ids], px, py)
         frags += _write(u, pm, ps, phys, px, py, keep & inbox, zf)
     for i in draw[(bw > SMALL) | (bh > SMALL)]:
-        for vy in range(py0[i] // ps, py1[i] // ps + 1):
-            for vx in range(px0[i] // ps, px1[i] // ps + 1):
-                if pm[vy, vx, 0] < 0:
-                    continue
-                x0, x1 = max(px0[i], vx * ps), min(px1[i], vx * ps + ps - 1)
-                y0, y1 = max(py0[i], vy * ps), min(py1[i], vy * ps + ps - 1)
-                gy, gx = np.mgrid[y0:y1 + 1, x0:x1 + 1]
-                px, py = gx.reshape(1, -1), gy.reshape(1, -1)
-                keep, zf = _fragments(X[i:i + 1], Y[i:i + 1], z[i:i + 1], px, py)
-                frags += _write(u, pm, ps, phys, px, py, keep, zf)
-    return pairs, frags
+        vys, vxs = np.nonzero(pm[py0[i] // ps:py1[i] // ps + 1, px0[i] // ps:px1[i] // ps + 1, 0] >= 0)
+        for vy, vx in zip((vys + py0[i] // ps).tolist(), (vxs + px0[i] // ps).tolist()):
+            x0, x1 = max(px0[i], vx * ps), min(px1[i], vx * ps + ps - 1)
+            y0, y1 = max(py0[i], vy * ps), min(py1[i], vy * ps + ps - 1)
+            gy, gx = np.mgrid[y0:y1 + 1, x0:x1 + 1]
+            px, py = gx.reshape(1, -1), gy.reshape(1, -1)
+            keep, zf = _fragments(X[i:i + 1], Y[i:i + 1], z[i:i + 1], px, py)
+            frags += _write(u, pm, ps, phys, px, py, keep, zf)
+    return pairs, frags, int(k["big"].sum()), int(k["tiles"].sum())
+
+
+def _setups(scene, meshlet_instances, indices, draw_cmd, table, clipmaps, dirty_flags, n, ps, phys, count, wide):
+    """Per active clipmap (descending): (clipmap, page map, triangle of the list [K], fan index [K] (-1: not clipped), ok, X, Y, z, crossing
+    pairs) for every triangle the setup is run on."""
+    cmd = np.asarray(draw_cmd, dtype=np.int64).reshape(-1) & 0xFFFFFFFF
+    active = active_clipmaps(dirty_flags, count)
+    T = 0 if cmd[1] == 0 else int(cmd[0]) // 3
+    if not active or not T:
+        return
+    world = fetch_world(scene, meshlet_instances, indices, wide, T)
+    pm = page_map(table, clipmaps, count, n, ps, phys)
+    mats = VM.unpack_clipmaps(clipmaps)[0]
+    for c in active:
+        with np.errstate(invalid="ignore", over="ignore"):
+            clip = mul_mp(mats[c], world)  # [T, 3, 4]
+        cls = clip_class(clip)
+        tris, tri, fan = [clip[cls == 0]], [np.flatnonzero(cls == 0)], [np.full(int((cls == 0).sum()), -1, np.int64)]
+        for t in np.flatnonzero(cls == 1):
+            with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+                pieces = clip_polygon(clip[t])
+            tris += [p[None] for p in pieces]
+            tri.append(np.full(len(pieces), t, np.int64))
+            fan.append(np.arange(len(pieces), dtype=np.int64))
+        ok, X, Y, z = setup(np.concatenate(tris).reshape(-1, 3, 4), V=n * ps)
+        yield c, pm[c], np.concatenate(tri), np.concatenate(fan), ok, X, Y, z, int((cls == 1).sum())
+
+
+def predict(scene, meshlet_instances, indices, draw_cmd, table, clipmaps, dirty_flags, *, page_size: int, page_table_size: int,
+            physical_page_table_size: int, clipmap_count: int, wide=0) -> list:
+    """What the kernels have to do with every (triangle, clipmap) pair that reaches the setup, in the order clipmaps descending, unclipped
+    triangles in list order, then the clipper's fan triangles: dicts {clipmap, triangle, fan (-1: not clipped), path, pages, box_pages,
+    tiles, bw, bh, spread}.  path: `dropped` (zero area, empty pixel box, or no drawable page in its page box), `small` (drawn where it was
+    set up), `direct` / `tiled` (big list; see `classify`)."""
+    n, ps = page_table_size, page_size
+    out = []
+    for c, pm, tri, fan, ok, X, Y, z, _ in _setups(scene, meshlet_instances, indices, draw_cmd, table, clipmaps, dirty_flags, n, ps,
+                                                    physical_page_table_size, clipmap_count, wide):
+        k = classify(X, Y, n * ps, pm, ps, fan >= 0)
+        for i in range(len(tri)):
+            live = bool(ok[i]) and bool(k["kept"][i])
+            path = DROPPED if not live else SMALL_PATH if k["small"][i] else TILED if k["tiled"][i] else DIRECT
+            out.append(dict(clipmap=int(c), triangle=int(tri[i]), fan=int(fan[i]), path=path, pages=int(k["pages"][i]) if live else 0,
+                            box_pages=int(k["box_pages"][i]) if live else 0, tiles=int(k["tiles"][i]) if live else 0,
+                            bw=int(k["px1"][i] - k["px0"][i] + 1), bh=int(k["py1"][i] - k["py0"][i] + 1), spread=int(k["spread"][i]),
+                            X=X[i].tolist(), Y=Y[i].tolist()))
+    return out
 
 
 def draw(image, scene, meshlet_instances, indices, draw_cmd, table, clipmaps, dirty_flags, *, page_size: int, page_table_size: int,
          physical_page_table_size: int, clipmap_count: int, wide=0, stats: dict = None) -> np.ndarray:
-    """One oxc_draw_physical_pages call on a copy of `image` (float32 [phys, phys]): the physical image after it."""
+    """One oxc_draw_physical_pages call on a copy of `image` (float32 [phys, phys]): the physical image after it.  `stats` receives what
+    oxc_debug_vsm_draw_stats counts when no queue overflows: pairs, fragments, big_pairs, tiles, clipped_pairs."""
     n, ps, phys, count = page_table_size, page_size, physical_page_table_size, clipmap_count
-    V = n * ps
     img = np.array(image, dtype=np.float32).reshape(phys, phys).copy()
     u = img.view(np.uint32).reshape(-1)
-    cmd = np.asarray(draw_cmd, dtype=np.int64).reshape(-1) & 0xFFFFFFFF
-    active = active_clipmaps(dirty_flags, count)
-    T = 0 if cmd[1] == 0 else int(cmd[0]) // 3
-    pairs = frags = 0
-    if active and T:
-        world = fetch_world(scene, meshlet_instances, indices, wide, T)
-        pm = page_map(table, clipmaps, count, n, ps, phys)
-        mats = VM.unpack_clipmaps(clipmaps)[0]
-        for c in active:
-            clip = mul_mp(mats[c], world)  # [T, 3, 4]
-            cls = clip_class(clip)
-            tris = [clip[cls == 0]]
-            for t in np.flatnonzero(cls == 1):
-                tris += [p[None] for p in clip_polygon(clip[t])]
-            ok, X, Y, z = setup(np.concatenate(tris).reshape(-1, 3, 4), V)
-            p, fr = raster(u, X[ok], Y[ok], z[ok], V, pm[c], ps, phys)
-            pairs, frags = pairs + p, frags + fr
+    pairs = frags = big = tiles = crossing = 0
+    for c, pm, tri, fan, ok, X, Y, z, cross in _setups(scene, meshlet_instances, indices, draw_cmd, table, clipmaps, dirty_flags, n, ps, phys, count, wide):
+        p, fr, b, t = raster(u, X[ok], Y[ok], z[ok], n * ps, pm, ps, phys, from_clipper=(fan >= 0)[ok])
+        pairs, frags, big, tiles, crossing = pairs + p, frags + fr, big + b, tiles + t, crossing + cross
     if stats is not None:
-        stats.update(pairs=pairs, fragments=frags)
+        stats.update(pairs=pairs, fragments=frags, big_pairs=big, tiles=tiles, clipped_pairs=crossing)
     return img
 
 
