@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import raster_model as RM
 import vsm_draw_frames as VF
 import vsm_draw_model as DM
 from oxylus_amd import lib as L
@@ -180,3 +181,49 @@ def test_draw_command(counting, cmd, form):
     assert np.array_equal(got, VF.command_frame(form, (3 * drawn, 1, 0, 0, 0)).model()[0].view(np.uint32))
     if drawn < 5:  # the list's tail would have drawn
         assert not np.array_equal(got, VF.command_frame(form).model()[0].view(np.uint32))
+
+
+# ---- 10. the two draws agree where their rules coincide ----------------------------------------------------------------------------------------------
+def _written_depth(vf):
+    """(mask of written texels, their depth bits, vis per texel) of the frame's visbuffer image by the CPU checkers, and (mask, bits) of
+    its shadow image by vsm_draw_model."""
+    vd = vf.frame.oracle_image().numpy().view(np.uint64)
+    shadow = vf.model()[0].view(np.uint32)
+    return (vd != 0, (vd >> np.uint64(32)).astype(np.uint32), (vd & np.uint64(0xFFFFFFFF)).astype(np.uint32)), (shadow != F2_BITS, shadow)
+
+
+F2_BITS = int(np.float32(2.0).view(np.uint32))
+
+
+def _assert_agree(main, shadow, vf, label):
+    (m_mask, m_bits, m_vis), (s_mask, s_bits) = main, shadow
+    assert np.array_equal(m_mask, s_mask), f"{label}: {int((m_mask != s_mask).sum())} texels written by one draw only"
+    assert np.array_equal(m_bits[m_mask], s_bits[s_mask]), f"{label}: {int((m_bits != s_bits)[m_mask].sum())} depths differ"
+    for i, name in enumerate(VF.AGREEMENT_CLASSES):
+        assert int((m_mask & (m_vis == vf.frame.vis(i, 0, 0))).sum()) > 0, (label, name)
+
+
+def test_the_two_draws_agree_where_their_rules_coincide(counting, renderer, oracle_lib):
+    """The same five triangles (vsm_draw_frames.agreement_frame: front-facing, disjoint, depth inside (0, 1), one per path) through
+    oxc_draw_visbuffer at 128 x 128 and through oxc_draw_physical_pages with one identity-mapped clipmap of V = 128 under the same
+    projection_view: the same texels are written and they hold the same depth bits -- first by the two CPU checkers, then on the device."""
+    import test_gpu_raster_paths as RP
+
+    vf = VF.agreement_frame()
+    main, shadow = _written_depth(vf)
+    # the unclipped four once more by the Python raster model, which does not clip
+    rm, setups = vf.frame.model_image(vf.frame.draw[:4])
+    four = vf.frame.oracle_image(draw=vf.frame.draw[:4]).numpy().view(np.uint64)
+    assert np.array_equal(rm, four)
+    assert [RM.predict(t)[0] for t in setups] == [RM.SMALL, RM.RECT32, RM.RECT32, RM.TILES32]
+    _assert_agree(main, shadow, vf, "CPU checkers")
+    # the device: each draw against its checker (bytes, path counts), then against the other
+    got_s, st = _run(counting, vf, "agreement")
+    assert (st["pairs"], st["big_pairs"], st["tiles"], st["clipped_pairs"]) == (6, 5, 9 + 20 + 48 + 30, 1), st  # the sliver leaves the clipper as two tiled pieces
+    got_m = RP._draw(renderer, vf.frame)
+    rs = renderer.debug_raster_stats()
+    print("agreement", rs)
+    RP._assert_same(got_m, vf.frame.oracle_image(), "agreement")
+    assert (rs["clipped"], rs["big"], rs["tiles"], rs["overflowed_segments"]) == (1, 5, 2 + 4 + 4, 0), rs  # boxes of 50 x 70, 128 x 96 and 68 x 96 px in tiles of 64
+    vd = got_m.numpy().view(np.uint64)
+    _assert_agree((vd != 0, (vd >> np.uint64(32)).astype(np.uint32), (vd & np.uint64(0xFFFFFFFF)).astype(np.uint32)), (got_s != F2_BITS, got_s), vf, "device")

@@ -433,6 +433,29 @@ def limit_frame():
     return VFrame(f, shape, t, clipmaps=rec)
 
 
+# ---- 10. the two draws on one frame ----------------------------------------------------------------------------------------------------------
+AGREEMENT_SHAPE = (8, 16, 128, 1)
+AGREEMENT_CLASSES = ("small box", "big box in one page", "box over 9 pages", "box over 64 px", "crossing w = 2^-10")
+
+
+@functools.lru_cache(maxsize=None)
+def agreement_frame():
+    """One frame for oxc_draw_visbuffer at 128 x 128 and oxc_draw_physical_pages with one clipmap of 8 x 8 pages of 16 px, every page backed,
+    dirty and mapped to itself (V = 128), both under raster_frames.clipped_stride_frame's matrix clip = (x, y, 0.25, z): depth is 0.25 / w.
+    Five front-facing triangles that share no pixel, one per AGREEMENT_CLASSES: boxes of 6 x 6, 12 x 12 (inside page (1, 0)), 40 x 40 (pages
+    5..7 x 0..2) and 50 x 70 px at w = 1, 0.5, 0.3125, 0.4, and a sliver down the middle columns from w = 1 to w = -0.5, whose pixels with
+    w > 0.25 have a depth below 1.  The image starts at 2.0, so every texel the shadow draw writes shows."""
+    def flat(t, w):  # a triangle given in 1/256 px on the plane of clip w
+        return [((X / 256.0 / 64.0 - 1.0) * w, (Y / 256.0 / 64.0 - 1.0) * w, w) for X, Y in t]
+
+    tris = [flat(right_triangle(4, 4, 6, 6), 1.0), flat(right_triangle(17, 1, 12, 12), 0.5), flat(right_triangle(80, 4, 40, 40), 0.3125),
+            flat(right_triangle(2, 50, 50, 70), 0.4), [(-0.0625, -0.5, 1.0), (0.0, 1.0, -0.5), (0.0625, -0.5, 1.0)]]
+    f = RF.Frame(RF.UNIT, [affine(*t) for t in tris], 128, 128, pv=RF.clipped_stride_frame().pv)
+    table = table_of(AGREEMENT_SHAPE, {(x, y): x + 8 * y for y in range(8) for x in range(8)})
+    return VFrame(f, AGREEMENT_SHAPE, table, clipmaps=perspective_clipmaps(1), image=np.full((128, 128), 2.0, np.float32),
+                  expect=[DM.SMALL_PATH, (DM.DIRECT, 1, 0), (DM.TILED, 9, 9), DM.TILED, None])
+
+
 # ---- every frame by name (the CPU tests walk this; the GPU tests take the frames from the functions above) --------------------------------------
 @functools.lru_cache(maxsize=None)
 def all_frames():
@@ -450,5 +473,5 @@ def all_frames():
     c.update({f"command-form{form}": command_frame(form) for form in (0, 2)})
     c.update({f"offset-n{n}-{i}": offset_frame(n, i) for n in OFFSET_NS for i in range(8)})
     c.update({"neg-zero": neg_zero_frame(), "half-depth": half_depth_frame(), "nan": nonfinite_frame(0x7E00), "inf": nonfinite_frame(0x7C00),
-              "shared-edge-8": shared_edge_frame(8), "shared-edge-40": shared_edge_frame(40), "limit": limit_frame()})
+              "shared-edge-8": shared_edge_frame(8), "shared-edge-40": shared_edge_frame(40), "limit": limit_frame(), "agreement": agreement_frame()})
     return c
