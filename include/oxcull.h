@@ -2141,7 +2141,8 @@ oxc_status oxc_decode_terrain(oxc_ctx* ctx, const oxc_terrain_decode_context* co
  * overdraw heat, one G-buffer channel or the ambient occlusion, with a depth outline; or, for OXC_DEBUG_VIEW_RMVSM, the state of the VSM
  * page the pixel falls in.  One launch, one R16G16B16A16 Sfloat image out.
  * Not built: a producer for the overdraw image (oxc_draw_visbuffer has no counting mode, visbuffer_encode.slang:69-71; the caller fills
- * the u32 image); draw_bounding_boxes (Debug.cpp:155-211, line rasterisation); the editor's picking and highlight passes.
+ * the u32 image); draw_bounding_boxes (Debug.cpp:155-211, line rasterisation).  The editor's picking and highlight passes are
+ * oxc_pick_transform and oxc_apply_highlight below.
  * Arithmetic: the conventions of oxc_apply_pbr's block -- binary32, round to nearest even, the Slang's order left to right, no
  * contraction, IEEE division; min, max and saturate through fminf / fmaxf (a NaN operand loses, saturate(NaN) = 0); a comparison with a
  * NaN operand is false; f32(u32) rounds to nearest even; a half store is round to nearest even with denormals kept and a NaN stored as
@@ -2264,6 +2265,107 @@ typedef struct oxc_debug_view_context {
 } oxc_debug_view_context;
 
 oxc_status oxc_apply_debug_view(oxc_ctx* ctx, const oxc_prepared_frame* frame, const oxc_debug_view_context* context, void* hip_stream);
+
+/* ---- the editor's selection path: which entity is under the cursor, and the outline around the selected ones -------------------------------
+ * oxc_pick_transform is the `mouse_picking` stage and oxc_apply_highlight the `highlight_mask` and `entity_highlighting` stages of the
+ * reference's editor (OxylusEditor/src/Panels/ViewportPanel.cpp:1166-1556: mouse_picking_stages, highlight_mask_stage,
+ * highlight_composite_stage; shaders editor/mouse_picking.slang, highlight_mask.slang, highlight_dilate_horizontal.slang and
+ * highlight_composite.slang).  Not built: mouse_picking_2d.slang (the library has no 2D pass).
+ * Arithmetic: the conventions of oxc_apply_debug_view's block -- binary32, round to nearest even, the Slang's order, no contraction, IEEE
+ * division; saturate through fminf / fmaxf (saturate(NaN) = 0); a comparison with a NaN operand is false; pow by the pow rule of
+ * oxc_apply_pbr (a base that is zero, negative, below 2^-126 or NaN has log2 -Inf).
+ *   P. transform of a texel  (mouse_picking.slang:21-35, highlight_mask.slang:18-30)
+ *              texel == ~0u: ~0u.  (texel >> 8) == 0xFFFFFE, a terrain texel: terrain_transform_index.  Otherwise
+ *              mesh_instances[meshlet_instances[texel >> 8].mesh_instance_index].transform_index.  Stated rule, V3 of oxc_apply_debug_view:
+ *              a texel with (texel >> 8) >= meshlet_instance_count uses an all-zero MeshInstance and loads nothing, so its transform is 0;
+ *              the Slang reads past the buffer there.  mesh_instance_index is the scene's own and is not checked.
+ * oxc_pick_transform writes P of the texel (x, y) as one u32 to transform_id.  Limits (else OXC_INVALID_ARG, nothing launched, nothing
+ * written; the first broken rule in this order gives the message, each has its own): struct_size; width and height non-zero and at most
+ * 65536; x < width and y < height; `frame` non-null; then visbuffer_attachment, transform_id, the frame's meshlet_instances_buffer and
+ * mesh_instances_buffer, each non-null, then 4-byte aligned, then large enough (one u32 per pixel; one u32; meshlet_instance_count records
+ * of 8 bytes; mesh_instances_buffer as given); then transform_id shares no byte with any of them.  One launch, no scratch, no allocation,
+ * no host synchronisation; capturable into a HIP graph.
+ *
+ * oxc_apply_highlight runs the stages of `stages`, the mask first.  The engine runs the mask after VisBufferEncode and the rest after
+ * post-processing, so each stage can be called alone.
+ * Stage OXC_HIGHLIGHT_MASK (highlight_mask.slang), per pixel (x, y):
+ *   M1. selected  (:15-41)  t = P of the visbuffer texel.  Not selected when the texel is ~0u or t == ~0u; otherwise selected when t equals
+ *              one of the selected_count entries of transform_indices that is not ~0u.  selected_count == 0 selects nothing and
+ *              transform_indices is not looked at.
+ *   M2. store     (:63)  The engine's R8 `selection_silhouette_mask` is here one bit per pixel: bit x % 64 of word x / 64 of row y of
+ *              mask_bits, u64 [height][ceil(width / 64)]; the bits past `width` in a row's last word are written as zero.  When
+ *              mask_attachment is not null it receives the engine's image as well, u8 [height][width], 255 for selected and 0 otherwise.
+ * Stage OXC_HIGHLIGHT_COMPOSITE (highlight_dilate_horizontal.slang, highlight_composite.slang), per pixel (x, y); mask(x, y) is the bit of
+ * mask_bits (bits past `width` in a row's last word are ignored):
+ *   H1. dilation  (highlight_dilate_horizontal.slang:26-35, highlight_composite.slang:33-41)  rx = max(1, dilate_radius), ry = max(1,
+ *              outline_width);  dilated = any mask bit in [x - rx, x + rx] x [y - ry, y + ry] cut to the image.  Cutting equals the
+ *              Slang's clamped loads: a clamped tap repeats an edge pixel the window already holds, and the maximum of the rows' maxima
+ *              is the maximum over the rectangle.  Stated limit, the Slang has none: rx and ry are at most 255.  The engine's
+ *              `temp_horiz_dilated_mask` has no other reader and is not produced.
+ *   H2. edge      (:44-45)  edge = dilated && !mask(x, y).  This is the Slang's max_mask - center_mask > 0.01 exactly: both are 0.0 or 1.0.
+ *   H3. back      (:47)  Stated rule: the linear sampler at the pixel centre of an image of the same extent is the load of texel (x, y) of
+ *              color_attachment.  color_format as oxc_apply_tonemap's output_format (0: R8G8B8A8 Srgb, 1: B8G8R8A8 Srgb, 2: R8G8B8A8
+ *              Unorm).  The Srgb formats decode a colour byte as oxc_apply_debug_view's Albedo rule (oxc_apply_pbr step 2); format 2 and
+ *              every alpha byte are f32(byte) / 255.0f.
+ *   H4. outline   (:49-64)  only when edge.  is_occluded = depth(x, y) > 0.00001f (a NaN is not occluded).  final_outline =
+ *              (srgb_to_linear(outline_color.rgb), outline_color.a), srgb_to_linear as written at common/color.slang:75-77: c < 0.04045f
+ *              ? c / 12.92f : pow(|c + 0.055f| / 1.055f, 2.4f) -- a strict comparison, unlike the decode's -- evaluated once on the host.
+ *              is_occluded and occluded_mode == 0: the back colour.  is_occluded and occluded_mode == 1: back + (final_outline - back) *
+ *              0.35f per channel, alpha included.  Everything else, any other mode value included: final_outline.
+ *   H5. blend     Stated rule (the vuk headers that define them are not part of the reference tree): the pass draws with
+ *              vuk::BlendPreset::eAlphaBlend -- colour factors SrcAlpha / OneMinusSrcAlpha, alpha factors One / OneMinusSrcAlpha -- onto an
+ *              image cleared to vuk::Black<f32>, taken as (0, 0, 0, 1).  src is the outline colour of H4 for an edge pixel and the back
+ *              colour for every other.  out.rgb = src.rgb * src.a per channel: the destination term 0 * (1 - src.a) is dropped (stated; it
+ *              differs only for a non-finite alpha).  out.a = src.a + (1.0f - src.a).  The store is oxc_apply_tonemap step 11 for
+ *              color_format, a NaN stores 0.  A pixel that is no edge and whose alpha byte is 255 comes back with its four bytes
+ *              (tests/test_highlight_model.py shows it for every byte and format), so the kernel copies such words.
+ * Inputs: an input the selected stages do not read is not read, not checked and may be null.  The mask reads visbuffer_attachment,
+ * transform_indices (selected_count > 0) and the frame's meshlet_instances_buffer and mesh_instances_buffer; the composite reads mask_bits,
+ * depth_attachment and color_attachment.
+ * Limits (else OXC_INVALID_ARG, nothing launched, nothing written; the first broken rule in this order gives the message, each has its
+ * own): struct_size; stages non-zero with no unknown bit; width and height non-zero and at most 65536; color_format 0 .. 2 and rx, ry at
+ * most 255 (composite); the depth attachment one R32F level at offset 0 of width x height (composite); `frame` non-null (mask); then
+ * every buffer the stages touch in the order of the context's fields, then the frame's two -- non-null (mask_attachment may be), then
+ * aligned (mask_bits 8 bytes, mask_attachment 1, the others 4), then large enough (one texel per pixel; selected_count u32; height *
+ * ceil(width / 64) u64; meshlet_instance_count records of 8 bytes; mesh_instances_buffer as given); then no buffer a stage writes shares
+ * a byte with another buffer the call touches.  Floats are taken as given, NaN included.  One launch per stage, no scratch beyond the
+ * caller's mask_bits, no allocation, no host synchronisation; capturable into a HIP graph. */
+typedef struct oxc_pick_context {
+  uint32_t struct_size; /* sizeof(oxc_pick_context) */
+  uint32_t width, height;
+  uint32_t x, y;                    /* the picking texel */
+  uint32_t terrain_transform_index; /* P */
+  uint32_t meshlet_instance_count;  /* P */
+  oxc_buffer visbuffer_attachment;  /* in: u32[height][width] */
+  oxc_buffer transform_id;          /* out: one u32 */
+} oxc_pick_context;
+
+oxc_status oxc_pick_transform(oxc_ctx* ctx, const oxc_prepared_frame* frame, const oxc_pick_context* context, void* hip_stream);
+
+#define OXC_HIGHLIGHT_MASK 1u
+#define OXC_HIGHLIGHT_COMPOSITE 2u
+typedef struct oxc_highlight_context {
+  uint32_t struct_size; /* sizeof(oxc_highlight_context) */
+  uint32_t stages;      /* OXC_HIGHLIGHT_* */
+  uint32_t width, height;
+  uint32_t color_format;            /* H3, H5: 0: R8G8B8A8 Srgb;  1: B8G8R8A8 Srgb;  2: R8G8B8A8 Unorm */
+  uint32_t terrain_transform_index; /* P */
+  uint32_t meshlet_instance_count;  /* P */
+  uint32_t selected_count;          /* M1 */
+  float outline_color[4];           /* H4: (1.0, 0.53, 0.0, 1.0), ViewportPanel.cpp:1307 */
+  int32_t dilate_radius;            /* H1: 8, the horizontal radius (ViewportPanel.cpp:1273) */
+  int32_t outline_width;            /* H1: 5, the vertical radius */
+  int32_t occluded_mode;            /* H4: 0 hide behind walls, 1 faded behind walls, 2 always visible (the engine's value) */
+  oxc_buffer visbuffer_attachment;  /* mask in: u32[height][width] */
+  oxc_buffer transform_indices;     /* mask in: u32[selected_count] */
+  oxc_buffer mask_bits;             /* mask out, composite in: u64[height][ceil(width / 64)] */
+  oxc_buffer mask_attachment;       /* mask out, may be null: u8[height][width] */
+  oxc_image depth_attachment;       /* composite in: R32F, levels = 1 */
+  oxc_buffer color_attachment;      /* composite in: u32[height][width], what oxc_apply_tonemap wrote */
+  oxc_buffer dst_attachment;        /* composite out: u32[height][width], color_format */
+} oxc_highlight_context;
+
+oxc_status oxc_apply_highlight(oxc_ctx* ctx, const oxc_prepared_frame* frame, const oxc_highlight_context* context, void* hip_stream);
 
 /* ---- multi-GPU exchange: one process per GPU, RCCL over xGMI ---------------------------
  * The meshlet-instance array shards by contiguous range and every rank culls its shard on its own; the only

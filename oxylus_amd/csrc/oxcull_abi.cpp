@@ -16,6 +16,7 @@
 //   oxcull_abi_post.cpp   eye adaptation, bloom, tonemap, FXAA, the sky LUTs
 //   oxcull_abi_terrain.cpp the terrain map producers, the terrain brush and the terrain decode
 //   oxcull_abi_debug.cpp  the debug views
+//   oxcull_abi_editor.cpp the editor's selection path: the transform pick and the selection highlight
 //   oxcull_abi_comm.cpp   the RCCL exchange
 #include <new>
 

@@ -865,6 +865,41 @@ struct DebugViewVsmArgs {  // OXC_DEBUG_VIEW_RMVSM
   float lvl_thr[16];
 };
 void launch_debug_view_vsm(const DebugViewVsmArgs& a, hipStream_t s);
+// oxcull_highlight.hip: the editor's selection path (oxc_pick_transform, oxc_apply_highlight)
+struct HighlightRecords {  // what resolves a visbuffer texel to a transform index
+  const uint32_t* vis;     // u32 [h][w]
+  const GpuMeshletInstance* meshlet_instances;
+  const GpuMeshInstance* mesh_instances;
+  uint32_t w, h, meshlet_instance_count, terrain_transform_index;
+};
+struct PickArgs {
+  HighlightRecords r;
+  uint32_t x, y;
+  uint32_t* out;
+};
+void launch_pick_transform(const PickArgs& a, hipStream_t s);
+struct HighlightMaskArgs {
+  HighlightRecords r;
+  const uint32_t* selected;  // transform_indices[selected_count]
+  uint32_t selected_count;
+  uint64_t* mask_bits;       // u64 [h][ceil(w / 64)]
+  uint8_t* mask_attachment;  // u8 [h][w] or null
+};
+void launch_highlight_mask(const HighlightMaskArgs& a, hipStream_t s);
+struct HighlightCompositeArgs {
+  const uint64_t* mask_bits;
+  const float* depth;
+  const uint32_t* color;
+  uint32_t* dst;
+  uint32_t w, h, format;
+  uint32_t rx, ry;      // H1: max(1, dilate_radius), max(1, outline_width)
+  int32_t occluded_mode;
+  float outline[4];     // H4: final_outline, evaluated by highlight_outline_linear
+};
+void highlight_outline_linear(const float* outline_color, float* final_outline);
+void launch_highlight_composite(const HighlightCompositeArgs& a, hipStream_t s);
+// the pow rule on the host (oxcull_tonemap.hip keeps the host's copy of the log2 rule)
+float pow_rule_host(float v, float p);
 // oxcull_bounds.hip: meshlet bounds producer
 void launch_build_meshlet_bounds(const float* pos, uint32_t vertex_count, const void* meshlets, uint32_t meshlet_count, const uint32_t* vidx,
                                  const uint8_t* micro, void* out_bounds, float* out_mesh6, void* out_qpos, float* meshlet_minmax, float* normals,

@@ -124,6 +124,12 @@ OXC_DEV uint32_t srgb_unorm(float x) {
   return pack_unorm(e);
 }
 
+// the sRGB encoding of one colour channel before its unorm8 store (oxc_apply_tonemap step 11; the highlight composite stores by it too)
+OXC_DEV float srgb_encode(float c) {
+  c = saturate_f(c);
+  return c <= 0.0031308f ? c * 12.92f : 1.055f * pow_rule(c, 0.4166666666666667f) - 0.055f;
+}
+
 // one channel of the sRGB decode (oxc_apply_pbr step 2; the Albedo debug view reads by it too)
 OXC_DEV float srgb_decode(uint32_t byte) {
   const float c = (float)byte / 255.0f;

@@ -93,6 +93,8 @@ XY lerp_xy(XY a, XY b, float t) { return {a.x + (b.x - a.x) * t, a.y + (b.y - a.
 }  // namespace host_rules
 }  // namespace
 
+float pow_rule_host(float v, float p) { return host_rules::pow_rule(v, p); }
+
 void tonemap_constants(float chromatic_aberration_amount, TonemapConstants& k) {
   using host_rules::M3;
   using host_rules::XY;
@@ -311,11 +313,6 @@ OXC_DEV float film_grain(uint32_t px, uint32_t py, const TonemapArgs& a) {
   const float f_x = P_x - (Pi_x - v), f_y = P_y - (Pi_y - v);
   const float length = __builtin_sqrtf(f_x * f_x + f_y * f_y);
   return 1.0f - 2.0f * exp2_rule((-length) * 3.0f);
-}
-
-OXC_DEV float srgb_encode(float c) {
-  c = saturate_f(c);
-  return c <= 0.0031308f ? c * 12.92f : 1.055f * pow_rule(c, 0.4166666666666667f) - 0.055f;
 }
 }  // namespace
 

@@ -176,6 +176,31 @@ struct DebugContext {
   Buffer debug_attachment = {};
 };
 
+// The editor's selection path (OxylusEditor/src/Panels/ViewportPanel.cpp:1166-1556).  The reference keeps these values in lambda captures and
+// push-constant blocks; the names are its own.  HighlightContext: highlight_mask_stage's transform_indices and terrain_transform_index, the
+// shared `silhouette_mask` (here one bit per pixel, mask_bits, with the R8 image optional), and highlight_composite_stage's push constants
+// and attachments; outlined_composite, which the reference declares inside the pass, is caller-owned.
+struct HighlightContext {
+  Buffer transform_indices = {};  // u32 per selected transform
+  uint32_t terrain_transform_index = ~0u;
+  Buffer visbuffer_attachment = {};
+  Buffer silhouette_mask_bits = {};  // u64 [height][ceil(width / 64)]
+  Buffer silhouette_mask = {};       // optional: the R8 image
+  ImageAttachment depth_attachment = {};
+  float outline_color[4] = {1.0f, 0.53f, 0.0f, 1.0f};
+  int32_t dilate_radius = 8;
+  int32_t outline_width = 5;
+  int32_t occluded_mode = 2;  // OccludeMode::AlwaysVisible
+  Buffer outlined_composite = {};
+};
+// mouse_picking_stages: the texel under the cursor and the u32 the pass writes
+struct PickingContext {
+  uint32_t picking_texel[2] = {0, 0};
+  uint32_t terrain_transform_index = ~0u;
+  Buffer visbuffer_attachment = {};
+  Buffer transform_id = {};
+};
+
 struct PostProcessContext {
   float delta_time = 0.0f;
   Extent3D extent = {};
@@ -688,6 +713,47 @@ public:
     check(oxc_apply_debug_view(ctx_, &f, &c, stream_));
     return context.debug_attachment;
   }
+  // The editor's mouse_picking stage (ViewportPanel.cpp:1439-1497): the transform index behind context.picking_texel into
+  // context.transform_id.  Rules: include/oxcull.h, oxc_pick_transform.
+  auto pick_transform(PickingContext& context, Extent3D extent) -> Buffer {
+    const oxc_prepared_frame f = record_frame();
+    oxc_pick_context c = {};
+    c.struct_size = sizeof c;
+    c.width = extent.width, c.height = extent.height;
+    c.x = context.picking_texel[0], c.y = context.picking_texel[1];
+    c.terrain_transform_index = context.terrain_transform_index;
+    c.meshlet_instance_count = static_cast<uint32_t>(prepared_frame.meshlet_instances_buffer.bytes / 8u);
+    c.visbuffer_attachment = context.visbuffer_attachment;
+    c.transform_id = context.transform_id;
+    check(oxc_pick_transform(ctx_, &f, &c, stream_));
+    return context.transform_id;
+  }
+  // The editor's highlight_mask_stage and highlight_composite_stage (ViewportPanel.cpp:1166-1345) as the stages of `stages`
+  // (OXC_HIGHLIGHT_MASK after the visbuffer is drawn, OXC_HIGHLIGHT_COMPOSITE after apply_tonemap): the outline of the selected transforms
+  // over original_result_attachment, an image of `dst_format` as apply_tonemap wrote it, into context.outlined_composite.  Rules:
+  // include/oxcull.h, oxc_apply_highlight.
+  auto apply_highlight(HighlightContext& context, uint32_t stages, Extent3D extent, Buffer original_result_attachment = {}, uint32_t dst_format = 0) -> Buffer {
+    const oxc_prepared_frame f = record_frame();
+    oxc_highlight_context c = {};
+    c.struct_size = sizeof c;
+    c.stages = stages;
+    c.width = extent.width, c.height = extent.height;
+    c.color_format = dst_format;
+    c.terrain_transform_index = context.terrain_transform_index;
+    c.meshlet_instance_count = static_cast<uint32_t>(prepared_frame.meshlet_instances_buffer.bytes / 8u);
+    c.selected_count = static_cast<uint32_t>(context.transform_indices.bytes / 4u);
+    for (int i = 0; i < 4; i++) c.outline_color[i] = context.outline_color[i];
+    c.dilate_radius = context.dilate_radius, c.outline_width = context.outline_width, c.occluded_mode = context.occluded_mode;
+    c.visbuffer_attachment = context.visbuffer_attachment;
+    c.transform_indices = context.transform_indices;
+    c.mask_bits = context.silhouette_mask_bits;
+    c.mask_attachment = context.silhouette_mask;
+    c.depth_attachment = context.depth_attachment;
+    c.color_attachment = original_result_attachment;
+    c.dst_attachment = context.outlined_composite;
+    check(oxc_apply_highlight(ctx_, &f, &c, stream_));
+    return context.outlined_composite;
+  }
   auto build_meshlet_bounds(oxc_meshlet_bounds_desc desc) -> void {
     desc.struct_size = sizeof desc;
     check(oxc_build_meshlet_bounds(ctx_, &desc, stream_));
@@ -701,6 +767,15 @@ public:
   oxc_ctx* native() { return ctx_; }
 
 private:
+  // the record buffers the editor's passes resolve a visbuffer texel with
+  oxc_prepared_frame record_frame() const {
+    oxc_prepared_frame f = {};
+    f.mesh_instance_count = prepared_frame.mesh_instance_count;
+    f.max_meshlet_instance_count = prepared_frame.max_meshlet_instance_count;
+    f.mesh_instances_buffer = prepared_frame.mesh_instances_buffer;
+    f.meshlet_instances_buffer = prepared_frame.meshlet_instances_buffer;
+    return f;
+  }
   void check(oxc_status st) {
     if (st != OXC_OK) throw std::runtime_error(std::string("oxcull: ") + oxc_last_error(ctx_));
   }

@@ -121,5 +121,18 @@ int main(int argc, char**) {
   } catch (const std::exception& e) {
     std::printf("expected (no attachments bound): %s\n", e.what());
   }
+  try {  // ViewportPanel.cpp:1439-1556: the editor's pick behind VisBufferEncode, its mask there and its composite behind PostProcessing
+    auto picking_context = PickingContext{.picking_texel = {3, 5}};
+    (void)self.pick_transform(picking_context, Extent3D{.width = 16, .height = 16});
+  } catch (const std::exception& e) {
+    std::printf("expected (no attachments bound): %s\n", e.what());
+  }
+  try {
+    auto highlight_context = HighlightContext{.terrain_transform_index = 7, .outline_width = 5, .occluded_mode = 2};
+    self.apply_highlight(highlight_context, OXC_HIGHLIGHT_MASK, Extent3D{.width = 16, .height = 16});
+    (void)self.apply_highlight(highlight_context, OXC_HIGHLIGHT_COMPOSITE, Extent3D{.width = 16, .height = 16}, Buffer{}, /*dst_format*/ 1);
+  } catch (const std::exception& e) {
+    std::printf("expected (no attachments bound): %s\n", e.what());
+  }
   return 0;
 }

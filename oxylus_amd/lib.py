@@ -50,6 +50,7 @@ LIGHT_KIND_DIRECTIONAL, LIGHT_KIND_POINT, LIGHT_KIND_SPOT = 0, 1, 2  # GPU::Ligh
 TERRAIN_GENERATE, TERRAIN_DERIVE, TERRAIN_MINMAX, TERRAIN_ALL = 1, 2, 4, 7  # oxc_terrain_maps_context.stages
 TERRAIN_BRUSH_TRACE, TERRAIN_BRUSH_APPLY, TERRAIN_BRUSH_ALL = 1, 2, 3  # oxc_terrain_brush_context.stages
 TERRAIN_INVALID_LAYER_MATERIAL = 0xFFFFFFFF  # scene.slang:632
+HIGHLIGHT_MASK, HIGHLIGHT_COMPOSITE, HIGHLIGHT_ALL = 1, 2, 3  # oxc_highlight_context.stages
 # GPU::DebugView (scene.slang:10-26; RMVSM from SceneGPU.hpp:44), oxc_debug_view_context.debug_view
 (DEBUG_VIEW_TRIANGLES, DEBUG_VIEW_MESHLETS, DEBUG_VIEW_OVERDRAW, DEBUG_VIEW_MATERIALS, DEBUG_VIEW_MESH_INSTANCES, DEBUG_VIEW_MESH_LODS, DEBUG_VIEW_ALBEDO,
  DEBUG_VIEW_NORMAL, DEBUG_VIEW_EMISSIVE, DEBUG_VIEW_METALLIC, DEBUG_VIEW_ROUGHNESS, DEBUG_VIEW_BAKED_OCCLUSION, DEBUG_VIEW_GTAO, DEBUG_VIEW_GEOMETRIC_NORMAL,
@@ -827,6 +828,46 @@ class DebugViewContext(C.Structure):
     ]
 
 
+class PickContext(C.Structure):
+    _c_name_ = "oxc_pick_context"
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("x", C.c_uint32),
+        ("y", C.c_uint32),
+        ("terrain_transform_index", C.c_uint32),
+        ("meshlet_instance_count", C.c_uint32),
+        ("visbuffer_attachment", Buffer),
+        ("transform_id", Buffer),
+    ]
+
+
+class HighlightContext(C.Structure):
+    _c_name_ = "oxc_highlight_context"
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("stages", C.c_uint32),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("color_format", C.c_uint32),
+        ("terrain_transform_index", C.c_uint32),
+        ("meshlet_instance_count", C.c_uint32),
+        ("selected_count", C.c_uint32),
+        ("outline_color", C.c_float * 4),
+        ("dilate_radius", C.c_int32),
+        ("outline_width", C.c_int32),
+        ("occluded_mode", C.c_int32),
+        ("visbuffer_attachment", Buffer),
+        ("transform_indices", Buffer),
+        ("mask_bits", Buffer),
+        ("mask_attachment", Buffer),
+        ("depth_attachment", Image),
+        ("color_attachment", Buffer),
+        ("dst_attachment", Buffer),
+    ]
+
+
 class MeshBuildDesc(C.Structure):
     _c_name_ = "oxc_mesh_build_desc"
     _fields_ = [("struct_size", C.c_uint32), ("vertex_count", C.c_uint32), ("index_count", C.c_uint32), ("max_lods", C.c_uint32), ("max_vertices", C.c_uint32),
@@ -896,6 +937,8 @@ PROTOTYPES = {
     "oxc_apply_terrain_brush": (_status, [_vp, _P(TerrainBrushContext), _vp]),
     "oxc_decode_terrain": (_status, [_vp, _P(TerrainDecodeContext), _vp]),
     "oxc_apply_debug_view": (_status, [_vp, _P(PreparedFrame), _P(DebugViewContext), _vp]),
+    "oxc_pick_transform": (_status, [_vp, _P(PreparedFrame), _P(PickContext), _vp]),
+    "oxc_apply_highlight": (_status, [_vp, _P(PreparedFrame), _P(HighlightContext), _vp]),
     "oxc_draw_physical_pages": (_status, [_vp, _P(PreparedFrame), _P(VsmDrawContext), _vp]),
     "oxc_debug_vsm_draw_stats": _stats,
     "oxc_resolve_shadowmap": (_status, [_vp, _P(ShadowResolveContext), _vp]),

@@ -1035,6 +1035,66 @@ class DebugViewContext(Marshalled):
 
 
 @dataclass
+class PickingContext(Marshalled):
+    """oxc_pick_context: the editor's `mouse_picking` stage (ViewportPanel.cpp:1439-1497, editor/mouse_picking.slang): the transform index
+    behind visbuffer texel `picking_texel`, one u32 into `transform_id`.  The record buffers come from the renderer's prepared_frame."""
+    _ctype = L.PickContext
+    _derived = {"x": lambda self: int(self.picking_texel[0]), "y": lambda self: int(self.picking_texel[1])}
+    visbuffer_attachment: torch.Tensor      # int32 [H, W]
+    width: int
+    height: int
+    picking_texel: tuple
+    terrain_transform_index: int
+    meshlet_instance_count: int
+    transform_id: torch.Tensor              # int32 [1] out
+
+    @staticmethod
+    def over(visbuffer: torch.Tensor, picking_texel, terrain_transform_index: int, meshlet_instance_count: int, transform_id: Optional[torch.Tensor] = None) -> "PickingContext":
+        out = torch.zeros(1, dtype=torch.int32, device=visbuffer.device) if transform_id is None else transform_id
+        return PickingContext(visbuffer, visbuffer.shape[1], visbuffer.shape[0], tuple(picking_texel), terrain_transform_index, meshlet_instance_count, out)
+
+
+@dataclass
+class HighlightContext(Marshalled):
+    """oxc_highlight_context: the editor's highlight_mask_stage and highlight_composite_stage (ViewportPanel.cpp:1166-1345; editor/
+    highlight_mask.slang, highlight_dilate_horizontal.slang, highlight_composite.slang).  `stages` selects the mask (after the visbuffer is
+    drawn), the composite (after the tonemap) or both; only what they read has to be given (include/oxcull.h, oxc_apply_highlight).
+    `transform_indices` is the selection, `mask_bits` the one-bit-per-pixel silhouette mask the two stages share."""
+    _ctype = L.HighlightContext
+    _derived = {"selected_count": lambda self: 0 if self.transform_indices is None else self.transform_indices.numel()}
+    stages: int
+    width: int
+    height: int
+    mask_bits: Optional[torch.Tensor]                    # int64 [H, ceil(W / 64)]
+    visbuffer_attachment: Optional[torch.Tensor] = None  # int32 [H, W]
+    transform_indices: Optional[torch.Tensor] = None     # int32 [selected_count]
+    terrain_transform_index: int = 0xFFFFFFFF
+    meshlet_instance_count: int = 0
+    mask_attachment: Optional[torch.Tensor] = None       # uint8 [H, W] out: the engine's R8 image, optional
+    depth_attachment: Optional[ImageAttachment] = None   # R32F, levels = 1
+    color_attachment: Optional[torch.Tensor] = None      # int32 [H, W]: what apply_tonemap wrote
+    dst_attachment: Optional[torch.Tensor] = None        # int32 [H, W] out
+    color_format: int = 0                                # the tonemap's output_format
+    outline_color: tuple = (1.0, 0.53, 0.0, 1.0)
+    dilate_radius: int = 8
+    outline_width: int = 5
+    occluded_mode: int = 2
+
+    @staticmethod
+    def mask_words(width: int, height: int, device="cuda") -> torch.Tensor:
+        return torch.zeros((height, (width + 63) // 64), dtype=torch.int64, device=device)
+
+    @staticmethod
+    def over(visbuffer: torch.Tensor, transform_indices, meshlet_instance_count: int, depth: ImageAttachment, color: torch.Tensor, color_format: int = 0,
+             **settings) -> "HighlightContext":
+        """Both stages over a drawn visbuffer and a tonemapped image; allocates mask_bits and dst_attachment."""
+        H, W = visbuffer.shape
+        return HighlightContext(L.HIGHLIGHT_ALL, W, H, HighlightContext.mask_words(W, H, visbuffer.device), visbuffer_attachment=visbuffer,
+                                transform_indices=transform_indices, meshlet_instance_count=meshlet_instance_count, depth_attachment=depth, color_attachment=color,
+                                dst_attachment=torch.zeros_like(color), color_format=color_format, **settings)
+
+
+@dataclass
 class VisbufferDecodeContext(Marshalled):
     """oxc_decode_context: RendererInstance::decode_visbuffer (Passes/DrawGeometry.cpp:192-274), the geometry and material-factor half of
     visbuffer_decode.slang.  `create` takes the visbuffer and the depth as oxc_draw_visbuffer resolved them, the matrix they were drawn with and
@@ -1380,6 +1440,16 @@ class RendererInstance:
         (include/oxcull.h, oxc_apply_debug_view).  The prepared frame is passed when there is one; only the Materials, MeshInstances and
         MeshLods views read it."""
         self._call("oxc_apply_debug_view", context, stream, frame="optional")
+
+    def pick_transform(self, context: PickingContext, stream=None) -> None:
+        """ViewportPanel.cpp:1439-1497 (mouse_picking): the transform index behind `context.picking_texel` into `context.transform_id`, one
+        launch (include/oxcull.h, oxc_pick_transform)."""
+        self._call("oxc_pick_transform", context, stream, frame=True)
+
+    def apply_highlight(self, context: HighlightContext, stream=None) -> None:
+        """ViewportPanel.cpp:1166-1345 (highlight_mask_stage, highlight_composite_stage): the stages of `context.stages`, one launch each
+        (include/oxcull.h, oxc_apply_highlight).  The prepared frame is passed when there is one; only the mask stage needs it."""
+        self._call("oxc_apply_highlight", context, stream, frame="optional")
 
     def generate_terrain_maps(self, context: TerrainMapsContext, stream=None) -> None:
         """Scene/Terrain.cpp:406-461 and Passes/Terrain.cpp:134-156 (terrain_generate, terrain_derive, terrain_minmax): the stages of
