@@ -307,7 +307,14 @@ oxc_status oxc_read_counters(oxc_ctx* ctx, const oxc_cull_geometry_context* cont
  * vertices -> meshopt_quantizeHalf, normal cone of meshopt_computeMeshletBounds -> cone_axis_s8 /
  * cone_cutoff_s8, running mesh AABB) and the position quantisation of :573-578.  meshopt_buildMeshlets itself
  * (the greedy clusteriser that produces `meshlets`, `indirect_vertex_indices`, `local_triangle_indices`) stays
- * on the host, as in the reference.  All pointers are device pointers. */
+ * on the host, as in the reference.  All pointers are device pointers.
+ * NaN normals (a cross product that overflowed to inf - inf at coordinates around 1e20, NaN coordinates) count as valid
+ * triangles, since `area == 0` is false.  Every compare with a NaN is false, so they are never extremal, never grow the
+ * sphere and never lower the minimum dot; a meshlet whose other normals fix the axis gets the cone of those.  Where the NaN
+ * reaches the axis (every normal NaN, or the first one with no other to replace it) the minimum dot stays 1, each NaN axis
+ * component is stored as cone_axis_s8 = -127 (meshopt_quantizeSnorm clamps before it converts: NaN -> -1), and
+ * cone_cutoff_s8 = 0: the sum of the quantisation errors is NaN, and its float -> int conversion gives 0 (v_cvt_i32_f32).
+ * NaN coordinates never enter an AABB (`b < a ? b : a` keeps a). */
 typedef struct oxc_meshlet_bounds_desc {
   uint32_t struct_size;
   uint32_t vertex_count;

@@ -92,6 +92,8 @@ enum { OXC_TUNE_ASYNC_MTEST_BLOCKS_PER_CU = 0, OXC_TUNE_ASYNC_TRI_BLOCKS_PER_CU 
        OXC_TUNE_EYE_ADAPTATION_GRID = 15 /* cap of oxc_apply_eye_adaptation's histogram kernel in blocks; 0 (default): uncapped (four blocks per CU).  With it a small image makes every block run its stride loop several times.  Same outputs either way */,
        OXC_TUNE_RASTER_GRID = 18 /* cap, in blocks, of every launch of oxc_draw_visbuffer; 0 (default): uncapped (eight blocks per CU; 256 for the clip queue's kernel).  It takes effect at the next draw.  With it a small triangle list makes every wave run its stride loop several times.  Same outputs either way */,
        OXC_TUNE_VSM_DRAW_GRID = 19 /* cap, in blocks, of every launch of oxc_draw_physical_pages (the prologue's x extent, the rows kernel and the clip queue's kernel included); 0 (default): uncapped (eight blocks per CU; 256 for the clip queue's kernel).  It takes effect at the next draw.  With it a small frame makes every wave run its stride loop several times.  Same outputs either way */,
+       OXC_TUNE_BOUNDS_GRID = 20 /* cap, in blocks, of every grid-stride launch of oxc_build_meshlet_bounds and oxc_quantize_vertex_streams (the quantisers, the gather kernel and the mesh fold's partial kernel, whose block count the final fold then reads; the cone kernel runs a thread per meshlet and the final fold one block, so neither has a grid to cap); 0 (default): uncapped (eight blocks per CU for the quantisers, sixteen for the gather kernel, 256 partial blocks).  It takes effect at the next call.  With it a small mesh makes every wave and every fold thread run its stride loop several times.  Same outputs either way */,
+       OXC_TUNE_BOUNDS_CHUNK = 21 /* meshlets per gather / cone launch pair of oxc_build_meshlet_bounds; 0 (default): 2^18.  Only the loop's step: the scratch keeps the layout and size of the default, so a value above 2^18 (or above the rows the scratch holds) is clamped.  It takes effect at the next call.  With it a small mesh is processed in several chunks with a ragged last one.  Same outputs either way */,
        OXC_TUNE_FXAA_STATS = 17/* 1: oxc_apply_fxaa runs its counting instantiation (oxc_debug_fxaa_stats); 0 (default): off */,
        OXC_TUNE_BLOOM_TAIL_LEVEL = 16 /* the level T from which oxc_apply_bloom's one-block tail kernel takes over (downsample levels T .. L - 1, upsample levels back to T); 0 (default): chosen by the library; a value >= L: no tail kernel, one launch per level.  A forced T is raised to the first level whose source level has at most 16 384 texels (64 per thread of the one block), so the knob cannot turn a large image into one long single-block kernel.  Same outputs either way */ };
 oxc_status oxc_debug_set_tuning(oxc_ctx* ctx, uint32_t knob, uint32_t value);

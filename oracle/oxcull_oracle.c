@@ -1098,7 +1098,13 @@ void orc_build_meshlet_bounds(const float* positions, uint32_t vertex_count, con
         float e0 = fabsf((float)axis_s8[0] / 127.0f - axis[0]);
         float e1 = fabsf((float)axis_s8[1] / 127.0f - axis[1]);
         float e2 = fabsf((float)axis_s8[2] / 127.0f - axis[2]);
-        int c = (int)(127.0f * (((cone_cutoff + e0) + e1) + e2) + 1.0f); /* rounded up, not to nearest */
+        /* Rounded up, not to nearest.  NaN normals (a cross product that overflowed to inf - inf, NaN coordinates) that reach the
+         * axis leave mindp at 1 -- every compare with a NaN is false --, so cone_cutoff is 0, each NaN axis component quantises to
+         * -127 (quantize_snorm clamps before it converts) and its error term is NaN.  The conversion of that NaN is undefined in
+         * C; the rule (include/oxcull.h) is the device's v_cvt_i32_f32: NaN -> 0, so the cutoff byte is 0.  The sum is otherwise
+         * finite (cone_cutoff <= 1, each error <= 2), far inside int. */
+        float cf = 127.0f * (((cone_cutoff + e0) + e1) + e2) + 1.0f;
+        int c = (cf != cf) ? 0 : (int)cf;
         cutoff_s8 = (c > 127) ? 127 : (int8_t)c;
       }
     }

@@ -29,12 +29,13 @@ oxc_status oxc_build_meshlet_bounds(oxc_ctx* ctx, const oxc_meshlet_bounds_desc*
   const uint32_t chunk = std::min(kBoundsChunk, ctx->bounds_scratch_cap);
   float* fold = ctx->bounds_scratch + align_up((size_t)ctx->bounds_scratch_cap * 24u, 256) / 4;
   float* normals = fold + 256 * 12;
+  const uint32_t step = ctx->bounds_chunk ? std::min(ctx->bounds_chunk, chunk) : chunk;  // OXC_TUNE_BOUNDS_CHUNK: the loop's step only; the rows stay laid out for `chunk`
   {
     KernelTimer t(ctx, OXC_K_MESHLET_BOUNDS, s);
     launch_build_meshlet_bounds(static_cast<const float*>(d->positions.dptr), d->vertex_count, d->meshlets.dptr, d->meshlet_count,
                                 static_cast<const uint32_t*>(d->indirect_vertex_indices.dptr), static_cast<const uint8_t*>(d->local_triangle_indices.dptr),
                                 d->meshlet_bounds.dptr, static_cast<float*>(d->mesh_bounds.dptr), d->quantized_positions.dptr, ctx->bounds_scratch, normals,
-                                reinterpret_cast<uint32_t*>(normals + (size_t)chunk * 192), fold, chunk, ctx->num_cus * 8, s);
+                                reinterpret_cast<uint32_t*>(normals + (size_t)chunk * 192), fold, step, ctx->num_cus * 8, ctx->bounds_grid, s);
   }
   OXC_HIP(ctx, hipGetLastError());
   return OXC_OK;
@@ -54,9 +55,10 @@ oxc_status oxc_quantize_vertex_streams(oxc_ctx* ctx, const oxc_vertex_streams_de
   for (const Stream& st : streams)
     if (st.in->dptr && n && (!st.out->dptr || st.in->bytes < n * st.in_stride || st.out->bytes < n * st.out_stride)) return fail(ctx, OXC_INVALID_ARG, st.what);
   OXC_ENTER(ctx, hip_stream, s);
+  const uint32_t full_grid = ctx->num_cus * 8;
   launch_quantize_vertex_streams(static_cast<const float*>(d->positions.dptr), static_cast<const float*>(d->normals.dptr),
                                  static_cast<const float*>(d->texcoords.dptr), d->vertex_count, d->quantized_positions.dptr, d->quantized_normals.dptr,
-                                 d->quantized_texcoords.dptr, ctx->num_cus * 8, s);
+                                 d->quantized_texcoords.dptr, ctx->bounds_grid ? std::min(ctx->bounds_grid, full_grid) : full_grid, s);  // OXC_TUNE_BOUNDS_GRID
   OXC_HIP(ctx, hipGetLastError());
   return OXC_OK;
 }

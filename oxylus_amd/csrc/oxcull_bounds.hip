@@ -123,7 +123,7 @@ __global__ __launch_bounds__(256) void k_quantize_texcoords(const float2* __rest
 }
 
 void launch_quantize_vertex_streams(const float* pos, const float* nrm, const float* uv, uint32_t vertex_count, void* out_qpos, void* out_qnrm,
-                                    void* out_quv, uint32_t max_grid, hipStream_t s) {
+                                    void* out_quv, uint32_t max_grid /* already capped by OXC_TUNE_BOUNDS_GRID */, hipStream_t s) {
   if (!vertex_count) return;
   const dim3 grid(min((vertex_count + 255u) / 256u, max_grid));
   if (pos) hipLaunchKernelGGL(k_quantize_positions, grid, dim3(256), 0, s, pos, vertex_count, reinterpret_cast<uint2*>(out_qpos));
@@ -516,14 +516,17 @@ __global__ __launch_bounds__(256) void k_mesh_bounds_final(const float* __restri
 
 void launch_build_meshlet_bounds(const float* pos, uint32_t vertex_count, const void* meshlets, uint32_t meshlet_count, const uint32_t* vidx,
                                  const uint8_t* micro, void* out_bounds, float* out_mesh6, void* out_qpos, float* meshlet_minmax, float* normals,
-                                 uint32_t* normal_counts, float* fold_scratch /* 256 * 12 words */, uint32_t chunk, uint32_t max_grid, hipStream_t s) {
+                                 uint32_t* normal_counts, float* fold_scratch /* 256 * 12 words */, uint32_t chunk, uint32_t max_grid,
+                                 uint32_t grid_cap /* OXC_TUNE_BOUNDS_GRID: blocks, 0 = uncapped */, hipStream_t s) {
+  // k_meshlet_cone (a thread per meshlet, no stride loop) and the one-block final fold have nothing to cap
+  auto capped = [grid_cap](uint32_t blocks) { return (grid_cap && grid_cap < blocks) ? grid_cap : blocks; };
   if (out_qpos && vertex_count)
-    hipLaunchKernelGGL(k_quantize_positions, dim3(min((vertex_count + 255u) / 256u, max_grid)), dim3(256), 0, s, pos, vertex_count,
+    hipLaunchKernelGGL(k_quantize_positions, dim3(capped(min((vertex_count + 255u) / 256u, max_grid))), dim3(256), 0, s, pos, vertex_count,
                        reinterpret_cast<uint2*>(out_qpos));
   // the normals scratch (768 B per meshlet) is bounded by processing `chunk` meshlets at a time
   for (uint32_t first = 0; first < meshlet_count; first += chunk) {
     const uint32_t n = min(chunk, meshlet_count - first);
-    hipLaunchKernelGGL(k_meshlet_gather, dim3(min((n + 3u) / 4u, max_grid * 2u)), dim3(256), 0, s, pos, reinterpret_cast<const uint4*>(meshlets), first, n, vidx,
+    hipLaunchKernelGGL(k_meshlet_gather, dim3(capped(min((n + 3u) / 4u, max_grid * 2u))), dim3(256), 0, s, pos, reinterpret_cast<const uint4*>(meshlets), first, n, vidx,
                        micro, reinterpret_cast<uint4*>(out_bounds), meshlet_minmax, normals, normal_counts);
     hipLaunchKernelGGL(k_meshlet_cone, dim3((n + 255u) / 256u), dim3(256), 0, s, first, n, meshlet_minmax, normals, normal_counts,
                        reinterpret_cast<uint4*>(out_bounds));
@@ -531,8 +534,9 @@ void launch_build_meshlet_bounds(const float* pos, uint32_t vertex_count, const 
   // partials live behind the per-meshlet boxes (the caller sized meshlet_minmax for it)
   float* part_v = fold_scratch;
   uint32_t* part_i = reinterpret_cast<uint32_t*>(fold_scratch + kMeshFoldBlocks * 6);
-  hipLaunchKernelGGL(k_mesh_bounds_partial, dim3(kMeshFoldBlocks), dim3(256), 0, s, meshlet_minmax, meshlet_count, part_v, part_i);
-  hipLaunchKernelGGL(k_mesh_bounds_final, dim3(1), dim3(256), 0, s, part_v, part_i, kMeshFoldBlocks, out_mesh6);
+  const uint32_t parts = capped(kMeshFoldBlocks);  // the final fold reads exactly the partials that were written
+  hipLaunchKernelGGL(k_mesh_bounds_partial, dim3(parts), dim3(256), 0, s, meshlet_minmax, meshlet_count, part_v, part_i);
+  hipLaunchKernelGGL(k_mesh_bounds_final, dim3(1), dim3(256), 0, s, part_v, part_i, parts, out_mesh6);
 }
 
 }  // namespace oxc

@@ -80,6 +80,8 @@ struct oxc_ctx {
   // meshlets the compacted triangle normals (768 B each) and their counts
   float* bounds_scratch = nullptr;
   uint32_t bounds_scratch_cap = 0;
+  uint32_t bounds_grid = 0;   // OXC_TUNE_BOUNDS_GRID: cap of every grid-stride launch of the bounds producer and the stream quantiser in blocks, 0 = uncapped
+  uint32_t bounds_chunk = 0;  // OXC_TUNE_BOUNDS_CHUNK: meshlets per gather/cone launch pair, 0 = kBoundsChunk; the scratch layout does not follow it
   void* raster_scratch = nullptr;  // oxc_draw_visbuffer: list of large triangles + its counter
   uint32_t raster_capacity = 0;    // entries of the big / clip lists (the tile list has twice as many)
   uint32_t raster_capacity_request = 0;  // oxc_debug_set_tuning(OXC_TUNE_RASTER_BIG_CAPACITY): used by the first draw instead of the default

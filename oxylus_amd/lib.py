@@ -36,6 +36,8 @@ TUNE_BLOOM_TAIL_LEVEL = 16
 TUNE_FXAA_STATS = 17
 TUNE_RASTER_GRID = 18
 TUNE_VSM_DRAW_GRID = 19
+TUNE_BOUNDS_GRID = 20
+TUNE_BOUNDS_CHUNK = 21
 
 # GPU::SceneFlags bits oxc_apply_pbr reads (scene.slang:242-256)
 SCENE_HAS_DIRECTIONAL_LIGHT, SCENE_HAS_ATMOSPHERE, SCENE_HAS_CONTACT_SHADOWS, SCENE_HAS_SKY, SCENE_TRANSPARENT_BACKGROUND = 1 << 0, 1 << 1, 1 << 9, 1 << 10, 1 << 11

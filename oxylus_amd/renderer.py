@@ -1505,7 +1505,7 @@ class RendererInstance:
         return self._read_stats("raster", stream)
 
     def debug_set_tuning(self, knob: int, value: int):
-        """Harness knobs (L.TUNE_*): async stage grid caps, the raster queues' capacity (before the first draw)."""
+        """Harness knobs (L.TUNE_*): async stage grid caps, the raster queues' capacity (before the first draw), the bounds producer's grid cap and chunk."""
         self._check(self._lib.oxc_debug_set_tuning(self._ctx, knob, value))
 
     def debug_count_occlusion_candidates(self, counters):
