@@ -2277,7 +2277,7 @@ oxc_status oxc_apply_debug_view(oxc_ctx* ctx, const oxc_prepared_frame* frame, c
  * oxc_pick_transform is the `mouse_picking` stage and oxc_apply_highlight the `highlight_mask` and `entity_highlighting` stages of the
  * reference's editor (OxylusEditor/src/Panels/ViewportPanel.cpp:1166-1556: mouse_picking_stages, highlight_mask_stage,
  * highlight_composite_stage; shaders editor/mouse_picking.slang, highlight_mask.slang, highlight_dilate_horizontal.slang and
- * highlight_composite.slang).  Not built: mouse_picking_2d.slang (the library has no 2D pass).
+ * highlight_composite.slang).  mouse_picking_2d.slang is oxc_pick_sprite, in the block of oxc_draw_sprites below.
  * Arithmetic: the conventions of oxc_apply_debug_view's block -- binary32, round to nearest even, the Slang's order, no contraction, IEEE
  * division; saturate through fminf / fmaxf (saturate(NaN) = 0); a comparison with a NaN operand is false; pow by the pow rule of
  * oxc_apply_pbr (a base that is zero, negative, below 2^-126 or NaN has log2 -Inf).
@@ -2373,6 +2373,119 @@ typedef struct oxc_highlight_context {
 } oxc_highlight_context;
 
 oxc_status oxc_apply_highlight(oxc_ctx* ctx, const oxc_prepared_frame* frame, const oxc_highlight_context* context, void* hip_stream);
+
+/* ---- the 2D pass: sprites and particles between oxc_apply_pbr and oxc_apply_fxaa ------------------------------------------------------------
+ * oxc_draw_sprites is the 2D block of the reference's frame (RendererInstance.cpp:1080-1223, between apply_pbr :1072 and the FXAA pass :1225):
+ * the passes `2d_forward_vis_pass` (passes/2d_forward_vis.slang) and `2d_forward_pass` (passes/2d_forward.slang) over one DrawBatch2D of
+ * GPU::SpriteGPUData (include/Scene/SceneGPU.hpp:455-558), filled and sorted by the host at RendererInstance.cpp:1473-1532 -- here
+ * oxc_pack_sprite and oxc_sort_sprites.  oxc_pick_sprite is the editor's mouse_picking_2d stage (editor/mouse_picking_2d.slang).
+ * Arithmetic: the conventions of oxc_draw_visbuffer's block for everything up to the depth, and of oxc_apply_pbr's block for the colour --
+ * binary32, round to nearest even, the Slang's order, no contraction, IEEE division; a comparison with a NaN operand is false.
+ *
+ * oxc_pack_sprite (host, plain memory) is RenderQueue2D::add (SceneGPU.hpp:532-545): material_id16_ypos16 = u16(material_id) | half(position_y)
+ * << 16, flags16_distance16 = u16(render_flags) | half(distance) << 16, transform_id as given.  half() is the round-to-nearest-even binary32 ->
+ * binary16 conversion with denormals kept, every NaN 0x7E00; glm::packHalf1x16 stands there in the reference.  OXC_INVALID_ARG for a null `out`.
+ * oxc_sort_sprites (host, plain memory) is RenderQueue2D::sort with SpriteGPUData::operator> (SceneGPU.hpp:473-506, :547): descending by the
+ * 64-bit key (distance bits << 32) | ykey, ykey = half_sort_key(ypos bits) when OXC_SPRITE_SORT_Y is set in the sprite's flags and 0 otherwise,
+ * half_sort_key(b) = (b & 0x8000) ? (~b & 0xFFFF) : (b | 0x8000).  The distance is compared by its raw bits, as the reference does.  Stated
+ * rule, the library's decision: the sort is stable -- sprites with equal keys keep their submission order; the reference's std::ranges::sort
+ * leaves their order open.  count == 0 is valid (`sprites` may be null then); otherwise OXC_INVALID_ARG for a null `sprites`.
+ *
+ * oxc_draw_sprites runs the stages of `stages` over sprites [first_sprite, first_sprite + sprite_count) of sprites_buffer; with both set
+ * OXC_SPRITES_VIS runs first, as in the engine.
+ *   S1. fetch     (2d_forward.slang:29-59, 2d_forward_vis.slang:28-58)  flags = low 16 bits of flags16_distance16; material index = low 16 bits
+ *              of material_id16_ypos16; a material index >= material_count uses the all-zero Material, as in oxc_decode_visbuffer.  Stated
+ *              rule: a sprite whose transform_id >= transform_count is dropped whole (the Slang reads past the buffer).  The world matrix is
+ *              transforms_world_buffer[transform_id] of `frame`, read as oxc_draw_visbuffer reads it.
+ *   S2. colour    (2d_forward.slang:62-78)  sample_albedo_color without the image branch, as everywhere in this library: HasAlbedoImage is
+ *              ignored, and uv, uv_size, uv_offset, ddx and ddy, which feed only the sample, are not computed.  color = the four dequantized
+ *              halves of albedo_color (com::dequantize_half: a denormal half is a signed zero), linear.  The fragment is discarded when
+ *              color.w <= get_alpha_cutoff(); a NaN on either side does not discard.  The test is uniform per sprite and is decided once per
+ *              sprite.  The all-zero Material has 0 <= 0 and is therefore always discarded.
+ *   S3. corners   (:42-55)  The six vertices are the Slang's `positions` table, (-0.5, -0.5), (0.5, -0.5), (0.5, 0.5), (0.5, 0.5), (-0.5, 0.5),
+ *              (-0.5, -0.5); x is negated when OXC_SPRITE_FLIP_X is set.  world.r = ((W_r0 x + W_r1 y) + W_r2 * 0.0f) + W_r3, the `* 0` term
+ *              included; clip = mul(projection_view, (world.xyz, 1)) as oxc_draw_visbuffer's vertex rule.  Two triangles, (v0, v1, v2) then
+ *              (v3, v4, v5), in that order.
+ *   S4. raster    The rules of oxc_draw_visbuffer, unchanged and from the same device header: the five clip planes (w >= 2^-10, |x|, |y| <= 64 w)
+ *              and the fan of the clipped polygon from its corner 0, the 1/256 snap, pixel centres at (px + 0.5, py + 0.5), integer edge
+ *              functions, the top-left rule, depth ((e0 z0 + e1 z1) + e2 z2) * (1 / area) in binary64 rounded once to binary32.  cullMode eNone
+ *              (RendererInstance.cpp:1117, :1182): a triangle of either orientation is drawn, negative area swaps corners 1 and 2; zero area is
+ *              dropped.  A fragment is kept when its depth is in (0, 1], as in the visbuffer draw.
+ *   S5. order     Per pixel the fragments run in this order: sprites in buffer order from first_sprite; within a sprite triangle 0, then
+ *              triangle 1; within a clipped triangle the fan order.  Each fragment does  if (d >= depth[pixel]) { depth[pixel] = d; write }
+ *              (depth test eGreaterOrEqual with depth write, RendererInstance.cpp:1108-1110, :1173-1175) -- a binary32 comparison with what the attachment holds at that
+ *              moment, false for a NaN.  VIS writes visbuffer_2d[pixel] = transform_id (2d_forward_vis.slang:76); COLOR blends.
+ *   S6. blend     Stated rule, as H5 of oxc_apply_highlight: vuk::BlendPreset::eAlphaBlend (RendererInstance.cpp:1181) is colour SrcAlpha / OneMinusSrcAlpha and alpha One /
+ *              OneMinusSrcAlpha.  dst = the stored texel decoded to binary32 (source_format 0: the exact UF11 / UF11 / UF10 decode; 1: the four
+ *              halves, denormals kept).  out.c = src.c * src.a + dst.c * (1.0f - src.a), each product rounded, then the sum; source_format 1
+ *              also out.a = src.a + dst.a * (1.0f - src.a); source_format 0 has no alpha and drops that result.  The result is stored by step
+ *              12 of oxc_apply_pbr for the format (truncating small floats; halves round to nearest even, a NaN 0x7E00).  The store happens
+ *              after every fragment: the quantisation to the attachment's format sits between two sprites on one pixel, as a ROP does it (the
+ *              kernel keeps the pixel in registers as its stored word and decodes it again for the next fragment).
+ *   S7. stages    With OXC_SPRITES_VIS | OXC_SPRITES_COLOR the colour stage tests against the depth the vis stage left: only fragments at the
+ *              pixel's final depth blend, in order when several are equal; a translucent sprite behind the front one does not show through.
+ *              OXC_SPRITES_COLOR alone is the ordered depth-tested blend.  This is the engine's behaviour (both passes share the depth
+ *              attachment with eGreaterOrEqual) and it surprises people.
+ * `clear` != 0 fills visbuffer_2d with ~0u first, the engine's clear (RendererInstance.cpp:644) folded in; it has a meaning only with
+ * OXC_SPRITES_VIS.  sprite_count == 0 is valid: only `clear` acts.
+ * Limits (else OXC_INVALID_ARG, nothing launched, nothing written; the first broken rule in this order gives the message, each has its own):
+ * struct_size; stages non-zero with no unknown bit; width and height non-zero and at most 16384 (the guard band of S4 is built for that);
+ * source_format 0 or 1 (OXC_SPRITES_COLOR); first_sprite + sprite_count does not wrap 32 bits and sprite_count is at most 1048576 (2^20; stated,
+ * the Slang has no cap); depth_attachment is one R32F level at offset 0 of width x height; `frame` non-null; then every buffer the stages
+ * touch in the order of the context's fields, then the frame's transforms_world_buffer -- non-null (materials_buffer may be when material_count
+ * is 0), then aligned (4 bytes; final_attachment 8 with source_format 1), then large enough (first_sprite + sprite_count records of 12 bytes;
+ * material_count records of 56; one texel per pixel; transform_count matrices of 64 bytes); then no buffer the call writes shares a byte with
+ * another buffer it touches.  visbuffer_2d is touched by OXC_SPRITES_VIS only and final_attachment by OXC_SPRITES_COLOR only; an input a stage
+ * does not read is not checked.  Floats are taken as given, NaN included.
+ * Scratch comes from the context (576 + 136 bytes per sprite of the call, 4 bytes per 128 x 128 pixel bin and per entry of a bin's list of
+ * at most 2048): the first call, or one with more sprites or bins than any before, allocates and is refused while the stream is being
+ * captured -- make one un-captured call first.  After that: three launches, no allocation, no host synchronisation, capturable into a HIP
+ * graph; no atomic takes part in any result, two runs over the same input are byte-identical.
+ *
+ * oxc_pick_sprite writes texel (x, y) of visbuffer_2d as one u32 to transform_id (mouse_picking_2d.slang:18-24: both branches store the
+ * same word).  Limits as oxc_pick_transform's without the frame: struct_size; width and height non-zero and at most 65536; x < width and
+ * y < height; visbuffer_2d and transform_id non-null, 4-byte aligned, large enough; transform_id shares no byte with visbuffer_2d. */
+#define OXC_SPRITE_SORT_Y 1u /* RENDER_FLAGS_2D_SORT_Y */
+#define OXC_SPRITE_FLIP_X 2u /* RENDER_FLAGS_2D_FLIP_X */
+typedef struct oxc_sprite { /* GPU::SpriteGPUData, 12 bytes */
+  uint32_t material_id16_ypos16;
+  uint32_t flags16_distance16;
+  uint32_t transform_id;
+} oxc_sprite;
+
+oxc_status oxc_pack_sprite(uint32_t render_flags, float position_y, uint32_t transform_id, uint32_t material_id, float distance, oxc_sprite* out);
+oxc_status oxc_sort_sprites(oxc_sprite* sprites, uint64_t count);
+
+#define OXC_SPRITES_VIS 1u
+#define OXC_SPRITES_COLOR 2u
+typedef struct oxc_sprite_context {
+  uint32_t struct_size; /* sizeof(oxc_sprite_context) */
+  uint32_t stages;      /* OXC_SPRITES_* */
+  uint32_t width, height;
+  uint32_t clear;         /* != 0: visbuffer_2d is filled with ~0u first (OXC_SPRITES_VIS) */
+  uint32_t source_format; /* S6: 0: B10G11R11 UfloatPack32;  1: R16G16B16A16 Sfloat, as oxc_apply_fxaa */
+  uint32_t first_sprite, sprite_count; /* one DrawBatch2D */
+  uint32_t material_count;             /* S1 */
+  uint32_t transform_count;            /* S1 */
+  float projection_view[16];           /* S3: column-major */
+  oxc_buffer sprites_buffer;           /* in: oxc_sprite[first_sprite + sprite_count] */
+  oxc_buffer materials_buffer;         /* in: GPU::Material[material_count], 56 bytes each */
+  oxc_image depth_attachment;          /* in/out: R32F, levels = 1 */
+  oxc_buffer visbuffer_2d;             /* vis out: u32[height][width] */
+  oxc_buffer final_attachment;         /* colour in/out: u32[height][width] or u16[height][width][4], what oxc_apply_pbr wrote */
+} oxc_sprite_context;
+
+oxc_status oxc_draw_sprites(oxc_ctx* ctx, const oxc_prepared_frame* frame, const oxc_sprite_context* context, void* hip_stream);
+
+typedef struct oxc_sprite_pick_context {
+  uint32_t struct_size; /* sizeof(oxc_sprite_pick_context) */
+  uint32_t width, height;
+  uint32_t x, y;           /* the picking texel */
+  oxc_buffer visbuffer_2d; /* in: u32[height][width] */
+  oxc_buffer transform_id; /* out: one u32 */
+} oxc_sprite_pick_context;
+
+oxc_status oxc_pick_sprite(oxc_ctx* ctx, const oxc_sprite_pick_context* context, void* hip_stream);
 
 /* ---- multi-GPU exchange: one process per GPU, RCCL over xGMI ---------------------------
  * The meshlet-instance array shards by contiguous range and every rank culls its shard on its own; the only

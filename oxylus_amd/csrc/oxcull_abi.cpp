@@ -17,6 +17,7 @@
 //   oxcull_abi_terrain.cpp the terrain map producers, the terrain brush and the terrain decode
 //   oxcull_abi_debug.cpp  the debug views
 //   oxcull_abi_editor.cpp the editor's selection path: the transform pick and the selection highlight
+//   oxcull_abi_sprites.cpp the 2D pass: the sprite queue's host helpers, the sprite draw and the sprite pick
 //   oxcull_abi_comm.cpp   the RCCL exchange
 #include <new>
 
@@ -65,6 +66,7 @@ void oxc_destroy(oxc_ctx* ctx) {
   if (ctx->bounds_scratch) (void)hipFree(ctx->bounds_scratch);
   if (ctx->raster_scratch) (void)hipFree(ctx->raster_scratch);
   if (ctx->raster_rows) (void)hipFree(ctx->raster_rows);
+  if (ctx->sprite_scratch) (void)hipFree(ctx->sprite_scratch);
   if (ctx->vsm_scratch) (void)hipFree(ctx->vsm_scratch);
   if (ctx->vsm_draw_scratch) (void)hipFree(ctx->vsm_draw_scratch);
   for (const auto& pc : {ctx->vsm_resolve_stats, ctx->contact_shadows_stats, ctx->ambient_occlusion_stats, ctx->visbuffer_decode_stats, ctx->pbr_apply_stats, ctx->fxaa_stats})

@@ -88,6 +88,8 @@ struct oxc_ctx {
   uint32_t raster_grid = 0;              // OXC_TUNE_RASTER_GRID: cap of every launch of the draw in blocks, 0 = uncapped
   void* raster_rows = nullptr;     // oxc_draw_visbuffer: one DrawRow per mesh instance
   uint32_t raster_rows_cap = 0;
+  void* sprite_scratch = nullptr;  // oxc_draw_sprites: records, boxes, the clipped sprites' side array, bin counts and bin lists
+  uint64_t sprite_scratch_bytes = 0;
   void* vsm_scratch = nullptr;     // oxc_update_virtual_shadowmap: free page list (u32 per physical page), then the per-page mark map (a byte per entry)
   uint64_t vsm_scratch_bytes = 0;
   void* vsm_draw_scratch = nullptr;  // oxc_draw_physical_pages: header, drawable-page bitmaps and maps, rows, big-pair / clip / tile queues

@@ -900,6 +900,47 @@ void highlight_outline_linear(const float* outline_color, float* final_outline);
 void launch_highlight_composite(const HighlightCompositeArgs& a, hipStream_t s);
 // the pow rule on the host (oxcull_tonemap.hip keeps the host's copy of the log2 rule)
 float pow_rule_host(float v, float p);
+// oxcull_sprites.hip: the 2D pass (oxc_draw_sprites, oxc_pick_sprite)
+constexpr uint32_t kSpriteBin = 128;           // side of a coarse bin in pixels; one block of k_sprites_bin per bin
+constexpr uint32_t kSpriteTile = 16;           // side of a tile in pixels; one block of k_sprites_pixels per tile, one pixel per lane
+constexpr uint32_t kSpriteChunk = 256;         // sprites a block tests per step of its ordered compaction (bin and tile kernels alike)
+constexpr uint32_t kSpriteBinCapacity = 2048;  // entries of a bin's list; a bin that meets more makes its tiles walk the sprite records themselves
+constexpr uint32_t kSpriteMaxTris = 12;        // fan triangles of a sprite that crosses clip planes: 6 per source triangle
+constexpr uint32_t kSpriteMaxCount = 1u << 20; // sprites of one call (stated limit)
+constexpr int32_t kSpriteNarrowSpread = 28672; // corner spread (1/256 px) below which every edge value of a tile the sprite touches fits edge_fn32
+struct SpriteTri {  // one set-up triangle, oriented with positive area (48 bytes)
+  int32_t x[3], y[3];
+  float z[3];
+  uint32_t inv_area_lo, inv_area_hi;  // binary64 1 / area
+  uint32_t bias;                      // bit k: edge k is not inclusive
+};
+struct SpriteRecord {   // what a pixel needs of a sprite (128 bytes)
+  float ca[3];          // S6: src.c * src.a
+  float a, one_minus_a;
+  uint32_t transform_id;
+  uint32_t shape;       // triangle count | clipped << 8 (the triangles are in the side array) | narrow << 9
+  uint32_t pad;
+  SpriteTri tri[2];     // the usual sprite: two triangles inside every plane
+};
+struct SpriteArgs {
+  const uint32_t* sprites;    // oxc_sprite records from first_sprite on
+  const uint32_t* materials;  // GPU::Material[material_count], 14 words each
+  const float* transforms;
+  uint32_t sprite_count, material_count, transform_count;
+  float pv[16];
+  uint32_t w, h, stages, clear;
+  uint32_t bins_x, bins_y, list_stride;  // list_stride = min(sprite_count, kSpriteBinCapacity)
+  SpriteRecord* records;                 // [sprite_count]
+  uint2* boxes;                          // [sprite_count] {px0 | py0 << 16, px1 | py1 << 16}; empty: {~0u, 0}
+  SpriteTri* clipped;                    // [sprite_count][kSpriteMaxTris], written for sprites that cross a plane only
+  uint32_t* bin_counts;                  // [bins]: the sprites whose box meets the bin (above list_stride: the list is cut short)
+  uint32_t* bin_lists;                   // [bins][list_stride], ascending
+  float* depth;
+  uint32_t* vis;
+  void* color;
+};
+void launch_draw_sprites(const SpriteArgs& a, uint32_t format, hipStream_t s);
+void launch_pick_sprite(const uint32_t* vis, uint32_t w, uint32_t x, uint32_t y, uint32_t* out, hipStream_t s);
 // oxcull_bounds.hip: meshlet bounds producer
 void launch_build_meshlet_bounds(const float* pos, uint32_t vertex_count, const void* meshlets, uint32_t meshlet_count, const uint32_t* vidx,
                                  const uint8_t* micro, void* out_bounds, float* out_mesh6, void* out_qpos, float* meshlet_minmax, float* normals,

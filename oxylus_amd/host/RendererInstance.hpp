@@ -201,6 +201,23 @@ struct PickingContext {
   Buffer transform_id = {};
 };
 
+// The 2D block of the render function (RendererInstance.cpp:1080-1223): what `2d_forward_vis_pass` and `2d_forward_pass` capture and bind.  The
+// sprites are one DrawBatch2D of the render queue's GPU::SpriteGPUData (oxc_pack_sprite and oxc_sort_sprites fill and sort the queue on the
+// host); the world matrices are prepared_frame.transforms_world_buffer, the materials prepared_frame.materials_buffer.
+struct SpriteContext {
+  Buffer sprites_buffer = {};       // the render queue's vertex buffer
+  uint32_t batch_offset = 0;        // DrawBatch2D::offset
+  uint32_t batch_count = 0;         // DrawBatch2D::count
+  float projection_view[16] = {};   // camera_buffer->projection_view
+  Buffer visbuffer_attachment_2d = {};
+};
+// mouse_picking_2d: the texel under the cursor and the u32 the pass writes
+struct SpritePickingContext {
+  uint32_t picking_texel[2] = {0, 0};
+  Buffer visbuffer_attachment_2d = {};
+  Buffer transform_id = {};
+};
+
 struct PostProcessContext {
   float delta_time = 0.0f;
   Extent3D extent = {};
@@ -753,6 +770,43 @@ public:
     c.dst_attachment = context.outlined_composite;
     check(oxc_apply_highlight(ctx_, &f, &c, stream_));
     return context.outlined_composite;
+  }
+  // The 2D block of the render function (RendererInstance.cpp:1080-1223), between apply_pbr and the FXAA pass: `2d_forward_vis_pass` and
+  // `2d_forward_pass` as the stages of `stages` over context's batch, onto depth_attachment and final_attachment (an image of `source_format`
+  // as apply_pbr wrote it); the engine's clear of visbuffer_attachment_2d is folded in.  Returns final_attachment.  Rules: include/oxcull.h,
+  // oxc_draw_sprites.
+  auto draw_sprites(SpriteContext& context, uint32_t stages, Extent3D extent, ImageAttachment depth_attachment, Buffer final_attachment = {}, uint32_t source_format = 0)
+      -> Buffer {
+    oxc_prepared_frame f = {};
+    f.transforms_world_buffer = prepared_frame.transforms_world_buffer;
+    oxc_sprite_context c = {};
+    c.struct_size = sizeof c;
+    c.stages = stages;
+    c.width = extent.width, c.height = extent.height;
+    c.clear = 1;
+    c.source_format = source_format;
+    c.first_sprite = context.batch_offset, c.sprite_count = context.batch_count;
+    c.material_count = static_cast<uint32_t>(prepared_frame.materials_buffer.bytes / 56u);
+    c.transform_count = static_cast<uint32_t>(prepared_frame.transforms_world_buffer.bytes / 64u);
+    for (int i = 0; i < 16; i++) c.projection_view[i] = context.projection_view[i];
+    c.sprites_buffer = context.sprites_buffer;
+    c.materials_buffer = prepared_frame.materials_buffer;
+    c.depth_attachment = depth_attachment;
+    c.visbuffer_2d = context.visbuffer_attachment_2d;
+    c.final_attachment = final_attachment;
+    check(oxc_draw_sprites(ctx_, &f, &c, stream_));
+    return final_attachment;
+  }
+  // The editor's mouse_picking_2d stage: texel context.picking_texel of visbuffer_attachment_2d into context.transform_id.
+  auto pick_sprite(SpritePickingContext& context, Extent3D extent) -> Buffer {
+    oxc_sprite_pick_context c = {};
+    c.struct_size = sizeof c;
+    c.width = extent.width, c.height = extent.height;
+    c.x = context.picking_texel[0], c.y = context.picking_texel[1];
+    c.visbuffer_2d = context.visbuffer_attachment_2d;
+    c.transform_id = context.transform_id;
+    check(oxc_pick_sprite(ctx_, &c, stream_));
+    return context.transform_id;
   }
   auto build_meshlet_bounds(oxc_meshlet_bounds_desc desc) -> void {
     desc.struct_size = sizeof desc;

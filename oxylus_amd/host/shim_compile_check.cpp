@@ -134,5 +134,13 @@ int main(int argc, char**) {
   } catch (const std::exception& e) {
     std::printf("expected (no attachments bound): %s\n", e.what());
   }
+  try {  // RendererInstance.cpp:1080-1223: the 2D block between apply_pbr and the FXAA pass, and the editor's mouse_picking_2d behind it
+    auto sprite_context = SpriteContext{.batch_offset = 0, .batch_count = 4};
+    (void)self.draw_sprites(sprite_context, OXC_SPRITES_VIS | OXC_SPRITES_COLOR, Extent3D{.width = 16, .height = 16}, ImageAttachment{}, Buffer{}, /*source_format*/ 0);
+    auto sprite_picking = SpritePickingContext{.picking_texel = {3, 5}};
+    (void)self.pick_sprite(sprite_picking, Extent3D{.width = 16, .height = 16});
+  } catch (const std::exception& e) {
+    std::printf("expected (no attachments bound): %s\n", e.what());
+  }
   return 0;
 }

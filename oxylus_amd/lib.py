@@ -53,6 +53,8 @@ TERRAIN_GENERATE, TERRAIN_DERIVE, TERRAIN_MINMAX, TERRAIN_ALL = 1, 2, 4, 7  # ox
 TERRAIN_BRUSH_TRACE, TERRAIN_BRUSH_APPLY, TERRAIN_BRUSH_ALL = 1, 2, 3  # oxc_terrain_brush_context.stages
 TERRAIN_INVALID_LAYER_MATERIAL = 0xFFFFFFFF  # scene.slang:632
 HIGHLIGHT_MASK, HIGHLIGHT_COMPOSITE, HIGHLIGHT_ALL = 1, 2, 3  # oxc_highlight_context.stages
+SPRITES_VIS, SPRITES_COLOR, SPRITES_ALL = 1, 2, 3  # oxc_sprite_context.stages
+SPRITE_SORT_Y, SPRITE_FLIP_X = 1, 2  # GPU::RenderFlags2D, the low half of oxc_sprite.flags16_distance16
 # GPU::DebugView (scene.slang:10-26; RMVSM from SceneGPU.hpp:44), oxc_debug_view_context.debug_view
 (DEBUG_VIEW_TRIANGLES, DEBUG_VIEW_MESHLETS, DEBUG_VIEW_OVERDRAW, DEBUG_VIEW_MATERIALS, DEBUG_VIEW_MESH_INSTANCES, DEBUG_VIEW_MESH_LODS, DEBUG_VIEW_ALBEDO,
  DEBUG_VIEW_NORMAL, DEBUG_VIEW_EMISSIVE, DEBUG_VIEW_METALLIC, DEBUG_VIEW_ROUGHNESS, DEBUG_VIEW_BAKED_OCCLUSION, DEBUG_VIEW_GTAO, DEBUG_VIEW_GEOMETRIC_NORMAL,
@@ -870,6 +872,46 @@ class HighlightContext(C.Structure):
     ]
 
 
+class Sprite(C.Structure):
+    _c_name_ = "oxc_sprite"
+    _fields_ = [("material_id16_ypos16", C.c_uint32), ("flags16_distance16", C.c_uint32), ("transform_id", C.c_uint32)]
+
+
+class SpriteContext(C.Structure):
+    _c_name_ = "oxc_sprite_context"
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("stages", C.c_uint32),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("clear", C.c_uint32),
+        ("source_format", C.c_uint32),
+        ("first_sprite", C.c_uint32),
+        ("sprite_count", C.c_uint32),
+        ("material_count", C.c_uint32),
+        ("transform_count", C.c_uint32),
+        ("projection_view", C.c_float * 16),
+        ("sprites_buffer", Buffer),
+        ("materials_buffer", Buffer),
+        ("depth_attachment", Image),
+        ("visbuffer_2d", Buffer),
+        ("final_attachment", Buffer),
+    ]
+
+
+class SpritePickContext(C.Structure):
+    _c_name_ = "oxc_sprite_pick_context"
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("x", C.c_uint32),
+        ("y", C.c_uint32),
+        ("visbuffer_2d", Buffer),
+        ("transform_id", Buffer),
+    ]
+
+
 class MeshBuildDesc(C.Structure):
     _c_name_ = "oxc_mesh_build_desc"
     _fields_ = [("struct_size", C.c_uint32), ("vertex_count", C.c_uint32), ("index_count", C.c_uint32), ("max_lods", C.c_uint32), ("max_vertices", C.c_uint32),
@@ -941,6 +983,10 @@ PROTOTYPES = {
     "oxc_apply_debug_view": (_status, [_vp, _P(PreparedFrame), _P(DebugViewContext), _vp]),
     "oxc_pick_transform": (_status, [_vp, _P(PreparedFrame), _P(PickContext), _vp]),
     "oxc_apply_highlight": (_status, [_vp, _P(PreparedFrame), _P(HighlightContext), _vp]),
+    "oxc_pack_sprite": (_status, [_u32, C.c_float, _u32, _u32, C.c_float, _P(Sprite)]),
+    "oxc_sort_sprites": (_status, [_P(Sprite), _u64]),
+    "oxc_draw_sprites": (_status, [_vp, _P(PreparedFrame), _P(SpriteContext), _vp]),
+    "oxc_pick_sprite": (_status, [_vp, _P(SpritePickContext), _vp]),
     "oxc_draw_physical_pages": (_status, [_vp, _P(PreparedFrame), _P(VsmDrawContext), _vp]),
     "oxc_debug_vsm_draw_stats": _stats,
     "oxc_resolve_shadowmap": (_status, [_vp, _P(ShadowResolveContext), _vp]),

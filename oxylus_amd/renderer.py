@@ -1094,6 +1094,75 @@ class HighlightContext(Marshalled):
                                 dst_attachment=torch.zeros_like(color), color_format=color_format, **settings)
 
 
+def pack_sprite(render_flags: int, position_y: float, transform_id: int, material_id: int, distance: float) -> tuple:
+    """RenderQueue2D::add (SceneGPU.hpp:532-545) through oxc_pack_sprite: the three words of one GPU::SpriteGPUData.  Host only."""
+    out = L.Sprite()
+    st = L.load().oxc_pack_sprite(int(render_flags), float(position_y), int(transform_id), int(material_id), float(distance), C.byref(out))
+    if st != L.OXC_OK:
+        raise L.OxcError(st, "oxc_pack_sprite")
+    return out.material_id16_ypos16, out.flags16_distance16, out.transform_id
+
+
+def sort_sprites(sprites):
+    """RenderQueue2D::sort (SceneGPU.hpp:547) through oxc_sort_sprites: `sprites`, a C-contiguous numpy uint32 [n, 3] array, sorted in place --
+    descending by distance bits, then by the y key of the SORT_Y sprites; stable.  Host only.  Returns the array."""
+    assert sprites.dtype.name == "uint32" and sprites.ndim == 2 and sprites.shape[1] == 3 and sprites.flags.c_contiguous
+    st = L.load().oxc_sort_sprites(sprites.ctypes.data_as(C.POINTER(L.Sprite)), sprites.shape[0])
+    if st != L.OXC_OK:
+        raise L.OxcError(st, "oxc_sort_sprites")
+    return sprites
+
+
+@dataclass
+class SpriteContext(Marshalled):
+    """oxc_sprite_context: the 2D block of the frame (RendererInstance.cpp:1080-1223; passes/2d_forward_vis.slang, passes/2d_forward.slang)
+    over one DrawBatch2D.  `stages` selects the vis pass, the colour pass or both; `final_attachment` is the image apply_pbr wrote -- int32
+    [H, W] (B10G11R11) or int16 [H, W, 4] (R16G16B16A16 Sfloat); `depth_attachment` is tested and written (include/oxcull.h, S1 - S7)."""
+    _ctype = L.SpriteContext
+    stages: int
+    width: int
+    height: int
+    projection_view: tuple
+    sprites_buffer: Optional[torch.Tensor]               # int32 [n, 3]: GPU::SpriteGPUData
+    sprite_count: int
+    transform_count: int
+    depth_attachment: Optional[ImageAttachment]          # R32F, levels = 1, in/out
+    materials_buffer: Optional[torch.Tensor] = None      # uint8 [material_count * 56]
+    material_count: int = 0
+    visbuffer_2d: Optional[torch.Tensor] = None          # int32 [H, W] out (vis)
+    final_attachment: Optional[torch.Tensor] = None      # in/out (colour)
+    source_format: int = 0
+    first_sprite: int = 0
+    clear: bool = True
+
+    @staticmethod
+    def create(sprites: torch.Tensor, materials: torch.Tensor, transform_count: int, projection_view, depth: ImageAttachment, final_attachment: torch.Tensor,
+               stages: int = L.SPRITES_ALL, first_sprite: int = 0, sprite_count: Optional[int] = None, clear: bool = True) -> "SpriteContext":
+        """Both stages over the depth and the lit image of a frame; allocates visbuffer_2d.  The format follows from the image's shape."""
+        fmt = L.EYE_SOURCE_R16G16B16A16 if final_attachment.dim() == 3 else L.EYE_SOURCE_B10G11R11
+        count = sprites.shape[0] - first_sprite if sprite_count is None else sprite_count
+        vis = torch.full((depth.height, depth.width), -1, dtype=torch.int32, device=sprites.device)
+        return SpriteContext(stages, depth.width, depth.height, tuple(float(v) for v in projection_view), sprites, count, transform_count, depth, materials,
+                             materials.numel() * materials.element_size() // 56, vis, final_attachment, fmt, first_sprite, clear)
+
+
+@dataclass
+class SpritePickContext(Marshalled):
+    """oxc_sprite_pick_context: the editor's mouse_picking_2d stage: texel `picking_texel` of `visbuffer_2d`, one u32 into `transform_id`."""
+    _ctype = L.SpritePickContext
+    _derived = {"x": lambda self: int(self.picking_texel[0]), "y": lambda self: int(self.picking_texel[1])}
+    visbuffer_2d: torch.Tensor   # int32 [H, W]
+    width: int
+    height: int
+    picking_texel: tuple
+    transform_id: torch.Tensor   # int32 [1] out
+
+    @staticmethod
+    def over(visbuffer_2d: torch.Tensor, picking_texel, transform_id: Optional[torch.Tensor] = None) -> "SpritePickContext":
+        out = torch.zeros(1, dtype=torch.int32, device=visbuffer_2d.device) if transform_id is None else transform_id
+        return SpritePickContext(visbuffer_2d, visbuffer_2d.shape[1], visbuffer_2d.shape[0], tuple(picking_texel), out)
+
+
 @dataclass
 class VisbufferDecodeContext(Marshalled):
     """oxc_decode_context: RendererInstance::decode_visbuffer (Passes/DrawGeometry.cpp:192-274), the geometry and material-factor half of
@@ -1450,6 +1519,18 @@ class RendererInstance:
         """ViewportPanel.cpp:1166-1345 (highlight_mask_stage, highlight_composite_stage): the stages of `context.stages`, one launch each
         (include/oxcull.h, oxc_apply_highlight).  The prepared frame is passed when there is one; only the mask stage needs it."""
         self._call("oxc_apply_highlight", context, stream, frame="optional")
+
+    def draw_sprites(self, context: "SpriteContext", stream=None) -> None:
+        """RendererInstance.cpp:1080-1223 (2d_forward_vis_pass, 2d_forward_pass): the stages of `context.stages` over one batch of sprites,
+        between apply_pbr and apply_fxaa (include/oxcull.h, oxc_draw_sprites).  The world matrices come from the prepared frame."""
+        self._call("oxc_draw_sprites", context, stream, frame=True)
+
+    def pick_sprite(self, context: "SpritePickContext", stream=None) -> None:
+        """editor/mouse_picking_2d.slang: texel `context.picking_texel` of visbuffer_2d into `context.transform_id`."""
+        self._call("oxc_pick_sprite", context, stream)
+
+    pack_sprite = staticmethod(lambda *a, **k: pack_sprite(*a, **k))
+    sort_sprites = staticmethod(lambda *a, **k: sort_sprites(*a, **k))
 
     def generate_terrain_maps(self, context: TerrainMapsContext, stream=None) -> None:
         """Scene/Terrain.cpp:406-461 and Passes/Terrain.cpp:134-156 (terrain_generate, terrain_derive, terrain_minmax): the stages of
