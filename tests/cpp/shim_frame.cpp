@@ -12,17 +12,10 @@
 //     generate_hiz({depth_attachment = depth1, hiz_attachment})
 //     cull_geometry({use_hiz, init_cull_meshes = false, TestAll | LatePass, same hoisted context})    -- late
 // Container format (little endian): "OXCF", u32 count, then count x {char name[24]; u64 offset; u64 bytes}, then the payloads.
-#include <hip/hip_runtime_api.h>
-
 #include <cstdint>
-#include <cstdio>
-#include <cstring>
 #include <map>
-#include <stdexcept>
-#include <string>
-#include <vector>
 
-#include "RendererInstance.hpp"
+#include "shim_io.hpp"
 
 using namespace ox::amd;
 
@@ -34,15 +27,8 @@ struct Entry {
 using Blob = std::vector<uint8_t>;
 
 std::map<std::string, Blob> read_container(const char* path) {
-  FILE* f = std::fopen(path, "rb");
-  if (!f) throw std::runtime_error(std::string("cannot open ") + path);
-  std::fseek(f, 0, SEEK_END);
-  long size = std::ftell(f);
-  std::fseek(f, 0, SEEK_SET);
-  Blob all((size_t)size);
-  if (std::fread(all.data(), 1, all.size(), f) != all.size()) throw std::runtime_error("short read");
-  std::fclose(f);
-  if (std::memcmp(all.data(), "OXCF", 4) != 0) throw std::runtime_error("bad magic");
+  const std::vector<char> all = shim_io::read_file(path);
+  if (all.size() < 8 || std::memcmp(all.data(), "OXCF", 4) != 0) throw std::runtime_error("bad magic");
   uint32_t n;
   std::memcpy(&n, all.data() + 4, 4);
   std::map<std::string, Blob> out;

@@ -2,17 +2,10 @@
 // RendererInstance.hpp.  Reads <dir>/params.bin (Params below) and the inputs as <dir>/<name>.bin; writes the picked transform as
 // <dir>/pick.out, the mask words and the mask image as <dir>/mask_bits.out and <dir>/mask_attachment.out, and the composite of format f in
 // mode m as <dir>/dst_format<f>_mode<m>.out.  tests/test_gpu_highlight_shim.py compares them with the golden fixture's bytes.
-#include <hip/hip_runtime.h>
-
-#include <cstdio>
-#include <fstream>
-#include <iterator>
-#include <string>
-#include <vector>
-
-#include "RendererInstance.hpp"
+#include "shim_io.hpp"
 
 using namespace ox::amd;
+using namespace shim_io;
 
 struct Params {
   uint32_t width, height;
@@ -21,42 +14,13 @@ struct Params {
   uint32_t pick_x, pick_y;
 };
 
-static std::vector<char> read_file(const std::string& path) {
-  std::ifstream f(path, std::ios::binary);
-  if (!f) throw std::runtime_error("cannot read " + path);
-  return {std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>()};
-}
-
-static Buffer device_buffer(size_t bytes, const std::string& path = "") {
-  void* dev = nullptr;
-  if (hipMalloc(&dev, bytes) != hipSuccess || hipMemset(dev, 0xEE, bytes) != hipSuccess) throw std::runtime_error("hipMalloc failed");
-  if (!path.empty()) {
-    const std::vector<char> host = read_file(path);
-    if (host.size() != bytes || hipMemcpy(dev, host.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("upload failed: " + path);
-  }
-  return Buffer{dev, bytes};
-}
-
-static void write_out(const std::string& path, const Buffer& b) {
-  std::vector<char> host(b.bytes);
-  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(host.data(), b.dptr, b.bytes, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("read back failed");
-  std::ofstream(path, std::ios::binary).write(host.data(), (std::streamsize)host.size());
-}
-
 int main(int argc, char** argv) {
-  if (argc != 2) {
-    std::printf("usage: shim_highlight <dir>\n");
-    return 2;
-  }
-  try {
-    const std::string dir = argv[1];
-    const std::vector<char> raw = read_file(dir + "/params.bin");
-    if (raw.size() != sizeof(Params)) throw std::runtime_error("params.bin has the wrong size");
-    const Params& p = *reinterpret_cast<const Params*>(raw.data());
+  return run(argc, argv, "shim_highlight", [](const std::string& dir) {
+    const Params p = read_params<Params>(dir);
     const size_t pixels = (size_t)p.width * p.height;
     const Extent3D extent = {p.width, p.height, 1};
     RendererInstance self(0);
-    const auto load = [&](const char* name, size_t bytes) { return device_buffer(bytes, dir + "/" + name + ".bin"); };
+    const auto load = [&](const char* name, size_t bytes) { return device_buffer(bytes, 0xEE, dir + "/" + name + ".bin"); };
     self.prepared_frame.mesh_instance_count = p.mesh_instances;
     self.prepared_frame.meshlet_instances_buffer = load("meshlet_instances", (size_t)p.meshlet_instances * 8u);
     self.prepared_frame.mesh_instances_buffer = load("mesh_instances", (size_t)p.mesh_instances * 20u);
@@ -65,19 +29,19 @@ int main(int argc, char** argv) {
     picking.picking_texel[0] = p.pick_x, picking.picking_texel[1] = p.pick_y;
     picking.terrain_transform_index = p.terrain_transform_index;
     picking.visbuffer_attachment = load("vis", pixels * 4u);
-    picking.transform_id = device_buffer(4u);
+    picking.transform_id = device_buffer(4u, 0xEE);
     write_out(dir + "/pick.out", self.pick_transform(picking, extent));
 
     HighlightContext context = {};
     context.transform_indices = load("selected", (size_t)p.selected * 4u);
     context.terrain_transform_index = p.terrain_transform_index;
     context.visbuffer_attachment = picking.visbuffer_attachment;
-    context.silhouette_mask_bits = device_buffer((size_t)((p.width + 63u) / 64u) * p.height * 8u);
-    context.silhouette_mask = device_buffer(pixels);
+    context.silhouette_mask_bits = device_buffer((size_t)((p.width + 63u) / 64u) * p.height * 8u, 0xEE);
+    context.silhouette_mask = device_buffer(pixels, 0xEE);
     const Buffer depth = load("depth", pixels * 4u);
     context.depth_attachment.dptr = depth.dptr;
     context.depth_attachment.width = p.width, context.depth_attachment.height = p.height, context.depth_attachment.levels = 1;
-    context.outlined_composite = device_buffer(pixels * 4u);
+    context.outlined_composite = device_buffer(pixels * 4u, 0xEE);
     self.apply_highlight(context, OXC_HIGHLIGHT_MASK, extent);
     write_out(dir + "/mask_bits.out", context.silhouette_mask_bits);
     write_out(dir + "/mask_attachment.out", context.silhouette_mask);
@@ -90,9 +54,5 @@ int main(int argc, char** argv) {
         write_out(dir + "/dst_format" + std::to_string(format) + "_mode" + std::to_string(mode) + ".out", written);
       }
     std::printf("highlight ok\n");
-    return 0;
-  } catch (const std::exception& e) {
-    std::fprintf(stderr, "%s\n", e.what());
-    return 1;
-  }
+  });
 }

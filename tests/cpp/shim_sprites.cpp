@@ -2,17 +2,10 @@
 // Reads <dir>/params.bin (Params below) and the inputs as <dir>/<name>.bin; for source format f and stage set s it writes the depth, the
 // visbuffer and the colour image as <dir>/<image>_format<f>_stages<s>.out, and the picked word as <dir>/pick.out.
 // tests/test_gpu_sprites_shim.py compares them with the golden fixture's bytes.
-#include <hip/hip_runtime.h>
-
-#include <cstdio>
-#include <fstream>
-#include <iterator>
-#include <string>
-#include <vector>
-
-#include "RendererInstance.hpp"
+#include "shim_io.hpp"
 
 using namespace ox::amd;
+using namespace shim_io;
 
 struct Params {
   uint32_t width, height;
@@ -20,42 +13,13 @@ struct Params {
   uint32_t pick_x, pick_y;
 };
 
-static std::vector<char> read_file(const std::string& path) {
-  std::ifstream f(path, std::ios::binary);
-  if (!f) throw std::runtime_error("cannot read " + path);
-  return {std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>()};
-}
-
-static Buffer device_buffer(size_t bytes, const std::string& path = "") {
-  void* dev = nullptr;
-  if (hipMalloc(&dev, bytes) != hipSuccess || hipMemset(dev, 0xEE, bytes) != hipSuccess) throw std::runtime_error("hipMalloc failed");
-  if (!path.empty()) {
-    const std::vector<char> host = read_file(path);
-    if (host.size() != bytes || hipMemcpy(dev, host.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("upload failed: " + path);
-  }
-  return Buffer{dev, bytes};
-}
-
-static void write_out(const std::string& path, const Buffer& b) {
-  std::vector<char> host(b.bytes);
-  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(host.data(), b.dptr, b.bytes, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("read back failed");
-  std::ofstream(path, std::ios::binary).write(host.data(), (std::streamsize)host.size());
-}
-
 int main(int argc, char** argv) {
-  if (argc != 2) {
-    std::printf("usage: shim_sprites <dir>\n");
-    return 2;
-  }
-  try {
-    const std::string dir = argv[1];
-    const std::vector<char> raw = read_file(dir + "/params.bin");
-    if (raw.size() != sizeof(Params)) throw std::runtime_error("params.bin has the wrong size");
-    const Params& p = *reinterpret_cast<const Params*>(raw.data());
+  return run(argc, argv, "shim_sprites", [](const std::string& dir) {
+    const Params p = read_params<Params>(dir);
     const size_t pixels = (size_t)p.width * p.height;
     const Extent3D extent = {p.width, p.height, 1};
     RendererInstance self(0);
-    const auto load = [&](const std::string& name, size_t bytes) { return device_buffer(bytes, dir + "/" + name + ".bin"); };
+    const auto load = [&](const std::string& name, size_t bytes) { return device_buffer(bytes, 0xEE, dir + "/" + name + ".bin"); };
     self.prepared_frame.transforms_world_buffer = load("transforms", (size_t)p.transforms * 64u);
     self.prepared_frame.materials_buffer = load("materials", (size_t)p.materials * 56u);
 
@@ -65,7 +29,7 @@ int main(int argc, char** argv) {
     const std::vector<char> pv = read_file(dir + "/pv.bin");
     if (pv.size() != 64u) throw std::runtime_error("pv.bin has the wrong size");
     for (int i = 0; i < 16; i++) context.projection_view[i] = reinterpret_cast<const float*>(pv.data())[i];
-    context.visbuffer_attachment_2d = device_buffer(pixels * 4u);
+    context.visbuffer_attachment_2d = device_buffer(pixels * 4u, 0xEE);
     for (uint32_t format = 0; format < 2; format++)
       for (uint32_t stages = 1; stages <= 3; stages++) {
         const std::string tag = "_format" + std::to_string(format) + "_stages" + std::to_string(stages) + ".out";
@@ -82,12 +46,8 @@ int main(int argc, char** argv) {
     SpritePickingContext picking = {};
     picking.picking_texel[0] = p.pick_x, picking.picking_texel[1] = p.pick_y;
     picking.visbuffer_attachment_2d = context.visbuffer_attachment_2d;  // the last call ran both stages
-    picking.transform_id = device_buffer(4u);
+    picking.transform_id = device_buffer(4u, 0xEE);
     write_out(dir + "/pick.out", self.pick_sprite(picking, extent));
     std::printf("sprites ok\n");
-    return 0;
-  } catch (const std::exception& e) {
-    std::fprintf(stderr, "%s\n", e.what());
-    return 1;
-  }
+  });
 }

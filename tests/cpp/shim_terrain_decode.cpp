@@ -1,17 +1,10 @@
 // shim_terrain_decode <dir>: runs one terrain decode through ox::amd::decode_terrain of RendererInstance.hpp.  Reads <dir>/params.bin (Params
 // below) and the inputs and the four attachments as earlier passes left them, <dir>/<name>.bin, and writes the four attachments as
 // <dir>/<name>.out.  tests/test_gpu_terrain_decode_shim.py compares them with the Python path's bytes.
-#include <hip/hip_runtime.h>
-
-#include <cstdio>
-#include <fstream>
-#include <iterator>
-#include <string>
-#include <vector>
-
-#include "RendererInstance.hpp"
+#include "shim_io.hpp"
 
 using namespace ox::amd;
+using namespace shim_io;
 
 struct Params {
   uint32_t width, height;
@@ -21,39 +14,12 @@ struct Params {
   uint32_t material_count;
 };
 
-static std::vector<char> read_file(const std::string& path) {
-  std::ifstream f(path, std::ios::binary);
-  if (!f) throw std::runtime_error("cannot read " + path);
-  return {std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>()};
-}
-
-static Buffer device_buffer(size_t bytes, const std::string& path) {
-  void* dev = nullptr;
-  if (hipMalloc(&dev, bytes) != hipSuccess) throw std::runtime_error("hipMalloc failed");
-  const std::vector<char> host = read_file(path);
-  if (host.size() != bytes || hipMemcpy(dev, host.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) throw std::runtime_error("upload failed: " + path);
-  return Buffer{dev, bytes};
-}
-
-static void write_out(const std::string& path, const Buffer& b) {
-  std::vector<char> host(b.bytes);
-  if (hipMemcpy(host.data(), b.dptr, b.bytes, hipMemcpyDeviceToHost) != hipSuccess) throw std::runtime_error("read back failed");
-  std::ofstream(path, std::ios::binary).write(host.data(), (std::streamsize)host.size());
-}
-
 int main(int argc, char** argv) {
-  if (argc != 2) {
-    std::printf("usage: shim_terrain_decode <dir>\n");
-    return 2;
-  }
-  try {
-    const std::string dir = argv[1];
-    const std::vector<char> raw = read_file(dir + "/params.bin");
-    if (raw.size() != sizeof(Params)) throw std::runtime_error("params.bin has the wrong size");
-    const Params& p = *reinterpret_cast<const Params*>(raw.data());
+  return run(argc, argv, "shim_terrain_decode", [](const std::string& dir) {
+    const Params p = read_params<Params>(dir);
     const size_t pixels = (size_t)p.width * p.height, texels = (size_t)p.map_resolution[0] * p.map_resolution[1];
     RendererInstance self(0);
-    const auto load = [&](const char* name, size_t bytes) { return device_buffer(bytes, dir + "/" + name + ".bin"); };
+    const auto load = [&](const char* name, size_t bytes) { return device_buffer(bytes, no_fill, dir + "/" + name + ".bin"); };
     TerrainDecodeContext context = {};
     context.renderer = &self;
     context.terrain = p.terrain;
@@ -79,9 +45,5 @@ int main(int argc, char** argv) {
     write_out(dir + "/emissive.out", context.emissive_attachment);
     write_out(dir + "/mro.out", context.metallic_roughness_occlusion_attachment);
     std::printf("terrain decode ok\n");
-    return 0;
-  } catch (const std::exception& e) {
-    std::fprintf(stderr, "%s\n", e.what());
-    return 1;
-  }
+  });
 }

@@ -4,9 +4,7 @@ buffers by a compiled C++ program (tests/cpp/shim_frame.cpp) in the order of Ren
 with the checker run live (two-pass occlusion in the reference's order: early cull -> new pyramid -> late cull)."""
 import ctypes as C
 import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,6 +14,7 @@ import oracle
 from oxylus_amd import lib as L
 from oxylus_amd.synth import hiz_layout, make_depth
 
+import shim_programs
 from util import oracle_hiz, scene_from_golden
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -49,28 +48,16 @@ def _image_desc(w, h, levels, offs, total):
     return struct.pack("<IIII13QQ", w, h, levels, 0, *(list(offs) + [0] * (13 - len(offs))), total)
 
 
-def build_shim_frame(tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    L.build()
-    exe = str(tmp_path / "shim_frame")
-    subprocess.check_call(["g++", "-std=c++20", "-O1", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "oxylus_amd", "host"), os.path.join(ROOT, "tests", "cpp", "shim_frame.cpp"), "-o", exe,
-                           "-L" + os.path.join(ROOT, "oxylus_amd"), "-loxcull", "-Wl,-rpath," + os.path.join(ROOT, "oxylus_amd"), "-L/opt/rocm/lib", "-lamdhip64",
-                           "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
-
-
 def test_shim_frame_program_builds(tmp_path):
     """(no GPU) the C++ driver compiles against the shim header + C ABI with plain g++ and links to liboxcull.so."""
-    exe = build_shim_frame(tmp_path)
-    p = subprocess.run([exe], capture_output=True, text=True)
+    exe = shim_programs.build("shim_frame", tmp_path)
+    p = shim_programs.run(exe)
     assert p.returncode == 2 and "usage" in p.stdout
 
 
 @pytest.mark.gpu
 def test_cpp_shim_runs_the_reference_sequence_with_data(tmp_path, oracle_lib):
-    exe = build_shim_frame(tmp_path)
+    exe = shim_programs.build("shim_frame", tmp_path)
     s, z = scene_from_golden(os.path.join(ROOT, "tests", "golden", "pipeline_12x40.npz"), "cpu")
     t = s._lod_tables
     Lc = s.spec.lod_count
@@ -106,7 +93,7 @@ def test_cpp_shim_runs_the_reference_sequence_with_data(tmp_path, oracle_lib):
               ("depth1desc", _image_desc(depth1.shape[1], depth1.shape[0], 1, [0], depth1.numel() * 4)), ("max_meshlets", struct.pack("<I", N))]
     fin, fout = str(tmp_path / "in.oxcf"), str(tmp_path / "out.oxcf")
     _write_container(fin, items)
-    p = subprocess.run([exe, fin, fout], capture_output=True, text=True)
+    p = shim_programs.run(exe, fin, fout)
     assert p.returncode == 0, p.stderr + p.stdout
     got = _read_container(fout)
     u32 = lambda b: np.frombuffer(b, dtype=np.uint32)  # noqa: E731

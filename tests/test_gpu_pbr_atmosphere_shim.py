@@ -1,33 +1,16 @@
 """The C++ shim reaches oxc_apply_pbr_atmosphere: tests/cpp/shim_atmosphere.cpp sets HasAtmosphere in gpu_scene_flags and calls
 ox::amd::RendererInstance::apply_pbr on the 33 x 17 synthetic frame; the image it writes equals the checker's."""
-import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
-from oxylus_amd import lib as L
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def build_program(tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    L.build()
-    exe = str(tmp_path / "shim_atmosphere")
-    subprocess.check_call(["g++", "-std=c++20", "-O1", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "oxylus_amd", "host"), os.path.join(ROOT, "tests", "cpp", "shim_atmosphere.cpp"), "-o", exe,
-                           "-L" + os.path.join(ROOT, "oxylus_amd"), "-loxcull", "-Wl,-rpath," + os.path.join(ROOT, "oxylus_amd"), "-L/opt/rocm/lib", "-lamdhip64",
-                           "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
+import shim_programs
 
 
 def test_the_program_builds(tmp_path):
     """(no GPU) the program compiles against the shim header and links to liboxcull.so."""
-    p = subprocess.run([build_program(tmp_path)], capture_output=True, text=True)
+    p = shim_programs.run(shim_programs.build("shim_atmosphere", tmp_path))
     assert p.returncode == 2 and "usage" in p.stdout
 
 
@@ -39,7 +22,7 @@ def test_the_shim_takes_the_atmosphere_branch(tmp_path):
     from oxylus_amd.synth import pack_lights
     from scenes import CAMERA, INV_PV, PBR_SUN, SUN_INTENSITY
 
-    exe = build_program(tmp_path)
+    exe = shim_programs.build("shim_atmosphere", tmp_path)
     inp = PF.frame()
     H, W = inp["depth"].shape
     A = PF.atmosphere("far")
@@ -50,7 +33,7 @@ def test_the_shim_takes_the_atmosphere_branch(tmp_path):
     (tmp_path / "params.bin").write_bytes(struct.pack("<4I23f", W, H, 32, 0, *INV_PV, *CAMERA, *PBR_SUN, SUN_INTENSITY) + record)
     for name, data in dict(inp, lights=lights, **sky).items():
         (tmp_path / f"{name}.bin").write_bytes(np.ascontiguousarray(data).tobytes())
-    p = subprocess.run([exe, str(tmp_path)], capture_output=True, text=True)
+    p = shim_programs.run(exe, tmp_path)
     assert p.returncode == 0 and "atmosphere branch ok" in p.stdout, p.stderr + p.stdout
     got = np.frombuffer((tmp_path / "final.bin").read_bytes(), dtype=np.uint32).reshape(H, W)
     same(got, PF.want(inp, PF.ALL_READ, A, sky, lights), "the shim's image")

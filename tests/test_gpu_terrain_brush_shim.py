@@ -1,33 +1,16 @@
 """The C++ shim reaches oxc_apply_terrain_brush: tests/cpp/shim_terrain_brush.cpp runs ox::amd::apply_terrain_brush -- trace, apply and the
 three regional passes with the reference's dispatch sizes -- on the 24 x 20 map; what it writes equals the Python path's bytes."""
 import dataclasses
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from oxylus_amd import lib as L
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def build_program(tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    L.build()
-    exe = str(tmp_path / "shim_terrain_brush")
-    subprocess.check_call(["g++", "-std=c++20", "-O1", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "oxylus_amd", "host"), os.path.join(ROOT, "tests", "cpp", "shim_terrain_brush.cpp"), "-o", exe,
-                           "-L" + os.path.join(ROOT, "oxylus_amd"), "-loxcull", "-Wl,-rpath," + os.path.join(ROOT, "oxylus_amd"), "-L/opt/rocm/lib", "-lamdhip64",
-                           "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
+import shim_programs
 
 
 def test_the_program_builds(tmp_path):
     """(no GPU) the program compiles against the shim header -- TerrainBrushContext and the free function -- and links to liboxcull.so."""
-    p = subprocess.run([build_program(tmp_path)], capture_output=True, text=True)
+    p = shim_programs.run(shim_programs.build("shim_terrain_brush", tmp_path))
     assert p.returncode == 2 and "usage" in p.stdout
 
 
@@ -40,7 +23,7 @@ def test_the_free_function_runs_the_edit_step(tmp_path, renderer):
     import terrain_maps_frames as TF
     from gpu_passes import same
 
-    exe = build_program(tmp_path)
+    exe = shim_programs.build("shim_terrain_brush", tmp_path)
     res, pc = BF.GOLDEN_SHAPE
     G, D = TF.engine(res)
     he, se = BF.edits(res)
@@ -50,7 +33,7 @@ def test_the_free_function_runs_the_edit_step(tmp_path, renderer):
     (tmp_path / "params.bin").write_bytes(bytes(BF.renderer_params(B).c()) + bytes(g.c()) + bytes(d.c()))
     for name in TF.IMAGES:
         (tmp_path / f"{name}.bin").write_bytes(images[name].tobytes())
-    p = subprocess.run([exe, str(tmp_path)], capture_output=True, text=True)
+    p = shim_programs.run(exe, tmp_path)
     assert p.returncode == 0 and "terrain brush ok" in p.stdout, p.stderr + p.stdout
 
     # the Python path: the same calls through the renderer
@@ -66,5 +49,4 @@ def test_the_free_function_runs_the_edit_step(tmp_path, renderer):
     python = {**TF.got_of(gs, images), **BF.got_of(records, {"hit": np.zeros(4, np.uint32), "region": np.zeros(4, np.uint32)})}
     assert python["hit"][3] == 1 and (python["height_edit"] != images["height_edit"]).any() and (python["heightmap"] != images["heightmap"]).any()
     for name, want in python.items():
-        got = np.frombuffer((tmp_path / f"{name}.out").read_bytes(), dtype=want.dtype).reshape(want.shape)
-        same(got, want, f"the shim's {name}")
+        same(shim_programs.read_out(tmp_path, name, want.dtype, want.shape), want, f"the shim's {name}")
