@@ -2048,7 +2048,7 @@ oxc_status oxc_apply_terrain_brush(oxc_ctx* ctx, const oxc_terrain_brush_context
  * oxc_decode_visbuffer on the same attachments.  The first consumer of the normal map and the splat map of oxc_generate_terrain_maps and of
  * the `hit` record of oxc_apply_terrain_brush.
  * Scope: the cut of oxc_decode_visbuffer -- the geometry and material-factor half of the shader; texture sampling is NOT done (D6).  The
- * tessellated terrain draw (terrain_visbuffer.slang) that produces the terrain texels and their depth stays out of scope.
+ * tessellated terrain draw (terrain_visbuffer.slang) that produces the terrain texels and their depth is oxc_draw_terrain below.
  * Arithmetic: the conventions of the terrain maps block (binary32, the Slang's expressions left to right, one rounding per operation, no
  * contraction; min / max / saturate through fmin / fmax, so saturate(NaN) = 0; length, normalize, lerp(a, b, t) = a + (b - a) * t and
  * smoothstep as oxc_apply_pbr states them; the unorm8 load f32(byte) / 255.0f; a binary16 load is exact, denormals kept); decimal literals
@@ -2140,6 +2140,91 @@ typedef struct oxc_terrain_decode_context {
 } oxc_terrain_decode_context;
 
 oxc_status oxc_decode_terrain(oxc_ctx* ctx, const oxc_terrain_decode_context* context, void* hip_stream);
+
+/* ---- the terrain draw: tessellated patches into the depth|vis image ---------------------------------------------------------------------------
+ * oxc_draw_terrain is RendererInstance::draw_terrain_for_visbuffer (Passes/Terrain.cpp:218-277, pipeline terrain_visbuffer,
+ * passes/terrain_visbuffer.slang): the consumer of oxc_cull_terrain's visible_patches and VkDrawIndirectCommand {4, instance_count, 0, 0} and
+ * the producer of the terrain texels oxc_decode_terrain reads.  It writes the u64 image of oxc_draw_visbuffer, so terrain and meshes compete
+ * per pixel; with it a frame with ground runs cull -> draw -> HiZ -> late cull -> decode -> PBR on the device
+ * (RendererInstance.cpp:868-884).  The reference's vertex positions come from the fixed-function tessellator, whose placement of the
+ * fractional-odd short segments and triangulation of the outer ring the Vulkan specification leaves open; as with the rasteriser, the rules
+ * are stated here (T1 - T7), implemented twice (tests/terrain_draw_model.py and the device code) and held to byte identity, and a stated
+ * rule is one of the behaviours the reference may legally show.
+ * Arithmetic: the conventions of the terrain maps block -- binary32, the Slang's expressions left to right, one rounding per operation, no
+ * contraction; lerp(a, b, t) = a + (b - a) * t; distance(a, b) = sqrt((dx * dx + dy * dy) + dz * dz) of d = a - b, IEEE sqrt; min / max /
+ * clamp through fminf / fmaxf (a NaN operand loses); IEEE division.  T = terrain (oxc_terrain_data).
+ *   T1. corners   (vs_main)  instance_count = draw_cmd[1] and first_instance = draw_cmd[3] are read on the device; words 0 and 2 are not
+ *              read.  For i in 0 .. instance_count - 1: p = visible_patches[first_instance + i] (the sum in 64 bits).  An entry at or past
+ *              the end of visible_patches_buffer (or past its first 2^24 entries, more than any grid has patches), or p >= T.patch_count.x * T.patch_count.y, is skipped and counted (the Slang would run
+ *              on garbage).  patch = (p % T.patch_count.x, p / T.patch_count.x).  Corner c of (0,0), (1,0), (1,1), (0,1) named p0 .. p3:
+ *              grid = f32(patch + c) / f32(T.patch_count) per component;  xz = T.world_min + grid * T.world_size (scene.slang:649-652):
+ *              neighbouring patches form the same integers, so a shared corner has the same bits.  y = sample_height(xz), step B3 of
+ *              oxc_apply_terrain_brush on the map_resolution.x x map_resolution.y heightmap with T's world_min, inv_world_size, base_height
+ *              and height_scale.  world = (xz.x, y, xz.y).
+ *   T2. factors   (edge_tessellation, hs_constants)  For an edge (a, b): center = (a + b) * 0.5 per component;  radius = distance(a, b) *
+ *              0.5;  view_distance = max(distance(center, camera_position) - radius, near_clip);  projected_pixels = ((2.0 * radius) *
+ *              projection_scale) / view_distance;  factor = clamp(projected_pixels / T.target_edge_pixels, 1.0, T.max_tessellation) =
+ *              fminf(fmaxf(q, 1.0), max_tessellation).  projection_scale is taken as given: the engine's value is resolution.y * 0.5 /
+ *              tan(radians(fov) * 0.5); the bindings have a helper that evaluates it in binary64 and rounds once, so no transcendental
+ *              enters the rule.  Edges 0: (p0, p3), 1: (p0, p1), 2: (p1, p2), 3: (p3, p2).  inside[0] = max(e1, e3) subdivides u;
+ *              inside[1] = max(e0, e2) subdivides v.  A patch with any edge factor <= 0 or NaN is discarded and counted (Vulkan's rule;
+ *              reachable with max_tessellation <= 0, or a NaN from the camera or the maps).
+ *   T3. fractional_odd subdivision of one factor f   fc = fminf(fmaxf(f, 1), 63);  n = the smallest odd integer >= fc;  r = 1.0f / fc;
+ *              s = (1.0f - f32(n - 2) * r) * 0.5f;  t_0 = 0, t_n = 1;  t_k = s + f32(k - 1) * r for 1 <= k <= (n - 1) / 2;  t_k = 1.0f -
+ *              t_(n-k) above that.  n == 1 gives {0, 1}.  That is n - 2 segments of length 1 / f and two shorter ones at the ends, which
+ *              shrink to nothing as f falls to n - 2.
+ *   T4. topology  (the Vulkan quad rule)  If all six n are 1 the patch is the two triangles (p0, p1, p2), (p0, p2, p3) in (u, v).
+ *              Otherwise an inner n of 1 is redone with fc = 0x3F800001 (n = 3), U = the inside[0] list (nu segments), V = the inside[1]
+ *              list (nv), and the patch is: the inner grid (U_i, V_j), 1 <= i <= nu - 1, 1 <= j <= nv - 1, every cell as ((i, j), (i+1, j),
+ *              (i+1, j+1)) and ((i, j), (i+1, j+1), (i, j+1));  and four ring strips -- side 0: outer points (0, t) over edge 0's list
+ *              against the inner points (U_1, V_j); side 1: (t, 0) over edge 1's list against (U_i, V_1); side 2: (1, t) over edge 2's
+ *              against (U_(nu-1), V_j); side 3: (t, 1) over edge 3's against (U_i, V_(nv-1)).  A strip is the merge of its two sorted
+ *              parameter lists from (outer 0, inner 1): advance the outer point when the inner list is exhausted, or when the outer list
+ *              is not exhausted and its next parameter <= the inner list's next parameter; otherwise advance the inner point.  The
+ *              triangle is (current outer, current inner, the point advanced to); on sides 1 and 2 its last two corners are exchanged.
+ *              With these orders every triangle of non-zero area is counter-clockwise in (u, v).  Triangles per patch: 2 (nu - 2)(nv - 2)
+ *              + sum over the sides of (n_side + n_inner_axis - 2), at most 7938.
+ *   T5. domain point  (ds_main)  a = lerp(p0, p1, u), b = lerp(p3, p2, u), q = lerp(a, b, v) on x and z;  world = (q.x,
+ *              sample_height(q.xz), q.z);  clip = mul(projection_view, (world, 1)) row by row, ((m0 x + m1 y) + m2 z) + m3, as
+ *              oxc_decode_visbuffer step 4.  Stated deviation: a lerp whose coordinate is exactly 0 or 1 returns its first or second operand
+ *              itself (the Slang's a + (b - a) * 1 can differ from b in the last bit).  With it the points of an edge two patches share
+ *              are bit-identical from both, and the top-left rule makes the seam watertight.  A point is evaluated once.
+ *   T6. facing    A triangle seen from +y is a front face: a triangle (c0, c1, c2) of T4 is handed to the set-up as (c0, c2, c1), the one
+ *              global exchange under which cullMode eBack of oxc_draw_visbuffer (fixed-point area >= 0 is dropped) keeps the triangles
+ *              a camera above the ground sees.  (DESIGN.md section 30 derives what the reference's state gives.)
+ *   T7. raster    The oxc_draw_visbuffer block unchanged on the three clip-space corners in T6's order: the clipper against the five
+ *              planes with its fan, set-up, cover, depth in (0, 1], with vis = 0xFFFFFE00 (VisBufferData(TERRAIN_INSTANCE_ID, 0).encode())
+ *              and the 64-bit maximum of depth bits << 32 | vis.  Terrain therefore wins an exact depth tie against every mesh texel: what
+ *              GreaterOrEqual with the terrain drawn second gives.
+ * `clear` zeroes the image first; without it the call adds to what oxc_draw_visbuffer or an earlier call left.  The optional resolves are
+ * those of oxc_draw_visbuffer (vis 0 / depth 0 for uncovered pixels).
+ * Limits (else OXC_INVALID_ARG, nothing launched, nothing written; the first broken rule in this order gives the message, each has its own):
+ * struct_size; width and height in 1 .. 16384; every side of map_resolution in 1 .. 16384; every side of terrain.patch_count in 1 .. 4096;
+ * then the buffers in the order heightmap, visible_patches_buffer, draw_cmd_buffer, visdepth_buffer -- non-null, then aligned to its texel
+ * (2, 4, 4 and 8 bytes), then at least as large as its extent (map texels of 2 bytes; one u32; 16 bytes; width * height u64);
+ * depth_attachment, when given, one R32F level of the draw's extent; visbuffer_attachment, when given, width * height u32.  Every float is
+ * taken as given.  The scratch (big list, tiles) is the one oxc_draw_visbuffer uses, allocated by whichever of the two draws runs first on
+ * the context: that first call must not be captured; afterwards the call allocates nothing, does not synchronise the host and is
+ * capturable into a HIP graph. */
+typedef struct oxc_terrain_draw_context {
+  uint32_t struct_size; /* sizeof(oxc_terrain_draw_context) */
+  uint32_t clear;
+  uint32_t width, height;
+  float projection_view[16]; /* Camera::projection_view, column-major */
+  float camera_position[3];
+  float near_clip;
+  float projection_scale;        /* T2 */
+  oxc_terrain_data terrain;      /* read: world_min, world_size, inv_world_size, patch_count, base_height, height_scale, target_edge_pixels, max_tessellation */
+  uint32_t map_resolution[2];    /* the extent of heightmap */
+  oxc_buffer heightmap;              /* in: u16 [map_resolution.y][.x], R16 Unorm, as oxc_generate_terrain_maps writes it */
+  oxc_buffer visible_patches_buffer; /* in: u32 patch indices, as oxc_cull_terrain writes them */
+  oxc_buffer draw_cmd_buffer;        /* in: VkDrawIndirectCommand {vertex_count, instance_count, first_vertex, first_instance}, read on the device */
+  oxc_buffer visdepth_buffer;        /* in/out: u64[height][width], the image of oxc_draw_visbuffer */
+  oxc_image depth_attachment;        /* optional resolve: R32F */
+  oxc_buffer visbuffer_attachment;   /* optional resolve: u32[height][width] */
+} oxc_terrain_draw_context;
+
+oxc_status oxc_draw_terrain(oxc_ctx* ctx, const oxc_terrain_draw_context* context, void* hip_stream);
 
 /* ---- the debug views: what the cull, the LOD select, the rasteriser, the decodes and the page update decided, as a picture ----------------
  * oxc_apply_debug_view is RendererInstance::apply_debug_view (Passes/Debug.cpp:9-153, pipelines debug_view and rmvsm_debug, shaders

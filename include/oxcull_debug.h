@@ -94,6 +94,8 @@ enum { OXC_TUNE_ASYNC_MTEST_BLOCKS_PER_CU = 0, OXC_TUNE_ASYNC_TRI_BLOCKS_PER_CU 
        OXC_TUNE_VSM_DRAW_GRID = 19 /* cap, in blocks, of every launch of oxc_draw_physical_pages (the prologue's x extent, the rows kernel and the clip queue's kernel included); 0 (default): uncapped (eight blocks per CU; 256 for the clip queue's kernel).  It takes effect at the next draw.  With it a small frame makes every wave run its stride loop several times.  Same outputs either way */,
        OXC_TUNE_BOUNDS_GRID = 20 /* cap, in blocks, of every grid-stride launch of oxc_build_meshlet_bounds and oxc_quantize_vertex_streams (the quantisers, the gather kernel and the mesh fold's partial kernel, whose block count the final fold then reads; the cone kernel runs a thread per meshlet and the final fold one block, so neither has a grid to cap); 0 (default): uncapped (eight blocks per CU for the quantisers, sixteen for the gather kernel, 256 partial blocks).  It takes effect at the next call.  With it a small mesh makes every wave and every fold thread run its stride loop several times.  Same outputs either way */,
        OXC_TUNE_BOUNDS_CHUNK = 21 /* meshlets per gather / cone launch pair of oxc_build_meshlet_bounds; 0 (default): 2^18.  Only the loop's step: the scratch keeps the layout and size of the default, so a value above 2^18 (or above the rows the scratch holds) is clamped.  It takes effect at the next call.  With it a small mesh is processed in several chunks with a ragged last one.  Same outputs either way */,
+       OXC_TUNE_TERRAIN_DRAW_GRID = 22 /* cap, in blocks, of every launch of oxc_draw_terrain; 0 (default): uncapped (eight blocks per CU).  It takes effect at the next draw.  With it a block takes several patches through its stride loop.  Same outputs either way */,
+       OXC_TUNE_TERRAIN_DRAW_STATS = 23 /* 1: oxc_draw_terrain runs counting instantiations of its kernel and of the big-list kernels (the fragment counter of oxc_debug_terrain_draw_stats); 0 (default): off.  Same image */,
        OXC_TUNE_FXAA_STATS = 17/* 1: oxc_apply_fxaa runs its counting instantiation (oxc_debug_fxaa_stats); 0 (default): off */,
        OXC_TUNE_BLOOM_TAIL_LEVEL = 16 /* the level T from which oxc_apply_bloom's one-block tail kernel takes over (downsample levels T .. L - 1, upsample levels back to T); 0 (default): chosen by the library; a value >= L: no tail kernel, one launch per level.  A forced T is raised to the first level whose source level has at most 16 384 texels (64 per thread of the one block), so the knob cannot turn a large image into one long single-block kernel.  Same outputs either way */ };
 oxc_status oxc_debug_set_tuning(oxc_ctx* ctx, uint32_t knob, uint32_t value);
@@ -108,6 +110,15 @@ oxc_status oxc_debug_count_occlusion_candidates(oxc_ctx* ctx, void* counters_dpt
  * out4 = {triangles queued for the big path (pixel box beyond 8 x 8), triangles that crossed a clip plane, 64 x 64 tiles handed to
  * the tile list, big-list segments that overflowed (their excess triangles were walked by the setup lane: slow, correct)}. */
 oxc_status oxc_debug_raster_stats(oxc_ctx* ctx, uint32_t* host_out4, void* hip_stream);
+
+/* Test hook: what the last oxc_draw_terrain on this context did (no draw of either kind since); synchronises the stream.
+ * out8 = {patches drawn, patches discarded by T2 (an edge factor <= 0 or NaN), list entries skipped by T1 (index out of range), triangles
+ * generated (T4's count over the drawn patches), triangles and clipper fan pieces the set-up kept (front-facing, non-zero area),
+ * triangles that crossed a clip plane, kept triangles and pieces queued for the big path (pixel box beyond 8 x 8, or the corners' spread
+ * at or beyond 4096 units for an unclipped one), fragments that passed the depth range (covered pixels of kept triangles with a depth in
+ * (0, 1]: one per atomic maximum issued, on every path -- in-wave boxes, the clipper's lane walks, big list, tiles)}.  The last is counted
+ * only after oxc_debug_set_tuning(OXC_TUNE_TERRAIN_DRAW_STATS, 1) (counting instantiations of the kernels, same image, slower); 0 otherwise. */
+oxc_status oxc_debug_terrain_draw_stats(oxc_ctx* ctx, uint32_t* host_out8, void* hip_stream);
 
 /* Measurement hook: what the last oxc_draw_physical_pages on this context did; synchronises the stream.
  * out8 = {(triangle, clipmap) pairs whose page box holds a drawable page, fragments written (page and depth tests passed: atomicMin

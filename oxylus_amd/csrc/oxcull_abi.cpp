@@ -171,6 +171,8 @@ oxc_status oxc_debug_set_tuning(oxc_ctx* ctx, uint32_t knob, uint32_t value) {
     case OXC_TUNE_FXAA_STATS: ctx->fxaa_stats.on = value != 0u; return OXC_OK;
     case OXC_TUNE_EYE_ADAPTATION_GRID: ctx->eye_adaptation_grid = value; return OXC_OK;
     case OXC_TUNE_RASTER_GRID: ctx->raster_grid = value; return OXC_OK;
+    case OXC_TUNE_TERRAIN_DRAW_GRID: ctx->terrain_draw_grid = value; return OXC_OK;
+    case OXC_TUNE_TERRAIN_DRAW_STATS: ctx->terrain_draw_stats = value != 0; return OXC_OK;
     case OXC_TUNE_VSM_DRAW_GRID: ctx->vsm_draw_grid = value; return OXC_OK;
     case OXC_TUNE_BOUNDS_GRID: ctx->bounds_grid = value; return OXC_OK;
     case OXC_TUNE_BOUNDS_CHUNK: ctx->bounds_chunk = value; return OXC_OK;

@@ -6,6 +6,33 @@
 // oxc_debug_set_tuning(OXC_TUNE_RASTER_BIG_CAPACITY) before that first draw shrinks it so that the tests can reach the overflow paths with a small scene.
 constexpr uint32_t kRasterBigCapacity = 1u << 22;
 
+// The scratch of the draws into the depth|vis image (oxc_draw_visbuffer, oxc_draw_terrain): allocated by whichever runs first on the context
+oxc_status ensure_raster_scratch(oxc_ctx* ctx, hipStream_t s, const char* capture_msg) {
+  if (ctx->raster_scratch) return OXC_OK;
+  if (stream_is_capturing(s)) return fail(ctx, OXC_INVALID_ARG, capture_msg);
+  uint32_t cap = kRasterBigCapacity;
+  if (ctx->raster_capacity_request) cap = std::min<uint32_t>(std::max<uint32_t>(ctx->raster_capacity_request, kBigSegs * 16), 1u << 24) / kBigSegs * kBigSegs;
+  hipError_t e = hipMalloc(&ctx->raster_scratch, (size_t)cap * kTriSetupBytes + kRasterHeaderBytes + (size_t)cap * 4 + (size_t)cap * 2 * 8);
+  if (e != hipSuccess) return fail(ctx, OXC_OUT_OF_MEMORY, "hipMalloc(raster scratch)", e);
+  ctx->raster_capacity = cap;
+  return OXC_OK;
+}
+
+// ... and its parts as the kernels see them: header (clip / tile counters, segment counters), big list, clip queue, tile list
+void bind_raster_scratch(const oxc_ctx* ctx, DrawArgs& a) {
+  char* const rs = static_cast<char*>(ctx->raster_scratch);
+  a.clip_count = reinterpret_cast<uint32_t*>(rs);
+  a.tile_count = reinterpret_cast<uint32_t*>(rs) + 32;
+  a.big_seg_counts = reinterpret_cast<uint32_t*>(rs + 256);
+  const uint32_t cap = ctx->raster_capacity;
+  a.big_seg_capacity = cap / kBigSegs;
+  a.big_list = reinterpret_cast<TriSetup*>(rs + kRasterHeaderBytes);
+  a.clip_capacity = cap;  // more clipped triangles than that in one draw: k_draw_clipped<RESCAN> finds them again
+  a.clip_list = reinterpret_cast<uint32_t*>(rs + kRasterHeaderBytes + (size_t)cap * kTriSetupBytes);
+  a.tile_capacity = cap * 2;
+  a.tile_list = reinterpret_cast<uint2*>(rs + kRasterHeaderBytes + (size_t)cap * (kTriSetupBytes + 4));
+}
+
 extern "C" {
 
 oxc_status oxc_draw_visbuffer(oxc_ctx* ctx, const oxc_prepared_frame* f, const oxc_draw_context* d, void* hip_stream) {
@@ -24,14 +51,7 @@ oxc_status oxc_draw_visbuffer(oxc_ctx* ctx, const oxc_prepared_frame* f, const o
   if (d->visbuffer_attachment.dptr && d->visbuffer_attachment.bytes < n * 4u) return fail(ctx, OXC_INVALID_ARG, "draw_visbuffer: visbuffer_attachment smaller than width*height u32");
   OXC_ENTER(ctx, hip_stream, s);
   OXC_JOIN(ctx, s);  // reads reordered_indices / the draw command
-  if (!ctx->raster_scratch) {
-    if (stream_is_capturing(s)) return fail(ctx, OXC_INVALID_ARG, "draw_visbuffer: the first call allocates its scratch; make one un-captured call first");
-    uint32_t cap = kRasterBigCapacity;
-    if (ctx->raster_capacity_request) cap = std::min<uint32_t>(std::max<uint32_t>(ctx->raster_capacity_request, kBigSegs * 16), 1u << 24) / kBigSegs * kBigSegs;
-    hipError_t e = hipMalloc(&ctx->raster_scratch, (size_t)cap * kTriSetupBytes + kRasterHeaderBytes + (size_t)cap * 4 + (size_t)cap * 2 * 8);
-    if (e != hipSuccess) return fail(ctx, OXC_OUT_OF_MEMORY, "hipMalloc(raster scratch)", e);
-    ctx->raster_capacity = cap;
-  }
+  OXC_TRY(ensure_raster_scratch(ctx, s, "draw_visbuffer: the first call allocates its scratch; make one un-captured call first"));
   OXC_TRY(grow_scratch(ctx, s, ctx->raster_rows, ctx->raster_rows_cap, f->mesh_instance_count, (size_t)f->mesh_instance_count * sizeof(DrawRow),
                        "draw_visbuffer: more mesh instances than any earlier call (scratch would grow); make one un-captured call first", "hipMalloc(raster rows)"));
   DrawArgs a;
@@ -49,17 +69,7 @@ oxc_status oxc_draw_visbuffer(oxc_ctx* ctx, const oxc_prepared_frame* f, const o
   a.width = d->width;
   a.height = d->height;
   a.wide = d->wide_triangle_index;
-  char* const rs = static_cast<char*>(ctx->raster_scratch);
-  a.clip_count = reinterpret_cast<uint32_t*>(rs);
-  a.tile_count = reinterpret_cast<uint32_t*>(rs) + 32;
-  a.big_seg_counts = reinterpret_cast<uint32_t*>(rs + 256);
-  const uint32_t cap = ctx->raster_capacity;
-  a.big_seg_capacity = cap / kBigSegs;
-  a.big_list = reinterpret_cast<TriSetup*>(rs + kRasterHeaderBytes);
-  a.clip_capacity = cap;  // more clipped triangles than that in one draw: k_draw_clipped<RESCAN> finds them again
-  a.clip_list = reinterpret_cast<uint32_t*>(rs + kRasterHeaderBytes + (size_t)cap * kTriSetupBytes);
-  a.tile_capacity = cap * 2;
-  a.tile_list = reinterpret_cast<uint2*>(rs + kRasterHeaderBytes + (size_t)cap * (kTriSetupBytes + 4));
+  bind_raster_scratch(ctx, a);
   const uint32_t full_grid = ctx->num_cus * 8;
   const uint32_t max_grid = ctx->raster_grid ? std::min(ctx->raster_grid, full_grid) : full_grid;  // OXC_TUNE_RASTER_GRID
   {

@@ -1,7 +1,7 @@
 // oxcull_abi_terrain.cpp -- the terrain map producers of liboxcull.so's C ABI: oxc_generate_terrain_maps (height, ridge, normal, splat and the
 // per-patch min / max), oxc_apply_terrain_brush (the brush ray trace and the strokes into the edit images) and oxc_decode_terrain (the
-// G-buffer of the terrain pixels, the consumer of the normal map, the splat map and the hit record).  The terrain cull, the consumer of
-// the min / max, is in oxcull_abi_cull.cpp.
+// G-buffer of the terrain pixels, the consumer of the normal map, the splat map and the hit record) -- and oxc_draw_terrain, the tessellated
+// patches into the depth|vis image, with its stats reader.  The terrain cull, the consumer of the min / max, is in oxcull_abi_cull.cpp.
 #include "oxcull_host.hpp"
 
 namespace {
@@ -168,6 +168,63 @@ oxc_status oxc_decode_terrain(oxc_ctx* ctx, const oxc_terrain_decode_context* c,
   a.mro = static_cast<uint32_t*>(mro.dptr);
   launch_terrain_decode(a, s);
   OXC_HIP(ctx, hipGetLastError());
+  return OXC_OK;
+}
+
+oxc_status oxc_draw_terrain(oxc_ctx* ctx, const oxc_terrain_draw_context* c, void* hip_stream) {
+  if (!ctx) return OXC_INVALID_ARG;
+  if (!c || c->struct_size != sizeof(oxc_terrain_draw_context)) return fail(ctx, OXC_INVALID_ARG, "draw_terrain: bad context / struct_size");
+  const char* const entry = "draw_terrain";
+  const oxc_terrain_data& T = c->terrain;
+  if (c->width < 1u || c->width > 16384u || c->height < 1u || c->height > 16384u) return bad_arg(ctx, entry, "the extent must be 1 .. 16384 a side");
+  const uint32_t *res = c->map_resolution, *pc = T.patch_count;
+  if (res[0] < 1u || res[0] > 16384u || res[1] < 1u || res[1] > 16384u) return bad_arg(ctx, entry, "map_resolution: every side must be in 1 .. 16384");
+  if (pc[0] < 1u || pc[0] > 4096u || pc[1] < 1u || pc[1] > 4096u) return bad_arg(ctx, entry, "terrain.patch_count: every side must be in 1 .. 4096");
+  const uint64_t pixels = (uint64_t)c->width * c->height, texels = (uint64_t)res[0] * res[1];
+  const oxc_buffer &vp = c->visible_patches_buffer, &cmd = c->draw_cmd_buffer, &vd = c->visdepth_buffer;
+  const MapBuffer buffers[] = {
+      {"heightmap", c->heightmap.dptr, c->heightmap.bytes, texels * 2u, 2u, 1u, 0u, false},
+      {"visible_patches_buffer", vp.dptr, vp.bytes, 4u, 4u, 1u, 0u, false},
+      {"draw_cmd_buffer", cmd.dptr, cmd.bytes, 16u, 4u, 1u, 0u, false},
+      {"visdepth_buffer", vd.dptr, vd.bytes, pixels * 8u, 8u, 1u, 1u, false},
+  };
+  if (const oxc_status st = check_buffers(ctx, entry, buffers, 1u)) return st;
+  const oxc_image& dep = c->depth_attachment;
+  if (dep.dptr && (dep.width != c->width || dep.height != c->height || dep.levels != 1u)) return bad_arg(ctx, entry, "depth_attachment must be one R32F level of the draw's extent");
+  if (c->visbuffer_attachment.dptr && c->visbuffer_attachment.bytes < pixels * 4u) return bad_arg(ctx, entry, "visbuffer_attachment smaller than width * height u32");
+
+  OXC_ENTER(ctx, hip_stream, s);
+  OXC_TRY(ensure_raster_scratch(ctx, s, "draw_terrain: the first draw of a context allocates the raster scratch; make one un-captured call first"));
+  TerrainDrawArgs a;
+  std::memset(&a, 0, sizeof a);
+  std::memcpy(a.r.pv, c->projection_view, 64);
+  a.r.visdepth = static_cast<unsigned long long*>(vd.dptr);
+  a.r.width = c->width, a.r.height = c->height;
+  bind_raster_scratch(ctx, a.r);
+  for (int k = 0; k < 3; k++) a.camera_position[k] = c->camera_position[k];
+  a.near_clip = c->near_clip, a.projection_scale = c->projection_scale;
+  a.t = T;
+  a.map_w = res[0], a.map_h = res[1];
+  a.heightmap = static_cast<const uint16_t*>(c->heightmap.dptr);
+  a.visible = static_cast<const uint32_t*>(vp.dptr);
+  a.visible_capacity = std::min<uint64_t>(vp.bytes / 4u, 1ull << 24);  // no list of distinct patches is longer: what lies beyond is skipped like an entry past the end
+  a.draw_cmd = static_cast<const uint32_t*>(cmd.dptr);
+  a.stats = a.r.clip_count + kTerrainStatsWord;
+  const uint32_t full_grid = ctx->num_cus * 8;
+  const uint32_t max_grid = ctx->terrain_draw_grid ? std::min(ctx->terrain_draw_grid, full_grid) : full_grid;  // OXC_TUNE_TERRAIN_DRAW_GRID
+  launch_draw_terrain(a, c->clear != 0, ctx->terrain_draw_stats, dep.dptr ? reinterpret_cast<float*>(static_cast<char*>(dep.dptr) + dep.level_offset[0]) : nullptr,
+                      static_cast<uint32_t*>(c->visbuffer_attachment.dptr), max_grid, s);
+  OXC_HIP(ctx, hipGetLastError());
+  return OXC_OK;
+}
+
+oxc_status oxc_debug_terrain_draw_stats(oxc_ctx* ctx, uint32_t* host_out8, void* hip_stream) {
+  if (!ctx) return OXC_INVALID_ARG;
+  if (!host_out8) return fail(ctx, OXC_INVALID_ARG, "debug_terrain_draw_stats: null pointer");
+  if (!ctx->raster_scratch) return fail(ctx, OXC_INVALID_ARG, "debug_terrain_draw_stats: no oxc_draw_terrain call on this context yet");
+  OXC_ENTER(ctx, hip_stream, s);
+  OXC_HIP(ctx, hipMemcpyAsync(host_out8, static_cast<const uint32_t*>(ctx->raster_scratch) + kTerrainStatsWord, 32, hipMemcpyDeviceToHost, s));
+  OXC_HIP(ctx, hipStreamSynchronize(s));
   return OXC_OK;
 }
 

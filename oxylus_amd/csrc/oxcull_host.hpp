@@ -86,6 +86,8 @@ struct oxc_ctx {
   uint32_t raster_capacity = 0;    // entries of the big / clip lists (the tile list has twice as many)
   uint32_t raster_capacity_request = 0;  // oxc_debug_set_tuning(OXC_TUNE_RASTER_BIG_CAPACITY): used by the first draw instead of the default
   uint32_t raster_grid = 0;              // OXC_TUNE_RASTER_GRID: cap of every launch of the draw in blocks, 0 = uncapped
+  uint32_t terrain_draw_grid = 0;        // OXC_TUNE_TERRAIN_DRAW_GRID: the same for oxc_draw_terrain
+  bool terrain_draw_stats = false;       // OXC_TUNE_TERRAIN_DRAW_STATS: counting kernels (the fragment counter)
   void* raster_rows = nullptr;     // oxc_draw_visbuffer: one DrawRow per mesh instance
   uint32_t raster_rows_cap = 0;
   void* sprite_scratch = nullptr;  // oxc_draw_sprites: records, boxes, the clipped sprites' side array, bin counts and bin lists
@@ -258,6 +260,11 @@ inline oxc_status order_stream(oxc_ctx* ctx, hipStream_t s) {
   ctx->has_last_stream = true;
   return OXC_OK;
 }
+
+// The scratch the draws into the depth|vis image share (oxcull_abi_raster.cpp): allocated by the first of them, never inside a capture
+// (`capture_msg`); bind_raster_scratch points the kernels' argument struct at its parts.
+oxc_status ensure_raster_scratch(oxc_ctx* ctx, hipStream_t s, const char* capture_msg);
+void bind_raster_scratch(const oxc_ctx* ctx, DrawArgs& a);
 
 // Grows the lane's scratch arena when the call needs more than it holds (oxcull_abi_cull.cpp; oxc_reserve calls it too)
 oxc_status ensure_capacity(oxc_ctx* ctx, uint32_t mesh_instances, uint32_t meshlets, uint32_t views = 0, uint32_t lane_index = 0, hipStream_t s = nullptr);

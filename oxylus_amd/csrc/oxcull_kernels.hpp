@@ -435,6 +435,11 @@ struct DrawArgs {
   uint32_t* tile_count;
 };
 void launch_draw_visbuffer(const DrawArgs& a, bool clear, float* depth_out, uint32_t* vis_out, uint32_t max_grid, hipStream_t s);
+// its launches around the draw's own kernels, which oxc_draw_terrain takes as well: the clears (image with `clear`, scratch header always), the
+// big list with its tiles, the optional resolve.  They read visdepth, width, height and the big / tile / clip fields of `a`.
+void launch_draw_clear(const DrawArgs& a, bool clear, uint32_t max_grid, hipStream_t s);
+void launch_draw_big(const DrawArgs& a, uint32_t max_grid, hipStream_t s, uint32_t* fragments = nullptr);  // fragments: the counting instantiations add theirs to it
+void launch_resolve_visbuffer(const DrawArgs& a, float* depth_out, uint32_t* vis_out, uint32_t max_grid, hipStream_t s);
 constexpr uint32_t kTriSetupBytes = 40;
 constexpr uint32_t kBigSegs = 256, kBigSegStride = 16;
 constexpr uint32_t kRasterHeaderBytes = 256 + kBigSegs * kBigSegStride * 4;  // clip / tile counters, then the segment counters
@@ -829,6 +834,20 @@ struct TerrainDecodeArgs {
   uint32_t* mro;
 };
 void launch_terrain_decode(const TerrainDecodeArgs& a, hipStream_t s);
+// oxcull_terrain_draw.hip: the tessellated terrain patches into the depth|vis image (oxc_draw_terrain)
+constexpr uint32_t kTerrainStatsWord = 8;  // the call's eight counters are words 8 .. 15 of the raster scratch header, zeroed with it
+struct TerrainDrawArgs {
+  DrawArgs r;  // pv, visdepth, width, height and the big / tile lists of the shared raster scratch; the mesh fields stay null
+  float camera_position[3], near_clip, projection_scale;
+  oxc_terrain_data t;
+  uint32_t map_w, map_h;
+  const uint16_t* heightmap;
+  const uint32_t* visible;    // visible_patches
+  uint64_t visible_capacity;  // its entries
+  const uint32_t* draw_cmd;   // VkDrawIndirectCommand: [1] = instanceCount, [3] = firstInstance
+  uint32_t* stats;            // u32[8]
+};
+void launch_draw_terrain(const TerrainDrawArgs& a, bool clear, bool count_fragments, float* depth_out, uint32_t* vis_out, uint32_t max_grid, hipStream_t s);
 // oxcull_debug_view.hip: the debug views (oxc_apply_debug_view)
 struct DebugViewArgs {  // the main views, OXC_DEBUG_VIEW_TRIANGLES .. OXC_DEBUG_VIEW_GEOMETRIC_NORMAL
   uint32_t w, h, clear, meshlet_instance_count;

@@ -17,90 +17,16 @@
 //
 // The rules themselves -- clip planes and clipper, index decode and vertex fetch, row builder, snap and cull mode, pixel box, edge
 // functions, top-left rule, depth interpolation, the box-distribution pass -- live in oxcull_raster_device.hpp, shared with the VSM shadow
-// draw (oxcull_vsm_draw.hip).  This file keeps what is the visbuffer draw's own: cullMode eBack, the zf > 0 depth test, the 64-bit
-// atomicMax of depth|vis, the segmented big list with its 64 x 64 tiles, and the launches.
+// draw (oxcull_vsm_draw.hip).  What is the depth|vis image's own and the terrain draw (oxcull_terrain_draw.hip) needs as well -- cullMode
+// eBack, the zf > 0 depth test, the 64-bit atomicMax of depth|vis, the push into the segmented big list -- is in
+// oxcull_visbuffer_device.hpp.  This file keeps the vertex fetch, the kernels that walk the big list and its 64 x 64 tiles, and the launches.
 #include <hip/hip_runtime.h>
 
-#include "oxcull_raster_device.hpp"
+#include "oxcull_visbuffer_device.hpp"
 
 #pragma clang fp contract(off)
 
 namespace oxc {
-
-struct TriSetup {
-  int32_t x[3], y[3];  // 24.8 fixed point, oriented with positive area
-  float z[3];
-  uint32_t vis;
-};
-constexpr int64_t kBigTile = 64;
-
-static_assert(sizeof(TriSetup) == kTriSetupBytes, "layout");
-
-struct TriRaster {
-  int64_t X[3], Y[3];
-  float z[3];
-  uint32_t vis;
-  int64_t area, b0, b1, b2;
-  int64_t px0, px1, py0, py1;
-  double inv_area;
-  int64_t dx0, dx1, dx2, dy0, dy1, dy2;  // change of the three edge functions per pixel step in x / in y (exact)
-};
-
-OXC_DEV void tri_prepare(const TriSetup& t, uint32_t W, uint32_t H, TriRaster& r) {
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    r.X[k] = t.x[k];
-    r.Y[k] = t.y[k];
-    r.z[k] = t.z[k];
-  }
-  r.vis = t.vis;
-  r.area = edge_fn(r.X[0], r.Y[0], r.X[1], r.Y[1], r.X[2], r.Y[2]);
-  int32_t px0, py0, px1, py1;
-  (void)pixel_box(t, (int32_t)W, (int32_t)H, px0, py0, px1, py1);
-  r.px0 = px0, r.py0 = py0, r.px1 = px1, r.py1 = py1;
-  r.b0 = edge_inclusive(r.X[1], r.Y[1], r.X[2], r.Y[2]) ? 0 : -1;
-  r.b1 = edge_inclusive(r.X[2], r.Y[2], r.X[0], r.Y[0]) ? 0 : -1;
-  r.b2 = edge_inclusive(r.X[0], r.Y[0], r.X[1], r.Y[1]) ? 0 : -1;
-  r.inv_area = 1.0 / (double)r.area;  // one reciprocal per triangle
-  // E(a->b)(p) = (bx - ax)(py - ay) - (by - ay)(px - ax): one pixel = 256 units
-  r.dx0 = -(r.Y[2] - r.Y[1]) * 256;
-  r.dy0 = (r.X[2] - r.X[1]) * 256;
-  r.dx1 = -(r.Y[0] - r.Y[2]) * 256;
-  r.dy1 = (r.X[0] - r.X[2]) * 256;
-  r.dx2 = -(r.Y[1] - r.Y[0]) * 256;
-  r.dy2 = (r.X[1] - r.X[0]) * 256;
-}
-
-// edge values (weights of corners 0, 1, 2) at the centre of pixel (px, py)
-OXC_DEV void tri_edges(const TriRaster& r, int64_t px, int64_t py, int64_t& e0, int64_t& e1, int64_t& e2) {
-  const int64_t cx = px * 256 + 128, cy = py * 256 + 128;
-  e0 = edge_fn(r.X[1], r.Y[1], r.X[2], r.Y[2], cx, cy);
-  e1 = edge_fn(r.X[2], r.Y[2], r.X[0], r.Y[0], cx, cy);
-  e2 = edge_fn(r.X[0], r.Y[0], r.X[1], r.Y[1], cx, cy);
-}
-// fs of a covered pixel: depth test, then the maximum of depth|vis (I: the width of the edge values, P: of the pixel coordinates)
-template <class I, class P>
-OXC_DEV void fragment(I e0, I e1, I e2, float z0, float z1, float z2, double inv_area, uint32_t vis, P px, P py, uint32_t W, unsigned long long* visdepth) {
-  const float zf = interpolate_depth(e0, e1, e2, z0, z1, z2, inv_area);
-  if (!(zf > 0.0f) || zf > 1.0f) return;
-  const unsigned long long packed = ((unsigned long long)asu(zf) << 32) | vis;
-  // (reading the stored value first to skip occluded fragments was measured slower: 1.61 -> 2.15 ms per frame)
-  atomicMax(&visdepth[(size_t)py * W + (size_t)px], packed);
-}
-OXC_DEV void tri_fragment(const TriRaster& r, int64_t e0, int64_t e1, int64_t e2, int64_t px, int64_t py, uint32_t W, unsigned long long* visdepth) {
-  if (covered(e0, e1, e2, r.b0, r.b1, r.b2)) fragment(e0, e1, e2, r.z[0], r.z[1], r.z[2], r.inv_area, r.vis, px, py, W, visdepth);
-}
-
-// SmallTri with the triangle's vis value (56 bytes).  A record of its own, not SmallTri plus a trailing word: with vis behind misc
-// k_draw_setup moves its record with two more LDS instructions, and the draw at 3840 x 2160 measured 0.06 ms (0.6 %) over the parent,
-// twice the parent's own spread in that session (profiles/raster_device_timing.jsonl).
-struct TriLds {
-  int32_t x[3], y[3];
-  float z[3];
-  uint32_t vis;
-  uint32_t inv_area_lo, inv_area_hi;
-  uint32_t box, misc;
-};
 
 __global__ __launch_bounds__(256) void k_draw_rows(DrawArgs a) { build_draw_rows(a); }
 
@@ -118,61 +44,6 @@ OXC_DEV void tri_clip_coords(const DrawArgs& a, const IdxEntry<PAIR> (&idx)[3], 
     mul_mp4(a.pv, world, clip[k]);
     if (k == 0) vis_out = (mli_index << 8) | ((corner / 3u) & 0xFFu);  // VisBufferData(mli, triangle_index / 3).encode()
   }
-}
-
-// setup_tri with cullMode eBack for the draw's extent
-OXC_DEV bool tri_finish(const DrawArgs& a, const float* c0, const float* c1, const float* c2, uint32_t vis, TriSetup& out, int32_t& spread) {
-  out.vis = vis;
-  return setup_tri<true>((float)a.width, (float)a.height, c0, c1, c2, out, spread);
-}
-
-// one lane walks a pixel rectangle of its triangle
-OXC_DEV void walk_box(const DrawArgs& a, const TriRaster& r, int64_t x0, int64_t y0, int64_t x1, int64_t y1) {
-  int64_t r0, r1, r2;  // edge values at the start of the row: stepped exactly (integers) instead of re-multiplied
-  tri_edges(r, x0, y0, r0, r1, r2);
-  for (int64_t py = y0; py <= y1; py++) {
-    int64_t e0 = r0, e1 = r1, e2 = r2;
-    for (int64_t px = x0; px <= x1; px++) {
-      tri_fragment(r, e0, e1, e2, px, py, a.width, a.visdepth);
-      e0 += r.dx0;
-      e1 += r.dx1;
-      e2 += r.dx2;
-    }
-    r0 += r.dy0;
-    r1 += r.dy1;
-    r2 += r.dy2;
-  }
-}
-
-// A triangle whose pixel box exceeds kSmallSpan goes to segment `seg` of the big list (k_draw_big: one wave per triangle).  A triangle
-// that does not fit its segment any more is walked by this lane (slow, correct).
-OXC_DEV void push_big(const DrawArgs& a, const TriSetup& t, uint32_t seg) {
-  const uint32_t slot = atomicAdd(a.big_seg_counts + seg * kBigSegStride, 1u);
-  if (slot < a.big_seg_capacity) {
-    a.big_list[(size_t)seg * a.big_seg_capacity + slot] = t;
-    return;
-  }
-  TriRaster r;
-  tri_prepare(t, a.width, a.height, r);
-  for (int64_t py = r.py0; py <= r.py1; py++)
-    for (int64_t px = r.px0; px <= r.px1; px++) {
-      int64_t e0, e1, e2;
-      tri_edges(r, px, py, e0, e1, e2);
-      tri_fragment(r, e0, e1, e2, px, py, a.width, a.visdepth);
-    }
-}
-
-// rasterise one set-up triangle from this lane (small ones) or queue it for k_draw_big
-OXC_DEV void tri_emit(const DrawArgs& a, const TriSetup& t, uint32_t seg) {
-  TriRaster r;
-  tri_prepare(t, a.width, a.height, r);
-  if (r.px1 < r.px0 || r.py1 < r.py0) return;
-  const bool small = (r.px1 - r.px0) < kSmallSpan && (r.py1 - r.py0) < kSmallSpan;
-  if (!small) {
-    push_big(a, t, seg);
-    return;
-  }
-  walk_box(a, r, r.px0, r.py0, r.px1, r.py1);
 }
 
 template <bool PAIR>
@@ -280,19 +151,19 @@ __global__ __launch_bounds__(64) void k_draw_clipped(DrawArgs a) {
 }
 
 // A pixel rectangle of a big triangle's box, walked by a wave in 8 x 8 pixel blocks (lane = pixel of the block), 64-bit edge functions.
-OXC_DEV void raster_rect64(const DrawArgs& a, const TriRaster& r, int64_t ox, int64_t oy, int64_t x1, int64_t y1, int lane) {
+OXC_DEV void raster_rect64(const DrawArgs& a, const TriRaster& r, int64_t ox, int64_t oy, int64_t x1, int64_t y1, int lane, uint32_t* tally = nullptr) {
   for (int64_t by = oy; by <= y1; by += 8)
     for (int64_t bx = ox; bx <= x1; bx += 8) {
       const int64_t px = bx + (lane & 7), py = by + (lane >> 3);
       if (px <= x1 && py <= y1) {
         int64_t e0, e1, e2;
         tri_edges(r, px, py, e0, e1, e2);
-        tri_fragment(r, e0, e1, e2, px, py, a.width, a.visdepth);
+        tri_fragment(r, e0, e1, e2, px, py, a.width, a.visdepth, tally);
       }
     }
 }
 // The same with 32-bit edge functions when they are exact for this rectangle (wave-uniform test).
-OXC_DEV void raster_rect(const DrawArgs& a, const TriRaster& r, int64_t ox, int64_t oy, int64_t x1, int64_t y1, int lane) {
+OXC_DEV void raster_rect(const DrawArgs& a, const TriRaster& r, int64_t ox, int64_t oy, int64_t x1, int64_t y1, int lane, uint32_t* tally = nullptr) {
   // every difference the edge functions of this rectangle see: corner - corner, pixel centre - corner
   const int64_t cx0 = ox * 256 + 128, cx1 = x1 * 256 + 128, cy0 = oy * 256 + 128, cy1 = y1 * 256 + 128;
   const int64_t lox = min(min(min(r.X[0], r.X[1]), r.X[2]), cx0), hix = max(max(max(r.X[0], r.X[1]), r.X[2]), cx1);
@@ -306,11 +177,11 @@ OXC_DEV void raster_rect(const DrawArgs& a, const TriRaster& r, int64_t ox, int6
           const int32_t cx = px * 256 + 128, cy = py * 256 + 128;
           const int32_t e0 = edge_fn32(X1, Y1, X2, Y2, cx, cy), e1 = edge_fn32(X2, Y2, X0, Y0, cx, cy), e2 = edge_fn32(X0, Y0, X1, Y1, cx, cy);
           if (covered(e0, e1, e2, (int32_t)r.b0, (int32_t)r.b1, (int32_t)r.b2))
-            fragment(e0, e1, e2, r.z[0], r.z[1], r.z[2], r.inv_area, r.vis, (uint32_t)px, (uint32_t)py, a.width, a.visdepth);
+            fragment(e0, e1, e2, r.z[0], r.z[1], r.z[2], r.inv_area, r.vis, (uint32_t)px, (uint32_t)py, a.width, a.visdepth, tally);
         }
       }
   } else {
-    raster_rect64(a, r, ox, oy, x1, y1, lane);
+    raster_rect64(a, r, ox, oy, x1, y1, lane, tally);
   }
 }
 
@@ -319,67 +190,51 @@ OXC_DEV void raster_rect(const DrawArgs& a, const TriRaster& r, int64_t ox, int6
 // at most 64 x 64 pixels (nearly all) is walked at once; a larger one is cut into 64 x 64 tiles that go to the tile list
 // (k_draw_big_tiles: one wave per tile), so a screen-filling triangle becomes a thousand balanced items.
 __global__ __launch_bounds__(256) void k_draw_big(DrawArgs a) {
-  __shared__ uint32_t s_prefix[kBigSegs + 1];
-  __shared__ uint32_t s_wsum[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  {  // the segments' fill counts -> exclusive prefix (every block computes the same 256-entry scan)
-    static_assert(kBigSegs == 256, "one count per thread");
-    const uint32_t c = min(a.big_seg_counts[threadIdx.x * kBigSegStride], a.big_seg_capacity);
-    const uint32_t incl = wave_incl_scan(c, lane);
-    if (lane == 63) s_wsum[wave] = incl;
-    __syncthreads();
-    uint32_t base = 0;
-    for (int w = 0; w < wave; w++) base += s_wsum[w];
-    s_prefix[threadIdx.x + 1] = base + incl;
-    if (threadIdx.x == 0) s_prefix[0] = 0;
-    __syncthreads();
-  }
-  const uint32_t total = s_prefix[kBigSegs];
-  const uint32_t wave_id = blockIdx.x * 4u + (uint32_t)wave, nwaves = gridDim.x * 4u;
-  for (uint32_t i = wave_id; i < total; i += nwaves) {  // wave-uniform
-    uint32_t seg = 0;  // the segment task i falls into: the last one whose prefix is <= i
-#pragma unroll
-    for (uint32_t stp = kBigSegs / 2; stp >= 1u; stp >>= 1)
-      if (s_prefix[seg + stp] <= i) seg += stp;
-    const uint32_t slot = seg * a.big_seg_capacity + (i - s_prefix[seg]);
-    TriRaster r;
-    tri_prepare(a.big_list[slot], a.width, a.height, r);
-    const uint32_t ntx = (uint32_t)((r.px1 - r.px0 + kBigTile) / kBigTile), nty = (uint32_t)((r.py1 - r.py0 + kBigTile) / kBigTile);
-    const uint32_t n = ntx * nty;
-    if (n == 1u) {
-      raster_rect(a, r, r.px0, r.py0, r.px1, r.py1, lane);
-      continue;
-    }
-    uint32_t first = 0;
-    if (lane == 0) first = atomicAdd(a.tile_count, n);
-    first = readlane_u(first, 0);
-    for (uint32_t k = (uint32_t)lane; k < n; k += 64u) {
-      if (first + k < a.tile_capacity && first + k >= first) a.tile_list[first + k] = make_uint2(slot, k);
-    }
-    if (first + n > a.tile_capacity || first + n < first) {  // the tile list is full: the tiles that did not fit are walked here (slow, correct)
-#pragma clang loop unroll(disable)
-      for (uint32_t k = 0; k < n; k++) {
-        if (first + k < a.tile_capacity && first + k >= first) continue;
-        const int64_t ox = r.px0 + (int64_t)(k % ntx) * kBigTile, oy = r.py0 + (int64_t)(k / ntx) * kBigTile;
-        raster_rect64(a, r, ox, oy, min(ox + kBigTile - 1, r.px1), min(oy + kBigTile - 1, r.py1), lane);
-      }
-    }
-  }
+#define OXC_BIG_PART 1
+#define OXC_BIG_TALLY nullptr
+#include "oxcull_draw_big.inc"
+#undef OXC_BIG_TALLY
+#undef OXC_BIG_PART
 }
+
 
 // One wave per tile-list item: a 64 x 64 pixel tile of a triangle whose box is larger than that.
 __global__ __launch_bounds__(256) void k_draw_big_tiles(DrawArgs a) {
-  const uint32_t count = min(*a.tile_count, a.tile_capacity);
-  const int lane = threadIdx.x & 63;
-  const uint32_t wave_id = blockIdx.x * 4u + (threadIdx.x >> 6), nwaves = gridDim.x * 4u;
-  for (uint32_t i = wave_id; i < count; i += nwaves) {
-    const uint2 item = a.tile_list[i];
-    TriRaster r;
-    tri_prepare(a.big_list[item.x], a.width, a.height, r);
-    const uint32_t ntx = (uint32_t)((r.px1 - r.px0 + kBigTile) / kBigTile);
-    const int64_t ox = r.px0 + (int64_t)(item.y % ntx) * kBigTile, oy = r.py0 + (int64_t)(item.y / ntx) * kBigTile;
-    raster_rect(a, r, ox, oy, min(ox + kBigTile - 1, r.px1), min(oy + kBigTile - 1, r.py1), lane);
+#define OXC_BIG_PART 2
+#define OXC_BIG_TALLY nullptr
+#include "oxcull_draw_big.inc"
+#undef OXC_BIG_TALLY
+#undef OXC_BIG_PART
+}
+
+// The counting instantiations of the two, for a draw that reports its fragments (oxc_draw_terrain with OXC_TUNE_TERRAIN_DRAW_STATS): every
+// lane counts the fragments of its pixels that passed the depth range, a wave adds its sum to *fragments.  Same image.
+OXC_DEV void add_wave_tally(uint32_t tally, uint32_t* fragments) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) tally += __shfl_xor(tally, o, 64);
+  if ((threadIdx.x & 63) == 0 && tally) atomicAdd(fragments, tally);
+}
+__global__ __launch_bounds__(256) void k_draw_big_count(DrawArgs a, uint32_t* fragments) {
+  uint32_t tally = 0;
+  {
+#define OXC_BIG_PART 1
+#define OXC_BIG_TALLY (&tally)
+#include "oxcull_draw_big.inc"
+#undef OXC_BIG_TALLY
+#undef OXC_BIG_PART
   }
+  add_wave_tally(tally, fragments);
+}
+__global__ __launch_bounds__(256) void k_draw_big_tiles_count(DrawArgs a, uint32_t* fragments) {
+  uint32_t tally = 0;
+  {
+#define OXC_BIG_PART 2
+#define OXC_BIG_TALLY (&tally)
+#include "oxcull_draw_big.inc"
+#undef OXC_BIG_TALLY
+#undef OXC_BIG_PART
+  }
+  add_wave_tally(tally, fragments);
 }
 
 // The draw's clears as one kernel: `n` texels of the packed image and `words` u32 of the scratch header.  Not hipMemsetAsync: captured into
@@ -400,11 +255,31 @@ __global__ __launch_bounds__(256) void k_resolve_visbuffer(const unsigned long l
   }
 }
 
-void launch_draw_visbuffer(const DrawArgs& a, bool clear, float* depth_out, uint32_t* vis_out, uint32_t max_grid, hipStream_t s) {
+// The three launches around a draw's own kernels, also taken by oxc_draw_terrain (oxcull_terrain_draw.hip), whose triangles go through the
+// same big list and tiles: the clears, the big list with its tiles, the optional resolve.
+void launch_draw_clear(const DrawArgs& a, bool clear, uint32_t max_grid, hipStream_t s) {
   const uint64_t n = (uint64_t)a.width * a.height;
   // the image (with `clear`) and the clip / tile counters and the big list's segment counters
   hipLaunchKernelGGL(k_draw_clear, dim3((uint32_t)std::min<uint64_t>(((clear ? n : 0) + kRasterHeaderBytes / 4u + 255) / 256, max_grid)), dim3(256), 0, s,
                      a.visdepth, clear ? n : 0, a.clip_count, kRasterHeaderBytes / 4u);
+}
+void launch_draw_big(const DrawArgs& a, uint32_t max_grid, hipStream_t s, uint32_t* fragments) {
+  if (fragments) {
+    hipLaunchKernelGGL(k_draw_big_count, dim3(max_grid), dim3(256), 0, s, a, fragments);
+    hipLaunchKernelGGL(k_draw_big_tiles_count, dim3(max_grid), dim3(256), 0, s, a, fragments);
+    return;
+  }
+  hipLaunchKernelGGL(k_draw_big, dim3(max_grid), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_draw_big_tiles, dim3(max_grid), dim3(256), 0, s, a);
+}
+void launch_resolve_visbuffer(const DrawArgs& a, float* depth_out, uint32_t* vis_out, uint32_t max_grid, hipStream_t s) {
+  const uint64_t n = (uint64_t)a.width * a.height;
+  if (depth_out || vis_out)
+    hipLaunchKernelGGL(k_resolve_visbuffer, dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, max_grid)), dim3(256), 0, s, a.visdepth, n, depth_out, vis_out);
+}
+
+void launch_draw_visbuffer(const DrawArgs& a, bool clear, float* depth_out, uint32_t* vis_out, uint32_t max_grid, hipStream_t s) {
+  launch_draw_clear(a, clear, max_grid, s);
   hipLaunchKernelGGL(k_draw_rows, dim3(std::max(1u, std::min((a.mesh_instance_count + 255u) / 256u, max_grid))), dim3(256), 0, s, a);
   if (a.wide == 2u) {  // {id, corner} pairs
     hipLaunchKernelGGL(k_draw_setup<true>, dim3(max_grid), dim3(256), 0, s, a);
@@ -415,10 +290,8 @@ void launch_draw_visbuffer(const DrawArgs& a, bool clear, float* depth_out, uint
     hipLaunchKernelGGL((k_draw_clipped<false, false>), dim3(std::min(256u, max_grid)), dim3(64), 0, s, a);
     hipLaunchKernelGGL((k_draw_clipped<true, false>), dim3(max_grid), dim3(64), 0, s, a);  // (returns at once unless the id queue overflowed)
   }
-  hipLaunchKernelGGL(k_draw_big, dim3(max_grid), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(k_draw_big_tiles, dim3(max_grid), dim3(256), 0, s, a);
-  if (depth_out || vis_out)
-    hipLaunchKernelGGL(k_resolve_visbuffer, dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, max_grid)), dim3(256), 0, s, a.visdepth, n, depth_out, vis_out);
+  launch_draw_big(a, max_grid, s);
+  launch_resolve_visbuffer(a, depth_out, vis_out, max_grid, s);
 }
 
 }  // namespace oxc

@@ -690,6 +690,17 @@ public:
     context.struct_size = sizeof context;
     check(oxc_decode_terrain(ctx_, &context, stream_));
   }
+  // RendererInstance::draw_terrain_for_visbuffer (Passes/Terrain.cpp:218-277, pipeline terrain_visbuffer): the visible patches of the terrain
+  // cull, tessellated by the stated rules, into the depth|vis image of draw_for_visbuffer.  projection_scale is the engine's resolution.y *
+  // 0.5 / tan(radians(fov) * 0.5), evaluated in binary64 and rounded once by terrain_projection_scale.  Rules: include/oxcull.h,
+  // oxc_draw_terrain.
+  auto draw_terrain_for_visbuffer(oxc_terrain_draw_context context) -> void {
+    context.struct_size = sizeof context;
+    check(oxc_draw_terrain(ctx_, &context, stream_));
+  }
+  static auto terrain_projection_scale(double resolution_y, double fov_degrees) -> float {
+    return static_cast<float>(resolution_y * 0.5 / std::tan(fov_degrees * 3.14159265358979323846 / 180.0 * 0.5));
+  }
   // RendererInstance::apply_debug_view (Passes/Debug.cpp:9-153, pipelines debug_view and rmvsm_debug): the picture of context.debug_view
   // into context.debug_attachment, cleared to black first as the reference's clear_image does; with no mesh instance in the frame the six
   // geometry views return the cleared image (Debug.cpp:36-49), here without a launch on an image the caller cleared.  Rules:

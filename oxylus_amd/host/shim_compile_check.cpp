@@ -142,5 +142,13 @@ int main(int argc, char**) {
   } catch (const std::exception& e) {
     std::printf("expected (no attachments bound): %s\n", e.what());
   }
+  try {  // Passes/Terrain.cpp:218-277: the tessellated terrain draw behind draw_for_visbuffer
+    oxc_terrain_draw_context terrain_draw = {};
+    terrain_draw.width = terrain_draw.height = 16;
+    terrain_draw.projection_scale = RendererInstance::terrain_projection_scale(16.0, 60.0);
+    self.draw_terrain_for_visbuffer(terrain_draw);
+  } catch (const std::exception& e) {
+    std::printf("expected (no attachments bound): %s\n", e.what());
+  }
   return 0;
 }

@@ -38,6 +38,8 @@ TUNE_RASTER_GRID = 18
 TUNE_VSM_DRAW_GRID = 19
 TUNE_BOUNDS_GRID = 20
 TUNE_BOUNDS_CHUNK = 21
+TUNE_TERRAIN_DRAW_GRID = 22
+TUNE_TERRAIN_DRAW_STATS = 23
 
 # GPU::SceneFlags bits oxc_apply_pbr reads (scene.slang:242-256)
 SCENE_HAS_DIRECTIONAL_LIGHT, SCENE_HAS_ATMOSPHERE, SCENE_HAS_CONTACT_SHADOWS, SCENE_HAS_SKY, SCENE_TRANSPARENT_BACKGROUND = 1 << 0, 1 << 1, 1 << 9, 1 << 10, 1 << 11
@@ -799,6 +801,28 @@ class TerrainDecodeContext(C.Structure):
     ]
 
 
+class TerrainDrawContext(C.Structure):
+    _c_name_ = "oxc_terrain_draw_context"
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("clear", C.c_uint32),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("projection_view", C.c_float * 16),
+        ("camera_position", C.c_float * 3),
+        ("near_clip", C.c_float),
+        ("projection_scale", C.c_float),
+        ("terrain", TerrainData),
+        ("map_resolution", C.c_uint32 * 2),
+        ("heightmap", Buffer),
+        ("visible_patches_buffer", Buffer),
+        ("draw_cmd_buffer", Buffer),
+        ("visdepth_buffer", Buffer),
+        ("depth_attachment", Image),
+        ("visbuffer_attachment", Buffer),
+    ]
+
+
 class DebugViewContext(C.Structure):
     _c_name_ = "oxc_debug_view_context"
     _fields_ = [
@@ -949,6 +973,7 @@ PROTOTYPES = {
     "oxc_stream_read_probe": (_status, [_vp, _vp, _u64, _vp]),
     "oxc_debug_decode_bounds": (_status, [_vp, _vp, _u32, _vp, _vp]),
     "oxc_debug_raster_stats": _stats,
+    "oxc_debug_terrain_draw_stats": _stats,
     "oxc_profile_begin": (_status, [_vp]),
     "oxc_profile_end": (_status, [_vp, _P(KernelTimes)]),
     "oxc_build_meshlet_bounds": (_status, [_vp, _P(MeshletBoundsDesc), _vp]),
@@ -980,6 +1005,7 @@ PROTOTYPES = {
     "oxc_generate_terrain_maps": (_status, [_vp, _P(TerrainMapsContext), _vp]),
     "oxc_apply_terrain_brush": (_status, [_vp, _P(TerrainBrushContext), _vp]),
     "oxc_decode_terrain": (_status, [_vp, _P(TerrainDecodeContext), _vp]),
+    "oxc_draw_terrain": (_status, [_vp, _P(TerrainDrawContext), _vp]),
     "oxc_apply_debug_view": (_status, [_vp, _P(PreparedFrame), _P(DebugViewContext), _vp]),
     "oxc_pick_transform": (_status, [_vp, _P(PreparedFrame), _P(PickContext), _vp]),
     "oxc_apply_highlight": (_status, [_vp, _P(PreparedFrame), _P(HighlightContext), _vp]),

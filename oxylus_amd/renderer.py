@@ -975,6 +975,38 @@ class TerrainDecodeContext(Marshalled):
                                     decode.normal_attachment, decode.emissive_attachment, decode.metallic_roughness_occlusion_attachment)
 
 
+def terrain_projection_scale(resolution_y: float, fov_degrees: float) -> float:
+    """The engine's projection_scale of terrain_visbuffer.slang:36, resolution.y * 0.5 / tan(radians(fov) * 0.5), evaluated in binary64 and
+    rounded to binary32 once: the value oxc_terrain_draw_context.projection_scale takes as given (include/oxcull.h, step T2)."""
+    import math
+
+    import numpy as np
+
+    return float(np.float32(float(resolution_y) * 0.5 / math.tan(math.radians(float(fov_degrees)) * 0.5)))
+
+
+@dataclass
+class TerrainDrawContext(Marshalled):
+    """oxc_terrain_draw_context: RendererInstance::draw_terrain_for_visbuffer (Passes/Terrain.cpp:218-277, terrain_visbuffer.slang), the
+    tessellated patches of a terrain cull into the depth|vis image a draw_visbuffer call writes.  The patch list and the indirect command
+    are read on the device; `projection_scale` is taken as given (`terrain_projection_scale`)."""
+    _ctype = L.TerrainDrawContext
+    _derived = {"width": lambda self: self.visdepth_buffer.shape[1], "height": lambda self: self.visdepth_buffer.shape[0]}
+    visdepth_buffer: Optional[torch.Tensor]          # int64 [H, W]: depth bits << 32 | vis, in/out
+    projection_view: list                            # column-major float[16]
+    camera_position: tuple
+    near_clip: float
+    projection_scale: float
+    terrain: TerrainData
+    map_resolution: tuple
+    heightmap: Optional[torch.Tensor]                # int16 [h, w]: R16 Unorm
+    visible_patches_buffer: Optional[torch.Tensor]   # int32 [n]: patch indices
+    draw_cmd_buffer: Optional[torch.Tensor]          # int32 [4]: VkDrawIndirectCommand
+    clear: bool = False
+    depth_attachment: Optional[ImageAttachment] = None
+    visbuffer_attachment: Optional[torch.Tensor] = None
+
+
 @dataclass
 class DebugViewContext(Marshalled):
     """oxc_debug_view_context: RendererInstance::apply_debug_view (Passes/Debug.cpp:9-153), the views of debug_view.slang and rmvsm_debug.slang.
@@ -1206,6 +1238,7 @@ class MainGeometryContext(Marshalled):
 # the oxc_debug_*_stats read-backs: RendererInstance.debug_<key>_stats -> (symbol, the u32 counters in the library's order)
 _STATS = {
     "raster": ("oxc_debug_raster_stats", ("big", "clipped", "tiles", "overflowed_segments")),
+    "terrain_draw": ("oxc_debug_terrain_draw_stats", ("patches_drawn", "patches_discarded", "patches_skipped", "triangles", "set_up", "clipped", "big", "fragments")),
     "visbuffer_decode": ("oxc_debug_visbuffer_decode_stats", ("decoded", "empty", "zero_vertex_index", "default_material")),
     "vsm_draw": ("oxc_debug_vsm_draw_stats", ("pairs", "fragments", "big_pairs", "big_pairs_overflowed", "tiles", "tiles_overflowed", "clipped_pairs",
                                               "clipped_pairs_overflowed")),
@@ -1503,6 +1536,16 @@ class RendererInstance:
         """Passes/Terrain.cpp:279-360 (terrain_decode): the four G-buffer images at the terrain pixels, one launch (include/oxcull.h,
         oxc_decode_terrain).  After decode_visbuffer on the same attachments; every other pixel keeps its bytes."""
         self._call("oxc_decode_terrain", context, stream)
+
+    def draw_terrain_for_visbuffer(self, context: TerrainDrawContext, stream=None) -> None:
+        """Passes/Terrain.cpp:218-277 (terrain_visbuffer): the visible patches, tessellated by the stated rules T1 - T7, into
+        `context.visdepth_buffer` (include/oxcull.h, oxc_draw_terrain).  After draw_visbuffer on the same image, without `clear`."""
+        self._call("oxc_draw_terrain", context, stream)
+
+    def debug_terrain_draw_stats(self, stream=None) -> dict:
+        """What the last draw_terrain_for_visbuffer did with its patches and triangles (test hook; synchronises); `fragments` only after
+        debug_set_tuning(L.TUNE_TERRAIN_DRAW_STATS, 1)."""
+        return self._read_stats("terrain_draw", stream)
 
     def apply_debug_view(self, context: DebugViewContext, stream=None) -> None:
         """Passes/Debug.cpp:9-153 (debug_view, rmvsm_debug): the picture of `context.debug_view` into `context.debug_attachment`, one launch
