@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from pixel_rules import (cos_sin_turn, cvt_i32_sat, cvt_u32_sat, dot, f32a, from_half_bits, length, log2_rule, normalize, oct_to_vec3, pack_unorm4x8, pow_rule,
+from pixel_rules import (cos_sin_turn, cvt_i32_sat, cvt_u32_sat, dot, f32a, frac, from_half_bits, length, log2_rule, normalize, oct_to_vec3, pack_unorm4x8, pow_rule,
                          saturate, sign, to_half_bits)
 
 F = np.float32
@@ -21,10 +21,6 @@ GOLDEN = F(0.6180339887498948482)
 COUNTER_NAMES = ("non_sky_pixels", "samples", "mip0", "mip1", "mip2", "mip3", "mip4", "fractional", "result_one", "result_partial", "result_zero",
                  "zero_width", "sign_minus", "sign_zero", "sign_plus")
 PRESETS = {"low": (1, 2), "medium": (2, 2), "high": (3, 3), "ultra": (9, 3)}  # slice_count, samples_per_slice_side
-
-
-def frac(x):
-    return x - np.floor(x)
 
 
 # ---- small rules ----------------------------------------------------------------------------------------------------------------------------

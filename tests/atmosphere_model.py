@@ -1,7 +1,7 @@
 """The numpy checker of oxc_generate_sky_luts and oxc_draw_atmosphere: the host constants and rules 1-10 of their header block in
 include/oxcull.h, vectorised over the texels of a LUT (and, for the multiscattering pass, over the 64 directions), one masked pass per
-integration step.  Every binary32 operation is one numpy float32 operation in the order the header states; exp2 / pow and the rotation pair
-come from pixel_rules, the exp and cos rules built on them are local (no checker imports another).  A LUT is uint16 [H, W, 4] (the aerial
+integration step.  Every binary32 operation is one numpy float32 operation in the order the header states; pow, the exp and cos rules, lerp and the
+clamp bilinear's axis come from pixel_rules.  A LUT is uint16 [H, W, 4] (the aerial
 one [D, H, W, 4]) of binary16 bits.  `counts`, when given, receives how many texels, rays or steps took each side of the branches the tests
 must not leave empty."""
 from __future__ import annotations
@@ -11,11 +11,10 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from pixel_rules import INV_LN2, channel_half, cos_sin_turn, cvt_i32_sat, dot, exp2_f64_round, f32a, from_half_bits, length, normalize, pow_rule, saturate, unproject
+from pixel_rules import axis_clamp, channel_half, cos_turn_rule, count, dot, exp_rule, f32a, from_half_bits, length, lerp, normalize, pow_rule, saturate, unproject
 
 F = np.float32
 PI_F, TAU_F = F(3.1415926535897932384626433832795), F(6.283185307179586476925286766559)
-INV_TWO_PI = float.fromhex("0x1.45f306dc9c883p-3")
 PLANET_RADIUS_OFFSET = F(0.001)
 HALF_MAX, HALF_MIN_NORMAL = F(65504.0), F(6.103515625e-5)
 INV_4PI = F(1.0) / (F(4.0) * PI_F)
@@ -51,30 +50,7 @@ class Atmosphere:
         return tuple(F(x) for x in v) if isinstance(v, (tuple, list)) else F(v)
 
 
-def _count(counts, name, mask):
-    if counts is not None:
-        counts[name] = counts.get(name, 0) + int(np.asarray(mask).sum())
-
-
 # ---- the transcendentals ------------------------------------------------------------------------------------------------------------------------
-@np.errstate(all="ignore")
-def exp_rule(x) -> np.ndarray:
-    """exp(x) = exp2_f64_round((double)x * log2(e)), in the shape of x."""
-    x = f32a(x)
-    return exp2_f64_round(x.reshape(-1).astype(np.float64) * INV_LN2).reshape(x.shape)
-
-
-@np.errstate(all="ignore")
-def cos_rule(a) -> np.ndarray:
-    """cos(a): NaN for a non-finite a; else u = (double)|a| / (2 pi), t = (float)(u - floor(u)), t == 1 becomes 0, cos of the turn t."""
-    a = f32a(a)
-    u = np.abs(a).astype(np.float64) * INV_TWO_PI
-    u = np.where(np.isfinite(u), u, 0.0)
-    t = (u - np.floor(u)).astype(np.float32)
-    t = np.where(t == F(1.0), F(0.0), t).astype(np.float32)
-    return np.where(np.isfinite(a), cos_sin_turn(t)[0], F(np.nan)).astype(np.float32)
-
-
 def _pow(v, p):
     v = f32a(v)
     return pow_rule(v.reshape(-1), p).reshape(v.shape)
@@ -135,26 +111,13 @@ def medium(A: Atmosphere, altitude):
     return rayleigh, mie, tuple(r + m for r, m in zip(rayleigh, mie)), tuple((r + me) + o for r, o in zip(rayleigh, ozone))
 
 
-@np.errstate(all="ignore")
-def _lerp(a, b, t):
-    return (a + (b - a) * t).astype(np.float32)
-
-
-@np.errstate(all="ignore")
-def _axis(p, n: int):
-    g = (p * F(n) - F(0.5)).astype(np.float32)
-    fl = np.floor(g)
-    i = cvt_i32_sat(fl)
-    return np.clip(i, 0, n - 1), np.clip(i + 1, 0, n - 1), (g - fl).astype(np.float32)
-
-
 def sample_rgb(lut, u, v):
     """SampleLevel(LinearSamplerClamped, (u, v), 0).rgb of a uint16 [H, W, 4] LUT: the manual bilinear, clamp mode, on the decoded halves."""
     H, W = lut.shape[:2]
     planes = [from_half_bits(lut[..., c]) for c in range(3)]
-    x0, x1, fx = _axis(u, W)
-    y0, y1, fy = _axis(v, H)
-    return tuple(_lerp(_lerp(p[y0, x0], p[y0, x1], fx), _lerp(p[y1, x0], p[y1, x1], fx), fy) for p in planes)
+    x0, x1, fx = axis_clamp(u, W)
+    y0, y1, fy = axis_clamp(v, H)
+    return tuple(lerp(lerp(p[y0, x0], p[y0, x1], fx), lerp(p[y1, x0], p[y1, x1], fx), fy) for p in planes)
 
 
 @np.errstate(all="ignore")
@@ -191,11 +154,11 @@ def integrate(A, K, lut, eye, d, sun, sun_intensity, step_count, t_max=None, pla
         span = np.where(has_p, np.fmax(F(0.0), val_p), val_a).astype(np.float32)
     else:
         span = np.broadcast_to(f32a(t_max), shape)
-    _count(counts, "rays_hit_planet", has_p & ~dead)
-    _count(counts, "rays_miss_planet", ~has_p & ~dead)
+    count(counts, "rays_hit_planet", has_p & ~dead)
+    count(counts, "rays_miss_planet", ~has_p & ~dead)
     cos_theta = dot(sun, d)
     rayleigh_phase = RAYLEIGH_K * (F(1.0) + cos_theta * cos_theta)
-    mie_phase = _lerp(draine_phase(F(0.0), K["g_hg"], cos_theta), draine_phase(K["alpha"], K["g_d"], cos_theta), K["w_d"])
+    mie_phase = lerp(draine_phase(F(0.0), K["g_hg"], cos_theta), draine_phase(K["alpha"], K["g_d"], cos_theta), K["w_d"])
     lum = [np.zeros(shape, np.float32) for _ in range(3)]
     as1 = [np.zeros(shape, np.float32) for _ in range(3)]
     tr = [np.ones(shape, np.float32) for _ in range(3)]
@@ -215,8 +178,8 @@ def integrate(A, K, lut, eye, d, sun, sun_intensity, step_count, t_max=None, pla
         t_sun = sun_transmittance(A, K, lut, h, sun_theta)
         shadowed, _ = intersect(tuple(p - PLANET_RADIUS_OFFSET * u for p, u in zip(pos, up)), sun, pr)
         earth_shadow = np.where(shadowed, F(0.0), F(1.0)).astype(np.float32)
-        _count(counts, "steps_earth_shadow_0", shadowed & active)
-        _count(counts, "steps_earth_shadow_1", ~shadowed & active)
+        count(counts, "steps_earth_shadow_0", shadowed & active)
+        count(counts, "steps_earth_shadow_1", ~shadowed & active)
         for c in range(3):
             phase = mie[c] * mie_phase + rayleigh[c] * rayleigh_phase
             sun_luminance = (earth_shadow * t_sun[c]) * phase + F(0.0) * scattering[c]
@@ -228,8 +191,8 @@ def integrate(A, K, lut, eye, d, sun, sun_intensity, step_count, t_max=None, pla
             tr[c] = np.where(active, tr[c] * t, tr[c]).astype(np.float32)
     if planet_luminance:
         bounce = has_p & (span == val_p) & ~dead
-        _count(counts, "ground_bounce_taken", bounce)
-        _count(counts, "ground_bounce_not_taken", ~bounce)
+        count(counts, "ground_bounce_taken", bounce)
+        count(counts, "ground_bounce_not_taken", ~bounce)
         pos = tuple(e + span * c for e, c in zip(eye, d))
         h = length(pos)
         up = tuple(p / h for p in pos)
@@ -327,8 +290,8 @@ def sky_view_lut(A: Atmosphere, transmittance, camera_position, sun_dir, sun_int
     v = (v - F(0.5) / fh) * (fh / (fh - F(1.0)))
     zha, beta, h = K["zenith_horizon_angle"], K["beta"], K["eye_altitude"]
     above = v < F(0.5)
-    _count(counts, "sky_view_above_horizon", above)
-    _count(counts, "sky_view_below_horizon", ~above)
+    count(counts, "sky_view_above_horizon", above)
+    count(counts, "sky_view_below_horizon", ~above)
     ca = v * F(2.0)
     ca = F(1.0) - ca
     ca = ca * ca
@@ -337,16 +300,16 @@ def sky_view_lut(A: Atmosphere, transmittance, camera_position, sun_dir, sun_int
     cb = cb * cb
     angle = np.where(above, zha * ca, zha + beta * cb).astype(np.float32)
     longitude = u * TAU_F
-    cz = cos_rule(angle)
+    cz = cos_turn_rule(angle)
     sz = safe_sqrt(F(1.0) - cz * cz) * np.where(angle > 0, F(1.0), F(-1.0)).astype(np.float32)
-    cl = cos_rule(longitude)
+    cl = cos_turn_rule(longitude)
     sl = safe_sqrt(F(1.0) - cl * cl) * np.where(longitude <= PI_F, F(1.0), F(-1.0)).astype(np.float32)
     d = (sz * cl, cz, sz * sl)
     zero = np.zeros((H, W), np.float32)
     ok, eye = move_to_top_atmosphere((zero, zero + h, zero), d, A.f("atmos_radius"))
     if h > A.f("atmos_radius"):
-        _count(counts, "sky_view_moved_to_top", ok)
-        _count(counts, "sky_view_missed_atmosphere", ~ok)
+        count(counts, "sky_view_moved_to_top", ok)
+        count(counts, "sky_view_missed_atmosphere", ~ok)
     up = tuple(e / h for e in eye)
     sun_in = tuple(F(s) for s in sun_dir)
     szc = dot(sun_in, up)
@@ -385,9 +348,9 @@ def aerial_lut(A: Atmosphere, transmittance, camera_position, inv_projection_vie
         ok, moved = move_to_top_atmosphere(eye, d, ar)
         to_atmosphere = length(tuple(p - q for p, q in zip(eye, moved)))
         rejected = ok & (t_max < to_atmosphere)
-        _count(counts, "aerial_moved_to_top", ok & ~rejected)
-        _count(counts, "aerial_missed_atmosphere", ~ok)
-        _count(counts, "aerial_rejected_by_t_max", rejected)
+        count(counts, "aerial_moved_to_top", ok & ~rejected)
+        count(counts, "aerial_missed_atmosphere", ~ok)
+        count(counts, "aerial_rejected_by_t_max", rejected)
         zeroed = ~ok | rejected
         t_max = np.fmax(F(0.0), t_max - to_atmosphere)
         eye = moved

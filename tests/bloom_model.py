@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from pixel_rules import channel_half, cvt_i32_sat, f32a, from_half_bits, pack_b10g11r11, unpack_b10g11r11
+from pixel_rules import channel_half, cvt_i32_sat, f32a, from_half_bits, lerp, pack_b10g11r11, unpack_b10g11r11
 from pixel_rules import pack_ufloat  # noqa: F401  (the pack the B10G11R11 store goes through; the tests name it)
 
 F = np.float32
@@ -64,11 +64,6 @@ def fetch(plane, yy, xx, mode: int) -> np.ndarray:
         return t
     inside = ((yy >= 0) & (yy <= sh - 1))[:, None] & ((xx >= 0) & (xx <= sw - 1))[None, :]
     return np.where(inside, t, F(0.0)).astype(np.float32)
-
-
-@np.errstate(all="ignore")
-def lerp(a, b, t):
-    return (a + (b - a) * t).astype(np.float32)
 
 
 def bilinear(rgb, ow: int, oh: int, kx: int, ky: int, mode: int):

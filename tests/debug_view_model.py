@@ -7,7 +7,7 @@ from __future__ import annotations
 import numpy as np
 
 import vsm_resolve_model as RM
-from pixel_rules import channel_half, exp2_rule, f32a, from_half_bits, length, log2_rule, oct_to_vec3, pow_rule, saturate, unpack_b10g11r11, unproject
+from pixel_rules import _u32, channel_half, exp2_rule, f32a, from_half_bits, length, log2_rule, oct_to_vec3, saturate, srgb_decode, unpack_b10g11r11, unproject
 
 F = np.float32
 (TRIANGLES, MESHLETS, OVERDRAW, MATERIALS, MESH_INSTANCES, MESH_LODS, ALBEDO, NORMAL, EMISSIVE, METALLIC, ROUGHNESS, BAKED_OCCLUSION, GTAO, GEOMETRIC_NORMAL,
@@ -34,10 +34,6 @@ INFERNO = tuple(tuple(F(c) for c in row) for row in (
 SOBEL_X = (1, 0, -1, 2, 0, -2, 1, 0, -1)
 SOBEL_Y = (1, 2, 1, 0, 0, 0, -1, -2, -1)
 SAMPLE_OFFSET = ((-1, 1), (0, 1), (1, 1), (-1, 0), (0, 0), (1, 0), (-1, -1), (0, -1), (1, -1))
-
-
-def _u32(a) -> np.ndarray:
-    return np.ascontiguousarray(np.asarray(a)).view(np.uint32)
 
 
 # ---- the shared rules -----------------------------------------------------------------------------------------------------------------------
@@ -68,13 +64,6 @@ def hsv_to_rgb(hue):
         k = np.fmod(n + q, F(6.0)).astype(np.float32)
         out.append(F(0.5) - (F(0.5) * F(1.0)) * np.fmax(F(0.0), np.fmin(k, np.fmin(F(4.0) - k, F(1.0)))))
     return tuple(out)
-
-
-@np.errstate(all="ignore")
-def srgb_decode(byte) -> np.ndarray:
-    """oxc_apply_pbr step 2: c = f32(byte) / 255; c <= 0.04045 ? c / 12.92 : pow((c + 0.055) / 1.055, 2.4), the pow rule."""
-    c = np.atleast_1d(np.asarray(byte)).astype(np.float32) / F(255.0)
-    return np.where(c <= F(0.04045), c / F(12.92), pow_rule((c + F(0.055)) / F(1.055), F(2.4))).astype(np.float32)
 
 
 def inferno(t):

@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from pixel_rules import channel_half, cvt_i32_sat, from_half_bits, pack_b10g11r11, unpack_b10g11r11
+from pixel_rules import axis_clamp, channel_half, from_half_bits, lerp, pack_b10g11r11, unpack_b10g11r11
 
 F = np.float32
 FORMAT_B10G11R11, FORMAT_R16G16B16A16 = 0, 1
@@ -40,26 +40,12 @@ def luma_of(r, g, b):
     return np.sqrt((r * F(0.299) + g * F(0.587)) + b * F(0.114)).astype(np.float32)
 
 
-@np.errstate(all="ignore")
-def _lerp(a, b, t):
-    return (a + (b - a) * t).astype(np.float32)
-
-
-@np.errstate(all="ignore")
-def _axis(p, n: int):
-    """The clamp-mode axis of the manual bilinear at the normalised coordinates p of a side of n texels: (i0, i1, f)."""
-    g = (p * F(n) - F(0.5)).astype(np.float32)
-    fl = np.floor(g)
-    i = cvt_i32_sat(fl)
-    return np.clip(i, 0, n - 1), np.clip(i + 1, 0, n - 1), (g - fl).astype(np.float32)
-
-
 def bilinear(planes, u, v):
     """Sample(sampler, (u, v)) of every plane, clamp mode; u, v float32 [n]."""
     H, W = planes[0].shape
-    x0, x1, fx = _axis(u, W)
-    y0, y1, fy = _axis(v, H)
-    return tuple(_lerp(_lerp(p[y0, x0], p[y0, x1], fx), _lerp(p[y1, x0], p[y1, x1], fx), fy) for p in planes)
+    x0, x1, fx = axis_clamp(u, W)
+    y0, y1, fy = axis_clamp(v, H)
+    return tuple(lerp(lerp(p[y0, x0], p[y0, x1], fx), lerp(p[y1, x0], p[y1, x1], fx), fy) for p in planes)
 
 
 @np.errstate(all="ignore")

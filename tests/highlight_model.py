@@ -6,14 +6,13 @@ from __future__ import annotations
 
 import numpy as np
 
-from pixel_rules import F, pack_unorm4x8, pow_rule, saturate
+from pixel_rules import F, pack_unorm4x8, pow_rule, srgb_decode, srgb_encode
 
 EMPTY = 0xFFFFFFFF
 TERRAIN_INSTANCE = 0xFFFFFE
 MASK, COMPOSITE, ALL = 1, 2, 3
 RGBA8_SRGB, BGRA8_SRGB, RGBA8_UNORM = 0, 1, 2
 OUTLINE = (1.0, 0.53, 0.0, 1.0)   # ViewportPanel.cpp:1307
-SRGB_P = F(0.4166666666666667)
 
 
 # ---- P, M1, M2 ------------------------------------------------------------------------------------------------------------------------------
@@ -64,22 +63,11 @@ def mask_image(mask) -> np.ndarray:
 
 
 # ---- H1 - H5 --------------------------------------------------------------------------------------------------------------------------------
-def srgb_decode(byte) -> np.ndarray:
-    c = np.asarray(byte).astype(np.float32) / F(255.0)
-    return np.where(c <= F(0.04045), c / F(12.92), pow_rule((c + F(0.055)) / F(1.055), F(2.4)).reshape(c.shape)).astype(np.float32)
-
-
 def srgb_to_linear(c) -> np.ndarray:
     """common/color.slang:75-77 as written: a strict comparison, the absolute value of the base."""
     c = np.atleast_1d(np.asarray(c, dtype=np.float32))
     with np.errstate(all="ignore"):
         return np.where(c < F(0.04045), c / F(12.92), pow_rule(np.abs(c + F(0.055)) / F(1.055), F(2.4))).astype(np.float32)
-
-
-@np.errstate(all="ignore")
-def srgb_encode(c) -> np.ndarray:
-    c = saturate(c)
-    return np.where(c <= F(0.0031308), c * F(12.92), F(1.055) * pow_rule(c, SRGB_P).reshape(c.shape) - F(0.055)).astype(np.float32)
 
 
 def decode(color, color_format):

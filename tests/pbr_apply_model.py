@@ -6,8 +6,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from pixel_rules import (COS_C, SIN_C, channel_half, dot, exp2_rule, f32a, from_half_bits, normalize, oct_to_vec3, pack_b10g11r11, pow_rule, saturate,
-                         unpack_b10g11r11)
+from pixel_rules import (COS_C, SIN_C, channel_half, clamp, dot, exp2_rule, f32a, from_half_bits, normalize, oct_to_vec3, pack_b10g11r11, pow_rule, saturate,
+                         srgb_decode, unpack_b10g11r11)
 from pixel_rules import unpack_ufloat  # noqa: F401  (the decode behind unpack_b10g11r11; the tests name it)
 
 F = np.float32
@@ -30,8 +30,9 @@ LIGHT_FIELDS = dict(position=slice(0, 3), intensity=3, color=slice(4, 7), range=
 
 # ---- the closed forms ------------------------------------------------------------------------------------------------------------------------
 @np.errstate(all="ignore")
-def cos_rule(x) -> np.ndarray:
-    """The cos rule: two-constant reduction, the polynomials of the rotation rule, one rounding; NaN beyond 2^24 and for non-finite x."""
+def cos_reduced_rule(x) -> np.ndarray:
+    """The cos rule of this pass alone (its device function lives in oxcull_pbr_apply.hip, not in the shared header): two-constant reduction,
+    the polynomials of the rotation rule, one rounding; NaN beyond 2^24 and for non-finite x."""
     x = np.atleast_1d(f32a(x))
     ax = np.abs(x)
     ok = ax <= F(2.0 ** 24)
@@ -49,16 +50,6 @@ def cos_rule(x) -> np.ndarray:
 
 
 # ---- decodes and packers ---------------------------------------------------------------------------------------------------------------------
-@np.errstate(all="ignore")
-def srgb_decode(byte) -> np.ndarray:
-    c = np.atleast_1d(np.asarray(byte)).astype(np.float32) / F(255.0)
-    return np.where(c <= F(0.04045), c / F(12.92), pow_rule((c + F(0.055)) / F(1.055), F(2.4))).astype(np.float32)
-
-
-def clamp(x, lo, hi):
-    return np.fmin(np.fmax(f32a(x), F(lo)), F(hi))
-
-
 def unpack_lights(lights, count: int = None) -> dict:
     """uint8 / uint32 records -> the fields as float32 arrays [n] / [n, 3] and kind uint32 [n]."""
     w = np.ascontiguousarray(np.asarray(lights)).view(np.uint32).reshape(-1, 16)
@@ -236,7 +227,7 @@ def apply_pbr(depth, albedo, normal, emissive, mro, ao, resolved, contact, scene
                 if kind == KIND_SPOT:
                     sd = normalize(tuple(lt["direction"][i]))
                     cos_angle = dot((-Ll[0], -Ll[1], -Ll[2]), sd)
-                    att = att * smoothstep(cos_rule(lt["outer_cone_angle"][i])[0], cos_rule(lt["inner_cone_angle"][i])[0], cos_angle)
+                    att = att * smoothstep(cos_reduced_rule(lt["outer_cone_angle"][i])[0], cos_reduced_rule(lt["inner_cone_angle"][i])[0], cos_angle)
                 intensity = lt["intensity"][i]
                 out_att = (att <= 0) | bool(intensity <= 0)
                 NdotL = saturate(dot(N, Ll))

@@ -1,7 +1,8 @@
 """Checker of oxc_apply_pbr_atmosphere: the atmosphere branch of RendererInstance::apply_pbr (Passes/PBR.cpp:318-434, passes/pbr_apply.slang with
 pbr.slang and sky.slang) in numpy, following steps A - K of its header block in include/oxcull.h.  What the other checkers already implement
-is imported and left as it is: decode, surface, BRDF and the lights from pbr_apply_model, the record, the host constants, intersect, exp and
-the transmittance sample from atmosphere_model, the .rgba clamp bilinear and sky_view_params_to_lut_uv from sky_ibl_model.  New here: the sun
+is imported and left as it is: the surface, BRDF and the lights from pbr_apply_model, the record, the host constants, intersect and the
+transmittance sample from atmosphere_model, the .rgba clamp bilinear and sky_view_params_to_lut_uv from sky_ibl_model; the numeric rules
+(exp, the sRGB decode, clamp, lerp, the bilinear's axis) from pixel_rules.  New here: the sun
 term per channel (C), the sky pixel with draw_sun (D), sample_aerial_perspective (E), the face-local cube sample (F) and the sky ambient (G).
 Returns the image and a dict of counts: the pixel classes, the aerial branches and the four light outcomes."""
 from __future__ import annotations
@@ -12,7 +13,8 @@ import atmosphere_model as AM
 import pbr_apply_model as PM
 import sky_ibl_model as SM
 from pbr_apply_model import HAS_CONTACT_SHADOWS, HAS_DIRECTIONAL_LIGHT, TRANSPARENT_BACKGROUND
-from pixel_rules import channel_half, cross, dot, exp2_rule, f32a, from_half_bits, length, normalize, oct_to_vec3, pack_b10g11r11, pow_rule, saturate, unpack_b10g11r11
+from pixel_rules import (axis_clamp, channel_half, clamp, count, cross, dot, exp2_rule, exp_rule, f32a, from_half_bits, length, lerp, normalize, oct_to_vec3,
+                         pack_b10g11r11, pow_rule, saturate, srgb_decode, unpack_b10g11r11)
 
 F = np.float32
 HALF_SLICE = F(0.70710678118654752)
@@ -29,7 +31,7 @@ def host_constants(A: AM.Atmosphere, camera_position, sun_dir) -> dict:
     K["min_altitude"] = A.f("planet_radius") + F(0.001)
     K["sun_cos_theta"] = (L[0] * F(0.0) + L[1] * F(1.0)) + L[2] * F(0.0)
     K["horizon_darkening"] = PM.smoothstep(F(-0.1), F(0.3), K["sun_cos_theta"])
-    K["min_cos"] = PM.cos_rule((F(1.0) * PM.PI) / F(180.0))[0]
+    K["min_cos"] = PM.cos_reduced_rule((F(1.0) * PM.PI) / F(180.0))[0]
     lut = tuple(F(n) for n in A.aerial_perspective_lut_size)
     K["aerial_depth"] = lut[2]
     K["inv_per_slice_depth"] = F(1.0) / (lut[0] / lut[2])
@@ -45,7 +47,7 @@ def draw_sun(min_cos, ct):
     ct = f32a(ct)
     inside = ct >= min_cos  # false for a NaN
     offset = min_cos - ct
-    g = AM.exp_rule(-offset * F(50000.0)) * F(0.5)
+    g = exp_rule(-offset * F(50000.0)) * F(0.5)
     inv = (F(1.0) / (F(0.02) + offset * F(300.0))) * F(0.01)
     return np.where(inside, F(1.0), g + inv).astype(np.float32), inside
 
@@ -62,10 +64,10 @@ def aerial_perspective(A, K, aerial, u, v, rel, counts=None):
     near = non_linear_slice < HALF_SLICE
     weight = np.where(near, saturate((non_linear_slice * non_linear_slice) * F(2.0)), F(1.0)).astype(np.float32)
     weight = weight * saturate(relative_depth * K["near_depth_fade_out"])
-    AM._count(counts, "aerial_near_slice", near)
-    AM._count(counts, "aerial_zero_depth", relative_depth == 0)
+    count(counts, "aerial_near_slice", near)
+    count(counts, "aerial_zero_depth", relative_depth == 0)
     D = aerial.shape[0]
-    z0, z1, fz = AM._axis(non_linear_w, D)
+    z0, z1, fz = axis_clamp(non_linear_w, D)
     t0 = [np.zeros(len(u), np.float32) for _ in range(4)]
     t1 = [np.zeros(len(u), np.float32) for _ in range(4)]
     for z in range(D):  # the bilinear .rgba of slice i0 and of slice i1
@@ -74,7 +76,7 @@ def aerial_perspective(A, K, aerial, u, v, rel, counts=None):
             if m.any():
                 for c, plane in enumerate(SM.sample_rgba(aerial[z], u[m], v[m])):
                     t[c][m] = plane
-    a = [SM._lerp(t0[c], t1[c], fz) for c in range(4)]
+    a = [lerp(t0[c], t1[c], fz) for c in range(4)]
     rgb = [a[c] * weight for c in range(3)]
     w = F(1.0) - (weight * (F(1.0) - a[3]))
     rgb = [c * A.f("aerial_perspective_exposure") for c in rgb]
@@ -152,14 +154,14 @@ def apply_pbr_atmosphere(depth, albedo, normal, emissive, mro, ao, resolved, con
         return out, st
     d = depth[ys, xs]
     aw = albedo[ys, xs]
-    alb = [PM.srgb_decode((aw >> np.uint32(8 * c)) & np.uint32(0xFF)) for c in range(3)]
+    alb = [srgb_decode((aw >> np.uint32(8 * c)) & np.uint32(0xFF)) for c in range(3)]
     nh = from_half_bits(normal[ys, xs])
     mapped, smooth = oct_to_vec3(nh[:, 0], nh[:, 1]), oct_to_vec3(nh[:, 2], nh[:, 3])
     emission = unpack_b10g11r11(emissive[ys, xs])
     mw = mro[ys, xs]
     byte = lambda k: ((mw >> np.uint32(8 * k)) & np.uint32(0xFF)).astype(np.float32) / F(255.0)  # noqa: E731
-    metallic = PM.clamp(byte(0), 0.0, 1.0)
-    roughness = PM.clamp(byte(1), 0.045, 1.0)
+    metallic = clamp(byte(0), 0.0, 1.0)
+    roughness = clamp(byte(1), 0.045, 1.0)
     occlusion = byte(2) * from_half_bits(ao[ys, xs])
     u, v = (xs.astype(np.float32) + F(0.5)) / F(W), (ys.astype(np.float32) + F(0.5)) / F(H)
     nx, ny = u * F(2.0) - F(1.0), v * F(2.0) - F(1.0)
@@ -219,7 +221,7 @@ def apply_pbr_atmosphere(depth, albedo, normal, emissive, mro, ao, resolved, con
             aerial_c[c][lit] = plane
         # F, G. sky ambient
         t = F(1.0) - roughness
-        refl = normalize(tuple(SM._lerp(N[c], R[c], t) for c in range(3)))
+        refl = normalize(tuple(lerp(N[c], R[c], t) for c in range(3)))
         spec = cube_sample(cube, tuple(c[lit] for c in refl))
         diff = cube_sample(cube, tuple(c[lit] for c in N))
         for c in range(3):
@@ -260,7 +262,7 @@ def apply_pbr_atmosphere(depth, albedo, normal, emissive, mro, ao, resolved, con
             if kind == PM.KIND_SPOT:
                 sd = normalize(tuple(lt["direction"][i]))
                 cos_angle = dot((-Ll[0], -Ll[1], -Ll[2]), sd)
-                att = att * PM.smoothstep(PM.cos_rule(lt["outer_cone_angle"][i])[0], PM.cos_rule(lt["inner_cone_angle"][i])[0], cos_angle)
+                att = att * PM.smoothstep(PM.cos_reduced_rule(lt["outer_cone_angle"][i])[0], PM.cos_reduced_rule(lt["inner_cone_angle"][i])[0], cos_angle)
             intensity = lt["intensity"][i]
             out_att = (att <= 0) | bool(intensity <= 0)
             NdotL = saturate(dot(N, Ll))

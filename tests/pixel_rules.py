@@ -1,7 +1,12 @@
 """The numeric rules the checkers share, one copy each: the Python counterpart of include/oxcull_pixel_device.hpp and oxcull_device.hpp.
 Binary32 in the stated evaluation order, no contraction, IEEE division and square root, the closed forms of log2 / exp2 / pow and of the
 rotation pair in binary64 rounded once, saturating conversions, the half and small-float packers.  A checker (tests/*_model.py) imports
-what it uses from here; no checker takes a numeric rule from another checker."""
+what it uses from here; no checker takes a numeric rule from another checker, and none defines a function under a name this module has
+(tests/test_pixel_rules.py holds both).  What a checker still imports from another checker is a step or a constant of that checker's
+own pass.
+Shapes: the closed forms (log2, exp2, pow, the small-float packers) return at least one dimension, as they always have; every rule of the
+section "the per-pixel rules of oxcull_pixel_device.hpp" returns the shape of its input, a scalar's included, and a caller that wants
+one dimension more asks for it itself."""
 from __future__ import annotations
 
 import numpy as np
@@ -15,6 +20,7 @@ LOG_C = [1.0 / k for k in (3.0, 5.0, 7.0, 9.0, 11.0, 13.0, 15.0, 17.0)]  # the b
 EXP_C = [1.0, 1.0, 1.0 / 2.0, 1.0 / 6.0, 1.0 / 24.0, 1.0 / 120.0, 1.0 / 720.0, 1.0 / 5040.0, 1.0 / 40320.0, 1.0 / 362880.0, 1.0 / 3628800.0,
          1.0 / 39916800.0, 1.0 / 479001600.0, 1.0 / 6227020800.0]
 PIO2 = float.fromhex("0x1.921fb54442d18p+0")
+INV_TWO_PI = float.fromhex("0x1.45f306dc9c883p-3")
 SIN_C = [float.fromhex(h) for h in ("-0x1.5555555555555p-3", "0x1.1111111111111p-7", "-0x1.a01a01a01a01ap-13", "0x1.71de3a556c734p-19")]
 COS_C = [float.fromhex(h) for h in ("-0x1.0000000000000p-1", "0x1.5555555555555p-5", "-0x1.6c16c16c16c17p-10", "0x1.a01a01a01a01ap-16",
                                     "-0x1.27e4fb7789f5cp-22")]
@@ -129,6 +135,93 @@ def cos_sin_turn(t):
     return cos.astype(np.float32), sin.astype(np.float32)
 
 
+# ---- the per-pixel rules of oxcull_pixel_device.hpp ------------------------------------------------------------------------------------------
+def count(counts, name, n=1):
+    """counts[name] += n, n a number or a mask (its true elements); nothing where counts is None."""
+    if counts is not None:
+        counts[name] = counts.get(name, 0) + int(np.asarray(n).sum())
+
+
+def frac(x):
+    """x - floor(x)."""
+    return (x - np.floor(x)).astype(np.float32)
+
+
+@np.errstate(all="ignore")
+def lerp(a, b, t):
+    """lerp_f: a + (b - a) * t."""
+    return (a + (b - a) * t).astype(np.float32)
+
+
+def clamp(x, lo, hi):
+    """min(max(x, lo), hi): a NaN gives lo."""
+    return np.fmin(np.fmax(f32a(x), F(lo)), F(hi))
+
+
+@np.errstate(all="ignore")
+def exp_rule(x):
+    """exp_rule: exp(x) = exp2_f64_round((double)x * log2(e))."""
+    x = f32a(x)
+    return exp2_f64_round(x.astype(np.float64) * INV_LN2).reshape(x.shape)
+
+
+@np.errstate(all="ignore")
+def cos_sin_angle_rule(a):
+    """cos_sin_angle_rule: (cos(a), sin(a)) of a binary32 angle, both NaN for a non-finite a; else u = (double)|a| / (2 pi), t = (float)(u -
+    floor(u)), t == 1 becomes 0, the pair of the turn t, the sine negated for a < 0."""
+    a = f32a(a)
+    u = np.abs(a).astype(np.float64) * INV_TWO_PI
+    u = np.where(np.isfinite(u), u, 0.0)
+    t = (u - np.floor(u)).astype(np.float32)
+    t = np.where(t == F(1.0), F(0.0), t).astype(np.float32)
+    cs, sn = cos_sin_turn(t)
+    sn = np.where(a < 0, -sn, sn)
+    ok = np.isfinite(a)
+    return np.where(ok, cs, F(np.nan)).astype(np.float32), np.where(ok, sn, F(np.nan)).astype(np.float32)
+
+
+def cos_turn_rule(a):
+    """cos_turn_rule: cos(a) of a binary32 angle, the cosine of cos_sin_angle_rule bit for bit."""
+    return cos_sin_angle_rule(a)[0]
+
+
+@np.errstate(all="ignore")
+def srgb_decode(byte):
+    """srgb_decode: c = f32(byte) / 255; c <= 0.04045 ? c / 12.92 : pow_rule((c + 0.055) / 1.055, 2.4)."""
+    c = np.asarray(byte).astype(np.float32) / F(255.0)
+    return np.where(c <= F(0.04045), c / F(12.92), pow_rule((c + F(0.055)) / F(1.055), F(2.4)).reshape(c.shape)).astype(np.float32)
+
+
+@np.errstate(all="ignore")
+def srgb_encode(c):
+    """srgb_encode: c = saturate(c); c <= 0.0031308 ? c * 12.92 : 1.055 * pow_rule(c, 0.4166666666666667f) - 0.055."""
+    c = saturate(c)
+    return np.where(c <= F(0.0031308), c * F(12.92), F(1.055) * pow_rule(c, F(0.4166666666666667)).reshape(c.shape) - F(0.055)).astype(np.float32)
+
+
+@np.errstate(all="ignore")
+def srgb_unorm_encode(x):
+    """The encode inside srgb_unorm, not saturated: x <= 0.0031308 ? 12.92 * x : 1.055 * pow_rule(x, 1.0f / 2.4f) - 0.055."""
+    x = f32a(x)
+    return np.where(x <= F(0.0031308), F(12.92) * x, F(1.055) * pow_rule(x, F(1.0) / F(2.4)).reshape(x.shape) - F(0.055)).astype(np.float32)
+
+
+@np.errstate(all="ignore")
+def unorm8(e):
+    """pack_unorm, one channel of pack_unorm4x8: u32(floor(saturate(e) * 255.0 + 0.5)); a NaN gives 0."""
+    return cvt_u32_sat(np.floor(saturate(e) * F(255.0) + F(0.5))).astype(np.uint32)
+
+
+@np.errstate(all="ignore")
+def axis_clamp(p, n: int):
+    """axis_at<false>: (i0, i1, f) of the manual bilinear at the normalised coordinate p of a side of n texels, g = p * n - 0.5, f = g -
+    floor(g), both indices in [0, n - 1] for every bit pattern of p."""
+    g = (p * F(n) - F(0.5)).astype(np.float32)
+    fl = np.floor(g)
+    i = cvt_i32_sat(fl)
+    return np.clip(i, 0, n - 1), np.clip(i + 1, 0, n - 1), (g - fl).astype(np.float32)
+
+
 # ---- vectors and matrices -------------------------------------------------------------------------------------------------------------------
 def cross(a, b):
     """cross(a, b).x = a.y * b.z - a.z * b.y and its rotations, each product rounded before the subtraction."""
@@ -215,7 +308,7 @@ def pack_unorm4x8(e0, e1, e2, e3) -> np.ndarray:
     """byte k = u32(floor(saturate(e_k) * 255.0 + 0.5)), component 0 in the low byte."""
     out = np.zeros(np.shape(e0), dtype=np.uint32)
     for k, e in enumerate((e0, e1, e2, e3)):
-        out |= cvt_u32_sat(np.floor(saturate(e) * F(255.0) + F(0.5))).astype(np.uint32) << np.uint32(8 * k)
+        out |= unorm8(e) << np.uint32(8 * k)
     return out
 
 

@@ -1,7 +1,8 @@
 """The numpy checker of oxc_generate_sky_ibl: steps 11-15 of its header block in include/oxcull.h, vectorised over the texels of the cube
 and their 64 samples ([texels, 64] arrays).  Every binary32 operation is one numpy float32 operation in the order the header states, the
-closed forms of acos / atan2 are the same binary64 operations the device runs.  The shared rules come from pixel_rules; intersect, the clamp
-bilinear, the host constants and the cos turn are local copies of what the LUT checker has (no checker imports another).  An image is
+closed forms of acos / atan2 are the same binary64 operations the device runs.  The shared rules -- the cos / sin of an angle, frac, lerp and the clamp
+bilinear's axis among them -- come from pixel_rules; intersect and the host constants are local copies of the LUT checker's own steps (no
+checker takes a numeric rule from another).  An image is
 uint16 [..., 4] of binary16 bits; the cube is [6, S, S, 4].  `counts`, when given, receives how many texels or samples took each side of the
 branches the tests must not leave empty."""
 from __future__ import annotations
@@ -10,11 +11,10 @@ import math
 
 import numpy as np
 
-from pixel_rules import channel_half, cos_sin_turn, cross, cvt_i32_sat, dot, f32a, from_half_bits, length, normalize, saturate
+from pixel_rules import axis_clamp, channel_half, cos_sin_angle_rule, count, cross, dot, f32a, frac, from_half_bits, length, lerp, normalize, saturate
 
 F = np.float32
 PI_F, TAU_F = F(3.1415926535897932384626433832795), F(6.283185307179586476925286766559)
-INV_TWO_PI = float.fromhex("0x1.45f306dc9c883p-3")
 PI_D, PIO2_D, PIO4_D = (float.fromhex(h) for h in ("0x1.921fb54442d18p+1", "0x1.921fb54442d18p+0", "0x1.921fb54442d18p-1"))
 ATAN_FOLD = float.fromhex("0x1.a827999fcef32p-2")  # sqrt(2) - 1
 ATAN_C = [1.0 / k for k in range(1, 40, 2)]        # the binary64 quotients 1, 1/3 .. 1/39
@@ -28,11 +28,6 @@ CUBE_FACE = np.array([[+0, +0, -1, +0, -1, +0, -1, +0, +0], [+0, +0, +1, +0, -1,
                       [+1, +0, +0, +0, +0, +1, +0, -1, +0], [+1, +0, +0, +0, -1, +0, +0, +0, -1], [-1, +0, +0, +0, -1, +0, +0, +0, +1]], dtype=np.float32)
 CLASSES = ("samples_hit_planet", "samples_miss_planet", "side_vec_fallback", "side_vec_normalized", "light_on_plane_fallback", "light_on_plane_normalized",
            "up_is_x", "up_is_y", "has_history", "no_history", "clamped_at_half_max", "sanitized_sample")
-
-
-def _count(counts, name, mask):
-    if counts is not None:
-        counts[name] = counts.get(name, 0) + int(np.asarray(mask).sum())
 
 
 # ---- step 11: the closed forms ---------------------------------------------------------------------------------------------------------------------
@@ -72,24 +67,6 @@ def acos_rule(x) -> np.ndarray:
     return np.where(np.abs(x) <= F(1.0), r, F(np.nan)).astype(np.float32)
 
 
-@np.errstate(all="ignore")
-def cos_sin_rule(a):
-    """(cos(a), sin(a)): the turn of the cos rule, the sine negated for a < 0; NaN for a non-finite a."""
-    a = f32a(a)
-    u = np.abs(a).astype(np.float64) * INV_TWO_PI
-    u = np.where(np.isfinite(u), u, 0.0)
-    t = (u - np.floor(u)).astype(np.float32)
-    t = np.where(t == F(1.0), F(0.0), t).astype(np.float32)
-    cs, sn = cos_sin_turn(t)
-    sn = np.where(a < 0, -sn, sn)
-    ok = np.isfinite(a)
-    return np.where(ok, cs, F(np.nan)).astype(np.float32), np.where(ok, sn, F(np.nan)).astype(np.float32)
-
-
-def frac(x):
-    return (x - np.floor(x)).astype(np.float32)
-
-
 def radical_inverse_vdc(i) -> np.ndarray:
     """sky_ibl.slang:32-39: the five swaps as written, then f32(bits) * 2.3283064365386963e-10."""
     b = np.asarray(i, dtype=np.uint64) & 0xFFFFFFFF
@@ -117,26 +94,13 @@ def intersect_has(o, d, radius):
     return ~(delta < 0) & ~((s0 < 0) & (s1 < 0))
 
 
-@np.errstate(all="ignore")
-def _lerp(a, b, t):
-    return (a + (b - a) * t).astype(np.float32)
-
-
-@np.errstate(all="ignore")
-def _axis(p, n: int):
-    g = (p * F(n) - F(0.5)).astype(np.float32)
-    fl = np.floor(g)
-    i = cvt_i32_sat(fl)
-    return np.clip(i, 0, n - 1), np.clip(i + 1, 0, n - 1), (g - fl).astype(np.float32)
-
-
 def sample_rgba(lut, u, v):
     """SampleLevel(LinearSamplerClamped, (u, v), 0) of a uint16 [H, W, 4] image: the manual bilinear, clamp mode, on the four decoded halves."""
     H, W = lut.shape[:2]
     planes = [from_half_bits(lut[..., c]) for c in range(4)]
-    x0, x1, fx = _axis(u, W)
-    y0, y1, fy = _axis(v, H)
-    return tuple(_lerp(_lerp(p[y0, x0], p[y0, x1], fx), _lerp(p[y1, x0], p[y1, x1], fx), fy) for p in planes)
+    x0, x1, fx = axis_clamp(u, W)
+    y0, y1, fy = axis_clamp(v, H)
+    return tuple(lerp(lerp(p[y0, x0], p[y0, x1], fx), lerp(p[y1, x0], p[y1, x1], fx), fy) for p in planes)
 
 
 @np.errstate(all="ignore")
@@ -171,7 +135,7 @@ def cosine_hemisphere_sample(i, rotation):
     u1 = (f32a(i) + F(0.5)) / F(SAMPLES)
     u2 = frac(radical_inverse_vdc(i) + rotation)
     r, phi = np.sqrt(u1), TAU_F * u2
-    cs, sn = cos_sin_rule(phi)
+    cs, sn = cos_sin_angle_rule(phi)
     return r * cs, r * sn, np.sqrt(np.fmax(F(0.0), F(1.0) - u1))
 
 
@@ -204,26 +168,26 @@ def illuminance(K, planet_radius, sky_view, eye, d, sun_dir, counts=None, uv_out
     keep_side = length(side_raw) > SIDE_LIMIT
     side_n = normalize(side_raw)
     side = tuple(np.where(keep_side, s, F(f)).astype(np.float32) for s, f in zip(side_n, (1.0, 0.0, 0.0)))
-    _count(counts, "side_vec_fallback", ~keep_side)
-    _count(counts, "side_vec_normalized", keep_side)
+    count(counts, "side_vec_fallback", ~keep_side)
+    count(counts, "side_vec_normalized", keep_side)
     forward = normalize(cross(side, up))
     sun = normalize(sun_dir)
     lx, ly = dot(sun, forward), dot(sun, side)
     len_sq = lx * lx + ly * ly
     inv = F(1.0) / np.sqrt(len_sq)
     keep = len_sq > PLANE_LIMIT
-    _count(counts, "light_on_plane_fallback", ~keep)
-    _count(counts, "light_on_plane_normalized", keep)
+    count(counts, "light_on_plane_fallback", ~keep)
+    count(counts, "light_on_plane_normalized", keep)
     lop = (np.where(keep, lx * inv, F(1.0)).astype(np.float32), np.where(keep, ly * inv, F(0.0)).astype(np.float32))
     hit = intersect_has(eye, d, F(planet_radius))
-    _count(counts, "samples_hit_planet", hit)
-    _count(counts, "samples_miss_planet", ~hit)
+    count(counts, "samples_hit_planet", hit)
+    count(counts, "samples_miss_planet", ~hit)
     u, v = sky_view_uv(K, (sky_view.shape[1], sky_view.shape[0]), hit, c, lop)
     if uv_out is not None:
         uv_out.extend((u, v, hit))
     r, g, b, a = sample_rgba(sky_view, u, v)
     raw = (r * a, g * a, b * a)
-    _count(counts, "sanitized_sample", ~(np.isfinite(raw[0]) & np.isfinite(raw[1]) & np.isfinite(raw[2])))
+    count(counts, "sanitized_sample", ~(np.isfinite(raw[0]) & np.isfinite(raw[1]) & np.isfinite(raw[2])))
     return tuple(np.where(np.isfinite(x), x, F(0.0)).astype(np.float32) for x in raw)
 
 
@@ -249,15 +213,15 @@ def sky_ibl(planet_radius, atmos_radius, sky_view, transmittance, cube, camera_p
     n = face.size
     zero = np.zeros(n, np.float32)
     up_x = ~(np.abs(out_dir[1]) < UP_LIMIT)
-    _count(counts, "up_is_x", up_x)
-    _count(counts, "up_is_y", ~up_x)
+    count(counts, "up_is_x", up_x)
+    count(counts, "up_is_y", ~up_x)
     up = (np.where(up_x, F(1.0), F(0.0)).astype(np.float32), np.where(up_x, F(0.0), F(1.0)).astype(np.float32), zero)
     tangent = normalize(cross(up, out_dir))
     bitangent = cross(out_dir, tangent)
     history = [from_half_bits(cube[..., c]).reshape(-1) for c in range(4)]
     has_history = (history[3] > 0) & np.isfinite(history[0]) & np.isfinite(history[1]) & np.isfinite(history[2])
-    _count(counts, "has_history", has_history)
-    _count(counts, "no_history", ~has_history)
+    count(counts, "has_history", has_history)
+    count(counts, "no_history", ~has_history)
     px = x.astype(np.float32) + face.astype(np.float32) * F(37.0)
     py = y.astype(np.float32) + face.astype(np.float32) * F(17.0)
     base_rotation = frac(NOISE[2] * frac(px * NOISE[0] + py * NOISE[1]))
@@ -289,7 +253,7 @@ def sky_ibl(planet_radius, atmos_radius, sky_view, transmittance, cube, camera_p
         v = np.where(v > 0, v, F(0.0)).astype(np.float32)
         clamped |= ~(v < HALF_MAX)
         v = np.where(v < HALF_MAX, v, HALF_MAX).astype(np.float32)
-        out.append(np.where(has_history, _lerp(history[c], v, BLEND), v).astype(np.float32))
-    _count(counts, "clamped_at_half_max", clamped)
+        out.append(np.where(has_history, lerp(history[c], v, BLEND), v).astype(np.float32))
+    count(counts, "clamped_at_half_max", clamped)
     words = np.stack([channel_half(c) for c in (*out, np.ones(n, np.float32))], axis=-1).astype(np.uint16)
     return words.reshape(6, S, S, 4)

@@ -1,7 +1,7 @@
 """The numpy checker of oxc_apply_terrain_brush: steps B1-B10 of its header block in include/oxcull.h.  Every binary32 operation is one numpy
 float32 operation in the order the header states.  It joins rules that already have a Python copy and adds none of its own for them:
-noised (T3), the unorm loads and stores, lerp and clamp come from terrain_maps_model, saturate, the saturating conversions and pow from
-pixel_rules.  Images are numpy arrays in the header's layouts: heightmap uint16 [H, W], height_edit float32 [H, W], splat_edit uint32 [H, W],
+noised (T3) and the unorm16 load come from terrain_maps_model, whose pass defines them; lerp, clamp, the unorm8 store, the clamp bilinear's
+axis, saturate, the saturating conversions and pow from pixel_rules.  Images are numpy arrays in the header's layouts: heightmap uint16 [H, W], height_edit float32 [H, W], splat_edit uint32 [H, W],
 hit and region uint32 [4].  A stage returns new arrays and leaves its arguments unchanged.  `counts`, when given, receives how often each
 branch was taken: miss_clip, miss_parallel, miss_no_crossing, hit_step (a dict: march step -> hits), texels_outside, texels_zero_falloff,
 texels_written and mode_<name> (texels written per mode)."""
@@ -11,8 +11,8 @@ import dataclasses
 
 import numpy as np
 
-from pixel_rules import cvt_i32_sat, cvt_u32_sat, pow_rule, saturate
-from terrain_maps_model import clamp, lerp, load_unorm16, noised, unorm8
+from pixel_rules import axis_clamp, clamp, count, cvt_i32_sat, cvt_u32_sat, lerp, pow_rule, saturate, unorm8
+from terrain_maps_model import load_unorm16, noised
 
 F = np.float32
 TRACE, APPLY, BOTH = 1, 2, 3
@@ -42,11 +42,6 @@ class Params:
     layer: int = 0
 
 
-def _count(counts, name, n=1):
-    if counts is not None:
-        counts[name] = counts.get(name, 0) + int(n)
-
-
 def _f3(v):
     return [F(c) for c in v]
 
@@ -68,7 +63,7 @@ def clip_to_footprint(B: Params, origin, direction, counts=None):
         hi = lo + F(size)
         if np.abs(d) < F(1e-6):
             if o < lo or o > hi:
-                _count(counts, "miss_parallel")
+                count(counts, "miss_parallel")
                 return F(1.0), F(0.0)
             continue
         t0, t1 = (lo - o) / d, (hi - o) / d
@@ -77,20 +72,13 @@ def clip_to_footprint(B: Params, origin, direction, counts=None):
     return near, far
 
 
-def _axis(p, size: int):
-    g = (p * F(size) - F(0.5)).astype(np.float32)
-    fl = np.floor(g)
-    i = cvt_i32_sat(fl)
-    return np.clip(i, 0, size - 1), np.clip(i + 1, 0, size - 1), (g - fl).astype(np.float32)
-
-
 @np.errstate(all="ignore")
 def sample_height(B: Params, heightmap, wx, wz):
     W, H = int(B.resolution[0]), int(B.resolution[1])
     u = ((wx - F(B.world_min[0])) * F(B.inv_world_size[0])).astype(np.float32)
     v = ((wz - F(B.world_min[1])) * F(B.inv_world_size[1])).astype(np.float32)
-    x0, x1, fx = _axis(u, W)
-    y0, y1, fy = _axis(v, H)
+    x0, x1, fx = axis_clamp(u, W)
+    y0, y1, fy = axis_clamp(v, H)
     t = load_unorm16(heightmap)
     n = lerp(lerp(t[y0, x0], t[y0, x1], fx), lerp(t[y1, x0], t[y1, x1], fx), fy)
     return (F(B.base_height) + n * F(B.height_scale)).astype(np.float32)
@@ -124,13 +112,13 @@ def trace(B: Params, heightmap, counts=None, info=None):
     if info is not None:
         info.update(step=0, span=(span_x, span_y))
     if not span_x <= span_y:
-        _count(counts, "miss_parallel" if parallel else "miss_clip")
+        count(counts, "miss_parallel" if parallel else "miss_clip")
         return hit, region
     t = march_parameters(span_x, span_y)
     gaps = gap_at(B, heightmap, d, t)
     crossing = (gaps[1:] <= 0) & (gaps[:-1] > 0)
     if not crossing.any():
-        _count(counts, "miss_no_crossing")
+        count(counts, "miss_no_crossing")
         return hit, region
     i = int(np.argmax(crossing)) + 1
     if counts is not None:
@@ -191,14 +179,14 @@ def apply(B: Params, hit, heightmap, height_edit, splat_edit, counts=None):
     ty, tx = (g.reshape(-1) for g in np.mgrid[0:n, 0:n].astype(np.int64))
     sx, sy = int(cvt_i32_sat(np.floor(cx))) - radius + tx, int(cvt_i32_sat(np.floor(cy))) - radius + ty
     inside = (sx >= 0) & (sy >= 0) & (sx < W) & (sy < H)
-    _count(counts, "texels_outside", (~inside).sum())
+    count(counts, "texels_outside", (~inside).sum())
     x, y = sx[inside], sy[inside]
     dx, dy = (x.astype(np.float32) + F(0.5)) - cx, (y.astype(np.float32) + F(0.5)) - cy
     falloff = falloff_of(B, np.sqrt(dx * dx + dy * dy))
     keep = falloff > 0
-    _count(counts, "texels_zero_falloff", (~keep).sum())
-    _count(counts, "texels_written", keep.sum())
-    _count(counts, "mode_" + MODE_NAMES[int(B.mode)], keep.sum())
+    count(counts, "texels_zero_falloff", (~keep).sum())
+    count(counts, "texels_written", keep.sum())
+    count(counts, "mode_" + MODE_NAMES[int(B.mode)], keep.sum())
     x, y = x[keep], y[keep]
     amount = (falloff[keep] * F(B.strength)).astype(np.float32)
     if int(B.mode) == PAINT_LAYER:

@@ -1,8 +1,7 @@
 """The numpy checker of oxc_decode_terrain: steps D1-D8 of its header block in include/oxcull.h.  Every binary32 operation is one numpy float32
-operation in the order the header states.  It joins rules that already have a Python copy and adds none of its own for them: the G-buffer
-encodings (sRGB, unorm8, the normal halves, the flushing dequantize_half) come from visbuffer_decode_model, the pow rule, unproject,
-vec3_to_oct, saturate and the B10G11R11 pack from pixel_rules, the clamp bilinear's axis from terrain_brush_model, lerp and smoothstep from
-terrain_maps_model.  Images are numpy arrays in the header's layouts: vis uint32 [H, W], depth float32 [H, W], normalmap uint16 [h, w, 2],
+operation in the order the header states.  It joins rules that already have a Python copy and adds none of its own for them: the normal
+halves and the flushing dequantize_half come from visbuffer_decode_model and smoothstep from terrain_maps_model, whose passes define them;
+the unsaturated sRGB encode, unorm8, lerp, the clamp bilinear's axis, unproject, vec3_to_oct, saturate and the B10G11R11 pack from pixel_rules.  Images are numpy arrays in the header's layouts: vis uint32 [H, W], depth float32 [H, W], normalmap uint16 [h, w, 2],
 splatmap uint32 [h, w], materials uint8 [56 * material_count], hit uint32 [4]; the outputs as visbuffer_decode_model.decode returns them.
 `decode` returns new arrays and leaves its arguments unchanged.  `counts`, when given, receives how often each class and branch was taken
 (COUNTS); `pre`, when given, the values before quantisation at the terrain pixels."""
@@ -12,10 +11,9 @@ import dataclasses
 
 import numpy as np
 
-from pixel_rules import normalize, pack_b10g11r11, pack_unorm4x8, saturate, unproject, vec3_to_oct
-from terrain_brush_model import _axis
-from terrain_maps_model import lerp, smoothstep
-from visbuffer_decode_model import IMAGES, MATERIAL_BYTES, dequantize_half_flush, normal_half, srgb_encode, unorm8
+from pixel_rules import axis_clamp, count, lerp, normalize, pack_b10g11r11, pack_unorm4x8, saturate, srgb_unorm_encode, unorm8, unproject, vec3_to_oct
+from terrain_maps_model import smoothstep
+from visbuffer_decode_model import IMAGES, MATERIAL_BYTES, dequantize_half_flush, normal_half
 
 F = np.float32
 TERRAIN_INSTANCE_ID = 0xFFFFFE
@@ -44,11 +42,6 @@ class Terrain:
     brush_radius: float = 0.0
 
 
-def _count(counts, name, n=1):
-    if counts is not None:
-        counts[name] = counts.get(name, 0) + int(n)
-
-
 def is_terrain(vis) -> np.ndarray:
     return (np.asarray(vis).view(np.uint32) >> np.uint32(8)) == np.uint32(TERRAIN_INSTANCE_ID)
 
@@ -67,8 +60,8 @@ def sample_maps(T: Terrain, normalmap, splatmap, wx, wz):
     h, w = splatmap.shape
     u = ((wx - F(T.world_min[0])) * F(T.inv_world_size[0])).astype(np.float32)
     v = ((wz - F(T.world_min[1])) * F(T.inv_world_size[1])).astype(np.float32)
-    x0, x1, fx = _axis(u, w)
-    y0, y1, fy = _axis(v, h)
+    x0, x1, fx = axis_clamp(u, w)
+    y0, y1, fy = axis_clamp(v, h)
     bil = lambda t: lerp(lerp(t[y0, x0], t[y0, x1], fx), lerp(t[y1, x0], t[y1, x1], fx), fy)  # noqa: E731
     nm = np.ascontiguousarray(normalmap).view(np.float16).astype(np.float32)
     sp = np.asarray(splatmap, np.uint32)
@@ -86,8 +79,8 @@ def weights_of(w, counts=None):
     """D4."""
     weight_sum = ((w[0] + w[1]) + w[2]) + w[3]
     kept = weight_sum > F(1e-4)
-    _count(counts, "weight_sum_kept", kept.sum())
-    _count(counts, "weight_sum_default", (~kept).sum())
+    count(counts, "weight_sum_kept", kept.sum())
+    count(counts, "weight_sum_default", (~kept).sum())
     return [np.where(kept, w[k] / weight_sum, F(1.0 if k == 0 else 0.0)).astype(np.float32) for k in range(4)], weight_sum
 
 
@@ -117,8 +110,8 @@ def blend_layers(T: Terrain, weights, materials, material_count: int, counts=Non
         weight = weights[i]
         skip = weight <= F(0.0)
         on = ~skip
-        _count(counts, f"layer{i}_skipped", skip.sum())
-        _count(counts, f"layer{i}_{kind}", on.sum())
+        count(counts, f"layer{i}_skipped", skip.sum())
+        count(counts, f"layer{i}_{kind}", on.sum())
         if kind == "invalid":
             f = [1.0, 1.0, 1.0, 1.0, None, None, None, 1.0, 0.0]
         for k in range(4):
@@ -159,10 +152,10 @@ def decode(T: Terrain, vis, depth, inv_projection_view, normalmap, splatmap, mat
     # D1
     terrain = is_terrain(vis)
     ys, xs = np.nonzero(terrain)
-    _count(counts, "pixels_not_terrain", (~terrain).sum())
-    _count(counts, "pixels_terrain", terrain.sum())
+    count(counts, "pixels_not_terrain", (~terrain).sum())
+    count(counts, "pixels_terrain", terrain.sum())
     ring_state = "ring_off" if not F(T.brush_radius) > F(0.0) else ("ring_on" if int(np.asarray(hit, np.uint32)[3]) != 0 else "ring_invalid_hit")
-    _count(counts, ring_state)
+    count(counts, ring_state)
     if len(ys) == 0:
         return img
     # D2 - D5
@@ -177,16 +170,16 @@ def decode(T: Terrain, vis, depth, inv_projection_view, normalmap, splatmap, mat
     ring = None
     if ring_state == "ring_on":
         ring = ring_of(T, hit, wx, wz)
-        _count(counts, "ring_pixels_touched", (ring > 0).sum())
+        count(counts, "ring_pixels_touched", (ring > 0).sum())
         for k in range(3):
             s["albedo"][k] = lerp(s["albedo"][k], RING_COLOUR[k], ring)
     # D8
     for k in range(3):
         linear = s["albedo"][k] <= SRGB_KNEE
-        _count(counts, "srgb_linear", linear.sum())
-        _count(counts, "srgb_power", (~linear).sum())
+        count(counts, "srgb_linear", linear.sum())
+        count(counts, "srgb_power", (~linear).sum())
     a = s["albedo"]
-    img["albedo"][ys, xs] = unorm8(srgb_encode(a[0])) | (unorm8(srgb_encode(a[1])) << np.uint32(8)) | (unorm8(srgb_encode(a[2])) << np.uint32(16)) | (unorm8(a[3]) << np.uint32(24))
+    img["albedo"][ys, xs] = unorm8(srgb_unorm_encode(a[0])) | (unorm8(srgb_unorm_encode(a[1])) << np.uint32(8)) | (unorm8(srgb_unorm_encode(a[2])) << np.uint32(16)) | (unorm8(a[3]) << np.uint32(24))
     sx, sy = vec3_to_oct(shading)
     gx, gy = vec3_to_oct(geometric)
     img["normal"][ys, xs] = np.stack([normal_half(sx), normal_half(sy), normal_half(gx), normal_half(gy)], axis=-1)

@@ -16,7 +16,7 @@ import numpy as np
 import raster_model as RM
 import terrain_brush_model as TB
 import vsm_draw_model as VD
-from pixel_rules import mul_mp
+from pixel_rules import count, mul_mp
 
 F = np.float32
 VIS = 0xFFFFFE00  # VisBufferData(TERRAIN_INSTANCE_ID, 0).encode()
@@ -39,11 +39,6 @@ def projection_scale(resolution_y, fov_degrees) -> float:
     import math
 
     return float(F(float(resolution_y) * 0.5 / math.tan(math.radians(float(fov_degrees)) * 0.5)))
-
-
-def _count(counts, name, n=1):
-    if counts is not None:
-        counts[name] = counts.get(name, 0) + int(n)
 
 
 # ---- T1, T2 ----------------------------------------------------------------------------------------------------------------------------------------
@@ -142,7 +137,7 @@ def topology(lists, counts=None):
     """T4: (u float32 [P], v float32 [P], triangles int64 [K, 3]) of a patch, every triangle counter-clockwise in (u, v) unless its area is zero."""
     (n0, t0), (n1, t1), (n2, t2), (n3, t3), (nu, U), (nv, V) = lists
     if all(n == 1 for n, _ in lists):
-        _count(counts, "patches_all_one")
+        count(counts, "patches_all_one")
         return np.array([0, 1, 1, 0], np.float32), np.array([0, 0, 1, 1], np.float32), np.array([[0, 1, 2], [0, 2, 3]], np.int64)
     pw = nu - 1  # inner points a row
     u = [np.tile(U[1:nu], nv - 1)]
@@ -163,13 +158,13 @@ def topology(lists, counts=None):
         while oa < no or ib < ni:
             outer = ib == ni or (oa < no and to[oa + 1] <= axis[ib + 2])
             if counts is not None:
-                _count(counts, f"side{side}_{'outer' if outer else 'inner'}_steps")
+                count(counts, f"side{side}_{'outer' if outer else 'inner'}_steps")
                 if outer and ib < ni and to[oa + 1] == axis[ib + 2]:
-                    _count(counts, f"side{side}_ties")
+                    count(counts, f"side{side}_ties")
                 if ib == ni - 1 and not outer and oa < no:
-                    _count(counts, f"side{side}_inner_exhausted_first")
+                    count(counts, f"side{side}_inner_exhausted_first")
                 if oa == no - 1 and outer and ib < ni:
-                    _count(counts, f"side{side}_outer_exhausted_first")
+                    count(counts, f"side{side}_outer_exhausted_first")
             c0, c1 = base + oa, inner_of[side](ib)
             c2 = base + oa + 1 if outer else inner_of[side](ib + 1)
             tris.append(np.array([[c0, c2, c1] if flip else [c0, c1, c2]], np.int64))
@@ -251,7 +246,7 @@ def raster(image, clip, counts=None):
     tris, fc = np.concatenate(groups).reshape(-1, 3, 4).astype(np.float32), np.concatenate(from_clipper)
     kept, X, Y, z = _snap(tris, W, H)
     X, Y, z, fc = X[kept], Y[kept], z[kept], fc[kept]
-    _count(counts, "clipped", int((cls == 1).sum()))
+    count(counts, "clipped", int((cls == 1).sum()))
     if len(X) == 0:
         return
     minx, maxx, miny, maxy = X.min(1), X.max(1), Y.min(1), Y.max(1)
@@ -260,18 +255,18 @@ def raster(image, clip, counts=None):
     boxed = (px1 >= px0) & (py1 >= py0)
     fits = (px1 - px0 < RM.SMALL_SPAN) & (py1 - py0 < RM.SMALL_SPAN)
     small = boxed & fits & (fc | (np.maximum(maxx - minx, maxy - miny) < RM.SMALL_SPREAD))
-    _count(counts, "set_up", len(X))
-    _count(counts, "big", int((boxed & ~small).sum()))
+    count(counts, "set_up", len(X))
+    count(counts, "big", int((boxed & ~small).sum()))
     s = boxed & fits  # every walk writes the same texels: the box alone decides how the checker evaluates it
     if s.any():
-        _count(counts, "fragments", _small_fragments(image, X[s], Y[s], z[s], px0[s], py0[s], px1[s], py1[s]))
+        count(counts, "fragments", _small_fragments(image, X[s], Y[s], z[s], px0[s], py0[s], px1[s], py1[s]))
     for i in np.flatnonzero(boxed & ~fits):
         t = RM.setup(([int(X[i, 0]), int(X[i, 2]), int(X[i, 1])], [int(Y[i, 0]), int(Y[i, 2]), int(Y[i, 1])], [z[i, 0], z[i, 2], z[i, 1]]), W, H)
         RM.draw_triangle(t, VIS, image)
         if counts is not None:  # the fragments of this triangle alone: what it leaves in an empty window of its own box
             alone = np.zeros((H, W), np.uint64)
             RM.draw_triangle(t, VIS, alone)
-            _count(counts, "fragments", int((alone[t["py0"]:t["py1"] + 1, t["px0"]:t["px1"] + 1] != 0).sum()))
+            count(counts, "fragments", int((alone[t["py0"]:t["py1"] + 1, t["px0"]:t["px1"] + 1] != 0).sum()))
 
 
 def patch_clip(T, heightmap, cam: Camera, p: int, counts=None):
@@ -279,13 +274,13 @@ def patch_clip(T, heightmap, cam: Camera, p: int, counts=None):
     cs = corners(T, heightmap, p)
     e4 = factors(T, cam, cs)
     if any(not (e > 0) for e in e4):
-        _count(counts, "patches_discarded")
+        count(counts, "patches_discarded")
         return None
     lists, redone = lists_of(e4)
-    _count(counts, "inner_redone", redone)
+    count(counts, "inner_redone", redone)
     u, v, tris = topology(lists, counts)
-    _count(counts, "patches_drawn")
-    _count(counts, "triangles", len(tris))
+    count(counts, "patches_drawn")
+    count(counts, "triangles", len(tris))
     assert all(n == 1 for n, _ in lists) or len(tris) == triangle_count([n for n, _ in lists])
     world = domain_points(T, heightmap, cs, u, v)
     with np.errstate(all="ignore"):
@@ -305,7 +300,7 @@ def draw(T, heightmap, cam: Camera, visible, draw_cmd, W, H, image=None, clear=T
     for i in range(int(cmd[1])):
         entry = int(cmd[3]) + i
         if entry >= len(vis) or int(vis[entry]) >= patches:
-            _count(counts, "patches_skipped")
+            count(counts, "patches_skipped")
             continue
         clip = patch_clip(T, heightmap, cam, int(vis[entry]), counts)
         if clip is not None:

@@ -1,7 +1,7 @@
 """The numpy checker of oxc_generate_terrain_maps: steps T1-T12 of its header block in include/oxcull.h, vectorised over the texels (patches)
-a call writes.  Every binary32 operation is one numpy float32 operation in the order the header states; exp, pow and the rotation pair are
-the shared closed forms of pixel_rules, the cos / sin of an angle a local copy of what the sky checkers have (no checker imports another).
-Images are numpy arrays in the layouts of the header: heightmap uint16 [H, W], ridgemap uint16 [H, W] of binary16 bits, normalmap uint16
+a call writes.  Every binary32 operation is one numpy float32 operation in the order the header states; exp, pow, the cos / sin of an angle,
+frac, lerp, clamp and the unorm8 store are the shared rules of pixel_rules; the terrain-only rules (smoothstep, the unorm16 pair, noised)
+live here.  Images are numpy arrays in the layouts of the header: heightmap uint16 [H, W], ridgemap uint16 [H, W] of binary16 bits, normalmap uint16
 [H, W, 2], splatmap uint32 [H, W], height_edit float32 [H, W], splat_edit uint32 [H, W], patch_minmax float32 [py, px, 2].  A stage returns
 new arrays and leaves its arguments unchanged.  `counts`, when given, receives how many texels (or cells) took each side of the branches
 the tests must not leave empty; `pre`, when given, the values before their quantisation."""
@@ -11,11 +11,10 @@ import dataclasses
 
 import numpy as np
 
-from pixel_rules import INV_LN2, channel_half, cos_sin_turn, cvt_u32_sat, exp2_f64_round, f32a, from_half_bits, pow_rule, saturate, sign
+from pixel_rules import channel_half, clamp, cos_sin_angle_rule, count, cvt_u32_sat, exp_rule, f32a, frac, from_half_bits, lerp, pow_rule, saturate, sign, unorm8
 
 F = np.float32
 TAU_F = F(6.283185307179586476925286766559)
-INV_TWO_PI = float.fromhex("0x1.45f306dc9c883p-3")
 EPSILON = F(1e-10)
 K0, K1 = F(0.3183099), F(0.3678794)
 S0, S1 = F(0.06711056), F(0.00583715)
@@ -68,24 +67,7 @@ class Derive:
     ridge_drainage_scale: float = 1.0
 
 
-def _count(counts, name, mask):
-    if counts is not None:
-        counts[name] = counts.get(name, 0) + int(np.asarray(mask).sum())
-
-
 # ---- the small rules ---------------------------------------------------------------------------------------------------------------------------
-def frac(x):
-    return (x - np.floor(x)).astype(np.float32)
-
-
-def lerp(a, b, t):
-    return (a + (b - a) * t).astype(np.float32)
-
-
-def clamp(x, lo, hi):
-    return np.fmin(np.fmax(f32a(x), F(lo)), F(hi))
-
-
 def ease_out(t):
     v = F(1.0) - saturate(t)
     return (F(1.0) - v * v).astype(np.float32)
@@ -94,8 +76,8 @@ def ease_out(t):
 @np.errstate(all="ignore")
 def smooth_start(t, s, counts=None):
     linear = t >= s
-    _count(counts, "smooth_start_linear", linear)
-    _count(counts, "smooth_start_quadratic", ~linear)
+    count(counts, "smooth_start_linear", linear)
+    count(counts, "smooth_start_quadratic", ~linear)
     return np.where(linear, t - F(0.5) * s, ((F(0.5) * t) * t) / s).astype(np.float32)
 
 
@@ -106,32 +88,8 @@ def smoothstep(e0, e1, x):
 
 
 @np.errstate(all="ignore")
-def exp_rule(x):
-    return exp2_f64_round(f32a(x).astype(np.float64) * INV_LN2).reshape(np.shape(x))
-
-
-@np.errstate(all="ignore")
-def cos_sin_rule(a):
-    """(cos(a), sin(a)): the turn of the cos rule, the sine negated for a < 0; NaN for a non-finite a."""
-    a = f32a(a)
-    u = np.abs(a).astype(np.float64) * INV_TWO_PI
-    u = np.where(np.isfinite(u), u, 0.0)
-    t = (u - np.floor(u)).astype(np.float32)
-    t = np.where(t == F(1.0), F(0.0), t).astype(np.float32)
-    cs, sn = cos_sin_turn(t)
-    sn = np.where(a < 0, -sn, sn)
-    ok = np.isfinite(a)
-    return np.where(ok, cs, F(np.nan)).astype(np.float32), np.where(ok, sn, F(np.nan)).astype(np.float32)
-
-
-@np.errstate(all="ignore")
 def unorm16(e) -> np.ndarray:
     return cvt_u32_sat(np.floor(saturate(e) * F(65535.0) + F(0.5))).astype(np.uint16)
-
-
-@np.errstate(all="ignore")
-def unorm8(e) -> np.ndarray:
-    return cvt_u32_sat(np.floor(saturate(e) * F(255.0) + F(0.5))).astype(np.uint32)
 
 
 def load_unorm16(q) -> np.ndarray:
@@ -192,8 +150,8 @@ def phacelle(ppx, ppy, gx, gy, E: Erosion, seed: int, counts=None, ties=None):
     """-> (ph.x, ph.y, side.x, side.y)."""
     ln = np.sqrt(gx * gx + gy * gy)
     keep = ln > EPSILON
-    _count(counts, "normalize_safe_zero", ~keep)
-    _count(counts, "normalize_safe_kept", keep)
+    count(counts, "normalize_safe_zero", ~keep)
+    count(counts, "normalize_safe_kept", keep)
     nx, ny = np.where(keep, gx / ln, F(0.0)).astype(np.float32), np.where(keep, gy / ln, F(0.0)).astype(np.float32)
     cell = F(E.cell_scale)
     side_x, side_y = ((ny * F(-1.0)) * cell) * TAU_F, ((nx * F(1.0)) * cell) * TAU_F
@@ -209,11 +167,11 @@ def phacelle(ppx, ppy, gx, gy, E: Erosion, seed: int, counts=None, ties=None):
             dx, dy = (fx - ga) - hx * F(0.5), (fy - gb) - hy * F(0.5)
             sq = dx * dx + dy * dy
             weight = np.fmax(F(0.0), exp_rule((-sq) * F(2.0)) - WEIGHT_BIAS)
-            _count(counts, "weight_zero_cells", weight == 0)
-            _count(counts, "weight_positive_cells", weight > 0)
+            count(counts, "weight_zero_cells", weight == 0)
+            count(counts, "weight_positive_cells", weight > 0)
             weight_sum = weight_sum + weight
             w = (dx * side_x + dy * side_y) + phase_offset
-            cs, sn = cos_sin_rule(w)
+            cs, sn = cos_sin_angle_rule(w)
             dir_x, dir_y = dir_x + cs * weight, dir_y + sn * weight
     den = np.fmax(weight_sum, EPSILON)
     ipx, ipy = dir_x / den, dir_y / den
@@ -297,9 +255,9 @@ def generate(G: Generate, resolution, height_edit, heightmap, ridgemap, texel_or
     ty, tx = (g.reshape(-1) for g in np.meshgrid(ys, xs, indexing="ij"))
     h, ridge = generate_values(G, resolution, tx, ty, counts)
     total = h + height_edit[ty, tx]
-    _count(counts, "height_clipped_low", total <= 0)
-    _count(counts, "height_clipped_high", total >= 1)
-    _count(counts, "height_inside", (total > 0) & (total < 1))
+    count(counts, "height_clipped_low", total <= 0)
+    count(counts, "height_clipped_high", total >= 1)
+    count(counts, "height_inside", (total > 0) & (total < 1))
     if pre is not None:
         pre.update(tx=tx, ty=ty, height=h, ridge=ridge)
     heightmap[ty, tx] = unorm16(total)
@@ -345,7 +303,7 @@ def derive(D: Derive, resolution, heightmap, ridgemap, splat_edit, normalmap, sp
     out = [lerp(a, b, p[3]) for a, b in zip((grass, rock, drainage, snow), painted)]
     layers = np.stack(out)
     for k, name in enumerate(("grass_dominant", "rock_dominant", "drainage_dominant", "snow_dominant")):
-        _count(counts, name, (np.argmax(np.nan_to_num(layers), axis=0) == k) & (np.nan_to_num(layers[k]) > 0.5))
+        count(counts, name, (np.argmax(np.nan_to_num(layers), axis=0) == k) & (np.nan_to_num(layers[k]) > 0.5))
     splatmap[ty, tx] = unorm8(out[0]) | (unorm8(out[1]) << np.uint32(8)) | (unorm8(out[2]) << np.uint32(16)) | (unorm8(out[3]) << np.uint32(24))
     return normalmap, splatmap
 

@@ -53,7 +53,7 @@ def test_one_exp_rule():
     x = np.concatenate([x, np.linspace(-90.0, 90.0, 4001).astype(np.float32)])
     a, b = AM.exp_rule(x), TM.exp_rule(x)
     assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
-    c, d = AM.cos_rule(x), TM.cos_rule(x)
+    c, d = AM.cos_turn_rule(x), TM.cos_turn_rule(x)
     assert np.array_equal(c.view(np.uint32), d.view(np.uint32))
 
 

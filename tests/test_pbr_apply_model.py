@@ -11,6 +11,7 @@ import ambient_occlusion_model as AM
 import pbr_apply_model as PM
 import visbuffer_decode_model as VD
 from pbr_apply_model import HAS_CONTACT_SHADOWS, HAS_DIRECTIONAL_LIGHT, HAS_SKY, TRANSPARENT_BACKGROUND
+from pixel_rules import srgb_unorm_encode, unorm8
 from scenes import CAMERA, I16, INV_PV, SKY, SUN_INTENSITY
 from scenes import PBR_SUN as SUN
 from scenes import synthetic_inputs
@@ -27,7 +28,7 @@ def ulps(a, b):
 
 def test_srgb_decode_inverts_the_decode_pass_encoder():
     byte = np.arange(256)
-    assert np.array_equal(VD.unorm8(VD.srgb_encode(PM.srgb_decode(byte))), byte)
+    assert np.array_equal(unorm8(srgb_unorm_encode(PM.srgb_decode(byte))), byte)
     lin = PM.srgb_decode(byte)
     assert lin[0] == 0 and lin[255] == 1 and (np.diff(lin) > 0).all()
 
@@ -57,13 +58,13 @@ def test_exp2_rule_is_within_one_ulp():
 
 def test_cos_rule_is_within_one_ulp():
     x = np.linspace(0.0, np.pi, 200001).astype(np.float32)
-    got, want = PM.cos_rule(x), np.cos(x.astype(np.float64)).astype(np.float32)
+    got, want = PM.cos_reduced_rule(x), np.cos(x.astype(np.float64)).astype(np.float32)
     assert ulps(got, want).max() <= 1  # also next to pi / 2: the reduction keeps the small cosines of the binary32 neighbours of pi / 2 to full precision
-    assert PM.cos_rule(F(0.0))[0] == 1.0 and np.array_equal(PM.cos_rule(-x[:1000]), got[:1000])
+    assert PM.cos_reduced_rule(F(0.0))[0] == 1.0 and np.array_equal(PM.cos_reduced_rule(-x[:1000]), got[:1000])
     wide = np.array([10.0, 1000.0, 1.0e6, 16777216.0], dtype=np.float32)
-    assert np.abs(PM.cos_rule(wide).astype(np.float64) - np.cos(wide.astype(np.float64))).max() < 1e-7
+    assert np.abs(PM.cos_reduced_rule(wide).astype(np.float64) - np.cos(wide.astype(np.float64))).max() < 1e-7
     for bad in (np.nan, np.inf, -np.inf, 16777218.0, -3.0e7):
-        assert np.isnan(PM.cos_rule(F(bad))[0])
+        assert np.isnan(PM.cos_reduced_rule(F(bad))[0])
 
 
 def test_pow_rule_is_unchanged():
@@ -168,7 +169,7 @@ def test_fully_metallic_pixel():
     NoV = F(F(1.0) + F(1e-5))
     want = []
     for byte, mbits in ((255, 6), (0, 6), (128, 5)):
-        alb = PM.srgb_decode(byte)[0]
+        alb = PM.srgb_decode([byte])[0]
         F0 = F(F(0.04) + F(F(alb - F(0.04)) * F(1.0)))
         d, s = rough_brdf(NoV, 1.0, 1.0, F0, metallic=1.0, albedo=alb)
         assert d == 0.0
@@ -230,7 +231,7 @@ def test_spot_light_inside_the_band_and_outside():
     tilt = (F(np.sin(0.3)), F(0.0), F(-np.cos(0.3)))
     ln = F(np.sqrt(F(F(F(tilt[0] * tilt[0]) + F(0.0)) + F(tilt[2] * tilt[2]))))
     cos_angle = F(F(F(F(-0.0) * F(tilt[0] / ln)) + F(F(-0.0) * F(tilt[1] / ln))) + F(F(-1.0) * F(tilt[2] / ln)))
-    c_in, c_out = PM.cos_rule(F(0.2))[0], PM.cos_rule(F(0.4))[0]
+    c_in, c_out = PM.cos_reduced_rule(F(0.2))[0], PM.cos_reduced_rule(F(0.4))[0]
     t = F(F(cos_angle - c_out) / F(c_in - c_out))
     assert 0.3 < t < 0.7
     band = F(F(t * t) * F(F(3.0) - F(F(2.0) * t)))

@@ -98,13 +98,13 @@ def test_closed_forms_at_their_exact_points():
     for g, w in zip(got.tolist(), want):
         assert (math.isnan(g) if w is None else g == w), (got, want)
     assert not np.signbit(got[2])  # a negative zero y counts as positive: +pi, where IEEE atan2 gives -pi
-    cs, sn = SM.cos_sin_rule(np.array([0.0, math.pi / 2, -math.pi / 2, np.inf, np.nan, 1.0, -1.0], dtype=np.float32))
+    cs, sn = SM.cos_sin_angle_rule(np.array([0.0, math.pi / 2, -math.pi / 2, np.inf, np.nan, 1.0, -1.0], dtype=np.float32))
     assert cs[0] == 1 and sn[0] == 0 and np.isnan(cs[3:5]).all() and np.isnan(sn[3:5]).all() and sn[5] == -sn[6] and cs[5] == cs[6]
     assert abs(float(sn[1]) - 1.0) < 1e-7 and abs(float(sn[2]) + 1.0) < 1e-7
-    from atmosphere_model import cos_rule
+    from pixel_rules import cos_turn_rule as cos_rule
 
     a = np.linspace(-7.0, 7.0, 20001).astype(np.float32)
-    assert np.array_equal(SM.cos_sin_rule(a)[0].view(np.uint32), cos_rule(a).view(np.uint32))  # the one cos rule
+    assert np.array_equal(SM.cos_sin_angle_rule(a)[0].view(np.uint32), cos_rule(a).view(np.uint32))  # the one cos rule
 
 
 def _ulps(a, b):
@@ -129,7 +129,7 @@ def test_closed_form_accuracy():
     assert np.max(np.abs(ours - exact)[ordinary] / np.maximum(np.abs(exact[ordinary]), 1e-300)) <= 12 * 2.0 ** -53
     assert _ulps(SM.atan2_rule(gy, gx), exact.astype(np.float32))[ordinary].max() <= 1
     phi = (SM.TAU_F * np.linspace(0.0, 1.0, 1_000_001, endpoint=False).astype(np.float32)).astype(np.float32)
-    cs, sn = SM.cos_sin_rule(phi)
+    cs, sn = SM.cos_sin_angle_rule(phi)
     bound = 2.0 * math.pi * 2.0 ** -25 + 2.0 ** -25  # the turn is rounded to binary32 (half a step of 2^-24 under 1), then the result
     assert np.abs(sn.astype(np.float64) - np.sin(phi.astype(np.float64))).max() <= bound
     assert np.abs(cs.astype(np.float64) - np.cos(phi.astype(np.float64))).max() <= bound

@@ -63,13 +63,13 @@ def test_vignette_amount_zero_leaves_the_colour_alone():
 
 
 def test_cos_rule():
-    assert TM.cos_rule(np.array([0.0, -0.0], dtype=np.float32)).tolist() == [1.0, 1.0]
-    assert np.isnan(TM.cos_rule(np.array([np.inf, -np.inf, np.nan], dtype=np.float32))).all()
+    assert TM.cos_turn_rule(np.array([0.0, -0.0], dtype=np.float32)).tolist() == [1.0, 1.0]
+    assert np.isnan(TM.cos_turn_rule(np.array([np.inf, -np.inf, np.nan], dtype=np.float32))).all()
     a = np.linspace(-40.0, 40.0, 2001, dtype=np.float32)  # more than six turns to either side
     # the rule rounds the turn t in [0, 1) to binary32: up to 2^-25 of a turn, 2 pi 2^-25 = 1.9e-7 of angle, and |d cos| <= |d angle|; the result
     # is rounded to binary32 once more, half an ulp of a value up to 1: 2^-25
     bound = 2.0 * math.pi * 2.0 ** -25 + 2.0 ** -25
-    assert np.max(np.abs(TM.cos_rule(a).astype(np.float64) - np.cos(a.astype(np.float64)))) <= bound
+    assert np.max(np.abs(TM.cos_turn_rule(a).astype(np.float64) - np.cos(a.astype(np.float64)))) <= bound
 
 
 def test_pcg3d16_known_answers():

@@ -8,7 +8,7 @@ import torch
 
 import visbuffer_decode_model as VD
 import vsm_draw_model as DM
-from pixel_rules import to_half_bits
+from pixel_rules import srgb_unorm_encode, to_half_bits, unorm8
 from scenes import DECODE_MAIN_SIZE as MAIN_SIZE
 from scenes import build_scene
 from scenes import decode_assert_not_degenerate as assert_not_degenerate
@@ -73,14 +73,14 @@ def test_srgb_bytes():
     """0 -> 0; 0.0031308f is on the linear branch: 12.92 * 0.0031308 = 0.04045 -> floor(0.04045 * 255 + 0.5) = floor(10.81) = 10;
     0.5 -> 1.055 * 0.5^(1 / 2.4) - 0.055 = 0.73536 -> floor(188.02) = 188; 1 -> pow = 1 exactly, 1.055f - 0.055f rounds to at least
     0.99999994: floor(255.49998) = 255; above 1 saturates: 255; negative and NaN: 0."""
-    got = VD.unorm8(VD.srgb_encode(np.array([0.0, 0.0031308, 0.5, 1.0, np.nextafter(F(1.0), F(2.0)), 1.5, -0.5, np.nan, np.inf], dtype=np.float32)))
+    got = unorm8(srgb_unorm_encode(np.array([0.0, 0.0031308, 0.5, 1.0, np.nextafter(F(1.0), F(2.0)), 1.5, -0.5, np.nan, np.inf], dtype=np.float32)))
     assert got.tolist() == [0, 10, 188, 255, 255, 255, 0, 0, 255]
 
 
 def test_srgb_encoder_inverts_the_binary64_decoder_on_every_byte():
     b = np.arange(256, dtype=np.float64) / 255.0
     linear = np.where(b <= 0.04045, b / 12.92, ((b + 0.055) / 1.055) ** 2.4)
-    assert VD.unorm8(VD.srgb_encode(linear.astype(np.float32))).tolist() == list(range(256))
+    assert unorm8(srgb_unorm_encode(linear.astype(np.float32))).tolist() == list(range(256))
 
 
 def test_ufloat_words():
@@ -95,7 +95,7 @@ def test_ufloat_words():
 
 def test_unorm8_at_the_half_way_value():
     """v * 255 + 0.5 lands on an integer for v = (k + 0.5) / 255 only up to rounding; 0.5f gives 127.5 + 0.5 = 128 exactly: floor 128."""
-    assert VD.unorm8(np.array([0.5, 0.0, 1.0, 0.5 / 255.0, np.nan, -1.0, 2.0], dtype=np.float32)).tolist() == [128, 0, 255, 1, 0, 0, 255]
+    assert unorm8(np.array([0.5, 0.0, 1.0, 0.5 / 255.0, np.nan, -1.0, 2.0], dtype=np.float32)).tolist() == [128, 0, 255, 1, 0, 0, 255]
 
 
 def test_explicit_flush_equals_dequantize_half_on_every_half():

@@ -1,6 +1,6 @@
 """The numpy checker of oxc_apply_tonemap: steps 1-11 of its header block in include/oxcull.h, vectorised over the image.  Every binary32
-operation is one numpy float32 operation in the order the header states; log2 / exp2 / pow and the rotation pair come from pixel_rules, the
-exp and cos rules (only this pass needs them) live here.  The pixel-independent constants of step 5 are evaluated once by `constants()`, in
+operation is one numpy float32 operation in the order the header states; log2 / exp2 / pow, the exp and cos rules and the sRGB encode come
+from pixel_rules.  The pixel-independent constants of step 5 are evaluated once by `constants()`, in
 binary32 in the Slang's order -- the same way the library's host code does.  The source is uint32 [H, W] (B10G11R11) or uint16 [H, W, 4]
 (R16G16B16A16 Sfloat); the bloom is U level 0 in the same format; the result is uint32 [H, W].  `stats`, when given, receives how many
 values took each side of every branch of the rule."""
@@ -8,17 +8,16 @@ from __future__ import annotations
 
 import numpy as np
 
-from pixel_rules import INV_LN2, cos_sin_turn, cvt_i32_sat, exp2_f64_round, exp2_rule, f32a, from_half_bits, log2_rule, pack_unorm4x8, pow_rule, saturate, unpack_b10g11r11
+from pixel_rules import cos_turn_rule, count, cvt_i32_sat, exp2_rule, exp_rule, f32a, from_half_bits, log2_rule, pack_unorm4x8, pow_rule, saturate, unpack_b10g11r11
+from pixel_rules import srgb_encode as shared_srgb_encode
 
 F = np.float32
 NONE, ACES, AGX, GT7 = 0, 1, 2, 3
 OUT_RGBA8_SRGB, OUT_BGRA8_SRGB, OUT_RGBA8_UNORM = 0, 1, 2
 HAS_EYE_ADAPTATION, HAS_BLOOM, HAS_FILM_GRAIN, HAS_CHROMATIC_ABERRATION, HAS_VIGNETTE, TRANSPARENT_BACKGROUND = 1 << 2, 1 << 3, 1 << 6, 1 << 7, 1 << 8, 1 << 11
-INV_TWO_PI = float.fromhex("0x1.45f306dc9c883p-3")
 PI_F = F(3.1415926535897932384626433832795)
 SIMPLEX_F2 = F((np.sqrt(3.0) - 1.0) / 2.0)  # the binary32 nearest the real value
 SIMPLEX_G2 = F((3.0 - np.sqrt(3.0)) / 6.0)
-SRGB_P = F(1.0 / 2.4)                       # the binary32 nearest 1 / 2.4
 
 ACES_IN = [[0.59719, 0.35458, 0.04823], [0.07600, 0.90834, 0.01566], [0.02840, 0.13383, 0.83777]]
 ACES_OUT = [[1.60475, -0.53108, -0.07367], [-0.10208, 1.10813, -0.00605], [-0.00327, -0.07276, 1.07602]]
@@ -31,11 +30,9 @@ PQ_M1, PQ_M2_BASE, PQ_C1, PQ_C2, PQ_C3, PQ_C = F(0.1593017578125), F(78.84375), 
 REFERENCE_LUMINANCE, SDR_PAPER_WHITE = F(100.0), F(250.0)
 
 
-def _count(stats, name, mask):
-    if stats is not None:
-        mask = np.asarray(mask)
-        stats[name] = stats.get(name, 0) + int(mask.sum())
-        stats["not " + name] = stats.get("not " + name, 0) + int(mask.size - mask.sum())
+def _count_sides(stats, name, mask):
+    count(stats, name, mask)
+    count(stats, "not " + name, ~np.asarray(mask))
 
 
 def mat(rows):
@@ -53,34 +50,13 @@ def mul_mm(A, B):
     return [[F(F(F(A[r][0] * B[0][c]) + F(A[r][1] * B[1][c])) + F(A[r][2] * B[2][c])) for c in range(3)] for r in range(3)]
 
 
-# ---- the transcendentals only this pass needs (step 6) ------------------------------------------------------------------------------------------
-@np.errstate(all="ignore")
-def exp_rule(x) -> np.ndarray:
-    """exp(x) = exp2_f64_round((double)x * log2(e))."""
-    return exp2_f64_round(np.atleast_1d(f32a(x)).astype(np.float64) * INV_LN2)
-
-
-@np.errstate(all="ignore")
-def cos_rule(a) -> np.ndarray:
-    """cos(a): NaN for a non-finite a; else u = (double)|a| / (2 pi), t = (float)(u - floor(u)), t == 1 becomes 0, cos of the turn t."""
-    a = np.atleast_1d(f32a(a))
-    u = np.abs(a).astype(np.float64) * INV_TWO_PI
-    u = np.where(np.isfinite(u), u, 0.0)
-    t = (u - np.floor(u)).astype(np.float32)
-    t = np.where(t == F(1.0), F(0.0), t).astype(np.float32)
-    return np.where(np.isfinite(a), cos_sin_turn(t)[0], F(np.nan)).astype(np.float32)
-
-
+# ---- the closed forms in the shape of their argument ---------------------------------------------------------------------------------------------
 def log2_r(x):
     return log2_rule(x).reshape(np.shape(x))
 
 
 def _pow(v, p):
     return pow_rule(np.asarray(v, dtype=np.float32).reshape(-1), p).reshape(np.shape(v))
-
-
-def _exp(x):
-    return exp_rule(np.asarray(x, dtype=np.float32).reshape(-1)).reshape(np.shape(x))
 
 
 def _exp2(x):
@@ -167,7 +143,7 @@ def constants(chromatic_aberration_amount=0.0) -> dict:
     kk = F(F(lin - F(1.0)) / F(alpha - F(1.0)))
     k["gt_mid"], k["gt_toe"] = mid, toe
     k["gt_ka"] = F(F(target * lin) + F(target * kk))
-    k["gt_kb"] = F(F(F(-target) * kk) * exp_rule(F(lin / kk))[0])
+    k["gt_kb"] = F(F(F(-target) * kk) * exp_rule(F(lin / kk)))
     k["gt_kc"] = F(F(-1.0) / F(kk * target))
     k["gt_lin_peak"] = F(lin * target)
     k["gt_mid_span"] = F(mid - F(0.0))
@@ -199,16 +175,16 @@ def aces_fitted(c, stats=None):
         fit.append((a / b).astype(np.float32))
     out = mul_mv(mat(ACES_OUT), fit)
     for x in out:
-        _count(stats, "aces below 0", x < 0)
-        _count(stats, "aces above 1", x > 1)
+        _count_sides(stats, "aces below 0", x < 0)
+        _count_sides(stats, "aces above 1", x > 1)
     return tuple(saturate(x) for x in out)
 
 
 @np.errstate(all="ignore")
 def dual_section(x, k, stats=None):
     linear = x < k["agx_s"]
-    _count(stats, "agx linear", linear)
-    curved = k["agx_peak"] - k["agx_span"] * _exp((k["agx_neg_c"] * (x - k["agx_s"])) / k["agx_peak"])
+    _count_sides(stats, "agx linear", linear)
+    curved = k["agx_peak"] - k["agx_span"] * exp_rule((k["agx_neg_c"] * (x - k["agx_s"])) / k["agx_peak"])
     return np.where(linear, x, curved).astype(np.float32)
 
 
@@ -227,8 +203,8 @@ def smooth_step(x, edge0, edge1, span, stats=None, name=None):
     t = (x - edge0) / span
     below, above = x < edge0, x > edge1
     if name:
-        _count(stats, name + " below", below)
-        _count(stats, name + " above", above)
+        _count_sides(stats, name + " below", below)
+        _count_sides(stats, name + " above", above)
     return np.where(below, F(0.0), np.where(above, F(1.0), (t * t) * (F(3.0) - F(2.0) * t))).astype(np.float32)
 
 
@@ -239,10 +215,10 @@ def gt_curve(x, k, stats=None):
     negative = x < F(0.0)
     weight_linear = smooth_step(x, F(0.0), k["gt_mid"], k["gt_mid_span"], stats, "gt weight")
     weight_toe = F(1.0) - weight_linear
-    shoulder = k["gt_ka"] + k["gt_kb"] * _exp(x * k["gt_kc"])
+    shoulder = k["gt_ka"] + k["gt_kb"] * exp_rule(x * k["gt_kc"])
     toe = x < k["gt_lin_peak"]
-    _count(stats, "gt negative", negative)
-    _count(stats, "gt toe or linear", toe & ~negative)
+    _count_sides(stats, "gt negative", negative)
+    _count_sides(stats, "gt toe or linear", toe & ~negative)
     toe_mapped = k["gt_mid"] * _pow(x / k["gt_mid"], k["gt_toe"])
     return np.where(negative, F(0.0), np.where(toe, weight_toe * toe_mapped + weight_linear * x, shoulder)).astype(np.float32)
 
@@ -251,13 +227,13 @@ def gt_curve(x, k, stats=None):
 def eotf(n, k, stats=None):
     """eotfSt2084 (tonemap.slang:387-424)."""
     n = f32a(n)
-    _count(stats, "eotf below 0", n < 0)
-    _count(stats, "eotf above 1", n > 1)
+    _count_sides(stats, "eotf below 0", n < 0)
+    _count_sides(stats, "eotf above 1", n > 1)
     n = np.where(n < F(0.0), F(0.0), n)
     n = np.where(n > F(1.0), F(1.0), n).astype(np.float32)
     np_ = _pow(n, k["pq_inv_m2"])
     l = np_ - PQ_C1  # noqa: E741
-    _count(stats, "eotf l below 0", l < 0)
+    _count_sides(stats, "eotf l below 0", l < 0)
     l = np.where(l < F(0.0), F(0.0), l).astype(np.float32)  # noqa: E741
     l = l / (PQ_C2 - PQ_C3 * np_)  # noqa: E741
     l = _pow(l, k["pq_inv_m1"])  # noqa: E741
@@ -286,7 +262,7 @@ def gt7_apply(rgb, k, stats=None):
     out = []
     for ch in range(3):
         blended = k["gt_one_minus_blend"] * skewed[ch] + k["gt_blend"] * scaled[ch]
-        _count(stats, "gt above target", blended > k["gt_target"])
+        _count_sides(stats, "gt above target", blended > k["gt_target"])
         out.append((k["gt_sdr"] * np.fmin(blended, k["gt_target"])).astype(np.float32))
     return tuple(out)
 
@@ -366,7 +342,7 @@ def vignette_factor(W, H, xs, ys, amount):
     pi_over_4 = F(PI_F * F(0.25))
     mask = []
     for d, c in ((np.abs(xs - cx), cx), (np.abs(ys - cy), cy)):
-        m = cos_rule(((d.astype(np.float32) / F(c)) * F(amount) * pi_over_4).reshape(-1)).reshape(d.shape)
+        m = cos_turn_rule((d.astype(np.float32) / F(c)) * F(amount) * pi_over_4)
         m = m * m
         mask.append(m * m)
     return np.fmin(np.fmax(mask[0] * mask[1], F(0.0)), F(1.0)).astype(np.float32)
@@ -394,10 +370,9 @@ def film_grain(xs, ys, scale, seed, stats=None):
 # ---- step 11: the store -------------------------------------------------------------------------------------------------------------------------
 @np.errstate(all="ignore")
 def srgb_encode(c, stats=None):
-    c = saturate(c)
-    low = c <= F(0.0031308)
-    _count(stats, "srgb linear", low)
-    return np.where(low, c * F(12.92), F(1.055) * _pow(c, SRGB_P) - F(0.055)).astype(np.float32)
+    """The shared srgb_encode; `stats` receives which side of its comparison each value took."""
+    _count_sides(stats, "srgb linear", saturate(c) <= F(0.0031308))
+    return shared_srgb_encode(c)
 
 
 def store(rgb, alpha, output_format: int, stats=None) -> np.ndarray:

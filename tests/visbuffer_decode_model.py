@@ -7,13 +7,12 @@ from __future__ import annotations
 import numpy as np
 
 import vsm_draw_model as DM
-from pixel_rules import _u32, cross, mul_mp, pack_ufloat, pack_unorm4x8, pow_rule, to_half_bits, vec3_to_oct
+from pixel_rules import _u32, cross, mul_mp, pack_ufloat, pack_unorm4x8, srgb_unorm_encode, to_half_bits, unorm8, vec3_to_oct
 
 F = np.float32
 TERRAIN_INSTANCE_ID = 0xFFFFFE
 HALF_NAN = 0x7E00
 MATERIAL_BYTES = 56
-SRGB_EXPONENT = F(1.0) / F(2.4)
 IMAGES = ("albedo", "normal", "emissive", "mro")
 COUNTER_NAMES = ("decoded", "empty", "zero_vertex_index", "default_material")
 
@@ -26,22 +25,10 @@ def dequantize_half_flush(h) -> np.ndarray:
     return np.where((h & 0x7C00) == 0, sign, h.view(np.float16).astype(np.float32)).astype(np.float32)
 
 
-def decode_normal(packed) -> np.ndarray:
-    """Mesh::decode_normal (scene.slang:486-489): uint32 [...] -> float32 [..., 3]."""
+def decode_mesh_normal(packed) -> np.ndarray:
+    """Mesh::decode_mesh_normal (scene.slang:486-489): uint32 [...] -> float32 [..., 3]."""
     p = np.asarray(packed, dtype=np.uint32)
     return np.stack([((p >> np.uint32(s)) & np.uint32(1023)).astype(np.float32) / F(511.0) - F(1.0) for s in (20, 10, 0)], axis=-1)
-
-
-@np.errstate(all="ignore")
-def srgb_encode(x) -> np.ndarray:
-    x = np.atleast_1d(np.asarray(x, dtype=np.float32))
-    return np.where(x <= F(0.0031308), F(12.92) * x, F(1.055) * pow_rule(x, SRGB_EXPONENT) - F(0.055)).astype(np.float32)
-
-
-def unorm8(v) -> np.ndarray:
-    """u32(floor(saturate(v) * 255.0 + 0.5)); a NaN gives 0."""
-    v = np.asarray(v, dtype=np.float32)
-    return pack_unorm4x8(v, np.zeros_like(v), np.zeros_like(v), np.zeros_like(v))
 
 
 def normal_half(x) -> np.ndarray:
@@ -112,7 +99,7 @@ def fetch(scene, meshlet_instances, texels, materials, material_count: int) -> d
     has = mesh[v, 1] != 0  # a null vertex_normals decodes (0, 0, 0)
     if has.any():
         packed = _u32(scene.normals).reshape(-1)[((mesh[v, 1][has] - scene.normals.data_ptr()) // 4)[:, None] + vi[v][has]]
-        normals[has] = decode_normal(packed)
+        normals[has] = decode_mesh_normal(packed)
     out["normals"] = normals
     out["world"] = np.asarray(scene.transforms, dtype=np.float32).reshape(-1, 16)[mi[v, 3]]
     mat = np.zeros((len(v), MATERIAL_BYTES // 2), dtype=np.uint16)
@@ -183,7 +170,7 @@ def decode(scene, meshlet_instances, vis, depth, projection_view, materials=None
             img["normal"][ys, xs] = np.stack([hx, hy, hx, hy], axis=-1)
             # 6. - 8. the material factors, per distinct triangle
             m = dequantize_half_flush(f["material_halves"][:, :9])
-            albedo = (unorm8(srgb_encode(m[:, 0])) | (unorm8(srgb_encode(m[:, 1])) << np.uint32(8)) | (unorm8(srgb_encode(m[:, 2])) << np.uint32(16))
+            albedo = (unorm8(srgb_unorm_encode(m[:, 0])) | (unorm8(srgb_unorm_encode(m[:, 1])) << np.uint32(8)) | (unorm8(srgb_unorm_encode(m[:, 2])) << np.uint32(16))
                       | (unorm8(m[:, 3]) << np.uint32(24)))
             emissive = pack_ufloat(m[:, 4], 6) | (pack_ufloat(m[:, 5], 6) << np.uint32(11)) | (pack_ufloat(m[:, 6], 5) << np.uint32(22))
             mro = pack_unorm4x8(m[:, 8], m[:, 7], np.ones_like(m[:, 7]), np.zeros_like(m[:, 7]))
