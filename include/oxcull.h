@@ -948,7 +948,8 @@ oxc_status oxc_draw_visbuffer(oxc_ctx* ctx, const oxc_prepared_frame* frame, con
  * factor alone (scene.slang:110-159 without the image branches), sample_occlusion_color is 1.0, normal.xy equals normal.zw, and what feeds
  * only the sampling -- uv_size, uv_offset, the texcoord stream, the tangent frame, the rescaled ddx / ddy of compute_partial_derivatives
  * (visbuffer_decode.slang:74-83) -- is not computed.  Camera::position is read by the Slang for the tangent frame only; the context has no
- * such field.  Terrain pixels and the mesh-shader path are out of scope.
+ * such field.  Terrain pixels and the mesh-shader path are out of scope.  oxc_decode_visbuffer_textured (below) is the pass with an
+ * image table and everything left out here.
  * Arithmetic: canonical binary32 -- round to nearest even, one fixed evaluation order, no contraction, IEEE division and square root; 1.0 / x
  * is a division; sums run left to right as written in the Slang; mul(M, (p, 1)).r = ((M[r][0] * p.x + M[r][1] * p.y) + M[r][2] * p.z) +
  * M[r][3]; mul(vec, mat) is the dot product in component order; saturate(x) = min(max(x, 0), 1) with fmaxf / fminf, so a NaN gives 0.  The
@@ -1023,6 +1024,102 @@ typedef struct oxc_decode_context {
 
 /* meshlet_instances, mesh_instances, meshes and transforms come from `frame`, as in oxc_draw_visbuffer. */
 oxc_status oxc_decode_visbuffer(oxc_ctx* ctx, const oxc_prepared_frame* frame, const oxc_decode_context* context, void* hip_stream);
+
+/* ---- Textured visbuffer decode: the same pass with the five material images sampled ------------------------------------------
+ * The whole of passes/visbuffer_decode.slang: what oxc_decode_visbuffer leaves out -- the texcoord stream, uv_size / uv_offset, the
+ * rescaled ddx / ddy (visbuffer_decode.slang:74-83), the tangent frame (:128-151), SampleGrad of the albedo, normal, emissive,
+ * metallic-roughness and occlusion images (scene.slang:110-159) and the normal map (:153-167).  oxc_decode_visbuffer does not change; this
+ * entry takes its context, with the same limits and the same four outputs, and an image table.
+ * A hardware sampler's fixed-point weights, LOD approximation and anisotropy are implementation-defined; as for the bilinear of
+ * oxc_apply_bloom, the trilinear of oxc_generate_ambient_occlusion and the repeat axis of oxc_apply_tonemap, the rule here is a stated
+ * one in the canonical binary32 of oxc_decode_visbuffer (round to nearest even, evaluation in the order written, no contraction, IEEE
+ * division and square root) that the device and the checker (tests/textured_decode_model.py) both follow.  Stated differences from a
+ * Vulkan sampler: weights are binary32, not 8-bit fixed point; lambda is the closed-form log2 of the exact rho, not an approximation;
+ * LinearSamplerRepeatedAnisotropy is sampled as linear / repeat / linear-mip -- anisotropic filtering is not attempted.
+ * Out of scope: block-compressed formats; mip generation (the caller supplies every level); the alpha test of the draw (alpha_cutoff
+ * is not read); the mesh-shader path.
+ * Image formats: OXC_IMAGE_R8G8B8A8_UNORM (channel = f32(byte) / 255.0f), OXC_IMAGE_R8G8B8A8_SRGB (r, g, b = srgb_decode(byte) of
+ * oxc_apply_pbr step 2; alpha = f32(byte) / 255.0f) and OXC_IMAGE_R8G8_UNORM (r, g as Unorm, b = 0, a = 1: NormalTwoComponent maps).  R is
+ * the lowest byte of a texel.  Level k of an image is max(1, width >> k) x max(1, height >> k) texels, row-major, tightly packed, at
+ * dptr + level_offset[k]; a side is at most 16384 and an image has at most 15 levels (a larger `levels` is taken as 15).
+ * Sampler records: filter 0 nearest / 1 linear, address 0 repeat / 1 clamp to edge, mip_filter 0 nearest / 1 linear; any other value of
+ * a field is taken as 1.  The five SamplingMode presets of Renderer.cpp:64-70: LinearRepeated {1, 0, 1}, LinearClamped {1, 1, 1}, NearestRepeated
+ * {0, 0, 0}, NearestClamped {0, 1, 0}, LinearRepeatedAnisotropy {1, 0, 1}.
+ * Per pixel, steps 1 - 5 of oxc_decode_visbuffer unchanged (step 2 reads the whole 14-word Material; the default Material is all zero:
+ * no flag set).  Then:
+ *   9. texcoords  (Mesh::decode_texcoord, scene.slang:491-497)  t_i = (dequantize_half(packed.x), dequantize_half(packed.y)) of
+ *              texture_coords[vertex_i], x in the low half, by the flushing dequantize_half of step 3.  A null Mesh::texture_coords
+ *              decodes every texcoord as (0, 0).
+ *  10. gradients (visbuffer_decode.slang:74-83, 32-39, 119-122)  two_over_resolution = (2.0 / f32(W), 2.0 / f32(H));  sx =
+ *              two_over_resolution.x, sy = -two_over_resolution.y;  ddx' = ddx * sx, ddy' = ddy * sy per component, ddx_sum' = ddx_sum * sx,
+ *              ddy_sum' = ddy_sum * sy (ddx, ddy and the sums of step 4);  interp_ddx_w = 1.0 / (interp_inv_w + ddx_sum'), interp_ddy_w =
+ *              1.0 / (interp_inv_w + ddy_sum');  ddx''.c = interp_ddx_w * (lambda.c * interp_inv_w + ddx'.c) - lambda.c, ddy''.c =
+ *              interp_ddy_w * (lambda.c * interp_inv_w + ddy'.c) - lambda.c.  gradient_of: uv.c = (lambda.x * t_0.c + lambda.y * t_1.c) +
+ *              lambda.z * t_2.c, uv_ddx.c = (ddx''.x * t_0.c + ddx''.y * t_1.c) + ddx''.z * t_2.c, uv_ddy likewise.  Then with uv_size and
+ *              uv_offset through dequantize_half: uv.c = uv.c * uv_size.c + uv_offset.c, uv_ddx.c = uv_ddx.c * uv_size.c, uv_ddy.c =
+ *              uv_ddy.c * uv_size.c.
+ *  11. tangent frame (:128-151), computed where a normal image is sampled.  r_i = world_i - camera_position per component;  pos_ddx.c =
+ *              (ddx''.x * r_0.c + ddx''.y * r_1.c) + ddx''.z * r_2.c, pos_ddy likewise;  dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z;
+ *              N = world_normal of step 5;  pos_ddx_s.c = pos_ddx.c - dot(pos_ddx, N) * N.c, pos_ddy_s likewise;  jacobian_sign =
+ *              sign(uv_ddx.x * uv_ddy.y - uv_ddx.y * uv_ddy.x) with sign(NaN) = 0 and sign(+-0) = 0;  T.c = jacobian_sign * (uv_ddy.y *
+ *              pos_ddx_s.c - uv_ddx.y * pos_ddy_s.c), normalised by step 5's normalize (sqrt, three divisions) only when jacobian_sign != 0;
+ *              w = jacobian_sign * sign(dot(pos_ddy, cross(N, pos_ddx)));  B.c = (-w) * cross(N, T).c;  cross(a, b).x = a.y * b.z - a.z *
+ *              b.y and its rotations.
+ *  12. SampleGrad, one rule for all five images, of image (width, height, levels) under the material's sampler:
+ *              LOD.  mx = (uv_ddx.x * f32(width), uv_ddx.y * f32(height)), my likewise from uv_ddy;  rho = fmaxf(sqrt(mx.x * mx.x + mx.y *
+ *              mx.y), sqrt(my.x * my.x + my.y * my.y)) (fmaxf: a NaN loses to a number);  lambda = (float)log2_f64(rho), the closed form of
+ *              oxc_generate_ambient_occlusion before its rounding (zero, a denormal, a negative value and NaN give -Inf);  a NaN lambda is
+ *              taken as 0;  lambda = fminf(fmaxf(lambda, 0), f32(levels - 1)).  Linear mips: lo = (int)floor(lambda), hi = min(lo + 1,
+ *              levels - 1); both levels are always tapped; result.c = lerp(tap_lo.c, tap_hi.c, lambda - floor(lambda)), lerp(a, b, t) = a +
+ *              (b - a) * t.  Nearest mips: the one level min((int)floor(lambda + 0.5f), levels - 1).
+ *              Level tap of a w x h level at uv.  Linear filter, per axis with coordinate p and side n: repeat is the repeat axis of
+ *              oxc_apply_tonemap (g = p * f32(n) - 0.5, i0 = floor_mod(the saturating conversion of floor(g), n), i1 = i0 + 1 wrapped to 0,
+ *              f = g - floor(g)); clamp is the clamp axis of oxc_apply_bloom (i0 and i1 = i and i + 1 clamped to [0, n - 1]).  The four
+ *              texels are decoded first, then combined per channel in the bloom's order: lerp(lerp(t00, t10, fx), lerp(t01, t11, fx), fy).
+ *              Nearest filter: the texel at i = the saturating conversion of floor(p * f32(n)), floor_mod(i, n) under repeat, clamped to
+ *              [0, n - 1] under clamp.  A NaN coordinate converts to texel 0, +-Inf saturates to INT_MAX / INT_MIN before the wrap or the
+ *              clamp, and a coordinate beyond int32 likewise: every tap reads inside its level for every bit pattern of uv.
+ *  13. bounds  An image whose Has*Image flag is set is "absent" when its index is >= image_count, or its record has levels == 0, a null
+ *              dptr, a format above 2 or a side of 0 or above 16384: nothing of it is read and the result is that of a clear flag.  A
+ *              sampler_index >= sampler_count samples as linear / repeat / linear-mip.  The one sampler_index serves all five images.
+ *  14. outputs  albedo = albedo_factor * texel in all four channels, then step 6.  Normal, when the normal image is present: s = texel.rgb *
+ *              2.0 - 1.0 per channel;  NormalFlipY: s.y = -s.y;  NormalTwoComponent: s.z = sqrt(saturate(1.0 - (s.x * s.x + s.y * s.y)));
+ *              n.c = (s.x * T.c + s.y * B.c) + s.z * N.c, normalised as in step 5;  normal.rg = vec3_to_oct(n).  normal.ba is always
+ *              vec3_to_oct(world_normal), the bytes oxc_decode_visbuffer writes; without a normal image .rg equals .ba.  emissive = factor *
+ *              texel.rgb, then step 8.  (metallic, roughness) = (metallic_factor * texel.b, roughness_factor * texel.g);  occlusion =
+ *              texel.r of the occlusion image, 1.0 without one;  then step 7.  With no image flag set (or every flagged image absent) all
+ *              four outputs are oxc_decode_visbuffer's, byte for byte.
+ * Limits (else OXC_INVALID_ARG, nothing launched): those of oxc_decode_visbuffer; images->struct_size; images_buffer not null, 8-byte
+ * aligned and image_count * 144 bytes when image_count != 0; samplers_buffer not null, 4-byte aligned and sampler_count * 16 bytes when
+ * sampler_count != 0.  With a count of 0 its buffer is not looked at.  The image records live on the device and the host cannot validate
+ * them: beyond step 13 the scene owns their correctness (level offsets inside the allocation, R8G8B8A8 levels 4-byte aligned, R8G8 levels
+ * 2-byte aligned), as it does for the mesh chain.  One launch, 2 KiB of LDS, no scratch, no allocation, no host synchronisation;
+ * capturable into a HIP graph. */
+enum { OXC_IMAGE_R8G8B8A8_UNORM = 0, OXC_IMAGE_R8G8B8A8_SRGB = 1, OXC_IMAGE_R8G8_UNORM = 2 };
+enum { OXC_FILTER_NEAREST = 0, OXC_FILTER_LINEAR = 1 };
+enum { OXC_ADDRESS_REPEAT = 0, OXC_ADDRESS_CLAMP_TO_EDGE = 1 };
+
+typedef struct oxc_material_image { /* device record, 144 bytes */
+  uint64_t dptr;
+  uint32_t width, height, levels, format;
+  uint64_t level_offset[15]; /* bytes from dptr */
+} oxc_material_image;
+
+typedef struct oxc_material_sampler { /* device record, 16 bytes */
+  uint32_t filter, address, mip_filter, _pad;
+} oxc_material_sampler;
+
+typedef struct oxc_material_images {
+  uint32_t struct_size;     /* sizeof(oxc_material_images) */
+  float camera_position[3]; /* Camera::position: the tangent frame reads it */
+  uint32_t image_count;
+  uint32_t sampler_count;
+  oxc_buffer images_buffer;   /* in: oxc_material_image[image_count]: what Material::*_image_index name (the engine's global_images) */
+  oxc_buffer samplers_buffer; /* in: oxc_material_sampler[sampler_count]: what Material::sampler_index names (global_samplers) */
+} oxc_material_images;
+
+oxc_status oxc_decode_visbuffer_textured(oxc_ctx* ctx, const oxc_prepared_frame* frame, const oxc_decode_context* context,
+                                         const oxc_material_images* images, void* hip_stream);
 
 /* ---- PBR apply: the lit HDR image from the G-buffer and the shadow terms --------------------------------------------------
  * Replaces the no-atmosphere branch of RendererInstance::apply_pbr (Oxylus/src/Render/Passes/PBR.cpp:313-534, the else branch from :435,

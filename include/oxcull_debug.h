@@ -96,6 +96,7 @@ enum { OXC_TUNE_ASYNC_MTEST_BLOCKS_PER_CU = 0, OXC_TUNE_ASYNC_TRI_BLOCKS_PER_CU 
        OXC_TUNE_BOUNDS_CHUNK = 21 /* meshlets per gather / cone launch pair of oxc_build_meshlet_bounds; 0 (default): 2^18.  Only the loop's step: the scratch keeps the layout and size of the default, so a value above 2^18 (or above the rows the scratch holds) is clamped.  It takes effect at the next call.  With it a small mesh is processed in several chunks with a ragged last one.  Same outputs either way */,
        OXC_TUNE_TERRAIN_DRAW_GRID = 22 /* cap, in blocks, of every launch of oxc_draw_terrain; 0 (default): uncapped (eight blocks per CU).  It takes effect at the next draw.  With it a block takes several patches through its stride loop.  Same outputs either way */,
        OXC_TUNE_TERRAIN_DRAW_STATS = 23 /* 1: oxc_draw_terrain runs counting instantiations of its kernel and of the big-list kernels (the fragment counter of oxc_debug_terrain_draw_stats); 0 (default): off.  Same image */,
+       OXC_TUNE_VISBUFFER_DECODE_TEXTURED_STATS = 24 /* 1: oxc_decode_visbuffer_textured runs its counting instantiation (oxc_debug_visbuffer_decode_textured_stats); 0 (default): off.  Same images */,
        OXC_TUNE_FXAA_STATS = 17/* 1: oxc_apply_fxaa runs its counting instantiation (oxc_debug_fxaa_stats); 0 (default): off */,
        OXC_TUNE_BLOOM_TAIL_LEVEL = 16 /* the level T from which oxc_apply_bloom's one-block tail kernel takes over (downsample levels T .. L - 1, upsample levels back to T); 0 (default): chosen by the library; a value >= L: no tail kernel, one launch per level.  A forced T is raised to the first level whose source level has at most 16 384 texels (64 per thread of the one block), so the knob cannot turn a large image into one long single-block kernel.  Same outputs either way */ };
 oxc_status oxc_debug_set_tuning(oxc_ctx* ctx, uint32_t knob, uint32_t value);
@@ -155,6 +156,14 @@ oxc_status oxc_debug_ambient_occlusion_stats(oxc_ctx* ctx, uint32_t* host_out15,
  * out4 = {decoded pixels (all four images written from a triangle), empty pixels (rule 1), pixels written as zeros because a vertex index
  * exceeds vertex_count - 1 (rule 2), decoded pixels whose material_index is beyond material_count (the all-zero Material)}. */
 oxc_status oxc_debug_visbuffer_decode_stats(oxc_ctx* ctx, uint32_t* host_out4, void* hip_stream);
+
+/* Measurement hook: what the last oxc_decode_visbuffer_textured on this context did, after oxc_debug_set_tuning(
+ * OXC_TUNE_VISBUFFER_DECODE_TEXTURED_STATS, 1); synchronises the stream.  out13 = {the four counters of oxc_debug_visbuffer_decode_stats;
+ * pixels that sampled their albedo, normal, emissive, metallic-roughness, occlusion image (flag set and the image present, step 13);
+ * level taps (two per sampled image under a linear mip filter, one under a nearest one); pixels that sampled a normal image with
+ * jacobian_sign == 0; waves with a decoded pixel whose live lanes all named one material (the uniform path), and the other such waves
+ * (the per-lane path)}. */
+oxc_status oxc_debug_visbuffer_decode_textured_stats(oxc_ctx* ctx, uint32_t* host_out13, void* hip_stream);
 
 /* Measurement hook: what the last oxc_apply_pbr on this context did, counted by a counting instantiation of its kernel (same image,
  * slower) after oxc_debug_set_tuning(OXC_TUNE_PBR_APPLY_STATS, 1); synchronises the stream.

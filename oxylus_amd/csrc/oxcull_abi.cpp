@@ -69,7 +69,7 @@ void oxc_destroy(oxc_ctx* ctx) {
   if (ctx->sprite_scratch) (void)hipFree(ctx->sprite_scratch);
   if (ctx->vsm_scratch) (void)hipFree(ctx->vsm_scratch);
   if (ctx->vsm_draw_scratch) (void)hipFree(ctx->vsm_draw_scratch);
-  for (const auto& pc : {ctx->vsm_resolve_stats, ctx->contact_shadows_stats, ctx->ambient_occlusion_stats, ctx->visbuffer_decode_stats, ctx->pbr_apply_stats, ctx->fxaa_stats})
+  for (const auto& pc : {ctx->vsm_resolve_stats, ctx->contact_shadows_stats, ctx->ambient_occlusion_stats, ctx->visbuffer_decode_stats, ctx->visbuffer_decode_textured_stats, ctx->pbr_apply_stats, ctx->fxaa_stats})
     if (pc.dev) (void)hipFree(pc.dev);
   if (ctx->comm) (void)oxc_comm_destroy(ctx);
   if (ctx->slots) (void)hipFree(ctx->slots);
@@ -167,6 +167,7 @@ oxc_status oxc_debug_set_tuning(oxc_ctx* ctx, uint32_t knob, uint32_t value) {
     case OXC_TUNE_VSM_RESOLVE_STATS: ctx->vsm_resolve_stats.on = value != 0u; return OXC_OK;
     case OXC_TUNE_CONTACT_SHADOWS_STATS: ctx->contact_shadows_stats.on = value != 0u; return OXC_OK;
     case OXC_TUNE_VISBUFFER_DECODE_STATS: ctx->visbuffer_decode_stats.on = value != 0u; return OXC_OK;
+    case OXC_TUNE_VISBUFFER_DECODE_TEXTURED_STATS: ctx->visbuffer_decode_textured_stats.on = value != 0u; return OXC_OK;
     case OXC_TUNE_PBR_APPLY_STATS: ctx->pbr_apply_stats.on = value != 0u; return OXC_OK;
     case OXC_TUNE_FXAA_STATS: ctx->fxaa_stats.on = value != 0u; return OXC_OK;
     case OXC_TUNE_EYE_ADAPTATION_GRID: ctx->eye_adaptation_grid = value; return OXC_OK;

@@ -119,10 +119,11 @@ oxc_status oxc_generate_ambient_occlusion(oxc_ctx* ctx, const oxc_ambient_occlus
   return OXC_OK;
 }
 
-oxc_status oxc_decode_visbuffer(oxc_ctx* ctx, const oxc_prepared_frame* f, const oxc_decode_context* c, void* hip_stream) {
-  if (!ctx) return OXC_INVALID_ARG;
-  if (!f || !c || c->struct_size != sizeof(oxc_decode_context)) return fail(ctx, OXC_INVALID_ARG, "decode_visbuffer: bad frame / context / struct_size");
-  const char* const entry = "decode_visbuffer";
+}  // extern "C"
+
+namespace {
+// The limits oxc_decode_visbuffer and oxc_decode_visbuffer_textured share, in the header's order
+oxc_status decode_limits(oxc_ctx* ctx, const char* entry, const oxc_prepared_frame* f, const oxc_decode_context* c) {
   const oxc_image& dimg = c->depth_attachment;
   if (c->width == 0u || c->height == 0u) return bad_arg(ctx, entry, "the extent must not be zero");
   if (dimg.width != c->width || dimg.height != c->height) return bad_arg(ctx, entry, "depth_attachment extent differs from the visbuffer's (width, height)");
@@ -141,10 +142,13 @@ oxc_status oxc_decode_visbuffer(oxc_ctx* ctx, const oxc_prepared_frame* f, const
   if (f->meshlet_instances_buffer.bytes < (uint64_t)c->meshlet_instance_count * sizeof(GpuMeshletInstance))
     return bad_arg(ctx, entry, "meshlet_instances_buffer smaller than meshlet_instance_count records");
   if (reinterpret_cast<uintptr_t>(f->transforms_world_buffer.dptr) & 15u) return bad_arg(ctx, entry, "transforms_world_buffer must be 16-byte aligned");
-  OXC_ENTER(ctx, hip_stream, s);
-  VisbufferDecodeArgs a;
-  std::memset(&a, 0, sizeof a);
-  OXC_TRY(arm_counters(ctx, entry, "hipMalloc(visbuffer decode counters)", ctx->visbuffer_decode_stats, 16, s, &a.stats));
+  return OXC_OK;
+}
+
+// The kernel arguments both calls take from the frame and the context (`a` zeroed; stats set by the caller)
+void decode_args(const oxc_prepared_frame* f, const oxc_decode_context* c, VisbufferDecodeArgs& a) {
+  const oxc_image& dimg = c->depth_attachment;
+  const oxc_buffer& mat = c->materials_buffer;
   a.vis = static_cast<const uint32_t*>(c->visbuffer_attachment.dptr);
   a.depth_bits = static_cast<const uint32_t*>(dimg.dptr);
   a.albedo = static_cast<uint32_t*>(c->albedo_attachment.dptr);
@@ -164,7 +168,49 @@ oxc_status oxc_decode_visbuffer(oxc_ctx* ctx, const oxc_prepared_frame* f, const
   a.transforms = static_cast<const float*>(f->transforms_world_buffer.dptr);
   a.materials = static_cast<const uint32_t*>(mat.dptr);
   for (int k = 0; k < 16; k++) a.pv[k] = c->projection_view[k];
+}
+}  // namespace
+
+extern "C" {
+
+oxc_status oxc_decode_visbuffer(oxc_ctx* ctx, const oxc_prepared_frame* f, const oxc_decode_context* c, void* hip_stream) {
+  if (!ctx) return OXC_INVALID_ARG;
+  if (!f || !c || c->struct_size != sizeof(oxc_decode_context)) return fail(ctx, OXC_INVALID_ARG, "decode_visbuffer: bad frame / context / struct_size");
+  const char* const entry = "decode_visbuffer";
+  OXC_TRY(decode_limits(ctx, entry, f, c));
+  OXC_ENTER(ctx, hip_stream, s);
+  VisbufferDecodeArgs a;
+  std::memset(&a, 0, sizeof a);
+  OXC_TRY(arm_counters(ctx, entry, "hipMalloc(visbuffer decode counters)", ctx->visbuffer_decode_stats, 16, s, &a.stats));
+  decode_args(f, c, a);
   launch_visbuffer_decode(a, s);
+  OXC_HIP(ctx, hipGetLastError());
+  return OXC_OK;
+}
+
+oxc_status oxc_decode_visbuffer_textured(oxc_ctx* ctx, const oxc_prepared_frame* f, const oxc_decode_context* c, const oxc_material_images* m, void* hip_stream) {
+  if (!ctx) return OXC_INVALID_ARG;
+  if (!f || !c || !m || c->struct_size != sizeof(oxc_decode_context) || m->struct_size != sizeof(oxc_material_images))
+    return fail(ctx, OXC_INVALID_ARG, "decode_visbuffer_textured: bad frame / context / images / struct_size");
+  const char* const entry = "decode_visbuffer_textured";
+  OXC_TRY(decode_limits(ctx, entry, f, c));
+  const oxc_buffer& img = m->images_buffer;
+  if (m->image_count && (!img.dptr || img.bytes < (uint64_t)m->image_count * sizeof(oxc_material_image) || (reinterpret_cast<uintptr_t>(img.dptr) & 7u)))
+    return bad_arg(ctx, entry, "images_buffer must hold image_count 8-byte aligned oxc_material_image records of 144 bytes");
+  const oxc_buffer& smp = m->samplers_buffer;
+  if (m->sampler_count && (!smp.dptr || smp.bytes < (uint64_t)m->sampler_count * sizeof(oxc_material_sampler) || (reinterpret_cast<uintptr_t>(smp.dptr) & 3u)))
+    return bad_arg(ctx, entry, "samplers_buffer must hold sampler_count 4-byte aligned oxc_material_sampler records of 16 bytes");
+  OXC_ENTER(ctx, hip_stream, s);
+  VisbufferDecodeTexturedArgs a;
+  std::memset(&a, 0, sizeof a);
+  OXC_TRY(arm_counters(ctx, entry, "hipMalloc(textured visbuffer decode counters)", ctx->visbuffer_decode_textured_stats, 64, s, &a.g.stats));
+  decode_args(f, c, a.g);
+  for (int k = 0; k < 3; k++) a.camera_position[k] = m->camera_position[k];
+  a.image_count = m->image_count;
+  a.sampler_count = m->sampler_count;
+  a.images = m->image_count ? static_cast<const MaterialImage*>(img.dptr) : nullptr;
+  a.samplers = m->sampler_count ? static_cast<const uint32_t*>(smp.dptr) : nullptr;
+  launch_visbuffer_decode_textured(a, s);
   OXC_HIP(ctx, hipGetLastError());
   return OXC_OK;
 }
@@ -350,6 +396,10 @@ oxc_status oxc_debug_ambient_occlusion_stats(oxc_ctx* ctx, uint32_t* host_out15,
 
 oxc_status oxc_debug_visbuffer_decode_stats(oxc_ctx* ctx, uint32_t* host_out4, void* hip_stream) {
   return read_counters(ctx, "debug_visbuffer_decode_stats", "oxc_decode_visbuffer", &oxc_ctx::visbuffer_decode_stats, host_out4, 16, hip_stream);
+}
+
+oxc_status oxc_debug_visbuffer_decode_textured_stats(oxc_ctx* ctx, uint32_t* host_out13, void* hip_stream) {
+  return read_counters(ctx, "debug_visbuffer_decode_textured_stats", "oxc_decode_visbuffer_textured", &oxc_ctx::visbuffer_decode_textured_stats, host_out13, 52, hip_stream);
 }
 
 oxc_status oxc_debug_pbr_apply_stats(oxc_ctx* ctx, uint32_t* host_out9, void* hip_stream) {

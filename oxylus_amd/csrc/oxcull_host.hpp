@@ -110,6 +110,7 @@ struct oxc_ctx {
   PassCounters contact_shadows_stats;    // OXC_TUNE_CONTACT_SHADOWS_STATS: u32[12]
   PassCounters ambient_occlusion_stats;  // OXC_TUNE_AMBIENT_OCCLUSION_STATS: u32[15] (16 allocated)
   PassCounters visbuffer_decode_stats;   // OXC_TUNE_VISBUFFER_DECODE_STATS: u32[4]
+  PassCounters visbuffer_decode_textured_stats;  // OXC_TUNE_VISBUFFER_DECODE_TEXTURED_STATS: u32[13] (16 allocated)
   PassCounters pbr_apply_stats;          // OXC_TUNE_PBR_APPLY_STATS: u32[9]
   PassCounters fxaa_stats;               // OXC_TUNE_FXAA_STATS: u32[4]
   uint32_t eye_adaptation_grid = 0;      // OXC_TUNE_EYE_ADAPTATION_GRID: cap of the histogram kernel's grid in blocks, 0 = uncapped

@@ -627,6 +627,21 @@ struct VisbufferDecodeArgs {
   float pv[16];
 };
 void launch_visbuffer_decode(const VisbufferDecodeArgs& a, hipStream_t s);
+// oxcull_visbuffer_decode_textured.hip: the same with the five material images sampled (oxc_decode_visbuffer_textured)
+struct MaterialImage {  // oxc_material_image
+  uint64_t dptr;
+  uint32_t width, height, levels, format;
+  uint64_t level_offset[15];
+};
+static_assert(sizeof(MaterialImage) == 144, "layout");
+struct VisbufferDecodeTexturedArgs {
+  VisbufferDecodeArgs g;        // stats: nullptr, or u32[13] (oxc_debug_visbuffer_decode_textured_stats)
+  float camera_position[3];
+  uint32_t image_count, sampler_count;
+  const MaterialImage* images;  // [image_count]
+  const uint32_t* samplers;     // [sampler_count][4]: {filter, address, mip_filter, _pad}, 4-byte aligned
+};
+void launch_visbuffer_decode_textured(const VisbufferDecodeTexturedArgs& a, hipStream_t s);
 // oxcull_pbr_apply.hip: the lit HDR image from the G-buffer and the shadow terms (oxc_apply_pbr)
 struct PbrApplyArgs {
   const float* depth;       // [h][w]

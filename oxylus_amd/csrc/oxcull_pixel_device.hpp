@@ -211,6 +211,23 @@ OXC_DEV Axis axis_at(float p, float fsize, int last) {
   return a;
 }
 
+// One axis of a repeat-mode bilinear tap at the normalised coordinate `coord` of a level `size` texels wide: both texel coordinates lie in
+// [0, size - 1] for every bit pattern of `coord` (a NaN converts to 0, +-Inf saturates).  oxc_apply_tonemap's bloom and lens taps and the
+// repeat address mode of oxc_decode_visbuffer_textured.
+struct WrapAxis {
+  int i0, i1;
+  float f;
+};
+OXC_DEV WrapAxis wrap_axis(float coord, int size) {
+  const float g = coord * (float)size - 0.5f;
+  const float fl = floorf(g);
+  WrapAxis a;
+  a.i0 = floor_mod_i(cvt_i32_sat(fl), size);
+  a.i1 = a.i0 + 1 == size ? 0 : a.i0 + 1;
+  a.f = g - fl;
+  return a;
+}
+
 // The pixel of this thread: an 8 x 8 pixel tile per wave, a 16 x 16 tile per block of 256 threads.
 OXC_DEV uint2 tile_pixel() {
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;

@@ -269,22 +269,6 @@ OXC_DEV float load_channel(const void* base, size_t i) {
   return dequantize_half(static_cast<const unsigned short*>(base)[i * 4u + CH]);
 }
 
-// One axis of a repeat-mode bilinear tap at the normalised coordinate `coord` of a level `size` texels wide: both texel coordinates lie in
-// [0, size - 1] for every bit pattern of `coord` (a NaN converts to 0, +-Inf saturates).
-struct WrapAxis {
-  int i0, i1;
-  float f;
-};
-OXC_DEV WrapAxis wrap_axis(float coord, int size) {
-  const float g = coord * (float)size - 0.5f;
-  const float fl = floorf(g);
-  WrapAxis a;
-  a.i0 = floor_mod_i(cvt_i32_sat(fl), size);
-  a.i1 = a.i0 + 1 == size ? 0 : a.i0 + 1;
-  a.f = g - fl;
-  return a;
-}
-
 template <int FORMAT, int CH>
 OXC_DEV float tap_channel(const void* src, int sw, int sh, float u, float v) {
   const WrapAxis ax = wrap_axis(u, sw), ay = wrap_axis(v, sh);

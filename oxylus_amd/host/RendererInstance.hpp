@@ -399,8 +399,11 @@ public:
 
   // Oxylus/src/Render/Passes/DrawGeometry.cpp:192-274, the full-screen pass after the draw (RendererInstance.cpp:924): the four G-buffer
   // images from visbuffer_attachment / depth_attachment, with context.cull_camera.projection_view as Camera::projection_view and
-  // prepared_frame.materials_buffer.  Material factors only, no texture sampling.  Rules: include/oxcull.h, oxc_decode_visbuffer.
-  auto decode_visbuffer(MainGeometryContext& context) -> void {
+  // prepared_frame.materials_buffer.  Without tables: material factors only, no texture sampling (oxc_decode_visbuffer).  With the image
+  // and sampler tables -- what the engine binds as global_images and global_samplers -- the whole shader: the five material images through
+  // SampleGrad by the stated rule, the normal map, with context.cull_camera.position as Camera::position (oxc_decode_visbuffer_textured).
+  // Rules: include/oxcull.h.
+  auto decode_visbuffer(MainGeometryContext& context, Buffer images = {}, Buffer samplers = {}) -> void {
     oxc_prepared_frame f = {};
     f.mesh_instance_count = prepared_frame.mesh_instance_count;
     f.max_meshlet_instance_count = prepared_frame.max_meshlet_instance_count;
@@ -423,7 +426,18 @@ public:
     d.normal_attachment = context.normal_attachment;
     d.emissive_attachment = context.emissive_attachment;
     d.metallic_roughness_occlusion_attachment = context.metallic_roughness_occlusion_attachment;
-    check(oxc_decode_visbuffer(ctx_, &f, &d, stream_));
+    if (!images.dptr && !samplers.dptr) {
+      check(oxc_decode_visbuffer(ctx_, &f, &d, stream_));
+      return;
+    }
+    oxc_material_images m = {};
+    m.struct_size = sizeof m;
+    for (int i = 0; i < 3; i++) m.camera_position[i] = context.cull_camera.position[i];
+    m.image_count = static_cast<uint32_t>(images.bytes / sizeof(oxc_material_image));
+    m.sampler_count = static_cast<uint32_t>(samplers.bytes / sizeof(oxc_material_sampler));
+    m.images_buffer = images;
+    m.samplers_buffer = samplers;
+    check(oxc_decode_visbuffer_textured(ctx_, &f, &d, &m, stream_));
   }
 
   // Oxylus/src/Render/Passes/Terrain.cpp:159-216 (the reference's TerrainContext carries the Terrain object; here its GPU-side fields)

@@ -40,6 +40,12 @@ int main(int argc, char**) {
   }
   run_geometry_pass(true);
   try { self.decode_visbuffer(main_geometry_context); } catch (const std::exception& e) { std::printf("expected (no attachments bound): %s\n", e.what()); }  // RendererInstance.cpp:924
+  try {  // the same pass with the image and sampler tables: oxc_decode_visbuffer_textured
+    oxc_material_sampler linear_repeated = {OXC_FILTER_LINEAR, OXC_ADDRESS_REPEAT, OXC_FILTER_LINEAR, 0};
+    self.decode_visbuffer(main_geometry_context, Buffer{}, Buffer{&linear_repeated, sizeof linear_repeated});
+  } catch (const std::exception& e) {
+    std::printf("expected (no attachments bound): %s\n", e.what());
+  }
   try {  // RendererInstance.cpp:974-985: the shadow term, after draw_virtual_shadowmap
     self.resolve_shadowmap(ShadowResolveContext{});
   } catch (const std::exception& e) {

@@ -40,6 +40,7 @@ TUNE_BOUNDS_GRID = 20
 TUNE_BOUNDS_CHUNK = 21
 TUNE_TERRAIN_DRAW_GRID = 22
 TUNE_TERRAIN_DRAW_STATS = 23
+TUNE_VISBUFFER_DECODE_TEXTURED_STATS = 24
 
 # GPU::SceneFlags bits oxc_apply_pbr reads (scene.slang:242-256)
 SCENE_HAS_DIRECTIONAL_LIGHT, SCENE_HAS_ATMOSPHERE, SCENE_HAS_CONTACT_SHADOWS, SCENE_HAS_SKY, SCENE_TRANSPARENT_BACKGROUND = 1 << 0, 1 << 1, 1 << 9, 1 << 10, 1 << 11
@@ -50,6 +51,13 @@ SCENE_HAS_FILM_GRAIN, SCENE_HAS_CHROMATIC_ABERRATION, SCENE_HAS_VIGNETTE = 1 << 
 SCENE_HAS_FXAA = 1 << 4  # SceneGPU.hpp:259; oxc_apply_fxaa does not read it: RendererInstance.apply_fxaa decides by it which image the later passes read
 TONEMAP_NONE, TONEMAP_ACES, TONEMAP_AGX, TONEMAP_GT7 = 0, 1, 2, 3  # GPU::TonemapType, oxc_tonemap_context.tonemap_type
 TONEMAP_OUT_R8G8B8A8_SRGB, TONEMAP_OUT_B8G8R8A8_SRGB, TONEMAP_OUT_R8G8B8A8_UNORM = 0, 1, 2  # oxc_tonemap_context.output_format
+# oxc_material_image.format; oxc_material_sampler.filter / .mip_filter and .address (oxc_decode_visbuffer_textured)
+IMAGE_R8G8B8A8_UNORM, IMAGE_R8G8B8A8_SRGB, IMAGE_R8G8_UNORM = 0, 1, 2
+FILTER_NEAREST, FILTER_LINEAR = 0, 1
+ADDRESS_REPEAT, ADDRESS_CLAMP_TO_EDGE = 0, 1
+# GPU::MaterialFlag (scene.slang:34-49): the bits oxc_decode_visbuffer_textured reads
+(MATERIAL_HAS_ALBEDO_IMAGE, MATERIAL_HAS_NORMAL_IMAGE, MATERIAL_HAS_EMISSIVE_IMAGE, MATERIAL_HAS_METALLIC_ROUGHNESS_IMAGE, MATERIAL_HAS_OCCLUSION_IMAGE,
+ MATERIAL_NORMAL_TWO_COMPONENT, MATERIAL_NORMAL_FLIP_Y) = (1 << k for k in range(7))
 LIGHT_KIND_DIRECTIONAL, LIGHT_KIND_POINT, LIGHT_KIND_SPOT = 0, 1, 2  # GPU::LightKind
 TERRAIN_GENERATE, TERRAIN_DERIVE, TERRAIN_MINMAX, TERRAIN_ALL = 1, 2, 4, 7  # oxc_terrain_maps_context.stages
 TERRAIN_BRUSH_TRACE, TERRAIN_BRUSH_APPLY, TERRAIN_BRUSH_ALL = 1, 2, 3  # oxc_terrain_brush_context.stages
@@ -421,6 +429,40 @@ class DecodeContext(C.Structure):
         ("normal_attachment", Buffer),
         ("emissive_attachment", Buffer),
         ("metallic_roughness_occlusion_attachment", Buffer),
+    ]
+
+
+class MaterialImage(C.Structure):
+    _c_name_ = "oxc_material_image"
+    _fields_ = [
+        ("dptr", C.c_uint64),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("levels", C.c_uint32),
+        ("format", C.c_uint32),
+        ("level_offset", C.c_uint64 * 15),
+    ]
+
+
+class MaterialSampler(C.Structure):
+    _c_name_ = "oxc_material_sampler"
+    _fields_ = [
+        ("filter", C.c_uint32),
+        ("address", C.c_uint32),
+        ("mip_filter", C.c_uint32),
+        ("_pad", C.c_uint32),
+    ]
+
+
+class MaterialImages(C.Structure):
+    _c_name_ = "oxc_material_images"
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("camera_position", C.c_float * 3),
+        ("image_count", C.c_uint32),
+        ("sampler_count", C.c_uint32),
+        ("images_buffer", Buffer),
+        ("samplers_buffer", Buffer),
     ]
 
 
@@ -991,6 +1033,8 @@ PROTOTYPES = {
     "oxc_draw_visbuffer": (_status, [_vp, _P(PreparedFrame), _P(DrawContext), _vp]),
     "oxc_decode_visbuffer": (_status, [_vp, _P(PreparedFrame), _P(DecodeContext), _vp]),
     "oxc_debug_visbuffer_decode_stats": _stats,
+    "oxc_decode_visbuffer_textured": (_status, [_vp, _P(PreparedFrame), _P(DecodeContext), _P(MaterialImages), _vp]),
+    "oxc_debug_visbuffer_decode_textured_stats": _stats,
     "oxc_apply_pbr": (_status, [_vp, _P(PbrContext), _vp]),
     "oxc_debug_pbr_apply_stats": _stats,
     "oxc_apply_eye_adaptation": (_status, [_vp, _P(EyeAdaptationContext), _vp]),

@@ -1226,6 +1226,61 @@ class VisbufferDecodeContext(Marshalled):
                                       torch.zeros((d.height, d.width, 4), dtype=torch.int16, device=dev), z32(), z32(), bool(clear))
 
 
+# the five SamplingMode presets of Renderer.cpp:64-70 as oxc_material_sampler records {filter, address, mip_filter}; anisotropy is not sampled
+SAMPLER_PRESETS = {"LinearRepeated": (1, 0, 1), "LinearClamped": (1, 1, 1), "NearestRepeated": (0, 0, 0), "NearestClamped": (0, 1, 0),
+                   "LinearRepeatedAnisotropy": (1, 0, 1)}
+_TEXEL_BYTES = {L.IMAGE_R8G8B8A8_UNORM: 4, L.IMAGE_R8G8B8A8_SRGB: 4, L.IMAGE_R8G8_UNORM: 2}
+
+
+def pack_material_images(images, device="cuda") -> tuple:
+    """`images`: [(levels, format)] with `levels` a list of uint8 arrays [h_k, w_k, 4] (or [h_k, w_k, 2] for IMAGE_R8G8_UNORM), level k of
+    max(1, w >> k) x max(1, h >> k) texels -> (records uint8 [n * 144] on `device`, the texel tensors the records point into).  Each image
+    is one allocation, its levels one behind the other, each 4-byte aligned.  Keep the second value alive while the records are used."""
+    import numpy as np
+
+    records, keep = (L.MaterialImage * max(1, len(images)))(), []
+    for i, (levels, fmt) in enumerate(images):
+        per = _TEXEL_BYTES[int(fmt)]
+        h0, w0 = levels[0].shape[:2]
+        blob, offsets = bytearray(), []
+        for k, lvl in enumerate(levels):
+            a = np.ascontiguousarray(lvl, dtype=np.uint8)
+            assert a.shape == (max(1, h0 >> k), max(1, w0 >> k), per), (i, k, a.shape)
+            offsets.append(len(blob))
+            blob += a.tobytes() + bytes(-a.size % 4)
+        t = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(device)
+        keep.append(t)
+        rec = records[i]
+        rec.dptr, rec.width, rec.height, rec.levels, rec.format = t.data_ptr(), w0, h0, len(levels), int(fmt)
+        rec.level_offset[:len(offsets)] = offsets
+    raw = torch.frombuffer(bytearray(bytes(records)), dtype=torch.uint8)  # at least one record long: an empty table is an empty slice of it
+    return raw[:144 * len(images)].to(device), keep
+
+
+def pack_material_samplers(samplers, device="cuda") -> torch.Tensor:
+    """[(filter, address, mip_filter)] or names of SAMPLER_PRESETS -> int32 [n, 4] oxc_material_sampler records on `device`."""
+    rows = [list(SAMPLER_PRESETS[s] if isinstance(s, str) else s) + [0] for s in samplers]
+    return torch.tensor(rows, dtype=torch.int32).reshape(-1, 4).to(device)
+
+
+@dataclass
+class MaterialImagesContext(Marshalled):
+    """oxc_material_images: the image and sampler tables oxc_decode_visbuffer_textured samples through (the engine's global_images and
+    global_samplers) and the camera position its tangent frame reads.  `images_buffer` holds oxc_material_image records
+    (pack_material_images), `samplers_buffer` oxc_material_sampler records (pack_material_samplers); either may be None with its count 0."""
+    _ctype = L.MaterialImages
+    camera_position: tuple
+    images_buffer: Optional[torch.Tensor] = None    # uint8 [image_count * 144]
+    samplers_buffer: Optional[torch.Tensor] = None  # int32 [sampler_count, 4]
+    image_count: int = 0
+    sampler_count: int = 0
+
+    @staticmethod
+    def create(camera_position, images_buffer=None, samplers_buffer=None) -> "MaterialImagesContext":
+        n = lambda t, size: 0 if t is None else t.numel() * t.element_size() // size  # noqa: E731
+        return MaterialImagesContext(tuple(float(v) for v in camera_position), images_buffer, samplers_buffer, n(images_buffer, 144), n(samplers_buffer, 16))
+
+
 @dataclass
 class MainGeometryContext(Marshalled):
     """The fields generate_hiz uses (RendererInstance.hpp:199-216)."""
@@ -1240,6 +1295,10 @@ _STATS = {
     "raster": ("oxc_debug_raster_stats", ("big", "clipped", "tiles", "overflowed_segments")),
     "terrain_draw": ("oxc_debug_terrain_draw_stats", ("patches_drawn", "patches_discarded", "patches_skipped", "triangles", "set_up", "clipped", "big", "fragments")),
     "visbuffer_decode": ("oxc_debug_visbuffer_decode_stats", ("decoded", "empty", "zero_vertex_index", "default_material")),
+    "visbuffer_decode_textured": ("oxc_debug_visbuffer_decode_textured_stats", ("decoded", "empty", "zero_vertex_index", "default_material", "sampled_albedo",
+                                                                                "sampled_normal", "sampled_emissive", "sampled_metallic_roughness",
+                                                                                "sampled_occlusion", "level_taps", "jacobian_zero", "uniform_waves",
+                                                                                "per_lane_waves")),
     "vsm_draw": ("oxc_debug_vsm_draw_stats", ("pairs", "fragments", "big_pairs", "big_pairs_overflowed", "tiles", "tiles_overflowed", "clipped_pairs",
                                               "clipped_pairs_overflowed")),
     "vsm_resolve": ("oxc_debug_vsm_resolve_stats", ("non_sky_pixels", "taps", "misses", "fallback_minus", "fallback_plus", "hard", "no_blocker",
@@ -1459,6 +1518,20 @@ class RendererInstance:
         barycentrics, the interpolated vertex normal and the material factors, into the four G-buffer images of `context`
         (include/oxcull.h, oxc_decode_visbuffer)."""
         self._call("oxc_decode_visbuffer", context, stream, frame=True)
+
+    def decode_visbuffer_textured(self, context: VisbufferDecodeContext, images: "MaterialImagesContext", stream=None):
+        """The whole of visbuffer_decode.slang: decode_visbuffer with the five material images sampled through `images` -- texcoords,
+        gradients, the tangent frame, SampleGrad by the stated rule, the normal map (include/oxcull.h, oxc_decode_visbuffer_textured).  One
+        launch; with no image flag set the outputs are decode_visbuffer's."""
+        assert self.prepared_frame is not None
+        self._keep = (context, images)
+        self._check(self._lib.oxc_decode_visbuffer_textured(self._ctx, C.byref(self.prepared_frame.c()), C.byref(context.c()), C.byref(images.c()),
+                                                            self._stream(stream)))
+
+    def debug_visbuffer_decode_textured_stats(self, stream=None) -> dict:
+        """What the last decode_visbuffer_textured did, after debug_set_tuning(L.TUNE_VISBUFFER_DECODE_TEXTURED_STATS, 1) (measurement hook;
+        synchronises)."""
+        return self._read_stats("visbuffer_decode_textured", stream)
 
     def debug_visbuffer_decode_stats(self, stream=None) -> dict:
         """What the last decode_visbuffer did, after debug_set_tuning(L.TUNE_VISBUFFER_DECODE_STATS, 1) (measurement hook; synchronises)."""

@@ -80,6 +80,7 @@ class Scene:
     # what visbuffer_decode reads beyond the cull path (both optional; sub-scenes made by prefix / slice / take do not carry them)
     normals: Optional[torch.Tensor] = None    # int32 [.., ]  10:10:10 vertex normals, one per entry of `positions`
     materials: Optional[torch.Tensor] = None  # uint8 [n * 56]  GPU::Material records (pack_materials)
+    texcoords: Optional[torch.Tensor] = None  # int16 [.., 2]  u16x2 half texcoords, one per entry of `positions` (the textured decode reads them)
 
     @property
     def n_mesh_instances(self) -> int:
@@ -118,7 +119,7 @@ class Scene:
         meshes = self.meshes
         meshes[:, 0] = base_pos + t["mesh_vertex_start"].to(dev) * 8
         meshes[:, 1] = 0 if self.normals is None else self.normals.data_ptr() + t["mesh_vertex_start"].to(dev) * 4
-        meshes[:, 2] = 0
+        meshes[:, 2] = 0 if self.texcoords is None else self.texcoords.data_ptr() + t["mesh_vertex_start"].to(dev) * 4
         L = self.spec.lod_count
         meshes[:, 4] = lods.data_ptr() + torch.arange(self.n_meshes, dtype=torch.int64, device=dev) * (64 * L)
         return self
@@ -129,7 +130,7 @@ class Scene:
         for name in ("bounds", "meshlets", "micro", "vidx", "positions", "lods", "meshes", "transforms",
                      "mesh_instances", "meshlet_instances"):
             kw[name] = getattr(self, name).to(device).contiguous().clone()
-        for name in ("normals", "materials"):
+        for name in ("normals", "materials", "texcoords"):
             if getattr(self, name) is not None:
                 kw[name] = getattr(self, name).to(device).contiguous().clone()
         s = Scene(spec=self.spec, device=device, camera=self.camera, n_meshes=self.n_meshes,
@@ -693,10 +694,12 @@ def make_scene_from_mesh(n_mesh_instances: int, bounds: torch.Tensor, meshlets: 
     return s.bind()
 
 
-def pack_materials(albedo, emissive=None, roughness=None, metallic=None, alpha_cutoff=None, flags=None) -> torch.Tensor:
-    """-> uint8 [n * 56]: GPU::Material records (SceneGPU.hpp:67-82).  albedo [n, 4], emissive [n, 3], roughness / metallic / alpha_cutoff [n]
-    are rounded to binary16; an integer array (any of them) is taken as the half bit patterns themselves.  The image indices, the sampler
-    index, uv_size and uv_offset stay zero: oxc_decode_visbuffer reads none of them."""
+def pack_materials(albedo, emissive=None, roughness=None, metallic=None, alpha_cutoff=None, flags=None, sampler_index=None, image_indices=None,
+                   uv_size=None, uv_offset=None) -> torch.Tensor:
+    """-> uint8 [n * 56]: GPU::Material records (SceneGPU.hpp:67-82).  albedo [n, 4], emissive [n, 3], roughness / metallic / alpha_cutoff [n],
+    uv_size / uv_offset [n, 2] are rounded to binary16; an integer array (any of them) is taken as the half bit patterns themselves.
+    sampler_index [n] and image_indices [n, 5] (albedo, normal, emissive, metallic-roughness, occlusion) are u32.  What is not given stays
+    zero; oxc_decode_visbuffer reads none of the last four, oxc_decode_visbuffer_textured all of them."""
     import numpy as np
 
     def halves(v, shape):
@@ -717,6 +720,12 @@ def pack_materials(albedo, emissive=None, roughness=None, metallic=None, alpha_c
     rec[:, 9] = halves(alpha_cutoff, (n,))
     if flags is not None:
         rec.view(np.uint32)[:, 5] = np.asarray(flags, dtype=np.uint32)
+    if sampler_index is not None:
+        rec.view(np.uint32)[:, 6] = np.asarray(sampler_index, dtype=np.uint32)
+    if image_indices is not None:
+        rec.view(np.uint32)[:, 7:12] = np.asarray(image_indices, dtype=np.uint32).reshape(n, 5)
+    rec[:, 24:26] = halves(uv_size, (n, 2))
+    rec[:, 26:28] = halves(uv_offset, (n, 2))
     return torch.from_numpy(rec.view(np.uint8).reshape(-1).copy())
 
 
