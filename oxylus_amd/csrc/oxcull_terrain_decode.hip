@@ -15,7 +15,7 @@
 // dequantize_half_flush; the kernel must not call set_half_denorm_flush().
 #include <hip/hip_runtime.h>
 
-#include "oxcull_kernels.hpp"
+#include "oxcull_decode_device.hpp"
 #include "oxcull_terrain_device.hpp"
 
 namespace oxc {
@@ -122,9 +122,9 @@ __global__ __launch_bounds__(256) void k_terrain_decode(TerrainDecodeArgs a) {
   // D6, D8
   const V3 shading = normalize3(geometric);
   a.normal[pix] = make_uint2(oct_halves(shading), oct_halves(geometric));
-  a.albedo[pix] = srgb_unorm(albedo[0]) | (srgb_unorm(albedo[1]) << 8) | (srgb_unorm(albedo[2]) << 16) | (pack_unorm(albedo[3]) << 24);
-  a.emissive[pix] = pack_ufloat<6>(emissive[0]) | (pack_ufloat<6>(emissive[1]) << 11) | (pack_ufloat<5>(emissive[2]) << 22);
-  a.mro[pix] = pack_unorm(metallic) | (pack_unorm(roughness) << 8) | (pack_unorm(occlusion) << 16);
+  a.albedo[pix] = pack_albedo(albedo[0], albedo[1], albedo[2], albedo[3]);
+  a.emissive[pix] = pack_emissive(emissive[0], emissive[1], emissive[2]);
+  a.mro[pix] = pack_mro(metallic, roughness, occlusion);
 }
 
 void launch_terrain_decode(const TerrainDecodeArgs& a, hipStream_t s) {

@@ -4,7 +4,8 @@
 // measurements: DESIGN.md section 31.
 //
 //   k_visbuffer_decode_textured   the shape of k_visbuffer_decode: one thread per pixel, an 8 x 8 pixel tile per wave, a 16 x 16 tile per
-//                        block.  Steps 1 - 5 are that kernel's lines, float operation for float operation.  Then:
+//                        block.  Steps 1 - 5 are oxcull_decode_device.hpp's, the one copy both kernels run, with what the sampling
+//                        reads switched on (DecodedPixel<true>).  Then:
 //                        - the block fills two 256-entry LDS tables, byte / 255.0f and srgb_decode(byte), one entry per thread, when the call
 //                          has an image table at all: a texel channel is one LDS read, not a division or three binary64 pow;
 //                        - a wave whose live lanes all name one material reads that material, its sampler and its image records through a
@@ -21,19 +22,13 @@
 // k_visbuffer_decode.
 #include <hip/hip_runtime.h>
 
-#include "oxcull_kernels.hpp"
-#include "oxcull_pixel_device.hpp"
+#include "oxcull_decode_device.hpp"
 
 namespace oxc {
 
 namespace {
-// Mesh::decode_normal, scene.slang:486-489
-OXC_DEV V3 decode_normal(uint32_t packed) {
-  return {(float)((packed >> 20) & 1023u) / 511.0f - 1.0f, (float)((packed >> 10) & 1023u) / 511.0f - 1.0f, (float)(packed & 1023u) / 511.0f - 1.0f};
-}
-
-// the counters of oxc_debug_visbuffer_decode_textured_stats
-enum : int { kDecoded = 0, kEmpty, kZeroVertexIndex, kDefaultMaterial, kSampled /* + image kind, 5 */, kLevelTaps = 9, kJacobianZero, kUniformWaves, kPerLaneWaves };
+// the counters of oxc_debug_visbuffer_decode_textured_stats after the four both decodes keep
+enum : int { kSampled = kDecodeCounters /* + image kind, 5 */, kLevelTaps = 9, kJacobianZero, kUniformWaves, kPerLaneWaves };
 enum : uint32_t { kHasAlbedo = 1u, kHasNormal = 2u, kHasEmissive = 4u, kHasMetallicRoughness = 8u, kHasOcclusion = 16u, kNormalTwoComponent = 32u, kNormalFlipY = 64u };
 
 template <bool STATS>
@@ -48,12 +43,10 @@ struct F2 {
   float x, y;
 };
 
-// What shade() needs of one pixel after steps 1 - 5 and 9 - 10
-struct Pixel {
+// One pixel after steps 1 - 5 and 9 (the shared part: crw, wnrm and what step 10 reads) and step 10
+struct Pixel : DecodedPixel<true> {
   F2 uv, ddx, ddy;      // tex_coord_grad before the material's uv_size / uv_offset
   float bx[3], by[3];   // the final ddx / ddy of compute_partial_derivatives
-  V3 crw[3];            // camera-relative world positions
-  V3 wnrm;              // world_normal
 };
 
 // One axis of a level tap (step 12): linear filter -> the repeat axis of oxc_apply_tonemap or axis_at<false>; nearest -> the texel at
@@ -226,11 +219,10 @@ OXC_DEV void shade(const VisbufferDecodeTexturedArgs& a, const float* tab, size_
   }
 
   // step 14: albedo
-  const float ar = dequantize_half_flush(mw[0] & 0xFFFFu), ag = dequantize_half_flush(mw[0] >> 16), ab = dequantize_half_flush(mw[1] & 0xFFFFu),
-              aa = dequantize_half_flush(mw[1] >> 16);
-  F4 albedo = {ar, ag, ab, aa};
-  if (has[0]) albedo = {ar * texel[0].r, ag * texel[0].g, ab * texel[0].b, aa * texel[0].a};
-  a.g.albedo[pix] = srgb_unorm(albedo.r) | (srgb_unorm(albedo.g) << 8) | (srgb_unorm(albedo.b) << 16) | (pack_unorm(albedo.a) << 24);
+  const MaterialFactors f = material_factors(mw);
+  F4 albedo = {f.ar, f.ag, f.ab, f.aa};
+  if (has[0]) albedo = {f.ar * texel[0].r, f.ag * texel[0].g, f.ab * texel[0].b, f.aa * texel[0].a};
+  a.g.albedo[pix] = pack_albedo(albedo.r, albedo.g, albedo.b, albedo.a);
 
   // step 11 and the normal: the tangent frame is computed where a normal image is sampled
   const uint32_t geometric = oct_halves(p.wnrm);
@@ -266,13 +258,13 @@ OXC_DEV void shade(const VisbufferDecodeTexturedArgs& a, const float* tab, size_
   a.g.normal[pix] = make_uint2(shading, geometric);
 
   // emissive, metallic / roughness, occlusion
-  float er = dequantize_half_flush(mw[2] & 0xFFFFu), eg = dequantize_half_flush(mw[2] >> 16), eb = dequantize_half_flush(mw[3] & 0xFFFFu);
+  float er = f.er, eg = f.eg, eb = f.eb;
   if (has[2]) er = er * texel[2].r, eg = eg * texel[2].g, eb = eb * texel[2].b;
-  a.g.emissive[pix] = pack_ufloat<6>(er) | (pack_ufloat<6>(eg) << 11) | (pack_ufloat<5>(eb) << 22);
-  float roughness = dequantize_half_flush(mw[3] >> 16), metallic = dequantize_half_flush(mw[4] & 0xFFFFu);
+  a.g.emissive[pix] = pack_emissive(er, eg, eb);
+  float roughness = f.roughness, metallic = f.metallic;
   if (has[3]) metallic = metallic * texel[3].b, roughness = roughness * texel[3].g;
   const float occlusion = has[4] ? texel[4].r : 1.0f;
-  a.g.mro[pix] = pack_unorm(metallic) | (pack_unorm(roughness) << 8) | (pack_unorm(occlusion) << 16);
+  a.g.mro[pix] = pack_mro(metallic, roughness, occlusion);
   count<STATS>(a, kDecoded);
 }
 }  // namespace
@@ -291,124 +283,40 @@ __global__ __launch_bounds__(256) void k_visbuffer_decode_textured(VisbufferDeco
   const uint32_t px = tp.x, py = tp.y;
   if (px >= g.w || py >= g.h) return;
   const size_t pix = (size_t)py * g.w + px;
-  const uint32_t texel = g.vis[pix];
-  const uint32_t depth_bits = g.depth_bits[pix];
-  const uint32_t instance = texel >> 8, triangle = texel & 0xFFu;
 
-  // 1. empty pixel
-  if (texel == ~0u || instance == kTerrainInstanceId || depth_bits == 0u || instance >= g.meshlet_instance_count) {
-    if (g.clear) {
-      g.albedo[pix] = 0u;
-      g.normal[pix] = make_uint2(0u, 0u);
-      g.emissive[pix] = 0u;
-      g.mro[pix] = 0u;
-    }
-    count<STATS>(a, kEmpty);
-    return;
-  }
-
-  // 2. fetch chain (visbuffer_decode.slang:95-103) and Meshlet::indices
-  const GpuMeshletInstance mli = g.meshlet_instances[instance];
-  const GpuMeshInstance* mi = g.mesh_instances + mli.mesh_instance_index;
-  const uint32_t mesh_index = mi->mesh_index, lod_index = mi->lod_index, material_index = mi->material_index, transform_index = mi->transform_index;
-  const GpuMesh* mesh = g.meshes + mesh_index;
-  const uint64_t positions = mesh->vertex_positions, normals = mesh->vertex_normals, texcoords = mesh->texture_coords, lods = mesh->lods;
-  const uint32_t vertex_count = mesh->vertex_count;
-  const uint64_t lod = lods + (uint64_t)lod_index * sizeof(GpuMeshLOD);
-  const uint2 meshlets2 = load_global_u2(lod, 1), micro2 = load_global_u2(lod, 3), vidx2 = load_global_u2(lod, 4);  // GpuMeshLOD's pointers
-  const uint64_t meshlets = meshlets2.x | ((uint64_t)meshlets2.y << 32), micro = micro2.x | ((uint64_t)micro2.y << 32),
-                 vidx = vidx2.x | ((uint64_t)vidx2.y << 32);
-  const uint4 meshlet = load_global_u4(meshlets, mli.meshlet_index);  // {vertex offset, triangle offset, vertex count, triangle count}
-  const uint32_t base = meshlet.y + triangle * 3u;
-  uint32_t vi[3];
-#pragma unroll
-  for (uint32_t k = 0; k < 3; k++) {
-    const uint32_t byte = base + k;
-    const uint32_t local = (load_global_u32(micro, byte >> 2) >> ((byte & 3u) * 8u)) & 0xFFu;
-    vi[k] = load_global_u32(vidx, meshlet.x + local);
-  }
-  const uint32_t last = vertex_count - 1u;  // wraps for vertex_count == 0, as in the Slang
-  if (vi[0] > last || vi[1] > last || vi[2] > last) {
-    g.albedo[pix] = 0u;
-    g.normal[pix] = make_uint2(0u, 0u);
-    g.emissive[pix] = 0u;
-    g.mro[pix] = 0u;
-    count<STATS>(a, kZeroVertexIndex);
-    return;
-  }
-
-  float world[16];
-  {
-    const float4* t = reinterpret_cast<const float4*>(g.transforms) + (size_t)transform_index * 4u;
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-      const float4 col = t[c];
-      world[c * 4 + 0] = col.x, world[c * 4 + 1] = col.y, world[c * 4 + 2] = col.z, world[c * 4 + 3] = col.w;
-    }
-  }
-
-  // 3. positions and normals, 4. the three clip positions; 9. the texcoords (a null stream decodes (0, 0))
+  // 1. empty pixel, 2. fetch chain
   Pixel p;
-  float nm[9];
-  normal_matrix(world, nm);
-  float cx[3], cy[3], inv_w[3], tu[3], tv[3];
-  V3 wn[3];
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    const uint2 q = load_global_u2(positions, vi[k]);
-    const float lx = dequantize_half_flush(q.x & 0xFFFFu), ly = dequantize_half_flush(q.x >> 16), lz = dequantize_half_flush(q.y & 0xFFFFu);
-    const float wx = row1(world, 0, lx, ly, lz), wy = row1(world, 1, lx, ly, lz), wz = row1(world, 2, lx, ly, lz);
-    cx[k] = row1(g.pv, 0, wx, wy, wz);
-    cy[k] = row1(g.pv, 1, wx, wy, wz);
-    inv_w[k] = 1.0f / row1(g.pv, 3, wx, wy, wz);
-    const V3 n = normals ? decode_normal(load_global_u32(normals, vi[k])) : V3{0.0f, 0.0f, 0.0f};
-    wn[k] = {(nm[0] * n.x + nm[3] * n.y) + nm[6] * n.z, (nm[1] * n.x + nm[4] * n.y) + nm[7] * n.z, (nm[2] * n.x + nm[5] * n.y) + nm[8] * n.z};
-    p.crw[k] = {wx - a.camera_position[0], wy - a.camera_position[1], wz - a.camera_position[2]};
-    const uint32_t tc = texcoords ? load_global_u32(texcoords, vi[k]) : 0u;
-    tu[k] = dequantize_half_flush(tc & 0xFFFFu), tv[k] = dequantize_half_flush(tc >> 16);
+  const int outcome = decode_fetch(g, pix, p);
+  if (outcome != kDecoded) {
+    count<STATS>(a, outcome);
+    return;
   }
-
-  // 4. barycentrics (visbuffer_decode.slang:45-73)
-  const float n0x = cx[0] * inv_w[0], n0y = cy[0] * inv_w[0];
-  const float n1x = cx[1] * inv_w[1], n1y = cy[1] * inv_w[1];
-  const float n2x = cx[2] * inv_w[2], n2y = cy[2] * inv_w[2];
-  const float inv_det = 1.0f / ((n2x - n1x) * (n0y - n1y) - (n2y - n1y) * (n0x - n1x));
-  const float ddx0 = ((n1y - n2y) * inv_det) * inv_w[0], ddx1 = ((n2y - n0y) * inv_det) * inv_w[1], ddx2 = ((n0y - n1y) * inv_det) * inv_w[2];
-  const float ddy0 = ((n2x - n1x) * inv_det) * inv_w[0], ddy1 = ((n0x - n2x) * inv_det) * inv_w[1], ddy2 = ((n1x - n0x) * inv_det) * inv_w[2];
-  const float ddx_sum = (ddx0 + ddx1) + ddx2, ddy_sum = (ddy0 + ddy1) + ddy2;
-  const float u = (((float)px + 0.5f) / g.fw) * 2.0f - 1.0f, v = (((float)py + 0.5f) / g.fh) * 2.0f - 1.0f;
-  const float dvx = u - n0x, dvy = v - n0y;
-  const float interp_inv_w = (inv_w[0] + dvx * ddx_sum) + dvy * ddy_sum;
-  const float interp_w = 1.0f / interp_inv_w;
-  const float l0 = interp_w * ((inv_w[0] + dvx * ddx0) + dvy * ddy0);
-  const float l1 = interp_w * (dvx * ddx1 + dvy * ddy1);
-  const float l2 = interp_w * (dvx * ddx2 + dvy * ddy2);
-
-  // 5. normal
-  p.wnrm = normalize3({(l0 * wn[0].x + l1 * wn[1].x) + l2 * wn[2].x, (l0 * wn[0].y + l1 * wn[1].y) + l2 * wn[2].y,
-                       (l0 * wn[0].z + l1 * wn[1].z) + l2 * wn[2].z});
+  // 3. positions and normals, 4. clip positions and barycentrics, 5. normal; 9. the texcoords
+  decode_interpolate(g, a.camera_position, px, py, p);
 
   // 10. the gradients (visbuffer_decode.slang:74-83) and gradient_of (:32-39)
   {
+    const Barycentrics& b = p.bary;
+    const float l0 = b.l[0], l1 = b.l[1], l2 = b.l[2], *tu = p.tu, *tv = p.tv;
     const float sx = 2.0f / g.fw, sy = -(2.0f / g.fh);
-    const float rx0 = ddx0 * sx, rx1 = ddx1 * sx, rx2 = ddx2 * sx, ry0 = ddy0 * sy, ry1 = ddy1 * sy, ry2 = ddy2 * sy;
-    const float rx_sum = ddx_sum * sx, ry_sum = ddy_sum * sy;
-    const float interp_ddx_w = 1.0f / (interp_inv_w + rx_sum), interp_ddy_w = 1.0f / (interp_inv_w + ry_sum);
-    p.bx[0] = interp_ddx_w * (l0 * interp_inv_w + rx0) - l0, p.bx[1] = interp_ddx_w * (l1 * interp_inv_w + rx1) - l1, p.bx[2] = interp_ddx_w * (l2 * interp_inv_w + rx2) - l2;
-    p.by[0] = interp_ddy_w * (l0 * interp_inv_w + ry0) - l0, p.by[1] = interp_ddy_w * (l1 * interp_inv_w + ry1) - l1, p.by[2] = interp_ddy_w * (l2 * interp_inv_w + ry2) - l2;
+    const float rx0 = b.ddx[0] * sx, rx1 = b.ddx[1] * sx, rx2 = b.ddx[2] * sx, ry0 = b.ddy[0] * sy, ry1 = b.ddy[1] * sy, ry2 = b.ddy[2] * sy;
+    const float rx_sum = b.ddx_sum * sx, ry_sum = b.ddy_sum * sy;
+    const float interp_ddx_w = 1.0f / (b.interp_inv_w + rx_sum), interp_ddy_w = 1.0f / (b.interp_inv_w + ry_sum);
+    p.bx[0] = interp_ddx_w * (l0 * b.interp_inv_w + rx0) - l0, p.bx[1] = interp_ddx_w * (l1 * b.interp_inv_w + rx1) - l1, p.bx[2] = interp_ddx_w * (l2 * b.interp_inv_w + rx2) - l2;
+    p.by[0] = interp_ddy_w * (l0 * b.interp_inv_w + ry0) - l0, p.by[1] = interp_ddy_w * (l1 * b.interp_inv_w + ry1) - l1, p.by[2] = interp_ddy_w * (l2 * b.interp_inv_w + ry2) - l2;
     p.uv = {(l0 * tu[0] + l1 * tu[1]) + l2 * tu[2], (l0 * tv[0] + l1 * tv[1]) + l2 * tv[2]};
     p.ddx = {(p.bx[0] * tu[0] + p.bx[1] * tu[1]) + p.bx[2] * tu[2], (p.bx[0] * tv[0] + p.bx[1] * tv[1]) + p.bx[2] * tv[2]};
     p.ddy = {(p.by[0] * tu[0] + p.by[1] * tu[1]) + p.by[2] * tu[2], (p.by[0] * tv[0] + p.by[1] * tv[1]) + p.by[2] * tv[2]};
   }
 
   // the wave's live lanes all name one material: the uniform path
-  const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)material_index);
-  const bool uniform = __ballot(material_index != first) == 0ull;
+  const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.material_index);
+  const bool uniform = __ballot(p.material_index != first) == 0ull;
   if (STATS && lane_id() == __builtin_ctzll(__ballot(1))) count<STATS>(a, uniform ? kUniformWaves : kPerLaneWaves);  // the first live lane
   if (uniform)
     shade<true, STATS>(a, tab, pix, first, p);
   else
-    shade<false, STATS>(a, tab, pix, material_index, p);
+    shade<false, STATS>(a, tab, pix, p.material_index, p);
 }
 
 void launch_visbuffer_decode_textured(const VisbufferDecodeTexturedArgs& a, hipStream_t s) {
