@@ -257,7 +257,11 @@ const char* oxc_last_error(const oxc_ctx* ctx);
 oxc_status oxc_reserve(oxc_ctx* ctx, uint32_t max_mesh_instances, uint32_t max_meshlet_instances);
 
 /* ---- the two reference entry points ---- */
-/* Replaces RendererInstance::generate_hiz (Passes/CullGeometry.cpp:10-59, passes/hiz.slang). */
+/* Replaces RendererInstance::generate_hiz (Passes/CullGeometry.cpp:10-59, passes/hiz.slang).
+ * Limits (else OXC_INVALID_ARG, nothing launched): the pyramid at most 4096 a side with 1..13 levels, every level offset a multiple of 4
+ * bytes; either both sides multiples of 64 (then mip 0 16-byte and mip 1 8-byte aligned: they are stored as vectors) or at most 4096 texels.
+ * Zeros: the reduction is min with -0.0 < +0.0 (the device's v_min_f32), whatever the order of the operands -- the reference's `min` leaves
+ * the sign of a zero result open, this library and its checker pin that one.  A NaN operand is dropped (fminf). */
 oxc_status oxc_generate_hiz(oxc_ctx* ctx, const oxc_main_geometry_context* context, void* hip_stream);
 
 /* Replaces RendererInstance::cull_geometry (Passes/CullGeometry.cpp:61-404; kernels

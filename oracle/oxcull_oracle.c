@@ -349,6 +349,12 @@ int orc_test_triangle_backface(const float* cp) { return backface_m(cp, NULL); }
 /* ------------------------------------------------------------------------------------------
  * HiZ -- passes/hiz.slang:42-267, host Passes/CullGeometry.cpp:10-59
  * ---------------------------------------------------------------------------------------- */
+/* include/oxcull.h, oxc_generate_hiz: min with -0.0 < +0.0 whatever the operand order (fminf may return either zero) */
+static inline float hiz_min(float a, float b) {
+  if (a == 0.0f && b == 0.0f) return signbit(a) ? a : b;
+  return fminf(a, b);
+}
+
 void orc_generate_hiz(const float* depth, uint32_t dw, uint32_t dh, orc_hiz* hiz) {
   float* out = (float*)hiz->data;
   uint32_t W = hiz->width, H = hiz->height;
@@ -383,7 +389,7 @@ void orc_generate_hiz(const float* depth, uint32_t dw, uint32_t dh, orc_hiz* hiz
         uint32_t x1 = x0 + 1 < pw ? x0 + 1 : pw - 1, y1 = y0 + 1 < ph ? y0 + 1 : ph - 1;
         float a = src[(size_t)y0 * pw + x0], b = src[(size_t)y0 * pw + x1];
         float c = src[(size_t)y1 * pw + x0], d = src[(size_t)y1 * pw + x1];
-        dst[(size_t)y * cw + x] = min2(min2(a, b), min2(c, d));
+        dst[(size_t)y * cw + x] = hiz_min(hiz_min(a, b), hiz_min(c, d));
       }
   }
 }

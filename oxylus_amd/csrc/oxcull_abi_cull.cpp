@@ -865,6 +865,7 @@ oxc_status oxc_generate_hiz(oxc_ctx* ctx, const oxc_main_geometry_context* c, vo
   const bool tiled = (a.w % 64 == 0) && (a.h % 64 == 0);
   if (!tiled && (uint64_t)a.w * a.h > 4096) return fail(ctx, OXC_INVALID_ARG, "generate_hiz: extent must be a multiple of 64 or <= 4096 texels");
   if (tiled && (h.level_offset[0] & 15u)) return fail(ctx, OXC_INVALID_ARG, "generate_hiz: mip 0 must be 16-byte aligned");
+  if (tiled && a.levels > 1 && (h.level_offset[1] & 7u)) return fail(ctx, OXC_INVALID_ARG, "generate_hiz: mip 1 must be 8-byte aligned");  // (k_hiz_tile stores it as float2)
   OXC_ENTER(ctx, hip_stream, s);
   {
     KernelTimer t(ctx, OXC_K_HIZ, s);

@@ -236,6 +236,142 @@ def test_hiz_general_depth_ratio():
         assert m[y, x].item() == float(sy * 1920 + sx)
 
 
+# ---- B.5 / B.6 off the square: cull.slang:86-135 and hiz.slang on pyramids whose sides differ ------------------------------------------
+def _pyramid(w, h, level_values):
+    """A pyramid whose texels are given per level (row-major lists)."""
+    levels, offs, total = hiz_layout(w, h, len(level_values))
+    data = np.full(total // 4, -1.0, dtype=np.float32)
+    for k, vals in enumerate(level_values):
+        mw, mh = max(1, w >> k), max(1, h >> k)
+        assert len(vals) == mw * mh
+        data[offs[k] // 4: offs[k] // 4 + mw * mh] = vals
+    return data, oracle.make_hiz(data, w, h, levels, offs), offs
+
+
+def _decisive_texels(box, data, hz, offs, w, h, levels):
+    """(level, y, x) of every texel whose lowering to 0 makes `box` (placed just behind the minimum it sees) visible: the taps."""
+    assert oracle.test_occlusion(box, hz)
+    out = set()
+    for k in range(levels):
+        mw, mh = max(1, w >> k), max(1, h >> k)
+        for i in range(mw * mh):
+            keep = data[offs[k] // 4 + i]
+            data[offs[k] // 4 + i] = 0.0
+            if not oracle.test_occlusion(box, hz):
+                out.add((k, i // mw, i % mw))
+            data[offs[k] // 4 + i] = keep
+    return out
+
+
+def _box(w, h, x0, y0, x1, y1, z=0.0):
+    return [np.float32(x0) / np.float32(w), np.float32(y0) / np.float32(h), 0.0, np.float32(x1) / np.float32(w), np.float32(y1) / np.float32(h), z]
+
+
+def _expect(box, data, hz, offs, w, h, levels, mip, taps, d):
+    """`box` picks `mip`, reads exactly the texels `taps` = {(y, x)} of it, and is occluded up to z = d - 1e-7 (reversed-Z)."""
+    assert oracle.occlusion_mip(box, hz) == mip
+    d = np.float32(d)
+    box[5] = float(d - np.float32(2.5e-7))
+    assert _decisive_texels(box, data, hz, offs, w, h, levels) == {(mip, y, x) for y, x in taps}
+    box[5] = float(d)
+    assert not oracle.test_occlusion(box, hz)  # d - 1e-7 < d at these magnitudes: the box at the texel's own depth is visible
+
+
+# 8 x 4: levels 8x4, 4x2, 2x1, 1x1.  Texel i (row-major) of level k holds (100 (k + 1) + i) / 1000: all distinct, so the minimum names its tap.
+_L84 = [[(100 + i) / 1000 for i in range(32)], [(200 + i) / 1000 for i in range(8)], [0.300, 0.301], [0.400]]
+
+
+def test_occlusion_8x4_one_box_per_level():
+    data, hz, offs = _pyramid(8, 4, _L84)
+    args = (data, hz, offs, 8, 4, 4)
+    # A: x 2.2 .. 3.8, y 1.2 .. 1.8 -> texels x 2 .. 3, y 1 .. 1: size max(1, 0) = 1 -> mip 0.  uv = (2.5 / 8, 1 / 4); base = floor((2.5, 1) - 0.5) =
+    # (2, 0): taps x {2, 3}, y {0, 1} = texels 2, 3, 10, 11 -> d = 0.102
+    _expect(_box(8, 4, 2.2, 1.2, 3.8, 1.8), *args, mip=0, taps={(0, 2), (0, 3), (1, 2), (1, 3)}, d=0.102)
+    # B: x 1.2 .. 3.8 (1 .. 3), y 0.2 .. 1.9 (0 .. 1): size 2 -> mip 1 (4 x 2).  uv = (2 / 8, 0.5 / 4); base = floor((1, 0.25) - 0.5) = (0, -1): the upper
+    # row clamps onto row 0 -> taps (0, 0), (0, 1) -> d = 0.200
+    _expect(_box(8, 4, 1.2, 0.2, 3.8, 1.9), *args, mip=1, taps={(0, 0), (0, 1)}, d=0.200)
+    # C: x 1.5 .. 5.5 (1 .. 5), y 1.1 .. 3.9 (1 .. min(3.9, 3) = 3): size 4 -> mip 2 (2 x 1).  uv = (3 / 8, 2 / 4); base = floor((0.75, 0.5) - 0.5) = (0, 0):
+    # the lower-right tap (1, 1) clamps in y (one row) and not in x -> taps (0, 0), (0, 1) -> d = 0.300
+    _expect(_box(8, 4, 1.5, 1.1, 5.5, 3.9), *args, mip=2, taps={(0, 0), (0, 1)}, d=0.300)
+    # D: x 0.5 .. 7.5 (0 .. 7): size 7 -> ceil(log2 7) = 3, the top: one texel -> d = 0.400
+    _expect(_box(8, 4, 0.5, 1.2, 7.5, 1.8), *args, mip=3, taps={(0, 0)}, d=0.400)
+    # E: wholly right of the image: min texel 9 > max texel min(10, 7) = 7 -> 7 - 9 wraps to 2^32 - 2 -> log2 = 32, clamped to the top
+    _expect(_box(8, 4, 9.0, 1.2, 10.0, 1.8), *args, mip=3, taps={(0, 0)}, d=0.400)
+
+
+def test_occlusion_8x4_short_chain_clamps_the_mip():
+    # the same pyramid with two levels: D's raw mip 3 clamps to 1 (4 x 2).  uv = (3.5 / 8, 1 / 4); base = floor((1.75, 0.5) - 0.5) = (1, 0):
+    # taps x {1, 2}, y {0, 1} = texels 1, 2, 5, 6 of level 1 -> d = 0.201
+    data, hz, offs = _pyramid(8, 4, _L84[:2])
+    _expect(_box(8, 4, 0.5, 1.2, 7.5, 1.8), data, hz, offs, 8, 4, 2, mip=1, taps={(0, 1), (0, 2), (1, 1), (1, 2)}, d=0.201)
+
+
+def _division_case(w, levels_values, must_move):
+    """cull.slang:129 divides the box centre by the extent.  For a width that is no power of two, 1 / w is inexact and for some centre uc the
+    product uc * (1 / w) is not the quotient uc / w; where it lands one ulp below k + 0.5 the tap column moves one to the left."""
+    f = np.float32
+    diff = [uc for uc in (f(0.5) + f(k) for k in range(w - 1)) if uc / f(w) != uc * (f(1) / f(w))]
+    assert diff, f"no centre of a one-texel-wide box distinguishes the quotient from the product at width {w}"
+    moved = [uc for uc in diff if np.floor(uc * (f(1) / f(w)) * f(w) - f(0.5)) != np.floor(uc / f(w) * f(w) - f(0.5))]
+    assert bool(moved) == must_move
+    data, hz, offs = _pyramid(w, 3, levels_values)
+    for uc in (moved or diff)[:4]:
+        x = int(uc - f(0.5))  # the box covers texels x .. x + 1, y 1 .. 1: mip 0, centre (x + 0.5, 1)
+        # by hand: u = (x + 0.5) / w, u * w - 0.5 = x -> columns x, x + 1; v = 1 / 3, v * 3 - 0.5 = 0.5 -> rows 0, 1; the minimum is texel (0, x)
+        assert np.floor(uc / f(w) * f(w) - f(0.5)) == x
+        _expect(_box(w, 3, x + 0.2, 1.2, x + 1.8, 1.8), data, hz, offs, w, 3, len(levels_values), mip=0, taps={(0, x), (0, x + 1), (1, x), (1, x + 1)},
+                d=(100 + x) / 1000)
+    return moved
+
+
+def test_occlusion_6x3_divides_by_the_extent():
+    _division_case(6, [[(100 + i) / 1000 for i in range(18)], [0.200, 0.201, 0.202], [0.300]], must_move=False)  # (at width 6 no product moves a column)
+
+
+def test_occlusion_100x3_product_would_move_the_tap_column():
+    # width 100: for uc = 2.5 (texels 2 .. 3) the product gives u * 100 - 0.5 just below 2 -> columns 1, 2, and the minimum would be texel (0, 1)
+    moved = _division_case(100, [[(100 + i) / 1000 for i in range(300)]], must_move=True)
+    assert np.float32(2.5) in moved
+
+
+_D53 = [[7, 3, 9, 1, 8],
+        [4, 6, 2, 10, 0.25],
+        [12, 0.5, 11, 14, 13]]
+
+
+def _generate(w, h):
+    levels, offs, total = hiz_layout(w, h)
+    data = torch.full((total // 4,), -1.0)
+    oracle.generate_hiz(torch.tensor(_D53, dtype=torch.float32), data, w, h, levels, offs)
+    return [data[offs[k] // 4: offs[k] // 4 + max(1, w >> k) * max(1, h >> k)].tolist() for k in range(levels)]
+
+
+def test_generate_hiz_5x3_into_4x2():
+    # hiz.slang:92-95: level 0 texel (x, y) = depth texel (floor((x + 1) / 4 * 5), floor((y + 1) / 2 * 3)) clamped = columns 1, 2, 3, 5 -> 4; rows 1, 3 -> 2
+    # level 1 (2 x 1) = 2 x 2 minima; level 2 (1 x 1) from a 2 x 1 level: the second row clamps onto the first
+    assert _generate(4, 2) == [[6, 2, 10, 0.25, 0.5, 11, 14, 13], [0.5, 0.25], [0.25]]
+
+
+def test_generate_hiz_5x3_into_3x2():
+    # columns floor((x + 1) * (1/3) * 5): x * inv + inv = 0.33333334, 0.6666667, 1.0 (2 * inv + inv rounds to 1) -> 1, 3, 5 -> 4; rows 1, 2.
+    # level 1 (1 x 1) from the odd 3 x 2 level: columns 0 and 1 only -- column 2, which holds the smallest value, is not read
+    assert _generate(3, 2) == [[6, 10, 0.25, 0.5, 14, 13], [0.5]]
+
+
+def test_generate_hiz_zero_signs():
+    # include/oxcull.h, oxc_generate_hiz: -0.0 < +0.0 in either operand order.  A 4 x 4 depth into 2 x 2: level 0 is the depth's texels
+    # (min(2x + 2, 3), min(2y + 2, 3)) = its lower-right 2 x 2 block, level 1 the minimum of that block
+    NZ, PZ, NINE = -2**31, 0, 0x41100000
+    for quad in ([PZ, NZ, NINE, NINE], [NZ, PZ, NINE, NINE], [NINE, PZ, NINE, NZ], [NZ, NINE, PZ, PZ], [NINE, NINE, PZ, NZ], [NINE, NINE, NZ, PZ]):
+        depth = torch.full((4, 4), 5.0)
+        depth[2:4, 2:4] = torch.tensor(quad, dtype=torch.int32).view(torch.float32).view(2, 2)
+        levels, offs, total = hiz_layout(2, 2)
+        data = torch.full((total // 4,), -1.0)
+        oracle.generate_hiz(depth, data, 2, 2, levels, offs)
+        assert data[:4].view(torch.int32).tolist() == quad
+        assert data[offs[1] // 4: offs[1] // 4 + 1].view(torch.int32).item() == NZ, quad
+
+
 # ---- B.8 cull_triangles: cull_triangles.slang:27-90, visbuffer.slang:13-14 ---------------------
 def test_triangle_backface_determinant():
     # determinant(float3x3(c0.xyw, c1.xyw, c2.xyw)) >= 1e-4 => backface
