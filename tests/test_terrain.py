@@ -6,41 +6,8 @@ import pytest
 import torch
 
 from oxylus_amd import lib as L
-from oxylus_amd.lib import CullCamera
-from oxylus_amd.synth import make_depth, perspective_reversed_z
-
-
-def _camera(eye=(0.0, 40.0, 0.0), near=0.1, far=2000.0):
-    """Camera at `eye` looking down -Z (view = translate(-eye)); reversed-Z projection as everywhere else."""
-    proj = perspective_reversed_z(60.0, 1.0, near, far).view(4, 4)  # [col][row]
-    view = torch.eye(4)
-    view[3, 0:3] = -torch.tensor(eye)  # column 3 = translation
-    pv = (proj.t() @ view.t()).t().contiguous()  # column-major product proj * view
-    cam = CullCamera()
-    for i, v in enumerate(pv.flatten().tolist()):
-        cam.projection_view[i] = v
-    for i in range(3):
-        cam.position[i] = eye[i]
-    cam.near_clip = near
-    cam.resolution[0] = cam.resolution[1] = 1024.0
-    cam.acceptable_lod_error = 2.0
-    return cam
-
-
-def _terrain(pcx, pcy, seed):
-    g = torch.Generator().manual_seed(seed)
-    lo = torch.rand((pcy, pcx), generator=g) * 0.6
-    hi = lo + torch.rand((pcy, pcx), generator=g) * 0.4
-    flat = torch.rand((pcy, pcx), generator=g) < 0.1
-    hi = torch.where(flat, lo, hi)  # flat patches: extent.y falls back to 1e-3
-    return torch.stack([lo, hi], -1).contiguous()
-
-
-def _mask(total, seed, p):
-    g = torch.Generator().manual_seed(seed)
-    words = (total + 31) // 32
-    bits = (torch.rand((words, 32), generator=g) < p).to(torch.int64)
-    return (bits << torch.arange(32)).sum(1).to(torch.int32)
+from oxylus_amd.synth import make_depth
+from terrain_cull_frames import _camera, _mask, _terrain  # noqa: F401  (other test modules take them from here)
 
 
 def test_oracle_frustum_only_keeps_the_patches_in_front(oracle_lib):
