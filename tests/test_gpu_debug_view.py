@@ -3,7 +3,6 @@ poisoned guard bands (debug_view_frames.run / run_vsm), on the drawn 192 x 192 f
 captured graph, and at every limit."""
 import ctypes as C
 import dataclasses
-import types
 
 import numpy as np
 import pytest
@@ -11,6 +10,7 @@ import torch
 
 import debug_view_frames as DF
 import debug_view_model as DV
+import refusals as R
 from gpu_passes import DrawnFrame, Guard, same
 
 pytestmark = pytest.mark.gpu
@@ -314,82 +314,6 @@ def test_draw_decode_ao_debug_view_in_one_graph(r, drawn):
 
 
 # ---- limits ---------------------------------------------------------------------------------------------------------------------------------
-def _frame_with(frame, **fields):
-    """`frame` with some of the three record buffers replaced: meshlet_instances_buffer is its own, the other two are the scene's."""
-    scene = types.SimpleNamespace(**vars(frame.scene))
-    own = {k: fields.pop(k) for k in list(fields) if k == "meshlet_instances_buffer"}
-    for k, v in fields.items():
-        setattr(scene, k, v)
-    return rep(frame, scene=scene, **own)
-
-
-def _attempt(r, base, frame, changes):
-    """One call of the C entry point with `changes` applied to the context `base` and the prepared frame `frame`: a plain key replaces a
-    field of the context, "frame" the whole prepared frame, "frame:<name>" one of its record buffers, "raw:<name>" a field of the filled C
-    structure (what the dataclass derives and cannot be told: struct_size, width, height).  Returns (status, oxc_last_error)."""
-    c = rep(base, **{k: v for k, v in changes.items() if ":" not in k and k != "frame"}).c()
-    for k, v in changes.items():
-        if k.startswith("raw:"):
-            setattr(c, k[4:], v)
-    frame = changes.get("frame", frame)
-    records = {k[6:]: v for k, v in changes.items() if k.startswith("frame:")}
-    if frame is not None and records:
-        frame = _frame_with(frame, **records)
-    fc = frame.c() if frame is not None else None
-    status = r._lib.oxc_apply_debug_view(r._ctx, C.byref(fc) if fc is not None else None, C.byref(c), r._stream(None))
-    return status, r._lib.oxc_last_error(r._ctx).decode()
-
-
-def _refused(r, base, changes, message, label, frame=None):
-    """OXC_INVALID_ARG with `message` right behind the entry point's name: the message of that rule and of no other."""
-    from oxylus_amd import lib as L
-
-    status, error = _attempt(r, base, frame, changes)
-    assert status == L.OXC_INVALID_ARG and f"apply_debug_view: {message}" in error, f"{label}: status {status}, {error!r}, expected {message!r}"
-
-
-def _alone_and_in_pairs(r, cases, base, frame, unwritten):
-    """Every case alone, then every two cases that change different things: the message is that of the case earlier in the documented
-    order.  `unwritten(label)` asserts that the output holds its pre-fill and every band its poison; what a call wrote would stay, so it
-    is asked after every single case and after each case's pairs."""
-    for name, change, message in cases:
-        _refused(r, base, change, message, name, frame)
-        torch.cuda.synchronize()
-        unwritten(name)
-    for i, (name, first, message) in enumerate(cases):
-        for other, second, _ in cases[i + 1:]:
-            if not set(first) & set(second):
-                _refused(r, base, {**first, **second}, message, f"{name} + {other}", frame)
-        torch.cuda.synchronize()
-        unwritten(f"{name} and a later one")
-
-
-def _null_image(W, H):
-    """A one-level image descriptor of W x H with no memory behind it."""
-    from oxylus_amd import lib as L
-
-    im = L.Image()
-    im.width, im.height, im.levels = W, H, 1
-    return types.SimpleNamespace(width=W, height=H, c=lambda: im)
-
-
-def _later(x, unit):
-    """The tensor's bytes from `unit`'s size onwards: a start that is aligned to `unit` and to nothing larger."""
-    return x.view(-1).view(unit)[1:]
-
-
-def _buffer_cases(field, tensor, texel, smaller=None, name=None):
-    """Null, then unaligned (half a texel later), then one element short: the three rules of one buffer, in the header's order.  `name` is
-    what the messages call the buffer where that is not the key."""
-    name = name or field
-    unit = {2: torch.int8, 4: torch.int16, 8: torch.int32}[texel]
-    cases = [(f"{name} null", {field: None}, f"{name} must not be null"),
-             (f"{name} unaligned", {field: _later(tensor, unit)}, f"{name} must be aligned to its texel")]
-    if smaller:
-        cases.append((f"{name} small", {field: tensor.view(-1)[:-1]}, name + smaller))
-    return cases
-
-
 def _shared_first_cases(W, H, depth):
     """The rules in front of the buffers, as every view has them: struct_size, debug_view, the extent, the depth image."""
     from oxylus_amd import lib as L
@@ -402,7 +326,7 @@ def _shared_first_cases(W, H, depth):
             ("width differs", {"raw:width": W + 1}, "depth_attachment extent differs"), ("height differs", {"raw:height": H - 1 or 2}, "depth_attachment extent differs"),
             ("65537 wide", dict(depth_attachment=ImageAttachment(depth.view(-1), 65537, H, 1, [0])), "depth extent beyond 65536"),
             ("65537 tall", dict(depth_attachment=ImageAttachment(depth.view(-1), W, 65537, 1, [0])), "depth extent beyond 65536"),
-            ("depth null", dict(depth_attachment=_null_image(W, H)), one_level),
+            ("depth null", dict(depth_attachment=R.null_image(W, H)), one_level),
             ("two levels", dict(depth_attachment=ImageAttachment(depth.view(-1), W, H, 2, [0, 0])), one_level),
             ("level offset", dict(depth_attachment=ImageAttachment(depth.view(-1), W, H, 1, [4])), one_level)]
 
@@ -414,31 +338,30 @@ def _limit_cases(f, gs, view):
 
     W, H = f.extent
     t = lambda name: gs[name].tensor  # noqa: E731
-    small = " is smaller than its extent"
     debug = t("debug")
     words = debug.view(-1).view(torch.int32)   # the output's bytes as 2 * W * H words
     over = lambda what: f"debug_attachment must not overlap {what}"  # noqa: E731
     cases = _shared_first_cases(W, H, t("depth"))
     if view in DV.RECORD_VIEWS:
         cases.append(("frame null", {"frame": None}, "the frame must not be null"))
-    cases += _buffer_cases("visbuffer_attachment", t("vis"), 4, small)
-    cases.append(("depth unaligned", dict(depth_attachment=ImageAttachment(_later(t("depth"), torch.int16), W, H, 1, [0])), "depth_attachment must be aligned to its texel"))
+    cases += R.buffer_cases("visbuffer_attachment", t("vis"), torch.int16)
+    cases.append(("depth unaligned", dict(depth_attachment=ImageAttachment(R.later(t("depth"), torch.int16), W, H, 1, [0])), "depth_attachment must be aligned to its texel"))
     overlaps = [("over the visbuffer", dict(visbuffer_attachment=words[:W * H]), over("visbuffer_attachment")),
                 ("over the depth", dict(depth_attachment=ImageAttachment(words[-W * H:].view(torch.float32), W, H, 1, [0])), over("depth_attachment"))]
     if view in DF.READS:
         name = DF.READS[view]
         field = {"mr_occlusion": "metallic_roughness_occlusion_attachment", "ao": "ambient_occlusion_attachment"}.get(name, name + "_attachment")
-        texel = {"ao": 2, "normal": 8}.get(name, 4)
-        cases += _buffer_cases(field, t(name), texel, small)
+        half_texel = {"ao": torch.int8, "normal": torch.int32}.get(name, torch.int16)
+        cases += R.buffer_cases(field, t(name), half_texel)
         overlaps.append((f"over {field}", {field: debug.view(-1).view(t(name).dtype)[-t(name).numel():]}, over(field)))
     if view in DV.RECORD_VIEWS:
-        cases += _buffer_cases("frame:meshlet_instances_buffer", t("meshlet_instances"), 4, " is smaller than meshlet_instance_count records", "meshlet_instances_buffer")
-        cases += _buffer_cases("frame:mesh_instances", t("mesh_instances"), 4, name="mesh_instances_buffer")
-        cases += _buffer_cases("frame:meshes", t("meshes"), 8, name="meshes_buffer")
+        cases += R.buffer_cases("frame:meshlet_instances_buffer", t("meshlet_instances"), torch.int16, " is smaller than meshlet_instance_count records", "meshlet_instances_buffer")
+        cases += R.buffer_cases("frame:mesh_instances", t("mesh_instances"), torch.int16, None, "mesh_instances_buffer")
+        cases += R.buffer_cases("frame:meshes", t("meshes"), torch.int32, None, "meshes_buffer")
         overlaps += [("over the meshlet instances", {"frame:meshlet_instances_buffer": words[:2 * f.meshlet_instance_count].view(-1, 2)}, over("meshlet_instances_buffer")),
                      ("over the mesh instances", {"frame:mesh_instances": words[-f.mesh_instances.size:]}, over("mesh_instances_buffer")),
                      ("over the meshes", {"frame:meshes": words[:f.meshes.size]}, over("meshes_buffer"))]
-    cases += _buffer_cases("debug_attachment", debug, 8, small)
+    cases += R.buffer_cases("debug_attachment", debug, torch.int32)
     return cases + overlaps
 
 
@@ -448,7 +371,7 @@ def test_limits_alone_and_in_pairs(r, view):
     gs = DF.guards(f, view)
     frame = DF.prepared_frame(gs, f) if view in DV.RECORD_VIEWS else None
     base = DF.context(f, gs, view)
-    _alone_and_in_pairs(r, _limit_cases(f, gs, view), base, frame, lambda label: DF.check_unwritten(gs, f, label))
+    R.alone_and_in_pairs(r, "oxc_apply_debug_view", _limit_cases(f, gs, view), base, frame, lambda label: DF.check_unwritten(gs, f, label))
     r.prepared_frame = frame
     # and the frame accepted after all: the same context runs
     r.apply_debug_view(base)
@@ -471,10 +394,10 @@ def test_rmvsm_limits(r):
               ("table of 12", dict(page_table_size=12), "page_table_size must be a multiple of 8 in [8, 256]"), ("page of 24", dict(page_size=24), pages),
               ("physical 72", dict(physical_page_table_size=72), pages),
               ("257 x 257 pages", dict(physical_page_table_size=257 * f.shape["page_size"]), "more than 65536 physical pages"),
-              ("depth unaligned", dict(depth_attachment=ImageAttachment(_later(t("depth"), torch.int16), W, H, 1, [0])), "depth_attachment must be aligned to its texel")]
-    cases += _buffer_cases("vsm_clipmaps_buffer", t("clipmaps"), 4, " is smaller than clipmap_count records")
-    cases += _buffer_cases("virtual_page_table", t("table"), 4, " is smaller than clipmap_count * n * n u32")
-    cases += _buffer_cases("debug_attachment", t("debug"), 8, " is smaller than its extent")
+              ("depth unaligned", dict(depth_attachment=ImageAttachment(R.later(t("depth"), torch.int16), W, H, 1, [0])), "depth_attachment must be aligned to its texel")]
+    cases += R.buffer_cases("vsm_clipmaps_buffer", t("clipmaps"), torch.int16, " is smaller than clipmap_count records")
+    cases += R.buffer_cases("virtual_page_table", t("table"), torch.int16, " is smaller than clipmap_count * n * n u32")
+    cases += R.buffer_cases("debug_attachment", t("debug"), torch.int32)
     over = lambda what: f"debug_attachment must not overlap {what}"  # noqa: E731
     cases += [("over the depth", dict(depth_attachment=ImageAttachment(words[-W * H:].view(torch.float32), W, H, 1, [0])), over("depth_attachment")),
               ("over the clipmaps", dict(vsm_clipmaps_buffer=words[:t("clipmaps").numel()]), over("vsm_clipmaps_buffer")),
@@ -485,7 +408,7 @@ def test_rmvsm_limits(r):
             g.check(label)
         assert (gs["debug"].bits()[1] == DF.FILL16).all(), f"{label}: written after a refusal"
 
-    _alone_and_in_pairs(r, cases, base, None, unwritten)
+    R.alone_and_in_pairs(r, "oxc_apply_debug_view", cases, base, None, unwritten)
     r.prepared_frame = None
     # the inputs of the main views are not looked at: null and fine
     r.apply_debug_view(base)

@@ -3,7 +3,6 @@ image, every word of the composite and the pick's word equal to the checker's be
 on the drawn 192 x 192 frame, at the word and tile boundaries, on hand-made frames, in a captured graph, and at every limit."""
 import ctypes as C
 import dataclasses
-import types
 
 import numpy as np
 import pytest
@@ -11,6 +10,7 @@ import torch
 
 import highlight_frames as HF
 import highlight_model as HM
+import refusals as R
 from gpu_passes import ALL_FLAGS, DrawnFrame, Guard, lights_tensor, same
 
 pytestmark = pytest.mark.gpu
@@ -308,71 +308,6 @@ def test_draw_pick_mask_tonemap_composite_in_one_graph(r, drawn):
 
 
 # ---- limits ---------------------------------------------------------------------------------------------------------------------------------
-def _later(x, unit):
-    """The tensor's bytes from `unit`'s size onwards: a start aligned to `unit` and to nothing larger."""
-    return x.view(-1).view(unit)[1:]
-
-
-def _with_records(frame, **fields):
-    scene = types.SimpleNamespace(**vars(frame.scene))
-    own = {k: fields.pop(k) for k in list(fields) if k == "meshlet_instances_buffer"}
-    for k, v in fields.items():
-        setattr(scene, k, v)
-    return rep(frame, scene=scene, **own)
-
-
-def _attempt(r, symbol, base, frame, changes):
-    """One call of the C entry point with `changes` applied: a plain key replaces a field of the context, "frame" the prepared frame,
-    "frame:<name>" one of its record buffers, "raw:<name>" a field of the filled C structure.  Returns (status, oxc_last_error)."""
-    c = rep(base, **{k: v for k, v in changes.items() if ":" not in k and k != "frame"}).c()
-    for k, v in changes.items():
-        if k.startswith("raw:"):
-            setattr(c, k[4:], v)
-    frame = changes.get("frame", frame)
-    records = {k[6:]: v for k, v in changes.items() if k.startswith("frame:")}
-    if frame is not None and records:
-        frame = _with_records(frame, **records)
-    fc = frame.c() if frame is not None else None
-    status = getattr(r._lib, symbol)(r._ctx, C.byref(fc) if fc is not None else None, C.byref(c), r._stream(None))
-    return status, r._lib.oxc_last_error(r._ctx).decode()
-
-
-def _alone_and_in_pairs(r, symbol, cases, base, frame, unwritten):
-    """Every case alone, then every two cases that change different things: the message is that of the case earlier in the documented
-    order.  `unwritten(label)` asserts that the outputs hold their pre-fill and every band its poison."""
-    from oxylus_amd import lib as L
-
-    def refused(changes, message, label):
-        status, error = _attempt(r, symbol, base, frame, changes)
-        assert status == L.OXC_INVALID_ARG and f"{symbol[4:]}: {message}" in error, f"{label}: status {status}, {error!r}, expected {message!r}"
-
-    for i, (name, first, message) in enumerate(cases):
-        refused(first, message, name)
-        for other, second, _ in cases[i + 1:]:
-            if not set(first) & set(second):
-                refused({**first, **second}, message, f"{name} + {other}")
-        torch.cuda.synchronize()
-        unwritten(name)
-
-
-def _buffer_cases(field, tensor, unit, smaller=" is smaller than its extent", name=None, aligned=" must be aligned to its texel"):
-    name = name or field
-    cases = [(f"{name} null", {field: None}, f"{name} must not be null")]
-    if unit is not None:
-        cases.append((f"{name} unaligned", {field: _later(tensor, unit)}, name + aligned))
-    if smaller:
-        cases.append((f"{name} small", {field: tensor.view(-1)[:-1]}, name + smaller))
-    return cases
-
-
-def _null_image(W, H):
-    from oxylus_amd import lib as L
-
-    im = L.Image()
-    im.width, im.height, im.levels = W, H, 1
-    return types.SimpleNamespace(width=W, height=H, c=lambda: im)
-
-
 def _unwritten(gs, f, outputs):
     def check(label):
         for g in gs.values():
@@ -412,22 +347,22 @@ def test_highlight_limits_alone_and_in_pairs(r, stages):
                   ("level offset", dict(depth_attachment=ImageAttachment(depth.view(-1), W, H, 1, [4])), one_level)]
     if has_mask:
         cases.append(("frame null", {"frame": None}, "the frame must not be null"))
-        cases += _buffer_cases("visbuffer_attachment", t("vis"), torch.int16)
+        cases += R.buffer_cases("visbuffer_attachment", t("vis"), torch.int16)
         # a null list with selected_count 0 is accepted, so the count is kept beside it
         cases += [("transform_indices null", {"transform_indices": None, "raw:selected_count": len(f.selected)}, "transform_indices must not be null"),
-                  ("transform_indices unaligned", {"transform_indices": _later(t("selected"), torch.int16)}, "transform_indices must be aligned to its texel")]
+                  ("transform_indices unaligned", {"transform_indices": R.later(t("selected"), torch.int16)}, "transform_indices must be aligned to its texel")]
         cases.append(("transform_indices small", {"raw:selected_count": len(f.selected) + 1}, "transform_indices is smaller than selected_count u32"))
-    cases += _buffer_cases("mask_bits", t("mask_bits"), torch.int32)
+    cases += R.buffer_cases("mask_bits", t("mask_bits"), torch.int32)
     if has_mask:
         cases.append(("mask_attachment small", dict(mask_attachment=base.mask_attachment[:-1]), "mask_attachment is smaller than its extent"))
     if has_composite:
-        cases += [("depth null", dict(depth_attachment=_null_image(W, H)), "depth_attachment must not be null"),
-                  ("depth unaligned", dict(depth_attachment=ImageAttachment(_later(t("depth"), torch.int16), W, H, 1, [0])), "depth_attachment must be aligned to its texel")]
-        cases += _buffer_cases("color_attachment", t("color"), torch.int16)
-        cases += _buffer_cases("dst_attachment", t("dst"), torch.int16)
+        cases += [("depth null", dict(depth_attachment=R.null_image(W, H)), "depth_attachment must not be null"),
+                  ("depth unaligned", dict(depth_attachment=ImageAttachment(R.later(t("depth"), torch.int16), W, H, 1, [0])), "depth_attachment must be aligned to its texel")]
+        cases += R.buffer_cases("color_attachment", t("color"), torch.int16)
+        cases += R.buffer_cases("dst_attachment", t("dst"), torch.int16)
     if has_mask:
-        cases += _buffer_cases("frame:meshlet_instances_buffer", t("meshlet_instances"), torch.int16, " is smaller than meshlet_instance_count records", "meshlet_instances_buffer")
-        cases += _buffer_cases("frame:mesh_instances", t("mesh_instances"), torch.int16, None, "mesh_instances_buffer")
+        cases += R.buffer_cases("frame:meshlet_instances_buffer", t("meshlet_instances"), torch.int16, " is smaller than meshlet_instance_count records", "meshlet_instances_buffer")
+        cases += R.buffer_cases("frame:mesh_instances", t("mesh_instances"), torch.int16, None, "mesh_instances_buffer")
         # the visbuffer's window starts at an odd multiple of 4 bytes: one word later it is aligned to 8
         cases += [("mask_bits over the visbuffer", dict(mask_bits=t("vis").view(-1)[1:]), "mask_bits must not overlap visbuffer_attachment")]
     if has_composite:
@@ -435,7 +370,7 @@ def test_highlight_limits_alone_and_in_pairs(r, stages):
         cases += [("dst over the depth", dict(depth_attachment=ImageAttachment(words.view(torch.float32), W, H, 1, [0])), "dst_attachment must not overlap depth_attachment"),
                   ("dst over the colour", dict(color_attachment=words), "dst_attachment must not overlap color_attachment")]
     outputs = (("mask_bits", "mask_image") if has_mask else ()) + (("dst",) if has_composite else ())
-    _alone_and_in_pairs(r, "oxc_apply_highlight", cases, base, frame, _unwritten(gs, f, outputs))
+    R.alone_and_in_pairs(r, "oxc_apply_highlight", cases, base, frame, _unwritten(gs, f, outputs))
     # accepted after all
     r.prepared_frame = frame
     r.apply_highlight(base)
@@ -463,13 +398,13 @@ def test_pick_limits_alone_and_in_pairs(r):
              ("65537 wide", dict(width=65537), "extent beyond 65536"),
              ("x == width", dict(picking_texel=(W, 0)), outside), ("y == height", dict(picking_texel=(0, H)), outside), ("x huge", dict(picking_texel=(0xFFFFFFFF, 0)), outside),
              ("frame null", {"frame": None}, "the frame must not be null")]
-    cases += _buffer_cases("visbuffer_attachment", t("vis"), torch.int16)
-    cases += _buffer_cases("transform_id", t("transform_id"), torch.int16, None)
+    cases += R.buffer_cases("visbuffer_attachment", t("vis"), torch.int16)
+    cases += R.buffer_cases("transform_id", t("transform_id"), torch.int16, None)
     cases.append(("transform_id small", dict(transform_id=t("transform_id").view(torch.int16)[:1]), "transform_id is smaller than its extent"))   # two bytes
-    cases += _buffer_cases("frame:meshlet_instances_buffer", t("meshlet_instances"), torch.int16, " is smaller than meshlet_instance_count records", "meshlet_instances_buffer")
-    cases += _buffer_cases("frame:mesh_instances", t("mesh_instances"), torch.int16, None, "mesh_instances_buffer")
+    cases += R.buffer_cases("frame:meshlet_instances_buffer", t("meshlet_instances"), torch.int16, " is smaller than meshlet_instance_count records", "meshlet_instances_buffer")
+    cases += R.buffer_cases("frame:mesh_instances", t("mesh_instances"), torch.int16, None, "mesh_instances_buffer")
     cases.append(("over the visbuffer", dict(transform_id=t("vis").view(-1)[5:6]), "transform_id must not overlap visbuffer_attachment"))
-    _alone_and_in_pairs(r, "oxc_pick_transform", cases, base, frame, _unwritten(gs, f, ("transform_id",)))
+    R.alone_and_in_pairs(r, "oxc_pick_transform", cases, base, frame, _unwritten(gs, f, ("transform_id",)))
     r.prepared_frame = frame
     r.pick_transform(base)
     torch.cuda.synchronize()

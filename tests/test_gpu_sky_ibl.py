@@ -11,6 +11,7 @@ import torch
 import atmosphere_frames as AF
 import sky_ibl_frames as SF
 import sky_ibl_model as SM
+from refusals import raises_refusal
 
 pytestmark = pytest.mark.gpu
 
@@ -163,11 +164,7 @@ def test_captured_graph(r):
 
 # ---- invalid arguments ---------------------------------------------------------------------------------------------------------------------------
 def _refused(call, message, gs, before):
-    from oxylus_amd import lib as L
-
-    with pytest.raises(L.OxcError, match=message):
-        call()
-    torch.cuda.synchronize()
+    raises_refusal(call, message)
     for g, data in zip(gs, before):
         g.check("refused")
         assert (g.bits()[1] == data.reshape(-1)).all(), f"{g.name} was written"

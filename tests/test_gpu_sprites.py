@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import refusals as R
 import sprites_frames as SF
 import sprites_model as SM
 from gpu_passes import ALL_FLAGS, DrawnFrame, Guard, lights_tensor, same
@@ -299,56 +300,6 @@ def test_pick_sprite_on_hit_empty_and_corner_texels(r):
 
 
 # ---- limits ---------------------------------------------------------------------------------------------------------------------------------
-def _later(x, unit):
-    return x.view(-1).view(unit)[1:]
-
-
-def _attempt(r, symbol, base, frame, changes):
-    c = rep(base, **{k: v for k, v in changes.items() if ":" not in k and k != "frame"}).c()
-    for k, v in changes.items():
-        if k.startswith("raw:"):
-            setattr(c, k[4:], v)
-    frame = changes.get("frame", frame)
-    if frame is not None and "frame:transforms" in changes:
-        import types
-        frame = rep(frame, scene=types.SimpleNamespace(**{**vars(frame.scene), "transforms": changes["frame:transforms"]}))
-    args = [r._ctx] + ([C.byref(frame.c()) if frame is not None else None] if symbol == "oxc_draw_sprites" else []) + [C.byref(c), r._stream(None)]
-    status = getattr(r._lib, symbol)(*args)
-    return status, r._lib.oxc_last_error(r._ctx).decode()
-
-
-def _alone_and_in_pairs(r, symbol, cases, base, frame, unwritten):
-    from oxylus_amd import lib as L
-
-    def refused(changes, message, label):
-        status, error = _attempt(r, symbol, base, frame, changes)
-        assert status == L.OXC_INVALID_ARG and f"{symbol[4:]}: {message}" in error, f"{label}: status {status}, {error!r}, expected {message!r}"
-
-    for i, (name, first, message) in enumerate(cases):
-        refused(first, message, name)
-        for other, second, _ in cases[i + 1:]:
-            if not set(first) & set(second):
-                refused({**first, **second}, message, f"{name} + {other}")
-        torch.cuda.synchronize()
-        unwritten(name)
-
-
-def _buffer_cases(field, tensor, unit, smaller, name=None):
-    name = name or field.split(":")[-1]
-    return [(f"{name} null", {field: None}, f"{name} must not be null"), (f"{name} unaligned", {field: _later(tensor, unit)}, f"{name} must be aligned to its texel"),
-            (f"{name} small", {field: tensor.view(-1)[:-1]}, name + smaller)]
-
-
-def _null_image(W, H):
-    import types
-
-    from oxylus_amd import lib as L
-
-    im = L.Image()
-    im.width, im.height, im.levels = W, H, 1
-    return types.SimpleNamespace(width=W, height=H, c=lambda: im)
-
-
 @pytest.mark.parametrize("fmt", SF.FORMATS, ids=FORMAT_IDS)
 @pytest.mark.parametrize("stages", SF.STAGES, ids=STAGE_IDS)
 def test_sprite_limits_alone_and_in_pairs(r, stages, fmt):
@@ -375,14 +326,14 @@ def test_sprite_limits_alone_and_in_pairs(r, stages, fmt):
               ("depth of another extent", dict(depth_attachment=ImageAttachment.depth(torch.zeros((H, W + 1), device="cuda"))), "depth_attachment extent differs"),
               ("two depth levels", dict(depth_attachment=rep(ImageAttachment.depth(t("depth")), levels=2, level_offset=[0, 0])), "depth_attachment must be one R32F level"),
               ("no frame", {"frame": None}, "the frame must not be null")]
-    cases += _buffer_cases("sprites_buffer", t("sprites"), torch.int16, " is smaller than first_sprite + sprite_count records")
-    cases += _buffer_cases("materials_buffer", t("materials").view(-1), torch.int16, " is smaller than material_count records")
-    cases.append(("depth null", dict(depth_attachment=_null_image(W, H)), "depth_attachment must not be null"))
+    cases += R.buffer_cases("sprites_buffer", t("sprites"), torch.int16, " is smaller than first_sprite + sprite_count records")
+    cases += R.buffer_cases("materials_buffer", t("materials").view(-1), torch.int16, " is smaller than material_count records")
+    cases.append(("depth null", dict(depth_attachment=R.null_image(W, H)), "depth_attachment must not be null"))
     if has_vis:
-        cases += _buffer_cases("visbuffer_2d", t("vis"), torch.int16, " is smaller than its extent")
+        cases += R.buffer_cases("visbuffer_2d", t("vis"), torch.int16)
     if has_color:
-        cases += _buffer_cases("final_attachment", t("color"), torch.int32 if fmt else torch.int16, " is smaller than its extent")
-    cases += _buffer_cases("frame:transforms", t("transforms"), torch.int16, " is smaller than transform_count matrices", "transforms_world_buffer")
+        cases += R.buffer_cases("final_attachment", t("color"), torch.int32 if fmt else torch.int16)
+    cases += R.buffer_cases("frame:transforms", t("transforms"), torch.int16, " is smaller than transform_count matrices", "transforms_world_buffer")
     # every written buffer over every other buffer of the call
     written = (["depth_attachment"] + (["visbuffer_2d"] if has_vis else []) + (["final_attachment"] if has_color else []))
     tensors = {"sprites_buffer": t("sprites"), "materials_buffer": t("materials").view(-1), "depth_attachment": t("depth"), "frame:transforms": t("transforms")}
@@ -408,14 +359,13 @@ def test_sprite_limits_alone_and_in_pairs(r, stages, fmt):
 
     # a case that aliases replaces a field a pair partner might need intact: pairs only among the cases before the overlaps
     first_overlap = next(i for i, c in enumerate(cases) if " on the bytes of " in c[0])
-    _alone_and_in_pairs(r, "oxc_draw_sprites", cases[:first_overlap], base, frame, unwritten)
+    R.alone_and_in_pairs(r, "oxc_draw_sprites", cases[:first_overlap], base, frame, unwritten)
     for name, changes, message in cases[first_overlap:]:
-        status, error = _attempt(r, "oxc_draw_sprites", base, frame, changes)
-        assert status == L.OXC_INVALID_ARG and f"draw_sprites: {message}" in error, f"{name}: status {status}, {error!r}, expected {message!r}"
+        R.refused(r, "oxc_draw_sprites", base, changes, message, name, frame)
     torch.cuda.synchronize()
     unwritten("overlaps")
     # an input the stage does not read is not checked; a null materials_buffer is fine with material_count 0; sprite_count 0 only clears
-    status, error = _attempt(r, "oxc_draw_sprites", base, frame, dict(materials_buffer=None, material_count=0, sprite_count=0, **({} if has_color else dict(source_format=9))))
+    status, error = R.attempt(r, "oxc_draw_sprites", base, dict(materials_buffer=None, material_count=0, sprite_count=0, **({} if has_color else dict(source_format=9))), frame)
     assert status == L.OXC_OK, error
     torch.cuda.synchronize()
     if has_vis:
@@ -436,12 +386,12 @@ def test_pick_sprite_limits(r):
     cases = [("struct_size", {"raw:struct_size": C.sizeof(L.SpritePickContext) - 8}, "bad context / struct_size"),
              ("width 0", dict(width=0), "the extent must not be zero"), ("65537 wide", dict(width=65537), "extent beyond 65536"),
              ("x outside", dict(picking_texel=(W, 5)), "the texel lies outside the image"), ("y outside", dict(picking_texel=(3, H)), "the texel lies outside the image")]
-    cases += _buffer_cases("visbuffer_2d", src.tensor, torch.int16, " is smaller than its extent")
-    cases += [c for c in _buffer_cases("transform_id", out.tensor, torch.int16, " is smaller than its extent") if "small" not in c[0]]
+    cases += R.buffer_cases("visbuffer_2d", src.tensor, torch.int16)
+    cases += R.buffer_cases("transform_id", out.tensor, torch.int16, None)
     cases.append(("the word inside the image", dict(transform_id=src.tensor.view(-1)[4:5]), "transform_id must not overlap visbuffer_2d"))
 
     def unwritten(label):
         src.check(label), out.check(label)
         assert (out.bits()[1] == 0x0BADBAD0).all() and (src.bits()[1] == 7).all(), label
 
-    _alone_and_in_pairs(r, "oxc_pick_sprite", cases, base, None, unwritten)
+    R.alone_and_in_pairs(r, "oxc_pick_sprite", cases, base, R.NO_FRAME, unwritten)

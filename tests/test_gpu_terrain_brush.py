@@ -8,6 +8,7 @@ import torch
 
 import terrain_brush_frames as BF
 import terrain_brush_model as TB
+from refusals import ALIGNED, NULL, SHORT, raises_refusal
 
 pytestmark = pytest.mark.gpu
 RES, PC = (24, 20), (3, 5)
@@ -244,18 +245,11 @@ def refusal(r):
 
 
 def _refused(r, context, message, gs, images):
-    from oxylus_amd import lib as L
-
-    with pytest.raises(L.OxcError, match=message):
-        r.apply_terrain_brush(context)
-    torch.cuda.synchronize()
+    raises_refusal(lambda: r.apply_terrain_brush(context), message)
     got = BF.got_of(gs, images)
     for name, g in gs.items():
         g.check("refused")
         assert (got[name].view(np.uint8) == images[name].view(np.uint8)).all(), f"{name} was written"
-
-
-NULL, ALIGNED, SHORT = " must not be null", " must be aligned to its texel", " is smaller than its extent"
 
 
 def _with(base, **params):

@@ -15,6 +15,7 @@ import torch
 import hiz_frames
 from hiz_frames import LAYOUTS, POISON, SHAPE_BY_ID, SHAPES, cell_depth, inside_mask, oracle_pyramid
 from oxylus_amd import lib as L
+from refusals import raises_refusal
 from terrain_cull_frames import (EDGE_CASES, FLAG_SETS, FRUSTUM, GUARD_WORDS, LATE, MASK_GUARD, OCCLUSION, PASSES, SEAM_GRIDS, VISIBLE_FILL, World, _camera, _mask,
                                  _terrain, assert_call, assert_exercised, checker, collect, edge_case, edge_minmax, enqueue, flag_classes, flag_frame, guarded, mask_words,
                                  random_words, read_cmd, run, shape_frame, shape_report, shape_want, small_pyramid, terrain_context, two_pass_want, visible_allocation)
@@ -94,12 +95,7 @@ def _refused(renderer, flags, world, mm_gpu, hiz=None, tweak=None, message=None,
     """A call that must return OXC_INVALID_ARG and write nothing: the mask, the visible buffer and their guard words keep their bytes."""
     mask = random_words(world.total, 21)
     alloc, vis = guarded(mask), visible_allocation(world.total)
-    with pytest.raises(L.OxcError) as ei:
-        run(renderer, flags, cam or _camera(), world, mm_gpu, alloc, hiz, visible_alloc=vis, tweak=tweak)
-    assert ei.value.status == L.OXC_INVALID_ARG, str(ei.value)
-    if message:
-        assert message in str(ei.value), str(ei.value)
-    torch.cuda.synchronize()
+    raises_refusal(lambda: run(renderer, flags, cam or _camera(), world, mm_gpu, alloc, hiz, visible_alloc=vis, tweak=tweak), message or "")
     assert torch.equal(alloc.cpu(), guarded(mask, "cpu")) and bool((vis == VISIBLE_FILL).all())
 
 

@@ -8,6 +8,7 @@ import torch
 
 import terrain_decode_frames as DF
 import terrain_decode_model as TD
+from refusals import ALIGNED, NULL, SHORT, Raw, raises_refusal
 
 pytestmark = pytest.mark.gpu
 rep = dataclasses.replace
@@ -275,7 +276,6 @@ def test_the_frame_chain_in_one_graph_then_eagerly(r):
 
 
 # ---- invalid arguments ---------------------------------------------------------------------------------------------------------------------------
-NULL, ALIGNED, SHORT = " must not be null", " must be aligned to its texel", " is smaller than its extent"
 BUFFERS = ("visbuffer_attachment", "normalmap", "splatmap", "materials_buffer", "brush_hit", "albedo_attachment", "normal_attachment", "emissive_attachment",
            "metallic_roughness_occlusion_attachment")
 GUARD_OF = {"visbuffer_attachment": "vis", "materials_buffer": "materials", "brush_hit": "hit", "albedo_attachment": "albedo", "normal_attachment": "normal",
@@ -289,25 +289,8 @@ def refusal(r):
     return f, gs, DF.context(f, gs)
 
 
-class _Raw:
-    """A context whose C structure has fields the dataclass derives (width, height) set by hand."""
-
-    def __init__(self, base, **fields):
-        self.base, self.fields = base, fields
-
-    def c(self):
-        c = self.base.c()
-        for k, v in self.fields.items():
-            setattr(c, k, v)
-        return c
-
-
 def _refused(r, context, message, gs, f):
-    from oxylus_amd import lib as L
-
-    with pytest.raises(L.OxcError, match=message):
-        r.decode_terrain(context)
-    torch.cuda.synchronize()
+    raises_refusal(lambda: r.decode_terrain(context), message)
     DF.check_unwritten(gs, f, message)
 
 
@@ -320,7 +303,7 @@ def _cases(base, gs):
     from oxylus_amd.renderer import ImageAttachment
 
     d = base.depth_attachment
-    cases = [(_Raw(base, width=16), "depth_attachment extent differs"), (_Raw(base, height=10), "depth_attachment extent differs"),
+    cases = [(Raw(base, width=16), "depth_attachment extent differs"), (Raw(base, height=10), "depth_attachment extent differs"),
              (rep(base, depth_attachment=ImageAttachment(d.data, 17, 9, 2, [0, 4])), "depth_attachment must be one R32F level"),
              (rep(base, depth_attachment=ImageAttachment(d.data, 17, 9, 1, [4])), "depth_attachment must be one R32F level")]
     cases += [(rep(base, map_resolution=v), "map_resolution: every side") for v in ((0, 20), (24, 0), (16385, 20), (24, 16385))]
@@ -351,7 +334,7 @@ def test_zero_extent(r, refusal):
     f, gs, base = refusal
     d = base.depth_attachment
     for w, h in ((0, 9), (17, 0), (0, 0)):
-        _refused(r, _Raw(base, width=w, height=h), "the extent must not be zero", gs, f)
+        _refused(r, Raw(base, width=w, height=h), "the extent must not be zero", gs, f)
     _refused(r, rep(base, depth_attachment=ImageAttachment(d.data, 0, 9, 1, [0])), "the extent must not be zero", gs, f)
 
 
@@ -361,8 +344,8 @@ def test_the_first_broken_rule_gives_the_message(r, refusal):
 
     f, gs, base = refusal
     d = base.depth_attachment
-    pairs = [(_Raw(rep(base, depth_attachment=ImageAttachment(d.data, 17, 9, 2, [0, 4])), width=0), "the extent must not be zero"),
-             (_Raw(rep(base, depth_attachment=ImageAttachment(d.data, 17, 9, 2, [0, 4])), height=8), "depth_attachment extent differs"),
+    pairs = [(Raw(rep(base, depth_attachment=ImageAttachment(d.data, 17, 9, 2, [0, 4])), width=0), "the extent must not be zero"),
+             (Raw(rep(base, depth_attachment=ImageAttachment(d.data, 17, 9, 2, [0, 4])), height=8), "depth_attachment extent differs"),
              (rep(base, depth_attachment=ImageAttachment(d.data, 17, 9, 2, [0, 4]), map_resolution=(0, 0)), "depth_attachment must be one R32F level"),
              (rep(base, map_resolution=(0, 0), visbuffer_attachment=None), "map_resolution: every side")]
     for a, b in zip(BUFFERS[:-1], BUFFERS[1:]):

@@ -9,6 +9,7 @@ import torch
 import terrain_draw_frames as FR
 import terrain_draw_model as TM
 from oxylus_amd import lib as L
+from refusals import ALIGNED, NULL, SHORT, Raw, raises_refusal
 
 pytestmark = pytest.mark.gpu
 rep = dataclasses.replace
@@ -136,65 +137,24 @@ def test_captured_graph_replayed_twice(r):
 
 
 # ---- limits --------------------------------------------------------------------------------------------------------------------------------------
-class _Raw:
-    """A context whose C structure is changed by hand after the dataclass has filled it."""
-
-    def __init__(self, base, *changes):
-        self.base, self.changes = base, changes
-
-    def c(self):
-        c = self.base.c()
-        for change in self.changes:
-            change(c)
-        return c
-
-
-def _set(field, value):
-    return lambda c: setattr(c, field, value)
-
-
-def _pair(field, a, b):
-    def change(c):
-        getattr(c, field)[0], getattr(c, field)[1] = a, b
-    return change
-
-
-def _patches(a, b):
-    def change(c):
-        c.terrain.patch_count[0], c.terrain.patch_count[1] = a, b
-    return change
-
-
-def _null(field):
-    return lambda c: setattr(c, field, L.Buffer(None, 0))
-
-
-def _shifted(field, by):
-    return lambda c: setattr(c, field, L.Buffer(getattr(c, field).dptr + by, getattr(c, field).bytes - by))
-
-
-def _short(field, need):
-    return lambda c: setattr(c, field, L.Buffer(getattr(c, field).dptr, need - 1))
-
-
-def _depth(width=17, height=9, levels=1):
-    def change(c):
-        c.depth_attachment.width, c.depth_attachment.height, c.depth_attachment.levels = width, height, levels
-    return change
+# changes to the filled C structure, as refusals.Raw takes them
+_null = lambda field: {field: L.Buffer(None, 0)}  # noqa: E731
+_shifted = lambda field, by, short=0: {field: lambda b: L.Buffer(b.dptr + by, (short or b.bytes) - by)}  # noqa: E731
+_short = lambda field, need: {field: lambda b: L.Buffer(b.dptr, need - 1)}  # noqa: E731
+_depth = lambda width=17, height=9, levels=1: {"depth_attachment.width": width, "depth_attachment.height": height, "depth_attachment.levels": levels}  # noqa: E731
 
 
 EXTENT, MAPRES, PATCHES = "the extent must be 1 .. 16384 a side", "map_resolution: every side", "terrain.patch_count: every side"
-NULL, ALIGNED, SHORT = " must not be null", " must be aligned to its texel", " is smaller than its extent"
 BUFFERS = (("heightmap", 1, 24 * 20 * 2), ("visible_patches_buffer", 2, 4), ("draw_cmd_buffer", 2, 16), ("visdepth_buffer", 4, 17 * 9 * 8))
-# (what is changed, the message, the fields it touches), in the order of the header's limits paragraph
-CASES = [(_set("width", 0), EXTENT, "width"), (_set("width", 16385), EXTENT, "width"), (_set("height", 0), EXTENT, "height"), (_set("height", 16385), EXTENT, "height"),
-         (_pair("map_resolution", 0, 20), MAPRES, "map_resolution"), (_pair("map_resolution", 24, 16385), MAPRES, "map_resolution"),
-         (_patches(0, 2), PATCHES, "patch_count"), (_patches(3, 4097), PATCHES, "patch_count")]
+# (the fields of the filled C structure that are changed, the message, the field they touch), in the order of the header's limits paragraph
+CASES = [(dict(width=0), EXTENT, "width"), (dict(width=16385), EXTENT, "width"), (dict(height=0), EXTENT, "height"), (dict(height=16385), EXTENT, "height"),
+         (dict(map_resolution=(0, 20)), MAPRES, "map_resolution"), (dict(map_resolution=(24, 16385)), MAPRES, "map_resolution"),
+         ({"terrain.patch_count": (0, 2)}, PATCHES, "patch_count"), ({"terrain.patch_count": (3, 4097)}, PATCHES, "patch_count")]
 for _field, _by, _need in BUFFERS:
     CASES += [(_null(_field), _field + NULL, _field), (_shifted(_field, _by), _field + ALIGNED, _field), (_short(_field, _need), _field + SHORT, _field)]
 CASES += [(_depth(width=16), "depth_attachment must be one R32F level", "depth_attachment"), (_depth(height=10), "depth_attachment must be one R32F level", "depth_attachment"),
           (_depth(levels=2), "depth_attachment must be one R32F level", "depth_attachment"),
-          (_short("visbuffer_attachment", 17 * 9 * 4), "visbuffer_attachment smaller than width \\* height u32", "visbuffer_attachment")]
+          (_short("visbuffer_attachment", 17 * 9 * 4), "visbuffer_attachment smaller than width * height u32", "visbuffer_attachment")]
 
 
 @pytest.fixture(scope="module")
@@ -205,16 +165,14 @@ def refusal(r):
 
 
 def _refused(r, context, message, gs, f):
-    with pytest.raises(L.OxcError, match=message):
-        r.draw_terrain_for_visbuffer(context)
-    torch.cuda.synchronize()
+    raises_refusal(lambda: r.draw_terrain_for_visbuffer(context), message)
     FR.check_unwritten(gs, f, message)
 
 
 def test_every_limit_on_its_own(r, refusal):
     f, gs, base = refusal
     for change, message, _ in CASES:
-        _refused(r, _Raw(base, change), message, gs, f)
+        _refused(r, Raw(base, **change), message, gs, f)
     FR.run(r, f, "the frame still draws")
 
 
@@ -225,12 +183,12 @@ def test_the_first_broken_rule_gives_the_message(r, refusal):
     for i, (first, message, field) in enumerate(CASES):
         for later, _, other in CASES[i + 1:]:
             if other != field:
-                _refused(r, _Raw(base, later, first), message, gs, f)
+                _refused(r, Raw(base, **later, **first), message, gs, f)
                 pairs += 1
     assert pairs > 200
     # within one buffer: null before aligned before small
     for field, by, need in BUFFERS:
-        _refused(r, _Raw(base, _shifted(field, by), lambda c, field=field, need=need: setattr(c, field, L.Buffer(getattr(c, field).dptr, need - 1 - by))), field + ALIGNED, gs, f)
+        _refused(r, Raw(base, **_shifted(field, by, short=need - 1)), field + ALIGNED, gs, f)
     FR.run(r, f, "the frame still draws")
 
 

@@ -8,6 +8,7 @@ import torch
 
 import terrain_maps_frames as TF
 import terrain_maps_model as TM
+from refusals import ALIGNED, NULL, SHORT, raises_refusal
 
 pytestmark = pytest.mark.gpu
 
@@ -213,18 +214,11 @@ def refusal(r):
 
 
 def _refused(r, context, message, gs, images):
-    from oxylus_amd import lib as L
-
-    with pytest.raises(L.OxcError, match=message):
-        r.generate_terrain_maps(context)
-    torch.cuda.synchronize()
+    raises_refusal(lambda: r.generate_terrain_maps(context), message)
     got = TF.got_of(gs, images)
     for name, g in gs.items():
         g.check("refused")
         assert (got[name].view(np.uint8) == images[name].view(np.uint8)).all(), f"{name} was written"
-
-
-NULL, ALIGNED, SHORT = " must not be null", " must be aligned to its texel", " is smaller than its extent"
 
 
 def _cases(base, gs):
